@@ -9,6 +9,8 @@ N > 1: one process per GPU, each rank its own seeds (weak scaling), no data-path
 barrier and the max-over-ranks time.  `--job-mb M` instead times ONE job of M Mb (M / 10 distinct batches) sharded over the ranks
 (configs[3] / configs[4]: strong scaling; longest-processing-time assignment by the batches' read bases, optional RCCL queue rebalance).
 Other shapes: --shape ont (configs[2]), --shape sv (configs[4]: 60x noisy reads, 1-10 kb INS/DEL).
+A plain run sets up, warms up, times the steps and prints the line; everything measured or checked beside `value` (depth profile, PCIe-inclusive
+figures and digest, roofline, CPU baseline, f3) runs only with --full.  --dump-outputs DIR writes the results of the last timed step as .npy files.
 """
 import argparse
 import json
@@ -94,6 +96,39 @@ def _k4_reference(pairs, n_threads, budget_s=6.0):
     return sum(done) / el, el, sum(done)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_REGIONS = 128
+
+
+def dump_outputs(bt, out_dir, seed=0):
+    """--dump-outputs: the results a caller of the timed path receives for batch `bt` (lcd_batch_region_result after a download), for up to DUMP_MAX_REGIONS of
+    its regions taken in a fixed seeded order while the files stay under DUMP_MAX_BYTES.  Alignment rows are base codes (5 = gap) in float32, everything
+    else float64; aln_rows = (region, cluster, row, aln_len, target_beg, target_end, query_beg, query_end) per row that is present."""
+    import numpy as np
+    bt.download()
+    regions, n_cons, clu_n, clu_ids, rows, tgt, qry = [], [], [], [], [], [], []
+    n_bytes = 0
+    for i in np.random.default_rng(seed).permutation(len(bt.n_reads))[:DUMP_MAX_REGIONS]:
+        res = bt.result(int(i))
+        strs = [(c, j, s) for c in range(res["n_cons"]) for j, s in enumerate(res["aln_strs"][c]) if s is not None]
+        ids = [x for c in range(res["n_cons"]) for x in res["clu_read_ids"][c]]
+        add = 8 * (4 + len(ids) + 8 * len(strs)) + 4 * 2 * sum(s["aln_len"] for _, _, s in strs)
+        if n_bytes + add > DUMP_MAX_BYTES:
+            break
+        n_bytes += add
+        regions.append(int(i)); n_cons.append(res["n_cons"]); clu_n.append(res["clu_n_seqs"]); clu_ids += ids
+        for c, j, s in strs:
+            rows.append((int(i), c, j, s["aln_len"], s["target_beg"], s["target_end"], s["query_beg"], s["query_end"]))
+            tgt.append(s["target"]); qry.append(s["query"])
+    os.makedirs(out_dir, exist_ok=True)
+    out = {"region": np.array(regions, np.float64), "n_cons": np.array(n_cons, np.float64), "clu_n_seqs": np.array(clu_n, np.float64).reshape(-1, 2),
+           "clu_read_ids": np.array(clu_ids, np.float64), "aln_rows": np.array(rows, np.float64).reshape(-1, 8),
+           "aln_target": np.concatenate(tgt).astype(np.float32) if tgt else np.zeros(0, np.float32),
+           "aln_query": np.concatenate(qry).astype(np.float32) if qry else np.zeros(0, np.float32)}
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def job_block(n_chunks, rank, world):
     """--job-mb: the contiguous block of chunks (genome order, src/call_var_main.c:599-621) rank `rank` of `world` generates: [lo, hi)"""
     return rank * n_chunks // world, (rank + 1) * n_chunks // world
@@ -147,6 +182,8 @@ def _inproc(args, align, lib, timed_regs, warm_regs, n_regions, shape, torch):
         busy, nsub = disp.busy()
         reps.append(dict(elapsed=el, allocs=int(lib.lcd_alloc_events() - a0), busy=[round(float(x), 2) for x in busy], nsub=[int(x) for x in nsub]))
     med = sorted(reps, key=lambda r: r["elapsed"])[(n_rep - 1) // 2]
+    if args.dump_outputs:
+        dump_outputs(slots[-1][1], args.dump_outputs)
     sts = [bt.stats() for _, bt in slots]
     tot_regions = float(sum(x["n_regions"] for x in sts)); tot_bases = float(sum(x["poa_aligned_bases"] for x in sts))
     assert all(int(dev_of[i]) == slots[i][0] for i in range(len(slots)))   # a batch bound to a device stays there
@@ -204,13 +241,17 @@ def main():
                     "MEDIAN repeat, all of them are listed (0 = 5 when the region is a single submission -- the driver's flags: 0.3 s -- else 1)")
     ap.add_argument("--inproc", type=int, default=0, help="1: ONE process drives all --gpus devices through lcd_dispatch_run (submitter threads over one cost-ordered queue: the "
                     "drop-in's model -- kt_for workers of one longcallD process, src/call_var_main.c:773) instead of one process per GPU; not under torchrun")
-    ap.add_argument("--depth-profile", type=int, default=-1, help="also time lone submissions of 1 / 4 / 16 batches (what a caller with fewer chunks in flight gets); "
+    ap.add_argument("--full", action="store_true", help="also run every figure and check beside `value`: depth profile, PCIe-inclusive figures and digest, "
+                    "roofline, CPU baseline, f3 (the options below switch them off one by one); without it the run does only what `value` needs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the results of the last timed step (every alignment row of a "
+                    "seeded sample of its regions) to DIR/<name>.npy in float32 / float64")
+    ap.add_argument("--depth-profile", type=int, default=-1, help="(--full) also time lone submissions of 1 / 4 / 16 batches (what a caller with fewer chunks in flight gets); "
                     "-1 = on for the single-GPU HiFi run")
     ap.add_argument("--shape", default="hifi", choices=["hifi", "ont", "ont60", "sv"])
-    ap.add_argument("--cpu-sample", type=int, default=200, help="cap on regions per CPU worker of the cpu_baseline leg, which is bounded to ~12 s (rank 0, N=1 only; 0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=200, help="(--full) cap on regions per CPU worker of the cpu_baseline leg, which is bounded to ~12 s (rank 0, N=1 only; 0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="CPU worker processes of the cpu_baseline leg (0 = all host cores)")
     ap.add_argument("--seed", type=int, default=20250928)
-    ap.add_argument("--f3", type=int, default=-1, help="also measure the step in FRONT of the path on the device (SURVEY 8f f3; never part of `value`): BGZF inflate of 128 MB of BAM-like "
+    ap.add_argument("--f3", type=int, default=-1, help="(--full) also measure the step in FRONT of the path on the device (SURVEY 8f f3; never part of `value`): BGZF inflate of 128 MB of BAM-like "
                                                        "data against host zlib, and one 500 kb chunk of an indexed BAM -> device-resident chunk against the host loader; -1 = on for the "
                                                        "single-GPU HiFi line, 0 = off")
     ap.add_argument("--lanes", type=int, default=0,
@@ -223,11 +264,13 @@ def main():
     ap.add_argument("--coalesce", type=int, default=0,
                     help="steps (batches) submitted together through lcd_batch_run_many: one set of launches per stage over the chains of "
                          "all of them, so that the GPU's workgroup dispatcher -- not HIP streams -- packs several chunks' chains onto the CUs")
-    ap.add_argument("--overlap", type=int, default=-1, help="PCIe-inclusive pipeline (never `value`): BENCH_OVL_LANES (3) submissions of the timed region's size take turns on the GPU while a pool of "
+    ap.add_argument("--overlap", type=int, default=-1, help="(--full) PCIe-inclusive pipeline (never `value`): BENCH_OVL_LANES (3) submissions of the timed region's size take turns on the GPU while a pool of "
                     "host threads downloads and materialises the previous one's results and uploads the next one's inputs; -1 = on for the single-GPU HiFi line, 0 = off")
-    ap.add_argument("--e2e", type=int, default=0, help="also time the PCIe-inclusive path with E lanes (host threads) each doing upload -> run -> download -> "
+    ap.add_argument("--e2e", type=int, default=0, help="(--full) also time the PCIe-inclusive path with E lanes (host threads) each doing upload -> run -> download -> "
                     "materialisation of every result for its own batches, so that one lane's copies overlap another's kernels; reported under pcie_inclusive")
     args = ap.parse_args()
+    if not args.full and (args.depth_profile > 0 or args.f3 > 0 or args.overlap > 0 or args.e2e > 0):
+        ap.error("--depth-profile / --f3 / --overlap / --e2e measure beside `value`: add --full")
     if needs_self_launch(args, os.environ):
         # `python bench.py --gpus N` by itself: become N ranks (the first multi-GPU run must not die at init_process_group for want of a launcher)
         cmd = launcher_command(args.gpus, [a for a in sys.argv[1:]])
@@ -384,10 +427,21 @@ def main():
     # per batch and submits them `coalesce` at a time, each exactly once
     n_slots = max(args.steps, 1) if job_mode else n_lanes * n_co
 
+    from longcalld_amd import rebalance as rb_
+    import ctypes as C_
+    packed = {}   # id(region list) -> its packed buffer: a distinct batch is packed once, however many slots it fills
+
     def load_slot(bt, regs):
+        # ONE lcd_batch_add_packed call (the same batch as lcd_batch_add_region per region: tests/test_gpu_rebalance.py); adding the 1 250 regions one by one
+        # from Python costs ~0.15 s per slot, which was most of a plain run's set-up
+        if id(regs) not in packed:
+            packed[id(regs)] = rb_.pack_regions(regs)
+        buf = packed[id(regs)]
         bt.clear()
-        for r in regs:
-            bt.add_region(r)
+        n_ = rb_._clib().lcd_batch_add_packed(bt.h, buf.ctypes.data_as(C_.c_void_p), len(buf))
+        if n_ != len(regs):
+            raise RuntimeError(f"lcd_batch_add_packed: {n_} of {len(regs)} regions ({rb_._clib().lcd_rebalance_last_error()})")
+        bt.n_reads = [len(r["seqs"]) for r in regs]
         t0_ = time.perf_counter()
         bt.upload()
         return time.perf_counter() - t0_
@@ -437,6 +491,8 @@ def main():
             t.join()
         if lane_errors:
             raise lane_errors[0]
+        a, k = subs[-1]   # the last step: the last batch of the last submission, dealt to lane (len(subs) - 1) % n_lanes
+        return groups[(len(subs) - 1) % n_lanes][a + k - 1]
 
     # ---- warm-up on OTHER seeds: every slot's buffers grow to size, the capacity hints settle (the noisy-read shapes need three submissions:
     # the hints rise one level per submission that overflowed) -- none of it on the data that is timed ----
@@ -449,6 +505,8 @@ def main():
     for q, bt in enumerate(batches):
         if args.steps > 0:
             t_up = load_slot(bt, timed_regs[q % len(timed_regs)])
+    for regs_ in warm_regs:
+        packed.pop(id(regs_), None)
     # the timed region = exactly --steps steps between two (barrier + synchronize); a region that is ONE submission lasts a third of a second, so it is repeated
     # and the MEDIAN repeat is the one reported (value, stage times, statistics all come from that repeat; every repeat's time is listed)
     n_rep = args.repeats if args.repeats > 0 else (5 if (not job_mode and args.steps <= n_co * n_lanes) else 1)
@@ -462,7 +520,7 @@ def main():
         allocs0 = lib.lcd_alloc_events()
         t0 = time.perf_counter()
         if args.steps > 0:
-            run_steps(args.steps, True)
+            last_bt = run_steps(args.steps, True)
         barrier()
         el = time.perf_counter() - t0
         rank_el = el
@@ -492,6 +550,8 @@ def main():
     order = sorted(clean, key=lambda i: reps[i]["elapsed"])
     med = reps[order[(len(order) - 1) // 2]]
     elapsed, rank_elapsed, allocs_timed = med["elapsed"], med["rank_elapsed"], med["allocs"]
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(last_bt, args.dump_outputs)
     acc.update(med["acc"])
     dev_gb = lib.lcd_device_bytes(local_rank) / 1e9
     # host threads of this rank beside the submitting thread: the library divides the CPUs the process may use (affinity mask, cgroup quota) by the
@@ -515,7 +575,7 @@ def main():
     # lone submissions of 1 / 4 / 16 batches: what a caller with fewer chunks in flight than the timed region's gets (kt_for offers n_threads chunks per pass,
     # src/collect_var.c:2952-2969); never `value`
     depth = None
-    if (args.depth_profile > 0 or (args.depth_profile < 0 and args.shape == "hifi" and not job_mode)) and world == 1 and args.steps > 0 and not args.vars:
+    if args.full and (args.depth_profile > 0 or (args.depth_profile < 0 and args.shape == "hifi" and not job_mode)) and world == 1 and args.steps > 0 and not args.vars:
         depth = {}
         for dsz, dn in ((1, 5), (4, 3), (16, 3)):
             if dsz > len(groups[0]):
@@ -533,7 +593,7 @@ def main():
     # PCIe-inclusive with overlap (never `value`): E lanes, each upload -> run_many -> download -> digest (lcd_batch_digest materialises every
     # malloc()'d aln_str_t / variant record of the batch exactly as a caller would receive them) on its own group of slots
     e2e = None
-    if args.e2e > 0 and args.steps > 0 and world == 1:
+    if args.full and args.e2e > 0 and args.steps > 0 and world == 1:
         E = max(1, min(args.e2e, n_slots))
         per_lane = max(1, min(n_co, n_slots // E))
         egroups = [batches[i * per_lane:(i + 1) * per_lane] for i in range(E)]
@@ -579,7 +639,7 @@ def main():
     # time-slice the hardware queues), then a pool of host threads does lcd_batch_download + lcd_batch_region_results_arena of every batch (and uploads the inputs
     # again, as a new pass would) WHILE the other lane's kernels run.
     overlap = None
-    if (args.overlap > 0 or (args.overlap < 0 and args.shape == "hifi")) and world == 1 and not job_mode and args.steps > 0 and args.vars != 2 and st is not None:
+    if args.full and (args.overlap > 0 or (args.overlap < 0 and args.shape == "hifi")) and world == 1 and not job_mode and args.steps > 0 and args.vars != 2 and st is not None:
         from concurrent.futures import ThreadPoolExecutor
         n_sub = min(n_co, len(groups[0]))
         n_ol = max(2, int(os.environ.get("BENCH_OVL_LANES", "3")))   # (three: a lane's cycle is run + results + upload = ~300 ms of which 200 on the GPU -- with two lanes the GPU waits for results a fifth of the time)
@@ -673,7 +733,7 @@ def main():
 
     # PCIe-inclusive figure for DESIGN.md (never `value`)
     digest, t_dl, t_ar, arena_bytes = 0, 0.0, 0.0, 0
-    if st is not None:
+    if args.full and st is not None:
         t_dl0 = time.perf_counter()
         batches[0].download()
         batches[0].materialize()          # every result as a caller receives it (malloc()'d rows); the digest below also hashes every byte
@@ -688,53 +748,55 @@ def main():
         steps = max(args.steps, 1)
         ms_step = elapsed / steps * 1e3
         value = tot_regions / elapsed
-        # roofline of the dominant kernel (POA chains): algorithmic bytes (SURVEY 8d B_poa) per launch / mean launch time
-        alg_bytes = acc["alg"] / max(poa_launches, 1)     # per launch set: the chains of `coalesce` batches
-        mean_launch_s = poa_kernel_ms / max(poa_launches, 1) * 1e-3
-        achieved = alg_bytes / mean_launch_s / 1e9 if mean_launch_s > 0 else 0.0
-        # HBM bytes of the same launch from the PMC counters: they need rocprofv3 (separate --pmc passes, tools/profile_round.sh), so the
-        # figure is the committed measurement of this exact workload (profiles/<tag>_traffic.json), or null for any other workload
-        traffic, traffic_src = None, None
-        import glob
-        import re
-        if args.ref_mb == 10 and shape["name"] in ("hifi", "ont", "sv") and world == 1 and not job_mode:
-            # (the driver's workload: profiles/rNN_vM_traffic.json; the two noisy shapes' builder commands: profiles/rNN_vM_<shape>_traffic.json, tools/profile_shapes.sh)
-            pat = r"^r\d+_v\d+_traffic\.json$" if shape["name"] == "hifi" else r"^r\d+_v\d+_" + shape["name"] + r"_traffic\.json$"
-            cand = sorted((f for f in glob.glob(os.path.join(ROOT, "profiles", "*_traffic.json")) if re.match(pat, os.path.basename(f))),
-                          key=lambda f: [int(x) for x in re.findall(r"\d+", os.path.basename(f))])   # r01_v9 < r01_v10 < r02_v1
-            if cand:
-                tj = json.load(open(cand[-1]))
-                traffic, traffic_src = float(tj["hbm_bytes_per_step"]) * n_co, tj["source"] + f" x {n_co} coalesced steps"
-        # secondary roofline: integer VALU issue.  Wavefront instructions of the POA kernels per step from the committed SQ counter
-        # pass (same rule as `traffic`), x 64 lanes, over the live launch time; peak = 256 CUs x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 Tops/s
-        valu = None
-        if traffic is not None:
-            cand2 = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_sq.json")), key=lambda f: [int(x) for x in re.findall(r"\d+", os.path.basename(f))])
-            if cand2 and mean_launch_s > 0 and shape["name"] == "hifi":
-                sj = json.load(open(cand2[-1]))
-                ops = float(sj["valu_wave_insts_per_step"]) * 64 * n_co
-                valu = {"achieved": round(ops / mean_launch_s / 1e12, 3), "peak": 78.6, "unit": "Tops/s (int32 lane-ops)", "frac": round(ops / mean_launch_s / 78.6e12, 4),
-                        "source": sj["source"]}
-                if n_lanes > 1 and world == 1:   # chip-wide rate over the wall clock of the timed region (see roofline.achieved_wall)
-                    ops_all = float(sj["valu_wave_insts_per_step"]) * 64 * args.steps
-                    valu["achieved_wall"] = round(ops_all / elapsed / 1e12, 3); valu["frac_wall"] = round(ops_all / elapsed / 78.6e12, 4)
-        roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
-                    "traffic": traffic, "traffic_source": traffic_src, "kernel": "lcd_poa_chain_kernel", "ms_per_launch": round(mean_launch_s * 1e3, 4),
-                    "alg_bytes_per_launch": alg_bytes, "cells_per_launch": int(acc["cells"] / max(poa_launches, 1)),
-                    "gcups": round(acc["cells"] / max(poa_launches, 1) / mean_launch_s / 1e9, 3) if mean_launch_s > 0 else 0.0,
-                    # cells / bytes above are those of the REFERENCE's algorithm (K1 adaptive band, K2 full rows).  K2 chains of clean reads run
-                    # over a certified band (same alignments): what the kernels actually computed / streamed is the smaller figure below
-                    "cells_computed_per_launch": int(acc["cells_computed"] / max(poa_launches, 1)),
-                    "gcups_computed": round(acc["cells_computed"] / max(poa_launches, 1) / mean_launch_s / 1e9, 3) if mean_launch_s > 0 else 0.0,
-                    "achieved_computed": round((acc["alg"] - acc["cells"] + acc["cells_computed"]) / max(poa_launches, 1) / mean_launch_s / 1e9, 3) if mean_launch_s > 0 else 0.0,
-                    "valu": valu}
-        if n_lanes > 1 and world == 1:
-            # `achieved` prices ONE lane's launch set against its own duration while the other lanes' chains share the CUs; the chip-wide rate is
-            # all algorithmic bytes of the timed region over its wall clock (conservative: the non-POA stages are inside that time)
-            roofline["concurrent_launch_sets"] = n_lanes
-            roofline["achieved_wall"] = round(acc["alg"] / elapsed / 1e9, 3); roofline["frac_wall"] = round(acc["alg"] / elapsed / 1e9 / HBM_PEAK_GBS, 6)
+        roofline = None
+        if args.full:
+            # roofline of the dominant kernel (POA chains): algorithmic bytes (SURVEY 8d B_poa) per launch / mean launch time
+            alg_bytes = acc["alg"] / max(poa_launches, 1)     # per launch set: the chains of `coalesce` batches
+            mean_launch_s = poa_kernel_ms / max(poa_launches, 1) * 1e-3
+            achieved = alg_bytes / mean_launch_s / 1e9 if mean_launch_s > 0 else 0.0
+            # HBM bytes of the same launch from the PMC counters: they need rocprofv3 (separate --pmc passes, tools/profile_round.sh), so the
+            # figure is the committed measurement of this exact workload (profiles/<tag>_traffic.json), or null for any other workload
+            traffic, traffic_src = None, None
+            import glob
+            import re
+            if args.ref_mb == 10 and shape["name"] in ("hifi", "ont", "sv") and world == 1 and not job_mode:
+                # (the driver's workload: profiles/rNN_vM_traffic.json; the two noisy shapes' builder commands: profiles/rNN_vM_<shape>_traffic.json, tools/profile_shapes.sh)
+                pat = r"^r\d+_v\d+_traffic\.json$" if shape["name"] == "hifi" else r"^r\d+_v\d+_" + shape["name"] + r"_traffic\.json$"
+                cand = sorted((f for f in glob.glob(os.path.join(ROOT, "profiles", "*_traffic.json")) if re.match(pat, os.path.basename(f))),
+                              key=lambda f: [int(x) for x in re.findall(r"\d+", os.path.basename(f))])   # r01_v9 < r01_v10 < r02_v1
+                if cand:
+                    tj = json.load(open(cand[-1]))
+                    traffic, traffic_src = float(tj["hbm_bytes_per_step"]) * n_co, tj["source"] + f" x {n_co} coalesced steps"
+            # secondary roofline: integer VALU issue.  Wavefront instructions of the POA kernels per step from the committed SQ counter
+            # pass (same rule as `traffic`), x 64 lanes, over the live launch time; peak = 256 CUs x 4 SIMD x 32 lanes x 2.4 GHz = 78.6 Tops/s
+            valu = None
+            if traffic is not None:
+                cand2 = sorted(glob.glob(os.path.join(ROOT, "profiles", "*_sq.json")), key=lambda f: [int(x) for x in re.findall(r"\d+", os.path.basename(f))])
+                if cand2 and mean_launch_s > 0 and shape["name"] == "hifi":
+                    sj = json.load(open(cand2[-1]))
+                    ops = float(sj["valu_wave_insts_per_step"]) * 64 * n_co
+                    valu = {"achieved": round(ops / mean_launch_s / 1e12, 3), "peak": 78.6, "unit": "Tops/s (int32 lane-ops)", "frac": round(ops / mean_launch_s / 78.6e12, 4),
+                            "source": sj["source"]}
+                    if n_lanes > 1 and world == 1:   # chip-wide rate over the wall clock of the timed region (see roofline.achieved_wall)
+                        ops_all = float(sj["valu_wave_insts_per_step"]) * 64 * args.steps
+                        valu["achieved_wall"] = round(ops_all / elapsed / 1e12, 3); valu["frac_wall"] = round(ops_all / elapsed / 78.6e12, 4)
+            roofline = {"bound": "hbm", "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
+                        "traffic": traffic, "traffic_source": traffic_src, "kernel": "lcd_poa_chain_kernel", "ms_per_launch": round(mean_launch_s * 1e3, 4),
+                        "alg_bytes_per_launch": alg_bytes, "cells_per_launch": int(acc["cells"] / max(poa_launches, 1)),
+                        "gcups": round(acc["cells"] / max(poa_launches, 1) / mean_launch_s / 1e9, 3) if mean_launch_s > 0 else 0.0,
+                        # cells / bytes above are those of the REFERENCE's algorithm (K1 adaptive band, K2 full rows).  K2 chains of clean reads run
+                        # over a certified band (same alignments): what the kernels actually computed / streamed is the smaller figure below
+                        "cells_computed_per_launch": int(acc["cells_computed"] / max(poa_launches, 1)),
+                        "gcups_computed": round(acc["cells_computed"] / max(poa_launches, 1) / mean_launch_s / 1e9, 3) if mean_launch_s > 0 else 0.0,
+                        "achieved_computed": round((acc["alg"] - acc["cells"] + acc["cells_computed"]) / max(poa_launches, 1) / mean_launch_s / 1e9, 3) if mean_launch_s > 0 else 0.0,
+                        "valu": valu}
+            if n_lanes > 1 and world == 1:
+                # `achieved` prices ONE lane's launch set against its own duration while the other lanes' chains share the CUs; the chip-wide rate is
+                # all algorithmic bytes of the timed region over its wall clock (conservative: the non-POA stages are inside that time)
+                roofline["concurrent_launch_sets"] = n_lanes
+                roofline["achieved_wall"] = round(acc["alg"] / elapsed / 1e9, 3); roofline["frac_wall"] = round(acc["alg"] / elapsed / 1e9 / HBM_PEAK_GBS, 6)
         cpu = None
-        if world == 1 and args.cpu_sample > 0 and st is not None:
+        if args.full and world == 1 and args.cpu_sample > 0 and st is not None:
             # the reference runs this path on kt_for worker threads (src/call_var_main.c:773): time the CPU port the same way, one
             # process per host core (spawned: no fork after HIP start-up), every worker on its own slice of the same workload shape
             n_avail = _host_cores()
@@ -792,7 +854,7 @@ def main():
             "repeats": {"n": n_rep, "seconds": [round(r_["elapsed"], 4) for r_ in reps], "reported": reported, "allocations_per_repeat": [r_.get("allocs_any_rank", r_["allocs"]) for r_ in reps]},
             "depth": depth,
             "device_memory": {"library_buffers_gb": round(dev_gb, 2), "allocations_inside_timed_region": int(allocs_timed)},
-            "pcie_inclusive": {"upload_s": round(t_up, 4), "download_and_materialize_s": round(t_dl, 4),
+            "pcie_inclusive": None if not args.full else {"upload_s": round(t_up, 4), "download_and_materialize_s": round(t_dl, 4),
                                # the pipelined rate when it was measured (two submissions in flight, see `pipeline`); else the serial sum of one batch's phases
                                "regions_per_sec": overlap["regions_per_sec"] if overlap else round(tot_regions / max(world, 1) / steps / (t_up + ms_step / 1e3 + t_dl), 2),
                                "regions_per_sec_one_batch_serial": round(tot_regions / max(world, 1) / steps / (t_up + ms_step / 1e3 + t_dl), 2),
@@ -801,11 +863,11 @@ def main():
                                "regions_per_sec_arena": round(tot_regions / max(world, 1) / steps / (t_up + ms_step / 1e3 + t_ar), 2) if t_ar > 0 else None,
                                "what": "one batch: upload + its share of the timed run + download + every result on the host -- one malloc() per row as the reference's contract "
                                        "has it (lcd_batch_region_result), or one block per batch (lcd_batch_region_results_arena)", "overlapped": e2e},
-            "digest": f"{digest:016x}",
+            "digest": f"{digest:016x}" if args.full else None,
             "roofline": roofline,
             "cpu_baseline": cpu,
         }
-        if (args.f3 > 0 or (args.f3 < 0 and world == 1 and not job_mode and args.shape == "hifi" and args.cpu_sample > 0)):
+        if args.full and (args.f3 > 0 or (args.f3 < 0 and world == 1 and not job_mode and args.shape == "hifi" and args.cpu_sample > 0)):
             try:   # (tools/: importable measurements; a failure here never costs the line)
                 sys.path.insert(0, os.path.join(ROOT, "tools"))
                 import bench_f3

@@ -1,12 +1,13 @@
 #!/bin/bash
 # on the GPU box: tools/ab_run.sh <out-prefix> <variant> [<variant> ...]   -- runs the driver's bench line with exp/lib_<variant>.so in place of the library
 # (extra bench flags: AB_FLAGS; the library on disk is restored afterwards)
+OUT=${OUT:-out}   # where the lines / logs go
 out=$1; shift
 cp longcalld_amd/liblcd_hotpath.so /tmp/lib_orig.so
 for v in "$@"; do
   cp exp/lib_$v.so longcalld_amd/liblcd_hotpath.so
-  python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-sample 0 --f3 0 --overlap 0 ${AB_FLAGS} > gpurun_out/${out}_$v.json 2> gpurun_out/${out}_$v.err
-  python - "$v" gpurun_out/${out}_$v.json <<'PY'
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-sample 0 --f3 0 --overlap 0 ${AB_FLAGS} > $OUT/${out}_$v.json 2> $OUT/${out}_$v.err
+  python - "$v" $OUT/${out}_$v.json <<'PY'
 import json,sys
 try:
     d=json.loads([l for l in open(sys.argv[2]) if l.startswith('{')][-1])
