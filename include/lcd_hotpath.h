@@ -565,6 +565,48 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
                   const uint8_t *pool, uint64_t pool_len, int *status, int *n_cons, int *cons_len, int *msa_len, int *clu_n,
                   uint8_t *cons, int cons_stride, uint8_t *msa, int msa_stride, int max_reads, int *clu_ids);
 
+/* ---- the first round of collect_var_main on a DEVICE-RESIDENT chunk (src/collect_var.c:2897-2980, steps 1.2 - 3.1; germline) ----
+ * == collect_all_cand_var_sites (:1209) + collect_cand_vars (:238, update_cand_vars_from_digar src/bam_utils.c:287) + classify_cand_vars (:902: classify_var_cate,
+ * the extra noisy regions of low-complexity / overlapping variants, cr_merge2, post_process_noisy_regs, the compaction :1007-1023) + collect_read_var_profile (:1389,
+ * update_read_vs_all_var_profile_from_digar src/bam_utils.c:446) on the digars, bases and qualities the chunk keeps in HBM (clean_vars_kernel.hip).  No digar crosses
+ * PCIe (lcd_copy_counters()[0] is unchanged); a chunk made by lcd_chunk_create keeps its qualities on the host until the first call uploads them once
+ * (qual_upload_bytes).  Host code, as in the reference: the interval logic (var_pos_cr counts, cr_add_var_cr, cr_merge2, post_process_noisy_regs, cr_is_contained)
+ * and the ONT strand-bias test (var_is_strand_bias :270, fisher_exact_test src/math_utils.c:119, double precision).
+ * Inputs: ordered_read_ids (chunk->ordered_read_ids; a read with status -1 is skipped); is_rev[r] = bam_is_rev (NULL: all forward; only the strand counts read it);
+ * ref_seq[0] = position ref_beg (1-based), ref_end inclusive (chunk->ref_seq; codes 0-4 or letters); [reg_beg, reg_end] = chunk->reg_beg / reg_end;
+ * pre_regs = lcd_pre_process_noisy_regs' output (chunk->chunk_noisy_regs, index order); low_comp = chunk->low_comp_cr as (start, end) pairs (lcd_sdust).
+ * out_somatic != 0 returns -2 (somatic mode is out of scope).  Every array of *out is malloc()'d (lcd_clean_vars_free).  Returns 0 or < 0 (lcd_last_error()). */
+typedef struct lcd_clean_opt_t {
+    int min_dp, min_alt_dp, min_bq, min_sv_len, noisy_reg_max_xgaps, noisy_reg_flank_len, noisy_reg_merge_dis, is_ont, out_somatic;
+    double min_af, max_af; float strand_bias_pval;
+} lcd_clean_opt_t;
+void lcd_clean_opt_default(lcd_clean_opt_t *o, int is_ont);   /* src/call_var_main.c:113-224: 5, 2, 10, 30, 5, 10, 500, is_ont, 0, 0.2, 0.8, 0.01 */
+typedef struct lcd_clean_vars_t {
+    int n_vars;                                      /* candidate variants after the compaction of classify_cand_vars, in chunk order */
+    int64_t *pos; int *var_type, *ref_len, *alt_len, *cate;  /* cand_var_t fields; cate = chunk->var_i_to_cate */
+    int *total_cov, *low_qual_cov, *alle_covs /* 2 per variant: ref, alt */, *strand_alle_covs /* 4 per variant: [fwd ref, fwd alt, rev ref, rev alt] */;
+    uint64_t *alt_off; uint8_t *alt_pool;            /* n_vars + 1 offsets; alt_seq codes 0-4 of X / INS variants (none for DEL) */
+    int *is_homopolymer_indel;                       /* 0 for every clean-region variant (set by the noisy-region pass only, src/collect_var.c:1754) */
+    int n_regs; lcd_noisy_iv_t *regs;                /* chunk->chunk_noisy_regs after cr_merge2 + post_process_noisy_regs, index order */
+    int n_reads; int *start_var_idx, *end_var_idx;   /* read_var_profile_t per chunk read (-1 / -2: none) */
+    uint64_t *allele_off; int *alleles, *alt_qi;     /* n_reads + 1 offsets; end - start + 1 entries per read with a profile */
+    int n_cr; int *cr_read;                          /* chunk->read_var_cr labels in cr_index order */
+    uint64_t qual_upload_bytes;                      /* quality bytes this call uploaded (a host-array chunk's first call; else 0) */
+} lcd_clean_vars_t;
+int lcd_chunk_clean_vars(const lcd_chunk_t *c, const lcd_clean_opt_t *opt, const int *ordered_read_ids, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
+                         int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre_regs, const int64_t *low_comp, int n_low,
+                         lcd_clean_vars_t *out);
+/* the same for n chunks of a pipeline step, each argument an array of n (is_rev / low_comp entries may be NULL): the chunks run concurrently, each on a stream of
+ * its own (one host thread per chunk, at most LCD_HOST_TEAM at a time).  Results == n single calls.  Returns 0 or the first failure. */
+int lcd_chunk_clean_vars_batch(int n, const lcd_chunk_t *const *chunks, const lcd_clean_opt_t *opt, const int *const *ordered_read_ids, const uint8_t *const *is_rev,
+                               const uint8_t *const *ref_seq, const int64_t *ref_beg, const int64_t *ref_end, const int64_t *reg_beg, const int64_t *reg_end,
+                               const lcd_noisy_iv_t *const *pre_regs, const int *n_pre_regs, const int64_t *const *low_comp, const int *n_low, lcd_clean_vars_t *outs);
+void lcd_clean_vars_free(lcd_clean_vars_t *v);
+/* an lcd_hap_problem_t view over v for K5 (lcd_assign_hap_germline): pointers into v and the caller's arrays; alle_off (n_vars + 1) and allele_off (n_reads + 1)
+ * are filled here; haps / phase_sets / ... (the outputs) stay the caller's to set.  Returns 0. */
+int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int *ordered_read_ids, const uint8_t *is_skipped, int *alle_off, int *allele_off,
+                               lcd_hap_problem_t *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,22 @@ class LcdHapProblem(C.Structure):
                 ("n_clean_conflict_snps", _i32p), ("var_phase_set", _i64p), ("hap_to_cons_alle", _i32p), ("hap_to_alle_profile", _i32p)]
 
 
+class LcdCleanOpt(C.Structure):
+    """lcd_clean_opt_t: the call_var_opt_t fields the first round of collect_var_main reads"""
+    _fields_ = [(n, C.c_int) for n in ("min_dp", "min_alt_dp", "min_bq", "min_sv_len", "noisy_reg_max_xgaps", "noisy_reg_flank_len", "noisy_reg_merge_dis",
+                                       "is_ont", "out_somatic")] + [("min_af", C.c_double), ("max_af", C.c_double), ("strand_bias_pval", C.c_float)]
+
+
+class LcdCleanVars(C.Structure):
+    """lcd_clean_vars_t: candidate variants, noisy regions and the read x variant profile of one chunk (every array malloc()'d)"""
+    _i32p, _i64p, _u64p, _u8p = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+    _fields_ = [("n_vars", C.c_int), ("pos", _i64p), ("var_type", _i32p), ("ref_len", _i32p), ("alt_len", _i32p), ("cate", _i32p), ("total_cov", _i32p),
+                ("low_qual_cov", _i32p), ("alle_covs", _i32p), ("strand_alle_covs", _i32p), ("alt_off", _u64p), ("alt_pool", _u8p),
+                ("is_homopolymer_indel", _i32p), ("n_regs", C.c_int), ("regs", C.POINTER(LcdNoisyIv)), ("n_reads", C.c_int), ("start_var_idx", _i32p),
+                ("end_var_idx", _i32p), ("allele_off", _u64p), ("alleles", _i32p), ("alt_qi", _i32p), ("n_cr", C.c_int), ("cr_read", _i32p),
+                ("qual_upload_bytes", C.c_uint64)]
+
+
 _lib = None
 
 # every symbol include/lcd_hotpath.h declares (tests check the .so exports all of them)
@@ -93,6 +109,7 @@ EXPORTS = [
     "lcd_batch_download", "lcd_dispatch_create", "lcd_dispatch_destroy", "lcd_dispatch_n_devices", "lcd_dispatch_run", "lcd_dispatch_set_flags", "lcd_dispatch_busy", "lcd_batch_cost", "lcd_lpt_assign", "lcd_batch_region_result", "lcd_batch_region_sorted_ids", "lcd_batch_region_read_slices", "lcd_batch_get_stats", "lcd_batch_k4_jobs", "lcd_chunk_create", "lcd_chunk_create_from_bam", "lcd_chunk_destroy", "lcd_chunk_n_reads", "lcd_chunk_read_info", "lcd_chunk_intervals", "lcd_chunk_region_slices", "lcd_batch_add_region_from_chunk_dev", "lcd_copy_counters", "lcd_batch_digest", "lcd_batch_materialize", "lcd_batch_region_results_arena",
     "lcd_edlib_batch", "lcd_edlib_batch_hw", "lcd_wfa_batch", "lcd_wfa_arena_bytes", "lcd_poa_batch", "lcd_assign_hap_germline", "lcd_assign_hap_batch", "lcd_flip_variant_hap", "lcd_stitch_chunks", "lcd_call_opt_default", "lcd_make_variants", "lcd_free_variants", "lcd_format_vcf", "lcd_read_tags", "lcd_update_digars_from_msa1", "lcd_bam_load_region", "lcd_bam_load_region_indexed", "lcd_bam_reads_free", "lcd_fasta_fetch", "lcd_vcf_header", "lcd_io_last_error",
     "lcd_region_job_cost", "lcd_region_jobs_pack", "lcd_batch_add_packed", "lcd_rebalance_plan", "lcd_rccl_unique_id", "lcd_comm_create", "lcd_comm_destroy", "lcd_comm_info", "lcd_rebalance_exchange", "lcd_rebalance_last_error",
+    "lcd_clean_opt_default", "lcd_chunk_clean_vars", "lcd_chunk_clean_vars_batch", "lcd_clean_vars_free", "lcd_clean_vars_hap_problem",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -166,6 +183,15 @@ def load_library():
                                                C.POINTER(C.POINTER(LcdNoisyIv))]
     lib.lcd_post_process_noisy_regs.argtypes = [C.POINTER(LcdNoisyIv), C.c_int, C.c_int, i64p, i32p, i32p, C.c_int, C.POINTER(C.POINTER(LcdNoisyIv))]
     lib.lcd_sdust.argtypes = [u8p, C.c_int64, C.c_int, C.c_int, C.POINTER(i64p)]
+    lib.lcd_clean_opt_default.argtypes = [C.POINTER(LcdCleanOpt), C.c_int]
+    lib.lcd_clean_opt_default.restype = None
+    lib.lcd_chunk_clean_vars.argtypes = [C.c_void_p, C.POINTER(LcdCleanOpt), i32p, u8p, u8p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(LcdNoisyIv), C.c_int,
+                                         i64p, C.c_int, C.POINTER(LcdCleanVars)]
+    lib.lcd_chunk_clean_vars_batch.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(LcdCleanOpt), C.POINTER(i32p), C.POINTER(u8p), C.POINTER(u8p), i64p, i64p, i64p,
+                                               i64p, C.POINTER(C.POINTER(LcdNoisyIv)), i32p, C.POINTER(i64p), i32p, C.POINTER(LcdCleanVars)]
+    lib.lcd_clean_vars_free.argtypes = [C.POINTER(LcdCleanVars)]
+    lib.lcd_clean_vars_free.restype = None
+    lib.lcd_clean_vars_hap_problem.argtypes = [C.POINTER(LcdCleanVars), C.c_int, i32p, u8p, i32p, i32p, C.POINTER(LcdHapProblem)]
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]
     lib.lcd_batch_digest.argtypes = [C.c_void_p]

@@ -7,7 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import LcdAlnStr, LcdBatchStats, LcdDigar, LcdDigar1, LcdDigarOpt, LcdNoisyIv, LcdNoisyVar, LcdOpt, LcdReadView, check, load_library
+from ._lib import (LcdAlnStr, LcdBatchStats, LcdCleanOpt, LcdCleanVars, LcdDigar, LcdDigar1, LcdDigarOpt, LcdNoisyIv, LcdNoisyVar, LcdOpt, LcdReadView, check,
+                   load_library)
 
 _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
@@ -550,6 +551,11 @@ class DeviceChunk:
         batch.n_reads.append(len(ids))
         return ri
 
+    def clean_vars(self, ordered_read_ids, ref, ref_beg, ref_end, reg_beg, reg_end, pre_regs=(), low_comp=(), is_rev=None, opt=None):
+        """lcd_chunk_clean_vars: steps 1.2 - 3.1 of collect_var_main on this chunk -> dict (clean_vars_dict)"""
+        return chunk_clean_vars_batch([self], [dict(ordered_read_ids=ordered_read_ids, ref=ref, ref_beg=ref_beg, ref_end=ref_end, reg_beg=reg_beg, reg_end=reg_end,
+                                                    pre_regs=pre_regs, low_comp=low_comp, is_rev=is_rev)], opt, single=True)[0]
+
     def close(self):
         if self.h:
             self.lib.lcd_chunk_destroy.argtypes = [C.c_void_p]
@@ -778,3 +784,110 @@ def assign_hap_batch(probs, target_var_cates, states=None):
     cates = np.ascontiguousarray(target_var_cates, np.int32)
     check(lib.lcd_assign_hap_batch(len(probs), arr, cates.ctypes.data_as(C.POINTER(C.c_int))), lib)
     return states
+
+
+# ---------------- the first round of collect_var_main on a device-resident chunk (lcd_chunk_clean_vars) ----------------
+def clean_opt(is_ont=0, **kw):
+    """lcd_clean_opt_t with the defaults of src/call_var_main.c (HiFi or ONT); keyword arguments override fields"""
+    lib = load_library()
+    o = LcdCleanOpt()
+    lib.lcd_clean_opt_default(C.byref(o), int(is_ont))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def clean_vars_dict(v):
+    """an lcd_clean_vars_t (this library's or the test oracle's: same layout) -> dict of numpy copies"""
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy() if n > 0 and p else np.zeros(0, dt)
+    V, R = v.n_vars, v.n_reads
+    alt_off = arr(v.alt_off, V + 1, np.uint64) if v.alt_off else np.zeros(1, np.uint64)
+    aoff = arr(v.allele_off, R + 1, np.uint64) if v.allele_off else np.zeros(1, np.uint64)
+    regs = np.array([(v.regs[i].start, v.regs[i].end, v.regs[i].label) for i in range(v.n_regs)], np.int64).reshape(-1, 3)
+    return dict(n_vars=V, pos=arr(v.pos, V, np.int64), var_type=arr(v.var_type, V, np.int32), ref_len=arr(v.ref_len, V, np.int32), alt_len=arr(v.alt_len, V, np.int32),
+                cate=arr(v.cate, V, np.int32), total_cov=arr(v.total_cov, V, np.int32), low_qual_cov=arr(v.low_qual_cov, V, np.int32),
+                alle_covs=arr(v.alle_covs, 2 * V, np.int32), strand_alle_covs=arr(v.strand_alle_covs, 4 * V, np.int32), alt_off=alt_off,
+                alt_pool=arr(v.alt_pool, int(alt_off[-1]), np.uint8), is_homopolymer_indel=arr(v.is_homopolymer_indel, V, np.int32), regs=regs, n_reads=R,
+                start_var_idx=arr(v.start_var_idx, R, np.int32), end_var_idx=arr(v.end_var_idx, R, np.int32), allele_off=aoff,
+                alleles=arr(v.alleles, int(aoff[-1]), np.int32), alt_qi=arr(v.alt_qi, int(aoff[-1]), np.int32), cr_read=arr(v.cr_read, v.n_cr, np.int32),
+                qual_upload_bytes=int(v.qual_upload_bytes))
+
+
+# every array of lcd_clean_vars_t (what "equal field for field" compares)
+CLEAN_VARS_FIELDS = ("pos", "var_type", "ref_len", "alt_len", "cate", "total_cov", "low_qual_cov", "alle_covs", "strand_alle_covs", "alt_off", "alt_pool",
+                     "is_homopolymer_indel", "regs", "start_var_idx", "end_var_idx", "allele_off", "alleles", "alt_qi", "cr_read")
+
+
+def _clean_args(a, keep):
+    i32p, i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+    ordered = np.ascontiguousarray(a["ordered_read_ids"], np.int32)
+    ref = np.ascontiguousarray(a["ref"], np.uint8)
+    pre = np.asarray(a.get("pre_regs", ()), np.int64).reshape(-1, 3)
+    prearr = (LcdNoisyIv * max(1, len(pre)))(*[LcdNoisyIv(int(x[0]), int(x[1]), int(x[2]), 0) for x in pre])
+    low = np.ascontiguousarray(np.asarray(a.get("low_comp", ()), np.int64).reshape(-1, 2))
+    lowa = low.reshape(-1) if low.size else np.zeros(2, np.int64)
+    rev = None if a.get("is_rev") is None else np.ascontiguousarray(a["is_rev"], np.uint8)
+    keep += [ordered, ref, prearr, lowa, rev]
+    return (ordered.ctypes.data_as(i32p), None if rev is None else _p8(rev), _p8(ref), int(a["ref_beg"]), int(a["ref_end"]), int(a["reg_beg"]), int(a["reg_end"]),
+            C.cast(prearr, C.POINTER(LcdNoisyIv)), len(pre), lowa.ctypes.data_as(i64p), len(low))
+
+
+def chunk_clean_vars_batch(chunks, args, opt=None, single=False):
+    """lcd_chunk_clean_vars_batch over DeviceChunks; args[i] = dict(ordered_read_ids, ref, ref_beg, ref_end, reg_beg, reg_end, pre_regs (k,3), low_comp (n,2), is_rev)
+    -> list of clean_vars_dict; single=True: one chunk through lcd_chunk_clean_vars"""
+    lib = load_library()
+    opt = opt if opt is not None else clean_opt()
+    keep = []
+    packs = [_clean_args(a, keep) for a in args]
+    n = len(chunks)
+    outs = (LcdCleanVars * n)()
+    if single:
+        check(lib.lcd_chunk_clean_vars(chunks[0].h, C.byref(opt), *packs[0], C.byref(outs[0])), lib)
+    else:
+        i32p, i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        col = lambda k, ty: (ty * n)(*[p[k] for p in packs])
+        check(lib.lcd_chunk_clean_vars_batch(n, (C.c_void_p * n)(*[c.h for c in chunks]), C.byref(opt), col(0, i32p), col(1, u8p), col(2, u8p), col(3, C.c_int64),
+                                             col(4, C.c_int64), col(5, C.c_int64), col(6, C.c_int64), col(7, C.POINTER(LcdNoisyIv)), col(8, C.c_int),
+                                             col(9, i64p), col(10, C.c_int), outs), lib)
+    res = []
+    for i in range(n):
+        res.append(clean_vars_dict(outs[i]))
+        lib.lcd_clean_vars_free(C.byref(outs[i]))
+    return res
+
+
+def clean_vars_hap_problem(cv, ordered_read_ids, is_skipped, is_ont=0):
+    """the K5 problem (assign_hap_germline's dict) over a clean_vars_dict, laid out by lcd_clean_vars_hap_problem (the C entry point fills the view; the
+    arrays it points at are copied out)"""
+    from ._lib import LcdHapProblem
+    lib = load_library()
+    V, R = cv["n_vars"], cv["n_reads"]
+    keep = []
+    def P(a, dt, ty):
+        a = np.ascontiguousarray(a, dt)
+        if a.size == 0:
+            a = np.zeros(1, dt)
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(ty))
+    v = LcdCleanVars()
+    v.n_vars, v.n_reads, v.n_cr = V, R, len(cv["cr_read"])
+    v.pos = P(cv["pos"], np.int64, C.c_int64); v.var_type = P(cv["var_type"], np.int32, C.c_int); v.cate = P(cv["cate"], np.int32, C.c_int)
+    v.is_homopolymer_indel = P(cv["is_homopolymer_indel"], np.int32, C.c_int); v.total_cov = P(cv["total_cov"], np.int32, C.c_int)
+    v.alle_covs = P(cv["alle_covs"], np.int32, C.c_int); v.start_var_idx = P(cv["start_var_idx"], np.int32, C.c_int)
+    v.end_var_idx = P(cv["end_var_idx"], np.int32, C.c_int); v.allele_off = P(cv["allele_off"], np.uint64, C.c_uint64)
+    v.alleles = P(cv["alleles"], np.int32, C.c_int); v.cr_read = P(cv["cr_read"], np.int32, C.c_int)
+    ordered = np.ascontiguousarray(ordered_read_ids, np.int32); skipped = np.ascontiguousarray(is_skipped, np.uint8)
+    alle_off = np.zeros(V + 1, np.int32); allele_off = np.zeros(R + 1, np.int32)
+    p = LcdHapProblem()
+    check(lib.lcd_clean_vars_hap_problem(C.byref(v), int(is_ont), ordered.ctypes.data_as(C.POINTER(C.c_int)), _p8(skipped), alle_off.ctypes.data_as(C.POINTER(C.c_int)),
+                                         allele_off.ctypes.data_as(C.POINTER(C.c_int)), C.byref(p)), lib)
+    def out(ptr, n, dt):
+        return np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt).copy() if n > 0 else np.zeros(0, dt)
+    na = int(allele_off[-1])
+    return dict(n_reads=p.n_reads, n_vars=p.n_vars, is_ont=p.is_ont, var_pos=out(p.var_pos, V, np.int64), var_type=out(p.var_type, V, np.int32),
+                var_cate=out(p.var_cate, V, np.int32), is_homopolymer_indel=out(p.is_homopolymer_indel, V, np.int32), total_cov=out(p.total_cov, V, np.int32),
+                alle_off=out(p.alle_off, V + 1, np.int32), alle_covs=out(p.alle_covs, int(alle_off[-1]), np.int32),
+                start_var_idx=out(p.start_var_idx, R, np.int32), end_var_idx=out(p.end_var_idx, R, np.int32), allele_off=out(p.allele_off, R + 1, np.int32),
+                alleles=out(p.alleles, na, np.int32), ordered_read_ids=out(p.ordered_read_ids, R, np.int32), is_skipped=out(p.is_skipped, R, np.uint8),
+                cr_read=out(p.cr_read, p.n_cr, np.int32))

@@ -15,6 +15,7 @@
 #include <atomic>
 #include <array>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -3208,6 +3209,7 @@ struct lcd_chunk_s {
     std::vector<uint8_t> h_qual; std::vector<uint64_t> qual_off;   // host copy: the sampling rule of >= 10 kb regions reads qualities on the host (src/seq.c:429)
     std::vector<int> status, n_cand; std::vector<int64_t> beg, end;
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
+    DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); }
 };
 lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
@@ -3771,6 +3773,359 @@ int lcd_collect_noisy_reg_aln_strs(const lcd_opt_t *opt, const lcd_read_view_t *
     int nc = lcd_batch_region_result(b, 0, clu_n_seqs, clu_read_ids, aln_strs);
     lcd_batch_destroy(b);
     return nc;
+}
+
+// ---- the first round of collect_var_main on a device-resident chunk (src/collect_var.c:2897-2980, steps 1.2 - 3.1), see include/lcd_hotpath.h ----
+void lcd_clean_opt_default(lcd_clean_opt_t *o, int is_ont) {
+    o->min_dp = 5; o->min_alt_dp = 2; o->min_bq = 10; o->min_sv_len = 30; o->noisy_reg_max_xgaps = 5; o->noisy_reg_flank_len = 10; o->noisy_reg_merge_dis = 500;
+    o->is_ont = is_ont ? 1 : 0; o->out_somatic = 0; o->min_af = 0.20; o->max_af = 0.80; o->strand_bias_pval = 0.01f;
+}
+namespace {
+constexpr int CV_NON_VAR = 0x800, CV_LOW_COV = 0x001, CV_STRAND_BIAS = 0x002, CV_LOW_AF = 0x400, CV_REP_HET = 0x010, CV_NOT_CAND = 0x800 | 0x001 | 0x002;
+// fisher_exact_test (src/math_utils.c:119-168; fast_lgamma is lgamma: its cache holds lgamma(i))
+double cv_log_hyper(int a, int b, int c, int d) {
+    const int n1 = a + b, n2 = c + d, m1 = a + c, m2 = b + d, N = n1 + n2;
+    if (n1 > n2) return cv_log_hyper(c, d, a, b);
+    if (m1 > m2) return cv_log_hyper(b, a, d, c);
+    return lgamma(n1 + 1) + lgamma(n2 + 1) + lgamma(m1 + 1) + lgamma(m2 + 1) - (lgamma(a + 1) + lgamma(b + 1) + lgamma(c + 1) + lgamma(d + 1) + lgamma(N + 1));
+}
+double cv_fisher(int a, int b, int c, int d) {
+    const double p_obs = exp(cv_log_hyper(a, b, c, d));
+    double total = 0.0;
+    const int min_a = (0 > (a + c) - (a + b + c + d)) ? 0 : (a + c) - (b + d), max_a = (a + b) < (a + c) ? (a + b) : (a + c);
+    const int mode_a = (int)((a + b) * (a + c) / (double)(a + b + c + d));
+    auto term = [&](int ca) {
+        const int cb = (a + b) - ca, cc = (a + c) - ca, cd = (b + d) - cb;
+        if (cb >= 0 && cc >= 0 && cd >= 0) { const double p = exp(cv_log_hyper(ca, cb, cc, cd)); if (p <= p_obs + DBL_EPSILON) total += p; }
+    };
+    for (int delta = 0; delta <= max_a - min_a; delta++) {
+        if (mode_a + delta <= max_a) term(mode_a + delta);
+        if (delta > 0 && mode_a - delta >= min_a) term(mode_a - delta);
+    }
+    return total;
+}
+int cv_strand_bias(const CvCov &v, float pval) { // var_is_strand_bias (src/collect_var.c:270)
+    const int f = v.strand[1], r = v.strand[3], e = (f + r) / 2;
+    if (e == 0) return 0;
+    const float p = (float)cv_fisher(f, r, e, e);
+    return p < pval;
+}
+// intervals [st, en) sorted by start, for counting overlaps with short queries (cr_overlap's count)
+struct CvOvl {
+    std::vector<long long> st, en; long long maxlen = 0;
+    void build(std::vector<std::pair<long long, long long>> v) {
+        std::sort(v.begin(), v.end());
+        for (auto &x : v) { st.push_back(x.first); en.push_back(x.second); maxlen = std::max(maxlen, x.second - x.first); }
+    }
+    long long count(long long qs, long long qe) const {
+        long long n = 0;
+        for (long long i = (long long)(std::lower_bound(st.begin(), st.end(), qe) - st.begin()) - 1; i >= 0 && st[i] >= qs - maxlen; --i) if (qs < en[i]) n++;
+        return n;
+    }
+};
+} // namespace
+
+static int clean_vars_one(const lcd_chunk_t *c0, const lcd_clean_opt_t *opt, const int *ordered, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
+                          int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre, const int64_t *low_comp, int n_low,
+                          lcd_clean_vars_t *out) {
+    memset(out, 0, sizeof(*out));
+    lcd_chunk_s *c = const_cast<lcd_chunk_s *>(c0);
+    if (!c || !opt || !out) return set_err(-4, "lcd_chunk_clean_vars: NULL argument");
+    if (opt->out_somatic) return set_err(-2, "lcd_chunk_clean_vars: somatic mode (out_somatic) is not supported");
+    if (use_device(c->device)) return -1;
+    const int n = c->n_reads;
+    if (reg_beg < 1 || reg_end < reg_beg || reg_end - reg_beg > (1ll << 28)) return set_err(-4, "lcd_chunk_clean_vars: region [reg_beg, reg_end] out of range");
+    if (!ref_seq || ref_end < ref_beg) return set_err(-4, "lcd_chunk_clean_vars: no reference");
+    if (n > 0 && !ordered) return set_err(-4, "lcd_chunk_clean_vars: no ordered_read_ids");
+    // the reads as the kernels see them; the qualities of a host-array chunk go up once
+    std::vector<CvRead> reads(n + 1);
+    uint64_t qbase = c->qual_base;
+    if (n > 0 && !qbase) {
+        std::lock_guard<std::mutex> lk(c->qual_mu);
+        if (!c->d_qual.p) {
+            if (c->d_qual.ensure(c->h_qual.size() + 64)) return -11;
+            if (!c->h_qual.empty() && hipMemcpy(c->d_qual.p, c->h_qual.data(), c->h_qual.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); c->d_qual.release(); return set_err(-10, "lcd_chunk_clean_vars: quality upload failed"); }
+            out->qual_upload_bytes = c->h_qual.size();
+        }
+        qbase = c->d_qual.addr();
+    }
+    uint64_t n_rec = 0;
+    for (int r = 0; r < n; ++r) {
+        CvRead &x = reads[r];
+        x.dig = c->slot[r]; x.n_digar = c->n_digar[r]; x.seq = c->seq_base + c->seq_off[r]; x.qual = qbase + c->qual_off[r]; x.beg = c->beg[r]; x.end = c->end[r];
+        x.qlen = c->qlen[r]; x.strand = is_rev ? (is_rev[r] != 0) : 0; x.iv = c->iv_off[r]; x.n_iv = (int)(c->iv_off[r + 1] - c->iv_off[r]);
+        n_rec = std::max<uint64_t>(n_rec, x.dig + (uint64_t)x.n_digar);
+    }
+    std::vector<int> order;
+    for (int i = 0; i < n; ++i) {
+        const int r = ordered[i];
+        if (r < 0 || r >= n) return set_err(-4, "lcd_chunk_clean_vars: ordered_read_ids out of range");
+        if (c->status[r] != -1) order.push_back(r);
+    }
+    const int m = (int)order.size();
+    CvOpt o; o.min_dp = opt->min_dp; o.min_alt_dp = opt->min_alt_dp; o.min_bq = opt->min_bq; o.min_sv_len = opt->min_sv_len; o.max_xgaps = opt->noisy_reg_max_xgaps; o.pad = 0;
+    o.min_af = opt->min_af; o.max_af = opt->max_af; o.reg_beg = reg_beg; o.reg_end = reg_end; o.ref_beg = ref_beg; o.ref_end = ref_end;
+    const uint64_t n_iv = n > 0 ? c->iv_off[n] : 0, ref_len = (uint64_t)(ref_end - ref_beg + 1);
+    StreamGuard st; if (st.create()) return -10;
+    DevBuf d_reads, d_order, d_ivs, d_ref, d_cnt, d_tot;
+    if (d_reads.ensure((n + 1) * sizeof(CvRead)) || d_order.ensure((m + 1) * 4ull) || d_ivs.ensure((n_iv + 1) * sizeof(IvRec)) || d_ref.ensure(ref_len + 64) ||
+        d_cnt.ensure((m + 1) * 4ull) || d_tot.ensure(64)) return -11;
+    const DigarRec *dg = (const DigarRec *)c->d_dig.p;
+    HIPCHK(hipMemcpyAsync(d_reads.p, reads.data(), (n + 1) * sizeof(CvRead), hipMemcpyHostToDevice, st));
+    if (m) HIPCHK(hipMemcpyAsync(d_order.p, order.data(), m * 4ull, hipMemcpyHostToDevice, st));
+    if (n_iv) HIPCHK(hipMemcpyAsync(d_ivs.p, c->ivs, n_iv * sizeof(IvRec), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(d_ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, st));
+    const CvRead *R = (const CvRead *)d_reads.p; const int *O = (const int *)d_order.p;
+    // 1.2 candidate sites: count, offsets, emit with the key histogram, counting sort + bucket rank sort, dedup, compaction
+    lcd_launch_cv_count(R, O, m, dg, reg_beg, reg_end, (int *)d_cnt.p, st);
+    HIPCHK(hipGetLastError());
+    std::vector<int> cnt(m + 1, 0);
+    if (m) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, m * 4ull, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    long long n_raw = 0;
+    for (int k = 0; k < m; ++k) { const int x = cnt[k]; cnt[k] = (int)n_raw; n_raw += x; }
+    if (n_raw > (1ll << 30)) return set_err(-4, "lcd_chunk_clean_vars: too many site records");
+    const int nr = (int)n_raw;
+    const long long key0 = reg_beg - 1; const int nb = (int)(((reg_end - reg_beg + 1) >> 6) + 1); // (64 position keys per bucket, clean_vars_kernel.hip)
+    DevBuf d_off, d_sites, d_hist, d_fill, d_tmp, d_sorted, d_keep, d_kidx, d_u, d_cov, d_cate;
+    if (d_off.ensure((m + 1) * 4ull) || d_sites.ensure((nr + 1) * sizeof(CvSite)) || d_hist.ensure((nb + 2) * 4ull) || d_fill.ensure((nb + 2) * 4ull) ||
+        d_tmp.ensure((nr + 1) * 4ull) || d_sorted.ensure((nr + 1) * 4ull) || d_keep.ensure((nr + 1) * 4ull) || d_kidx.ensure((nr + 1) * 4ull)) return -11;
+    if (m) HIPCHK(hipMemcpyAsync(d_off.p, cnt.data(), m * 4ull, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(d_hist.p, 0, (nb + 2) * 4ull, st));
+    HIPCHK(hipMemsetAsync(d_fill.p, 0, (nb + 2) * 4ull, st));
+    lcd_launch_cv_emit(R, O, m, dg, reg_beg, reg_end, (const int *)d_off.p, (CvSite *)d_sites.p, (int *)d_hist.p, key0, st);
+    lcd_launch_cv_scan((int *)d_hist.p, nb + 1, (int *)d_tot.p, st);
+    lcd_launch_cv_sort((const CvSite *)d_sites.p, nr, R, (const int *)d_hist.p, (int *)d_fill.p, (int *)d_tmp.p, (int *)d_sorted.p, key0, nb, (int *)d_keep.p,
+                       opt->min_sv_len, st);
+    HIPCHK(hipGetLastError());
+    int ns = 0;
+    if (nr) {
+        HIPCHK(hipMemcpyAsync(d_kidx.p, d_keep.p, nr * 4ull, hipMemcpyDeviceToDevice, st));
+        lcd_launch_cv_scan((int *)d_kidx.p, nr, (int *)d_tot.p, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&ns, d_tot.p, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    if (d_u.ensure((ns + 1) * sizeof(CvSite)) || d_cov.ensure((ns + 1) * sizeof(CvCov)) || d_cate.ensure((ns + 1) * 4ull)) return -11;
+    const CvSite *U = (const CvSite *)d_u.p;
+    lcd_launch_cv_compact((const CvSite *)d_sites.p, (const int *)d_sorted.p, (const int *)d_keep.p, (const int *)d_kidx.p, nr, (CvSite *)d_u.p, st);
+    // 1.3 pile-up and 2.2 per-site classification
+    HIPCHK(hipMemsetAsync(d_cov.p, 0, (ns + 1) * sizeof(CvCov), st));
+    lcd_launch_cv_pileup(R, O, m, dg, U, ns, (CvCov *)d_cov.p, o, st);
+    lcd_launch_cv_classify(U, R, (const CvCov *)d_cov.p, ns, (const unsigned char *)d_ref.p, o, (int *)d_cate.p, st);
+    HIPCHK(hipGetLastError());
+    std::vector<CvSite> sites(ns + 1); std::vector<CvCov> cov(ns + 1); std::vector<int> cate(ns + 1);
+    if (ns) {
+        HIPCHK(hipMemcpyAsync(sites.data(), d_u.p, ns * sizeof(CvSite), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(cov.data(), d_cov.p, ns * sizeof(CvCov), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(cate.data(), d_cate.p, ns * 4ull, hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    // 2.2 / 2.3 classify_cand_vars (:902-1040), host side: the ONT strand-bias test, var_pos_cr, the noisy-region tests, cr_add_var_cr, cr_merge2, post_process
+    std::vector<std::pair<long long, long long>> vp;
+    for (int i = 0; i < ns; ++i) {
+        if (opt->is_ont && cate[i] != CV_LOW_COV && cv_strand_bias(cov[i], opt->strand_bias_pval)) cate[i] = CV_STRAND_BIAS;
+        if (cate[i] == CV_LOW_COV) continue;
+        if (opt->is_ont && cate[i] == CV_STRAND_BIAS) continue;
+        const CvSite &v = sites[i];
+        const long long a = std::max<long long>(0, v.pos - 1), b = v.var_type == 1 ? v.pos : v.pos + v.ref_len - 1; // cr_add: start clamped at 0, st > en dropped
+        if (a <= b) vp.push_back({a, b});
+    }
+    CvOvl var_pos; var_pos.build(vp);
+    std::vector<std::pair<long long, long long>> low;
+    for (int k = 0; k < n_low; ++k) { const long long a = std::max<long long>(0, low_comp[2 * k]), b = low_comp[2 * k + 1]; if (a <= b) low.push_back({a, b}); }
+    std::vector<std::pair<long long, long long>> pre;
+    for (int i = 0; i < n_pre; ++i) { const long long a = std::max<long long>(0, pre_regs[i].start), b = pre_regs[i].end; if (a <= b) pre.push_back({a, b}); }
+    struct Act { int check; long long vs, ve; };
+    std::vector<Act> acts; std::vector<long long> q;
+    for (int i = 0; i < ns; ++i) {
+        const CvSite &v = sites[i]; const int vc = cate[i];
+        if (vc == CV_NON_VAR || vc == CV_STRAND_BIAS) continue;
+        const long long qs = v.pos - 1, qe = v.var_type == 1 ? v.pos : v.pos + v.ref_len - 1;
+        if (!pre.empty()) {
+            bool hit = false;
+            for (auto &x : pre) if (x.first < qe && qs < x.second) { hit = true; break; }
+            if (hit) { cate[i] = CV_NON_VAR; continue; }
+        }
+        if (vc == CV_LOW_COV) continue;
+        const bool in_reg = v.pos >= reg_beg && v.pos <= reg_end;
+        auto add_var_cr = [&](int check) { // cr_add_var_cr (:750-775): grow to the overlapping low-complexity intervals (one query with the variant's own span)
+            long long vs = v.pos, ve = v.var_type == 1 ? v.pos : v.pos + v.ref_len - 1;
+            const long long ls = vs - 1, le = ve;
+            for (auto &x : low) if (x.first < le && ls < x.second) { vs = std::min(vs, x.first + 1); ve = std::max(ve, x.second); }
+            acts.push_back({check ? (int)(q.size() / 2) : -1, vs, ve});
+            if (check) { q.push_back(vs); q.push_back(ve); }
+        };
+        if (vc == CV_REP_HET) { if (in_reg) add_var_cr(0); continue; }
+        if (var_pos.count(qs, qe) > 1 && in_reg) add_var_cr(1);
+        if (vc == CV_LOW_AF) cate[i] = CV_LOW_COV;
+    }
+    std::vector<int> qc(q.size() + 2, 0);
+    const int nq = (int)(q.size() / 2);
+    if (nq) { // var_noisy_reads_ratio on the digars in HBM
+        DevBuf d_err, d_nerr, d_q, d_qc;
+        if (d_err.ensure((n_rec + 1) * sizeof(IvRec)) || d_nerr.ensure((n + 1) * 4ull) || d_q.ensure(q.size() * 8 + 64) || d_qc.ensure(q.size() * 4 + 64)) return -11;
+        HIPCHK(hipMemsetAsync(d_nerr.p, 0xff, (n + 1) * 4ull, st));
+        HIPCHK(hipMemcpyAsync(d_q.p, q.data(), q.size() * 8, hipMemcpyHostToDevice, st));
+        lcd_launch_cv_err_ivs(R, O, m, dg, (IvRec *)d_err.p, (int *)d_nerr.p, st);
+        lcd_launch_cv_ratio(R, O, m, (const IvRec *)d_err.p, (const int *)d_nerr.p, (const long long *)d_q.p, nq, (int *)d_qc.p, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(qc.data(), d_qc.p, q.size() * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    std::vector<NIv> nv;
+    for (const Act &a : acts) {
+        if (a.check >= 0) {
+            const int tot = qc[2 * a.check], noisy = qc[2 * a.check + 1];
+            const float ratio = tot == 0 ? 0.0f : (float)noisy / (tot + 0.0);
+            if (!(ratio >= opt->min_af)) continue;
+        }
+        niv_add(nv, a.vs - 1, a.ve, 1);
+    }
+    std::vector<NIv> regs;
+    for (int i = 0; i < n_pre; ++i) niv_add(regs, pre_regs[i].start, pre_regs[i].end, pre_regs[i].label);
+    if (!nv.empty()) { // cr_merge2(chunk_noisy_regs, noisy_var_cr, -1, ..): both lists in their index order, cr_index, cr_merge
+        niv_index(nv);
+        for (const NIv &x : nv) regs.push_back(x);
+        niv_index(regs);
+        niv_merge(regs);
+    }
+    std::vector<lcd_noisy_iv_t> rin(regs.size() + 1);
+    for (size_t i = 0; i < regs.size(); ++i) { rin[i].start = (int64_t)regs[i].x; rin[i].end = regs[i].en; rin[i].label = regs[i].label; rin[i].pad = 0; }
+    std::vector<int64_t> vpos(ns + 1); std::vector<int> vrl(ns + 1);
+    for (int i = 0; i < ns; ++i) { vpos[i] = sites[i].pos; vrl[i] = sites[i].ref_len; }
+    lcd_noisy_iv_t *fin = nullptr;
+    const int n_fin = lcd_post_process_noisy_regs(rin.data(), (int)regs.size(), ns, vpos.data(), vrl.data(), cate.data(), opt->noisy_reg_flank_len, &fin);
+    // compaction (:1007-1023): candidates not contained in a final noisy region (cr_is_contained: the last region starting at or before the query start)
+    std::vector<int> keep;
+    for (int i = 0; i < ns; ++i) {
+        if (cate[i] & CV_NOT_CAND) continue;
+        if (n_fin > 0) {
+            const long long qs = sites[i].pos - 1, qe = sites[i].pos + sites[i].ref_len;
+            int lo = 0, hi = n_fin;
+            while (hi > lo) { const int mid = lo + ((hi - lo) >> 1); if (fin[mid].start <= qs) lo = mid + 1; else hi = mid; }
+            if (lo > 0 && fin[lo - 1].start < qe && fin[lo - 1].end >= qe) { cate[i] = CV_NON_VAR; continue; }
+        }
+        keep.push_back(i);
+    }
+    const int V = (int)keep.size();
+    out->n_regs = n_fin > 0 ? n_fin : 0;
+    out->regs = fin ? fin : (lcd_noisy_iv_t *)calloc(1, sizeof(lcd_noisy_iv_t));
+    std::vector<CvSite> vars(V + 1); std::vector<int> vcate(V + 1); std::vector<unsigned long long> aoff(V + 1, 0);
+    out->n_vars = V;
+    out->pos = (int64_t *)malloc((V + 1) * 8ull); out->var_type = (int *)malloc((V + 1) * 4ull); out->ref_len = (int *)malloc((V + 1) * 4ull);
+    out->alt_len = (int *)malloc((V + 1) * 4ull); out->cate = (int *)malloc((V + 1) * 4ull); out->total_cov = (int *)malloc((V + 1) * 4ull);
+    out->low_qual_cov = (int *)malloc((V + 1) * 4ull); out->alle_covs = (int *)malloc((V + 1) * 8ull); out->strand_alle_covs = (int *)malloc((V + 1) * 16ull);
+    out->alt_off = (uint64_t *)malloc((V + 1) * 8ull); out->is_homopolymer_indel = (int *)calloc(V + 1, 4);
+    unsigned long long na = 0;
+    for (int k = 0; k < V; ++k) {
+        const int i = keep[k]; const CvSite &v = sites[i]; const CvCov &cv = cov[i];
+        vars[k] = v; vcate[k] = cate[i];
+        out->pos[k] = v.pos; out->var_type[k] = v.var_type; out->ref_len[k] = v.ref_len; out->alt_len[k] = v.alt_len; out->cate[k] = cate[i];
+        out->total_cov[k] = cv.total; out->low_qual_cov[k] = cv.low; out->alle_covs[2 * k] = cv.alle[0]; out->alle_covs[2 * k + 1] = cv.alle[1];
+        for (int j = 0; j < 4; ++j) out->strand_alle_covs[4 * k + j] = cv.strand[j];
+        aoff[k] = na; out->alt_off[k] = na;
+        if (v.var_type == 8 || v.var_type == 1) na += (unsigned long long)v.alt_len;
+    }
+    aoff[V] = na; out->alt_off[V] = na;
+    out->alt_pool = (uint8_t *)malloc(na + 1);
+    // 3.1 collect_read_var_profile: spans, CSR offsets, alleles; the alt bases of the variants
+    DevBuf d_vars, d_vcate, d_aoff, d_pool, d_se, d_poff, d_al, d_qi;
+    if (d_vars.ensure((V + 1) * sizeof(CvSite)) || d_vcate.ensure((V + 1) * 4ull) || d_aoff.ensure((V + 1) * 8ull) || d_pool.ensure(na + 64) ||
+        d_se.ensure(2ull * (n + 1) * 4) || d_poff.ensure((n + 1) * 8ull)) return -11;
+    int *d_start = (int *)d_se.p, *d_end = d_start + (n + 1);
+    if (V) {
+        HIPCHK(hipMemcpyAsync(d_vars.p, vars.data(), V * sizeof(CvSite), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_vcate.p, vcate.data(), V * 4ull, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_aoff.p, aoff.data(), (V + 1) * 8ull, hipMemcpyHostToDevice, st));
+    }
+    const CvSite *VV = (const CvSite *)d_vars.p;
+    lcd_launch_cv_alt(VV, R, (const unsigned long long *)d_aoff.p, V, (unsigned char *)d_pool.p, st);
+    lcd_launch_cv_profile(0, R, O, m, dg, VV, (const int *)d_vcate.p, V, (const IvRec *)d_ivs.p, d_start, d_end, nullptr, nullptr, nullptr, o, st);
+    HIPCHK(hipGetLastError());
+    std::vector<int> se(2ull * (n + 1));
+    if (na) HIPCHK(hipMemcpyAsync(out->alt_pool, d_pool.p, na, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(se.data(), d_se.p, 2ull * (n + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    out->n_reads = n;
+    out->start_var_idx = (int *)malloc((n + 1) * 4ull); out->end_var_idx = (int *)malloc((n + 1) * 4ull); out->allele_off = (uint64_t *)malloc((n + 1) * 8ull);
+    std::vector<char> walked(n + 1, 0);
+    for (int r : order) walked[r] = 1;
+    uint64_t tot = 0;
+    for (int r = 0; r < n; ++r) {
+        const int s0 = walked[r] ? se[r] : -1, e0 = walked[r] ? se[(n + 1) + r] : -2;
+        out->start_var_idx[r] = s0; out->end_var_idx[r] = e0; out->allele_off[r] = tot;
+        if (s0 >= 0) tot += (uint64_t)(e0 - s0 + 1);
+    }
+    out->allele_off[n] = tot;
+    out->alleles = (int *)malloc((tot + 1) * 4); out->alt_qi = (int *)malloc((tot + 1) * 4);
+    if (tot) {
+        if (d_al.ensure(tot * 4 + 64) || d_qi.ensure(tot * 4 + 64)) return -11;
+        HIPCHK(hipMemcpyAsync(d_poff.p, out->allele_off, (n + 1) * 8ull, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d_al.p, 0xff, tot * 4, st)); HIPCHK(hipMemsetAsync(d_qi.p, 0xff, tot * 4, st));
+        lcd_launch_cv_profile(1, R, O, m, dg, VV, (const int *)d_vcate.p, V, (const IvRec *)d_ivs.p, d_start, d_end, (const unsigned long long *)d_poff.p, (int *)d_al.p,
+                              (int *)d_qi.p, o, st);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out->alleles, d_al.p, tot * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(out->alt_qi, d_qi.p, tot * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+    }
+    // read_var_cr: cr_add(start, end + 1, read) in ordered_read_ids order, cr_index
+    std::vector<NIv> rv;
+    for (int r : order) if (out->start_var_idx[r] >= 0 && out->end_var_idx[r] >= 0) niv_add(rv, out->start_var_idx[r], out->end_var_idx[r] + 1, r);
+    niv_index(rv);
+    out->n_cr = (int)rv.size();
+    out->cr_read = (int *)malloc((rv.size() + 1) * 4);
+    for (size_t i = 0; i < rv.size(); ++i) out->cr_read[i] = rv[i].label;
+    return 0;
+}
+int lcd_chunk_clean_vars(const lcd_chunk_t *c, const lcd_clean_opt_t *opt, const int *ordered_read_ids, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
+                         int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre_regs, const int64_t *low_comp, int n_low,
+                         lcd_clean_vars_t *out) {
+    if (ensure_init()) { if (out) memset(out, 0, sizeof(*out)); return -1; }
+    const int rc = clean_vars_one(c, opt, ordered_read_ids, is_rev, ref_seq, ref_beg, ref_end, reg_beg, reg_end, pre_regs, n_pre_regs, low_comp, n_low, out);
+    if (rc) lcd_clean_vars_free(out);
+    return rc;
+}
+int lcd_chunk_clean_vars_batch(int n, const lcd_chunk_t *const *chunks, const lcd_clean_opt_t *opt, const int *const *ordered_read_ids, const uint8_t *const *is_rev,
+                               const uint8_t *const *ref_seq, const int64_t *ref_beg, const int64_t *ref_end, const int64_t *reg_beg, const int64_t *reg_end,
+                               const lcd_noisy_iv_t *const *pre_regs, const int *n_pre_regs, const int64_t *const *low_comp, const int *n_low, lcd_clean_vars_t *outs) {
+    if (n <= 0) return 0;
+    if (ensure_init()) return -1;
+    std::vector<int> rc(n, 0);
+    std::vector<std::string> err(n);
+    std::atomic<int> next(0);
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < n;) {
+            rc[i] = lcd_chunk_clean_vars(chunks[i], opt, ordered_read_ids[i], is_rev ? is_rev[i] : nullptr, ref_seq[i], ref_beg[i], ref_end[i], reg_beg[i], reg_end[i],
+                                         pre_regs ? pre_regs[i] : nullptr, n_pre_regs ? n_pre_regs[i] : 0, low_comp ? low_comp[i] : nullptr, n_low ? n_low[i] : 0, outs + i);
+            if (rc[i]) err[i] = lcd_last_error();
+        }
+    };
+    const int nt = std::max(1, std::min(n, host_team()));
+    std::vector<std::thread> th;
+    for (int t = 1; t < nt; ++t) th.emplace_back(work);
+    work();
+    for (auto &t : th) t.join();
+    for (int i = 0; i < n; ++i) if (rc[i]) { for (int j = 0; j < n; ++j) lcd_clean_vars_free(outs + j); return set_err(rc[i], "chunk " + std::to_string(i) + ": " + err[i]); }
+    return 0;
+}
+void lcd_clean_vars_free(lcd_clean_vars_t *v) {
+    if (!v) return;
+    free(v->pos); free(v->var_type); free(v->ref_len); free(v->alt_len); free(v->cate); free(v->total_cov); free(v->low_qual_cov); free(v->alle_covs);
+    free(v->strand_alle_covs); free(v->alt_off); free(v->alt_pool); free(v->is_homopolymer_indel); free(v->regs); free(v->start_var_idx); free(v->end_var_idx);
+    free(v->allele_off); free(v->alleles); free(v->alt_qi); free(v->cr_read);
+    memset(v, 0, sizeof(*v));
+}
+int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int *ordered_read_ids, const uint8_t *is_skipped, int *alle_off, int *allele_off,
+                               lcd_hap_problem_t *p) {
+    for (int i = 0; i <= v->n_vars; ++i) alle_off[i] = 2 * i;
+    for (int r = 0; r <= v->n_reads; ++r) allele_off[r] = (int)v->allele_off[r];
+    p->n_reads = v->n_reads; p->n_vars = v->n_vars; p->is_ont = is_ont;
+    p->var_pos = v->pos; p->var_type = v->var_type; p->var_cate = v->cate; p->is_homopolymer_indel = v->is_homopolymer_indel; p->total_cov = v->total_cov;
+    p->alle_off = alle_off; p->alle_covs = v->alle_covs; p->start_var_idx = v->start_var_idx; p->end_var_idx = v->end_var_idx; p->allele_off = allele_off;
+    p->alleles = v->alleles; p->ordered_read_ids = ordered_read_ids; p->is_skipped = is_skipped; p->n_cr = v->n_cr; p->cr_read = v->cr_read;
+    return 0;
 }
 
 } // extern "C"

@@ -30,3 +30,19 @@ void lcd_launch_region_support(const IvRec *regs, int n_regs, const long long *r
                                const IvRec *ivs, int n_reads, int *total, int *noisy, hipStream_t stream);
 void lcd_launch_sdust(const unsigned char *pool, const SdSeg *segs, int T, int W, int seg, int n_seg, int cap, int *n_out, int2 *out, int4 *pbuf, int pcap, hipStream_t stream);
 void lcd_launch_hap(const HapProb *probs, int n, hipStream_t stream);
+// clean_vars_kernel.hip: candidate sites, pile-up, classification, noisy-read ratios and the read x variant profile of a device-resident chunk
+void lcd_launch_cv_count(const CvRead *reads, const int *order, int n, const DigarRec *dg, long long reg_beg, long long reg_end, int *cnt, hipStream_t st);
+void lcd_launch_cv_emit(const CvRead *reads, const int *order, int n, const DigarRec *dg, long long reg_beg, long long reg_end, const int *off, CvSite *sites,
+                        int *hist, long long key0, hipStream_t st);
+int lcd_launch_cv_scan(int *a, int n, int *total, hipStream_t st);   // exclusive prefix sum in place, *total = the sum (device int)
+void lcd_launch_cv_sort(const CvSite *sites, int n_sites, const CvRead *reads, const int *bstart, int *fill, int *tmp, int *sorted, long long key0, int n_buckets,
+                        int *keep, int min_sv_len, hipStream_t st);
+void lcd_launch_cv_compact(const CvSite *sites, const int *sorted, const int *keep, const int *kidx, int n, CvSite *out, hipStream_t st);
+void lcd_launch_cv_pileup(const CvRead *reads, const int *order, int n, const DigarRec *dg, const CvSite *sites, int n_sites, CvCov *cov, CvOpt opt, hipStream_t st);
+void lcd_launch_cv_classify(const CvSite *sites, const CvRead *reads, const CvCov *cov, int n_sites, const unsigned char *ref, CvOpt opt, int *cate, hipStream_t st);
+void lcd_launch_cv_err_ivs(const CvRead *reads, const int *order, int n, const DigarRec *dg, IvRec *err, int *n_err, hipStream_t st);
+void lcd_launch_cv_ratio(const CvRead *reads, const int *order, int n, const IvRec *err, const int *n_err, const long long *q, int n_q, int *counts, hipStream_t st);
+// pass 0: start / end index per read; pass 1: alleles / alt_qi at allele_off[read]
+void lcd_launch_cv_profile(int pass, const CvRead *reads, const int *order, int n, const DigarRec *dg, const CvSite *vars, const int *cate, int n_vars,
+                           const IvRec *ivs, int *start, int *end, const unsigned long long *allele_off, int *alleles, int *alt_qi, CvOpt opt, hipStream_t st);
+void lcd_launch_cv_alt(const CvSite *vars, const CvRead *reads, const unsigned long long *alt_off, int n_vars, unsigned char *pool, hipStream_t st);

@@ -331,3 +331,11 @@ struct HapProb {
     // scratch
     int *valid, *vii, *het, *is_het, *n_agree, *n_conflict, *cur_cons, *flags;
 };
+
+// ---- the first round of collect_var_main on a device-resident chunk (clean_vars_kernel.hip) ----
+// one read of the chunk as the walks see it: digars (record index into the chunk's DigarRec array), 4-bit bases and qualities at absolute device addresses
+struct CvRead { uint64_t dig, seq, qual; long long beg, end; int n_digar, qlen, strand, n_iv; uint64_t iv; };
+// var_site_t / cand_var_t key: the alt bases stay in the read they came from (read index, query offset)
+struct CvSite { long long pos; int var_type, ref_len, alt_len, read, qi, pad; };
+struct CvCov { int total, low, alle[2], strand[4]; };   // total_cov, low_qual_cov, alle_covs, strand_to_alle_covs[0][0..1], [1][0..1]
+struct CvOpt { int min_dp, min_alt_dp, min_bq, min_sv_len, max_xgaps, pad; double min_af, max_af; long long reg_beg, reg_end, ref_beg, ref_end; };
