@@ -257,7 +257,7 @@ int lcd_batch_region_result(lcd_batch_t *b, int region, int *clu_n_seqs, int **c
  * == make_vars_from_msa_cons_aln (src/collect_var.c:2279-2347: make_cand_vars_from_msa :1855, update_cand_var_profile_from_cons_aln_str1/2
  * :2164/:2206) computed on the device from the strings of lcd_batch_run.  What stays with the caller, as host code in the reference too:
  * TSD / polyA / TE annotation of gaps >= min_sv_len (collect_te_info_from_cons, :1815/:1834, SURVEY a14: lcd_collect_te_info_from_cons below, applied by the
- * caller to the INS / DEL records it gets) and merge_var_profile (:2712). */
+ * caller to the INS / DEL records it gets) and merge_var_profile (:2712; lcd_merge_region_vars below does it on the library's flat chunk state). */
 typedef struct lcd_noisy_var_t {   /* the cand_var_t fields make_cand_vars0 (src/collect_var.c:1746) and the profile update fill */
     int64_t pos;
     int var_type, ref_len, alt_len; /* BAM_CDIFF 8 / BAM_CINS 1 / BAM_CDEL 2 */
@@ -606,6 +606,40 @@ void lcd_clean_vars_free(lcd_clean_vars_t *v);
  * are filled here; haps / phase_sets / ... (the outputs) stay the caller's to set.  Returns 0. */
 int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int *ordered_read_ids, const uint8_t *is_skipped, int *alle_off, int *allele_off,
                                lcd_hap_problem_t *p);
+
+/* ---- a pass's noisy-region variants folded into the chunk: merge_var_profile (src/collect_var.c:1298-1387) as collect_noisy_vars1 (:2711) calls it per region ----
+ * cur = the chunk's state (lcd_chunk_clean_vars' output, or an earlier merge's); regions[k] = what lcd_batch_region_vars returned for the k-th region the caller
+ * processed (borrowed; the order matters: lcd_sort_noisy_regs below gives the reference's).  The result is the left fold of one merge per region; a region with
+ * n_vars <= 0 changes nothing.
+ *   variant table   a two-pointer walk of the current table with the region's list IN THE ORDER GIVEN (MSA column order; not sorted first), compared with
+ *                   exact_comp_var_site (:1878: position key, type, ref_len, alt_len, alt bases of X / INS; no fuzzy insertion match): the smaller entry is
+ *                   emitted, on equality the table's entry stays and the region's is dropped.  A kept table entry carries all its fields; a kept region entry
+ *                   takes pos, var_type, ref_len, alt_len, cate, total_cov, alle_covs, is_homopolymer_indel and alt_seq from its lcd_noisy_var_t, and its
+ *                   low_qual_cov and strand_alle_covs are 0: make_cand_vars0 (:1746) clears the whole cand_var_t and the noisy-region pass never counts them.
+ *   profile         per chunk read (skipped reads: (-1, -2), no cells): every cell of its current span moves to the merged index of its variant, every cell of
+ *                   its row's span in a region (prof_start >= 0 and prof_end >= prof_start) to the merged index of that region variant with alt_qi = -1, unless
+ *                   the variant was dropped (the old allele at the equal variant stays); start / end = min / max of the moved indices, cells nobody moved are
+ *                   allele -1 / alt_qi -1, a read without a cell keeps (-1, -2).  Computed on the device (merge_vars_kernel.hip).
+ *   cr_read / n_cr  rebuilt as in lcd_chunk_clean_vars; n_regs / regs are copied; qual_upload_bytes = 0.
+ * out is freed with lcd_clean_vars_free and lcd_clean_vars_hap_problem works on it unchanged; cur->n_vars == 0 is legal.  cur_to_merged (cur->n_vars entries) and
+ * region_to_merged[k] (regions[k].n_vars entries, -1 = dropped) are the maps through the whole fold: what a caller carries per-variant K5 state (var_phase_set,
+ * hap_to_cons_alle, hap_to_alle_profile) across the merge with; both may be NULL.  Malformed input -- a row read id outside [0, n_reads), a span outside
+ * [0, n_vars), a read twice in one region, n_regions < 0 -- returns < 0 (lcd_last_error()) before anything is launched.  The table walk is host code (sequential,
+ * regions x table size); the batch form runs all chunks through one upload, one set of launches on one stream, one device allocation, one download and one
+ * synchronisation (every argument an array of n_chunks; cur_to_merged / region_to_merged and their entries may be NULL).  Results == n_chunks single calls. */
+typedef struct lcd_region_vars_t {   /* one region's lcd_batch_region_vars output, borrowed */
+    int n_vars; const lcd_noisy_var_t *vars;
+    int n_rows; const int *row_read_ids, *prof_start, *prof_end, *prof_alleles;
+} lcd_region_vars_t;
+int lcd_merge_region_vars(const lcd_clean_vars_t *cur, int n_regions, const lcd_region_vars_t *regions, const int *ordered_read_ids, const uint8_t *is_skipped,
+                          lcd_clean_vars_t *out, int *cur_to_merged /* cur->n_vars, may be NULL */,
+                          int **region_to_merged /* n_regions arrays of n_vars, may be NULL; -1 = dropped */);
+int lcd_merge_region_vars_batch(int n_chunks, const lcd_clean_vars_t *const *cur, const int *n_regions, const lcd_region_vars_t *const *regions,
+                                const int *const *ordered_read_ids, const uint8_t *const *is_skipped, lcd_clean_vars_t *outs, int *const *cur_to_merged,
+                                int **const *region_to_merged);
+/* sort_noisy_regs (src/collect_var.c:2745-2769), host code: the order in which collect_var_main processes the chunk's noisy regions -- by label, then by
+ * end - start, as that function's exchange sort leaves them (NOT stable: regions with equal keys can change places).  order_out[i] = index of the i-th region. */
+int lcd_sort_noisy_regs(const lcd_noisy_iv_t *regs, int n, int *order_out);
 
 #ifdef __cplusplus
 }

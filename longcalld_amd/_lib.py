@@ -99,6 +99,13 @@ class LcdCleanVars(C.Structure):
                 ("qual_upload_bytes", C.c_uint64)]
 
 
+class LcdRegionVars(C.Structure):
+    """lcd_region_vars_t: one region's lcd_batch_region_vars output as lcd_merge_region_vars borrows it"""
+    _i32p = C.POINTER(C.c_int)
+    _fields_ = [("n_vars", C.c_int), ("vars", C.POINTER(LcdNoisyVar)), ("n_rows", C.c_int), ("row_read_ids", _i32p), ("prof_start", _i32p), ("prof_end", _i32p),
+                ("prof_alleles", _i32p)]
+
+
 _lib = None
 
 # every symbol include/lcd_hotpath.h declares (tests check the .so exports all of them)
@@ -110,6 +117,7 @@ EXPORTS = [
     "lcd_edlib_batch", "lcd_edlib_batch_hw", "lcd_wfa_batch", "lcd_wfa_arena_bytes", "lcd_poa_batch", "lcd_assign_hap_germline", "lcd_assign_hap_batch", "lcd_flip_variant_hap", "lcd_stitch_chunks", "lcd_call_opt_default", "lcd_make_variants", "lcd_free_variants", "lcd_format_vcf", "lcd_read_tags", "lcd_update_digars_from_msa1", "lcd_bam_load_region", "lcd_bam_load_region_indexed", "lcd_bam_reads_free", "lcd_fasta_fetch", "lcd_vcf_header", "lcd_io_last_error",
     "lcd_region_job_cost", "lcd_region_jobs_pack", "lcd_batch_add_packed", "lcd_rebalance_plan", "lcd_rccl_unique_id", "lcd_comm_create", "lcd_comm_destroy", "lcd_comm_info", "lcd_rebalance_exchange", "lcd_rebalance_last_error",
     "lcd_clean_opt_default", "lcd_chunk_clean_vars", "lcd_chunk_clean_vars_batch", "lcd_clean_vars_free", "lcd_clean_vars_hap_problem",
+    "lcd_merge_region_vars", "lcd_merge_region_vars_batch", "lcd_sort_noisy_regs",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -192,6 +200,10 @@ def load_library():
     lib.lcd_clean_vars_free.argtypes = [C.POINTER(LcdCleanVars)]
     lib.lcd_clean_vars_free.restype = None
     lib.lcd_clean_vars_hap_problem.argtypes = [C.POINTER(LcdCleanVars), C.c_int, i32p, u8p, i32p, i32p, C.POINTER(LcdHapProblem)]
+    lib.lcd_merge_region_vars.argtypes = [C.POINTER(LcdCleanVars), C.c_int, C.POINTER(LcdRegionVars), i32p, u8p, C.POINTER(LcdCleanVars), i32p, C.POINTER(i32p)]
+    lib.lcd_merge_region_vars_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(LcdCleanVars)), i32p, C.POINTER(C.POINTER(LcdRegionVars)), C.POINTER(i32p), C.POINTER(u8p),
+                                                C.POINTER(LcdCleanVars), C.POINTER(i32p), C.POINTER(C.POINTER(i32p))]
+    lib.lcd_sort_noisy_regs.argtypes = [C.POINTER(LcdNoisyIv), C.c_int, i32p]
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]
     lib.lcd_batch_digest.argtypes = [C.c_void_p]

@@ -891,3 +891,99 @@ def clean_vars_hap_problem(cv, ordered_read_ids, is_skipped, is_ont=0):
                 start_var_idx=out(p.start_var_idx, R, np.int32), end_var_idx=out(p.end_var_idx, R, np.int32), allele_off=out(p.allele_off, R + 1, np.int32),
                 alleles=out(p.alleles, na, np.int32), ordered_read_ids=out(p.ordered_read_ids, R, np.int32), is_skipped=out(p.is_skipped, R, np.uint8),
                 cr_read=out(p.cr_read, p.n_cr, np.int32))
+
+
+# ---------------- a pass's noisy-region variants merged into the chunk (lcd_merge_region_vars) ----------------
+def _clean_vars_struct(cv, keep):
+    """a clean_vars_dict -> LcdCleanVars over numpy copies (kept alive in `keep`)"""
+    def P(a, dt, ty):
+        a = np.ascontiguousarray(a, dt).reshape(-1)
+        if a.size == 0:
+            a = np.zeros(1, dt)
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(ty))
+    v = LcdCleanVars()
+    v.n_vars, v.n_reads, v.n_cr = int(cv["n_vars"]), int(cv["n_reads"]), len(cv["cr_read"])
+    v.pos = P(cv["pos"], np.int64, C.c_int64)
+    for k in ("var_type", "ref_len", "alt_len", "cate", "total_cov", "low_qual_cov", "alle_covs", "strand_alle_covs", "is_homopolymer_indel", "start_var_idx",
+              "end_var_idx", "alleles", "alt_qi", "cr_read"):
+        setattr(v, k, P(cv[k], np.int32, C.c_int))
+    v.alt_off = P(cv["alt_off"], np.uint64, C.c_uint64); v.allele_off = P(cv["allele_off"], np.uint64, C.c_uint64); v.alt_pool = P(cv["alt_pool"], np.uint8, C.c_uint8)
+    regs = np.asarray(cv["regs"], np.int64).reshape(-1, 3)
+    ra = (LcdNoisyIv * max(1, len(regs)))(*[LcdNoisyIv(int(x[0]), int(x[1]), int(x[2]), 0) for x in regs])
+    keep.append(ra)
+    v.n_regs, v.regs = len(regs), C.cast(ra, C.POINTER(LcdNoisyIv))
+    return v
+
+
+def _region_vars_array(regions, keep):
+    """RegionBatch.region_vars dicts -> (LcdRegionVars * n)"""
+    from ._lib import LcdRegionVars
+    arr = (LcdRegionVars * max(1, len(regions)))()
+    for k, g in enumerate(regions):
+        n, rows = int(g["n_vars"]), int(g.get("n_rows", len(g["row_read_ids"])))
+        va = (LcdNoisyVar * max(1, n))()
+        for i in range(max(n, 0)):
+            x = va[i]
+            x.pos, x.var_type, x.ref_len, x.alt_len, x.cate = int(g["pos"][i]), int(g["var_type"][i]), int(g["ref_len"][i]), int(g["alt_len"][i]), int(g["cate"][i])
+            x.is_homopolymer_indel, x.total_cov = int(g["is_homopolymer_indel"][i]), int(g["total_cov"][i])
+            x.alle_covs[0], x.alle_covs[1] = int(g["alle_covs"][i][0]), int(g["alle_covs"][i][1])
+            a = np.ascontiguousarray(g["alt_seqs"][i], np.uint8)
+            if a.size:
+                keep.append(a)
+                x.alt_seq = _p8(a)
+        cols = [np.ascontiguousarray(g[name], np.int32).reshape(-1) for name in ("row_read_ids", "prof_start", "prof_end", "prof_alleles")]
+        cols = [c if c.size else np.zeros(1, np.int32) for c in cols]
+        keep += [va] + cols
+        arr[k].n_vars, arr[k].vars, arr[k].n_rows = n, C.cast(va, C.POINTER(LcdNoisyVar)), rows
+        arr[k].row_read_ids, arr[k].prof_start, arr[k].prof_end, arr[k].prof_alleles = [c.ctypes.data_as(i32p) for c in cols]
+    keep.append(arr)
+    return arr
+
+
+def merge_region_vars_batch(cvs, regions, ordered, skipped, single=False, n_regions=None):
+    """lcd_merge_region_vars_batch: cvs[i] = clean_vars_dict, regions[i] = list of RegionBatch.region_vars dicts in processing order, ordered[i] / skipped[i] = the
+    chunk's ordered_read_ids / is_skipped -> list of (clean_vars_dict, cur_to_merged, [region_to_merged per region]); single=True: one chunk through
+    lcd_merge_region_vars.  n_regions overrides the region counts handed to the library (tests of the argument checks)."""
+    from ._lib import LcdRegionVars
+    lib = load_library()
+    n = len(cvs)
+    keep = []
+    cur = [_clean_vars_struct(cv, keep) for cv in cvs]
+    regs = [_region_vars_array(r, keep) for r in regions]
+    nreg = [len(r) for r in regions] if n_regions is None else list(n_regions)
+    ords = [np.ascontiguousarray(o, np.int32) if len(o) else np.zeros(1, np.int32) for o in ordered]
+    skips = [np.ascontiguousarray(s_, np.uint8) if len(s_) else np.zeros(1, np.uint8) for s_ in skipped]
+    c2m = [np.full(max(1, cv["n_vars"]), -1, np.int32) for cv in cvs]
+    r2m = [[np.full(max(1, int(g["n_vars"])), -1, np.int32) for g in r] for r in regions]
+    r2m_p = [(i32p * max(1, len(r)))(*[a.ctypes.data_as(i32p) for a in r]) for r in r2m]
+    outs = (LcdCleanVars * n)()
+    if single:
+        check(lib.lcd_merge_region_vars(C.byref(cur[0]), nreg[0], regs[0], ords[0].ctypes.data_as(i32p), _p8(skips[0]), C.byref(outs[0]), c2m[0].ctypes.data_as(i32p),
+                                        r2m_p[0]), lib)
+    else:
+        check(lib.lcd_merge_region_vars_batch(n, (C.POINTER(LcdCleanVars) * n)(*[C.pointer(c) for c in cur]), (C.c_int * n)(*nreg),
+                                              (C.POINTER(LcdRegionVars) * n)(*[C.cast(r, C.POINTER(LcdRegionVars)) for r in regs]),
+                                              (i32p * n)(*[o.ctypes.data_as(i32p) for o in ords]), (u8p * n)(*[_p8(s_) for s_ in skips]), outs,
+                                              (i32p * n)(*[a.ctypes.data_as(i32p) for a in c2m]), (C.POINTER(i32p) * n)(*[C.cast(p, C.POINTER(i32p)) for p in r2m_p])), lib)
+    res = []
+    for i in range(n):
+        d = clean_vars_dict(outs[i])
+        lib.lcd_clean_vars_free(C.byref(outs[i]))
+        res.append((d, c2m[i][:cvs[i]["n_vars"]].copy(), [a[:max(0, int(g["n_vars"]))].copy() for a, g in zip(r2m[i], regions[i])]))
+    return res
+
+
+def merge_region_vars(cv, regions, ordered, skipped, n_regions=None):
+    """lcd_merge_region_vars on one chunk -> (clean_vars_dict, cur_to_merged, [region_to_merged per region])"""
+    return merge_region_vars_batch([cv], [regions], [ordered], [skipped], single=True, n_regions=None if n_regions is None else [n_regions])[0]
+
+
+def sort_noisy_regs(regs):
+    """lcd_sort_noisy_regs (sort_noisy_regs, src/collect_var.c:2745): regs (n, 3) start / end / label -> the processing order (indices)"""
+    lib = load_library()
+    regs = np.asarray(regs, np.int64).reshape(-1, 3)
+    arr = (LcdNoisyIv * max(1, len(regs)))(*[LcdNoisyIv(int(x[0]), int(x[1]), int(x[2]), 0) for x in regs])
+    order = np.zeros(max(1, len(regs)), np.int32)
+    check(lib.lcd_sort_noisy_regs(arr, len(regs), order.ctypes.data_as(i32p)), lib)
+    return order[:len(regs)].copy()

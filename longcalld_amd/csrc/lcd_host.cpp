@@ -4128,4 +4128,263 @@ int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------------
+// merge_var_profile (src/collect_var.c:1298-1387) for every region of a pass: table walk on the host, profile on the device (merge_vars_kernel.hip)
+} // extern "C"
+namespace {
+struct MvVar { int64_t pos; int type, ref_len, alt_len; const uint8_t *alt; int origin /* -1: the chunk's table, else the region */, idx; };
+// exact_comp_var_site (:1878): position key, type, ref_len, alt_len, alt bases of X / INS
+int mv_cmp(const MvVar &a, const MvVar &b) {
+    const int64_t ka = a.type == 8 ? a.pos : a.pos - 1, kb = b.type == 8 ? b.pos : b.pos - 1;
+    if (ka != kb) return ka < kb ? -1 : 1;
+    if (a.type != b.type) return a.type < b.type ? -1 : 1;
+    if (a.ref_len != b.ref_len) return a.ref_len < b.ref_len ? -1 : 1;
+    if (a.alt_len != b.alt_len) return a.alt_len < b.alt_len ? -1 : 1;
+    if ((a.type == 8 || a.type == 1) && a.alt_len > 0) return memcmp(a.alt, b.alt, (size_t)a.alt_len);
+    return 0;
+}
+struct MvChunk {                       // one chunk of a call between the host walk and the device profile
+    std::vector<int> a2m; std::vector<std::vector<int>> b2m; std::vector<char> active;
+    uint64_t o_a2m = 0, o_al = 0, o_qi = 0; std::vector<uint64_t> o_b2m, o_prof;
+    int read0 = 0;
+};
+// validation + the fold of two-pointer walks; fills every per-variant array of *out and the maps.  No device call.
+int mv_walk(const char *who, const lcd_clean_vars_t *cur, int n_regions, const lcd_region_vars_t *regions, const int *ordered, const uint8_t *is_skipped,
+            lcd_clean_vars_t *out, MvChunk &mc) {
+    const std::string W(who);
+    if (!cur || !out) return set_err(-4, W + ": NULL argument");
+    if (n_regions < 0) return set_err(-4, W + ": n_regions < 0");
+    if (n_regions > 0 && !regions) return set_err(-4, W + ": no regions");
+    const int V = cur->n_vars, R = cur->n_reads;
+    if (V < 0 || R < 0) return set_err(-4, W + ": negative n_vars / n_reads");
+    if (R > 0 && (!ordered || !is_skipped || !cur->start_var_idx || !cur->end_var_idx || !cur->allele_off)) return set_err(-4, W + ": no ordered_read_ids / is_skipped / profile");
+    if (V > 0 && (!cur->pos || !cur->var_type || !cur->ref_len || !cur->alt_len || !cur->cate || !cur->total_cov || !cur->low_qual_cov || !cur->alle_covs ||
+                  !cur->strand_alle_covs || !cur->alt_off || !cur->is_homopolymer_indel)) return set_err(-4, W + ": incomplete variant table");
+    for (int i = 0; i < V; ++i) {
+        const uint64_t nb = cur->alt_off[i + 1] - cur->alt_off[i];
+        if (cur->alt_off[i + 1] < cur->alt_off[i] || cur->alt_len[i] < 0 || ((cur->var_type[i] == 8 || cur->var_type[i] == 1) && nb != (uint64_t)cur->alt_len[i]))
+            return set_err(-4, W + ": alt_off does not match alt_len at variant " + std::to_string(i));
+    }
+    mc.active.assign(R + 1, 0);
+    for (int i = 0; i < R; ++i) {
+        const int r = ordered[i];
+        if (r < 0 || r >= R) return set_err(-4, W + ": ordered_read_ids out of range");
+        if (!is_skipped[r]) mc.active[r] = 1;
+    }
+    for (int r = 0; r < R; ++r) {
+        const int s = cur->start_var_idx[r], e = cur->end_var_idx[r];
+        const uint64_t nc = cur->allele_off[r + 1] - cur->allele_off[r];
+        if (cur->allele_off[r + 1] < cur->allele_off[r]) return set_err(-4, W + ": allele_off decreases at read " + std::to_string(r));
+        if (s < 0) continue;
+        if (e < s || e >= V || nc != (uint64_t)(e - s + 1)) return set_err(-4, W + ": profile span of read " + std::to_string(r) + " outside [0, n_vars) or not matching allele_off");
+        if (!cur->alleles || !cur->alt_qi) return set_err(-4, W + ": no profile cells");
+    }
+    std::vector<int> seen(R + 1, -1);
+    for (int k = 0; k < n_regions; ++k) {
+        const lcd_region_vars_t &g = regions[k];
+        if (g.n_vars <= 0) continue;
+        if (!g.vars || g.n_rows < 0 || (g.n_rows > 0 && (!g.row_read_ids || !g.prof_start || !g.prof_end || !g.prof_alleles))) return set_err(-4, W + ": region " + std::to_string(k) + " incomplete");
+        for (int j = 0; j < g.n_vars; ++j)
+            if (g.vars[j].alt_len < 0 || ((g.vars[j].var_type == 8 || g.vars[j].var_type == 1) && g.vars[j].alt_len > 0 && !g.vars[j].alt_seq))
+                return set_err(-4, W + ": region " + std::to_string(k) + " variant " + std::to_string(j) + " has no alt_seq");
+        for (int q = 0; q < g.n_rows; ++q) {
+            const int r = g.row_read_ids[q];
+            if (r < 0 || r >= R) return set_err(-4, W + ": region " + std::to_string(k) + " row " + std::to_string(q) + ": read id outside [0, n_reads)");
+            if (seen[r] == k) return set_err(-4, W + ": region " + std::to_string(k) + ": read " + std::to_string(r) + " twice");
+            seen[r] = k;
+            if (g.prof_start[q] >= 0 && g.prof_end[q] >= g.prof_start[q] && g.prof_end[q] >= g.n_vars)
+                return set_err(-4, W + ": region " + std::to_string(k) + " row " + std::to_string(q) + ": span outside [0, n_vars)");
+        }
+    }
+    // the fold
+    std::vector<MvVar> tab(V), nxt;
+    for (int i = 0; i < V; ++i) tab[i] = {cur->pos[i], cur->var_type[i], cur->ref_len[i], cur->alt_len[i], cur->alt_pool ? cur->alt_pool + cur->alt_off[i] : nullptr, -1, i};
+    for (int k = 0; k < n_regions; ++k) {
+        const lcd_region_vars_t &g = regions[k];
+        if (g.n_vars <= 0) continue;
+        nxt.clear(); nxt.reserve(tab.size() + g.n_vars);
+        size_t i = 0; int j = 0;
+        auto reg_var = [&](int q) { const lcd_noisy_var_t &v = g.vars[q]; return MvVar{v.pos, v.var_type, v.ref_len, v.alt_len, v.alt_seq, k, q}; };
+        while (i < tab.size() && j < g.n_vars) {
+            const MvVar b = reg_var(j);
+            const int c = mv_cmp(tab[i], b);
+            if (c < 0) nxt.push_back(tab[i++]);
+            else if (c > 0) { nxt.push_back(b); ++j; }
+            else { nxt.push_back(tab[i++]); ++j; }   // equal: the table's entry stays, the region's is dropped
+        }
+        for (; i < tab.size(); ++i) nxt.push_back(tab[i]);
+        for (; j < g.n_vars; ++j) nxt.push_back(reg_var(j));
+        tab.swap(nxt);
+    }
+    const int M = (int)tab.size();
+    mc.a2m.assign(V + 1, -1); mc.b2m.resize(n_regions);
+    for (int k = 0; k < n_regions; ++k) mc.b2m[k].assign(regions[k].n_vars > 0 ? regions[k].n_vars : 0, -1);
+    out->n_vars = M;
+    out->pos = (int64_t *)malloc((M + 1) * 8ull); out->var_type = (int *)malloc((M + 1) * 4ull); out->ref_len = (int *)malloc((M + 1) * 4ull);
+    out->alt_len = (int *)malloc((M + 1) * 4ull); out->cate = (int *)malloc((M + 1) * 4ull); out->total_cov = (int *)malloc((M + 1) * 4ull);
+    out->low_qual_cov = (int *)calloc(M + 1, 4); out->alle_covs = (int *)malloc((M + 1) * 8ull); out->strand_alle_covs = (int *)calloc(M + 1, 16);
+    out->alt_off = (uint64_t *)malloc((M + 1) * 8ull); out->is_homopolymer_indel = (int *)calloc(M + 1, 4);
+    uint64_t na = 0;
+    for (int m = 0; m < M; ++m) { const MvVar &t = tab[m]; if (t.origin < 0) na += cur->alt_off[t.idx + 1] - cur->alt_off[t.idx]; else if (t.type == 8 || t.type == 1) na += (uint64_t)t.alt_len; }
+    out->alt_pool = (uint8_t *)malloc(na + 1);
+    na = 0;
+    for (int m = 0; m < M; ++m) {
+        const MvVar &t = tab[m];
+        out->pos[m] = t.pos; out->var_type[m] = t.type; out->ref_len[m] = t.ref_len; out->alt_len[m] = t.alt_len; out->alt_off[m] = na;
+        if (t.origin < 0) {
+            const int i = t.idx; mc.a2m[i] = m;
+            out->cate[m] = cur->cate[i]; out->total_cov[m] = cur->total_cov[i]; out->low_qual_cov[m] = cur->low_qual_cov[i];
+            out->alle_covs[2 * m] = cur->alle_covs[2 * i]; out->alle_covs[2 * m + 1] = cur->alle_covs[2 * i + 1];
+            memcpy(out->strand_alle_covs + 4 * m, cur->strand_alle_covs + 4 * i, 16); out->is_homopolymer_indel[m] = cur->is_homopolymer_indel[i];
+            const uint64_t nb = cur->alt_off[i + 1] - cur->alt_off[i];
+            if (nb) memcpy(out->alt_pool + na, cur->alt_pool + cur->alt_off[i], nb);
+            na += nb;
+        } else {
+            const lcd_noisy_var_t &v = regions[t.origin].vars[t.idx]; mc.b2m[t.origin][t.idx] = m;
+            out->cate[m] = v.cate; out->total_cov[m] = v.total_cov; out->alle_covs[2 * m] = v.alle_covs[0]; out->alle_covs[2 * m + 1] = v.alle_covs[1];
+            out->is_homopolymer_indel[m] = v.is_homopolymer_indel;
+            if ((t.type == 8 || t.type == 1) && t.alt_len > 0) { memcpy(out->alt_pool + na, v.alt_seq, (size_t)t.alt_len); na += (uint64_t)t.alt_len; }
+        }
+    }
+    out->alt_off[M] = na;
+    out->n_regs = cur->n_regs > 0 ? cur->n_regs : 0;
+    out->regs = (lcd_noisy_iv_t *)calloc(out->n_regs + 1, sizeof(lcd_noisy_iv_t));
+    if (out->n_regs) memcpy(out->regs, cur->regs, out->n_regs * sizeof(lcd_noisy_iv_t));
+    out->n_reads = R; out->qual_upload_bytes = 0;
+    return 0;
+}
+} // namespace
+extern "C" {
+int lcd_merge_region_vars_batch(int n_chunks, const lcd_clean_vars_t *const *cur, const int *n_regions, const lcd_region_vars_t *const *regions,
+                                const int *const *ordered_read_ids, const uint8_t *const *is_skipped, lcd_clean_vars_t *outs, int *const *cur_to_merged,
+                                int **const *region_to_merged) {
+    if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, "lcd_merge_region_vars_batch: n_chunks < 0") : 0;
+    if (!cur || !n_regions || !regions || !ordered_read_ids || !is_skipped || !outs) return set_err(-4, "lcd_merge_region_vars_batch: NULL argument");
+    memset(outs, 0, sizeof(lcd_clean_vars_t) * (size_t)n_chunks);
+    auto fail = [&](int rc) { const std::string m = g_err; for (int c = 0; c < n_chunks; ++c) lcd_clean_vars_free(outs + c); g_err = m; return rc; };
+    std::vector<MvChunk> mcs(n_chunks);
+    // 1. host: validation and the table walks of every chunk (nothing is launched on malformed input)
+    for (int c = 0; c < n_chunks; ++c) {
+        const int rc = mv_walk("lcd_merge_region_vars", cur[c], n_regions[c], regions[c], ordered_read_ids[c], is_skipped[c], outs + c, mcs[c]);
+        if (rc) { if (n_chunks > 1) g_err = "chunk " + std::to_string(c) + ": " + g_err; return fail(rc); }
+    }
+    // 2. one staging block: maps, source cells, the source table, the reads' new start / end (min / max identities) and the flag
+    std::vector<uint8_t> hb(16, 0);   // (offset 0 stays unused: MvSrc.alt_qi == 0 means "no alt_qi")
+    auto put = [&](const void *p, size_t bytes) { size_t o = lcd_align_up(hb.size(), 16); hb.resize(o + bytes); if (p && bytes) memcpy(hb.data() + o, p, bytes); return (uint64_t)o; };
+    std::vector<MvSrc> srcs;
+    int G = 0;
+    for (int c = 0; c < n_chunks; ++c) { mcs[c].read0 = G; G += cur[c]->n_reads; }
+    std::vector<int> lo(G + 1, 0x7fffffff), hi(G + 1, -1);   // per read: bounds of its merged span (exact for the current profile, the region's extent for a row)
+    unsigned long long n_cells = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        MvChunk &mc = mcs[c]; const lcd_clean_vars_t &cv = *cur[c];
+        const int R = cv.n_reads, V = cv.n_vars; const uint64_t NA = R ? cv.allele_off[R] : 0;
+        mc.o_a2m = put(mc.a2m.data(), (size_t)V * 4); mc.o_al = put(cv.alleles, NA * 4); mc.o_qi = put(cv.alt_qi, NA * 4);
+        for (int r = 0; r < R; ++r) {
+            const int s = cv.start_var_idx[r], e = cv.end_var_idx[r];
+            if (!mc.active[r] || s < 0) continue;
+            srcs.push_back({mc.o_a2m, mc.o_al + cv.allele_off[r] * 4, mc.o_qi + cv.allele_off[r] * 4, c, mc.read0 + r, s, e - s + 1, n_cells});
+            n_cells += (unsigned long long)(e - s + 1);
+            lo[mc.read0 + r] = mc.a2m[s]; hi[mc.read0 + r] = mc.a2m[e];
+        }
+        mc.o_b2m.assign(n_regions[c], 0); mc.o_prof.assign(n_regions[c], 0);
+        for (int k = 0; k < n_regions[c]; ++k) {
+            const lcd_region_vars_t &g = regions[c][k];
+            if (g.n_vars <= 0) continue;
+            int mn = 0x7fffffff, mx = -1;
+            for (int m : mc.b2m[k]) if (m >= 0) { mn = std::min(mn, m); mx = std::max(mx, m); }
+            if (mx < 0 || g.n_rows <= 0) continue;   // every variant dropped: no cell of this region moves
+            mc.o_b2m[k] = put(mc.b2m[k].data(), (size_t)g.n_vars * 4); mc.o_prof[k] = put(g.prof_alleles, (size_t)g.n_rows * g.n_vars * 4);
+            for (int q = 0; q < g.n_rows; ++q) {
+                const int r = g.row_read_ids[q], s = g.prof_start[q], e = g.prof_end[q];
+                if (!mc.active[r] || s < 0 || e < s) continue;
+                srcs.push_back({mc.o_b2m[k], mc.o_prof[k] + ((uint64_t)q * g.n_vars + s) * 4, 0, c, mc.read0 + r, s, e - s + 1, n_cells});
+                n_cells += (unsigned long long)(e - s + 1);
+                lo[mc.read0 + r] = std::min(lo[mc.read0 + r], mn); hi[mc.read0 + r] = std::max(hi[mc.read0 + r], mx);
+            }
+        }
+    }
+    unsigned long long cap = 0;
+    for (int g = 0; g < G; ++g) if (hi[g] >= lo[g]) cap += (unsigned long long)(hi[g] - lo[g] + 1);
+    const int S = (int)srcs.size(), NB = (G + 255) / 256;
+    std::vector<int> se;                              // downloaded: start[G], end[G]
+    std::vector<uint8_t> dl;
+    const unsigned long long *off = nullptr; const int *d_al = nullptr, *d_qi = nullptr;
+    std::vector<unsigned long long> zero_off(G + 1, 0);
+    if (S > 0) {
+        if (ensure_init()) return fail(-1);
+        const uint64_t o_src = put(nullptr, (size_t)S * sizeof(MvSrc));
+        const uint64_t o_start = put(nullptr, (size_t)G * 4), o_end = put(nullptr, (size_t)G * 4), o_flag = put(nullptr, 16);
+        for (int g = 0; g < G; ++g) { ((int *)(hb.data() + o_start))[g] = 0x7fffffff; ((int *)(hb.data() + o_end))[g] = -1; }
+        const uint64_t up_bytes = lcd_align_up(hb.size(), 16);
+        const uint64_t o_off = up_bytes, o_bsum = o_off + lcd_align_up((uint64_t)(G + 1) * 8, 16), o_cells = o_bsum + lcd_align_up((uint64_t)NB * 8 + 16, 16);
+        const uint64_t total = o_cells + 2 * cap * 4 + 64;
+        StreamGuard st; if (st.create()) return fail(-10);
+        DevBuf d; if (d.ensure(total, 63)) return fail(-11);          // the call's one allocation
+        const uint64_t B = d.addr();
+        for (MvSrc &s : srcs) { s.map += B; s.alleles += B; if (s.alt_qi) s.alt_qi += B; }
+        memcpy(hb.data() + o_src, srcs.data(), (size_t)S * sizeof(MvSrc));
+#define MVCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(-10, std::string(#x) + ": " + hipGetErrorString(e_)); return fail(-10); } } while (0)
+        MVCHK(hipMemcpyAsync(d.p, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
+        const MvSrc *SS = (const MvSrc *)(uintptr_t)(B + o_src);
+        int *d_start = (int *)(uintptr_t)(B + o_start), *d_end = (int *)(uintptr_t)(B + o_end), *d_flag = (int *)(uintptr_t)(B + o_flag);
+        unsigned long long *d_off = (unsigned long long *)(uintptr_t)(B + o_off), *d_bsum = (unsigned long long *)(uintptr_t)(B + o_bsum);
+        int *cells = (int *)(uintptr_t)(B + o_cells);
+        lcd_launch_mv_span(SS, S, d_start, d_end, st);
+        lcd_launch_mv_scan(d_start, d_end, G, d_off, d_bsum, st);
+        lcd_launch_mv_fill(cells, 2 * cap, st);
+        lcd_launch_mv_scatter(SS, S, n_cells, d_start, d_off, cells, cells + cap, cap, d_flag, st);
+        MVCHK(hipGetLastError());
+        dl.resize(o_cells + 2 * cap * 4 - o_start);
+        MVCHK(hipMemcpyAsync(dl.data(), (const uint8_t *)d.p + o_start, dl.size(), hipMemcpyDeviceToHost, st));
+        MVCHK(hipStreamSynchronize(st));
+#undef MVCHK
+        auto at = [&](uint64_t o) { return dl.data() + (o - o_start); };   // the downloaded copy of device offset o (>= o_start)
+        se.assign((const int *)at(o_start), (const int *)at(o_start) + G); se.insert(se.end(), (const int *)at(o_end), (const int *)at(o_end) + G);
+        off = (const unsigned long long *)at(o_off); d_al = (const int *)at(o_cells); d_qi = d_al + cap;
+        if (*(const int *)at(o_flag) || off[G] > cap) { set_err(-24, "lcd_merge_region_vars: cell capacity exceeded (" + std::to_string(off[G]) + " cells, " + std::to_string(cap) + " allocated)"); return fail(-24); }
+    } else {
+        se.assign(G, -1); se.insert(se.end(), G, -2); off = zero_off.data();
+    }
+    // 3. per chunk: spans, CSR, cells, the interval index; the maps
+    for (int c = 0; c < n_chunks; ++c) {
+        const MvChunk &mc = mcs[c]; lcd_clean_vars_t *out = outs + c; const int R = out->n_reads, g0 = mc.read0;
+        out->start_var_idx = (int *)malloc((R + 1) * 4ull); out->end_var_idx = (int *)malloc((R + 1) * 4ull); out->allele_off = (uint64_t *)malloc((R + 1) * 8ull);
+        for (int r = 0; r < R; ++r) { out->start_var_idx[r] = se[g0 + r]; out->end_var_idx[r] = se[G + g0 + r]; out->allele_off[r] = off[g0 + r] - off[g0]; }
+        const uint64_t tot = off[g0 + R] - off[g0];
+        out->allele_off[R] = tot;
+        out->alleles = (int *)malloc((tot + 1) * 4); out->alt_qi = (int *)malloc((tot + 1) * 4);
+        if (tot) { memcpy(out->alleles, d_al + off[g0], tot * 4); memcpy(out->alt_qi, d_qi + off[g0], tot * 4); }
+        std::vector<NIv> rv;   // read_var_cr: cr_add(start, end + 1, read) in ordered_read_ids order, cr_index
+        for (int i = 0; i < R; ++i) { const int r = ordered_read_ids[c][i]; if (is_skipped[c][r]) continue; if (out->start_var_idx[r] >= 0 && out->end_var_idx[r] >= 0) niv_add(rv, out->start_var_idx[r], out->end_var_idx[r] + 1, r); }
+        niv_index(rv);
+        out->n_cr = (int)rv.size();
+        out->cr_read = (int *)malloc((rv.size() + 1) * 4);
+        for (size_t i = 0; i < rv.size(); ++i) out->cr_read[i] = rv[i].label;
+        if (cur_to_merged && cur_to_merged[c] && cur[c]->n_vars > 0) memcpy(cur_to_merged[c], mc.a2m.data(), (size_t)cur[c]->n_vars * 4);
+        if (region_to_merged && region_to_merged[c])
+            for (int k = 0; k < n_regions[c]; ++k) if (region_to_merged[c][k] && !mc.b2m[k].empty()) memcpy(region_to_merged[c][k], mc.b2m[k].data(), mc.b2m[k].size() * 4);
+    }
+    return 0;
+}
+int lcd_merge_region_vars(const lcd_clean_vars_t *cur, int n_regions, const lcd_region_vars_t *regions, const int *ordered_read_ids, const uint8_t *is_skipped,
+                          lcd_clean_vars_t *out, int *cur_to_merged, int **region_to_merged) {
+    if (!out) return set_err(-4, "lcd_merge_region_vars: NULL argument");
+    return lcd_merge_region_vars_batch(1, &cur, &n_regions, &regions, &ordered_read_ids, &is_skipped, out, cur_to_merged ? &cur_to_merged : nullptr,
+                                       region_to_merged ? &region_to_merged : nullptr);
+}
+// sort_noisy_regs (src/collect_var.c:2745-2769): exchange sort by label, then by end - start, with that function's swap sequence (not stable)
+int lcd_sort_noisy_regs(const lcd_noisy_iv_t *regs, int n, int *order_out) {
+    if (n < 0 || (n > 0 && (!regs || !order_out))) return set_err(-4, "lcd_sort_noisy_regs: bad arguments");
+    for (int i = 0; i < n; ++i) order_out[i] = i;
+    auto after = [&](int a, int b) { // region a belongs behind region b
+        if (regs[a].label != regs[b].label) return regs[a].label > regs[b].label;
+        return (int)(regs[a].end - regs[a].start) > (int)(regs[b].end - regs[b].start);
+    };
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (after(order_out[i], order_out[j])) std::swap(order_out[i], order_out[j]);
+    return 0;
+}
+
 } // extern "C"

@@ -46,3 +46,10 @@ void lcd_launch_cv_ratio(const CvRead *reads, const int *order, int n, const IvR
 void lcd_launch_cv_profile(int pass, const CvRead *reads, const int *order, int n, const DigarRec *dg, const CvSite *vars, const int *cate, int n_vars,
                            const IvRec *ivs, int *start, int *end, const unsigned long long *allele_off, int *alleles, int *alt_qi, CvOpt opt, hipStream_t st);
 void lcd_launch_cv_alt(const CvSite *vars, const CvRead *reads, const unsigned long long *alt_off, int n_vars, unsigned char *pool, hipStream_t st);
+// merge_vars_kernel.hip: the read x variant profile after a pass's region variants are folded into the chunk (all chunks of a call in one set of launches)
+void lcd_launch_mv_span(const MvSrc *srcs, int n_src, int *start, int *end, hipStream_t st);
+// cells per read -> off[0 .. n_reads] (off[n_reads] = the total); reads without a cell get (-1, -2); bsum: one entry per 256 reads
+void lcd_launch_mv_scan(int *start, int *end, int n_reads, unsigned long long *off, unsigned long long *bsum, hipStream_t st);
+void lcd_launch_mv_fill(int *cells, unsigned long long n, hipStream_t st);
+void lcd_launch_mv_scatter(const MvSrc *srcs, int n_src, unsigned long long n_cells, const int *start, const unsigned long long *off, int *alleles, int *alt_qi,
+                           unsigned long long cap, int *flag, hipStream_t st);

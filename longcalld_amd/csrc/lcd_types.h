@@ -339,3 +339,9 @@ struct CvRead { uint64_t dig, seq, qual; long long beg, end; int n_digar, qlen, 
 struct CvSite { long long pos; int var_type, ref_len, alt_len, read, qi, pad; };
 struct CvCov { int total, low, alle[2], strand[4]; };   // total_cov, low_qual_cov, alle_covs, strand_to_alle_covs[0][0..1], [1][0..1]
 struct CvOpt { int min_dp, min_alt_dp, min_bq, min_sv_len, max_xgaps, pad; double min_af, max_af; long long reg_beg, reg_end, ref_beg, ref_end; };
+
+// ---- merge of noisy-region variants into the chunk's read x variant profile (merge_vars_kernel.hip) ----
+// one source of cells: a read's current profile span, or one row of a region's profile.  read: index into the call's read table (all chunks of a batch back to
+// back); map / alleles / alt_qi: absolute device addresses of the source's index map (old or region variant index -> merged index, -1 = dropped), of its n
+// alleles and of its n alt_qi values (0: every cell gets -1); first: variant index of the source's first cell; cell0: the source's first lane in the scatter
+struct MvSrc { uint64_t map, alleles, alt_qi; int chunk, read, first, n; unsigned long long cell0; };
