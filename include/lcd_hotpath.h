@@ -641,6 +641,85 @@ int lcd_merge_region_vars_batch(int n_chunks, const lcd_clean_vars_t *const *cur
  * end - start, as that function's exchange sort leaves them (NOT stable: regions with equal keys can change places).  order_out[i] = index of the i-th region. */
 int lcd_sort_noisy_regs(const lcd_noisy_iv_t *regs, int n, int *order_out);
 
+/* ---- the noisy-region rounds of collect_var_main (src/collect_var.c:2946-2977) on device-resident chunks (germline) ----
+ * lcd_chunk_plan_pass: the plan of one pass -- per region of regs[] (lcd_clean_vars_t.regs) whose done[i] is 0 what collect_noisy_vars1 (:2650-2663) and
+ * collect_noisy_read_info (src/align.c:1377-1461) work out before the alignment, computed on the chunk's reads in HBM (plan_kernel.hip):
+ *   beg / end    [regs[i].start, regs[i].end] clamped to [ref_beg, ref_end] (collect_reg_ref_bseq, src/seq.c:415-426);
+ *   status       LCD_PLAN_DONE_BEFORE (done[i] != 0) | LCD_PLAN_SKIP_LONG (clamped length > max_noisy_reg_len: the reference returns 0, the region is done without a
+ *                variant) | LCD_PLAN_SKIP_DEEP (more than max_noisy_reg_cov reads: the same) | LCD_PLAN_NO_READS (collect_noisy_reg_aln_strs returns 0 for
+ *                n <= 0, src/align.c:1763: not done, tried again in the next pass) | LCD_PLAN_SUBMIT;
+ *   read list    collect_noisy_reg_reads1 (:1047-1061): every read of ordered_read_ids, in that order, that is not skipped (is_skipped[r], or the chunk's own status
+ *                of the read is not 0) and satisfies !(read.beg > end || read.end <= beg) -- the reference's asymmetric test on the clamped interval;
+ *   slices       per (region, read) pair read_beg / read_end / cover, as lcd_chunk_region_slices gives them for the pair with noisy_reg_flank_len.
+ * read_off (n_regs + 1 entries) is the CSR into read_ids / read_beg / read_end / cover; only submitted regions have pairs.  Every array of *out is malloc()'d
+ * (lcd_pass_plan_free).  The first plan of a chunk uploads its reads' beg / end / status / digar slots once (40 bytes per read, a blocking copy); after that a call
+ * uploads the region tables, ordered_read_ids and is_skipped in one staged copy, allocates the pair area once (sized after the count launch), downloads once and
+ * synchronises twice: after the counts and at the end.  No digar and no base crosses PCIe (lcd_copy_counters is unchanged).  The batch form takes all regions of
+ * all chunks (one device) in one grid on one stream; every argument is an array of n_chunks; results == n_chunks single calls.  Malformed input -- n_regs < 0,
+ * ref_end < ref_beg, a NULL chunk, an ordered_read_ids entry outside [0, n_reads) -- returns < 0 (lcd_last_error()) before any device call. */
+typedef struct lcd_pass_opt_t { int max_noisy_reg_len, max_noisy_reg_cov, noisy_reg_flank_len; } lcd_pass_opt_t;
+void lcd_pass_opt_default(lcd_pass_opt_t *o);   /* 50000, 1000, 10 (src/call_var_main.h:36-42) */
+#define LCD_PLAN_DONE_BEFORE 0
+#define LCD_PLAN_SKIP_LONG 1
+#define LCD_PLAN_SKIP_DEEP 2
+#define LCD_PLAN_NO_READS 3
+#define LCD_PLAN_SUBMIT 4
+typedef struct lcd_pass_plan_t {
+    int n_regs; int *status; int64_t *beg, *end;    /* per region */
+    uint64_t *read_off;                             /* n_regs + 1 */
+    int *read_ids, *read_beg, *read_end, *cover;    /* per pair */
+} lcd_pass_plan_t;
+int lcd_chunk_plan_pass(const lcd_chunk_t *c, const lcd_pass_opt_t *opt, int n_regs, const lcd_noisy_iv_t *regs, const int *done, const int *ordered_read_ids,
+                        const uint8_t *is_skipped, int64_t ref_beg, int64_t ref_end, lcd_pass_plan_t *out);
+int lcd_chunk_plan_pass_batch(int n_chunks, const lcd_chunk_t *const *chunks, const lcd_pass_opt_t *opt, const int *n_regs, const lcd_noisy_iv_t *const *regs,
+                              const int *const *done, const int *const *ordered_read_ids, const uint8_t *const *is_skipped, const int64_t *ref_beg,
+                              const int64_t *ref_end, lcd_pass_plan_t *outs);
+void lcd_pass_plan_free(lcd_pass_plan_t *p);
+/* n_cons of a region of a downloaded batch (0: collect_noisy_reg_aln_strs could not resolve it; also with opt.collect_noisy_vars == 2, where
+ * lcd_batch_region_result is not available): what tells "no consensus" from "resolved without a variant" for the done[] rule of the loop */
+int lcd_batch_region_n_cons(lcd_batch_t *b, int region);
+/* every LCD_PLAN_SUBMIT region of a plan into a batch through lcd_batch_add_region_from_chunk_dev, in region order: reference bases ref_seq[beg - ref_beg ..
+ * end - ref_beg] (codes; ref_seq[0] = position ref_beg), haps / phase_sets (chunk->haps / phase_sets, indexed by read id) gathered by the region's read ids.
+ * region_idx_out[i] (plan->n_regs entries, may be NULL) = the batch index of region i, or -1.  Returns the number of regions added or < 0.  Results ==
+ * calling lcd_batch_add_region_from_chunk_dev region by region with the same arrays. */
+int lcd_batch_add_planned(lcd_batch_t *b, const lcd_chunk_t *c, const lcd_pass_plan_t *plan, const int *haps, const int64_t *phase_sets, const uint8_t *ref_seq,
+                          int64_t ref_beg, int *region_idx_out);
+/* K5's state (the in/out arrays of lcd_hap_problem_t) on its own, and its way across a merge (host code).  lcd_hap_state_init: malloc()'d arrays with the values
+ * the first K5 call starts from (haps 0, phase sets -1, counts 0, var_phase_set -1, hap_to_cons_alle -1, hap_to_alle_profile 0; two alleles per variant).
+ * lcd_hap_state_carry: old state -> the merged table of lcd_merge_region_vars: per-read arrays unchanged; per-variant entries of old variant i at
+ * cur_to_merged[i] (var_phase_set, hap_to_cons_alle[3i ..], the three hap_to_alle_profile planes through 2 i -> 2 cur_to_merged[i]); variants that came from a
+ * region get the fresh values.  A map entry outside [0, n_merged_vars) or two old variants with one target return -4.  *out is malloc()'d (lcd_hap_state_free);
+ * out may not alias old. */
+typedef struct lcd_hap_state_t {
+    int n_reads, n_vars;
+    int *haps; int64_t *phase_sets; int *n_clean_agree_snps, *n_clean_conflict_snps;    /* n_reads */
+    int64_t *var_phase_set; int *hap_to_cons_alle /* 3 n_vars */, *hap_to_alle_profile /* 3 planes of 2 n_vars */;
+} lcd_hap_state_t;
+int lcd_hap_state_init(int n_reads, int n_vars, lcd_hap_state_t *out);
+int lcd_hap_state_carry(const lcd_hap_state_t *old, int n_merged_vars, const int *cur_to_merged, lcd_hap_state_t *out);
+void lcd_hap_state_free(lcd_hap_state_t *s);
+/* lcd_chunks_noisy_rounds: n_chunks device chunks (one device) from "first round done" (lcd_chunk_clean_vars + K5 over the clean categories) to the fixed point of
+ * the loop at :2952-2975.  lcd_sort_noisy_regs once per chunk; then per pass: lcd_chunk_plan_pass_batch over the chunks that are still in the loop, one batch per
+ * chunk (lcd_batch_add_planned) through ONE lcd_batch_run_many, lcd_batch_region_vars per submitted region in sorted-region order, done[] by the reference's rule
+ * (a region whose call returned >= 0 variants is done, n_cons == 0 leaves it, long / deep regions are done), lcd_merge_region_vars_batch + lcd_hap_state_carry +
+ * lcd_clean_vars_hap_problem + lcd_assign_hap_batch over LONGCALLD_CAND_GERMLINE_VAR_CATE for exactly the chunks that got a variant (new_var), and a chunk leaves
+ * the loop after a pass in which none of its regions became done.  Regions of one pass are independent in germline mode (SURVEY CS-2); opt->collect_ref_read_aln_str
+ * != 0 (out_somatic / refine) returns -2.  opt->collect_noisy_vars is forced to 2: only variants and alleles cross PCIe.
+ * In per chunk: chunk, vars (lcd_chunk_clean_vars' output: owned by the driver from a successful return on, i.e. freed and replaced), state (after the clean-
+ * category K5 call, arrays malloc()'d: freed and replaced), ordered_read_ids, is_skipped, ref_seq (codes 0-4, ref_seq[0] = position ref_beg) / ref_beg / ref_end,
+ * is_ont.  Out per chunk: vars (final table + profile), state (final, arrays sized to the final table), done (malloc()'d, n_regs), n_passes, n_first_vars and
+ * first_to_final (malloc()'d: first-round variant index -> final index).  On a failure of any stage everything the driver allocated is freed, vars / state are as
+ * they were handed in, the out fields are NULL / 0 and the stage's error is returned. */
+typedef struct lcd_rounds_chunk_t {
+    const lcd_chunk_t *chunk;
+    lcd_clean_vars_t *vars; lcd_hap_state_t *state;
+    const int *ordered_read_ids; const uint8_t *is_skipped;
+    const uint8_t *ref_seq; int64_t ref_beg, ref_end;
+    int is_ont;
+    int *done; int n_passes; int n_first_vars; int *first_to_final;   /* out */
+} lcd_rounds_chunk_t;
+int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,32 @@ class LcdRegionVars(C.Structure):
                 ("prof_alleles", _i32p)]
 
 
+class LcdPassOpt(C.Structure):
+    """lcd_pass_opt_t: the call_var_opt_t fields the plan of a noisy-region pass reads"""
+    _fields_ = [(n, C.c_int) for n in ("max_noisy_reg_len", "max_noisy_reg_cov", "noisy_reg_flank_len")]
+
+
+class LcdPassPlan(C.Structure):
+    """lcd_pass_plan_t: per region status / clamped interval, CSR of (region, read) pairs with their slices (every array malloc()'d)"""
+    _i32p = C.POINTER(C.c_int)
+    _fields_ = [("n_regs", C.c_int), ("status", _i32p), ("beg", C.POINTER(C.c_int64)), ("end", C.POINTER(C.c_int64)), ("read_off", C.POINTER(C.c_uint64)),
+                ("read_ids", _i32p), ("read_beg", _i32p), ("read_end", _i32p), ("cover", _i32p)]
+
+
+class LcdHapState(C.Structure):
+    """lcd_hap_state_t: the in/out arrays of K5"""
+    _i32p, _i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+    _fields_ = [("n_reads", C.c_int), ("n_vars", C.c_int), ("haps", _i32p), ("phase_sets", _i64p), ("n_clean_agree_snps", _i32p), ("n_clean_conflict_snps", _i32p),
+                ("var_phase_set", _i64p), ("hap_to_cons_alle", _i32p), ("hap_to_alle_profile", _i32p)]
+
+
+class LcdRoundsChunk(C.Structure):
+    """lcd_rounds_chunk_t: one chunk of lcd_chunks_noisy_rounds"""
+    _fields_ = [("chunk", C.c_void_p), ("vars", C.POINTER(LcdCleanVars)), ("state", C.POINTER(LcdHapState)), ("ordered_read_ids", C.POINTER(C.c_int)),
+                ("is_skipped", C.POINTER(C.c_uint8)), ("ref_seq", C.POINTER(C.c_uint8)), ("ref_beg", C.c_int64), ("ref_end", C.c_int64), ("is_ont", C.c_int),
+                ("done", C.POINTER(C.c_int)), ("n_passes", C.c_int), ("n_first_vars", C.c_int), ("first_to_final", C.POINTER(C.c_int))]
+
+
 _lib = None
 
 # every symbol include/lcd_hotpath.h declares (tests check the .so exports all of them)
@@ -118,6 +144,8 @@ EXPORTS = [
     "lcd_region_job_cost", "lcd_region_jobs_pack", "lcd_batch_add_packed", "lcd_rebalance_plan", "lcd_rccl_unique_id", "lcd_comm_create", "lcd_comm_destroy", "lcd_comm_info", "lcd_rebalance_exchange", "lcd_rebalance_last_error",
     "lcd_clean_opt_default", "lcd_chunk_clean_vars", "lcd_chunk_clean_vars_batch", "lcd_clean_vars_free", "lcd_clean_vars_hap_problem",
     "lcd_merge_region_vars", "lcd_merge_region_vars_batch", "lcd_sort_noisy_regs",
+    "lcd_pass_opt_default", "lcd_chunk_plan_pass", "lcd_chunk_plan_pass_batch", "lcd_pass_plan_free", "lcd_batch_region_n_cons", "lcd_batch_add_planned",
+    "lcd_hap_state_init", "lcd_hap_state_carry", "lcd_hap_state_free", "lcd_chunks_noisy_rounds",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -204,6 +232,20 @@ def load_library():
     lib.lcd_merge_region_vars_batch.argtypes = [C.c_int, C.POINTER(C.POINTER(LcdCleanVars)), i32p, C.POINTER(C.POINTER(LcdRegionVars)), C.POINTER(i32p), C.POINTER(u8p),
                                                 C.POINTER(LcdCleanVars), C.POINTER(i32p), C.POINTER(C.POINTER(i32p))]
     lib.lcd_sort_noisy_regs.argtypes = [C.POINTER(LcdNoisyIv), C.c_int, i32p]
+    lib.lcd_pass_opt_default.argtypes = [C.POINTER(LcdPassOpt)]
+    lib.lcd_pass_opt_default.restype = None
+    lib.lcd_chunk_plan_pass.argtypes = [C.c_void_p, C.POINTER(LcdPassOpt), C.c_int, C.POINTER(LcdNoisyIv), i32p, i32p, u8p, C.c_int64, C.c_int64, C.POINTER(LcdPassPlan)]
+    lib.lcd_chunk_plan_pass_batch.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(LcdPassOpt), i32p, C.POINTER(C.POINTER(LcdNoisyIv)), C.POINTER(i32p), C.POINTER(i32p),
+                                              C.POINTER(u8p), i64p, i64p, C.POINTER(LcdPassPlan)]
+    lib.lcd_pass_plan_free.argtypes = [C.POINTER(LcdPassPlan)]
+    lib.lcd_pass_plan_free.restype = None
+    lib.lcd_batch_region_n_cons.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_batch_add_planned.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(LcdPassPlan), i32p, i64p, u8p, C.c_int64, i32p]
+    lib.lcd_hap_state_init.argtypes = [C.c_int, C.c_int, C.POINTER(LcdHapState)]
+    lib.lcd_hap_state_carry.argtypes = [C.POINTER(LcdHapState), C.c_int, i32p, C.POINTER(LcdHapState)]
+    lib.lcd_hap_state_free.argtypes = [C.POINTER(LcdHapState)]
+    lib.lcd_hap_state_free.restype = None
+    lib.lcd_chunks_noisy_rounds.argtypes = [C.c_int, C.POINTER(LcdRoundsChunk), C.POINTER(LcdOpt), C.POINTER(LcdPassOpt)]
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]
     lib.lcd_batch_digest.argtypes = [C.c_void_p]

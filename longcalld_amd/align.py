@@ -374,6 +374,25 @@ class RegionBatch:
                 _libc.free(C.cast(p, C.c_void_p))
         return out
 
+    def n_cons(self, region):
+        """lcd_batch_region_n_cons: 0 = the region could not be resolved (works with opt.collect_noisy_vars == 2, where result() does not)"""
+        return check(self.lib.lcd_batch_region_n_cons(self.h, int(region)), self.lib)
+
+    def add_planned(self, chunk, plan, haps, phase_sets, ref, ref_beg):
+        """lcd_batch_add_planned: every LCD_PLAN_SUBMIT region of a plan (plan_pass) of DeviceChunk `chunk`; haps / phase_sets per chunk read, ref = the chunk's
+        reference codes starting at ref_beg -> batch index per region of the plan (-1: not submitted)"""
+        keep = []
+        pl = _pass_plan_struct(plan, keep)
+        hp = np.ascontiguousarray(haps, np.int32); ps = np.ascontiguousarray(phase_sets, np.int64); rf = np.ascontiguousarray(ref, np.uint8)
+        idx = np.full(max(1, len(plan["status"])), -1, np.int32)
+        check(self.lib.lcd_batch_add_planned(self.h, chunk.h, C.byref(pl), hp.ctypes.data_as(i32p), ps.ctypes.data_as(C.POINTER(C.c_int64)), _p8(rf), int(ref_beg),
+                                             idx.ctypes.data_as(i32p)), self.lib)
+        idx = idx[:len(plan["status"])].copy()
+        for i in np.argsort(np.where(idx >= 0, idx, 1 << 30), kind="stable"):
+            if idx[i] >= 0:
+                self.n_reads.append(int(plan["read_off"][i + 1] - plan["read_off"][i]))
+        return idx
+
     def result(self, region):
         """-> dict(n_cons, clu_n_seqs, clu_read_ids, aln_strs[c][j] = None | dict(target, query, beg/end...)), freeing the C buffers"""
         n = self.n_reads[region]
@@ -987,3 +1006,198 @@ def sort_noisy_regs(regs):
     order = np.zeros(max(1, len(regs)), np.int32)
     check(lib.lcd_sort_noisy_regs(arr, len(regs), order.ctypes.data_as(i32p)), lib)
     return order[:len(regs)].copy()
+
+
+# ---------------- the noisy-region rounds of collect_var_main on device-resident chunks (lcd_chunk_plan_pass ... lcd_chunks_noisy_rounds) ----------------
+PLAN_DONE_BEFORE, PLAN_SKIP_LONG, PLAN_SKIP_DEEP, PLAN_NO_READS, PLAN_SUBMIT = range(5)   # LCD_PLAN_*
+_libc.malloc.restype = C.c_void_p
+_libc.malloc.argtypes = [C.c_size_t]
+
+
+def pass_opt(**kw):
+    """lcd_pass_opt_t with the defaults of src/call_var_main.h:36-42 (50000 / 1000 / 10); keyword arguments override fields"""
+    from ._lib import LcdPassOpt
+    o = LcdPassOpt()
+    load_library().lcd_pass_opt_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _iv_array(regs, keep):
+    regs = np.asarray(regs, np.int64).reshape(-1, 3)
+    arr = (LcdNoisyIv * max(1, len(regs)))(*[LcdNoisyIv(int(x[0]), int(x[1]), int(x[2]), 0) for x in regs])
+    keep.append(arr)
+    return arr, len(regs)
+
+
+def _pass_plan_struct(plan, keep):
+    """a plan_pass dict -> LcdPassPlan over numpy copies"""
+    from ._lib import LcdPassPlan
+    def P(a, dt, ty):
+        a = np.ascontiguousarray(a, dt).reshape(-1)
+        if a.size == 0:
+            a = np.zeros(1, dt)
+        keep.append(a)
+        return a.ctypes.data_as(C.POINTER(ty))
+    pl = LcdPassPlan()
+    pl.n_regs = len(plan["status"])
+    pl.status = P(plan["status"], np.int32, C.c_int); pl.beg = P(plan["beg"], np.int64, C.c_int64); pl.end = P(plan["end"], np.int64, C.c_int64)
+    pl.read_off = P(plan["read_off"], np.uint64, C.c_uint64)
+    for k in ("read_ids", "read_beg", "read_end", "cover"):
+        setattr(pl, k, P(plan[k], np.int32, C.c_int))
+    return pl
+
+
+def _pass_plan_dict(pl):
+    def arr(p, n, dt):
+        return np.ctypeslib.as_array(p, shape=(n,)).astype(dt).copy() if n > 0 and p else np.zeros(0, dt)
+    n = pl.n_regs
+    off = arr(pl.read_off, n + 1, np.uint64) if pl.read_off else np.zeros(1, np.uint64)
+    m = int(off[-1])
+    return dict(status=arr(pl.status, n, np.int32), beg=arr(pl.beg, n, np.int64), end=arr(pl.end, n, np.int64), read_off=off.astype(np.int64),
+                read_ids=arr(pl.read_ids, m, np.int32), read_beg=arr(pl.read_beg, m, np.int32), read_end=arr(pl.read_end, m, np.int32), cover=arr(pl.cover, m, np.int32))
+
+
+def plan_pass_batch(chunks, args, opt=None, single=False, n_regs=None):
+    """lcd_chunk_plan_pass_batch over DeviceChunks: args[i] = dict(regs (n, 3) start / end / label, done (n), ordered_read_ids, is_skipped, ref_beg, ref_end)
+    -> list of dict(status, beg, end, read_off, read_ids, read_beg, read_end, cover); single=True: one chunk through lcd_chunk_plan_pass.  A chunk may be None
+    and n_regs may override the region counts (tests of the argument checks)."""
+    from ._lib import LcdPassPlan
+    lib = load_library()
+    opt = opt if opt is not None else pass_opt()
+    n = len(chunks)
+    keep = []
+    ivs = [_iv_array(a["regs"], keep) for a in args]
+    nreg = [x[1] for x in ivs] if n_regs is None else list(n_regs)
+    nz = lambda a, dt: np.ascontiguousarray(a, dt) if len(a) else np.zeros(1, dt)
+    done = [nz(a["done"], np.int32) for a in args]; ords = [nz(a["ordered_read_ids"], np.int32) for a in args]; skips = [nz(a["is_skipped"], np.uint8) for a in args]
+    hs = [None if c is None else c.h for c in chunks]
+    outs = (LcdPassPlan * n)()
+    if single:
+        check(lib.lcd_chunk_plan_pass(hs[0], C.byref(opt), nreg[0], ivs[0][0], done[0].ctypes.data_as(i32p), ords[0].ctypes.data_as(i32p), _p8(skips[0]),
+                                      int(args[0]["ref_beg"]), int(args[0]["ref_end"]), C.byref(outs[0])), lib)
+    else:
+        check(lib.lcd_chunk_plan_pass_batch(n, (C.c_void_p * n)(*hs), C.byref(opt), (C.c_int * n)(*nreg),
+                                            (C.POINTER(LcdNoisyIv) * n)(*[C.cast(x[0], C.POINTER(LcdNoisyIv)) for x in ivs]),
+                                            (i32p * n)(*[d.ctypes.data_as(i32p) for d in done]), (i32p * n)(*[o.ctypes.data_as(i32p) for o in ords]),
+                                            (u8p * n)(*[_p8(s) for s in skips]), (C.c_int64 * n)(*[int(a["ref_beg"]) for a in args]),
+                                            (C.c_int64 * n)(*[int(a["ref_end"]) for a in args]), outs), lib)
+    res = []
+    for i in range(n):
+        res.append(_pass_plan_dict(outs[i]))
+        lib.lcd_pass_plan_free(C.byref(outs[i]))
+    return res
+
+
+def plan_pass(chunk, regs, done, ordered_read_ids, is_skipped, ref_beg, ref_end, opt=None, n_regs=None):
+    """lcd_chunk_plan_pass: the plan of one noisy-region pass of a DeviceChunk (see plan_pass_batch)"""
+    return plan_pass_batch([chunk], [dict(regs=regs, done=done, ordered_read_ids=ordered_read_ids, is_skipped=is_skipped, ref_beg=ref_beg, ref_end=ref_end)], opt,
+                           single=True, n_regs=None if n_regs is None else [n_regs])[0]
+
+
+_STATE_FIELDS = (("haps", np.int32), ("phase_sets", np.int64), ("n_clean_agree_snps", np.int32), ("n_clean_conflict_snps", np.int32), ("var_phase_set", np.int64),
+                 ("hap_to_cons_alle", np.int32), ("hap_to_alle_profile", np.int32))
+
+
+def _malloc_copy(a, ty):
+    """a numpy array -> a malloc()'d copy (for structures the library takes ownership of)"""
+    a = np.ascontiguousarray(a).reshape(-1)
+    p = _libc.malloc(max(a.nbytes, 8))
+    if a.nbytes:
+        C.memmove(p, a.ctypes.data, a.nbytes)
+    return C.cast(p, C.POINTER(ty))
+
+
+def _hap_state_struct(state, n_reads, n_vars, keep=None):
+    """a K5 state dict -> LcdHapState; keep=None: malloc()'d copies, else numpy copies kept alive in keep"""
+    from ._lib import LcdHapState
+    s = LcdHapState()
+    s.n_reads, s.n_vars = int(n_reads), int(n_vars)
+    for k, dt in _STATE_FIELDS:
+        ty = C.c_int64 if dt is np.int64 else C.c_int
+        a = np.ascontiguousarray(state[k], dt).reshape(-1)
+        if keep is None:
+            setattr(s, k, _malloc_copy(a, ty))
+        else:
+            a = a.copy() if a.size else np.zeros(1, dt)
+            keep.append(a)
+            setattr(s, k, a.ctypes.data_as(C.POINTER(ty)))
+    return s
+
+
+def _hap_state_dict(s):
+    R, V = s.n_reads, s.n_vars
+    size = dict(haps=R, phase_sets=R, n_clean_agree_snps=R, n_clean_conflict_snps=R, var_phase_set=V, hap_to_cons_alle=3 * V, hap_to_alle_profile=6 * V)
+    return {k: (np.ctypeslib.as_array(getattr(s, k), shape=(size[k],)).astype(dt).copy() if size[k] > 0 else np.zeros(0, dt)) for k, dt in _STATE_FIELDS}
+
+
+def hap_state_carry(state, n_merged_vars, cur_to_merged):
+    """lcd_hap_state_carry: K5's state dict (assign_hap_germline) on the merged table of merge_region_vars: per-read arrays unchanged, per-variant arrays through
+    cur_to_merged, fresh values for the variants that came from a region"""
+    from ._lib import LcdHapState
+    lib = load_library()
+    keep = []
+    c2m = np.ascontiguousarray(cur_to_merged, np.int32)
+    old = _hap_state_struct(state, len(state["haps"]), len(state["var_phase_set"]), keep)
+    out = LcdHapState()
+    check(lib.lcd_hap_state_carry(C.byref(old), int(n_merged_vars), (c2m if c2m.size else np.zeros(1, np.int32)).ctypes.data_as(i32p), C.byref(out)), lib)
+    res = _hap_state_dict(out)
+    lib.lcd_hap_state_free(C.byref(out))
+    return res
+
+
+def _clean_vars_struct_malloc(cv):
+    """a clean_vars_dict -> LcdCleanVars whose arrays are malloc()'d (lcd_clean_vars_free releases them)"""
+    v = LcdCleanVars()
+    v.n_vars, v.n_reads, v.n_cr = int(cv["n_vars"]), int(cv["n_reads"]), len(cv["cr_read"])
+    v.pos = _malloc_copy(np.asarray(cv["pos"], np.int64), C.c_int64)
+    for k in ("var_type", "ref_len", "alt_len", "cate", "total_cov", "low_qual_cov", "alle_covs", "strand_alle_covs", "is_homopolymer_indel", "start_var_idx",
+              "end_var_idx", "alleles", "alt_qi", "cr_read"):
+        setattr(v, k, _malloc_copy(np.asarray(cv[k], np.int32), C.c_int))
+    v.alt_off = _malloc_copy(np.asarray(cv["alt_off"], np.uint64), C.c_uint64); v.allele_off = _malloc_copy(np.asarray(cv["allele_off"], np.uint64), C.c_uint64)
+    v.alt_pool = _malloc_copy(np.asarray(cv["alt_pool"], np.uint8), C.c_uint8)
+    regs = np.asarray(cv["regs"], np.int64).reshape(-1, 3)
+    flat = np.zeros((max(1, len(regs)), 3), np.int64)    # lcd_noisy_iv_t: int64 start, end | int32 label, pad
+    flat[:len(regs), :2] = regs[:, :2]; flat.view(np.int32).reshape(len(flat), 6)[:len(regs), 4] = regs[:, 2]
+    v.n_regs, v.regs = len(regs), C.cast(_malloc_copy(flat, C.c_int64), C.POINTER(LcdNoisyIv))
+    return v
+
+
+def chunks_noisy_rounds(chunks, items, opt=None, popt=None):
+    """lcd_chunks_noisy_rounds: DeviceChunks from "first round done" to the fixed point of collect_var_main's noisy-region loop (src/collect_var.c:2946-2977).
+    items[i] = dict(cv = clean_vars_dict of the first round, state = K5 state after the clean-category call, ordered_read_ids, is_skipped, ref (codes),
+    ref_beg, is_ont (optional)) -> list of dict(cv, state, done, n_passes, first_to_final)"""
+    from ._lib import LcdRoundsChunk
+    lib = load_library()
+    opt = opt if opt is not None else default_opt()
+    popt = popt if popt is not None else pass_opt()
+    n = len(chunks)
+    keep = []
+    arr = (LcdRoundsChunk * max(1, n))()
+    vs, ss = [], []
+    for i, (ch, it) in enumerate(zip(chunks, items)):
+        v = _clean_vars_struct_malloc(it["cv"]); s = _hap_state_struct(it["state"], it["cv"]["n_reads"], it["cv"]["n_vars"])
+        vs.append(v); ss.append(s)
+        ordered = np.ascontiguousarray(it["ordered_read_ids"], np.int32); skipped = np.ascontiguousarray(it["is_skipped"], np.uint8); ref = np.ascontiguousarray(it["ref"], np.uint8)
+        keep += [ordered, skipped, ref]
+        x = arr[i]
+        x.chunk, x.vars, x.state = ch.h, C.pointer(v), C.pointer(s)
+        x.ordered_read_ids, x.is_skipped, x.ref_seq = ordered.ctypes.data_as(i32p), _p8(skipped), _p8(ref)
+        x.ref_beg, x.ref_end, x.is_ont = int(it["ref_beg"]), int(it["ref_beg"]) + len(ref) - 1, int(it.get("is_ont", 0))
+    rc = lib.lcd_chunks_noisy_rounds(n, arr, C.byref(opt), C.byref(popt))
+    res = []
+    try:
+        check(rc, lib)
+        for i in range(n):
+            x = arr[i]
+            nr, nf = vs[i].n_regs, x.n_first_vars
+            res.append(dict(cv=clean_vars_dict(vs[i]), state=_hap_state_dict(ss[i]), n_passes=int(x.n_passes),
+                            done=np.array([x.done[k] for k in range(nr)], np.int32), first_to_final=np.array([x.first_to_final[k] for k in range(nf)], np.int32)))
+    finally:
+        for i in range(n):
+            lib.lcd_clean_vars_free(C.byref(vs[i])); lib.lcd_hap_state_free(C.byref(ss[i]))
+            for p in (arr[i].done, arr[i].first_to_final):
+                if p:
+                    _libc.free(C.cast(p, C.c_void_p))
+    return res

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -3210,6 +3211,7 @@ struct lcd_chunk_s {
     std::vector<int> status, n_cand; std::vector<int64_t> beg, end;
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
+    DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use
     ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); }
 };
 lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
@@ -4384,6 +4386,348 @@ int lcd_sort_noisy_regs(const lcd_noisy_iv_t *regs, int n, int *order_out) {
     for (int i = 0; i < n; ++i)
         for (int j = i + 1; j < n; ++j)
             if (after(order_out[i], order_out[j])) std::swap(order_out[i], order_out[j]);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// the noisy-region rounds of collect_var_main (src/collect_var.c:2946-2977) on device-resident chunks: pass plan (plan_kernel.hip), planned regions into a
+// batch, K5 state across a merge, and the driver that composes them with lcd_batch_run_many, lcd_merge_region_vars_batch and lcd_assign_hap_batch
+void lcd_pass_opt_default(lcd_pass_opt_t *o) { o->max_noisy_reg_len = 50000; o->max_noisy_reg_cov = 1000; o->noisy_reg_flank_len = 10; } // src/call_var_main.h:36-42
+void lcd_pass_plan_free(lcd_pass_plan_t *p) {
+    if (!p) return;
+    free(p->status); free(p->beg); free(p->end); free(p->read_off); free(p->read_ids); free(p->read_beg); free(p->read_end); free(p->cover);
+    memset(p, 0, sizeof(*p));
+}
+int lcd_chunk_plan_pass_batch(int n_chunks, const lcd_chunk_t *const *chunks, const lcd_pass_opt_t *opt, const int *n_regs, const lcd_noisy_iv_t *const *regs,
+                              const int *const *done, const int *const *ordered_read_ids, const uint8_t *const *is_skipped, const int64_t *ref_beg,
+                              const int64_t *ref_end, lcd_pass_plan_t *outs) {
+    const std::string W = "lcd_chunk_plan_pass";
+    if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, W + ": n_chunks < 0") : 0;
+    if (!chunks || !opt || !n_regs || !regs || !done || !ordered_read_ids || !is_skipped || !ref_beg || !ref_end || !outs) return set_err(-4, W + ": NULL argument");
+    memset(outs, 0, sizeof(lcd_pass_plan_t) * (size_t)n_chunks);
+    // 1. host: validation; nothing touches the device on malformed input
+    long long G = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+        const std::string at = n_chunks > 1 ? "chunk " + std::to_string(c) + ": " : "";
+        if (n_regs[c] < 0) return set_err(-4, W + ": " + at + "n_regs < 0");
+        if (ref_end[c] < ref_beg[c]) return set_err(-4, W + ": " + at + "ref_end < ref_beg");
+        if (n_regs[c] > 0 && (!regs[c] || !done[c])) return set_err(-4, W + ": " + at + "no regs / done");
+    }
+    for (int c = 0; c < n_chunks; ++c) {
+        const std::string at = n_chunks > 1 ? "chunk " + std::to_string(c) + ": " : "";
+        if (!chunks[c]) return set_err(-4, W + ": " + at + "NULL chunk");
+        if (chunks[c]->device != chunks[0]->device) return set_err(-4, W + ": chunks on different devices");
+        const int R = chunks[c]->n_reads;
+        if (R > 0 && (!ordered_read_ids[c] || !is_skipped[c])) return set_err(-4, W + ": " + at + "no ordered_read_ids / is_skipped");
+        for (int i = 0; i < R; ++i) if (ordered_read_ids[c][i] < 0 || ordered_read_ids[c][i] >= R) return set_err(-4, W + ": " + at + "ordered_read_ids entry outside [0, n_reads)");
+        G += n_regs[c];
+    }
+    if (G > (1ll << 30)) return set_err(-4, W + ": too many regions");
+    // 2. the region tables; long and done regions are decided here
+    std::vector<PlanReg> pr((size_t)G); std::vector<int> reg0(n_chunks + 1, 0);
+    int n_pending = 0;
+    for (int c = 0, g = 0; c < n_chunks; ++c) {
+        reg0[c] = g;
+        for (int i = 0; i < n_regs[c]; ++i, ++g) {
+            PlanReg &q = pr[g]; q.chunk = c;
+            q.beg = std::max<int64_t>(regs[c][i].start, ref_beg[c]); q.end = std::min<int64_t>(regs[c][i].end, ref_end[c]);   // collect_reg_ref_bseq, src/seq.c:417-418
+            q.status = done[c][i] ? LCD_PLAN_DONE_BEFORE : q.end - q.beg + 1 > (long long)opt->max_noisy_reg_len ? LCD_PLAN_SKIP_LONG : LCD_PLAN_SUBMIT;
+            n_pending += q.status == LCD_PLAN_SUBMIT;
+        }
+        reg0[c + 1] = g;
+    }
+    std::vector<int> st_h((size_t)G); std::vector<unsigned long long> off_h((size_t)G + 1, 0);
+    for (long long g = 0; g < G; ++g) st_h[g] = pr[g].status;
+    std::vector<uint8_t> pairs;                       // downloaded: SliceOut[P], read ids[P]
+    unsigned long long P = 0;
+    if (n_pending > 0) {
+        if (use_device(chunks[0]->device)) return -1;
+        // the chunks' read tables: once per chunk
+        for (int c = 0; c < n_chunks; ++c) {
+            lcd_chunk_s *ch = const_cast<lcd_chunk_s *>(chunks[c]);
+            std::lock_guard<std::mutex> lk(ch->plan_mu);
+            if (ch->plan_ready || ch->n_reads <= 0) continue;
+            std::vector<PlanRead> tab(ch->n_reads);
+            for (int r = 0; r < ch->n_reads; ++r) { PlanRead &x = tab[r]; x.beg = ch->beg[r]; x.end = ch->end[r]; x.digar_off = ch->slot[r]; x.n_digar = ch->n_digar[r]; x.qlen = ch->qlen[r]; x.status = ch->status[r]; x.pad = 0; }
+            if (ch->d_plan.ensure(tab.size() * sizeof(PlanRead), 63)) return -11;
+            if (hipMemcpy(ch->d_plan.p, tab.data(), tab.size() * sizeof(PlanRead), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); ch->d_plan.release(); return set_err(-10, W + ": read table upload failed"); }
+            ch->plan_ready = true;
+        }
+        // one staged block: chunk table, region table, every chunk's ordered_read_ids and is_skipped; behind it on the device: counts, statuses, offsets
+        std::vector<uint8_t> hb;
+        auto put = [&](const void *p, size_t bytes) { size_t o = lcd_align_up(hb.size(), 16); hb.resize(o + bytes); if (p && bytes) memcpy(hb.data() + o, p, bytes); return (uint64_t)o; };
+        const uint64_t o_ch = put(nullptr, (size_t)n_chunks * sizeof(PlanChunk)), o_pr = put(pr.data(), (size_t)G * sizeof(PlanReg));
+        std::vector<PlanChunk> pc(n_chunks);
+        for (int c = 0; c < n_chunks; ++c) {
+            const lcd_chunk_s *ch = chunks[c]; const int R = ch->n_reads;
+            pc[c].reads = ch->d_plan.addr(); pc[c].digars = ch->d_dig.addr(); pc[c].n_reads = R; pc[c].pad = 0;
+            pc[c].order = put(ordered_read_ids[c], (size_t)R * 4); pc[c].skipped = put(is_skipped[c], (size_t)R);
+        }
+        const uint64_t up_bytes = lcd_align_up(hb.size(), 16);
+        const uint64_t o_cnt = up_bytes, o_st = o_cnt + lcd_align_up((uint64_t)G * 4, 16), o_off = o_st + lcd_align_up((uint64_t)G * 4, 16);
+        const uint64_t total = o_off + ((uint64_t)G + 1) * 8 + 64;
+        StreamGuard st; if (st.create()) return -10;
+        DevBuf d; if (d.ensure(total, 63)) return -11;
+        const uint64_t B = d.addr();
+        for (int c = 0; c < n_chunks; ++c) { pc[c].order += B; pc[c].skipped += B; }
+        memcpy(hb.data() + o_ch, pc.data(), (size_t)n_chunks * sizeof(PlanChunk));
+        HIPCHK(hipMemcpyAsync(d.p, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
+        const PlanChunk *d_ch = (const PlanChunk *)(uintptr_t)(B + o_ch); const PlanReg *d_pr = (const PlanReg *)(uintptr_t)(B + o_pr);
+        int *d_cnt = (int *)(uintptr_t)(B + o_cnt), *d_st = (int *)(uintptr_t)(B + o_st); unsigned long long *d_off = (unsigned long long *)(uintptr_t)(B + o_off);
+        lcd_launch_plan_count(d_ch, d_pr, (int)G, opt->max_noisy_reg_cov, d_cnt, d_st, st);
+        lcd_launch_plan_scan(d_cnt, (int)G, d_off, st);
+        HIPCHK(hipGetLastError());
+        std::vector<uint8_t> dl(o_off + ((uint64_t)G + 1) * 8 - o_st);
+        HIPCHK(hipMemcpyAsync(dl.data(), (const uint8_t *)d.p + o_st, dl.size(), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));                                             // (1) the counts size the pair area
+        memcpy(st_h.data(), dl.data(), (size_t)G * 4); memcpy(off_h.data(), dl.data() + (o_off - o_st), ((size_t)G + 1) * 8);
+        P = off_h[G];
+        if (P > 0x7fffffffull) return set_err(-24, W + ": more than 2^31 - 1 (region, read) pairs in one call");
+        if (P > 0) {
+            DevBuf dp; if (dp.ensure(P * (sizeof(SliceOut) + 8) + 64, 63)) return -11;     // the pair area: slices, read ids, region of the pair
+            SliceOut *d_so = (SliceOut *)dp.p; int *d_ids = (int *)((uint8_t *)dp.p + P * sizeof(SliceOut)), *d_preg = d_ids + P;
+            lcd_launch_plan_fill(d_ch, d_pr, (int)G, d_st, d_off, d_ids, d_preg, st);
+            lcd_launch_plan_slices(d_ch, d_pr, d_ids, d_preg, P, opt->noisy_reg_flank_len, d_so, st);
+            HIPCHK(hipGetLastError());
+            pairs.resize(P * (sizeof(SliceOut) + 4));
+            HIPCHK(hipMemcpyAsync(pairs.data(), dp.p, pairs.size(), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));                                         // (2)
+        }
+    }
+    // 3. per chunk: the malloc()'d plan
+    const SliceOut *so = (const SliceOut *)pairs.data(); const int *ids = (const int *)(pairs.data() + P * sizeof(SliceOut));
+    for (int c = 0; c < n_chunks; ++c) {
+        lcd_pass_plan_t &o = outs[c]; const int n = n_regs[c], g0 = reg0[c];
+        const unsigned long long p0 = off_h[g0], np = off_h[g0 + n] - p0;
+        o.n_regs = n;
+        o.status = (int *)malloc((n + 1) * 4ull); o.beg = (int64_t *)malloc((n + 1) * 8ull); o.end = (int64_t *)malloc((n + 1) * 8ull); o.read_off = (uint64_t *)malloc((n + 1) * 8ull);
+        o.read_ids = (int *)malloc((np + 1) * 4); o.read_beg = (int *)malloc((np + 1) * 4); o.read_end = (int *)malloc((np + 1) * 4); o.cover = (int *)malloc((np + 1) * 4);
+        for (int i = 0; i < n; ++i) { o.status[i] = st_h[g0 + i]; o.beg[i] = pr[g0 + i].beg; o.end[i] = pr[g0 + i].end; o.read_off[i] = off_h[g0 + i] - p0; }
+        o.read_off[n] = np;
+        for (unsigned long long k = 0; k < np; ++k) { o.read_ids[k] = ids[p0 + k]; o.read_beg[k] = so[p0 + k].read_beg; o.read_end[k] = so[p0 + k].read_end; o.cover[k] = so[p0 + k].cover; }
+    }
+    return 0;
+}
+int lcd_chunk_plan_pass(const lcd_chunk_t *c, const lcd_pass_opt_t *opt, int n_regs, const lcd_noisy_iv_t *regs, const int *done, const int *ordered_read_ids,
+                        const uint8_t *is_skipped, int64_t ref_beg, int64_t ref_end, lcd_pass_plan_t *out) {
+    if (!out) return set_err(-4, "lcd_chunk_plan_pass: NULL argument");
+    return lcd_chunk_plan_pass_batch(1, &c, opt, &n_regs, &regs, &done, &ordered_read_ids, &is_skipped, &ref_beg, &ref_end, out);
+}
+int lcd_batch_region_n_cons(lcd_batch_t *b, int region) {
+    if (!b->downloaded) return set_err(-3, "lcd_batch_region_n_cons before lcd_batch_download");
+    if (region < 0 || region >= (int)b->regs.size()) return set_err(-4, "bad region index");
+    return b->regs[region].n_cons > 0 ? b->regs[region].n_cons : 0;
+}
+int lcd_batch_add_planned(lcd_batch_t *b, const lcd_chunk_t *c, const lcd_pass_plan_t *plan, const int *haps, const int64_t *phase_sets, const uint8_t *ref_seq,
+                          int64_t ref_beg, int *region_idx_out) {
+    if (!b || !c || !plan || !haps || !phase_sets || !ref_seq) return set_err(-4, "lcd_batch_add_planned: NULL argument");
+    if (plan->n_regs < 0 || (plan->n_regs > 0 && (!plan->status || !plan->beg || !plan->end || !plan->read_off))) return set_err(-4, "lcd_batch_add_planned: incomplete plan");
+    for (int i = 0; i < plan->n_regs; ++i) {
+        if (plan->status[i] != LCD_PLAN_SUBMIT) continue;
+        if (plan->beg[i] < ref_beg || plan->end[i] < plan->beg[i] || plan->read_off[i + 1] < plan->read_off[i]) return set_err(-4, "lcd_batch_add_planned: region " + std::to_string(i) + " outside the reference or with a decreasing read_off");
+        for (uint64_t k = plan->read_off[i]; k < plan->read_off[i + 1]; ++k)
+            if (plan->read_ids[k] < 0 || plan->read_ids[k] >= c->n_reads) return set_err(-4, "lcd_batch_add_planned: read id outside [0, n_reads)");
+    }
+    int added = 0; std::vector<int> hp; std::vector<int64_t> ps;
+    for (int i = 0; i < plan->n_regs; ++i) {
+        if (region_idx_out) region_idx_out[i] = -1;
+        if (plan->status[i] != LCD_PLAN_SUBMIT) continue;
+        const uint64_t k0 = plan->read_off[i]; const int n = (int)(plan->read_off[i + 1] - k0);
+        hp.resize(n); ps.resize(n);
+        for (int k = 0; k < n; ++k) { hp[k] = haps[plan->read_ids[k0 + k]]; ps[k] = phase_sets[plan->read_ids[k0 + k]]; }
+        const int ri = lcd_batch_add_region_from_chunk_dev(b, c, plan->beg[i], plan->end[i], n, plan->read_ids + k0, plan->read_beg + k0, plan->read_end + k0, plan->cover + k0,
+                                                           hp.data(), ps.data(), ref_seq + (plan->beg[i] - ref_beg), (int)(plan->end[i] - plan->beg[i] + 1));
+        if (ri < 0) return ri;
+        if (region_idx_out) region_idx_out[i] = ri;
+        ++added;
+    }
+    return added;
+}
+void lcd_hap_state_free(lcd_hap_state_t *s) {
+    if (!s) return;
+    free(s->haps); free(s->phase_sets); free(s->n_clean_agree_snps); free(s->n_clean_conflict_snps); free(s->var_phase_set); free(s->hap_to_cons_alle); free(s->hap_to_alle_profile);
+    memset(s, 0, sizeof(*s));
+}
+int lcd_hap_state_init(int R, int V, lcd_hap_state_t *o) {
+    if (!o || R < 0 || V < 0) return set_err(-4, "lcd_hap_state_init: bad arguments");
+    o->n_reads = R; o->n_vars = V;
+    o->haps = (int *)calloc(R + 1, 4); o->phase_sets = (int64_t *)malloc((R + 1) * 8ull); o->n_clean_agree_snps = (int *)calloc(R + 1, 4); o->n_clean_conflict_snps = (int *)calloc(R + 1, 4);
+    o->var_phase_set = (int64_t *)malloc((V + 1) * 8ull); o->hap_to_cons_alle = (int *)malloc((3ull * V + 1) * 4); o->hap_to_alle_profile = (int *)calloc(6ull * V + 1, 4);
+    for (int r = 0; r < R; ++r) o->phase_sets[r] = -1;
+    for (int i = 0; i < V; ++i) o->var_phase_set[i] = -1;
+    for (int i = 0; i < 3 * V; ++i) o->hap_to_cons_alle[i] = -1;
+    return 0;
+}
+int lcd_hap_state_carry(const lcd_hap_state_t *old, int M, const int *c2m, lcd_hap_state_t *out) {
+    if (!old || !out || old == out || M < 0 || old->n_vars < 0 || old->n_reads < 0 || (old->n_vars > 0 && !c2m)) return set_err(-4, "lcd_hap_state_carry: bad arguments");
+    const int V = old->n_vars, R = old->n_reads;
+    std::vector<char> taken(M + 1, 0);
+    for (int i = 0; i < V; ++i) {
+        if (c2m[i] < 0 || c2m[i] >= M) return set_err(-4, "lcd_hap_state_carry: cur_to_merged[" + std::to_string(i) + "] outside [0, merged n_vars)");
+        if (taken[c2m[i]]) return set_err(-4, "lcd_hap_state_carry: two variants map to merged variant " + std::to_string(c2m[i]));
+        taken[c2m[i]] = 1;
+    }
+    if (lcd_hap_state_init(R, M, out)) return -4;
+    if (R) { memcpy(out->haps, old->haps, R * 4ull); memcpy(out->phase_sets, old->phase_sets, R * 8ull); memcpy(out->n_clean_agree_snps, old->n_clean_agree_snps, R * 4ull); memcpy(out->n_clean_conflict_snps, old->n_clean_conflict_snps, R * 4ull); }
+    for (int i = 0; i < V; ++i) {
+        const int m = c2m[i];
+        out->var_phase_set[m] = old->var_phase_set[i];
+        for (int h = 0; h < 3; ++h) {
+            out->hap_to_cons_alle[3 * m + h] = old->hap_to_cons_alle[3 * i + h];
+            out->hap_to_alle_profile[(size_t)h * 2 * M + 2 * m] = old->hap_to_alle_profile[(size_t)h * 2 * V + 2 * i];
+            out->hap_to_alle_profile[(size_t)h * 2 * M + 2 * m + 1] = old->hap_to_alle_profile[(size_t)h * 2 * V + 2 * i + 1];
+        }
+    }
+    return 0;
+}
+} // extern "C"
+namespace {
+struct RoundsChunk {               // one chunk of lcd_chunks_noisy_rounds between passes
+    lcd_clean_vars_t own_vars; lcd_hap_state_t own_state; bool has_own = false;   // the driver's own current state (else the caller's)
+    std::vector<int> order, done, f2f; int n_passes = 0; bool in_loop = false;
+};
+struct RegionVarsOwned {           // lcd_batch_region_vars' outputs, freed with the object
+    lcd_noisy_var_t *vars = nullptr; int n = 0, rows = 0; int *ids = nullptr, *ps = nullptr, *pe = nullptr, *pa = nullptr;
+    void release() { for (int i = 0; i < n; ++i) free(vars[i].alt_seq); free(vars); free(ids); free(ps); free(pe); free(pa); vars = nullptr; ids = ps = pe = pa = nullptr; n = rows = 0; }
+};
+}
+extern "C" {
+int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt) {
+    const std::string W = "lcd_chunks_noisy_rounds";
+    if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, W + ": n_chunks < 0") : 0;
+    if (!chunks || !opt || !pass_opt) return set_err(-4, W + ": NULL argument");
+    if (opt->collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode (collect_ref_read_aln_str) is not supported: the regions of a pass are order-dependent there");
+    for (int c = 0; c < n_chunks; ++c) {
+        lcd_rounds_chunk_t &x = chunks[c];
+        x.done = nullptr; x.first_to_final = nullptr; x.n_passes = 0; x.n_first_vars = 0;
+        const std::string at = W + ": chunk " + std::to_string(c) + ": ";
+        if (!x.chunk || !x.vars || !x.state || !x.ref_seq) return set_err(-4, at + "NULL member");
+        if (x.ref_end < x.ref_beg) return set_err(-4, at + "ref_end < ref_beg");
+        if (x.vars->n_reads != x.chunk->n_reads || x.state->n_reads != x.vars->n_reads || x.state->n_vars != x.vars->n_vars) return set_err(-4, at + "chunk, vars and state disagree on n_reads / n_vars");
+        if (x.vars->n_regs < 0 || (x.vars->n_regs > 0 && !x.vars->regs)) return set_err(-4, at + "no regs");
+        if (x.vars->n_reads > 0 && (!x.ordered_read_ids || !x.is_skipped)) return set_err(-4, at + "no ordered_read_ids / is_skipped");
+        if (x.chunk->device != chunks[0].chunk->device) return set_err(-4, W + ": chunks on different devices");
+    }
+    lcd_opt_t bopt = *opt; bopt.collect_noisy_vars = 2;
+    std::vector<RoundsChunk> rc(n_chunks);
+    std::vector<lcd_batch_t *> batches;            // of the current pass
+    std::vector<lcd_pass_plan_t> plans;
+    auto drop_pass = [&]() { for (lcd_batch_t *b : batches) if (b) lcd_batch_destroy(b); batches.clear(); for (lcd_pass_plan_t &p : plans) lcd_pass_plan_free(&p); plans.clear(); };
+    auto fail = [&](int code) {
+        const std::string m = g_err; drop_pass();
+        for (RoundsChunk &r : rc) if (r.has_own) { lcd_clean_vars_free(&r.own_vars); lcd_hap_state_free(&r.own_state); r.has_own = false; }
+        g_err = m; return code;
+    };
+    auto cur_vars = [&](int c) -> lcd_clean_vars_t * { return rc[c].has_own ? &rc[c].own_vars : chunks[c].vars; };
+    auto cur_state = [&](int c) -> lcd_hap_state_t * { return rc[c].has_own ? &rc[c].own_state : chunks[c].state; };
+    for (int c = 0; c < n_chunks; ++c) {
+        RoundsChunk &r = rc[c]; const lcd_clean_vars_t *v = chunks[c].vars;
+        r.order.resize(v->n_regs); r.done.assign(v->n_regs, 0); r.f2f.resize(v->n_vars); std::iota(r.f2f.begin(), r.f2f.end(), 0);
+        if (v->n_regs > 0 && lcd_sort_noisy_regs(v->regs, v->n_regs, r.order.data())) return fail(-4);
+        r.in_loop = v->n_regs > 0;
+    }
+    for (;;) {
+        std::vector<int> A;
+        for (int c = 0; c < n_chunks; ++c) if (rc[c].in_loop) A.push_back(c);
+        if (A.empty()) break;
+        const int na = (int)A.size();
+        // 1. the plan of this pass over the chunks still in the loop
+        std::vector<const lcd_chunk_t *> p_ch(na); std::vector<int> p_n(na); std::vector<const lcd_noisy_iv_t *> p_regs(na); std::vector<const int *> p_done(na), p_ord(na);
+        std::vector<const uint8_t *> p_skip(na); std::vector<int64_t> p_rb(na), p_re(na);
+        for (int a = 0; a < na; ++a) {
+            const int c = A[a]; const lcd_clean_vars_t *v = cur_vars(c);
+            p_ch[a] = chunks[c].chunk; p_n[a] = v->n_regs; p_regs[a] = v->regs; p_done[a] = rc[c].done.data(); p_ord[a] = chunks[c].ordered_read_ids; p_skip[a] = chunks[c].is_skipped;
+            p_rb[a] = chunks[c].ref_beg; p_re[a] = chunks[c].ref_end;
+        }
+        plans.assign(na, lcd_pass_plan_t());
+        int rcode = lcd_chunk_plan_pass_batch(na, p_ch.data(), pass_opt, p_n.data(), p_regs.data(), p_done.data(), p_ord.data(), p_skip.data(), p_rb.data(), p_re.data(), plans.data());
+        if (rcode) return fail(rcode);
+        // 2. one batch per chunk, one joint run
+        batches.assign(na, nullptr);
+        std::vector<std::vector<int>> ridx(na);
+        std::vector<lcd_batch_t *> run;
+        for (int a = 0; a < na; ++a) {
+            const int c = A[a];
+            ridx[a].assign(plans[a].n_regs + 1, -1);
+            bool any = false; for (int i = 0; i < plans[a].n_regs; ++i) any |= plans[a].status[i] == LCD_PLAN_SUBMIT;
+            if (!any) continue;
+            batches[a] = lcd_batch_create_on(&bopt, chunks[c].chunk->device);
+            if (!batches[a]) return fail(-10);
+            rcode = lcd_batch_add_planned(batches[a], chunks[c].chunk, &plans[a], cur_state(c)->haps, cur_state(c)->phase_sets, chunks[c].ref_seq, chunks[c].ref_beg, ridx[a].data());
+            if (rcode < 0) return fail(rcode);
+            if ((rcode = lcd_batch_upload(batches[a]))) return fail(rcode);
+            run.push_back(batches[a]);
+        }
+        if (!run.empty()) {
+            if ((rcode = lcd_batch_run_many(run.data(), (int)run.size()))) return fail(rcode);
+            for (lcd_batch_t *b : run) if ((rcode = lcd_batch_download(b))) return fail(rcode);
+        }
+        // 3. the regions' variants in sorted-region order, done[] by the reference's rule
+        std::vector<std::vector<RegionVarsOwned>> got(na); std::vector<char> new_var(na, 0), new_done(na, 0);
+        auto free_got = [&]() { for (auto &g : got) for (RegionVarsOwned &x : g) x.release(); };
+        for (int a = 0; a < na; ++a) {
+            const int c = A[a]; RoundsChunk &r = rc[c];
+            for (int k = 0; k < plans[a].n_regs; ++k) {
+                const int i = r.order[k], st = plans[a].status[i];
+                if (st == LCD_PLAN_SKIP_LONG || st == LCD_PLAN_SKIP_DEEP) { r.done[i] = 1; new_done[a] = 1; continue; }   // collect_noisy_vars1 returns 0
+                if (st != LCD_PLAN_SUBMIT) continue;
+                if (batches[a]->regs[ridx[a][i]].n_cons <= 0) continue;                                                  // returns -1: tried again
+                RegionVarsOwned x;
+                const int n = lcd_batch_region_vars(batches[a], ridx[a][i], plans[a].beg[i], chunks[c].ref_seq, chunks[c].ref_beg, chunks[c].ref_end - chunks[c].ref_beg + 1, &x.vars,
+                                                    &x.rows, &x.ids, &x.ps, &x.pe, &x.pa);
+                x.n = n > 0 ? n : 0;
+                got[a].push_back(x);
+                if (n < 0) { const std::string m = g_err; free_got(); g_err = m; return fail(n); }
+                r.done[i] = 1; new_done[a] = 1;
+                if (n > 0) new_var[a] = 1;
+            }
+        }
+        // 4. merge + carry + K5 over all germline categories for the chunks that got a variant
+        std::vector<int> M; for (int a = 0; a < na; ++a) if (new_var[a]) M.push_back(a);
+        if (!M.empty()) {
+            const int nm = (int)M.size();
+            std::vector<std::vector<lcd_region_vars_t>> rv(nm); std::vector<const lcd_clean_vars_t *> m_cur(nm); std::vector<int> m_n(nm); std::vector<const lcd_region_vars_t *> m_rv(nm);
+            std::vector<const int *> m_ord(nm); std::vector<const uint8_t *> m_skip(nm); std::vector<std::vector<int>> c2m(nm); std::vector<int *> m_c2m(nm);
+            for (int q = 0; q < nm; ++q) {
+                const int a = M[q], c = A[a];
+                for (const RegionVarsOwned &x : got[a]) rv[q].push_back(lcd_region_vars_t{x.n, x.vars, x.rows, x.ids, x.ps, x.pe, x.pa});
+                m_cur[q] = cur_vars(c); m_n[q] = (int)rv[q].size(); m_rv[q] = rv[q].data(); m_ord[q] = chunks[c].ordered_read_ids; m_skip[q] = chunks[c].is_skipped;
+                c2m[q].assign(m_cur[q]->n_vars + 1, -1); m_c2m[q] = c2m[q].data();
+            }
+            std::vector<lcd_clean_vars_t> merged(nm); std::vector<lcd_hap_state_t> carried(nm, lcd_hap_state_t());
+            rcode = lcd_merge_region_vars_batch(nm, m_cur.data(), m_n.data(), m_rv.data(), m_ord.data(), m_skip.data(), merged.data(), m_c2m.data(), nullptr);
+            free_got();
+            auto drop_new = [&]() { const std::string m = g_err; for (int q = 0; q < nm; ++q) { lcd_clean_vars_free(&merged[q]); lcd_hap_state_free(&carried[q]); } g_err = m; };
+            if (rcode) return fail(rcode);   // (the merge freed its outputs)
+            std::vector<lcd_hap_problem_t> probs(nm); std::vector<std::vector<int>> alle_off(nm), allele_off(nm); std::vector<int> targets(nm, 0x004 | 0x008 | 0x080 | 0x100 | 0x200); // LONGCALLD_CAND_GERMLINE_VAR_CATE, src/collect_var.h:25
+            for (int q = 0; q < nm; ++q) {
+                const int c = A[M[q]];
+                if ((rcode = lcd_hap_state_carry(cur_state(c), merged[q].n_vars, c2m[q].data(), &carried[q]))) { drop_new(); return fail(rcode); }
+                alle_off[q].resize(merged[q].n_vars + 1); allele_off[q].resize(merged[q].n_reads + 1);
+                lcd_clean_vars_hap_problem(&merged[q], chunks[c].is_ont, chunks[c].ordered_read_ids, chunks[c].is_skipped, alle_off[q].data(), allele_off[q].data(), &probs[q]);
+                lcd_hap_problem_t &p = probs[q]; const lcd_hap_state_t &s = carried[q];
+                p.haps = s.haps; p.phase_sets = s.phase_sets; p.n_clean_agree_snps = s.n_clean_agree_snps; p.n_clean_conflict_snps = s.n_clean_conflict_snps;
+                p.var_phase_set = s.var_phase_set; p.hap_to_cons_alle = s.hap_to_cons_alle; p.hap_to_alle_profile = s.hap_to_alle_profile;
+            }
+            if ((rcode = lcd_assign_hap_batch(nm, probs.data(), targets.data()))) { drop_new(); return fail(rcode); }
+            for (int q = 0; q < nm; ++q) {
+                const int c = A[M[q]]; RoundsChunk &r = rc[c];
+                if (r.has_own) { lcd_clean_vars_free(&r.own_vars); lcd_hap_state_free(&r.own_state); }
+                r.own_vars = merged[q]; r.own_state = carried[q]; r.has_own = true;
+                for (int &f : r.f2f) f = c2m[q][f];
+            }
+        } else free_got();
+        for (int a = 0; a < na; ++a) { RoundsChunk &r = rc[A[a]]; ++r.n_passes; if (!new_done[a]) r.in_loop = false; }
+        drop_pass();
+    }
+    // the caller's structures take the final state
+    for (int c = 0; c < n_chunks; ++c) {
+        RoundsChunk &r = rc[c]; lcd_rounds_chunk_t &x = chunks[c];
+        x.n_first_vars = (int)r.f2f.size(); x.n_passes = r.n_passes;
+        x.done = (int *)malloc((r.done.size() + 1) * 4); if (!r.done.empty()) memcpy(x.done, r.done.data(), r.done.size() * 4);
+        x.first_to_final = (int *)malloc((r.f2f.size() + 1) * 4); if (!r.f2f.empty()) memcpy(x.first_to_final, r.f2f.data(), r.f2f.size() * 4);
+        if (r.has_own) { lcd_clean_vars_free(x.vars); *x.vars = r.own_vars; lcd_hap_state_free(x.state); *x.state = r.own_state; r.has_own = false; }
+    }
     return 0;
 }
 

@@ -53,3 +53,10 @@ void lcd_launch_mv_scan(int *start, int *end, int n_reads, unsigned long long *o
 void lcd_launch_mv_fill(int *cells, unsigned long long n, hipStream_t st);
 void lcd_launch_mv_scatter(const MvSrc *srcs, int n_src, unsigned long long n_cells, const int *start, const unsigned long long *off, int *alleles, int *alt_qi,
                            unsigned long long cap, int *flag, hipStream_t st);
+// plan_kernel.hip: the plan of a noisy-region pass over device-resident chunks (all regions of all chunks of a call in one grid)
+void lcd_launch_plan_count(const PlanChunk *chunks, const PlanReg *regs, int n_regs, int max_cov, int *cnt, int *status, hipStream_t st);
+void lcd_launch_plan_scan(const int *cnt, int n_regs, unsigned long long *off, hipStream_t st);   // exclusive scan, off[n_regs] = the total
+void lcd_launch_plan_fill(const PlanChunk *chunks, const PlanReg *regs, int n_regs, const int *status, const unsigned long long *off, int *read_ids, int *pair_reg,
+                          hipStream_t st);
+void lcd_launch_plan_slices(const PlanChunk *chunks, const PlanReg *regs, const int *read_ids, const int *pair_reg, unsigned long long n_pairs, int flank,
+                            SliceOut *outs, hipStream_t st);

@@ -345,3 +345,16 @@ struct CvOpt { int min_dp, min_alt_dp, min_bq, min_sv_len, max_xgaps, pad; doubl
 // back); map / alleles / alt_qi: absolute device addresses of the source's index map (old or region variant index -> merged index, -1 = dropped), of its n
 // alleles and of its n alt_qi values (0: every cell gets -1); first: variant index of the source's first cell; cell0: the source's first lane in the scatter
 struct MvSrc { uint64_t map, alleles, alt_qi; int chunk, read, first, n; unsigned long long cell0; };
+
+// ---- the plan of a noisy-region pass (plan_kernel.hip): which reads overlap which pending region, and each pair's slice ----
+// PlanRead: what a chunk keeps per read in HBM for the plan (uploaded once): digar->beg / end, the read's first DigarRec and their number, qlen, status (0 / -1 / -2)
+struct PlanRead { long long beg, end; unsigned long long digar_off; int n_digar, qlen, status, pad; };
+// one chunk of a call: absolute device addresses of its PlanRead table, of the call's copy of ordered_read_ids / is_skipped and of the chunk's digars
+struct PlanChunk { uint64_t reads, order, skipped, digars; int n_reads, pad; };
+// one region of a call: the clamped interval, its chunk (index into the call's PlanChunk table) and the status the host decided (LCD_PLAN_SUBMIT = pending)
+struct PlanReg { long long beg, end; int chunk, status; };
+#define LCD_PLAN_DONE_BEFORE 0
+#define LCD_PLAN_SKIP_LONG 1
+#define LCD_PLAN_SKIP_DEEP 2
+#define LCD_PLAN_NO_READS 3
+#define LCD_PLAN_SUBMIT 4
