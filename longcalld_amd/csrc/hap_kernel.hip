@@ -6,7 +6,10 @@
 //   * the phase-set walk (:388-419) is a serial prefix over the valid variants.
 // What is not order-dependent is data-parallel: adjacent-het agree/conflict counts (one lane per read, integer atomics),
 // the re-assignment of every read (:436-447; the "fill the missing consensus with 1-other" side effect of
-// read_to_cons_allele_score :141-142 is idempotent, so lanes may apply it concurrently), the per-variant arg-max (:449-453).
+// read_to_cons_allele_score :141-142 is safe under concurrent lanes: a filled haplotype is never filled again, and the partner it is
+// computed from is itself != -1 and so is never written in this pass -- every lane that fills computes the same value from the same
+// unchanged partner, and a lane that reads the slot sees either -1, and fills its own copy with that value, or the value; with the
+// partner at allele 2 the "fill" is -1 again and both outcomes score 0), the per-variant arg-max (:449-453).
 // Semantics are defined by oracle/assign_hap.c; integer results must match it bit for bit.
 #include <hip/hip_runtime.h>
 #include "lcd_types.h"
@@ -31,8 +34,9 @@ __device__ __forceinline__ void score_var(const HapProb &P, int v, int cate, int
     if (c1 == -1 && c2 == -1) { s1 = 0; s2 = 0; return; }
     if (c1 == -1) { c1 = 1 - c2; CONS(v, 1) = c1; }
     if (c2 == -1) { c2 = 1 - c1; CONS(v, 2) = c2; }
-    s1 = c1 == al ? var_score : -var_score;
-    s2 = c2 == al ? var_score : -var_score;
+    // three-way result (:143-146): a consensus that is still -1 after the fill (the other haplotype holds allele 2: 1 - 2 == -1) scores 0, not -var_score
+    s1 = c1 == al ? var_score : c1 == -1 ? 0 : -var_score;
+    s2 = c2 == al ? var_score : c2 == -1 ? 0 : -var_score;
 }
 
 // update_var_hap_to_cons_alle (:244-268)

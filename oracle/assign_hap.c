@@ -24,6 +24,14 @@ typedef lcdo_hap_problem_t P;
 #define CONS(p, v, h) (p)->hap_to_cons_alle[(v) * 3 + (h)]
 #define ALLELE(p, r, v) (p)->alleles[(p)->allele_off[r] + ((v) - (p)->start_var_idx[r])]
 
+/* optional branch counters (lcdo_assign_hap_germline_trace): which paths one call took.  Bookkeeping only -- no counter feeds back into the result.
+ * The pointer travels in a thread-local and not as a parameter, so that the functions below keep the reference's signatures.  It is set and cleared
+ * in lcdo_assign_hap_germline_trace alone, around its one call of lcdo_assign_hap_germline: that wrapper has a single return, after the clear, and
+ * nothing under it calls back into either entry point.  Whoever adds a return path or a nested call there must clear g_tr on it as well, or the next
+ * plain call on this thread would count into a trace that no longer exists. */
+static __thread lcdo_hap_trace_t *g_tr = NULL;
+#define TR(stmt) do { if (g_tr) { stmt; } } while (0)
+
 /* src/assign_hap.c:23-36 */
 static int init_max_cov_allele(const P *p, int v) {
     if (p->is_ont == 1 && p->is_homopolymer_indel[v]) return -1;
@@ -43,7 +51,7 @@ static int read_to_cons_allele_score(P *p, int hap, int v, int cate, int allele_
         if (CONS(p, v, 3 - hap) == -1) CONS(p, v, 3 - hap) = 1 - CONS(p, v, hap);
     }
     if (CONS(p, v, hap) == allele_i) return var_score;
-    else if (CONS(p, v, hap) == -1) return 0;
+    else if (CONS(p, v, hap) == -1) { TR(g_tr->n_zero_after_fill++); return 0; }
     else return -var_score;
 }
 
@@ -51,6 +59,7 @@ static int read_to_cons_allele_score(P *p, int hap, int v, int cate, int allele_
 static int init_assign_read_hap(P *p, int r, int target) {
     int hap_scores[3] = {0, 0, 0}, n_used[3] = {0, 0, 0}, agree[3] = {0, 0, 0}, conflict[3] = {0, 0, 0};
     p->n_clean_agree_snps[r] = p->n_clean_conflict_snps[r] = 0;
+    TR(const int span = p->end_var_idx[r] - p->start_var_idx[r] + 1; if (span > 64) g_tr->n_scored_gt64++; if (span > 128) g_tr->n_scored_gt128++);
     for (int v = p->start_var_idx[r]; v <= p->end_var_idx[r]; ++v) {
         const int cate = p->var_cate[v];
         if ((cate & target) == 0) continue;
@@ -71,8 +80,8 @@ static int init_assign_read_hap(P *p, int r, int target) {
         if (hap_scores[hap] > max_score) { max_hap = hap; max_score = hap_scores[hap]; }
         else if (hap_scores[hap] < min_score) { min_hap = hap; min_score = hap_scores[hap]; }
     }
-    if (n_used[1] == 0 && n_used[2] == 0) return -1;
-    else if (max_score == 0 && min_score == 0) return 0;
+    if (n_used[1] == 0 && n_used[2] == 0) { TR(g_tr->n_hap0_unused++); return -1; }
+    else if (max_score == 0 && min_score == 0) { TR(g_tr->n_hap0_both_zero++); return 0; }
     else if (max_score > 0) { p->n_clean_agree_snps[r] = agree[max_hap]; p->n_clean_conflict_snps[r] = conflict[max_hap]; return max_hap; }
     else return 3 - min_hap;
 }
@@ -85,7 +94,9 @@ static void update_var_hap_to_cons_alle(P *p, int v, int hap) {
         total += PROF(p, hap, v, i);
         if (PROF(p, hap, v, i) > max_cov) { max_cov = PROF(p, hap, v, i); mi = i; }
     }
+    TR(if (p->is_ont && p->is_homopolymer_indel[v] == 1) { const long d = (long)max_cov * 100 - (long)total * 67; if (d >= -1 && d <= 1) g_tr->n_ont_hp_near++; if (max_cov < total * 0.67) g_tr->n_ont_hp_reject++; });
     if (p->is_ont && p->is_homopolymer_indel[v] == 1 && max_cov < total * 0.67) mi = -1;
+    TR(if (mi >= 2) g_tr->n_cons_ge2++);
     CONS(p, v, hap) = mi;
 }
 
@@ -148,9 +159,10 @@ static int iter_update_phase_set(P *p, const int *var_idx, int n) {
         const int v = var_idx[i];
         if (i == 0) { phase_set = p->var_type[v] == LCDO_CDIFF ? p->var_pos[v] : p->var_pos[v] - 1; p->var_phase_set[v] = phase_set; continue; }
         if (is_het[i] == 1) {
-            if (n_agree[i] < 2 && n_conflict[i] < 2) phase_set = p->var_type[v] == LCDO_CDIFF ? p->var_pos[v] : p->var_pos[v] - 1;
+            if (n_agree[i] < 2 && n_conflict[i] < 2) { TR(g_tr->n_ps_breaks++); phase_set = p->var_type[v] == LCDO_CDIFF ? p->var_pos[v] : p->var_pos[v] - 1; }
             else if (n_conflict[i] > n_agree[i]) flip ^= 1;
             if (flip == 1) {
+                TR(g_tr->n_flip_visits++);
                 changed = 1;
                 for (int hap = 1; hap <= 2; ++hap) { int t = CONS(p, v, hap); CONS(p, v, hap) = CONS(p, v, 3 - hap); CONS(p, v, 3 - hap) = t; } /* two swaps == identity, :406-411 */
             }
@@ -169,11 +181,12 @@ static int iter_update_cons_alle(P *p, const int *var_idx, int n, int target) {
         const int v = var_idx[i];
         for (int h = 0; h <= 2; ++h) for (int a = 0; a < NALLE(p, v); ++a) PROF(p, h, v, a) = 0;
     }
+    TR(g_tr->n_hap0_unused = g_tr->n_hap0_both_zero = 0); /* the two counters describe the last pass over the reads: where each read ended */
     for (int i = 0; i < p->n_reads; ++i) {
         const int r = p->ordered_read_ids[i];
         if (p->is_skipped[r]) continue;
         int hap = (p->start_var_idx[r] < 0) ? -1 : init_assign_read_hap(p, r, target);
-        if (p->start_var_idx[r] < 0) { p->n_clean_agree_snps[r] = p->n_clean_conflict_snps[r] = 0; }
+        if (p->start_var_idx[r] < 0) { p->n_clean_agree_snps[r] = p->n_clean_conflict_snps[r] = 0; TR(g_tr->n_hap0_unused++); } /* :441 calls it on an empty span: "nothing used" */
         if (hap == -1) hap = 0;
         p->haps[r] = hap;
         if (p->start_var_idx[r] >= 0) update_profile_by_read(p, r, hap, target);
@@ -190,6 +203,7 @@ int lcdo_assign_hap_germline(lcdo_hap_problem_t *p, int target) {
     int n = 0, *valid = (int *)malloc((p->n_vars > 0 ? p->n_vars : 1) * sizeof(int));
     uint8_t *is_valid = (uint8_t *)calloc(p->n_vars > 0 ? p->n_vars : 1, 1);
     for (int i = 0; i < p->n_vars; ++i) if (p->var_cate[i] & target) { valid[n++] = i; is_valid[i] = 1; }
+    TR(g_tr->n_valid = n);
     if (n == 0) { free(valid); free(is_valid); return 0; }
     for (int r = 0; r < p->n_reads; ++r) { p->haps[r] = 0; p->phase_sets[r] = -1; }            /* :16-20 */
     for (int i = 0; i < n; ++i) {                                                                /* :39-63 */
@@ -213,6 +227,7 @@ int lcdo_assign_hap_germline(lcdo_hap_problem_t *p, int target) {
             }
         }
         init = ci != -1 ? ci : ii != -1 ? ii : ns != -1 ? ns : ni;
+        TR(g_tr->seed_index = init; g_tr->seed_class = ci != -1 ? 0 : ii != -1 ? 1 : ns != -1 ? 2 : ni != -1 ? 3 : -1);
     }
     if (init != -1) {
         int *vii = (int *)malloc(n * sizeof(int));
@@ -226,6 +241,7 @@ int lcdo_assign_hap_germline(lcdo_hap_problem_t *p, int target) {
                 const int r = p->cr_read[c];
                 if (!(p->start_var_idx[r] < v + 1 && v < p->end_var_idx[r] + 1)) continue;
                 if (p->is_skipped[r] || p->haps[r] != 0) continue;
+                TR(const int span = p->end_var_idx[r] - p->start_var_idx[r] + 1; if (span > 64) g_tr->n_seed_gt64++; if (span > 128) g_tr->n_seed_gt128++);
                 int hap = init_assign_read_hap(p, r, target);
                 if (hap == -1) hap = 1;
                 p->haps[r] = hap;
@@ -237,6 +253,7 @@ int lcdo_assign_hap_germline(lcdo_hap_problem_t *p, int target) {
     for (int it = 0; it < 10; ++it) {
         int c1 = iter_update_phase_set(p, valid, n);
         int c2 = iter_update_cons_alle(p, valid, n, target);
+        TR(g_tr->n_iters = it + 1; g_tr->hit_cap = it == 9 && (c1 || c2));
         if (c1 == 0 && c2 == 0) break;
     }
     for (int i = 0; i < p->n_reads; ++i) { /* update_read_phase_set :322-339 */
@@ -253,6 +270,14 @@ int lcdo_assign_hap_germline(lcdo_hap_problem_t *p, int target) {
     }
     free(valid); free(is_valid);
     return 0;
+}
+
+int lcdo_assign_hap_germline_trace(lcdo_hap_problem_t *p, int target, lcdo_hap_trace_t *trace) {
+    if (trace) { memset(trace, 0, sizeof(*trace)); trace->seed_class = trace->seed_index = -1; }
+    g_tr = trace;
+    const int rc = lcdo_assign_hap_germline(p, target);
+    g_tr = NULL;
+    return rc;
 }
 
 /* ---- cgranges order: cr_is_sorted() ? as added : radix_sort_cr_intv (src/cgranges.c:13-86; RS_MIN_SIZE 64, RS_MAX_BITS 8, key = x) ---- */

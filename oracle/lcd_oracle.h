@@ -256,6 +256,20 @@ typedef struct {
     int *hap_to_alle_profile;        /* 3 planes of alle_off[n_vars] ints: [h*total + alle_off[v] + a] */
 } lcdo_hap_problem_t;
 int lcdo_assign_hap_germline(lcdo_hap_problem_t *p, int target_var_cate);
+/* the same call with branch counters: which paths of src/assign_hap.c this input took (tests use it to prove that a crafted case reaches its branch) */
+typedef struct {
+    int n_valid;                        /* variants in the target categories */
+    int seed_class, seed_index;         /* select_init_var: 0 clean het SNP, 1 clean het indel, 2 noisy het SNP, 3 noisy het non-homopolymer indel, -1 none; index in valid[] */
+    int n_scored_gt64, n_scored_gt128;  /* init_assign_read_hap calls on a read spanning more than 64 / 128 variants (both passes) */
+    int n_seed_gt64, n_seed_gt128;      /* ... of these, in the seeding pass */
+    int n_zero_after_fill;              /* read_to_cons_allele_score returned 0 after the fill (consensus still -1, i.e. the other haplotype holds allele 2) */
+    int n_cons_ge2;                     /* update_var_hap_to_cons_alle stored a consensus allele >= 2 */
+    int n_ont_hp_reject, n_ont_hp_near; /* ONT homopolymer indel: max_cov < total * 0.67 true; evaluations with |max_cov * 100 - total * 67| <= 1 */
+    int n_flip_visits, n_ps_breaks;     /* het variants visited with flip == 1; phase sets started at a het variant after the first */
+    int n_iters, hit_cap;               /* iterations run; the loop ended on the cap of 10 with a change still pending */
+    int n_hap0_both_zero, n_hap0_unused;/* last re-assignment pass: reads left at hap 0 with both scores zero / with no variant used (reads without a span included) */
+} lcdo_hap_trace_t;
+int lcdo_assign_hap_germline_trace(lcdo_hap_problem_t *p, int target_var_cate, lcdo_hap_trace_t *trace);
 
 /* ---------------- update_digars_from_msa1 (oracle/digar_rewrite.c) ---------------- */
 int lcdo_update_digars_from_msa1(const lcdo_digar_t *digars, int n_digar, int qlen, int msa_len, const uint8_t *ref_str, const uint8_t *read_str, int full_cover,

@@ -519,8 +519,15 @@ class HapProblem(C.Structure):
                 ("n_clean_conflict_snps", i32p), ("var_phase_set", _i64p), ("hap_to_cons_alle", i32p), ("hap_to_alle_profile", i32p)]
 
 
-def assign_hap_germline(prob, target_var_cate, state=None):
-    """K5 oracle (oracle/assign_hap.c) on the same flattened problem dict the HIP mirror takes"""
+class HapTrace(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("n_valid", "seed_class", "seed_index", "n_scored_gt64", "n_scored_gt128", "n_seed_gt64", "n_seed_gt128", "n_zero_after_fill",
+                                       "n_cons_ge2", "n_ont_hp_reject", "n_ont_hp_near", "n_flip_visits", "n_ps_breaks", "n_iters", "hit_cap", "n_hap0_both_zero",
+                                       "n_hap0_unused")]
+
+
+def assign_hap_germline(prob, target_var_cate, state=None, trace=False):
+    """K5 oracle (oracle/assign_hap.c) on the same flattened problem dict the HIP mirror takes; trace=True -> (state, dict of the branch counters of
+    lcdo_hap_trace_t: which paths of src/assign_hap.c this call took)"""
     R, V, TA = prob["n_reads"], prob["n_vars"], int(prob["alle_off"][-1])
     state = state or dict(haps=np.zeros(R, np.int32), phase_sets=np.full(R, -1, np.int64), n_clean_agree_snps=np.zeros(R, np.int32),
                           n_clean_conflict_snps=np.zeros(R, np.int32), var_phase_set=np.full(V, -1, np.int64),
@@ -543,6 +550,11 @@ def assign_hap_germline(prob, target_var_cate, state=None):
                      ("hap_to_cons_alle", i32p), ("hap_to_alle_profile", i32p)):
         setattr(s, name, state[name].ctypes.data_as(ty))
     L = lib()
+    if trace:
+        t = HapTrace()
+        L.lcdo_assign_hap_germline_trace.argtypes = [C.POINTER(HapProblem), C.c_int, C.POINTER(HapTrace)]
+        L.lcdo_assign_hap_germline_trace(C.byref(s), int(target_var_cate), C.byref(t))
+        return state, {k: getattr(t, k) for k, _ in HapTrace._fields_}
     L.lcdo_assign_hap_germline.argtypes = [C.POINTER(HapProblem), C.c_int]
     L.lcdo_assign_hap_germline(C.byref(s), int(target_var_cate))
     return state
