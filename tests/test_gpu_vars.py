@@ -1,10 +1,14 @@
 """SURVEY 8(f) f1 on the GPU: candidate variants + read x variant profile of a region (stage S6, vars_kernel.hip through
 lcd_batch_region_vars) vs the oracle's restatement of make_vars_from_msa_cons_aln (src/collect_var.c:2279) run on the oracle's strings --
-every field bit-identical, on seeded synthetic regions (HiFi / ONT shapes, K1 and K2 branches) and on the reference's bundled real chunk."""
+every field bit-identical, on seeded synthetic regions (HiFi / ONT shapes, K1 and K2 branches), on the reference's bundled real chunk and on the
+planted-variant cases of tests/vars_cases.py (tests/test_vars_cases_oracle.py shows on the CPU which edge each of those reaches)."""
+import functools
+
 import numpy as np
 import pytest
 
 import testdata_common as tc
+import vars_cases as vc
 
 pytestmark = pytest.mark.gpu
 
@@ -110,5 +114,78 @@ def test_vars_joint_submission(lcd, oracle):
         for k, r in enumerate(regs):
             res = oracle.collect_noisy_reg_aln_strs(r)
             same_vars(oracle.make_vars_from_msa_cons_aln(res, 500, r["ref"], 500), b.region_vars(k, 500, r["ref"], 500))
+    for b in reversed(bs):
+        b.close()
+
+
+# ---------------------------------------------------------------- planted-variant cases (tests/vars_cases.py) ----------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _expected(oracle, name, gap_aln):
+    """the oracle's (variants, row read ids) of a case, computed once and shared"""
+    res, exp = vc.through_oracle(oracle, vc.cases()[name], gap_aln)
+    return exp, [res["clu_read_ids"][c] for c in range(res["n_cons"])]
+
+
+def _case_opt(lcd, mode, gap_aln=1):
+    o = _opt(lcd, mode)
+    o.gap_aln = gap_aln
+    return o
+
+
+def _same_case(oracle, b, k, name, gap_aln=1):
+    case = vc.cases()[name]
+    exp, ids = _expected(oracle, name, gap_aln)
+    same_vars(exp, b.region_vars(k, case["beg"], case["chunk_ref"], case["chunk_ref_beg"]), ids)
+
+
+@pytest.mark.parametrize("name", vc.CASE_NAMES)
+def test_vars_planted_case(lcd, oracle, name):
+    """one case, one batch, with the gap side the case asks for: every field and row_read_ids as the oracle has them"""
+    case = vc.cases()[name]
+    b = lcd.RegionBatch(_case_opt(lcd, 1, case["gap_aln"]))
+    b.add_region(case["region"])
+    b.upload(); b.run(); b.download()
+    _same_case(oracle, b, 0, name, case["gap_aln"])
+    b.close()
+
+
+def test_vars_planted_cases_share_launches(lcd, oracle):
+    """every case in one batch (many scan and profile jobs per launch, packed work buffers; the one-consensus and the no-variant regions sit between the
+    others), then the same cases dealt over two batches of one lcd_batch_run_many, once with collect_noisy_vars == 1 and once with == 2 (strings left in
+    HBM): each region's result is what the region gives alone.  The batches of one joint submission share their options (lcd_batch_run_many checks it before
+    anything is launched), so a pair with 1 and 2 mixed is refused and the two modes take one submission each."""
+    from longcalld_amd._lib import LcdError
+    names = list(vc.CASE_NAMES)
+    b = lcd.RegionBatch(_case_opt(lcd, 1))
+    for name in names:
+        b.add_region(vc.cases()[name]["region"])
+    b.upload(); b.run(); b.download()
+    for k, name in enumerate(names):
+        _same_case(oracle, b, k, name)
+    b.close()
+    halves = [names[0::2], names[1::2]]
+
+    def pair(modes):
+        bs = []
+        for mode, part in zip(modes, halves):
+            b = lcd.RegionBatch(_case_opt(lcd, mode))
+            for name in part:
+                b.add_region(vc.cases()[name]["region"])
+            b.upload(); bs.append(b)
+        return bs
+
+    for mode in (1, 2):
+        bs = pair((mode, mode))
+        lcd.RegionBatch.run_many(bs)
+        for b in bs:
+            b.download()
+        for b, part in zip(bs, halves):
+            for k, name in enumerate(part):
+                _same_case(oracle, b, k, name)
+        for b in reversed(bs):
+            b.close()
+    bs = pair((1, 2))
+    with pytest.raises(LcdError, match="different options"):
+        lcd.RegionBatch.run_many(bs)
     for b in reversed(bs):
         b.close()
