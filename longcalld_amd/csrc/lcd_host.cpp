@@ -1,4 +1,5 @@
-// lcd_host.cpp -- host orchestration + C ABI of liblcd_hotpath.so (compiled with hipcc, HIP runtime only).
+// lcd_host.cpp -- the region-batch pipeline of liblcd_hotpath.so: host orchestration of a submission + its C ABI (compiled with hipcc, HIP runtime only).
+// The runtime core, the per-call entry points, the interval code, the chunk and the collect_var_main port are in the files beside it (DESIGN "Source map").
 //
 // Host glue kept in C++ because the reference's glue is compiled C (src/align.c): read ordering
 // (sort_noisy_region_reads :955), phase-set choice (:1225), homopolymer test (:1000), anchor windows
@@ -8,204 +9,17 @@
 //
 // All *_off fields handed to kernels are absolute device addresses (kernels get nullptr bases), so every
 // stage can live in its own grow-only hipMalloc buffer.
-#include <hip/hip_runtime.h>
-#include <sched.h>
 #include <sys/mman.h>
-#include <algorithm>
-#include <atomic>
 #include <array>
-#include <chrono>
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include <numeric>
-#include <string>
-#include <thread>
-#include <vector>
 #include <map>
-#include <memory>
-#include "../../include/lcd_hotpath.h"
-#include "lcd_kernels.h"
-#include "lcd_types.h"
-#include "lcd_io_internal.h"
+#include "lcd_host_internal.h"
+
+using namespace lcd_internal;
 
 namespace {
-
-thread_local std::string g_err;
-int set_err(int code, const std::string &m) { g_err = m; return code; }
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { return set_err(-10, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-
-std::mutex g_init_mu;
-#define LCD_MAX_DEV 16
-int g_device = -1;                 // the process default device (lcd_init, else LOCAL_RANK % n, else 0)
-int g_n_devices = 0;
-thread_local int t_device = -1;    // lcd_set_thread_device: the device of this thread's per-call entry points and of the batches it creates
-
-int g_n_cus = 256; // compute units of the device (MI355X: 256)
-// One process may drive every GPU of the node (the reference's kt_for workers are threads of ONE process, src/call_var_main.c:773): a device belongs
-// to an lcd_batch_t (lcd_batch_create_on) or, for the per-call mirrors, to the calling thread (lcd_set_thread_device); nothing is process-global
-// except the default.  HIP's current device is per host thread, so every entry point selects its device first.
-// GPU_MAX_HW_QUEUES: a submission uses a pool of 4 streams; with more hardware queues holding runnable kernels the queue scheduler time-slices
-// them (DESIGN section 4 "Submission").  The host sets GPU_MAX_HW_QUEUES=4 in its environment before its first HIP call; the library
-// does not touch the environment of the process it is loaded into.
-int init_default_device() {
-    std::lock_guard<std::mutex> lk(g_init_mu);
-    if (g_device >= 0) return 0;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { (void)hipGetLastError(); return set_err(-1, "liblcd_hotpath: no HIP device visible (this library has no CPU path)"); }
-    int dev = 0;
-    const char *lr = getenv("LOCAL_RANK");
-    if (lr) dev = atoi(lr) % n;
-    g_n_devices = n;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) g_n_cus = prop.multiProcessorCount;
-    g_device = dev;
-    return 0;
-}
-int use_device(int dev) {
-    if (init_default_device()) return -1;
-    if (dev < 0) dev = t_device >= 0 ? t_device : g_device;
-    if (dev >= g_n_devices) return set_err(-1, "bad device index " + std::to_string(dev));
-    if (hipSetDevice(dev) != hipSuccess) { (void)hipGetLastError(); return set_err(-1, "hipSetDevice failed"); }
-    return 0;
-}
-int ensure_init() { return use_device(-1); }
-int cur_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; } return d < LCD_MAX_DEV ? d : 0; }
-
-// Device memory budget: the library keeps its grow-only buffers under ~92 % of each device (the HIP runtime allocates kernel scratch and
-// queue resources lazily at dispatch time -- with HBM full a launch aborts the queue with HSA_STATUS_ERROR_OUT_OF_RESOURCES instead of
-// returning an error).  A request over the budget fails like an out-of-memory hipMalloc (-11); lcd_batch_run_many then splits.
-std::atomic<long long> g_dev_bytes[LCD_MAX_DEV];
-std::atomic<long long> g_dev_budget[LCD_MAX_DEV];
-std::once_flag g_budget_once[LCD_MAX_DEV];
-std::atomic<unsigned long long> g_copy_bytes[4]; // [0] digars device -> host, [1] digars host -> device, [2] read bases host -> device (packed or unpacked), [3] read bases device -> host
-std::atomic<long long> g_alloc_events{0}; // hipMalloc calls of the grow-only buffers (bench.py reports how many fell into its timed region)
-long long dev_budget(int d) {
-    std::call_once(g_budget_once[d], [d] {
-        size_t fr = 0, tot = 0;
-        g_dev_budget[d] = (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) ? (long long)((double)tot * (getenv("LCD_MEM_FRACTION") ? atof(getenv("LCD_MEM_FRACTION")) : 0.92)) : (1ll << 62);
-        (void)hipGetLastError();
-    });
-    return g_dev_budget[d].load();
-}
-// grow-only PINNED host block (hipHostMalloc): the destination of a batch's result download -- a pageable destination is staged by the runtime at a few GB/s
-struct PinnedBuf {
-    uint8_t *p = nullptr; size_t n = 0, cap = 0;
-    void resize(size_t want) {
-        if (want > cap) {
-            if (p) hipHostFree(p);
-            p = nullptr; cap = 0;
-            const size_t c = want + (want >> 2) + 4096;
-            void *q = nullptr;
-            if (hipHostMalloc(&q, c, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); q = malloc(c); pageable = true; }
-            p = (uint8_t *)q; cap = c;
-        }
-        n = want;
-    }
-    bool pageable = false;
-    uint8_t *data() { return p; } const uint8_t *data() const { return p; } size_t size() const { return n; }
-    ~PinnedBuf() { if (p) { if (pageable) free(p); else hipHostFree(p); } }
-    PinnedBuf() = default; PinnedBuf(const PinnedBuf &) = delete; PinnedBuf &operator=(const PinnedBuf &) = delete;
-};
-struct DevBuf {
-    void *p = nullptr; size_t cap = 0; int dev = 0;
-    int ensure(size_t n, int headroom_shift = 2) {
-        if (n <= cap) return 0;
-        release();
-        dev = cur_device();
-        const long long budget = dev_budget(dev);
-        size_t want = n + (n >> headroom_shift) + 256; // (headroom: the buffers only grow, a slightly larger next batch does not reallocate)
-        // the budget is RESERVED before the allocation (compare-exchange): the submission's helper threads grow buffers beside the calling thread
-        auto reserve = [&](const size_t bytes) { long long cur = g_dev_bytes[dev].load(); while (cur + (long long)bytes <= budget) if (g_dev_bytes[dev].compare_exchange_weak(cur, cur + (long long)bytes)) return true; return false; };
-        if (!reserve(want)) { want = n + 256; if (!reserve(want)) return set_err(-11, "device memory budget: " + std::to_string(want) + " more bytes on top of " + std::to_string(g_dev_bytes[dev].load())); }
-        if (hipMalloc(&p, want) != hipSuccess) {
-            (void)hipGetLastError(); // out-of-memory is not sticky, but the "last error" slot is read after every launch
-            g_dev_bytes[dev] -= (long long)want;
-            p = nullptr; cap = 0; return set_err(-11, "hipMalloc failed for " + std::to_string(want) + " bytes");
-        }
-        if (getenv("LCD_ALLOC_DEBUG")) fprintf(stderr, "[alloc] %zu bytes asked, %zu allocated (device %d now %.2f GB)\n", n, want, dev, g_dev_bytes[dev].load() / 1e9);
-        cap = want; ++g_alloc_events; return 0;
-    }
-    void release() { if (p) { hipFree(p); g_dev_bytes[dev] -= (long long)cap; p = nullptr; cap = 0; } }
-    uint64_t addr() const { return (uint64_t)(uintptr_t)p; }
-    ~DevBuf() { release(); }
-    DevBuf() = default; DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
-};
-// an ad-hoc stream of a per-call entry point: destroyed on every return path
-struct StreamGuard {
-    hipStream_t s = nullptr;
-    int create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? 0 : set_err(-10, "hipStreamCreate failed"); }
-    ~StreamGuard() { if (s) hipStreamDestroy(s); }
-    operator hipStream_t() const { return s; }
-};
-struct PinBuf {
-    void *p = nullptr; size_t cap = 0;
-    int ensure(size_t n) {
-        if (n <= cap) return 0;
-        if (p) hipHostFree(p);
-        size_t want = n + n / 4 + 256;
-        if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) { p = nullptr; cap = 0; return set_err(-11, "hipHostMalloc failed"); }
-        cap = want; return 0;
-    }
-    ~PinBuf() { if (p) hipHostFree(p); }
-};
-
-double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// host threads per team of the submission's short parallel loops (capacities, job tables, records, plans).  LCD_HOST_TEAM, read per call: a caller whose own
-// threads are busy beside the submission -- bench.py's PCIe-inclusive pipeline on a box whose cgroup allows 16 CPUs -- asks for fewer; a team that overruns the
-// quota freezes every thread of the process, the submitter included, until the next period
-// CPUs this process may use: its affinity mask, cut by the cgroup's CPU quota (v2 cpu.max, v1 cpu.cfs_quota_us / cpu.cfs_period_us) -- a container with 128 visible
-// cores and a 16-CPU quota is a 16-CPU box for thread teams
-static int host_cpus() {
-    static const int n = [] {
-        int k = 0;
-        cpu_set_t set; CPU_ZERO(&set);
-        if (sched_getaffinity(0, sizeof(set), &set) == 0) k = CPU_COUNT(&set);
-        if (k <= 0) k = (int)std::max(1u, std::thread::hardware_concurrency());
-        double quota = 0;
-        if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) { char a[64] = {0}; long long per = 0; if (fscanf(f, "%63s %lld", a, &per) == 2 && strcmp(a, "max") != 0 && per > 0) quota = atof(a) / (double)per; fclose(f); }
-        else {
-            long long q = -1, per = 0;
-            if (FILE *fq = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) { if (fscanf(fq, "%lld", &q) != 1) q = -1; fclose(fq); }
-            if (FILE *fp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(fp, "%lld", &per) != 1) per = 0; fclose(fp); }
-            if (q > 0 && per > 0) quota = (double)q / (double)per;
-        }
-        if (quota > 0) k = std::max(1, std::min(k, (int)(quota + 0.5)));
-        return k;
-    }();
-    return n;
-}
-// processes of this job on this host: one per GPU under torch.distributed.run (LOCAL_WORLD_SIZE; WORLD_SIZE on a single node)
-static int host_local_world() {
-    const char *e = getenv("LOCAL_WORLD_SIZE"); if (!e || atoi(e) < 1) e = getenv("WORLD_SIZE");
-    const int w = e ? atoi(e) : 1;
-    return w < 1 ? 1 : w;
-}
-// With N ranks on one host every rank runs these teams at the same moments (the ranks step together): the default is the host's CPUs divided by the ranks, at most 8.
-static int host_team() {
-    const char *e = getenv("LCD_HOST_TEAM");
-    const int v = e ? atoi(e) : std::min(8, std::max(1, host_cpus() / host_local_world()));
-    return v < 1 ? 1 : v > 32 ? 32 : v;
-}
-// (threads that lay results out on the host, lcd_batch_results_arena: LCD_ARENA_THREADS, default 16 -- or the rank's share of the host's CPUs)
-static int host_arena_threads() {
-    const char *e = getenv("LCD_ARENA_THREADS");
-    return e ? std::max(1, atoi(e)) : std::min(16, std::max(1, host_cpus() / host_local_world()));
-}
-// a loop over [0, n) cut into chunks taken by up to `max_threads` host threads (the calling thread is one of them); f(lo, hi, thread index)
-template <class F> static void par_chunks(const size_t n, const int max_threads, const size_t chunk, F f) {
-    const int nth = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, max_threads), (n + chunk - 1) / std::max<size_t>(1, chunk)));
-    if (nth <= 1) { if (n) f((size_t)0, n, 0); return; }
-    std::atomic<size_t> next{0};
-    auto work = [&](const int t) { for (size_t lo; (lo = next.fetch_add(chunk)) < n;) f(lo, std::min(n, lo + chunk), t); };
-    std::vector<std::thread> ths;
-    for (int t = 1; t < nth; ++t) ths.emplace_back(work, t);
-    work(0);
-    for (auto &t : ths) t.join();
-}
 
 // ---------------- host glue (restating src/align.c; see cited lines) ----------------
 int full_cover_cmp(int c1, int c2) { // src/align.c:945-952
@@ -231,100 +45,6 @@ bool is_homopolymer(const uint8_t *seq, int seq_len, int flank) { // src/align.c
     }
     return hp_len >= 5;
 }
-
-struct RegRead { // one read of a region, in sorted order after add
-    int id, len, cover, hap; int64_t ps; uint64_t off; double err;
-    int rb = -1, re = -2; // read_reg_beg / read_reg_end of collect_noisy_read_info (chunk-view entry only)
-};
-struct ChainRec {
-    int region, clu;              // clu: hap-1 for K1, 0 for K2 (clusters come out of the kernel)
-    int mode;
-    std::vector<int> members;     // indices into the region's sorted read list
-    int read0;                    // first PoaRead
-    int cert_fail_round = -1;     // K2: the last round in which the certified band did not fit its class's window (the chain then moves one class up)
-    int solo = -1;                // -1: by the fixed threshold (LCD_SOLO_RL); 0 / 1: decided for the submission at hand (run_many_once: the longest chains of what is in flight)
-    int cert_level = -1;          // -1: not chosen yet; 1: certified band in the single-wavefront rows; 2: in the systolic rows of the class the reads' length asks for (noisy reads); 0: full rows
-};
-struct AnchorRec {
-    int pread;                    // index into preads
-    int ext;                      // 1 L->R, 2 R->L ; 0: sampling-mode full-read K4 filter only
-    int tlen_full, qlen_full;     // _tlen, _qlen
-    int ed_job, wfa_job;
-    int min_len;
-};
-struct RegionRec {
-    int64_t reg_len; int n_reads;
-    std::vector<RegRead> reads;   // sorted (src/align.c:1774)
-    uint64_t ref_off; int ref_len;
-    int branch;                   // 0 skipped, 1 with-PS (K1 x2), 2 no-PS (K2)
-    int sampling;
-    int chain[2];                 // chain indices (-1 none)
-    // results
-    int n_cons = 0;
-};
-
-struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
-struct OutStr { // one aln_str in the final output pool
-    uint64_t off; int stride; int aln_len, tb, te, qb, qe, shift; bool present;
-};
-
-} // namespace
-
-#define LCD_NSIDE 12
-struct lcd_batch_s {
-    lcd_opt_t opt;
-    int device = 0;                      // every entry point on this batch selects it (HIP's current device is per host thread)
-    hipStream_t stream = nullptr;
-    hipStream_t side[LCD_NSIDE] = {};
-    hipEvent_t ev[10];
-    hipEvent_t sev[LCD_NSIDE + 1];
-    std::vector<uint8_t> h_pool;
-    std::vector<UnpackJob> unpack_abs; DevBuf d_unpack_abs; uint64_t pool_read_bytes = 0; // slices whose packed bases are ALREADY in HBM (lcd_chunk_t): src = device address; read bases inside h_pool (the copy counter)
-    std::vector<uint8_t> h_packed; std::vector<UnpackJob> unpack_jobs; // read slices handed over 4-bit packed: unpacked into d_in after the upload
-    std::vector<RegionRec> regs;
-    std::vector<ChainRec> chains;
-    std::vector<PoaRead> preads;         // seq_off relative to h_pool until run()
-    std::vector<AnchorRec> anchors;
-    std::vector<EdJob> ed_jobs;          // offsets relative to h_pool until run()
-    std::vector<WfaJob> wfa_jobs;
-    // device
-    // (d_poa_arena: the ONE transient workspace of a submission led by this batch -- chain arenas, WFA wavefronts and edlib blocks in turn)
-    DevBuf d_read_patches, d_aends_jobs, d_aends_outs, d_in, d_chains, d_preads, d_poa_arena, d_poa_out, d_poa_outs, d_ed_jobs, d_ed_outs, d_wfa_jobs,
-        d_wfa_out, d_wfa_outs, d_str_jobs, d_str_outs, d_final, d_gate, d_cmp_jobs, d_cmp_outs, d_cmp_seg, d_cmp_segres, d_seg_out, d_rr,
-        d_var_jobs, d_var_outs, d_var_work, d_vreg_jobs, d_vreg_outs, d_var_out, d_slot_flags, d_spare, d_packed, d_unpack,
-        d_early_arena, d_chains_early, d_poa_outs_early,   // the long K2 chains that start before the anchor stage (run_many_once)
-        d_ed_arena;                                                         // K4's stored columns when it runs beside K3 in the anchor stage
-    bool uploaded = false, ran = false, downloaded = false;
-    // results (host)
-    std::vector<PoaChainOut> couts;
-    std::vector<PoaChain> pchains;
-    std::vector<WfaJob> rc_jobs; std::vector<WfaOut> rc_outs; // ref<->cons
-    std::vector<int> rc_region, rc_clu;
-    std::vector<uint32_t> reg_rc0, reg_str0;   // [n_regions + 1]: the ref<->cons / string jobs of region r are [reg_rc0[r], reg_rc0[r + 1]) and [reg_str0[r], reg_str0[r + 1]) (jobs are made region by region)
-    std::vector<StrJob> str_jobs; std::vector<StrOut> str_outs;
-    std::vector<int> str_region, str_clu, str_k;
-    PinnedBuf h_final; std::vector<uint8_t> h_poa_out; std::vector<uint8_t> h_cig;
-    PinnedBuf h_sub_pin, h_tmp_pin; // leader: the chain table of a round and the chains' output records (page-locked and kept: 7 + 9 MB per 20-batch round were allocated, zeroed and faulted in every time)
-    std::vector<std::pair<int, uint32_t>> clu_gather_index;
-    bool gathered = false; uint64_t g_extra = 0, g_clu_base = 0; std::vector<uint64_t> g_rc_off; // the scattered result pieces are already in d_gather (stage_gather at the end of the run): the download is copies only
-    DevBuf d_gather, d_gather_jobs; std::vector<std::pair<int, uint32_t>> clu_index;   // download: staging block of the scattered pieces; (chain, offset into h_poa_out) of the K2 cluster lists
-    std::vector<WfaJob> h_rc_all; std::vector<StrJob> h_str_all; std::vector<StrOut> h_str_outs; // leader: the joint job tables of a submission (kept between submissions: no reallocation, no first-touch page faults in the steady state)
-    // ref<->read strings (opt.collect_ref_read_aln_str): per string job, rows in d_rr at rr_off (target row, query row at +rr_stride)
-    std::vector<uint64_t> rr_off; std::vector<int> rr_len, rr_stride; std::vector<uint8_t> h_rr; uint64_t rr_bytes = 0;
-    // candidate variants (opt.collect_noisy_vars): per resolved region, offsets into d_var_out / h_var
-    std::vector<VarRegionRec> vregs; std::vector<int> vreg_of; std::vector<uint8_t> h_var; uint64_t var_bytes = 0;
-    std::vector<std::unique_ptr<DevBuf>> retry_out; // output blocks of chains re-run with a larger graph capacity (live until the next run; the buffers
-    size_t retry_out_used = 0;                      // themselves are kept and re-used: freeing ~60 of them per noisy-read submission synchronised the device each time)
-    // the chains' work arenas live in d_poa_arena and, when a later submission needs more, in additional chunks: growing by a chunk costs the difference,
-    // re-allocating tens of GB costs seconds (and the pools' slot sizes make the total jump by a third from one set of chunks to the next)
-    std::vector<std::unique_ptr<DevBuf>> arena_extra;
-    uint64_t final_bytes = 0;
-    lcd_batch_stats_t st;
-};
-
-namespace {
-
-LcdScoring scoring_of(const lcd_opt_t &o) { LcdScoring s; s.match = o.match; s.mismatch = o.mismatch; s.o1 = o.gap_open1; s.e1 = o.gap_ext1; s.o2 = o.gap_open2; s.e2 = o.gap_ext2; s.dbg = getenv("LCD_DBG") ? atoi(getenv("LCD_DBG")) : 0; s.wd_s = getenv("LCD_WATCHDOG_S") ? atoi(getenv("LCD_WATCHDOG_S")) : 0; return s; }
 
 std::atomic<int> g_wfa_hint{0}; // 0..2: learned from the overflow retries of earlier ANCHOR stages (read vs read windows of noisy reads)
 // first score bound of a job (WfaJob.s_cap on entry of run_wfa_stage; overflow -> x4 + 64): the length difference as one long gap plus a little
@@ -517,34 +237,6 @@ void lcd_opt_default(lcd_opt_t *o) {
     o->gap_aln = 1; o->min_af = 0.20; o->min_dp = 5; o->partial_aln_ratio = 1.1;
     o->min_noisy_reg_size_to_sample_reads = 10000; o->max_noisy_reg_len = 50000; o->noisy_reg_flank_len = 10;
     o->min_hap_full_reads = 1; o->min_hap_reads = 2; o->collect_ref_read_aln_str = 0; o->is_ont = 0; o->collect_noisy_vars = 0; o->min_sv_len = 30; // LONGCALLD_MIN_SV_LEN, src/call_var_main.h:54
-}
-int lcd_init(int device) { // the process default device (bench.py: LOCAL_RANK); batches and threads may choose another one
-    if (init_default_device()) return -1;
-    std::lock_guard<std::mutex> lk(g_init_mu);
-    if (device < 0 || device >= g_n_devices) return set_err(-1, "bad device index");
-    if (hipSetDevice(device) != hipSuccess) return set_err(-1, "hipSetDevice failed");
-    g_device = device;
-    return 0;
-}
-long long lcd_alloc_events(void) { return g_alloc_events.load(); }
-void lcd_copy_counters(unsigned long long out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_copy_bytes[i].load(); }
-void lcd_account_device_bytes(int device, long long delta) { if (device >= 0 && device < LCD_MAX_DEV) g_dev_bytes[device] += delta; } // (buffers allocated outside DevBuf: lcd_io.cpp's inflated streams)
-long long lcd_device_bytes(int device) { return device >= 0 && device < LCD_MAX_DEV ? g_dev_bytes[device].load() : 0; }
-int lcd_device_count(void) { return init_default_device() ? 0 : g_n_devices; }
-int lcd_set_thread_device(int device) {
-    if (init_default_device()) return -1;
-    if (device >= g_n_devices) return set_err(-1, "bad device index");
-    t_device = device; // < 0: back to the process default
-    return use_device(-1);
-}
-const char *lcd_last_error(void) { return g_err.c_str(); }
-const char *lcd_version(void) { return "longcalld_amd hot path 0.1 (gfx950)"; }
-int lcd_host_threads(int *team, int *arena_threads, int *cpus, int *local_world) {
-    if (team) *team = host_team();
-    if (arena_threads) *arena_threads = host_arena_threads();
-    if (cpus) *cpus = host_cpus();
-    if (local_world) *local_world = host_local_world();
-    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -2731,691 +2423,6 @@ int lcd_wfa_batch(int n, const uint8_t *pool, uint64_t pool_len, const uint64_t 
     return 0;
 }
 
-// ---- sdust on the device (sdust_kernel.hip): segments on lanes, the host chains their reports with sdust's merge rule ----
-// lcd_sdust_batch: the references of MANY chunks in one launch.  A lane's automaton is serial and latency-bound (21 ms for one 500 kb chunk against 9 ms
-// for the reference's sdust() on one core), but the chip holds ~60 000 lanes: the chunk workers' references of one pipeline step go in together.
-int lcd_sdust_batch(int n_seqs, const uint8_t *const *seqs, const int64_t *lens, int T, int W, int64_t **intervals_out, int *n_out) {
-    for (int q = 0; q < n_seqs; ++q) { intervals_out[q] = nullptr; n_out[q] = 0; }
-    if (ensure_init()) return -1;
-    if (n_seqs <= 0) return 0;
-    if (W > 64 || W < 4) return set_err(-4, "lcd_sdust: W must be in [4, 64]");
-    // segment length: the automaton is serial inside a segment (plus ~3W bases of lead-in and run-out), so short segments = more lanes, less latency
-    const int seg = W <= 32 ? 128 : 256, cap = seg + 8;
-    auto code = [](uint8_t c) { return c < 4 ? (int)c : (c == 'A' || c == 'a') ? 0 : (c == 'C' || c == 'c') ? 1 : (c == 'G' || c == 'g') ? 2 : (c == 'T' || c == 't') ? 3 : 4; };
-    std::vector<SdSeg> segs; std::vector<size_t> first(n_seqs + 1, 0);
-    uint64_t pool_bytes = 0;
-    for (int q = 0; q < n_seqs; ++q) {
-        first[q] = segs.size();
-        if (lens[q] <= 0) continue;
-        if (lens[q] > 2000000000ll) return set_err(-4, "lcd_sdust: sequences below 2 Gb");
-        const int len = (int)lens[q], n_seg = (len + seg - 1) / seg;
-        const uint8_t *seq = seqs[q];
-        // where each segment's automaton starts: 2W + 4 triplet words before (segment start - W); a word ends at i when i-2..i are all A/C/G/T
-        std::vector<int> ring(2 * W + 4, -1); size_t rn = 0; // ring of the last 2W+4 word-end positions
-        int l = 0, next = 0;
-        std::vector<int> from(n_seg, 0);
-        for (int i = 0; i < len && next < n_seg; ++i) {
-            while (next < n_seg && std::max(0, next * seg - W) == i) { from[next] = rn >= ring.size() ? std::max(0, ring[rn % ring.size()] - 2) : 0; ++next; }
-            if (code(seq[i]) < 4) { if (++l >= 3) { ring[rn % ring.size()] = i; ++rn; } } else l = 0;
-        }
-        for (int k = 0; k < n_seg; ++k) { SdSeg sg; sg.seq_off = pool_bytes; sg.len = len; sg.a = k * seg; sg.from = from[k]; sg.pad = 0; segs.push_back(sg); }
-        pool_bytes += lcd_align_up((uint64_t)len + 16, 16);
-    }
-    first[n_seqs] = segs.size();
-    const size_t n_seg = segs.size();
-    if (n_seg == 0) return 0;
-    // (grow-only buffers and one stream kept across calls: five hipMalloc / hipFree pairs cost more than the kernel)
-    static std::mutex mu; std::lock_guard<std::mutex> lk(mu);
-    static hipStream_t st[LCD_MAX_DEV] = {};
-    static DevBuf d_seq[LCD_MAX_DEV], d_segs[LCD_MAX_DEV], d_n[LCD_MAX_DEV], d_out[LCD_MAX_DEV], d_p[LCD_MAX_DEV];
-    const int dv = cur_device();
-    if (!st[dv]) HIPCHK(hipStreamCreateWithFlags(&st[dv], hipStreamNonBlocking));
-    const int pcap = W * W + 8;
-    if (d_seq[dv].ensure(pool_bytes + 64) || d_segs[dv].ensure(n_seg * sizeof(SdSeg)) || d_n[dv].ensure(n_seg * 4) || d_out[dv].ensure(n_seg * (size_t)cap * 8) ||
-        d_p[dv].ensure(n_seg * (size_t)pcap * 16)) return -11;
-    { uint64_t o = 0; for (int q = 0; q < n_seqs; ++q) if (lens[q] > 0) { HIPCHK(hipMemcpyAsync((uint8_t *)d_seq[dv].p + o, seqs[q], (size_t)lens[q], hipMemcpyHostToDevice, st[dv])); o += lcd_align_up((uint64_t)lens[q] + 16, 16); } }
-    HIPCHK(hipMemcpyAsync(d_segs[dv].p, segs.data(), n_seg * sizeof(SdSeg), hipMemcpyHostToDevice, st[dv]));
-    lcd_launch_sdust((const unsigned char *)d_seq[dv].p, (const SdSeg *)d_segs[dv].p, T, W, seg, (int)n_seg, cap, (int *)d_n[dv].p, (int2 *)d_out[dv].p, (int4 *)d_p[dv].p, pcap, st[dv]);
-    HIPCHK(hipGetLastError());
-    std::vector<int> n(n_seg); std::vector<int> raw(n_seg * (size_t)cap * 2);
-    HIPCHK(hipMemcpyAsync(n.data(), d_n[dv].p, n_seg * 4, hipMemcpyDeviceToHost, st[dv]));
-    HIPCHK(hipMemcpyAsync(raw.data(), d_out[dv].p, n_seg * (size_t)cap * 8, hipMemcpyDeviceToHost, st[dv]));
-    HIPCHK(hipStreamSynchronize(st[dv]));
-    for (int q = 0; q < n_seqs; ++q) {
-        std::vector<int64_t> res; // save_masked_regions' merge (src/sdust.c:97-103) over the segments' reports in order
-        for (size_t s = first[q]; s < first[q + 1]; ++s) {
-            if (n[s] < 0 || n[s] > cap) return set_err(-24, "lcd_sdust: per-segment capacity exceeded (sequence " + std::to_string(q) + ", segment " + std::to_string(s - first[q]) + ": " + std::to_string(n[s]) + ")");
-            for (int k = 0; k < n[s]; ++k) {
-                const int64_t ps = raw[(s * cap + k) * 2], pf = raw[(s * cap + k) * 2 + 1];
-                if (!res.empty() && ps <= res.back()) { if (pf > res.back()) res.back() = pf; }
-                else { res.push_back(ps); res.push_back(pf); }
-            }
-        }
-        int64_t *out = (int64_t *)malloc((res.size() + 2) * sizeof(int64_t));
-        memcpy(out, res.data(), res.size() * sizeof(int64_t));
-        intervals_out[q] = out; n_out[q] = (int)(res.size() / 2);
-    }
-    return 0;
-}
-int lcd_sdust(const uint8_t *seq, int64_t len, int T, int W, int64_t **intervals_out) {
-    int n = 0;
-    const int rc = lcd_sdust_batch(1, &seq, &len, T, W, intervals_out, &n);
-    return rc ? rc : n;
-}
-
-// ---- SURVEY 8(f) f2, chunk level: pre_process_noisy_regs (src/collect_var.c:557-638) ----
-namespace {
-struct NIv { uint64_t x; long long en; int label; }; // x: the interval index's sort key (contig 0: the start)
-// cr_index's ordering (src/cgranges.c:13-86, :350-353): kept as added when the keys are non-decreasing, otherwise klib's in-place MSD radix sort
-// on the 64-bit key (8 bits per pass from bit 56, buckets of <= 64 entries by insertion sort) -- NOT stable, and windows found in many reads give
-// many equal starts, so the tie order of the real thing is reproduced, not approximated
-void niv_insertion(NIv *b, NIv *e) {
-    for (NIv *i = b + 1; i < e; ++i)
-        if (i->x < (i - 1)->x) { NIv t = *i, *j; for (j = i; j > b && t.x < (j - 1)->x; --j) *j = *(j - 1); *j = t; }
-}
-void niv_radix(NIv *beg, NIv *end, int s) {
-    struct Bk { NIv *b, *e; } bk[256];
-    for (auto &k : bk) k.b = k.e = beg;
-    for (NIv *i = beg; i != end; ++i) ++bk[(i->x >> s) & 255].e;
-    for (int k = 1; k < 256; ++k) { bk[k].e += bk[k - 1].e - beg; bk[k].b = bk[k - 1].e; }
-    for (Bk *k = bk; k != bk + 256;) {
-        if (k->b != k->e) {
-            Bk *l = bk + ((k->b->x >> s) & 255);
-            if (l != k) { NIv tmp = *k->b, sw; do { sw = tmp; tmp = *l->b; *l->b++ = sw; l = bk + ((tmp.x >> s) & 255); } while (l != k); *k->b++ = tmp; }
-            else ++k->b;
-        } else ++k;
-    }
-    bk[0].b = beg; for (int k = 1; k < 256; ++k) bk[k].b = bk[k - 1].e;
-    if (s) {
-        s = s > 8 ? s - 8 : 0;
-        for (auto &k : bk) { if (k.e - k.b > 64) niv_radix(k.b, k.e, s); else if (k.e - k.b > 1) niv_insertion(k.b, k.e); }
-    }
-}
-void niv_index(std::vector<NIv> &v) {
-    bool sorted = true; for (size_t i = 1; i < v.size(); ++i) if (v[i - 1].x > v[i].x) { sorted = false; break; }
-    if (sorted) return;
-    if (v.size() <= 64) niv_insertion(v.data(), v.data() + v.size()); else niv_radix(v.data(), v.data() + v.size(), 56);
-}
-void niv_add(std::vector<NIv> &v, long long st, long long en, int label) { if (st < 0) st = 0; if (st > en) return; v.push_back({(uint64_t)st, en, label}); } // cr_add :145-149
-// cr_merge(cr, -1, ...) (src/cgranges.c:225-300): passes of "merge every later interval that starts within min(label, label') of the running end"
-// until the number of intervals stops changing; each pass re-indexes
-void niv_merge(std::vector<NIv> &v, const int fixed_win = -1) { // fixed_win >= 0: cr_merge(cr, fixed_win, ..): that window instead of the smaller label
-    size_t cur = v.size();
-    for (;;) {
-        std::vector<NIv> out; std::vector<char> merged(v.size(), 0);
-        for (size_t j = 0; j < v.size(); ++j) {
-            if (merged[j]) continue;
-            uint64_t ms = v[j].x; long long me = v[j].en; int ml = v[j].label;
-            for (size_t k = j + 1; k < v.size(); ++k) {
-                if (merged[k]) continue;
-                const int win = fixed_win >= 0 ? fixed_win : (ml < v[k].label ? ml : v[k].label);
-                if ((uint64_t)(me + win) >= v[k].x) { ml = std::max(ml, v[k].label); ms = std::min(ms, v[k].x); me = std::max(me, v[k].en); merged[k] = 1; }
-            }
-            niv_add(out, (long long)ms, me, ml);
-        }
-        niv_index(out);
-        v.swap(out);
-        if (v.size() == cur) break;
-        cur = v.size();
-    }
-}
-} // namespace
-
-// collect_noisy_read_info's digar walk (src/align.c:1392-1456) for many (region, read) pairs in one launch, on digars as lcd_digar_batch returns them: which
-// query interval of each read lies over its region and how the read covers the region's ends.  The per-region form of the same walk is the host loop of
-// lcd_batch_add_region_from_chunk; this is the chunk-level form of SURVEY f2 (all regions of a chunk against all their reads: tens of thousands of pairs).
-int lcd_region_read_slices_batch(int n_pairs, const int *pair_read, const int64_t *pair_reg_beg, const int64_t *pair_reg_end, int n_reads,
-                                 const uint64_t *digar_off, const lcd_digar_t *digars, const int *qlen, int noisy_reg_flank_len,
-                                 int *read_beg, int *read_end, int *cover) {
-    static_assert(sizeof(lcd_digar_t) == sizeof(DigarRec), "lcd_digar_t is DigarRec");
-    if (ensure_init()) return -1;
-    if (n_pairs <= 0) return 0;
-    if (n_reads <= 0) return set_err(-4, "lcd_region_read_slices_batch: no reads");
-    std::vector<SliceJob> jobs(n_pairs);
-    for (int i = 0; i < n_pairs; ++i) {
-        const int r = pair_read[i];
-        if (r < 0 || r >= n_reads) return set_err(-4, "lcd_region_read_slices_batch: read index out of range");
-        SliceJob &j = jobs[i]; j.digar_off = digar_off[r]; j.n_digar = (int)(digar_off[r + 1] - digar_off[r]); j.qlen = qlen[r]; j.reg_beg = pair_reg_beg[i]; j.reg_end = pair_reg_end[i];
-    }
-    const uint64_t nd = digar_off[n_reads];
-    StreamGuard st; if (st.create()) return -10;
-    DevBuf d_dig, d_jobs, d_outs;
-    if (d_dig.ensure((nd + 1) * sizeof(DigarRec)) || d_jobs.ensure(n_pairs * sizeof(SliceJob)) || d_outs.ensure(n_pairs * sizeof(SliceOut))) return -11;
-    if (nd) { HIPCHK(hipMemcpyAsync(d_dig.p, digars, nd * sizeof(DigarRec), hipMemcpyHostToDevice, st)); g_copy_bytes[1] += nd * sizeof(DigarRec); }
-    HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), n_pairs * sizeof(SliceJob), hipMemcpyHostToDevice, st));
-    lcd_launch_slices((const SliceJob *)d_jobs.p, (SliceOut *)d_outs.p, (const DigarRec *)d_dig.p, noisy_reg_flank_len, n_pairs, st);
-    HIPCHK(hipGetLastError());
-    std::vector<SliceOut> outs(n_pairs);
-    HIPCHK(hipMemcpyAsync(outs.data(), d_outs.p, n_pairs * sizeof(SliceOut), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < n_pairs; ++i) { read_beg[i] = outs[i].read_beg; read_end[i] = outs[i].read_end; cover[i] = outs[i].cover; }
-    return 0;
-}
-
-int lcd_pre_process_noisy_regs(const lcd_noisy_iv_t *chunk_noisy, int n_noisy, const int64_t *low_comp, int n_low, int n_reads, const int64_t *read_beg,
-                               const int64_t *read_end, const uint64_t *read_iv_off, const lcd_noisy_iv_t *read_ivs, int min_alt_dp, float min_af,
-                               lcd_noisy_iv_t **regs_out) {
-    *regs_out = nullptr;
-    if (ensure_init()) return -1;
-    if (n_noisy <= 0) return 0;
-    std::vector<NIv> v;
-    for (int i = 0; i < n_noisy; ++i) niv_add(v, chunk_noisy[i].start, chunk_noisy[i].end, chunk_noisy[i].label);
-    niv_index(v);
-    if (n_low > 0) { // cr_extend_noisy_regs_with_low_comp / low_comp_cr_start_end (:466-478, :538-551): grow to every overlapping low-complexity interval
-        std::vector<NIv> w;
-        for (const NIv &a : v) {
-            const long long start = (long long)a.x + 1, end = a.en; long long ns = start, ne = end;
-            for (int k = 0; k < n_low; ++k) {
-                long long ls = low_comp[2 * k] < 0 ? 0 : low_comp[2 * k], le = low_comp[2 * k + 1];
-                if (ls > le) continue;
-                if (ls < end && start - 1 < le) { if (ls + 1 < ns) ns = ls + 1; if (le > ne) ne = le; }
-            }
-            niv_add(w, ns - 1, ne, a.label);
-        }
-        niv_index(w); v.swap(w);
-    }
-    niv_merge(v); niv_merge(v); // (:552 and :568)
-    const int nr = (int)v.size();
-    if (nr == 0) return 0;
-    // read support on the device
-    StreamGuard st; if (st.create()) return -10;
-    std::vector<IvRec> regs(nr);
-    for (int i = 0; i < nr; ++i) { regs[i].st = (long long)v[i].x; regs[i].en = v[i].en; regs[i].label = v[i].label; regs[i].pad = 0; }
-    const uint64_t niv = n_reads > 0 ? read_iv_off[n_reads] : 0;
-    DevBuf d_regs, d_rb, d_re, d_off, d_iv, d_cnt;
-    if (d_regs.ensure(nr * sizeof(IvRec)) || d_rb.ensure((n_reads + 1) * 8) || d_re.ensure((n_reads + 1) * 8) || d_off.ensure((n_reads + 2) * 8) || d_iv.ensure((niv + 1) * sizeof(IvRec)) ||
-        d_cnt.ensure(2ull * nr * 4 + 64)) return -11;
-    HIPCHK(hipMemcpyAsync(d_regs.p, regs.data(), nr * sizeof(IvRec), hipMemcpyHostToDevice, st));
-    if (n_reads > 0) {
-        HIPCHK(hipMemcpyAsync(d_rb.p, read_beg, n_reads * 8, hipMemcpyHostToDevice, st)); HIPCHK(hipMemcpyAsync(d_re.p, read_end, n_reads * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_off.p, read_iv_off, (n_reads + 1) * 8, hipMemcpyHostToDevice, st));
-        if (niv) HIPCHK(hipMemcpyAsync(d_iv.p, read_ivs, niv * sizeof(IvRec), hipMemcpyHostToDevice, st));
-    }
-    lcd_launch_region_support((const IvRec *)d_regs.p, nr, (const long long *)d_rb.p, (const long long *)d_re.p, (const unsigned long long *)d_off.p, (const IvRec *)d_iv.p, n_reads,
-                              (int *)d_cnt.p, (int *)d_cnt.p + nr, st);
-    HIPCHK(hipGetLastError());
-    std::vector<int> cnt(2 * (size_t)nr);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, 2ull * nr * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    lcd_noisy_iv_t *out = (lcd_noisy_iv_t *)malloc((nr + 1) * sizeof(lcd_noisy_iv_t));
-    int n_out = 0;
-    for (int i = 0; i < nr; ++i) {
-        const int tot = cnt[i], nz = cnt[nr + i];
-        if (nz < min_alt_dp || (float)nz / tot < min_af) continue; // (:609-610; 0 / 0 compares false, the first test already dropped it)
-        out[n_out].start = (long long)v[i].x; out[n_out].end = v[i].en; out[n_out].label = v[i].label; out[n_out].pad = 0; ++n_out;
-    }
-    *regs_out = out;
-    return n_out;
-}
-
-// cr_merge (src/cgranges.c:289-300; cr_cluster0 :225-268) of n labelled intervals: cr_add (negative starts clamped to 0, st > en dropped), cr_index, then passes of
-// "from every interval not yet merged, swallow every later one that starts within the window of the running end" until the count stops changing.  Window:
-// fixed_merge_win if >= 0 (src/collect_var.c:657 uses 0), else the smaller of the two labels (the dynamic window and its label minimum are not used by the
-// reference's code: src/cgranges.c:248-254).  Host code, as in the reference.  *out malloc()'d, index order; returns the number of merged intervals.
-int lcd_cr_merge(const lcd_noisy_iv_t *iv, int n, int fixed_merge_win, lcd_noisy_iv_t **out) {
-    std::vector<NIv> v;
-    for (int i = 0; i < n; ++i) niv_add(v, iv[i].start, iv[i].end, iv[i].label);
-    niv_index(v);
-    niv_merge(v, fixed_merge_win);
-    lcd_noisy_iv_t *o = (lcd_noisy_iv_t *)calloc(v.size() + 1, sizeof(lcd_noisy_iv_t));
-    for (size_t i = 0; i < v.size(); ++i) { o[i].start = (int64_t)v[i].x; o[i].end = v[i].en; o[i].label = v[i].label; }
-    *out = o;
-    return (int)v.size();
-}
-
-// post_process_noisy_regs (src/collect_var.c:640-660) -- host glue, see include/lcd_hotpath.h
-int lcd_post_process_noisy_regs(const lcd_noisy_iv_t *regs, int n_regs, int n_vars, const int64_t *var_pos, const int *var_ref_len, const int *var_cate,
-                                int flank, lcd_noisy_iv_t **regs_out) {
-    *regs_out = nullptr;
-    if (n_regs <= 0) return 0;
-    const int NOT_CAND = 0x800 | 0x001 | 0x002; // LONGCALLD_NOT_CAND_VAR_CATE
-    std::vector<NIv> v;
-    for (int i = 0; i < n_regs; ++i) niv_add(v, regs[i].start, regs[i].end, regs[i].label);
-    niv_index(v);
-    const int n = (int)v.size();
-    std::vector<int> maxl(n, -1), minr(n, -1);
-    auto cand = [&](int vi) { return !(var_cate[vi] & NOT_CAND); };
-    for (int ri = 0, vi = 0; ri < n && vi < n_vars;) { // (:488-503) last candidate left of each region, first one right of it
-        if (!cand(vi)) { ++vi; continue; }
-        const long long vs = var_pos[vi], ve = var_pos[vi] + var_ref_len[vi] - 1, rs = (long long)v[ri].x + 1, re = v[ri].en;
-        if (vs > re) { if (minr[ri] == -1) minr[ri] = vi; ++ri; }
-        else if (ve < rs) { maxl[ri] = vi; ++vi; }
-        else ++vi;
-    }
-    std::vector<NIv> w;
-    for (int ri = 0; ri < n; ++ri) { // (:505-533)
-        if (maxl[ri] == -1) maxl[ri] = std::min(n_vars - 1, 0);
-        if (minr[ri] == -1) minr[ri] = std::max(0, n_vars - 1);
-        long long cs = (long long)v[ri].x + 1 - flank, ce = v[ri].en + flank;
-        for (int vi = maxl[ri]; vi >= 0; --vi) {
-            if (!cand(vi)) continue;
-            const long long vs = var_pos[vi], ve = var_pos[vi] + var_ref_len[vi] - 1;
-            if (ve < cs - 1) break;
-            if (vs - flank < cs) cs = vs - flank;
-        }
-        for (int vi = minr[ri]; vi < n_vars; ++vi) {
-            if (!cand(vi)) continue;
-            const long long vs = var_pos[vi], ve = var_pos[vi] + var_ref_len[vi] - 1;
-            if (vs > ce + 1) break;
-            if (ve + flank > ce) ce = ve + flank;
-        }
-        niv_add(w, cs, ce, v[ri].label); // (the reference stores the 1-based start as the interval start here, :648)
-    }
-    niv_index(w);
-    // cr_merge(cr, 0, -1, -1): fixed window 0 -- join while the running end reaches the next start (src/cgranges.c:225-300)
-    size_t cur = w.size();
-    for (;;) {
-        std::vector<NIv> out; std::vector<char> merged(w.size(), 0);
-        for (size_t j = 0; j < w.size(); ++j) {
-            if (merged[j]) continue;
-            uint64_t ms = w[j].x; long long me = w[j].en; int ml = w[j].label;
-            for (size_t k = j + 1; k < w.size(); ++k) {
-                if (merged[k]) continue;
-                if ((uint64_t)me >= w[k].x) { ml = std::max(ml, w[k].label); ms = std::min(ms, w[k].x); me = std::max(me, w[k].en); merged[k] = 1; }
-            }
-            niv_add(out, (long long)ms, me, ml);
-        }
-        niv_index(out); w.swap(out);
-        if (w.size() == cur) break;
-        cur = w.size();
-    }
-    lcd_noisy_iv_t *o = (lcd_noisy_iv_t *)malloc((w.size() + 1) * sizeof(lcd_noisy_iv_t));
-    for (size_t i = 0; i < w.size(); ++i) { o[i].start = (long long)w[i].x; o[i].end = w[i].en; o[i].label = w[i].label; o[i].pad = 0; }
-    *regs_out = o;
-    return (int)w.size();
-}
-
-// SURVEY 8(f) f2, first part: collect_digar_from_eqx_cigar (src/bam_utils.c:701-842) for all reads of a chunk
-void lcd_digar_opt_default(lcd_digar_opt_t *o, int is_ont) {
-    o->min_bq = 10; o->noisy_reg_max_xgaps = 5; o->noisy_reg_slide_win = is_ont ? 25 : 100; o->end_clip_reg = 30; o->end_clip_reg_flank_win = 100;
-    o->max_noisy_frac_per_read = 0.5; o->max_var_ratio_per_read = 0.05;
-}
-// the four collect_digar_from_* entry points share everything behind the CIGAR-shaped operation words: `words` are host words (h_pool) or words already in
-// HBM (d_words: the reference-comparison rewrite) with their per-read digar / event counts; clip_rule as DigarJob; rlen_true: bam_cigar2rlen of the BAM
-// CIGAR where the words were derived from a tag instead (digar->end = bam_endpos(read), src/bam_utils.c:852)
-namespace {
-struct DigarWords {
-    const uint32_t *h_pool = nullptr; const uint64_t *off = nullptr; const int *n_cigar = nullptr;
-    const DevBuf *d_words = nullptr; const RefCmpOut *counts = nullptr;
-    int clip_rule = 0; const int64_t *rlen_true = nullptr; const int *pre_status = nullptr;
-    const int *n_indel = nullptr; // with counts: how many of the window events are insertions / deletions (tighter window capacity)
-    uint64_t d_qual_base = 0;   // != 0: the qualities are already in HBM (qual_off relative to this address; qual_pool unused)
-};
-// keep: the digars stay in HBM (a device-resident chunk, lcd_chunk_t): `keep->d_dig` receives them, nothing of them is downloaded, *digars_out stays NULL and
-// keep->slot / keep->n_digar say where read r's digars are (record index into d_dig, count)
-struct DigarKeep { DevBuf *d_dig; std::vector<uint64_t> slot; std::vector<int> n_digar; };
-int digar_batch_core(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const DigarWords &W,
-                    const uint8_t *qual_pool, const uint64_t *qual_off, const int *qlen, const uint8_t *pal_flags, int64_t reg_beg, int64_t reg_end,
-                    int64_t whole_ref_len, uint64_t **digar_off_out, lcd_digar_t **digars_out, uint64_t **iv_off_out, lcd_noisy_iv_t **ivs_out,
-                    uint8_t **iv_in_chunk_out, int *status, int64_t *beg, int64_t *end, int *n_cand_vars, hipStream_t st, DigarKeep *keep = nullptr) {
-    const uint32_t *cigar_pool = W.h_pool; const uint64_t *cigar_off = W.off; const int *n_cigar = W.n_cigar;
-    static_assert(sizeof(lcd_digar_t) == sizeof(DigarRec) && sizeof(lcd_noisy_iv_t) == sizeof(IvRec), "ABI structs mirror the device records");
-    // capacities from one pass over the CIGAR words (the host has them in hand anyway), or from the rewrite's count pass
-    std::vector<DigarJob> jobs(n);
-    uint64_t cig_words = 0, qual_bytes = 0, dtot = 0, itot = 0, etot = 0;
-    for (int r = 0; r < n; ++r) { cig_words = std::max<uint64_t>(cig_words, cigar_off[r] + n_cigar[r]); qual_bytes = std::max<uint64_t>(qual_bytes, qual_off[r] + qlen[r]); }
-    for (int r = 0; r < n; ++r) {
-        DigarJob &j = jobs[r];
-        long long nd = 0, nev = 0, nid = -1; // digars; window events; of those insertions / deletions (-1: not counted)
-        if (W.counts) { nd = W.counts[r].nd; nev = W.counts[r].nev; if (W.n_indel) nid = W.n_indel[r]; }
-        else { nid = 0; for (int i = 0; i < n_cigar[r]; ++i) { const uint32_t c = cigar_pool[cigar_off[r] + i]; const int op = c & 0xf, len = (int)(c >> 4); if (op == 8) { nd += len; nev += len; } else if (op != 3 && op != 9) { ++nd; if (op == 1 || op == 2) { ++nev; ++nid; } } } }
-        j.n_cigar = n_cigar[r]; j.qlen = qlen[r]; j.pos0 = pos0[r]; j.left_pal = pal_flags ? pal_flags[r] & 1 : 0; j.right_pal = pal_flags ? (pal_flags[r] >> 1) & 1 : 0;
-        j.digar_cap = (int)nd; j.ev_cap = (int)nev + 1; j.clip_rule = W.clip_rule;
-        // windows are disjoint and each holds events of total weight > max_xgaps (a mismatch weighs 1, an insertion / deletion its length): at most one per
-        // indel event plus one per max_xgaps + 1 mismatches, plus the two clip flanks
-        j.iv_cap = (int)(nid >= 0 ? nid + (nev - nid) / (opt->noisy_reg_max_xgaps + 1) : nev) + 4;
-        j.cigar_off = cigar_off[r] * 4; j.qual_off = qual_off[r];
-        j.digar_off = dtot * sizeof(DigarRec); dtot += nd; j.iv_off = itot * sizeof(IvRec); itot += j.iv_cap; j.ev_off = etot * 16; etot += j.ev_cap;
-    }
-    DevBuf d_cig, d_qual, d_jobs, d_outs, d_dig_local, d_iv, d_ev;
-    DevBuf &d_dig = keep ? *keep->d_dig : d_dig_local;
-    if ((!W.d_words && d_cig.ensure(cig_words * 4 + 64)) || (!W.d_qual_base && d_qual.ensure(qual_bytes + 64)) || d_jobs.ensure(n * sizeof(DigarJob)) || d_outs.ensure(n * sizeof(DigarOut)) ||
-        d_dig.ensure(dtot * sizeof(DigarRec) + 64) || d_iv.ensure(itot * sizeof(IvRec) + 64) || d_ev.ensure(etot * 16 + 64)) return -11;
-    const uint64_t cig_base = W.d_words ? W.d_words->addr() : d_cig.addr();
-    for (DigarJob &j : jobs) { j.cigar_off += cig_base; j.qual_off += W.d_qual_base ? W.d_qual_base : d_qual.addr(); j.digar_off += d_dig.addr(); j.iv_off += d_iv.addr(); j.ev_off += d_ev.addr(); }
-    if (!W.d_words) HIPCHK(hipMemcpyAsync(d_cig.p, cigar_pool, cig_words * 4, hipMemcpyHostToDevice, st));
-    if (!W.d_qual_base) HIPCHK(hipMemcpyAsync(d_qual.p, qual_pool, qual_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(DigarJob), hipMemcpyHostToDevice, st));
-    DigarOpt dopt; dopt.min_bq = opt->min_bq; dopt.max_xgaps = opt->noisy_reg_max_xgaps; dopt.win = opt->noisy_reg_slide_win; dopt.end_clip_reg = opt->end_clip_reg;
-    dopt.end_clip_flank = opt->end_clip_reg_flank_win; dopt.pad = 0; dopt.whole_ref_len = whole_ref_len;
-    lcd_launch_digar((const DigarJob *)d_jobs.p, (DigarOut *)d_outs.p, dopt, n, st);
-    HIPCHK(hipGetLastError());
-    std::vector<DigarOut> outs(n);
-    std::vector<DigarRec> hd(keep ? 1 : dtot + 1); std::vector<IvRec> hiv(itot + 1);
-    HIPCHK(hipMemcpyAsync(outs.data(), d_outs.p, n * sizeof(DigarOut), hipMemcpyDeviceToHost, st));
-    if (dtot && !keep) { HIPCHK(hipMemcpyAsync(hd.data(), d_dig.p, dtot * sizeof(DigarRec), hipMemcpyDeviceToHost, st)); g_copy_bytes[0] += dtot * sizeof(DigarRec); }
-    if (itot) HIPCHK(hipMemcpyAsync(hiv.data(), d_iv.p, itot * sizeof(IvRec), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    uint64_t *doff = (uint64_t *)malloc((n + 1) * sizeof(uint64_t)), *ioff = (uint64_t *)malloc((n + 1) * sizeof(uint64_t));
-    uint64_t niv = 0;
-    for (int r = 0; r < n; ++r) { if (outs[r].status == -3) { free(doff); free(ioff); return set_err(-24, "digar batch: capacity estimate too small"); } niv += outs[r].n_iv; }
-    lcd_digar_t *dg = keep ? nullptr : (lcd_digar_t *)malloc((dtot + 1) * sizeof(lcd_digar_t));
-    if (keep) { keep->slot.resize(n); keep->n_digar.resize(n); }
-    lcd_noisy_iv_t *iv = (lcd_noisy_iv_t *)malloc((niv + 1) * sizeof(lcd_noisy_iv_t)); uint8_t *inc = (uint8_t *)calloc(niv + 1, 1);
-    uint64_t dw = 0, iw = 0;
-    for (int r = 0; r < n; ++r) {
-        const DigarJob &j = jobs[r]; const DigarOut &o = outs[r];
-        doff[r] = dw; ioff[r] = iw;
-        if (keep) { keep->slot[r] = (j.digar_off - d_dig.addr()) / sizeof(DigarRec); keep->n_digar[r] = o.n_digar; }
-        else memcpy(dg + dw, hd.data() + (j.digar_off - d_dig.addr()) / sizeof(DigarRec), (size_t)o.n_digar * sizeof(DigarRec));
-        dw += o.n_digar;
-        const IvRec *src = hiv.data() + (j.iv_off - d_iv.addr()) / sizeof(IvRec);
-        std::vector<IvRec> v(src, src + o.n_iv);
-        // cr_index (src/cgranges.c): intervals stay as added when their starts are non-decreasing, otherwise they are sorted by start --
-        // an insertion sort for up to 64 of them, i.e. stable (longer unsorted lists: radix passes whose tie order is not reproduced here;
-        // a tie needs a window starting exactly where the right-clip flank starts)
-        // (starts are >= 0: the kernel clamps like cr_add does, src/cgranges.c:146)
-        auto key = [](const IvRec &a) { return (uint64_t)(long long)(int)a.st; };
-        bool sorted = true; for (int k = 1; k < o.n_iv; ++k) if (key(v[k]) < key(v[k - 1])) sorted = false;
-        if (!sorted) std::stable_sort(v.begin(), v.end(), [&](const IvRec &a, const IvRec &b) { return key(a) < key(b); });
-        long long total = 0;
-        for (const IvRec &x : v) total += x.en - x.st + 1;                     // collect_noisy_region_len (:631)
-        beg[r] = j.pos0 + 1; end[r] = j.pos0 + (W.rlen_true ? W.rlen_true[r] : o.rlen); n_cand_vars[r] = o.n_cand;
-        const long long mapped = end[r] - beg[r] + 1;
-        const bool skip = (double)total > mapped * opt->max_noisy_frac_per_read || (double)o.n_cand > mapped * opt->max_var_ratio_per_read; // (:811)
-        status[r] = (o.status == -2 || (W.pre_status && W.pre_status[r])) ? -2 : skip ? -1 : 0;
-        for (int k = 0; k < o.n_iv; ++k) {
-            iv[iw + k].start = v[k].st; iv[iw + k].end = v[k].en; iv[iw + k].label = v[k].label; iv[iw + k].pad = 0;
-            inc[iw + k] = !skip && !(v[k].st + 1 > reg_end || v[k].en < reg_beg);    // is_overlap_reg(start + 1, end, ...) (:820)
-        }
-        iw += o.n_iv;
-    }
-    doff[n] = dw; ioff[n] = iw;
-    *digar_off_out = doff; *digars_out = dg; *iv_off_out = ioff; *ivs_out = iv; *iv_in_chunk_out = inc;
-    return 0;
-}
-
-// ---- host side of the cs / MD paths: the tag strings are O(events) long, so they are parsed here into EQX-shaped operation words ----
-inline bool is_alpha(char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
-inline bool is_digit(char c) { return c >= '0' && c <= '9'; }
-inline uint32_t opw(long long len, int op) { return ((uint32_t)len << 4) | (uint32_t)op; }
-// collect_digar_from_cs_tag, src/bam_utils.c:876-976: clips from the first / last CIGAR operation, everything else from the cs string
-bool cs_to_words(const uint32_t *cig, int n_cigar, const char *cs, std::vector<uint32_t> &w) {
-    if (n_cigar <= 0 || !cs) return false;
-    if ((cig[0] & 0xf) == 4 || (cig[0] & 0xf) == 5) w.push_back(cig[0]);
-    while (*cs) {
-        if (*cs == ':') { char *e; const long len = strtol(cs + 1, &e, 10); if (e == cs + 1 || len < 0) return false; cs = e; w.push_back(opw(len, 7)); }
-        else if (*cs == '=' || *cs == '+' || *cs == '-') { const int op = *cs == '=' ? 7 : *cs == '+' ? 1 : 2; ++cs; long len = 0; while (is_alpha(*cs)) { ++len; ++cs; } w.push_back(opw(len, op)); }
-        else if (*cs == '*') { if (!cs[1] || !cs[2]) return false; w.push_back(opw(1, 8)); cs += 3; }
-        else if (*cs == '~') { ++cs; while (is_alpha(*cs) || is_digit(*cs)) ++cs; }   // intron: stepped over without moving pos (:951-953)
-        else return false;                                                             // the reference exits (:955)
-    }
-    const uint32_t last = cig[n_cigar - 1];
-    if ((last & 0xf) == 4 || (last & 0xf) == 5) w.push_back(last);
-    return true;
-}
-// collect_digar_from_MD_tag, src/bam_utils.c:1035-1134: 'M' operations split by the MD string ('=' runs that may continue over an insertion into the
-// next 'M', one 'X' per letter), deletions step over "^LETTERS", a "0" after either is skipped
-bool md_to_words(const uint32_t *cig, int n_cigar, const char *md0, std::vector<uint32_t> &w) {
-    if (!md0) return false;
-    const char *md = md0, *md_end = md0 + strlen(md0); long md_i = 0;
-    auto at = [&](long k) -> char { const char *q = md + k; return (q >= md0 && q < md_end) ? *q : '\0'; };
-    long last_eq = 0;
-    for (int i = 0; i < n_cigar; ++i) {
-        const int op = cig[i] & 0xf; const long len = cig[i] >> 4;
-        if (op == 0) {
-            long m = len;
-            while (1) {
-                if (last_eq > 0) {
-                    if (last_eq >= m) { w.push_back(opw(m, 7)); last_eq -= m; m = 0; }
-                    else { w.push_back(opw(last_eq, 7)); m -= last_eq; md_i = 0; last_eq = 0; }
-                } else if (is_digit(at(md_i))) {
-                    char *e; long eq = strtol(md + md_i, &e, 10); md = e;
-                    bool emit = true;
-                    if (eq > m) { last_eq = eq - m; eq = m; }
-                    else if (eq == 0) { md_i = 0; emit = false; }
-                    if (emit) { w.push_back(opw(eq, 7)); m -= eq; md_i = 0; }
-                    else continue;
-                } else if (is_alpha(at(md_i))) {
-                    w.push_back(opw(1, 8)); m -= 1;
-                    if (at(md_i + 1) == '\0' || at(md_i + 1) != '0') md_i++; else md_i += 2;
-                } else return false;                                                   // "MD and CIGAR do not match": the reference exits (:1088)
-                if (m <= 0) break;
-            }
-        } else if (op == 2) {
-            w.push_back(cig[i]);
-            md_i++;
-            while (at(md_i) && is_alpha(at(md_i))) md_i++;
-            if (at(md_i) == '0') md_i++;
-        } else if (op == 1 || op == 4 || op == 5 || op == 3) w.push_back(cig[i]);
-        else if (op == 7 || op == 8) return false;                                     // '=' / 'X' next to an MD tag: the reference exits (:1134)
-    }
-    return true;
-}
-} // namespace
-
-int lcd_digar_batch(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
-                    const uint8_t *qual_pool, const uint64_t *qual_off, const int *qlen, const uint8_t *pal_flags, int64_t reg_beg, int64_t reg_end,
-                    int64_t whole_ref_len, uint64_t **digar_off_out, lcd_digar_t **digars_out, uint64_t **iv_off_out, lcd_noisy_iv_t **ivs_out,
-                    uint8_t **iv_in_chunk_out, int *status, int64_t *beg, int64_t *end, int *n_cand_vars) {
-    *digar_off_out = *iv_off_out = nullptr; *digars_out = nullptr; *ivs_out = nullptr; *iv_in_chunk_out = nullptr;
-    if (ensure_init()) return -1;
-    if (n <= 0) return 0;
-    StreamGuard st; if (st.create()) return -10;
-    DigarWords W; W.h_pool = cigar_pool; W.off = cigar_off; W.n_cigar = n_cigar;
-    return digar_batch_core(opt, n, pos0, W, qual_pool, qual_off, qlen, pal_flags, reg_beg, reg_end, whole_ref_len, digar_off_out, digars_out, iv_off_out, ivs_out,
-                            iv_in_chunk_out, status, beg, end, n_cand_vars, st);
-}
-
-// ---- a DEVICE-RESIDENT chunk (SURVEY 8f f2 -> region jobs without the host round trips): the reads' CIGARs, qualities and 4-bit bases go up ONCE, the digars are
-// made and KEPT in HBM, the (region, read) slices are cut there and a batch's read slices are unpacked from there -- the host sees what its glue needs (per-read
-// status / span / candidate count, the noisy intervals: tens per read; per slice two offsets and a cover flag) and never a digar or a base.
-// Reference: collect_digar_from_eqx_cigar src/bam_utils.c:701-842, collect_noisy_read_info src/align.c:1377-1461. ----
-struct lcd_chunk_s {
-    int device = 0, n_reads = 0; lcd_digar_opt_t opt;
-    DevBuf d_dig, d_seq;                                   // digars (DigarRec, per read at slot[r], n_digar[r] of them); the records' 4-bit packed bases
-    lcd_inflated_t *stream = nullptr;                      // lcd_chunk_create_from_bam: the inflated BGZF blocks; bases and qualities are read where they lie in it
-    uint64_t seq_base = 0, qual_base = 0;                  // device address seq_off / qual_off are relative to (qual_base 0: the qualities are in h_qual)
-    std::vector<uint64_t> slot, seq_off; std::vector<int> n_digar, qlen;
-    std::vector<uint8_t> h_qual; std::vector<uint64_t> qual_off;   // host copy: the sampling rule of >= 10 kb regions reads qualities on the host (src/seq.c:429)
-    std::vector<int> status, n_cand; std::vector<int64_t> beg, end;
-    uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
-    DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
-    DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use
-    ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); }
-};
-lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
-                              const uint8_t *qual_pool, const uint64_t *qual_off, const int *qlen, const uint8_t *pal_flags, const uint8_t *seq_pool,
-                              const uint64_t *seq_off, int64_t reg_beg, int64_t reg_end, int64_t whole_ref_len) {
-    if (ensure_init() || n <= 0) return nullptr;
-    std::unique_ptr<lcd_chunk_s> c(new lcd_chunk_s());
-    c->device = cur_device(); c->n_reads = n; c->opt = *opt;
-    c->qlen.assign(qlen, qlen + n); c->seq_off.assign(seq_off, seq_off + n); c->qual_off.assign(qual_off, qual_off + n);
-    uint64_t seq_bytes = 0, qual_bytes = 0;
-    for (int r = 0; r < n; ++r) { seq_bytes = std::max<uint64_t>(seq_bytes, seq_off[r] + (uint64_t)(qlen[r] + 1) / 2); qual_bytes = std::max<uint64_t>(qual_bytes, qual_off[r] + (uint64_t)qlen[r]); }
-    c->h_qual.assign(qual_pool, qual_pool + qual_bytes);
-    StreamGuard st; if (st.create()) return nullptr;
-    if (c->d_seq.ensure(seq_bytes + 64)) return nullptr;
-    if (hipMemcpyAsync(c->d_seq.p, seq_pool, seq_bytes, hipMemcpyHostToDevice, st) != hipSuccess) { set_err(-10, "lcd_chunk_create: upload failed"); return nullptr; }
-    g_copy_bytes[2] += seq_bytes; // the records' bases: once per chunk, 4-bit packed
-    c->status.resize(n); c->n_cand.resize(n); c->beg.resize(n); c->end.resize(n);
-    DigarWords W; W.h_pool = cigar_pool; W.off = cigar_off; W.n_cigar = n_cigar;
-    DigarKeep keep; keep.d_dig = &c->d_dig;
-    uint64_t *doff = nullptr; lcd_digar_t *dg = nullptr;
-    const int rc = digar_batch_core(opt, n, pos0, W, qual_pool, qual_off, qlen, pal_flags, reg_beg, reg_end, whole_ref_len, &doff, &dg, &c->iv_off, &c->ivs, &c->iv_in_chunk,
-                                    c->status.data(), c->beg.data(), c->end.data(), c->n_cand.data(), st, &keep);
-    free(doff);
-    if (rc) return nullptr;
-    if (hipStreamSynchronize(st) != hipSuccess) { set_err(-10, "lcd_chunk_create: synchronize failed"); return nullptr; }
-    c->slot.swap(keep.slot); c->n_digar.swap(keep.n_digar);
-    c->seq_base = c->d_seq.addr();
-    return c.release();
-}
-// f3 on the device, in front of the chunk: the region's BGZF blocks (through the .bai) are read from the file and uploaded compressed, inflated by
-// lcd_inflate_kernel, the records are found / measured / filtered in HBM (bam_kernel.hip) and their digars made there -- what sam_itr_queryi + sam_itr_next
-// (htslib: bgzf_read_block, inflate, bam_read1) and the record loop of collect_ref_seq_bam_main (src/bam_utils.c:1672-1706) followed by
-// collect_digar_from_eqx_cigar (:701-842) do for the reference on the calling thread.  The host sees 40 + 40 bytes per record (descriptor, CIGAR statistics),
-// never a base, a quality or a digar.  Records, filters, order and stop rule are lcd_bam_load_region_indexed's (Collector::take).
-lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
-                                       int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
-    if (meta) memset(meta, 0, sizeof(*meta));
-    if (ensure_init()) return nullptr;
-    LcdRegionImage im;
-    if (lcd_io_region_image(bam_path, bai_path, chrom, reg_beg, reg_end, im)) { set_err(-30, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
-    std::unique_ptr<lcd_chunk_s> c(new lcd_chunk_s());
-    c->device = cur_device(); c->n_reads = 0; c->opt = *opt;
-    if (meta) { meta->tid = im.tid; meta->n_targets = im.n_ref; meta->target_len = im.tlen; }
-    if (im.image.empty() || im.ranges.empty()) return c.release();
-    c->stream = lcd_bgzf_inflate_dev(im.image.data(), im.image.size(), verify_crc);
-    if (!c->stream) { set_err(-32, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
-    const uint64_t base = lcd_inflated_dev_ptr(c->stream), usize = lcd_inflated_size(c->stream);
-    if (!usize) return c.release();
-    StreamGuard st; if (st.create()) return nullptr;
-    auto fail = [&](int code, const std::string &m) -> lcd_chunk_t * { set_err(code, "lcd_chunk_create_from_bam: " + m); return nullptr; };
-#define CHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return fail(-10, "HIP call failed: " #x); } } while (0)
-    // 1. the records of every range: one serial hop per record on the device
-    const int nr = (int)im.ranges.size();
-    std::vector<BamWalkJob> wj(nr); std::vector<BamWalkOut> wo(nr);
-    std::vector<BamRecDesc> descs; std::vector<size_t> first(nr + 1, 0);
-    DevBuf d_desc, d_wj, d_wo;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        size_t tot = 0;
-        for (int k = 0; k < nr; ++k) {
-            const uint64_t len = im.ranges[k].second > im.ranges[k].first ? im.ranges[k].second - im.ranges[k].first : 0;
-            const size_t cap = attempt == 0 ? (size_t)(len / 256 + 1024) : (size_t)(len / 36 + 2); // (a record is at least 36 bytes; long reads are tens of kilobytes)
-            first[k] = tot; tot += cap; wj[k].cap = (int)cap;
-        }
-        first[nr] = tot;
-        if (d_desc.ensure(tot * sizeof(BamRecDesc)) || d_wj.ensure(nr * sizeof(BamWalkJob)) || d_wo.ensure(nr * sizeof(BamWalkOut))) return nullptr;
-        for (int k = 0; k < nr; ++k) {
-            wj[k].stream = base; wj[k].ubeg = im.ranges[k].first; wj[k].uend = std::min<uint64_t>(im.ranges[k].second, usize); wj[k].usize = usize;
-            wj[k].descs = d_desc.addr() + first[k] * sizeof(BamRecDesc); wj[k].reg_end = reg_end; wj[k].tid = im.tid;
-        }
-        CHK(hipMemcpyAsync(d_wj.p, wj.data(), nr * sizeof(BamWalkJob), hipMemcpyHostToDevice, st));
-        lcd_launch_bam_walk((const BamWalkJob *)d_wj.p, (BamWalkOut *)d_wo.p, nr, st);
-        CHK(hipGetLastError());
-        CHK(hipMemcpyAsync(wo.data(), d_wo.p, nr * sizeof(BamWalkOut), hipMemcpyDeviceToHost, st));
-        CHK(hipStreamSynchronize(st));
-        bool over = false; for (int k = 0; k < nr; ++k) if (wo[k].status == 3) over = true;
-        if (!over) break;
-        if (attempt == 1) return fail(-24, "record descriptor capacity");
-    }
-    size_t nrec = 0; std::vector<size_t> at(nr + 1, 0);
-    for (int k = 0; k < nr; ++k) { at[k] = nrec; nrec += (size_t)wo[k].n; } at[nr] = nrec;
-    descs.resize(nrec + 1);
-    for (int k = 0; k < nr; ++k) if (wo[k].n) CHK(hipMemcpyAsync(descs.data() + at[k], (const uint8_t *)d_desc.p + first[k] * sizeof(BamRecDesc), (size_t)wo[k].n * sizeof(BamRecDesc), hipMemcpyDeviceToHost, st));
-    CHK(hipStreamSynchronize(st));
-    // 2. CIGAR statistics of the wanted reference's records
-    std::vector<int> stat_of(nrec, -1); std::vector<BamStatJob> sj;
-    for (size_t i = 0; i < nrec; ++i) if (descs[i].refid == im.tid) {
-        BamStatJob j; j.rec = base + descs[i].off; j.bs = descs[i].bs; j.lname = descs[i].lname; j.nc = descs[i].nc; j.lseq = descs[i].lseq;
-        stat_of[i] = (int)sj.size(); sj.push_back(j);
-    }
-    std::vector<BamStatOut> so(sj.size() + 1);
-    DevBuf d_sj, d_so;
-    if (!sj.empty()) {
-        if (d_sj.ensure(sj.size() * sizeof(BamStatJob)) || d_so.ensure(sj.size() * sizeof(BamStatOut))) return nullptr;
-        CHK(hipMemcpyAsync(d_sj.p, sj.data(), sj.size() * sizeof(BamStatJob), hipMemcpyHostToDevice, st));
-        lcd_launch_bam_stat((const BamStatJob *)d_sj.p, (BamStatOut *)d_so.p, (int)sj.size(), st);
-        CHK(hipGetLastError());
-        CHK(hipMemcpyAsync(so.data(), d_so.p, sj.size() * sizeof(BamStatOut), hipMemcpyDeviceToHost, st));
-        CHK(hipStreamSynchronize(st));
-    }
-    // 3. the loader's rule, record by record in file order (Collector::take in lcd_io.cpp)
-    std::vector<int64_t> pos0, endp; std::vector<int> mapq, flag, ncig, qlen; std::vector<uint64_t> coff, soff, qoff, noff; std::vector<RefCmpOut> counts; std::vector<int> nindel; std::vector<GatherJob> gj, nj;
-    uint64_t cw = 0, nbytes = 0; bool done = false;
-    const char *malformed = "malformed BAM record (a field runs past the record, or a placeholder CIGAR without its CG tag)";
-    for (int k = 0; k < nr && !done; ++k) {
-        for (size_t i = at[k]; i < at[k + 1] && !done; ++i) {
-            const BamRecDesc &d = descs[i];
-            if (d.refid != im.tid) { if ((d.refid > im.tid || d.refid < 0) && !pos0.empty()) done = true; continue; }
-            const BamStatOut &x = so[stat_of[i]];
-            if (x.kind == -2) return fail(-33, malformed);
-            const int64_t e0 = (int64_t)d.pos + (x.rl > 0 ? x.rl : 1);
-            if (d.pos >= reg_end) { done = true; break; }
-            if (e0 <= reg_beg - 1) continue;
-            if ((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq) continue;
-            pos0.push_back(d.pos); endp.push_back(e0); mapq.push_back(d.mapq); flag.push_back(d.flag); ncig.push_back(x.nc); qlen.push_back(d.lseq);
-            const uint64_t sq = d.off + 32 + d.lname + 4ull * d.nc;
-            soff.push_back(sq); qoff.push_back(sq + ((uint64_t)d.lseq + 1) / 2);
-            coff.push_back(cw); { GatherJob g; g.src = x.cig_src; g.dst = cw * 4; g.bytes = (uint32_t)x.nc * 4u; g.pad_ = 0; gj.push_back(g); } cw += (uint64_t)x.nc;
-            RefCmpOut rc; rc.n_ops = x.nc; rc.nd = (int)x.nd; rc.nev = (int)x.nev; rc.pad = 0; counts.push_back(rc); nindel.push_back((int)x.nid);
-            noff.push_back(nbytes); { GatherJob g; g.src = base + d.off + 32; g.dst = nbytes; g.bytes = d.lname; g.pad_ = 0; nj.push_back(g); } nbytes += d.lname;
-        }
-        if (!done) {
-            if (wo[k].status == 1) return fail(-33, "truncated BAM record");
-            if (wo[k].status == 2) return fail(-33, malformed);
-        }
-    }
-    const int n = (int)pos0.size();
-    c->n_reads = n;
-    // read names: one gather + one copy (the only record bytes that come to the host)
-    std::vector<char> names(nbytes + 1, 0);
-    DevBuf d_cig, d_gj, d_names;
-    if (n > 0) {
-        if (d_cig.ensure(cw * 4 + 64) || d_gj.ensure((size_t)n * sizeof(GatherJob)) || d_names.ensure(nbytes + 64)) return nullptr;
-        for (GatherJob &g : gj) g.dst += d_cig.addr();
-        CHK(hipMemcpyAsync(d_gj.p, gj.data(), (size_t)n * sizeof(GatherJob), hipMemcpyHostToDevice, st));
-        lcd_launch_bam_cigar((const GatherJob *)d_gj.p, n, st);
-        CHK(hipGetLastError());
-        if (meta) {
-            CHK(hipStreamSynchronize(st)); // (d_gj is reused)
-            for (GatherJob &g : nj) g.dst += d_names.addr();
-            CHK(hipMemcpyAsync(d_gj.p, nj.data(), (size_t)n * sizeof(GatherJob), hipMemcpyHostToDevice, st));
-            lcd_launch_gather((const GatherJob *)d_gj.p, n, st);
-            CHK(hipGetLastError());
-            CHK(hipMemcpyAsync(names.data(), d_names.p, nbytes, hipMemcpyDeviceToHost, st));
-            CHK(hipStreamSynchronize(st));
-        }
-    }
-    auto dupv = [](const auto &v) { using T = typename std::decay<decltype(v[0])>::type; T *p = (T *)malloc((v.size() + 1) * sizeof(T)); if (!v.empty()) memcpy(p, v.data(), v.size() * sizeof(T)); return p; };
-    if (meta) {
-        meta->n_reads = n; meta->pos0 = dupv(pos0); meta->end_pos = dupv(endp); meta->mapq = dupv(mapq); meta->flag = dupv(flag); meta->n_cigar = dupv(ncig); meta->qlen = dupv(qlen);
-        meta->cigar_off = dupv(coff); meta->seq_off = dupv(soff); meta->qual_off = dupv(qoff); meta->name_off = dupv(noff); meta->name_pool = dupv(names);
-        // (cigar_pool / seq_pool / qual_pool stay NULL: those bytes are in HBM; seq_off / qual_off are offsets of the inflated stream)
-    }
-    if (n == 0) return c.release();
-    // 4. digars, kept in HBM; bases and qualities are read in place
-    c->qlen = qlen; c->seq_off = soff; c->qual_off = qoff; c->seq_base = base; c->qual_base = base;
-    c->status.resize(n); c->n_cand.resize(n); c->beg.resize(n); c->end.resize(n);
-    DigarWords W; W.off = coff.data(); W.n_cigar = ncig.data(); W.d_words = &d_cig; W.counts = counts.data(); W.n_indel = nindel.data(); W.d_qual_base = base;
-    DigarKeep keep; keep.d_dig = &c->d_dig;
-    uint64_t *doff = nullptr; lcd_digar_t *dg = nullptr;
-    const int rc = digar_batch_core(opt, n, pos0.data(), W, nullptr, qoff.data(), qlen.data(), nullptr, reg_beg, reg_end, im.tlen, &doff, &dg, &c->iv_off, &c->ivs, &c->iv_in_chunk,
-                                    c->status.data(), c->beg.data(), c->end.data(), c->n_cand.data(), st, &keep);
-    free(doff);
-    if (rc) { if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return nullptr; } // (the caller's arrays were handed out above)
-    if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return fail(-10, "HIP call failed: hipStreamSynchronize"); }
-#undef CHK
-    c->slot.swap(keep.slot); c->n_digar.swap(keep.n_digar);
-    return c.release();
-}
-void lcd_chunk_destroy(lcd_chunk_t *c) { delete c; }
-int lcd_chunk_n_reads(const lcd_chunk_t *c) { return c ? c->n_reads : 0; }
-// what collect_digar_from_eqx_cigar leaves on the host side of the reference: per read 0 / -1 (skipped as too noisy) / -2 ('M' operation), digar->beg / end, the number
-// of candidate variants; the reads' noisy windows in cr_index order (CSR; pointers into the chunk, valid until it is destroyed) and which of them enter chunk_noisy_regs
-int lcd_chunk_read_info(const lcd_chunk_t *c, int *status, int64_t *beg, int64_t *end, int *n_cand_vars, int *n_digars) {
-    for (int r = 0; r < c->n_reads; ++r) { if (status) status[r] = c->status[r]; if (beg) beg[r] = c->beg[r]; if (end) end[r] = c->end[r]; if (n_cand_vars) n_cand_vars[r] = c->n_cand[r]; if (n_digars) n_digars[r] = c->n_digar[r]; }
-    return c->n_reads;
-}
-int lcd_chunk_intervals(const lcd_chunk_t *c, const uint64_t **iv_off, const lcd_noisy_iv_t **ivs, const uint8_t **iv_in_chunk) {
-    *iv_off = c->iv_off; *ivs = c->ivs; *iv_in_chunk = c->iv_in_chunk;
-    return c->n_reads;
-}
-// collect_noisy_read_info's digar walk (src/align.c:1392-1456) for many (region, read) pairs, on the digars in HBM: out per pair the read's query interval over the
-// region and the cover flag -- 12 bytes per pair come back
-int lcd_chunk_region_slices(const lcd_chunk_t *c, int n_pairs, const int *pair_read, const int64_t *pair_reg_beg, const int64_t *pair_reg_end, int noisy_reg_flank_len,
-                            int *read_beg, int *read_end, int *cover) {
-    if (n_pairs <= 0) return 0;
-    if (use_device(c->device)) return -1;
-    std::vector<SliceJob> jobs(n_pairs);
-    for (int i = 0; i < n_pairs; ++i) {
-        const int r = pair_read[i];
-        if (r < 0 || r >= c->n_reads) return set_err(-4, "lcd_chunk_region_slices: read index out of range");
-        SliceJob &j = jobs[i]; j.digar_off = c->slot[r]; j.n_digar = c->n_digar[r]; j.qlen = c->qlen[r]; j.reg_beg = pair_reg_beg[i]; j.reg_end = pair_reg_end[i];
-    }
-    StreamGuard st; if (st.create()) return -10;
-    DevBuf d_jobs, d_outs;
-    if (d_jobs.ensure(n_pairs * sizeof(SliceJob)) || d_outs.ensure(n_pairs * sizeof(SliceOut))) return -11;
-    HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), n_pairs * sizeof(SliceJob), hipMemcpyHostToDevice, st));
-    lcd_launch_slices((const SliceJob *)d_jobs.p, (SliceOut *)d_outs.p, (const DigarRec *)c->d_dig.p, noisy_reg_flank_len, n_pairs, st);
-    HIPCHK(hipGetLastError());
-    std::vector<SliceOut> outs(n_pairs);
-    HIPCHK(hipMemcpyAsync(outs.data(), d_outs.p, n_pairs * sizeof(SliceOut), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < n_pairs; ++i) { read_beg[i] = outs[i].read_beg; read_end[i] = outs[i].read_end; cover[i] = outs[i].cover; }
-    return 0;
-}
 // a region of the batch from the chunk in HBM: the slices (read_beg / read_end / cover, from lcd_chunk_region_slices) give the lengths and cover flags the host
 // plans the chains with; the bases are unpacked on the device from the chunk's packed records into the batch's input pool at lcd_batch_upload -- no base crosses
 // PCIe for a region.  Otherwise lcd_batch_add_region_from_chunk (same results).  The batch must live on the chunk's device.
@@ -3456,70 +2463,6 @@ int lcd_batch_add_region_from_chunk_dev(lcd_batch_t *b, const lcd_chunk_t *c, in
                 break;
             }
     return ri;
-}
-
-int lcd_digar_batch_tags(const lcd_digar_opt_t *opt, int mode, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
-                         const char *const *tags, const uint8_t *qual_pool, const uint64_t *qual_off, const int *qlen, const uint8_t *pal_flags, int64_t reg_beg,
-                         int64_t reg_end, int64_t whole_ref_len, uint64_t **digar_off_out, lcd_digar_t **digars_out, uint64_t **iv_off_out,
-                         lcd_noisy_iv_t **ivs_out, uint8_t **iv_in_chunk_out, int *status, int64_t *beg, int64_t *end, int *n_cand_vars) {
-    *digar_off_out = *iv_off_out = nullptr; *digars_out = nullptr; *ivs_out = nullptr; *iv_in_chunk_out = nullptr;
-    if (mode != LCD_DIGAR_CS && mode != LCD_DIGAR_MD) return set_err(-2, "lcd_digar_batch_tags: mode is LCD_DIGAR_CS or LCD_DIGAR_MD");
-    if (ensure_init()) return -1;
-    if (n <= 0) return 0;
-    StreamGuard st; if (st.create()) return -10;
-    std::vector<uint32_t> words; std::vector<uint64_t> off(n); std::vector<int> cnt(n), pre(n, 0); std::vector<int64_t> rlen(n);
-    for (int r = 0; r < n; ++r) {
-        const uint32_t *cig = cigar_pool + cigar_off[r];
-        off[r] = words.size();
-        const bool ok = mode == LCD_DIGAR_CS ? cs_to_words(cig, n_cigar[r], tags[r], words) : md_to_words(cig, n_cigar[r], tags[r], words);
-        if (!ok) { pre[r] = 1; words.resize(off[r]); }           // the reference stops the program here; the read comes back with status -2 and no digars
-        cnt[r] = (int)(words.size() - off[r]);
-        long long rl = 0;
-        for (int i = 0; i < n_cigar[r]; ++i) { const int op = cig[i] & 0xf; if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += cig[i] >> 4; }
-        rlen[r] = rl;
-    }
-    words.push_back(0);
-    DigarWords W; W.h_pool = words.data(); W.off = off.data(); W.n_cigar = cnt.data(); W.clip_rule = mode == LCD_DIGAR_CS ? 1 : 0; W.rlen_true = rlen.data(); W.pre_status = pre.data();
-    return digar_batch_core(opt, n, pos0, W, qual_pool, qual_off, qlen, pal_flags, reg_beg, reg_end, whole_ref_len, digar_off_out, digars_out, iv_off_out, ivs_out,
-                            iv_in_chunk_out, status, beg, end, n_cand_vars, st);
-}
-
-int lcd_digar_batch_ref(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
-                        const uint8_t *seq_pool, const uint64_t *seq_off, const uint8_t *qual_pool, const uint64_t *qual_off, const int *qlen, const uint8_t *pal_flags,
-                        const char *ref_seq, int64_t ref_beg, int64_t ref_end, int64_t reg_beg, int64_t reg_end, int64_t whole_ref_len, uint64_t **digar_off_out,
-                        lcd_digar_t **digars_out, uint64_t **iv_off_out, lcd_noisy_iv_t **ivs_out, uint8_t **iv_in_chunk_out, int *status, int64_t *beg,
-                        int64_t *end, int *n_cand_vars) {
-    *digar_off_out = *iv_off_out = nullptr; *digars_out = nullptr; *ivs_out = nullptr; *iv_in_chunk_out = nullptr;
-    if (ensure_init()) return -1;
-    if (n <= 0) return 0;
-    if (ref_end < ref_beg) return set_err(-2, "lcd_digar_batch_ref: empty reference window");
-    StreamGuard st; if (st.create()) return -10;
-    uint64_t cig_words = 0, seq_bytes = 0;
-    for (int r = 0; r < n; ++r) { cig_words = std::max<uint64_t>(cig_words, cigar_off[r] + n_cigar[r]); seq_bytes = std::max<uint64_t>(seq_bytes, seq_off[r] + (uint64_t)(qlen[r] + 1) / 2); }
-    const uint64_t ref_len = (uint64_t)(ref_end - ref_beg + 1);
-    DevBuf d_cig, d_seq, d_ref, d_jobs, d_cnt, d_words;
-    if (d_cig.ensure(cig_words * 4 + 64) || d_seq.ensure(seq_bytes + 64) || d_ref.ensure(ref_len + 64) || d_jobs.ensure(n * sizeof(RefCmpJob)) || d_cnt.ensure(n * sizeof(RefCmpOut))) return -11;
-    std::vector<RefCmpJob> jobs(n);
-    for (int r = 0; r < n; ++r) { RefCmpJob &j = jobs[r]; j.cigar_off = d_cig.addr() + cigar_off[r] * 4; j.seq_off = d_seq.addr() + seq_off[r]; j.out_off = 0; j.n_cigar = n_cigar[r]; j.pad = 0; j.pos0 = pos0[r]; }
-    HIPCHK(hipMemcpyAsync(d_cig.p, cigar_pool, cig_words * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_seq.p, seq_pool, seq_bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(RefCmpJob), hipMemcpyHostToDevice, st));
-    lcd_launch_refcmp(false, (const RefCmpJob *)d_jobs.p, (RefCmpOut *)d_cnt.p, (const char *)d_ref.p, ref_beg, ref_end, n, st);
-    HIPCHK(hipGetLastError());
-    std::vector<RefCmpOut> cnt(n);
-    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, n * sizeof(RefCmpOut), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::vector<uint64_t> off(n); std::vector<int> nw(n); uint64_t tot = 0;
-    for (int r = 0; r < n; ++r) { off[r] = tot; nw[r] = cnt[r].n_ops; tot += (uint64_t)cnt[r].n_ops; }
-    if (d_words.ensure(tot * 4 + 64)) return -11;
-    for (int r = 0; r < n; ++r) jobs[r].out_off = d_words.addr() + off[r] * 4;
-    HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(RefCmpJob), hipMemcpyHostToDevice, st));
-    lcd_launch_refcmp(true, (const RefCmpJob *)d_jobs.p, (RefCmpOut *)d_cnt.p, (const char *)d_ref.p, ref_beg, ref_end, n, st);
-    HIPCHK(hipGetLastError());
-    DigarWords W; W.off = off.data(); W.n_cigar = nw.data(); W.d_words = &d_words; W.counts = cnt.data();
-    return digar_batch_core(opt, n, pos0, W, qual_pool, qual_off, qlen, pal_flags, reg_beg, reg_end, whole_ref_len, digar_off_out, digars_out, iv_off_out, ivs_out,
-                            iv_in_chunk_out, status, beg, end, n_cand_vars, st);
 }
 
 int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int *chain_read0, const int *chain_n_reads, int n_reads_total,
@@ -3607,912 +2550,6 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------------
-// K5
-int lcd_assign_hap_batch(int n, lcd_hap_problem_t *probs, const int *targets) {
-    if (ensure_init()) return -1;
-    if (n <= 0) return 0;
-    StreamGuard st; if (st.create()) return -10;
-    std::vector<uint8_t> hb; // host staging; offsets become device addresses
-    auto put = [&](const void *p, size_t bytes) { size_t o = lcd_align_up(hb.size(), 16); hb.resize(o + bytes); if (p && bytes) memcpy(hb.data() + o, p, bytes); return (uint64_t)o; };
-    struct Off { uint64_t var_pos, var_type, var_cate, is_hp, total_cov, alle_off, alle_covs, start_var, end_var, allele_off, alleles, ordered, cr_read, is_skipped,
-                 haps, phase_sets, agree, conflict, var_ps, cons, prof, valid, vii, het, is_het, n_agree, n_conflict, cur_cons, flags; };
-    std::vector<Off> offs(n);
-    for (int i = 0; i < n; ++i) {
-        const lcd_hap_problem_t &p = probs[i]; Off &o = offs[i];
-        const int R = p.n_reads, V = p.n_vars, TA = V ? p.alle_off[V] : 0, NA = R ? p.allele_off[R] : 0;
-        o.var_pos = put(p.var_pos, (size_t)V * 8); o.var_type = put(p.var_type, (size_t)V * 4); o.var_cate = put(p.var_cate, (size_t)V * 4);
-        o.is_hp = put(p.is_homopolymer_indel, (size_t)V * 4); o.total_cov = put(p.total_cov, (size_t)V * 4);
-        o.alle_off = put(p.alle_off, (size_t)(V + 1) * 4); o.alle_covs = put(p.alle_covs, (size_t)TA * 4);
-        o.start_var = put(p.start_var_idx, (size_t)R * 4); o.end_var = put(p.end_var_idx, (size_t)R * 4);
-        o.allele_off = put(p.allele_off, (size_t)(R + 1) * 4); o.alleles = put(p.alleles, (size_t)NA * 4);
-        o.ordered = put(p.ordered_read_ids, (size_t)R * 4); o.cr_read = put(p.cr_read, (size_t)p.n_cr * 4); o.is_skipped = put(p.is_skipped, (size_t)R);
-        o.haps = put(p.haps, (size_t)R * 4); o.phase_sets = put(p.phase_sets, (size_t)R * 8);
-        o.agree = put(p.n_clean_agree_snps, (size_t)R * 4); o.conflict = put(p.n_clean_conflict_snps, (size_t)R * 4);
-        o.var_ps = put(p.var_phase_set, (size_t)V * 8); o.cons = put(p.hap_to_cons_alle, (size_t)V * 3 * 4); o.prof = put(p.hap_to_alle_profile, (size_t)TA * 3 * 4);
-        o.valid = put(nullptr, (size_t)V * 4); o.vii = put(nullptr, (size_t)V * 4); o.het = put(nullptr, (size_t)V * 4); o.is_het = put(nullptr, (size_t)V * 4);
-        o.n_agree = put(nullptr, (size_t)V * 4); o.n_conflict = put(nullptr, (size_t)V * 4); o.cur_cons = put(nullptr, (size_t)V * 2 * 4); o.flags = put(nullptr, 64);
-    }
-    DevBuf d_buf, d_probs;
-    if (d_buf.ensure(hb.size() + 64) || d_probs.ensure(n * sizeof(HapProb))) return -11;
-    HIPCHK(hipMemcpyAsync(d_buf.p, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
-    std::vector<HapProb> hp(n);
-    const uint64_t B = d_buf.addr();
-    for (int i = 0; i < n; ++i) {
-        const lcd_hap_problem_t &p = probs[i]; const Off &o = offs[i]; HapProb &q = hp[i];
-        q.n_reads = p.n_reads; q.n_vars = p.n_vars; q.is_ont = p.is_ont; q.n_cr = p.n_cr; q.total_alle = p.n_vars ? p.alle_off[p.n_vars] : 0; q.target = targets[i];
-#define DP(T, f) (T)(uintptr_t)(B + o.f)
-        q.var_pos = DP(const long long *, var_pos); q.var_type = DP(const int *, var_type); q.var_cate = DP(const int *, var_cate); q.is_hp = DP(const int *, is_hp);
-        q.total_cov = DP(const int *, total_cov); q.alle_off = DP(const int *, alle_off); q.alle_covs = DP(const int *, alle_covs);
-        q.start_var = DP(const int *, start_var); q.end_var = DP(const int *, end_var); q.allele_off = DP(const int *, allele_off); q.alleles = DP(const int *, alleles);
-        q.ordered = DP(const int *, ordered); q.cr_read = DP(const int *, cr_read); q.is_skipped = DP(const uint8_t *, is_skipped);
-        q.haps = DP(int *, haps); q.phase_sets = DP(long long *, phase_sets); q.n_agree_snps = DP(int *, agree); q.n_conflict_snps = DP(int *, conflict);
-        q.var_ps = DP(long long *, var_ps); q.cons = DP(int *, cons); q.prof = DP(int *, prof);
-        q.valid = DP(int *, valid); q.vii = DP(int *, vii); q.het = DP(int *, het); q.is_het = DP(int *, is_het); q.n_agree = DP(int *, n_agree); q.n_conflict = DP(int *, n_conflict);
-        q.cur_cons = DP(int *, cur_cons); q.flags = DP(int *, flags);
-#undef DP
-    }
-    HIPCHK(hipMemcpyAsync(d_probs.p, hp.data(), n * sizeof(HapProb), hipMemcpyHostToDevice, st));
-    lcd_launch_hap((const HapProb *)d_probs.p, n, st);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hb.data(), d_buf.p, hb.size(), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) {
-        lcd_hap_problem_t &p = probs[i]; const Off &o = offs[i];
-        const int R = p.n_reads, V = p.n_vars, TA = V ? p.alle_off[V] : 0;
-        memcpy(p.haps, hb.data() + o.haps, (size_t)R * 4); memcpy(p.phase_sets, hb.data() + o.phase_sets, (size_t)R * 8);
-        memcpy(p.n_clean_agree_snps, hb.data() + o.agree, (size_t)R * 4); memcpy(p.n_clean_conflict_snps, hb.data() + o.conflict, (size_t)R * 4);
-        memcpy(p.var_phase_set, hb.data() + o.var_ps, (size_t)V * 8); memcpy(p.hap_to_cons_alle, hb.data() + o.cons, (size_t)V * 3 * 4);
-        memcpy(p.hap_to_alle_profile, hb.data() + o.prof, (size_t)TA * 3 * 4);
-    }
-    return 0;
-}
-int lcd_assign_hap_germline(lcd_hap_problem_t *p, int target_var_cate) { return lcd_assign_hap_batch(1, p, &target_var_cate); }
-
-// ---------------------------------------------------------------------------------------------------
-// per-call mirrors of src/align.h
-int lcd_wfa_end2end_aln(uint8_t *pattern, int plen, uint8_t *text, int tlen, int gap_aln, int b, int q, int e, int q2, int e2, int heuristic,
-                        int affine_gap, uint32_t **cigar_buf, int *cigar_length, uint8_t **pattern_alg, uint8_t **text_alg, int *alg_length) {
-    if (heuristic != 0 || affine_gap != 1) return set_err(-2, "only heuristic=NONE, affine_gap=2P (the germline-live WFA configuration) is implemented");
-    std::vector<uint8_t> pool((size_t)plen + tlen + 32, 4);
-    if (plen) memcpy(pool.data(), pattern, plen);
-    const uint64_t toff = lcd_align_up(plen, 16);
-    pool.resize(toff + tlen + 16, 4);
-    if (tlen) memcpy(pool.data() + toff, text, tlen);
-    const uint64_t po = 0; const int want = ((cigar_buf && cigar_length) ? 1 : 0) | ((pattern_alg && text_alg) ? 2 : 0);
-    const int maxl = plen + tlen + 1;
-    std::vector<uint32_t> cig(maxl); std::vector<uint8_t> rows(2 * (size_t)maxl);
-    int score = 0, nc = 0, al = 0;
-    int rc = lcd_wfa_batch(1, pool.data(), pool.size(), &po, &plen, &toff, &tlen, &gap_aln, b, q, e, q2, e2, want, &score, cig.data(), maxl, &nc, rows.data(), maxl, &al);
-    if (rc) return rc;
-    if (want & 1) { *cigar_buf = (uint32_t *)malloc((nc > 0 ? nc : 1) * sizeof(uint32_t)); memcpy(*cigar_buf, cig.data(), (size_t)nc * 4); *cigar_length = nc; }
-    if (want & 2) {
-        uint8_t *mem = (uint8_t *)calloc(2 * (size_t)maxl, 1); // src/align.c:288-291
-        memcpy(mem, rows.data(), al); memcpy(mem + maxl, rows.data() + maxl, al);
-        *pattern_alg = mem; *text_alg = mem + maxl; *alg_length = al;
-    }
-    return 0;
-}
-
-// end2end_aln (src/align.c:610-628): target given as letters, mapped with nst_nt4_table (src/seq.c:14-31: ACGT / acgt -> 0..3, '-' -> 5, else 4;
-// the bytes 0..3 map to themselves), then the 2-piece WFA with opt's penalties; returns the CIGAR length, *cigar_buf malloc()'d
-int lcd_end2end_aln(const lcd_opt_t *opt, char *tseq, int tlen, uint8_t *qseq, int qlen, uint32_t **cigar_buf) {
-    if (qlen <= 0 || tlen <= 0) return 0;
-    std::vector<uint8_t> t2((size_t)tlen);
-    for (int i = 0; i < tlen; ++i) {
-        const uint8_t c = (uint8_t)tseq[i];
-        t2[i] = c < 4 ? c : (c == 'A' || c == 'a') ? 0 : (c == 'C' || c == 'c') ? 1 : (c == 'G' || c == 'g') ? 2 : (c == 'T' || c == 't') ? 3 : c == '-' ? 5 : 4;
-    }
-    int cigar_len = 0;
-    const int rc = lcd_wfa_end2end_aln(t2.data(), tlen, qseq, qlen, opt->gap_aln, opt->mismatch, opt->gap_open1, opt->gap_ext1, opt->gap_open2, opt->gap_ext2, 0, 1,
-                                       cigar_buf, &cigar_len, nullptr, nullptr, nullptr);
-    return rc < 0 ? rc : cigar_len;
-}
-// wfa_collect_diff_ins_seq (src/align.c:463-494): align large vs small, return the longest run of large-only columns (first one on ties)
-int lcd_wfa_collect_diff_ins_seq(const lcd_opt_t *opt, uint8_t *large_seq, int large_len, uint8_t *small_seq, int small_len, uint8_t **diff_seq) {
-    uint8_t *la = nullptr, *sa = nullptr; int aln_len = 0;
-    const int rc = lcd_wfa_end2end_aln(large_seq, large_len, small_seq, small_len, opt->gap_aln, opt->mismatch, opt->gap_open1, opt->gap_ext1, opt->gap_open2, opt->gap_ext2, 0, 1,
-                                       nullptr, nullptr, &la, &sa, &aln_len);
-    if (rc < 0) return rc;
-    int best_len = 0, best_pos = -1;
-    for (int i = 0; i < aln_len; ++i) {
-        if (sa[i] == 5 && la[i] != 5) {
-            int j = i; while (j < aln_len && sa[j] == 5 && la[j] != 5) ++j;
-            if (j - i > best_len) { best_len = j - i; best_pos = i; }
-            i = j - 1;
-        }
-    }
-    if (best_len > 0) { *diff_seq = (uint8_t *)malloc((size_t)best_len); memcpy(*diff_seq, la + best_pos, (size_t)best_len); }
-    free(la);
-    return best_len;
-}
-// The two exports of src/align.h that the germline path never reaches (edlib_infix_aln is only called from somatic-mode code,
-// wfa_heuristic_aln has no caller at all): present so that a longcallD built against this library links, and loud when reached
-// edlib_infix_aln (src/align.c:256-275): edlib's HW mode with the path -- a somatic-mode (-s) call in longcallD, implemented and pinned to the reference's own edlib
-// (tests/golden/edlib_golden.json, hw_cases).  Returns the edit distance, -1 on error; *n_eq / *n_xid from the path as edlibAlignmentToXID counts them.
-int lcd_edlib_infix_aln(uint8_t *target, int tlen, uint8_t *query, int qlen, int *n_eq, int *n_xid) {
-    std::vector<uint8_t> pool((size_t)lcd_align_up(qlen, 16) + tlen + 32, 4);
-    if (qlen) memcpy(pool.data(), query, qlen);
-    const uint64_t qo = 0, to = lcd_align_up(qlen, 16);
-    if (tlen) memcpy(pool.data() + to, target, tlen);
-    int d, x, a, c, s0, e0;
-    if (lcd_edlib_batch_hw(1, pool.data(), pool.size(), &qo, &qlen, &to, &tlen, &d, &x, &a, &c, &s0, &e0)) { if (n_eq) *n_eq = -1; if (n_xid) *n_xid = -1; return -1; }
-    if (n_eq && n_xid) { *n_eq = a; *n_xid = c; }
-    return d;
-}
-// The export of src/align.h that has no caller at all in longcallD: present so that a longcallD built against this library links, and loud when reached
-int lcd_wfa_heuristic_aln(uint8_t *, int, uint8_t *, int, int, int, int, int, int, int, int *n_eq, int *n_xid) {
-    if (n_eq) *n_eq = -1; if (n_xid) *n_xid = -1;
-    fprintf(stderr, "liblcd_hotpath: wfa_heuristic_aln (x-drop WFA, src/align.c:332) has no caller in longcallD and is not implemented\n");
-    return set_err(-2, "wfa_heuristic_aln (x-drop heuristic) is not implemented");
-}
-
-static int ed1(uint8_t *target, int tlen, uint8_t *query, int qlen, int *dist, int *xg, int *neq, int *nxid) {
-    std::vector<uint8_t> pool((size_t)lcd_align_up(qlen, 16) + tlen + 32, 4);
-    if (qlen) memcpy(pool.data(), query, qlen);
-    const uint64_t qo = 0, to = lcd_align_up(qlen, 16);
-    if (tlen) memcpy(pool.data() + to, target, tlen);
-    return lcd_edlib_batch(1, pool.data(), pool.size(), &qo, &qlen, &to, &tlen, dist, xg, neq, nxid);
-}
-int lcd_edlib_end2end_aln(uint8_t *target, int tlen, uint8_t *query, int qlen, int *n_eq, int *n_xid) {
-    int d, x, a, c; if (ed1(target, tlen, query, qlen, &d, &x, &a, &c)) return -1;
-    if (n_eq && n_xid) { *n_eq = a; *n_xid = c; }
-    return d;
-}
-int lcd_edlib_xgaps(uint8_t *target, int tlen, uint8_t *query, int qlen) { int d, x, a, c; if (ed1(target, tlen, query, qlen, &d, &x, &a, &c)) return -1; return x; }
-int lcd_edlib_edit_distance(uint8_t *target, int tlen, uint8_t *query, int qlen) { int d, x, a, c; if (ed1(target, tlen, query, qlen, &d, &x, &a, &c)) return -1; return d; }
-
-int lcd_collect_noisy_reg_aln_strs(const lcd_opt_t *opt, const lcd_read_view_t *chunk_reads, int64_t noisy_reg_beg, int64_t noisy_reg_end, int noisy_reg_i,
-                                   int n, int *noisy_reads, const uint8_t *ref_seq, int ref_seq_len, int *clu_n_seqs, int **clu_read_ids, lcd_aln_str_t **aln_strs) {
-    (void)noisy_reg_i;
-    if (n <= 0) return 0;
-    lcd_batch_t *b = lcd_batch_create(opt);
-    if (!b) return -1;
-    int rc = lcd_batch_add_region_from_chunk(b, chunk_reads, noisy_reg_beg, noisy_reg_end, n, noisy_reads, ref_seq, ref_seq_len);
-    if (rc < 0) { lcd_batch_destroy(b); return rc; }
-    if ((rc = lcd_batch_upload(b)) || (rc = lcd_batch_run(b)) || (rc = lcd_batch_download(b))) { lcd_batch_destroy(b); return rc; }
-    lcd_batch_region_sorted_ids(b, 0, noisy_reads);
-    int nc = lcd_batch_region_result(b, 0, clu_n_seqs, clu_read_ids, aln_strs);
-    lcd_batch_destroy(b);
-    return nc;
-}
-
-// ---- the first round of collect_var_main on a device-resident chunk (src/collect_var.c:2897-2980, steps 1.2 - 3.1), see include/lcd_hotpath.h ----
-void lcd_clean_opt_default(lcd_clean_opt_t *o, int is_ont) {
-    o->min_dp = 5; o->min_alt_dp = 2; o->min_bq = 10; o->min_sv_len = 30; o->noisy_reg_max_xgaps = 5; o->noisy_reg_flank_len = 10; o->noisy_reg_merge_dis = 500;
-    o->is_ont = is_ont ? 1 : 0; o->out_somatic = 0; o->min_af = 0.20; o->max_af = 0.80; o->strand_bias_pval = 0.01f;
-}
-namespace {
-constexpr int CV_NON_VAR = 0x800, CV_LOW_COV = 0x001, CV_STRAND_BIAS = 0x002, CV_LOW_AF = 0x400, CV_REP_HET = 0x010, CV_NOT_CAND = 0x800 | 0x001 | 0x002;
-// fisher_exact_test (src/math_utils.c:119-168; fast_lgamma is lgamma: its cache holds lgamma(i))
-double cv_log_hyper(int a, int b, int c, int d) {
-    const int n1 = a + b, n2 = c + d, m1 = a + c, m2 = b + d, N = n1 + n2;
-    if (n1 > n2) return cv_log_hyper(c, d, a, b);
-    if (m1 > m2) return cv_log_hyper(b, a, d, c);
-    return lgamma(n1 + 1) + lgamma(n2 + 1) + lgamma(m1 + 1) + lgamma(m2 + 1) - (lgamma(a + 1) + lgamma(b + 1) + lgamma(c + 1) + lgamma(d + 1) + lgamma(N + 1));
-}
-double cv_fisher(int a, int b, int c, int d) {
-    const double p_obs = exp(cv_log_hyper(a, b, c, d));
-    double total = 0.0;
-    const int min_a = (0 > (a + c) - (a + b + c + d)) ? 0 : (a + c) - (b + d), max_a = (a + b) < (a + c) ? (a + b) : (a + c);
-    const int mode_a = (int)((a + b) * (a + c) / (double)(a + b + c + d));
-    auto term = [&](int ca) {
-        const int cb = (a + b) - ca, cc = (a + c) - ca, cd = (b + d) - cb;
-        if (cb >= 0 && cc >= 0 && cd >= 0) { const double p = exp(cv_log_hyper(ca, cb, cc, cd)); if (p <= p_obs + DBL_EPSILON) total += p; }
-    };
-    for (int delta = 0; delta <= max_a - min_a; delta++) {
-        if (mode_a + delta <= max_a) term(mode_a + delta);
-        if (delta > 0 && mode_a - delta >= min_a) term(mode_a - delta);
-    }
-    return total;
-}
-int cv_strand_bias(const CvCov &v, float pval) { // var_is_strand_bias (src/collect_var.c:270)
-    const int f = v.strand[1], r = v.strand[3], e = (f + r) / 2;
-    if (e == 0) return 0;
-    const float p = (float)cv_fisher(f, r, e, e);
-    return p < pval;
-}
-// intervals [st, en) sorted by start, for counting overlaps with short queries (cr_overlap's count)
-struct CvOvl {
-    std::vector<long long> st, en; long long maxlen = 0;
-    void build(std::vector<std::pair<long long, long long>> v) {
-        std::sort(v.begin(), v.end());
-        for (auto &x : v) { st.push_back(x.first); en.push_back(x.second); maxlen = std::max(maxlen, x.second - x.first); }
-    }
-    long long count(long long qs, long long qe) const {
-        long long n = 0;
-        for (long long i = (long long)(std::lower_bound(st.begin(), st.end(), qe) - st.begin()) - 1; i >= 0 && st[i] >= qs - maxlen; --i) if (qs < en[i]) n++;
-        return n;
-    }
-};
-} // namespace
-
-static int clean_vars_one(const lcd_chunk_t *c0, const lcd_clean_opt_t *opt, const int *ordered, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
-                          int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre, const int64_t *low_comp, int n_low,
-                          lcd_clean_vars_t *out) {
-    memset(out, 0, sizeof(*out));
-    lcd_chunk_s *c = const_cast<lcd_chunk_s *>(c0);
-    if (!c || !opt || !out) return set_err(-4, "lcd_chunk_clean_vars: NULL argument");
-    if (opt->out_somatic) return set_err(-2, "lcd_chunk_clean_vars: somatic mode (out_somatic) is not supported");
-    if (use_device(c->device)) return -1;
-    const int n = c->n_reads;
-    if (reg_beg < 1 || reg_end < reg_beg || reg_end - reg_beg > (1ll << 28)) return set_err(-4, "lcd_chunk_clean_vars: region [reg_beg, reg_end] out of range");
-    if (!ref_seq || ref_end < ref_beg) return set_err(-4, "lcd_chunk_clean_vars: no reference");
-    if (n > 0 && !ordered) return set_err(-4, "lcd_chunk_clean_vars: no ordered_read_ids");
-    // the reads as the kernels see them; the qualities of a host-array chunk go up once
-    std::vector<CvRead> reads(n + 1);
-    uint64_t qbase = c->qual_base;
-    if (n > 0 && !qbase) {
-        std::lock_guard<std::mutex> lk(c->qual_mu);
-        if (!c->d_qual.p) {
-            if (c->d_qual.ensure(c->h_qual.size() + 64)) return -11;
-            if (!c->h_qual.empty() && hipMemcpy(c->d_qual.p, c->h_qual.data(), c->h_qual.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); c->d_qual.release(); return set_err(-10, "lcd_chunk_clean_vars: quality upload failed"); }
-            out->qual_upload_bytes = c->h_qual.size();
-        }
-        qbase = c->d_qual.addr();
-    }
-    uint64_t n_rec = 0;
-    for (int r = 0; r < n; ++r) {
-        CvRead &x = reads[r];
-        x.dig = c->slot[r]; x.n_digar = c->n_digar[r]; x.seq = c->seq_base + c->seq_off[r]; x.qual = qbase + c->qual_off[r]; x.beg = c->beg[r]; x.end = c->end[r];
-        x.qlen = c->qlen[r]; x.strand = is_rev ? (is_rev[r] != 0) : 0; x.iv = c->iv_off[r]; x.n_iv = (int)(c->iv_off[r + 1] - c->iv_off[r]);
-        n_rec = std::max<uint64_t>(n_rec, x.dig + (uint64_t)x.n_digar);
-    }
-    std::vector<int> order;
-    for (int i = 0; i < n; ++i) {
-        const int r = ordered[i];
-        if (r < 0 || r >= n) return set_err(-4, "lcd_chunk_clean_vars: ordered_read_ids out of range");
-        if (c->status[r] != -1) order.push_back(r);
-    }
-    const int m = (int)order.size();
-    CvOpt o; o.min_dp = opt->min_dp; o.min_alt_dp = opt->min_alt_dp; o.min_bq = opt->min_bq; o.min_sv_len = opt->min_sv_len; o.max_xgaps = opt->noisy_reg_max_xgaps; o.pad = 0;
-    o.min_af = opt->min_af; o.max_af = opt->max_af; o.reg_beg = reg_beg; o.reg_end = reg_end; o.ref_beg = ref_beg; o.ref_end = ref_end;
-    const uint64_t n_iv = n > 0 ? c->iv_off[n] : 0, ref_len = (uint64_t)(ref_end - ref_beg + 1);
-    StreamGuard st; if (st.create()) return -10;
-    DevBuf d_reads, d_order, d_ivs, d_ref, d_cnt, d_tot;
-    if (d_reads.ensure((n + 1) * sizeof(CvRead)) || d_order.ensure((m + 1) * 4ull) || d_ivs.ensure((n_iv + 1) * sizeof(IvRec)) || d_ref.ensure(ref_len + 64) ||
-        d_cnt.ensure((m + 1) * 4ull) || d_tot.ensure(64)) return -11;
-    const DigarRec *dg = (const DigarRec *)c->d_dig.p;
-    HIPCHK(hipMemcpyAsync(d_reads.p, reads.data(), (n + 1) * sizeof(CvRead), hipMemcpyHostToDevice, st));
-    if (m) HIPCHK(hipMemcpyAsync(d_order.p, order.data(), m * 4ull, hipMemcpyHostToDevice, st));
-    if (n_iv) HIPCHK(hipMemcpyAsync(d_ivs.p, c->ivs, n_iv * sizeof(IvRec), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_ref.p, ref_seq, ref_len, hipMemcpyHostToDevice, st));
-    const CvRead *R = (const CvRead *)d_reads.p; const int *O = (const int *)d_order.p;
-    // 1.2 candidate sites: count, offsets, emit with the key histogram, counting sort + bucket rank sort, dedup, compaction
-    lcd_launch_cv_count(R, O, m, dg, reg_beg, reg_end, (int *)d_cnt.p, st);
-    HIPCHK(hipGetLastError());
-    std::vector<int> cnt(m + 1, 0);
-    if (m) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, m * 4ull, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    long long n_raw = 0;
-    for (int k = 0; k < m; ++k) { const int x = cnt[k]; cnt[k] = (int)n_raw; n_raw += x; }
-    if (n_raw > (1ll << 30)) return set_err(-4, "lcd_chunk_clean_vars: too many site records");
-    const int nr = (int)n_raw;
-    const long long key0 = reg_beg - 1; const int nb = (int)(((reg_end - reg_beg + 1) >> 6) + 1); // (64 position keys per bucket, clean_vars_kernel.hip)
-    DevBuf d_off, d_sites, d_hist, d_fill, d_tmp, d_sorted, d_keep, d_kidx, d_u, d_cov, d_cate;
-    if (d_off.ensure((m + 1) * 4ull) || d_sites.ensure((nr + 1) * sizeof(CvSite)) || d_hist.ensure((nb + 2) * 4ull) || d_fill.ensure((nb + 2) * 4ull) ||
-        d_tmp.ensure((nr + 1) * 4ull) || d_sorted.ensure((nr + 1) * 4ull) || d_keep.ensure((nr + 1) * 4ull) || d_kidx.ensure((nr + 1) * 4ull)) return -11;
-    if (m) HIPCHK(hipMemcpyAsync(d_off.p, cnt.data(), m * 4ull, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemsetAsync(d_hist.p, 0, (nb + 2) * 4ull, st));
-    HIPCHK(hipMemsetAsync(d_fill.p, 0, (nb + 2) * 4ull, st));
-    lcd_launch_cv_emit(R, O, m, dg, reg_beg, reg_end, (const int *)d_off.p, (CvSite *)d_sites.p, (int *)d_hist.p, key0, st);
-    lcd_launch_cv_scan((int *)d_hist.p, nb + 1, (int *)d_tot.p, st);
-    lcd_launch_cv_sort((const CvSite *)d_sites.p, nr, R, (const int *)d_hist.p, (int *)d_fill.p, (int *)d_tmp.p, (int *)d_sorted.p, key0, nb, (int *)d_keep.p,
-                       opt->min_sv_len, st);
-    HIPCHK(hipGetLastError());
-    int ns = 0;
-    if (nr) {
-        HIPCHK(hipMemcpyAsync(d_kidx.p, d_keep.p, nr * 4ull, hipMemcpyDeviceToDevice, st));
-        lcd_launch_cv_scan((int *)d_kidx.p, nr, (int *)d_tot.p, st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&ns, d_tot.p, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    if (d_u.ensure((ns + 1) * sizeof(CvSite)) || d_cov.ensure((ns + 1) * sizeof(CvCov)) || d_cate.ensure((ns + 1) * 4ull)) return -11;
-    const CvSite *U = (const CvSite *)d_u.p;
-    lcd_launch_cv_compact((const CvSite *)d_sites.p, (const int *)d_sorted.p, (const int *)d_keep.p, (const int *)d_kidx.p, nr, (CvSite *)d_u.p, st);
-    // 1.3 pile-up and 2.2 per-site classification
-    HIPCHK(hipMemsetAsync(d_cov.p, 0, (ns + 1) * sizeof(CvCov), st));
-    lcd_launch_cv_pileup(R, O, m, dg, U, ns, (CvCov *)d_cov.p, o, st);
-    lcd_launch_cv_classify(U, R, (const CvCov *)d_cov.p, ns, (const unsigned char *)d_ref.p, o, (int *)d_cate.p, st);
-    HIPCHK(hipGetLastError());
-    std::vector<CvSite> sites(ns + 1); std::vector<CvCov> cov(ns + 1); std::vector<int> cate(ns + 1);
-    if (ns) {
-        HIPCHK(hipMemcpyAsync(sites.data(), d_u.p, ns * sizeof(CvSite), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(cov.data(), d_cov.p, ns * sizeof(CvCov), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(cate.data(), d_cate.p, ns * 4ull, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
-    // 2.2 / 2.3 classify_cand_vars (:902-1040), host side: the ONT strand-bias test, var_pos_cr, the noisy-region tests, cr_add_var_cr, cr_merge2, post_process
-    std::vector<std::pair<long long, long long>> vp;
-    for (int i = 0; i < ns; ++i) {
-        if (opt->is_ont && cate[i] != CV_LOW_COV && cv_strand_bias(cov[i], opt->strand_bias_pval)) cate[i] = CV_STRAND_BIAS;
-        if (cate[i] == CV_LOW_COV) continue;
-        if (opt->is_ont && cate[i] == CV_STRAND_BIAS) continue;
-        const CvSite &v = sites[i];
-        const long long a = std::max<long long>(0, v.pos - 1), b = v.var_type == 1 ? v.pos : v.pos + v.ref_len - 1; // cr_add: start clamped at 0, st > en dropped
-        if (a <= b) vp.push_back({a, b});
-    }
-    CvOvl var_pos; var_pos.build(vp);
-    std::vector<std::pair<long long, long long>> low;
-    for (int k = 0; k < n_low; ++k) { const long long a = std::max<long long>(0, low_comp[2 * k]), b = low_comp[2 * k + 1]; if (a <= b) low.push_back({a, b}); }
-    std::vector<std::pair<long long, long long>> pre;
-    for (int i = 0; i < n_pre; ++i) { const long long a = std::max<long long>(0, pre_regs[i].start), b = pre_regs[i].end; if (a <= b) pre.push_back({a, b}); }
-    struct Act { int check; long long vs, ve; };
-    std::vector<Act> acts; std::vector<long long> q;
-    for (int i = 0; i < ns; ++i) {
-        const CvSite &v = sites[i]; const int vc = cate[i];
-        if (vc == CV_NON_VAR || vc == CV_STRAND_BIAS) continue;
-        const long long qs = v.pos - 1, qe = v.var_type == 1 ? v.pos : v.pos + v.ref_len - 1;
-        if (!pre.empty()) {
-            bool hit = false;
-            for (auto &x : pre) if (x.first < qe && qs < x.second) { hit = true; break; }
-            if (hit) { cate[i] = CV_NON_VAR; continue; }
-        }
-        if (vc == CV_LOW_COV) continue;
-        const bool in_reg = v.pos >= reg_beg && v.pos <= reg_end;
-        auto add_var_cr = [&](int check) { // cr_add_var_cr (:750-775): grow to the overlapping low-complexity intervals (one query with the variant's own span)
-            long long vs = v.pos, ve = v.var_type == 1 ? v.pos : v.pos + v.ref_len - 1;
-            const long long ls = vs - 1, le = ve;
-            for (auto &x : low) if (x.first < le && ls < x.second) { vs = std::min(vs, x.first + 1); ve = std::max(ve, x.second); }
-            acts.push_back({check ? (int)(q.size() / 2) : -1, vs, ve});
-            if (check) { q.push_back(vs); q.push_back(ve); }
-        };
-        if (vc == CV_REP_HET) { if (in_reg) add_var_cr(0); continue; }
-        if (var_pos.count(qs, qe) > 1 && in_reg) add_var_cr(1);
-        if (vc == CV_LOW_AF) cate[i] = CV_LOW_COV;
-    }
-    std::vector<int> qc(q.size() + 2, 0);
-    const int nq = (int)(q.size() / 2);
-    if (nq) { // var_noisy_reads_ratio on the digars in HBM
-        DevBuf d_err, d_nerr, d_q, d_qc;
-        if (d_err.ensure((n_rec + 1) * sizeof(IvRec)) || d_nerr.ensure((n + 1) * 4ull) || d_q.ensure(q.size() * 8 + 64) || d_qc.ensure(q.size() * 4 + 64)) return -11;
-        HIPCHK(hipMemsetAsync(d_nerr.p, 0xff, (n + 1) * 4ull, st));
-        HIPCHK(hipMemcpyAsync(d_q.p, q.data(), q.size() * 8, hipMemcpyHostToDevice, st));
-        lcd_launch_cv_err_ivs(R, O, m, dg, (IvRec *)d_err.p, (int *)d_nerr.p, st);
-        lcd_launch_cv_ratio(R, O, m, (const IvRec *)d_err.p, (const int *)d_nerr.p, (const long long *)d_q.p, nq, (int *)d_qc.p, st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(qc.data(), d_qc.p, q.size() * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    std::vector<NIv> nv;
-    for (const Act &a : acts) {
-        if (a.check >= 0) {
-            const int tot = qc[2 * a.check], noisy = qc[2 * a.check + 1];
-            const float ratio = tot == 0 ? 0.0f : (float)noisy / (tot + 0.0);
-            if (!(ratio >= opt->min_af)) continue;
-        }
-        niv_add(nv, a.vs - 1, a.ve, 1);
-    }
-    std::vector<NIv> regs;
-    for (int i = 0; i < n_pre; ++i) niv_add(regs, pre_regs[i].start, pre_regs[i].end, pre_regs[i].label);
-    if (!nv.empty()) { // cr_merge2(chunk_noisy_regs, noisy_var_cr, -1, ..): both lists in their index order, cr_index, cr_merge
-        niv_index(nv);
-        for (const NIv &x : nv) regs.push_back(x);
-        niv_index(regs);
-        niv_merge(regs);
-    }
-    std::vector<lcd_noisy_iv_t> rin(regs.size() + 1);
-    for (size_t i = 0; i < regs.size(); ++i) { rin[i].start = (int64_t)regs[i].x; rin[i].end = regs[i].en; rin[i].label = regs[i].label; rin[i].pad = 0; }
-    std::vector<int64_t> vpos(ns + 1); std::vector<int> vrl(ns + 1);
-    for (int i = 0; i < ns; ++i) { vpos[i] = sites[i].pos; vrl[i] = sites[i].ref_len; }
-    lcd_noisy_iv_t *fin = nullptr;
-    const int n_fin = lcd_post_process_noisy_regs(rin.data(), (int)regs.size(), ns, vpos.data(), vrl.data(), cate.data(), opt->noisy_reg_flank_len, &fin);
-    // compaction (:1007-1023): candidates not contained in a final noisy region (cr_is_contained: the last region starting at or before the query start)
-    std::vector<int> keep;
-    for (int i = 0; i < ns; ++i) {
-        if (cate[i] & CV_NOT_CAND) continue;
-        if (n_fin > 0) {
-            const long long qs = sites[i].pos - 1, qe = sites[i].pos + sites[i].ref_len;
-            int lo = 0, hi = n_fin;
-            while (hi > lo) { const int mid = lo + ((hi - lo) >> 1); if (fin[mid].start <= qs) lo = mid + 1; else hi = mid; }
-            if (lo > 0 && fin[lo - 1].start < qe && fin[lo - 1].end >= qe) { cate[i] = CV_NON_VAR; continue; }
-        }
-        keep.push_back(i);
-    }
-    const int V = (int)keep.size();
-    out->n_regs = n_fin > 0 ? n_fin : 0;
-    out->regs = fin ? fin : (lcd_noisy_iv_t *)calloc(1, sizeof(lcd_noisy_iv_t));
-    std::vector<CvSite> vars(V + 1); std::vector<int> vcate(V + 1); std::vector<unsigned long long> aoff(V + 1, 0);
-    out->n_vars = V;
-    out->pos = (int64_t *)malloc((V + 1) * 8ull); out->var_type = (int *)malloc((V + 1) * 4ull); out->ref_len = (int *)malloc((V + 1) * 4ull);
-    out->alt_len = (int *)malloc((V + 1) * 4ull); out->cate = (int *)malloc((V + 1) * 4ull); out->total_cov = (int *)malloc((V + 1) * 4ull);
-    out->low_qual_cov = (int *)malloc((V + 1) * 4ull); out->alle_covs = (int *)malloc((V + 1) * 8ull); out->strand_alle_covs = (int *)malloc((V + 1) * 16ull);
-    out->alt_off = (uint64_t *)malloc((V + 1) * 8ull); out->is_homopolymer_indel = (int *)calloc(V + 1, 4);
-    unsigned long long na = 0;
-    for (int k = 0; k < V; ++k) {
-        const int i = keep[k]; const CvSite &v = sites[i]; const CvCov &cv = cov[i];
-        vars[k] = v; vcate[k] = cate[i];
-        out->pos[k] = v.pos; out->var_type[k] = v.var_type; out->ref_len[k] = v.ref_len; out->alt_len[k] = v.alt_len; out->cate[k] = cate[i];
-        out->total_cov[k] = cv.total; out->low_qual_cov[k] = cv.low; out->alle_covs[2 * k] = cv.alle[0]; out->alle_covs[2 * k + 1] = cv.alle[1];
-        for (int j = 0; j < 4; ++j) out->strand_alle_covs[4 * k + j] = cv.strand[j];
-        aoff[k] = na; out->alt_off[k] = na;
-        if (v.var_type == 8 || v.var_type == 1) na += (unsigned long long)v.alt_len;
-    }
-    aoff[V] = na; out->alt_off[V] = na;
-    out->alt_pool = (uint8_t *)malloc(na + 1);
-    // 3.1 collect_read_var_profile: spans, CSR offsets, alleles; the alt bases of the variants
-    DevBuf d_vars, d_vcate, d_aoff, d_pool, d_se, d_poff, d_al, d_qi;
-    if (d_vars.ensure((V + 1) * sizeof(CvSite)) || d_vcate.ensure((V + 1) * 4ull) || d_aoff.ensure((V + 1) * 8ull) || d_pool.ensure(na + 64) ||
-        d_se.ensure(2ull * (n + 1) * 4) || d_poff.ensure((n + 1) * 8ull)) return -11;
-    int *d_start = (int *)d_se.p, *d_end = d_start + (n + 1);
-    if (V) {
-        HIPCHK(hipMemcpyAsync(d_vars.p, vars.data(), V * sizeof(CvSite), hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_vcate.p, vcate.data(), V * 4ull, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_aoff.p, aoff.data(), (V + 1) * 8ull, hipMemcpyHostToDevice, st));
-    }
-    const CvSite *VV = (const CvSite *)d_vars.p;
-    lcd_launch_cv_alt(VV, R, (const unsigned long long *)d_aoff.p, V, (unsigned char *)d_pool.p, st);
-    lcd_launch_cv_profile(0, R, O, m, dg, VV, (const int *)d_vcate.p, V, (const IvRec *)d_ivs.p, d_start, d_end, nullptr, nullptr, nullptr, o, st);
-    HIPCHK(hipGetLastError());
-    std::vector<int> se(2ull * (n + 1));
-    if (na) HIPCHK(hipMemcpyAsync(out->alt_pool, d_pool.p, na, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(se.data(), d_se.p, 2ull * (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    out->n_reads = n;
-    out->start_var_idx = (int *)malloc((n + 1) * 4ull); out->end_var_idx = (int *)malloc((n + 1) * 4ull); out->allele_off = (uint64_t *)malloc((n + 1) * 8ull);
-    std::vector<char> walked(n + 1, 0);
-    for (int r : order) walked[r] = 1;
-    uint64_t tot = 0;
-    for (int r = 0; r < n; ++r) {
-        const int s0 = walked[r] ? se[r] : -1, e0 = walked[r] ? se[(n + 1) + r] : -2;
-        out->start_var_idx[r] = s0; out->end_var_idx[r] = e0; out->allele_off[r] = tot;
-        if (s0 >= 0) tot += (uint64_t)(e0 - s0 + 1);
-    }
-    out->allele_off[n] = tot;
-    out->alleles = (int *)malloc((tot + 1) * 4); out->alt_qi = (int *)malloc((tot + 1) * 4);
-    if (tot) {
-        if (d_al.ensure(tot * 4 + 64) || d_qi.ensure(tot * 4 + 64)) return -11;
-        HIPCHK(hipMemcpyAsync(d_poff.p, out->allele_off, (n + 1) * 8ull, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d_al.p, 0xff, tot * 4, st)); HIPCHK(hipMemsetAsync(d_qi.p, 0xff, tot * 4, st));
-        lcd_launch_cv_profile(1, R, O, m, dg, VV, (const int *)d_vcate.p, V, (const IvRec *)d_ivs.p, d_start, d_end, (const unsigned long long *)d_poff.p, (int *)d_al.p,
-                              (int *)d_qi.p, o, st);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(out->alleles, d_al.p, tot * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(out->alt_qi, d_qi.p, tot * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-    }
-    // read_var_cr: cr_add(start, end + 1, read) in ordered_read_ids order, cr_index
-    std::vector<NIv> rv;
-    for (int r : order) if (out->start_var_idx[r] >= 0 && out->end_var_idx[r] >= 0) niv_add(rv, out->start_var_idx[r], out->end_var_idx[r] + 1, r);
-    niv_index(rv);
-    out->n_cr = (int)rv.size();
-    out->cr_read = (int *)malloc((rv.size() + 1) * 4);
-    for (size_t i = 0; i < rv.size(); ++i) out->cr_read[i] = rv[i].label;
-    return 0;
-}
-int lcd_chunk_clean_vars(const lcd_chunk_t *c, const lcd_clean_opt_t *opt, const int *ordered_read_ids, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
-                         int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre_regs, const int64_t *low_comp, int n_low,
-                         lcd_clean_vars_t *out) {
-    if (ensure_init()) { if (out) memset(out, 0, sizeof(*out)); return -1; }
-    const int rc = clean_vars_one(c, opt, ordered_read_ids, is_rev, ref_seq, ref_beg, ref_end, reg_beg, reg_end, pre_regs, n_pre_regs, low_comp, n_low, out);
-    if (rc) lcd_clean_vars_free(out);
-    return rc;
-}
-int lcd_chunk_clean_vars_batch(int n, const lcd_chunk_t *const *chunks, const lcd_clean_opt_t *opt, const int *const *ordered_read_ids, const uint8_t *const *is_rev,
-                               const uint8_t *const *ref_seq, const int64_t *ref_beg, const int64_t *ref_end, const int64_t *reg_beg, const int64_t *reg_end,
-                               const lcd_noisy_iv_t *const *pre_regs, const int *n_pre_regs, const int64_t *const *low_comp, const int *n_low, lcd_clean_vars_t *outs) {
-    if (n <= 0) return 0;
-    if (ensure_init()) return -1;
-    std::vector<int> rc(n, 0);
-    std::vector<std::string> err(n);
-    std::atomic<int> next(0);
-    auto work = [&]() {
-        for (int i; (i = next.fetch_add(1)) < n;) {
-            rc[i] = lcd_chunk_clean_vars(chunks[i], opt, ordered_read_ids[i], is_rev ? is_rev[i] : nullptr, ref_seq[i], ref_beg[i], ref_end[i], reg_beg[i], reg_end[i],
-                                         pre_regs ? pre_regs[i] : nullptr, n_pre_regs ? n_pre_regs[i] : 0, low_comp ? low_comp[i] : nullptr, n_low ? n_low[i] : 0, outs + i);
-            if (rc[i]) err[i] = lcd_last_error();
-        }
-    };
-    const int nt = std::max(1, std::min(n, host_team()));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(work);
-    work();
-    for (auto &t : th) t.join();
-    for (int i = 0; i < n; ++i) if (rc[i]) { for (int j = 0; j < n; ++j) lcd_clean_vars_free(outs + j); return set_err(rc[i], "chunk " + std::to_string(i) + ": " + err[i]); }
-    return 0;
-}
-void lcd_clean_vars_free(lcd_clean_vars_t *v) {
-    if (!v) return;
-    free(v->pos); free(v->var_type); free(v->ref_len); free(v->alt_len); free(v->cate); free(v->total_cov); free(v->low_qual_cov); free(v->alle_covs);
-    free(v->strand_alle_covs); free(v->alt_off); free(v->alt_pool); free(v->is_homopolymer_indel); free(v->regs); free(v->start_var_idx); free(v->end_var_idx);
-    free(v->allele_off); free(v->alleles); free(v->alt_qi); free(v->cr_read);
-    memset(v, 0, sizeof(*v));
-}
-int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int *ordered_read_ids, const uint8_t *is_skipped, int *alle_off, int *allele_off,
-                               lcd_hap_problem_t *p) {
-    for (int i = 0; i <= v->n_vars; ++i) alle_off[i] = 2 * i;
-    for (int r = 0; r <= v->n_reads; ++r) allele_off[r] = (int)v->allele_off[r];
-    p->n_reads = v->n_reads; p->n_vars = v->n_vars; p->is_ont = is_ont;
-    p->var_pos = v->pos; p->var_type = v->var_type; p->var_cate = v->cate; p->is_homopolymer_indel = v->is_homopolymer_indel; p->total_cov = v->total_cov;
-    p->alle_off = alle_off; p->alle_covs = v->alle_covs; p->start_var_idx = v->start_var_idx; p->end_var_idx = v->end_var_idx; p->allele_off = allele_off;
-    p->alleles = v->alleles; p->ordered_read_ids = ordered_read_ids; p->is_skipped = is_skipped; p->n_cr = v->n_cr; p->cr_read = v->cr_read;
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// merge_var_profile (src/collect_var.c:1298-1387) for every region of a pass: table walk on the host, profile on the device (merge_vars_kernel.hip)
-} // extern "C"
-namespace {
-struct MvVar { int64_t pos; int type, ref_len, alt_len; const uint8_t *alt; int origin /* -1: the chunk's table, else the region */, idx; };
-// exact_comp_var_site (:1878): position key, type, ref_len, alt_len, alt bases of X / INS
-int mv_cmp(const MvVar &a, const MvVar &b) {
-    const int64_t ka = a.type == 8 ? a.pos : a.pos - 1, kb = b.type == 8 ? b.pos : b.pos - 1;
-    if (ka != kb) return ka < kb ? -1 : 1;
-    if (a.type != b.type) return a.type < b.type ? -1 : 1;
-    if (a.ref_len != b.ref_len) return a.ref_len < b.ref_len ? -1 : 1;
-    if (a.alt_len != b.alt_len) return a.alt_len < b.alt_len ? -1 : 1;
-    if ((a.type == 8 || a.type == 1) && a.alt_len > 0) return memcmp(a.alt, b.alt, (size_t)a.alt_len);
-    return 0;
-}
-struct MvChunk {                       // one chunk of a call between the host walk and the device profile
-    std::vector<int> a2m; std::vector<std::vector<int>> b2m; std::vector<char> active;
-    uint64_t o_a2m = 0, o_al = 0, o_qi = 0; std::vector<uint64_t> o_b2m, o_prof;
-    int read0 = 0;
-};
-// validation + the fold of two-pointer walks; fills every per-variant array of *out and the maps.  No device call.
-int mv_walk(const char *who, const lcd_clean_vars_t *cur, int n_regions, const lcd_region_vars_t *regions, const int *ordered, const uint8_t *is_skipped,
-            lcd_clean_vars_t *out, MvChunk &mc) {
-    const std::string W(who);
-    if (!cur || !out) return set_err(-4, W + ": NULL argument");
-    if (n_regions < 0) return set_err(-4, W + ": n_regions < 0");
-    if (n_regions > 0 && !regions) return set_err(-4, W + ": no regions");
-    const int V = cur->n_vars, R = cur->n_reads;
-    if (V < 0 || R < 0) return set_err(-4, W + ": negative n_vars / n_reads");
-    if (R > 0 && (!ordered || !is_skipped || !cur->start_var_idx || !cur->end_var_idx || !cur->allele_off)) return set_err(-4, W + ": no ordered_read_ids / is_skipped / profile");
-    if (V > 0 && (!cur->pos || !cur->var_type || !cur->ref_len || !cur->alt_len || !cur->cate || !cur->total_cov || !cur->low_qual_cov || !cur->alle_covs ||
-                  !cur->strand_alle_covs || !cur->alt_off || !cur->is_homopolymer_indel)) return set_err(-4, W + ": incomplete variant table");
-    for (int i = 0; i < V; ++i) {
-        const uint64_t nb = cur->alt_off[i + 1] - cur->alt_off[i];
-        if (cur->alt_off[i + 1] < cur->alt_off[i] || cur->alt_len[i] < 0 || ((cur->var_type[i] == 8 || cur->var_type[i] == 1) && nb != (uint64_t)cur->alt_len[i]))
-            return set_err(-4, W + ": alt_off does not match alt_len at variant " + std::to_string(i));
-    }
-    mc.active.assign(R + 1, 0);
-    for (int i = 0; i < R; ++i) {
-        const int r = ordered[i];
-        if (r < 0 || r >= R) return set_err(-4, W + ": ordered_read_ids out of range");
-        if (!is_skipped[r]) mc.active[r] = 1;
-    }
-    for (int r = 0; r < R; ++r) {
-        const int s = cur->start_var_idx[r], e = cur->end_var_idx[r];
-        const uint64_t nc = cur->allele_off[r + 1] - cur->allele_off[r];
-        if (cur->allele_off[r + 1] < cur->allele_off[r]) return set_err(-4, W + ": allele_off decreases at read " + std::to_string(r));
-        if (s < 0) continue;
-        if (e < s || e >= V || nc != (uint64_t)(e - s + 1)) return set_err(-4, W + ": profile span of read " + std::to_string(r) + " outside [0, n_vars) or not matching allele_off");
-        if (!cur->alleles || !cur->alt_qi) return set_err(-4, W + ": no profile cells");
-    }
-    std::vector<int> seen(R + 1, -1);
-    for (int k = 0; k < n_regions; ++k) {
-        const lcd_region_vars_t &g = regions[k];
-        if (g.n_vars <= 0) continue;
-        if (!g.vars || g.n_rows < 0 || (g.n_rows > 0 && (!g.row_read_ids || !g.prof_start || !g.prof_end || !g.prof_alleles))) return set_err(-4, W + ": region " + std::to_string(k) + " incomplete");
-        for (int j = 0; j < g.n_vars; ++j)
-            if (g.vars[j].alt_len < 0 || ((g.vars[j].var_type == 8 || g.vars[j].var_type == 1) && g.vars[j].alt_len > 0 && !g.vars[j].alt_seq))
-                return set_err(-4, W + ": region " + std::to_string(k) + " variant " + std::to_string(j) + " has no alt_seq");
-        for (int q = 0; q < g.n_rows; ++q) {
-            const int r = g.row_read_ids[q];
-            if (r < 0 || r >= R) return set_err(-4, W + ": region " + std::to_string(k) + " row " + std::to_string(q) + ": read id outside [0, n_reads)");
-            if (seen[r] == k) return set_err(-4, W + ": region " + std::to_string(k) + ": read " + std::to_string(r) + " twice");
-            seen[r] = k;
-            if (g.prof_start[q] >= 0 && g.prof_end[q] >= g.prof_start[q] && g.prof_end[q] >= g.n_vars)
-                return set_err(-4, W + ": region " + std::to_string(k) + " row " + std::to_string(q) + ": span outside [0, n_vars)");
-        }
-    }
-    // the fold
-    std::vector<MvVar> tab(V), nxt;
-    for (int i = 0; i < V; ++i) tab[i] = {cur->pos[i], cur->var_type[i], cur->ref_len[i], cur->alt_len[i], cur->alt_pool ? cur->alt_pool + cur->alt_off[i] : nullptr, -1, i};
-    for (int k = 0; k < n_regions; ++k) {
-        const lcd_region_vars_t &g = regions[k];
-        if (g.n_vars <= 0) continue;
-        nxt.clear(); nxt.reserve(tab.size() + g.n_vars);
-        size_t i = 0; int j = 0;
-        auto reg_var = [&](int q) { const lcd_noisy_var_t &v = g.vars[q]; return MvVar{v.pos, v.var_type, v.ref_len, v.alt_len, v.alt_seq, k, q}; };
-        while (i < tab.size() && j < g.n_vars) {
-            const MvVar b = reg_var(j);
-            const int c = mv_cmp(tab[i], b);
-            if (c < 0) nxt.push_back(tab[i++]);
-            else if (c > 0) { nxt.push_back(b); ++j; }
-            else { nxt.push_back(tab[i++]); ++j; }   // equal: the table's entry stays, the region's is dropped
-        }
-        for (; i < tab.size(); ++i) nxt.push_back(tab[i]);
-        for (; j < g.n_vars; ++j) nxt.push_back(reg_var(j));
-        tab.swap(nxt);
-    }
-    const int M = (int)tab.size();
-    mc.a2m.assign(V + 1, -1); mc.b2m.resize(n_regions);
-    for (int k = 0; k < n_regions; ++k) mc.b2m[k].assign(regions[k].n_vars > 0 ? regions[k].n_vars : 0, -1);
-    out->n_vars = M;
-    out->pos = (int64_t *)malloc((M + 1) * 8ull); out->var_type = (int *)malloc((M + 1) * 4ull); out->ref_len = (int *)malloc((M + 1) * 4ull);
-    out->alt_len = (int *)malloc((M + 1) * 4ull); out->cate = (int *)malloc((M + 1) * 4ull); out->total_cov = (int *)malloc((M + 1) * 4ull);
-    out->low_qual_cov = (int *)calloc(M + 1, 4); out->alle_covs = (int *)malloc((M + 1) * 8ull); out->strand_alle_covs = (int *)calloc(M + 1, 16);
-    out->alt_off = (uint64_t *)malloc((M + 1) * 8ull); out->is_homopolymer_indel = (int *)calloc(M + 1, 4);
-    uint64_t na = 0;
-    for (int m = 0; m < M; ++m) { const MvVar &t = tab[m]; if (t.origin < 0) na += cur->alt_off[t.idx + 1] - cur->alt_off[t.idx]; else if (t.type == 8 || t.type == 1) na += (uint64_t)t.alt_len; }
-    out->alt_pool = (uint8_t *)malloc(na + 1);
-    na = 0;
-    for (int m = 0; m < M; ++m) {
-        const MvVar &t = tab[m];
-        out->pos[m] = t.pos; out->var_type[m] = t.type; out->ref_len[m] = t.ref_len; out->alt_len[m] = t.alt_len; out->alt_off[m] = na;
-        if (t.origin < 0) {
-            const int i = t.idx; mc.a2m[i] = m;
-            out->cate[m] = cur->cate[i]; out->total_cov[m] = cur->total_cov[i]; out->low_qual_cov[m] = cur->low_qual_cov[i];
-            out->alle_covs[2 * m] = cur->alle_covs[2 * i]; out->alle_covs[2 * m + 1] = cur->alle_covs[2 * i + 1];
-            memcpy(out->strand_alle_covs + 4 * m, cur->strand_alle_covs + 4 * i, 16); out->is_homopolymer_indel[m] = cur->is_homopolymer_indel[i];
-            const uint64_t nb = cur->alt_off[i + 1] - cur->alt_off[i];
-            if (nb) memcpy(out->alt_pool + na, cur->alt_pool + cur->alt_off[i], nb);
-            na += nb;
-        } else {
-            const lcd_noisy_var_t &v = regions[t.origin].vars[t.idx]; mc.b2m[t.origin][t.idx] = m;
-            out->cate[m] = v.cate; out->total_cov[m] = v.total_cov; out->alle_covs[2 * m] = v.alle_covs[0]; out->alle_covs[2 * m + 1] = v.alle_covs[1];
-            out->is_homopolymer_indel[m] = v.is_homopolymer_indel;
-            if ((t.type == 8 || t.type == 1) && t.alt_len > 0) { memcpy(out->alt_pool + na, v.alt_seq, (size_t)t.alt_len); na += (uint64_t)t.alt_len; }
-        }
-    }
-    out->alt_off[M] = na;
-    out->n_regs = cur->n_regs > 0 ? cur->n_regs : 0;
-    out->regs = (lcd_noisy_iv_t *)calloc(out->n_regs + 1, sizeof(lcd_noisy_iv_t));
-    if (out->n_regs) memcpy(out->regs, cur->regs, out->n_regs * sizeof(lcd_noisy_iv_t));
-    out->n_reads = R; out->qual_upload_bytes = 0;
-    return 0;
-}
-} // namespace
-extern "C" {
-int lcd_merge_region_vars_batch(int n_chunks, const lcd_clean_vars_t *const *cur, const int *n_regions, const lcd_region_vars_t *const *regions,
-                                const int *const *ordered_read_ids, const uint8_t *const *is_skipped, lcd_clean_vars_t *outs, int *const *cur_to_merged,
-                                int **const *region_to_merged) {
-    if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, "lcd_merge_region_vars_batch: n_chunks < 0") : 0;
-    if (!cur || !n_regions || !regions || !ordered_read_ids || !is_skipped || !outs) return set_err(-4, "lcd_merge_region_vars_batch: NULL argument");
-    memset(outs, 0, sizeof(lcd_clean_vars_t) * (size_t)n_chunks);
-    auto fail = [&](int rc) { const std::string m = g_err; for (int c = 0; c < n_chunks; ++c) lcd_clean_vars_free(outs + c); g_err = m; return rc; };
-    std::vector<MvChunk> mcs(n_chunks);
-    // 1. host: validation and the table walks of every chunk (nothing is launched on malformed input)
-    for (int c = 0; c < n_chunks; ++c) {
-        const int rc = mv_walk("lcd_merge_region_vars", cur[c], n_regions[c], regions[c], ordered_read_ids[c], is_skipped[c], outs + c, mcs[c]);
-        if (rc) { if (n_chunks > 1) g_err = "chunk " + std::to_string(c) + ": " + g_err; return fail(rc); }
-    }
-    // 2. one staging block: maps, source cells, the source table, the reads' new start / end (min / max identities) and the flag
-    std::vector<uint8_t> hb(16, 0);   // (offset 0 stays unused: MvSrc.alt_qi == 0 means "no alt_qi")
-    auto put = [&](const void *p, size_t bytes) { size_t o = lcd_align_up(hb.size(), 16); hb.resize(o + bytes); if (p && bytes) memcpy(hb.data() + o, p, bytes); return (uint64_t)o; };
-    std::vector<MvSrc> srcs;
-    int G = 0;
-    for (int c = 0; c < n_chunks; ++c) { mcs[c].read0 = G; G += cur[c]->n_reads; }
-    std::vector<int> lo(G + 1, 0x7fffffff), hi(G + 1, -1);   // per read: bounds of its merged span (exact for the current profile, the region's extent for a row)
-    unsigned long long n_cells = 0;
-    for (int c = 0; c < n_chunks; ++c) {
-        MvChunk &mc = mcs[c]; const lcd_clean_vars_t &cv = *cur[c];
-        const int R = cv.n_reads, V = cv.n_vars; const uint64_t NA = R ? cv.allele_off[R] : 0;
-        mc.o_a2m = put(mc.a2m.data(), (size_t)V * 4); mc.o_al = put(cv.alleles, NA * 4); mc.o_qi = put(cv.alt_qi, NA * 4);
-        for (int r = 0; r < R; ++r) {
-            const int s = cv.start_var_idx[r], e = cv.end_var_idx[r];
-            if (!mc.active[r] || s < 0) continue;
-            srcs.push_back({mc.o_a2m, mc.o_al + cv.allele_off[r] * 4, mc.o_qi + cv.allele_off[r] * 4, c, mc.read0 + r, s, e - s + 1, n_cells});
-            n_cells += (unsigned long long)(e - s + 1);
-            lo[mc.read0 + r] = mc.a2m[s]; hi[mc.read0 + r] = mc.a2m[e];
-        }
-        mc.o_b2m.assign(n_regions[c], 0); mc.o_prof.assign(n_regions[c], 0);
-        for (int k = 0; k < n_regions[c]; ++k) {
-            const lcd_region_vars_t &g = regions[c][k];
-            if (g.n_vars <= 0) continue;
-            int mn = 0x7fffffff, mx = -1;
-            for (int m : mc.b2m[k]) if (m >= 0) { mn = std::min(mn, m); mx = std::max(mx, m); }
-            if (mx < 0 || g.n_rows <= 0) continue;   // every variant dropped: no cell of this region moves
-            mc.o_b2m[k] = put(mc.b2m[k].data(), (size_t)g.n_vars * 4); mc.o_prof[k] = put(g.prof_alleles, (size_t)g.n_rows * g.n_vars * 4);
-            for (int q = 0; q < g.n_rows; ++q) {
-                const int r = g.row_read_ids[q], s = g.prof_start[q], e = g.prof_end[q];
-                if (!mc.active[r] || s < 0 || e < s) continue;
-                srcs.push_back({mc.o_b2m[k], mc.o_prof[k] + ((uint64_t)q * g.n_vars + s) * 4, 0, c, mc.read0 + r, s, e - s + 1, n_cells});
-                n_cells += (unsigned long long)(e - s + 1);
-                lo[mc.read0 + r] = std::min(lo[mc.read0 + r], mn); hi[mc.read0 + r] = std::max(hi[mc.read0 + r], mx);
-            }
-        }
-    }
-    unsigned long long cap = 0;
-    for (int g = 0; g < G; ++g) if (hi[g] >= lo[g]) cap += (unsigned long long)(hi[g] - lo[g] + 1);
-    const int S = (int)srcs.size(), NB = (G + 255) / 256;
-    std::vector<int> se;                              // downloaded: start[G], end[G]
-    std::vector<uint8_t> dl;
-    const unsigned long long *off = nullptr; const int *d_al = nullptr, *d_qi = nullptr;
-    std::vector<unsigned long long> zero_off(G + 1, 0);
-    if (S > 0) {
-        if (ensure_init()) return fail(-1);
-        const uint64_t o_src = put(nullptr, (size_t)S * sizeof(MvSrc));
-        const uint64_t o_start = put(nullptr, (size_t)G * 4), o_end = put(nullptr, (size_t)G * 4), o_flag = put(nullptr, 16);
-        for (int g = 0; g < G; ++g) { ((int *)(hb.data() + o_start))[g] = 0x7fffffff; ((int *)(hb.data() + o_end))[g] = -1; }
-        const uint64_t up_bytes = lcd_align_up(hb.size(), 16);
-        const uint64_t o_off = up_bytes, o_bsum = o_off + lcd_align_up((uint64_t)(G + 1) * 8, 16), o_cells = o_bsum + lcd_align_up((uint64_t)NB * 8 + 16, 16);
-        const uint64_t total = o_cells + 2 * cap * 4 + 64;
-        StreamGuard st; if (st.create()) return fail(-10);
-        DevBuf d; if (d.ensure(total, 63)) return fail(-11);          // the call's one allocation
-        const uint64_t B = d.addr();
-        for (MvSrc &s : srcs) { s.map += B; s.alleles += B; if (s.alt_qi) s.alt_qi += B; }
-        memcpy(hb.data() + o_src, srcs.data(), (size_t)S * sizeof(MvSrc));
-#define MVCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err(-10, std::string(#x) + ": " + hipGetErrorString(e_)); return fail(-10); } } while (0)
-        MVCHK(hipMemcpyAsync(d.p, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
-        const MvSrc *SS = (const MvSrc *)(uintptr_t)(B + o_src);
-        int *d_start = (int *)(uintptr_t)(B + o_start), *d_end = (int *)(uintptr_t)(B + o_end), *d_flag = (int *)(uintptr_t)(B + o_flag);
-        unsigned long long *d_off = (unsigned long long *)(uintptr_t)(B + o_off), *d_bsum = (unsigned long long *)(uintptr_t)(B + o_bsum);
-        int *cells = (int *)(uintptr_t)(B + o_cells);
-        lcd_launch_mv_span(SS, S, d_start, d_end, st);
-        lcd_launch_mv_scan(d_start, d_end, G, d_off, d_bsum, st);
-        lcd_launch_mv_fill(cells, 2 * cap, st);
-        lcd_launch_mv_scatter(SS, S, n_cells, d_start, d_off, cells, cells + cap, cap, d_flag, st);
-        MVCHK(hipGetLastError());
-        dl.resize(o_cells + 2 * cap * 4 - o_start);
-        MVCHK(hipMemcpyAsync(dl.data(), (const uint8_t *)d.p + o_start, dl.size(), hipMemcpyDeviceToHost, st));
-        MVCHK(hipStreamSynchronize(st));
-#undef MVCHK
-        auto at = [&](uint64_t o) { return dl.data() + (o - o_start); };   // the downloaded copy of device offset o (>= o_start)
-        se.assign((const int *)at(o_start), (const int *)at(o_start) + G); se.insert(se.end(), (const int *)at(o_end), (const int *)at(o_end) + G);
-        off = (const unsigned long long *)at(o_off); d_al = (const int *)at(o_cells); d_qi = d_al + cap;
-        if (*(const int *)at(o_flag) || off[G] > cap) { set_err(-24, "lcd_merge_region_vars: cell capacity exceeded (" + std::to_string(off[G]) + " cells, " + std::to_string(cap) + " allocated)"); return fail(-24); }
-    } else {
-        se.assign(G, -1); se.insert(se.end(), G, -2); off = zero_off.data();
-    }
-    // 3. per chunk: spans, CSR, cells, the interval index; the maps
-    for (int c = 0; c < n_chunks; ++c) {
-        const MvChunk &mc = mcs[c]; lcd_clean_vars_t *out = outs + c; const int R = out->n_reads, g0 = mc.read0;
-        out->start_var_idx = (int *)malloc((R + 1) * 4ull); out->end_var_idx = (int *)malloc((R + 1) * 4ull); out->allele_off = (uint64_t *)malloc((R + 1) * 8ull);
-        for (int r = 0; r < R; ++r) { out->start_var_idx[r] = se[g0 + r]; out->end_var_idx[r] = se[G + g0 + r]; out->allele_off[r] = off[g0 + r] - off[g0]; }
-        const uint64_t tot = off[g0 + R] - off[g0];
-        out->allele_off[R] = tot;
-        out->alleles = (int *)malloc((tot + 1) * 4); out->alt_qi = (int *)malloc((tot + 1) * 4);
-        if (tot) { memcpy(out->alleles, d_al + off[g0], tot * 4); memcpy(out->alt_qi, d_qi + off[g0], tot * 4); }
-        std::vector<NIv> rv;   // read_var_cr: cr_add(start, end + 1, read) in ordered_read_ids order, cr_index
-        for (int i = 0; i < R; ++i) { const int r = ordered_read_ids[c][i]; if (is_skipped[c][r]) continue; if (out->start_var_idx[r] >= 0 && out->end_var_idx[r] >= 0) niv_add(rv, out->start_var_idx[r], out->end_var_idx[r] + 1, r); }
-        niv_index(rv);
-        out->n_cr = (int)rv.size();
-        out->cr_read = (int *)malloc((rv.size() + 1) * 4);
-        for (size_t i = 0; i < rv.size(); ++i) out->cr_read[i] = rv[i].label;
-        if (cur_to_merged && cur_to_merged[c] && cur[c]->n_vars > 0) memcpy(cur_to_merged[c], mc.a2m.data(), (size_t)cur[c]->n_vars * 4);
-        if (region_to_merged && region_to_merged[c])
-            for (int k = 0; k < n_regions[c]; ++k) if (region_to_merged[c][k] && !mc.b2m[k].empty()) memcpy(region_to_merged[c][k], mc.b2m[k].data(), mc.b2m[k].size() * 4);
-    }
-    return 0;
-}
-int lcd_merge_region_vars(const lcd_clean_vars_t *cur, int n_regions, const lcd_region_vars_t *regions, const int *ordered_read_ids, const uint8_t *is_skipped,
-                          lcd_clean_vars_t *out, int *cur_to_merged, int **region_to_merged) {
-    if (!out) return set_err(-4, "lcd_merge_region_vars: NULL argument");
-    return lcd_merge_region_vars_batch(1, &cur, &n_regions, &regions, &ordered_read_ids, &is_skipped, out, cur_to_merged ? &cur_to_merged : nullptr,
-                                       region_to_merged ? &region_to_merged : nullptr);
-}
-// sort_noisy_regs (src/collect_var.c:2745-2769): exchange sort by label, then by end - start, with that function's swap sequence (not stable)
-int lcd_sort_noisy_regs(const lcd_noisy_iv_t *regs, int n, int *order_out) {
-    if (n < 0 || (n > 0 && (!regs || !order_out))) return set_err(-4, "lcd_sort_noisy_regs: bad arguments");
-    for (int i = 0; i < n; ++i) order_out[i] = i;
-    auto after = [&](int a, int b) { // region a belongs behind region b
-        if (regs[a].label != regs[b].label) return regs[a].label > regs[b].label;
-        return (int)(regs[a].end - regs[a].start) > (int)(regs[b].end - regs[b].start);
-    };
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (after(order_out[i], order_out[j])) std::swap(order_out[i], order_out[j]);
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------------
-// the noisy-region rounds of collect_var_main (src/collect_var.c:2946-2977) on device-resident chunks: pass plan (plan_kernel.hip), planned regions into a
-// batch, K5 state across a merge, and the driver that composes them with lcd_batch_run_many, lcd_merge_region_vars_batch and lcd_assign_hap_batch
-void lcd_pass_opt_default(lcd_pass_opt_t *o) { o->max_noisy_reg_len = 50000; o->max_noisy_reg_cov = 1000; o->noisy_reg_flank_len = 10; } // src/call_var_main.h:36-42
-void lcd_pass_plan_free(lcd_pass_plan_t *p) {
-    if (!p) return;
-    free(p->status); free(p->beg); free(p->end); free(p->read_off); free(p->read_ids); free(p->read_beg); free(p->read_end); free(p->cover);
-    memset(p, 0, sizeof(*p));
-}
-int lcd_chunk_plan_pass_batch(int n_chunks, const lcd_chunk_t *const *chunks, const lcd_pass_opt_t *opt, const int *n_regs, const lcd_noisy_iv_t *const *regs,
-                              const int *const *done, const int *const *ordered_read_ids, const uint8_t *const *is_skipped, const int64_t *ref_beg,
-                              const int64_t *ref_end, lcd_pass_plan_t *outs) {
-    const std::string W = "lcd_chunk_plan_pass";
-    if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, W + ": n_chunks < 0") : 0;
-    if (!chunks || !opt || !n_regs || !regs || !done || !ordered_read_ids || !is_skipped || !ref_beg || !ref_end || !outs) return set_err(-4, W + ": NULL argument");
-    memset(outs, 0, sizeof(lcd_pass_plan_t) * (size_t)n_chunks);
-    // 1. host: validation; nothing touches the device on malformed input
-    long long G = 0;
-    for (int c = 0; c < n_chunks; ++c) {
-        const std::string at = n_chunks > 1 ? "chunk " + std::to_string(c) + ": " : "";
-        if (n_regs[c] < 0) return set_err(-4, W + ": " + at + "n_regs < 0");
-        if (ref_end[c] < ref_beg[c]) return set_err(-4, W + ": " + at + "ref_end < ref_beg");
-        if (n_regs[c] > 0 && (!regs[c] || !done[c])) return set_err(-4, W + ": " + at + "no regs / done");
-    }
-    for (int c = 0; c < n_chunks; ++c) {
-        const std::string at = n_chunks > 1 ? "chunk " + std::to_string(c) + ": " : "";
-        if (!chunks[c]) return set_err(-4, W + ": " + at + "NULL chunk");
-        if (chunks[c]->device != chunks[0]->device) return set_err(-4, W + ": chunks on different devices");
-        const int R = chunks[c]->n_reads;
-        if (R > 0 && (!ordered_read_ids[c] || !is_skipped[c])) return set_err(-4, W + ": " + at + "no ordered_read_ids / is_skipped");
-        for (int i = 0; i < R; ++i) if (ordered_read_ids[c][i] < 0 || ordered_read_ids[c][i] >= R) return set_err(-4, W + ": " + at + "ordered_read_ids entry outside [0, n_reads)");
-        G += n_regs[c];
-    }
-    if (G > (1ll << 30)) return set_err(-4, W + ": too many regions");
-    // 2. the region tables; long and done regions are decided here
-    std::vector<PlanReg> pr((size_t)G); std::vector<int> reg0(n_chunks + 1, 0);
-    int n_pending = 0;
-    for (int c = 0, g = 0; c < n_chunks; ++c) {
-        reg0[c] = g;
-        for (int i = 0; i < n_regs[c]; ++i, ++g) {
-            PlanReg &q = pr[g]; q.chunk = c;
-            q.beg = std::max<int64_t>(regs[c][i].start, ref_beg[c]); q.end = std::min<int64_t>(regs[c][i].end, ref_end[c]);   // collect_reg_ref_bseq, src/seq.c:417-418
-            q.status = done[c][i] ? LCD_PLAN_DONE_BEFORE : q.end - q.beg + 1 > (long long)opt->max_noisy_reg_len ? LCD_PLAN_SKIP_LONG : LCD_PLAN_SUBMIT;
-            n_pending += q.status == LCD_PLAN_SUBMIT;
-        }
-        reg0[c + 1] = g;
-    }
-    std::vector<int> st_h((size_t)G); std::vector<unsigned long long> off_h((size_t)G + 1, 0);
-    for (long long g = 0; g < G; ++g) st_h[g] = pr[g].status;
-    std::vector<uint8_t> pairs;                       // downloaded: SliceOut[P], read ids[P]
-    unsigned long long P = 0;
-    if (n_pending > 0) {
-        if (use_device(chunks[0]->device)) return -1;
-        // the chunks' read tables: once per chunk
-        for (int c = 0; c < n_chunks; ++c) {
-            lcd_chunk_s *ch = const_cast<lcd_chunk_s *>(chunks[c]);
-            std::lock_guard<std::mutex> lk(ch->plan_mu);
-            if (ch->plan_ready || ch->n_reads <= 0) continue;
-            std::vector<PlanRead> tab(ch->n_reads);
-            for (int r = 0; r < ch->n_reads; ++r) { PlanRead &x = tab[r]; x.beg = ch->beg[r]; x.end = ch->end[r]; x.digar_off = ch->slot[r]; x.n_digar = ch->n_digar[r]; x.qlen = ch->qlen[r]; x.status = ch->status[r]; x.pad = 0; }
-            if (ch->d_plan.ensure(tab.size() * sizeof(PlanRead), 63)) return -11;
-            if (hipMemcpy(ch->d_plan.p, tab.data(), tab.size() * sizeof(PlanRead), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); ch->d_plan.release(); return set_err(-10, W + ": read table upload failed"); }
-            ch->plan_ready = true;
-        }
-        // one staged block: chunk table, region table, every chunk's ordered_read_ids and is_skipped; behind it on the device: counts, statuses, offsets
-        std::vector<uint8_t> hb;
-        auto put = [&](const void *p, size_t bytes) { size_t o = lcd_align_up(hb.size(), 16); hb.resize(o + bytes); if (p && bytes) memcpy(hb.data() + o, p, bytes); return (uint64_t)o; };
-        const uint64_t o_ch = put(nullptr, (size_t)n_chunks * sizeof(PlanChunk)), o_pr = put(pr.data(), (size_t)G * sizeof(PlanReg));
-        std::vector<PlanChunk> pc(n_chunks);
-        for (int c = 0; c < n_chunks; ++c) {
-            const lcd_chunk_s *ch = chunks[c]; const int R = ch->n_reads;
-            pc[c].reads = ch->d_plan.addr(); pc[c].digars = ch->d_dig.addr(); pc[c].n_reads = R; pc[c].pad = 0;
-            pc[c].order = put(ordered_read_ids[c], (size_t)R * 4); pc[c].skipped = put(is_skipped[c], (size_t)R);
-        }
-        const uint64_t up_bytes = lcd_align_up(hb.size(), 16);
-        const uint64_t o_cnt = up_bytes, o_st = o_cnt + lcd_align_up((uint64_t)G * 4, 16), o_off = o_st + lcd_align_up((uint64_t)G * 4, 16);
-        const uint64_t total = o_off + ((uint64_t)G + 1) * 8 + 64;
-        StreamGuard st; if (st.create()) return -10;
-        DevBuf d; if (d.ensure(total, 63)) return -11;
-        const uint64_t B = d.addr();
-        for (int c = 0; c < n_chunks; ++c) { pc[c].order += B; pc[c].skipped += B; }
-        memcpy(hb.data() + o_ch, pc.data(), (size_t)n_chunks * sizeof(PlanChunk));
-        HIPCHK(hipMemcpyAsync(d.p, hb.data(), hb.size(), hipMemcpyHostToDevice, st));
-        const PlanChunk *d_ch = (const PlanChunk *)(uintptr_t)(B + o_ch); const PlanReg *d_pr = (const PlanReg *)(uintptr_t)(B + o_pr);
-        int *d_cnt = (int *)(uintptr_t)(B + o_cnt), *d_st = (int *)(uintptr_t)(B + o_st); unsigned long long *d_off = (unsigned long long *)(uintptr_t)(B + o_off);
-        lcd_launch_plan_count(d_ch, d_pr, (int)G, opt->max_noisy_reg_cov, d_cnt, d_st, st);
-        lcd_launch_plan_scan(d_cnt, (int)G, d_off, st);
-        HIPCHK(hipGetLastError());
-        std::vector<uint8_t> dl(o_off + ((uint64_t)G + 1) * 8 - o_st);
-        HIPCHK(hipMemcpyAsync(dl.data(), (const uint8_t *)d.p + o_st, dl.size(), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));                                             // (1) the counts size the pair area
-        memcpy(st_h.data(), dl.data(), (size_t)G * 4); memcpy(off_h.data(), dl.data() + (o_off - o_st), ((size_t)G + 1) * 8);
-        P = off_h[G];
-        if (P > 0x7fffffffull) return set_err(-24, W + ": more than 2^31 - 1 (region, read) pairs in one call");
-        if (P > 0) {
-            DevBuf dp; if (dp.ensure(P * (sizeof(SliceOut) + 8) + 64, 63)) return -11;     // the pair area: slices, read ids, region of the pair
-            SliceOut *d_so = (SliceOut *)dp.p; int *d_ids = (int *)((uint8_t *)dp.p + P * sizeof(SliceOut)), *d_preg = d_ids + P;
-            lcd_launch_plan_fill(d_ch, d_pr, (int)G, d_st, d_off, d_ids, d_preg, st);
-            lcd_launch_plan_slices(d_ch, d_pr, d_ids, d_preg, P, opt->noisy_reg_flank_len, d_so, st);
-            HIPCHK(hipGetLastError());
-            pairs.resize(P * (sizeof(SliceOut) + 4));
-            HIPCHK(hipMemcpyAsync(pairs.data(), dp.p, pairs.size(), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));                                         // (2)
-        }
-    }
-    // 3. per chunk: the malloc()'d plan
-    const SliceOut *so = (const SliceOut *)pairs.data(); const int *ids = (const int *)(pairs.data() + P * sizeof(SliceOut));
-    for (int c = 0; c < n_chunks; ++c) {
-        lcd_pass_plan_t &o = outs[c]; const int n = n_regs[c], g0 = reg0[c];
-        const unsigned long long p0 = off_h[g0], np = off_h[g0 + n] - p0;
-        o.n_regs = n;
-        o.status = (int *)malloc((n + 1) * 4ull); o.beg = (int64_t *)malloc((n + 1) * 8ull); o.end = (int64_t *)malloc((n + 1) * 8ull); o.read_off = (uint64_t *)malloc((n + 1) * 8ull);
-        o.read_ids = (int *)malloc((np + 1) * 4); o.read_beg = (int *)malloc((np + 1) * 4); o.read_end = (int *)malloc((np + 1) * 4); o.cover = (int *)malloc((np + 1) * 4);
-        for (int i = 0; i < n; ++i) { o.status[i] = st_h[g0 + i]; o.beg[i] = pr[g0 + i].beg; o.end[i] = pr[g0 + i].end; o.read_off[i] = off_h[g0 + i] - p0; }
-        o.read_off[n] = np;
-        for (unsigned long long k = 0; k < np; ++k) { o.read_ids[k] = ids[p0 + k]; o.read_beg[k] = so[p0 + k].read_beg; o.read_end[k] = so[p0 + k].read_end; o.cover[k] = so[p0 + k].cover; }
-    }
-    return 0;
-}
-int lcd_chunk_plan_pass(const lcd_chunk_t *c, const lcd_pass_opt_t *opt, int n_regs, const lcd_noisy_iv_t *regs, const int *done, const int *ordered_read_ids,
-                        const uint8_t *is_skipped, int64_t ref_beg, int64_t ref_end, lcd_pass_plan_t *out) {
-    if (!out) return set_err(-4, "lcd_chunk_plan_pass: NULL argument");
-    return lcd_chunk_plan_pass_batch(1, &c, opt, &n_regs, &regs, &done, &ordered_read_ids, &is_skipped, &ref_beg, &ref_end, out);
-}
 int lcd_batch_region_n_cons(lcd_batch_t *b, int region) {
     if (!b->downloaded) return set_err(-3, "lcd_batch_region_n_cons before lcd_batch_download");
     if (region < 0 || region >= (int)b->regs.size()) return set_err(-4, "bad region index");
@@ -4542,193 +2579,6 @@ int lcd_batch_add_planned(lcd_batch_t *b, const lcd_chunk_t *c, const lcd_pass_p
         ++added;
     }
     return added;
-}
-void lcd_hap_state_free(lcd_hap_state_t *s) {
-    if (!s) return;
-    free(s->haps); free(s->phase_sets); free(s->n_clean_agree_snps); free(s->n_clean_conflict_snps); free(s->var_phase_set); free(s->hap_to_cons_alle); free(s->hap_to_alle_profile);
-    memset(s, 0, sizeof(*s));
-}
-int lcd_hap_state_init(int R, int V, lcd_hap_state_t *o) {
-    if (!o || R < 0 || V < 0) return set_err(-4, "lcd_hap_state_init: bad arguments");
-    o->n_reads = R; o->n_vars = V;
-    o->haps = (int *)calloc(R + 1, 4); o->phase_sets = (int64_t *)malloc((R + 1) * 8ull); o->n_clean_agree_snps = (int *)calloc(R + 1, 4); o->n_clean_conflict_snps = (int *)calloc(R + 1, 4);
-    o->var_phase_set = (int64_t *)malloc((V + 1) * 8ull); o->hap_to_cons_alle = (int *)malloc((3ull * V + 1) * 4); o->hap_to_alle_profile = (int *)calloc(6ull * V + 1, 4);
-    for (int r = 0; r < R; ++r) o->phase_sets[r] = -1;
-    for (int i = 0; i < V; ++i) o->var_phase_set[i] = -1;
-    for (int i = 0; i < 3 * V; ++i) o->hap_to_cons_alle[i] = -1;
-    return 0;
-}
-int lcd_hap_state_carry(const lcd_hap_state_t *old, int M, const int *c2m, lcd_hap_state_t *out) {
-    if (!old || !out || old == out || M < 0 || old->n_vars < 0 || old->n_reads < 0 || (old->n_vars > 0 && !c2m)) return set_err(-4, "lcd_hap_state_carry: bad arguments");
-    const int V = old->n_vars, R = old->n_reads;
-    std::vector<char> taken(M + 1, 0);
-    for (int i = 0; i < V; ++i) {
-        if (c2m[i] < 0 || c2m[i] >= M) return set_err(-4, "lcd_hap_state_carry: cur_to_merged[" + std::to_string(i) + "] outside [0, merged n_vars)");
-        if (taken[c2m[i]]) return set_err(-4, "lcd_hap_state_carry: two variants map to merged variant " + std::to_string(c2m[i]));
-        taken[c2m[i]] = 1;
-    }
-    if (lcd_hap_state_init(R, M, out)) return -4;
-    if (R) { memcpy(out->haps, old->haps, R * 4ull); memcpy(out->phase_sets, old->phase_sets, R * 8ull); memcpy(out->n_clean_agree_snps, old->n_clean_agree_snps, R * 4ull); memcpy(out->n_clean_conflict_snps, old->n_clean_conflict_snps, R * 4ull); }
-    for (int i = 0; i < V; ++i) {
-        const int m = c2m[i];
-        out->var_phase_set[m] = old->var_phase_set[i];
-        for (int h = 0; h < 3; ++h) {
-            out->hap_to_cons_alle[3 * m + h] = old->hap_to_cons_alle[3 * i + h];
-            out->hap_to_alle_profile[(size_t)h * 2 * M + 2 * m] = old->hap_to_alle_profile[(size_t)h * 2 * V + 2 * i];
-            out->hap_to_alle_profile[(size_t)h * 2 * M + 2 * m + 1] = old->hap_to_alle_profile[(size_t)h * 2 * V + 2 * i + 1];
-        }
-    }
-    return 0;
-}
-} // extern "C"
-namespace {
-struct RoundsChunk {               // one chunk of lcd_chunks_noisy_rounds between passes
-    lcd_clean_vars_t own_vars; lcd_hap_state_t own_state; bool has_own = false;   // the driver's own current state (else the caller's)
-    std::vector<int> order, done, f2f; int n_passes = 0; bool in_loop = false;
-};
-struct RegionVarsOwned {           // lcd_batch_region_vars' outputs, freed with the object
-    lcd_noisy_var_t *vars = nullptr; int n = 0, rows = 0; int *ids = nullptr, *ps = nullptr, *pe = nullptr, *pa = nullptr;
-    void release() { for (int i = 0; i < n; ++i) free(vars[i].alt_seq); free(vars); free(ids); free(ps); free(pe); free(pa); vars = nullptr; ids = ps = pe = pa = nullptr; n = rows = 0; }
-};
-}
-extern "C" {
-int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt) {
-    const std::string W = "lcd_chunks_noisy_rounds";
-    if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, W + ": n_chunks < 0") : 0;
-    if (!chunks || !opt || !pass_opt) return set_err(-4, W + ": NULL argument");
-    if (opt->collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode (collect_ref_read_aln_str) is not supported: the regions of a pass are order-dependent there");
-    for (int c = 0; c < n_chunks; ++c) {
-        lcd_rounds_chunk_t &x = chunks[c];
-        x.done = nullptr; x.first_to_final = nullptr; x.n_passes = 0; x.n_first_vars = 0;
-        const std::string at = W + ": chunk " + std::to_string(c) + ": ";
-        if (!x.chunk || !x.vars || !x.state || !x.ref_seq) return set_err(-4, at + "NULL member");
-        if (x.ref_end < x.ref_beg) return set_err(-4, at + "ref_end < ref_beg");
-        if (x.vars->n_reads != x.chunk->n_reads || x.state->n_reads != x.vars->n_reads || x.state->n_vars != x.vars->n_vars) return set_err(-4, at + "chunk, vars and state disagree on n_reads / n_vars");
-        if (x.vars->n_regs < 0 || (x.vars->n_regs > 0 && !x.vars->regs)) return set_err(-4, at + "no regs");
-        if (x.vars->n_reads > 0 && (!x.ordered_read_ids || !x.is_skipped)) return set_err(-4, at + "no ordered_read_ids / is_skipped");
-        if (x.chunk->device != chunks[0].chunk->device) return set_err(-4, W + ": chunks on different devices");
-    }
-    lcd_opt_t bopt = *opt; bopt.collect_noisy_vars = 2;
-    std::vector<RoundsChunk> rc(n_chunks);
-    std::vector<lcd_batch_t *> batches;            // of the current pass
-    std::vector<lcd_pass_plan_t> plans;
-    auto drop_pass = [&]() { for (lcd_batch_t *b : batches) if (b) lcd_batch_destroy(b); batches.clear(); for (lcd_pass_plan_t &p : plans) lcd_pass_plan_free(&p); plans.clear(); };
-    auto fail = [&](int code) {
-        const std::string m = g_err; drop_pass();
-        for (RoundsChunk &r : rc) if (r.has_own) { lcd_clean_vars_free(&r.own_vars); lcd_hap_state_free(&r.own_state); r.has_own = false; }
-        g_err = m; return code;
-    };
-    auto cur_vars = [&](int c) -> lcd_clean_vars_t * { return rc[c].has_own ? &rc[c].own_vars : chunks[c].vars; };
-    auto cur_state = [&](int c) -> lcd_hap_state_t * { return rc[c].has_own ? &rc[c].own_state : chunks[c].state; };
-    for (int c = 0; c < n_chunks; ++c) {
-        RoundsChunk &r = rc[c]; const lcd_clean_vars_t *v = chunks[c].vars;
-        r.order.resize(v->n_regs); r.done.assign(v->n_regs, 0); r.f2f.resize(v->n_vars); std::iota(r.f2f.begin(), r.f2f.end(), 0);
-        if (v->n_regs > 0 && lcd_sort_noisy_regs(v->regs, v->n_regs, r.order.data())) return fail(-4);
-        r.in_loop = v->n_regs > 0;
-    }
-    for (;;) {
-        std::vector<int> A;
-        for (int c = 0; c < n_chunks; ++c) if (rc[c].in_loop) A.push_back(c);
-        if (A.empty()) break;
-        const int na = (int)A.size();
-        // 1. the plan of this pass over the chunks still in the loop
-        std::vector<const lcd_chunk_t *> p_ch(na); std::vector<int> p_n(na); std::vector<const lcd_noisy_iv_t *> p_regs(na); std::vector<const int *> p_done(na), p_ord(na);
-        std::vector<const uint8_t *> p_skip(na); std::vector<int64_t> p_rb(na), p_re(na);
-        for (int a = 0; a < na; ++a) {
-            const int c = A[a]; const lcd_clean_vars_t *v = cur_vars(c);
-            p_ch[a] = chunks[c].chunk; p_n[a] = v->n_regs; p_regs[a] = v->regs; p_done[a] = rc[c].done.data(); p_ord[a] = chunks[c].ordered_read_ids; p_skip[a] = chunks[c].is_skipped;
-            p_rb[a] = chunks[c].ref_beg; p_re[a] = chunks[c].ref_end;
-        }
-        plans.assign(na, lcd_pass_plan_t());
-        int rcode = lcd_chunk_plan_pass_batch(na, p_ch.data(), pass_opt, p_n.data(), p_regs.data(), p_done.data(), p_ord.data(), p_skip.data(), p_rb.data(), p_re.data(), plans.data());
-        if (rcode) return fail(rcode);
-        // 2. one batch per chunk, one joint run
-        batches.assign(na, nullptr);
-        std::vector<std::vector<int>> ridx(na);
-        std::vector<lcd_batch_t *> run;
-        for (int a = 0; a < na; ++a) {
-            const int c = A[a];
-            ridx[a].assign(plans[a].n_regs + 1, -1);
-            bool any = false; for (int i = 0; i < plans[a].n_regs; ++i) any |= plans[a].status[i] == LCD_PLAN_SUBMIT;
-            if (!any) continue;
-            batches[a] = lcd_batch_create_on(&bopt, chunks[c].chunk->device);
-            if (!batches[a]) return fail(-10);
-            rcode = lcd_batch_add_planned(batches[a], chunks[c].chunk, &plans[a], cur_state(c)->haps, cur_state(c)->phase_sets, chunks[c].ref_seq, chunks[c].ref_beg, ridx[a].data());
-            if (rcode < 0) return fail(rcode);
-            if ((rcode = lcd_batch_upload(batches[a]))) return fail(rcode);
-            run.push_back(batches[a]);
-        }
-        if (!run.empty()) {
-            if ((rcode = lcd_batch_run_many(run.data(), (int)run.size()))) return fail(rcode);
-            for (lcd_batch_t *b : run) if ((rcode = lcd_batch_download(b))) return fail(rcode);
-        }
-        // 3. the regions' variants in sorted-region order, done[] by the reference's rule
-        std::vector<std::vector<RegionVarsOwned>> got(na); std::vector<char> new_var(na, 0), new_done(na, 0);
-        auto free_got = [&]() { for (auto &g : got) for (RegionVarsOwned &x : g) x.release(); };
-        for (int a = 0; a < na; ++a) {
-            const int c = A[a]; RoundsChunk &r = rc[c];
-            for (int k = 0; k < plans[a].n_regs; ++k) {
-                const int i = r.order[k], st = plans[a].status[i];
-                if (st == LCD_PLAN_SKIP_LONG || st == LCD_PLAN_SKIP_DEEP) { r.done[i] = 1; new_done[a] = 1; continue; }   // collect_noisy_vars1 returns 0
-                if (st != LCD_PLAN_SUBMIT) continue;
-                if (batches[a]->regs[ridx[a][i]].n_cons <= 0) continue;                                                  // returns -1: tried again
-                RegionVarsOwned x;
-                const int n = lcd_batch_region_vars(batches[a], ridx[a][i], plans[a].beg[i], chunks[c].ref_seq, chunks[c].ref_beg, chunks[c].ref_end - chunks[c].ref_beg + 1, &x.vars,
-                                                    &x.rows, &x.ids, &x.ps, &x.pe, &x.pa);
-                x.n = n > 0 ? n : 0;
-                got[a].push_back(x);
-                if (n < 0) { const std::string m = g_err; free_got(); g_err = m; return fail(n); }
-                r.done[i] = 1; new_done[a] = 1;
-                if (n > 0) new_var[a] = 1;
-            }
-        }
-        // 4. merge + carry + K5 over all germline categories for the chunks that got a variant
-        std::vector<int> M; for (int a = 0; a < na; ++a) if (new_var[a]) M.push_back(a);
-        if (!M.empty()) {
-            const int nm = (int)M.size();
-            std::vector<std::vector<lcd_region_vars_t>> rv(nm); std::vector<const lcd_clean_vars_t *> m_cur(nm); std::vector<int> m_n(nm); std::vector<const lcd_region_vars_t *> m_rv(nm);
-            std::vector<const int *> m_ord(nm); std::vector<const uint8_t *> m_skip(nm); std::vector<std::vector<int>> c2m(nm); std::vector<int *> m_c2m(nm);
-            for (int q = 0; q < nm; ++q) {
-                const int a = M[q], c = A[a];
-                for (const RegionVarsOwned &x : got[a]) rv[q].push_back(lcd_region_vars_t{x.n, x.vars, x.rows, x.ids, x.ps, x.pe, x.pa});
-                m_cur[q] = cur_vars(c); m_n[q] = (int)rv[q].size(); m_rv[q] = rv[q].data(); m_ord[q] = chunks[c].ordered_read_ids; m_skip[q] = chunks[c].is_skipped;
-                c2m[q].assign(m_cur[q]->n_vars + 1, -1); m_c2m[q] = c2m[q].data();
-            }
-            std::vector<lcd_clean_vars_t> merged(nm); std::vector<lcd_hap_state_t> carried(nm, lcd_hap_state_t());
-            rcode = lcd_merge_region_vars_batch(nm, m_cur.data(), m_n.data(), m_rv.data(), m_ord.data(), m_skip.data(), merged.data(), m_c2m.data(), nullptr);
-            free_got();
-            auto drop_new = [&]() { const std::string m = g_err; for (int q = 0; q < nm; ++q) { lcd_clean_vars_free(&merged[q]); lcd_hap_state_free(&carried[q]); } g_err = m; };
-            if (rcode) return fail(rcode);   // (the merge freed its outputs)
-            std::vector<lcd_hap_problem_t> probs(nm); std::vector<std::vector<int>> alle_off(nm), allele_off(nm); std::vector<int> targets(nm, 0x004 | 0x008 | 0x080 | 0x100 | 0x200); // LONGCALLD_CAND_GERMLINE_VAR_CATE, src/collect_var.h:25
-            for (int q = 0; q < nm; ++q) {
-                const int c = A[M[q]];
-                if ((rcode = lcd_hap_state_carry(cur_state(c), merged[q].n_vars, c2m[q].data(), &carried[q]))) { drop_new(); return fail(rcode); }
-                alle_off[q].resize(merged[q].n_vars + 1); allele_off[q].resize(merged[q].n_reads + 1);
-                lcd_clean_vars_hap_problem(&merged[q], chunks[c].is_ont, chunks[c].ordered_read_ids, chunks[c].is_skipped, alle_off[q].data(), allele_off[q].data(), &probs[q]);
-                lcd_hap_problem_t &p = probs[q]; const lcd_hap_state_t &s = carried[q];
-                p.haps = s.haps; p.phase_sets = s.phase_sets; p.n_clean_agree_snps = s.n_clean_agree_snps; p.n_clean_conflict_snps = s.n_clean_conflict_snps;
-                p.var_phase_set = s.var_phase_set; p.hap_to_cons_alle = s.hap_to_cons_alle; p.hap_to_alle_profile = s.hap_to_alle_profile;
-            }
-            if ((rcode = lcd_assign_hap_batch(nm, probs.data(), targets.data()))) { drop_new(); return fail(rcode); }
-            for (int q = 0; q < nm; ++q) {
-                const int c = A[M[q]]; RoundsChunk &r = rc[c];
-                if (r.has_own) { lcd_clean_vars_free(&r.own_vars); lcd_hap_state_free(&r.own_state); }
-                r.own_vars = merged[q]; r.own_state = carried[q]; r.has_own = true;
-                for (int &f : r.f2f) f = c2m[q][f];
-            }
-        } else free_got();
-        for (int a = 0; a < na; ++a) { RoundsChunk &r = rc[A[a]]; ++r.n_passes; if (!new_done[a]) r.in_loop = false; }
-        drop_pass();
-    }
-    // the caller's structures take the final state
-    for (int c = 0; c < n_chunks; ++c) {
-        RoundsChunk &r = rc[c]; lcd_rounds_chunk_t &x = chunks[c];
-        x.n_first_vars = (int)r.f2f.size(); x.n_passes = r.n_passes;
-        x.done = (int *)malloc((r.done.size() + 1) * 4); if (!r.done.empty()) memcpy(x.done, r.done.data(), r.done.size() * 4);
-        x.first_to_final = (int *)malloc((r.f2f.size() + 1) * 4); if (!r.f2f.empty()) memcpy(x.first_to_final, r.f2f.data(), r.f2f.size() * 4);
-        if (r.has_own) { lcd_clean_vars_free(x.vars); *x.vars = r.own_vars; lcd_hap_state_free(x.state); *x.state = r.own_state; r.has_own = false; }
-    }
-    return 0;
 }
 
 } // extern "C"

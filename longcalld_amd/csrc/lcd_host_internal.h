@@ -1,0 +1,255 @@
+// lcd_host_internal.h -- what the host files of liblcd_hotpath.so share: the runtime core (error string, device selection, the device-memory budget and its
+// buffers, host thread teams), the interval helpers and the definitions of the two opaque handles.  Not part of the C ABI, not installed; every name lives in
+// lcd_internal, whose visibility is hidden, so nothing here becomes an exported symbol of the library.  State is defined in lcd_runtime.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <sched.h>
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+#include "../../include/lcd_hotpath.h"
+#include "lcd_kernels.h"
+#include "lcd_types.h"
+#include "lcd_io_internal.h"
+
+namespace lcd_internal __attribute__((visibility("hidden"))) {
+
+extern thread_local std::string g_err;   // what lcd_last_error returns on this thread
+inline int set_err(int code, const std::string &m) { g_err = m; return code; }
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { return set_err(-10, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
+
+#define LCD_MAX_DEV 16
+extern int g_n_devices;
+extern int g_n_cus; // compute units of the device (MI355X: 256)
+// (device selection: lcd_runtime.cpp)
+int init_default_device();
+int use_device(int dev); // dev < 0: the calling thread's device (lcd_set_thread_device), else the process default
+inline int ensure_init() { return use_device(-1); }
+inline int cur_device() { int d = 0; if (hipGetDevice(&d) != hipSuccess) { (void)hipGetLastError(); d = 0; } return d < LCD_MAX_DEV ? d : 0; }
+
+// the device-memory ledger of the grow-only buffers and its budget (lcd_runtime.cpp)
+extern std::atomic<long long> g_dev_bytes[LCD_MAX_DEV];
+extern std::atomic<unsigned long long> g_copy_bytes[4]; // [0] digars device -> host, [1] digars host -> device, [2] read bases host -> device (packed or unpacked), [3] read bases device -> host
+extern std::atomic<long long> g_alloc_events; // hipMalloc calls of the grow-only buffers (bench.py reports how many fell into its timed region)
+long long dev_budget(int d);
+// grow-only PINNED host block (hipHostMalloc): the destination of a batch's result download -- a pageable destination is staged by the runtime at a few GB/s
+struct PinnedBuf {
+    uint8_t *p = nullptr; size_t n = 0, cap = 0;
+    void resize(size_t want) {
+        if (want > cap) {
+            if (p) hipHostFree(p);
+            p = nullptr; cap = 0;
+            const size_t c = want + (want >> 2) + 4096;
+            void *q = nullptr;
+            if (hipHostMalloc(&q, c, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); q = malloc(c); pageable = true; }
+            p = (uint8_t *)q; cap = c;
+        }
+        n = want;
+    }
+    bool pageable = false;
+    uint8_t *data() { return p; } const uint8_t *data() const { return p; } size_t size() const { return n; }
+    ~PinnedBuf() { if (p) { if (pageable) free(p); else hipHostFree(p); } }
+    PinnedBuf() = default; PinnedBuf(const PinnedBuf &) = delete; PinnedBuf &operator=(const PinnedBuf &) = delete;
+};
+struct DevBuf {
+    void *p = nullptr; size_t cap = 0; int dev = 0;
+    int ensure(size_t n, int headroom_shift = 2);
+    void release() { if (p) { hipFree(p); g_dev_bytes[dev] -= (long long)cap; p = nullptr; cap = 0; } }
+    uint64_t addr() const { return (uint64_t)(uintptr_t)p; }
+    ~DevBuf() { release(); }
+    DevBuf() = default; DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete;
+};
+// an ad-hoc stream of a per-call entry point: destroyed on every return path
+struct StreamGuard {
+    hipStream_t s = nullptr;
+    int create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess ? 0 : set_err(-10, "hipStreamCreate failed"); }
+    ~StreamGuard() { if (s) hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+// one host staging block whose offsets become device addresses: put(p, bytes) appends `bytes` at the next 16-byte boundary (copied from p; left zero where p is
+// NULL) and returns their offset
+struct StagePut {
+    std::vector<uint8_t> &hb;
+    uint64_t operator()(const void *p, size_t bytes) const { size_t o = lcd_align_up(hb.size(), 16); hb.resize(o + bytes); if (p && bytes) memcpy(hb.data() + o, p, bytes); return (uint64_t)o; }
+};
+
+inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// host threads per team of the submission's short parallel loops (capacities, job tables, records, plans).  LCD_HOST_TEAM, read per call: a caller whose own
+// threads are busy beside the submission -- bench.py's PCIe-inclusive pipeline on a box whose cgroup allows 16 CPUs -- asks for fewer; a team that overruns the
+// quota freezes every thread of the process, the submitter included, until the next period
+// CPUs this process may use: its affinity mask, cut by the cgroup's CPU quota (v2 cpu.max, v1 cpu.cfs_quota_us / cpu.cfs_period_us) -- a container with 128 visible
+// cores and a 16-CPU quota is a 16-CPU box for thread teams
+inline int host_cpus() {
+    static const int n = [] {
+        int k = 0;
+        cpu_set_t set; CPU_ZERO(&set);
+        if (sched_getaffinity(0, sizeof(set), &set) == 0) k = CPU_COUNT(&set);
+        if (k <= 0) k = (int)std::max(1u, std::thread::hardware_concurrency());
+        double quota = 0;
+        if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) { char a[64] = {0}; long long per = 0; if (fscanf(f, "%63s %lld", a, &per) == 2 && strcmp(a, "max") != 0 && per > 0) quota = atof(a) / (double)per; fclose(f); }
+        else {
+            long long q = -1, per = 0;
+            if (FILE *fq = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) { if (fscanf(fq, "%lld", &q) != 1) q = -1; fclose(fq); }
+            if (FILE *fp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(fp, "%lld", &per) != 1) per = 0; fclose(fp); }
+            if (q > 0 && per > 0) quota = (double)q / (double)per;
+        }
+        if (quota > 0) k = std::max(1, std::min(k, (int)(quota + 0.5)));
+        return k;
+    }();
+    return n;
+}
+// processes of this job on this host: one per GPU under torch.distributed.run (LOCAL_WORLD_SIZE; WORLD_SIZE on a single node)
+inline int host_local_world() {
+    const char *e = getenv("LOCAL_WORLD_SIZE"); if (!e || atoi(e) < 1) e = getenv("WORLD_SIZE");
+    const int w = e ? atoi(e) : 1;
+    return w < 1 ? 1 : w;
+}
+// With N ranks on one host every rank runs these teams at the same moments (the ranks step together): the default is the host's CPUs divided by the ranks, at most 8.
+inline int host_team() {
+    const char *e = getenv("LCD_HOST_TEAM");
+    const int v = e ? atoi(e) : std::min(8, std::max(1, host_cpus() / host_local_world()));
+    return v < 1 ? 1 : v > 32 ? 32 : v;
+}
+// (threads that lay results out on the host, lcd_batch_results_arena: LCD_ARENA_THREADS, default 16 -- or the rank's share of the host's CPUs)
+inline int host_arena_threads() {
+    const char *e = getenv("LCD_ARENA_THREADS");
+    return e ? std::max(1, atoi(e)) : std::min(16, std::max(1, host_cpus() / host_local_world()));
+}
+// a loop over [0, n) cut into chunks taken by up to `max_threads` host threads (the calling thread is one of them); f(lo, hi, thread index)
+template <class F> static void par_chunks(const size_t n, const int max_threads, const size_t chunk, F f) {
+    const int nth = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(1, max_threads), (n + chunk - 1) / std::max<size_t>(1, chunk)));
+    if (nth <= 1) { if (n) f((size_t)0, n, 0); return; }
+    std::atomic<size_t> next{0};
+    auto work = [&](const int t) { for (size_t lo; (lo = next.fetch_add(chunk)) < n;) f(lo, std::min(n, lo + chunk), t); };
+    std::vector<std::thread> ths;
+    for (int t = 1; t < nth; ++t) ths.emplace_back(work, t);
+    work(0);
+    for (auto &t : ths) t.join();
+}
+inline LcdScoring scoring_of(const lcd_opt_t &o) { LcdScoring s; s.match = o.match; s.mismatch = o.mismatch; s.o1 = o.gap_open1; s.e1 = o.gap_ext1; s.o2 = o.gap_open2; s.e2 = o.gap_ext2; s.dbg = getenv("LCD_DBG") ? atoi(getenv("LCD_DBG")) : 0; s.wd_s = getenv("LCD_WATCHDOG_S") ? atoi(getenv("LCD_WATCHDOG_S")) : 0; return s; }
+struct NIv { uint64_t x; long long en; int label; }; // x: the interval index's sort key (contig 0: the start)
+
+// ---- the records of a region batch (lcd_host.cpp) ----
+struct RegRead { // one read of a region, in sorted order after add
+    int id, len, cover, hap; int64_t ps; uint64_t off; double err;
+    int rb = -1, re = -2; // read_reg_beg / read_reg_end of collect_noisy_read_info (chunk-view entry only)
+};
+struct ChainRec {
+    int region, clu;              // clu: hap-1 for K1, 0 for K2 (clusters come out of the kernel)
+    int mode;
+    std::vector<int> members;     // indices into the region's sorted read list
+    int read0;                    // first PoaRead
+    int cert_fail_round = -1;     // K2: the last round in which the certified band did not fit its class's window (the chain then moves one class up)
+    int solo = -1;                // -1: by the fixed threshold (LCD_SOLO_RL); 0 / 1: decided for the submission at hand (run_many_once: the longest chains of what is in flight)
+    int cert_level = -1;          // -1: not chosen yet; 1: certified band in the single-wavefront rows; 2: in the systolic rows of the class the reads' length asks for (noisy reads); 0: full rows
+};
+struct AnchorRec {
+    int pread;                    // index into preads
+    int ext;                      // 1 L->R, 2 R->L ; 0: sampling-mode full-read K4 filter only
+    int tlen_full, qlen_full;     // _tlen, _qlen
+    int ed_job, wfa_job;
+    int min_len;
+};
+struct RegionRec {
+    int64_t reg_len; int n_reads;
+    std::vector<RegRead> reads;   // sorted (src/align.c:1774)
+    uint64_t ref_off; int ref_len;
+    int branch;                   // 0 skipped, 1 with-PS (K1 x2), 2 no-PS (K2)
+    int sampling;
+    int chain[2];                 // chain indices (-1 none)
+    // results
+    int n_cons = 0;
+};
+
+struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
+
+} // namespace lcd_internal
+
+extern "C" void lcd_account_device_bytes(int device, long long delta); // the ledger's entry for buffers allocated outside DevBuf (lcd_io.cpp's inflated streams); exported, not in the public header
+
+// lcd_batch_s and lcd_chunk_s are the global types behind the public handles: their members name the types above
+using lcd_internal::RegRead; using lcd_internal::ChainRec; using lcd_internal::AnchorRec; using lcd_internal::RegionRec; using lcd_internal::VarRegionRec;
+using lcd_internal::DevBuf; using lcd_internal::PinnedBuf;
+#define LCD_NSIDE 12
+struct lcd_batch_s {
+    lcd_opt_t opt;
+    int device = 0;                      // every entry point on this batch selects it (HIP's current device is per host thread)
+    hipStream_t stream = nullptr;
+    hipStream_t side[LCD_NSIDE] = {};
+    hipEvent_t ev[10];
+    hipEvent_t sev[LCD_NSIDE + 1];
+    std::vector<uint8_t> h_pool;
+    std::vector<UnpackJob> unpack_abs; DevBuf d_unpack_abs; uint64_t pool_read_bytes = 0; // slices whose packed bases are ALREADY in HBM (lcd_chunk_t): src = device address; read bases inside h_pool (the copy counter)
+    std::vector<uint8_t> h_packed; std::vector<UnpackJob> unpack_jobs; // read slices handed over 4-bit packed: unpacked into d_in after the upload
+    std::vector<RegionRec> regs;
+    std::vector<ChainRec> chains;
+    std::vector<PoaRead> preads;         // seq_off relative to h_pool until run()
+    std::vector<AnchorRec> anchors;
+    std::vector<EdJob> ed_jobs;          // offsets relative to h_pool until run()
+    std::vector<WfaJob> wfa_jobs;
+    // device
+    // (d_poa_arena: the ONE transient workspace of a submission led by this batch -- chain arenas, WFA wavefronts and edlib blocks in turn)
+    DevBuf d_read_patches, d_aends_jobs, d_aends_outs, d_in, d_chains, d_preads, d_poa_arena, d_poa_out, d_poa_outs, d_ed_jobs, d_ed_outs, d_wfa_jobs,
+        d_wfa_out, d_wfa_outs, d_str_jobs, d_str_outs, d_final, d_gate, d_cmp_jobs, d_cmp_outs, d_cmp_seg, d_cmp_segres, d_seg_out, d_rr,
+        d_var_jobs, d_var_outs, d_var_work, d_vreg_jobs, d_vreg_outs, d_var_out, d_slot_flags, d_spare, d_packed, d_unpack,
+        d_early_arena, d_chains_early, d_poa_outs_early,   // the long K2 chains that start before the anchor stage (run_many_once)
+        d_ed_arena;                                                         // K4's stored columns when it runs beside K3 in the anchor stage
+    bool uploaded = false, ran = false, downloaded = false;
+    // results (host)
+    std::vector<PoaChainOut> couts;
+    std::vector<PoaChain> pchains;
+    std::vector<WfaJob> rc_jobs; std::vector<WfaOut> rc_outs; // ref<->cons
+    std::vector<int> rc_region, rc_clu;
+    std::vector<uint32_t> reg_rc0, reg_str0;   // [n_regions + 1]: the ref<->cons / string jobs of region r are [reg_rc0[r], reg_rc0[r + 1]) and [reg_str0[r], reg_str0[r + 1]) (jobs are made region by region)
+    std::vector<StrJob> str_jobs; std::vector<StrOut> str_outs;
+    std::vector<int> str_region, str_clu, str_k;
+    PinnedBuf h_final; std::vector<uint8_t> h_poa_out; std::vector<uint8_t> h_cig;
+    PinnedBuf h_sub_pin, h_tmp_pin; // leader: the chain table of a round and the chains' output records (page-locked and kept: 7 + 9 MB per 20-batch round were allocated, zeroed and faulted in every time)
+    std::vector<std::pair<int, uint32_t>> clu_gather_index;
+    bool gathered = false; uint64_t g_extra = 0, g_clu_base = 0; std::vector<uint64_t> g_rc_off; // the scattered result pieces are already in d_gather (stage_gather at the end of the run): the download is copies only
+    DevBuf d_gather, d_gather_jobs; std::vector<std::pair<int, uint32_t>> clu_index;   // download: staging block of the scattered pieces; (chain, offset into h_poa_out) of the K2 cluster lists
+    std::vector<WfaJob> h_rc_all; std::vector<StrJob> h_str_all; std::vector<StrOut> h_str_outs; // leader: the joint job tables of a submission (kept between submissions: no reallocation, no first-touch page faults in the steady state)
+    // ref<->read strings (opt.collect_ref_read_aln_str): per string job, rows in d_rr at rr_off (target row, query row at +rr_stride)
+    std::vector<uint64_t> rr_off; std::vector<int> rr_len, rr_stride; std::vector<uint8_t> h_rr; uint64_t rr_bytes = 0;
+    // candidate variants (opt.collect_noisy_vars): per resolved region, offsets into d_var_out / h_var
+    std::vector<VarRegionRec> vregs; std::vector<int> vreg_of; std::vector<uint8_t> h_var; uint64_t var_bytes = 0;
+    std::vector<std::unique_ptr<DevBuf>> retry_out; // output blocks of chains re-run with a larger graph capacity (live until the next run; the buffers
+    size_t retry_out_used = 0;                      // themselves are kept and re-used: freeing ~60 of them per noisy-read submission synchronised the device each time)
+    // the chains' work arenas live in d_poa_arena and, when a later submission needs more, in additional chunks: growing by a chunk costs the difference,
+    // re-allocating tens of GB costs seconds (and the pools' slot sizes make the total jump by a third from one set of chunks to the next)
+    std::vector<std::unique_ptr<DevBuf>> arena_extra;
+    uint64_t final_bytes = 0;
+    lcd_batch_stats_t st;
+};
+
+// a device-resident chunk (lcd_chunk.cpp)
+struct lcd_chunk_s {
+    int device = 0, n_reads = 0; lcd_digar_opt_t opt;
+    DevBuf d_dig, d_seq;                                   // digars (DigarRec, per read at slot[r], n_digar[r] of them); the records' 4-bit packed bases
+    lcd_inflated_t *stream = nullptr;                      // lcd_chunk_create_from_bam: the inflated BGZF blocks; bases and qualities are read where they lie in it
+    uint64_t seq_base = 0, qual_base = 0;                  // device address seq_off / qual_off are relative to (qual_base 0: the qualities are in h_qual)
+    std::vector<uint64_t> slot, seq_off; std::vector<int> n_digar, qlen;
+    std::vector<uint8_t> h_qual; std::vector<uint64_t> qual_off;   // host copy: the sampling rule of >= 10 kb regions reads qualities on the host (src/seq.c:429)
+    std::vector<int> status, n_cand; std::vector<int64_t> beg, end;
+    uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
+    DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
+    DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use
+    ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); }
+};
+
+// ---- noisy-region intervals with cgranges' index order and merge rule (lcd_noisy_regs.cpp).  These names have C linkage and default visibility: written inside
+// an extern "C" block they have been dynamic symbols of the library from the start, and the export surface stays as it is ----
+using lcd_internal::NIv;
+extern "C" {
+void niv_index(std::vector<NIv> &v);
+void niv_add(std::vector<NIv> &v, long long st, long long en, int label);
+void niv_merge(std::vector<NIv> &v, const int fixed_win = -1);
+} // extern "C"

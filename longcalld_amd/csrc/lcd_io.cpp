@@ -19,7 +19,7 @@
 #include <thread>
 #include <vector>
 #include "../../include/lcd_hotpath.h"
-#include "lcd_io_internal.h"
+#include "lcd_host_internal.h"
 
 namespace {
 thread_local std::string g_io_err;
@@ -482,7 +482,7 @@ unsigned gf2_mulmod_h(unsigned a, unsigned b) { unsigned m = 1u << 31, p = 0; fo
 }
 struct lcd_inflated_s { void *d_in = nullptr, *d_out = nullptr, *d_jobs = nullptr, *d_outs = nullptr; size_t total = 0, n_blocks = 0, comp_bytes = 0; double ms_kernel = 0, ms_h2d = 0;
                         long long accounted = 0; int device = 0; hipStream_t st = nullptr; hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; };
-extern "C" void lcd_account_device_bytes(int device, long long delta); // lcd_host.cpp: the library's device-memory ledger (LCD_MEM_FRACTION planning sees an inflated stream too)
+// lcd_account_device_bytes (lcd_host_internal.h, lcd_runtime.cpp): the library's device-memory ledger (LCD_MEM_FRACTION planning sees an inflated stream too)
 extern "C" {
 #define IOHIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { io_err(-40, std::string("HIP: ") + hipGetErrorString(e_) + " in " #x); lcd_inflated_free(h); return nullptr; } } while (0)
 void lcd_inflated_free(lcd_inflated_t *h) {

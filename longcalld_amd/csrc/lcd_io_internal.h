@@ -1,4 +1,4 @@
-// lcd_io.cpp's helpers used by lcd_host.cpp (same library; not part of the C ABI)
+// lcd_io.cpp's helpers used by lcd_chunk.cpp (same library; not part of the C ABI)
 #pragma once
 #include <stdint.h>
 #include <utility>

@@ -1,4 +1,4 @@
-// lcd_types.h -- POD descriptors shared by the host orchestration (lcd_host.cpp) and the gfx950 kernels.
+// lcd_types.h -- POD descriptors shared by the host orchestration (lcd_host.cpp and the host files beside it, DESIGN "Source map") and the gfx950 kernels.
 // Names follow the reference's domain (regions, reads, chains = one abPOA graph build, cons, msa).
 #pragma once
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // merge_vars_kernel.hip -- the read x variant profile after merge_var_profile (src/collect_var.c:1298-1387) for every region of a pass at once.
-// The variant-table walk is sequential and tiny and stays on the host (lcd_host.cpp, lcd_merge_region_vars); it yields, per chunk, the composed index maps
+// The variant-table walk is sequential and tiny and stays on the host (lcd_chunk_vars.cpp, lcd_merge_region_vars); it yields, per chunk, the composed index maps
 // old variant -> merged variant and region variant -> merged variant (-1: dropped as equal to a kept one).  What scales with reads x variants runs here, for
 // all chunks of a call in one set of launches (sources carry absolute addresses and an index into the call's read table):
 //   span     one lane per source (a read's current profile, or one region row): min / max of the merged indices its cells move to, integer atomics on the
