@@ -389,11 +389,48 @@ lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n_reads, const int
  * than 65 535 operations; file order; the loader's stop rule) and their digars made and kept there.  Bases and qualities are never moved: the region jobs unpack
  * bases from the inflated stream, the sampling rule of long regions (calc_read_error_rate, src/seq.c:429) runs on the qualities in HBM.  The host receives 80 bytes
  * per record and, with `meta`, the per-read scalars of lcd_bam_reads_t and the read names (cigar_pool / seq_pool / qual_pool stay NULL; seq_off / qual_off are
- * offsets of the device stream; free with lcd_bam_reads_free).  whole_ref_len = the contig's length in the BAM header; pal_flags = 0 (is_ont_palindrome_clip needs
- * the caller's clip test).  Result == lcd_bam_load_region_indexed + lcd_chunk_create on the same region.  A region without reads gives a chunk of 0 reads.
+ * offsets of the device stream; free with lcd_bam_reads_free).  whole_ref_len = the contig's length in the BAM header; pal_flags = 0 and only reads with an
+ * EQX CIGAR (an 'M' operation: status -2, whatever tags the read carries) -- lcd_chunk_create_from_bam_src below lifts both.  Result == lcd_bam_load_region_indexed + lcd_chunk_create on the same region.  A region without reads gives a chunk of 0 reads.
  * NULL on failure (lcd_last_error()); no host path: without a HIP device the call fails. */
 lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
                                        int min_mapq, int verify_crc, struct lcd_bam_reads_t *meta);
+/* Chunks from ANY BAM: per read the digar source the reference chooses (collect_digars_from_bam, src/collect_var.c:1072-1079), and on ONT data the SA-tag palindrome
+ * rule (is_ont_palindrome_clip + check_ont_palindrome, src/bam_utils.c:642-698).  minimap2 without --eqx and dorado's aligner write 'M' CIGARs: through
+ * lcd_chunk_create_from_bam every such read is status -2; through this entry point it is a read like any other.
+ *   Selection (has_equal_X_in_bam_cigar, :51-66): the FIRST operation among '=' / 'X' / 'M' decides -- '=' or 'X': LCD_SRC_EQX; 'M', or none of the three: the first
+ *   auxiliary field named cs gives LCD_SRC_CS, else the first named MD gives LCD_SRC_MD, else LCD_SRC_REF.  The fields are walked as bam_aux_get walks them: a field
+ *   that runs past the record ends the walk silently, the tags behind it do not exist.  A cs / MD field whose type is not Z: status -2 (the reference would read it as
+ *   a string).  LCD_SRC_REF without a reference window (src->ref_seq NULL or ref_end < ref_beg), or with a CIGAR that does not consume exactly the record's l_seq
+ *   bases (the comparison reads the 4-bit bases in place): status -2.  A cs / MD value that does not fit its CIGAR: status -2, as lcd_digar_batch_tags.
+ *   Per read, digars / noisy windows / iv_in_chunk / status / beg / end / n_cand_vars == lcd_digar_batch, lcd_digar_batch_tags (LCD_DIGAR_CS with the cs function's
+ *   own clip rule, LCD_DIGAR_MD; digar->end = bam_endpos) or lcd_digar_batch_ref on that read.  One chunk may mix all four sources; ONE digar launch covers them.
+ *   SA rule (src->is_ont != 0 only): the first field named SA, of type Z (another type counts as no tag); its value split on ';', empty pieces skipped; an entry is
+ *   `rname,pos,strand,cigar[,...]` with rname and cigar non-empty, pos a decimal integer (one optional sign), strand one character.  PROJECT RULE: an entry that does
+ *   not give these four is skipped (the reference's sscanf leaves its variables uninitialised there).  sa_end = pos + the lengths of the M / D / = / X operations of the
+ *   entry's CIGAR ('N' is not counted; an operation letter without digits counts 0); primary = [pos0 + 1, bam_endpos]; overlap as check_ont_palindrome's four cases;
+ *   palindromic if (double)overlap >= (double)primary_len * 0.9 for any entry.  rname and strand are not consulted.  A palindromic read on the reverse strand (flag 16)
+ *   gets the left-clip flag, any other the right-clip flag (pal_flags bit 0 / bit 1 of lcd_digar_batch).
+ *   What crosses PCIe: the cs / MD tag VALUES of the CS / MD reads (with their CIGAR words; O(events) bytes, parsed on the host like lcd_digar_batch_tags does) and the
+ *   operation words made from them going back -- never a base, a quality or a digar; the reference window goes up once per chunk.
+ * src == NULL: lcd_chunk_create_from_bam.  The chunk is the same kind of chunk: every lcd_chunk_* / lcd_chunks_* call accepts it.
+ * lcd_chunk_read_sources: per read LCD_SRC_* (what the reference would have chosen, whatever the outcome; LCD_SRC_EQX for a chunk made any other way), the
+ * chunk->is_ont_palindrome flag, and the summed strlen of the cs / MD values brought to the host; any pointer may be NULL.  lcd_chunk_stage_ms: wall-clock
+ * milliseconds of lcd_chunk_create_from_bam_src's stages [aux fields, reference comparison, tag download + host parse, digars] (zeros without src).
+ * lcd_chunk_digars: a malloc()'d CSR copy of the digars ANY chunk holds in HBM (tests, debugging; counted in lcd_copy_counters[0]); free() both. */
+#define LCD_SRC_EQX 0
+#define LCD_SRC_CS  1
+#define LCD_SRC_MD  2
+#define LCD_SRC_REF 3
+typedef struct lcd_chunk_src_t {
+    const char *ref_seq; int64_t ref_beg, ref_end;  /* chunk->ref_seq window, letters or codes 0-4, 1-based inclusive; NULL: no reference */
+    int is_ont;                                     /* != 0: apply the SA-tag palindrome rule */
+} lcd_chunk_src_t;
+lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom,
+                                           int64_t reg_beg, int64_t reg_end, int min_mapq, int verify_crc,
+                                           const lcd_chunk_src_t *src, struct lcd_bam_reads_t *meta);
+int lcd_chunk_read_sources(const lcd_chunk_t *c, uint8_t *source, uint8_t *is_ont_palindrome, uint64_t *tag_bytes_d2h);
+void lcd_chunk_stage_ms(const lcd_chunk_t *c, double out[4]);
+int lcd_chunk_digars(const lcd_chunk_t *c, uint64_t **digar_off, lcd_digar_t **digars);   /* malloc()'d CSR copy; counted in lcd_copy_counters[0] */
 void lcd_chunk_destroy(lcd_chunk_t *c);
 int lcd_chunk_n_reads(const lcd_chunk_t *c);
 int lcd_chunk_read_info(const lcd_chunk_t *c, int *status, int64_t *beg, int64_t *end, int *n_cand_vars, int *n_digars);

@@ -505,10 +505,12 @@ class DeviceChunk:
         self.packed_bytes = int(soff[-1])
 
     @classmethod
-    def from_bam(cls, bam_path, bai_path, chrom, reg_beg, reg_end, min_mapq=30, is_ont=0, verify_crc=1):
+    def from_bam(cls, bam_path, bai_path, chrom, reg_beg, reg_end, min_mapq=30, is_ont=0, verify_crc=1, src=None):
         """lcd_chunk_create_from_bam: the region's BGZF blocks inflated on the device, records found / filtered / turned into digars there.
-        -> the chunk; .meta = per-read scalars and names (dict of numpy arrays / list)"""
-        from ._lib import LcdBamReads
+        src=(ref, ref_beg, ref_end, is_ont) -> lcd_chunk_create_from_bam_src: every read from the source the reference chooses for it (EQX CIGAR, cs tag, MD tag,
+        comparison with `ref` = the chunk's reference window as letters or codes 0-4, bytes / uint8 array or None) and, with is_ont, the SA-tag palindrome rule;
+        the digar options are those of src's is_ont.  -> the chunk; .meta = per-read scalars and names (dict of numpy arrays / list)"""
+        from ._lib import LcdBamReads, LcdChunkSrc
         self = cls.__new__(cls)
         self.lib = lib = load_library()
         opt = LcdDigarOpt(); lib.lcd_digar_opt_default(C.byref(opt), int(is_ont))
@@ -516,7 +518,21 @@ class DeviceChunk:
         lib.lcd_chunk_create_from_bam.restype = C.c_void_p
         lib.lcd_chunk_create_from_bam.argtypes = [C.POINTER(LcdDigarOpt), C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(LcdBamReads)]
         enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
-        self.h = lib.lcd_chunk_create_from_bam(C.byref(opt), enc(bam_path), enc(bai_path), enc(chrom), int(reg_beg), int(reg_end), int(min_mapq), int(verify_crc), C.byref(m))
+        if src is None:
+            self.h = lib.lcd_chunk_create_from_bam(C.byref(opt), enc(bam_path), enc(bai_path), enc(chrom), int(reg_beg), int(reg_end), int(min_mapq), int(verify_crc), C.byref(m))
+        else:
+            ref, ref_beg, ref_end, src_ont = src
+            lib.lcd_digar_opt_default(C.byref(opt), int(src_ont))
+            refb = None if ref is None else (bytes(ref) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, np.uint8).tobytes())
+            refbuf = C.create_string_buffer(refb, len(refb) + 1) if refb is not None else None   # (codes 0-4 contain NULs: not a C string; alive until the call returns)
+            cs = LcdChunkSrc(); cs.ref_seq = C.cast(refbuf, C.c_char_p) if refbuf is not None else None
+            cs.ref_beg, cs.ref_end, cs.is_ont = int(ref_beg), int(ref_end), int(src_ont)
+            if refb is not None and len(refb) < cs.ref_end - cs.ref_beg + 1:
+                raise ValueError("DeviceChunk.from_bam: ref is shorter than [ref_beg, ref_end]")
+            lib.lcd_chunk_create_from_bam_src.restype = C.c_void_p
+            lib.lcd_chunk_create_from_bam_src.argtypes = lib.lcd_chunk_create_from_bam.argtypes[:-1] + [C.POINTER(LcdChunkSrc), C.POINTER(LcdBamReads)]
+            self.h = lib.lcd_chunk_create_from_bam_src(C.byref(opt), enc(bam_path), enc(bai_path), enc(chrom), int(reg_beg), int(reg_end), int(min_mapq), int(verify_crc),
+                                                       C.byref(cs), C.byref(m))
         if not self.h:
             raise RuntimeError("lcd_chunk_create_from_bam failed: " + lib.lcd_last_error().decode())
         n = self.n = m.n_reads
@@ -536,6 +552,40 @@ class DeviceChunk:
         self.lib.lcd_chunk_read_info.argtypes = [C.c_void_p, i32p, i64p, i64p, i32p, i32p]
         self.lib.lcd_chunk_read_info(self.h, st.ctypes.data_as(i32p), beg.ctypes.data_as(i64p), end.ctypes.data_as(i64p), nc.ctypes.data_as(i32p), nd.ctypes.data_as(i32p))
         return dict(status=st, beg=beg, end=end, n_cand=nc, n_digars=nd)
+
+    def sources(self):
+        """lcd_chunk_read_sources -> dict(source: LCD_SRC_* per read (0 EQX, 1 cs, 2 MD, 3 reference comparison), is_ont_palindrome per read, tag_bytes_d2h)"""
+        so = np.zeros(max(self.n, 1), np.uint8); pl = np.zeros(max(self.n, 1), np.uint8); tb = C.c_uint64(0)
+        self.lib.lcd_chunk_read_sources.argtypes = [C.c_void_p, u8p, u8p, C.POINTER(C.c_uint64)]
+        self.lib.lcd_chunk_read_sources(self.h, _p8(so), _p8(pl), C.byref(tb))
+        return dict(source=so[:self.n], is_ont_palindrome=pl[:self.n], tag_bytes_d2h=int(tb.value))
+
+    def stage_ms(self):
+        """lcd_chunk_stage_ms -> [aux fields, reference comparison, tag download + host parse, digars] of from_bam(src=...), milliseconds"""
+        out = (C.c_double * 4)()
+        self.lib.lcd_chunk_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self.lib.lcd_chunk_stage_ms.restype = None
+        self.lib.lcd_chunk_stage_ms(self.h, out)
+        return [float(x) for x in out]
+
+    def digars(self):
+        """lcd_chunk_digars: the digars the chunk holds in HBM, downloaded -> per read an (n, 5) int64 array [pos, type, len, qi, is_low_qual] (digar_batch's layout)"""
+        u64p_ = C.POINTER(C.c_uint64)
+        doff, dg = u64p_(), C.POINTER(LcdDigar)()
+        self.lib.lcd_chunk_digars.argtypes = [C.c_void_p, C.POINTER(u64p_), C.POINTER(C.POINTER(LcdDigar))]
+        check(self.lib.lcd_chunk_digars(self.h, C.byref(doff), C.byref(dg)), self.lib)
+        if not doff:
+            return []
+        tot = int(doff[self.n])
+        dt = np.dtype([("pos", "<i8"), ("type", "<i4"), ("len", "<i4"), ("qi", "<i4"), ("lq", "<i4")])
+        D = np.frombuffer((C.c_char * (24 * max(tot, 1))).from_address(C.addressof(dg.contents)), dtype=dt, count=tot).copy() if tot else np.zeros(0, dt)
+        out = []
+        for r in range(self.n):
+            d = D[int(doff[r]):int(doff[r + 1])]
+            out.append(np.stack([d["pos"], d["type"].astype(np.int64), d["len"].astype(np.int64), d["qi"].astype(np.int64), d["lq"].astype(np.int64)], 1).reshape(-1, 5))
+        for p_ in (doff, dg):
+            _libc.free(C.cast(p_, C.c_void_p))
+        return out
 
     def intervals(self):
         """-> per read (noisy (m, 3) int64 [start, end, label], in_chunk mask)"""

@@ -4,6 +4,8 @@
 //                         records of ~25 KB per 500 kb HiFi chunk, one dependent load each) and leaves a 40-byte descriptor per record;
 //   lcd_bam_stat_kernel   one wavefront per record of the wanted reference: reference span (bam_endpos), digar / window-event capacities of its CIGAR (the counts
 //                         lcd_digar_batch's host pass makes), the CG:B,I tag behind the placeholder CIGAR of a read with more than 65 535 operations;
+//   lcd_bam_aux_kernel    one wavefront per kept record: the digar source the reference would choose for it (EQX CIGAR / cs / MD / reference comparison), where
+//                         its cs / MD value lies, and the SA tag's palindrome test of ONT reads;
 //   lcd_bam_cigar_kernel  the kept records' CIGAR words -> a 4-byte aligned pool (records sit at any byte offset of the stream);
 //   lcd_errrate_kernel    calc_read_error_rate (src/seq.c:429-436) of a read slice on the qualities in HBM: the same table values added in the same order as the
 //                         host loop, so the doubles are the host's.
@@ -120,6 +122,127 @@ __global__ void __launch_bounds__(64) lcd_bam_cigar_kernel(const GatherJob *jobs
     for (unsigned k = threadIdx.x; k < nw; k += 64) dst[k] = ld32u(src + 4 * (size_t)k);
 }
 
+// ---- lcd_bam_aux_kernel: which of the reference's four digar sources a kept record gets (collect_digar_from_bam, src/collect_var.c:1072-1079), where its cs / MD
+// value lies, and is_ont_palindrome_clip (src/bam_utils.c:642-698) on its SA tag.  One wavefront per record.  The auxiliary fields are hopped as bam_aux_get does:
+// a field that runs past the record ends the walk, and what lies behind it does not exist.  Every lane walks the same fields (the loads are wave-uniform); the NUL
+// search of a Z / H value is cooperative -- cs strings of long reads run to hundreds of kilobytes -- and bounded by the record's end. ----
+namespace {
+// offset of the first NUL in [p, end), or -1: four independent byte loads per lane and step, one ballot of 64 bytes each
+__device__ __forceinline__ long long wave_find_nul(const uint8_t *p, const uint8_t *end, const int lane) {
+    const long long n = end - p;
+    for (long long k = 0; k < n; k += 256) {
+        unsigned b[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const long long i = k + 64 * u + lane; b[u] = i < n ? p[i] : 1u; }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const unsigned long long m = __ballot(b[u] == 0); if (m) return k + 64 * u + (__ffsll((long long)m) - 1); }
+    }
+    return -1;
+}
+__device__ __forceinline__ bool is_dig(const uint8_t c) { return c >= '0' && c <= '9'; }
+// the SA value s[0, n): entries between ';' (empty ones skipped), each `rname,pos,strand,cigar[,...]` with a non-empty rname and cigar, a decimal pos (one optional
+// sign) and a one-character strand -- an entry that does not give these four is skipped (the reference's sscanf leaves its variables unset there).  sa_end = pos +
+// the lengths of the M / D / = / X operations (an operation letter without digits counts 0); check_ont_palindrome's four overlap cases; any entry decides.
+__device__ int sa_is_palindrome(const uint8_t *s, const int n, const long long prim_pos, const long long prim_end) {
+    const long long prim_len = prim_end - prim_pos + 1;
+    int i = 0;
+    while (i < n) {
+        int e = i; while (e < n && s[e] != ';') ++e;
+        int p = i;                                                     // the entry is s[i, e)
+        i = e + 1;
+        const int r0 = p; while (p < e && s[p] != ',') ++p;
+        if (p == r0 || p >= e) continue;                               // rname
+        ++p;
+        bool neg = false;
+        if (p < e && (s[p] == '-' || s[p] == '+')) { neg = s[p] == '-'; ++p; }
+        const int d0 = p; long long pos = 0;
+        while (p < e && is_dig(s[p])) { pos = pos * 10 + (s[p] - '0'); if (pos > 2147483647ll) pos = 2147483647ll; ++p; }
+        if (p == d0 || p >= e || s[p] != ',') continue;                // pos
+        if (neg) pos = -pos;
+        ++p;
+        if (p + 1 >= e || s[p + 1] != ',') continue;                   // strand
+        p += 2;
+        int ce = p; while (ce < e && s[ce] != ',') ++ce;
+        if (ce == p) continue;                                         // cigar
+        long long sa_end = pos;
+        while (p < ce) {
+            long long len = 0;
+            while (p < ce && is_dig(s[p])) { len = len * 10 + (s[p] - '0'); if (len > 2147483647ll) len = 2147483647ll; ++p; }
+            if (p >= ce) break;
+            const uint8_t c = s[p++];
+            if (c == 'M' || c == 'D' || c == '=' || c == 'X') sa_end += len;
+        }
+        const long long sa_len = sa_end - pos + 1;
+        long long ov = 0;                                              // check_ont_palindrome (src/bam_utils.c:642-654)
+        if (pos <= prim_pos) { if (sa_end >= prim_end) ov = prim_len; else if (sa_end >= prim_pos) ov = sa_end - prim_pos + 1; }
+        else if (pos <= prim_end) { if (sa_end >= prim_end) ov = prim_end - pos + 1; else ov = sa_len; }
+        if ((double)ov >= (double)prim_len * 0.9) return 1;
+    }
+    return 0;
+}
+} // namespace
+__global__ void __launch_bounds__(64) lcd_bam_aux_kernel(const BamAuxJob *jobs, BamAuxOut *outs, const int is_ont, const int n_jobs) {
+    const int jb = blockIdx.x;
+    if (jb >= n_jobs) return;
+    const BamAuxJob j = jobs[jb];
+    const int lane = threadIdx.x;
+    const uint8_t *r = (const uint8_t *)(uintptr_t)j.rec, *cig = (const uint8_t *)(uintptr_t)j.cig;
+    // has_equal_X_in_bam_cigar (src/bam_utils.c:51-66): the first of '=' / 'X' / 'M' decides
+    bool eqx = false;
+    for (int c0 = 0; c0 < j.nc; c0 += 64) {
+        const int k = c0 + lane;
+        const int op = k < j.nc ? (int)(ld32u(cig + 4 * (size_t)k) & 0xf) : -1;
+        const unsigned long long m = __ballot(op == 0 || op == 7 || op == 8);
+        if (m) { eqx = __shfl(op, __ffsll((long long)m) - 1) != 0; break; }
+    }
+    long long cig_qlen = 0;
+    if (!eqx) {
+        for (int k = lane; k < j.nc; k += 64) { const unsigned c = ld32u(cig + 4 * (size_t)k); const int op = (int)(c & 0xf); if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) cig_qlen += (long long)(c >> 4); }
+        cig_qlen = wave_sum(cig_qlen);
+    }
+    const uint8_t *v_cs = nullptr, *v_md = nullptr, *v_sa = nullptr; long long l_cs = 0, l_md = 0, l_sa = 0; uint8_t t_cs = 0, t_md = 0, t_sa = 0; // the first cs / MD / SA field: value, strlen, type
+    if (!eqx || is_ont) {
+        const uint8_t *aux = r + 32 + j.lname + 4 * (size_t)j.nc16 + ((size_t)j.lseq + 1) / 2 + (size_t)j.lseq, *end = r + j.bs;
+        while (aux + 3 <= end) {
+            const uint8_t t0 = aux[0], t1 = aux[1], ty = aux[2]; aux += 3;
+            size_t sz = 0; bool bad = false; long long zl = 0;
+            if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+            else if (ty == 's' || ty == 'S') sz = 2;
+            else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+            else if (ty == 'Z' || ty == 'H') { zl = wave_find_nul(aux, end, lane); if (zl < 0) bad = true; else sz = (size_t)zl + 1; }
+            else if (ty == 'B') {
+                if (aux + 5 > end) bad = true;
+                else {
+                    const uint8_t sub = aux[0]; const unsigned cnt = ld32u(aux + 1);
+                    const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+                    if (!es || (size_t)(end - (aux + 5)) < (size_t)cnt * es) bad = true;
+                    else sz = 5 + (size_t)cnt * es;
+                }
+            } else bad = true;
+            if (bad || (size_t)(end - aux) < sz) break;
+            if (t0 == 'c' && t1 == 's') { if (!t_cs) { t_cs = ty; v_cs = aux; l_cs = zl; } }
+            else if (t0 == 'M' && t1 == 'D') { if (!t_md) { t_md = ty; v_md = aux; l_md = zl; } }
+            else if (t0 == 'S' && t1 == 'A') { if (!t_sa) { t_sa = ty; v_sa = aux; l_sa = zl; } }
+            if ((eqx || t_cs) && (!is_ont || t_sa)) break;      // nothing a later field could change
+            aux += sz;
+        }
+    }
+    const int source = eqx ? 0 : t_cs ? 1 : t_md ? 2 : 3;
+    int pal = 0;
+    if (is_ont && t_sa == 'Z') {
+        if (lane == 0) pal = sa_is_palindrome(v_sa, (int)l_sa, j.prim_pos, j.prim_end);
+        pal = __builtin_amdgcn_readfirstlane(pal);
+    }
+    if (lane == 0) {
+        BamAuxOut o; o.tag = 0; o.tag_len = 0; o.source = (uint8_t)source; o.pal = (uint8_t)(pal ? ((j.flag & 16) ? 1 : 2) : 0); o.bad_type = 0; o.pad = 0; o.cig_qlen = cig_qlen;
+        if (source == 1 || source == 2) {
+            if ((source == 1 ? t_cs : t_md) != 'Z') o.bad_type = 1;
+            else { o.tag = (uint64_t)(uintptr_t)(source == 1 ? v_cs : v_md); o.tag_len = (uint32_t)(source == 1 ? l_cs : l_md); }
+        }
+        outs[jb] = o;
+    }
+}
+
 // e = sum over the slice of 10^(-q / 10), in slice order, divided by the length: tab[q] is the host's pow(10.0, -q / 10.0)
 __global__ void __launch_bounds__(64) lcd_errrate_kernel(const ErrJob *jobs, const double *tab, double *out, const int n_jobs) {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -138,4 +261,5 @@ __global__ void __launch_bounds__(64) lcd_errrate_kernel(const ErrJob *jobs, con
 void lcd_launch_bam_walk(const BamWalkJob *jobs, BamWalkOut *outs, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_walk_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, outs); }
 void lcd_launch_bam_stat(const BamStatJob *jobs, BamStatOut *outs, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_stat_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, outs, n_jobs); }
 void lcd_launch_bam_cigar(const GatherJob *jobs, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_cigar_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, n_jobs); }
+void lcd_launch_bam_aux(const BamAuxJob *jobs, BamAuxOut *outs, int is_ont, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_aux_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, outs, is_ont, n_jobs); }
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_errrate_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, st, jobs, tab, out, n_jobs); }

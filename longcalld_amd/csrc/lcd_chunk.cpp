@@ -2,6 +2,7 @@
 // indexed BAM, the host's view of it and the (region, read) slices cut in HBM.  The struct itself is in lcd_host_internal.h.
 #include <cmath>
 #include "lcd_host_internal.h"
+#include "tag_words.h"
 
 using namespace lcd_internal;
 
@@ -22,6 +23,8 @@ struct DigarWords {
     int clip_rule = 0; const int64_t *rlen_true = nullptr; const int *pre_status = nullptr;
     const int *n_indel = nullptr; // with counts: how many of the window events are insertions / deletions (tighter window capacity)
     uint64_t d_qual_base = 0;   // != 0: the qualities are already in HBM (qual_off relative to this address; qual_pool unused)
+    // a chunk that mixes the four sources (lcd_chunk_create_from_bam_src): per read the device address of its words (they lie in several pools) and its clip rule
+    const uint64_t *addr = nullptr; const int *clip_rule_r = nullptr;
 };
 // keep: the digars stay in HBM (a device-resident chunk, lcd_chunk_t): `keep->d_dig` receives them, nothing of them is downloaded, *digars_out stays NULL and
 // keep->slot / keep->n_digar say where read r's digars are (record index into d_dig, count)
@@ -42,11 +45,11 @@ int digar_batch_core(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, con
         if (W.counts) { nd = W.counts[r].nd; nev = W.counts[r].nev; if (W.n_indel) nid = W.n_indel[r]; }
         else { nid = 0; for (int i = 0; i < n_cigar[r]; ++i) { const uint32_t c = cigar_pool[cigar_off[r] + i]; const int op = c & 0xf, len = (int)(c >> 4); if (op == 8) { nd += len; nev += len; } else if (op != 3 && op != 9) { ++nd; if (op == 1 || op == 2) { ++nev; ++nid; } } } }
         j.n_cigar = n_cigar[r]; j.qlen = qlen[r]; j.pos0 = pos0[r]; j.left_pal = pal_flags ? pal_flags[r] & 1 : 0; j.right_pal = pal_flags ? (pal_flags[r] >> 1) & 1 : 0;
-        j.digar_cap = (int)nd; j.ev_cap = (int)nev + 1; j.clip_rule = W.clip_rule;
+        j.digar_cap = (int)nd; j.ev_cap = (int)nev + 1; j.clip_rule = W.clip_rule_r ? W.clip_rule_r[r] : W.clip_rule;
         // windows are disjoint and each holds events of total weight > max_xgaps (a mismatch weighs 1, an insertion / deletion its length): at most one per
         // indel event plus one per max_xgaps + 1 mismatches, plus the two clip flanks
         j.iv_cap = (int)(nid >= 0 ? nid + (nev - nid) / (opt->noisy_reg_max_xgaps + 1) : nev) + 4;
-        j.cigar_off = cigar_off[r] * 4; j.qual_off = qual_off[r];
+        j.cigar_off = W.addr ? W.addr[r] : cigar_off[r] * 4; j.qual_off = qual_off[r];
         j.digar_off = dtot * sizeof(DigarRec); dtot += nd; j.iv_off = itot * sizeof(IvRec); itot += j.iv_cap; j.ev_off = etot * 16; etot += j.ev_cap;
     }
     DevBuf d_cig, d_qual, d_jobs, d_outs, d_dig_local, d_iv, d_ev;
@@ -54,7 +57,7 @@ int digar_batch_core(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, con
     if ((!W.d_words && d_cig.ensure(cig_words * 4 + 64)) || (!W.d_qual_base && d_qual.ensure(qual_bytes + 64)) || d_jobs.ensure(n * sizeof(DigarJob)) || d_outs.ensure(n * sizeof(DigarOut)) ||
         d_dig.ensure(dtot * sizeof(DigarRec) + 64) || d_iv.ensure(itot * sizeof(IvRec) + 64) || d_ev.ensure(etot * 16 + 64)) return -11;
     const uint64_t cig_base = W.d_words ? W.d_words->addr() : d_cig.addr();
-    for (DigarJob &j : jobs) { j.cigar_off += cig_base; j.qual_off += W.d_qual_base ? W.d_qual_base : d_qual.addr(); j.digar_off += d_dig.addr(); j.iv_off += d_iv.addr(); j.ev_off += d_ev.addr(); }
+    for (DigarJob &j : jobs) { if (!W.addr) j.cigar_off += cig_base; j.qual_off += W.d_qual_base ? W.d_qual_base : d_qual.addr(); j.digar_off += d_dig.addr(); j.iv_off += d_iv.addr(); j.ev_off += d_ev.addr(); }
     if (!W.d_words) HIPCHK(hipMemcpyAsync(d_cig.p, cigar_pool, cig_words * 4, hipMemcpyHostToDevice, st));
     if (!W.d_qual_base) HIPCHK(hipMemcpyAsync(d_qual.p, qual_pool, qual_bytes, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), n * sizeof(DigarJob), hipMemcpyHostToDevice, st));
@@ -107,63 +110,8 @@ int digar_batch_core(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, con
     return 0;
 }
 
-// ---- host side of the cs / MD paths: the tag strings are O(events) long, so they are parsed here into EQX-shaped operation words ----
-inline bool is_alpha(char c) { return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'); }
-inline bool is_digit(char c) { return c >= '0' && c <= '9'; }
-inline uint32_t opw(long long len, int op) { return ((uint32_t)len << 4) | (uint32_t)op; }
-// collect_digar_from_cs_tag, src/bam_utils.c:876-976: clips from the first / last CIGAR operation, everything else from the cs string
-bool cs_to_words(const uint32_t *cig, int n_cigar, const char *cs, std::vector<uint32_t> &w) {
-    if (n_cigar <= 0 || !cs) return false;
-    if ((cig[0] & 0xf) == 4 || (cig[0] & 0xf) == 5) w.push_back(cig[0]);
-    while (*cs) {
-        if (*cs == ':') { char *e; const long len = strtol(cs + 1, &e, 10); if (e == cs + 1 || len < 0) return false; cs = e; w.push_back(opw(len, 7)); }
-        else if (*cs == '=' || *cs == '+' || *cs == '-') { const int op = *cs == '=' ? 7 : *cs == '+' ? 1 : 2; ++cs; long len = 0; while (is_alpha(*cs)) { ++len; ++cs; } w.push_back(opw(len, op)); }
-        else if (*cs == '*') { if (!cs[1] || !cs[2]) return false; w.push_back(opw(1, 8)); cs += 3; }
-        else if (*cs == '~') { ++cs; while (is_alpha(*cs) || is_digit(*cs)) ++cs; }   // intron: stepped over without moving pos (:951-953)
-        else return false;                                                             // the reference exits (:955)
-    }
-    const uint32_t last = cig[n_cigar - 1];
-    if ((last & 0xf) == 4 || (last & 0xf) == 5) w.push_back(last);
-    return true;
-}
-// collect_digar_from_MD_tag, src/bam_utils.c:1035-1134: 'M' operations split by the MD string ('=' runs that may continue over an insertion into the
-// next 'M', one 'X' per letter), deletions step over "^LETTERS", a "0" after either is skipped
-bool md_to_words(const uint32_t *cig, int n_cigar, const char *md0, std::vector<uint32_t> &w) {
-    if (!md0) return false;
-    const char *md = md0, *md_end = md0 + strlen(md0); long md_i = 0;
-    auto at = [&](long k) -> char { const char *q = md + k; return (q >= md0 && q < md_end) ? *q : '\0'; };
-    long last_eq = 0;
-    for (int i = 0; i < n_cigar; ++i) {
-        const int op = cig[i] & 0xf; const long len = cig[i] >> 4;
-        if (op == 0) {
-            long m = len;
-            while (1) {
-                if (last_eq > 0) {
-                    if (last_eq >= m) { w.push_back(opw(m, 7)); last_eq -= m; m = 0; }
-                    else { w.push_back(opw(last_eq, 7)); m -= last_eq; md_i = 0; last_eq = 0; }
-                } else if (is_digit(at(md_i))) {
-                    char *e; long eq = strtol(md + md_i, &e, 10); md = e;
-                    bool emit = true;
-                    if (eq > m) { last_eq = eq - m; eq = m; }
-                    else if (eq == 0) { md_i = 0; emit = false; }
-                    if (emit) { w.push_back(opw(eq, 7)); m -= eq; md_i = 0; }
-                    else continue;
-                } else if (is_alpha(at(md_i))) {
-                    w.push_back(opw(1, 8)); m -= 1;
-                    if (at(md_i + 1) == '\0' || at(md_i + 1) != '0') md_i++; else md_i += 2;
-                } else return false;                                                   // "MD and CIGAR do not match": the reference exits (:1088)
-                if (m <= 0) break;
-            }
-        } else if (op == 2) {
-            w.push_back(cig[i]);
-            md_i++;
-            while (at(md_i) && is_alpha(at(md_i))) md_i++;
-            if (at(md_i) == '0') md_i++;
-        } else if (op == 1 || op == 4 || op == 5 || op == 3) w.push_back(cig[i]);
-        else if (op == 7 || op == 8) return false;                                     // '=' / 'X' next to an MD tag: the reference exits (:1134)
-    }
-    return true;
-}
+// (the host side of the cs / MD paths, cs_to_words / md_to_words: tag_words.h)
+using lcd_tag_words::cs_to_words; using lcd_tag_words::md_to_words;
 } // namespace
 
 int lcd_digar_batch(const lcd_digar_opt_t *opt, int n, const int64_t *pos0, const uint32_t *cigar_pool, const uint64_t *cigar_off, const int *n_cigar,
@@ -215,8 +163,13 @@ lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n, const int64_t *
 // (htslib: bgzf_read_block, inflate, bam_read1) and the record loop of collect_ref_seq_bam_main (src/bam_utils.c:1672-1706) followed by
 // collect_digar_from_eqx_cigar (:701-842) do for the reference on the calling thread.  The host sees 40 + 40 bytes per record (descriptor, CIGAR statistics),
 // never a base, a quality or a digar.  Records, filters, order and stop rule are lcd_bam_load_region_indexed's (Collector::take).
-lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
-                                       int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
+//
+// With `src` every read gets the source the reference would choose for it (collect_digar_from_bam, src/collect_var.c:1072-1079): lcd_bam_aux_kernel hops the kept
+// records' auxiliary fields in HBM; reads compared with the reference go through the lcd_refcmp_kernel passes on the CIGAR words and the 4-bit bases where the
+// inflate left them; the cs / MD VALUES (O(events) bytes, the only record bytes that cross PCIe) come to the host, are parsed by cs_to_words / md_to_words and go
+// back as EQX-shaped words; ONE digar launch covers all reads.  src == NULL is lcd_chunk_create_from_bam as it always was.
+lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
+                                           int min_mapq, int verify_crc, const lcd_chunk_src_t *src, lcd_bam_reads_t *meta) {
     if (meta) memset(meta, 0, sizeof(*meta));
     if (ensure_init()) return nullptr;
     LcdRegionImage im;
@@ -282,6 +235,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *b
     }
     // 3. the loader's rule, record by record in file order (Collector::take in lcd_io.cpp)
     std::vector<int64_t> pos0, endp; std::vector<int> mapq, flag, ncig, qlen; std::vector<uint64_t> coff, soff, qoff, noff; std::vector<RefCmpOut> counts; std::vector<int> nindel; std::vector<GatherJob> gj, nj;
+    std::vector<BamAuxJob> auxj; std::vector<int64_t> rl_true;   // (src only)
     uint64_t cw = 0, nbytes = 0; bool done = false;
     const char *malformed = "malformed BAM record (a field runs past the record, or a placeholder CIGAR without its CG tag)";
     for (int k = 0; k < nr && !done; ++k) {
@@ -299,6 +253,10 @@ lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *b
             soff.push_back(sq); qoff.push_back(sq + ((uint64_t)d.lseq + 1) / 2);
             coff.push_back(cw); { GatherJob g; g.src = x.cig_src; g.dst = cw * 4; g.bytes = (uint32_t)x.nc * 4u; g.pad_ = 0; gj.push_back(g); } cw += (uint64_t)x.nc;
             RefCmpOut rc; rc.n_ops = x.nc; rc.nd = (int)x.nd; rc.nev = (int)x.nev; rc.pad = 0; counts.push_back(rc); nindel.push_back((int)x.nid);
+            if (src) {
+                BamAuxJob a; a.rec = base + d.off; a.cig = x.cig_src; a.bs = d.bs; a.lname = d.lname; a.nc16 = d.nc; a.lseq = d.lseq; a.nc = x.nc; a.flag = d.flag; a.prim_pos = (long long)d.pos + 1; a.prim_end = e0;
+                auxj.push_back(a); rl_true.push_back(x.rl);
+            }
             noff.push_back(nbytes); { GatherJob g; g.src = base + d.off + 32; g.dst = nbytes; g.bytes = d.lname; g.pad_ = 0; nj.push_back(g); } nbytes += d.lname;
         }
         if (!done) {
@@ -334,20 +292,141 @@ lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *b
         // (cigar_pool / seq_pool / qual_pool stay NULL: those bytes are in HBM; seq_off / qual_off are offsets of the inflated stream)
     }
     if (n == 0) return c.release();
+    auto drop_meta = [&]() { if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } }; // (the caller's arrays were handed out above)
+    // 3b. the reads' sources: what the words of the digar launch are made from
+    std::vector<uint8_t> pal; std::vector<int> pre, clip, nw; std::vector<uint64_t> waddr;
+    DevBuf d_aj, d_ao, d_ref, d_rj, d_rc, d_rw, d_tg, d_tpool, d_tw;
+    double t0 = now_ms();
+    if (src) {
+        c->source.assign(n, 0); c->pal.assign(n, 0); pal.assign(n, 0); pre.assign(n, 0); clip.assign(n, 0); nw = ncig; waddr.resize(n);
+        std::vector<BamAuxOut> ao(n);
+        if (d_aj.ensure((size_t)n * sizeof(BamAuxJob)) || d_ao.ensure((size_t)n * sizeof(BamAuxOut))) { drop_meta(); return nullptr; }
+#define CHKM(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); drop_meta(); return fail(-10, "HIP call failed: " #x); } } while (0)
+        CHKM(hipMemcpyAsync(d_aj.p, auxj.data(), (size_t)n * sizeof(BamAuxJob), hipMemcpyHostToDevice, st));
+        lcd_launch_bam_aux((const BamAuxJob *)d_aj.p, (BamAuxOut *)d_ao.p, src->is_ont != 0, n, st);
+        CHKM(hipGetLastError());
+        CHKM(hipMemcpyAsync(ao.data(), d_ao.p, (size_t)n * sizeof(BamAuxOut), hipMemcpyDeviceToHost, st));
+        CHKM(hipStreamSynchronize(st));
+        c->stage_ms[0] = now_ms() - t0; t0 = now_ms();
+        const bool have_ref = src->ref_seq && src->ref_end >= src->ref_beg;
+        std::vector<int> ref_reads, tag_reads;
+        for (int r = 0; r < n; ++r) {
+            c->source[r] = ao[r].source; c->pal[r] = ao[r].pal != 0; pal[r] = ao[r].pal; waddr[r] = d_cig.addr() + coff[r] * 4;
+            // a read compared with the reference needs the window, and a CIGAR that consumes exactly the record's bases (the comparison reads them in place)
+            if (ao[r].source == LCD_SRC_REF) { if (!have_ref || ao[r].cig_qlen != (long long)qlen[r]) pre[r] = 1; else ref_reads.push_back(r); }
+            else if (ao[r].source != LCD_SRC_EQX) { if (ao[r].bad_type) pre[r] = 1; else tag_reads.push_back(r); }
+        }
+        if (!ref_reads.empty()) {
+            const int m = (int)ref_reads.size(); const uint64_t ref_len = (uint64_t)(src->ref_end - src->ref_beg + 1);
+            if (d_ref.ensure(ref_len + 64) || d_rj.ensure((size_t)m * sizeof(RefCmpJob)) || d_rc.ensure((size_t)m * sizeof(RefCmpOut))) { drop_meta(); return nullptr; }
+            std::vector<RefCmpJob> rj(m); std::vector<RefCmpOut> cnt(m);
+            for (int k = 0; k < m; ++k) { const int r = ref_reads[k]; RefCmpJob &j = rj[k]; j.cigar_off = waddr[r]; j.seq_off = base + soff[r]; j.out_off = 0; j.n_cigar = ncig[r]; j.pad = 0; j.pos0 = pos0[r]; }
+            CHKM(hipMemcpyAsync(d_ref.p, src->ref_seq, ref_len, hipMemcpyHostToDevice, st));
+            CHKM(hipMemcpyAsync(d_rj.p, rj.data(), (size_t)m * sizeof(RefCmpJob), hipMemcpyHostToDevice, st));
+            lcd_launch_refcmp(false, (const RefCmpJob *)d_rj.p, (RefCmpOut *)d_rc.p, (const char *)d_ref.p, src->ref_beg, src->ref_end, m, st);
+            CHKM(hipGetLastError());
+            CHKM(hipMemcpyAsync(cnt.data(), d_rc.p, (size_t)m * sizeof(RefCmpOut), hipMemcpyDeviceToHost, st));
+            CHKM(hipStreamSynchronize(st));
+            uint64_t tot = 0;
+            for (int k = 0; k < m; ++k) tot += (uint64_t)cnt[k].n_ops;
+            if (d_rw.ensure(tot * 4 + 64)) { drop_meta(); return nullptr; }
+            tot = 0;
+            for (int k = 0; k < m; ++k) { const int r = ref_reads[k]; rj[k].out_off = d_rw.addr() + tot * 4; waddr[r] = rj[k].out_off; nw[r] = cnt[k].n_ops; counts[r] = cnt[k]; tot += (uint64_t)cnt[k].n_ops; }
+            CHKM(hipMemcpyAsync(d_rj.p, rj.data(), (size_t)m * sizeof(RefCmpJob), hipMemcpyHostToDevice, st));
+            lcd_launch_refcmp(true, (const RefCmpJob *)d_rj.p, (RefCmpOut *)d_rc.p, (const char *)d_ref.p, src->ref_beg, src->ref_end, m, st);
+            CHKM(hipGetLastError());
+            CHKM(hipStreamSynchronize(st));
+        }
+        c->stage_ms[1] = now_ms() - t0; t0 = now_ms();
+        std::vector<uint32_t> words;
+        if (!tag_reads.empty()) {
+            // one pool: per read its CIGAR words (4-byte aligned), then the tag value with its NUL
+            const int m = (int)tag_reads.size();
+            std::vector<GatherJob> tj(2 * (size_t)m); std::vector<uint64_t> at_cig(m), at_tag(m);
+            uint64_t tb = 0;
+            for (int k = 0; k < m; ++k) {
+                const int r = tag_reads[k];
+                at_cig[k] = tb; tj[2 * k] = GatherJob{waddr[r], tb, (uint32_t)ncig[r] * 4u, 0}; tb += (uint64_t)ncig[r] * 4;
+                at_tag[k] = tb; tj[2 * k + 1] = GatherJob{ao[r].tag, tb, ao[r].tag_len + 1u, 0}; tb = lcd_align_up(tb + ao[r].tag_len + 1, 4);
+                c->tag_bytes += ao[r].tag_len;
+            }
+            if (d_tpool.ensure(tb + 64) || d_tg.ensure(tj.size() * sizeof(GatherJob))) { drop_meta(); return nullptr; }
+            for (GatherJob &g : tj) g.dst += d_tpool.addr();
+            std::vector<uint8_t> hp(tb + 4);
+            CHKM(hipMemcpyAsync(d_tg.p, tj.data(), tj.size() * sizeof(GatherJob), hipMemcpyHostToDevice, st));
+            lcd_launch_gather((const GatherJob *)d_tg.p, (int)tj.size(), st);
+            CHKM(hipGetLastError());
+            CHKM(hipMemcpyAsync(hp.data(), d_tpool.p, tb, hipMemcpyDeviceToHost, st));
+            CHKM(hipStreamSynchronize(st));
+            std::vector<uint64_t> woff(m);
+            for (int k = 0; k < m; ++k) {
+                const int r = tag_reads[k];
+                const uint32_t *cig = (const uint32_t *)(hp.data() + at_cig[k]); char *tag = (char *)(hp.data() + at_tag[k]);
+                tag[ao[r].tag_len] = 0;
+                woff[k] = words.size();
+                const bool ok = ao[r].source == LCD_SRC_CS ? cs_to_words(cig, ncig[r], tag, words) : md_to_words(cig, ncig[r], tag, words);
+                if (!ok) { pre[r] = 1; words.resize(woff[k]); }     // the reference stops the program here: status -2, no digars
+                long long nd = 0, nev = 0, nid = 0;                 // (lcd_digar_batch's capacity pass)
+                for (size_t i = woff[k]; i < words.size(); ++i) { const uint32_t w = words[i]; const int op = w & 0xf, len = (int)(w >> 4); if (op == 8) { nd += len; nev += len; } else if (op != 3 && op != 9) { ++nd; if (op == 1 || op == 2) { ++nev; ++nid; } } }
+                nw[r] = (int)(words.size() - woff[k]); counts[r].n_ops = nw[r]; counts[r].nd = (int)nd; counts[r].nev = (int)nev; nindel[r] = (int)nid;
+                clip[r] = ao[r].source == LCD_SRC_CS;
+            }
+            words.push_back(0);
+            if (d_tw.ensure(words.size() * 4 + 64)) { drop_meta(); return nullptr; }
+            CHKM(hipMemcpyAsync(d_tw.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+            for (int k = 0; k < m; ++k) waddr[tag_reads[k]] = d_tw.addr() + woff[k] * 4;
+        }
+        for (int r = 0; r < n; ++r) if (pre[r] && c->source[r] != LCD_SRC_EQX) { nw[r] = 0; counts[r].n_ops = counts[r].nd = counts[r].nev = 0; nindel[r] = 0; }
+        CHKM(hipStreamSynchronize(st));   // (`words` leaves scope below)
+#undef CHKM
+        c->stage_ms[2] = now_ms() - t0; t0 = now_ms();
+    }
     // 4. digars, kept in HBM; bases and qualities are read in place
     c->qlen = qlen; c->seq_off = soff; c->qual_off = qoff; c->seq_base = base; c->qual_base = base;
     c->status.resize(n); c->n_cand.resize(n); c->beg.resize(n); c->end.resize(n);
     DigarWords W; W.off = coff.data(); W.n_cigar = ncig.data(); W.d_words = &d_cig; W.counts = counts.data(); W.n_indel = nindel.data(); W.d_qual_base = base;
+    if (src) { W.n_cigar = nw.data(); W.addr = waddr.data(); W.clip_rule_r = clip.data(); W.rlen_true = rl_true.data(); W.pre_status = pre.data(); }
     DigarKeep keep; keep.d_dig = &c->d_dig;
     uint64_t *doff = nullptr; lcd_digar_t *dg = nullptr;
-    const int rc = digar_batch_core(opt, n, pos0.data(), W, nullptr, qoff.data(), qlen.data(), nullptr, reg_beg, reg_end, im.tlen, &doff, &dg, &c->iv_off, &c->ivs, &c->iv_in_chunk,
+    const int rc = digar_batch_core(opt, n, pos0.data(), W, nullptr, qoff.data(), qlen.data(), src ? pal.data() : nullptr, reg_beg, reg_end, im.tlen, &doff, &dg, &c->iv_off, &c->ivs, &c->iv_in_chunk,
                                     c->status.data(), c->beg.data(), c->end.data(), c->n_cand.data(), st, &keep);
     free(doff);
     if (rc) { if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return nullptr; } // (the caller's arrays were handed out above)
     if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return fail(-10, "HIP call failed: hipStreamSynchronize"); }
 #undef CHK
     c->slot.swap(keep.slot); c->n_digar.swap(keep.n_digar);
+    if (src) c->stage_ms[3] = now_ms() - t0;
     return c.release();
+}
+lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
+                                       int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
+    return lcd_chunk_create_from_bam_src(opt, bam_path, bai_path, chrom, reg_beg, reg_end, min_mapq, verify_crc, nullptr, meta);
+}
+// per read the source the reference would choose (LCD_SRC_*; a chunk made without `src`: LCD_SRC_EQX), chunk->is_ont_palindrome, and the cs / MD bytes that came
+// to the host when the chunk was made
+int lcd_chunk_read_sources(const lcd_chunk_t *c, uint8_t *source, uint8_t *is_ont_palindrome, uint64_t *tag_bytes_d2h) {
+    for (int r = 0; r < c->n_reads; ++r) { if (source) source[r] = c->source.empty() ? LCD_SRC_EQX : c->source[r]; if (is_ont_palindrome) is_ont_palindrome[r] = c->pal.empty() ? 0 : c->pal[r]; }
+    if (tag_bytes_d2h) *tag_bytes_d2h = c->tag_bytes;
+    return c->n_reads;
+}
+void lcd_chunk_stage_ms(const lcd_chunk_t *c, double out[4]) { for (int k = 0; k < 4; ++k) out[k] = c->stage_ms[k]; }
+// the chunk's digars as lcd_digar_batch returns them (tests and debugging: everything else reads them in HBM)
+int lcd_chunk_digars(const lcd_chunk_t *c, uint64_t **digar_off, lcd_digar_t **digars) {
+    *digar_off = nullptr; *digars = nullptr;
+    if (use_device(c->device)) return -1;
+    const int n = c->n_reads;
+    uint64_t span = 0, tot = 0;
+    for (int r = 0; r < n; ++r) { span = std::max<uint64_t>(span, c->slot[r] + (uint64_t)c->n_digar[r]); tot += (uint64_t)c->n_digar[r]; }
+    if (span * sizeof(DigarRec) > c->d_dig.cap) return set_err(-4, "lcd_chunk_digars: digar slots outside the chunk's buffer");
+    std::vector<DigarRec> h(span + 1);
+    if (span) { HIPCHK(hipMemcpy(h.data(), c->d_dig.p, span * sizeof(DigarRec), hipMemcpyDeviceToHost)); g_copy_bytes[0] += span * sizeof(DigarRec); }
+    uint64_t *off = (uint64_t *)malloc(((size_t)n + 1) * sizeof(uint64_t)); lcd_digar_t *dg = (lcd_digar_t *)malloc((tot + 1) * sizeof(lcd_digar_t));
+    if (!off || !dg) { free(off); free(dg); return set_err(-11, "lcd_chunk_digars: out of memory"); }
+    uint64_t w = 0;
+    for (int r = 0; r < n; ++r) { off[r] = w; if (c->n_digar[r]) memcpy(dg + w, h.data() + c->slot[r], (size_t)c->n_digar[r] * sizeof(DigarRec)); w += (uint64_t)c->n_digar[r]; }
+    off[n] = w;
+    *digar_off = off; *digars = dg;
+    return n;
 }
 void lcd_chunk_destroy(lcd_chunk_t *c) { delete c; }
 int lcd_chunk_n_reads(const lcd_chunk_t *c) { return c ? c->n_reads : 0; }

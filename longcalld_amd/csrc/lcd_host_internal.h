@@ -239,6 +239,8 @@ struct lcd_chunk_s {
     std::vector<uint64_t> slot, seq_off; std::vector<int> n_digar, qlen;
     std::vector<uint8_t> h_qual; std::vector<uint64_t> qual_off;   // host copy: the sampling rule of >= 10 kb regions reads qualities on the host (src/seq.c:429)
     std::vector<int> status, n_cand; std::vector<int64_t> beg, end;
+    std::vector<uint8_t> source, pal; uint64_t tag_bytes = 0;   // lcd_chunk_create_from_bam_src: LCD_SRC_* and is_ont_palindrome per read; cs / MD bytes brought to the host
+    double stage_ms[4] = {0, 0, 0, 0};                          // ... and its wall-clock split: aux fields, reference comparison, tag download + host parse, digars
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use

@@ -18,6 +18,7 @@ void lcd_launch_anchor_ends(const AnchorEndsJob *jobs, AnchorEndsOut *outs, int 
 void lcd_launch_bam_walk(const BamWalkJob *jobs, BamWalkOut *outs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_stat(const BamStatJob *jobs, BamStatOut *outs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_cigar(const GatherJob *jobs, int n_jobs, hipStream_t st);
+void lcd_launch_bam_aux(const BamAuxJob *jobs, BamAuxOut *outs, int is_ont, int n_jobs, hipStream_t st);
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st);
 void lcd_launch_compose(const CmpJob *jobs, CmpOut *outs, const CmpSeg *segs, int n_jobs, int emit, hipStream_t stream);
 void lcd_launch_vars_scan(const VarScanJob *jobs, VarScanOut *outs, int n_jobs, hipStream_t stream);

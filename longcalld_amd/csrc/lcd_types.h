@@ -225,6 +225,12 @@ struct BamRecDesc { uint64_t off; int bs, refid, pos, lseq; uint16_t flag, nc; u
 struct BamWalkOut { int n, status; uint64_t next; };   // status 0 range done, 1 truncated record, 2 a field runs past the record, 3 descriptor capacity, 4 stopped at the first record at / behind reg_end
 struct BamStatJob { uint64_t rec; int bs, lname, nc, lseq; };
 struct BamStatOut { long long rl, nd, nev, nid; uint64_t cig_src; int nc, kind; };   // kind 0 the record's own CIGAR, 1 the CG tag's, -2 placeholder without its tag; cig_src: where the operations are
+// lcd_bam_aux_kernel: one kept record.  rec as BamStatJob; cig / nc: the operations the record is read with (BamStatOut::cig_src / nc: its own or its CG tag's);
+// nc16: the record's 16-bit n_cigar_op (where its auxiliary block starts); prim_pos / prim_end: pos0 + 1 and bam_endpos (the SA rule's primary interval)
+struct BamAuxJob { uint64_t rec, cig; int bs, lname, nc16, lseq, nc, flag; long long prim_pos, prim_end; };
+// source: LCD_SRC_*; tag / tag_len: the cs / MD value (device address, strlen) of a CS / MD read; pal: DigarJob's left (bit 0) / right (bit 1) palindrome flags;
+// bad_type: the deciding cs / MD field is not of type Z; cig_qlen: query bases of the CIGAR (reads that are not EQX only, else 0)
+struct BamAuxOut { uint64_t tag; uint32_t tag_len; uint8_t source, pal, bad_type, pad; long long cig_qlen; };
 struct ErrJob { uint64_t qual; int len, pad; };
 struct EdJob {
     uint64_t q_off, t_off;
