@@ -429,6 +429,18 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
                                            int64_t reg_beg, int64_t reg_end, int min_mapq, int verify_crc,
                                            const lcd_chunk_src_t *src, struct lcd_bam_reads_t *meta);
 int lcd_chunk_read_sources(const lcd_chunk_t *c, uint8_t *source, uint8_t *is_ont_palindrome, uint64_t *tag_bytes_d2h);
+/* chunk->ordered_read_ids: sort_chunk_reads (src/bam_utils.c:1616-1656) orders a chunk's reads by position, then end DESCENDING, then the NM tag, then the read name;
+ * a coordinate-sorted BAM fixes only the first key, and the pile-up, K5 and collect_noisy_reg_reads1 all walk the reads in this order.
+ * lcd_chunk_read_nm: bam_get_NM (:1632-1639) per kept read of a chunk made from a BAM, computed on the records in the inflated stream in HBM (one lane per record;
+ *   4 bytes per read come back).  The auxiliary fields are hopped as bam_aux_get hops them: a field that runs past the record ends the walk.  The first field named
+ *   NM gives the value for the types c C s S i I (an I above 2^31 - 1 wraps: the reference stores bam_aux2i's result in an int).  PROJECT RULE: any other type
+ *   gives 0 and no NM field gives 0 (htslib's bam_aux2i is not part of the reference checkout; this is its documented behaviour: 0 with errno EINVAL).
+ *   Returns n_reads, or -4 for a chunk that was not made from a BAM (its records never existed on the device).
+ * lcd_sort_chunk_reads: comp_bam_read_sort on flat arrays, pure host code (no device needed): pos0 ascending, end_pos descending, nm ascending, strcmp of
+ *   name_pool + name_off[i] (lcd_bam_reads_t's fields).  PROJECT RULE: entries equal in all four keys keep file order (qsort leaves their order unspecified).
+ *   order_out[k] = the read at rank k.  Returns n or < 0. */
+int lcd_chunk_read_nm(const lcd_chunk_t *c, int *nm_out);
+int lcd_sort_chunk_reads(int n, const int64_t *pos0, const int64_t *end_pos, const int *nm, const uint64_t *name_off, const char *name_pool, int *order_out);
 void lcd_chunk_stage_ms(const lcd_chunk_t *c, double out[4]);
 int lcd_chunk_digars(const lcd_chunk_t *c, uint64_t **digar_off, lcd_digar_t **digars);   /* malloc()'d CSR copy; counted in lcd_copy_counters[0] */
 void lcd_chunk_destroy(lcd_chunk_t *c);
@@ -629,6 +641,9 @@ typedef struct lcd_clean_vars_t {
     uint64_t *allele_off; int *alleles, *alt_qi;     /* n_reads + 1 offsets; end - start + 1 entries per read with a profile */
     int n_cr; int *cr_read;                          /* chunk->read_var_cr labels in cr_index order */
     uint64_t qual_upload_bytes;                      /* quality bytes this call uploaded (a host-array chunk's first call; else 0) */
+    uint8_t *alt_ref_base;                           /* cand_var_t.alt_ref_base per variant: the base make_variants writes in front of a gap record's ALT when it is not 4
+                                                      * (src/collect_var.c:1544).  4 = unknown for every first-round variant (:44); see lcd_merge_region_vars.  Last member:
+                                                      * a table built by an older caller (NULL here) counts as all 4 wherever the library reads it */
 } lcd_clean_vars_t;
 int lcd_chunk_clean_vars(const lcd_chunk_t *c, const lcd_clean_opt_t *opt, const int *ordered_read_ids, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
                          int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre_regs, const int64_t *low_comp, int n_low,
@@ -653,6 +668,9 @@ int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int 
  *                   emitted, on equality the table's entry stays and the region's is dropped.  A kept table entry carries all its fields; a kept region entry
  *                   takes pos, var_type, ref_len, alt_len, cate, total_cov, alle_covs, is_homopolymer_indel and alt_seq from its lcd_noisy_var_t, and its
  *                   low_qual_cov and strand_alle_covs are 0: make_cand_vars0 (:1746) clears the whole cand_var_t and the noisy-region pass never counts them.
+ *                   alt_ref_base: a kept table entry carries its value (all 4 when cur->alt_ref_base is NULL); a kept region entry follows make_cand_vars0's
+ *                   rule (:1755-1756: `if (var_type == BAM_CDIFF) var->ref_base = ref_base; else var->alt_ref_base = alt_ref_base;` on the cleared struct):
+ *                   0 for an X variant, lcd_noisy_var_t.alt_ref_base for an insertion / deletion.
  *   profile         per chunk read (skipped reads: (-1, -2), no cells): every cell of its current span moves to the merged index of its variant, every cell of
  *                   its row's span in a region (prof_start >= 0 and prof_end >= prof_start) to the merged index of that region variant with alt_qi = -1, unless
  *                   the variant was dropped (the old allele at the equal variant stays); start / end = min / max of the moved indices, cells nobody moved are
@@ -756,6 +774,72 @@ typedef struct lcd_rounds_chunk_t {
     int *done; int n_passes; int n_first_vars; int *first_to_final;   /* out */
 } lcd_rounds_chunk_t;
 int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt);
+
+/* ---- the head of collect_var_main (src/collect_var.c:2897-2945) for a pipeline step's device chunks (one device): from the chunk handles to "first round done",
+ * i.e. to the lcd_rounds_chunk_t fields lcd_chunks_noisy_rounds takes.  Per chunk, in the reference's order:
+ *   order        ordered_read_ids as given (copied), or -- NULL -- sort_chunk_reads from meta (pos0, end_pos, names) + lcd_chunk_read_nm + lcd_sort_chunk_reads:
+ *                that needs a chunk made from a BAM and its meta, else -4;
+ *   is_skipped   is_skipped[r] = the chunk's status of read r != 0.  The reference has ONE writer of is_skipped on this path, collect_digars_from_bam
+ *                (src/collect_var.c:1081: `if (ret < 0)`), and every collect_digar_from_* failure is negative: status -1 (too noisy) and -2 (no usable source) both
+ *                skip the read, everywhere from pre_process_noisy_regs (:586) on;
+ *   low_comp     chunk->low_comp_cr (src/bam_utils.c:1573-1581): sdust (T 5, W 20) over the reference bases of [reg_beg, reg_end] -- NOT of the whole window -- as
+ *                (reg_beg + start - 1, reg_beg + finish - 1) pairs; all chunks in one lcd_sdust_batch.  A region reaching outside [ref_beg, ref_end] is cut to it;
+ *   pre_regs     pre_process_noisy_regs (:557-638) from the handle: the windows of the reads that are not skipped, in ordered_read_ids order (the order
+ *                collect_digars_from_bam cr_add()s them in), filtered by iv_in_chunk; index, low-complexity extension and cr_merge on the host; the read support
+ *                of ALL chunks' regions in one upload, one launch on one stream and one synchronisation; kept when noisy >= opt->min_alt_dp and
+ *                noisy / total >= (float)opt->min_af;
+ *   vars         lcd_chunk_clean_vars_batch (is_rev as given, or meta->flag & 16 when is_rev is NULL and meta is given, else all forward);
+ *   state        lcd_hap_state_init; for the chunks with n_vars > 0 (:2934) lcd_clean_vars_hap_problem and ONE lcd_assign_hap_batch over
+ *                LONGCALLD_CLEAN_HET_SNP | LONGCALLD_CLEAN_HET_INDEL | LONGCALLD_CLEAN_HOM_VAR (:2944).  A chunk without variants keeps the initial state; one
+ *                without variants and regions (:2932) or without reads is legal and comes back empty.
+ * Every out member is malloc()'d and released by lcd_first_round_free (vars and state are single malloc()'d structs: hand `vars` / `state` to lcd_rounds_chunk_t as
+ * they are).  Malformed input -- a NULL chunk / reference, ref_end < ref_beg, a region outside [1, ..], an ordered_read_ids entry outside [0, n_reads) or twice,
+ * chunks on different devices -- returns < 0 before anything is launched; opt->out_somatic returns -2.  On a failure of any stage everything allocated is freed,
+ * the out members are NULL / 0 and the stage's error is returned.  No digar and no base crosses PCIe. */
+typedef struct lcd_first_chunk_t {
+    const lcd_chunk_t *chunk;                                        /* in */
+    const uint8_t *ref_seq; int64_t ref_beg, ref_end;                /* codes 0-4 or letters, ref_seq[0] = position ref_beg (1-based), ref_end inclusive */
+    int64_t reg_beg, reg_end; int is_ont;
+    const int *ordered_read_ids; const uint8_t *is_rev;              /* both may be NULL */
+    const struct lcd_bam_reads_t *meta;                              /* may be NULL when ordered_read_ids is given */
+    int n_reads; int *order; uint8_t *is_skipped;                    /* out: chunk->ordered_read_ids, chunk->is_skipped */
+    int n_low; int64_t *low_comp;                                    /* out: (start, end) pairs */
+    int n_pre_regs; lcd_noisy_iv_t *pre_regs;                        /* out: pre_process_noisy_regs' regions, index order */
+    lcd_clean_vars_t *vars; lcd_hap_state_t *state;                  /* out */
+} lcd_first_chunk_t;
+int lcd_chunks_first_round(int n_chunks, lcd_first_chunk_t *chunks, const lcd_clean_opt_t *opt);
+void lcd_first_round_free(lcd_first_chunk_t *c);
+
+/* ---- the whole germline path in one call: chunks -> stitched genotype records and VCF body lines ----
+ * lcd_chunks_call: n chunks of ONE contig in genome order (one device).  Runs lcd_chunks_first_round, lcd_chunks_noisy_rounds, lcd_stitch_chunks
+ * (stitch_var_main, src/collect_var.c:2983-2989), per chunk lcd_make_variants on its own [reg_beg, reg_end] + lcd_annotate_te without a TE library, and
+ * lcd_format_vcf over the records concatenated in chunk order (merge_vars appends, :2996-2998).
+ *   in           chunks[c].first's input members, as for lcd_chunks_first_round; ref_seq as CODES 0-4 (lcd_chunks_noisy_rounds reads them as codes);
+ *   stitch       the overlap lists of chunk c are its reads, in file order, whose [beg, end] (digar beg / end = pos0 + 1, bam_endpos) overlaps the previous
+ *                (up) / next (down) chunk's [reg_beg, reg_end] by the test of is_ovlp_with_prev_region / _next_region (src/bam_utils.c:1586-1614:
+ *                !(read_end < reg_beg || read_beg > reg_end)).  Reads the loader's flag / MAPQ filter dropped never reach a chunk, so only the kept lists
+ *                exist.  update_reads = 1: the reads' haplotypes and phase sets are final (what lcd_read_tags takes).  Two neighbours that do not hold the
+ *                same number of shared reads return -6, as the reference exits;
+ *   out          chunks[c].first's out members, with vars / state = the FINAL table and K5 state (state->haps / phase_sets after the stitch); n_passes of the
+ *                noisy-region loop; flip_hap / flip_pre_PS / flip_cur_PS of the stitch (0 / -1 / -1 for a chunk that was not joined); n_records = how many
+ *                of the records are this chunk's (they are consecutive).  *records (lcd_var1_t.cand_i indexes the chunk's final table), *vcf_body.
+ * cfg->clean.out_somatic or cfg->opt.collect_ref_read_aln_str (somatic / refine) return -2.  On failure everything is freed and the outputs are NULL / 0.
+ * lcd_call_free releases the chunks' out members, the records and the text (it does not destroy the chunk handles).
+ * lcd_call_bam_regions: the file-level wrapper for n regions of one contig in genome order.  Per region: a first device pass (lcd_chunk_create_from_bam with
+ * meta) gives the reads' span; the reference window is fetched around min(reg_beg, read begins) / max(reg_end, read ends) with get_bam_chunk_reg_ref_seq0's
+ * 50 000-base padding (src/bam_utils.c:1558-1571) -- the reference, too, loads first and fetches then; when the pass left a read without a digar source (an 'M'
+ * CIGAR: status -2) or the data is ONT (the SA-tag rule), the chunk is made again through lcd_chunk_create_from_bam_src with that window.  Then lcd_chunks_call;
+ * the chunk handles are destroyed before the call returns (chunks[c].first.chunk / ref_seq / meta are NULL afterwards).  chunks: n caller-allocated entries. */
+typedef struct lcd_cfg_t { lcd_clean_opt_t clean; lcd_opt_t opt; lcd_pass_opt_t pass; lcd_call_opt_t call; } lcd_cfg_t;
+void lcd_cfg_default(lcd_cfg_t *cfg, int is_ont);   /* lcd_clean_opt_default(is_ont), lcd_opt_default + is_ont, lcd_pass_opt_default, lcd_call_opt_default */
+typedef struct lcd_call_chunk_t {
+    lcd_first_chunk_t first;
+    int n_passes, flip_hap; int64_t flip_pre_PS, flip_cur_PS; int n_records;   /* out */
+} lcd_call_chunk_t;
+int lcd_chunks_call(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body);
+int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
+                         const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body);
+void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_records, char *vcf_body);
 
 #ifdef __cplusplus
 }

@@ -100,7 +100,7 @@ class LcdCleanVars(C.Structure):
                 ("low_qual_cov", _i32p), ("alle_covs", _i32p), ("strand_alle_covs", _i32p), ("alt_off", _u64p), ("alt_pool", _u8p),
                 ("is_homopolymer_indel", _i32p), ("n_regs", C.c_int), ("regs", C.POINTER(LcdNoisyIv)), ("n_reads", C.c_int), ("start_var_idx", _i32p),
                 ("end_var_idx", _i32p), ("allele_off", _u64p), ("alleles", _i32p), ("alt_qi", _i32p), ("n_cr", C.c_int), ("cr_read", _i32p),
-                ("qual_upload_bytes", C.c_uint64)]
+                ("qual_upload_bytes", C.c_uint64), ("alt_ref_base", _u8p)]
 
 
 class LcdRegionVars(C.Structure):
@@ -136,6 +136,40 @@ class LcdRoundsChunk(C.Structure):
                 ("done", C.POINTER(C.c_int)), ("n_passes", C.c_int), ("n_first_vars", C.c_int), ("first_to_final", C.POINTER(C.c_int))]
 
 
+class LcdFirstChunk(C.Structure):
+    """lcd_first_chunk_t: one chunk of lcd_chunks_first_round"""
+    _fields_ = [("chunk", C.c_void_p), ("ref_seq", C.POINTER(C.c_uint8)), ("ref_beg", C.c_int64), ("ref_end", C.c_int64), ("reg_beg", C.c_int64), ("reg_end", C.c_int64),
+                ("is_ont", C.c_int), ("ordered_read_ids", C.POINTER(C.c_int)), ("is_rev", C.POINTER(C.c_uint8)), ("meta", C.POINTER(LcdBamReads)),
+                ("n_reads", C.c_int), ("order", C.POINTER(C.c_int)), ("is_skipped", C.POINTER(C.c_uint8)), ("n_low", C.c_int), ("low_comp", C.POINTER(C.c_int64)),
+                ("n_pre_regs", C.c_int), ("pre_regs", C.POINTER(LcdNoisyIv)), ("vars", C.POINTER(LcdCleanVars)), ("state", C.POINTER(LcdHapState))]
+
+
+class LcdCallOpt(C.Structure):
+    """lcd_call_opt_t"""
+    _fields_ = [("log_p", C.c_double), ("log_1p", C.c_double), ("log_2", C.c_double)] + [(n, C.c_int) for n in ("max_gq", "max_qual", "min_sv_len", "min_dp", "min_alt_dp",
+                                                                                                                 "out_amb_base")]
+
+
+class LcdCfg(C.Structure):
+    """lcd_cfg_t: the option structs of the whole path"""
+    _fields_ = [("clean", LcdCleanOpt), ("opt", LcdOpt), ("pass_", LcdPassOpt), ("call", LcdCallOpt)]
+
+
+class LcdVar1(C.Structure):
+    """lcd_var1_t: one genotype record"""
+    _u8p = C.POINTER(C.c_uint8)
+    _fields_ = [("pos", C.c_int64), ("PS", C.c_int64), ("type", C.c_int), ("ref_len", C.c_int), ("n_alt_allele", C.c_int), ("alt_len", C.c_int * 2),
+                ("ref_bases", _u8p), ("alt_bases", _u8p * 2), ("GT", C.c_int * 2), ("DP", C.c_int), ("AD", C.c_int * 3), ("QUAL", C.c_int), ("GQ", C.c_int),
+                ("is_sv", C.c_int), ("is_clean", C.c_int), ("n_alt_reads", C.c_int), ("alt_read_i", C.POINTER(C.c_int)),
+                ("cand_i", C.c_int), ("tsd_len", C.c_int), ("polya_len", C.c_int), ("te_seq_i", C.c_int), ("te_is_rev", C.c_int), ("tsd_pos1", C.c_int64),
+                ("tsd_pos2", C.c_int64), ("tsd_seq", _u8p)]
+
+
+class LcdCallChunk(C.Structure):
+    """lcd_call_chunk_t: one chunk of lcd_chunks_call / one region of lcd_call_bam_regions"""
+    _fields_ = [("first", LcdFirstChunk), ("n_passes", C.c_int), ("flip_hap", C.c_int), ("flip_pre_PS", C.c_int64), ("flip_cur_PS", C.c_int64), ("n_records", C.c_int)]
+
+
 _lib = None
 
 # every symbol include/lcd_hotpath.h declares (tests check the .so exports all of them)
@@ -150,6 +184,8 @@ EXPORTS = [
     "lcd_merge_region_vars", "lcd_merge_region_vars_batch", "lcd_sort_noisy_regs",
     "lcd_pass_opt_default", "lcd_chunk_plan_pass", "lcd_chunk_plan_pass_batch", "lcd_pass_plan_free", "lcd_batch_region_n_cons", "lcd_batch_add_planned",
     "lcd_hap_state_init", "lcd_hap_state_carry", "lcd_hap_state_free", "lcd_chunks_noisy_rounds",
+    "lcd_chunk_read_nm", "lcd_sort_chunk_reads", "lcd_chunks_first_round", "lcd_first_round_free",
+    "lcd_cfg_default", "lcd_chunks_call", "lcd_call_bam_regions", "lcd_call_free",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -250,6 +286,18 @@ def load_library():
     lib.lcd_hap_state_free.argtypes = [C.POINTER(LcdHapState)]
     lib.lcd_hap_state_free.restype = None
     lib.lcd_chunks_noisy_rounds.argtypes = [C.c_int, C.POINTER(LcdRoundsChunk), C.POINTER(LcdOpt), C.POINTER(LcdPassOpt)]
+    lib.lcd_chunk_read_nm.argtypes = [C.c_void_p, i32p]
+    lib.lcd_sort_chunk_reads.argtypes = [C.c_int, i64p, i64p, i32p, u64p_, C.c_char_p, i32p]
+    lib.lcd_chunks_first_round.argtypes = [C.c_int, C.POINTER(LcdFirstChunk), C.POINTER(LcdCleanOpt)]
+    lib.lcd_first_round_free.argtypes = [C.POINTER(LcdFirstChunk)]
+    lib.lcd_first_round_free.restype = None
+    lib.lcd_cfg_default.argtypes = [C.POINTER(LcdCfg), C.c_int]
+    lib.lcd_cfg_default.restype = None
+    lib.lcd_chunks_call.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdCfg), C.c_char_p, C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p)]
+    lib.lcd_call_bam_regions.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, i64p, i64p, C.c_int, C.POINTER(LcdCfg), C.POINTER(LcdCallChunk),
+                                         C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p)]
+    lib.lcd_call_free.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdVar1), C.c_int, C.c_void_p]
+    lib.lcd_call_free.restype = None
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]
     lib.lcd_batch_digest.argtypes = [C.c_void_p]

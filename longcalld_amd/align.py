@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (LcdAlnStr, LcdBatchStats, LcdCleanOpt, LcdCleanVars, LcdDigar, LcdDigar1, LcdDigarOpt, LcdNoisyIv, LcdNoisyVar, LcdOpt, LcdReadView, check,
+from ._lib import (LcdAlnStr, LcdBatchStats, LcdCleanOpt, LcdCleanVars, LcdDigar, LcdDigar1, LcdDigarOpt, LcdError, LcdNoisyIv, LcdNoisyVar, LcdOpt, LcdReadView, check,
                    load_library)
 
 _libc = C.CDLL(None)
@@ -855,6 +855,33 @@ def assign_hap_batch(probs, target_var_cates, states=None):
     return states
 
 
+# ---------------- chunk->ordered_read_ids: the NM tags of a BAM chunk's records and sort_chunk_reads ----------------
+def chunk_read_nm(chunk):
+    """lcd_chunk_read_nm: bam_get_NM per kept read of a DeviceChunk made from a BAM, computed on the records in HBM; LcdError (-4) for a host-array chunk"""
+    lib = load_library()
+    n = int(chunk.n)
+    nm = np.zeros(max(1, n), np.int32)
+    check(lib.lcd_chunk_read_nm(chunk.h, nm.ctypes.data_as(i32p)), lib)
+    return nm[:n].copy()
+
+
+def sort_chunk_reads(pos0, end_pos, nm, names):
+    """lcd_sort_chunk_reads (sort_chunk_reads, src/bam_utils.c:1616-1656; host code): pos ascending, end descending, NM ascending, strcmp of the names, file order
+    on a full tie -> the read ids in that order.  names: bytes / str per read."""
+    lib = load_library()
+    n = len(pos0)
+    pos0 = np.ascontiguousarray(pos0, np.int64); end_pos = np.ascontiguousarray(end_pos, np.int64); nm = np.ascontiguousarray(nm, np.int32)
+    raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+    off = np.zeros(max(1, n), np.uint64); pool = bytearray()
+    for i, x in enumerate(raw):
+        off[i] = len(pool); pool += x + b"\0"
+    order = np.zeros(max(1, n), np.int32)
+    z = lambda a, dt: a if a.size else np.zeros(1, dt)
+    check(lib.lcd_sort_chunk_reads(n, z(pos0, np.int64).ctypes.data_as(C.POINTER(C.c_int64)), z(end_pos, np.int64).ctypes.data_as(C.POINTER(C.c_int64)),
+                                   z(nm, np.int32).ctypes.data_as(i32p), off.ctypes.data_as(C.POINTER(C.c_uint64)), bytes(pool) + b"\0", order.ctypes.data_as(i32p)), lib)
+    return order[:n].copy()
+
+
 # ---------------- the first round of collect_var_main on a device-resident chunk (lcd_chunk_clean_vars) ----------------
 def clean_opt(is_ont=0, **kw):
     """lcd_clean_opt_t with the defaults of src/call_var_main.c (HiFi or ONT); keyword arguments override fields"""
@@ -874,7 +901,8 @@ def clean_vars_dict(v):
     alt_off = arr(v.alt_off, V + 1, np.uint64) if v.alt_off else np.zeros(1, np.uint64)
     aoff = arr(v.allele_off, R + 1, np.uint64) if v.allele_off else np.zeros(1, np.uint64)
     regs = np.array([(v.regs[i].start, v.regs[i].end, v.regs[i].label) for i in range(v.n_regs)], np.int64).reshape(-1, 3)
-    return dict(n_vars=V, pos=arr(v.pos, V, np.int64), var_type=arr(v.var_type, V, np.int32), ref_len=arr(v.ref_len, V, np.int32), alt_len=arr(v.alt_len, V, np.int32),
+    arb = getattr(v, "alt_ref_base", None)    # (the test oracle's struct ends before this member; a NULL member counts as all 4)
+    return dict(alt_ref_base=arr(arb, V, np.uint8) if arb else np.full(V, 4, np.uint8), n_vars=V, pos=arr(v.pos, V, np.int64), var_type=arr(v.var_type, V, np.int32), ref_len=arr(v.ref_len, V, np.int32), alt_len=arr(v.alt_len, V, np.int32),
                 cate=arr(v.cate, V, np.int32), total_cov=arr(v.total_cov, V, np.int32), low_qual_cov=arr(v.low_qual_cov, V, np.int32),
                 alle_covs=arr(v.alle_covs, 2 * V, np.int32), strand_alle_covs=arr(v.strand_alle_covs, 4 * V, np.int32), alt_off=alt_off,
                 alt_pool=arr(v.alt_pool, int(alt_off[-1]), np.uint8), is_homopolymer_indel=arr(v.is_homopolymer_indel, V, np.int32), regs=regs, n_reads=R,
@@ -978,6 +1006,8 @@ def _clean_vars_struct(cv, keep):
               "end_var_idx", "alleles", "alt_qi", "cr_read"):
         setattr(v, k, P(cv[k], np.int32, C.c_int))
     v.alt_off = P(cv["alt_off"], np.uint64, C.c_uint64); v.allele_off = P(cv["allele_off"], np.uint64, C.c_uint64); v.alt_pool = P(cv["alt_pool"], np.uint8, C.c_uint8)
+    if cv.get("alt_ref_base") is not None:      # (absent: the member stays NULL = all 4)
+        v.alt_ref_base = P(cv["alt_ref_base"], np.uint8, C.c_uint8)
     regs = np.asarray(cv["regs"], np.int64).reshape(-1, 3)
     ra = (LcdNoisyIv * max(1, len(regs)))(*[LcdNoisyIv(int(x[0]), int(x[1]), int(x[2]), 0) for x in regs])
     keep.append(ra)
@@ -996,6 +1026,8 @@ def _region_vars_array(regions, keep):
             x = va[i]
             x.pos, x.var_type, x.ref_len, x.alt_len, x.cate = int(g["pos"][i]), int(g["var_type"][i]), int(g["ref_len"][i]), int(g["alt_len"][i]), int(g["cate"][i])
             x.is_homopolymer_indel, x.total_cov = int(g["is_homopolymer_indel"][i]), int(g["total_cov"][i])
+            if "alt_ref_base" in g:
+                x.alt_ref_base = int(g["alt_ref_base"][i])
             x.alle_covs[0], x.alle_covs[1] = int(g["alle_covs"][i][0]), int(g["alle_covs"][i][1])
             a = np.ascontiguousarray(g["alt_seqs"][i], np.uint8)
             if a.size:
@@ -1207,6 +1239,8 @@ def _clean_vars_struct_malloc(cv):
         setattr(v, k, _malloc_copy(np.asarray(cv[k], np.int32), C.c_int))
     v.alt_off = _malloc_copy(np.asarray(cv["alt_off"], np.uint64), C.c_uint64); v.allele_off = _malloc_copy(np.asarray(cv["allele_off"], np.uint64), C.c_uint64)
     v.alt_pool = _malloc_copy(np.asarray(cv["alt_pool"], np.uint8), C.c_uint8)
+    if cv.get("alt_ref_base") is not None:
+        v.alt_ref_base = _malloc_copy(np.asarray(cv["alt_ref_base"], np.uint8), C.c_uint8)
     regs = np.asarray(cv["regs"], np.int64).reshape(-1, 3)
     flat = np.zeros((max(1, len(regs)), 3), np.int64)    # lcd_noisy_iv_t: int64 start, end | int32 label, pad
     flat[:len(regs), :2] = regs[:, :2]; flat.view(np.int32).reshape(len(flat), 6)[:len(regs), 4] = regs[:, 2]
@@ -1251,3 +1285,139 @@ def chunks_noisy_rounds(chunks, items, opt=None, popt=None):
                 if p:
                     _libc.free(C.cast(p, C.c_void_p))
     return res
+
+
+# ---------------- the head of collect_var_main on device-resident chunks (lcd_chunks_first_round) ----------------
+def _bam_reads_struct(meta, keep):
+    """DeviceChunk.meta -> LcdBamReads with the members the read order and the strands need (pos0, end_pos, flag, names)"""
+    from ._lib import LcdBamReads
+    m = LcdBamReads()
+    n = len(meta["pos0"])
+    pos0 = np.ascontiguousarray(meta["pos0"], np.int64); end = np.ascontiguousarray(meta["end_pos"], np.int64); flag = np.ascontiguousarray(meta["flag"], np.int32)
+    off = np.zeros(max(1, n), np.uint64); pool = bytearray()
+    for i, x in enumerate(meta["names"]):
+        off[i] = len(pool); pool += (x.encode() if isinstance(x, str) else bytes(x)) + b"\0"
+    buf = C.create_string_buffer(bytes(pool) + b"\0")
+    z = lambda a, dt: a if a.size else np.zeros(1, dt)
+    pos0, end, flag = z(pos0, np.int64), z(end, np.int64), z(flag, np.int32)
+    keep += [pos0, end, flag, off, buf]
+    m.n_reads = n
+    m.pos0 = pos0.ctypes.data_as(C.POINTER(C.c_int64)); m.end_pos = end.ctypes.data_as(C.POINTER(C.c_int64)); m.flag = flag.ctypes.data_as(i32p)
+    m.name_off = off.ctypes.data_as(C.POINTER(C.c_uint64)); m.name_pool = C.cast(buf, C.POINTER(C.c_char))
+    return m
+
+
+def _fill_first_chunk(x, ch, it, keep):
+    """the input members of an lcd_first_chunk_t from a DeviceChunk and an item dict (see chunks_first_round)"""
+    ref = np.ascontiguousarray(it["ref"], np.uint8)
+    keep.append(ref)
+    x.chunk = None if ch is None else ch.h
+    x.ref_seq = _p8(ref); x.ref_beg = int(it["ref_beg"]); x.ref_end = int(it.get("ref_end", int(it["ref_beg"]) + len(ref) - 1))
+    x.reg_beg, x.reg_end, x.is_ont = int(it["reg_beg"]), int(it["reg_end"]), int(it.get("is_ont", 0))
+    if it.get("ordered_read_ids") is not None:
+        o = np.ascontiguousarray(it["ordered_read_ids"], np.int32)
+        o = o if o.size else np.zeros(1, np.int32)
+        keep.append(o); x.ordered_read_ids = o.ctypes.data_as(i32p)
+    if it.get("is_rev") is not None:
+        r = np.ascontiguousarray(it["is_rev"], np.uint8)
+        r = r if r.size else np.zeros(1, np.uint8)
+        keep.append(r); x.is_rev = _p8(r)
+    if it.get("meta", True) and ch is not None and getattr(ch, "meta", None) is not None:
+        m = _bam_reads_struct(ch.meta, keep)
+        keep.append(m); x.meta = C.pointer(m)
+
+
+def _first_chunk_dict(x):
+    """the out members of an lcd_first_chunk_t -> dict(ordered_read_ids, is_skipped, low_comp (n, 2), pre_regs (n, 3), cv, state)"""
+    R = x.n_reads
+    take = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(k,)).astype(dt).copy() if k > 0 else np.zeros(0, dt)
+    return dict(ordered_read_ids=take(x.order, R, np.int32), is_skipped=take(x.is_skipped, R, np.uint8), low_comp=take(x.low_comp, 2 * x.n_low, np.int64).reshape(-1, 2),
+                pre_regs=np.array([(x.pre_regs[k].start, x.pre_regs[k].end, x.pre_regs[k].label) for k in range(x.n_pre_regs)], np.int64).reshape(-1, 3),
+                cv=clean_vars_dict(x.vars.contents), state=_hap_state_dict(x.state.contents))
+
+
+def chunks_first_round(chunks, items, opt=None):
+    """lcd_chunks_first_round: DeviceChunks -> "first round done" in one call.  items[i] = dict(ref (codes), ref_beg, reg_beg, reg_end, is_ont (0), ordered_read_ids
+    (None: sort_chunk_reads from the chunk's meta and its NM tags), is_rev (None: from meta's flags when meta is used, else all forward), meta (True: hand the chunk's
+    .meta to the library when it has one), ref_end (default ref_beg + len(ref) - 1)) -> list of dict(ordered_read_ids, is_skipped, low_comp (n, 2), pre_regs (n, 3),
+    cv = clean_vars_dict, state = K5 state dict)"""
+    from ._lib import LcdFirstChunk
+    lib = load_library()
+    opt = opt if opt is not None else clean_opt()
+    n = len(chunks)
+    keep = []
+    arr = (LcdFirstChunk * max(1, n))()
+    for i, (ch, it) in enumerate(zip(chunks, items)):
+        _fill_first_chunk(arr[i], ch, it, keep)
+    rc = lib.lcd_chunks_first_round(n, arr, C.byref(opt))
+    res = []
+    try:
+        check(rc, lib)
+        res = [_first_chunk_dict(arr[i]) for i in range(n)]
+    finally:
+        for i in range(n):
+            lib.lcd_first_round_free(C.byref(arr[i]))
+    return res
+
+
+# ---------------- chunks -> stitched genotype records and VCF body lines (lcd_chunks_call, lcd_call_bam_regions) ----------------
+def call_cfg(is_ont=0, clean=None, opt=None, pass_=None, call=None):
+    """lcd_cfg_t with lcd_cfg_default's values; the keyword dicts override fields of the four option structs"""
+    from ._lib import LcdCfg
+    cfg = LcdCfg()
+    load_library().lcd_cfg_default(C.byref(cfg), int(is_ont))
+    for part, kw in (("clean", clean), ("opt", opt), ("pass_", pass_), ("call", call)):
+        for k, v in (kw or {}).items():
+            setattr(getattr(cfg, part), k, v)
+    return cfg
+
+
+def _var1_dict(v):
+    return dict(cand_i=v.cand_i, pos=v.pos, PS=v.PS, type=v.type, ref_len=v.ref_len, n_alt=v.n_alt_allele, alt_len=list(v.alt_len)[:v.n_alt_allele],
+                ref=bytes(v.ref_bases[j] for j in range(v.ref_len)), alt=[bytes(v.alt_bases[a][j] for j in range(v.alt_len[a])) for a in range(v.n_alt_allele)],
+                GT=list(v.GT), DP=v.DP, AD=list(v.AD), QUAL=v.QUAL, GQ=v.GQ, is_sv=v.is_sv, is_clean=v.is_clean, alt_reads=[v.alt_read_i[j] for j in range(v.n_alt_reads)],
+                tsd=bytes(v.tsd_seq[j] for j in range(v.tsd_len)), polya_len=v.polya_len, te_seq_i=v.te_seq_i, te_is_rev=v.te_is_rev, tsd_pos1=v.tsd_pos1, tsd_pos2=v.tsd_pos2)
+
+
+def _call_result(lib, n, arr, recs, n_recs, text):
+    try:
+        chunks = []
+        for i in range(n):
+            d = _first_chunk_dict(arr[i].first)
+            d.update(n_passes=int(arr[i].n_passes), flip_hap=int(arr[i].flip_hap), flip_pre_PS=int(arr[i].flip_pre_PS), flip_cur_PS=int(arr[i].flip_cur_PS),
+                     n_records=int(arr[i].n_records), haps=d["state"]["haps"], phase_sets=d["state"]["phase_sets"])
+            chunks.append(d)
+        return dict(chunks=chunks, records=[_var1_dict(recs[i]) for i in range(n_recs.value)], vcf_body=C.string_at(text).decode() if text else "")
+    finally:
+        lib.lcd_call_free(n, arr, recs, n_recs.value, text)
+
+
+def chunks_call(chunks, items, cfg=None, chrom="chr11"):
+    """lcd_chunks_call: DeviceChunks of one contig in genome order -> dict(chunks = per chunk the first-round dict with cv / state FINAL plus n_passes, flip_hap,
+    flip_pre_PS, flip_cur_PS, n_records, haps, phase_sets; records = genotype records as dicts in chunk order; vcf_body).  items as for chunks_first_round."""
+    from ._lib import LcdCallChunk, LcdVar1
+    lib = load_library()
+    cfg = cfg if cfg is not None else call_cfg()
+    n = len(chunks)
+    keep = []
+    arr = (LcdCallChunk * max(1, n))()
+    for i, (ch, it) in enumerate(zip(chunks, items)):
+        _fill_first_chunk(arr[i].first, ch, it, keep)
+    recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
+    check(lib.lcd_chunks_call(n, arr, C.byref(cfg), chrom.encode(), C.byref(recs), C.byref(n_recs), C.byref(text)), lib)
+    return _call_result(lib, n, arr, recs, n_recs, text)
+
+
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None):
+    """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call"""
+    from ._lib import LcdCallChunk, LcdVar1
+    lib = load_library()
+    cfg = cfg if cfg is not None else call_cfg()
+    n = len(reg_beg)
+    arr = (LcdCallChunk * max(1, n))()
+    rb = (C.c_int64 * max(1, n))(*[int(x) for x in reg_beg]); re_ = (C.c_int64 * max(1, n))(*[int(x) for x in reg_end])
+    recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
+    enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+    check(lib.lcd_call_bam_regions(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
+                                   C.byref(text)), lib)
+    return _call_result(lib, n, arr, recs, n_recs, text)

@@ -6,6 +6,7 @@
 //                         lcd_digar_batch's host pass makes), the CG:B,I tag behind the placeholder CIGAR of a read with more than 65 535 operations;
 //   lcd_bam_aux_kernel    one wavefront per kept record: the digar source the reference would choose for it (EQX CIGAR / cs / MD / reference comparison), where
 //                         its cs / MD value lies, and the SA tag's palindrome test of ONT reads;
+//   lcd_bam_nm_kernel     one lane per kept record: the value of its first NM field (bam_get_NM, src/bam_utils.c:1632-1639), a key of the chunk's read order;
 //   lcd_bam_cigar_kernel  the kept records' CIGAR words -> a 4-byte aligned pool (records sit at any byte offset of the stream);
 //   lcd_errrate_kernel    calc_read_error_rate (src/seq.c:429-436) of a read slice on the qualities in HBM: the same table values added in the same order as the
 //                         host loop, so the doubles are the host's.
@@ -243,6 +244,66 @@ __global__ void __launch_bounds__(64) lcd_bam_aux_kernel(const BamAuxJob *jobs, 
     }
 }
 
+// ---- lcd_bam_nm_kernel: bam_get_NM (src/bam_utils.c:1632-1639) of a kept record, the third key of sort_chunk_reads (:1641).  One lane per record: tens of fields,
+// about 1 000 records per chunk.  The fields are hopped exactly as lcd_bam_aux_kernel hops them -- a field that runs past the record ends the walk and what lies
+// behind it does not exist -- and the first field named NM decides: types c C s S i I give their value (an I above 2^31 - 1 wraps, as the reference's int does),
+// any other type gives 0 (bam_aux2i), no NM field gives 0. ----
+namespace {
+// offset of the first NUL in [p, end), or -1, one lane: aligned words (the stream buffer is padded behind its end), the bytes in front of p masked out
+__device__ __forceinline__ long long lane_find_nul(const uint8_t *p, const uint8_t *end) {
+    if (p >= end) return -1;
+    const uintptr_t a = (uintptr_t)p;
+    const unsigned *q = (const unsigned *)(a & ~(uintptr_t)3);
+    const long long n = end - p;
+    long long at = -(long long)(a & 3);                    // offset (relative to p) of the word's first byte
+    unsigned w = *q | ((1u << (8 * (unsigned)(a & 3))) - 1u);   // (a & 3) low bytes forced non-zero
+    for (;;) {
+        const unsigned z = (w - 0x01010101u) & ~w & 0x80808080u;   // the lowest set bit marks the first zero byte
+        if (z) { const long long i = at + ((__ffs((int)z) - 1) >> 3); return i < n ? i : -1; }
+        at += 4;
+        if (at >= n) return -1;
+        w = *++q;
+    }
+}
+} // namespace
+__global__ void __launch_bounds__(64) lcd_bam_nm_kernel(const BamNmJob *jobs, int *nm, const int n_jobs) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n_jobs) return;
+    const BamNmJob j = jobs[i];
+    const uint8_t *aux = (const uint8_t *)(uintptr_t)j.aux, *end = (const uint8_t *)(uintptr_t)j.end;
+    int v = 0;
+    while (aux + 3 <= end) {
+        const unsigned h = ld32u(aux);
+        const uint8_t t0 = (uint8_t)(h & 0xff), t1 = (uint8_t)((h >> 8) & 0xff), ty = (uint8_t)((h >> 16) & 0xff); aux += 3;
+        size_t sz = 0; bool bad = false;
+        if (ty == 'A' || ty == 'c' || ty == 'C') sz = 1;
+        else if (ty == 's' || ty == 'S') sz = 2;
+        else if (ty == 'i' || ty == 'I' || ty == 'f') sz = 4;
+        else if (ty == 'Z' || ty == 'H') { const long long zl = lane_find_nul(aux, end); if (zl < 0) bad = true; else sz = (size_t)zl + 1; }
+        else if (ty == 'B') {
+            if (aux + 5 > end) bad = true;
+            else {
+                const uint8_t sub = aux[0]; const unsigned cnt = ld32u(aux + 1);
+                const size_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : 0;
+                if (!es || (size_t)(end - (aux + 5)) < (size_t)cnt * es) bad = true;
+                else sz = 5 + (size_t)cnt * es;
+            }
+        } else bad = true;
+        if (bad || (size_t)(end - aux) < sz) break;
+        if (t0 == 'N' && t1 == 'M') {
+            const unsigned w = ld32u(aux);
+            if (ty == 'c') v = (int)(signed char)(w & 0xff);
+            else if (ty == 'C') v = (int)(w & 0xff);
+            else if (ty == 's') v = (int)(short)(w & 0xffff);
+            else if (ty == 'S') v = (int)(w & 0xffff);
+            else if (ty == 'i' || ty == 'I') v = (int)w;
+            break;
+        }
+        aux += sz;
+    }
+    nm[i] = v;
+}
+
 // e = sum over the slice of 10^(-q / 10), in slice order, divided by the length: tab[q] is the host's pow(10.0, -q / 10.0)
 __global__ void __launch_bounds__(64) lcd_errrate_kernel(const ErrJob *jobs, const double *tab, double *out, const int n_jobs) {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -262,4 +323,5 @@ void lcd_launch_bam_walk(const BamWalkJob *jobs, BamWalkOut *outs, int n_jobs, h
 void lcd_launch_bam_stat(const BamStatJob *jobs, BamStatOut *outs, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_stat_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, outs, n_jobs); }
 void lcd_launch_bam_cigar(const GatherJob *jobs, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_cigar_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, n_jobs); }
 void lcd_launch_bam_aux(const BamAuxJob *jobs, BamAuxOut *outs, int is_ont, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_aux_kernel, dim3(n_jobs), dim3(64), 0, st, jobs, outs, is_ont, n_jobs); }
+void lcd_launch_bam_nm(const BamNmJob *jobs, int *nm, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_bam_nm_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, st, jobs, nm, n_jobs); }
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st) { if (n_jobs > 0) hipLaunchKernelGGL(lcd_errrate_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, st, jobs, tab, out, n_jobs); }

@@ -233,6 +233,34 @@ void lcd_launch_region_support(const IvRec *regs, int n_regs, const long long *r
     if (n_regs > 0) hipLaunchKernelGGL(lcd_region_support_kernel, dim3(n_regs), dim3(64), 0, stream, regs, n_regs, read_beg, read_end, iv_off, ivs, n_reads, total, noisy);
 }
 
+// the same for the regions of ALL chunks of a pipeline step in one grid (lcd_chunks_first_round): every region names its chunk, whose kept reads (skipped ones left
+// out by the host) and their windows lie in one staged block.  One wavefront per region, as above.
+__global__ void __launch_bounds__(64) lcd_region_support_batch_kernel(const SupChunk *chunks, const SupReg *regs, int n_regs, int *total, int *noisy) {
+    const int ri = blockIdx.x;
+    if (ri >= n_regs) return;
+    const int lane = threadIdx.x;
+    const SupReg g = regs[ri];
+    const SupChunk c = chunks[g.chunk];
+    const long long *read_beg = (const long long *)(uintptr_t)c.read_beg, *read_end = (const long long *)(uintptr_t)c.read_end;
+    const unsigned long long *iv_off = (const unsigned long long *)(uintptr_t)c.iv_off;
+    const IvRec *ivs = (const IvRec *)(uintptr_t)c.ivs;
+    const long long rs = g.st, re = g.en;
+    int tot = 0, nz = 0;
+    for (int r = lane; r < c.n_reads; r += 64) {
+        const long long qb = read_beg[r] - 1, qe = read_end[r];
+        if (!(rs < qe && qb < re)) continue;
+        ++tot;
+        int hit = 0;
+        for (unsigned long long k = iv_off[r]; k < iv_off[r + 1] && !hit; ++k) hit = ivs[k].st < re && rs < ivs[k].en;
+        nz += hit;
+    }
+    for (int d = 32; d >= 1; d >>= 1) { tot += __shfl_xor(tot, d); nz += __shfl_xor(nz, d); }
+    if (lane == 0) { total[ri] = tot; noisy[ri] = nz; }
+}
+void lcd_launch_region_support_batch(const SupChunk *chunks, const SupReg *regs, int n_regs, int *total, int *noisy, hipStream_t stream) {
+    if (n_regs > 0) hipLaunchKernelGGL(lcd_region_support_batch_kernel, dim3(n_regs), dim3(64), 0, stream, chunks, regs, n_regs, total, noisy);
+}
+
 // collect_noisy_read_info's digar walk (src/align.c:1392-1441), one wavefront per (region, read) pair: lcd_slice_walk (slice_walk.h, shared with plan_kernel.hip)
 __global__ void __launch_bounds__(64) lcd_slice_kernel(const SliceJob *jobs, SliceOut *outs, const DigarRec *digars, const int flank, const int n_jobs) {
     const int ji = blockIdx.x, lane = threadIdx.x;

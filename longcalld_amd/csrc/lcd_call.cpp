@@ -1,0 +1,158 @@
+// lcd_call.cpp -- the germline path joined end to end: lcd_chunks_call (first round, noisy-region rounds, cross-chunk stitch, genotype records, VCF body lines
+// for a pipeline step's chunks of one contig) and lcd_call_bam_regions (the same from an indexed BAM and a FASTA).  Every stage is an export of its own
+// (lcd_first_round.cpp, lcd_chunk_vars.cpp, lcd_emit.cpp, lcd_chunk.cpp, lcd_io.cpp); this file only composes them as collect_var_main / stitch_var_main /
+// make_var_main do (src/collect_var.c:2897-3000).
+#include "lcd_host_internal.h"
+
+using namespace lcd_internal;
+
+extern "C" {
+
+void lcd_cfg_default(lcd_cfg_t *cfg, int is_ont) {
+    lcd_clean_opt_default(&cfg->clean, is_ont); lcd_opt_default(&cfg->opt); cfg->opt.is_ont = is_ont != 0; lcd_pass_opt_default(&cfg->pass); lcd_call_opt_default(&cfg->call);
+}
+
+void lcd_call_free(int n, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_records, char *vcf_body) {
+    for (int c = 0; chunks && c < n; ++c) { lcd_first_round_free(&chunks[c].first); chunks[c].n_passes = chunks[c].flip_hap = chunks[c].n_records = 0; chunks[c].flip_pre_PS = chunks[c].flip_cur_PS = -1; }
+    lcd_free_variants(records, n_records);
+    free(vcf_body);
+}
+
+int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body) {
+    const std::string W = "lcd_chunks_call";
+    if (records) *records = nullptr;
+    if (n_records) *n_records = 0;
+    if (vcf_body) *vcf_body = nullptr;
+    if (!records || !n_records || !vcf_body || !cfg || !chrom) return set_err(-4, W + ": NULL argument");
+    if (n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": bad chunk list");
+    if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
+    for (int c = 0; c < n; ++c) { lcd_call_chunk_t &x = chunks[c]; x.n_passes = x.flip_hap = x.n_records = 0; x.flip_pre_PS = x.flip_cur_PS = -1; }
+    // 1. the head of collect_var_main
+    std::vector<lcd_first_chunk_t> f(n);
+    for (int c = 0; c < n; ++c) f[c] = chunks[c].first;
+    int rc = lcd_chunks_first_round(n, f.data(), &cfg->clean);
+    for (int c = 0; c < n; ++c) chunks[c].first = f[c];      // (on failure the out members are NULL / 0)
+    if (rc) return rc;
+    auto fail = [&](int code) { const std::string m = g_err; lcd_call_free(n, chunks, nullptr, 0, nullptr); g_err = m; return code; };
+    // 2. the noisy-region loop
+    {
+        std::vector<lcd_rounds_chunk_t> r(n);
+        for (int c = 0; c < n; ++c) {
+            const lcd_first_chunk_t &x = chunks[c].first;
+            memset(&r[c], 0, sizeof(lcd_rounds_chunk_t));
+            r[c].chunk = x.chunk; r[c].vars = x.vars; r[c].state = x.state; r[c].ordered_read_ids = x.order; r[c].is_skipped = x.is_skipped;
+            r[c].ref_seq = x.ref_seq; r[c].ref_beg = x.ref_beg; r[c].ref_end = x.ref_end; r[c].is_ont = x.is_ont;
+        }
+        rc = lcd_chunks_noisy_rounds(n, r.data(), &cfg->opt, &cfg->pass);
+        if (rc) return fail(rc);
+        for (int c = 0; c < n; ++c) { chunks[c].n_passes = r[c].n_passes; free(r[c].done); free(r[c].first_to_final); }
+    }
+    // 3. stitch_var_main: the phase sets of neighbours joined through the reads they share
+    {
+        std::vector<lcd_chunk_phase_t> ph(n); std::vector<std::vector<int>> up(n), down(n);
+        for (int c = 0; c < n; ++c) {
+            const lcd_first_chunk_t &x = chunks[c].first; const lcd_chunk_s *k = x.chunk;
+            for (int r = 0; r < k->n_reads; ++r) {
+                const int64_t rb = k->beg[r], re = k->end[r];
+                if (c > 0 && !(re < chunks[c - 1].first.reg_beg || rb > chunks[c - 1].first.reg_end)) up[c].push_back(r);
+                if (c + 1 < n && !(re < chunks[c + 1].first.reg_beg || rb > chunks[c + 1].first.reg_end)) down[c].push_back(r);
+            }
+            lcd_chunk_phase_t &p = ph[c]; memset(&p, 0, sizeof(p));
+            p.tid = 0; p.n_reads = x.vars->n_reads; p.n_vars = x.vars->n_vars; p.ordered_read_ids = x.order; p.is_skipped = x.is_skipped;
+            p.haps = x.state->haps; p.phase_sets = x.state->phase_sets; p.var_phase_set = x.state->var_phase_set; p.hap_to_cons_alle = x.state->hap_to_cons_alle;
+            p.n_up_ovlp = (int)up[c].size(); p.n_down_ovlp = (int)down[c].size(); p.up_ovlp_read_i = up[c].data(); p.down_ovlp_read_i = down[c].data();
+            p.flip_hap = 0; p.flip_pre_PS = p.flip_cur_PS = -1;
+        }
+        rc = lcd_stitch_chunks(ph.data(), n, 1);
+        if (rc) return fail(set_err(rc, W + ": neighbouring chunks disagree on the reads they share (the overlap counts differ)"));
+        for (int c = 0; c < n; ++c) { chunks[c].flip_hap = ph[c].flip_hap; chunks[c].flip_pre_PS = ph[c].flip_pre_PS; chunks[c].flip_cur_PS = ph[c].flip_cur_PS; }
+    }
+    // 4. make_var_main per chunk, records appended in chunk order; the VCF body lines
+    std::vector<lcd_var1_t> all;
+    lcd_te_opt_t te; lcd_te_opt_default(&te);
+    for (int c = 0; c < n; ++c) {
+        const lcd_first_chunk_t &x = chunks[c].first; const lcd_clean_vars_t *v = x.vars;
+        lcd_hap_problem_t p; memset(&p, 0, sizeof(p));
+        std::vector<int> alle_off(v->n_vars + 1), allele_off(v->n_reads + 1);
+        lcd_clean_vars_hap_problem(v, x.is_ont, x.order, x.is_skipped, alle_off.data(), allele_off.data(), &p);
+        const lcd_hap_state_t &s = *x.state;
+        p.haps = s.haps; p.phase_sets = s.phase_sets; p.n_clean_agree_snps = s.n_clean_agree_snps; p.n_clean_conflict_snps = s.n_clean_conflict_snps;
+        p.var_phase_set = s.var_phase_set; p.hap_to_cons_alle = s.hap_to_cons_alle; p.hap_to_alle_profile = s.hap_to_alle_profile;
+        std::vector<uint8_t> unknown;
+        if (!v->alt_ref_base) unknown.assign((size_t)v->n_vars + 1, 4);
+        lcd_var1_t *recs = nullptr;
+        const int m = lcd_make_variants(&cfg->call, &p, v->ref_len, v->alt_len, v->alt_off, v->alt_pool, v->alt_ref_base ? v->alt_ref_base : unknown.data(), (const char *)x.ref_seq,
+                                        x.ref_beg, x.reg_beg, x.reg_end, &recs);
+        if (m < 0) {   // (the reference exits: more reads carry the alt allele than its coverage says)
+            lcd_var1_t *tmp = (lcd_var1_t *)malloc((all.size() + 1) * sizeof(lcd_var1_t));
+            if (!all.empty()) memcpy(tmp, all.data(), all.size() * sizeof(lcd_var1_t));
+            lcd_free_variants(tmp, (int)all.size());
+            return fail(set_err(m, W + ": lcd_make_variants failed on chunk " + std::to_string(c)));
+        }
+        if (m > 0) lcd_annotate_te(&cfg->call, &te, nullptr, (const char *)x.ref_seq, x.ref_beg, x.ref_end, recs, m);
+        for (int i = 0; i < m; ++i) all.push_back(recs[i]);
+        free(recs);                                            // (the members moved into `all`)
+        chunks[c].n_records = m;
+    }
+    lcd_var1_t *out = (lcd_var1_t *)malloc((all.size() + 1) * sizeof(lcd_var1_t));
+    if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(lcd_var1_t));
+    char *text = nullptr;
+    const int nl = lcd_format_vcf(&cfg->call, chrom, out, (int)all.size(), &text);
+    if (nl < 0) { lcd_free_variants(out, (int)all.size()); return fail(nl); }
+    *records = out; *n_records = (int)all.size(); *vcf_body = text;
+    return 0;
+}
+
+int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                         int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body) {
+    const std::string W = "lcd_call_bam_regions";
+    if (records) *records = nullptr;
+    if (n_records) *n_records = 0;
+    if (vcf_body) *vcf_body = nullptr;
+    if (!bam_path || !bai_path || !fasta_path || !chrom || !cfg || !records || !n_records || !vcf_body) return set_err(-4, W + ": NULL argument");
+    if (n < 0 || (n > 0 && (!reg_beg || !reg_end || !chunks))) return set_err(-4, W + ": bad region list");
+    for (int c = 0; c < n; ++c) if (reg_beg[c] < 1 || reg_end[c] < reg_beg[c] || (c > 0 && reg_beg[c] <= reg_end[c - 1])) return set_err(-4, W + ": regions must be 1-based, non-empty and in genome order");
+    if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
+    const int is_ont = cfg->clean.is_ont != 0;
+    lcd_digar_opt_t dopt; lcd_digar_opt_default(&dopt, is_ont);
+    std::vector<lcd_chunk_t *> handles(n, nullptr); std::vector<uint8_t *> refs(n, nullptr); std::vector<lcd_bam_reads_t> metas(n);
+    for (int c = 0; c < n; ++c) { memset(&chunks[c], 0, sizeof(lcd_call_chunk_t)); memset(&metas[c], 0, sizeof(lcd_bam_reads_t)); }
+    auto drop_inputs = [&]() {
+        for (int c = 0; c < n; ++c) {
+            if (handles[c]) lcd_chunk_destroy(handles[c]);
+            free(refs[c]); lcd_bam_reads_free(&metas[c]);
+            handles[c] = nullptr; refs[c] = nullptr; chunks[c].first.chunk = nullptr; chunks[c].first.ref_seq = nullptr; chunks[c].first.meta = nullptr;
+        }
+    };
+    auto fail = [&](int code) { const std::string m = g_err; drop_inputs(); g_err = m; return code; };
+    for (int c = 0; c < n; ++c) {
+        // a first pass on the device for the reads' span (and, for EQX data, the chunk itself)
+        handles[c] = lcd_chunk_create_from_bam(&dopt, bam_path, bai_path, chrom, reg_beg[c], reg_end[c], min_mapq, 1, &metas[c]);
+        if (!handles[c]) return fail(-30);
+        int64_t lo = reg_beg[c], hi = reg_end[c];
+        for (int r = 0; r < metas[c].n_reads; ++r) { lo = std::min(lo, metas[c].pos0[r] + 1); hi = std::max(hi, metas[c].end_pos[r]); }
+        // get_bam_chunk_reg_ref_seq0 (src/bam_utils.c:1558-1571): 0-based [max(flank, beg - 1) - flank, min(len - flank - 1, end - 1) + flank], cut to the contig
+        const int64_t flank = 50000, len = metas[c].target_len;
+        const int64_t b0 = std::max<int64_t>(flank, lo - 1) - flank, e0 = std::min<int64_t>(len - flank - 1, hi - 1) + flank;
+        const int64_t got = lcd_fasta_fetch(fasta_path, chrom, b0 + 1, e0 + 1, &refs[c]);
+        if (got <= 0) return fail(set_err(got < 0 ? (int)got : -30, W + ": no reference sequence for the region (" + (got < 0 ? lcd_io_last_error() : "empty window") + ")"));
+        bool again = is_ont;
+        for (int r = 0; r < handles[c]->n_reads && !again; ++r) again = handles[c]->status[r] == -2;
+        if (again) {
+            lcd_chunk_destroy(handles[c]); handles[c] = nullptr; lcd_bam_reads_free(&metas[c]); memset(&metas[c], 0, sizeof(lcd_bam_reads_t));
+            lcd_chunk_src_t src; src.ref_seq = (const char *)refs[c]; src.ref_beg = b0 + 1; src.ref_end = b0 + got; src.is_ont = is_ont;
+            handles[c] = lcd_chunk_create_from_bam_src(&dopt, bam_path, bai_path, chrom, reg_beg[c], reg_end[c], min_mapq, 1, &src, &metas[c]);
+            if (!handles[c]) return fail(-30);
+        }
+        lcd_first_chunk_t &x = chunks[c].first;
+        x.chunk = handles[c]; x.ref_seq = refs[c]; x.ref_beg = b0 + 1; x.ref_end = b0 + got; x.reg_beg = reg_beg[c]; x.reg_end = reg_end[c]; x.is_ont = is_ont;
+        x.ordered_read_ids = nullptr; x.is_rev = nullptr; x.meta = &metas[c];
+    }
+    const int rc = lcd_chunks_call(n, chunks, cfg, chrom, records, n_records, vcf_body);
+    const std::string m = g_err;
+    drop_inputs();
+    g_err = m;
+    return rc;
+}
+
+} // extern "C"

@@ -175,7 +175,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
     LcdRegionImage im;
     if (lcd_io_region_image(bam_path, bai_path, chrom, reg_beg, reg_end, im)) { set_err(-30, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
     std::unique_ptr<lcd_chunk_s> c(new lcd_chunk_s());
-    c->device = cur_device(); c->n_reads = 0; c->opt = *opt;
+    c->device = cur_device(); c->n_reads = 0; c->opt = *opt; c->from_bam = true;
     if (meta) { meta->tid = im.tid; meta->n_targets = im.n_ref; meta->target_len = im.tlen; }
     if (im.image.empty() || im.ranges.empty()) return c.release();
     c->stream = lcd_bgzf_inflate_dev(im.image.data(), im.image.size(), verify_crc);
@@ -251,6 +251,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
             pos0.push_back(d.pos); endp.push_back(e0); mapq.push_back(d.mapq); flag.push_back(d.flag); ncig.push_back(x.nc); qlen.push_back(d.lseq);
             const uint64_t sq = d.off + 32 + d.lname + 4ull * d.nc;
             soff.push_back(sq); qoff.push_back(sq + ((uint64_t)d.lseq + 1) / 2);
+            c->aux_off.push_back(sq + ((uint64_t)d.lseq + 1) / 2 + (uint64_t)d.lseq); c->rec_end.push_back(d.off + (uint64_t)d.bs); // (the walk checked: the fixed fields end inside the record)
             coff.push_back(cw); { GatherJob g; g.src = x.cig_src; g.dst = cw * 4; g.bytes = (uint32_t)x.nc * 4u; g.pad_ = 0; gj.push_back(g); } cw += (uint64_t)x.nc;
             RefCmpOut rc; rc.n_ops = x.nc; rc.nd = (int)x.nd; rc.nev = (int)x.nev; rc.pad = 0; counts.push_back(rc); nindel.push_back((int)x.nid);
             if (src) {
@@ -408,6 +409,48 @@ int lcd_chunk_read_sources(const lcd_chunk_t *c, uint8_t *source, uint8_t *is_on
     for (int r = 0; r < c->n_reads; ++r) { if (source) source[r] = c->source.empty() ? LCD_SRC_EQX : c->source[r]; if (is_ont_palindrome) is_ont_palindrome[r] = c->pal.empty() ? 0 : c->pal[r]; }
     if (tag_bytes_d2h) *tag_bytes_d2h = c->tag_bytes;
     return c->n_reads;
+}
+// bam_get_NM (src/bam_utils.c:1632-1639) per kept read of a chunk made from a BAM, on the records where the inflate left them (lcd_bam_nm_kernel): 16 bytes per read go
+// up, 4 come back.  A chunk made from host arrays has no records: -4.
+int lcd_chunk_read_nm(const lcd_chunk_t *c, int *nm_out) {
+    if (!c || !c->from_bam) return set_err(-4, "lcd_chunk_read_nm: the chunk was not made from a BAM");
+    const int n = c->n_reads;
+    if (n <= 0) return 0;
+    if (!nm_out) return set_err(-4, "lcd_chunk_read_nm: NULL output");
+    if (!c->stream || (int)c->aux_off.size() != n || (int)c->rec_end.size() != n) return set_err(-4, "lcd_chunk_read_nm: the chunk has no record stream");
+    if (use_device(c->device)) return -1;
+    const uint64_t base = lcd_inflated_dev_ptr(c->stream), usize = lcd_inflated_size(c->stream);
+    std::vector<BamNmJob> jobs(n);
+    for (int r = 0; r < n; ++r) {
+        if (c->aux_off[r] > c->rec_end[r] || c->rec_end[r] > usize) return set_err(-4, "lcd_chunk_read_nm: record outside the stream");
+        jobs[r].aux = base + c->aux_off[r]; jobs[r].end = base + c->rec_end[r];
+    }
+    StreamGuard st; if (st.create()) return -10;
+    DevBuf d_jobs, d_nm;
+    if (d_jobs.ensure((size_t)n * sizeof(BamNmJob)) || d_nm.ensure((size_t)n * 4)) return -11;
+    HIPCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)n * sizeof(BamNmJob), hipMemcpyHostToDevice, st));
+    lcd_launch_bam_nm((const BamNmJob *)d_jobs.p, (int *)d_nm.p, n, st);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(nm_out, d_nm.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return n;
+}
+// sort_chunk_reads (src/bam_utils.c:1616-1656), host code: comp_bam_read_sort's keys -- pos ascending, end DESCENDING, NM ascending, strcmp of the names -- and, where
+// all four are equal (qsort leaves that order open), file order
+int lcd_sort_chunk_reads(int n, const int64_t *pos0, const int64_t *end_pos, const int *nm, const uint64_t *name_off, const char *name_pool, int *order_out) {
+    if (n < 0) return set_err(-4, "lcd_sort_chunk_reads: n < 0");
+    if (n == 0) return 0;
+    if (!pos0 || !end_pos || !nm || !name_off || !name_pool || !order_out) return set_err(-4, "lcd_sort_chunk_reads: NULL argument");
+    std::vector<int> o(n);
+    for (int i = 0; i < n; ++i) o[i] = i;
+    std::stable_sort(o.begin(), o.end(), [&](const int a, const int b) {
+        if (pos0[a] != pos0[b]) return pos0[a] < pos0[b];
+        if (end_pos[a] != end_pos[b]) return end_pos[a] > end_pos[b];
+        if (nm[a] != nm[b]) return nm[a] < nm[b];
+        return strcmp(name_pool + name_off[a], name_pool + name_off[b]) < 0;
+    });
+    memcpy(order_out, o.data(), (size_t)n * sizeof(int));
+    return n;
 }
 void lcd_chunk_stage_ms(const lcd_chunk_t *c, double out[4]) { for (int k = 0; k < 4; ++k) out[k] = c->stage_ms[k]; }
 // the chunk's digars as lcd_digar_batch returns them (tests and debugging: everything else reads them in HBM)

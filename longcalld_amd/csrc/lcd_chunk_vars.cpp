@@ -251,6 +251,7 @@ static int clean_vars_one(const lcd_chunk_t *c0, const lcd_clean_opt_t *opt, con
     out->alt_len = (int *)malloc((V + 1) * 4ull); out->cate = (int *)malloc((V + 1) * 4ull); out->total_cov = (int *)malloc((V + 1) * 4ull);
     out->low_qual_cov = (int *)malloc((V + 1) * 4ull); out->alle_covs = (int *)malloc((V + 1) * 8ull); out->strand_alle_covs = (int *)malloc((V + 1) * 16ull);
     out->alt_off = (uint64_t *)malloc((V + 1) * 8ull); out->is_homopolymer_indel = (int *)calloc(V + 1, 4);
+    out->alt_ref_base = (uint8_t *)malloc((size_t)V + 1); memset(out->alt_ref_base, 4, (size_t)V + 1);   // unknown (src/collect_var.c:44)
     unsigned long long na = 0;
     for (int k = 0; k < V; ++k) {
         const int i = keep[k]; const CvSite &v = sites[i]; const CvCov &cv = cov[i];
@@ -348,7 +349,7 @@ void lcd_clean_vars_free(lcd_clean_vars_t *v) {
     if (!v) return;
     free(v->pos); free(v->var_type); free(v->ref_len); free(v->alt_len); free(v->cate); free(v->total_cov); free(v->low_qual_cov); free(v->alle_covs);
     free(v->strand_alle_covs); free(v->alt_off); free(v->alt_pool); free(v->is_homopolymer_indel); free(v->regs); free(v->start_var_idx); free(v->end_var_idx);
-    free(v->allele_off); free(v->alleles); free(v->alt_qi); free(v->cr_read);
+    free(v->allele_off); free(v->alleles); free(v->alt_qi); free(v->cr_read); free(v->alt_ref_base);
     memset(v, 0, sizeof(*v));
 }
 int lcd_clean_vars_hap_problem(const lcd_clean_vars_t *v, int is_ont, const int *ordered_read_ids, const uint8_t *is_skipped, int *alle_off, int *allele_off,
@@ -458,6 +459,7 @@ int mv_walk(const char *who, const lcd_clean_vars_t *cur, int n_regions, const l
     out->alt_len = (int *)malloc((M + 1) * 4ull); out->cate = (int *)malloc((M + 1) * 4ull); out->total_cov = (int *)malloc((M + 1) * 4ull);
     out->low_qual_cov = (int *)calloc(M + 1, 4); out->alle_covs = (int *)malloc((M + 1) * 8ull); out->strand_alle_covs = (int *)calloc(M + 1, 16);
     out->alt_off = (uint64_t *)malloc((M + 1) * 8ull); out->is_homopolymer_indel = (int *)calloc(M + 1, 4);
+    out->alt_ref_base = (uint8_t *)malloc((size_t)M + 1); out->alt_ref_base[M] = 4;
     uint64_t na = 0;
     for (int m = 0; m < M; ++m) { const MvVar &t = tab[m]; if (t.origin < 0) na += cur->alt_off[t.idx + 1] - cur->alt_off[t.idx]; else if (t.type == 8 || t.type == 1) na += (uint64_t)t.alt_len; }
     out->alt_pool = (uint8_t *)malloc(na + 1);
@@ -470,6 +472,7 @@ int mv_walk(const char *who, const lcd_clean_vars_t *cur, int n_regions, const l
             out->cate[m] = cur->cate[i]; out->total_cov[m] = cur->total_cov[i]; out->low_qual_cov[m] = cur->low_qual_cov[i];
             out->alle_covs[2 * m] = cur->alle_covs[2 * i]; out->alle_covs[2 * m + 1] = cur->alle_covs[2 * i + 1];
             memcpy(out->strand_alle_covs + 4 * m, cur->strand_alle_covs + 4 * i, 16); out->is_homopolymer_indel[m] = cur->is_homopolymer_indel[i];
+            out->alt_ref_base[m] = cur->alt_ref_base ? cur->alt_ref_base[i] : 4;   // (a table without the member: all unknown)
             const uint64_t nb = cur->alt_off[i + 1] - cur->alt_off[i];
             if (nb) memcpy(out->alt_pool + na, cur->alt_pool + cur->alt_off[i], nb);
             na += nb;
@@ -477,6 +480,7 @@ int mv_walk(const char *who, const lcd_clean_vars_t *cur, int n_regions, const l
             const lcd_noisy_var_t &v = regions[t.origin].vars[t.idx]; mc.b2m[t.origin][t.idx] = m;
             out->cate[m] = v.cate; out->total_cov[m] = v.total_cov; out->alle_covs[2 * m] = v.alle_covs[0]; out->alle_covs[2 * m + 1] = v.alle_covs[1];
             out->is_homopolymer_indel[m] = v.is_homopolymer_indel;
+            out->alt_ref_base[m] = t.type == 8 ? 0 : (uint8_t)v.alt_ref_base;      // make_cand_vars0 (:1755-1756): an X variant keeps the cleared struct's 0
             if ((t.type == 8 || t.type == 1) && t.alt_len > 0) { memcpy(out->alt_pool + na, v.alt_seq, (size_t)t.alt_len); na += (uint64_t)t.alt_len; }
         }
     }

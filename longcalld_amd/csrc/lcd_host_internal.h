@@ -169,6 +169,9 @@ struct RegionRec {
     int n_cons = 0;
 };
 
+// pre_process_noisy_regs' host part in front of the read support (lcd_noisy_regs.cpp): cr_index, low-complexity extension, cr_merge twice
+void pre_regs_merge(std::vector<NIv> &v, const int64_t *low_comp, int n_low);
+
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
 } // namespace lcd_internal
@@ -241,6 +244,7 @@ struct lcd_chunk_s {
     std::vector<int> status, n_cand; std::vector<int64_t> beg, end;
     std::vector<uint8_t> source, pal; uint64_t tag_bytes = 0;   // lcd_chunk_create_from_bam_src: LCD_SRC_* and is_ont_palindrome per read; cs / MD bytes brought to the host
     double stage_ms[4] = {0, 0, 0, 0};                          // ... and its wall-clock split: aux fields, reference comparison, tag download + host parse, digars
+    bool from_bam = false; std::vector<uint64_t> aux_off, rec_end;   // lcd_chunk_create_from_bam*: per read its auxiliary fields [aux_off, rec_end) as offsets of the inflated stream (lcd_chunk_read_nm)
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use

@@ -19,6 +19,7 @@ void lcd_launch_bam_walk(const BamWalkJob *jobs, BamWalkOut *outs, int n_jobs, h
 void lcd_launch_bam_stat(const BamStatJob *jobs, BamStatOut *outs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_cigar(const GatherJob *jobs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_aux(const BamAuxJob *jobs, BamAuxOut *outs, int is_ont, int n_jobs, hipStream_t st);
+void lcd_launch_bam_nm(const BamNmJob *jobs, int *nm, int n_jobs, hipStream_t st);
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st);
 void lcd_launch_compose(const CmpJob *jobs, CmpOut *outs, const CmpSeg *segs, int n_jobs, int emit, hipStream_t stream);
 void lcd_launch_vars_scan(const VarScanJob *jobs, VarScanOut *outs, int n_jobs, hipStream_t stream);
@@ -29,6 +30,7 @@ void lcd_launch_unpack(const UnpackJob *jobs, int n_jobs, const uint8_t *packed,
 void lcd_launch_refcmp(bool emit, const RefCmpJob *jobs, RefCmpOut *outs, const char *ref, long long ref_beg, long long ref_end, int n_jobs, hipStream_t stream);
 void lcd_launch_region_support(const IvRec *regs, int n_regs, const long long *read_beg, const long long *read_end, const unsigned long long *iv_off,
                                const IvRec *ivs, int n_reads, int *total, int *noisy, hipStream_t stream);
+void lcd_launch_region_support_batch(const SupChunk *chunks, const SupReg *regs, int n_regs, int *total, int *noisy, hipStream_t stream);
 void lcd_launch_sdust(const unsigned char *pool, const SdSeg *segs, int T, int W, int seg, int n_seg, int cap, int *n_out, int2 *out, int4 *pbuf, int pcap, hipStream_t stream);
 void lcd_launch_hap(const HapProb *probs, int n, hipStream_t stream);
 // clean_vars_kernel.hip: candidate sites, pile-up, classification, noisy-read ratios and the read x variant profile of a device-resident chunk

@@ -101,21 +101,7 @@ int lcd_pre_process_noisy_regs(const lcd_noisy_iv_t *chunk_noisy, int n_noisy, c
     if (n_noisy <= 0) return 0;
     std::vector<NIv> v;
     for (int i = 0; i < n_noisy; ++i) niv_add(v, chunk_noisy[i].start, chunk_noisy[i].end, chunk_noisy[i].label);
-    niv_index(v);
-    if (n_low > 0) { // cr_extend_noisy_regs_with_low_comp / low_comp_cr_start_end (:466-478, :538-551): grow to every overlapping low-complexity interval
-        std::vector<NIv> w;
-        for (const NIv &a : v) {
-            const long long start = (long long)a.x + 1, end = a.en; long long ns = start, ne = end;
-            for (int k = 0; k < n_low; ++k) {
-                long long ls = low_comp[2 * k] < 0 ? 0 : low_comp[2 * k], le = low_comp[2 * k + 1];
-                if (ls > le) continue;
-                if (ls < end && start - 1 < le) { if (ls + 1 < ns) ns = ls + 1; if (le > ne) ne = le; }
-            }
-            niv_add(w, ns - 1, ne, a.label);
-        }
-        niv_index(w); v.swap(w);
-    }
-    niv_merge(v); niv_merge(v); // (:552 and :568)
+    pre_regs_merge(v, low_comp, n_low);
     const int nr = (int)v.size();
     if (nr == 0) return 0;
     // read support on the device
@@ -241,3 +227,25 @@ int lcd_sort_noisy_regs(const lcd_noisy_iv_t *regs, int n, int *order_out) {
 }
 
 } // extern "C"
+
+// the host part of pre_process_noisy_regs in front of the read support (src/collect_var.c:559-568): cr_index, the extension to the overlapping low-complexity
+// intervals, cr_merge twice.  v: the chunk's windows in cr_add order.  Shared by lcd_pre_process_noisy_regs and lcd_chunks_first_round.
+namespace lcd_internal {
+void pre_regs_merge(std::vector<NIv> &v, const int64_t *low_comp, int n_low) {
+    niv_index(v);
+    if (n_low > 0) { // cr_extend_noisy_regs_with_low_comp / low_comp_cr_start_end (:466-478, :538-551): grow to every overlapping low-complexity interval
+        std::vector<NIv> w;
+        for (const NIv &a : v) {
+            const long long start = (long long)a.x + 1, end = a.en; long long ns = start, ne = end;
+            for (int k = 0; k < n_low; ++k) {
+                long long ls = low_comp[2 * k] < 0 ? 0 : low_comp[2 * k], le = low_comp[2 * k + 1];
+                if (ls > le) continue;
+                if (ls < end && start - 1 < le) { if (ls + 1 < ns) ns = ls + 1; if (le > ne) ne = le; }
+            }
+            niv_add(w, ns - 1, ne, a.label);
+        }
+        niv_index(w); v.swap(w);
+    }
+    niv_merge(v); niv_merge(v); // (:552 and :568)
+}
+} // namespace lcd_internal

@@ -232,6 +232,12 @@ struct BamAuxJob { uint64_t rec, cig; int bs, lname, nc16, lseq, nc, flag; long 
 // bad_type: the deciding cs / MD field is not of type Z; cig_qlen: query bases of the CIGAR (reads that are not EQX only, else 0)
 struct BamAuxOut { uint64_t tag; uint32_t tag_len; uint8_t source, pal, bad_type, pad; long long cig_qlen; };
 struct ErrJob { uint64_t qual; int len, pad; };
+// lcd_region_support_batch_kernel: the kept reads of one chunk (device addresses: read_beg / read_end int64 per read, iv_off n_reads + 1 offsets into ivs) and one
+// merged region with the chunk it belongs to
+struct SupChunk { uint64_t read_beg, read_end, iv_off, ivs; int n_reads, pad; };
+struct SupReg { long long st, en; int chunk, pad; };
+// lcd_bam_nm_kernel: a kept record's auxiliary fields [aux, end) as device addresses
+struct BamNmJob { uint64_t aux, end; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;
