@@ -584,6 +584,24 @@ double lcd_inflated_kernel_ms(const lcd_inflated_t *h);
 double lcd_inflated_upload_ms(const lcd_inflated_t *h);
 int lcd_inflated_to_host(const lcd_inflated_t *h, size_t off, size_t n, uint8_t *out);
 void lcd_inflated_free(lcd_inflated_t *h);
+
+/* ---- the inverse: BGZF blocks COMPRESSED on the device (deflate_kernel.hip), one wavefront per block ----
+ * The input (host bytes, or n bytes already in HBM at dev_ptr) is cut into payloads of block_payload bytes (0: 0xff00, htslib's size; 1 ... 0xff00); each becomes
+ * one BGZF member (SAM specification 4.1: 18-byte header with the BC field and BSIZE, a raw deflate stream, CRC-32, ISIZE); add_eof appends the standard 28-byte
+ * empty member; n == 0 gives that member alone, or an empty image.  LZ77 matches (distance <= 32 768, length 3 ... 258, one candidate per position from a hash table
+ * in LDS), dynamic Huffman codes limited to 15 bits, or fixed codes, or -- when neither is smaller -- stored: a member is at most payload + 5 + 26 bytes.  The file
+ * image is contiguous in HBM (the members are compacted by a second kernel); lcd_deflated_to_host copies a range of it.  lcd_deflated_block_info: a member's payload
+ * bytes, its total size and its kind (0 stored, 1 fixed codes, 2 dynamic codes).  lcd_deflated_kernel_ms: HIP-event time from the compressor's launch to the end
+ * of the compaction.  No host path: without a device the calls fail (NULL + lcd_last_error). */
+typedef struct lcd_deflated_s lcd_deflated_t;
+lcd_deflated_t *lcd_bgzf_deflate_dev(const uint8_t *data, size_t n, int block_payload, int add_eof);
+lcd_deflated_t *lcd_bgzf_deflate_dev_ptr(uint64_t dev_ptr, size_t n, int block_payload, int add_eof);
+size_t lcd_deflated_size(const lcd_deflated_t *h);
+size_t lcd_deflated_n_blocks(const lcd_deflated_t *h);
+double lcd_deflated_kernel_ms(const lcd_deflated_t *h);
+int lcd_deflated_block_info(const lcd_deflated_t *h, size_t i, uint32_t *payload, uint32_t *bsize, int *kind);
+int lcd_deflated_to_host(const lcd_deflated_t *h, size_t off, size_t n, uint8_t *out);
+void lcd_deflated_free(lcd_deflated_t *h);
 /* faidx_fetch_seq of chrom:[beg, end] (1-based inclusive, clipped to the contig) through <fa_path>.fai, as byte codes A0 C1 G2 T3 N4 (get_bam_chunk_reg_ref_seq0,
  * src/bam_utils.c:1558); returns the length, *codes_out malloc()'d */
 int64_t lcd_fasta_fetch(const char *fa_path, const char *chrom, int64_t beg, int64_t end, uint8_t **codes_out);
@@ -840,6 +858,40 @@ int lcd_chunks_call(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg
 int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
                          const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body);
 void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_records, char *vcf_body);
+
+/* ---- the phased alignment output (longcallD call -b): write_read_to_bam / write_processed_read_to_bam / write_unprocessed_read_to_bam, src/bam_utils.c:1944-2048 ----
+ * A chunk made from a BAM remembers every record its region's iterator yields, in file order: kept records (the chunk's reads) and records the loader's flag / MAPQ
+ * filter dropped.  The iterator's overlap test applies whatever the flags say; PROJECT RULE (htslib is not in the checkout): a record with the unmapped flag, or
+ * whose CIGAR consumes no reference, spans one base (bam_endpos).
+ * lcd_chunk_tag_records rewrites those records in HBM (bam_tag_kernel.hip) and leaves them back to back.  The auxiliary fields are hopped as lcd_chunk_read_nm hops
+ * them (a field that runs past the record ends the walk); bam_aux2i: types c C s S i I give their value, any other type 0.  A kept record of read r, hap = haps[r],
+ * ps = phase_sets[r]: HP first, then PS; a tag is wanted when hap != 0 / ps > 0.  Wanted and the first field of that name holds the value: it stays in place, byte
+ * for byte.  Wanted otherwise: the first field (if any) is deleted and HP:i / PS:i (4 bytes, little endian; PS: the low 32 bits) is appended.  Not wanted: the first
+ * field is deleted.  Later fields of the same name stay.  The record is its bytes without the deleted fields, the appended HP, the appended PS; only block_size
+ * changes.  A filtered record loses its first HP and first PS field.  The first n_skip_kept kept and n_skip_filtered filtered records are not written (the region
+ * before has written them).  NULL + lcd_last_error for a chunk that was not made from a BAM.
+ * lcd_write_phased_bam (after lcd_chunks_call, before lcd_call_free / the chunks' destruction): the input file's header block with pg_line (one finished @PG line
+ * without a newline, or NULL) appended to its text, compressed into its own block(s); then region c's records in region order, the skip counts of region c being
+ * its kept / filtered records that overlap region c - 1's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691); every region's stream through
+ * lcd_bgzf_deflate_dev_ptr; the EOF member last.  Only compressed bytes cross PCIe; the file is written with fwrite.  htslib's sam_hdr_add_pg chooses ID / PP
+ * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written; --refine-aln, CRAM / SAM output and several input files are not supported.
+ * lcd_call_bam_regions_out: lcd_call_bam_regions with the alignment output written after lcd_chunks_call succeeded (bam_out NULL: none).  A failure of the output
+ * (unwritable path) returns < 0 with lcd_last_error and leaves *records / *vcf_body / the chunks' out members valid: free them with lcd_call_free as usual. */
+typedef struct lcd_tagged_s lcd_tagged_t;
+lcd_tagged_t *lcd_chunk_tag_records(const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, int n_skip_kept, int n_skip_filtered);
+uint64_t lcd_tagged_dev_ptr(const lcd_tagged_t *h);
+size_t lcd_tagged_size(const lcd_tagged_t *h);
+int lcd_tagged_n_records(const lcd_tagged_t *h);
+int lcd_tagged_to_host(const lcd_tagged_t *h, size_t off, size_t n, uint8_t *out);
+void lcd_tagged_free(lcd_tagged_t *h);
+typedef struct lcd_bam_out_t {
+    const char *path; const char *pg_line; int block_payload;        /* in; pg_line may be NULL, block_payload 0 = 0xff00 */
+    int64_t n_records_out, n_filtered_out, bytes_inflated, bytes_file; double ms_tag, ms_deflate, ms_download_write;   /* out */
+} lcd_bam_out_t;
+int lcd_write_phased_bam(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out);
+int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
+                             const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                             lcd_bam_out_t *bam_out);
 
 #ifdef __cplusplus
 }

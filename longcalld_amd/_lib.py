@@ -170,6 +170,12 @@ class LcdCallChunk(C.Structure):
     _fields_ = [("first", LcdFirstChunk), ("n_passes", C.c_int), ("flip_hap", C.c_int), ("flip_pre_PS", C.c_int64), ("flip_cur_PS", C.c_int64), ("n_records", C.c_int)]
 
 
+class LcdBamOut(C.Structure):
+    """lcd_bam_out_t: the phased alignment output of lcd_call_bam_regions_out / lcd_write_phased_bam"""
+    _fields_ = [("path", C.c_char_p), ("pg_line", C.c_char_p), ("block_payload", C.c_int)] + [(n, C.c_int64) for n in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file")] + [
+        (n, C.c_double) for n in ("ms_tag", "ms_deflate", "ms_download_write")]
+
+
 _lib = None
 
 # every symbol include/lcd_hotpath.h declares (tests check the .so exports all of them)
@@ -186,6 +192,8 @@ EXPORTS = [
     "lcd_hap_state_init", "lcd_hap_state_carry", "lcd_hap_state_free", "lcd_chunks_noisy_rounds",
     "lcd_chunk_read_nm", "lcd_sort_chunk_reads", "lcd_chunks_first_round", "lcd_first_round_free",
     "lcd_cfg_default", "lcd_chunks_call", "lcd_call_bam_regions", "lcd_call_free",
+    "lcd_bgzf_deflate_dev", "lcd_bgzf_deflate_dev_ptr", "lcd_deflated_size", "lcd_deflated_n_blocks", "lcd_deflated_kernel_ms", "lcd_deflated_block_info", "lcd_deflated_to_host", "lcd_deflated_free",
+    "lcd_chunk_tag_records", "lcd_tagged_dev_ptr", "lcd_tagged_size", "lcd_tagged_n_records", "lcd_tagged_to_host", "lcd_tagged_free", "lcd_write_phased_bam", "lcd_call_bam_regions_out",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -296,6 +304,27 @@ def load_library():
     lib.lcd_chunks_call.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdCfg), C.c_char_p, C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p)]
     lib.lcd_call_bam_regions.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, i64p, i64p, C.c_int, C.POINTER(LcdCfg), C.POINTER(LcdCallChunk),
                                          C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p)]
+    lib.lcd_call_bam_regions_out.argtypes = lib.lcd_call_bam_regions.argtypes + [C.POINTER(LcdBamOut)]
+    lib.lcd_write_phased_bam.argtypes = [C.c_char_p, C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdBamOut)]
+    for f in ("lcd_bgzf_deflate_dev", "lcd_bgzf_deflate_dev_ptr", "lcd_chunk_tag_records"):
+        getattr(lib, f).restype = C.c_void_p
+    lib.lcd_bgzf_deflate_dev.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int]
+    lib.lcd_bgzf_deflate_dev_ptr.argtypes = [C.c_uint64, C.c_size_t, C.c_int, C.c_int]
+    lib.lcd_chunk_tag_records.argtypes = [C.c_void_p, i32p, i64p, C.c_int, C.c_int]
+    for f in ("lcd_deflated_size", "lcd_deflated_n_blocks", "lcd_tagged_size"):
+        getattr(lib, f).restype = C.c_size_t
+        getattr(lib, f).argtypes = [C.c_void_p]
+    lib.lcd_deflated_kernel_ms.restype = C.c_double
+    lib.lcd_deflated_kernel_ms.argtypes = [C.c_void_p]
+    lib.lcd_deflated_block_info.argtypes = [C.c_void_p, C.c_size_t, u32p, u32p, i32p]
+    lib.lcd_tagged_dev_ptr.restype = C.c_uint64
+    lib.lcd_tagged_dev_ptr.argtypes = [C.c_void_p]
+    lib.lcd_tagged_n_records.argtypes = [C.c_void_p]
+    for f in ("lcd_deflated_to_host", "lcd_tagged_to_host"):
+        getattr(lib, f).argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_char_p]
+    for f in ("lcd_deflated_free", "lcd_tagged_free"):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = None
     lib.lcd_call_free.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdVar1), C.c_int, C.c_void_p]
     lib.lcd_call_free.restype = None
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]

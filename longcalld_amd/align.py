@@ -545,6 +545,24 @@ class DeviceChunk:
         self.packed_bytes = 0
         return self
 
+    def tag_records(self, haps, phase_sets, n_skip_kept=0, n_skip_filtered=0):
+        """lcd_chunk_tag_records: the records of a chunk made from a BAM with HP:i / PS:i rewritten in HBM -> (bytes of the records back to back, their number)"""
+        lib = self.lib
+        hp = np.ascontiguousarray(haps, np.int32); ps = np.ascontiguousarray(phase_sets, np.int64)
+        if len(hp) < self.n or len(ps) < self.n:
+            raise ValueError("tag_records: haps / phase_sets shorter than the chunk's reads")
+        hp = np.concatenate([hp, np.zeros(1, np.int32)]); ps = np.concatenate([ps, np.zeros(1, np.int64)])
+        h = lib.lcd_chunk_tag_records(self.h, hp.ctypes.data_as(i32p), ps.ctypes.data_as(C.POINTER(C.c_int64)), int(n_skip_kept), int(n_skip_filtered))
+        if not h:
+            raise LcdError("lcd_chunk_tag_records failed: " + lib.lcd_last_error().decode())
+        try:
+            n = lib.lcd_tagged_size(h)
+            buf = C.create_string_buffer(max(n, 1))
+            check(lib.lcd_tagged_to_host(h, 0, n, buf), lib)
+            return buf.raw[:n], int(lib.lcd_tagged_n_records(h))
+        finally:
+            lib.lcd_tagged_free(h)
+
     def read_info(self):
         n = self.n
         st = np.zeros(n, np.int32); beg = np.zeros(n, np.int64); end = np.zeros(n, np.int64); nc = np.zeros(n, np.int32); nd = np.zeros(n, np.int32)
@@ -1408,9 +1426,52 @@ def chunks_call(chunks, items, cfg=None, chrom="chr11"):
     return _call_result(lib, n, arr, recs, n_recs, text)
 
 
-def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None):
-    """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call"""
-    from ._lib import LcdCallChunk, LcdVar1
+def bgzf_deflate(data, block_payload=0, add_eof=1):
+    """lcd_bgzf_deflate_dev: bytes -> dict(image = the BGZF file image compressed on the device, blocks = [(payload bytes, member bytes, kind 0 stored / 1 fixed /
+    2 dynamic)], kernel_ms)"""
+    lib = load_library()
+    data = bytes(data)
+    h = lib.lcd_bgzf_deflate_dev(data, len(data), int(block_payload), int(add_eof))
+    if not h:
+        raise LcdError("lcd_bgzf_deflate_dev failed: " + lib.lcd_last_error().decode())
+    try:
+        n = lib.lcd_deflated_size(h)
+        buf = C.create_string_buffer(max(n, 1))
+        check(lib.lcd_deflated_to_host(h, 0, n, buf), lib)
+        blocks = []
+        for i in range(lib.lcd_deflated_n_blocks(h)):
+            pl, bs, kind = C.c_uint32(0), C.c_uint32(0), C.c_int(0)
+            check(lib.lcd_deflated_block_info(h, i, C.byref(pl), C.byref(bs), C.byref(kind)), lib)
+            blocks.append((int(pl.value), int(bs.value), int(kind.value)))
+        return dict(image=buf.raw[:n], blocks=blocks, kernel_ms=float(lib.lcd_deflated_kernel_ms(h)))
+    finally:
+        lib.lcd_deflated_free(h)
+
+
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None):
+    """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
+    bam_out = dict(path[, pg_line, block_payload]): lcd_call_bam_regions_out, the phased alignment file is written too; the result gets "bam_out" = the counters and
+    stage times of lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised)"""
+    from ._lib import LcdBamOut, LcdCallChunk, LcdVar1
+    if bam_out is not None:
+        lib = load_library()
+        cfg = cfg if cfg is not None else call_cfg()
+        n = len(reg_beg)
+        arr = (LcdCallChunk * max(1, n))()
+        rb = (C.c_int64 * max(1, n))(*[int(x) for x in reg_beg]); re_ = (C.c_int64 * max(1, n))(*[int(x) for x in reg_end])
+        recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
+        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+        bo = LcdBamOut(); bo.path = enc(bam_out["path"]); bo.pg_line = enc(bam_out["pg_line"]) if bam_out.get("pg_line") is not None else None
+        bo.block_payload = int(bam_out.get("block_payload", 0))
+        rc = lib.lcd_call_bam_regions_out(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
+                                          C.byref(text), C.byref(bo))
+        err = lib.lcd_last_error().decode() if rc < 0 else ""
+        if rc < 0 and not text and not recs:
+            raise LcdError(f"liblcd_hotpath error {rc}: {err}")
+        res = _call_result(lib, n, arr, recs, n_recs, text)
+        res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
+                                                                                                   "ms_deflate", "ms_download_write")})
+        return res
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
     n = len(reg_beg)

@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "lcd_types.h"
 #include "lcd_kernels.h"
+#include "crc32_gf2.h"
 
 namespace {
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
@@ -197,22 +198,10 @@ __device__ __forceinline__ void flush_half(const unsigned lds, uint8_t *out, con
     for (int k = n16 + lane; k < n; k += 64) out[from + k] = win[(from + k) & WINM];
 }
 
-__device__ __forceinline__ unsigned gf2_mulmod(unsigned a, unsigned b) { // a * b mod P, reflected CRC-32 polynomial
-    unsigned m = 1u << 31, p = 0;
-    for (;;) {
-        if (a & m) { p ^= b; if ((a & (m - 1)) == 0) break; }
-        m >>= 1;
-        b = (b & 1) ? (b >> 1) ^ 0xedb88320u : b >> 1;
-    }
-    return p;
-}
 } // namespace
 
 struct InflateJob { unsigned long long src, dst; unsigned clen, ulen, crc, pad_; }; // src: first byte of the raw deflate stream; dst: its place in the inflated stream
 struct InflateOut { int status; unsigned crc; unsigned ulen; unsigned n_sym; unsigned long long t_total, t_tables, t_flush, t_match; }; // (t_*: s_memtime ticks, profiling aid)
-
-// x^(2^k) mod P, k = 0..31 (bits, reflected representation): filled by the host once
-__constant__ unsigned c_x2n[32];
 
 template <bool PROF> __device__ __forceinline__ long long tick() { if constexpr (PROF) return clock64(); else return 0; }
 template <bool PROF>
@@ -377,40 +366,18 @@ __global__ void __launch_bounds__(64) lcd_inflate_kernel(const InflateJob *jobs,
     if (status == 0) { __builtin_amdgcn_s_waitcnt(0xc07f); flush_half(lds, out, flushed, pos - flushed, lane); }
     unsigned crc = 0;
     if (status == 0 && verify) {
-        // CRC-32 of the block: byte table in LDS, a contiguous slice per lane, slices combined by x^(8 * bytes behind) mod P
+        // CRC-32 of the block (crc32_gf2.h): byte table in LDS, a contiguous slice per lane, slices combined by x^(8 * bytes behind) mod P
         lds_u32 *ct = (lds_u32 *)(uintptr_t)(lds + O_CRCT);
-        for (int k = lane; k < 256; k += 64) { unsigned c = (unsigned)k; for (int b = 0; b < 8; ++b) c = (c & 1) ? (c >> 1) ^ 0xedb88320u : c >> 1; ct[k] = c; }
+        lcd_crc::crc32_fill_table(ct, lane);
         __builtin_amdgcn_s_waitcnt(0x0070); // vmcnt(0) lgkmcnt(0): the block's stores have landed, the table is written
-        const int per = ((ulen + 63) / 64 + 15) & ~15; // slice length: a multiple of 16 bytes
-        const int b0 = imin(lane * per, ulen), b1 = imin(b0 + per, ulen);
-        unsigned c = 0xffffffffu;
-        int k = b0;
-        for (; k + 16 <= b1; k += 16) {
-            const v4u v = *(const v4u_u *)(out + k);
-            const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                unsigned x = w[q];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) { c = ct[(c ^ x) & 255] ^ (c >> 8); x >>= 8; }
-            }
-        }
-        for (; k < b1; ++k) c = ct[(c ^ out[k]) & 255] ^ (c >> 8);
-        c = b1 > b0 ? ~c : 0;
-        // shift by the bytes behind this slice: c * x^(8 n) mod P
-        unsigned n = (unsigned)(ulen - b1), p = 1u << 31; int kk = 3;
-        while (n) { if (n & 1) p = gf2_mulmod(c_x2n[kk & 31], p); n >>= 1; ++kk; }
-        c = b1 > b0 ? gf2_mulmod(p, c) : 0;
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) c ^= __shfl_xor(c, o);
-        crc = c;
+        crc = lcd_crc::crc32_wave(out, ulen, ct, lane);
         if (crc != job.crc) status = 13;
     }
     if (lane == 0) { outs[j].status = status; outs[j].crc = crc; outs[j].ulen = (unsigned)pos; outs[j].n_sym = n_sym;
                      outs[j].t_total = (unsigned long long)(tick<PROF>() - t_begin); outs[j].t_tables = t_tables; outs[j].t_flush = t_flush; outs[j].t_match = t_match; }
 }
 
-void lcd_inflate_set_x2n(const unsigned *t32, hipStream_t st) { (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(c_x2n), t32, 32 * sizeof(unsigned), 0, hipMemcpyHostToDevice, st); }
+void lcd_inflate_set_x2n(const unsigned *t32, hipStream_t st) { (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(lcd_crc::c_x2n), t32, 32 * sizeof(unsigned), 0, hipMemcpyHostToDevice, st); }
 void lcd_launch_inflate(const void *jobs, void *outs, int n_jobs, int verify, int timers, hipStream_t stream) { // timers: the per-phase tick counters of InflateOut are filled (a profiling build of the same kernel)
     if (n_jobs <= 0) return;
     if (timers) hipLaunchKernelGGL(lcd_inflate_kernel<true>, dim3(n_jobs), dim3(64), O_END, stream, (const InflateJob *)jobs, (InflateOut *)outs, n_jobs, verify);

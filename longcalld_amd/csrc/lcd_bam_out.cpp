@@ -1,0 +1,173 @@
+// lcd_bam_out.cpp -- the device side of the phased alignment output (longcallD call -b): BGZF members compressed in HBM (deflate_kernel.hip) and the HP:i / PS:i
+// rewrite of a chunk's records where the inflate left them (bam_tag_kernel.hip).  The writer that joins them into a file is lcd_write_phased_bam (lcd_call.cpp).
+#include "lcd_host_internal.h"
+
+using namespace lcd_internal;
+
+struct lcd_deflated_s {
+    DevBuf image; size_t size = 0, n_blocks = 0; double ms_kernel = 0; int device = 0; bool eof = false;
+    std::vector<DeflateOut> outs; std::vector<uint32_t> payloads;
+};
+struct lcd_tagged_s { DevBuf out; size_t size = 0; int n_records = 0, device = 0; };
+
+namespace {
+const uint8_t EOF_MEMBER[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+unsigned gf2_mulmod_h(unsigned a, unsigned b) { unsigned m = 1u << 31, p = 0; for (;;) { if (a & m) { p ^= b; if ((a & (m - 1)) == 0) break; } m >>= 1; b = (b & 1) ? (b >> 1) ^ 0xedb88320u : b >> 1; } return p; }
+
+// d_data: n bytes in HBM (readable as they are: the kernel never reads behind them)
+lcd_deflated_t *deflate_dev(const uint8_t *d_data, size_t n, int block_payload, int add_eof, hipStream_t st) {
+    const std::string W = "lcd_bgzf_deflate_dev";
+    if (block_payload == 0) block_payload = 0xff00;
+    if (block_payload < 1 || block_payload > 0xff00) { set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00"); return nullptr; }
+    const size_t nb = (n + (size_t)block_payload - 1) / (size_t)block_payload;
+    if (nb > (size_t)1 << 30) { set_err(-4, W + ": too many blocks"); return nullptr; }
+    std::unique_ptr<lcd_deflated_s> h(new lcd_deflated_s());
+    h->device = cur_device(); h->n_blocks = nb; h->eof = add_eof != 0;
+    auto hipfail = [&](const char *what) -> lcd_deflated_t * { (void)hipGetLastError(); set_err(-10, W + ": HIP call failed: " + what); return nullptr; };
+#define DCHK(x) do { if ((x) != hipSuccess) return hipfail(#x); } while (0)
+    std::vector<unsigned long long> offs(nb + 1, 0);
+    if (nb) {
+        const unsigned stride = (unsigned)lcd_align_up((uint64_t)block_payload + 5 + 16, 16);
+        const int grid = (int)std::min<size_t>(nb, 2048);
+        DevBuf d_slots, d_toks, d_outs, d_offs;
+        if (d_slots.ensure(nb * (size_t)stride + 64, 31) || d_toks.ensure((size_t)grid * (size_t)block_payload * 4 + 64, 31) || d_outs.ensure(nb * sizeof(DeflateOut), 31) ||
+            d_offs.ensure(nb * 8, 31)) return nullptr;
+        { unsigned t[32]; unsigned p = 1u << 30; t[0] = p; for (int k = 1; k < 32; ++k) t[k] = p = gf2_mulmod_h(p, p); lcd_deflate_set_x2n(t, st); }
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        DCHK(hipEventCreate(&ev[0]));
+        if (hipEventCreate(&ev[1]) != hipSuccess) { (void)hipEventDestroy(ev[0]); return hipfail("hipEventCreate"); }
+        auto drop = [&]() { (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); };
+#define ECHK(x) do { if ((x) != hipSuccess) { drop(); return hipfail(#x); } } while (0)
+        ECHK(hipEventRecord(ev[0], st));
+        lcd_launch_deflate(d_data, (unsigned long long)n, block_payload, (int)nb, (uint8_t *)d_slots.p, stride, (unsigned *)d_toks.p, (DeflateOut *)d_outs.p, grid, st);
+        ECHK(hipGetLastError());
+        h->outs.resize(nb);
+        ECHK(hipMemcpyAsync(h->outs.data(), d_outs.p, nb * sizeof(DeflateOut), hipMemcpyDeviceToHost, st));
+        ECHK(hipStreamSynchronize(st));
+        h->payloads.resize(nb);
+        for (size_t i = 0; i < nb; ++i) {
+            h->payloads[i] = (uint32_t)std::min<size_t>((size_t)block_payload, n - i * (size_t)block_payload);
+            if (h->outs[i].clen > h->payloads[i] + 5u) { drop(); set_err(-24, W + ": a member exceeds its stored size"); return nullptr; }
+            offs[i + 1] = offs[i] + 18ull + h->outs[i].clen + 8ull;
+        }
+        h->size = (size_t)offs[nb] + (add_eof ? 28 : 0);
+        if (h->image.ensure(h->size + 64, 31)) { drop(); return nullptr; }
+        ECHK(hipMemcpyAsync(d_offs.p, offs.data(), nb * 8, hipMemcpyHostToDevice, st));
+        lcd_launch_deflate_pack((const uint8_t *)d_slots.p, stride, (const DeflateOut *)d_outs.p, (const unsigned long long *)d_offs.p, (uint8_t *)h->image.p, (unsigned long long)n,
+                                block_payload, (int)nb, st);
+        ECHK(hipGetLastError());
+        ECHK(hipEventRecord(ev[1], st));
+        if (add_eof) ECHK(hipMemcpyAsync((uint8_t *)h->image.p + offs[nb], EOF_MEMBER, 28, hipMemcpyHostToDevice, st));
+        ECHK(hipStreamSynchronize(st));
+        float ms = 0; (void)hipEventElapsedTime(&ms, ev[0], ev[1]);     // both kernels and the size round trip between them
+        h->ms_kernel = ms;
+        drop();
+#undef ECHK
+    } else {
+        h->size = add_eof ? 28 : 0;
+        if (h->size) { if (h->image.ensure(h->size + 64, 31)) return nullptr; DCHK(hipMemcpyAsync(h->image.p, EOF_MEMBER, 28, hipMemcpyHostToDevice, st)); DCHK(hipStreamSynchronize(st)); }
+    }
+#undef DCHK
+    return h.release();
+}
+} // namespace
+
+extern "C" {
+
+lcd_deflated_t *lcd_bgzf_deflate_dev_ptr(uint64_t dev_ptr, size_t n, int block_payload, int add_eof) {
+    if (ensure_init()) return nullptr;
+    if (n && !dev_ptr) { set_err(-4, "lcd_bgzf_deflate_dev_ptr: NULL device pointer"); return nullptr; }
+    StreamGuard st; if (st.create()) return nullptr;
+    return deflate_dev((const uint8_t *)(uintptr_t)dev_ptr, n, block_payload, add_eof, st);
+}
+lcd_deflated_t *lcd_bgzf_deflate_dev(const uint8_t *data, size_t n, int block_payload, int add_eof) {
+    if (ensure_init()) return nullptr;
+    if (n && !data) { set_err(-4, "lcd_bgzf_deflate_dev: NULL data"); return nullptr; }
+    StreamGuard st; if (st.create()) return nullptr;
+    DevBuf d_in;
+    if (n) {
+        if (d_in.ensure(n + 64, 31)) return nullptr;
+        if (hipMemcpyAsync(d_in.p, data, n, hipMemcpyHostToDevice, st) != hipSuccess) { (void)hipGetLastError(); set_err(-10, "lcd_bgzf_deflate_dev: upload failed"); return nullptr; }
+    }
+    return deflate_dev((const uint8_t *)d_in.p, n, block_payload, add_eof, st);   // (synchronised before d_in leaves scope)
+}
+size_t lcd_deflated_size(const lcd_deflated_t *h) { return h ? h->size : 0; }
+size_t lcd_deflated_n_blocks(const lcd_deflated_t *h) { return h ? h->n_blocks : 0; }
+double lcd_deflated_kernel_ms(const lcd_deflated_t *h) { return h ? h->ms_kernel : 0; }
+int lcd_deflated_block_info(const lcd_deflated_t *h, size_t i, uint32_t *payload, uint32_t *bsize, int *kind) {
+    if (!h || i >= h->n_blocks) return set_err(-4, "lcd_deflated_block_info: no such block");
+    if (payload) *payload = h->payloads[i];
+    if (bsize) *bsize = 18u + h->outs[i].clen + 8u;
+    if (kind) *kind = (int)h->outs[i].kind;
+    return 0;
+}
+int lcd_deflated_to_host(const lcd_deflated_t *h, size_t off, size_t n, uint8_t *out) {
+    if (!h || off + n > h->size) return set_err(-41, "lcd_deflated_to_host: range past the end of the image");
+    if (n == 0) return 0;
+    if (use_device(h->device)) return -1;
+    HIPCHK(hipMemcpy(out, (const uint8_t *)h->image.p + off, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+void lcd_deflated_free(lcd_deflated_t *h) { delete h; }
+
+// ---- HP / PS rewrite of a chunk's records ----
+lcd_tagged_t *lcd_chunk_tag_records(const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, int n_skip_kept, int n_skip_filtered) {
+    const std::string W = "lcd_chunk_tag_records";
+    if (!c || !c->from_bam) { set_err(-4, W + ": the chunk was not made from a BAM"); return nullptr; }
+    if (c->n_reads > 0 && (!haps || !phase_sets)) { set_err(-4, W + ": NULL haps / phase_sets"); return nullptr; }
+    if (n_skip_kept < 0 || n_skip_filtered < 0) { set_err(-4, W + ": negative skip count"); return nullptr; }
+    if (use_device(c->device)) return nullptr;
+    std::unique_ptr<lcd_tagged_s> h(new lcd_tagged_s());
+    h->device = c->device;
+    const uint64_t base = c->stream ? lcd_inflated_dev_ptr(c->stream) : 0, usize = c->stream ? lcd_inflated_size(c->stream) : 0;
+    std::vector<BamTagJob> jobs;
+    int sk = n_skip_kept, sf = n_skip_filtered;
+    for (size_t i = 0; i < c->rec_beg.size(); ++i) {
+        const int r = c->rec_read[i];
+        if (r >= 0 ? sk > 0 : sf > 0) { --(r >= 0 ? sk : sf); continue; }
+        if (c->rec_stop[i] > usize || c->rec_beg[i] + 36 > c->rec_stop[i] || r >= c->n_reads) { set_err(-4, W + ": record outside the stream"); return nullptr; }
+        BamTagJob j; j.src = base + c->rec_beg[i]; j.len = (uint32_t)(c->rec_stop[i] - c->rec_beg[i]); j.kept = r >= 0; j.hap = r >= 0 ? haps[r] : 0; j.pad = 0; j.ps = r >= 0 ? phase_sets[r] : 0;
+        jobs.push_back(j);
+    }
+    const int n = (int)jobs.size();
+    h->n_records = n;
+    if (n == 0) return h.release();
+    StreamGuard st; if (st.create()) return nullptr;
+    DevBuf d_jobs, d_outs;
+    if (d_jobs.ensure((size_t)n * sizeof(BamTagJob), 31) || d_outs.ensure((size_t)n * sizeof(BamTagOut), 31)) return nullptr;
+    auto hipfail = [&](const char *what) -> lcd_tagged_t * { (void)hipGetLastError(); set_err(-10, W + ": HIP call failed: " + what); return nullptr; };
+#define TCHK(x) do { if ((x) != hipSuccess) return hipfail(#x); } while (0)
+    TCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)n * sizeof(BamTagJob), hipMemcpyHostToDevice, st));
+    lcd_launch_bam_tag_measure((const BamTagJob *)d_jobs.p, (BamTagOut *)d_outs.p, n, st);
+    TCHK(hipGetLastError());
+    std::vector<BamTagOut> outs(n);
+    TCHK(hipMemcpyAsync(outs.data(), d_outs.p, (size_t)n * sizeof(BamTagOut), hipMemcpyDeviceToHost, st));
+    TCHK(hipStreamSynchronize(st));
+    uint64_t tot = 0;
+    for (int i = 0; i < n; ++i) {
+        const BamTagOut &o = outs[i];
+        if (o.hp_end < o.hp_beg || o.ps_end < o.ps_beg || o.hp_end > jobs[i].len || o.ps_end > jobs[i].len || o.new_len < 36 || o.new_len > jobs[i].len + 14) { set_err(-24, W + ": inconsistent measure pass"); return nullptr; }
+        outs[i].dst = tot; tot += o.new_len;
+    }
+    h->size = (size_t)tot;
+    if (h->out.ensure((size_t)tot + 64, 31)) return nullptr;
+    TCHK(hipMemcpyAsync(d_outs.p, outs.data(), (size_t)n * sizeof(BamTagOut), hipMemcpyHostToDevice, st));
+    lcd_launch_bam_tag_emit((const BamTagJob *)d_jobs.p, (const BamTagOut *)d_outs.p, (uint8_t *)h->out.p, n, st);
+    TCHK(hipGetLastError());
+    TCHK(hipStreamSynchronize(st));
+#undef TCHK
+    return h.release();
+}
+uint64_t lcd_tagged_dev_ptr(const lcd_tagged_t *h) { return h ? h->out.addr() : 0; }
+size_t lcd_tagged_size(const lcd_tagged_t *h) { return h ? h->size : 0; }
+int lcd_tagged_n_records(const lcd_tagged_t *h) { return h ? h->n_records : 0; }
+int lcd_tagged_to_host(const lcd_tagged_t *h, size_t off, size_t n, uint8_t *out) {
+    if (!h || off + n > h->size) return set_err(-41, "lcd_tagged_to_host: range past the end of the records");
+    if (n == 0) return 0;
+    if (use_device(h->device)) return -1;
+    HIPCHK(hipMemcpy(out, (const uint8_t *)h->out.p + off, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+void lcd_tagged_free(lcd_tagged_t *h) { delete h; }
+
+} // extern "C"

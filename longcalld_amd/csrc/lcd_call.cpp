@@ -1,5 +1,6 @@
 // lcd_call.cpp -- the germline path joined end to end: lcd_chunks_call (first round, noisy-region rounds, cross-chunk stitch, genotype records, VCF body lines
-// for a pipeline step's chunks of one contig) and lcd_call_bam_regions (the same from an indexed BAM and a FASTA).  Every stage is an export of its own
+// for a pipeline step's chunks of one contig), lcd_call_bam_regions (the same from an indexed BAM and a FASTA) and the phased alignment file beside it
+// (lcd_write_phased_bam, lcd_call_bam_regions_out).  Every stage is an export of its own
 // (lcd_first_round.cpp, lcd_chunk_vars.cpp, lcd_emit.cpp, lcd_chunk.cpp, lcd_io.cpp); this file only composes them as collect_var_main / stitch_var_main /
 // make_var_main do (src/collect_var.c:2897-3000).
 #include "lcd_host_internal.h"
@@ -103,13 +104,86 @@ int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const
     return 0;
 }
 
+// write_read_to_bam for every region of a call (src/bam_utils.c:1944-2048, called from the output step at src/call_var_main.c:801): the input's header block plus
+// one @PG line, then per region its records with HP:i / PS:i rewritten in HBM (lcd_chunk_tag_records) and compressed there (lcd_bgzf_deflate_dev_ptr); only
+// compressed bytes come down, and they go to the file with fwrite.  A region leaves out the records the region before it already wrote: its kept and its filtered
+// records that overlap that region's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691) -- in a sorted file they are the first ones.
+int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) {
+    const std::string W = "lcd_write_phased_bam";
+    if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
+    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
+    if (out->block_payload < 0 || out->block_payload > 0xff00) return set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00");
+    for (int c = 0; c < n; ++c) {
+        const lcd_chunk_s *k = chunks[c].first.chunk;
+        if (!k || !k->from_bam) return set_err(-4, W + ": chunk " + std::to_string(c) + " was not made from a BAM");
+        if (k->n_reads > 0 && (!chunks[c].first.state || !chunks[c].first.state->haps || !chunks[c].first.state->phase_sets || chunks[c].first.state->n_reads != k->n_reads))
+            return set_err(-4, W + ": chunk " + std::to_string(c) + " has no final haplotypes (call lcd_chunks_call first)");
+    }
+    std::vector<uint8_t> hdr;
+    if (lcd_io_bam_header(in_bam_path, hdr)) return set_err(-30, W + ": " + lcd_io_last_error());
+    if (out->pg_line && out->pg_line[0]) {
+        int l_text = 0; memcpy(&l_text, hdr.data() + 4, 4);
+        size_t te = 8 + (size_t)l_text;
+        while (te > 8 && hdr[te - 1] == 0) --te;                          // (a NUL-padded text: the line goes in front of the padding)
+        std::string add = (te > 8 && hdr[te - 1] != '\n') ? "\n" : "";
+        add += out->pg_line; add += '\n';
+        hdr.insert(hdr.begin() + (long)te, add.begin(), add.end());
+        l_text += (int)add.size(); memcpy(hdr.data() + 4, &l_text, 4);
+    }
+    FILE *f = fopen(out->path, "wb");
+    if (!f) return set_err(-30, W + ": cannot open " + out->path + " for writing");
+    std::vector<uint8_t> buf;
+    auto put = [&](lcd_deflated_t *d) -> int {   // download + fwrite, then free
+        if (!d) return -1;
+        const double t0 = now_ms();
+        const size_t sz = lcd_deflated_size(d);
+        buf.resize(sz + 1);
+        int rc = lcd_deflated_to_host(d, 0, sz, buf.data());
+        if (!rc && sz && fwrite(buf.data(), 1, sz, f) != sz) rc = set_err(-30, W + ": short write on " + out->path);
+        out->ms_deflate += lcd_deflated_kernel_ms(d); out->bytes_file += (int64_t)sz;
+        lcd_deflated_free(d);
+        out->ms_download_write += now_ms() - t0;
+        return rc;
+    };
+    auto fail = [&](int code) { const std::string m = g_err; fclose(f); g_err = m; return code; };
+    if (int rc = put(lcd_bgzf_deflate_dev(hdr.data(), hdr.size(), out->block_payload, 0))) return fail(rc);
+    out->bytes_inflated += (int64_t)hdr.size();
+    for (int c = 0; c < n; ++c) {
+        const lcd_first_chunk_t &x = chunks[c].first; const lcd_chunk_s *k = x.chunk;
+        int nsk = 0, nsf = 0;
+        if (c > 0)
+            for (size_t i = 0; i < k->rec_beg.size(); ++i)
+                if (!(k->rec_endpos[i] < chunks[c - 1].first.reg_beg || k->rec_pos0[i] + 1 > chunks[c - 1].first.reg_end)) ++(k->rec_read[i] >= 0 ? nsk : nsf);
+        const double t0 = now_ms();
+        lcd_tagged_t *t = lcd_chunk_tag_records(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, nsk, nsf);
+        if (!t) return fail(-30);
+        out->ms_tag += now_ms() - t0;
+        int kept = 0, filt = 0;
+        for (int r : k->rec_read) ++(r >= 0 ? kept : filt);
+        out->n_records_out += kept - nsk; out->n_filtered_out += filt - nsf; out->bytes_inflated += (int64_t)lcd_tagged_size(t);
+        lcd_deflated_t *d = lcd_tagged_size(t) ? lcd_bgzf_deflate_dev_ptr(lcd_tagged_dev_ptr(t), lcd_tagged_size(t), out->block_payload, 0) : nullptr;
+        const int rc = lcd_tagged_size(t) ? put(d) : 0;
+        lcd_tagged_free(t);
+        if (rc) return fail(rc);
+    }
+    if (int rc = put(lcd_bgzf_deflate_dev(nullptr, 0, out->block_payload, 1))) return fail(rc);   // the EOF member
+    if (fclose(f) != 0) return set_err(-30, W + ": closing " + out->path + " failed");
+    return 0;
+}
+
 int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
                          int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body) {
+    return lcd_call_bam_regions_out(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, chunks, records, n_records, vcf_body, nullptr);
+}
+
+int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                             int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out) {
     const std::string W = "lcd_call_bam_regions";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (vcf_body) *vcf_body = nullptr;
     if (!bam_path || !bai_path || !fasta_path || !chrom || !cfg || !records || !n_records || !vcf_body) return set_err(-4, W + ": NULL argument");
+    if (bam_out && !bam_out->path) return set_err(-4, W + ": bam_out without a path");
     if (n < 0 || (n > 0 && (!reg_beg || !reg_end || !chunks))) return set_err(-4, W + ": bad region list");
     for (int c = 0; c < n; ++c) if (reg_beg[c] < 1 || reg_end[c] < reg_beg[c] || (c > 0 && reg_beg[c] <= reg_end[c - 1])) return set_err(-4, W + ": regions must be 1-based, non-empty and in genome order");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
@@ -148,7 +222,8 @@ int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char 
         x.chunk = handles[c]; x.ref_seq = refs[c]; x.ref_beg = b0 + 1; x.ref_end = b0 + got; x.reg_beg = reg_beg[c]; x.reg_end = reg_end[c]; x.is_ont = is_ont;
         x.ordered_read_ids = nullptr; x.is_rev = nullptr; x.meta = &metas[c];
     }
-    const int rc = lcd_chunks_call(n, chunks, cfg, chrom, records, n_records, vcf_body);
+    int rc = lcd_chunks_call(n, chunks, cfg, chrom, records, n_records, vcf_body);
+    if (rc == 0 && bam_out) rc = lcd_write_phased_bam(bam_path, n, chunks, bam_out);   // (a failure here leaves the records and the text valid)
     const std::string m = g_err;
     drop_inputs();
     g_err = m;

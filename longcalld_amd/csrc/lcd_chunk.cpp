@@ -246,6 +246,14 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
             if (x.kind == -2) return fail(-33, malformed);
             const int64_t e0 = (int64_t)d.pos + (x.rl > 0 ? x.rl : 1);
             if (d.pos >= reg_end) { done = true; break; }
+            // the record table of the alignment output: the iterator's overlap test applies whatever the flags say; PROJECT RULE (htslib is not in the checkout): a
+            // record with the unmapped flag spans one base, like one whose CIGAR consumes no reference (bam_endpos)
+            const int64_t e0_any = (d.flag & 0x4) ? (int64_t)d.pos + 1 : e0;
+            const bool kept = e0 > reg_beg - 1 && !((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq);
+            if (e0_any > reg_beg - 1) {
+                c->rec_beg.push_back(d.off - 4); c->rec_stop.push_back(d.off + (uint64_t)d.bs); c->rec_read.push_back(kept ? (int)pos0.size() : -1);
+                c->rec_pos0.push_back(d.pos); c->rec_endpos.push_back(e0_any);
+            }
             if (e0 <= reg_beg - 1) continue;
             if ((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq) continue;
             pos0.push_back(d.pos); endp.push_back(e0); mapq.push_back(d.mapq); flag.push_back(d.flag); ncig.push_back(x.nc); qlen.push_back(d.lseq);

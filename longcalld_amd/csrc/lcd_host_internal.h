@@ -245,6 +245,9 @@ struct lcd_chunk_s {
     std::vector<uint8_t> source, pal; uint64_t tag_bytes = 0;   // lcd_chunk_create_from_bam_src: LCD_SRC_* and is_ont_palindrome per read; cs / MD bytes brought to the host
     double stage_ms[4] = {0, 0, 0, 0};                          // ... and its wall-clock split: aux fields, reference comparison, tag download + host parse, digars
     bool from_bam = false; std::vector<uint64_t> aux_off, rec_end;   // lcd_chunk_create_from_bam*: per read its auxiliary fields [aux_off, rec_end) as offsets of the inflated stream (lcd_chunk_read_nm)
+    // lcd_chunk_create_from_bam*: EVERY record the region's iterator yields, in file order (lcd_chunk_tag_records, lcd_write_phased_bam): [rec_beg, rec_stop) of the
+    // inflated stream from its block_size word on, the chunk read id of a kept record or -1 for one the loader's flag / MAPQ filter dropped, pos0 and bam_endpos
+    std::vector<uint64_t> rec_beg, rec_stop; std::vector<int> rec_read; std::vector<int64_t> rec_pos0, rec_endpos;
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use

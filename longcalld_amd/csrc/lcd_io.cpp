@@ -341,6 +341,29 @@ int lcd_io_region_image(const char *bam_path, const char *bai_path, const char *
     return 0;
 }
 
+// the BAM header block of a file as it lies in the inflated stream: magic, l_text, text, n_ref, the reference table
+int lcd_io_bam_header(const char *bam_path, std::vector<uint8_t> &hdr) {
+    hdr.clear();
+    BgzfStream bz;
+    bz.f = fopen(bam_path, "rb");
+    if (!bz.f) return io_err(-30, std::string("cannot open ") + bam_path);
+    if (int rc = bz.seek(0)) return rc;
+    auto take = [&](size_t n) -> int { const size_t o = hdr.size(); hdr.resize(o + n); return n && bz.read(hdr.data() + o, n) != 0 ? io_err(-33, "truncated BAM header") : 0; };
+    if (take(8) || memcmp(hdr.data(), "BAM\1", 4) != 0) return io_err(-33, "not a BAM file");
+    const int l_text = le32(hdr.data() + 4);
+    if (l_text < 0) return io_err(-33, "not a BAM file");
+    if (int rc = take((size_t)l_text)) return rc;
+    if (int rc = take(4)) return rc;
+    const int n_ref = le32(hdr.data() + hdr.size() - 4);
+    for (int i = 0; i < n_ref; ++i) {
+        if (int rc = take(4)) return rc;
+        const int ln = le32(hdr.data() + hdr.size() - 4);
+        if (ln < 0) return io_err(-33, "truncated BAM header");
+        if (int rc = take((size_t)ln + 4)) return rc;
+    }
+    return 0;
+}
+
 extern "C" {
 
 const char *lcd_io_last_error(void) { return g_io_err.c_str(); }

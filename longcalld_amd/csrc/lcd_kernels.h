@@ -20,6 +20,17 @@ void lcd_launch_bam_stat(const BamStatJob *jobs, BamStatOut *outs, int n_jobs, h
 void lcd_launch_bam_cigar(const GatherJob *jobs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_aux(const BamAuxJob *jobs, BamAuxOut *outs, int is_ont, int n_jobs, hipStream_t st);
 void lcd_launch_bam_nm(const BamNmJob *jobs, int *nm, int n_jobs, hipStream_t st);
+// deflate_kernel.hip: BGZF payloads -> raw deflate streams in per-payload slots (one wavefront per payload, `grid` workgroups stride over them; toks: grid x
+// payload words of token workspace), then the members (header, stream, CRC-32, ISIZE) packed at offs[] of the file image
+void lcd_deflate_set_x2n(const unsigned *t32, hipStream_t st);
+void lcd_launch_deflate(const uint8_t *data, unsigned long long n, int payload, int n_blocks, uint8_t *slots, unsigned slot_stride, unsigned *toks, DeflateOut *outs,
+                        int grid, hipStream_t st);
+void lcd_launch_deflate_pack(const uint8_t *slots, unsigned slot_stride, const DeflateOut *outs, const unsigned long long *offs, uint8_t *image, unsigned long long n,
+                             int payload, int n_blocks, hipStream_t st);
+int lcd_deflate_lds_bytes();
+// bam_tag_kernel.hip: HP / PS rewrite of records in the inflated stream: measure (one lane per record), emit (one wavefront per record)
+void lcd_launch_bam_tag_measure(const BamTagJob *jobs, BamTagOut *outs, int n_jobs, hipStream_t st);
+void lcd_launch_bam_tag_emit(const BamTagJob *jobs, const BamTagOut *outs, uint8_t *out, int n_jobs, hipStream_t st);
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st);
 void lcd_launch_compose(const CmpJob *jobs, CmpOut *outs, const CmpSeg *segs, int n_jobs, int emit, hipStream_t stream);
 void lcd_launch_vars_scan(const VarScanJob *jobs, VarScanOut *outs, int n_jobs, hipStream_t stream);

@@ -238,6 +238,15 @@ struct SupChunk { uint64_t read_beg, read_end, iv_off, ivs; int n_reads, pad; };
 struct SupReg { long long st, en; int chunk, pad; };
 // lcd_bam_nm_kernel: a kept record's auxiliary fields [aux, end) as device addresses
 struct BamNmJob { uint64_t aux, end; };
+// ---------------- the phased alignment output (deflate_kernel.hip, bam_tag_kernel.hip) ----------------
+// one BGZF payload's raw deflate stream in its slot: clen bytes, CRC-32 of the payload, kind 0 stored / 1 fixed / 2 dynamic codes, LZ77 tokens
+struct DeflateOut { uint32_t clen, crc, kind, n_tok; };
+// lcd_bam_tag_kernel: one record to write ([src, src + len): its block_size word and body); kept: 1 a chunk read (hap / ps wanted as write_read_to_bam decides),
+// 0 a record the loader filtered (first HP / PS fields deleted)
+struct BamTagJob { uint64_t src; uint32_t len; int kept, hap, pad; long long ps; };
+// what the measure pass found: the record's new length, the first HP / PS field to delete as [beg, end) offsets from src (beg == end: none), flags bit 0 / 1:
+// HP:i / PS:i appended; dst: the record's place in the output (filled by the host's prefix sum)
+struct BamTagOut { uint32_t new_len, hp_beg, hp_end, ps_beg, ps_end, flags; uint64_t dst; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;

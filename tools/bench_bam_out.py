@@ -1,0 +1,106 @@
+"""Measurement of the phased alignment output's GPU side: the deflate kernel (lcd_bgzf_deflate_dev) on the payload classes of tests/test_gpu_deflate.py and on a
+HiFi-shape BAM stream, against Python zlib level 6 (htslib's default) on 16 host threads over the same blocks; and the stage times of the whole writer
+(lcd_call_bam_regions_out's lcd_bam_out_t) on the tests' seeded two-region BAM.  Prints one JSON line; no threshold is set on any number.
+usage: python tools/bench_bam_out.py [MB per payload class, default 32] [repeats, default 3]"""
+import hashlib
+import json
+import os
+import sys
+import tempfile
+import time
+import zlib
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from longcalld_amd import align  # noqa: E402
+from bench_inflate import bam_like  # noqa: E402
+
+BP = 0xff00
+
+
+def source_hash():
+    h = hashlib.sha1()
+    for f in ("deflate_kernel.hip", "bam_tag_kernel.hip", "crc32_gf2.h", "wave_copy.h", "lcd_bam_out.cpp", "lcd_call.cpp"):
+        h.update(open(os.path.join(ROOT, "longcalld_amd", "csrc", f), "rb").read())
+    return h.hexdigest()[:12]
+
+
+def zlib6(chunk):
+    co = zlib.compressobj(6, zlib.DEFLATED, -15)
+    return len(co.compress(chunk) + co.flush()) + 26
+
+
+def one(name, data, reps):
+    blocks = [data[o:o + BP] for o in range(0, len(data), BP)]
+    best, size, kinds = None, 0, [0, 0, 0]
+    for r in range(reps + 1):
+        t0 = time.perf_counter()
+        d = align.bgzf_deflate(data, 0, 1)
+        wall = (time.perf_counter() - t0) * 1e3
+        if r == 0:
+            size = len(d["image"]) - 28
+            for _, _, k in d["blocks"]:
+                kinds[k] += 1
+            assert b"".join(zlib.decompress(d["image"][o + 18:o + 18 + bs - 26], -15) for o, bs in _members(d)) == data   # checked once
+        elif best is None or d["kernel_ms"] < best[0]:
+            best = (d["kernel_ms"], wall)
+    with ThreadPoolExecutor(16) as ex:
+        t0 = time.perf_counter(); zsize = sum(ex.map(zlib6, blocks, chunksize=4)); th = time.perf_counter() - t0
+    return dict(name=name, mb=round(len(data) / 2**20, 1), blocks=len(blocks), kernel_ms=round(best[0], 3), call_ms=round(best[1], 1), GBps_in=round(len(data) / best[0] / 1e6, 2),
+                ratio=round(size / len(data), 4), zlib6_ratio=round(zsize / len(data), 4), size_vs_zlib6=round(size / zsize, 3), kinds_stored_fixed_dynamic=kinds,
+                host_zlib6_16_threads_GBps_in=round(len(data) / th / 1e9, 3))
+
+
+def _members(d):
+    o = 0
+    for _, bs, _ in d["blocks"]:
+        yield o, bs
+        o += bs
+
+
+def writer_stages():
+    """lcd_bam_out_t of lcd_call_bam_regions_out on the tests' two-region seed (small: the stage split, not a throughput)"""
+    import call_chunks_common as kc
+    import clean_vars_common as cc
+    from test_gpu_clean_vars import write_chunk_bam
+    whole = cc.make_diploid_chunk(kc.SEED_FLIP, ref_len=12000, depth=12)
+    chs = kc.split_chunk(whole, [6000])
+    with tempfile.TemporaryDirectory() as tmp:
+        bam, fa, out = os.path.join(tmp, "in.bam"), os.path.join(tmp, "ref.fa"), os.path.join(tmp, "out.bam")
+        write_chunk_bam(whole, bam)
+        kc.write_fasta(fa, "chr11", whole)
+        cfg = align.call_cfg(0, pass_=dict(max_noisy_reg_len=kc.TWO_CHUNK_MAX_LEN))
+        best = None
+        for _ in range(3):
+            t0 = time.perf_counter()
+            got = align.call_bam_regions(bam, bam + ".bai", fa, "chr11", [c["reg_beg"] for c in chs], [c["reg_end"] for c in chs], min_mapq=30, cfg=cfg,
+                                         bam_out=dict(path=out, pg_line="@PG\tID:longcalld_amd"))
+            wall = (time.perf_counter() - t0) * 1e3
+            assert got["bam_out_rc"] == 0, got["bam_out_error"]
+            b = dict(got["bam_out"], call_ms=round(wall, 1))
+            if best is None or b["ms_tag"] + b["ms_deflate"] + b["ms_download_write"] < best["ms_tag"] + best["ms_deflate"] + best["ms_download_write"]:
+                best = b
+    return {k: (round(v, 3) if isinstance(v, float) else v) for k, v in best.items()}
+
+
+def main():
+    mb = int(sys.argv[1]) if len(sys.argv) > 1 else 32
+    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+    from test_gpu_deflate import _payloads
+    P = _payloads(np.random.default_rng(5))
+    res = dict(source=source_hash(), block_payload=BP, classes=[])
+    for name in ("text", "bam", "skew", "run", "random", "far", "zeros_then_text"):
+        blk = (P[name] * (BP // len(P[name]) + 1))[:BP]
+        res["classes"].append(one(name, blk * ((mb << 20) // BP), reps))
+    res["classes"].append(one("hifi_bam_stream", bam_like(np.random.default_rng(1), mb << 20), reps))
+    res["writer"] = writer_stages()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
