@@ -893,6 +893,112 @@ int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const c
                              const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
                              lcd_bam_out_t *bam_out);
 
+/* ---- a whole BAM in one call (longcallD call ref.fa in.bam -o out.vcf -b out.bam): call_var_worker_pipeline, src/call_var_main.c:762-815, germline path ----
+ * lcd_bam_contigs: the reference table of the BAM header, in header order.  *names: n malloc()'d strings in a malloc()'d array, *lens malloc()'d; release with
+ * lcd_bam_contigs_free.  Returns 0 or < 0 (lcd_last_error).
+ * lcd_bam_sample_name == extract_sample_name_from_bam_header (src/bam_utils.c:2051-2070): the SM of the first @RG line that has one (a later, different SM does not
+ * replace it); *name malloc()'d (free()), or NULL when no @RG line carries SM -- the caller then falls back to the BAM path (src/call_var_main.c:733-735). */
+int lcd_bam_contigs(const char *bam_path, int *n_contigs, char ***names, int64_t **lens);
+void lcd_bam_contigs_free(int n_contigs, char **names, int64_t *lens);
+int lcd_bam_sample_name(const char *bam_path, char **name);
+/* lcd_plan_chunks == collect_regions (src/call_var_main.c:404-634) + the fallback of :744-749, host code without a device: the (tid, reg_beg, reg_end) entries, 1-based
+ * inclusive, in processing order.
+ *   classes      classify_chromosome as written: an optional "chr" prefix is removed; X / Y are sex chromosomes; M / MT are other; a name strtol consumes completely
+ *                with a value >= 1 is an autosome (no upper bound: chr23 is one, chr1_random is not).  LCD_CTG_AUTOSOME_XY keeps autosomes and sex chromosomes,
+ *                LCD_CTG_AUTOSOME autosomes, LCD_CTG_ALL every contig.  `exclude` (-E) names are always left out;
+ *   whole genome per kept contig ceil(len / chunk_len) chunks [i L + 1, min((i + 1) L, len)];
+ *   regions      "chr", "chr:beg", "chr:beg-end" (commas in numbers ignored; a string that is a contig name as a whole is that contig), clamped to the contig
+ *                (beg = max(1, beg), end = min(end, len)), each cut into chunks from its own beg.  Regions or a BED file switch the classes off, not `exclude`; with
+ *                both, the strings win.  An unknown contig or an empty interval plans nothing;
+ *   BED          '#' lines are skipped, an unknown contig is skipped, "chr" alone is the whole contig, column 2 is 0-based (+ 1), a missing column 3 is the contig's
+ *                end, a line with beg > end or a non-positive bound is skipped; a last line without a newline counts;
+ *   several      PROJECT RULE (the reference hands them to htslib's sam_itr_regarray, which is not in the checkout): regions are grouped by contig in header order,
+ *                sorted by begin inside a contig, and regions that overlap (beg <= previous end) are merged;
+ *   fallback     when nothing is planned, the whole file is planned with the classes off (`exclude` still applies) and out->fallback = 1.
+ * chunk_len 0 = 500 000 (LONGCALLD_BAM_CHUNK_REG_SIZE).  The reference's steps (reg_chunks, min_reg_chunks_per_run) are not reproduced: a step boundary only falls
+ * where the contig changes and neighbours of another contig are ignored, so they cannot change a result.  The neighbour of an entry is the previous / next entry
+ * when it has the same tid.  Arrays malloc()'d; lcd_chunk_plan_free.  Returns the number of entries or < 0 (an unreadable BED file: -30). */
+enum { LCD_CTG_AUTOSOME_XY = 0, LCD_CTG_AUTOSOME = 1, LCD_CTG_ALL = 2 };
+typedef struct lcd_chunk_plan_t { int n; int *tid; int64_t *reg_beg, *reg_end; int fallback; } lcd_chunk_plan_t;
+int lcd_plan_chunks(int n_contigs, const char *const *names, const int64_t *lens, int contig_mode, int n_exclude, const char *const *exclude, int n_regions,
+                    const char *const *regions, const char *region_bed_path, int64_t chunk_len, lcd_chunk_plan_t *out);
+void lcd_chunk_plan_free(lcd_chunk_plan_t *p);
+/* The stitch carried across windows of chunks.  flip_variant_hap(pre, cur) reads pre's FINAL state (src/collect_var.c:1640-1695): its down overlap list, is_skipped,
+ * haps, phase_sets and n_vars.  lcd_stitch_carry_t owns copies of those arrays of a window's last chunk (taken after that chunk's own join and swap) with the
+ * chunk's tid and region.  lcd_stitch_chunks_carry: the first chunk is joined to carry_in (when given, valid and of the same tid), then lcd_stitch_chunks over the n
+ * chunks, then carry_out (when given) is set from the last chunk (n == 0: carry_out becomes a copy of carry_in).  carry_in == carry_out is allowed.  The caller
+ * sets carry_out->reg_beg / reg_end (lcd_chunk_phase_t has no region).  A zeroed struct is an empty carry; lcd_stitch_carry_free releases one.  Returns 0 or -6. */
+typedef struct lcd_stitch_carry_t {
+    int valid, tid; int64_t reg_beg, reg_end;
+    int n_reads, n_vars, n_down_ovlp;
+    uint8_t *is_skipped; int *haps; int64_t *phase_sets; int *down_ovlp_read_i;
+} lcd_stitch_carry_t;
+int lcd_stitch_chunks_carry(lcd_chunk_phase_t *chunks, int n_chunks, int update_reads, const lcd_stitch_carry_t *carry_in, lcd_stitch_carry_t *carry_out);
+void lcd_stitch_carry_free(lcd_stitch_carry_t *c);
+/* Two-phase chunk creation: a region is read and inflated ONCE for every kind of input.  lcd_chunk_open_from_bam does lcd_chunk_create_from_bam_src's region image,
+ * inflate, record walk, CIGAR statistics, loader's rule and record table, and fills meta (so the reads' span is known); lcd_chunk_resolve(chunk, src or NULL) does
+ * the sources, the comparison with the window, the cs / MD words and the digar launch.  What the second phase needs (the CIGAR words in HBM and their offsets, the
+ * counts, the aux jobs, the true reference lengths) stays in the handle until lcd_chunk_resolve and is released there.  lcd_chunk_create_from_bam_src is open
+ * followed by resolve.  A handle that was opened and not resolved is refused (-4) by every export that needs digars; lcd_chunk_destroy frees it.  lcd_chunk_resolve
+ * on a resolved handle (or one not made by lcd_chunk_open_from_bam) is -4; on failure the handle stays unresolved and is only good for lcd_chunk_destroy. */
+lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
+                                     int min_mapq, int verify_crc, struct lcd_bam_reads_t *meta);
+int lcd_chunk_resolve(lcd_chunk_t *chunk, const lcd_chunk_src_t *src);
+/* The appendable phased-BAM writer.  open: the input's header block with out->pg_line appended, in its own BGZF member(s); the counters of *out are zeroed and then
+ * accumulate.  append: the records of n called chunks in order (lcd_chunk_tag_records + lcd_bgzf_deflate_dev_ptr per chunk); a chunk leaves out the records that
+ * overlap the region of the chunk before it when both are on the same contig (tids[c] == tids[c - 1]; tids NULL: all the same) -- across a window border that chunk
+ * is described by prev (NULL: none; prev->valid, tid, reg_beg, reg_end are read).  close: the one EOF member and fclose; lcd_bam_writer_abort closes the file as
+ * it is, without the EOF member.  Both free the writer.  lcd_write_phased_bam is open + one append + close.  *out must outlive the writer. */
+typedef struct lcd_bam_writer_s lcd_bam_writer_t;
+lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out);
+int lcd_bam_writer_append(lcd_bam_writer_t *w, int n_chunks, const lcd_call_chunk_t *chunks, const int *tids, const lcd_stitch_carry_t *prev);
+int lcd_bam_writer_close(lcd_bam_writer_t *w);
+void lcd_bam_writer_abort(lcd_bam_writer_t *w);
+/* The VCF writer.  path NULL or "-": stdout.  bgzf 0: plain text through fwrite; 1 (-O z): every append is compressed by lcd_bgzf_deflate_dev into BGZF members
+ * of its own and close adds the EOF member.  header_text NULL: no header (-H).  lcd_vcf_writer_abort closes without the EOF member. */
+typedef struct lcd_vcf_writer_s lcd_vcf_writer_t;
+lcd_vcf_writer_t *lcd_vcf_writer_open(const char *path, int bgzf, const char *header_text);
+int lcd_vcf_writer_append(lcd_vcf_writer_t *w, const char *text);
+int lcd_vcf_writer_close(lcd_vcf_writer_t *w);
+void lcd_vcf_writer_abort(lcd_vcf_writer_t *w);
+/* lcd_call_file: the whole-file run.  The plan (lcd_plan_chunks on the BAM header) is processed in windows of window_chunks consecutive entries (a window may span
+ * contigs).  Per window -- load: every chunk is opened (lcd_chunk_open_from_bam, up to loader_threads host threads), its reference window fetched around the reads'
+ * span with get_bam_chunk_reg_ref_seq0's padding, and resolved with that window (one file read and one inflate per chunk); a chunk without reads stays as an empty
+ * entry: it yields nothing, but it is still the neighbour of the chunks beside it.  call: the body of lcd_chunks_call with a contig per chunk, the first chunk's up
+ * list taken against the carried region, the last chunk's down list against the next PLANNED region, and lcd_stitch_chunks_carry (update_reads = 1).  write: the
+ * text to the VCF writer, the window to the BAM writer; then the window is freed: nothing of it stays but the carry.  overlap 1: the three stages run on three host
+ * threads joined by queues of depth one (at most three windows alive); 0: in turn on the calling thread.  Records, text, flips and the output BAM's record stream do
+ * not depend on window_chunks, overlap or loader_threads.  The first error stops the pipeline, every thread is joined, both outputs are closed as they are (no EOF
+ * member) and the failing stage's code and lcd_last_error are returned.  Somatic / refine settings: -2.  A missing .bai / .fai: -30 with the path in the message.
+ * Defaults: chunk_len 0 = 500 000; window_chunks 0 = 32 (HiFi) / 16 (ONT); overlap -1 = 0 (pipelining did not win reliably where it was measured, profiles/NOTES_call_file.md);
+ * loader_threads 0 = 4, or the CPUs the process may use when fewer (an explicit value is cut to 16); bai_path NULL =
+ * <bam>.bai; sample_name NULL = lcd_bam_sample_name, else the BAM path; vcf_path NULL or "-" = stdout.  The VCF header names every contig of the BAM header.
+ * keep_records != 0: the records of all windows, the per-chunk flips and n_passes are also kept in *stats (tests).  Whatever the return code, release *stats with
+ * lcd_file_stats_free (after an error it holds what the finished windows left). */
+typedef struct lcd_file_job_t {
+    const char *bam_path, *bai_path, *fasta_path;
+    int contig_mode; int n_exclude; const char *const *exclude;
+    int n_regions; const char *const *regions; const char *region_bed_path;
+    int64_t chunk_len;
+    int window_chunks, overlap, loader_threads, min_mapq;
+    const char *vcf_path; int vcf_bgzf, no_vcf_header; const char *sample_name, *source_version, *cmdline, *date_yyyymmdd;
+    lcd_bam_out_t *bam_out;
+    int keep_records;
+} lcd_file_job_t;
+typedef struct lcd_file_stats_t {
+    int n_planned, n_loaded, n_empty, n_windows, plan_fallback;
+    int64_t n_reads, n_records, n_vcf_lines, n_region_loads;
+    double ms_load, ms_call, ms_write, ms_wall;
+    int64_t peak_device_bytes;                         /* the ledger of the library's device buffers, sampled after every stage */
+    /* keep_records: */
+    int n_chunks; int *chunk_tid; int64_t *chunk_reg_beg, *chunk_reg_end; int *chunk_n_reads, *chunk_n_passes, *chunk_flip_hap, *chunk_n_records;
+    int64_t *chunk_flip_pre_PS, *chunk_flip_cur_PS;
+    lcd_var1_t *records; int n_kept_records;
+} lcd_file_stats_t;
+void lcd_file_job_default(lcd_file_job_t *job);     /* zeroes; overlap = -1 */
+int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats);
+void lcd_file_stats_free(lcd_file_stats_t *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,46 @@ class LcdBamOut(C.Structure):
         (n, C.c_double) for n in ("ms_tag", "ms_deflate", "ms_download_write")]
 
 
+class LcdChunkPhase(C.Structure):
+    """lcd_chunk_phase_t: one chunk of the cross-chunk stitch"""
+    _i32p, _i64p, _u8p = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_uint8)
+    _fields_ = [("tid", C.c_int), ("n_reads", C.c_int), ("n_vars", C.c_int), ("ordered_read_ids", _i32p), ("is_skipped", _u8p), ("haps", _i32p), ("phase_sets", _i64p),
+                ("var_phase_set", _i64p), ("hap_to_cons_alle", _i32p), ("n_up_ovlp", C.c_int), ("n_down_ovlp", C.c_int), ("up_ovlp_read_i", _i32p), ("down_ovlp_read_i", _i32p),
+                ("flip_hap", C.c_int), ("flip_pre_PS", C.c_int64), ("flip_cur_PS", C.c_int64)]
+
+
+class LcdStitchCarry(C.Structure):
+    """lcd_stitch_carry_t: what the stitch of the next window reads of a window's last chunk"""
+    _fields_ = [("valid", C.c_int), ("tid", C.c_int), ("reg_beg", C.c_int64), ("reg_end", C.c_int64), ("n_reads", C.c_int), ("n_vars", C.c_int), ("n_down_ovlp", C.c_int),
+                ("is_skipped", C.POINTER(C.c_uint8)), ("haps", C.POINTER(C.c_int)), ("phase_sets", C.POINTER(C.c_int64)), ("down_ovlp_read_i", C.POINTER(C.c_int))]
+
+
+class LcdChunkPlan(C.Structure):
+    """lcd_chunk_plan_t: the (tid, reg_beg, reg_end) entries of lcd_plan_chunks"""
+    _fields_ = [("n", C.c_int), ("tid", C.POINTER(C.c_int)), ("reg_beg", C.POINTER(C.c_int64)), ("reg_end", C.POINTER(C.c_int64)), ("fallback", C.c_int)]
+
+
+class LcdFileJob(C.Structure):
+    """lcd_file_job_t: one whole-file run of lcd_call_file"""
+    _fields_ = [("bam_path", C.c_char_p), ("bai_path", C.c_char_p), ("fasta_path", C.c_char_p), ("contig_mode", C.c_int), ("n_exclude", C.c_int),
+                ("exclude", C.POINTER(C.c_char_p)), ("n_regions", C.c_int), ("regions", C.POINTER(C.c_char_p)), ("region_bed_path", C.c_char_p), ("chunk_len", C.c_int64),
+                ("window_chunks", C.c_int), ("overlap", C.c_int), ("loader_threads", C.c_int), ("min_mapq", C.c_int), ("vcf_path", C.c_char_p), ("vcf_bgzf", C.c_int),
+                ("no_vcf_header", C.c_int), ("sample_name", C.c_char_p), ("source_version", C.c_char_p), ("cmdline", C.c_char_p), ("date_yyyymmdd", C.c_char_p),
+                ("bam_out", C.POINTER(LcdBamOut)), ("keep_records", C.c_int)]
+
+
+class LcdFileStats(C.Structure):
+    """lcd_file_stats_t: the counters of lcd_call_file (and, with keep_records, the per-chunk results and the records)"""
+    _i32p, _i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+    _fields_ = [(n, C.c_int) for n in ("n_planned", "n_loaded", "n_empty", "n_windows", "plan_fallback")] + [
+        (n, C.c_int64) for n in ("n_reads", "n_records", "n_vcf_lines", "n_region_loads")] + [(n, C.c_double) for n in ("ms_load", "ms_call", "ms_write", "ms_wall")] + [
+        ("peak_device_bytes", C.c_int64), ("n_chunks", C.c_int), ("chunk_tid", _i32p), ("chunk_reg_beg", _i64p), ("chunk_reg_end", _i64p), ("chunk_n_reads", _i32p),
+        ("chunk_n_passes", _i32p), ("chunk_flip_hap", _i32p), ("chunk_n_records", _i32p), ("chunk_flip_pre_PS", _i64p), ("chunk_flip_cur_PS", _i64p),
+        ("records", C.POINTER(LcdVar1)), ("n_kept_records", C.c_int)]
+
+
+LCD_CTG_AUTOSOME_XY, LCD_CTG_AUTOSOME, LCD_CTG_ALL = 0, 1, 2
+
 _lib = None
 
 # every symbol include/lcd_hotpath.h declares (tests check the .so exports all of them)
@@ -194,6 +234,9 @@ EXPORTS = [
     "lcd_cfg_default", "lcd_chunks_call", "lcd_call_bam_regions", "lcd_call_free",
     "lcd_bgzf_deflate_dev", "lcd_bgzf_deflate_dev_ptr", "lcd_deflated_size", "lcd_deflated_n_blocks", "lcd_deflated_kernel_ms", "lcd_deflated_block_info", "lcd_deflated_to_host", "lcd_deflated_free",
     "lcd_chunk_tag_records", "lcd_tagged_dev_ptr", "lcd_tagged_size", "lcd_tagged_n_records", "lcd_tagged_to_host", "lcd_tagged_free", "lcd_write_phased_bam", "lcd_call_bam_regions_out",
+    "lcd_bam_contigs", "lcd_bam_contigs_free", "lcd_bam_sample_name", "lcd_plan_chunks", "lcd_chunk_plan_free", "lcd_stitch_chunks_carry", "lcd_stitch_carry_free",
+    "lcd_chunk_open_from_bam", "lcd_chunk_resolve", "lcd_bam_writer_open", "lcd_bam_writer_append", "lcd_bam_writer_close", "lcd_bam_writer_abort",
+    "lcd_vcf_writer_open", "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_call_file", "lcd_file_stats_free",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -326,6 +369,37 @@ def load_library():
         getattr(lib, f).argtypes = [C.c_void_p]
         getattr(lib, f).restype = None
     lib.lcd_call_free.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdVar1), C.c_int, C.c_void_p]
+    strv, i64p_ = C.POINTER(C.c_char_p), C.POINTER(C.c_int64)
+    lib.lcd_bam_contigs.argtypes = [C.c_char_p, i32p, C.POINTER(C.POINTER(C.c_void_p)), C.POINTER(i64p_)]
+    lib.lcd_bam_contigs_free.argtypes = [C.c_int, C.POINTER(C.c_void_p), i64p_]
+    lib.lcd_bam_contigs_free.restype = None
+    lib.lcd_bam_sample_name.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    lib.lcd_plan_chunks.argtypes = [C.c_int, strv, i64p_, C.c_int, C.c_int, strv, C.c_int, strv, C.c_char_p, C.c_int64, C.POINTER(LcdChunkPlan)]
+    lib.lcd_chunk_plan_free.argtypes = [C.POINTER(LcdChunkPlan)]
+    lib.lcd_chunk_plan_free.restype = None
+    lib.lcd_stitch_chunks_carry.argtypes = [C.POINTER(LcdChunkPhase), C.c_int, C.c_int, C.POINTER(LcdStitchCarry), C.POINTER(LcdStitchCarry)]
+    lib.lcd_stitch_carry_free.argtypes = [C.POINTER(LcdStitchCarry)]
+    lib.lcd_stitch_carry_free.restype = None
+    lib.lcd_chunk_open_from_bam.restype = C.c_void_p
+    lib.lcd_chunk_open_from_bam.argtypes = [C.POINTER(LcdDigarOpt), C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(LcdBamReads)]
+    lib.lcd_chunk_resolve.argtypes = [C.c_void_p, C.POINTER(LcdChunkSrc)]
+    lib.lcd_bam_writer_open.restype = C.c_void_p
+    lib.lcd_bam_writer_open.argtypes = [C.c_char_p, C.POINTER(LcdBamOut)]
+    lib.lcd_bam_writer_append.argtypes = [C.c_void_p, C.c_int, C.POINTER(LcdCallChunk), i32p, C.POINTER(LcdStitchCarry)]
+    lib.lcd_bam_writer_close.argtypes = [C.c_void_p]
+    lib.lcd_bam_writer_abort.argtypes = [C.c_void_p]
+    lib.lcd_bam_writer_abort.restype = None
+    lib.lcd_vcf_writer_open.restype = C.c_void_p
+    lib.lcd_vcf_writer_open.argtypes = [C.c_char_p, C.c_int, C.c_char_p]
+    lib.lcd_vcf_writer_append.argtypes = [C.c_void_p, C.c_char_p]
+    lib.lcd_vcf_writer_close.argtypes = [C.c_void_p]
+    lib.lcd_vcf_writer_abort.argtypes = [C.c_void_p]
+    lib.lcd_vcf_writer_abort.restype = None
+    lib.lcd_file_job_default.argtypes = [C.POINTER(LcdFileJob)]
+    lib.lcd_file_job_default.restype = None
+    lib.lcd_call_file.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdFileStats)]
+    lib.lcd_file_stats_free.argtypes = [C.POINTER(LcdFileStats)]
+    lib.lcd_file_stats_free.restype = None
     lib.lcd_call_free.restype = None
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]

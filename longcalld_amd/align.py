@@ -545,6 +545,43 @@ class DeviceChunk:
         self.packed_bytes = 0
         return self
 
+    @classmethod
+    def open_from_bam(cls, bam_path, bai_path, chrom, reg_beg, reg_end, min_mapq=30, is_ont=0, verify_crc=1):
+        """lcd_chunk_open_from_bam: the first phase of from_bam -- region image, inflate, record walk, loader's rule; .meta is filled (the reads' span is known), the
+        handle has no digars until resolve()"""
+        from ._lib import LcdBamReads
+        self = cls.__new__(cls)
+        self.lib = lib = load_library()
+        opt = LcdDigarOpt(); lib.lcd_digar_opt_default(C.byref(opt), int(is_ont))
+        m = LcdBamReads()
+        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+        self.h = lib.lcd_chunk_open_from_bam(C.byref(opt), enc(bam_path), enc(bai_path), enc(chrom), int(reg_beg), int(reg_end), int(min_mapq), int(verify_crc), C.byref(m))
+        if not self.h:
+            raise RuntimeError("lcd_chunk_open_from_bam failed: " + lib.lcd_last_error().decode())
+        n = self.n = m.n_reads
+        arr = lambda p, dt: np.array([p[i] for i in range(n)], dt)
+        self.meta = dict(tid=m.tid, n_targets=m.n_targets, target_len=m.target_len, pos0=arr(m.pos0, np.int64), end_pos=arr(m.end_pos, np.int64), mapq=arr(m.mapq, np.int32),
+                         flag=arr(m.flag, np.int32), n_cigar=arr(m.n_cigar, np.int32), qlen=arr(m.qlen, np.int32),
+                         names=[C.string_at(C.addressof(m.name_pool.contents) + m.name_off[i]).decode() for i in range(n)])
+        lib.lcd_bam_reads_free.argtypes = [C.POINTER(LcdBamReads)]
+        lib.lcd_bam_reads_free(C.byref(m))
+        self.packed_bytes = 0
+        return self
+
+    def resolve(self, src=None):
+        """lcd_chunk_resolve: the second phase -- src = (ref, ref_beg, ref_end, is_ont) as for from_bam, or None; a second call raises (-4)"""
+        from ._lib import LcdChunkSrc
+        if src is None:
+            return check(self.lib.lcd_chunk_resolve(self.h, None), self.lib)
+        ref, ref_beg, ref_end, src_ont = src
+        refb = None if ref is None else (bytes(ref) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, np.uint8).tobytes())
+        refbuf = C.create_string_buffer(refb, len(refb) + 1) if refb is not None else None
+        cs = LcdChunkSrc(); cs.ref_seq = C.cast(refbuf, C.c_char_p) if refbuf is not None else None
+        cs.ref_beg, cs.ref_end, cs.is_ont = int(ref_beg), int(ref_end), int(src_ont)
+        if refb is not None and len(refb) < cs.ref_end - cs.ref_beg + 1:
+            raise ValueError("DeviceChunk.resolve: ref is shorter than [ref_beg, ref_end]")
+        return check(self.lib.lcd_chunk_resolve(self.h, C.byref(cs)), self.lib)
+
     def tag_records(self, haps, phase_sets, n_skip_kept=0, n_skip_filtered=0):
         """lcd_chunk_tag_records: the records of a chunk made from a BAM with HP:i / PS:i rewritten in HBM -> (bytes of the records back to back, their number)"""
         lib = self.lib
@@ -568,7 +605,7 @@ class DeviceChunk:
         st = np.zeros(n, np.int32); beg = np.zeros(n, np.int64); end = np.zeros(n, np.int64); nc = np.zeros(n, np.int32); nd = np.zeros(n, np.int32)
         i64p = C.POINTER(C.c_int64)
         self.lib.lcd_chunk_read_info.argtypes = [C.c_void_p, i32p, i64p, i64p, i32p, i32p]
-        self.lib.lcd_chunk_read_info(self.h, st.ctypes.data_as(i32p), beg.ctypes.data_as(i64p), end.ctypes.data_as(i64p), nc.ctypes.data_as(i32p), nd.ctypes.data_as(i32p))
+        check(self.lib.lcd_chunk_read_info(self.h, st.ctypes.data_as(i32p), beg.ctypes.data_as(i64p), end.ctypes.data_as(i64p), nc.ctypes.data_as(i32p), nd.ctypes.data_as(i32p)), self.lib)
         return dict(status=st, beg=beg, end=end, n_cand=nc, n_digars=nd)
 
     def sources(self):
@@ -1482,3 +1519,116 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     check(lib.lcd_call_bam_regions(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
                                    C.byref(text)), lib)
     return _call_result(lib, n, arr, recs, n_recs, text)
+
+
+# ---------------- a whole BAM in one call (lcd_call_file and what it is composed of) ----------------
+def _enc(x):
+    return x if isinstance(x, bytes) else str(x).encode()
+
+
+def _str_array(xs):
+    xs = [_enc(x) for x in (xs or [])]
+    return (C.c_char_p * max(1, len(xs)))(*xs), len(xs)
+
+
+def bam_contigs(bam_path):
+    """lcd_bam_contigs -> [(name, length)] in header order"""
+    lib = load_library()
+    n, names, lens = C.c_int(0), C.POINTER(C.c_void_p)(), C.POINTER(C.c_int64)()
+    check(lib.lcd_bam_contigs(_enc(bam_path), C.byref(n), C.byref(names), C.byref(lens)), lib)
+    try:
+        return [(C.string_at(names[i]).decode(), int(lens[i])) for i in range(n.value)]
+    finally:
+        lib.lcd_bam_contigs_free(n.value, names, lens)
+
+
+def bam_sample_name(bam_path):
+    """lcd_bam_sample_name -> the SM of the first @RG line that has one, or None"""
+    lib = load_library()
+    p = C.c_void_p()
+    check(lib.lcd_bam_sample_name(_enc(bam_path), C.byref(p)), lib)
+    if not p:
+        return None
+    try:
+        return C.string_at(p).decode()
+    finally:
+        _libc.free(p)
+
+
+def plan_chunks(contigs, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0):
+    """lcd_plan_chunks: contigs = [(name, length)] -> ([(tid, reg_beg, reg_end)], fallback flag)"""
+    from ._lib import LcdChunkPlan
+    lib = load_library()
+    names, n = _str_array([c[0] for c in contigs])
+    lens = (C.c_int64 * max(1, n))(*[int(c[1]) for c in contigs])
+    exc, n_exc = _str_array(exclude)
+    regs, n_regs = _str_array(regions)
+    out = LcdChunkPlan()
+    check(lib.lcd_plan_chunks(n, names, lens, int(contig_mode), n_exc, exc, n_regs, regs, _enc(region_bed_path) if region_bed_path is not None else None, int(chunk_len),
+                              C.byref(out)), lib)
+    try:
+        return [(int(out.tid[i]), int(out.reg_beg[i]), int(out.reg_end[i])) for i in range(out.n)], int(out.fallback)
+    finally:
+        lib.lcd_chunk_plan_free(C.byref(out))
+
+
+def stitch_chunks_carry(phases, update_reads=1, carry_in=None, carry_out=None, n=None):
+    """lcd_stitch_chunks_carry on an array of _lib.LcdChunkPhase (mutated; its first n entries, default all); carry_in / carry_out: _lib.LcdStitchCarry or None
+    -> the return code (0 or -6)"""
+    lib = load_library()
+    return lib.lcd_stitch_chunks_carry(phases, len(phases) if n is None else int(n), int(update_reads), C.byref(carry_in) if carry_in is not None else None,
+                                       C.byref(carry_out) if carry_out is not None else None)
+
+
+def vcf_write(path, texts, bgzf=0, header_text=None):
+    """lcd_vcf_writer_open / _append per text / _close"""
+    lib = load_library()
+    w = lib.lcd_vcf_writer_open(_enc(path) if path is not None else None, int(bgzf), _enc(header_text) if header_text is not None else None)
+    if not w:
+        raise LcdError("lcd_vcf_writer_open failed: " + lib.lcd_last_error().decode())
+    for t in texts:
+        rc = lib.lcd_vcf_writer_append(w, _enc(t))
+        if rc < 0:
+            lib.lcd_vcf_writer_abort(w)
+            check(rc, lib)
+    check(lib.lcd_vcf_writer_close(w), lib)
+
+
+def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
+              min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
+              keep_records=False):
+    """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
+    phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
+    flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters"""
+    from ._lib import LcdBamOut, LcdFileJob, LcdFileStats
+    lib = load_library()
+    cfg = cfg if cfg is not None else call_cfg()
+    job = LcdFileJob(); lib.lcd_file_job_default(C.byref(job))
+    opt_s = lambda x: _enc(x) if x is not None else None
+    job.bam_path, job.bai_path, job.fasta_path = _enc(bam_path), opt_s(bai_path), _enc(fasta_path)
+    exc, job.n_exclude = _str_array(exclude); job.exclude = exc
+    regs, job.n_regions = _str_array(regions); job.regions = regs
+    job.contig_mode, job.region_bed_path, job.chunk_len = int(contig_mode), opt_s(region_bed_path), int(chunk_len)
+    job.window_chunks, job.overlap, job.loader_threads, job.min_mapq = int(window_chunks), int(overlap), int(loader_threads), int(min_mapq)
+    job.vcf_path, job.vcf_bgzf, job.no_vcf_header = opt_s(vcf_path), int(vcf_bgzf), int(no_vcf_header)
+    job.sample_name, job.source_version, job.cmdline, job.date_yyyymmdd = opt_s(sample_name), opt_s(source_version), opt_s(cmdline), opt_s(date_yyyymmdd)
+    job.keep_records = int(bool(keep_records))
+    bo = None
+    if bam_out is not None:
+        bo = LcdBamOut(); bo.path = _enc(bam_out["path"]); bo.pg_line = opt_s(bam_out.get("pg_line")); bo.block_payload = int(bam_out.get("block_payload", 0))
+        job.bam_out = C.pointer(bo)
+    st = LcdFileStats()
+    rc = lib.lcd_call_file(C.byref(job), C.byref(cfg), C.byref(st))
+    try:
+        check(rc, lib)
+        res = {k: getattr(st, k) for k, _t in LcdFileStats._fields_[:14]}
+        if keep_records:
+            res["chunks"] = [dict(tid=int(st.chunk_tid[i]), reg_beg=int(st.chunk_reg_beg[i]), reg_end=int(st.chunk_reg_end[i]), n_reads=int(st.chunk_n_reads[i]),
+                                  n_passes=int(st.chunk_n_passes[i]), flip_hap=int(st.chunk_flip_hap[i]), flip_pre_PS=int(st.chunk_flip_pre_PS[i]),
+                                  flip_cur_PS=int(st.chunk_flip_cur_PS[i]), n_records=int(st.chunk_n_records[i])) for i in range(st.n_chunks)]
+            res["records"] = [_var1_dict(st.records[i]) for i in range(st.n_kept_records)]
+        if bo is not None:
+            res["bam_out"] = {k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag", "ms_deflate", "ms_download_write")}
+        return res
+    finally:
+        lib.lcd_file_stats_free(C.byref(st))

@@ -1,0 +1,130 @@
+"""python -m longcalld_amd.cli call ref.fa in.bam [region ...] -- the reference's command line (src/call_var_main.c:812-1000) for what the library supports: a thin
+argument parser over lcd_call_file.  What is not supported is refused with one line and exit status 2."""
+import sys
+
+VERSION_FALLBACK = "longcalld_amd"
+REFUSED = {
+    "-s": "somatic / mosaic calling is not supported", "--mosaic": "somatic / mosaic calling is not supported", "--somatic": "somatic / mosaic calling is not supported",
+    "--refine-aln": "--refine-aln is not supported", "-L": "a list of input files (-L) is not supported: one BAM per run", "--input-is-list": "a list of input files (-L) is not supported: one BAM per run",
+    "-X": "extra input files (-X) are not supported: one BAM per run", "--extra-bam": "extra input files (-X) are not supported: one BAM per run",
+    "-T": "a transposable-element library (-T) is not supported", "--trans-elem": "a transposable-element library (-T) is not supported",
+    "-S": "SAM output (-S) is not supported: use -b", "--out-sam": "SAM output (-S) is not supported: use -b", "--out-cram": "CRAM output (-C FILE) is not supported: use -b",
+    "--out-var-rnames": "--out-var-rnames is not supported", "--out-som-var-rnames": "--out-som-var-rnames is not supported", "--out-sv-rnames": "--out-sv-rnames is not supported",
+}
+FLAGS = {"--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap"}
+VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
+          "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
+          "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
+          "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
+          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len"}
+USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
+  ref.fa needs ref.fa.fai, in.bam needs in.bam.bai (the library does not build indexes)
+Input:    --hifi (default) | --ont   --region-file FILE   --autosome-XY (default) | --autosome | --all-ctg   -E/--exclude-ctg STR (repeatable)   -r/--ref-idx FILE
+Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z   -l/--min-sv-len INT   -H/--no-vcf-header   --amb-base   -b/--out-bam FILE
+Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
+Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
+Not supported (refused with exit status 2): -s, --refine-aln, -L, -X, -T, -S, -C FILE, --out-*-rnames
+"""
+
+
+def refuse(msg):
+    sys.stderr.write("longcalld_amd call: " + msg + "\n")
+    return 2
+
+
+def parse(argv):
+    """-> (dict of options, positional arguments) or an int exit status"""
+    o = dict(flags=set(), exclude=[])
+    pos, i = [], 0
+    while i < len(argv):
+        a = argv[i]; i += 1
+        if a == "--":
+            pos += argv[i:]; break
+        if a in ("-h", "--help"):
+            sys.stdout.write(USAGE); return 0
+        key, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") else (a, None)
+        if len(a) > 2 and a[0] == "-" and a[1] != "-" and a[:2] in VALUED:           # -o out.vcf written as -oout.vcf
+            key, val = a[:2], a[2:]
+        if key in REFUSED:
+            return refuse(REFUSED[key])
+        if key in FLAGS:
+            o["flags"].add(key); continue
+        if key in VALUED:
+            if val is None:
+                if i >= len(argv):
+                    return refuse(f"{key} needs a value")
+                val = argv[i]; i += 1
+            if VALUED[key] == "max_cov" and not val.lstrip("+").isdigit():
+                return refuse(REFUSED["--out-cram"])
+            if VALUED[key] == "exclude":
+                o["exclude"].append(val)
+            else:
+                o[VALUED[key]] = val
+            continue
+        if a.startswith("-") and a != "-":
+            return refuse(f"unknown option {a}")
+        pos.append(a)
+    return o, pos
+
+
+def main(argv=None):
+    argv = list(sys.argv[1:] if argv is None else argv)
+    if not argv or argv[0] in ("-h", "--help"):
+        sys.stdout.write(USAGE); return 0 if argv else 2
+    if argv[0] != "call":
+        return refuse(f"unknown command {argv[0]} (the only command is: call)")
+    p = parse(argv[1:])
+    if isinstance(p, int):
+        return p
+    o, pos = p
+    if len(pos) < 2:
+        sys.stderr.write(USAGE); return 2
+    fasta, bam, regions = pos[0], pos[1], pos[2:]
+    if o.get("out_type", "v") not in ("v", "z"):
+        return refuse("-O/--out-type can only be v or z")
+    if "ref_idx" in o and o["ref_idx"] != fasta + ".fai":
+        return refuse("-r/--ref-idx: only <ref.fa>.fai next to the FASTA is supported")
+    try:
+        num = {k: int(o[k]) for k in ("min_sv_len", "min_cov", "alt_cov", "min_mapq", "min_bq", "max_cov", "window_chunks", "loader_threads", "chunk_len") if k in o}
+        if "alt_ratio" in o:
+            num["alt_ratio"] = float(o["alt_ratio"])
+    except ValueError as e:
+        return refuse(f"not a number: {e}")
+    from . import align
+    is_ont = 1 if "--ont" in o["flags"] else 0
+    clean, opt, pass_, call = {}, {}, {}, {}
+    if "min_cov" in num:
+        clean["min_dp"] = opt["min_dp"] = call["min_dp"] = num["min_cov"]
+    if "alt_cov" in num:
+        clean["min_alt_dp"] = call["min_alt_dp"] = num["alt_cov"]
+    if "alt_ratio" in num:
+        clean["min_af"] = opt["min_af"] = num["alt_ratio"]
+    if "min_bq" in num:
+        clean["min_bq"] = num["min_bq"]
+    if "min_sv_len" in num:
+        clean["min_sv_len"] = opt["min_sv_len"] = call["min_sv_len"] = num["min_sv_len"]
+    if "max_cov" in num:
+        pass_["max_noisy_reg_cov"] = num["max_cov"]
+    if "--amb-base" in o["flags"]:
+        call["out_amb_base"] = 1
+    cfg = align.call_cfg(is_ont, clean=clean, opt=opt, pass_=pass_, call=call)
+    mode = 2 if "--all-ctg" in o["flags"] else 1 if "--autosome" in o["flags"] else 0
+    cmdline = "longcalld_amd call " + " ".join(argv[1:])
+    bam_out = dict(path=o["out_bam"], pg_line="@PG\tID:longcalld_amd\tPN:longcalld_amd\tCL:" + cmdline) if "out_bam" in o else None
+    try:
+        st = align.call_file(bam, fasta, contig_mode=mode, exclude=o["exclude"], regions=regions, region_bed_path=o.get("region_file"), chunk_len=num.get("chunk_len", 0),
+                             window_chunks=num.get("window_chunks", 0), overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0),
+                             min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
+                             no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg)
+    except align.LcdError as e:
+        sys.stderr.write(f"longcalld_amd call: {e}\n")
+        return 2 if "error -2:" in str(e) else 1
+    if st["plan_fallback"]:
+        sys.stderr.write("longcalld_amd call: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
+    sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads, {st['n_vcf_lines']} VCF lines, "
+                     f"{st['ms_wall'] / 1000:.2f} s\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,6 +1,7 @@
 // lcd_call.cpp -- the germline path joined end to end: lcd_chunks_call (first round, noisy-region rounds, cross-chunk stitch, genotype records, VCF body lines
 // for a pipeline step's chunks of one contig), lcd_call_bam_regions (the same from an indexed BAM and a FASTA) and the phased alignment file beside it
-// (lcd_write_phased_bam, lcd_call_bam_regions_out).  Every stage is an export of its own
+// (the appendable writer lcd_bam_writer_*, lcd_write_phased_bam, lcd_call_bam_regions_out).  chunks_call_core is the body of lcd_chunks_call that lcd_call_file
+// (lcd_call_file.cpp) runs per window of chunks.  Every stage is an export of its own
 // (lcd_first_round.cpp, lcd_chunk_vars.cpp, lcd_emit.cpp, lcd_chunk.cpp, lcd_io.cpp); this file only composes them as collect_var_main / stitch_var_main /
 // make_var_main do (src/collect_var.c:2897-3000).
 #include "lcd_host_internal.h"
@@ -20,11 +21,19 @@ void lcd_call_free(int n, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_r
 }
 
 int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body) {
+    return chunks_call_core(n, chunks, cfg, chrom, nullptr, records, n_records, vcf_body);
+}
+
+} // extern "C"
+
+// the body of lcd_chunks_call.  links == NULL: n chunks of the one contig `chrom`.  With links (lcd_call_file's window): a contig name and tid per chunk, the first
+// chunk's up list against the carried region, the last chunk's down list against the next planned region, the stitch carried in and out
+int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, lcd_var1_t **records, int *n_records, char **vcf_body) {
     const std::string W = "lcd_chunks_call";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (vcf_body) *vcf_body = nullptr;
-    if (!records || !n_records || !vcf_body || !cfg || !chrom) return set_err(-4, W + ": NULL argument");
+    if (!records || !n_records || !vcf_body || !cfg || (!chrom && !links)) return set_err(-4, W + ": NULL argument");
     if (n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": bad chunk list");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
     for (int c = 0; c < n; ++c) { lcd_call_chunk_t &x = chunks[c]; x.n_passes = x.flip_hap = x.n_records = 0; x.flip_pre_PS = x.flip_cur_PS = -1; }
@@ -51,20 +60,29 @@ int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const
     // 3. stitch_var_main: the phase sets of neighbours joined through the reads they share
     {
         std::vector<lcd_chunk_phase_t> ph(n); std::vector<std::vector<int>> up(n), down(n);
+        const lcd_stitch_carry_t *cin = links ? links->carry_in : nullptr;
         for (int c = 0; c < n; ++c) {
             const lcd_first_chunk_t &x = chunks[c].first; const lcd_chunk_s *k = x.chunk;
+            const int tid = links ? links->tids[c] : 0;
+            // the neighbours' regions: the chunk beside it, or across the window's border the carried / the next planned region; none on another contig
+            bool has_up = c > 0 && (!links || links->tids[c - 1] == tid), has_down = c + 1 < n && (!links || links->tids[c + 1] == tid);
+            int64_t ub = has_up ? chunks[c - 1].first.reg_beg : 0, ue = has_up ? chunks[c - 1].first.reg_end : 0;
+            int64_t db = has_down ? chunks[c + 1].first.reg_beg : 0, de = has_down ? chunks[c + 1].first.reg_end : 0;
+            if (c == 0 && cin && cin->valid && cin->tid == tid) { has_up = true; ub = cin->reg_beg; ue = cin->reg_end; }
+            if (c == n - 1 && links && links->next_tid == tid) { has_down = true; db = links->next_beg; de = links->next_end; }
             for (int r = 0; r < k->n_reads; ++r) {
                 const int64_t rb = k->beg[r], re = k->end[r];
-                if (c > 0 && !(re < chunks[c - 1].first.reg_beg || rb > chunks[c - 1].first.reg_end)) up[c].push_back(r);
-                if (c + 1 < n && !(re < chunks[c + 1].first.reg_beg || rb > chunks[c + 1].first.reg_end)) down[c].push_back(r);
+                if (has_up && !(re < ub || rb > ue)) up[c].push_back(r);
+                if (has_down && !(re < db || rb > de)) down[c].push_back(r);
             }
             lcd_chunk_phase_t &p = ph[c]; memset(&p, 0, sizeof(p));
-            p.tid = 0; p.n_reads = x.vars->n_reads; p.n_vars = x.vars->n_vars; p.ordered_read_ids = x.order; p.is_skipped = x.is_skipped;
+            p.tid = tid; p.n_reads = x.vars->n_reads; p.n_vars = x.vars->n_vars; p.ordered_read_ids = x.order; p.is_skipped = x.is_skipped;
             p.haps = x.state->haps; p.phase_sets = x.state->phase_sets; p.var_phase_set = x.state->var_phase_set; p.hap_to_cons_alle = x.state->hap_to_cons_alle;
             p.n_up_ovlp = (int)up[c].size(); p.n_down_ovlp = (int)down[c].size(); p.up_ovlp_read_i = up[c].data(); p.down_ovlp_read_i = down[c].data();
             p.flip_hap = 0; p.flip_pre_PS = p.flip_cur_PS = -1;
         }
-        rc = lcd_stitch_chunks(ph.data(), n, 1);
+        rc = links ? lcd_stitch_chunks_carry(ph.data(), n, 1, links->carry_in, links->carry_out) : lcd_stitch_chunks(ph.data(), n, 1);
+        if (!rc && links && links->carry_out && n > 0) { links->carry_out->reg_beg = chunks[n - 1].first.reg_beg; links->carry_out->reg_end = chunks[n - 1].first.reg_end; }
         if (rc) return fail(set_err(rc, W + ": neighbouring chunks disagree on the reads they share (the overlap counts differ)"));
         for (int c = 0; c < n; ++c) { chunks[c].flip_hap = ph[c].flip_hap; chunks[c].flip_pre_PS = ph[c].flip_pre_PS; chunks[c].flip_cur_PS = ph[c].flip_cur_PS; }
     }
@@ -98,29 +116,64 @@ int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const
     lcd_var1_t *out = (lcd_var1_t *)malloc((all.size() + 1) * sizeof(lcd_var1_t));
     if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(lcd_var1_t));
     char *text = nullptr;
-    const int nl = lcd_format_vcf(&cfg->call, chrom, out, (int)all.size(), &text);
-    if (nl < 0) { lcd_free_variants(out, (int)all.size()); return fail(nl); }
+    if (!links) {
+        const int nl = lcd_format_vcf(&cfg->call, chrom, out, (int)all.size(), &text);
+        if (nl < 0) { lcd_free_variants(out, (int)all.size()); return fail(nl); }
+    } else {   // the lines of every chunk under its own contig name
+        std::string t; size_t at = 0;
+        for (int c = 0; c < n; ++c) {
+            char *one = nullptr;
+            const int nl = lcd_format_vcf(&cfg->call, links->chroms[c], out + at, chunks[c].n_records, &one);
+            if (nl < 0) { lcd_free_variants(out, (int)all.size()); return fail(nl); }
+            if (one) t += one;
+            free(one); at += (size_t)chunks[c].n_records;
+        }
+        text = (char *)malloc(t.size() + 1); memcpy(text, t.c_str(), t.size() + 1);
+    }
     *records = out; *n_records = (int)all.size(); *vcf_body = text;
     return 0;
 }
+
+extern "C" {
 
 // write_read_to_bam for every region of a call (src/bam_utils.c:1944-2048, called from the output step at src/call_var_main.c:801): the input's header block plus
 // one @PG line, then per region its records with HP:i / PS:i rewritten in HBM (lcd_chunk_tag_records) and compressed there (lcd_bgzf_deflate_dev_ptr); only
 // compressed bytes come down, and they go to the file with fwrite.  A region leaves out the records the region before it already wrote: its kept and its filtered
 // records that overlap that region's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691) -- in a sorted file they are the first ones.
-int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) {
-    const std::string W = "lcd_write_phased_bam";
-    if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
-    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
-    if (out->block_payload < 0 || out->block_payload > 0xff00) return set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00");
+struct lcd_bam_writer_s { FILE *f = nullptr; lcd_bam_out_t *out = nullptr; std::string path; std::vector<uint8_t> buf; };
+namespace {
+// download + fwrite of one compressed image, then free
+int writer_put(lcd_bam_writer_s *w, lcd_deflated_t *d, const std::string &W) {
+    if (!d) return -1;
+    lcd_bam_out_t *out = w->out;
+    const double t0 = now_ms();
+    const size_t sz = lcd_deflated_size(d);
+    w->buf.resize(sz + 1);
+    int rc = lcd_deflated_to_host(d, 0, sz, w->buf.data());
+    if (!rc && sz && fwrite(w->buf.data(), 1, sz, w->f) != sz) rc = set_err(-30, W + ": short write on " + w->path);
+    out->ms_deflate += lcd_deflated_kernel_ms(d); out->bytes_file += (int64_t)sz;
+    lcd_deflated_free(d);
+    out->ms_download_write += now_ms() - t0;
+    return rc;
+}
+int writer_check_chunks(const std::string &W, int n, const lcd_call_chunk_t *chunks) {
     for (int c = 0; c < n; ++c) {
         const lcd_chunk_s *k = chunks[c].first.chunk;
         if (!k || !k->from_bam) return set_err(-4, W + ": chunk " + std::to_string(c) + " was not made from a BAM");
         if (k->n_reads > 0 && (!chunks[c].first.state || !chunks[c].first.state->haps || !chunks[c].first.state->phase_sets || chunks[c].first.state->n_reads != k->n_reads))
             return set_err(-4, W + ": chunk " + std::to_string(c) + " has no final haplotypes (call lcd_chunks_call first)");
     }
+    return 0;
+}
+} // namespace
+
+lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out) {
+    const std::string W = "lcd_write_phased_bam";
+    if (!in_bam_path || !out || !out->path) { set_err(-4, W + ": NULL argument"); return nullptr; }
+    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
+    if (out->block_payload < 0 || out->block_payload > 0xff00) { set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00"); return nullptr; }
     std::vector<uint8_t> hdr;
-    if (lcd_io_bam_header(in_bam_path, hdr)) return set_err(-30, W + ": " + lcd_io_last_error());
+    if (lcd_io_bam_header(in_bam_path, hdr)) { set_err(-30, W + ": " + lcd_io_last_error()); return nullptr; }
     if (out->pg_line && out->pg_line[0]) {
         int l_text = 0; memcpy(&l_text, hdr.data() + 4, 4);
         size_t te = 8 + (size_t)l_text;
@@ -130,45 +183,68 @@ int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t 
         hdr.insert(hdr.begin() + (long)te, add.begin(), add.end());
         l_text += (int)add.size(); memcpy(hdr.data() + 4, &l_text, 4);
     }
-    FILE *f = fopen(out->path, "wb");
-    if (!f) return set_err(-30, W + ": cannot open " + out->path + " for writing");
-    std::vector<uint8_t> buf;
-    auto put = [&](lcd_deflated_t *d) -> int {   // download + fwrite, then free
-        if (!d) return -1;
-        const double t0 = now_ms();
-        const size_t sz = lcd_deflated_size(d);
-        buf.resize(sz + 1);
-        int rc = lcd_deflated_to_host(d, 0, sz, buf.data());
-        if (!rc && sz && fwrite(buf.data(), 1, sz, f) != sz) rc = set_err(-30, W + ": short write on " + out->path);
-        out->ms_deflate += lcd_deflated_kernel_ms(d); out->bytes_file += (int64_t)sz;
-        lcd_deflated_free(d);
-        out->ms_download_write += now_ms() - t0;
-        return rc;
-    };
-    auto fail = [&](int code) { const std::string m = g_err; fclose(f); g_err = m; return code; };
-    if (int rc = put(lcd_bgzf_deflate_dev(hdr.data(), hdr.size(), out->block_payload, 0))) return fail(rc);
+    std::unique_ptr<lcd_bam_writer_s> w(new lcd_bam_writer_s());
+    w->out = out; w->path = out->path;
+    w->f = fopen(out->path, "wb");
+    if (!w->f) { set_err(-30, W + ": cannot open " + out->path + " for writing"); return nullptr; }
+    if (writer_put(w.get(), lcd_bgzf_deflate_dev(hdr.data(), hdr.size(), out->block_payload, 0), W)) { const std::string m = g_err; fclose(w->f); g_err = m; return nullptr; }
     out->bytes_inflated += (int64_t)hdr.size();
+    return w.release();
+}
+int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *chunks, const int *tids, const lcd_stitch_carry_t *prev) {
+    const std::string W = "lcd_write_phased_bam";
+    if (!w || !w->f || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
+    if (int rc = writer_check_chunks(W, n, chunks)) return rc;
+    lcd_bam_out_t *out = w->out;
     for (int c = 0; c < n; ++c) {
         const lcd_first_chunk_t &x = chunks[c].first; const lcd_chunk_s *k = x.chunk;
         int nsk = 0, nsf = 0;
-        if (c > 0)
+        bool has_prev = c > 0 && (!tids || tids[c - 1] == tids[c]);
+        int64_t pb = has_prev ? chunks[c - 1].first.reg_beg : 0, pe = has_prev ? chunks[c - 1].first.reg_end : 0;
+        if (c == 0 && prev && prev->valid && (!tids || prev->tid == tids[0])) { has_prev = true; pb = prev->reg_beg; pe = prev->reg_end; }
+        if (has_prev)
             for (size_t i = 0; i < k->rec_beg.size(); ++i)
-                if (!(k->rec_endpos[i] < chunks[c - 1].first.reg_beg || k->rec_pos0[i] + 1 > chunks[c - 1].first.reg_end)) ++(k->rec_read[i] >= 0 ? nsk : nsf);
+                if (!(k->rec_endpos[i] < pb || k->rec_pos0[i] + 1 > pe)) ++(k->rec_read[i] >= 0 ? nsk : nsf);
         const double t0 = now_ms();
         lcd_tagged_t *t = lcd_chunk_tag_records(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, nsk, nsf);
-        if (!t) return fail(-30);
+        if (!t) return -30;
         out->ms_tag += now_ms() - t0;
         int kept = 0, filt = 0;
         for (int r : k->rec_read) ++(r >= 0 ? kept : filt);
         out->n_records_out += kept - nsk; out->n_filtered_out += filt - nsf; out->bytes_inflated += (int64_t)lcd_tagged_size(t);
         lcd_deflated_t *d = lcd_tagged_size(t) ? lcd_bgzf_deflate_dev_ptr(lcd_tagged_dev_ptr(t), lcd_tagged_size(t), out->block_payload, 0) : nullptr;
-        const int rc = lcd_tagged_size(t) ? put(d) : 0;
+        const int rc = lcd_tagged_size(t) ? writer_put(w, d, W) : 0;
         lcd_tagged_free(t);
-        if (rc) return fail(rc);
+        if (rc) return rc;
     }
-    if (int rc = put(lcd_bgzf_deflate_dev(nullptr, 0, out->block_payload, 1))) return fail(rc);   // the EOF member
-    if (fclose(f) != 0) return set_err(-30, W + ": closing " + out->path + " failed");
     return 0;
+}
+void lcd_bam_writer_abort(lcd_bam_writer_t *w) {
+    if (!w) return;
+    const std::string m = g_err;
+    if (w->f) fclose(w->f);
+    delete w;
+    g_err = m;
+}
+int lcd_bam_writer_close(lcd_bam_writer_t *w) {
+    const std::string W = "lcd_write_phased_bam";
+    if (!w) return set_err(-4, W + ": NULL argument");
+    if (int rc = writer_put(w, lcd_bgzf_deflate_dev(nullptr, 0, w->out->block_payload, 1), W)) { lcd_bam_writer_abort(w); return rc; }   // the EOF member
+    const std::string path = w->path;
+    const int rc = fclose(w->f);
+    delete w;
+    return rc != 0 ? set_err(-30, W + ": closing " + path + " failed") : 0;
+}
+int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) {
+    const std::string W = "lcd_write_phased_bam";
+    if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
+    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
+    if (out->block_payload < 0 || out->block_payload > 0xff00) return set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00");
+    if (int rc = writer_check_chunks(W, n, chunks)) return rc;     // (before the output file is touched)
+    lcd_bam_writer_t *w = lcd_bam_writer_open(in_bam_path, out);
+    if (!w) return -30;
+    if (int rc = lcd_bam_writer_append(w, n, chunks, nullptr, nullptr)) { lcd_bam_writer_abort(w); return rc; }
+    return lcd_bam_writer_close(w);
 }
 
 int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,

@@ -168,14 +168,17 @@ lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n, const int64_t *
 // records' auxiliary fields in HBM; reads compared with the reference go through the lcd_refcmp_kernel passes on the CIGAR words and the 4-bit bases where the
 // inflate left them; the cs / MD VALUES (O(events) bytes, the only record bytes that cross PCIe) come to the host, are parsed by cs_to_words / md_to_words and go
 // back as EQX-shaped words; ONE digar launch covers all reads.  src == NULL is lcd_chunk_create_from_bam as it always was.
-lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
-                                           int min_mapq, int verify_crc, const lcd_chunk_src_t *src, lcd_bam_reads_t *meta) {
+lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
+                                     int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
     if (meta) memset(meta, 0, sizeof(*meta));
+    if (!opt || !bam_path || !bai_path || !chrom) { set_err(-4, "lcd_chunk_create_from_bam: NULL argument"); return nullptr; }
     if (ensure_init()) return nullptr;
     LcdRegionImage im;
     if (lcd_io_region_image(bam_path, bai_path, chrom, reg_beg, reg_end, im)) { set_err(-30, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
     std::unique_ptr<lcd_chunk_s> c(new lcd_chunk_s());
     c->device = cur_device(); c->n_reads = 0; c->opt = *opt; c->from_bam = true;
+    c->pending.reset(new ChunkPending());
+    ChunkPending &P = *c->pending; P.reg_beg = reg_beg; P.reg_end = reg_end; P.tlen = im.tlen;
     if (meta) { meta->tid = im.tid; meta->n_targets = im.n_ref; meta->target_len = im.tlen; }
     if (im.image.empty() || im.ranges.empty()) return c.release();
     c->stream = lcd_bgzf_inflate_dev(im.image.data(), im.image.size(), verify_crc);
@@ -234,8 +237,9 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
         CHK(hipStreamSynchronize(st));
     }
     // 3. the loader's rule, record by record in file order (Collector::take in lcd_io.cpp)
-    std::vector<int64_t> pos0, endp; std::vector<int> mapq, flag, ncig, qlen; std::vector<uint64_t> coff, soff, qoff, noff; std::vector<RefCmpOut> counts; std::vector<int> nindel; std::vector<GatherJob> gj, nj;
-    std::vector<BamAuxJob> auxj; std::vector<int64_t> rl_true;   // (src only)
+    std::vector<int64_t> &pos0 = P.pos0, &rl_true = P.rl_true; std::vector<int> &ncig = P.ncig, &qlen = P.qlen, &nindel = P.nindel; std::vector<uint64_t> &coff = P.coff, &soff = P.soff, &qoff = P.qoff;
+    std::vector<RefCmpOut> &counts = P.counts; std::vector<BamAuxJob> &auxj = P.auxj; DevBuf &d_cig = P.d_cig;   // (kept for lcd_chunk_resolve)
+    std::vector<int64_t> endp; std::vector<int> mapq, flag; std::vector<uint64_t> noff; std::vector<GatherJob> gj, nj;
     uint64_t cw = 0, nbytes = 0; bool done = false;
     const char *malformed = "malformed BAM record (a field runs past the record, or a placeholder CIGAR without its CG tag)";
     for (int k = 0; k < nr && !done; ++k) {
@@ -262,7 +266,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
             c->aux_off.push_back(sq + ((uint64_t)d.lseq + 1) / 2 + (uint64_t)d.lseq); c->rec_end.push_back(d.off + (uint64_t)d.bs); // (the walk checked: the fixed fields end inside the record)
             coff.push_back(cw); { GatherJob g; g.src = x.cig_src; g.dst = cw * 4; g.bytes = (uint32_t)x.nc * 4u; g.pad_ = 0; gj.push_back(g); } cw += (uint64_t)x.nc;
             RefCmpOut rc; rc.n_ops = x.nc; rc.nd = (int)x.nd; rc.nev = (int)x.nev; rc.pad = 0; counts.push_back(rc); nindel.push_back((int)x.nid);
-            if (src) {
+            {
                 BamAuxJob a; a.rec = base + d.off; a.cig = x.cig_src; a.bs = d.bs; a.lname = d.lname; a.nc16 = d.nc; a.lseq = d.lseq; a.nc = x.nc; a.flag = d.flag; a.prim_pos = (long long)d.pos + 1; a.prim_end = e0;
                 auxj.push_back(a); rl_true.push_back(x.rl);
             }
@@ -277,7 +281,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
     c->n_reads = n;
     // read names: one gather + one copy (the only record bytes that come to the host)
     std::vector<char> names(nbytes + 1, 0);
-    DevBuf d_cig, d_gj, d_names;
+    DevBuf d_gj, d_names;
     if (n > 0) {
         if (d_cig.ensure(cw * 4 + 64) || d_gj.ensure((size_t)n * sizeof(GatherJob)) || d_names.ensure(nbytes + 64)) return nullptr;
         for (GatherJob &g : gj) g.dst += d_cig.addr();
@@ -300,8 +304,23 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
         meta->cigar_off = dupv(coff); meta->seq_off = dupv(soff); meta->qual_off = dupv(qoff); meta->name_off = dupv(noff); meta->name_pool = dupv(names);
         // (cigar_pool / seq_pool / qual_pool stay NULL: those bytes are in HBM; seq_off / qual_off are offsets of the inflated stream)
     }
-    if (n == 0) return c.release();
-    auto drop_meta = [&]() { if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } }; // (the caller's arrays were handed out above)
+    if (n > 0 && hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return fail(-10, "HIP call failed: hipStreamSynchronize"); }
+#undef CHK
+    return c.release();
+}
+int lcd_chunk_resolve(lcd_chunk_t *c, const lcd_chunk_src_t *src) {
+    if (!c || !c->pending) return set_err(-4, "lcd_chunk_resolve: the handle was not opened by lcd_chunk_open_from_bam, or is resolved already");
+    if (use_device(c->device)) return -1;
+    ChunkPending &P = *c->pending;
+    const int n = c->n_reads;
+    if (n == 0) { c->pending.reset(); return 0; }
+    const int64_t reg_beg = P.reg_beg, reg_end = P.reg_end;
+    const lcd_digar_opt_t *opt = &c->opt;
+    const uint64_t base = lcd_inflated_dev_ptr(c->stream);
+    std::vector<int64_t> &pos0 = P.pos0, &rl_true = P.rl_true; std::vector<int> &ncig = P.ncig, &qlen = P.qlen, &nindel = P.nindel; std::vector<uint64_t> &coff = P.coff, &soff = P.soff, &qoff = P.qoff;
+    std::vector<RefCmpOut> &counts = P.counts; std::vector<BamAuxJob> &auxj = P.auxj; DevBuf &d_cig = P.d_cig;
+    StreamGuard st; if (st.create()) return -10;
+    auto fail = [&](int code, const std::string &m) -> int { return set_err(code, "lcd_chunk_create_from_bam: " + m); };
     // 3b. the reads' sources: what the words of the digar launch are made from
     std::vector<uint8_t> pal; std::vector<int> pre, clip, nw; std::vector<uint64_t> waddr;
     DevBuf d_aj, d_ao, d_ref, d_rj, d_rc, d_rw, d_tg, d_tpool, d_tw;
@@ -309,8 +328,8 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
     if (src) {
         c->source.assign(n, 0); c->pal.assign(n, 0); pal.assign(n, 0); pre.assign(n, 0); clip.assign(n, 0); nw = ncig; waddr.resize(n);
         std::vector<BamAuxOut> ao(n);
-        if (d_aj.ensure((size_t)n * sizeof(BamAuxJob)) || d_ao.ensure((size_t)n * sizeof(BamAuxOut))) { drop_meta(); return nullptr; }
-#define CHKM(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); drop_meta(); return fail(-10, "HIP call failed: " #x); } } while (0)
+        if (d_aj.ensure((size_t)n * sizeof(BamAuxJob)) || d_ao.ensure((size_t)n * sizeof(BamAuxOut))) return -11;
+#define CHKM(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return fail(-10, "HIP call failed: " #x); } } while (0)
         CHKM(hipMemcpyAsync(d_aj.p, auxj.data(), (size_t)n * sizeof(BamAuxJob), hipMemcpyHostToDevice, st));
         lcd_launch_bam_aux((const BamAuxJob *)d_aj.p, (BamAuxOut *)d_ao.p, src->is_ont != 0, n, st);
         CHKM(hipGetLastError());
@@ -327,7 +346,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
         }
         if (!ref_reads.empty()) {
             const int m = (int)ref_reads.size(); const uint64_t ref_len = (uint64_t)(src->ref_end - src->ref_beg + 1);
-            if (d_ref.ensure(ref_len + 64) || d_rj.ensure((size_t)m * sizeof(RefCmpJob)) || d_rc.ensure((size_t)m * sizeof(RefCmpOut))) { drop_meta(); return nullptr; }
+            if (d_ref.ensure(ref_len + 64) || d_rj.ensure((size_t)m * sizeof(RefCmpJob)) || d_rc.ensure((size_t)m * sizeof(RefCmpOut))) return -11;
             std::vector<RefCmpJob> rj(m); std::vector<RefCmpOut> cnt(m);
             for (int k = 0; k < m; ++k) { const int r = ref_reads[k]; RefCmpJob &j = rj[k]; j.cigar_off = waddr[r]; j.seq_off = base + soff[r]; j.out_off = 0; j.n_cigar = ncig[r]; j.pad = 0; j.pos0 = pos0[r]; }
             CHKM(hipMemcpyAsync(d_ref.p, src->ref_seq, ref_len, hipMemcpyHostToDevice, st));
@@ -338,7 +357,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
             CHKM(hipStreamSynchronize(st));
             uint64_t tot = 0;
             for (int k = 0; k < m; ++k) tot += (uint64_t)cnt[k].n_ops;
-            if (d_rw.ensure(tot * 4 + 64)) { drop_meta(); return nullptr; }
+            if (d_rw.ensure(tot * 4 + 64)) return -11;
             tot = 0;
             for (int k = 0; k < m; ++k) { const int r = ref_reads[k]; rj[k].out_off = d_rw.addr() + tot * 4; waddr[r] = rj[k].out_off; nw[r] = cnt[k].n_ops; counts[r] = cnt[k]; tot += (uint64_t)cnt[k].n_ops; }
             CHKM(hipMemcpyAsync(d_rj.p, rj.data(), (size_t)m * sizeof(RefCmpJob), hipMemcpyHostToDevice, st));
@@ -359,7 +378,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
                 at_tag[k] = tb; tj[2 * k + 1] = GatherJob{ao[r].tag, tb, ao[r].tag_len + 1u, 0}; tb = lcd_align_up(tb + ao[r].tag_len + 1, 4);
                 c->tag_bytes += ao[r].tag_len;
             }
-            if (d_tpool.ensure(tb + 64) || d_tg.ensure(tj.size() * sizeof(GatherJob))) { drop_meta(); return nullptr; }
+            if (d_tpool.ensure(tb + 64) || d_tg.ensure(tj.size() * sizeof(GatherJob))) return -11;
             for (GatherJob &g : tj) g.dst += d_tpool.addr();
             std::vector<uint8_t> hp(tb + 4);
             CHKM(hipMemcpyAsync(d_tg.p, tj.data(), tj.size() * sizeof(GatherJob), hipMemcpyHostToDevice, st));
@@ -381,7 +400,7 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
                 clip[r] = ao[r].source == LCD_SRC_CS;
             }
             words.push_back(0);
-            if (d_tw.ensure(words.size() * 4 + 64)) { drop_meta(); return nullptr; }
+            if (d_tw.ensure(words.size() * 4 + 64)) return -11;
             CHKM(hipMemcpyAsync(d_tw.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
             for (int k = 0; k < m; ++k) waddr[tag_reads[k]] = d_tw.addr() + woff[k] * 4;
         }
@@ -397,15 +416,28 @@ lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const cha
     if (src) { W.n_cigar = nw.data(); W.addr = waddr.data(); W.clip_rule_r = clip.data(); W.rlen_true = rl_true.data(); W.pre_status = pre.data(); }
     DigarKeep keep; keep.d_dig = &c->d_dig;
     uint64_t *doff = nullptr; lcd_digar_t *dg = nullptr;
-    const int rc = digar_batch_core(opt, n, pos0.data(), W, nullptr, qoff.data(), qlen.data(), src ? pal.data() : nullptr, reg_beg, reg_end, im.tlen, &doff, &dg, &c->iv_off, &c->ivs, &c->iv_in_chunk,
+    const int rc = digar_batch_core(opt, n, pos0.data(), W, nullptr, qoff.data(), qlen.data(), src ? pal.data() : nullptr, reg_beg, reg_end, P.tlen, &doff, &dg, &c->iv_off, &c->ivs, &c->iv_in_chunk,
                                     c->status.data(), c->beg.data(), c->end.data(), c->n_cand.data(), st, &keep);
     free(doff);
-    if (rc) { if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return nullptr; } // (the caller's arrays were handed out above)
-    if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return fail(-10, "HIP call failed: hipStreamSynchronize"); }
-#undef CHK
+    if (rc) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); return fail(-10, "HIP call failed: hipStreamSynchronize"); }
     c->slot.swap(keep.slot); c->n_digar.swap(keep.n_digar);
     if (src) c->stage_ms[3] = now_ms() - t0;
-    return c.release();
+    c->pending.reset();
+    return 0;
+}
+lcd_chunk_t *lcd_chunk_create_from_bam_src(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
+                                           int min_mapq, int verify_crc, const lcd_chunk_src_t *src, lcd_bam_reads_t *meta) {
+    lcd_chunk_t *c = lcd_chunk_open_from_bam(opt, bam_path, bai_path, chrom, reg_beg, reg_end, min_mapq, verify_crc, meta);
+    if (!c) return nullptr;
+    if (lcd_chunk_resolve(c, src)) {
+        const std::string m = g_err;
+        lcd_chunk_destroy(c);
+        if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); }   // (the caller's arrays were handed out by the first phase)
+        g_err = m;
+        return nullptr;
+    }
+    return c;
 }
 lcd_chunk_t *lcd_chunk_create_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
                                        int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
@@ -464,6 +496,7 @@ void lcd_chunk_stage_ms(const lcd_chunk_t *c, double out[4]) { for (int k = 0; k
 // the chunk's digars as lcd_digar_batch returns them (tests and debugging: everything else reads them in HBM)
 int lcd_chunk_digars(const lcd_chunk_t *c, uint64_t **digar_off, lcd_digar_t **digars) {
     *digar_off = nullptr; *digars = nullptr;
+    if (c->pending) return set_err(-4, "lcd_chunk_digars: the chunk was opened and not resolved (lcd_chunk_resolve)");
     if (use_device(c->device)) return -1;
     const int n = c->n_reads;
     uint64_t span = 0, tot = 0;
@@ -484,10 +517,13 @@ int lcd_chunk_n_reads(const lcd_chunk_t *c) { return c ? c->n_reads : 0; }
 // what collect_digar_from_eqx_cigar leaves on the host side of the reference: per read 0 / -1 (skipped as too noisy) / -2 ('M' operation), digar->beg / end, the number
 // of candidate variants; the reads' noisy windows in cr_index order (CSR; pointers into the chunk, valid until it is destroyed) and which of them enter chunk_noisy_regs
 int lcd_chunk_read_info(const lcd_chunk_t *c, int *status, int64_t *beg, int64_t *end, int *n_cand_vars, int *n_digars) {
+    if (c->pending) return set_err(-4, "lcd_chunk_read_info: the chunk was opened and not resolved (lcd_chunk_resolve)");
     for (int r = 0; r < c->n_reads; ++r) { if (status) status[r] = c->status[r]; if (beg) beg[r] = c->beg[r]; if (end) end[r] = c->end[r]; if (n_cand_vars) n_cand_vars[r] = c->n_cand[r]; if (n_digars) n_digars[r] = c->n_digar[r]; }
     return c->n_reads;
 }
 int lcd_chunk_intervals(const lcd_chunk_t *c, const uint64_t **iv_off, const lcd_noisy_iv_t **ivs, const uint8_t **iv_in_chunk) {
+    *iv_off = nullptr; *ivs = nullptr; *iv_in_chunk = nullptr;
+    if (c->pending) return set_err(-4, "lcd_chunk_intervals: the chunk was opened and not resolved (lcd_chunk_resolve)");
     *iv_off = c->iv_off; *ivs = c->ivs; *iv_in_chunk = c->iv_in_chunk;
     return c->n_reads;
 }
@@ -496,6 +532,7 @@ int lcd_chunk_intervals(const lcd_chunk_t *c, const uint64_t **iv_off, const lcd
 int lcd_chunk_region_slices(const lcd_chunk_t *c, int n_pairs, const int *pair_read, const int64_t *pair_reg_beg, const int64_t *pair_reg_end, int noisy_reg_flank_len,
                             int *read_beg, int *read_end, int *cover) {
     if (n_pairs <= 0) return 0;
+    if (c->pending) return set_err(-4, "lcd_chunk_region_slices: the chunk was opened and not resolved (lcd_chunk_resolve)");
     if (use_device(c->device)) return -1;
     std::vector<SliceJob> jobs(n_pairs);
     for (int i = 0; i < n_pairs; ++i) {

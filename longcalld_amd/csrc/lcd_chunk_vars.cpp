@@ -317,6 +317,7 @@ static int clean_vars_one(const lcd_chunk_t *c0, const lcd_clean_opt_t *opt, con
 int lcd_chunk_clean_vars(const lcd_chunk_t *c, const lcd_clean_opt_t *opt, const int *ordered_read_ids, const uint8_t *is_rev, const uint8_t *ref_seq, int64_t ref_beg,
                          int64_t ref_end, int64_t reg_beg, int64_t reg_end, const lcd_noisy_iv_t *pre_regs, int n_pre_regs, const int64_t *low_comp, int n_low,
                          lcd_clean_vars_t *out) {
+    if (c && c->pending) { if (out) memset(out, 0, sizeof(*out)); return set_err(-4, "lcd_chunk_clean_vars: the chunk was opened and not resolved (lcd_chunk_resolve)"); }
     if (ensure_init()) { if (out) memset(out, 0, sizeof(*out)); return -1; }
     const int rc = clean_vars_one(c, opt, ordered_read_ids, is_rev, ref_seq, ref_beg, ref_end, reg_beg, reg_end, pre_regs, n_pre_regs, low_comp, n_low, out);
     if (rc) lcd_clean_vars_free(out);
@@ -326,6 +327,7 @@ int lcd_chunk_clean_vars_batch(int n, const lcd_chunk_t *const *chunks, const lc
                                const uint8_t *const *ref_seq, const int64_t *ref_beg, const int64_t *ref_end, const int64_t *reg_beg, const int64_t *reg_end,
                                const lcd_noisy_iv_t *const *pre_regs, const int *n_pre_regs, const int64_t *const *low_comp, const int *n_low, lcd_clean_vars_t *outs) {
     if (n <= 0) return 0;
+    for (int c = 0; c < n; ++c) if (chunks && chunks[c] && chunks[c]->pending) return set_err(-4, "lcd_chunk_clean_vars: the chunk was opened and not resolved (lcd_chunk_resolve)");
     if (ensure_init()) return -1;
     std::vector<int> rc(n, 0);
     std::vector<std::string> err(n);
@@ -628,6 +630,7 @@ int lcd_chunk_plan_pass_batch(int n_chunks, const lcd_chunk_t *const *chunks, co
     if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, W + ": n_chunks < 0") : 0;
     if (!chunks || !opt || !n_regs || !regs || !done || !ordered_read_ids || !is_skipped || !ref_beg || !ref_end || !outs) return set_err(-4, W + ": NULL argument");
     memset(outs, 0, sizeof(lcd_pass_plan_t) * (size_t)n_chunks);
+    for (int c = 0; c < n_chunks; ++c) if (chunks[c] && chunks[c]->pending) return set_err(-4, W + ": the chunk was opened and not resolved (lcd_chunk_resolve)");
     // 1. host: validation; nothing touches the device on malformed input
     long long G = 0;
     for (int c = 0; c < n_chunks; ++c) {

@@ -66,6 +66,42 @@ int lcd_stitch_chunks(lcd_chunk_phase_t *chunks, int n, int update_reads) {
     return 0;
 }
 
+// the stitch of a chain of chunks, window by window: what flip_variant_hap reads of `pre` is its FINAL state, so a copy of the last chunk's arrays taken after its
+// own join is all the next window needs
+void lcd_stitch_carry_free(lcd_stitch_carry_t *c) {
+    if (!c) return;
+    free(c->is_skipped); free(c->haps); free(c->phase_sets); free(c->down_ovlp_read_i);
+    memset(c, 0, sizeof(*c));
+}
+int lcd_stitch_chunks_carry(lcd_chunk_phase_t *chunks, int n, int update_reads, const lcd_stitch_carry_t *carry_in, lcd_stitch_carry_t *carry_out) {
+    if (n > 0 && carry_in && carry_in->valid) {
+        lcd_chunk_phase_t pre; memset(&pre, 0, sizeof(pre));
+        pre.tid = carry_in->tid; pre.n_reads = carry_in->n_reads; pre.n_vars = carry_in->n_vars; pre.is_skipped = carry_in->is_skipped; pre.haps = carry_in->haps;
+        pre.phase_sets = carry_in->phase_sets; pre.n_down_ovlp = carry_in->n_down_ovlp; pre.down_ovlp_read_i = carry_in->down_ovlp_read_i;
+        const int rc = lcd_flip_variant_hap(&pre, chunks, update_reads);
+        if (rc) return rc;
+    }
+    const int rc = lcd_stitch_chunks(chunks, n, update_reads);
+    if (rc) return rc;
+    if (!carry_out) return 0;
+    lcd_stitch_carry_t c; memset(&c, 0, sizeof(c));
+    auto dup = [](const void *p, size_t bytes) { void *q = malloc(bytes + 1); if (p && bytes) memcpy(q, p, bytes); return q; };
+    if (n > 0) {
+        const lcd_chunk_phase_t &l = chunks[n - 1];
+        c.valid = 1; c.tid = l.tid; c.n_reads = l.n_reads; c.n_vars = l.n_vars; c.n_down_ovlp = l.n_down_ovlp;
+        c.is_skipped = (uint8_t *)dup(l.is_skipped, (size_t)l.n_reads); c.haps = (int *)dup(l.haps, (size_t)l.n_reads * sizeof(int));
+        c.phase_sets = (int64_t *)dup(l.phase_sets, (size_t)l.n_reads * sizeof(int64_t)); c.down_ovlp_read_i = (int *)dup(l.down_ovlp_read_i, (size_t)l.n_down_ovlp * sizeof(int));
+    } else if (carry_in && carry_in->valid) {
+        if (carry_in == carry_out) return 0;
+        c = *carry_in;
+        c.is_skipped = (uint8_t *)dup(carry_in->is_skipped, (size_t)c.n_reads); c.haps = (int *)dup(carry_in->haps, (size_t)c.n_reads * sizeof(int));
+        c.phase_sets = (int64_t *)dup(carry_in->phase_sets, (size_t)c.n_reads * sizeof(int64_t)); c.down_ovlp_read_i = (int *)dup(carry_in->down_ovlp_read_i, (size_t)c.n_down_ovlp * sizeof(int));
+    }
+    lcd_stitch_carry_free(carry_out);   // (carry_in == carry_out: read above, replaced now)
+    *carry_out = c;
+    return 0;
+}
+
 void lcd_call_opt_default(lcd_call_opt_t *o) {
     o->log_p = -3.0; o->log_1p = -0.00043451177401769168 /* log10(1 - 0.001) */; o->log_2 = 0.301023; o->max_gq = 60; o->max_qual = 60;
     o->min_sv_len = 30; o->min_dp = 5; o->min_alt_dp = 2; o->out_amb_base = 0;

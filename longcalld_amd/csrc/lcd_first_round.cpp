@@ -26,6 +26,7 @@ int lcd_chunks_first_round(int n, lcd_first_chunk_t *ch, const lcd_clean_opt_t *
         const lcd_first_chunk_t &x = ch[c];
         const std::string at = W + ": chunk " + std::to_string(c) + ": ";
         if (!x.chunk || !x.ref_seq) return set_err(-4, at + "NULL chunk / ref_seq");
+        if (x.chunk->pending) return set_err(-4, at + "the chunk was opened and not resolved (lcd_chunk_resolve)");
         if (x.ref_end < x.ref_beg) return set_err(-4, at + "ref_end < ref_beg");
         if (x.reg_beg < 1 || x.reg_end < x.reg_beg || x.reg_end - x.reg_beg > (1ll << 28)) return set_err(-4, at + "region [reg_beg, reg_end] out of range");
         if (x.chunk->device != ch[0].chunk->device) return set_err(-4, W + ": chunks on different devices");

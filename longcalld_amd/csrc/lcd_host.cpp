@@ -2428,6 +2428,7 @@ int lcd_wfa_batch(int n, const uint8_t *pool, uint64_t pool_len, const uint64_t 
 // PCIe for a region.  Otherwise lcd_batch_add_region_from_chunk (same results).  The batch must live on the chunk's device.
 int lcd_batch_add_region_from_chunk_dev(lcd_batch_t *b, const lcd_chunk_t *c, int64_t reg_beg, int64_t reg_end, int n, const int *read_ids, const int *read_beg,
                                         const int *read_end, const int *cover, const int *haps, const int64_t *phase_sets, const uint8_t *ref_seq, int ref_seq_len) {
+    if (c->pending) return set_err(-4, "lcd_batch_add_region_from_chunk_dev: the chunk was opened and not resolved (lcd_chunk_resolve)");
     if (b->device >= 0 && b->device != c->device) return set_err(-4, "lcd_batch_add_region_from_chunk_dev: batch and chunk on different devices");
     std::vector<int> lens(n); std::vector<const uint8_t *> sp(n, nullptr), qp(n, nullptr);
     for (int i = 0; i < n; ++i) {
@@ -2558,6 +2559,7 @@ int lcd_batch_region_n_cons(lcd_batch_t *b, int region) {
 int lcd_batch_add_planned(lcd_batch_t *b, const lcd_chunk_t *c, const lcd_pass_plan_t *plan, const int *haps, const int64_t *phase_sets, const uint8_t *ref_seq,
                           int64_t ref_beg, int *region_idx_out) {
     if (!b || !c || !plan || !haps || !phase_sets || !ref_seq) return set_err(-4, "lcd_batch_add_planned: NULL argument");
+    if (c->pending) return set_err(-4, "lcd_batch_add_planned: the chunk was opened and not resolved (lcd_chunk_resolve)");
     if (plan->n_regs < 0 || (plan->n_regs > 0 && (!plan->status || !plan->beg || !plan->end || !plan->read_off))) return set_err(-4, "lcd_batch_add_planned: incomplete plan");
     for (int i = 0; i < plan->n_regs; ++i) {
         if (plan->status[i] != LCD_PLAN_SUBMIT) continue;

@@ -172,6 +172,10 @@ struct RegionRec {
 // pre_process_noisy_regs' host part in front of the read support (lcd_noisy_regs.cpp): cr_index, low-complexity extension, cr_merge twice
 void pre_regs_merge(std::vector<NIv> &v, const int64_t *low_comp, int n_low);
 
+// lcd_call_file's links of a window of chunks to what lies outside it (lcd_call.cpp: chunks_call_core)
+struct CallLinks { const char *const *chroms; const int *tids; const lcd_stitch_carry_t *carry_in; lcd_stitch_carry_t *carry_out; int next_tid; int64_t next_beg, next_end; };
+int chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, lcd_var1_t **records, int *n_records, char **vcf_body);
+
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
 } // namespace lcd_internal
@@ -233,6 +237,12 @@ struct lcd_batch_s {
     lcd_batch_stats_t st;
 };
 
+// what lcd_chunk_open_from_bam leaves for lcd_chunk_resolve (lcd_chunk.cpp): the loader's per-read tables, the CIGAR words gathered in HBM, the aux jobs
+struct ChunkPending {
+    int64_t reg_beg = 0, reg_end = 0, tlen = 0;
+    std::vector<int64_t> pos0, rl_true; std::vector<int> ncig, qlen, nindel; std::vector<uint64_t> coff, soff, qoff; std::vector<RefCmpOut> counts;
+    std::vector<BamAuxJob> auxj; lcd_internal::DevBuf d_cig;
+};
 // a device-resident chunk (lcd_chunk.cpp)
 struct lcd_chunk_s {
     int device = 0, n_reads = 0; lcd_digar_opt_t opt;
@@ -250,6 +260,7 @@ struct lcd_chunk_s {
     std::vector<uint64_t> rec_beg, rec_stop; std::vector<int> rec_read; std::vector<int64_t> rec_pos0, rec_endpos;
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
+    std::unique_ptr<ChunkPending> pending;                 // lcd_chunk_open_from_bam: set until lcd_chunk_resolve (a handle with it has no digars yet)
     DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use
     ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); }
 };
