@@ -874,7 +874,7 @@ void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, 
  * without a newline, or NULL) appended to its text, compressed into its own block(s); then region c's records in region order, the skip counts of region c being
  * its kept / filtered records that overlap region c - 1's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691); every region's stream through
  * lcd_bgzf_deflate_dev_ptr; the EOF member last.  Only compressed bytes cross PCIe; the file is written with fwrite.  htslib's sam_hdr_add_pg chooses ID / PP
- * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written; --refine-aln, CRAM / SAM output and several input files are not supported.
+ * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written by these entry points (lcd_bam_writer_open_indexed writes one); --refine-aln, CRAM / SAM output and several input files are not supported.
  * lcd_call_bam_regions_out: lcd_call_bam_regions with the alignment output written after lcd_chunks_call succeeded (bam_out NULL: none).  A failure of the output
  * (unwritable path) returns < 0 with lcd_last_error and leaves *records / *vcf_body / the chunks' out members valid: free them with lcd_call_free as usual. */
 typedef struct lcd_tagged_s lcd_tagged_t;
@@ -969,7 +969,7 @@ void lcd_vcf_writer_abort(lcd_vcf_writer_t *w);
  * text to the VCF writer, the window to the BAM writer; then the window is freed: nothing of it stays but the carry.  overlap 1: the three stages run on three host
  * threads joined by queues of depth one (at most three windows alive); 0: in turn on the calling thread.  Records, text, flips and the output BAM's record stream do
  * not depend on window_chunks, overlap or loader_threads.  The first error stops the pipeline, every thread is joined, both outputs are closed as they are (no EOF
- * member) and the failing stage's code and lcd_last_error are returned.  Somatic / refine settings: -2.  A missing .bai / .fai: -30 with the path in the message.
+ * member) and the failing stage's code and lcd_last_error are returned.  Somatic / refine settings: -2.  A missing .bai / .fai: -30 with the path in the message (lcd_call_file_indexed builds them on request).
  * Defaults: chunk_len 0 = 500 000; window_chunks 0 = 32 (HiFi) / 16 (ONT); overlap -1 = 0 (pipelining did not win reliably where it was measured, profiles/NOTES_call_file.md);
  * loader_threads 0 = 4, or the CPUs the process may use when fewer (an explicit value is cut to 16); bai_path NULL =
  * <bam>.bai; sample_name NULL = lcd_bam_sample_name, else the BAM path; vcf_path NULL or "-" = stdout.  The VCF header names every contig of the BAM header.
@@ -998,6 +998,84 @@ typedef struct lcd_file_stats_t {
 void lcd_file_job_default(lcd_file_job_t *job);     /* zeroes; overlap = -1 */
 int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats);
 void lcd_file_stats_free(lcd_file_stats_t *stats);
+
+/* ---- indexes: .bai built on the device, .fai on the host (htslib's sam_index_build / fai_build are not in the checkout; src/call_var_main.c:675-686 builds a
+ * missing alignment index and goes on).  The index content, SAM specification 5.2-5.3; any reader that follows it gets correct answers:
+ *   1 interval     beg = pos (0-based), end = bam_endpos under the rule above (a record with the unmapped flag, or whose CIGAR consumes no reference, spans one base;
+ *                  the CIGAR of a read with more than 65 535 operations comes from its CG tag).
+ *   2 no coord.    a record with refid < 0 or pos < 0 is not indexed and counts in n_no_coor.
+ *   3 order        indexed records are non-decreasing in (refid, pos) and none follows a no-coordinate record, else LCD_ERR_BAI_ORDER with the record number (0-based,
+ *                  counted over all records of the file) in the message; end > 2^29 is LCD_ERR_BAI_CSI ("only BAI is supported, not CSI").  PROJECT RULE, made by the
+ *                  device builder only (its window arrays are sized from the header's contig lengths, (len >> 14) + 1 words): a refid outside the header's table, or
+ *                  a record that ends behind the last 16 kb window of its contig, is LCD_ERR_BAI_CONTIG; lcd_bai_from_records has no lengths and does not test it.
+ *   4 bin          reg2bin(beg, end) of specification 5.3.
+ *   5 offsets      (compressed file offset of the member << 16) | offset inside its payload.  PROJECT RULE: a position at the very end of a member's payload is written
+ *                  as the immediately following member's start with offset 0 -- an empty member and the EOF member count as following members; if none follows, the
+ *                  file size.  A record's begin and the end of the record before it are the same position and get the same offset.
+ *   6 chunks       a maximal run of consecutive indexed records with equal (refid, bin) is one chunk [vbeg(first), vend(last)]; inside a bin chunks stay in file order.
+ *                  PROJECT RULE: a chunk is merged into the one before it in its bin when prev.vend >> 16 >= next.vbeg >> 16 (no member is inflated twice for one
+ *                  bin).  No bins are folded into parents.
+ *   7 bins         ascending bin number; for a contig that has records the pseudo-bin 37450 comes last with two chunks: (vbeg of its first record, vend of its last)
+ *                  and (n_mapped, n_unmapped); n_unmapped counts records with flag bit 4; n_bin includes the pseudo-bin.
+ *   8 linear       windows beg >> 14 .. (end - 1) >> 14 take the smallest vbeg; n_intv = highest set window + 1; an unset window takes the previous window's value,
+ *                  an unset window 0 is 0.
+ *   9 trailer      a contig without records has n_bin = 0 and n_intv = 0; the trailing uint64 n_no_coor is always written.
+ *  10 slabs        the bytes depend on nothing but the file: not on the slab size, the number of slabs, or where a slab border falls.
+ * lcd_bai_from_records: the finisher on its own, pure host code -- rules 2-9 applied to a record table (flag bit 4 = unmapped; vbeg / vend as rule 5 gives them).
+ * *bytes malloc()'d (free()).  Returns 0 or LCD_ERR_BAI_ORDER / LCD_ERR_BAI_CSI / -4.
+ * lcd_bai_builder_*: the accumulating builder.  add_stream takes a stream of whole BAM records that already lies in HBM, from first_record_offset on (the stream
+ * must be readable 64 bytes behind n_bytes), with the table of the BGZF members it was inflated from -- per member the inflated start offset inside the stream, the
+ * compressed file offset and the payload length -- and end_coff, the file offset behind the last member (rule 5 for a position at the stream's end).  It runs the
+ * record walk, the CIGAR statistics, lcd_bai_entry_kernel and lcd_bai_compact_kernel (bai_kernel.hip) and accumulates chunk lists, the per-contig window arrays in HBM
+ * (allocated for a contig when its first record arrives) and the counters.  *next_record_offset = the offset of the first record that is not complete inside the
+ * stream (== n_bytes when all were).  finish serialises (out_path NULL: nothing is written; the bytes are still available through lcd_bai_builder_bytes).  After an
+ * error the builder only accepts destroy.
+ * lcd_bai_build: the whole-file driver.  The file is read slab by slab (opt->slab_members BGZF members per slab; 0 = 4096, at most 256 MB inflated), every slab is
+ * inflated by lcd_bgzf_inflate_dev and handed to add_stream; the next slab starts at the member that holds the first unfinished record (at most one record's worth
+ * of members is inflated twice); a record larger than a slab doubles the slab for that step (a block_size below 32 is refused at once, -33, and the growth ends
+ * at one maximal record).  The file is read in pieces of 16 MB; bytes read behind a slab's last member are kept for the next slab.  The BAM header and the reference table are skipped by parsing them.
+ * Slabs run one after the other (no two in flight).  On an error nothing is left at out_path and no device buffer stays in the ledger.
+ * lcd_fai_build: host code; one NAME\tLENGTH\tOFFSET\tLINEBASES\tLINEWIDTH line per sequence.  The name ends at the first whitespace; \n and \r\n line ends, a last
+ * line without a newline, blank lines at the end of the file and a shorter last line per sequence are accepted; a sequence whose other lines differ in length
+ * (LCD_ERR_FAI_FORMAT, the sequence's name in the message), a duplicate name, a file that does not start with '>' and a compressed FASTA are refused. */
+#define LCD_ERR_BAI_ORDER (-50)
+#define LCD_ERR_BAI_CSI (-51)
+#define LCD_ERR_FAI_FORMAT (-52)
+#define LCD_ERR_BAI_CONTIG (-53)
+int lcd_bai_from_records(int n_ref, int64_t n_rec, const int *refid, const int64_t *beg, const int64_t *end, const int *flag, const uint64_t *vbeg, const uint64_t *vend,
+                         uint8_t **bytes, size_t *n);
+typedef struct lcd_bai_member_t { uint64_t uoff, coff; uint32_t ulen, pad; } lcd_bai_member_t;
+typedef struct lcd_bai_builder_s lcd_bai_builder_t;
+lcd_bai_builder_t *lcd_bai_builder_create(int n_ref, const int64_t *ref_lens);
+int lcd_bai_builder_add_stream(lcd_bai_builder_t *b, uint64_t dev_ptr, size_t n_bytes, size_t first_record_offset, size_t n_members, const lcd_bai_member_t *members,
+                               uint64_t end_coff, size_t *next_record_offset);
+int lcd_bai_builder_finish(lcd_bai_builder_t *b, const char *out_path);
+int lcd_bai_builder_bytes(const lcd_bai_builder_t *b, const uint8_t **bytes, size_t *n);   /* after finish; borrowed */
+void lcd_bai_builder_destroy(lcd_bai_builder_t *b);
+typedef struct lcd_bai_opt_t { int slab_members, verify_crc; } lcd_bai_opt_t;
+typedef struct lcd_bai_stats_t {
+    int64_t n_records, n_indexed, n_mapped, n_unmapped, n_no_coor, n_chunks, n_slabs, n_members, bytes_in, bytes_inflated, bytes_index;
+    double ms_read, ms_inflate, ms_walk, ms_stat, ms_entry, ms_finish, ms_wall;
+} lcd_bai_stats_t;
+int lcd_bai_build(const char *bam_path, const char *out_path, const lcd_bai_opt_t *opt /* may be NULL */, lcd_bai_stats_t *stats /* may be NULL */);
+int lcd_fai_build(const char *fasta_path, const char *out_path /* NULL: <fasta>.fai */);
+/* The outputs with their indexes.  lcd_bam_writer_open_indexed: the writer owns a builder; after each append's tag rewrite and deflate the tagged stream in HBM goes
+ * to add_stream with the member table the deflater reports and the writer's running file offset; close writes the index to index_path (NULL: <out.bam>.bai) after
+ * the EOF member.  If the output violates rule 3 -- lcd_plan_chunks sorts and merges a contig's regions, so the plan cannot cause it; an input whose records are out
+ * of order inside a region can, and so can a caller of lcd_bam_writer_append who hands chunks over out of order -- or names a position outside the header's contigs
+ * (LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_BAI_CONTIG), the BAM is still completed, no index file is left behind and idx_stats says so: that is not an error of
+ * the run.  Any other failure of the index (a malformed record in the writer's own stream, a device error) fails the append.  *idx_stats must outlive the writer.
+ * lcd_call_file_indexed: lcd_call_file is this call with idx == NULL.  build_missing_bai / build_missing_fai: a missing input index is built at the path the job
+ * would have read (bai_path or <bam>.bai, <fasta>.fai) and the run goes on; an unwritable location is -30 with the path in the message; an index that exists is
+ * never rebuilt or touched.  write_out_bai needs job->bam_out; out_bai_path NULL = <out.bam>.bai. */
+typedef struct lcd_index_opt_t { int build_missing_bai, build_missing_fai, write_out_bai; const char *out_bai_path; int slab_members; } lcd_index_opt_t;
+typedef struct lcd_index_stats_t {
+    int built_bai, built_fai, wrote_out_bai, out_bai_skipped;      /* out_bai_skipped: the LCD_ERR_* code that kept the output's index from being written, or 0 */
+    char out_bai_skip_reason[256];
+    int64_t out_bai_bytes, out_n_indexed, out_n_no_coor; double ms_build_bai, ms_build_fai, ms_out_bai;
+} lcd_index_stats_t;
+lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_out_t *out, const char *index_path, lcd_index_stats_t *idx_stats);
+int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats);
 
 #ifdef __cplusplus
 }

@@ -214,6 +214,32 @@ class LcdFileStats(C.Structure):
         ("records", C.POINTER(LcdVar1)), ("n_kept_records", C.c_int)]
 
 
+class LcdBaiMember(C.Structure):
+    """lcd_bai_member_t: one BGZF member of a stream handed to lcd_bai_builder_add_stream"""
+    _fields_ = [("uoff", C.c_uint64), ("coff", C.c_uint64), ("ulen", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class LcdBaiOpt(C.Structure):
+    _fields_ = [("slab_members", C.c_int), ("verify_crc", C.c_int)]
+
+
+class LcdBaiStats(C.Structure):
+    """lcd_bai_stats_t: the counters and per-stage times of lcd_bai_build"""
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_indexed", "n_mapped", "n_unmapped", "n_no_coor", "n_chunks", "n_slabs", "n_members", "bytes_in", "bytes_inflated",
+                                         "bytes_index")] + [(n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_walk", "ms_stat", "ms_entry", "ms_finish", "ms_wall")]
+
+
+class LcdIndexOpt(C.Structure):
+    """lcd_index_opt_t: what lcd_call_file_indexed builds and writes"""
+    _fields_ = [("build_missing_bai", C.c_int), ("build_missing_fai", C.c_int), ("write_out_bai", C.c_int), ("out_bai_path", C.c_char_p), ("slab_members", C.c_int)]
+
+
+class LcdIndexStats(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("built_bai", "built_fai", "wrote_out_bai", "out_bai_skipped")] + [("out_bai_skip_reason", C.c_char * 256)] + [
+        (n, C.c_int64) for n in ("out_bai_bytes", "out_n_indexed", "out_n_no_coor")] + [(n, C.c_double) for n in ("ms_build_bai", "ms_build_fai", "ms_out_bai")]
+
+
+LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG = -50, -51, -52, -53
 LCD_CTG_AUTOSOME_XY, LCD_CTG_AUTOSOME, LCD_CTG_ALL = 0, 1, 2
 
 _lib = None
@@ -237,6 +263,8 @@ EXPORTS = [
     "lcd_bam_contigs", "lcd_bam_contigs_free", "lcd_bam_sample_name", "lcd_plan_chunks", "lcd_chunk_plan_free", "lcd_stitch_chunks_carry", "lcd_stitch_carry_free",
     "lcd_chunk_open_from_bam", "lcd_chunk_resolve", "lcd_bam_writer_open", "lcd_bam_writer_append", "lcd_bam_writer_close", "lcd_bam_writer_abort",
     "lcd_vcf_writer_open", "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_call_file", "lcd_file_stats_free",
+    "lcd_bai_from_records", "lcd_bai_builder_create", "lcd_bai_builder_add_stream", "lcd_bai_builder_finish", "lcd_bai_builder_bytes", "lcd_bai_builder_destroy", "lcd_bai_build",
+    "lcd_fai_build", "lcd_bam_writer_open_indexed", "lcd_call_file_indexed",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -399,6 +427,19 @@ def load_library():
     lib.lcd_file_job_default.restype = None
     lib.lcd_call_file.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdFileStats)]
     lib.lcd_file_stats_free.argtypes = [C.POINTER(LcdFileStats)]
+    lib.lcd_call_file_indexed.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats)]
+    lib.lcd_bam_writer_open_indexed.restype = C.c_void_p
+    lib.lcd_bam_writer_open_indexed.argtypes = [C.c_char_p, C.POINTER(LcdBamOut), C.c_char_p, C.POINTER(LcdIndexStats)]
+    lib.lcd_bai_from_records.argtypes = [C.c_int, C.c_int64, i32p, i64p, i64p, i32p, u64p_, u64p_, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    lib.lcd_bai_builder_create.restype = C.c_void_p
+    lib.lcd_bai_builder_create.argtypes = [C.c_int, i64p]
+    lib.lcd_bai_builder_add_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(LcdBaiMember), C.c_uint64, C.POINTER(C.c_size_t)]
+    lib.lcd_bai_builder_finish.argtypes = [C.c_void_p, C.c_char_p]
+    lib.lcd_bai_builder_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    lib.lcd_bai_builder_destroy.argtypes = [C.c_void_p]
+    lib.lcd_bai_builder_destroy.restype = None
+    lib.lcd_bai_build.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(LcdBaiOpt), C.POINTER(LcdBaiStats)]
+    lib.lcd_fai_build.argtypes = [C.c_char_p, C.c_char_p]
     lib.lcd_file_stats_free.restype = None
     lib.lcd_call_free.restype = None
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]

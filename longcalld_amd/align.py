@@ -1596,11 +1596,13 @@ def vcf_write(path, texts, bgzf=0, header_text=None):
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False):
+              keep_records=False, index=None):
     """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
     phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
-    flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters"""
-    from ._lib import LcdBamOut, LcdFileJob, LcdFileStats
+    flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
+    index (default None: lcd_call_file as it is): True, or a dict with build_missing_bai / build_missing_fai / write_out_bai / out_bai_path / slab_members ->
+    lcd_call_file_indexed; the result then has "index" = lcd_index_stats_t's fields (out_bai_skipped != 0: the output's index was not written, out_bai_skip_reason says why)"""
+    from ._lib import LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
     job = LcdFileJob(); lib.lcd_file_job_default(C.byref(job))
@@ -1618,10 +1620,19 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
         bo = LcdBamOut(); bo.path = _enc(bam_out["path"]); bo.pg_line = opt_s(bam_out.get("pg_line")); bo.block_payload = int(bam_out.get("block_payload", 0))
         job.bam_out = C.pointer(bo)
     st = LcdFileStats()
-    rc = lib.lcd_call_file(C.byref(job), C.byref(cfg), C.byref(st))
+    ist = None
+    if index:
+        d = dict(build_missing_bai=1, build_missing_fai=1, write_out_bai=1 if bam_out is not None else 0) if index is True else dict(index)
+        io = LcdIndexOpt(int(d.get("build_missing_bai", 0)), int(d.get("build_missing_fai", 0)), int(d.get("write_out_bai", 0)), opt_s(d.get("out_bai_path")), int(d.get("slab_members", 0)))
+        ist = LcdIndexStats()
+        rc = lib.lcd_call_file_indexed(C.byref(job), C.byref(cfg), C.byref(io), C.byref(st), C.byref(ist))
+    else:
+        rc = lib.lcd_call_file(C.byref(job), C.byref(cfg), C.byref(st))
     try:
         check(rc, lib)
         res = {k: getattr(st, k) for k, _t in LcdFileStats._fields_[:14]}
+        if ist is not None:
+            res["index"] = {k: (getattr(ist, k).decode() if k == "out_bai_skip_reason" else getattr(ist, k)) for k, _t in LcdIndexStats._fields_}
         if keep_records:
             res["chunks"] = [dict(tid=int(st.chunk_tid[i]), reg_beg=int(st.chunk_reg_beg[i]), reg_end=int(st.chunk_reg_end[i]), n_reads=int(st.chunk_n_reads[i]),
                                   n_passes=int(st.chunk_n_passes[i]), flip_hap=int(st.chunk_flip_hap[i]), flip_pre_PS=int(st.chunk_flip_pre_PS[i]),
@@ -1632,3 +1643,42 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))
+
+
+# ---------------- indexes: .bai on the device, .fai on the host ----------------
+def bai_from_records(n_ref, refid, beg, end, flag, vbeg, vend):
+    """lcd_bai_from_records (pure host code): a record table -> the bytes of its .bai"""
+    lib = load_library()
+    a = [np.ascontiguousarray(refid, np.int32), np.ascontiguousarray(beg, np.int64), np.ascontiguousarray(end, np.int64), np.ascontiguousarray(flag, np.int32),
+         np.ascontiguousarray(vbeg, np.uint64), np.ascontiguousarray(vend, np.uint64)]
+    n = len(a[0])
+    assert all(len(x) == n for x in a)
+    out, sz = C.c_void_p(), C.c_size_t()
+    tys = [C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_uint64, C.c_uint64]
+    check(lib.lcd_bai_from_records(int(n_ref), n, *[x.ctypes.data_as(C.POINTER(t)) for x, t in zip(a, tys)], C.byref(out), C.byref(sz)), lib)
+    try:
+        return C.string_at(out.value, sz.value)
+    finally:
+        _libc_free(out)
+
+
+def _libc_free(p):
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free.restype = None
+    libc.free(p)
+
+
+def bai_build(bam_path, out_path=None, slab_members=0, verify_crc=0):
+    """lcd_bai_build: the .bai of a BAM of any size, built on the device (out_path None: <bam>.bai) -> dict of lcd_bai_stats_t"""
+    from ._lib import LcdBaiOpt, LcdBaiStats
+    lib = load_library()
+    opt, st = LcdBaiOpt(int(slab_members), int(verify_crc)), LcdBaiStats()
+    check(lib.lcd_bai_build(_enc(bam_path), _enc(out_path if out_path is not None else bam_path + ".bai"), C.byref(opt), C.byref(st)), lib)
+    return {k: getattr(st, k) for k, _t in LcdBaiStats._fields_}
+
+
+def fai_build(fasta_path, out_path=None):
+    """lcd_fai_build (host code): <fasta>.fai (or out_path) -> the number of sequences"""
+    lib = load_library()
+    return check(lib.lcd_fai_build(_enc(fasta_path), _enc(out_path) if out_path is not None else None), lib)

@@ -11,17 +11,20 @@ REFUSED = {
     "-S": "SAM output (-S) is not supported: use -b", "--out-sam": "SAM output (-S) is not supported: use -b", "--out-cram": "CRAM output (-C FILE) is not supported: use -b",
     "--out-var-rnames": "--out-var-rnames is not supported", "--out-som-var-rnames": "--out-som-var-rnames is not supported", "--out-sv-rnames": "--out-sv-rnames is not supported",
 }
-FLAGS = {"--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
           "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
-  ref.fa needs ref.fa.fai, in.bam needs in.bam.bai (the library does not build indexes)
+       python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
+       python -m longcalld_amd.cli faidx ref.fa               build ref.fa.fai
+  ref.fa needs ref.fa.fai, in.bam needs in.bam.bai; a missing one is an error unless --make-index is given
 Input:    --hifi (default) | --ont   --region-file FILE   --autosome-XY (default) | --autosome | --all-ctg   -E/--exclude-ctg STR (repeatable)   -r/--ref-idx FILE
 Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z   -l/--min-sv-len INT   -H/--no-vcf-header   --amb-base   -b/--out-bam FILE
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
+Index:    --make-index   build a missing in.bam.bai / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
 Not supported (refused with exit status 2): -s, --refine-aln, -L, -X, -T, -S, -C FILE, --out-*-rnames
 """
@@ -67,12 +70,46 @@ def parse(argv):
     return o, pos
 
 
+def parse_index(argv):
+    """index in.bam [out.bai] | faidx ref.fa -> (command, paths) or an int exit status"""
+    cmd, rest = argv[0], argv[1:]
+    if any(a in ("-h", "--help") for a in rest):
+        sys.stdout.write(USAGE); return 0
+    bad = [a for a in rest if a.startswith("-") and a != "-"]
+    if bad:
+        return refuse(f"unknown option {bad[0]}")
+    if (cmd == "index" and len(rest) not in (1, 2)) or (cmd == "faidx" and len(rest) != 1):
+        sys.stderr.write(USAGE); return 2
+    return cmd, rest
+
+
+def main_index(argv):
+    p = parse_index(argv)
+    if isinstance(p, int):
+        return p
+    cmd, paths = p
+    from . import align
+    try:
+        if cmd == "index":
+            st = align.bai_build(paths[0], paths[1] if len(paths) > 1 else None)
+            sys.stderr.write(f"longcalld_amd index: {st['n_records']} records ({st['n_no_coor']} without coordinate), {st['n_slabs']} slabs, {st['ms_wall'] / 1000:.2f} s\n")
+        else:
+            n = align.fai_build(paths[0])
+            sys.stderr.write(f"longcalld_amd faidx: {n} sequences\n")
+    except align.LcdError as e:
+        sys.stderr.write(f"longcalld_amd {cmd}: {e}\n")
+        return 1
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv or argv[0] in ("-h", "--help"):
         sys.stdout.write(USAGE); return 0 if argv else 2
+    if argv[0] in ("index", "faidx"):
+        return main_index(argv)
     if argv[0] != "call":
-        return refuse(f"unknown command {argv[0]} (the only command is: call)")
+        return refuse(f"unknown command {argv[0]} (the commands are: call, index, faidx)")
     p = parse(argv[1:])
     if isinstance(p, int):
         return p
@@ -115,10 +152,13 @@ def main(argv=None):
         st = align.call_file(bam, fasta, contig_mode=mode, exclude=o["exclude"], regions=regions, region_bed_path=o.get("region_file"), chunk_len=num.get("chunk_len", 0),
                              window_chunks=num.get("window_chunks", 0), overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0),
                              min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
-                             no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg)
+                             no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
+                             index=True if "--make-index" in o["flags"] else None)
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
+    if st.get("index", {}).get("out_bai_skipped"):
+        sys.stderr.write("longcalld_amd call: the output BAM was written without an index: " + st["index"]["out_bai_skip_reason"] + "\n")
     if st["plan_fallback"]:
         sys.stderr.write("longcalld_amd call: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
     sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads, {st['n_vcf_lines']} VCF lines, "

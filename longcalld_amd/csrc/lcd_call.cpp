@@ -140,7 +140,11 @@ extern "C" {
 // one @PG line, then per region its records with HP:i / PS:i rewritten in HBM (lcd_chunk_tag_records) and compressed there (lcd_bgzf_deflate_dev_ptr); only
 // compressed bytes come down, and they go to the file with fwrite.  A region leaves out the records the region before it already wrote: its kept and its filtered
 // records that overlap that region's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691) -- in a sorted file they are the first ones.
-struct lcd_bam_writer_s { FILE *f = nullptr; lcd_bam_out_t *out = nullptr; std::string path; std::vector<uint8_t> buf; };
+struct lcd_bam_writer_s {
+    FILE *f = nullptr; lcd_bam_out_t *out = nullptr; std::string path; std::vector<uint8_t> buf;
+    // lcd_bam_writer_open_indexed: the builder of the output's .bai (NULL: none, or given up), where the index goes, the file offset of the next member
+    lcd_bai_builder_t *bai = nullptr; std::string index_path; lcd_index_stats_t *ist = nullptr; uint64_t file_off = 0;
+};
 namespace {
 // download + fwrite of one compressed image, then free
 int writer_put(lcd_bam_writer_s *w, lcd_deflated_t *d, const std::string &W) {
@@ -151,9 +155,34 @@ int writer_put(lcd_bam_writer_s *w, lcd_deflated_t *d, const std::string &W) {
     w->buf.resize(sz + 1);
     int rc = lcd_deflated_to_host(d, 0, sz, w->buf.data());
     if (!rc && sz && fwrite(w->buf.data(), 1, sz, w->f) != sz) rc = set_err(-30, W + ": short write on " + w->path);
-    out->ms_deflate += lcd_deflated_kernel_ms(d); out->bytes_file += (int64_t)sz;
+    out->ms_deflate += lcd_deflated_kernel_ms(d); out->bytes_file += (int64_t)sz; w->file_off += sz;
     lcd_deflated_free(d);
     out->ms_download_write += now_ms() - t0;
+    return rc;
+}
+// the output's index gives up (rule 3: an input with records out of order inside a region, or chunks appended out of order; a position outside the header's
+// contigs): the BAM goes on, no index file stays, the statistics say why
+void writer_skip_index(lcd_bam_writer_s *w, int code) {
+    if (w->ist) { w->ist->out_bai_skipped = code; snprintf(w->ist->out_bai_skip_reason, sizeof(w->ist->out_bai_skip_reason), "%s", g_err.c_str()); }
+    lcd_bai_builder_destroy(w->bai); w->bai = nullptr;
+    remove(w->index_path.c_str());
+}
+// the records of one append (a tagged stream in HBM, about to be written as the members of d at the writer's file offset) into the output's index
+int writer_index_stream(lcd_bam_writer_s *w, const lcd_tagged_t *t, const lcd_deflated_t *d) {
+    const double t0 = now_ms();
+    const size_t nb = lcd_deflated_n_blocks(d);
+    std::vector<lcd_bai_member_t> tab(nb);
+    uint64_t u = 0, c = w->file_off;
+    for (size_t i = 0; i < nb; ++i) {
+        uint32_t payload = 0, bsize = 0;
+        if (int rc = lcd_deflated_block_info(d, i, &payload, &bsize, nullptr)) return rc;
+        tab[i].uoff = u; tab[i].coff = c; tab[i].ulen = payload; tab[i].pad = 0; u += payload; c += bsize;
+    }
+    size_t next = 0;
+    const int rc = lcd_bai_builder_add_stream(w->bai, lcd_tagged_dev_ptr(t), lcd_tagged_size(t), 0, nb, tab.data(), w->file_off + lcd_deflated_size(d), &next);
+    if (w->ist) w->ist->ms_out_bai += now_ms() - t0;
+    if (rc == LCD_ERR_BAI_ORDER || rc == LCD_ERR_BAI_CSI || rc == LCD_ERR_BAI_CONTIG) { writer_skip_index(w, rc); return 0; }
+    if (!rc && next != lcd_tagged_size(t)) return set_err(-24, "lcd_write_phased_bam: the tagged stream ends inside a record");
     return rc;
 }
 int writer_check_chunks(const std::string &W, int n, const lcd_call_chunk_t *chunks) {
@@ -213,7 +242,10 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
         for (int r : k->rec_read) ++(r >= 0 ? kept : filt);
         out->n_records_out += kept - nsk; out->n_filtered_out += filt - nsf; out->bytes_inflated += (int64_t)lcd_tagged_size(t);
         lcd_deflated_t *d = lcd_tagged_size(t) ? lcd_bgzf_deflate_dev_ptr(lcd_tagged_dev_ptr(t), lcd_tagged_size(t), out->block_payload, 0) : nullptr;
-        const int rc = lcd_tagged_size(t) ? writer_put(w, d, W) : 0;
+        int rc = 0;
+        if (lcd_tagged_size(t) && d && w->bai) rc = writer_index_stream(w, t, d);
+        if (rc) { lcd_deflated_free(d); lcd_tagged_free(t); return rc; }
+        rc = lcd_tagged_size(t) ? writer_put(w, d, W) : 0;
         lcd_tagged_free(t);
         if (rc) return rc;
     }
@@ -223,6 +255,7 @@ void lcd_bam_writer_abort(lcd_bam_writer_t *w) {
     if (!w) return;
     const std::string m = g_err;
     if (w->f) fclose(w->f);
+    if (w->bai) { lcd_bai_builder_destroy(w->bai); remove(w->index_path.c_str()); }
     delete w;
     g_err = m;
 }
@@ -231,9 +264,38 @@ int lcd_bam_writer_close(lcd_bam_writer_t *w) {
     if (!w) return set_err(-4, W + ": NULL argument");
     if (int rc = writer_put(w, lcd_bgzf_deflate_dev(nullptr, 0, w->out->block_payload, 1), W)) { lcd_bam_writer_abort(w); return rc; }   // the EOF member
     const std::string path = w->path;
-    const int rc = fclose(w->f);
+    int rc = fclose(w->f);
+    w->f = nullptr;
+    if (rc != 0) { lcd_bam_writer_abort(w); return set_err(-30, W + ": closing " + path + " failed"); }
+    if (w->bai) {   // the index after the EOF member
+        const double t0 = now_ms();
+        rc = lcd_bai_builder_finish(w->bai, w->index_path.c_str());
+        if (!rc && w->ist) {
+            const uint8_t *bytes = nullptr; size_t n = 0;
+            (void)lcd_bai_builder_bytes(w->bai, &bytes, &n);
+            w->ist->wrote_out_bai = 1; w->ist->out_bai_bytes = (int64_t)n;
+            if (n >= 8) { uint64_t nc = 0; memcpy(&nc, bytes + n - 8, 8); w->ist->out_n_no_coor = (int64_t)nc; }
+            w->ist->out_n_indexed = w->out->n_records_out + w->out->n_filtered_out - w->ist->out_n_no_coor;
+            w->ist->ms_out_bai += now_ms() - t0;
+        }
+        lcd_bai_builder_destroy(w->bai); w->bai = nullptr;
+    }
     delete w;
-    return rc != 0 ? set_err(-30, W + ": closing " + path + " failed") : 0;
+    return rc;
+}
+lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_out_t *out, const char *index_path, lcd_index_stats_t *idx_stats) {
+    const std::string W = "lcd_bam_writer_open_indexed";
+    if (!in_bam_path || !out || !out->path) { set_err(-4, W + ": NULL argument"); return nullptr; }
+    int n_ref = 0; char **names = nullptr; int64_t *lens = nullptr;
+    if (lcd_bam_contigs(in_bam_path, &n_ref, &names, &lens)) return nullptr;
+    lcd_bai_builder_t *bai = lcd_bai_builder_create(n_ref, lens);
+    lcd_bam_contigs_free(n_ref, names, lens);
+    if (!bai) return nullptr;
+    lcd_bam_writer_t *w = lcd_bam_writer_open(in_bam_path, out);
+    if (!w) { lcd_bai_builder_destroy(bai); return nullptr; }
+    w->bai = bai; w->ist = idx_stats; w->index_path = index_path ? std::string(index_path) : std::string(out->path) + ".bai";
+    remove(w->index_path.c_str());     // (an index of an earlier file at this path would not describe the one being written)
+    return w;
 }
 int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) {
     const std::string W = "lcd_write_phased_bam";

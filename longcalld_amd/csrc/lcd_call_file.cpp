@@ -383,9 +383,16 @@ struct Run {
 };
 } // namespace
 
-extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats) {
-    const std::string W = "lcd_call_file";
+extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats) { return lcd_call_file_indexed(job, cfg, nullptr, stats, nullptr); }
+
+extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats) {
+    const std::string W = idx ? "lcd_call_file_indexed" : "lcd_call_file";
     if (stats) memset(stats, 0, sizeof(*stats));
+    lcd_index_stats_t ist_local;
+    lcd_index_stats_t *ist = idx_stats ? idx_stats : &ist_local;
+    memset(ist, 0, sizeof(*ist));
+    if (idx && idx->write_out_bai && (!job || !job->bam_out)) return set_err(-4, W + ": write_out_bai needs bam_out");
+    if (idx && idx->slab_members < 0) return set_err(-4, W + ": negative slab_members");
     if (!job || !cfg || !stats || !job->bam_path || !job->fasta_path) return set_err(-4, W + ": NULL argument");
     if (job->bam_out && !job->bam_out->path) return set_err(-4, W + ": bam_out without a path");
     if (job->window_chunks < 0 || job->loader_threads < 0 || job->chunk_len < 0 || job->overlap < -1 || job->overlap > 1) return set_err(-4, W + ": negative window_chunks / loader_threads / chunk_len, or overlap outside -1 ... 1");
@@ -395,11 +402,24 @@ extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lc
     memset(&R.plan, 0, sizeof(R.plan)); memset(&R.carry, 0, sizeof(R.carry));
     R.bai = job->bai_path ? std::string(job->bai_path) : std::string(job->bam_path) + ".bai";
     R.is_ont = cfg->clean.is_ont != 0;
-    // the library reads indexes, it does not build them
-    for (const std::string &p : {R.bai, std::string(job->fasta_path) + ".fai"}) {
+    // an index that exists is read as it is; a missing one is built only when the caller asks for it (lcd_index_opt_t), at the path that would have been read
+    for (int which = 0; which < 2; ++which) {
+        const std::string p = which == 0 ? R.bai : std::string(job->fasta_path) + ".fai";
         FILE *f = fopen(p.c_str(), "rb");
-        if (!f) return set_err(-30, W + ": cannot open the index " + p + " (the library does not build indexes)");
-        fclose(f);
+        if (f) { fclose(f); continue; }
+        if (!idx) return set_err(-30, W + ": cannot open the index " + p + " (the library does not build indexes here: lcd_call_file_indexed / --make-index does)");
+        if (!(which == 0 ? idx->build_missing_bai : idx->build_missing_fai))
+            return set_err(-30, W + ": cannot open the index " + p + " (lcd_index_opt_t." + (which == 0 ? "build_missing_bai" : "build_missing_fai") + " would build it)");
+        const double t0 = now_ms();
+        if (which == 0) {
+            lcd_bai_opt_t bo; bo.slab_members = idx->slab_members; bo.verify_crc = 0;
+            if (int rc = lcd_bai_build(job->bam_path, p.c_str(), &bo, nullptr)) return rc;
+            ist->built_bai = 1; ist->ms_build_bai = now_ms() - t0;
+        } else {
+            const int rc = lcd_fai_build(job->fasta_path, p.c_str());
+            if (rc < 0) return rc;
+            ist->built_fai = 1; ist->ms_build_fai = now_ms() - t0;
+        }
     }
     std::string text;
     if (int rc = bam_header_parts(job->bam_path, text, R.names, R.lens, W)) return rc;
@@ -439,7 +459,7 @@ extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lc
         free(hdr); free(sm);
         if (!R.vcf) { lcd_file_stats_free(stats); return -30; }
         if (job->bam_out) {
-            R.bam = lcd_bam_writer_open(job->bam_path, job->bam_out);
+            R.bam = idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(job->bam_path, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(job->bam_path, job->bam_out);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
         }
     }

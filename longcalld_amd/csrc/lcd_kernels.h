@@ -31,6 +31,11 @@ int lcd_deflate_lds_bytes();
 // bam_tag_kernel.hip: HP / PS rewrite of records in the inflated stream: measure (one lane per record), emit (one wavefront per record)
 void lcd_launch_bam_tag_measure(const BamTagJob *jobs, BamTagOut *outs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_tag_emit(const BamTagJob *jobs, const BamTagOut *outs, uint8_t *out, int n_jobs, hipStream_t st);
+// bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
+// counters; compact: scan of the workgroups' run heads + the dense chunk list)
+void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);
+void lcd_launch_bai_entry(const BaiJob &j, hipStream_t st);
+void lcd_launch_bai_compact(const BaiJob &j, hipStream_t st);
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st);
 void lcd_launch_compose(const CmpJob *jobs, CmpOut *outs, const CmpSeg *segs, int n_jobs, int emit, hipStream_t stream);
 void lcd_launch_vars_scan(const VarScanJob *jobs, VarScanOut *outs, int n_jobs, hipStream_t stream);

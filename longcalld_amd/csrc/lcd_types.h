@@ -238,6 +238,21 @@ struct SupChunk { uint64_t read_beg, read_end, iv_off, ivs; int n_reads, pad; };
 struct SupReg { long long st, en; int chunk, pad; };
 // lcd_bam_nm_kernel: a kept record's auxiliary fields [aux, end) as device addresses
 struct BamNmJob { uint64_t aux, end; };
+// ---------------- the .bai builder (bai_kernel.hip) ----------------
+// one BGZF member of a stream: where its payload starts in the inflated stream, its compressed file offset, its payload length (lcd_bai_member_t)
+struct BaiMember { uint64_t uoff, coff; uint32_t ulen, pad; };
+// one record: cls 0 no coordinate, 1 mapped, 2 placed with the unmapped flag; head: the first record of a run of equal (refid, bin)
+struct BaiEntry { uint64_t vbeg, vend; int refid; uint32_t bin, cls, head; };
+struct BaiChunk { int refid; uint32_t bin; uint64_t vbeg, vend; };
+struct BaiCtg { unsigned long long n_mapped, n_unmapped, first_vbeg, last_vend; };   // per contig, accumulated over every stream (first_vbeg starts all-ones)
+// a batch of n records of one stream.  win: per contig the device address of its window array (0: not allocated), n_win its length; err: the smallest
+// (record number << 4 | code) of a refused record (code 1 order, 2 behind a record without coordinate, 3 end > 2^29, 4 refid outside the table, 5 ends behind its
+// contig / no window array); c_*: the record in front of the batch (c_have 0: none); rec0: the file-wide number of the batch's first record
+struct BaiJob {
+    uint64_t descs, stats, statjobs, members, entries, win, n_win, ctg, err, block_cnt, block_off, chunks, minmax, stream;
+    uint64_t end_coff; long long rec0;
+    int n, n_members, n_ref, c_have, c_refid, c_pos, c_nocoor, pad;
+};
 // ---------------- the phased alignment output (deflate_kernel.hip, bam_tag_kernel.hip) ----------------
 // one BGZF payload's raw deflate stream in its slot: clen bytes, CRC-32 of the payload, kind 0 stored / 1 fixed / 2 dynamic codes, LZ77 tokens
 struct DeflateOut { uint32_t clen, crc, kind, n_tok; };
