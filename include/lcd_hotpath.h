@@ -874,7 +874,7 @@ void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, 
  * without a newline, or NULL) appended to its text, compressed into its own block(s); then region c's records in region order, the skip counts of region c being
  * its kept / filtered records that overlap region c - 1's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691); every region's stream through
  * lcd_bgzf_deflate_dev_ptr; the EOF member last.  Only compressed bytes cross PCIe; the file is written with fwrite.  htslib's sam_hdr_add_pg chooses ID / PP
- * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written by these entry points (lcd_bam_writer_open_indexed writes one); --refine-aln, CRAM / SAM output and several input files are not supported.
+ * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written by these entry points (lcd_bam_writer_open_indexed writes one); --refine-aln and CRAM / SAM output are not supported (several input files: lcd_call_files).
  * lcd_call_bam_regions_out: lcd_call_bam_regions with the alignment output written after lcd_chunks_call succeeded (bam_out NULL: none).  A failure of the output
  * (unwritable path) returns < 0 with lcd_last_error and leaves *records / *vcf_body / the chunks' out members valid: free them with lcd_call_free as usual. */
 typedef struct lcd_tagged_s lcd_tagged_t;
@@ -1076,6 +1076,56 @@ typedef struct lcd_index_stats_t {
 } lcd_index_stats_t;
 lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_out_t *out, const char *index_path, lcd_index_stats_t *idx_stats);
 int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats);
+
+/* ---- one sample from several alignment files (longcallD call ref.fa in.bam -X more.bam ... / -L list): src/call_var_main.c:361-400, 640-741 ----
+ * The ordinary shape of a PacBio / ONT sample is one BAM per SMRT cell or flow cell.  A chunk is made from a region image (whole BGZF blocks plus ranges of the
+ * inflated stream), so several files become ONE chunk by appending their region images in file order: one inflate launch, one record walk launch, and everything
+ * behind the chunk (first round, noisy rounds, K5, stitch, records, VCF) runs unchanged on the concatenated reads.  No kernel knows about files.
+ *   1 reads        collect_ref_seq_bam_main (src/bam_utils.c:1659-1716): for file 0, then file 1, ... the region iterator's records in file order with the flag / MAPQ
+ *                  filter; kept reads are appended, so the chunk's read ids and its record table are file-major and the reference window (meta) spans all files'
+ *                  reads.  The loader's stop rules ("a record at or behind reg_end", "records of a later contig") restart at each file, and a walk job ends at its own
+ *                  file's segment of the stream.  lcd_sort_chunk_reads' last tie-break, file order, becomes file-major order.
+ *   2 stitch       the reference keeps the overlap lists per file and pairs them per file (src/collect_var.c:1640-1660); here one list per chunk is built in chunk
+ *                  order, as before.  Both agree whenever the per-file counts of neighbours agree, which holds for sorted files; the total-count check and its
+ *                  error stay.
+ *   3 headers      tids, the VCF header's contigs and the output BAM's header (plus the @PG line) come from file 0 (:733-741, :1018-1019); the sample name is file
+ *                  0's lcd_bam_sample_name, else all input paths joined by ','.  The chunk level looks the contig up by name in every file's header.  PROJECT RULE
+ *                  (the reference uses file 0's tids for every file unchecked): lcd_call_files demands of every further file the reference table of file 0 -- same
+ *                  names, same lengths, same order -- else LCD_ERR_INPUT_HEADERS with the file and the first differing entry in the message, before any output file
+ *                  is created.
+ *   4 BAM output   write_read_to_bam (src/bam_utils.c:2009-2048): per chunk the records of file 0, then file 1, ...; each file leaves out what the chunk before has
+ *                  written.  The reference counts those per file (n_up_ovlp_reads[i], n_up_ovlp_skip_reads[i]; in a sorted file that file's first ones).  PROJECT
+ *                  RULE: per record -- a record, kept or filtered, is left out if and only if it overlaps the previous chunk's region on the same contig
+ *                  (is_ovlp_with_prev_region on [pos0 + 1, bam_endpos]); identical for sorted inputs, no prefix assumption.  The merged output is therefore NOT
+ *                  coordinate-sorted (the reference says several inputs "will be merged" and no more).
+ *   5 sort_output  additive: within each chunk the records to be written are ordered by (pos0, file index, position in the file), stable, before the tag rewrite -- a
+ *                  host sort of the job table.  A chunk only writes records that do not overlap its predecessor, so the file is non-decreasing in (refid, pos) and the
+ *                  output's .bai can be written.  Without it interleaved inputs make the index builder give up with LCD_ERR_BAI_ORDER: the BAM is completed, no index
+ *                  is left, out_bai_skipped says so (lcd_bam_writer_open_indexed's rule, unchanged).
+ * lcd_chunk_open_from_bams: lcd_chunk_open_from_bam over n_bams files (1 ... LCD_MAX_INPUTS; bai_paths NULL, or an entry NULL: <bam>.bai); n_bams = 1 is
+ * lcd_chunk_open_from_bam.  meta->tid / n_targets / target_len are file 0's.  lcd_chunk_n_files; lcd_chunk_read_files: per kept read its file index (returns n_reads).
+ * lcd_merged_record_plan (pure host code): rules 4 and 5 on a record table in file-major order -- skip[i] = 1 for a record left out; order[0 .. m) = the records to
+ * write in output order, order[m .. n_rec) = -1; returns m.  rec_file NULL: one file.  has_prev 0: nothing is left out.  -4 for n_rec < 0 or a NULL table.
+ * lcd_chunk_tag_records_sel: lcd_chunk_tag_records for the records with skip[i] == 0 (skip NULL: all), in the order `order` names them (as the plan gives it; NULL:
+ * table order); an order that does not name every such record exactly once is -4.
+ * lcd_bam_writer_set_sort: the writer's appends use the plan with sort_output (default 0).  With one sorted input and 0 an append writes the bytes it always wrote.
+ * lcd_call_files: lcd_call_file_indexed over in->n files (idx / idx_stats may be NULL).  job->bam_path / bai_path must be NULL or equal entry 0 (-4).  Every file's
+ * .bai is looked for (in->bai_paths NULL, or an entry NULL: <bam>.bai) and, with build_missing_bai, built at its own path; existing ones are never touched; a
+ * missing one without the option is -30 with that path.  n_reads_per_file (in->n entries, or NULL): the kept reads each file contributed, summed over the chunks.
+ * With in->n == 1 the run is lcd_call_file_indexed.  NULL in, n < 1, n > LCD_MAX_INPUTS or a NULL path: -4. */
+#define LCD_ERR_INPUT_HEADERS (-54)
+#define LCD_MAX_INPUTS 64
+typedef struct lcd_inputs_t { int n; const char *const *bam_paths; const char *const *bai_paths; int sort_output; } lcd_inputs_t;
+lcd_chunk_t *lcd_chunk_open_from_bams(const lcd_digar_opt_t *opt, int n_bams, const char *const *bam_paths, const char *const *bai_paths /* NULL or entries NULL: <bam>.bai */,
+                                      const char *chrom, int64_t reg_beg, int64_t reg_end, int min_mapq, int verify_crc, struct lcd_bam_reads_t *meta);
+int lcd_chunk_n_files(const lcd_chunk_t *chunk);
+int lcd_chunk_read_files(const lcd_chunk_t *chunk, int *file_of_read);
+int lcd_merged_record_plan(int n_rec, const int *rec_file, const int64_t *rec_pos0, const int64_t *rec_endpos, int has_prev, int64_t prev_beg, int64_t prev_end,
+                           int sort_output, uint8_t *skip, int *order);
+lcd_tagged_t *lcd_chunk_tag_records_sel(const lcd_chunk_t *chunk, const int *haps, const int64_t *phase_sets, const uint8_t *skip, const int *order);
+int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output);
+int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
+                   lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file /* n entries or NULL */);
 
 #ifdef __cplusplus
 }

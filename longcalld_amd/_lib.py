@@ -239,7 +239,13 @@ class LcdIndexStats(C.Structure):
         (n, C.c_int64) for n in ("out_bai_bytes", "out_n_indexed", "out_n_no_coor")] + [(n, C.c_double) for n in ("ms_build_bai", "ms_build_fai", "ms_out_bai")]
 
 
-LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG = -50, -51, -52, -53
+class LcdInputs(C.Structure):
+    """lcd_inputs_t: the alignment files of one sample (lcd_call_files)"""
+    _fields_ = [("n", C.c_int), ("bam_paths", C.POINTER(C.c_char_p)), ("bai_paths", C.POINTER(C.c_char_p)), ("sort_output", C.c_int)]
+
+
+LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG, LCD_ERR_INPUT_HEADERS = -50, -51, -52, -53, -54
+LCD_MAX_INPUTS = 64
 LCD_CTG_AUTOSOME_XY, LCD_CTG_AUTOSOME, LCD_CTG_ALL = 0, 1, 2
 
 _lib = None
@@ -265,6 +271,7 @@ EXPORTS = [
     "lcd_vcf_writer_open", "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_call_file", "lcd_file_stats_free",
     "lcd_bai_from_records", "lcd_bai_builder_create", "lcd_bai_builder_add_stream", "lcd_bai_builder_finish", "lcd_bai_builder_bytes", "lcd_bai_builder_destroy", "lcd_bai_build",
     "lcd_fai_build", "lcd_bam_writer_open_indexed", "lcd_call_file_indexed",
+    "lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_bam_writer_set_sort", "lcd_call_files",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -441,6 +448,15 @@ def load_library():
     lib.lcd_bai_build.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(LcdBaiOpt), C.POINTER(LcdBaiStats)]
     lib.lcd_fai_build.argtypes = [C.c_char_p, C.c_char_p]
     lib.lcd_file_stats_free.restype = None
+    lib.lcd_chunk_open_from_bams.restype = C.c_void_p
+    lib.lcd_chunk_open_from_bams.argtypes = [C.POINTER(LcdDigarOpt), C.c_int, strv, strv, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(LcdBamReads)]
+    lib.lcd_chunk_n_files.argtypes = [C.c_void_p]
+    lib.lcd_chunk_read_files.argtypes = [C.c_void_p, i32p]
+    lib.lcd_merged_record_plan.argtypes = [C.c_int, i32p, i64p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int, u8p, i32p]
+    lib.lcd_chunk_tag_records_sel.restype = C.c_void_p
+    lib.lcd_chunk_tag_records_sel.argtypes = [C.c_void_p, i32p, i64p, u8p, i32p]
+    lib.lcd_bam_writer_set_sort.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_call_files.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats), i64p]
     lib.lcd_call_free.restype = None
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]

@@ -568,6 +568,57 @@ class DeviceChunk:
         self.packed_bytes = 0
         return self
 
+    @classmethod
+    def open_from_bams(cls, bam_paths, bai_paths, chrom, reg_beg, reg_end, min_mapq=30, is_ont=0, verify_crc=1):
+        """lcd_chunk_open_from_bams: open_from_bam over the files of one sample -- their region images appended, one inflate, the reads file-major.  bai_paths None, or
+        an entry None: <bam>.bai.  .n_files and .file_of_read (per kept read its file index) are filled beside .meta"""
+        from ._lib import LcdBamReads
+        self = cls.__new__(cls)
+        self.lib = lib = load_library()
+        opt = LcdDigarOpt(); lib.lcd_digar_opt_default(C.byref(opt), int(is_ont))
+        m = LcdBamReads()
+        bams, n = _str_array(bam_paths)
+        bais = None
+        if bai_paths is not None:
+            assert len(bai_paths) == n
+            bais = (C.c_char_p * max(1, n))(*[_enc(x) if x is not None else None for x in bai_paths])
+        self.h = lib.lcd_chunk_open_from_bams(C.byref(opt), n, bams, bais, _enc(chrom), int(reg_beg), int(reg_end), int(min_mapq), int(verify_crc), C.byref(m))
+        if not self.h:
+            raise LcdError("lcd_chunk_open_from_bams failed: " + lib.lcd_last_error().decode())
+        n = self.n = m.n_reads
+        arr = lambda p, dt: np.array([p[i] for i in range(n)], dt)
+        self.meta = dict(tid=m.tid, n_targets=m.n_targets, target_len=m.target_len, pos0=arr(m.pos0, np.int64), end_pos=arr(m.end_pos, np.int64), mapq=arr(m.mapq, np.int32),
+                         flag=arr(m.flag, np.int32), n_cigar=arr(m.n_cigar, np.int32), qlen=arr(m.qlen, np.int32),
+                         names=[C.string_at(C.addressof(m.name_pool.contents) + m.name_off[i]).decode() for i in range(n)])
+        lib.lcd_bam_reads_free.argtypes = [C.POINTER(LcdBamReads)]
+        lib.lcd_bam_reads_free(C.byref(m))
+        self.packed_bytes = 0
+        self.n_files = int(lib.lcd_chunk_n_files(self.h))
+        fr = np.zeros(max(n, 1), np.int32)
+        check(lib.lcd_chunk_read_files(self.h, fr.ctypes.data_as(i32p)), lib)
+        self.file_of_read = fr[:n]
+        return self
+
+    def tag_records_sel(self, haps, phase_sets, skip=None, order=None):
+        """lcd_chunk_tag_records_sel: tag_records for the records with skip[i] == 0, in the order `order` names them (merged_record_plan's outputs) -> (bytes, number)"""
+        lib = self.lib
+        hp = np.concatenate([np.ascontiguousarray(haps, np.int32), np.zeros(1, np.int32)]); ps = np.concatenate([np.ascontiguousarray(phase_sets, np.int64), np.zeros(1, np.int64)])
+        if len(hp) <= self.n or len(ps) <= self.n:
+            raise ValueError("tag_records_sel: haps / phase_sets shorter than the chunk's reads")
+        sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
+        od = np.ascontiguousarray(order, np.int32) if order is not None else None
+        h = lib.lcd_chunk_tag_records_sel(self.h, hp.ctypes.data_as(i32p), ps.ctypes.data_as(C.POINTER(C.c_int64)), _p8(sk) if sk is not None else None,
+                                          od.ctypes.data_as(i32p) if od is not None else None)
+        if not h:
+            raise LcdError("lcd_chunk_tag_records_sel failed: " + lib.lcd_last_error().decode())
+        try:
+            n = lib.lcd_tagged_size(h)
+            buf = C.create_string_buffer(max(n, 1))
+            check(lib.lcd_tagged_to_host(h, 0, n, buf), lib)
+            return buf.raw[:n], int(lib.lcd_tagged_n_records(h))
+        finally:
+            lib.lcd_tagged_free(h)
+
     def resolve(self, src=None):
         """lcd_chunk_resolve: the second phase -- src = (ref, ref_beg, ref_end, is_ont) as for from_bam, or None; a second call raises (-4)"""
         from ._lib import LcdChunkSrc
@@ -1594,9 +1645,36 @@ def vcf_write(path, texts, bgzf=0, header_text=None):
     check(lib.lcd_vcf_writer_close(w), lib)
 
 
+def chunk_open_from_bams(bam_paths, bai_paths, chrom, reg_beg, reg_end, min_mapq=30, is_ont=0, verify_crc=1):
+    """lcd_chunk_open_from_bams -> DeviceChunk (DeviceChunk.open_from_bams)"""
+    return DeviceChunk.open_from_bams(bam_paths, bai_paths, chrom, reg_beg, reg_end, min_mapq, is_ont, verify_crc)
+
+
+def merged_record_plan(rec_file, rec_pos0, rec_endpos, has_prev=0, prev_beg=0, prev_end=0, sort_output=0):
+    """lcd_merged_record_plan (pure host code): a chunk's record table in file-major order -> (skip mask, the records to write in output order).  rec_file None: one file"""
+    lib = load_library()
+    p0 = np.ascontiguousarray(rec_pos0, np.int64); e0 = np.ascontiguousarray(rec_endpos, np.int64)
+    n = len(p0)
+    assert len(e0) == n and (rec_file is None or len(rec_file) == n)
+    rf = np.ascontiguousarray(rec_file, np.int32) if rec_file is not None else None
+    skip = np.zeros(n + 1, np.uint8); order = np.zeros(n + 1, np.int32)
+    i64p = C.POINTER(C.c_int64)
+    m = check(lib.lcd_merged_record_plan(n, rf.ctypes.data_as(i32p) if rf is not None else None, p0.ctypes.data_as(i64p), e0.ctypes.data_as(i64p), int(has_prev), int(prev_beg),
+                                         int(prev_end), int(sort_output), _p8(skip), order.ctypes.data_as(i32p)), lib)
+    assert (order[m:n] == -1).all()
+    return skip[:n].astype(bool), order[:m].copy()
+
+
+def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw):
+    """lcd_call_files: the alignment files of ONE sample (one BAM per SMRT cell / flow cell) + a FASTA -> one VCF and, with bam_out, one phased BAM holding every
+    input's records (coordinate-sorted, and indexable, with sort_output).  bais None, or an entry None: <bam>.bai; every other keyword is call_file's.  The result has
+    "n_reads_per_file" beside call_file's entries"""
+    return call_file(list(bams), fasta_path, index=index, _inputs=dict(bais=bais, sort_output=sort_output), **kw)
+
+
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None):
+              keep_records=False, index=None, _inputs=None):
     """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
     phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
     flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -1607,7 +1685,19 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     cfg = cfg if cfg is not None else call_cfg()
     job = LcdFileJob(); lib.lcd_file_job_default(C.byref(job))
     opt_s = lambda x: _enc(x) if x is not None else None
-    job.bam_path, job.bai_path, job.fasta_path = _enc(bam_path), opt_s(bai_path), _enc(fasta_path)
+    if _inputs is None:
+        job.bam_path, job.bai_path, job.fasta_path = _enc(bam_path), opt_s(bai_path), _enc(fasta_path)
+    else:      # call_files: bam_path is the list of inputs
+        from ._lib import LcdInputs
+        job.fasta_path = _enc(fasta_path)
+        inp = LcdInputs()
+        in_bams, inp.n = _str_array(bam_path); inp.bam_paths = in_bams
+        in_bais = None
+        if _inputs["bais"] is not None:
+            assert len(_inputs["bais"]) == inp.n
+            in_bais = (C.c_char_p * max(1, inp.n))(*[opt_s(x) for x in _inputs["bais"]]); inp.bai_paths = in_bais
+        inp.sort_output = int(bool(_inputs["sort_output"]))
+        per_file = (C.c_int64 * max(1, inp.n))()
     exc, job.n_exclude = _str_array(exclude); job.exclude = exc
     regs, job.n_regions = _str_array(regions); job.regions = regs
     job.contig_mode, job.region_bed_path, job.chunk_len = int(contig_mode), opt_s(region_bed_path), int(chunk_len)
@@ -1620,17 +1710,22 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
         bo = LcdBamOut(); bo.path = _enc(bam_out["path"]); bo.pg_line = opt_s(bam_out.get("pg_line")); bo.block_payload = int(bam_out.get("block_payload", 0))
         job.bam_out = C.pointer(bo)
     st = LcdFileStats()
-    ist = None
+    ist, io = None, None
     if index:
         d = dict(build_missing_bai=1, build_missing_fai=1, write_out_bai=1 if bam_out is not None else 0) if index is True else dict(index)
         io = LcdIndexOpt(int(d.get("build_missing_bai", 0)), int(d.get("build_missing_fai", 0)), int(d.get("write_out_bai", 0)), opt_s(d.get("out_bai_path")), int(d.get("slab_members", 0)))
         ist = LcdIndexStats()
+    if _inputs is not None:
+        rc = lib.lcd_call_files(C.byref(inp), C.byref(job), C.byref(cfg), C.byref(io) if io is not None else None, C.byref(st), C.byref(ist) if ist is not None else None, per_file)
+    elif index:
         rc = lib.lcd_call_file_indexed(C.byref(job), C.byref(cfg), C.byref(io), C.byref(st), C.byref(ist))
     else:
         rc = lib.lcd_call_file(C.byref(job), C.byref(cfg), C.byref(st))
     try:
         check(rc, lib)
         res = {k: getattr(st, k) for k, _t in LcdFileStats._fields_[:14]}
+        if _inputs is not None:
+            res["n_reads_per_file"] = [int(per_file[f]) for f in range(inp.n)]
         if ist is not None:
             res["index"] = {k: (getattr(ist, k).decode() if k == "out_bai_skip_reason" else getattr(ist, k)) for k, _t in LcdIndexStats._fields_}
         if keep_records:

@@ -1,32 +1,35 @@
 """python -m longcalld_amd.cli call ref.fa in.bam [region ...] -- the reference's command line (src/call_var_main.c:812-1000) for what the library supports: a thin
-argument parser over lcd_call_file.  What is not supported is refused with one line and exit status 2."""
+argument parser over lcd_call_file / lcd_call_files.  What is not supported is refused with one line and exit status 2."""
 import sys
 
 VERSION_FALLBACK = "longcalld_amd"
 REFUSED = {
     "-s": "somatic / mosaic calling is not supported", "--mosaic": "somatic / mosaic calling is not supported", "--somatic": "somatic / mosaic calling is not supported",
-    "--refine-aln": "--refine-aln is not supported", "-L": "a list of input files (-L) is not supported: one BAM per run", "--input-is-list": "a list of input files (-L) is not supported: one BAM per run",
-    "-X": "extra input files (-X) are not supported: one BAM per run", "--extra-bam": "extra input files (-X) are not supported: one BAM per run",
+    "--refine-aln": "--refine-aln is not supported", "-L": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE", "--input-is-list": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE",
+    "-X": "-X/--extra-bam is not supported: give further input files with --add-bam FILE", "--extra-bam": "-X/--extra-bam is not supported: give further input files with --add-bam FILE",
     "-T": "a transposable-element library (-T) is not supported", "--trans-elem": "a transposable-element library (-T) is not supported",
     "-S": "SAM output (-S) is not supported: use -b", "--out-sam": "SAM output (-S) is not supported: use -b", "--out-cram": "CRAM output (-C FILE) is not supported: use -b",
     "--out-var-rnames": "--out-var-rnames is not supported", "--out-som-var-rnames": "--out-som-var-rnames is not supported", "--out-sv-rnames": "--out-sv-rnames is not supported",
 }
-FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
-          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len"}
+          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli faidx ref.fa               build ref.fa.fai
-  ref.fa needs ref.fa.fai, in.bam needs in.bam.bai; a missing one is an error unless --make-index is given
+  ref.fa needs ref.fa.fai, every input BAM needs its .bai; a missing one is an error unless --make-index is given
+Inputs:   one sample from several BAMs (one per SMRT cell / flow cell, same reference table): --add-bam FILE (repeatable)   --bam-list FILE (one path per line)
+          order: in.bam, the list's lines, the --add-bam files; the output BAM holds every input's records, file by file per chunk; --sort-merged orders them by
+          position (and lets --make-index write <out.bam>.bai)
 Input:    --hifi (default) | --ont   --region-file FILE   --autosome-XY (default) | --autosome | --all-ctg   -E/--exclude-ctg STR (repeatable)   -r/--ref-idx FILE
 Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z   -l/--min-sv-len INT   -H/--no-vcf-header   --amb-base   -b/--out-bam FILE
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
-Index:    --make-index   build a missing in.bam.bai / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched)
+Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
-Not supported (refused with exit status 2): -s, --refine-aln, -L, -X, -T, -S, -C FILE, --out-*-rnames
+Not supported (refused with exit status 2): -s, --refine-aln, -L (use --bam-list), -X (use --add-bam), -T, -S, -C FILE, --out-*-rnames
 """
 
 
@@ -37,7 +40,7 @@ def refuse(msg):
 
 def parse(argv):
     """-> (dict of options, positional arguments) or an int exit status"""
-    o = dict(flags=set(), exclude=[])
+    o = dict(flags=set(), exclude=[], add_bam=[])
     pos, i = [], 0
     while i < len(argv):
         a = argv[i]; i += 1
@@ -59,8 +62,8 @@ def parse(argv):
                 val = argv[i]; i += 1
             if VALUED[key] == "max_cov" and not val.lstrip("+").isdigit():
                 return refuse(REFUSED["--out-cram"])
-            if VALUED[key] == "exclude":
-                o["exclude"].append(val)
+            if VALUED[key] in ("exclude", "add_bam"):
+                o[VALUED[key]].append(val)
             else:
                 o[VALUED[key]] = val
             continue
@@ -68,6 +71,16 @@ def parse(argv):
             return refuse(f"unknown option {a}")
         pos.append(a)
     return o, pos
+
+
+def input_bams(o, bam):
+    """the input files in order: the positional BAM, the lines of --bam-list (blank lines skipped; the reference likewise puts list entries before -X files), the
+    --add-bam files"""
+    bams = [bam]
+    if "bam_list" in o:
+        with open(o["bam_list"]) as f:
+            bams += [ln.strip() for ln in f if ln.strip()]
+    return bams + list(o["add_bam"])
 
 
 def parse_index(argv):
@@ -149,7 +162,14 @@ def main(argv=None):
     cmdline = "longcalld_amd call " + " ".join(argv[1:])
     bam_out = dict(path=o["out_bam"], pg_line="@PG\tID:longcalld_amd\tPN:longcalld_amd\tCL:" + cmdline) if "out_bam" in o else None
     try:
-        st = align.call_file(bam, fasta, contig_mode=mode, exclude=o["exclude"], regions=regions, region_bed_path=o.get("region_file"), chunk_len=num.get("chunk_len", 0),
+        bams = input_bams(o, bam)
+    except OSError as e:
+        return refuse(f"--bam-list: {e}")
+    if len(bams) > 64:
+        return refuse("more than 64 input files")
+    run = align.call_file if len(bams) == 1 else (lambda _b, fa, **kw: align.call_files(bams, fa, sort_output="--sort-merged" in o["flags"], **kw))
+    try:
+        st = run(bam, fasta, contig_mode=mode, exclude=o["exclude"], regions=regions, region_bed_path=o.get("region_file"), chunk_len=num.get("chunk_len", 0),
                              window_chunks=num.get("window_chunks", 0), overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0),
                              min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
@@ -161,7 +181,8 @@ def main(argv=None):
         sys.stderr.write("longcalld_amd call: the output BAM was written without an index: " + st["index"]["out_bai_skip_reason"] + "\n")
     if st["plan_fallback"]:
         sys.stderr.write("longcalld_amd call: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
-    sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads, {st['n_vcf_lines']} VCF lines, "
+    per_file = f" ({' + '.join(str(x) for x in st['n_reads_per_file'])} from the {len(bams)} input files)" if len(bams) > 1 else ""
+    sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads{per_file}, {st['n_vcf_lines']} VCF lines, "
                      f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 

@@ -110,21 +110,37 @@ int lcd_deflated_to_host(const lcd_deflated_t *h, size_t off, size_t n, uint8_t 
 }
 void lcd_deflated_free(lcd_deflated_t *h) { delete h; }
 
+// ---- which records of a chunk's table are written, and in which order (rules 4 and 5 of the merged alignment output; pure host code) ----
+int lcd_merged_record_plan(int n_rec, const int *rec_file, const int64_t *rec_pos0, const int64_t *rec_endpos, int has_prev, int64_t prev_beg, int64_t prev_end,
+                           int sort_output, uint8_t *skip, int *order) {
+    const std::string W = "lcd_merged_record_plan";
+    if (n_rec < 0 || (n_rec > 0 && (!rec_pos0 || !rec_endpos || !skip || !order))) return set_err(-4, W + ": n_rec < 0 or NULL argument");
+    int m = 0;
+    for (int i = 0; i < n_rec; ++i) {
+        skip[i] = has_prev && !(rec_endpos[i] < prev_beg || rec_pos0[i] + 1 > prev_end);     // is_ovlp_with_prev_region on [pos0 + 1, bam_endpos]
+        if (!skip[i]) order[m++] = i;
+    }
+    if (sort_output)
+        std::stable_sort(order, order + m, [&](const int a, const int b) {
+            if (rec_pos0[a] != rec_pos0[b]) return rec_pos0[a] < rec_pos0[b];
+            const int fa = rec_file ? rec_file[a] : 0, fb = rec_file ? rec_file[b] : 0;
+            return fa != fb ? fa < fb : a < b;                                                 // (the table index is the position in the file)
+        });
+    for (int i = m; i < n_rec; ++i) order[i] = -1;
+    return m;
+}
+
 // ---- HP / PS rewrite of a chunk's records ----
-lcd_tagged_t *lcd_chunk_tag_records(const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, int n_skip_kept, int n_skip_filtered) {
-    const std::string W = "lcd_chunk_tag_records";
-    if (!c || !c->from_bam) { set_err(-4, W + ": the chunk was not made from a BAM"); return nullptr; }
-    if (c->n_reads > 0 && (!haps || !phase_sets)) { set_err(-4, W + ": NULL haps / phase_sets"); return nullptr; }
-    if (n_skip_kept < 0 || n_skip_filtered < 0) { set_err(-4, W + ": negative skip count"); return nullptr; }
+namespace {
+// the records `pick` names (indices of the chunk's record table), rewritten in that order
+lcd_tagged_t *tag_records_core(const std::string &W, const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, const std::vector<int> &pick) {
     if (use_device(c->device)) return nullptr;
     std::unique_ptr<lcd_tagged_s> h(new lcd_tagged_s());
     h->device = c->device;
     const uint64_t base = c->stream ? lcd_inflated_dev_ptr(c->stream) : 0, usize = c->stream ? lcd_inflated_size(c->stream) : 0;
     std::vector<BamTagJob> jobs;
-    int sk = n_skip_kept, sf = n_skip_filtered;
-    for (size_t i = 0; i < c->rec_beg.size(); ++i) {
+    for (const int i : pick) {
         const int r = c->rec_read[i];
-        if (r >= 0 ? sk > 0 : sf > 0) { --(r >= 0 ? sk : sf); continue; }
         if (c->rec_stop[i] > usize || c->rec_beg[i] + 36 > c->rec_stop[i] || r >= c->n_reads) { set_err(-4, W + ": record outside the stream"); return nullptr; }
         BamTagJob j; j.src = base + c->rec_beg[i]; j.len = (uint32_t)(c->rec_stop[i] - c->rec_beg[i]); j.kept = r >= 0; j.hap = r >= 0 ? haps[r] : 0; j.pad = 0; j.ps = r >= 0 ? phase_sets[r] : 0;
         jobs.push_back(j);
@@ -157,6 +173,38 @@ lcd_tagged_t *lcd_chunk_tag_records(const lcd_chunk_t *c, const int *haps, const
     TCHK(hipStreamSynchronize(st));
 #undef TCHK
     return h.release();
+}
+} // namespace
+
+lcd_tagged_t *lcd_chunk_tag_records(const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, int n_skip_kept, int n_skip_filtered) {
+    const std::string W = "lcd_chunk_tag_records";
+    if (!c || !c->from_bam) { set_err(-4, W + ": the chunk was not made from a BAM"); return nullptr; }
+    if (c->n_reads > 0 && (!haps || !phase_sets)) { set_err(-4, W + ": NULL haps / phase_sets"); return nullptr; }
+    if (n_skip_kept < 0 || n_skip_filtered < 0) { set_err(-4, W + ": negative skip count"); return nullptr; }
+    std::vector<int> pick;
+    int sk = n_skip_kept, sf = n_skip_filtered;
+    for (size_t i = 0; i < c->rec_beg.size(); ++i) {
+        const int r = c->rec_read[i];
+        if (r >= 0 ? sk > 0 : sf > 0) { --(r >= 0 ? sk : sf); continue; }
+        pick.push_back((int)i);
+    }
+    return tag_records_core(W, c, haps, phase_sets, pick);
+}
+lcd_tagged_t *lcd_chunk_tag_records_sel(const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, const uint8_t *skip, const int *order) {
+    const std::string W = "lcd_chunk_tag_records_sel";
+    if (!c || !c->from_bam) { set_err(-4, W + ": the chunk was not made from a BAM"); return nullptr; }
+    if (c->n_reads > 0 && (!haps || !phase_sets)) { set_err(-4, W + ": NULL haps / phase_sets"); return nullptr; }
+    const int n_rec = (int)c->rec_beg.size();
+    int m = 0;
+    for (int i = 0; i < n_rec; ++i) if (!skip || !skip[i]) ++m;
+    std::vector<int> pick(m); std::vector<uint8_t> seen(n_rec + 1, 0);
+    for (int k = 0, i = 0; k < m; ++k) {
+        if (order) i = order[k]; else { while (skip && skip[i]) ++i; }
+        if (i < 0 || i >= n_rec || (skip && skip[i]) || seen[i]) { set_err(-4, W + ": `order` must name every record that is not skipped exactly once"); return nullptr; }
+        seen[i] = 1; pick[k] = i;
+        if (!order) ++i;
+    }
+    return tag_records_core(W, c, haps, phase_sets, pick);
 }
 uint64_t lcd_tagged_dev_ptr(const lcd_tagged_t *h) { return h ? h->out.addr() : 0; }
 size_t lcd_tagged_size(const lcd_tagged_t *h) { return h ? h->size : 0; }

@@ -144,6 +144,7 @@ struct lcd_bam_writer_s {
     FILE *f = nullptr; lcd_bam_out_t *out = nullptr; std::string path; std::vector<uint8_t> buf;
     // lcd_bam_writer_open_indexed: the builder of the output's .bai (NULL: none, or given up), where the index goes, the file offset of the next member
     lcd_bai_builder_t *bai = nullptr; std::string index_path; lcd_index_stats_t *ist = nullptr; uint64_t file_off = 0;
+    int sort_output = 0;     // lcd_bam_writer_set_sort
 };
 namespace {
 // download + fwrite of one compressed image, then free
@@ -227,20 +228,21 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
     lcd_bam_out_t *out = w->out;
     for (int c = 0; c < n; ++c) {
         const lcd_first_chunk_t &x = chunks[c].first; const lcd_chunk_s *k = x.chunk;
-        int nsk = 0, nsf = 0;
         bool has_prev = c > 0 && (!tids || tids[c - 1] == tids[c]);
         int64_t pb = has_prev ? chunks[c - 1].first.reg_beg : 0, pe = has_prev ? chunks[c - 1].first.reg_end : 0;
         if (c == 0 && prev && prev->valid && (!tids || prev->tid == tids[0])) { has_prev = true; pb = prev->reg_beg; pe = prev->reg_end; }
-        if (has_prev)
-            for (size_t i = 0; i < k->rec_beg.size(); ++i)
-                if (!(k->rec_endpos[i] < pb || k->rec_pos0[i] + 1 > pe)) ++(k->rec_read[i] >= 0 ? nsk : nsf);
+        // the plan of the merged output: a record is left out iff it overlaps the region before (per record, whatever file it came from); the rest in table
+        // (file-major) order, or sorted by position
+        const int n_rec = (int)k->rec_beg.size();
+        std::vector<uint8_t> skip((size_t)n_rec + 1); std::vector<int> order((size_t)n_rec + 1);
+        const int n_out = lcd_merged_record_plan(n_rec, k->rec_file.data(), k->rec_pos0.data(), k->rec_endpos.data(), has_prev, pb, pe, w->sort_output, skip.data(), order.data());
+        if (n_out < 0) return n_out;
         const double t0 = now_ms();
-        lcd_tagged_t *t = lcd_chunk_tag_records(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, nsk, nsf);
+        lcd_tagged_t *t = lcd_chunk_tag_records_sel(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, skip.data(), order.data());
         if (!t) return -30;
         out->ms_tag += now_ms() - t0;
-        int kept = 0, filt = 0;
-        for (int r : k->rec_read) ++(r >= 0 ? kept : filt);
-        out->n_records_out += kept - nsk; out->n_filtered_out += filt - nsf; out->bytes_inflated += (int64_t)lcd_tagged_size(t);
+        for (int i = 0; i < n_rec; ++i) if (!skip[i]) ++(k->rec_read[i] >= 0 ? out->n_records_out : out->n_filtered_out);
+        out->bytes_inflated += (int64_t)lcd_tagged_size(t);
         lcd_deflated_t *d = lcd_tagged_size(t) ? lcd_bgzf_deflate_dev_ptr(lcd_tagged_dev_ptr(t), lcd_tagged_size(t), out->block_payload, 0) : nullptr;
         int rc = 0;
         if (lcd_tagged_size(t) && d && w->bai) rc = writer_index_stream(w, t, d);
@@ -249,6 +251,11 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
         lcd_tagged_free(t);
         if (rc) return rc;
     }
+    return 0;
+}
+int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output) {
+    if (!w) return set_err(-4, "lcd_bam_writer_set_sort: NULL writer");
+    w->sort_output = sort_output != 0;
     return 0;
 }
 void lcd_bam_writer_abort(lcd_bam_writer_t *w) {

@@ -2,6 +2,8 @@
 // the BAM header's contigs and sample name, the VCF writer, and the driver that runs call_var_worker_pipeline (:762-815) for the germline path over windows of
 // chunks: load (lcd_chunk_open_from_bam / lcd_fasta_fetch / lcd_chunk_resolve), call (chunks_call_core with the stitch carried across windows), write (the VCF and
 // the appendable BAM writer).  Everything here composes exports that exist; no kernel is launched from this file.
+// lcd_call_files runs the same driver over the alignment files of one sample (-X / -L, src/call_var_main.c:361-400, 640-741): every chunk is opened from all files at once
+// (lcd_chunk_open_from_bams), file 0 gives the contigs, the headers and the sample name, every further file must carry its reference table (LCD_ERR_INPUT_HEADERS).
 #include <condition_variable>
 #include <ctime>
 #include "lcd_host_internal.h"
@@ -289,7 +291,9 @@ struct Tokens {
 
 struct Run {
     const lcd_file_job_t *job; const lcd_cfg_t *cfg; lcd_file_stats_t *st;
-    std::string bai; int is_ont = 0, device = 0, loader_threads = 1;
+    std::vector<std::string> bams, bais; std::vector<const char *> bam_p, bai_p;     // the input files of the one sample, in input order
+    std::vector<int64_t> reads_per_file;
+    int is_ont = 0, device = 0, loader_threads = 1;
     std::vector<std::string> names; std::vector<int64_t> lens;
     lcd_chunk_plan_t plan;
     lcd_stitch_carry_t carry;
@@ -315,7 +319,7 @@ struct Run {
                 const int e = plan.tid[w.first + (int)c]; const int64_t rb = plan.reg_beg[w.first + (int)c], re = plan.reg_end[w.first + (int)c];
                 const char *chrom = names[e].c_str();
                 auto bad = [&](int code, const std::string &m) { rc[c] = code ? code : -1; msg[c] = m; stop = true; };
-                w.handles[c] = lcd_chunk_open_from_bam(&dopt, job->bam_path, bai.c_str(), chrom, rb, re, job->min_mapq, 1, &w.metas[c]);
+                w.handles[c] = lcd_chunk_open_from_bams(&dopt, (int)bam_p.size(), bam_p.data(), bai_p.data(), chrom, rb, re, job->min_mapq, 1, &w.metas[c]);
                 if (!w.handles[c]) { bad(-30, g_err); continue; }
                 int64_t lo1 = rb, hi1 = re;
                 for (int r = 0; r < w.metas[c].n_reads; ++r) { lo1 = std::min(lo1, w.metas[c].pos0[r] + 1); hi1 = std::max(hi1, w.metas[c].end_pos[r]); }
@@ -338,7 +342,11 @@ struct Run {
         {
             std::lock_guard<std::mutex> lk(err_mu);     // (the counters are written by one stage each; the lock only orders them with the final read)
             st->n_region_loads += w.n; st->n_windows += 1;
-            for (int c = 0; c < w.n; ++c) { if (w.handles[c]->n_reads > 0) ++st->n_loaded; else ++st->n_empty; st->n_reads += w.handles[c]->n_reads; }
+            for (int c = 0; c < w.n; ++c) {
+                if (w.handles[c]->n_reads > 0) ++st->n_loaded; else ++st->n_empty;
+                st->n_reads += w.handles[c]->n_reads;
+                for (const int f : w.handles[c]->read_file) ++reads_per_file[f];
+            }
             st->ms_load += now_ms() - t0;
         }
         return 0;
@@ -383,38 +391,54 @@ struct Run {
 };
 } // namespace
 
-extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats) { return lcd_call_file_indexed(job, cfg, nullptr, stats, nullptr); }
-
-extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats) {
-    const std::string W = idx ? "lcd_call_file_indexed" : "lcd_call_file";
+namespace {
+// the whole-file run over the n input files of one sample; in == NULL: the one file of the job (lcd_call_file / lcd_call_file_indexed)
+int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
+                    lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file) {
     if (stats) memset(stats, 0, sizeof(*stats));
     lcd_index_stats_t ist_local;
     lcd_index_stats_t *ist = idx_stats ? idx_stats : &ist_local;
     memset(ist, 0, sizeof(*ist));
     if (idx && idx->write_out_bai && (!job || !job->bam_out)) return set_err(-4, W + ": write_out_bai needs bam_out");
     if (idx && idx->slab_members < 0) return set_err(-4, W + ": negative slab_members");
-    if (!job || !cfg || !stats || !job->bam_path || !job->fasta_path) return set_err(-4, W + ": NULL argument");
+    if (!job || !cfg || !stats || (!in && !job->bam_path) || !job->fasta_path) return set_err(-4, W + ": NULL argument");
+    if (in) {
+        if (in->n < 1 || in->n > LCD_MAX_INPUTS || !in->bam_paths) return set_err(-4, W + ": the number of inputs must be 1 ... LCD_MAX_INPUTS, with their paths");
+        for (int f = 0; f < in->n; ++f) if (!in->bam_paths[f]) return set_err(-4, W + ": NULL input path");
+        if (job->bam_path && strcmp(job->bam_path, in->bam_paths[0]) != 0) return set_err(-4, W + ": job->bam_path must be NULL or the first input");
+        if (job->bai_path && in->bai_paths && in->bai_paths[0] && strcmp(job->bai_path, in->bai_paths[0]) != 0) return set_err(-4, W + ": job->bai_path must be NULL or the first input's index");
+    }
     if (job->bam_out && !job->bam_out->path) return set_err(-4, W + ": bam_out without a path");
     if (job->window_chunks < 0 || job->loader_threads < 0 || job->chunk_len < 0 || job->overlap < -1 || job->overlap > 1) return set_err(-4, W + ": negative window_chunks / loader_threads / chunk_len, or overlap outside -1 ... 1");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
     const double t_wall = now_ms();
     Run R; R.job = job; R.cfg = cfg; R.st = stats;
     memset(&R.plan, 0, sizeof(R.plan)); memset(&R.carry, 0, sizeof(R.carry));
-    R.bai = job->bai_path ? std::string(job->bai_path) : std::string(job->bam_path) + ".bai";
+    const int n_in = in ? in->n : 1;
+    for (int f = 0; f < n_in; ++f) {
+        R.bams.push_back(in ? in->bam_paths[f] : job->bam_path);
+        const char *b = in && in->bai_paths && in->bai_paths[f] ? in->bai_paths[f] : f == 0 ? job->bai_path : nullptr;
+        R.bais.push_back(b ? std::string(b) : R.bams[f] + ".bai");
+    }
+    for (int f = 0; f < n_in; ++f) { R.bam_p.push_back(R.bams[f].c_str()); R.bai_p.push_back(R.bais[f].c_str()); }
+    R.reads_per_file.assign(n_in, 0);
+    if (n_reads_per_file) for (int f = 0; f < n_in; ++f) n_reads_per_file[f] = 0;
+    const char *bam0 = R.bam_p[0];
     R.is_ont = cfg->clean.is_ont != 0;
     // an index that exists is read as it is; a missing one is built only when the caller asks for it (lcd_index_opt_t), at the path that would have been read
-    for (int which = 0; which < 2; ++which) {
-        const std::string p = which == 0 ? R.bai : std::string(job->fasta_path) + ".fai";
+    for (int which = 0; which <= n_in; ++which) {     // every input's .bai, then the .fai
+        const bool is_bai = which < n_in;
+        const std::string p = is_bai ? R.bais[which] : std::string(job->fasta_path) + ".fai";
         FILE *f = fopen(p.c_str(), "rb");
         if (f) { fclose(f); continue; }
         if (!idx) return set_err(-30, W + ": cannot open the index " + p + " (the library does not build indexes here: lcd_call_file_indexed / --make-index does)");
-        if (!(which == 0 ? idx->build_missing_bai : idx->build_missing_fai))
-            return set_err(-30, W + ": cannot open the index " + p + " (lcd_index_opt_t." + (which == 0 ? "build_missing_bai" : "build_missing_fai") + " would build it)");
+        if (!(is_bai ? idx->build_missing_bai : idx->build_missing_fai))
+            return set_err(-30, W + ": cannot open the index " + p + " (lcd_index_opt_t." + (is_bai ? "build_missing_bai" : "build_missing_fai") + " would build it)");
         const double t0 = now_ms();
-        if (which == 0) {
+        if (is_bai) {
             lcd_bai_opt_t bo; bo.slab_members = idx->slab_members; bo.verify_crc = 0;
-            if (int rc = lcd_bai_build(job->bam_path, p.c_str(), &bo, nullptr)) return rc;
-            ist->built_bai = 1; ist->ms_build_bai = now_ms() - t0;
+            if (int rc = lcd_bai_build(R.bam_p[which], p.c_str(), &bo, nullptr)) return rc;
+            ist->built_bai = 1; ist->ms_build_bai += now_ms() - t0;
         } else {
             const int rc = lcd_fai_build(job->fasta_path, p.c_str());
             if (rc < 0) return rc;
@@ -422,7 +446,20 @@ extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t 
         }
     }
     std::string text;
-    if (int rc = bam_header_parts(job->bam_path, text, R.names, R.lens, W)) return rc;
+    if (int rc = bam_header_parts(bam0, text, R.names, R.lens, W)) return rc;
+    // PROJECT RULE: every further file carries file 0's reference table -- names, lengths, order (the reference uses file 0's tids for every file unchecked)
+    for (int f = 1; f < n_in; ++f) {
+        std::string t2; std::vector<std::string> nm2; std::vector<int64_t> ln2;
+        if (int rc = bam_header_parts(R.bam_p[f], t2, nm2, ln2, W)) return rc;
+        const size_t m = std::min(nm2.size(), R.names.size());
+        size_t i = 0;
+        while (i < m && nm2[i] == R.names[i] && ln2[i] == R.lens[i]) ++i;
+        if (i < m || nm2.size() != R.names.size()) {
+            auto ent = [&](const std::vector<std::string> &nm, const std::vector<int64_t> &ln) { return i < nm.size() ? nm[i] + " (" + std::to_string((long long)ln[i]) + ")" : std::string("nothing"); };
+            return set_err(LCD_ERR_INPUT_HEADERS, W + ": " + R.bams[f] + " does not carry the reference table of " + R.bams[0] + ": entry " + std::to_string(i) + " is " + ent(nm2, ln2) +
+                                                      ", the first file has " + ent(R.names, R.lens));
+        }
+    }
     {
         std::vector<const char *> nm; for (const std::string &s : R.names) nm.push_back(s.c_str());
         const int rc = lcd_plan_chunks((int)nm.size(), nm.data(), R.lens.data(), job->contig_mode, job->n_exclude, job->exclude, job->n_regions, job->regions, job->region_bed_path,
@@ -448,19 +485,22 @@ extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t 
     {
         char *hdr = nullptr, *sm = nullptr;
         if (!job->no_vcf_header) {
-            if (!job->sample_name && lcd_bam_sample_name(job->bam_path, &sm)) return -30;
+            if (!job->sample_name && lcd_bam_sample_name(bam0, &sm)) return -30;
+            std::string joined;     // src/call_var_main.c:733-735: without an SM, the input paths
+            for (int f = 0; f < n_in; ++f) joined += (f ? "," : "") + R.bams[f];
             std::vector<const char *> nm; for (const std::string &s : R.names) nm.push_back(s.c_str());
             char date[16] = "";
             if (!job->date_yyyymmdd) { const time_t now = time(nullptr); struct tm tmv; localtime_r(&now, &tmv); strftime(date, sizeof(date), "%Y%m%d", &tmv); }
             lcd_vcf_header(job->source_version ? job->source_version : lcd_version(), job->cmdline ? job->cmdline : "", job->date_yyyymmdd ? job->date_yyyymmdd : date, (int)nm.size(),
-                           nm.data(), R.lens.data(), job->sample_name ? job->sample_name : sm ? sm : job->bam_path, &hdr);
+                           nm.data(), R.lens.data(), job->sample_name ? job->sample_name : sm ? sm : joined.c_str(), &hdr);
         }
         R.vcf = lcd_vcf_writer_open(job->vcf_path, job->vcf_bgzf, hdr);
         free(hdr); free(sm);
         if (!R.vcf) { lcd_file_stats_free(stats); return -30; }
         if (job->bam_out) {
-            R.bam = idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(job->bam_path, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(job->bam_path, job->bam_out);
+            R.bam = idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(bam0, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(bam0, job->bam_out);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
+            lcd_bam_writer_set_sort(R.bam, in ? in->sort_output : 0);
         }
     }
     const int n_windows = (R.plan.n + window - 1) / window;
@@ -516,6 +556,20 @@ extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t 
         stats->records = dup_vec(R.kept); stats->n_kept_records = (int)R.kept.size();
     }
     stats->peak_device_bytes = R.peak.load();
+    if (n_reads_per_file) for (int f = 0; f < n_in; ++f) n_reads_per_file[f] = R.reads_per_file[f];
     stats->ms_wall = now_ms() - t_wall;
     return rc ? set_err(rc, R.err_msg) : 0;
+}
+} // namespace
+
+extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats) { return lcd_call_file_indexed(job, cfg, nullptr, stats, nullptr); }
+
+extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats) {
+    return call_files_core(idx ? "lcd_call_file_indexed" : "lcd_call_file", nullptr, job, cfg, idx, stats, idx_stats, nullptr);
+}
+
+extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
+                              lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file) {
+    if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); return set_err(-4, "lcd_call_files: NULL argument"); }
+    return call_files_core("lcd_call_files", in, job, cfg, idx, stats, idx_stats, n_reads_per_file);
 }

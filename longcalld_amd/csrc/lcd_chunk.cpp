@@ -168,15 +168,19 @@ lcd_chunk_t *lcd_chunk_create(const lcd_digar_opt_t *opt, int n, const int64_t *
 // records' auxiliary fields in HBM; reads compared with the reference go through the lcd_refcmp_kernel passes on the CIGAR words and the 4-bit bases where the
 // inflate left them; the cs / MD VALUES (O(events) bytes, the only record bytes that cross PCIe) come to the host, are parsed by cs_to_words / md_to_words and go
 // back as EQX-shaped words; ONE digar launch covers all reads.  src == NULL is lcd_chunk_create_from_bam as it always was.
-lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
-                                     int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
-    if (meta) memset(meta, 0, sizeof(*meta));
-    if (!opt || !bam_path || !bai_path || !chrom) { set_err(-4, "lcd_chunk_create_from_bam: NULL argument"); return nullptr; }
+//
+// Several files of one sample (collect_ref_seq_bam_main's loop over the files, src/bam_utils.c:1659-1716): the files' region images are appended in file order and
+// inflated in ONE launch; every index range is one walk job that ends at its own file's segment of the stream; the loader's rule runs file by file (its stop rule and
+// the contig's tid, looked up by name in every header, restart at each file), so the chunk's reads and its record table are file-major.  Nothing behind this function
+// knows about files: no kernel takes a file index.  lcd_chunk_open_from_bam is the n = 1 case.
+namespace {
+lcd_chunk_t *chunk_open_files(const lcd_digar_opt_t *opt, int n_bams, const char *const *bam_paths, const char *const *bai_paths, const char *chrom, int64_t reg_beg,
+                              int64_t reg_end, int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
     if (ensure_init()) return nullptr;
     LcdRegionImage im;
-    if (lcd_io_region_image(bam_path, bai_path, chrom, reg_beg, reg_end, im)) { set_err(-30, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
+    if (lcd_io_region_images(n_bams, bam_paths, bai_paths, chrom, reg_beg, reg_end, im)) { set_err(-30, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
     std::unique_ptr<lcd_chunk_s> c(new lcd_chunk_s());
-    c->device = cur_device(); c->n_reads = 0; c->opt = *opt; c->from_bam = true;
+    c->device = cur_device(); c->n_reads = 0; c->opt = *opt; c->from_bam = true; c->n_files = n_bams;
     c->pending.reset(new ChunkPending());
     ChunkPending &P = *c->pending; P.reg_beg = reg_beg; P.reg_end = reg_end; P.tlen = im.tlen;
     if (meta) { meta->tid = im.tid; meta->n_targets = im.n_ref; meta->target_len = im.tlen; }
@@ -190,6 +194,8 @@ lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam
 #define CHK(x) do { if ((x) != hipSuccess) { (void)hipGetLastError(); return fail(-10, "HIP call failed: " #x); } } while (0)
     // 1. the records of every range: one serial hop per record on the device
     const int nr = (int)im.ranges.size();
+    std::vector<int> file_of(nr, 0);     // the file a range belongs to
+    for (int f = 0; f < n_bams; ++f) for (size_t k = 0; k < im.files[f].range_n; ++k) file_of[im.files[f].range_first + k] = f;
     std::vector<BamWalkJob> wj(nr); std::vector<BamWalkOut> wo(nr);
     std::vector<BamRecDesc> descs; std::vector<size_t> first(nr + 1, 0);
     DevBuf d_desc, d_wj, d_wo;
@@ -203,8 +209,10 @@ lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam
         first[nr] = tot;
         if (d_desc.ensure(tot * sizeof(BamRecDesc)) || d_wj.ensure(nr * sizeof(BamWalkJob)) || d_wo.ensure(nr * sizeof(BamWalkOut))) return nullptr;
         for (int k = 0; k < nr; ++k) {
-            wj[k].stream = base; wj[k].ubeg = im.ranges[k].first; wj[k].uend = std::min<uint64_t>(im.ranges[k].second, usize); wj[k].usize = usize;
-            wj[k].descs = d_desc.addr() + first[k] * sizeof(BamRecDesc); wj[k].reg_end = reg_end; wj[k].tid = im.tid;
+            // a walk ends at its FILE's segment of the stream, not at the stream's end: behind the segment lie the next file's bytes
+            const uint64_t fend = std::min<uint64_t>(im.files[file_of[k]].uend, usize);
+            wj[k].stream = base; wj[k].ubeg = std::min<uint64_t>(im.ranges[k].first, fend); wj[k].uend = std::min<uint64_t>(im.ranges[k].second, fend); wj[k].usize = fend;
+            wj[k].descs = d_desc.addr() + first[k] * sizeof(BamRecDesc); wj[k].reg_end = reg_end; wj[k].tid = im.files[file_of[k]].tid;
         }
         CHK(hipMemcpyAsync(d_wj.p, wj.data(), nr * sizeof(BamWalkJob), hipMemcpyHostToDevice, st));
         lcd_launch_bam_walk((const BamWalkJob *)d_wj.p, (BamWalkOut *)d_wo.p, nr, st);
@@ -222,7 +230,9 @@ lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam
     CHK(hipStreamSynchronize(st));
     // 2. CIGAR statistics of the wanted reference's records
     std::vector<int> stat_of(nrec, -1); std::vector<BamStatJob> sj;
-    for (size_t i = 0; i < nrec; ++i) if (descs[i].refid == im.tid) {
+    std::vector<int> tid_of(nrec + 1, -1);     // per record the wanted contig's tid in its own file
+    for (int k = 0; k < nr; ++k) for (size_t i = at[k]; i < at[k + 1]; ++i) tid_of[i] = im.files[file_of[k]].tid;
+    for (size_t i = 0; i < nrec; ++i) if (descs[i].refid == tid_of[i]) {
         BamStatJob j; j.rec = base + descs[i].off; j.bs = descs[i].bs; j.lname = descs[i].lname; j.nc = descs[i].nc; j.lseq = descs[i].lseq;
         stat_of[i] = (int)sj.size(); sj.push_back(j);
     }
@@ -240,41 +250,46 @@ lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam
     std::vector<int64_t> &pos0 = P.pos0, &rl_true = P.rl_true; std::vector<int> &ncig = P.ncig, &qlen = P.qlen, &nindel = P.nindel; std::vector<uint64_t> &coff = P.coff, &soff = P.soff, &qoff = P.qoff;
     std::vector<RefCmpOut> &counts = P.counts; std::vector<BamAuxJob> &auxj = P.auxj; DevBuf &d_cig = P.d_cig;   // (kept for lcd_chunk_resolve)
     std::vector<int64_t> endp; std::vector<int> mapq, flag; std::vector<uint64_t> noff; std::vector<GatherJob> gj, nj;
-    uint64_t cw = 0, nbytes = 0; bool done = false;
+    uint64_t cw = 0, nbytes = 0;
     const char *malformed = "malformed BAM record (a field runs past the record, or a placeholder CIGAR without its CG tag)";
-    for (int k = 0; k < nr && !done; ++k) {
-        for (size_t i = at[k]; i < at[k + 1] && !done; ++i) {
-            const BamRecDesc &d = descs[i];
-            if (d.refid != im.tid) { if ((d.refid > im.tid || d.refid < 0) && !pos0.empty()) done = true; continue; }
-            const BamStatOut &x = so[stat_of[i]];
-            if (x.kind == -2) return fail(-33, malformed);
-            const int64_t e0 = (int64_t)d.pos + (x.rl > 0 ? x.rl : 1);
-            if (d.pos >= reg_end) { done = true; break; }
-            // the record table of the alignment output: the iterator's overlap test applies whatever the flags say; PROJECT RULE (htslib is not in the checkout): a
-            // record with the unmapped flag spans one base, like one whose CIGAR consumes no reference (bam_endpos)
-            const int64_t e0_any = (d.flag & 0x4) ? (int64_t)d.pos + 1 : e0;
-            const bool kept = e0 > reg_beg - 1 && !((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq);
-            if (e0_any > reg_beg - 1) {
-                c->rec_beg.push_back(d.off - 4); c->rec_stop.push_back(d.off + (uint64_t)d.bs); c->rec_read.push_back(kept ? (int)pos0.size() : -1);
-                c->rec_pos0.push_back(d.pos); c->rec_endpos.push_back(e0_any);
+    for (int f = 0; f < n_bams; ++f) {
+        const int ftid = im.files[f].tid; const size_t n_before = pos0.size();     // (the stop rules see this file's reads only)
+        bool done = false;
+        for (int k = (int)im.files[f].range_first; k < (int)(im.files[f].range_first + im.files[f].range_n) && !done; ++k) {
+            for (size_t i = at[k]; i < at[k + 1] && !done; ++i) {
+                const BamRecDesc &d = descs[i];
+                if (d.refid != ftid) { if ((d.refid > ftid || d.refid < 0) && pos0.size() > n_before) done = true; continue; }
+                const BamStatOut &x = so[stat_of[i]];
+                if (x.kind == -2) return fail(-33, malformed);
+                const int64_t e0 = (int64_t)d.pos + (x.rl > 0 ? x.rl : 1);
+                if (d.pos >= reg_end) { done = true; break; }
+                // the record table of the alignment output: the iterator's overlap test applies whatever the flags say; PROJECT RULE (htslib is not in the checkout): a
+                // record with the unmapped flag spans one base, like one whose CIGAR consumes no reference (bam_endpos)
+                const int64_t e0_any = (d.flag & 0x4) ? (int64_t)d.pos + 1 : e0;
+                const bool kept = e0 > reg_beg - 1 && !((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq);
+                if (e0_any > reg_beg - 1) {
+                    c->rec_beg.push_back(d.off - 4); c->rec_stop.push_back(d.off + (uint64_t)d.bs); c->rec_read.push_back(kept ? (int)pos0.size() : -1);
+                    c->rec_pos0.push_back(d.pos); c->rec_endpos.push_back(e0_any); c->rec_file.push_back(f);
+                }
+                if (e0 <= reg_beg - 1) continue;
+                if ((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq) continue;
+                c->read_file.push_back(f);
+                pos0.push_back(d.pos); endp.push_back(e0); mapq.push_back(d.mapq); flag.push_back(d.flag); ncig.push_back(x.nc); qlen.push_back(d.lseq);
+                const uint64_t sq = d.off + 32 + d.lname + 4ull * d.nc;
+                soff.push_back(sq); qoff.push_back(sq + ((uint64_t)d.lseq + 1) / 2);
+                c->aux_off.push_back(sq + ((uint64_t)d.lseq + 1) / 2 + (uint64_t)d.lseq); c->rec_end.push_back(d.off + (uint64_t)d.bs); // (the walk checked: the fixed fields end inside the record)
+                coff.push_back(cw); { GatherJob g; g.src = x.cig_src; g.dst = cw * 4; g.bytes = (uint32_t)x.nc * 4u; g.pad_ = 0; gj.push_back(g); } cw += (uint64_t)x.nc;
+                RefCmpOut rc; rc.n_ops = x.nc; rc.nd = (int)x.nd; rc.nev = (int)x.nev; rc.pad = 0; counts.push_back(rc); nindel.push_back((int)x.nid);
+                {
+                    BamAuxJob a; a.rec = base + d.off; a.cig = x.cig_src; a.bs = d.bs; a.lname = d.lname; a.nc16 = d.nc; a.lseq = d.lseq; a.nc = x.nc; a.flag = d.flag; a.prim_pos = (long long)d.pos + 1; a.prim_end = e0;
+                    auxj.push_back(a); rl_true.push_back(x.rl);
+                }
+                noff.push_back(nbytes); { GatherJob g; g.src = base + d.off + 32; g.dst = nbytes; g.bytes = d.lname; g.pad_ = 0; nj.push_back(g); } nbytes += d.lname;
             }
-            if (e0 <= reg_beg - 1) continue;
-            if ((d.flag & (0x4 | 0x100 | 0x800)) || (int)d.mapq < min_mapq) continue;
-            pos0.push_back(d.pos); endp.push_back(e0); mapq.push_back(d.mapq); flag.push_back(d.flag); ncig.push_back(x.nc); qlen.push_back(d.lseq);
-            const uint64_t sq = d.off + 32 + d.lname + 4ull * d.nc;
-            soff.push_back(sq); qoff.push_back(sq + ((uint64_t)d.lseq + 1) / 2);
-            c->aux_off.push_back(sq + ((uint64_t)d.lseq + 1) / 2 + (uint64_t)d.lseq); c->rec_end.push_back(d.off + (uint64_t)d.bs); // (the walk checked: the fixed fields end inside the record)
-            coff.push_back(cw); { GatherJob g; g.src = x.cig_src; g.dst = cw * 4; g.bytes = (uint32_t)x.nc * 4u; g.pad_ = 0; gj.push_back(g); } cw += (uint64_t)x.nc;
-            RefCmpOut rc; rc.n_ops = x.nc; rc.nd = (int)x.nd; rc.nev = (int)x.nev; rc.pad = 0; counts.push_back(rc); nindel.push_back((int)x.nid);
-            {
-                BamAuxJob a; a.rec = base + d.off; a.cig = x.cig_src; a.bs = d.bs; a.lname = d.lname; a.nc16 = d.nc; a.lseq = d.lseq; a.nc = x.nc; a.flag = d.flag; a.prim_pos = (long long)d.pos + 1; a.prim_end = e0;
-                auxj.push_back(a); rl_true.push_back(x.rl);
+            if (!done) {
+                if (wo[k].status == 1) return fail(-33, "truncated BAM record");
+                if (wo[k].status == 2) return fail(-33, malformed);
             }
-            noff.push_back(nbytes); { GatherJob g; g.src = base + d.off + 32; g.dst = nbytes; g.bytes = d.lname; g.pad_ = 0; nj.push_back(g); } nbytes += d.lname;
-        }
-        if (!done) {
-            if (wo[k].status == 1) return fail(-33, "truncated BAM record");
-            if (wo[k].status == 2) return fail(-33, malformed);
         }
     }
     const int n = (int)pos0.size();
@@ -307,6 +322,33 @@ lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam
     if (n > 0 && hipStreamSynchronize(st) != hipSuccess) { (void)hipGetLastError(); if (meta) { lcd_bam_reads_free(meta); memset(meta, 0, sizeof(*meta)); } return fail(-10, "HIP call failed: hipStreamSynchronize"); }
 #undef CHK
     return c.release();
+}
+} // namespace
+
+lcd_chunk_t *lcd_chunk_open_from_bam(const lcd_digar_opt_t *opt, const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end,
+                                     int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
+    if (meta) memset(meta, 0, sizeof(*meta));
+    if (!opt || !bam_path || !bai_path || !chrom) { set_err(-4, "lcd_chunk_create_from_bam: NULL argument"); return nullptr; }
+    return chunk_open_files(opt, 1, &bam_path, &bai_path, chrom, reg_beg, reg_end, min_mapq, verify_crc, meta);
+}
+lcd_chunk_t *lcd_chunk_open_from_bams(const lcd_digar_opt_t *opt, int n_bams, const char *const *bam_paths, const char *const *bai_paths, const char *chrom, int64_t reg_beg,
+                                      int64_t reg_end, int min_mapq, int verify_crc, lcd_bam_reads_t *meta) {
+    if (meta) memset(meta, 0, sizeof(*meta));
+    if (!opt || !bam_paths || !chrom || n_bams < 1 || n_bams > LCD_MAX_INPUTS) { set_err(-4, "lcd_chunk_open_from_bams: NULL argument, or n_bams outside 1 ... LCD_MAX_INPUTS"); return nullptr; }
+    std::vector<std::string> bai(n_bams); std::vector<const char *> bp(n_bams);
+    for (int f = 0; f < n_bams; ++f) {
+        if (!bam_paths[f]) { set_err(-4, "lcd_chunk_open_from_bams: NULL path"); return nullptr; }
+        bai[f] = bai_paths && bai_paths[f] ? std::string(bai_paths[f]) : std::string(bam_paths[f]) + ".bai"; bp[f] = bai[f].c_str();
+    }
+    return chunk_open_files(opt, n_bams, bam_paths, bp.data(), chrom, reg_beg, reg_end, min_mapq, verify_crc, meta);
+}
+int lcd_chunk_n_files(const lcd_chunk_t *c) { return c ? c->n_files : 0; }
+// per kept read the index of the file it came from (a chunk made from host arrays, or from one BAM: 0)
+int lcd_chunk_read_files(const lcd_chunk_t *c, int *file_of_read) {
+    if (!c) return set_err(-4, "lcd_chunk_read_files: NULL chunk");
+    if (c->n_reads > 0 && !file_of_read) return set_err(-4, "lcd_chunk_read_files: NULL output");
+    for (int r = 0; r < c->n_reads; ++r) file_of_read[r] = r < (int)c->read_file.size() ? c->read_file[r] : 0;
+    return c->n_reads;
 }
 int lcd_chunk_resolve(lcd_chunk_t *c, const lcd_chunk_src_t *src) {
     if (!c || !c->pending) return set_err(-4, "lcd_chunk_resolve: the handle was not opened by lcd_chunk_open_from_bam, or is resolved already");

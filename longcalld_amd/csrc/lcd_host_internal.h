@@ -258,6 +258,8 @@ struct lcd_chunk_s {
     // lcd_chunk_create_from_bam*: EVERY record the region's iterator yields, in file order (lcd_chunk_tag_records, lcd_write_phased_bam): [rec_beg, rec_stop) of the
     // inflated stream from its block_size word on, the chunk read id of a kept record or -1 for one the loader's flag / MAPQ filter dropped, pos0 and bam_endpos
     std::vector<uint64_t> rec_beg, rec_stop; std::vector<int> rec_read; std::vector<int64_t> rec_pos0, rec_endpos;
+    // lcd_chunk_open_from_bams: the number of input files (1 otherwise), and per record / per kept read the file it came from; both tables are file-major
+    int n_files = 1; std::vector<int> rec_file, read_file;
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     std::unique_ptr<ChunkPending> pending;                 // lcd_chunk_open_from_bam: set until lcd_chunk_resolve (a handle with it has no digars yet)

@@ -341,6 +341,24 @@ int lcd_io_region_image(const char *bam_path, const char *bai_path, const char *
     return 0;
 }
 
+int lcd_io_region_images(int n, const char *const *bam_paths, const char *const *bai_paths, const char *chrom, int64_t reg_beg, int64_t reg_end, LcdRegionImage &out) {
+    out.image.clear(); out.ranges.clear(); out.files.clear();
+    uint64_t u = 0;
+    for (int f = 0; f < n; ++f) {
+        LcdRegionImage one;
+        if (int rc = lcd_io_region_image(bam_paths[f], bai_paths[f], chrom, reg_beg, reg_end, one)) { if (n > 1) g_io_err = std::string(bam_paths[f]) + ": " + g_io_err; return rc; }
+        std::vector<Blk> blks; size_t total = 0;     // (the ISIZE footers)
+        if (int rc = bgzf_blocks(Bytes{one.image.data(), one.image.size()}, blks, &total)) return rc;
+        LcdFileSeg s; s.ubeg = u; s.uend = u + total; s.range_first = out.ranges.size(); s.range_n = one.ranges.size(); s.tid = one.tid; s.n_ref = one.n_ref; s.tlen = one.tlen;
+        for (auto &r : one.ranges) out.ranges.emplace_back(r.first + u, r.second + u);
+        if (f == 0) { out.image.swap(one.image); out.tid = one.tid; out.n_ref = one.n_ref; out.tlen = one.tlen; }
+        else out.image.insert(out.image.end(), one.image.begin(), one.image.end());
+        out.files.push_back(s);
+        u += total;
+    }
+    return 0;
+}
+
 // the BAM header block of a file as it lies in the inflated stream: magic, l_text, text, n_ref, the reference table
 int lcd_io_bam_header(const char *bam_path, std::vector<uint8_t> &hdr) {
     hdr.clear();
