@@ -8,8 +8,9 @@
 //     ballot-driven pass walks the 64 results in stream order: runs of literals are taken at once, a match skips the lanes it covers.  Only the positions a pass
 //     consumed (its first 64) enter the table, after the pass -- a position never finds itself;
 //   * codes: symbol histograms in LDS (LDS atomics), dynamic Huffman lengths by the in-place minimum-redundancy construction (Moffat & Katajainen 1995) on the
-//     rank-sorted frequencies, limited to 15 bits (7 for the code-length alphabet) by moving codes down the Kraft sum; canonical codes by ballot ranks; the code
-//     lengths are written with the run-length symbols 16 / 17 / 18;
+//     rank-sorted frequencies, limited to 15 bits by moving codes down the Kraft sum (measured at most 0.016 % over the optimal limited code) and, for the
+//     code-length alphabet, to 7 bits by package-merge (the optimum: 19 symbols fit one wavefront); canonical codes by ballot ranks; the code lengths are written
+//     with the run-length symbols 16 / 17 / 18;
 //   * bits: 64 tokens at a time -- each lane makes its token's bits (<= 48), an inclusive prefix sum of the bit lengths gives every lane its bit offset, the
 //     lanes OR their bits into a 512-byte staging area in LDS and finished dwords go to HBM as one coalesced store;
 //   * the cheapest of stored / fixed / dynamic is written; a block whose coded form is not smaller than the stored form (payload + 5 bytes) is stored, so a
@@ -17,7 +18,7 @@
 //   * CRC-32 by crc32_gf2.h (the inflate kernel's slice-and-combine arithmetic).
 // Tokens (4 bytes each) wait in HBM between the match pass and the bit pass: a workspace of `payload` words per WORKGROUP; the grid strides over the blocks.
 // Every loop is bounded by the block's byte count or by a constant written in its header; none ends on data alone.
-// LDS: 14 540 bytes per block (8 KB of it the hash table) -> 11 blocks per CU (160 KB; 143 VGPRs allow 12); inflate_kernel.hip measured that small footprints win for this kind of
+// LDS: 14 540 bytes per block (8 KB of it the hash table) -> 11 blocks per CU (160 KB; 151 VGPRs allow 12); inflate_kernel.hip measured that small footprints win for this kind of
 // serial-per-wavefront work, so the 32 KB window is NOT kept in LDS: candidates are verified against the block's bytes in HBM (L2).
 // Written from RFC 1951 / RFC 1952 and the SAM specification's BGZF section only; no zlib source was consulted.
 #include <hip/hip_runtime.h>
@@ -86,15 +87,53 @@ __device__ __forceinline__ long long wave_sum_ll(long long v) {
     return v;
 }
 
+// Optimal lengths of at most `limit` bits for a SMALL alphabet whose unrestricted code is deeper than that: package-merge (Larmore & Hirschberg 1990), one list item
+// per lane.  n <= 21 symbols in use and limit <= 7, so that a list (n leaves and the pairs of the list before it: fewer than 2 n items) fits the wavefront and an
+// item's record of how often it holds each leaf (at most once per level: 3 bits each) fits 64 bits.  The leaves are the symbols in rank order (S.ssym); level by
+// level the pairs of the current list are merged with the leaves (a leaf goes in front of a pair of its weight), every item finding its place by counting; the
+// first 2 n - 2 items of the last list hold leaf i as often as its code is long.  -> S.cnt: the codes per length.  S.key is the staging area (free by now).
+__device__ void package_merge_counts(DeflLds &S, const unsigned *hist, const int n, const int limit, const int lane) {
+    const unsigned lw = lane < n ? hist[S.ssym[lane]] : 0u;
+    const unsigned long long lc = lane < n ? 1ull << (3 * imin(lane, 20)) : 0ull;
+    unsigned w = lw;
+    unsigned long long c = lc;
+    int m = n;
+    auto sh64 = [](const unsigned long long v, const int src) -> unsigned long long {
+        return ((unsigned long long)(unsigned)__shfl((int)(v >> 32), src, 64) << 32) | (unsigned long long)(unsigned)__shfl((int)(unsigned)v, src, 64);
+    };
+    for (int level = 2; level <= limit; ++level) {
+        const int np = m >> 1, a = imin(2 * lane, 63), b = imin(2 * lane + 1, 63);
+        const unsigned pw = (unsigned)__shfl((int)w, a, 64) + (unsigned)__shfl((int)w, b, 64);
+        const unsigned long long pc = sh64(c, a) + sh64(c, b);
+        int posl = lane, posp = lane;
+        for (int k = 0; k < np; ++k) posl += (unsigned)__shfl((int)pw, k, 64) < lw ? 1 : 0;
+        for (int i = 0; i < n; ++i) posp += (unsigned)__shfl((int)lw, i, 64) <= pw ? 1 : 0;
+        __syncthreads();
+        if (lane < n) { S.key[posl] = lw; S.key[64 + posl] = (unsigned)lc; S.key[128 + posl] = (unsigned)(lc >> 32); }     // posl, posp < n + np <= 41
+        if (lane < np) { S.key[posp] = pw; S.key[64 + posp] = (unsigned)pc; S.key[128 + posp] = (unsigned)(pc >> 32); }
+        __syncthreads();
+        m = n + np;
+        w = lane < m ? S.key[lane] : 0u;
+        c = lane < m ? ((unsigned long long)S.key[128 + lane] << 32) | S.key[64 + lane] : 0ull;
+    }
+    const unsigned long long tot = (unsigned long long)wave_sum_ll((long long)(lane < 2 * n - 2 ? c : 0ull));
+    __syncthreads();
+    if (lane < 16) S.cnt[lane] = 0;
+    __syncthreads();
+    if (lane < n) atomicAdd(&S.cnt[(int)((tot >> (3 * imin(lane, 20))) & 7ull)], 1u);
+}
+
 // Code lengths of one alphabet (nsym <= 288 symbols, frequencies in hist) limited to `limit` bits -> lens.  At least two symbols get a code (a lone symbol
-// would need a zero-bit code; the frequencies of the first free symbols are raised to 1), so the code is always complete.
+// would need a zero-bit code; the frequencies of the first free symbols are raised to 1 while the lengths are made), so the code is always complete.
 __device__ void huff_lengths(DeflLds &S, unsigned *hist, const int nsym, const int limit, unsigned char *lens, const int lane) {
     __syncthreads();
     int n = 0;
     for (int r = 0; r < 5; ++r) { const int s = r * 64 + lane; n += __popcll(__ballot(s < nsym && hist[s] > 0)); }
     n = ufl(n);
+    int raised = 0;                                                       // the symbols that were given a frequency here: they get a code and go back to 0
     if (n < 2) {
-        if (lane == 0) { int need = 2 - n; for (int s = 0; s < 3 && need > 0; ++s) if (!hist[s]) { hist[s] = 1; --need; } }
+        if (lane == 0) { int need = 2 - n; for (int s = 0; s < 3 && need > 0; ++s) if (!hist[s]) { hist[s] = 1; --need; raised |= 1 << s; } }
+        raised = ufl(raised);
         n = 2;
         __syncthreads();
     }
@@ -141,7 +180,9 @@ __device__ void huff_lengths(DeflLds &S, unsigned *hist, const int nsym, const i
     auto SC = [&](const int i, const int v) { if (lane == 0) S.cnt[i] = (unsigned)v; };
     int total = 0;
     for (int i = limit; i > 0; --i) total += Cn(i) << (limit - i);
-    for (int g = 0; g < 512 && total != (1 << limit); ++g) {              // the Kraft sum is over by less than one per clamped symbol
+    if (total != (1 << limit) && limit <= 7 && n <= 21) package_merge_counts(S, hist, n, limit, lane);   // the code-length alphabet: the optimum (its cost is a few hundred
+                                                                                                         // bits, where one bit given away is 0.15 %)
+    else for (int g = 0; g < 512 && total != (1 << limit); ++g) {         // the Kraft sum is over by less than one per clamped symbol
         SC(limit, Cn(limit) - 1);
         for (int i = limit - 1; i > 0; --i) if (Cn(i)) { SC(i, Cn(i) - 1); SC(i + 1, Cn(i + 1) + 2); break; }
         --total;
@@ -154,6 +195,7 @@ __device__ void huff_lengths(DeflLds &S, unsigned *hist, const int nsym, const i
         for (int i = 1; i <= 15; ++i) { if (i <= limit) { acc += (int)S.cnt[i]; if (q < acc) { L = i; break; } } }
         lens[S.ssym[j]] = (unsigned char)L;
     }
+    if (lane < 3 && ((raised >> lane) & 1)) hist[lane] = 0;               // a symbol that never occurs costs the block no bits (the dynamic form's size is counted from hist)
     __syncthreads();
 }
 
