@@ -1127,6 +1127,51 @@ int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output);
 int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
                    lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file /* n entries or NULL */);
 
+/* ---- VCF content: MEI annotation from a TE library (longcallD call -T FILE) and supporting read names (--out-var-rnames / --out-sv-rnames) ----
+ * lcd_te_lib_from_fasta == make_te_kmer_idx (src/kmer.c:120-148) with its file reading: every record of a plain or gzip-compressed FASTA file (gzopen / gzread) as
+ * kseq_read (src/kseq.h:175-215) yields it -- the name is the header up to the first whitespace, the sequence the letters as they are (any case, any number of
+ * lines, \n or \r\n), records in file order: te_seq_i is the record's index -- handed to lcd_te_lib_create.  kmer_len 0 = 15 (src/call_var_main.c:215).  *names:
+ * n malloc()'d strings in a malloc()'d array; *seq_lens (the pointer may be NULL): the sequences' lengths, malloc()'d; release everything with
+ * lcd_te_lib_from_fasta_free.  A file that cannot be opened or read: -30 with the path in lcd_last_error.  A file without a record is valid (*n_seqs = 0: the
+ * library matches nothing, as no library); a record with an empty sequence keeps its index and never matches.
+ * lcd_format_vcf_fields == lcd_format_vcf_te plus write_var_to_vcf's ALTREADS (src/vcf_utils.c:205-253).  rnames_mode LCD_RNAMES_NONE: exactly lcd_format_vcf_te;
+ * LCD_RNAMES_SV: records with is_sv; LCD_RNAMES_ALL: every record (the reference's `output_var_rnames || (is_sv && output_sv_rnames)`, :208).  A record that
+ * qualifies gets ":ALTREADS" behind the FORMAT keys (after the optional ":PS") and, behind the sample's last value, ':' + the names of alt_read_i[0 .. AD[1]) joined
+ * by ',' in the order lcd_make_variants stored them (ordered_read_ids order, skipped reads left out), or "." when AD[1] == 0; a two-alt record lists allele 1's
+ * reads only, as the reference does.  alt_read_i indexes the reads of the chunk that made the record: name_pool + name_off[r] for r < n_reads are that chunk's names
+ * (lcd_bam_reads_t's fields), so records are formatted chunk by chunk.  An index outside [0, n_reads), or AD[1] above n_alt_reads: -4 (nothing is read out of
+ * bounds), *text_out NULL.  *n_mei (may be NULL): the lines written that carry MEI.  lcd_alt_read_names: the ALTREADS value of one record, malloc()'d.
+ * lcd_vcf_fields_t: the options of the drivers below.  te_fasta_path NULL: no library; te_kmer_len 0 = 15; rnames_mode as above.  The library is read once per
+ * call -- before any output file is created: an unreadable file fails the call like the other input checks -- and shared read-only by every window and host
+ * thread; lcd_annotate_te gets it and the formatter its names.  With a names mode every chunk's records are formatted against chunks[c].first.meta's names (a chunk
+ * without meta->name_off / name_pool: -4), whatever the number of chunks, contigs, windows or input files (several files: the reads, and so the names, are
+ * file-major).  `fields` NULL or all zero: the text and every output file are byte-identical to the entry point without it.
+ * lcd_vcf_fields_out_t (may be NULL; release with lcd_vcf_fields_out_free): the library's names, the MEI lines written, and -- with a names mode -- per returned /
+ * kept record (*records of lcd_chunks_call_fields / lcd_call_bam_regions_fields, stats->records with keep_records) its ALTREADS value, NULL for a record the mode
+ * leaves out.  --out-som-var-rnames belongs to somatic mode and is not supported. */
+#define LCD_RNAMES_NONE 0
+#define LCD_RNAMES_SV 1
+#define LCD_RNAMES_ALL 2
+typedef struct lcd_vcf_fields_t { const char *te_fasta_path; int te_kmer_len; int rnames_mode; } lcd_vcf_fields_t;
+typedef struct lcd_vcf_fields_out_t { int n_te_seqs; char **te_names; int64_t n_mei_lines; int n_rnames; char **rnames; } lcd_vcf_fields_out_t;
+int lcd_te_lib_from_fasta(const char *path, int kmer_len, lcd_te_lib_t **lib, char ***names, int **seq_lens, int *n_seqs);
+void lcd_te_lib_from_fasta_free(lcd_te_lib_t *lib, char **names, int *seq_lens, int n_seqs);
+int lcd_format_vcf_fields(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n_vars, const char *const *te_names, int rnames_mode, int n_reads,
+                          const uint64_t *name_off, const char *name_pool, char **text_out, int *n_mei);
+int lcd_alt_read_names(const lcd_var1_t *var, int n_reads, const uint64_t *name_off, const char *name_pool, char **out);
+void lcd_vcf_fields_out_free(lcd_vcf_fields_out_t *out);
+/* the drivers with the options: lcd_chunks_call, lcd_call_bam_regions_out (bam_out may be NULL: lcd_call_bam_regions), lcd_call_file_indexed (idx may be NULL:
+ * lcd_call_file) and lcd_call_files are these calls with fields == NULL and fields_out == NULL */
+int lcd_chunks_call_fields(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const lcd_vcf_fields_t *fields, lcd_var1_t **records,
+                           int *n_records, char **vcf_body, lcd_vcf_fields_out_t *fields_out);
+int lcd_call_bam_regions_fields(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
+                                const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records,
+                                int *n_records, char **vcf_body, lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out);
+int lcd_call_file_fields(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields, lcd_file_stats_t *stats,
+                         lcd_index_stats_t *idx_stats, lcd_vcf_fields_out_t *fields_out);
+int lcd_call_files_fields(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
+                          lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -244,6 +244,17 @@ class LcdInputs(C.Structure):
     _fields_ = [("n", C.c_int), ("bam_paths", C.POINTER(C.c_char_p)), ("bai_paths", C.POINTER(C.c_char_p)), ("sort_output", C.c_int)]
 
 
+class LcdVcfFields(C.Structure):
+    """lcd_vcf_fields_t: the TE library (-T) and the supporting read names (--out-var-rnames / --out-sv-rnames) of a driver call"""
+    _fields_ = [("te_fasta_path", C.c_char_p), ("te_kmer_len", C.c_int), ("rnames_mode", C.c_int)]
+
+
+class LcdVcfFieldsOut(C.Structure):
+    """lcd_vcf_fields_out_t: the library's names, the MEI lines written, the ALTREADS value per returned / kept record"""
+    _fields_ = [("n_te_seqs", C.c_int), ("te_names", C.POINTER(C.c_char_p)), ("n_mei_lines", C.c_int64), ("n_rnames", C.c_int), ("rnames", C.POINTER(C.c_char_p))]
+
+
+LCD_RNAMES_NONE, LCD_RNAMES_SV, LCD_RNAMES_ALL = 0, 1, 2
 LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG, LCD_ERR_INPUT_HEADERS = -50, -51, -52, -53, -54
 LCD_MAX_INPUTS = 64
 LCD_CTG_AUTOSOME_XY, LCD_CTG_AUTOSOME, LCD_CTG_ALL = 0, 1, 2
@@ -272,6 +283,8 @@ EXPORTS = [
     "lcd_bai_from_records", "lcd_bai_builder_create", "lcd_bai_builder_add_stream", "lcd_bai_builder_finish", "lcd_bai_builder_bytes", "lcd_bai_builder_destroy", "lcd_bai_build",
     "lcd_fai_build", "lcd_bam_writer_open_indexed", "lcd_call_file_indexed",
     "lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_bam_writer_set_sort", "lcd_call_files",
+    "lcd_te_lib_from_fasta", "lcd_te_lib_from_fasta_free", "lcd_format_vcf_fields", "lcd_alt_read_names", "lcd_vcf_fields_out_free", "lcd_chunks_call_fields",
+    "lcd_call_bam_regions_fields", "lcd_call_file_fields", "lcd_call_files_fields",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -458,6 +471,23 @@ def load_library():
     lib.lcd_bam_writer_set_sort.argtypes = [C.c_void_p, C.c_int]
     lib.lcd_call_files.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats), i64p]
     lib.lcd_call_free.restype = None
+    fo = C.POINTER(LcdVcfFieldsOut)
+    lib.lcd_te_lib_from_fasta.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(i32p), i32p]
+    lib.lcd_te_lib_from_fasta_free.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), i32p, C.c_int]
+    lib.lcd_te_lib_from_fasta_free.restype = None
+    lib.lcd_format_vcf_fields.argtypes = [C.POINTER(LcdCallOpt), C.c_char_p, C.POINTER(LcdVar1), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, u64p_, C.c_char_p,
+                                          C.POINTER(C.c_void_p), i32p]
+    lib.lcd_alt_read_names.argtypes = [C.POINTER(LcdVar1), C.c_int, u64p_, C.c_char_p, C.POINTER(C.c_void_p)]
+    lib.lcd_vcf_fields_out_free.argtypes = [fo]
+    lib.lcd_vcf_fields_out_free.restype = None
+    lib.lcd_chunks_call_fields.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdCfg), C.c_char_p, C.POINTER(LcdVcfFields), C.POINTER(C.POINTER(LcdVar1)), i32p,
+                                           C.POINTER(C.c_void_p), fo]
+    lib.lcd_call_bam_regions_fields.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, i64p, i64p, C.c_int, C.POINTER(LcdCfg), C.POINTER(LcdVcfFields),
+                                                C.POINTER(LcdCallChunk), C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p), C.POINTER(LcdBamOut), fo]
+    lib.lcd_call_file_fields.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdVcfFields), C.POINTER(LcdFileStats),
+                                         C.POINTER(LcdIndexStats), fo]
+    lib.lcd_call_files_fields.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdVcfFields), C.POINTER(LcdFileStats),
+                                          C.POINTER(LcdIndexStats), i64p, fo]
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]
     lib.lcd_batch_digest.argtypes = [C.c_void_p]

@@ -1498,9 +1498,80 @@ def _call_result(lib, n, arr, recs, n_recs, text):
         lib.lcd_call_free(n, arr, recs, n_recs.value, text)
 
 
-def chunks_call(chunks, items, cfg=None, chrom="chr11"):
+class TeLib:
+    """a TE library read from a FASTA file (te_lib_from_fasta): .names, .seq_lens in file order; check(seq) = lcd_check_te_seq -> (te_seq_i or -1, is_rev)"""
+
+    def __init__(self, h, names, lens, n):
+        self.h, self._names, self._lens, self.n = h, names, lens, n
+        self.names = [names[i].decode() for i in range(n)]
+        self.seq_lens = [int(lens[i]) for i in range(n)]
+
+    def check(self, seq):
+        lib = load_library()
+        a = np.ascontiguousarray(seq, np.uint8)
+        a = a if a.size else np.zeros(1, np.uint8)
+        lib.lcd_check_te_seq.argtypes = [C.c_void_p, C.POINTER(C.c_uint8), C.c_int, i32p]
+        rev = C.c_int(0)
+        return int(lib.lcd_check_te_seq(self.h, _p8(a), int(len(seq)), C.byref(rev))), int(rev.value)
+
+    def close(self):
+        if self.h:
+            load_library().lcd_te_lib_from_fasta_free(self.h, self._names, self._lens, self.n)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def te_lib_from_fasta(path, kmer_len=0):
+    """lcd_te_lib_from_fasta: the -T file (plain or gzip FASTA, read as kseq reads it) -> TeLib; kmer_len 0 = 15"""
+    lib = load_library()
+    h, names, lens, n = C.c_void_p(), C.POINTER(C.c_char_p)(), i32p(), C.c_int(0)
+    check(lib.lcd_te_lib_from_fasta(str(path).encode(), int(kmer_len), C.byref(h), C.byref(names), C.byref(lens), C.byref(n)), lib)
+    return TeLib(h, names, lens, n.value)
+
+
+_RNAMES = {None: 0, "sv": 1, "all": 2}
+
+
+def _vcf_fields(te_fasta, rnames, te_kmer_len=0):
+    """the keywords te_fasta= / rnames=None|"sv"|"all" -> (LcdVcfFields, LcdVcfFieldsOut), or (None, None) without either: the entry point without options runs"""
+    from ._lib import LcdVcfFields, LcdVcfFieldsOut
+    if rnames not in _RNAMES:
+        raise ValueError('rnames must be None, "sv" or "all"')
+    if te_fasta is None and rnames is None:
+        return None, None
+    return LcdVcfFields(str(te_fasta).encode() if te_fasta is not None else None, int(te_kmer_len), _RNAMES[rnames]), LcdVcfFieldsOut()
+
+
+def _fields_result(lib, res, vf, fo):
+    """lcd_vcf_fields_out_t into a driver's result: "te_names", "n_mei_lines"; per record "te_name" (with a library) and "alt_read_names" (with a names mode: the list
+    behind ALTREADS, [] for ".", None for a record the mode leaves out).  Frees *fo."""
+    try:
+        names = [fo.te_names[i].decode() for i in range(fo.n_te_seqs)]
+        if vf.te_fasta_path is not None:
+            res.update(te_names=names, n_mei_lines=int(fo.n_mei_lines))
+        recs = res.get("records")
+        if recs is not None and vf.te_fasta_path is not None:
+            for r in recs:
+                r["te_name"] = names[r["te_seq_i"]] if r["te_seq_i"] >= 0 else None
+        if recs is not None and vf.rnames_mode:
+            assert fo.n_rnames == len(recs)
+            for i, r in enumerate(recs):
+                v = fo.rnames[i]
+                r["alt_read_names"] = None if v is None else [] if v == b"." else v.decode().split(",")
+    finally:
+        lib.lcd_vcf_fields_out_free(C.byref(fo))
+    return res
+
+
+def chunks_call(chunks, items, cfg=None, chrom="chr11", te_fasta=None, rnames=None):
     """lcd_chunks_call: DeviceChunks of one contig in genome order -> dict(chunks = per chunk the first-round dict with cv / state FINAL plus n_passes, flip_hap,
-    flip_pre_PS, flip_cur_PS, n_records, haps, phase_sets; records = genotype records as dicts in chunk order; vcf_body).  items as for chunks_first_round."""
+    flip_pre_PS, flip_cur_PS, n_records, haps, phase_sets; records = genotype records as dicts in chunk order; vcf_body).  items as for chunks_first_round.
+    te_fasta= (the -T file) / rnames=None|"sv"|"all": lcd_chunks_call_fields, see _fields_result for what the result gains."""
     from ._lib import LcdCallChunk, LcdVar1
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
@@ -1510,8 +1581,15 @@ def chunks_call(chunks, items, cfg=None, chrom="chr11"):
     for i, (ch, it) in enumerate(zip(chunks, items)):
         _fill_first_chunk(arr[i].first, ch, it, keep)
     recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
+    vf, fo = _vcf_fields(te_fasta, rnames)
+    if vf is not None:
+        check(lib.lcd_chunks_call_fields(n, arr, C.byref(cfg), chrom.encode(), C.byref(vf), C.byref(recs), C.byref(n_recs), C.byref(text), C.byref(fo)), lib)
+        return _fields_result(lib, _call_result(lib, n, arr, recs, n_recs, text), vf, fo)
     check(lib.lcd_chunks_call(n, arr, C.byref(cfg), chrom.encode(), C.byref(recs), C.byref(n_recs), C.byref(text)), lib)
     return _call_result(lib, n, arr, recs, n_recs, text)
+
+
+call_chunks = chunks_call
 
 
 def bgzf_deflate(data, block_payload=0, add_eof=1):
@@ -1536,12 +1614,14 @@ def bgzf_deflate(data, block_payload=0, add_eof=1):
         lib.lcd_deflated_free(h)
 
 
-def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None):
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
     bam_out = dict(path[, pg_line, block_payload]): lcd_call_bam_regions_out, the phased alignment file is written too; the result gets "bam_out" = the counters and
-    stage times of lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised)"""
+    stage times of lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
+    te_fasta= / rnames=: lcd_call_bam_regions_fields (as chunks_call)"""
     from ._lib import LcdBamOut, LcdCallChunk, LcdVar1
-    if bam_out is not None:
+    vf, fo = _vcf_fields(te_fasta, rnames)
+    if bam_out is not None or vf is not None:
         lib = load_library()
         cfg = cfg if cfg is not None else call_cfg()
         n = len(reg_beg)
@@ -1549,14 +1629,25 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
         rb = (C.c_int64 * max(1, n))(*[int(x) for x in reg_beg]); re_ = (C.c_int64 * max(1, n))(*[int(x) for x in reg_end])
         recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
         enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
-        bo = LcdBamOut(); bo.path = enc(bam_out["path"]); bo.pg_line = enc(bam_out["pg_line"]) if bam_out.get("pg_line") is not None else None
-        bo.block_payload = int(bam_out.get("block_payload", 0))
-        rc = lib.lcd_call_bam_regions_out(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
-                                          C.byref(text), C.byref(bo))
+        bo = None
+        if bam_out is not None:
+            bo = LcdBamOut(); bo.path = enc(bam_out["path"]); bo.pg_line = enc(bam_out["pg_line"]) if bam_out.get("pg_line") is not None else None
+            bo.block_payload = int(bam_out.get("block_payload", 0))
+        bop = C.byref(bo) if bo is not None else None
+        if vf is not None:
+            rc = lib.lcd_call_bam_regions_fields(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), C.byref(vf), arr, C.byref(recs),
+                                                 C.byref(n_recs), C.byref(text), bop, C.byref(fo))
+        else:
+            rc = lib.lcd_call_bam_regions_out(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
+                                              C.byref(text), bop)
         err = lib.lcd_last_error().decode() if rc < 0 else ""
         if rc < 0 and not text and not recs:
             raise LcdError(f"liblcd_hotpath error {rc}: {err}")
         res = _call_result(lib, n, arr, recs, n_recs, text)
+        if vf is not None:
+            res = _fields_result(lib, res, vf, fo)
+        if bo is None:
+            return res
         res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
                                                                                                    "ms_deflate", "ms_download_write")})
         return res
@@ -1674,12 +1765,14 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None):
     """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
     phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
     flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
     index (default None: lcd_call_file as it is): True, or a dict with build_missing_bai / build_missing_fai / write_out_bai / out_bai_path / slab_members ->
-    lcd_call_file_indexed; the result then has "index" = lcd_index_stats_t's fields (out_bai_skipped != 0: the output's index was not written, out_bai_skip_reason says why)"""
+    lcd_call_file_indexed; the result then has "index" = lcd_index_stats_t's fields (out_bai_skipped != 0: the output's index was not written, out_bai_skip_reason says why).
+    te_fasta= (the -T file) / rnames=None|"sv"|"all" (--out-sv-rnames / --out-var-rnames): lcd_call_file_fields / lcd_call_files_fields; the result gains "te_names" and
+    "n_mei_lines" (with a library) and the kept records "te_name" / "alt_read_names" (see _fields_result)"""
     from ._lib import LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
@@ -1715,7 +1808,13 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
         d = dict(build_missing_bai=1, build_missing_fai=1, write_out_bai=1 if bam_out is not None else 0) if index is True else dict(index)
         io = LcdIndexOpt(int(d.get("build_missing_bai", 0)), int(d.get("build_missing_fai", 0)), int(d.get("write_out_bai", 0)), opt_s(d.get("out_bai_path")), int(d.get("slab_members", 0)))
         ist = LcdIndexStats()
-    if _inputs is not None:
+    vf, fo = _vcf_fields(te_fasta, rnames)
+    iop, istp = (C.byref(io) if io is not None else None), (C.byref(ist) if ist is not None else None)
+    if vf is not None and _inputs is not None:
+        rc = lib.lcd_call_files_fields(C.byref(inp), C.byref(job), C.byref(cfg), iop, C.byref(vf), C.byref(st), istp, per_file, C.byref(fo))
+    elif vf is not None:
+        rc = lib.lcd_call_file_fields(C.byref(job), C.byref(cfg), iop, C.byref(vf), C.byref(st), istp, C.byref(fo))
+    elif _inputs is not None:
         rc = lib.lcd_call_files(C.byref(inp), C.byref(job), C.byref(cfg), C.byref(io) if io is not None else None, C.byref(st), C.byref(ist) if ist is not None else None, per_file)
     elif index:
         rc = lib.lcd_call_file_indexed(C.byref(job), C.byref(cfg), C.byref(io), C.byref(st), C.byref(ist))
@@ -1735,6 +1834,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["records"] = [_var1_dict(st.records[i]) for i in range(st.n_kept_records)]
         if bo is not None:
             res["bam_out"] = {k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag", "ms_deflate", "ms_download_write")}
+        if vf is not None:
+            res = _fields_result(lib, res, vf, fo)
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))

@@ -7,16 +7,18 @@ REFUSED = {
     "-s": "somatic / mosaic calling is not supported", "--mosaic": "somatic / mosaic calling is not supported", "--somatic": "somatic / mosaic calling is not supported",
     "--refine-aln": "--refine-aln is not supported", "-L": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE", "--input-is-list": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE",
     "-X": "-X/--extra-bam is not supported: give further input files with --add-bam FILE", "--extra-bam": "-X/--extra-bam is not supported: give further input files with --add-bam FILE",
-    "-T": "a transposable-element library (-T) is not supported", "--trans-elem": "a transposable-element library (-T) is not supported",
     "-S": "SAM output (-S) is not supported: use -b", "--out-sam": "SAM output (-S) is not supported: use -b", "--out-cram": "CRAM output (-C FILE) is not supported: use -b",
-    "--out-var-rnames": "--out-var-rnames is not supported", "--out-som-var-rnames": "--out-som-var-rnames is not supported", "--out-sv-rnames": "--out-sv-rnames is not supported",
+    "-T": "-T/--trans-elem is not supported: give the TE sequence file with --te-lib FILE", "--trans-elem": "-T/--trans-elem is not supported: give the TE sequence file with --te-lib FILE",
+    "--out-var-rnames": "--out-var-rnames is not supported: ask for the supporting read names of every record with --var-rnames",
+    "--out-sv-rnames": "--out-sv-rnames is not supported: ask for the supporting read names of SV records with --sv-rnames",
+    "--out-som-var-rnames": "--out-som-var-rnames is not supported: somatic / mosaic calling is not supported",
 }
-FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
-          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list"}
+          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli faidx ref.fa               build ref.fa.fai
@@ -26,10 +28,14 @@ Inputs:   one sample from several BAMs (one per SMRT cell / flow cell, same refe
           position (and lets --make-index write <out.bam>.bai)
 Input:    --hifi (default) | --ont   --region-file FILE   --autosome-XY (default) | --autosome | --all-ctg   -E/--exclude-ctg STR (repeatable)   -r/--ref-idx FILE
 Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z   -l/--min-sv-len INT   -H/--no-vcf-header   --amb-base   -b/--out-bam FILE
+          --te-lib FILE   TE sequences (FASTA, plain or gzip; the reference's -T): SVs that look like their insertion get MEI and REPNAME=
+          --var-rnames | --sv-rnames   the supporting read names of every record | of SV records as the FORMAT field ALTREADS (the reference's --out-var-rnames /
+          --out-sv-rnames; --var-rnames wins)
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
 Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
-Not supported (refused with exit status 2): -s, --refine-aln, -L (use --bam-list), -X (use --add-bam), -T, -S, -C FILE, --out-*-rnames
+Not supported (refused with exit status 2): -s, --refine-aln, -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S, -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
+          --out-som-var-rnames
 """
 
 
@@ -71,6 +77,12 @@ def parse(argv):
             return refuse(f"unknown option {a}")
         pos.append(a)
     return o, pos
+
+
+def vcf_fields(o):
+    """--te-lib FILE / --var-rnames / --sv-rnames -> the keywords te_fasta= / rnames= of align.call_file (the reference's `output_var_rnames || (is_sv &&
+    output_sv_rnames)`, src/vcf_utils.c:208: --var-rnames wins)"""
+    return dict(te_fasta=o.get("te_lib"), rnames="all" if "--var-rnames" in o["flags"] else "sv" if "--sv-rnames" in o["flags"] else None)
 
 
 def input_bams(o, bam):
@@ -173,7 +185,7 @@ def main(argv=None):
                              window_chunks=num.get("window_chunks", 0), overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0),
                              min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
-                             index=True if "--make-index" in o["flags"] else None)
+                             index=True if "--make-index" in o["flags"] else None, **vcf_fields(o))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
@@ -183,7 +195,7 @@ def main(argv=None):
         sys.stderr.write("longcalld_amd call: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
     per_file = f" ({' + '.join(str(x) for x in st['n_reads_per_file'])} from the {len(bams)} input files)" if len(bams) > 1 else ""
     sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads{per_file}, {st['n_vcf_lines']} VCF lines, "
-                     f"{st['ms_wall'] / 1000:.2f} s\n")
+                     + (f"{st['n_mei_lines']} MEI records, " if "n_mei_lines" in st else "") + f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 
 

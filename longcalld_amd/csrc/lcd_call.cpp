@@ -21,14 +21,58 @@ void lcd_call_free(int n, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_r
 }
 
 int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body) {
-    return chunks_call_core(n, chunks, cfg, chrom, nullptr, records, n_records, vcf_body);
+    return lcd_chunks_call_fields(n, chunks, cfg, chrom, nullptr, records, n_records, vcf_body, nullptr);
+}
+int lcd_chunks_call_fields(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const lcd_vcf_fields_t *fields, lcd_var1_t **records, int *n_records,
+                           char **vcf_body, lcd_vcf_fields_out_t *fields_out) {
+    if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
+    FieldsRun fr; fr.collect_rnames = fields_out != nullptr;
+    if (int rc = fr.open(fields, "lcd_chunks_call")) { if (records) *records = nullptr; if (n_records) *n_records = 0; if (vcf_body) *vcf_body = nullptr; return rc; }
+    const int rc = chunks_call_core(n, chunks, cfg, chrom, nullptr, &fr, records, n_records, vcf_body);
+    if (!rc) fr.give(fields_out);
+    return rc;
+}
+
+void lcd_vcf_fields_out_free(lcd_vcf_fields_out_t *o) {
+    if (!o) return;
+    for (int i = 0; o->te_names && i < o->n_te_seqs; ++i) free(o->te_names[i]);
+    for (int i = 0; o->rnames && i < o->n_rnames; ++i) free(o->rnames[i]);
+    free(o->te_names); free(o->rnames);
+    memset(o, 0, sizeof(*o));
 }
 
 } // extern "C"
 
+int lcd_internal::FieldsRun::open(const lcd_vcf_fields_t *f, const std::string &W) {
+    if (!f) return 0;
+    if (f->rnames_mode < LCD_RNAMES_NONE || f->rnames_mode > LCD_RNAMES_ALL) return set_err(-4, W + ": rnames_mode must be 0 (none), 1 (SV records) or 2 (all records)");
+    if (f->te_kmer_len < 0 || f->te_kmer_len > 15) return set_err(-4, W + ": te_kmer_len must be 0 (15) or 1 ... 15");
+    rnames_mode = f->rnames_mode;
+    if (!f->te_fasta_path) return 0;
+    return lcd_te_lib_from_fasta(f->te_fasta_path, f->te_kmer_len, &lib, &te_names, nullptr, &n_te);
+}
+void lcd_internal::FieldsRun::give(lcd_vcf_fields_out_t *out) {
+    if (!out) return;
+    out->n_te_seqs = n_te; out->te_names = te_names; te_names = nullptr;
+    out->n_mei_lines = n_mei;
+    if (collect_rnames && rnames_mode) {
+        out->n_rnames = (int)rnames.size();
+        out->rnames = (char **)malloc((rnames.size() + 1) * sizeof(char *));
+        if (!rnames.empty()) memcpy(out->rnames, rnames.data(), rnames.size() * sizeof(char *));
+        rnames.clear();
+    }
+}
+lcd_internal::FieldsRun::~FieldsRun() {
+    for (char *p : rnames) free(p);
+    for (int i = 0; te_names && i < n_te; ++i) free(te_names[i]);
+    free(te_names);
+    lcd_te_lib_destroy(lib);
+}
+
 // the body of lcd_chunks_call.  links == NULL: n chunks of the one contig `chrom`.  With links (lcd_call_file's window): a contig name and tid per chunk, the first
 // chunk's up list against the carried region, the last chunk's down list against the next planned region, the stitch carried in and out
-int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, lcd_var1_t **records, int *n_records, char **vcf_body) {
+int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, FieldsRun *fields, lcd_var1_t **records,
+                                   int *n_records, char **vcf_body) {
     const std::string W = "lcd_chunks_call";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
@@ -108,7 +152,7 @@ int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cf
             lcd_free_variants(tmp, (int)all.size());
             return fail(set_err(m, W + ": lcd_make_variants failed on chunk " + std::to_string(c)));
         }
-        if (m > 0) lcd_annotate_te(&cfg->call, &te, nullptr, (const char *)x.ref_seq, x.ref_beg, x.ref_end, recs, m);
+        if (m > 0) lcd_annotate_te(&cfg->call, &te, fields ? fields->lib : nullptr, (const char *)x.ref_seq, x.ref_beg, x.ref_end, recs, m);
         for (int i = 0; i < m; ++i) all.push_back(recs[i]);
         free(recs);                                            // (the members moved into `all`)
         chunks[c].n_records = m;
@@ -116,7 +160,30 @@ int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cf
     lcd_var1_t *out = (lcd_var1_t *)malloc((all.size() + 1) * sizeof(lcd_var1_t));
     if (!all.empty()) memcpy(out, all.data(), all.size() * sizeof(lcd_var1_t));
     char *text = nullptr;
-    if (!links) {
+    if (fields && fields->active()) {   // MEI / REPNAME from the library's names; ALTREADS: every chunk's records against that chunk's own read names
+        std::string t; size_t at = 0; const size_t rn0 = fields->rnames.size();
+        auto drop = [&](int code) { const std::string m = g_err; for (size_t i = rn0; i < fields->rnames.size(); ++i) free(fields->rnames[i]); fields->rnames.resize(rn0); lcd_free_variants(out, (int)all.size()); g_err = m; return fail(code); };
+        int64_t n_mei = 0;
+        for (int c = 0; c < n; ++c) {
+            const int m = chunks[c].n_records; const lcd_bam_reads_t *meta = chunks[c].first.meta;
+            if (m > 0 && fields->rnames_mode && (!meta || (meta->n_reads > 0 && (!meta->name_off || !meta->name_pool))))
+                return drop(set_err(-4, W + ": read names are wanted and chunk " + std::to_string(c) + " has no name table (first.meta with name_off / name_pool)"));
+            char *one = nullptr; int mei = 0;
+            const int nl = lcd_format_vcf_fields(&cfg->call, links ? links->chroms[c] : chrom, out + at, m, fields->te_names, fields->rnames_mode, meta ? meta->n_reads : 0,
+                                                 meta ? meta->name_off : nullptr, meta ? meta->name_pool : nullptr, &one, &mei);
+            if (nl < 0) return drop(nl);
+            if (one) t += one;
+            free(one); n_mei += mei;
+            for (int i = 0; fields->collect_rnames && fields->rnames_mode && i < m; ++i) {
+                const lcd_var1_t &v = out[at + (size_t)i]; char *s = nullptr;
+                if ((fields->rnames_mode == LCD_RNAMES_ALL || v.is_sv) && lcd_alt_read_names(&v, meta->n_reads, meta->name_off, meta->name_pool, &s)) return drop(-4);
+                fields->rnames.push_back(s);
+            }
+            at += (size_t)m;
+        }
+        fields->n_mei += n_mei;
+        text = (char *)malloc(t.size() + 1); memcpy(text, t.c_str(), t.size() + 1);
+    } else if (!links) {
         const int nl = lcd_format_vcf(&cfg->call, chrom, out, (int)all.size(), &text);
         if (nl < 0) { lcd_free_variants(out, (int)all.size()); return fail(nl); }
     } else {   // the lines of every chunk under its own contig name
@@ -323,15 +390,24 @@ int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char 
 
 int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
                              int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out) {
+    return lcd_call_bam_regions_fields(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, nullptr, chunks, records, n_records, vcf_body, bam_out, nullptr);
+}
+
+int lcd_call_bam_regions_fields(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                                int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                                lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out) {
     const std::string W = "lcd_call_bam_regions";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (vcf_body) *vcf_body = nullptr;
+    if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
     if (!bam_path || !bai_path || !fasta_path || !chrom || !cfg || !records || !n_records || !vcf_body) return set_err(-4, W + ": NULL argument");
     if (bam_out && !bam_out->path) return set_err(-4, W + ": bam_out without a path");
     if (n < 0 || (n > 0 && (!reg_beg || !reg_end || !chunks))) return set_err(-4, W + ": bad region list");
     for (int c = 0; c < n; ++c) if (reg_beg[c] < 1 || reg_end[c] < reg_beg[c] || (c > 0 && reg_beg[c] <= reg_end[c - 1])) return set_err(-4, W + ": regions must be 1-based, non-empty and in genome order");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
+    FieldsRun fr; fr.collect_rnames = fields_out != nullptr;
+    if (int rc0 = fr.open(fields, W)) return rc0;
     const int is_ont = cfg->clean.is_ont != 0;
     lcd_digar_opt_t dopt; lcd_digar_opt_default(&dopt, is_ont);
     std::vector<lcd_chunk_t *> handles(n, nullptr); std::vector<uint8_t *> refs(n, nullptr); std::vector<lcd_bam_reads_t> metas(n);
@@ -367,7 +443,8 @@ int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const c
         x.chunk = handles[c]; x.ref_seq = refs[c]; x.ref_beg = b0 + 1; x.ref_end = b0 + got; x.reg_beg = reg_beg[c]; x.reg_end = reg_end[c]; x.is_ont = is_ont;
         x.ordered_read_ids = nullptr; x.is_rev = nullptr; x.meta = &metas[c];
     }
-    int rc = lcd_chunks_call(n, chunks, cfg, chrom, records, n_records, vcf_body);
+    int rc = chunks_call_core(n, chunks, cfg, chrom, nullptr, &fr, records, n_records, vcf_body);
+    if (rc == 0) fr.give(fields_out);
     if (rc == 0 && bam_out) rc = lcd_write_phased_bam(bam_path, n, chunks, bam_out);   // (a failure here leaves the records and the text valid)
     const std::string m = g_err;
     drop_inputs();

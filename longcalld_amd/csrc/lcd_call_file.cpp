@@ -299,6 +299,7 @@ struct Run {
     lcd_stitch_carry_t carry;
     lcd_vcf_writer_t *vcf = nullptr; lcd_bam_writer_t *bam = nullptr;
     std::vector<lcd_var1_t> kept;          // keep_records
+    FieldsRun *fields = nullptr;           // the TE library and the names mode of the call (read-only here; its counters belong to the call stage)
     // the first error of any stage
     std::mutex err_mu; int err_code = 0; std::string err_msg; std::atomic<bool> failed{false};
     std::atomic<long long> peak{0};
@@ -358,7 +359,7 @@ struct Run {
         CallLinks links; links.chroms = w.chroms.data(); links.tids = w.tids.data(); links.carry_in = &carry; links.carry_out = &carry;
         const int nx = w.first + w.n;
         links.next_tid = nx < plan.n ? plan.tid[nx] : -1; links.next_beg = nx < plan.n ? plan.reg_beg[nx] : 0; links.next_end = nx < plan.n ? plan.reg_end[nx] : 0;
-        const int rc = chunks_call_core(w.n, w.chunks.data(), cfg, nullptr, &links, &w.records, &w.n_records, &w.text);
+        const int rc = chunks_call_core(w.n, w.chunks.data(), cfg, nullptr, &links, fields, &w.records, &w.n_records, &w.text);
         sample_peak();
         if (rc) { fail(rc, g_err); return rc; }
         w.called = true;
@@ -393,9 +394,10 @@ struct Run {
 
 namespace {
 // the whole-file run over the n input files of one sample; in == NULL: the one file of the job (lcd_call_file / lcd_call_file_indexed)
-int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
-                    lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file) {
+int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
+                    lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out) {
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
     lcd_index_stats_t ist_local;
     lcd_index_stats_t *ist = idx_stats ? idx_stats : &ist_local;
     memset(ist, 0, sizeof(*ist));
@@ -412,7 +414,9 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
     if (job->window_chunks < 0 || job->loader_threads < 0 || job->chunk_len < 0 || job->overlap < -1 || job->overlap > 1) return set_err(-4, W + ": negative window_chunks / loader_threads / chunk_len, or overlap outside -1 ... 1");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
     const double t_wall = now_ms();
-    Run R; R.job = job; R.cfg = cfg; R.st = stats;
+    FieldsRun fr; fr.collect_rnames = fields_out != nullptr && job->keep_records;
+    if (int rc = fr.open(fields, W)) return rc;     // (an unreadable TE file: before an index is built or an output file is created)
+    Run R; R.job = job; R.cfg = cfg; R.st = stats; R.fields = &fr;
     memset(&R.plan, 0, sizeof(R.plan)); memset(&R.carry, 0, sizeof(R.carry));
     const int n_in = in ? in->n : 1;
     for (int f = 0; f < n_in; ++f) {
@@ -555,6 +559,7 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
     if (job->keep_records) {
         stats->records = dup_vec(R.kept); stats->n_kept_records = (int)R.kept.size();
     }
+    if (!rc) fr.give(fields_out);
     stats->peak_device_bytes = R.peak.load();
     if (n_reads_per_file) for (int f = 0; f < n_in; ++f) n_reads_per_file[f] = R.reads_per_file[f];
     stats->ms_wall = now_ms() - t_wall;
@@ -565,11 +570,21 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
 extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats) { return lcd_call_file_indexed(job, cfg, nullptr, stats, nullptr); }
 
 extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats) {
-    return call_files_core(idx ? "lcd_call_file_indexed" : "lcd_call_file", nullptr, job, cfg, idx, stats, idx_stats, nullptr);
+    return lcd_call_file_fields(job, cfg, idx, nullptr, stats, idx_stats, nullptr);
+}
+
+extern "C" int lcd_call_file_fields(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields, lcd_file_stats_t *stats,
+                                    lcd_index_stats_t *idx_stats, lcd_vcf_fields_out_t *fields_out) {
+    return call_files_core(idx ? "lcd_call_file_indexed" : "lcd_call_file", nullptr, job, cfg, idx, fields, stats, idx_stats, nullptr, fields_out);
 }
 
 extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
                               lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file) {
-    if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); return set_err(-4, "lcd_call_files: NULL argument"); }
-    return call_files_core("lcd_call_files", in, job, cfg, idx, stats, idx_stats, n_reads_per_file);
+    return lcd_call_files_fields(in, job, cfg, idx, nullptr, stats, idx_stats, n_reads_per_file, nullptr);
+}
+
+extern "C" int lcd_call_files_fields(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
+                                     lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out) {
+    if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); if (fields_out) memset(fields_out, 0, sizeof(*fields_out)); return set_err(-4, "lcd_call_files: NULL argument"); }
+    return call_files_core("lcd_call_files", in, job, cfg, idx, fields, stats, idx_stats, n_reads_per_file, fields_out);
 }

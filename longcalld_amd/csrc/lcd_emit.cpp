@@ -2,7 +2,9 @@
 // (flip_variant_hap, src/collect_var.c:1618-1680), genotype records (make_variants :1465-1601, cal_sample_GQ :1435, cal_var_QUAL1 :1455), the VCF body
 // lines (write_var_to_vcf, src/vcf_utils.c:97-268) and the HP / PS tag policy (src/bam_utils.c:1955-2006).  Host code, as in the reference: serial,
 // tens of microseconds per chunk; it lives here so that a caller of the library gets from K5 + noisy-region variants to VCF text without the reference's
-// htslib-typed structs.  Germline fields only (somatic mode a20 is out of scope); the retrotransposon annotation of SV-size gaps (a14) is at the end of the file.
+// htslib-typed structs.  Germline fields only (somatic mode a20 is out of scope); the retrotransposon annotation of SV-size gaps (a14) is at the end of the file,
+// with the reader of the -T file (lcd_te_lib_from_fasta); lcd_format_vcf_fields adds the supporting read names (ALTREADS).  No HIP call or header in this file: a
+// stand-alone program can compile it with the host compiler and its sanitizers (tests/c/vcf_fields_sanitize.cpp).
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -11,6 +13,7 @@
 #include <string>
 #include <unordered_set>
 #include <vector>
+#include <zlib.h>
 #include "../../include/lcd_hotpath.h"
 
 namespace {
@@ -191,9 +194,33 @@ void lcd_free_variants(lcd_var1_t *vars, int n) {
     free(vars);
 }
 
-int lcd_format_vcf(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n, char **text_out) { return lcd_format_vcf_te(opt, chrom, vars, n, nullptr, text_out); }
-int lcd_format_vcf_te(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n, const char *const *te_names, char **text_out) {
-    std::string t; int n_out = 0; char num[64];
+} // extern "C"
+
+// defined in lcd_bai.cpp (sets lcd_last_error's string); absent from a stand-alone program
+extern "C" __attribute__((weak)) void lcd_index_set_last_error(const char *m);
+
+namespace {
+int emit_err(int code, const std::string &m) { if (lcd_index_set_last_error) lcd_index_set_last_error(m.c_str()); return code; }
+
+// the ALTREADS value of one record (src/vcf_utils.c:243-252): the names of alt_read_i[0 .. AD[1]) joined by ',', "." without one; false for an index outside the table
+bool alt_read_names(const lcd_var1_t &v, int n_reads, const uint64_t *name_off, const char *name_pool, std::string &out) {
+    out.clear();
+    if (v.AD[1] <= 0) { out = "."; return true; }
+    if (!v.alt_read_i || v.AD[1] > v.n_alt_reads) return false;
+    for (int i = 0; i < v.AD[1]; ++i) {
+        const int r = v.alt_read_i[i];
+        if (r < 0 || r >= n_reads) return false;
+        if (i) out += ',';
+        out += name_pool + name_off[r];
+    }
+    return true;
+}
+
+// write_var_to_vcf (src/vcf_utils.c:97-268), germline fields; rnames_mode 0: no ALTREADS (the two formatters without names)
+int format_vcf_core(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n, const char *const *te_names, int rnames_mode, int n_reads,
+                    const uint64_t *name_off, const char *name_pool, char **text_out, int *n_mei) {
+    std::string t, names; int n_out = 0; char num[64];
+    if (n_mei) *n_mei = 0;
     for (int i = 0; i < n; ++i) {
         const lcd_var1_t &v = vars[i];
         if (v.n_alt_allele == 0 || v.DP < opt->min_dp || v.AD[1] < opt->min_alt_dp) continue;
@@ -225,13 +252,19 @@ int lcd_format_vcf_te(const lcd_call_opt_t *opt, const char *chrom, const lcd_va
         t += '\t';
         int g1 = v.GT[0], g2 = v.GT[1]; const bool hom = g1 == g2; char sep = '|';
         if (v.PS == 0) { sep = '/'; if (g1 > g2) std::swap(g1, g2); }
+        const bool rnames = rnames_mode == 2 || (rnames_mode == 1 && v.is_sv); // :208
+        if (rnames && !alt_read_names(v, n_reads, name_off, name_pool, names))
+            return emit_err(-4, "lcd_format_vcf_fields: record " + std::to_string(i) + " names a read outside the " + std::to_string(n_reads) + " reads of its chunk");
+        if (n_mei && v.te_seq_i >= 0 && te_names) ++*n_mei;
         t += "GT:DP:AD:VAF:GQ";
         if (!hom && v.PS != 0) t += ":PS";
+        if (rnames) t += ":ALTREADS";
         t += '\t'; t += std::to_string(g1); t += sep; t += std::to_string(g2); t += ':'; t += std::to_string(v.DP); t += ':';
         for (int a = 0; a < 1 + v.n_alt_allele; ++a) { if (a) t += ','; t += std::to_string(v.AD[a]); }
         for (int a = 0; a < v.n_alt_allele; ++a) { t += a ? ',' : ':'; snprintf(num, sizeof(num), "%.3f", (float)v.AD[a + 1] / v.DP); t += num; }
         t += ':'; t += std::to_string(v.GQ);
         if (!hom && v.PS != 0) { t += ':'; t += std::to_string((long long)v.PS); }
+        if (rnames) { t += ':'; t += names; }
         t += '\n'; ++n_out;
     }
     char *o = (char *)malloc(t.size() + 1);
@@ -239,6 +272,32 @@ int lcd_format_vcf_te(const lcd_call_opt_t *opt, const char *chrom, const lcd_va
     *text_out = o;
     return n_out;
 }
+} // namespace
+
+extern "C" {
+
+int lcd_format_vcf(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n, char **text_out) { return lcd_format_vcf_te(opt, chrom, vars, n, nullptr, text_out); }
+int lcd_format_vcf_te(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n, const char *const *te_names, char **text_out) {
+    return format_vcf_core(opt, chrom, vars, n, te_names, 0, 0, nullptr, nullptr, text_out, nullptr);
+}
+int lcd_format_vcf_fields(const lcd_call_opt_t *opt, const char *chrom, const lcd_var1_t *vars, int n, const char *const *te_names, int rnames_mode, int n_reads,
+                          const uint64_t *name_off, const char *name_pool, char **text_out, int *n_mei) {
+    if (text_out) *text_out = nullptr;
+    if (n_mei) *n_mei = 0;
+    if (!opt || !chrom || !text_out || n < 0 || (n > 0 && !vars)) return emit_err(-4, "lcd_format_vcf_fields: NULL argument");
+    if (rnames_mode < 0 || rnames_mode > 2) return emit_err(-4, "lcd_format_vcf_fields: rnames_mode must be 0 (none), 1 (SV records) or 2 (all records)");
+    if (rnames_mode && (n_reads < 0 || (n_reads > 0 && (!name_off || !name_pool)))) return emit_err(-4, "lcd_format_vcf_fields: read names are wanted and the chunk's name table is missing");
+    return format_vcf_core(opt, chrom, vars, n, te_names, rnames_mode, n_reads, name_off, name_pool, text_out, n_mei);
+}
+int lcd_alt_read_names(const lcd_var1_t *var, int n_reads, const uint64_t *name_off, const char *name_pool, char **out) {
+    if (out) *out = nullptr;
+    if (!var || !out || n_reads < 0 || (n_reads > 0 && (!name_off || !name_pool))) return emit_err(-4, "lcd_alt_read_names: NULL argument");
+    std::string s;
+    if (!alt_read_names(*var, n_reads, name_off, name_pool, s)) return emit_err(-4, "lcd_alt_read_names: the record names a read outside the " + std::to_string(n_reads) + " reads of its chunk");
+    *out = (char *)malloc(s.size() + 1); memcpy(*out, s.c_str(), s.size() + 1);
+    return 0;
+}
+
 
 // ---- update_digars_from_msa1 (src/align.c:1701-1743) ----
 // A read's digar list is rebuilt around one noisy region from its ref<->read alignment string: the old digars left of the region
@@ -369,6 +428,91 @@ lcd_te_lib_t *lcd_te_lib_create(int n_seqs, const char *const *seqs, const int *
 }
 void lcd_te_lib_destroy(lcd_te_lib_t *lib) { delete lib; }
 int lcd_te_lib_n_seqs(const lcd_te_lib_t *lib) { return lib ? (int)lib->fwd.size() : 0; }
+
+// make_te_kmer_idx's file reading (src/kmer.c:120-148): every record of a plain or gzip-compressed FASTA / FASTQ file as kseq_read (src/kseq.h:175-215) yields it.
+//   header   the scan for the first record stops at '>' or '@'; the name ends at the first isspace() byte, the rest of the line is the comment;
+//   sequence lines up to one that STARTS with '>', '@' (the next record) or '+' (FASTQ qualities); empty lines are skipped; after each line a trailing '\r' is
+//            dropped while the sequence holds more than one byte (ks_getuntil2's KS_SEP_LINE rule, :140, applied to the accumulated string) -- not after a
+//            line that found the file already at its end;
+//   '+'      the rest of that line is skipped, quality lines are read until they hold as many bytes as the sequence; a missing or shorter quality string ends
+//            the file's records there (kseq_read returns -2 and make_te_kmer_idx's loop stops).
+namespace {
+struct TeRec { std::string name, seq; };
+void kseq_records(const std::vector<char> &buf, std::vector<TeRec> &out) {
+    const size_t n = buf.size(); size_t pos = 0; int last_char = 0;
+    auto is_space = [](char c) { return c == ' ' || c == '\t' || c == '\n' || c == '\v' || c == '\f' || c == '\r'; };
+    // ks_getuntil2(KS_SEP_LINE, append): false when the stream was already at its end (nothing read, no '\r' rule)
+    auto rest_of_line = [&](std::string &str) {
+        if (pos >= n) return false;
+        size_t e = pos; while (e < n && buf[e] != '\n') ++e;
+        str.append(buf.data() + pos, e - pos); pos = e < n ? e + 1 : n;
+        if (str.size() > 1 && str.back() == '\r') str.pop_back();
+        return true;
+    };
+    for (;;) {
+        if (last_char == 0) {
+            while (pos < n && buf[pos] != '>' && buf[pos] != '@') ++pos;
+            if (pos >= n) return;
+            last_char = buf[pos++];
+        }
+        if (pos >= n) return;
+        TeRec r; int c = 0;
+        { size_t e = pos; while (e < n && !is_space(buf[e])) ++e; r.name.assign(buf.data() + pos, e - pos); if (e < n) { c = buf[e]; pos = e + 1; } else pos = n; }
+        if (c != '\n') { std::string comment; rest_of_line(comment); }
+        c = -1;
+        while (pos < n) {
+            c = (unsigned char)buf[pos++];
+            if (c == '>' || c == '+' || c == '@') break;
+            if (c != '\n') { r.seq += (char)c; rest_of_line(r.seq); }
+            c = -1;
+        }
+        if (c == '>' || c == '@') last_char = c;
+        if (c == '+') {
+            while (pos < n && buf[pos] != '\n') ++pos;
+            if (pos >= n) return;                       // no quality string
+            ++pos;
+            std::string qual;
+            while (rest_of_line(qual) && qual.size() < r.seq.size()) {}
+            last_char = 0;
+            if (qual.size() != r.seq.size()) return;    // truncated quality string
+        }
+        out.push_back(std::move(r));
+    }
+}
+} // namespace
+
+int lcd_te_lib_from_fasta(const char *path, int kmer_len, lcd_te_lib_t **lib, char ***names, int **seq_lens, int *n_seqs) {
+    const std::string W = "lcd_te_lib_from_fasta";
+    if (lib) *lib = nullptr;
+    if (names) *names = nullptr;
+    if (seq_lens) *seq_lens = nullptr;
+    if (n_seqs) *n_seqs = 0;
+    if (!path || !lib || !names || !n_seqs) return emit_err(-4, W + ": NULL argument");
+    if (kmer_len == 0) kmer_len = 15;                   // src/call_var_main.c:215
+    if (kmer_len < 1 || kmer_len > 15) return emit_err(-4, W + ": kmer_len must be 1 ... 15 (0: 15)");
+    gzFile f = gzopen(path, "r");
+    if (!f) return emit_err(-30, W + ": cannot open the TE sequence file " + path);
+    std::vector<char> buf; char tmp[1 << 16]; int got;
+    while ((got = gzread(f, tmp, sizeof(tmp))) > 0) buf.insert(buf.end(), tmp, tmp + got);
+    gzclose(f);
+    if (got < 0) return emit_err(-30, W + ": read error on the TE sequence file " + path);
+    std::vector<TeRec> recs;
+    kseq_records(buf, recs);
+    std::vector<const char *> sp; std::vector<int> sl;
+    for (const TeRec &r : recs) { sp.push_back(r.seq.data()); sl.push_back((int)r.seq.size()); }
+    lcd_te_lib_t *L = lcd_te_lib_create((int)recs.size(), sp.data(), sl.data(), kmer_len);
+    if (!L) return emit_err(-4, W + ": lcd_te_lib_create failed");
+    char **nm = (char **)malloc((recs.size() + 1) * sizeof(char *));
+    for (size_t i = 0; i < recs.size(); ++i) { nm[i] = (char *)malloc(recs[i].name.size() + 1); memcpy(nm[i], recs[i].name.c_str(), recs[i].name.size() + 1); }
+    if (seq_lens) { *seq_lens = (int *)malloc((recs.size() + 1) * sizeof(int)); if (!sl.empty()) memcpy(*seq_lens, sl.data(), sl.size() * sizeof(int)); }
+    *lib = L; *names = nm; *n_seqs = (int)recs.size();
+    return 0;
+}
+void lcd_te_lib_from_fasta_free(lcd_te_lib_t *lib, char **names, int *seq_lens, int n_seqs) {
+    lcd_te_lib_destroy(lib);
+    for (int i = 0; names && i < n_seqs; ++i) free(names[i]);
+    free(names); free(seq_lens);
+}
 
 int lcd_check_te_seq(const lcd_te_lib_t *lib, const uint8_t *seq, int len, int *is_rev) {
     if (!lib) return -1;

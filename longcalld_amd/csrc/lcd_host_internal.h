@@ -174,7 +174,19 @@ void pre_regs_merge(std::vector<NIv> &v, const int64_t *low_comp, int n_low);
 
 // lcd_call_file's links of a window of chunks to what lies outside it (lcd_call.cpp: chunks_call_core)
 struct CallLinks { const char *const *chroms; const int *tids; const lcd_stitch_carry_t *carry_in; lcd_stitch_carry_t *carry_out; int next_tid; int64_t next_beg, next_end; };
-int chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, lcd_var1_t **records, int *n_records, char **vcf_body);
+// the VCF options of one driver call (lcd_vcf_fields_t), resolved once: the TE library and its names, the names mode; and what the call gives back
+// (lcd_vcf_fields_out_t).  The library is read-only after open(); n_mei / rnames are written by the one thread that runs chunks_call_core
+struct FieldsRun {
+    lcd_te_lib_t *lib = nullptr; char **te_names = nullptr; int n_te = 0, rnames_mode = 0;
+    bool collect_rnames = false; int64_t n_mei = 0; std::vector<char *> rnames;
+    int open(const lcd_vcf_fields_t *f, const std::string &W);       // before any output file is created
+    void give(lcd_vcf_fields_out_t *out);                            // moves the names and the collected values into *out (NULL: nothing)
+    bool active() const { return lib || rnames_mode; }
+    ~FieldsRun();
+    FieldsRun() = default; FieldsRun(const FieldsRun &) = delete; FieldsRun &operator=(const FieldsRun &) = delete;
+};
+int chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, FieldsRun *fields, lcd_var1_t **records, int *n_records,
+                     char **vcf_body);
 
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
