@@ -13,6 +13,7 @@
 #include <array>
 #include <cfloat>
 #include <cmath>
+#include <functional>
 #include <numeric>
 #include <map>
 #include "lcd_host_internal.h"
@@ -550,7 +551,7 @@ static int cert_next_level(const PoaChain &) { return 0; }
 // 3 ms x 8 threads this took)
 struct ChainEnv {
     int cert_mode, solo_len, cert_sys, solo_mw, solo_cyc, cell_shrink, ring16; long long solo_rl;
-    long long n_chains = 1ll << 40, solo_cyc_min; // (chains in the submission at hand: run_many_once sets it)
+    long long n_chains = 1ll << 40, solo_cyc_min; // (chains in the submission at hand: Submission sets it)
     ChainEnv() {
         ring16 = getenv("LCD_RING16") ? atoi(getenv("LCD_RING16")) : 1; // (0: 32-bit rings; 2: test switch -- 16-bit pools whatever the bounds below say, so that the kernel's own range guard is what sends a read to the generic rows)
         solo_cyc_min = getenv("LCD_SOLO_CYC_MIN") ? atoll(getenv("LCD_SOLO_CYC_MIN")) : 16000;
@@ -773,6 +774,24 @@ static void chain_class(PoaChain &pc, bool noisy) {
 }
 static int chain_threads(const PoaChain &pc) { return pc.threads; }
 static long long chain_group_key(const PoaChain &pc) { return (long long)pc.threads * (1 << 20) + pc.lds_words; }
+// Chains of one launch group that share a CU: 160 KiB of LDS over the chain's pool plus what a workgroup takes besides it, and 16 wavefronts at 128 VGPRs.
+// The overhead exists with TWO sets of constants, and they are kept apart on purpose: the scheduling estimates (launch groups, LCD_PROFILE_CHAINS) say 1 KiB
+// for the single-wavefront class and 6 KiB for the wider ones, the arena slots' count says 912 B and 6 096 B.  They decide launch groups and slot counts, so
+// making them equal would change behaviour; nobody has measured which pair is right.
+struct LdsOverhead { int wave64, wider; };
+static constexpr LdsOverhead kSchedOverhead{1 * 1024, 6 * 1024}, kSlotOverhead{912, 6096};
+static int chains_per_cu(const int lds, const int thr, const LdsOverhead &besides) { return std::max(1, std::min((160 * 1024) / (lds + (thr == 64 ? besides.wave64 : besides.wider)), 1024 / thr)); }
+// The retry policy of the POA rounds, shared by a submission and lcd_poa_batch.  chain_goes_back: does a chain with this status run again in the next round?  A
+// chain that ran out of DP cells, nodes or edges does, with larger capacities; a chain whose certified band outgrew its window does too, demoted
+// (cert_next_level) and with the round remembered.  Anything else that is not LCD_OK is the caller's error.
+static bool chain_goes_back(const int status, const PoaChain &pc, ChainRec &CR, const int round) {
+    if (status == LCD_ERR_CELLS || status == LCD_ERR_NODES || status == LCD_ERR_EDGES) return true;
+    if (status != LCD_ERR_CERT || pc.cert <= 0) return false;
+    CR.cert_fail_round = round; CR.cert_level = cert_next_level(pc); // one class up (512, 1 024 columns), then full rows
+    return true;
+}
+// ... and the capacity scale it restarts with (`scale` doubles per round with retries): a chain sent back by the certified band starts its capacity ladder in the round after
+static int retry_scale(const ChainRec &CR, const int scale) { return CR.cert_fail_round < 0 ? scale : std::max(1, scale >> (CR.cert_fail_round + 1)); }
 // uploads `sub` (already ordered so that equal classes are contiguous) and launches one kernel per class
 // (different classes go to side streams so a long wide chain does not hold back the narrow ones)
 static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_t sub_n, DevBuf &d_chains, const PoaRead *d_reads, DevBuf &d_outs, LcdScoring sc,
@@ -821,11 +840,7 @@ static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_
         static const double k1w = getenv("LCD_NOISY_K1_WEIGHT") ? atof(getenv("LCD_NOISY_K1_WEIGHT")) : 3.0;
         static const double k1w_from = getenv("LCD_NOISY_K1_FROM") ? atof(getenv("LCD_NOISY_K1_FROM")) : 150000.0; // read-bases (reads x longest read)
         while (j < sub.size() && chain_group_key(sub[j]) == key) { const double t = (double)sub[j].n_reads * (sub[j].max_len + 64); cost += t; tail = std::max(tail, t * (noisy && sub[j].mode == 0 && t >= k1w_from ? k1w : 1.0)); ++j; } // (the weight on a group's LONGEST chain only, and only on chains of SV-shape size: weighting the ONT shape's K1 groups -- many short chains -- as well moved that shape from 18.5 to 16.9 - 17.5 k regions/s)
-        {
-            const int lds = sub[i].lds_words * 4, thr = sub[i].threads;
-            const int per_cu = std::max(1, std::min((160 * 1024) / (lds + (thr == 64 ? 1 : 6) * 1024), 1024 / thr));
-            cost /= per_cu;
-        }
+        cost /= chains_per_cu(sub[i].lds_words * 4, sub[i].threads, kSchedOverhead);
         grps.push_back({i, j, cost, tail});
         i = j;
     }
@@ -869,14 +884,21 @@ static int launch_poa_grouped(hipStream_t st, const std::vector<PoaChain> &sub, 
     return launch_poa_grouped(st, sub.data(), sub.size(), d_chains, d_reads, d_outs, sc, side, sev, d_gate, spare, busy_idx, busy_load, noisy);
 }
 
-// Runs the hot path of n batches JOINTLY: every stage is one set of launches over the jobs / chains of all batches, so the GPU's
+// ================= one submission: the hot path of n batches run JOINTLY =================
+// Every stage is one set of launches over the jobs / chains of all batches, so the GPU's
 // own workgroup dispatcher packs the chains of several batches onto the CUs (a chain is a sequential object that can use at most
 // one CU; one batch of configs[1] size cannot fill 256 CUs, and separate streams per batch serialise on shared hardware queues).
 // The leader (batches[0]) lends its stream and its job / arena buffers; inputs, chain outputs and final strings stay per batch.
 // Results of batch k must be downloaded before the same leader runs again (the ref<->cons rows live in the leader's WFA buffer).
+//
+// A submission is a Submission object (below): its members are the state that crosses stage boundaries, its member functions are the stages, and
+// run_many_once is the list of the stages with the two helper threads started and joined in it.  Every stage says what it reads, what it writes and
+// which host thread runs it: the CALLING thread, the PREPARATION thread, the STRINGS thread, or a TEAM (host threads of one parallel loop, joined before
+// the stage that started them returns).
+
 // compact CU index of the arena slots: one probe launch per device records which (XCC, SE, SH, CU) ids exist (poa_kernel.hip lcd_cu_probe_kernel)
 static DevBuf *g_cu_rank[LCD_MAX_DEV]; static int g_cu_n[LCD_MAX_DEV]; static std::mutex g_cu_mu;
-static int cu_rank_table(hipStream_t st, uint64_t *addr, int *n_cu) {
+static int cu_rank_table(hipStream_t st, uint64_t *addr, int *n_cu, const bool mem_debug) {
     const int dev = cur_device();
     std::lock_guard<std::mutex> lk(g_cu_mu);
     if (!g_cu_rank[dev]) {
@@ -892,7 +914,7 @@ static int cu_rank_table(hipStream_t st, uint64_t *addr, int *n_cu) {
         for (int &x : h) x = x ? n++ : -1;
         HIPCHK(hipMemcpyAsync(rank->p, h.data(), 4096 * 4, hipMemcpyHostToDevice, st));
         HIPCHK(hipStreamSynchronize(st));
-        if (getenv("LCD_MEM_DEBUG")) fprintf(stderr, "[mem] device %d: %d compute units seen by the probe (%d reported)\n", dev, n, g_n_cus);
+        if (mem_debug) fprintf(stderr, "[mem] device %d: %d compute units seen by the probe (%d reported)\n", dev, n, g_n_cus);
         g_cu_n[dev] = std::max(n, 1); g_cu_rank[dev] = rank.release();
     }
     *addr = g_cu_rank[dev]->addr(); *n_cu = std::max(g_cu_n[dev], g_n_cus); // (a CU the probe missed hashes into the table: never fewer slots than CUs)
@@ -919,60 +941,178 @@ int lcd_batch_run_many(lcd_batch_t **bs, int nb) {
 // submissions in flight per device (host lanes: several threads inside lcd_batch_run_many at once)
 static std::atomic<int> g_inflight[LCD_MAX_DEV];
 struct InflightGuard { int dev; int n; InflightGuard(int d) : dev(d) { n = g_inflight[d].fetch_add(1) + 1; } ~InflightGuard() { g_inflight[dev].fetch_sub(1); } };
-static int run_many_once(lcd_batch_t **bs, int nb) {
-    if (nb <= 0) return 0;
-    for (int k = 0; k < nb; ++k) {
-        if (!bs[k]->uploaded) return set_err(-3, "lcd_batch_run before lcd_batch_upload");
-        if (memcmp(&bs[k]->opt, &bs[0]->opt, sizeof(lcd_opt_t)) != 0) return set_err(-4, "lcd_batch_run_many: batches with different options");
-        if (bs[k]->device != bs[0]->device) return set_err(-4, "lcd_batch_run_many: batches on different devices");
+
+namespace { // everything of a submission but its driver is local to this file
+
+// The switches of a submission.  PER CALL: read once at the start of every submission (the tests switch them between runs inside one process); nothing
+// else on the submission path reads the environment, apart from ChainEnv (the chains' sizing) and the stage runners' own test switches.
+struct SubmitEnv {
+    bool early, solo_rl, prep_thread, anchor_seq, strings_seq, wfa_seq, time_host, mem_debug, cert_debug, retry_debug, placement, profile_chains, dbg_intervals, spare_set;
+    double spare_gb;                        // LCD_SPARE_GB where spare_set (the default depends on the kind of reads)
+    int arena_slot_cus;                     // LCD_ARENA_SLOT_CUS, 0: not set
+    const char *dump_chain, *chain_times;   // LCD_DUMP_CHAIN, LCD_CHAIN_TIMES: file names, NULL: not set
+    SubmitEnv() {
+        auto on = [](const char *name) { return getenv(name) != nullptr; };
+        early = !(getenv("LCD_EARLY") && atoi(getenv("LCD_EARLY")) == 0);
+        solo_rl = on("LCD_SOLO_RL"); prep_thread = !on("LCD_NO_PREP_THREAD"); anchor_seq = on("LCD_ANCHOR_SEQ"); strings_seq = on("LCD_STRINGS_SEQ"); wfa_seq = on("LCD_WFA_SEQ");
+        time_host = on("LCD_TIME_HOST"); mem_debug = on("LCD_MEM_DEBUG"); cert_debug = on("LCD_CERT_DEBUG"); retry_debug = on("LCD_RETRY_DEBUG");
+        placement = on("LCD_PLACEMENT"); profile_chains = on("LCD_PROFILE_CHAINS"); dbg_intervals = getenv("LCD_DBG") && (atoi(getenv("LCD_DBG")) & 32);
+        spare_set = on("LCD_SPARE_GB"); spare_gb = spare_set ? atof(getenv("LCD_SPARE_GB")) : 0.0;
+        arena_slot_cus = on("LCD_ARENA_SLOT_CUS") ? std::max(1, atoi(getenv("LCD_ARENA_SLOT_CUS"))) : 0; // test switch: far fewer slots than resident workgroups (claims must wait)
+        dump_chain = getenv("LCD_DUMP_CHAIN"); chain_times = getenv("LCD_CHAIN_TIMES");
     }
-    if (use_device(bs[0]->device)) return -1;
-    lcd_batch_t *L = bs[0];
-    hipStream_t st = L->stream;
-    const LcdScoring sc = scoring_of(L->opt);
-    const double t_begin = now_ms();
-    // The long K2 chains ahead of the anchor stage (below) take a stream -- one of the runtime's four hardware queues -- for the length of the submission.  That pays
+};
+// ONCE PER PROCESS: read by the first submission, the same for every later one
+struct ProcessEnv {
+    long long solo_min; int solo_n, n_streams; bool arena_slots, anchor_wfa_two;
+    ProcessEnv() {
+        solo_min = getenv("LCD_SOLO_MIN") ? atoll(getenv("LCD_SOLO_MIN")) : 20000;
+        solo_n = getenv("LCD_SOLO_N") ? atoi(getenv("LCD_SOLO_N")) : -1;
+        n_streams = std::max(1, std::min(LCD_NSIDE + 1, getenv("LCD_STREAMS") ? atoi(getenv("LCD_STREAMS")) : 4));
+        arena_slots = !(getenv("LCD_ARENA_SLOTS") && atoi(getenv("LCD_ARENA_SLOTS")) == 0);
+        anchor_wfa_two = !(getenv("LCD_ANCHOR_WFA_SEQ") && atoi(getenv("LCD_ANCHOR_WFA_SEQ")) != 0);
+    }
+};
+static const ProcessEnv &process_env() { static const ProcessEnv e; return e; }
+
+// the arena layout of a round (pure host work: slot pools and private arenas per launch group); round 0's is made on the preparation thread
+struct ArenaItem { uint64_t start, bytes, phys; };
+struct ArenaPlan { uint64_t tot = 0, flag_ints = 0; size_t n_pooled = 0, n_pools = 0; uint64_t private_bytes = 0, pool_bytes = 0; std::vector<ArenaItem> items; std::vector<uint32_t> item_of; std::vector<uint64_t> need; bool valid = false; };
+// one POA round: what its steps hand each other (calling thread; the blocks the round's asynchronous copies read and write live here until the round ends)
+struct PoaRound {
+    int round = 0; ArenaPlan P;
+    PoaChain *sub = nullptr; size_t sub_n = 0;     // the round's chain table (leader's pinned block), in the order of `which`
+    PoaSpare *d_spare = nullptr; PoaSpare spare_hdr, spare_seen;
+    PoaChainOut *tmp = nullptr;                    // the chains' output records (leader's pinned block), in the order of `which`
+    std::vector<size_t> again; size_t n_node_ovf = 0, n_cert_fail = 0;
+};
+struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } };
+struct Submission;
+// diagnostics of a submission (behind the stages, below): they read the submission and print
+static void report_round_memory(const Submission &S, const PoaRound &R);
+static void report_round_retries(const Submission &S, const PoaRound &R);
+static void dump_failed_chain(const Submission &S, size_t g, int status);
+static std::string failed_chain_text(const Submission &S, size_t g, const PoaChainOut &o);
+static void report_placement(const Submission &S);
+static void report_chain_times(const Submission &S);
+static void report_profile_chains(const Submission &S);
+
+struct Submission {
+    // ---- set by the constructor, constant afterwards: read by every stage on every thread ----
+    lcd_batch_t **const bs; const int nb;
+    lcd_batch_t *const L;                 // the leader: lends its stream, events, job tables and arenas
+    const hipStream_t st; const LcdScoring sc; const SubmitEnv env; const double t_begin;
+    InflightGuard inflight;               // (alive for the whole submission)
+    // The long K2 chains ahead of the anchor stage (launch_early) take a stream -- one of the runtime's four hardware queues -- for the length of the submission.  That pays
     // when this submission has the device to itself; with other submissions in flight (host lanes) the queues are what is scarce and the lanes overlap each other's
     // stages anyway: measured with two lanes of 32 batches 82.8 k instead of 100 k regions/s.  LCD_EARLY=0: never.
-    InflightGuard inflight(L->device >= 0 && L->device < LCD_MAX_DEV ? L->device : 0);
-    const bool early_k2 = inflight.n == 1 && !(getenv("LCD_EARLY") && atoi(getenv("LCD_EARLY")) == 0);
-    for (int k = 0; k < nb; ++k) {
-        lcd_batch_stats_t &S = bs[k]->st;
-        const double keep_up = S.ms_upload;
-        memset(&S, 0, sizeof(S)); S.ms_upload = keep_up;
-        S.n_chains = (int)bs[k]->chains.size(); S.n_anchor_jobs = (int)bs[k]->anchors.size();
-    }
-    HIPCHK(hipEventRecord(L->ev[0], st));
-    // the reads of every chain with their device addresses (the anchor stage below narrows the partial reads of K1 chains; lengths never change)
-    std::vector<std::vector<PoaRead>> preads(nb);
+    const bool early_k2;
     ChainEnv cenv;
-    // (filled per batch by the host threads of size_chains below: 24 MB for a 20-batch submission, 3 ms when one thread copied them)
-    // ---- capacities, classes and output blocks of the chains: nothing here depends on the anchor stage, and the longest K2 chains start before it (below) ----
-    std::vector<size_t> chain_base(nb + 1, 0), pread_base(nb + 1, 0);
-    for (int k = 0; k < nb; ++k) { chain_base[k + 1] = chain_base[k] + bs[k]->chains.size(); pread_base[k + 1] = pread_base[k] + bs[k]->preads.size(); }
-    const size_t nC_all = chain_base[nb];
-    cenv.n_chains = (long long)nC_all;
-    std::vector<int> chain_batch(nC_all);
-    for (int k = 0; k < nb; ++k) for (size_t g = chain_base[k]; g < chain_base[k + 1]; ++g) chain_batch[g] = k;
-    std::vector<std::vector<uint64_t>> out_rel(nb);
-    std::vector<uint64_t> out_tots(nb, 0);
+    // chain g of the submission is chain g - chain_base[k] of batch k = chain_batch[g]; the device read table is the concatenation of the batches' tables
+    std::vector<size_t> chain_base, pread_base; std::vector<int> chain_batch; size_t nC_all = 0;
+    // (streams share the runtime's four hardware queues in creation order: the leader's stream and its first three side streams have one each -- a later side
+    //  stream would share the leader's queue and hold the anchor stage and the first launch group behind the long chains: measured, 272 instead of 220 ms of POA)
+    const hipStream_t es;                 // the long chains' stream
+    uint64_t cu_rank_addr = 0; int n_cu;  // the arena slots' CU table (begin)
+    // ---- written by prep_chains (preparation thread) and its teams ----
+    // the reads of every chain with their device addresses (the anchor stage narrows the partial reads of K1 chains; lengths never change)
+    // (filled per batch by the host threads of size_chains: 24 MB for a 20-batch submission, 3 ms when one thread copied them)
+    std::vector<std::vector<PoaRead>> preads;
+    std::vector<std::vector<uint64_t>> out_rel; std::vector<uint64_t> out_tots; // the chains' first output blocks: offsets into their batch's d_poa_out
+    std::vector<size_t> early;            // the long K2 chains that run on `es` since before the anchor stage
+    double early_load = 0; bool reads_up = false; // (reads_up: the read table is in d_preads already, as of before the anchor stage)
+    std::vector<size_t> which;            // the chains of the round at hand, in launch order (prepare_round0; then the POA rounds)
+    ArenaPlan plan0;                      // round 0's arena layout (prepare_round0)
+    // ---- THE HAND-OVER.  Written on the preparation thread, read by the calling thread only after join_prep() has returned: early, reads_up, early_load,
+    // preads, which, plan0 and pchains[*] of every batch (with them out_rel, out_tots, couts and the chains' solo / cert fields).  Until then the calling
+    // thread touches none of them: begin and anchor_stage run beside the preparation thread ----
+    bool order_async = false; int prep_rc = 0;
+    std::string prep_err;                 // (g_err is per thread: a helper's message is carried over to the calling thread at the join)
+    // ---- the POA rounds (calling thread) ----
+    double tp0 = 0, th0 = 0;              // host clock at the start of the POA stage / of the stages behind it
+    int scale = 1;
+    std::map<size_t, uint64_t> retry_out_off; // chains whose output block moved to a retry buffer
+    // ---- S3 / S4: the joint job tables live in the leader (kept between submissions: no reallocation, no first-touch page faults in the steady state) ----
+    std::vector<WfaJob> &rc_all; std::vector<StrJob> &str_all; std::vector<StrOut> &str_outs;
+    std::vector<size_t> rc_base, str_base; std::vector<uint64_t> str_tots;
+    bool strings_beside = false; int strings_rc = 0; std::string strings_err;
+    float ms_vars = 0;
+    // ---- the helper threads.  Declared LAST: members are destroyed in reverse order, so on every way out of run_many_once the two threads are joined before
+    // anything they touch dies ----
+    Joiner prep_thread, strings_thread;
+
+    Submission(lcd_batch_t **bs_, int nb_)
+        : bs(bs_), nb(nb_), L(bs_[0]), st(L->stream), sc(scoring_of(L->opt)), t_begin(now_ms()), inflight(L->device >= 0 && L->device < LCD_MAX_DEV ? L->device : 0),
+          early_k2(inflight.n == 1 && env.early), chain_base(nb_ + 1, 0), pread_base(nb_ + 1, 0), es(L->side[2]), n_cu(g_n_cus), preads(nb_), out_rel(nb_), out_tots(nb_, 0),
+          rc_all(L->h_rc_all), str_all(L->h_str_all), str_outs(L->h_str_outs), rc_base(nb_ + 1, 0), str_base(nb_ + 1, 0), str_tots(nb_, 0) {
+        for (int k = 0; k < nb; ++k) { chain_base[k + 1] = chain_base[k] + bs[k]->chains.size(); pread_base[k + 1] = pread_base[k] + bs[k]->preads.size(); }
+        nC_all = chain_base[nb];
+        cenv.n_chains = (long long)nC_all;
+        chain_batch.resize(nC_all);
+        for (int k = 0; k < nb; ++k) for (size_t g = chain_base[k]; g < chain_base[k + 1]; ++g) chain_batch[g] = k;
+        which.reserve(nC_all);
+    }
+    // chain g of the submission: its descriptor, its output record, its record in its batch
+    PoaChain &chain(size_t g) const { const int k = chain_batch[g]; return bs[k]->pchains[g - chain_base[k]]; }
+    PoaChainOut &out(size_t g) const { const int k = chain_batch[g]; return bs[k]->couts[g - chain_base[k]]; }
+    ChainRec &rec(size_t g) const { const int k = chain_batch[g]; return bs[k]->chains[g - chain_base[k]]; }
+    // f(k) for every batch, on a team of up to `team` host threads (the calling thread is one of them)
+    void over_batches(const int team, const std::function<void(int)> &f) const {
+        par_chunks((size_t)nb, std::min(nb, team), 1, [&](const size_t lo, const size_t hi, int) { for (size_t k = lo; k < hi; ++k) f((int)k); });
+    }
+
+    // ---- validation.  Reads: the batches' flags, options, devices.  Writes: nothing; selects the device.  Calling thread, before the submission exists ----
+    static int validate(lcd_batch_t **bs, int nb) {
+        for (int k = 0; k < nb; ++k) {
+            if (!bs[k]->uploaded) return set_err(-3, "lcd_batch_run before lcd_batch_upload");
+            if (memcmp(&bs[k]->opt, &bs[0]->opt, sizeof(lcd_opt_t)) != 0) return set_err(-4, "lcd_batch_run_many: batches with different options");
+            if (bs[k]->device != bs[0]->device) return set_err(-4, "lcd_batch_run_many: batches on different devices");
+        }
+        if (use_device(bs[0]->device)) return -1;
+        return 0;
+    }
+    // ---- statistics reset, the submission's first event, the arena slots' CU table.  Reads: env.  Writes: every batch's st, cu_rank_addr, n_cu; ev[0] on st
+    // (the probe of a device's first submission runs and synchronises on st).  Calling thread, before the preparation thread starts ----
+    int begin() {
+        for (int k = 0; k < nb; ++k) {
+            lcd_batch_stats_t &S = bs[k]->st;
+            const double keep_up = S.ms_upload;
+            memset(&S, 0, sizeof(S)); S.ms_upload = keep_up;
+            S.n_chains = (int)bs[k]->chains.size(); S.n_anchor_jobs = (int)bs[k]->anchors.size();
+        }
+        HIPCHK(hipEventRecord(L->ev[0], st));
+        if (process_env().arena_slots) { const int rc3 = cu_rank_table(st, &cu_rank_addr, &n_cu, env.mem_debug); if (rc3) return rc3; }
+        if (env.arena_slot_cus) n_cu = env.arena_slot_cus;
+        return 0;
+    }
+
+    // Everything between here and the round-0 arena layout needs nothing from the anchor stage and the anchor stage nothing from it (the reads' narrowed ends are applied
+    // after the join): capacities (3 ms of a 20-batch submission), the early launch of the long K2 chains (2 ms) and classes / order / arenas (1 ms) run on a helper
+    // thread while the calling thread builds the anchor job tables and runs the anchor kernels -- the anchor kernels start ~5 ms earlier.  LCD_NO_PREP_THREAD=1: in line, as before
+    //
+    // ---- prep_chains: long-chain cut, capacities, output blocks, early launch.  Reads: the batches' chains / preads, cenv, early_k2.  Writes: the hand-over state
+    // but which / plan0 (ChainRec.solo, preads, pchains, couts, out_rel, out_tots, d_poa_out, early, early_load, reads_up); the read table, ev[8] and the long
+    // chains' launches on es.  Preparation thread (LCD_NO_PREP_THREAD: calling thread), with one team ----
+    int prep_chains() {
+        choose_long_chains();
+        over_batches(host_team(), [&](const int k) { size_chains(k); });
+        for (int k = 0; k < nb; ++k) {
+            lcd_batch_t *b = bs[k];
+            const int nC = (int)b->chains.size();
+            if (nC && b->d_poa_out.ensure(out_tots[k])) return -11;
+            for (int c = 0; c < nC; ++c) b->pchains[c].out_off = b->d_poa_out.addr() + out_rel[k][c];
+        }
+        if (env.time_host) fprintf(stderr, "[host]   POA prep: capacities after %.1f ms\n", now_ms() - t_begin);
+        return launch_early();
+    }
     // Which chains are LONG (256-thread workgroup: rows on wavefront 0, per-read phases on four) is decided for the submission at hand: at most LCD_SOLO_N
     // (default: one per two CUs) of the longest chains in flight, and none below LCD_SOLO_MIN read-bases.  A lone batch leaves most of the chip idle and its
     // longest chain IS its latency, so there the cut is low; twenty batches keep the wide workgroups for their top hundred.  LCD_SOLO_RL fixes the cut instead.
-    auto PC = [&](size_t g) -> PoaChain & { const int k = chain_batch[g]; return bs[k]->pchains[g - chain_base[k]]; };
-    std::vector<size_t> early;
-    // (streams share the runtime's four hardware queues in creation order: the leader's stream and its first three side streams have one each -- a later side
-    //  stream would share the leader's queue and hold the anchor stage and the first launch group behind the long chains: measured, 272 instead of 220 ms of POA)
-    hipStream_t es = L->side[2];
-    double early_load = 0; bool reads_up = false; // (reads_up: the read table is in d_preads already, as of before the anchor stage)
-    // Everything between here and the row-0 arena layout needs nothing from the anchor stage and the anchor stage nothing from it (the reads' narrowed ends are applied
-    // after the join): capacities (3 ms of a 20-batch submission), the early launch of the long K2 chains (2 ms) and classes / order / arenas (1 ms) run on a helper
-    // thread while this one builds the anchor job tables and runs the anchor kernels -- the anchor kernels start ~5 ms earlier.  LCD_NO_PREP_THREAD=1: in line, as before
-    auto prep_chains = [&]() -> int {
-    if (!getenv("LCD_SOLO_RL")) {
-        static const long long solo_min = getenv("LCD_SOLO_MIN") ? atoll(getenv("LCD_SOLO_MIN")) : 20000;
-        static const int solo_n_env = getenv("LCD_SOLO_N") ? atoi(getenv("LCD_SOLO_N")) : -1;
-        const size_t solo_n = (size_t)(solo_n_env >= 0 ? solo_n_env : std::max(1, g_n_cus / 2));
+    // Reads: the batches' chains / preads, early_k2.  Writes: ChainRec.solo.  Preparation thread
+    void choose_long_chains() {
+        if (env.solo_rl) { for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) C.solo = -1; return; }
+        const long long solo_min = process_env().solo_min;
+        const size_t solo_n = (size_t)(process_env().solo_n >= 0 ? process_env().solo_n : std::max(1, g_n_cus / 2));
         std::vector<long long> rls;
         for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) {
             int maxl = 0; for (size_t q = 0; q < C.members.size(); ++q) maxl = std::max(maxl, bs[k]->preads[C.read0 + q].len);
@@ -982,11 +1122,13 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
         if (solo_n == 0) cut = 1ll << 62;
         else if (rls.size() > solo_n) { std::vector<long long> t = rls; std::nth_element(t.begin(), t.begin() + (solo_n - 1), t.end(), std::greater<long long>()); cut = std::max(cut, t[solo_n - 1]); }
         size_t q = 0;
-        // (with the long K2 chains launched ahead of the anchor stage -- below -- one of the four hardware queues is theirs for the length of the submission: K1 chains,
+        // (with the long K2 chains launched ahead of the anchor stage -- launch_early -- one of the four hardware queues is theirs for the length of the submission: K1 chains,
         //  which wait for their anchors, then stay in the single-wavefront class instead of forming a fourth launch group that would queue behind another)
         for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) C.solo = rls[q++] >= cut && (C.mode == 1 || !early_k2) ? 1 : 0; // (noisy reads have no certified-band K2 chains, but their long K1 chains are no faster in the wide workgroup: SV shape 1 608 with them there, 1 680 without)
-    } else for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) C.solo = -1;
-    auto size_chains = [&](const int k) { // capacities, class and output offsets of a batch's chains (independent of the other batches: host threads)
+    }
+    // capacities, class and output offsets of a batch's chains (independent of the other batches).  Reads: batch k, cenv.  Writes: preads[k], out_rel[k], out_tots[k],
+    // batch k's couts / pchains / cert fields.  Team of prep_chains
+    void size_chains(const int k) {
         lcd_batch_t *b = bs[k];
         { preads[k] = b->preads; const uint64_t in_base = b->d_in.addr(); for (auto &r : preads[k]) r.seq_off += in_base; }
         const int nC = (int)b->chains.size();
@@ -1000,28 +1142,12 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
             out_rel[k][c] = out_tot; out_tot += lcd_align_up(poa_out_bytes(b->pchains[c].node_cap, b->pchains[c].n_reads), 256);
         }
         out_tots[k] = out_tot;
-    };
-    {
-        const int nth = std::max(1, std::min(nb, host_team()));
-        if (nth == 1) size_chains(0);
-        else {
-            std::atomic<int> next{0};
-            std::vector<std::thread> ths;
-            for (int t = 0; t < nth; ++t) ths.emplace_back([&]() { for (int k; (k = next.fetch_add(1)) < nb;) size_chains(k); });
-            for (auto &t : ths) t.join();
-        }
     }
-    for (int k = 0; k < nb; ++k) {
-        lcd_batch_t *b = bs[k];
-        const int nC = (int)b->chains.size();
-        if (nC && b->d_poa_out.ensure(out_tots[k])) return -11;
-        for (int c = 0; c < nC; ++c) b->pchains[c].out_off = b->d_poa_out.addr() + out_rel[k][c];
-    }
-    if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   POA prep: capacities after %.1f ms\n", now_ms() - t_begin);
     // ---- the long K2 chains start NOW: they are the latency of the submission (the longest chain lasts as long as the whole POA stage) and need nothing from
     // the anchor stage -- their reads are aligned whole.  Own stream, own chain table / read table / arenas (the anchor stage's workspace is the leader's arena);
     // their results join the others' after the first round's launches.  LCD_EARLY=0: off (they start with everybody else, as before).
-    {
+    // Reads: preads, pchains, early_k2.  Writes: early, early_load, reads_up, the early chains' ws_off / slot fields; d_preads, ev[8] and the launches on es.  Preparation thread
+    int launch_early() {
         // the read table goes up ONCE, here, on the long chains' stream (24 MB for 20 batches: 1.5 - 1.8 ms of this helper thread instead of the calling thread's, which
         // used to send it a second time between the anchor stage and the main launches); the reads the anchor stage narrows are patched afterwards (lcd_patch_reads_kernel)
         if (early_k2 && es && nC_all && !L->d_preads.ensure(pread_base[nb] * sizeof(PoaRead))) {
@@ -1031,144 +1157,143 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
             HIPCHK(hipEventRecord(L->ev[8], es));
             reads_up = true;
         } else (void)hipGetLastError();
-        if (early_k2 && es) for (size_t g = 0; g < nC_all; ++g) { const PoaChain &pc = PC(g); if (pc.solo && pc.mode == 1 && pc.threads == 256 && pc.n_reads > 0) early.push_back(g); }
-        if (early.size() == nC_all) early.clear(); // (the first round below is built around the launches of the others)
-        if (!early.empty()) {
-            std::vector<PoaChain> sub_e(early.size());
-            uint64_t tot_e = 0;
-            for (size_t i = 0; i < early.size(); ++i) {
-                PoaChain &pc = PC(early[i]);
-                early_load = std::max(early_load, (double)pc.n_reads * (pc.max_len + 64));
-                pc.ws_off = tot_e; pc.slot_flags = 0; pc.slot_bytes = 0; pc.n_slots = 0; pc.per_cu = 0; pc.cu_rank = 0;
-                tot_e += lcd_align_up(poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, pc.cell_cap, pc.n_reads, pc.spill_x, pc.cert).total, 256);
-            }
-            if (!reads_up || L->d_early_arena.ensure(tot_e, 3) || L->d_chains_early.ensure(early.size() * sizeof(PoaChain)) ||
-                L->d_poa_outs_early.ensure(early.size() * sizeof(PoaChainOut))) { (void)hipGetLastError(); early.clear(); } // (no memory for it: they start with the others)
-            else {
-                for (size_t i = 0; i < early.size(); ++i) { PoaChain &pc = PC(early[i]); pc.ws_off += L->d_early_arena.addr(); sub_e[i] = pc; sub_e[i].read0 += (int)pread_base[chain_batch[early[i]]]; }
-                { const int rc2 = launch_poa_grouped(es, sub_e, L->d_chains_early, (const PoaRead *)L->d_preads.p, L->d_poa_outs_early, sc); if (rc2) return rc2; }
-                if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   %zu long K2 chains launched %.1f ms after the start (%.2f GB of arenas)\n", early.size(), now_ms() - t_begin, tot_e / 1e9);
-            }
+        if (early_k2 && es) for (size_t g = 0; g < nC_all; ++g) { const PoaChain &pc = chain(g); if (pc.solo && pc.mode == 1 && pc.threads == 256 && pc.n_reads > 0) early.push_back(g); }
+        if (early.size() == nC_all) early.clear(); // (the first round is built around the launches of the others)
+        if (early.empty()) return 0;
+        std::vector<PoaChain> sub_e(early.size());
+        uint64_t tot_e = 0;
+        for (size_t i = 0; i < early.size(); ++i) {
+            PoaChain &pc = chain(early[i]);
+            early_load = std::max(early_load, (double)pc.n_reads * (pc.max_len + 64));
+            pc.ws_off = tot_e; pc.slot_flags = 0; pc.slot_bytes = 0; pc.n_slots = 0; pc.per_cu = 0; pc.cu_rank = 0;
+            tot_e += lcd_align_up(poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, pc.cell_cap, pc.n_reads, pc.spill_x, pc.cert).total, 256);
         }
+        if (!reads_up || L->d_early_arena.ensure(tot_e, 3) || L->d_chains_early.ensure(early.size() * sizeof(PoaChain)) ||
+            L->d_poa_outs_early.ensure(early.size() * sizeof(PoaChainOut))) { (void)hipGetLastError(); early.clear(); return 0; } // (no memory for it: they start with the others)
+        for (size_t i = 0; i < early.size(); ++i) { PoaChain &pc = chain(early[i]); pc.ws_off += L->d_early_arena.addr(); sub_e[i] = pc; sub_e[i].read0 += (int)pread_base[chain_batch[early[i]]]; }
+        { const int rc2 = launch_poa_grouped(es, sub_e, L->d_chains_early, (const PoaRead *)L->d_preads.p, L->d_poa_outs_early, sc); if (rc2) return rc2; }
+        if (env.time_host) fprintf(stderr, "[host]   %zu long K2 chains launched %.1f ms after the start (%.2f GB of arenas)\n", early.size(), now_ms() - t_begin, tot_e / 1e9);
+        return 0;
     }
-    return 0;
-    };
-    // ---- classes and order of the chains that start after the anchor stage: host work that needs nothing from it -- made on a helper thread while the anchor kernels run
-    //      (4 ms of a 260 ms submission with the main launches waiting for it, before) ----
-    std::vector<size_t> which; which.reserve(nC_all);
-    auto order_chains = [&]() {
+
+    // ---- prepare_round0: classes and order of the chains that start after the anchor stage, and their arena layout: host work that needs nothing from the anchor
+    // stage -- made on the preparation thread while the anchor kernels run (4 ms of a 260 ms submission with the main launches waiting for it, before).
+    // Reads: early, pchains, n_cu, cu_rank_addr.  Writes: which, plan0, the chains' lds_words / ws_off / slot fields.  Preparation thread when order_async, else calling
+    // thread after the join ----
+    void prepare_round0() {
+        order_chains();
+        plan0.need.resize(which.size());
+        for (size_t i = 0; i < which.size(); ++i) { const PoaChain &pc = chain(which[i]); plan0.need[i] = poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, pc.cell_cap, pc.n_reads, pc.spill_x, pc.cert).total; }
+        segment_arenas(plan0);
+        plan0.valid = true;
+    }
+    void order_chains() {
         { std::vector<char> is_early(nC_all, 0); for (size_t g : early) is_early[g] = 1; for (size_t g = 0; g < nC_all; ++g) if (!is_early[g]) which.push_back(g); }
         // No more launch groups than streams: a stream runs its kernels one after the other, so a fifth group starts only when some other group's LAST chain has
         // ended -- with the bulk of the work (40 000 short chains in the smallest LDS bucket) queued behind a group of a few hundred long chains the chip idled for a
         // third of the stage.  The single-wavefront group with the fewest chains moves up into the next larger LDS bucket in use (a bigger pool is always valid).
-        {
-            static const int n_streams = std::max(1, std::min(LCD_NSIDE + 1, getenv("LCD_STREAMS") ? atoi(getenv("LCD_STREAMS")) : 4));
-            for (;;) {
-                // (only SMALL groups move -- less than 8 % of the submission's CU-time: a bigger pool means fewer chains per CU, and the bulk of the work must keep the
-                //  occupancy of its own bucket; noisy-read submissions have five wide classes besides, there is no getting down to four groups)
-                std::map<long long, std::pair<size_t, double>> cnt;
-                double tot_w = 0;
-                for (size_t g = 0; g < nC_all; ++g) {
-                    const PoaChain &pc = PC(g);
-                    const int lds = pc.lds_words * 4, thr = pc.threads;
-                    const int per_cu = std::max(1, std::min((160 * 1024) / (lds + (thr == 64 ? 1 : 6) * 1024), 1024 / thr));
-                    const double w = (double)pc.n_reads * (pc.max_len + 64) / per_cu;
-                    auto &e = cnt[chain_group_key(pc)]; e.first++; e.second += w; tot_w += w;
-                }
-                if ((int)cnt.size() <= n_streams) break;
-                long long from = -1, to = -1; double least = 0.08 * tot_w;
-                for (auto it = cnt.begin(); it != cnt.end(); ++it) {
-                    if ((it->first >> 20) != 64) continue;
-                    auto nx = std::next(it);
-                    if (nx == cnt.end() || (nx->first >> 20) != 64) continue;
-                    if (it->second.second < least) { least = it->second.second; from = it->first; to = nx->first; }
-                }
-                if (from < 0) break;
-                const int lw = (int)(to & ((1 << 20) - 1));
-                for (size_t g = 0; g < nC_all; ++g) if (chain_group_key(PC(g)) == from) PC(g).lds_words = lw;
+        for (const int n_streams = process_env().n_streams;;) {
+            // (only SMALL groups move -- less than 8 % of the submission's CU-time: a bigger pool means fewer chains per CU, and the bulk of the work must keep the
+            //  occupancy of its own bucket; noisy-read submissions have five wide classes besides, there is no getting down to four groups)
+            std::map<long long, std::pair<size_t, double>> cnt;
+            double tot_w = 0;
+            for (size_t g = 0; g < nC_all; ++g) {
+                const PoaChain &pc = chain(g);
+                const double w = (double)pc.n_reads * (pc.max_len + 64) / chains_per_cu(pc.lds_words * 4, pc.threads, kSchedOverhead);
+                auto &e = cnt[chain_group_key(pc)]; e.first++; e.second += w; tot_w += w;
             }
+            if ((int)cnt.size() <= n_streams) break;
+            long long from = -1, to = -1; double least = 0.08 * tot_w;
+            for (auto it = cnt.begin(); it != cnt.end(); ++it) {
+                if ((it->first >> 20) != 64) continue;
+                auto nx = std::next(it);
+                if (nx == cnt.end() || (nx->first >> 20) != 64) continue;
+                if (it->second.second < least) { least = it->second.second; from = it->first; to = nx->first; }
+            }
+            if (from < 0) break;
+            const int lw = (int)(to & ((1 << 20) - 1));
+            for (size_t g = 0; g < nC_all; ++g) if (chain_group_key(chain(g)) == from) chain(g).lds_words = lw;
         }
         // widest / largest-LDS group first, then biggest first so the long chains start early (LPT)
-        {   // (keys taken once: the comparator used to look both chains up through their batch for each of the ~600 000 comparisons of a 20-batch submission)
-            std::vector<std::pair<long long, uint64_t>> sk(nC_all);
-            for (size_t g = 0; g < nC_all; ++g) { const PoaChain &pc = PC(g); sk[g] = {chain_group_key(pc), pc.cell_cap}; }
-            std::sort(which.begin(), which.end(), [&](size_t a, size_t c2) {
-                if (sk[a].first != sk[c2].first) return sk[a].first > sk[c2].first;
-                if (sk[a].second != sk[c2].second) return sk[a].second > sk[c2].second;
-                return a < c2; });
-        }
-    };
-    // the arena layout of a round (pure host work: slot pools and private arenas per launch group); round 0's is made on the helper thread as well
-    struct Item { uint64_t start, bytes, phys; };
-    struct ArenaPlan { uint64_t tot = 0, flag_ints = 0; size_t n_pooled = 0, n_pools = 0; uint64_t private_bytes = 0, pool_bytes = 0; std::vector<Item> items; std::vector<uint32_t> item_of; std::vector<uint64_t> need; bool valid = false; };
-    static const bool use_slots = !(getenv("LCD_ARENA_SLOTS") && atoi(getenv("LCD_ARENA_SLOTS")) == 0);
-    uint64_t cu_rank_addr = 0; int n_cu = g_n_cus;
-    if (use_slots) { const int rc3 = cu_rank_table(st, &cu_rank_addr, &n_cu); if (rc3) return rc3; }
-    if (getenv("LCD_ARENA_SLOT_CUS")) n_cu = std::max(1, atoi(getenv("LCD_ARENA_SLOT_CUS"))); // test switch: far fewer slots than resident workgroups (claims must wait)
-    auto segment_arenas = [&](ArenaPlan &P) { // needs: which (ordered), P.need[i] for which[i]
-        P.tot = 0; P.flag_ints = 0; P.n_pooled = P.n_pools = 0; P.private_bytes = P.pool_bytes = 0; P.items.clear(); P.item_of.assign(which.size(), 0);
-    for (size_t i = 0; i < which.size();) {
-        const long long key = chain_group_key(PC(which[i]));
-        size_t j = i;
-        while (j < which.size() && chain_group_key(PC(which[j])) == key) ++j;
-        const PoaChain &p0 = PC(which[i]);
-        const int lds = p0.lds_words * 4, thr = p0.threads;
-        const int per_cu = std::max(1, std::min((160 * 1024) / (lds + (thr == 64 ? 912 : 6096)), 1024 / thr));
-        const uint64_t R = (uint64_t)n_cu * per_cu;
-        // the group's chains by arena size, largest first, cut into segments at breakpoints where the size has dropped by >= 1.3x; a segment
-        // either keeps private arenas (cost: the sum of its sizes) or, if it has more than R chains, shares R slots of its largest size
-        // (cost R x size).  The cheapest segmentation is a shortest path over the <= ~40 breakpoints (sizes of a group span two orders of magnitude).
-        std::vector<size_t> ord(j - i);
-        for (size_t q = 0; q < ord.size(); ++q) ord[q] = i + q;
-        std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b2) { return P.need[a] > P.need[b2]; });
-        const size_t n = ord.size();
-        std::vector<size_t> bp(1, 0);
-        for (size_t q = 1; q < n; ++q) if ((double)P.need[ord[q]] * 1.3 <= (double)P.need[ord[bp.back()]]) bp.push_back(q);
-        bp.push_back(n);
-        std::vector<uint64_t> pre(n + 1, 0);
-        for (size_t q = 0; q < n; ++q) pre[q + 1] = pre[q] + P.need[ord[q]];
-        const size_t nbp = bp.size();
-        std::vector<uint64_t> cost(nbp, ~0ull); std::vector<size_t> nxt(nbp, nbp - 1);
-        cost[nbp - 1] = 0;
-        auto seg_pooled = [&](size_t a, size_t b2) { return use_slots && bp[b2] - bp[a] > R && R * lcd_align_up(P.need[ord[bp[a]]], 256) < pre[bp[b2]] - pre[bp[a]]; };
-        for (size_t a = nbp - 1; a-- > 0;)
-            for (size_t b2 = a + 1; b2 < nbp; ++b2) {
-                const uint64_t c = (seg_pooled(a, b2) ? R * lcd_align_up(P.need[ord[bp[a]]], 256) : pre[bp[b2]] - pre[bp[a]]) + cost[b2];
-                if (c < cost[a]) { cost[a] = c; nxt[a] = b2; }
-            }
-        for (size_t a = 0; a + 1 < nbp; a = nxt[a]) {
-            const size_t b2 = nxt[a];
-            if (seg_pooled(a, b2)) {
-                const uint64_t slot = lcd_align_up(P.need[ord[bp[a]]], 256);
-                for (size_t q = bp[a]; q < bp[b2]; ++q) { PoaChain &pc = PC(which[ord[q]]); pc.ws_off = P.tot; pc.slot_flags = 1 + P.flag_ints; pc.slot_bytes = slot; pc.n_slots = (int)R; pc.per_cu = per_cu; pc.cu_rank = cu_rank_addr; P.item_of[ord[q]] = (uint32_t)P.items.size(); }
-                P.items.push_back({P.tot, R * slot, 0});
-                P.tot += R * slot; P.flag_ints += R; P.n_pooled += bp[b2] - bp[a]; ++P.n_pools; P.pool_bytes += R * slot;
-            } else
-                for (size_t q = bp[a]; q < bp[b2]; ++q) { PoaChain &pc = PC(which[ord[q]]); pc.ws_off = P.tot; pc.slot_flags = 0; pc.slot_bytes = 0; pc.n_slots = 0; pc.per_cu = 0; pc.cu_rank = 0; P.item_of[ord[q]] = (uint32_t)P.items.size(); P.items.push_back({P.tot, P.need[ord[q]], 0}); P.tot += P.need[ord[q]]; P.private_bytes += P.need[ord[q]]; }
-        }
-        i = j;
+        // (keys taken once: the comparator used to look both chains up through their batch for each of the ~600 000 comparisons of a 20-batch submission)
+        std::vector<std::pair<long long, uint64_t>> sk(nC_all);
+        for (size_t g = 0; g < nC_all; ++g) { const PoaChain &pc = chain(g); sk[g] = {chain_group_key(pc), pc.cell_cap}; }
+        std::sort(which.begin(), which.end(), [&](size_t a, size_t c2) {
+            if (sk[a].first != sk[c2].first) return sk[a].first > sk[c2].first;
+            if (sk[a].second != sk[c2].second) return sk[a].second > sk[c2].second;
+            return a < c2; });
     }
-    };
-    ArenaPlan plan0;
-    auto prepare_round0 = [&]() {
-        order_chains();
-        plan0.need.resize(which.size());
-        for (size_t i = 0; i < which.size(); ++i) { const PoaChain &pc = PC(which[i]); plan0.need[i] = poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, pc.cell_cap, pc.n_reads, pc.spill_x, pc.cert).total; }
-        segment_arenas(plan0);
-        plan0.valid = true;
-    };
-    struct Joiner { std::thread t; ~Joiner() { if (t.joinable()) t.join(); } } order_thread; // (joins on every way out of this function)
-    const bool prep_async = !getenv("LCD_NO_PREP_THREAD");
-    const bool order_async = nC_all >= 2048 && prep_async;
-    int prep_rc = 0;
-    std::string prep_err; // (g_err is per thread: a helper's message is carried over to the calling thread at the join)
-    if (prep_async) {
+    // Work arenas.  A chain's arena is live only while its workgroup is resident, and a CU holds at most per_cu workgroups of a launch group:
+    // runs of chains of one launch group and one size class (half octaves of the arena size) that outnumber the chip's capacity share a pool of
+    // n_cu x per_cu SLOTS claimed at workgroup start (poa_kernel.hip); the others keep private arenas.  Memory then scales with resident
+    // workgroups, not with the number of chains in flight.
+    // Reads: which (ordered), P.need[i] for which[i], n_cu, cu_rank_addr.  Writes: P, the chains' ws_off (relative to P) and slot fields.  The thread of its caller
+    void segment_arenas(ArenaPlan &P) {
+        const bool use_slots = process_env().arena_slots;
+        P.tot = 0; P.flag_ints = 0; P.n_pooled = P.n_pools = 0; P.private_bytes = P.pool_bytes = 0; P.items.clear(); P.item_of.assign(which.size(), 0);
+        for (size_t i = 0; i < which.size();) {
+            const long long key = chain_group_key(chain(which[i]));
+            size_t j = i;
+            while (j < which.size() && chain_group_key(chain(which[j])) == key) ++j;
+            const PoaChain &p0 = chain(which[i]);
+            const int per_cu = chains_per_cu(p0.lds_words * 4, p0.threads, kSlotOverhead);
+            const uint64_t R = (uint64_t)n_cu * per_cu;
+            // the group's chains by arena size, largest first, cut into segments at breakpoints where the size has dropped by >= 1.3x; a segment
+            // either keeps private arenas (cost: the sum of its sizes) or, if it has more than R chains, shares R slots of its largest size
+            // (cost R x size).  The cheapest segmentation is a shortest path over the <= ~40 breakpoints (sizes of a group span two orders of magnitude).
+            std::vector<size_t> ord(j - i);
+            for (size_t q = 0; q < ord.size(); ++q) ord[q] = i + q;
+            std::stable_sort(ord.begin(), ord.end(), [&](size_t a, size_t b2) { return P.need[a] > P.need[b2]; });
+            const size_t n = ord.size();
+            std::vector<size_t> bp(1, 0);
+            for (size_t q = 1; q < n; ++q) if ((double)P.need[ord[q]] * 1.3 <= (double)P.need[ord[bp.back()]]) bp.push_back(q);
+            bp.push_back(n);
+            std::vector<uint64_t> pre(n + 1, 0);
+            for (size_t q = 0; q < n; ++q) pre[q + 1] = pre[q] + P.need[ord[q]];
+            const size_t nbp = bp.size();
+            std::vector<uint64_t> cost(nbp, ~0ull); std::vector<size_t> nxt(nbp, nbp - 1);
+            cost[nbp - 1] = 0;
+            auto seg_pooled = [&](size_t a, size_t b2) { return use_slots && bp[b2] - bp[a] > R && R * lcd_align_up(P.need[ord[bp[a]]], 256) < pre[bp[b2]] - pre[bp[a]]; };
+            for (size_t a = nbp - 1; a-- > 0;)
+                for (size_t b2 = a + 1; b2 < nbp; ++b2) {
+                    const uint64_t c = (seg_pooled(a, b2) ? R * lcd_align_up(P.need[ord[bp[a]]], 256) : pre[bp[b2]] - pre[bp[a]]) + cost[b2];
+                    if (c < cost[a]) { cost[a] = c; nxt[a] = b2; }
+                }
+            for (size_t a = 0; a + 1 < nbp; a = nxt[a]) {
+                const size_t b2 = nxt[a];
+                if (seg_pooled(a, b2)) {
+                    const uint64_t slot = lcd_align_up(P.need[ord[bp[a]]], 256);
+                    for (size_t q = bp[a]; q < bp[b2]; ++q) { PoaChain &pc = chain(which[ord[q]]); pc.ws_off = P.tot; pc.slot_flags = 1 + P.flag_ints; pc.slot_bytes = slot; pc.n_slots = (int)R; pc.per_cu = per_cu; pc.cu_rank = cu_rank_addr; P.item_of[ord[q]] = (uint32_t)P.items.size(); }
+                    P.items.push_back({P.tot, R * slot, 0});
+                    P.tot += R * slot; P.flag_ints += R; P.n_pooled += bp[b2] - bp[a]; ++P.n_pools; P.pool_bytes += R * slot;
+                } else
+                    for (size_t q = bp[a]; q < bp[b2]; ++q) { PoaChain &pc = chain(which[ord[q]]); pc.ws_off = P.tot; pc.slot_flags = 0; pc.slot_bytes = 0; pc.n_slots = 0; pc.per_cu = 0; pc.cu_rank = 0; P.item_of[ord[q]] = (uint32_t)P.items.size(); P.items.push_back({P.tot, P.need[ord[q]], 0}); P.tot += P.need[ord[q]]; P.private_bytes += P.need[ord[q]]; }
+            }
+            i = j;
+        }
+    }
+    // ---- the preparation thread: prep_chains, then prepare_round0 when the submission is large enough to pay for it.  start_prep returns prep_chains' own code
+    // when it ran in line (LCD_NO_PREP_THREAD).  A helper thread selects the device first and hands its error text over at the join.  Calling thread ----
+    int start_prep() {
+        order_async = nC_all >= 2048 && env.prep_thread;
+        if (!env.prep_thread) return prep_chains();
         const int dev_here = cur_device();
-        order_thread.t = std::thread([&, dev_here]() { if (hipSetDevice(dev_here) != hipSuccess) { prep_rc = -1; prep_err = "hipSetDevice failed on the preparation thread"; return; } prep_rc = prep_chains(); if (!prep_rc && order_async) prepare_round0(); if (prep_rc) prep_err = g_err; });
-    } else { const int rc0 = prep_chains(); if (rc0) return rc0; }
-    auto join_prep = [&]() -> int { if (order_thread.t.joinable()) order_thread.t.join(); if (prep_rc && !prep_err.empty()) g_err = prep_err; return prep_rc; };
+        prep_thread.t = std::thread([this, dev_here]() {
+            if (hipSetDevice(dev_here) != hipSuccess) { prep_rc = -1; prep_err = "hipSetDevice failed on the preparation thread"; return; }
+            prep_rc = prep_chains();
+            if (!prep_rc && order_async) prepare_round0();
+            if (prep_rc) prep_err = g_err;
+        });
+        return 0;
+    }
+    // from here on the hand-over state (above) is the calling thread's
+    int join_prep() { if (prep_thread.t.joinable()) prep_thread.t.join(); if (prep_rc && !prep_err.empty()) g_err = prep_err; return prep_rc; }
+
     // ---------------- S1: anchors (K4 prefilter + K3b) ----------------
-    {
+    // Reads: the batches' anchors / ed_jobs / wfa_jobs, env.  Writes: the leader's anchor buffers; K4 on side[0] (or st), K3 on st and side[1], the ends kernel on st;
+    // synchronises st (and side[0]).  Joins the preparation thread before it touches preads (apply_anchor_ends); without anchor jobs it returns without joining.
+    // Calling thread, beside the preparation thread ----
+    int anchor_stage() {
         std::vector<EdJob> ej; std::vector<WfaJob> wj;
         std::vector<size_t> ej_base(nb + 1, 0), wj_base(nb + 1, 0);
         for (int k = 0; k < nb; ++k) {
@@ -1180,78 +1305,82 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
             for (WfaJob j : b->wfa_jobs) { j.p_off += in_base; j.t_off += in_base; j.s_cap = wfa_default_scap(j.plen, j.tlen, true); wj.push_back(j); } // (the hint may have risen since the region was added)
         }
         ej_base[nb] = ej.size(); wj_base[nb] = wj.size();
-        if (!ej.empty() || !wj.empty()) {
-            std::vector<EdOut> eo; std::vector<WfaOut> wo;
-            // (ONE transient arena per leader for every stage's workspace -- edlib blocks, WFA wavefronts, the chains' DP regions: the stages of a
-            // submission follow each other on the leader's stream and none of them reads another's workspace, so the arena is their maximum, not their sum)
-            const bool th = getenv("LCD_TIME_HOST") != nullptr;
-            if (th) fprintf(stderr, "[host]   anchors: job tables (%zu edlib, %zu WFA) after %.1f ms\n", ej.size(), wj.size(), now_ms() - t_begin);
-            // K4 and K3 of the anchor stage are independent and both latency-bound (one wavefront per pair, 60 % of its cycles waiting): side by side on two
-            // streams when K4's stored columns (1 MiB per pair, edlib's own rule) fit a workspace of their own of up to 20 GB -- 17 000 pairs; larger submissions and the noisy shapes keep the one shared arena and the old order
-            uint64_t ed_tot = 0; for (const EdJob &j : ej) ed_tot += lcd_align_up(ed_arena_bytes(j.qlen, j.tlen), 256);
-            const bool side_by_side = !ej.empty() && !wj.empty() && L->side[0] && ed_tot <= (20ull << 30) && !getenv("LCD_ANCHOR_SEQ");
-            hipStream_t ks = side_by_side ? L->side[0] : st;
-            if (side_by_side) HIPCHK(hipStreamWaitEvent(ks, L->ev[0], 0));
-            int rc = run_edlib_stage(ks, ej, L->d_ed_jobs, side_by_side ? L->d_ed_arena : L->d_poa_arena, L->d_ed_outs, eo, side_by_side);
-            if (rc) return rc;
-            if (th && !side_by_side) { hipStreamSynchronize(st); fprintf(stderr, "[host]   anchors: edlib stage done after %.1f ms\n", now_ms() - t_begin); }
-            // (K3's class launches -- each as long as its longest job -- on the leader's stream and the second side stream: the first has K4, the third the long chains;
-            //  LCD_ANCHOR_WFA_SEQ=1: one after the other on the leader's stream, as before)
-            static const bool k3_two = !(getenv("LCD_ANCHOR_WFA_SEQ") && atoi(getenv("LCD_ANCHOR_WFA_SEQ")) != 0);
-            rc = run_wfa_stage(st, wj, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, wo, sc, nullptr, true, k3_two && side_by_side && L->side[1] ? L->side + 1 : nullptr, L->sev, k3_two && side_by_side && L->side[1] ? 1 : 0);
-            if (rc) return rc;
-            if (side_by_side) { HIPCHK(hipMemcpyAsync(eo.data(), L->d_ed_outs.p, eo.size() * sizeof(EdOut), hipMemcpyDeviceToHost, ks)); HIPCHK(hipStreamSynchronize(ks)); }
+        if (ej.empty() && wj.empty()) return 0;
+        std::vector<EdOut> eo; std::vector<WfaOut> wo;
+        // (ONE transient arena per leader for every stage's workspace -- edlib blocks, WFA wavefronts, the chains' DP regions: the stages of a
+        // submission follow each other on the leader's stream and none of them reads another's workspace, so the arena is their maximum, not their sum)
+        const bool th = env.time_host;
+        if (th) fprintf(stderr, "[host]   anchors: job tables (%zu edlib, %zu WFA) after %.1f ms\n", ej.size(), wj.size(), now_ms() - t_begin);
+        // K4 and K3 of the anchor stage are independent and both latency-bound (one wavefront per pair, 60 % of its cycles waiting): side by side on two
+        // streams when K4's stored columns (1 MiB per pair, edlib's own rule) fit a workspace of their own of up to 20 GB -- 17 000 pairs; larger submissions and the noisy shapes keep the one shared arena and the old order
+        uint64_t ed_tot = 0; for (const EdJob &j : ej) ed_tot += lcd_align_up(ed_arena_bytes(j.qlen, j.tlen), 256);
+        const bool side_by_side = !ej.empty() && !wj.empty() && L->side[0] && ed_tot <= (20ull << 30) && !env.anchor_seq;
+        hipStream_t ks = side_by_side ? L->side[0] : st;
+        if (side_by_side) HIPCHK(hipStreamWaitEvent(ks, L->ev[0], 0));
+        int rc = run_edlib_stage(ks, ej, L->d_ed_jobs, side_by_side ? L->d_ed_arena : L->d_poa_arena, L->d_ed_outs, eo, side_by_side);
+        if (rc) return rc;
+        if (th && !side_by_side) { hipStreamSynchronize(st); fprintf(stderr, "[host]   anchors: edlib stage done after %.1f ms\n", now_ms() - t_begin); }
+        // (K3's class launches -- each as long as its longest job -- on the leader's stream and the second side stream: the first has K4, the third the long chains;
+        //  LCD_ANCHOR_WFA_SEQ=1: one after the other on the leader's stream, as before)
+        const bool k3_two = process_env().anchor_wfa_two;
+        rc = run_wfa_stage(st, wj, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, wo, sc, nullptr, true, k3_two && side_by_side && L->side[1] ? L->side + 1 : nullptr, L->sev, k3_two && side_by_side && L->side[1] ? 1 : 0);
+        if (rc) return rc;
+        if (side_by_side) { HIPCHK(hipMemcpyAsync(eo.data(), L->d_ed_outs.p, eo.size() * sizeof(EdOut), hipMemcpyDeviceToHost, ks)); HIPCHK(hipStreamSynchronize(ks)); }
+        HIPCHK(hipStreamSynchronize(st));
+        if (th) fprintf(stderr, "[host]   anchors: WFA stage done after %.1f ms\n", now_ms() - t_begin);
+        // cigars of the anchor jobs: ONE device->host copy of the output span of all of them (a copy per job costs more in
+        // launch overhead than in bytes)
+        // the alignments' ends (collect_aln_beg_end) are computed where the CIGARs are: 20 bytes per job come back (strings_kernel.hip lcd_anchor_ends_kernel)
+        std::vector<AnchorEndsOut> aends(wj.size());
+        if (!wj.empty()) {
+            std::vector<AnchorEndsJob> aj(wj.size());
+            for (size_t i = 0; i < wj.size(); ++i) { aj[i].cigar = wj[i].out_off; aj[i].n_cigar = wo[i].n_cigar; aj[i].pad_ = 0; }
+            if (L->d_aends_jobs.ensure(aj.size() * sizeof(AnchorEndsJob)) || L->d_aends_outs.ensure(aj.size() * sizeof(AnchorEndsOut))) return -11;
+            HIPCHK(hipMemcpyAsync(L->d_aends_jobs.p, aj.data(), aj.size() * sizeof(AnchorEndsJob), hipMemcpyHostToDevice, st));
+            lcd_launch_anchor_ends((const AnchorEndsJob *)L->d_aends_jobs.p, (AnchorEndsOut *)L->d_aends_outs.p, (int)aj.size(), st);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(aends.data(), L->d_aends_outs.p, aends.size() * sizeof(AnchorEndsOut), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            if (th) fprintf(stderr, "[host]   anchors: WFA stage done after %.1f ms\n", now_ms() - t_begin);
-            // cigars of the anchor jobs: ONE device->host copy of the output span of all of them (a copy per job costs more in
-            // launch overhead than in bytes)
-            // the alignments' ends (collect_aln_beg_end) are computed where the CIGARs are: 20 bytes per job come back (strings_kernel.hip lcd_anchor_ends_kernel)
-            std::vector<AnchorEndsOut> aends(wj.size());
-            if (!wj.empty()) {
-                std::vector<AnchorEndsJob> aj(wj.size());
-                for (size_t i = 0; i < wj.size(); ++i) { aj[i].cigar = wj[i].out_off; aj[i].n_cigar = wo[i].n_cigar; aj[i].pad_ = 0; }
-                if (L->d_aends_jobs.ensure(aj.size() * sizeof(AnchorEndsJob)) || L->d_aends_outs.ensure(aj.size() * sizeof(AnchorEndsOut))) return -11;
-                HIPCHK(hipMemcpyAsync(L->d_aends_jobs.p, aj.data(), aj.size() * sizeof(AnchorEndsJob), hipMemcpyHostToDevice, st));
-                lcd_launch_anchor_ends((const AnchorEndsJob *)L->d_aends_jobs.p, (AnchorEndsOut *)L->d_aends_outs.p, (int)aj.size(), st);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipMemcpyAsync(aends.data(), L->d_aends_outs.p, aends.size() * sizeof(AnchorEndsOut), hipMemcpyDeviceToHost, st));
-                HIPCHK(hipStreamSynchronize(st));
-            }
-            if (th) fprintf(stderr, "[host]   anchors: alignment ends (%.2f MB) on the host after %.1f ms\n", aends.size() * sizeof(AnchorEndsOut) / 1e6, now_ms() - t_begin);
-            for (auto &e : eo) if (e.status != LCD_OK) return set_err(-20, "edlib kernel status " + std::to_string(e.status));
-            { const int rcp = join_prep(); if (rcp) return rcp; } // (the read tables below are the helper thread's)
-            for (int k = 0; k < nb; ++k) {
-                lcd_batch_t *b = bs[k]; lcd_batch_stats_t &S = b->st;
-                for (size_t i = ej_base[k]; i < ej_base[k + 1]; ++i) S.edlib_blocks += eo[i].blocks;
-                for (size_t i = wj_base[k]; i < wj_base[k + 1]; ++i) S.wfa_offsets += wo[i].offsets;
-                S.n_edlib_jobs = (int)(ej_base[k + 1] - ej_base[k]); S.n_wfa_jobs += (int)(wj_base[k + 1] - wj_base[k]);
-                for (const AnchorRec &A : b->anchors) {
-                    PoaRead &pr = preads[k][A.pread];
-                    const int x = eo[ej_base[k] + A.ed_job].xgaps;
-                    if (x > A.min_len * 0.10) { pr.skip = 1; continue; }
-                    if (A.ext == 0) continue;
-                    const size_t wi = wj_base[k] + A.wfa_job;
-                    const int ncg = wo[wi].n_cigar;
-                    if (ncg == 0) { pr.skip = 1; continue; }
-                    // collect_aln_beg_end, src/align.c:630-663: left to right the end of the last '=' run, right to left the start of the first one (counted back from
-                    // tlen + 1 / qlen + 1); an alignment without a '=' run keeps the whole sequences
-                    const AnchorEndsOut &ae = aends[wi];
-                    int rb = 1, qb = 1, re = A.tlen_full, qe = A.qlen_full;
-                    if (ae.has_eq) {
-                        if (A.ext == 1) { re = ae.pre_r; qe = ae.pre_q; }
-                        else { rb = A.tlen_full + 1 - ae.suf_r; qb = A.qlen_full + 1 - ae.suf_q; }
-                    }
-                    pr.ref_beg = rb; pr.ref_end = re; pr.read_beg = qb; pr.read_end = qe;
+        }
+        if (th) fprintf(stderr, "[host]   anchors: alignment ends (%.2f MB) on the host after %.1f ms\n", aends.size() * sizeof(AnchorEndsOut) / 1e6, now_ms() - t_begin);
+        for (auto &e : eo) if (e.status != LCD_OK) return set_err(-20, "edlib kernel status " + std::to_string(e.status));
+        { const int rcp = join_prep(); if (rcp) return rcp; } // (the read tables below are the helper thread's)
+        apply_anchor_ends(ej_base, wj_base, eo, wo, aends);
+        return 0;
+    }
+    // the anchor stage's verdicts and narrowed ends, into the read tables.  Reads: the anchor stage's results, the batches' anchors.  Writes: preads (skip, the four
+    // ends), the batches' anchor statistics.  Calling thread, after join_prep
+    void apply_anchor_ends(const std::vector<size_t> &ej_base, const std::vector<size_t> &wj_base, const std::vector<EdOut> &eo, const std::vector<WfaOut> &wo, const std::vector<AnchorEndsOut> &aends) {
+        for (int k = 0; k < nb; ++k) {
+            lcd_batch_t *b = bs[k]; lcd_batch_stats_t &S = b->st;
+            for (size_t i = ej_base[k]; i < ej_base[k + 1]; ++i) S.edlib_blocks += eo[i].blocks;
+            for (size_t i = wj_base[k]; i < wj_base[k + 1]; ++i) S.wfa_offsets += wo[i].offsets;
+            S.n_edlib_jobs = (int)(ej_base[k + 1] - ej_base[k]); S.n_wfa_jobs += (int)(wj_base[k + 1] - wj_base[k]);
+            for (const AnchorRec &A : b->anchors) {
+                PoaRead &pr = preads[k][A.pread];
+                const int x = eo[ej_base[k] + A.ed_job].xgaps;
+                if (x > A.min_len * 0.10) { pr.skip = 1; continue; }
+                if (A.ext == 0) continue;
+                const size_t wi = wj_base[k] + A.wfa_job;
+                const int ncg = wo[wi].n_cigar;
+                if (ncg == 0) { pr.skip = 1; continue; }
+                // collect_aln_beg_end, src/align.c:630-663: left to right the end of the last '=' run, right to left the start of the first one (counted back from
+                // tlen + 1 / qlen + 1); an alignment without a '=' run keeps the whole sequences
+                const AnchorEndsOut &ae = aends[wi];
+                int rb = 1, qb = 1, re = A.tlen_full, qe = A.qlen_full;
+                if (ae.has_eq) {
+                    if (A.ext == 1) { re = ae.pre_r; qe = ae.pre_q; }
+                    else { rb = A.tlen_full + 1 - ae.suf_r; qb = A.qlen_full + 1 - ae.suf_q; }
                 }
+                pr.ref_beg = rb; pr.ref_end = re; pr.read_beg = qb; pr.read_end = qe;
             }
         }
     }
-    { const int rcp = join_prep(); if (rcp) return rcp; }
-    HIPCHK(hipEventRecord(L->ev[1], st));
-    const double tp0 = now_ms();
-    if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host] anchor stage: %.1f ms on the host clock\n", tp0 - t_begin);
+
     // ---------------- S2: POA chains ----------------
-    if (nC_all) {
+    // the read table: only what the anchor stage changed when it went up with the long chains (reads_up), else all of it.  Reads: preads, reads_up, the batches'
+    // anchors.  Writes: d_preads (st; waits for ev[8]), sizes d_chains / d_poa_outs.  Calling thread, after join_prep
+    int upload_reads() {
         if (L->d_preads.ensure(pread_base[nb] * sizeof(PoaRead)) || L->d_chains.ensure(nC_all * sizeof(PoaChain)) || L->d_poa_outs.ensure(nC_all * sizeof(PoaChainOut))) return -11;
         if (reads_up) { // only what the anchor stage changed
             std::vector<ReadPatch> pt;
@@ -1265,29 +1394,47 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
                 HIPCHK(hipStreamSynchronize(st)); // (pt is a local)
             }
         } else
-        for (int k = 0; k < nb; ++k)
-            if (!preads[k].empty())
-                HIPCHK(hipMemcpyAsync((PoaRead *)L->d_preads.p + pread_base[k], preads[k].data(), preads[k].size() * sizeof(PoaRead), hipMemcpyHostToDevice, st));
+            for (int k = 0; k < nb; ++k)
+                if (!preads[k].empty())
+                    HIPCHK(hipMemcpyAsync((PoaRead *)L->d_preads.p + pread_base[k], preads[k].data(), preads[k].size() * sizeof(PoaRead), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    // up to 12 rounds: the chains of `which`, then those that came back.  Reads / writes: everything the rounds' steps do (below).  Calling thread, after join_prep
+    int poa_stage() {
+        if (!nC_all) return 0;
+        if (const int rc = upload_reads()) return rc;
         if (!order_async) prepare_round0();
-        if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   POA prep: classes + order after %.1f ms\n", now_ms() - tp0);
-        int scale = 1;
-        std::map<size_t, uint64_t> retry_out_off; // chains whose output block moved to a retry buffer
+        if (env.time_host) fprintf(stderr, "[host]   POA prep: classes + order after %.1f ms\n", now_ms() - tp0);
         for (int k = 0; k < nb; ++k) bs[k]->retry_out_used = 0;
         for (int round = 0; round < 12 && !which.empty(); ++round) {
-            ArenaPlan P;
-            if (round == 0 && plan0.valid) P = std::move(plan0);
-            else P.need.assign(which.size(), 0);
-            const bool planned = P.valid;
-            uint64_t &tot = P.tot; std::vector<uint64_t> &need = P.need;
-            L->h_sub_pin.resize(which.size() * sizeof(PoaChain));
-            PoaChain *const sub = (PoaChain *)L->h_sub_pin.data(); const size_t sub_n = which.size();
-            if (!planned) for (size_t i = 0; i < which.size(); ++i) {
+            PoaRound R; R.round = round;
+            int rc = plan_round(R);
+            if (!rc) rc = place_arenas(R);
+            if (!rc) rc = spare_pool(R);
+            if (!rc) rc = launch_round(R);
+            if (!rc) rc = judge_round(R);
+            if (rc) return rc;
+        }
+        if (!which.empty()) return set_err(-21, "POA DP arena exhausted after retries");
+        return 0;
+    }
+    // a round's chain table and arena layout: round 0 takes plan0 when the preparation thread made it; a later round re-sizes its chains (retry_scale), gives a chain whose
+    // graph capacity grew a fresh output block of its batch, and lays the arenas out again.  Reads: which, plan0, scale, ChainRec, preads.  Writes: R.P, R.sub / R.sub_n,
+    // pchains (capacities, out_off, ws_off, slot fields), retry_out_off, the batches' retry_out.  Calling thread
+    int plan_round(PoaRound &R) {
+        ArenaPlan &P = R.P;
+        if (R.round == 0 && plan0.valid) P = std::move(plan0);
+        else P.need.assign(which.size(), 0);
+        const bool planned = P.valid;
+        L->h_sub_pin.resize(which.size() * sizeof(PoaChain));
+        R.sub = (PoaChain *)L->h_sub_pin.data(); R.sub_n = which.size();
+        if (!planned) {
+            for (size_t i = 0; i < which.size(); ++i) {
                 const int k = chain_batch[which[i]]; const size_t c = which[i] - chain_base[k];
-                PoaChain &pc = bs[k]->pchains[c];
-                if (round) {
+                PoaChain &pc = chain(which[i]);
+                if (R.round) {
                     const int old_cap = pc.node_cap;
-                    const ChainRec &CR = bs[k]->chains[c];   // (a chain sent back by the certified band starts its capacity ladder in the round after)
-                    chain_caps(bs[k]->opt, CR, preads[k], CR.cert_fail_round < 0 ? scale : std::max(1, scale >> (CR.cert_fail_round + 1)), pc, cenv);
+                    chain_caps(bs[k]->opt, rec(which[i]), preads[k], retry_scale(rec(which[i]), scale), pc, cenv);
                     if (pc.node_cap > old_cap) { // the chain's output block (cons + MSA rows of node_cap columns) grows with it: a fresh block
                         lcd_batch_t *b = bs[k];
                         if (b->retry_out_used == b->retry_out.size()) b->retry_out.emplace_back(new DevBuf());
@@ -1296,180 +1443,148 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
                         pc.out_off = ro2->addr(); retry_out_off[which[i]] = pc.out_off;
                     } else pc.out_off = retry_out_off.count(which[i]) ? retry_out_off[which[i]] : bs[k]->d_poa_out.addr() + out_rel[k][c];
                 }
-                need[i] = poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, pc.cell_cap, pc.n_reads, pc.spill_x, pc.cert).total;
+                P.need[i] = poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, pc.cell_cap, pc.n_reads, pc.spill_x, pc.cert).total;
             }
-            // Work arenas.  A chain's arena is live only while its workgroup is resident, and a CU holds at most per_cu workgroups of a launch group:
-            // runs of chains of one launch group and one size class (half octaves of the arena size) that outnumber the chip's capacity share a pool of
-            // n_cu x per_cu SLOTS claimed at workgroup start (poa_kernel.hip); the others keep private arenas.  Memory then scales with resident
-            // workgroups, not with the number of chains in flight.
-            if (!planned) segment_arenas(P);
-            uint64_t &flag_ints = P.flag_ints; size_t &n_pooled = P.n_pooled, &n_pools = P.n_pools; uint64_t &private_bytes = P.private_bytes, &pool_bytes = P.pool_bytes;
-            std::vector<Item> &items = P.items; std::vector<uint32_t> &item_of = P.item_of;
-            if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   POA prep: arenas laid out after %.1f ms\n", now_ms() - tp0);
-            if (getenv("LCD_MEM_DEBUG")) fprintf(stderr, "[mem] round %d arenas: %zu chains in %zu slot pools (%.2f GB), %zu with private arenas (%.2f GB)\n", round, n_pooled, n_pools, pool_bytes / 1e9, which.size() - n_pooled, private_bytes / 1e9);
-            if (flag_ints) {
-                if (L->d_slot_flags.ensure(flag_ints * 4 + 64)) return -11;
-                HIPCHK(hipMemsetAsync(L->d_slot_flags.p, 0, flag_ints * 4, st));
-            }
-            if (getenv("LCD_MEM_DEBUG")) {
-                double cellb = 0, nodeb = 0; double worstc = 0; size_t nbig = 0;
-                for (size_t i = 0; i < which.size(); ++i) { const PoaChain &pc = PC(which[i]); cellb += (pc.spill_x > 2 ? 5.0 + pc.spill_x : 4.0) * pc.cell_cap; PoaLayout Lay = poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, 0, pc.n_reads); nodeb += (double)Lay.total; if (4.0 * pc.cell_cap > worstc) worstc = 4.0 * pc.cell_cap; nbig += 4.0 * pc.cell_cap > 64e6; }
-                fprintf(stderr, "[mem] round %d: %zu chains, arena %.2f GB = DP regions %.2f GB (largest %.1f MB, %zu above 64 MB) + graph/plan arrays %.2f GB\n", round, which.size(), tot / 1e9, cellb / 1e9, worstc / 1e6, nbig, nodeb / 1e9);
-            }
-            { // placement: first fit over [d_poa_arena, extra chunks...] in item order; one more chunk (what is left of this submission) when they are full
-                if (L->d_poa_arena.cap == 0 && L->d_poa_arena.ensure(tot, 3)) return -11;
-                std::vector<DevBuf *> ch(1, &L->d_poa_arena);
-                for (auto &c : L->arena_extra) ch.push_back(c.get());
-                size_t k = 0; uint64_t off = 0, left = tot;
-                for (Item &it : items) {
-                    while (k < ch.size() && off + it.bytes > ch[k]->cap) { ++k; off = 0; }
-                    if (k == ch.size()) {
-                        L->arena_extra.emplace_back(new DevBuf());
-                        if (L->arena_extra.back()->ensure(left, 3)) { L->arena_extra.pop_back(); return -11; }
-                        ch.push_back(L->arena_extra.back().get());
-                        if (getenv("LCD_MEM_DEBUG")) fprintf(stderr, "[mem] arena chunk %zu: %.2f GB\n", ch.size() - 1, ch.back()->cap / 1e9);
-                    }
-                    it.phys = ch[k]->addr() + off; off += it.bytes; left -= it.bytes;
-                }
-            }
-            par_chunks(which.size(), host_team(), 4096, [&](const size_t lo, const size_t hi, int) { for (size_t i = lo; i < hi; ++i) {
-                const int k = chain_batch[which[i]];
-                PoaChain &pc = PC(which[i]);
-                pc.ws_off = items[item_of[i]].phys + (pc.ws_off - items[item_of[i]].start);
-                if (pc.slot_flags) pc.slot_flags = L->d_slot_flags.addr() + (pc.slot_flags - 1) * 4;
-                sub[i] = pc; sub[i].read0 += (int)pread_base[k]; // the device read table is the concatenation of the batches' tables
-            } });
-            // Spare DP memory (PoaSpare, poa_kernel.hip grow_dp_region): what a chain whose estimate was too small for one of its reads continues in.  Taken
-            // after the arenas have their memory, from what the budget leaves (LCD_SPARE_GB caps it, 0 switches it off); without it -- or once it is used
-            // up -- such a chain comes back with LCD_ERR_CELLS and is re-run from its first read in the next round, as before.
-            PoaSpare *d_spare = nullptr;
-            PoaSpare spare_hdr; // (lives until the round's stream synchronisation below: the source of an asynchronous copy)
-            {
-                // (noisy reads: 16 GB were used up by ~200 regions of an SV-shape submission and the chains refused after that -- a 36-read x 8 kb chain among them --
-                //  started over in a second round of 3 s)
-                const double spare_gb = getenv("LCD_SPARE_GB") ? atof(getenv("LCD_SPARE_GB")) : L->opt.is_ont ? 32.0 : 16.0; // (read per call: tests switch it)
-                if (spare_gb <= 0) L->d_spare.release();
-                else if (L->d_spare.cap == 0) {
-                    const long long room = (dev_budget(L->device) - g_dev_bytes[L->device].load() - (4ll << 30)) / 2;
-                    const long long want = std::min<long long>((long long)(spare_gb * (double)(1ll << 30)), room);
-                    if (want >= (64ll << 20) && L->d_spare.ensure((size_t)want, 40)) { /* no spare pool this time */ }
-                }
-                if (L->d_spare.cap > 4096) {
-                    spare_hdr.used = 0; spare_hdr.cap = L->d_spare.cap - 256; spare_hdr.base = L->d_spare.addr() + 256; spare_hdr.n_grown = spare_hdr.n_refused = 0;
-                    HIPCHK(hipMemcpyAsync(L->d_spare.p, &spare_hdr, sizeof(spare_hdr), hipMemcpyHostToDevice, st));
-                    d_spare = (PoaSpare *)L->d_spare.p;
-                }
-            }
-            if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host] POA stage: %.1f ms of host work before the launches of round %d\n", now_ms() - tp0, round);
-            HIPCHK(hipEventRecord(L->ev[6], st));
-            { int rc2 = launch_poa_grouped(st, sub, sub_n, L->d_chains, (const PoaRead *)L->d_preads.p, L->d_poa_outs, sc, L->side, L->sev, &L->d_gate, d_spare, round == 0 && !early.empty() ? 3 : -1, early_load, L->opt.is_ont != 0); if (rc2) return rc2; }
-            HIPCHK(hipEventRecord(L->ev[7], st));
-            L->h_tmp_pin.resize((sub_n + (round == 0 ? early.size() : 0)) * sizeof(PoaChainOut)); // (with room for the early chains' records: appending them to a vector re-allocated 9 MB with the GPU idle)
-            PoaChainOut *const tmp = (PoaChainOut *)L->h_tmp_pin.data();
-            HIPCHK(hipMemcpyAsync(tmp, L->d_poa_outs.p, sub_n * sizeof(PoaChainOut), hipMemcpyDeviceToHost, st));
-            PoaSpare spare_seen; spare_seen.used = 0; spare_seen.n_grown = spare_seen.n_refused = 0;
-            if (d_spare) HIPCHK(hipMemcpyAsync(&spare_seen, d_spare, sizeof(PoaSpare), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   round %d: kernels and statuses back %.1f ms after the stage's start\n", round, now_ms() - tp0);
-            if (round == 0 && !early.empty()) { // the long chains that started before the anchor stage: from here on they are chains of this round like the others
-                HIPCHK(hipMemcpyAsync(tmp + sub_n, L->d_poa_outs_early.p, early.size() * sizeof(PoaChainOut), hipMemcpyDeviceToHost, es));
-                HIPCHK(hipStreamSynchronize(es));
-                which.insert(which.end(), early.begin(), early.end());
-            }
-            if (d_spare) {
-                bs[0]->st.poa_grown += (int)spare_seen.n_grown; // (a count of the launch set: kept on the leader, so that the batches' statistics add up)
-                if (getenv("LCD_MEM_DEBUG")) fprintf(stderr, "[mem] round %d: spare DP memory %.2f GB: %u regions grown in place (%.2f GB), %u refused\n", round, L->d_spare.cap / 1e9, spare_seen.n_grown, spare_seen.used / 1e9, spare_seen.n_refused);
-            }
-            { float kms = 0; hipEventElapsedTime(&kms, L->ev[6], L->ev[7]); for (int k = 0; k < nb; ++k) { bs[k]->st.ms_poa_kernel += kms; bs[k]->st.n_poa_launches++; }
-              if (getenv("LCD_MEM_DEBUG")) fprintf(stderr, "[mem] round %d: %zu chains, POA kernels %.1f ms\n", round, which.size(), kms); }
-            std::vector<size_t> again; size_t n_node_ovf = 0, n_cert_fail = 0;
-            // (the chains' output records -- 200 B each, 46 000 of them in a 20-batch submission -- go to their batches on a few threads: serial this was 3.4 ms
-            //  with the GPU idle; the chains that did not end with LCD_OK are few and are looked at one by one below)
-            std::vector<size_t> flagged;
-            {
-                constexpr int NTH = 32; const int nth_r = host_team();
-                std::vector<size_t> fl[NTH];
-                par_chunks(which.size(), nth_r, 2048, [&](const size_t lo, const size_t hi, const int t) {
-                    for (size_t i = lo; i < hi; ++i) {
-                        const int k = chain_batch[which[i]];
-                        bs[k]->couts[which[i] - chain_base[k]] = tmp[i];
-                        if (tmp[i].status != LCD_OK) fl[t].push_back(i);
-                    }
-                });
-                for (int t = 0; t < NTH; ++t) flagged.insert(flagged.end(), fl[t].begin(), fl[t].end());
-                std::sort(flagged.begin(), flagged.end());
-            }
-            if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   round %d: records in their batches %.1f ms after the stage's start (%zu not LCD_OK)\n", round, now_ms() - tp0, flagged.size());
-            for (const size_t i : flagged) {
-                const int k = chain_batch[which[i]];
-                if (tmp[i].status == LCD_ERR_CELLS || tmp[i].status == LCD_ERR_NODES || tmp[i].status == LCD_ERR_EDGES) { again.push_back(which[i]); n_node_ovf += tmp[i].status != LCD_ERR_CELLS; }
-                else if (tmp[i].status == LCD_ERR_CERT && PC(which[i]).cert > 0) { // one class up (512, 1 024 columns), then full rows
-                    ChainRec &CR = bs[k]->chains[which[i] - chain_base[k]];
-                    CR.cert_fail_round = round; CR.cert_level = cert_next_level(PC(which[i]));
-                    again.push_back(which[i]); ++n_cert_fail;
-                }
-                else if (tmp[i].status != LCD_OK) { const PoaChain &pc = PC(which[i]);
-                    if (const char *dump = getenv("LCD_DUMP_CHAIN")) { // the failing chain's reads, for a replay in isolation (tools/replay_chain.py): header, then per read {len, skip, anchors, bases}
-                        if (FILE *f = fopen(dump, "wb")) {
-                            const int hdr[8] = {0x4c434443, pc.mode, pc.n_reads, tmp[i].status, pc.threads, pc.wmax, pc.ring_k, pc.lds_words * 4};
-                            fwrite(hdr, sizeof(int), 8, f);
-                            const std::vector<PoaRead> &pr = preads[k];
-                            for (int q = 0; q < pc.n_reads; ++q) {
-                                const PoaRead &r = pr[pc.read0 + q];
-                                const int rec[6] = {r.len, r.skip, r.ref_beg, r.ref_end, r.read_beg, r.read_end};
-                                fwrite(rec, sizeof(int), 6, f);
-                                std::vector<uint8_t> bases((size_t)std::max(r.len, 0));
-                                if (r.len > 0) (void)hipMemcpy(bases.data(), (const void *)(uintptr_t)r.seq_off, (size_t)r.len, hipMemcpyDeviceToHost);
-                                fwrite(bases.data(), 1, bases.size(), f);
-                            }
-                            fclose(f);
-                        }
-                    }
-                    return set_err(-20, "POA kernel status " + std::to_string(tmp[i].status) + " on chain " + std::to_string(which[i] - chain_base[k]) + " of batch " + std::to_string(k) + " (mode " + std::to_string(pc.mode) +
-                                   ", " + std::to_string(pc.n_reads) + " reads, longest " + std::to_string(pc.max_len) + ", threads " + std::to_string(pc.threads) + ", window " + std::to_string(pc.wmax) + ", ring slots " +
-                                   std::to_string(pc.ring_k) + ", LDS " + std::to_string(pc.lds_words * 4) + " B, nodes " + std::to_string(tmp[i].n_node) + "/" + std::to_string(pc.node_cap) + ", reads aligned " + std::to_string(tmp[i].n_aligned_reads) + ")" +
-                                   (tmp[i].status == LCD_ERR_WATCHDOG ? [&] { std::string t = "; last backtrack states (row, column, state):"; const unsigned long long w[4] = {tmp[i].t_plan, tmp[i].t_poll, tmp[i].t_bp, tmp[i].t_add};
-                                        for (int q = 0; q < 4; ++q) t += " (" + std::to_string((unsigned)(w[q] & 0xffffffffu)) + ", " + std::to_string((unsigned)((w[q] >> 32) & 0xffffff)) + ", " + std::to_string((unsigned)(w[q] >> 56)) + ")"; return t; }() : std::string())); }
-            }
-            if (getenv("LCD_MEM_DEBUG")) {
-                { size_t nc = 0; for (size_t g : which) nc += PC(g).cert != 0; fprintf(stderr, "[mem] round %d: %zu chains with a certified band, %zu sent back for full rows\n", round, nc, n_cert_fail); }
-                if (getenv("LCD_CERT_DEBUG")) for (size_t i = 0; i < which.size(); ++i) { const PoaChain &pc = PC(which[i]); if (!pc.cert) continue; const int k = chain_batch[which[i]];
-                    std::vector<int> ls; for (int r = 0; r < pc.n_reads; ++r) ls.push_back(preads[k][pc.read0 + r].len); std::sort(ls.begin(), ls.end());
-                    fprintf(stderr, "[cert] %s n %d max %d p75 %d med %d p25 %d min %d nodes %d\n", tmp[i].status == LCD_ERR_CERT ? "FAIL" : "ok  ", pc.n_reads, ls.back(), ls[ls.size() * 3 / 4], ls[ls.size() / 2], ls[ls.size() / 4], ls[0], tmp[i].n_node); if (tmp[i].status == LCD_ERR_CERT) fprintf(stderr, "[cert]    why %llu  attempt/qlen %llu  aligned reads %d hist?\n", tmp[i].t_plan, tmp[i].t_poll, tmp[i].n_aligned_reads); }
-                if (getenv("LCD_RETRY_DEBUG")) for (size_t g : again) { const PoaChain &pc = PC(g); const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]];
-                    fprintf(stderr, "[retry] round %d status %d: thr %d mode %d reads %d maxlen %d | caps nodes %d edges %d cells %llu (worst %llu) spill_x %d | reached nodes %d edges %d aligned reads %d cells %llu\n", round, o.status,
-                            chain_threads(pc), pc.mode, pc.n_reads, pc.max_len, pc.node_cap, pc.edge_cap, (unsigned long long)pc.cell_cap, (unsigned long long)pc.node_cap * (pc.max_len + 1), pc.spill_x, o.n_node, o.n_edge, o.n_aligned_reads, o.cells); }
-                int c[2][3] = {{0, 0, 0}, {0, 0, 0}};
-                for (size_t g : again) { const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]]; c[PC(g).mode ? 1 : 0][o.status == LCD_ERR_CELLS ? 0 : o.status == LCD_ERR_NODES ? 1 : 2]++; }
-                { std::map<int, std::pair<int, int>> byc; for (size_t g : which) if (PC(g).mode) byc[chain_threads(PC(g))].second++; for (size_t g : again) if (PC(g).mode) byc[chain_threads(PC(g))].first++;
-                  for (auto &kv : byc) fprintf(stderr, "[mem]   K2 class %4d: %d of %d overflow\n", kv.first, kv.second.first, kv.second.second); }
-                fprintf(stderr, "[mem] round %d overflows: K1 cells %d nodes %d edges %d | K2 cells %d nodes %d edges %d (hints: cells %d/%d nodes %d)\n", round, c[0][0], c[0][1], c[0][2], c[1][0], c[1][1], c[1][2],
-                        g_cell_hint[0].load(), g_cell_hint[1].load(), g_node_hint.load());
-            }
-            if (round == 0 && n_node_ovf * 20 > nC_all && g_node_hint.load() < 2) g_node_hint++;
-            if (round == 0) { // learn: more than 1 % of a mode's chains overflowed their DP region -> start from the next estimate next time
-                int tot[2] = {0, 0}, ovf[2] = {0, 0};
-                for (size_t g = 0; g < nC_all; ++g) tot[PC(g).mode ? 1 : 0]++;
-                for (size_t g : again) if (bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]].status != LCD_ERR_CERT) ovf[PC(g).mode ? 1 : 0]++;
-                for (int m = 0; m < 2; ++m) if (tot[m] && ovf[m] * 100 > tot[m] && g_cell_hint[m].load() < 2) g_cell_hint[m]++;
-            }
-            if (!again.empty()) { for (int k = 0; k < nb; ++k) bs[k]->st.poa_retries++; scale *= 2; }
-            which.swap(again);
+            segment_arenas(P);
         }
-        if (!which.empty()) return set_err(-21, "POA DP arena exhausted after retries");
+        if (env.time_host) fprintf(stderr, "[host]   POA prep: arenas laid out after %.1f ms\n", now_ms() - tp0);
+        if (env.mem_debug) report_round_memory(*this, R);
+        return 0;
     }
-    if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host] POA stage ends %.1f ms after its start\n", now_ms() - tp0);
-    HIPCHK(hipEventRecord(L->ev[2], st));
-    const double th0 = now_ms();
+    // device memory for the layout.  placement: first fit over [d_poa_arena, extra chunks...] in item order; one more chunk (what is left of this submission) when
+    // they are full.  Reads: R.P, which.  Writes: the slot flags (memset on st), the leader's arena chunks, the chains' final ws_off / slot_flags, R.sub.  Calling
+    // thread, with one team
+    int place_arenas(PoaRound &R) {
+        ArenaPlan &P = R.P;
+        if (P.flag_ints) {
+            if (L->d_slot_flags.ensure(P.flag_ints * 4 + 64)) return -11;
+            HIPCHK(hipMemsetAsync(L->d_slot_flags.p, 0, P.flag_ints * 4, st));
+        }
+        {
+            if (L->d_poa_arena.cap == 0 && L->d_poa_arena.ensure(P.tot, 3)) return -11;
+            std::vector<DevBuf *> ch(1, &L->d_poa_arena);
+            for (auto &c : L->arena_extra) ch.push_back(c.get());
+            size_t k = 0; uint64_t off = 0, left = P.tot;
+            for (ArenaItem &it : P.items) {
+                while (k < ch.size() && off + it.bytes > ch[k]->cap) { ++k; off = 0; }
+                if (k == ch.size()) {
+                    L->arena_extra.emplace_back(new DevBuf());
+                    if (L->arena_extra.back()->ensure(left, 3)) { L->arena_extra.pop_back(); return -11; }
+                    ch.push_back(L->arena_extra.back().get());
+                    if (env.mem_debug) fprintf(stderr, "[mem] arena chunk %zu: %.2f GB\n", ch.size() - 1, ch.back()->cap / 1e9);
+                }
+                it.phys = ch[k]->addr() + off; off += it.bytes; left -= it.bytes;
+            }
+        }
+        par_chunks(which.size(), host_team(), 4096, [&](const size_t lo, const size_t hi, int) { for (size_t i = lo; i < hi; ++i) {
+            PoaChain &pc = chain(which[i]);
+            pc.ws_off = P.items[P.item_of[i]].phys + (pc.ws_off - P.items[P.item_of[i]].start);
+            if (pc.slot_flags) pc.slot_flags = L->d_slot_flags.addr() + (pc.slot_flags - 1) * 4;
+            R.sub[i] = pc; R.sub[i].read0 += (int)pread_base[chain_batch[which[i]]]; // the device read table is the concatenation of the batches' tables
+        } });
+        return 0;
+    }
+    // Spare DP memory (PoaSpare, poa_kernel.hip grow_dp_region): what a chain whose estimate was too small for one of its reads continues in.  Taken
+    // after the arenas have their memory, from what the budget leaves (LCD_SPARE_GB caps it, 0 switches it off); without it -- or once it is used
+    // up -- such a chain comes back with LCD_ERR_CELLS and is re-run from its first read in the next round, as before.
+    // Reads: env, the device's budget.  Writes: the leader's d_spare (header copy on st), R.d_spare, R.spare_hdr.  Calling thread
+    int spare_pool(PoaRound &R) {
+        // (noisy reads: 16 GB were used up by ~200 regions of an SV-shape submission and the chains refused after that -- a 36-read x 8 kb chain among them --
+        //  started over in a second round of 3 s)
+        const double spare_gb = env.spare_set ? env.spare_gb : L->opt.is_ont ? 32.0 : 16.0; // (read per call: tests switch it)
+        if (spare_gb <= 0) L->d_spare.release();
+        else if (L->d_spare.cap == 0) {
+            const long long room = (dev_budget(L->device) - g_dev_bytes[L->device].load() - (4ll << 30)) / 2;
+            const long long want = std::min<long long>((long long)(spare_gb * (double)(1ll << 30)), room);
+            if (want >= (64ll << 20) && L->d_spare.ensure((size_t)want, 40)) { /* no spare pool this time */ }
+        }
+        if (L->d_spare.cap > 4096) { // (R.spare_hdr lives until the round's stream synchronisation: the source of an asynchronous copy)
+            R.spare_hdr.used = 0; R.spare_hdr.cap = L->d_spare.cap - 256; R.spare_hdr.base = L->d_spare.addr() + 256; R.spare_hdr.n_grown = R.spare_hdr.n_refused = 0;
+            HIPCHK(hipMemcpyAsync(L->d_spare.p, &R.spare_hdr, sizeof(R.spare_hdr), hipMemcpyHostToDevice, st));
+            R.d_spare = (PoaSpare *)L->d_spare.p;
+        }
+        return 0;
+    }
+    // the round's launches, and its records back on the host; after round 0 the early chains join `which`.  Reads: R.sub, R.d_spare, early, early_load.  Writes: ev[6],
+    // ev[7], the launch groups on st and side[] (launch_poa_grouped), R.tmp, R.spare_seen, which (+= early), the batches' kernel-time statistics; synchronises st (round 0
+    // with early chains: es too).  Calling thread
+    int launch_round(PoaRound &R) {
+        const int round = R.round; const size_t sub_n = R.sub_n;
+        if (env.time_host) fprintf(stderr, "[host] POA stage: %.1f ms of host work before the launches of round %d\n", now_ms() - tp0, round);
+        HIPCHK(hipEventRecord(L->ev[6], st));
+        { int rc2 = launch_poa_grouped(st, R.sub, sub_n, L->d_chains, (const PoaRead *)L->d_preads.p, L->d_poa_outs, sc, L->side, L->sev, &L->d_gate, R.d_spare, round == 0 && !early.empty() ? 3 : -1, early_load, L->opt.is_ont != 0); if (rc2) return rc2; }
+        HIPCHK(hipEventRecord(L->ev[7], st));
+        L->h_tmp_pin.resize((sub_n + (round == 0 ? early.size() : 0)) * sizeof(PoaChainOut)); // (with room for the early chains' records: appending them to a vector re-allocated 9 MB with the GPU idle)
+        R.tmp = (PoaChainOut *)L->h_tmp_pin.data();
+        HIPCHK(hipMemcpyAsync(R.tmp, L->d_poa_outs.p, sub_n * sizeof(PoaChainOut), hipMemcpyDeviceToHost, st));
+        R.spare_seen.used = 0; R.spare_seen.n_grown = R.spare_seen.n_refused = 0;
+        if (R.d_spare) HIPCHK(hipMemcpyAsync(&R.spare_seen, R.d_spare, sizeof(PoaSpare), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (env.time_host) fprintf(stderr, "[host]   round %d: kernels and statuses back %.1f ms after the stage's start\n", round, now_ms() - tp0);
+        if (round == 0 && !early.empty()) { // the long chains that started before the anchor stage: from here on they are chains of this round like the others
+            HIPCHK(hipMemcpyAsync(R.tmp + sub_n, L->d_poa_outs_early.p, early.size() * sizeof(PoaChainOut), hipMemcpyDeviceToHost, es));
+            HIPCHK(hipStreamSynchronize(es));
+            which.insert(which.end(), early.begin(), early.end());
+        }
+        if (R.d_spare) {
+            bs[0]->st.poa_grown += (int)R.spare_seen.n_grown; // (a count of the launch set: kept on the leader, so that the batches' statistics add up)
+            if (env.mem_debug) fprintf(stderr, "[mem] round %d: spare DP memory %.2f GB: %u regions grown in place (%.2f GB), %u refused\n", round, L->d_spare.cap / 1e9, R.spare_seen.n_grown, R.spare_seen.used / 1e9, R.spare_seen.n_refused);
+        }
+        float kms = 0; hipEventElapsedTime(&kms, L->ev[6], L->ev[7]);
+        for (int k = 0; k < nb; ++k) { bs[k]->st.ms_poa_kernel += kms; bs[k]->st.n_poa_launches++; }
+        if (env.mem_debug) fprintf(stderr, "[mem] round %d: %zu chains, POA kernels %.1f ms\n", round, which.size(), kms);
+        return 0;
+    }
+    // the records to their batches, then the verdict on every chain that did not end with LCD_OK: back into the next round (chain_goes_back), or the submission's
+    // error.  Reads: R.tmp, which.  Writes: the batches' couts, ChainRec's cert fields, R.again, the learned hints, poa_retries, scale, which (= the chains that
+    // go back).  Calling thread, with one team
+    int judge_round(PoaRound &R) {
+        const int round = R.round; const PoaChainOut *const tmp = R.tmp;
+        // (the chains' output records -- 200 B each, 46 000 of them in a 20-batch submission -- go to their batches on a few threads: serial this was 3.4 ms
+        //  with the GPU idle; the chains that did not end with LCD_OK are few and are looked at one by one below)
+        std::vector<size_t> flagged;
+        {
+            constexpr int NTH = 32; const int nth_r = host_team();
+            std::vector<size_t> fl[NTH];
+            par_chunks(which.size(), nth_r, 2048, [&](const size_t lo, const size_t hi, const int t) {
+                for (size_t i = lo; i < hi; ++i) {
+                    out(which[i]) = tmp[i];
+                    if (tmp[i].status != LCD_OK) fl[t].push_back(i);
+                }
+            });
+            for (int t = 0; t < NTH; ++t) flagged.insert(flagged.end(), fl[t].begin(), fl[t].end());
+            std::sort(flagged.begin(), flagged.end());
+        }
+        if (env.time_host) fprintf(stderr, "[host]   round %d: records in their batches %.1f ms after the stage's start (%zu not LCD_OK)\n", round, now_ms() - tp0, flagged.size());
+        for (const size_t i : flagged) {
+            const size_t g = which[i]; const int status = tmp[i].status;
+            if (chain_goes_back(status, chain(g), rec(g), round)) { R.again.push_back(g); R.n_node_ovf += status == LCD_ERR_NODES || status == LCD_ERR_EDGES; R.n_cert_fail += status == LCD_ERR_CERT; }
+            else { // the failing chain's reads, for a replay in isolation (tools/replay_chain.py)
+                if (env.dump_chain) dump_failed_chain(*this, g, status);
+                return set_err(-20, failed_chain_text(*this, g, tmp[i]));
+            }
+        }
+        if (env.mem_debug) report_round_retries(*this, R);
+        if (round == 0 && R.n_node_ovf * 20 > nC_all && g_node_hint.load() < 2) g_node_hint++;
+        if (round == 0) { // learn: more than 1 % of a mode's chains overflowed their DP region -> start from the next estimate next time
+            int tot[2] = {0, 0}, ovf[2] = {0, 0};
+            for (size_t g = 0; g < nC_all; ++g) tot[chain(g).mode ? 1 : 0]++;
+            for (size_t g : R.again) if (out(g).status != LCD_ERR_CERT) ovf[chain(g).mode ? 1 : 0]++;
+            for (int m = 0; m < 2; ++m) if (tot[m] && ovf[m] * 100 > tot[m] && g_cell_hint[m].load() < 2) g_cell_hint[m]++;
+        }
+        if (!R.again.empty()) { for (int k = 0; k < nb; ++k) bs[k]->st.poa_retries++; scale *= 2; }
+        which.swap(R.again);
+        return 0;
+    }
+
     // ---------------- S3: ref<->cons WFA, S4: MSA rows -> strings ----------------
-    std::vector<WfaJob> &rc_all = L->h_rc_all; std::vector<StrJob> &str_all = L->h_str_all;
-    std::vector<size_t> rc_base(nb + 1, 0), str_base(nb + 1, 0);
     // the job tables of the batches are independent: built on a few host threads (37 000 string jobs per configs[1] batch; serial, this was 30 ms of a 20-batch
     // submission), concatenated and given their device blocks afterwards
-    std::vector<uint64_t> str_tots(nb, 0);
     // (two passes over a batch's regions: `what` 1 = consensus counts, statistics and the ref<->cons jobs -- what the WFA stage waits for; 2 = the string jobs, twelve
     //  times as many, built on the strings stage's own thread while the WFA kernels run)
-    auto build_jobs = [&](const int k, const int what) {
+    // Reads: batch k's regs, couts, pchains.  Writes: what 1: batch k's rc_* tables, reg_rc0, the regions' n_cons, n_regions / n_regions_resolved; what 2: its str_*
+    // tables, reg_str0, str_tots[k].  A team of refcons_jobs (what 1) / of build_string_tables (what 2)
+    void build_jobs(const int k, const int what) {
         lcd_batch_t *b = bs[k]; lcd_batch_stats_t &S = b->st;
         const uint64_t in_base = b->d_in.addr();
         if (what == 1) { b->rc_jobs.clear(); b->rc_region.clear(); b->rc_clu.clear(); b->reg_rc0.assign(b->regs.size() + 1, 0); }
@@ -1520,25 +1635,24 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
         }
         if (what == 1) b->reg_rc0[b->regs.size()] = (uint32_t)b->rc_jobs.size();
         else { b->reg_str0[b->regs.size()] = (uint32_t)b->str_jobs.size(); str_tots[k] = str_tot; }
-    };
-    auto over_batches = [&](auto f) { // f(k) for every batch, on a team of host threads
-        const int nth = std::max(1, std::min(nb, 2 * host_team()));
-        if (nth == 1) { for (int k = 0; k < nb; ++k) f(k); return; }
-        std::atomic<int> next{0};
-        std::vector<std::thread> ths;
-        for (int t = 0; t < nth; ++t) ths.emplace_back([&]() { for (int k; (k = next.fetch_add(1)) < nb;) f(k); });
-        for (auto &t : ths) t.join();
-    };
-    over_batches([&](const int k) { build_jobs(k, 1); });
-    for (int k = 0; k < nb; ++k) rc_base[k + 1] = rc_base[k] + bs[k]->rc_jobs.size();
-    if (rc_all.capacity() < rc_base[nb]) rc_all.reserve(rc_base[nb] + rc_base[nb] / 4 + 64); // (headroom: the next submission's tables are a few per cent larger or smaller)
-    rc_all.resize(rc_base[nb]);
-    for (int k = 0; k < nb; ++k) if (!bs[k]->rc_jobs.empty()) memcpy(rc_all.data() + rc_base[k], bs[k]->rc_jobs.data(), bs[k]->rc_jobs.size() * sizeof(WfaJob));
-    if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host] job table of the WFA stage: %.1f ms (%zu jobs)\n", now_ms() - th0, rc_all.size());
+    }
+    // the joint ref<->cons job table.  Reads: the batches' couts / pchains.  Writes: the batches' rc tables and region statistics (teams), rc_base, rc_all; ev[3] on st.
+    // Calling thread, with one team
+    int refcons_jobs() {
+        over_batches(2 * host_team(), [&](const int k) { build_jobs(k, 1); });
+        for (int k = 0; k < nb; ++k) rc_base[k + 1] = rc_base[k] + bs[k]->rc_jobs.size();
+        if (rc_all.capacity() < rc_base[nb]) rc_all.reserve(rc_base[nb] + rc_base[nb] / 4 + 64); // (headroom: the next submission's tables are a few per cent larger or smaller)
+        rc_all.resize(rc_base[nb]);
+        for (int k = 0; k < nb; ++k) if (!bs[k]->rc_jobs.empty()) memcpy(rc_all.data() + rc_base[k], bs[k]->rc_jobs.data(), bs[k]->rc_jobs.size() * sizeof(WfaJob));
+        if (env.time_host) fprintf(stderr, "[host] job table of the WFA stage: %.1f ms (%zu jobs)\n", now_ms() - th0, rc_all.size());
+        HIPCHK(hipEventRecord(L->ev[3], st));
+        return 0;
+    }
     // the string jobs (670 000 per 20 batches; appended serially into fresh vectors their tables were 15 - 25 ms of a 300 ms submission with the GPU idle): per batch on
-    // host threads, the joint table sized once and filled by the same threads, the batches' output blocks given their device memory in between
-    auto build_string_tables = [&]() -> int {
-        over_batches([&](const int k) { build_jobs(k, 2); });
+    // host threads, the joint table sized once and filled by the same threads, the batches' output blocks given their device memory in between.
+    // Reads: the batches' couts / pchains / regs.  Writes: the batches' str tables, d_final, final_bytes, str_tots, str_base, str_all.  The thread of strings_stage, with two teams
+    int build_string_tables() {
+        over_batches(2 * host_team(), [&](const int k) { build_jobs(k, 2); });
         for (int k = 0; k < nb; ++k) {
             lcd_batch_t *b = bs[k]; const uint64_t str_tot = str_tots[k];
             if (!b->str_jobs.empty() && b->d_final.ensure(str_tot)) return -11;
@@ -1547,20 +1661,20 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
         }
         if (str_all.capacity() < str_base[nb]) str_all.reserve(str_base[nb] + str_base[nb] / 4 + 64);
         str_all.resize(str_base[nb]);
-        over_batches([&](const int k) {
+        over_batches(2 * host_team(), [&](const int k) {
             lcd_batch_t *b = bs[k];
             const uint64_t fin = b->d_final.addr();
             for (auto &j : b->str_jobs) j.out_off += fin;
             if (!b->str_jobs.empty()) memcpy(str_all.data() + str_base[k], b->str_jobs.data(), b->str_jobs.size() * sizeof(StrJob));
         });
         return 0;
-    };
-    HIPCHK(hipEventRecord(L->ev[3], st));
+    }
     // S4 (MSA rows -> strings) needs the chains' outputs only, not the ref<->cons alignments: it runs BESIDE S3 -- its 37 MB job table (670 000 jobs of a 20-batch
-    // submission) goes up from a helper thread on a side stream while this thread plans and launches the WFA classes (one after the other they were 8 + 4 ms, the
-    // table's pageable upload alone 2 ms of this thread).  LCD_STRINGS_SEQ=1: after S3 on the leader's stream, as before
-    std::vector<StrOut> &str_outs = L->h_str_outs;
-    auto strings_stage = [&](hipStream_t s2) -> int {
+    // submission) goes up from a helper thread on a side stream while the calling thread plans and launches the WFA classes (one after the other they were 8 + 4 ms, the
+    // table's pageable upload alone 2 ms of the calling thread).  LCD_STRINGS_SEQ=1: after S3 on the leader's stream, as before.
+    // Reads: what build_string_tables reads.  Writes: what it writes, str_outs, the leader's d_str_jobs / d_str_outs; table, kernel and download on s2 (not synchronised
+    // here).  Strings thread with s2 = side[3]; LCD_STRINGS_SEQ: calling thread with s2 = st
+    int strings_stage(hipStream_t s2) {
         if (const int rcb = build_string_tables()) return rcb;
         if (str_outs.capacity() < str_all.size()) str_outs.reserve(str_all.size() + str_all.size() / 4 + 64);
         str_outs.resize(str_all.size());
@@ -1571,25 +1685,28 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(str_outs.data(), L->d_str_outs.p, str_all.size() * sizeof(StrOut), hipMemcpyDeviceToHost, s2));
         return 0;
-    };
-    const bool strings_beside = L->side[3] && !getenv("LCD_STRINGS_SEQ");
-    int strings_rc = 0;
-    std::string strings_err;
-    Joiner strings_thread;
-    if (strings_beside) {
+    }
+    // starts the strings thread (side[3] waits for ev[3]); it synchronises side[3] itself.  Until join_strings the calling thread touches none of what strings_stage
+    // writes.  Writes: strings_beside; the thread writes strings_rc / strings_err.  Calling thread
+    int start_strings() {
+        strings_beside = L->side[3] && !env.strings_seq;
+        if (!strings_beside) return 0;
         HIPCHK(hipStreamWaitEvent(L->side[3], L->ev[3], 0));
         const int dev_here = cur_device();
-        strings_thread.t = std::thread([&, dev_here]() {
+        strings_thread.t = std::thread([this, dev_here]() {
             if (hipSetDevice(dev_here) != hipSuccess) { strings_rc = -1; return; }
             strings_rc = strings_stage(L->side[3]);
             if (strings_rc) strings_err = g_err;
             if (!strings_rc && hipStreamSynchronize(L->side[3]) != hipSuccess) strings_rc = -1;
         });
+        return 0;
     }
-    {
+    // the ref<->cons WFA stage.  Reads: rc_all, rc_base.  Writes: rc_all (planned jobs), the batches' rc_jobs / rc_outs and WFA statistics; the WFA classes on st
+    // and side[0..2] (LCD_WFA_SEQ: st alone), ev[4] on st; synchronises st per WFA round.  Calling thread, beside the strings thread
+    int wfa_stage() {
         int wret = 0;
         std::vector<WfaOut> rc_outs;
-        int rc = run_wfa_stage(st, rc_all, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, rc_outs, sc, &wret, false, getenv("LCD_WFA_SEQ") ? nullptr : L->side, L->sev, 3); // (the POA streams are idle by now)
+        int rc = run_wfa_stage(st, rc_all, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, rc_outs, sc, &wret, false, env.wfa_seq ? nullptr : L->side, L->sev, 3); // (the POA streams are idle by now)
         if (rc) return rc;
         for (int k = 0; k < nb; ++k) {
             lcd_batch_t *b = bs[k];
@@ -1598,15 +1715,24 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
             b->st.n_wfa_jobs += (int)b->rc_jobs.size();
             for (auto &w : b->rc_outs) b->st.wfa_offsets += w.offsets;
         }
+        HIPCHK(hipEventRecord(L->ev[4], st));
+        return 0;
     }
-    HIPCHK(hipEventRecord(L->ev[4], st));
-    if (strings_beside) { if (strings_thread.t.joinable()) strings_thread.t.join(); if (strings_rc) return strings_rc == -11 ? set_err(-11, strings_err.empty() ? "device memory budget (strings stage)" : strings_err) : set_err(-20, "strings stage failed on its side stream" + (strings_err.empty() ? std::string() : ": " + strings_err)); }
-    else { const int rcs = strings_stage(st); if (rcs) return rcs; }
-    HIPCHK(hipEventRecord(L->ev[5], st));
-    HIPCHK(hipStreamSynchronize(st));
+    // the strings stage's end: the join of its thread (its error text comes over with it), or the stage itself in line.  Writes: ev[5] on st; synchronises st.  Calling thread
+    int join_strings() {
+        if (strings_beside) { if (strings_thread.t.joinable()) strings_thread.t.join(); if (strings_rc) return strings_rc == -11 ? set_err(-11, strings_err.empty() ? "device memory budget (strings stage)" : strings_err) : set_err(-20, "strings stage failed on its side stream" + (strings_err.empty() ? std::string() : ": " + strings_err)); }
+        else { const int rcs = strings_stage(st); if (rcs) return rcs; }
+        HIPCHK(hipEventRecord(L->ev[5], st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+
     // ---------------- S5 (only with opt.collect_ref_read_aln_str): ref<->read strings, src/align.c:1056-1146 ----------------
-    for (int k = 0; k < nb; ++k) { bs[k]->rr_off.clear(); bs[k]->rr_len.clear(); bs[k]->rr_stride.clear(); bs[k]->rr_bytes = 0; }
-    if (L->opt.collect_ref_read_aln_str && !str_all.empty()) {
+    // Reads: the batches' rc / str tables, str_outs, str_base.  Writes: the batches' rr_* tables and d_rr, the leader's compose buffers; compose kernels and one WFA stage
+    // on st, synchronised.  Calling thread
+    int compose_ref_read() {
+        for (int k = 0; k < nb; ++k) { bs[k]->rr_off.clear(); bs[k]->rr_len.clear(); bs[k]->rr_stride.clear(); bs[k]->rr_bytes = 0; }
+        if (!(L->opt.collect_ref_read_aln_str && !str_all.empty())) return 0;
         std::vector<CmpJob> cj(str_all.size());
         uint64_t seg_tot = 0;
         for (int k = 0; k < nb; ++k) {
@@ -1665,40 +1791,20 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
         HIPCHK(hipMemcpyAsync(co.data(), L->d_cmp_outs.p, cj.size() * sizeof(CmpOut), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         for (int k = 0; k < nb; ++k) for (size_t j = 0; j < bs[k]->str_jobs.size(); ++j) bs[k]->rr_len[j] = co[str_base[k] + j].aln_len;
+        return 0;
     }
+
     // ---------------- S6 (opt.collect_noisy_vars): strings -> candidate variants + read x variant profile, SURVEY 8(f) f1 ----------------
-    // make_vars_from_msa_cons_aln, src/collect_var.c:2279: the strings are still in HBM; only variants and alleles go back to the host
-    for (int k = 0; k < nb; ++k) { bs[k]->vregs.clear(); bs[k]->vreg_of.assign(bs[k]->regs.size(), -1); bs[k]->var_bytes = 0; }
-    float ms_vars = 0;
-    if (L->opt.collect_noisy_vars && !rc_all.empty()) {
+    // make_vars_from_msa_cons_aln, src/collect_var.c:2279: the strings are still in HBM; only variants and alleles go back to the host.
+    // Reads: rc_all, rc_base, str_base, the batches' rc / str tables.  Writes: the batches' vregs / vreg_of / d_var_out / var_bytes, the leader's variant buffers,
+    // ms_vars; ev[6] and ev[7] on st (re-used: the POA rounds are over), synchronised.  Calling thread
+    int candidate_vars() {
+        for (int k = 0; k < nb; ++k) { bs[k]->vregs.clear(); bs[k]->vreg_of.assign(bs[k]->regs.size(), -1); bs[k]->var_bytes = 0; }
+        if (!(L->opt.collect_noisy_vars && !rc_all.empty())) return 0;
         HIPCHK(hipEventRecord(L->ev[6], st));
         const size_t nj = rc_all.size();
-        std::vector<VarScanJob> vj(nj);
-        uint64_t work_tot = 0;
-        for (int k = 0; k < nb; ++k) for (size_t i = 0; i < bs[k]->rc_jobs.size(); ++i) {
-            const WfaJob &wj = bs[k]->rc_jobs[i]; VarScanJob &v = vj[rc_base[k] + i];
-            v.rc_t = wj.out_off; v.rc_q = wj.out_off + (uint64_t)(wj.plen + wj.tlen + 1); v.rc_len = bs[k]->rc_outs[i].aln_len;
-            v.row_cap = (int)lcd_align_up((uint64_t)v.rc_len + 16, 16); v.work_off = work_tot; work_tot += 2ull * v.row_cap; v.rec_off = 0; v.rec_cap = 0; v.pad = 0;
-        }
-        if (L->d_var_jobs.ensure(nj * sizeof(VarScanJob)) || L->d_var_outs.ensure(nj * sizeof(VarScanOut)) || L->d_var_work.ensure(work_tot + 64)) return -11;
-        for (auto &v : vj) v.work_off += L->d_var_work.addr();
-        std::vector<VarScanOut> vo(nj);
-        for (int pass = 0; pass < 2; ++pass) { // pass 0 counts the variants of every consensus, pass 1 writes the records into exactly sized lists
-            HIPCHK(hipMemcpyAsync(L->d_var_jobs.p, vj.data(), nj * sizeof(VarScanJob), hipMemcpyHostToDevice, st));
-            lcd_launch_vars_scan((const VarScanJob *)L->d_var_jobs.p, (VarScanOut *)L->d_var_outs.p, (int)nj, st);
-            HIPCHK(hipGetLastError());
-            if (pass == 1) break;
-            HIPCHK(hipMemcpyAsync(vo.data(), L->d_var_outs.p, nj * sizeof(VarScanOut), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipStreamSynchronize(st));
-            uint64_t rec_tot = 0;
-            for (size_t g = 0; g < nj; ++g) { vj[g].rec_cap = vo[g].n_vars; vj[g].rec_off = rec_tot; rec_tot += (uint64_t)vo[g].n_vars * sizeof(VarRec); }
-            // the per-consensus lists live behind the compacted rows in the leader's work buffer (transient: consumed by the profile kernel below;
-            // ensure() may move the buffer -- nothing in it is live yet, pass 1 rewrites the rows)
-            const uint64_t rec_base = lcd_align_up(work_tot + 64, 64);
-            if (L->d_var_work.ensure(rec_base + rec_tot + 64)) return -11;
-            uint64_t wo = 0;
-            for (size_t g = 0; g < nj; ++g) { vj[g].work_off = L->d_var_work.addr() + wo; wo += 2ull * vj[g].row_cap; vj[g].rec_off += L->d_var_work.addr() + rec_base; }
-        }
+        std::vector<VarScanJob> vj(nj); std::vector<VarScanOut> vo(nj);
+        if (const int rc = scan_vars(vj, vo)) return rc;
         std::vector<VarRegJob> rj; std::vector<std::pair<int, int>> rj_owner;
         for (int k = 0; k < nb; ++k) {
             lcd_batch_t *b = bs[k];
@@ -1741,111 +1847,234 @@ static int run_many_once(lcd_batch_t **bs, int nb) {
             lcd_batch_t *b = bs[rj_owner[q].first]; const VarRegionRec &V = b->vregs[rj_owner[q].second]; const uint64_t base = b->d_var_out.addr();
             rj[q].out_rec = base + V.rec_off; rj[q].out_alt = base + V.alt_off; rj[q].out_prof = base + V.prof_off; rj[q].out_se = base + V.se_off;
         }
-        if (!rj.empty()) {
-            if (L->d_vreg_jobs.ensure(rj.size() * sizeof(VarRegJob)) || L->d_vreg_outs.ensure(rj.size() * sizeof(VarRegOut))) return -11;
-            HIPCHK(hipMemcpyAsync(L->d_vreg_jobs.p, rj.data(), rj.size() * sizeof(VarRegJob), hipMemcpyHostToDevice, st));
-            lcd_launch_vars_profile((const VarRegJob *)L->d_vreg_jobs.p, (VarRegOut *)L->d_vreg_outs.p, (const StrJob *)L->d_str_jobs.p, (const StrOut *)L->d_str_outs.p, (int)rj.size(), st);
+        if (rj.empty()) return 0;
+        if (L->d_vreg_jobs.ensure(rj.size() * sizeof(VarRegJob)) || L->d_vreg_outs.ensure(rj.size() * sizeof(VarRegOut))) return -11;
+        HIPCHK(hipMemcpyAsync(L->d_vreg_jobs.p, rj.data(), rj.size() * sizeof(VarRegJob), hipMemcpyHostToDevice, st));
+        lcd_launch_vars_profile((const VarRegJob *)L->d_vreg_jobs.p, (VarRegOut *)L->d_vreg_outs.p, (const StrJob *)L->d_str_jobs.p, (const StrOut *)L->d_str_outs.p, (int)rj.size(), st);
+        HIPCHK(hipGetLastError());
+        std::vector<VarRegOut> ro(rj.size());
+        HIPCHK(hipMemcpyAsync(ro.data(), L->d_vreg_outs.p, rj.size() * sizeof(VarRegOut), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(L->ev[7], st));
+        HIPCHK(hipStreamSynchronize(st));
+        for (size_t q = 0; q < rj.size(); ++q) { VarRegionRec &V = bs[rj_owner[q].first]->vregs[rj_owner[q].second]; V.n_vars = ro[q].n_vars; V.alt_bytes = ro[q].alt_bytes; }
+        hipEventElapsedTime(&ms_vars, L->ev[6], L->ev[7]);
+        return 0;
+    }
+    // S6's scan of every ref<->cons string: pass 0 counts the variants of every consensus, pass 1 writes the records into exactly sized lists.  Reads: the batches'
+    // rc_jobs / rc_outs, rc_base.  Writes: vj, vo, the leader's d_var_jobs / d_var_outs / d_var_work; both launches on st, one synchronisation.  Calling thread
+    int scan_vars(std::vector<VarScanJob> &vj, std::vector<VarScanOut> &vo) {
+        const size_t nj = vj.size();
+        uint64_t work_tot = 0;
+        for (int k = 0; k < nb; ++k) for (size_t i = 0; i < bs[k]->rc_jobs.size(); ++i) {
+            const WfaJob &wj = bs[k]->rc_jobs[i]; VarScanJob &v = vj[rc_base[k] + i];
+            v.rc_t = wj.out_off; v.rc_q = wj.out_off + (uint64_t)(wj.plen + wj.tlen + 1); v.rc_len = bs[k]->rc_outs[i].aln_len;
+            v.row_cap = (int)lcd_align_up((uint64_t)v.rc_len + 16, 16); v.work_off = work_tot; work_tot += 2ull * v.row_cap; v.rec_off = 0; v.rec_cap = 0; v.pad = 0;
+        }
+        if (L->d_var_jobs.ensure(nj * sizeof(VarScanJob)) || L->d_var_outs.ensure(nj * sizeof(VarScanOut)) || L->d_var_work.ensure(work_tot + 64)) return -11;
+        for (auto &v : vj) v.work_off += L->d_var_work.addr();
+        for (int pass = 0; pass < 2; ++pass) {
+            HIPCHK(hipMemcpyAsync(L->d_var_jobs.p, vj.data(), nj * sizeof(VarScanJob), hipMemcpyHostToDevice, st));
+            lcd_launch_vars_scan((const VarScanJob *)L->d_var_jobs.p, (VarScanOut *)L->d_var_outs.p, (int)nj, st);
             HIPCHK(hipGetLastError());
-            std::vector<VarRegOut> ro(rj.size());
-            HIPCHK(hipMemcpyAsync(ro.data(), L->d_vreg_outs.p, rj.size() * sizeof(VarRegOut), hipMemcpyDeviceToHost, st));
-            HIPCHK(hipEventRecord(L->ev[7], st));
+            if (pass == 1) break;
+            HIPCHK(hipMemcpyAsync(vo.data(), L->d_var_outs.p, nj * sizeof(VarScanOut), hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            for (size_t q = 0; q < rj.size(); ++q) { VarRegionRec &V = bs[rj_owner[q].first]->vregs[rj_owner[q].second]; V.n_vars = ro[q].n_vars; V.alt_bytes = ro[q].alt_bytes; }
-            hipEventElapsedTime(&ms_vars, L->ev[6], L->ev[7]);
+            uint64_t rec_tot = 0;
+            for (size_t g = 0; g < nj; ++g) { vj[g].rec_cap = vo[g].n_vars; vj[g].rec_off = rec_tot; rec_tot += (uint64_t)vo[g].n_vars * sizeof(VarRec); }
+            // the per-consensus lists live behind the compacted rows in the leader's work buffer (transient: consumed by the profile kernel;
+            // ensure() may move the buffer -- nothing in it is live yet, pass 1 rewrites the rows)
+            const uint64_t rec_base = lcd_align_up(work_tot + 64, 64);
+            if (L->d_var_work.ensure(rec_base + rec_tot + 64)) return -11;
+            uint64_t wo = 0;
+            for (size_t g = 0; g < nj; ++g) { vj[g].work_off = L->d_var_work.addr() + wo; wo += 2ull * vj[g].row_cap; vj[g].rec_off += L->d_var_work.addr() + rec_base; }
         }
+        return 0;
     }
-    float ms_anchor = 0, ms_poa = 0, ms_wfa = 0, ms_str = 0, ms_tot = 0;
-    hipEventElapsedTime(&ms_anchor, L->ev[0], L->ev[1]); hipEventElapsedTime(&ms_poa, L->ev[1], L->ev[2]);
-    hipEventElapsedTime(&ms_wfa, L->ev[3], L->ev[4]); hipEventElapsedTime(&ms_str, L->ev[4], L->ev[5]); hipEventElapsedTime(&ms_tot, L->ev[0], L->ev[5]);
-    const double host_ms = (now_ms() - t_begin) - ms_tot;
-    for (int k = 0; k < nb; ++k) {
-        lcd_batch_t *b = bs[k]; lcd_batch_stats_t &S = b->st;
-        b->str_outs.assign(str_outs.begin() + str_base[k], str_outs.begin() + str_base[k + 1]);
-        // stage times are those of the joint run (the same for every batch of the call)
-        S.ms_anchor = ms_anchor; S.ms_poa = ms_poa; S.ms_wfa = ms_wfa; S.ms_strings = ms_str; S.ms_total = ms_tot + ms_vars; S.ms_host = host_ms - ms_vars; S.ms_vars = ms_vars;
-        for (const PoaChainOut &o : b->couts) {
-            S.poa_aligned_bases += o.aligned_bases; S.poa_cells += o.cells_alg; S.poa_cells_computed += o.cells;
-            // B_poa = q + 5*N_sub + C + (q + N_sub) per aligned read; N_sub ~ final graph size (upper bound per read)
-            S.poa_alg_bytes += 2 * o.aligned_bases + o.cells_alg + 6ull * (uint64_t)o.n_node * (uint64_t)o.n_aligned_reads;
-        }
-        b->ran = true; b->downloaded = false; b->gathered = false;
-    }
-    if (int rc = stage_gather_many(bs, nb, st)) return rc;
-    if (getenv("LCD_MEM_DEBUG")) fprintf(stderr, "[mem] device buffers of this process after the submission: %.2f GB (budget %.2f GB)\n", g_dev_bytes[L->device].load() / 1e9, dev_budget(L->device) / 1e9);
-    if (getenv("LCD_PLACEMENT")) { // experiment: which CU did every wide chain run on, and when
-        for (size_t g = 0; g < nC_all; ++g) { if (chain_threads(PC(g)) < 512) continue; const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]];
-            fprintf(stderr, "[place] thr %d xcc %u se %u sh %u cu %u simd %u  t %.1f..%.1f ms ticks %.3e\n", chain_threads(PC(g)), o.xcc_id & 15, (o.hw_id >> 13) & 7, (o.hw_id >> 12) & 1, (o.hw_id >> 8) & 15, (o.hw_id >> 4) & 3,
-                    o.rt_begin / 1e5, o.rt_end / 1e5, (double)o.t_total); }
-    }
-    if (const char *ct = getenv("LCD_CHAIN_TIMES")) { // every chain's class, pool, start and end (100 MHz device clock, relative to the first start): tools/occupancy.py
-        if (FILE *f = fopen(ct, "w")) {
-            unsigned long long t0 = ~0ull;
-            for (size_t g = 0; g < nC_all; ++g) t0 = std::min(t0, bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]].rt_begin);
-            for (size_t g = 0; g < nC_all; ++g) { const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]]; const PoaChain &pc = PC(g);
-                fprintf(f, "%d %d %d %llu %llu %u %u %d %d %d %llu %llu %llu %llu %llu\n", pc.threads, pc.lds_words * 4, pc.mode, o.rt_begin - t0, o.rt_end - t0, o.xcc_id & 15, (o.hw_id >> 8) & 15, pc.max_len, pc.n_reads, pc.cert, (unsigned long long)o.t_setup,
-                        (unsigned long long)o.t_total, (unsigned long long)o.t_dp, (unsigned long long)o.cells, (unsigned long long)o.t_bt); }
-            fclose(f);
-        }
-    }
-    if (getenv("LCD_PROFILE_CHAINS")) {
-        { // the chains that end last: the tail of the submission (times on the device's 100 MHz clock, relative to the first chain's start)
-            std::vector<size_t> ord(nC_all); unsigned long long t0 = ~0ull;
-            for (size_t g = 0; g < nC_all; ++g) { ord[g] = g; t0 = std::min(t0, bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]].rt_begin); }
-            auto O = [&](size_t g) -> const PoaChainOut & { return bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]]; };
-            std::sort(ord.begin(), ord.end(), [&](size_t a, size_t c) { return O(a).rt_end > O(c).rt_end; });
-            for (size_t q = 0; q < std::min<size_t>(10, ord.size()); ++q) { const size_t g = ord[q]; const PoaChainOut &o = O(g);
-                fprintf(stderr, "[tail] thr %4d lds %3dK mode %d reads %3d maxlen %5d nodes %6d: %.1f .. %.1f ms  (dp %.0f%% bt %.0f%% graph %.0f%% out %.0f%%)  cells %.2e\n", chain_threads(PC(g)), PC(g).lds_words * 4 >> 10, PC(g).mode, PC(g).n_reads, PC(g).max_len, o.n_node,
-                        (o.rt_begin - t0) / 1e5, (o.rt_end - t0) / 1e5, 100.0 * o.t_dp / o.t_total, 100.0 * o.t_bt / o.t_total, 100.0 * o.t_graph / o.t_total, 100.0 * o.t_out / o.t_total, (double)o.cells); }
-        }
-        { // CU-seconds per launch group: sum of chain ticks / workgroups that fit a CU (LDS- or register-limited)
-            std::map<long long, std::pair<double, int>> gsum;
-            for (size_t g = 0; g < nC_all; ++g) { const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]]; auto &e = gsum[chain_group_key(PC(g))]; e.first += (double)o.t_total; e.second++; }
-            double tot = 0;
-            for (auto &kv : gsum) {
-                const int thr = (int)(kv.first >> 20), lds = (int)(kv.first & ((1 << 20) - 1)) * 4;
-                const int by_lds = std::max(1, (160 * 1024) / (lds + (thr == 64 ? 1 : 6) * 1024)), by_reg = std::max(1, 1024 / thr); // 128 VGPRs: 16 wavefronts per CU
-                const int per_cu = std::min(by_lds, by_reg);
-                const double cus = kv.second.first / 2.4e9 / per_cu; tot += cus;
-                fprintf(stderr, "[lcd] group thr %4d lds %3dK: %6d chains, %7.2f wg-s, %2d per CU -> %7.2f CU-s\n", thr, lds >> 10, kv.second.second, kv.second.first / 2.4e9, per_cu, cus);
+
+    // ---- final statistics and the gather of the scattered result pieces.  Reads: the events ev[0..5], ms_vars, str_outs, str_base, the batches' couts.  Writes: the
+    // batches' str_outs, stage times and POA totals, ran / downloaded / gathered; the gather launch on st, synchronised.  Calling thread ----
+    int finish() {
+        float ms_anchor = 0, ms_poa = 0, ms_wfa = 0, ms_str = 0, ms_tot = 0;
+        hipEventElapsedTime(&ms_anchor, L->ev[0], L->ev[1]); hipEventElapsedTime(&ms_poa, L->ev[1], L->ev[2]);
+        hipEventElapsedTime(&ms_wfa, L->ev[3], L->ev[4]); hipEventElapsedTime(&ms_str, L->ev[4], L->ev[5]); hipEventElapsedTime(&ms_tot, L->ev[0], L->ev[5]);
+        const double host_ms = (now_ms() - t_begin) - ms_tot;
+        for (int k = 0; k < nb; ++k) {
+            lcd_batch_t *b = bs[k]; lcd_batch_stats_t &S = b->st;
+            b->str_outs.assign(str_outs.begin() + str_base[k], str_outs.begin() + str_base[k + 1]);
+            // stage times are those of the joint run (the same for every batch of the call)
+            S.ms_anchor = ms_anchor; S.ms_poa = ms_poa; S.ms_wfa = ms_wfa; S.ms_strings = ms_str; S.ms_total = ms_tot + ms_vars; S.ms_host = host_ms - ms_vars; S.ms_vars = ms_vars;
+            for (const PoaChainOut &o : b->couts) {
+                S.poa_aligned_bases += o.aligned_bases; S.poa_cells += o.cells_alg; S.poa_cells_computed += o.cells;
+                // B_poa = q + 5*N_sub + C + (q + N_sub) per aligned read; N_sub ~ final graph size (upper bound per read)
+                S.poa_alg_bytes += 2 * o.aligned_bases + o.cells_alg + 6ull * (uint64_t)o.n_node * (uint64_t)o.n_aligned_reads;
             }
-            fprintf(stderr, "[lcd] total %.2f CU-s = %.1f ms of %d CUs\n", tot, tot / g_n_cus * 1e3, g_n_cus);
+            b->ran = true; b->downloaded = false; b->gathered = false;
         }
-        // per (class, kind of chain): ticks per phase and cells -- kind 0: K1 (adaptive band), 1: K2 full rows, 2: K2 certified band, +4: long-chain (solo) workgroup
-        {
-            struct Acc { double n = 0, tt = 0, td = 0, tb = 0, tbp = 0, tad = 0, tso = 0, tse = 0, tsub = 0, to = 0, cells = 0, reads = 0, rows = 0; };
-            std::map<int, Acc> by;
-            for (size_t g = 0; g < nC_all; ++g) { const PoaChain &pc = PC(g); const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]];
-                Acc &a = by[chain_threads(pc) * 8 + (pc.mode ? (pc.cert ? 2 : 1) : 0) + (pc.solo ? 4 : 0)];
-                a.n += 1; a.tt += (double)o.t_total; a.td += (double)o.t_dp; a.tb += (double)o.t_bt; a.tbp += (double)o.t_bp; a.tad += (double)o.t_add; a.tso += (double)o.t_sort; a.tse += (double)o.t_setup;
-                a.tsub += (double)o.t_sub; a.to += (double)o.t_out; a.cells += (double)o.cells; a.reads += o.n_aligned_reads; a.rows += (double)o.n_aligned_reads * o.n_node; }
-            for (auto &kv : by) { const Acc &a = kv.second;
-                fprintf(stderr, "[kind] thr %4d kind %d: %6.0f chains %8.0f reads  ticks total %.3e | dp %.1f%% bt %.1f%% plan %.1f%% update %.1f%% re-sort %.1f%% setup %.1f%% sub %.1f%% out %.1f%% | cells %.3e  ticks/cell(dp) %.2f  ~rows %.3e\n",
-                        kv.first >> 3, kv.first & 7, a.n, a.reads, a.tt, 100 * a.td / a.tt, 100 * a.tb / a.tt, 100 * a.tbp / a.tt, 100 * a.tad / a.tt, 100 * a.tso / a.tt, 100 * a.tse / a.tt, 100 * a.tsub / a.tt, 100 * a.to / a.tt,
-                        a.cells, a.td / std::max(1.0, a.cells), a.rows); }
-        }
-        // per-phase shader-clock ticks, summed per workgroup class and for the slowest chain
-        for (int cls : {64, 128, 256, 512, 1024}) {
-            unsigned long long tt = 0, td = 0, tb = 0, tg = 0, to = 0, ts = 0, mx = 0, tbp = 0, tad = 0, tso = 0, tse = 0, tpl = 0; int cnt = 0; size_t mxc = 0;
-            for (size_t g = 0; g < nC_all; ++g) { if (chain_threads(PC(g)) != cls) continue; const PoaChainOut &o = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]]; ++cnt;
-                tt += o.t_total; td += o.t_dp; tb += o.t_bt; tg += o.t_graph; to += o.t_out; ts += o.t_sub; tbp += o.t_bp; tad += o.t_add; tso += o.t_sort; tse += o.t_setup; tpl += o.t_plan; if (o.t_total >= mx) { mx = o.t_total; mxc = g; } }
-            if (!cnt) continue;
-            fprintf(stderr, "[lcd] class %4d: row plan %.3e  graph update %.3e  re-sort %.3e  row setup %.3e  bound arrays %.3e\n", cls, (double)tbp, (double)tad, (double)tso, (double)tse, (double)tpl);
-            if (getenv("LCD_DBG") && (atoi(getenv("LCD_DBG")) & 32)) { // reads of certified-band chains by their widest interval (the t_setup slot carries five 12-bit counters per chain)
-                unsigned long long h[5] = {0, 0, 0, 0, 0};
-                for (size_t g = 0; g < nC_all; ++g) { if (chain_threads(PC(g)) != cls || !PC(g).cert) continue; const unsigned long long v = bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]].t_setup; for (int q = 0; q < 5; ++q) h[q] += (v >> (12 * q)) & 4095; }
-                fprintf(stderr, "[lcd] class %4d: certified-band reads by widest interval <= 60 / 124 / 188 / 256 / wider: %llu / %llu / %llu / %llu / %llu\n", cls, h[0], h[1], h[2], h[3], h[4]);
-            }
-            { double tk = 0; for (size_t g = 0; g < nC_all; ++g) if (chain_threads(PC(g)) == cls) tk += (double)bs[chain_batch[g]]->couts[g - chain_base[chain_batch[g]]].t_poll;
-              fprintf(stderr, "[lcd] class %4d: %5d chains  sum ticks total %.3e dp %.3e bt %.3e graph %.3e (of which serial Kahn walk %.3e) sub %.3e out %.3e\n", cls, cnt, (double)tt, (double)td, (double)tb, (double)tg, tk, (double)ts, (double)to); }
-            const PoaChainOut &o = bs[chain_batch[mxc]]->couts[mxc - chain_base[chain_batch[mxc]]];
-            fprintf(stderr, "[lcd]   slowest chain %zu: mode %d reads %d maxlen %d nodes %d  total %.3e dp %.3e bt %.3e graph %.3e sub %.3e out %.3e cells %llu\n", mxc, PC(mxc).mode,
-                    PC(mxc).n_reads, PC(mxc).max_len, o.n_node, (double)o.t_total, (double)o.t_dp, (double)o.t_bt, (double)o.t_graph, (double)o.t_sub, (double)o.t_out, o.cells);
-            fprintf(stderr, "[lcd]     of its dp: plan-window refreshes %.3e  mailbox polls %.3e (one wavefront)\n", (double)o.t_plan, (double)o.t_poll);
-            fprintf(stderr, "[lcd]     row plan %.3e  graph update %.3e  re-sort %.3e  row setup %.3e\n", (double)o.t_bp, (double)o.t_add, (double)o.t_sort, (double)o.t_setup);
-            if (getenv("LCD_DBG") && (atoi(getenv("LCD_DBG")) & 32)) fprintf(stderr, "[lcd]     reads by widest interval <=60 / <=124 / <=188 / <=380 / wider: %llu %llu %llu %llu %llu\n", (unsigned long long)(o.t_setup & 4095), (unsigned long long)((o.t_setup >> 12) & 4095), (unsigned long long)((o.t_setup >> 24) & 4095), (unsigned long long)((o.t_setup >> 36) & 4095), (unsigned long long)((o.t_setup >> 48) & 4095));
-        }
+        if (int rc = stage_gather_many(bs, nb, st)) return rc;
+        if (env.mem_debug) fprintf(stderr, "[mem] device buffers of this process after the submission: %.2f GB (budget %.2f GB)\n", g_dev_bytes[L->device].load() / 1e9, dev_budget(L->device) / 1e9);
+        if (env.placement) report_placement(*this);
+        if (env.chain_times) report_chain_times(*this);
+        if (env.profile_chains) report_profile_chains(*this);
+        return 0;
     }
-    return 0;
+};
+
+// ---- diagnostics of a submission: they read it and print; tools parse these lines (tools/occupancy.py and the tools that set LCD_PROFILE_CHAINS) ----
+// LCD_MEM_DEBUG, per round: the arena layout and what it is made of
+static void report_round_memory(const Submission &S, const PoaRound &R) {
+    const ArenaPlan &P = R.P; const std::vector<size_t> &which = S.which;
+    fprintf(stderr, "[mem] round %d arenas: %zu chains in %zu slot pools (%.2f GB), %zu with private arenas (%.2f GB)\n", R.round, P.n_pooled, P.n_pools, P.pool_bytes / 1e9, which.size() - P.n_pooled, P.private_bytes / 1e9);
+    double cellb = 0, nodeb = 0; double worstc = 0; size_t nbig = 0;
+    for (size_t i = 0; i < which.size(); ++i) { const PoaChain &pc = S.chain(which[i]); cellb += (pc.spill_x > 2 ? 5.0 + pc.spill_x : 4.0) * pc.cell_cap; PoaLayout Lay = poa_layout(pc.node_cap, pc.edge_cap, pc.rid_words, pc.max_len, 0, pc.n_reads); nodeb += (double)Lay.total; if (4.0 * pc.cell_cap > worstc) worstc = 4.0 * pc.cell_cap; nbig += 4.0 * pc.cell_cap > 64e6; }
+    fprintf(stderr, "[mem] round %d: %zu chains, arena %.2f GB = DP regions %.2f GB (largest %.1f MB, %zu above 64 MB) + graph/plan arrays %.2f GB\n", R.round, which.size(), P.tot / 1e9, cellb / 1e9, worstc / 1e6, nbig, nodeb / 1e9);
+}
+// LCD_MEM_DEBUG, per round after the verdicts: certified bands, LCD_CERT_DEBUG / LCD_RETRY_DEBUG per chain, overflows by kind (S.which is still the round's set)
+static void report_round_retries(const Submission &S, const PoaRound &R) {
+    const int round = R.round; const std::vector<size_t> &which = S.which, &again = R.again; const PoaChainOut *const tmp = R.tmp;
+    { size_t nc = 0; for (size_t g : which) nc += S.chain(g).cert != 0; fprintf(stderr, "[mem] round %d: %zu chains with a certified band, %zu sent back for full rows\n", round, nc, R.n_cert_fail); }
+    if (S.env.cert_debug) for (size_t i = 0; i < which.size(); ++i) { const PoaChain &pc = S.chain(which[i]); if (!pc.cert) continue; const int k = S.chain_batch[which[i]];
+        std::vector<int> ls; for (int r = 0; r < pc.n_reads; ++r) ls.push_back(S.preads[k][pc.read0 + r].len); std::sort(ls.begin(), ls.end());
+        fprintf(stderr, "[cert] %s n %d max %d p75 %d med %d p25 %d min %d nodes %d\n", tmp[i].status == LCD_ERR_CERT ? "FAIL" : "ok  ", pc.n_reads, ls.back(), ls[ls.size() * 3 / 4], ls[ls.size() / 2], ls[ls.size() / 4], ls[0], tmp[i].n_node); if (tmp[i].status == LCD_ERR_CERT) fprintf(stderr, "[cert]    why %llu  attempt/qlen %llu  aligned reads %d hist?\n", tmp[i].t_plan, tmp[i].t_poll, tmp[i].n_aligned_reads); }
+    if (S.env.retry_debug) for (size_t g : again) { const PoaChain &pc = S.chain(g); const PoaChainOut &o = S.out(g);
+        fprintf(stderr, "[retry] round %d status %d: thr %d mode %d reads %d maxlen %d | caps nodes %d edges %d cells %llu (worst %llu) spill_x %d | reached nodes %d edges %d aligned reads %d cells %llu\n", round, o.status,
+                chain_threads(pc), pc.mode, pc.n_reads, pc.max_len, pc.node_cap, pc.edge_cap, (unsigned long long)pc.cell_cap, (unsigned long long)pc.node_cap * (pc.max_len + 1), pc.spill_x, o.n_node, o.n_edge, o.n_aligned_reads, o.cells); }
+    int c[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    for (size_t g : again) { const PoaChainOut &o = S.out(g); c[S.chain(g).mode ? 1 : 0][o.status == LCD_ERR_CELLS ? 0 : o.status == LCD_ERR_NODES ? 1 : 2]++; }
+    { std::map<int, std::pair<int, int>> byc; for (size_t g : which) if (S.chain(g).mode) byc[chain_threads(S.chain(g))].second++; for (size_t g : again) if (S.chain(g).mode) byc[chain_threads(S.chain(g))].first++;
+      for (auto &kv : byc) fprintf(stderr, "[mem]   K2 class %4d: %d of %d overflow\n", kv.first, kv.second.first, kv.second.second); }
+    fprintf(stderr, "[mem] round %d overflows: K1 cells %d nodes %d edges %d | K2 cells %d nodes %d edges %d (hints: cells %d/%d nodes %d)\n", round, c[0][0], c[0][1], c[0][2], c[1][0], c[1][1], c[1][2],
+            g_cell_hint[0].load(), g_cell_hint[1].load(), g_node_hint.load());
+}
+// LCD_DUMP_CHAIN: the failing chain's reads, for a replay in isolation (tools/replay_chain.py): header, then per read {len, skip, anchors, bases}
+static void dump_failed_chain(const Submission &S, const size_t g, const int status) {
+    const PoaChain &pc = S.chain(g);
+    FILE *f = fopen(S.env.dump_chain, "wb");
+    if (!f) return;
+    const int hdr[8] = {0x4c434443, pc.mode, pc.n_reads, status, pc.threads, pc.wmax, pc.ring_k, pc.lds_words * 4};
+    fwrite(hdr, sizeof(int), 8, f);
+    const std::vector<PoaRead> &pr = S.preads[S.chain_batch[g]];
+    for (int q = 0; q < pc.n_reads; ++q) {
+        const PoaRead &r = pr[pc.read0 + q];
+        const int rec[6] = {r.len, r.skip, r.ref_beg, r.ref_end, r.read_beg, r.read_end};
+        fwrite(rec, sizeof(int), 6, f);
+        std::vector<uint8_t> bases((size_t)std::max(r.len, 0));
+        if (r.len > 0) (void)hipMemcpy(bases.data(), (const void *)(uintptr_t)r.seq_off, (size_t)r.len, hipMemcpyDeviceToHost);
+        fwrite(bases.data(), 1, bases.size(), f);
+    }
+    fclose(f);
+}
+// the error text of a chain whose status ends the submission (o: its record of the round at hand)
+static std::string failed_chain_text(const Submission &S, const size_t g, const PoaChainOut &o) {
+    const PoaChain &pc = S.chain(g); const int k = S.chain_batch[g];
+    return "POA kernel status " + std::to_string(o.status) + " on chain " + std::to_string(g - S.chain_base[k]) + " of batch " + std::to_string(k) + " (mode " + std::to_string(pc.mode) +
+           ", " + std::to_string(pc.n_reads) + " reads, longest " + std::to_string(pc.max_len) + ", threads " + std::to_string(pc.threads) + ", window " + std::to_string(pc.wmax) + ", ring slots " +
+           std::to_string(pc.ring_k) + ", LDS " + std::to_string(pc.lds_words * 4) + " B, nodes " + std::to_string(o.n_node) + "/" + std::to_string(pc.node_cap) + ", reads aligned " + std::to_string(o.n_aligned_reads) + ")" +
+           (o.status == LCD_ERR_WATCHDOG ? [&] { std::string t = "; last backtrack states (row, column, state):"; const unsigned long long w[4] = {o.t_plan, o.t_poll, o.t_bp, o.t_add};
+                for (int q = 0; q < 4; ++q) t += " (" + std::to_string((unsigned)(w[q] & 0xffffffffu)) + ", " + std::to_string((unsigned)((w[q] >> 32) & 0xffffff)) + ", " + std::to_string((unsigned)(w[q] >> 56)) + ")"; return t; }() : std::string());
+}
+// LCD_PLACEMENT, experiment: which CU did every wide chain run on, and when
+static void report_placement(const Submission &S) {
+    for (size_t g = 0; g < S.nC_all; ++g) { if (chain_threads(S.chain(g)) < 512) continue; const PoaChainOut &o = S.out(g);
+        fprintf(stderr, "[place] thr %d xcc %u se %u sh %u cu %u simd %u  t %.1f..%.1f ms ticks %.3e\n", chain_threads(S.chain(g)), o.xcc_id & 15, (o.hw_id >> 13) & 7, (o.hw_id >> 12) & 1, (o.hw_id >> 8) & 15, (o.hw_id >> 4) & 3,
+                o.rt_begin / 1e5, o.rt_end / 1e5, (double)o.t_total); }
+}
+// LCD_CHAIN_TIMES=<file>: every chain's class, pool, start and end (100 MHz device clock, relative to the first start): tools/occupancy.py
+static void report_chain_times(const Submission &S) {
+    FILE *f = fopen(S.env.chain_times, "w");
+    if (!f) return;
+    unsigned long long t0 = ~0ull;
+    for (size_t g = 0; g < S.nC_all; ++g) t0 = std::min(t0, S.out(g).rt_begin);
+    for (size_t g = 0; g < S.nC_all; ++g) { const PoaChainOut &o = S.out(g); const PoaChain &pc = S.chain(g);
+        fprintf(f, "%d %d %d %llu %llu %u %u %d %d %d %llu %llu %llu %llu %llu\n", pc.threads, pc.lds_words * 4, pc.mode, o.rt_begin - t0, o.rt_end - t0, o.xcc_id & 15, (o.hw_id >> 8) & 15, pc.max_len, pc.n_reads, pc.cert, (unsigned long long)o.t_setup,
+                (unsigned long long)o.t_total, (unsigned long long)o.t_dp, (unsigned long long)o.cells, (unsigned long long)o.t_bt); }
+    fclose(f);
+}
+// LCD_PROFILE_CHAINS: the tail, CU-seconds per launch group, ticks per kind of chain and per workgroup class
+static void report_profile_chains(const Submission &S) {
+    const size_t nC_all = S.nC_all;
+    { // the chains that end last: the tail of the submission (times on the device's 100 MHz clock, relative to the first chain's start)
+        std::vector<size_t> ord(nC_all); unsigned long long t0 = ~0ull;
+        for (size_t g = 0; g < nC_all; ++g) { ord[g] = g; t0 = std::min(t0, S.out(g).rt_begin); }
+        std::sort(ord.begin(), ord.end(), [&](size_t a, size_t c) { return S.out(a).rt_end > S.out(c).rt_end; });
+        for (size_t q = 0; q < std::min<size_t>(10, ord.size()); ++q) { const size_t g = ord[q]; const PoaChainOut &o = S.out(g); const PoaChain &pc = S.chain(g);
+            fprintf(stderr, "[tail] thr %4d lds %3dK mode %d reads %3d maxlen %5d nodes %6d: %.1f .. %.1f ms  (dp %.0f%% bt %.0f%% graph %.0f%% out %.0f%%)  cells %.2e\n", chain_threads(pc), pc.lds_words * 4 >> 10, pc.mode, pc.n_reads, pc.max_len, o.n_node,
+                    (o.rt_begin - t0) / 1e5, (o.rt_end - t0) / 1e5, 100.0 * o.t_dp / o.t_total, 100.0 * o.t_bt / o.t_total, 100.0 * o.t_graph / o.t_total, 100.0 * o.t_out / o.t_total, (double)o.cells); }
+    }
+    { // CU-seconds per launch group: sum of chain ticks / workgroups that fit a CU (LDS- or register-limited: 128 VGPRs are 16 wavefronts per CU)
+        std::map<long long, std::pair<double, int>> gsum;
+        for (size_t g = 0; g < nC_all; ++g) { auto &e = gsum[chain_group_key(S.chain(g))]; e.first += (double)S.out(g).t_total; e.second++; }
+        double tot = 0;
+        for (auto &kv : gsum) {
+            const int thr = (int)(kv.first >> 20), lds = (int)(kv.first & ((1 << 20) - 1)) * 4;
+            const int per_cu = chains_per_cu(lds, thr, kSchedOverhead);
+            const double cus = kv.second.first / 2.4e9 / per_cu; tot += cus;
+            fprintf(stderr, "[lcd] group thr %4d lds %3dK: %6d chains, %7.2f wg-s, %2d per CU -> %7.2f CU-s\n", thr, lds >> 10, kv.second.second, kv.second.first / 2.4e9, per_cu, cus);
+        }
+        fprintf(stderr, "[lcd] total %.2f CU-s = %.1f ms of %d CUs\n", tot, tot / g_n_cus * 1e3, g_n_cus);
+    }
+    // per (class, kind of chain): ticks per phase and cells -- kind 0: K1 (adaptive band), 1: K2 full rows, 2: K2 certified band, +4: long-chain (solo) workgroup
+    {
+        struct Acc { double n = 0, tt = 0, td = 0, tb = 0, tbp = 0, tad = 0, tso = 0, tse = 0, tsub = 0, to = 0, cells = 0, reads = 0, rows = 0; };
+        std::map<int, Acc> by;
+        for (size_t g = 0; g < nC_all; ++g) { const PoaChain &pc = S.chain(g); const PoaChainOut &o = S.out(g);
+            Acc &a = by[chain_threads(pc) * 8 + (pc.mode ? (pc.cert ? 2 : 1) : 0) + (pc.solo ? 4 : 0)];
+            a.n += 1; a.tt += (double)o.t_total; a.td += (double)o.t_dp; a.tb += (double)o.t_bt; a.tbp += (double)o.t_bp; a.tad += (double)o.t_add; a.tso += (double)o.t_sort; a.tse += (double)o.t_setup;
+            a.tsub += (double)o.t_sub; a.to += (double)o.t_out; a.cells += (double)o.cells; a.reads += o.n_aligned_reads; a.rows += (double)o.n_aligned_reads * o.n_node; }
+        for (auto &kv : by) { const Acc &a = kv.second;
+            fprintf(stderr, "[kind] thr %4d kind %d: %6.0f chains %8.0f reads  ticks total %.3e | dp %.1f%% bt %.1f%% plan %.1f%% update %.1f%% re-sort %.1f%% setup %.1f%% sub %.1f%% out %.1f%% | cells %.3e  ticks/cell(dp) %.2f  ~rows %.3e\n",
+                    kv.first >> 3, kv.first & 7, a.n, a.reads, a.tt, 100 * a.td / a.tt, 100 * a.tb / a.tt, 100 * a.tbp / a.tt, 100 * a.tad / a.tt, 100 * a.tso / a.tt, 100 * a.tse / a.tt, 100 * a.tsub / a.tt, 100 * a.to / a.tt,
+                    a.cells, a.td / std::max(1.0, a.cells), a.rows); }
+    }
+    // per-phase shader-clock ticks, summed per workgroup class and for the slowest chain
+    for (int cls : {64, 128, 256, 512, 1024}) {
+        unsigned long long tt = 0, td = 0, tb = 0, tg = 0, to = 0, ts = 0, mx = 0, tbp = 0, tad = 0, tso = 0, tse = 0, tpl = 0; int cnt = 0; size_t mxc = 0;
+        for (size_t g = 0; g < nC_all; ++g) { if (chain_threads(S.chain(g)) != cls) continue; const PoaChainOut &o = S.out(g); ++cnt;
+            tt += o.t_total; td += o.t_dp; tb += o.t_bt; tg += o.t_graph; to += o.t_out; ts += o.t_sub; tbp += o.t_bp; tad += o.t_add; tso += o.t_sort; tse += o.t_setup; tpl += o.t_plan; if (o.t_total >= mx) { mx = o.t_total; mxc = g; } }
+        if (!cnt) continue;
+        fprintf(stderr, "[lcd] class %4d: row plan %.3e  graph update %.3e  re-sort %.3e  row setup %.3e  bound arrays %.3e\n", cls, (double)tbp, (double)tad, (double)tso, (double)tse, (double)tpl);
+        if (S.env.dbg_intervals) { // reads of certified-band chains by their widest interval (the t_setup slot carries five 12-bit counters per chain)
+            unsigned long long h[5] = {0, 0, 0, 0, 0};
+            for (size_t g = 0; g < nC_all; ++g) { if (chain_threads(S.chain(g)) != cls || !S.chain(g).cert) continue; const unsigned long long v = S.out(g).t_setup; for (int q = 0; q < 5; ++q) h[q] += (v >> (12 * q)) & 4095; }
+            fprintf(stderr, "[lcd] class %4d: certified-band reads by widest interval <= 60 / 124 / 188 / 256 / wider: %llu / %llu / %llu / %llu / %llu\n", cls, h[0], h[1], h[2], h[3], h[4]);
+        }
+        { double tk = 0; for (size_t g = 0; g < nC_all; ++g) if (chain_threads(S.chain(g)) == cls) tk += (double)S.out(g).t_poll;
+          fprintf(stderr, "[lcd] class %4d: %5d chains  sum ticks total %.3e dp %.3e bt %.3e graph %.3e (of which serial Kahn walk %.3e) sub %.3e out %.3e\n", cls, cnt, (double)tt, (double)td, (double)tb, (double)tg, tk, (double)ts, (double)to); }
+        const PoaChainOut &o = S.out(mxc); const PoaChain &pm = S.chain(mxc);
+        fprintf(stderr, "[lcd]   slowest chain %zu: mode %d reads %d maxlen %d nodes %d  total %.3e dp %.3e bt %.3e graph %.3e sub %.3e out %.3e cells %llu\n", mxc, pm.mode,
+                pm.n_reads, pm.max_len, o.n_node, (double)o.t_total, (double)o.t_dp, (double)o.t_bt, (double)o.t_graph, (double)o.t_sub, (double)o.t_out, o.cells);
+        fprintf(stderr, "[lcd]     of its dp: plan-window refreshes %.3e  mailbox polls %.3e (one wavefront)\n", (double)o.t_plan, (double)o.t_poll);
+        fprintf(stderr, "[lcd]     row plan %.3e  graph update %.3e  re-sort %.3e  row setup %.3e\n", (double)o.t_bp, (double)o.t_add, (double)o.t_sort, (double)o.t_setup);
+        if (S.env.dbg_intervals) fprintf(stderr, "[lcd]     reads by widest interval <=60 / <=124 / <=188 / <=380 / wider: %llu %llu %llu %llu %llu\n", (unsigned long long)(o.t_setup & 4095), (unsigned long long)((o.t_setup >> 12) & 4095), (unsigned long long)((o.t_setup >> 24) & 4095), (unsigned long long)((o.t_setup >> 36) & 4095), (unsigned long long)((o.t_setup >> 48) & 4095));
+    }
+}
+
+} // namespace
+
+// The driver: the stages of a submission in order.  The preparation thread runs beside begin's tail and the anchor stage, the strings thread beside the
+// ref<->cons WFA stage; both are joined here, and by the submission's destructor on an early return.
+static int run_many_once(lcd_batch_t **bs, int nb) {
+    if (nb <= 0) return 0;
+    if (const int rc = Submission::validate(bs, nb)) return rc;
+    Submission S(bs, nb);
+    lcd_batch_t *const L = S.L;
+    if (const int rc = S.begin()) return rc;
+    if (const int rc = S.start_prep()) return rc;       // prep_chains (+ prepare_round0) on the preparation thread
+    if (const int rc = S.anchor_stage()) return rc;     // S1; joins the preparation thread before it narrows the reads
+    if (const int rc = S.join_prep()) return rc;
+    HIPCHK(hipEventRecord(L->ev[1], S.st));
+    S.tp0 = now_ms();
+    if (S.env.time_host) fprintf(stderr, "[host] anchor stage: %.1f ms on the host clock\n", S.tp0 - S.t_begin);
+    if (const int rc = S.poa_stage()) return rc;        // S2: read table, round 0's plan, the rounds
+    if (S.env.time_host) fprintf(stderr, "[host] POA stage ends %.1f ms after its start\n", now_ms() - S.tp0);
+    HIPCHK(hipEventRecord(L->ev[2], S.st));
+    S.th0 = now_ms();
+    if (const int rc = S.refcons_jobs()) return rc;     // S3's job table
+    if (const int rc = S.start_strings()) return rc;    // S4 on the strings thread
+    if (const int rc = S.wfa_stage()) return rc;        // S3
+    if (const int rc = S.join_strings()) return rc;     // S4's end (LCD_STRINGS_SEQ: S4 itself)
+    if (const int rc = S.compose_ref_read()) return rc; // S5
+    if (const int rc = S.candidate_vars()) return rc;   // S6
+    return S.finish();
 }
 
 int lcd_batch_run(lcd_batch_t *b) { return lcd_batch_run_many(&b, 1); }
@@ -2503,7 +2732,7 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
             if (!round) pc.out_off = d_out.addr() + out_rel[which[i]];
             else {
                 const int old_cap = pc.node_cap; const uint64_t keep = pc.out_off;
-                chain_caps(*opt, crec[which[i]], preads, crec[which[i]].cert_fail_round < 0 ? scale : std::max(1, scale >> (crec[which[i]].cert_fail_round + 1)), pc, cenv);
+                chain_caps(*opt, crec[which[i]], preads, retry_scale(crec[which[i]], scale), pc, cenv);
                 pc.out_off = keep;
                 if (pc.node_cap > old_cap) { // larger graph capacity -> larger output block
                     retry_out.emplace_back(new DevBuf());
@@ -2523,12 +2752,7 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
         std::vector<int> again;
         for (size_t i = 0; i < which.size(); ++i) {
             couts[which[i]] = tmp[i];
-            if (tmp[i].status == LCD_ERR_CELLS || tmp[i].status == LCD_ERR_NODES || tmp[i].status == LCD_ERR_EDGES) again.push_back(which[i]);
-            else if (tmp[i].status == LCD_ERR_CERT && pch[which[i]].cert > 0) {
-                ChainRec &CR = crec[which[i]];
-                CR.cert_fail_round = round; CR.cert_level = cert_next_level(pch[which[i]]);
-                again.push_back(which[i]);
-            }
+            if (chain_goes_back(tmp[i].status, pch[which[i]], crec[which[i]], round)) again.push_back(which[i]);
         }
         if (!again.empty()) scale *= 2;
         which.swap(again);

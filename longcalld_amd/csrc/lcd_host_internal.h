@@ -148,7 +148,7 @@ struct ChainRec {
     std::vector<int> members;     // indices into the region's sorted read list
     int read0;                    // first PoaRead
     int cert_fail_round = -1;     // K2: the last round in which the certified band did not fit its class's window (the chain then moves one class up)
-    int solo = -1;                // -1: by the fixed threshold (LCD_SOLO_RL); 0 / 1: decided for the submission at hand (run_many_once: the longest chains of what is in flight)
+    int solo = -1;                // -1: by the fixed threshold (LCD_SOLO_RL); 0 / 1: decided for the submission at hand (lcd_host.cpp choose_long_chains: the longest chains of what is in flight)
     int cert_level = -1;          // -1: not chosen yet; 1: certified band in the single-wavefront rows; 2: in the systolic rows of the class the reads' length asks for (noisy reads); 0: full rows
 };
 struct AnchorRec {
@@ -219,7 +219,7 @@ struct lcd_batch_s {
     DevBuf d_read_patches, d_aends_jobs, d_aends_outs, d_in, d_chains, d_preads, d_poa_arena, d_poa_out, d_poa_outs, d_ed_jobs, d_ed_outs, d_wfa_jobs,
         d_wfa_out, d_wfa_outs, d_str_jobs, d_str_outs, d_final, d_gate, d_cmp_jobs, d_cmp_outs, d_cmp_seg, d_cmp_segres, d_seg_out, d_rr,
         d_var_jobs, d_var_outs, d_var_work, d_vreg_jobs, d_vreg_outs, d_var_out, d_slot_flags, d_spare, d_packed, d_unpack,
-        d_early_arena, d_chains_early, d_poa_outs_early,   // the long K2 chains that start before the anchor stage (run_many_once)
+        d_early_arena, d_chains_early, d_poa_outs_early,   // the long K2 chains that start before the anchor stage (lcd_host.cpp launch_early)
         d_ed_arena;                                                         // K4's stored columns when it runs beside K3 in the anchor stage
     bool uploaded = false, ran = false, downloaded = false;
     // results (host)
