@@ -1172,6 +1172,107 @@ int lcd_call_file_fields(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const 
 int lcd_call_files_fields(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
                           lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out);
 
+/* ---- refined alignments in the phased output (longcallD call --refine-aln -b): refine_bam1 + update_bam1_tags (src/bam_utils.c:1718-1942) in HBM ----
+ * lcd_chunk_refine_records == lcd_chunk_tag_records_sel (same records, same skip / order selection, same handle) where every KEPT record is first rewritten with the
+ * alignment of its read's FINAL digar list (bam_refine_kernel.hip, one wavefront per record; no record and no digar of an untouched read crosses PCIe):
+ *   digars   read r's list is touched_digars[touched_off[k] .. touched_off[k + 1]) when touched_reads[k] == r (the reads a noisy region rewrote,
+ *            lcd_update_digars_from_msa1 applied on the host in the reference's order; uploaded, counted in lcd_copy_counters[1]), else the chunk's own digars in
+ *            HBM.  touched_reads names each read at most once; a digar with type outside 0 ... 8 or len < 0, or a list whose lengths reach 2^28 in all, is -4;
+ *            qi is taken as it is (the reference's rewrite leaves '=' digars with qi -1): a base outside [0, l_seq) reads as n.
+ *   R1 pos   core.pos = digars[0].pos - 1, also when the CIGAR turns out identical.
+ *   R2 CIGAR one word per run of digars of equal type, in order (longcalld_push_cigar, :112-121: adjacent equal operations add up; a reference skip the input had
+ *            is not in the digars and so not in the result); then a hard clip as the FIRST or LAST word becomes a soft clip (kept reads are never supplementary).
+ *   R3       new words == the record's words: nothing else changes, no tag is touched (HP / PS excepted).
+ *   R4       otherwise the record is name, new words, then bases, qualities and fields as they were, n_cigar updated, and
+ *              NM  only if a first NM field exists and bam_aux2i of it (the project's rule: types c C s S i I give their value, any other type 0) differs from
+ *                  the sum of len over X / I / D digars: the field is deleted and NM:i (4 bytes) appended;
+ *              MD  only if a first MD field exists, has type Z and its string differs from get_md_from_digar (:1739-1771): deleted, MD:Z appended.  One number per
+ *                  X / D digar (the '=' bases since the last X / D digar, "0" included), '^' in front of a deletion's bases, the rest at the end if > 0; an M digar
+ *                  counts for nothing, as in the reference;
+ *              cs  the same with get_cs_from_digar (:1773-1805): ":len" per '=' digar (so the text depends on how the list is cut), "*" + ref + read base per X base,
+ *                  "+" bases, "-" ref bases.
+ *            A first MD / cs field of another type than Z is left alone; later fields of a name are never looked at.
+ *   R5       HP / PS then follow lcd_chunk_tag_records' rule on the record as it is: appended fields come in the order NM, MD, cs, HP, PS; every field that is not
+ *            deleted keeps its place and bytes.
+ * Project rules where the reference exits, is undefined, or htslib would decide:
+ *   unrefined  a kept record gets HP / PS only -- byte for byte lcd_chunk_tag_records_sel's record -- and is counted under the FIRST reason that holds:
+ *              n_no_digars (the read is skipped or has no digar); n_qlen_mismatch (digar2qlen != l_seq: the reference exits; hard-clipped primaries land here; also
+ *              a record whose name, CIGAR, bases and qualities do not fit its block_size); n_bad_pos (digars[0].pos < 1: the reference exits); n_too_many_ops (more
+ *              than 65 535 words in the result -- htslib would write a CG tag; the input's n_cigar is a 16-bit field); n_cg_cigar (the input's CIGAR lives in a CG
+ *              tag: n_cigar == 2, first word <l_seq>S, second word N, a first CG field of type B).
+ *   letters    MD letters are upper-case ACGTN and cs letters lower-case acgtn, from the codes 0-4 (the window's codes; seq_nt16_int of the record's 4-bit bases).
+ *   window     ref_seq[0] = position ref_beg (1-based), codes 0-4 or letters, ref_end INCLUSIVE as everywhere in this header (get_bam_chunk_reg_ref_seq0 sets
+ *              chunk->ref_end = ref_beg + len - 1 in these terms).  The reference's bounds test is `pos >= ref_beg && pos < ref_end` with that same number: a base
+ *              ON ref_end -- the window's last base -- reads as N / n, as does every position outside; this is kept.  ref_seq NULL or ref_end < ref_beg: all N.
+ *   bin        where pos or the CIGAR changed, bin = reg2bin(pos, pos + reference length of the new CIGAR), one base for a CIGAR without reference bases; else
+ *              the record's bin is left as it is.
+ *   order      a rewrite can move pos, so the stream may stop being sorted; nothing here sorts (the writer's index rule applies to the output as it is).
+ * stats (may be NULL): counts over the records written; n_refined = CIGAR changed (R4), n_identical = R3, n_unrefined = the sum of the five reasons; n_pos_moved
+ * counts refined or identical records whose pos changed; n_*_replaced the R4 fields; bytes_*_up what the call uploaded; ms_measure / ms_emit wall clock of the two
+ * passes (each includes its copies and one synchronisation).  NULL on failure (lcd_last_error()); a chunk that was not made from a BAM, or opened and not resolved,
+ * is -4.  Filtered records lose their first HP / PS as before. */
+/* The refine log of a chunk: one entry per (cluster, read) of every noisy region that resolved with n_cons > 0, in the order update_digars_from_aln_str
+ * (src/align.c:1745-1756, called at :1803-1806) walks them -- regions in the order the rounds resolve them, clusters 0 .. n_cons - 1, reads in clu_read_ids order.
+ * An entry holds what lcd_update_digars_from_msa1 takes: the read, its cover flag and read_reg_beg / read_reg_end for the region (the pass plan's slices, computed
+ * on the device), the region's bounds, and the read's ref<->read rows (stage S5, opt.collect_ref_read_aln_str); `pass` is the pass that resolved the region.
+ * lcd_chunks_noisy_rounds_log == lcd_chunks_noisy_rounds with a sink per chunk (logs NULL, or an entry NULL: no sink for that chunk; with no sink at all the call IS
+ * lcd_chunks_noisy_rounds, which still refuses opt->collect_ref_read_aln_str with -2).  With a sink the driver's batches run with collect_ref_read_aln_str = 1;
+ * collect_noisy_vars stays 2: only the ref<->read rows come down beside the variants, every other string stays in HBM.  The chunk's digars in HBM are never
+ * changed: a region is resolved at most once, noisy regions are disjoint, and a rewrite replaces digars inside its own region only, so vars / state / done come out
+ * as without a sink (tests/test_gpu_refine_log.py compares them).  A call that fails leaves in the log what it had appended up to there.
+ * lcd_refine_log_apply (pure host code): the log applied front to back with lcd_update_digars_from_msa1 on a running copy of the digars handed in (lcd_chunk_digars'
+ * CSR; qlen[r] = the read's length) -- return code 1 keeps the read's list (counted in *n_rejected), 2 leaves it untouched -- and the FINAL lists of the reads the
+ * log names as a CSR for lcd_chunk_refine_records (touched_reads ascending; malloc()'d, free() each).  Entries of one read are applied in log order: the cut of the
+ * list decides the cs text.  lcd_refine_log_append copies an entry's rows (the driver's sink; tests); lcd_refine_log_entry's rows point into the log. */
+typedef struct lcd_refine_log_s lcd_refine_log_t;
+typedef struct lcd_refine_entry_t { int read_id, cover, read_beg, read_end, aln_len, pass; int64_t reg_beg, reg_end; const uint8_t *target, *query; } lcd_refine_entry_t;
+lcd_refine_log_t *lcd_refine_log_create(void);
+void lcd_refine_log_free(lcd_refine_log_t *log);
+int64_t lcd_refine_log_n_entries(const lcd_refine_log_t *log);
+int64_t lcd_refine_log_row_bytes(const lcd_refine_log_t *log);   /* the rows' bytes: what crossed PCIe for the log */
+int lcd_refine_log_append(lcd_refine_log_t *log, const lcd_refine_entry_t *entry);
+int lcd_refine_log_entry(const lcd_refine_log_t *log, int64_t i, lcd_refine_entry_t *out);
+int lcd_refine_log_apply(const lcd_refine_log_t *log, int n_reads, const uint64_t *digar_off, const lcd_digar_t *digars, const int *qlen, int *n_touched,
+                         int **touched_reads, uint64_t **touched_off, lcd_digar_t **touched_digars, int64_t *n_rejected /* may be NULL */);
+int lcd_chunks_noisy_rounds_log(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt, lcd_refine_log_t *const *logs);
+/* per row of lcd_batch_region_vars' row_read_ids (cluster 0's reads, then cluster 1's) the read's ref<->read rows of a resolved region, pointing into the batch's
+ * download (valid until the batch runs or is cleared again); needs opt.collect_ref_read_aln_str (-5); returns the number of rows, 0 for an unresolved region */
+int lcd_batch_region_ref_read_rows(lcd_batch_t *b, int region, int n_rows, int *aln_len, const uint8_t **target, const uint8_t **query);
+typedef struct lcd_refine_stats_t {
+    int64_t n_records, n_kept, n_refined, n_identical, n_unrefined, n_pos_moved, n_no_digars, n_qlen_mismatch, n_bad_pos, n_too_many_ops, n_cg_cigar;
+    int64_t n_nm_replaced, n_md_replaced, n_cs_replaced, n_touched, bytes_digars_up, bytes_ref_up;
+    double ms_measure, ms_emit;
+    int64_t n_log_entries, bytes_log_down, n_log_rejected;   /* the drivers below: the refine logs of the chunks written (0 from lcd_chunk_refine_records itself) */
+} lcd_refine_stats_t;
+lcd_tagged_t *lcd_chunk_refine_records(const lcd_chunk_t *chunk, int n_touched, const int *touched_reads, const uint64_t *touched_off /* n_touched + 1 */,
+                                       const lcd_digar_t *touched_digars, const uint8_t *ref_seq, int64_t ref_beg, int64_t ref_end, const int *haps,
+                                       const int64_t *phase_sets, const uint8_t *skip, const int *order, lcd_refine_stats_t *stats);
+
+/* The drivers with refined alignments (longcallD call --refine-aln -b; here --refine-bam).  A chunk handle carries its own sink: lcd_chunk_set_refine(chunk, 1)
+ * gives it an empty refine log (0 takes it away; lcd_chunk_refine_log: the log, owned by the handle).  chunks_call's rounds then write that log
+ * (lcd_chunks_noisy_rounds_log), and the alignment writer -- lcd_bam_writer_append / lcd_write_phased_bam -- rewrites such a chunk's records with
+ * lcd_chunk_refine_records instead of lcd_chunk_tag_records_sel: lcd_chunk_digars once and only if the log has entries, lcd_refine_log_apply, the touched reads'
+ * final lists up, the window = the chunk's first.ref_seq / ref_beg / ref_end.  The VCF, HP and PS of a run are those of the run without it.  A several-file chunk
+ * is one chunk with a selection and goes the same way.  A right-cover rewrite can move POS: the output may stop being sorted; the writer then completes without
+ * <out.bam>.bai and says why (out_bai_skipped / out_bai_skip_reason), as for any unsorted stream; nothing is sorted here.
+ * lcd_chunks_call_refine: lcd_chunk_set_refine on every chunk, then lcd_chunks_call.  lcd_write_phased_bam_refine / lcd_bam_writer_set_refine_stats: the writer
+ * with the sum of the refined chunks' lcd_refine_stats_t (counters, times, and the logs: n_log_entries, bytes_log_down = the rows that came down,
+ * n_log_rejected = entries double_check_digar rejected); stats NULL: no sum.  lcd_call_bam_regions_refine == lcd_call_bam_regions_out, lcd_call_file_refine ==
+ * lcd_call_file_indexed (idx may be NULL), lcd_call_files_refine == lcd_call_files, each with every chunk refined when an alignment output is asked for; without
+ * bam_out the option has no effect, as in the reference.  Existing entry points, structs, return codes and messages are unchanged. */
+int lcd_chunk_set_refine(lcd_chunk_t *chunk, int on);
+lcd_refine_log_t *lcd_chunk_refine_log(const lcd_chunk_t *chunk);
+int lcd_chunks_call_refine(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body);
+int lcd_write_phased_bam_refine(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats);
+int lcd_bam_writer_set_refine_stats(lcd_bam_writer_t *w, lcd_refine_stats_t *refine_stats);
+int lcd_call_bam_regions_refine(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
+                                const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                                lcd_bam_out_t *bam_out, lcd_refine_stats_t *refine_stats);
+int lcd_call_file_refine(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats,
+                         lcd_refine_stats_t *refine_stats);
+int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
+                          lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_refine_stats_t *refine_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,20 @@ class LcdVcfFieldsOut(C.Structure):
     _fields_ = [("n_te_seqs", C.c_int), ("te_names", C.POINTER(C.c_char_p)), ("n_mei_lines", C.c_int64), ("n_rnames", C.c_int), ("rnames", C.POINTER(C.c_char_p))]
 
 
+class LcdRefineStats(C.Structure):
+    """lcd_refine_stats_t: what lcd_chunk_refine_records did to the records it wrote"""
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "n_refined", "n_identical", "n_unrefined", "n_pos_moved", "n_no_digars", "n_qlen_mismatch", "n_bad_pos",
+                                         "n_too_many_ops", "n_cg_cigar", "n_nm_replaced", "n_md_replaced", "n_cs_replaced", "n_touched", "bytes_digars_up",
+                                         "bytes_ref_up")] + [("ms_measure", C.c_double), ("ms_emit", C.c_double)] + [
+                    (n, C.c_int64) for n in ("n_log_entries", "bytes_log_down", "n_log_rejected")]
+
+
+class LcdRefineEntry(C.Structure):
+    """lcd_refine_entry_t: one (cluster, read) of a resolved noisy region -- what lcd_update_digars_from_msa1 takes"""
+    _fields_ = [(n, C.c_int) for n in ("read_id", "cover", "read_beg", "read_end", "aln_len", "pass_")] + [("reg_beg", C.c_int64), ("reg_end", C.c_int64),
+                                                                                                        ("target", C.POINTER(C.c_uint8)), ("query", C.POINTER(C.c_uint8))]
+
+
 LCD_RNAMES_NONE, LCD_RNAMES_SV, LCD_RNAMES_ALL = 0, 1, 2
 LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG, LCD_ERR_INPUT_HEADERS = -50, -51, -52, -53, -54
 LCD_MAX_INPUTS = 64
@@ -285,6 +299,10 @@ EXPORTS = [
     "lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_bam_writer_set_sort", "lcd_call_files",
     "lcd_te_lib_from_fasta", "lcd_te_lib_from_fasta_free", "lcd_format_vcf_fields", "lcd_alt_read_names", "lcd_vcf_fields_out_free", "lcd_chunks_call_fields",
     "lcd_call_bam_regions_fields", "lcd_call_file_fields", "lcd_call_files_fields",
+    "lcd_chunk_refine_records", "lcd_refine_log_create", "lcd_refine_log_free", "lcd_refine_log_n_entries", "lcd_refine_log_row_bytes", "lcd_refine_log_append",
+    "lcd_refine_log_entry", "lcd_refine_log_apply", "lcd_chunks_noisy_rounds_log", "lcd_batch_region_ref_read_rows",
+    "lcd_chunk_set_refine", "lcd_chunk_refine_log", "lcd_chunks_call_refine", "lcd_write_phased_bam_refine", "lcd_bam_writer_set_refine_stats", "lcd_call_bam_regions_refine",
+    "lcd_call_file_refine", "lcd_call_files_refine",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -469,6 +487,20 @@ def load_library():
     lib.lcd_chunk_tag_records_sel.restype = C.c_void_p
     lib.lcd_chunk_tag_records_sel.argtypes = [C.c_void_p, i32p, i64p, u8p, i32p]
     lib.lcd_bam_writer_set_sort.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_refine_log_create.restype = C.c_void_p
+    lib.lcd_refine_log_free.argtypes = [C.c_void_p]
+    lib.lcd_refine_log_free.restype = None
+    for f in ("lcd_refine_log_n_entries", "lcd_refine_log_row_bytes"):
+        getattr(lib, f).argtypes = [C.c_void_p]
+        getattr(lib, f).restype = C.c_int64
+    lib.lcd_refine_log_append.argtypes = [C.c_void_p, C.POINTER(LcdRefineEntry)]
+    lib.lcd_refine_log_entry.argtypes = [C.c_void_p, C.c_int64, C.POINTER(LcdRefineEntry)]
+    lib.lcd_refine_log_apply.argtypes = [C.c_void_p, C.c_int, u64p_, C.POINTER(LcdDigar), i32p, i32p, C.POINTER(i32p), C.POINTER(u64p_), C.POINTER(C.POINTER(LcdDigar)), i64p]
+    lib.lcd_chunks_noisy_rounds_log.argtypes = [C.c_int, C.POINTER(LcdRoundsChunk), C.POINTER(LcdOpt), C.POINTER(LcdPassOpt), C.POINTER(C.c_void_p)]
+    lib.lcd_batch_region_ref_read_rows.argtypes = [C.c_void_p, C.c_int, C.c_int, i32p, C.POINTER(u8p), C.POINTER(u8p)]
+    lib.lcd_chunk_refine_records.restype = C.c_void_p
+    lib.lcd_chunk_refine_records.argtypes = [C.c_void_p, C.c_int, i32p, u64p_, C.POINTER(LcdDigar), C.c_char_p, C.c_int64, C.c_int64, i32p, i64p, u8p, i32p,
+                                             C.POINTER(LcdRefineStats)]
     lib.lcd_call_files.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats), i64p]
     lib.lcd_call_free.restype = None
     fo = C.POINTER(LcdVcfFieldsOut)
@@ -507,6 +539,16 @@ def load_library():
     lib.lcd_edlib_edit_distance.argtypes = [u8p, C.c_int, u8p, C.c_int]
     lib.lcd_collect_noisy_reg_aln_strs.argtypes = [C.POINTER(LcdOpt), C.POINTER(LcdReadView), C.c_int64, C.c_int64, C.c_int, C.c_int, i32p,
                                                    u8p, C.c_int, i32p, C.POINTER(i32p), C.POINTER(C.POINTER(LcdAlnStr))]
+    rsp = C.POINTER(LcdRefineStats)
+    lib.lcd_chunk_set_refine.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_chunk_refine_log.restype = C.c_void_p
+    lib.lcd_chunk_refine_log.argtypes = [C.c_void_p]
+    lib.lcd_chunks_call_refine.argtypes = lib.lcd_chunks_call.argtypes
+    lib.lcd_write_phased_bam_refine.argtypes = lib.lcd_write_phased_bam.argtypes + [rsp]
+    lib.lcd_bam_writer_set_refine_stats.argtypes = [C.c_void_p, rsp]
+    lib.lcd_call_bam_regions_refine.argtypes = lib.lcd_call_bam_regions_out.argtypes + [rsp]
+    lib.lcd_call_file_refine.argtypes = lib.lcd_call_file_indexed.argtypes + [rsp]
+    lib.lcd_call_files_refine.argtypes = lib.lcd_call_files.argtypes + [rsp]
     _lib = lib
     return lib
 

@@ -619,6 +619,49 @@ class DeviceChunk:
         finally:
             lib.lcd_tagged_free(h)
 
+    def refine_records(self, haps, phase_sets, touched=None, ref=None, ref_beg=1, ref_end=0, skip=None, order=None):
+        """lcd_chunk_refine_records: tag_records_sel where every kept record first gets the alignment of its read's final digars (CIGAR, POS, bin, NM / MD / cs).
+        touched = {read id: (n, >= 4) rows [pos, type, len, qi(, is_low_qual)]} for the reads a noisy region rewrote (any other read uses the chunk's digars in HBM);
+        ref = the chunk's reference window as letters or codes 0-4 (bytes / uint8 array), ref[0] = position ref_beg, ref_end inclusive.
+        -> (bytes of the records back to back, their number, stats dict)"""
+        from ._lib import LcdDigar, LcdRefineStats
+        lib = self.lib
+        hp = np.concatenate([np.ascontiguousarray(haps, np.int32), np.zeros(1, np.int32)]); ps = np.concatenate([np.ascontiguousarray(phase_sets, np.int64), np.zeros(1, np.int64)])
+        if len(hp) <= self.n or len(ps) <= self.n:
+            raise ValueError("refine_records: haps / phase_sets shorter than the chunk's reads")
+        touched = touched or {}
+        ids = np.array(sorted(touched), np.int32)
+        rows = [np.asarray(touched[int(r)], np.int64) for r in ids]
+        rows = [x.reshape(-1, x.shape[-1]) if x.size else np.zeros((0, 5), np.int64) for x in rows]
+        off = np.concatenate([[0], np.cumsum([len(x) for x in rows])]).astype(np.uint64)
+        dg = (LcdDigar * max(int(off[-1]), 1))()
+        k = 0
+        for x in rows:
+            for d in x:
+                dg[k].pos, dg[k].type, dg[k].len, dg[k].qi = int(d[0]), int(d[1]), int(d[2]), int(d[3])
+                dg[k].is_low_qual = int(d[4]) if len(d) > 4 else 0
+                k += 1
+        refb = None if ref is None else (bytes(ref) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, np.uint8).tobytes())
+        if refb is not None and len(refb) < int(ref_end) - int(ref_beg) + 1:
+            raise ValueError("refine_records: ref is shorter than [ref_beg, ref_end]")
+        refbuf = C.create_string_buffer(refb, len(refb) + 1) if refb is not None else None     # (codes contain NULs: not a C string)
+        sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
+        od = np.ascontiguousarray(order, np.int32) if order is not None else None
+        st = LcdRefineStats()
+        h = lib.lcd_chunk_refine_records(self.h, len(ids), ids.ctypes.data_as(i32p), off.ctypes.data_as(C.POINTER(C.c_uint64)), dg,
+                                         C.cast(refbuf, C.c_char_p) if refbuf is not None else None, int(ref_beg), int(ref_end), hp.ctypes.data_as(i32p),
+                                         ps.ctypes.data_as(C.POINTER(C.c_int64)), _p8(sk) if sk is not None else None, od.ctypes.data_as(i32p) if od is not None else None,
+                                         C.byref(st))
+        if not h:
+            raise LcdError("lcd_chunk_refine_records failed: " + lib.lcd_last_error().decode())
+        try:
+            n = lib.lcd_tagged_size(h)
+            buf = C.create_string_buffer(max(n, 1))
+            check(lib.lcd_tagged_to_host(h, 0, n, buf), lib)
+            return buf.raw[:n], int(lib.lcd_tagged_n_records(h)), {f: getattr(st, f) for f, _ in LcdRefineStats._fields_}
+        finally:
+            lib.lcd_tagged_free(h)
+
     def resolve(self, src=None):
         """lcd_chunk_resolve: the second phase -- src = (ref, ref_beg, ref_end, is_ont) as for from_bam, or None; a second call raises (-4)"""
         from ._lib import LcdChunkSrc
@@ -1354,10 +1397,70 @@ def _clean_vars_struct_malloc(cv):
     return v
 
 
-def chunks_noisy_rounds(chunks, items, opt=None, popt=None):
+class RefineLog:
+    """lcd_refine_log_t: the (cluster, read) entries of the noisy regions a chunk's rounds resolved, in the reference's order"""
+
+    def __init__(self):
+        self.lib = load_library()
+        self.h = self.lib.lcd_refine_log_create()
+        if not self.h:
+            raise LcdError("lcd_refine_log_create failed")
+
+    def close(self):
+        if self.h:
+            self.lib.lcd_refine_log_free(self.h); self.h = None
+
+    def __len__(self):
+        return int(self.lib.lcd_refine_log_n_entries(self.h))
+
+    def row_bytes(self):
+        return int(self.lib.lcd_refine_log_row_bytes(self.h))
+
+    def append(self, read_id, cover, read_beg, read_end, reg_beg, reg_end, target, query, pass_=0):
+        from ._lib import LcdRefineEntry
+        t = np.ascontiguousarray(target, np.uint8); q = np.ascontiguousarray(query, np.uint8)
+        assert len(t) == len(q)
+        e = LcdRefineEntry(int(read_id), int(cover), int(read_beg), int(read_end), len(t), int(pass_), int(reg_beg), int(reg_end), _p8(t), _p8(q))
+        check(self.lib.lcd_refine_log_append(self.h, C.byref(e)), self.lib)
+
+    def entries(self):
+        """-> [dict(read_id, cover, read_beg, read_end, reg_beg, reg_end, pass_, target, query)] in log order"""
+        from ._lib import LcdRefineEntry
+        out = []
+        for i in range(len(self)):
+            e = LcdRefineEntry()
+            check(self.lib.lcd_refine_log_entry(self.h, i, C.byref(e)), self.lib)
+            row = lambda p: np.ctypeslib.as_array(p, shape=(max(e.aln_len, 1),))[:e.aln_len].copy() if e.aln_len else np.zeros(0, np.uint8)
+            out.append(dict(read_id=e.read_id, cover=e.cover, read_beg=e.read_beg, read_end=e.read_end, reg_beg=e.reg_beg, reg_end=e.reg_end, pass_=e.pass_,
+                            target=row(e.target), query=row(e.query)))
+        return out
+
+    def apply(self, digars, qlens):
+        """lcd_refine_log_apply on per-read (n, 5) digar rows (DeviceChunk.digars()) -> ({read id: final (n, 5) rows} of the reads the log names, entries rejected)"""
+        n = len(digars)
+        off = np.concatenate([[0], np.cumsum([len(d) for d in digars])]).astype(np.uint64)
+        dg = (LcdDigar * max(int(off[-1]), 1))()
+        k = 0
+        for d in digars:
+            for x in np.asarray(d, np.int64).reshape(-1, 5):
+                dg[k].pos, dg[k].type, dg[k].len, dg[k].qi, dg[k].is_low_qual = int(x[0]), int(x[1]), int(x[2]), int(x[3]), int(x[4]); k += 1
+        ql = np.ascontiguousarray(qlens, np.int32)
+        nt, ids, toff, tdg, rej = C.c_int(0), i32p(), C.POINTER(C.c_uint64)(), C.POINTER(LcdDigar)(), C.c_int64(0)
+        check(self.lib.lcd_refine_log_apply(self.h, n, off.ctypes.data_as(C.POINTER(C.c_uint64)), dg, ql.ctypes.data_as(i32p), C.byref(nt), C.byref(ids), C.byref(toff),
+                                            C.byref(tdg), C.byref(rej)), self.lib)
+        out = {}
+        for t in range(nt.value):
+            out[int(ids[t])] = np.array([[tdg[j].pos, tdg[j].type, tdg[j].len, tdg[j].qi, tdg[j].is_low_qual] for j in range(int(toff[t]), int(toff[t + 1]))], np.int64).reshape(-1, 5)
+        for p_ in (ids, toff, tdg):
+            if p_:
+                _libc.free(C.cast(p_, C.c_void_p))
+        return out, int(rej.value)
+
+
+def chunks_noisy_rounds(chunks, items, opt=None, popt=None, logs=None):
     """lcd_chunks_noisy_rounds: DeviceChunks from "first round done" to the fixed point of collect_var_main's noisy-region loop (src/collect_var.c:2946-2977).
     items[i] = dict(cv = clean_vars_dict of the first round, state = K5 state after the clean-category call, ordered_read_ids, is_skipped, ref (codes),
-    ref_beg, is_ont (optional)) -> list of dict(cv, state, done, n_passes, first_to_final)"""
+    ref_beg, is_ont (optional)) -> list of dict(cv, state, done, n_passes, first_to_final).  logs = one RefineLog (or None) per chunk: lcd_chunks_noisy_rounds_log"""
     from ._lib import LcdRoundsChunk
     lib = load_library()
     opt = opt if opt is not None else default_opt()
@@ -1375,7 +1478,11 @@ def chunks_noisy_rounds(chunks, items, opt=None, popt=None):
         x.chunk, x.vars, x.state = ch.h, C.pointer(v), C.pointer(s)
         x.ordered_read_ids, x.is_skipped, x.ref_seq = ordered.ctypes.data_as(i32p), _p8(skipped), _p8(ref)
         x.ref_beg, x.ref_end, x.is_ont = int(it["ref_beg"]), int(it["ref_beg"]) + len(ref) - 1, int(it.get("is_ont", 0))
-    rc = lib.lcd_chunks_noisy_rounds(n, arr, C.byref(opt), C.byref(popt))
+    if logs is None:
+        rc = lib.lcd_chunks_noisy_rounds(n, arr, C.byref(opt), C.byref(popt))
+    else:
+        assert len(logs) == n
+        rc = lib.lcd_chunks_noisy_rounds_log(n, arr, C.byref(opt), C.byref(popt), (C.c_void_p * max(1, n))(*[g.h if g is not None else None for g in logs]))
     res = []
     try:
         check(rc, lib)
@@ -1614,13 +1721,17 @@ def bgzf_deflate(data, block_payload=0, add_eof=1):
         lib.lcd_deflated_free(h)
 
 
-def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None):
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
     bam_out = dict(path[, pg_line, block_payload]): lcd_call_bam_regions_out, the phased alignment file is written too; the result gets "bam_out" = the counters and
     stage times of lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
-    te_fasta= / rnames=: lcd_call_bam_regions_fields (as chunks_call)"""
-    from ._lib import LcdBamOut, LcdCallChunk, LcdVar1
+    te_fasta= / rnames=: lcd_call_bam_regions_fields (as chunks_call).  refine=True (with bam_out; not with te_fasta / rnames): lcd_call_bam_regions_refine -- the
+    records are written with the alignments the call arrived at; the result gains "refine" = lcd_refine_stats_t's fields"""
+    from ._lib import LcdBamOut, LcdCallChunk, LcdRefineStats, LcdVar1
     vf, fo = _vcf_fields(te_fasta, rnames)
+    if refine and vf is not None:
+        raise ValueError("call_bam_regions: refine= goes with neither te_fasta= nor rnames=")
+    rst = LcdRefineStats() if refine and bam_out is not None else None
     if bam_out is not None or vf is not None:
         lib = load_library()
         cfg = cfg if cfg is not None else call_cfg()
@@ -1637,6 +1748,9 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
         if vf is not None:
             rc = lib.lcd_call_bam_regions_fields(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), C.byref(vf), arr, C.byref(recs),
                                                  C.byref(n_recs), C.byref(text), bop, C.byref(fo))
+        elif rst is not None:
+            rc = lib.lcd_call_bam_regions_refine(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs),
+                                                 C.byref(n_recs), C.byref(text), bop, C.byref(rst))
         else:
             rc = lib.lcd_call_bam_regions_out(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
                                               C.byref(text), bop)
@@ -1650,6 +1764,8 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
             return res
         res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
                                                                                                    "ms_deflate", "ms_download_write")})
+        if rst is not None:
+            res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
         return res
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
@@ -1765,15 +1881,17 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False):
     """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
     phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
     flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
     index (default None: lcd_call_file as it is): True, or a dict with build_missing_bai / build_missing_fai / write_out_bai / out_bai_path / slab_members ->
     lcd_call_file_indexed; the result then has "index" = lcd_index_stats_t's fields (out_bai_skipped != 0: the output's index was not written, out_bai_skip_reason says why).
     te_fasta= (the -T file) / rnames=None|"sv"|"all" (--out-sv-rnames / --out-var-rnames): lcd_call_file_fields / lcd_call_files_fields; the result gains "te_names" and
-    "n_mei_lines" (with a library) and the kept records "te_name" / "alt_read_names" (see _fields_result)"""
-    from ._lib import LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats
+    "n_mei_lines" (with a library) and the kept records "te_name" / "alt_read_names" (see _fields_result).
+    refine=True (the command line's --refine-bam; no effect without bam_out, not with te_fasta / rnames): lcd_call_file_refine / lcd_call_files_refine; the result
+    gains "refine" = lcd_refine_stats_t's fields"""
+    from ._lib import LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats, LcdRefineStats
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
     job = LcdFileJob(); lib.lcd_file_job_default(C.byref(job))
@@ -1810,7 +1928,14 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
         ist = LcdIndexStats()
     vf, fo = _vcf_fields(te_fasta, rnames)
     iop, istp = (C.byref(io) if io is not None else None), (C.byref(ist) if ist is not None else None)
-    if vf is not None and _inputs is not None:
+    if refine and vf is not None:
+        raise ValueError("call_file: refine= goes with neither te_fasta= nor rnames=")
+    rst = LcdRefineStats() if refine else None
+    if rst is not None and _inputs is not None:
+        rc = lib.lcd_call_files_refine(C.byref(inp), C.byref(job), C.byref(cfg), iop, C.byref(st), istp, per_file, C.byref(rst))
+    elif rst is not None:
+        rc = lib.lcd_call_file_refine(C.byref(job), C.byref(cfg), iop, C.byref(st), istp, C.byref(rst))
+    elif vf is not None and _inputs is not None:
         rc = lib.lcd_call_files_fields(C.byref(inp), C.byref(job), C.byref(cfg), iop, C.byref(vf), C.byref(st), istp, per_file, C.byref(fo))
     elif vf is not None:
         rc = lib.lcd_call_file_fields(C.byref(job), C.byref(cfg), iop, C.byref(vf), C.byref(st), istp, C.byref(fo))
@@ -1836,6 +1961,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["bam_out"] = {k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag", "ms_deflate", "ms_download_write")}
         if vf is not None:
             res = _fields_result(lib, res, vf, fo)
+        if rst is not None:
+            res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))

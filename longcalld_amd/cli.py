@@ -5,7 +5,7 @@ import sys
 VERSION_FALLBACK = "longcalld_amd"
 REFUSED = {
     "-s": "somatic / mosaic calling is not supported", "--mosaic": "somatic / mosaic calling is not supported", "--somatic": "somatic / mosaic calling is not supported",
-    "--refine-aln": "--refine-aln is not supported", "-L": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE", "--input-is-list": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE",
+    "--refine-aln": "--refine-aln is not supported: ask for refined alignments in the output BAM with --refine-bam", "-L": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE", "--input-is-list": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE",
     "-X": "-X/--extra-bam is not supported: give further input files with --add-bam FILE", "--extra-bam": "-X/--extra-bam is not supported: give further input files with --add-bam FILE",
     "-S": "SAM output (-S) is not supported: use -b", "--out-sam": "SAM output (-S) is not supported: use -b", "--out-cram": "CRAM output (-C FILE) is not supported: use -b",
     "-T": "-T/--trans-elem is not supported: give the TE sequence file with --te-lib FILE", "--trans-elem": "-T/--trans-elem is not supported: give the TE sequence file with --te-lib FILE",
@@ -13,7 +13,7 @@ REFUSED = {
     "--out-sv-rnames": "--out-sv-rnames is not supported: ask for the supporting read names of SV records with --sv-rnames",
     "--out-som-var-rnames": "--out-som-var-rnames is not supported: somatic / mosaic calling is not supported",
 }
-FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
@@ -31,10 +31,12 @@ Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z 
           --te-lib FILE   TE sequences (FASTA, plain or gzip; the reference's -T): SVs that look like their insertion get MEI and REPNAME=
           --var-rnames | --sv-rnames   the supporting read names of every record | of SV records as the FORMAT field ALTREADS (the reference's --out-var-rnames /
           --out-sv-rnames; --var-rnames wins)
+          --refine-bam   with -b: every kept read is written with the alignment the caller arrived at (CIGAR, POS, NM / MD / cs; the reference's --refine-aln);
+          without -b it has no effect; a rewrite can move POS, so the output may stop being sorted (then no <out.bam>.bai is written, and the reason is printed)
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
 Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
-Not supported (refused with exit status 2): -s, --refine-aln, -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S, -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
+Not supported (refused with exit status 2): -s, --refine-aln (use --refine-bam), -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S, -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
           --out-som-var-rnames
 """
 
@@ -173,6 +175,9 @@ def main(argv=None):
     mode = 2 if "--all-ctg" in o["flags"] else 1 if "--autosome" in o["flags"] else 0
     cmdline = "longcalld_amd call " + " ".join(argv[1:])
     bam_out = dict(path=o["out_bam"], pg_line="@PG\tID:longcalld_amd\tPN:longcalld_amd\tCL:" + cmdline) if "out_bam" in o else None
+    refine = "--refine-bam" in o["flags"]
+    if refine and any(v is not None for v in vcf_fields(o).values()):
+        return refuse("--refine-bam cannot be combined with --te-lib / --var-rnames / --sv-rnames in one run")
     try:
         bams = input_bams(o, bam)
     except OSError as e:
@@ -185,7 +190,7 @@ def main(argv=None):
                              window_chunks=num.get("window_chunks", 0), overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0),
                              min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
-                             index=True if "--make-index" in o["flags"] else None, **vcf_fields(o))
+                             index=True if "--make-index" in o["flags"] else None, **(dict(refine=True) if refine else vcf_fields(o)))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
@@ -195,7 +200,8 @@ def main(argv=None):
         sys.stderr.write("longcalld_amd call: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
     per_file = f" ({' + '.join(str(x) for x in st['n_reads_per_file'])} from the {len(bams)} input files)" if len(bams) > 1 else ""
     sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads{per_file}, {st['n_vcf_lines']} VCF lines, "
-                     + (f"{st['n_mei_lines']} MEI records, " if "n_mei_lines" in st else "") + f"{st['ms_wall'] / 1000:.2f} s\n")
+                     + (f"{st['n_mei_lines']} MEI records, " if "n_mei_lines" in st else "")
+                     + (f"{st['refine']['n_refined']} refined / {st['refine']['n_unrefined']} unrefined records, " if refine and bam_out is not None else "") + f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 
 

@@ -11,34 +11,12 @@
 #include "lcd_types.h"
 #include "lcd_kernels.h"
 #include "wave_copy.h"
+#include "bam_aux_hop.h"
 
 namespace {
 using lcd_wave::ld32u;
-// offset of the first NUL in [p, end), or -1, one lane: aligned words (the stream buffer is padded behind its end), the bytes in front of p masked out
-__device__ __forceinline__ long long lane_find_nul(const uint8_t *p, const uint8_t *end) {
-    if (p >= end) return -1;
-    const uintptr_t a = (uintptr_t)p;
-    const unsigned *q = (const unsigned *)(a & ~(uintptr_t)3);
-    const long long n = end - p;
-    long long at = -(long long)(a & 3);
-    unsigned w = *q | ((1u << (8 * (unsigned)(a & 3))) - 1u);
-    for (;;) {                                                            // ends at the record's end at the latest
-        const unsigned z = (w - 0x01010101u) & ~w & 0x80808080u;
-        if (z) { const long long i = at + ((__ffs((int)z) - 1) >> 3); return i < n ? i : -1; }
-        at += 4;
-        if (at >= n) return -1;
-        w = *++q;
-    }
-}
-__device__ __forceinline__ long long aux2i(const uint8_t ty, const unsigned w) {
-    if (ty == 'c') return (long long)(signed char)(w & 0xff);
-    if (ty == 'C') return (long long)(w & 0xff);
-    if (ty == 's') return (long long)(short)(w & 0xffff);
-    if (ty == 'S') return (long long)(w & 0xffff);
-    if (ty == 'i') return (long long)(int)w;
-    if (ty == 'I') return (long long)w;
-    return 0;
-}
+using lcd_aux::lane_find_nul;   // (the aux hop is shared with bam_refine_kernel.hip: bam_aux_hop.h)
+using lcd_aux::aux2i;
 } // namespace
 
 __global__ void __launch_bounds__(64) lcd_bam_tag_measure_kernel(const BamTagJob *jobs, BamTagOut *outs, const int n_jobs) {

@@ -132,6 +132,20 @@ int lcd_merged_record_plan(int n_rec, const int *rec_file, const int64_t *rec_po
 
 // ---- HP / PS rewrite of a chunk's records ----
 namespace {
+// the records with skip[i] == 0 (NULL: all) in the order `order` names them (NULL: table order)
+int pick_selected(const std::string &W, const lcd_chunk_t *c, const uint8_t *skip, const int *order, std::vector<int> &pick) {
+    const int n_rec = (int)c->rec_beg.size();
+    int m = 0;
+    for (int i = 0; i < n_rec; ++i) if (!skip || !skip[i]) ++m;
+    pick.assign(m, 0); std::vector<uint8_t> seen(n_rec + 1, 0);
+    for (int k = 0, i = 0; k < m; ++k) {
+        if (order) i = order[k]; else { while (skip && skip[i]) ++i; }
+        if (i < 0 || i >= n_rec || (skip && skip[i]) || seen[i]) return set_err(-4, W + ": `order` must name every record that is not skipped exactly once");
+        seen[i] = 1; pick[k] = i;
+        if (!order) ++i;
+    }
+    return 0;
+}
 // the records `pick` names (indices of the chunk's record table), rewritten in that order
 lcd_tagged_t *tag_records_core(const std::string &W, const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, const std::vector<int> &pick) {
     if (use_device(c->device)) return nullptr;
@@ -194,17 +208,129 @@ lcd_tagged_t *lcd_chunk_tag_records_sel(const lcd_chunk_t *c, const int *haps, c
     const std::string W = "lcd_chunk_tag_records_sel";
     if (!c || !c->from_bam) { set_err(-4, W + ": the chunk was not made from a BAM"); return nullptr; }
     if (c->n_reads > 0 && (!haps || !phase_sets)) { set_err(-4, W + ": NULL haps / phase_sets"); return nullptr; }
-    const int n_rec = (int)c->rec_beg.size();
-    int m = 0;
-    for (int i = 0; i < n_rec; ++i) if (!skip || !skip[i]) ++m;
-    std::vector<int> pick(m); std::vector<uint8_t> seen(n_rec + 1, 0);
-    for (int k = 0, i = 0; k < m; ++k) {
-        if (order) i = order[k]; else { while (skip && skip[i]) ++i; }
-        if (i < 0 || i >= n_rec || (skip && skip[i]) || seen[i]) { set_err(-4, W + ": `order` must name every record that is not skipped exactly once"); return nullptr; }
-        seen[i] = 1; pick[k] = i;
-        if (!order) ++i;
-    }
+    std::vector<int> pick;
+    if (pick_selected(W, c, skip, order, pick)) return nullptr;
     return tag_records_core(W, c, haps, phase_sets, pick);
+}
+// ---- refined alignments: the records rewritten from their reads' final digars (bam_refine_kernel.hip) ----
+lcd_tagged_t *lcd_chunk_refine_records(const lcd_chunk_t *c, int n_touched, const int *touched_reads, const uint64_t *touched_off, const lcd_digar_t *touched_digars,
+                                       const uint8_t *ref_seq, int64_t ref_beg, int64_t ref_end, const int *haps, const int64_t *phase_sets, const uint8_t *skip,
+                                       const int *order, lcd_refine_stats_t *stats) {
+    const std::string W = "lcd_chunk_refine_records";
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!c || !c->from_bam) { set_err(-4, W + ": the chunk was not made from a BAM"); return nullptr; }
+    if (c->pending) { set_err(-4, W + ": the chunk was opened and not resolved (lcd_chunk_resolve)"); return nullptr; }
+    if (c->n_reads > 0 && (!haps || !phase_sets)) { set_err(-4, W + ": NULL haps / phase_sets"); return nullptr; }
+    if (n_touched < 0 || (n_touched > 0 && (!touched_reads || !touched_off || (touched_off[n_touched] > touched_off[0] && !touched_digars)))) {
+        set_err(-4, W + ": n_touched < 0 or NULL digar arrays"); return nullptr;
+    }
+    static_assert(sizeof(lcd_digar_t) == sizeof(DigarRec), "lcd_digar_t is uploaded as DigarRec");
+    std::vector<int> touched_of(c->n_reads, -1);
+    for (int k = 0; k < n_touched; ++k) {
+        const int r = touched_reads[k];
+        if (r < 0 || r >= c->n_reads || touched_of[r] >= 0 || touched_off[k + 1] < touched_off[k] || touched_off[k + 1] - touched_off[k] > (uint64_t)INT32_MAX) {
+            set_err(-4, W + ": touched_reads must name reads of the chunk once each, touched_off must not fall"); return nullptr;
+        }
+        touched_of[r] = k;
+        uint64_t sum = 0;                                        // (the kernels' running sums are 32-bit: a list stays below 2^28 bases in all, as every CIGAR word must)
+        for (uint64_t d = touched_off[k]; d < touched_off[k + 1]; ++d) {
+            const lcd_digar_t &g = touched_digars[d];
+            // (qi is taken as it is: the reference's rewrite leaves '=' digars with qi -1 behind a right-cover walk; the kernels read a base outside the read as n)
+            if (g.type < 0 || g.type > 8 || g.len < 0 || g.len >= (1 << 28) || (sum += (uint64_t)g.len) >= (1u << 28)) {
+                set_err(-4, W + ": a digar with an unknown type, or lengths that are negative or reach 2^28 in all"); return nullptr;
+            }
+        }
+    }
+    const bool have_ref = ref_seq && ref_end >= ref_beg;
+    std::vector<int> pick;
+    if (pick_selected(W, c, skip, order, pick)) return nullptr;
+    if (use_device(c->device)) return nullptr;
+    std::unique_ptr<lcd_tagged_s> h(new lcd_tagged_s());
+    h->device = c->device;
+    const int n = (int)pick.size();
+    h->n_records = n;
+    if (n == 0) return h.release();
+    const uint64_t base = c->stream ? lcd_inflated_dev_ptr(c->stream) : 0, usize = c->stream ? lcd_inflated_size(c->stream) : 0;
+    const uint64_t t0 = n_touched ? touched_off[0] : 0, n_up = n_touched ? touched_off[n_touched] - t0 : 0;
+    DevBuf d_jobs, d_outs, d_up, d_words, d_ref;
+    // the word arena: one word per digar of every record written, each record's share at a 16-byte boundary and 16 bytes behind the last one
+    std::vector<BamRefineJob> jobs(n);
+    uint64_t arena = 0;
+    for (int k = 0; k < n; ++k) {
+        const int i = pick[k], r = c->rec_read[i];
+        if (c->rec_stop[i] > usize || c->rec_beg[i] + 36 > c->rec_stop[i] || r >= c->n_reads) { set_err(-4, W + ": record outside the stream"); return nullptr; }
+        BamRefineJob &j = jobs[k];
+        j.src = base + c->rec_beg[i]; j.len = (uint32_t)(c->rec_stop[i] - c->rec_beg[i]); j.kept = r >= 0; j.hap = r >= 0 ? haps[r] : 0; j.ps = r >= 0 ? phase_sets[r] : 0;
+        j.pad = 0; j.skipped = r >= 0 && c->status[r] != 0; j.n_digar = 0; j.dig = 0; j.words = arena;
+        if (r >= 0 && touched_of[r] >= 0) { const int t = touched_of[r]; j.n_digar = (int)(touched_off[t + 1] - touched_off[t]); j.dig = (touched_off[t] - t0) * sizeof(DigarRec); j.pad = 1; }
+        else if (r >= 0) {
+            j.n_digar = j.skipped ? 0 : std::max(0, c->n_digar[r]); j.dig = c->d_dig.addr() + c->slot[r] * sizeof(DigarRec);
+            if (j.n_digar && (c->slot[r] + (uint64_t)j.n_digar) * sizeof(DigarRec) > c->d_dig.cap) { set_err(-4, W + ": digar slots outside the chunk's buffer"); return nullptr; }
+        }
+        arena += lcd_align_up((uint64_t)std::max(0, j.n_digar) * 4, 16);
+    }
+    if (d_jobs.ensure((size_t)n * sizeof(BamRefineJob), 31) || d_outs.ensure((size_t)n * sizeof(BamRefineOut), 31) || d_words.ensure((size_t)arena + 64, 31) ||
+        d_up.ensure((size_t)n_up * sizeof(DigarRec) + 64, 31) || d_ref.ensure((have_ref ? (size_t)(ref_end - ref_beg + 1) : 0) + 64, 31)) return nullptr;
+    for (BamRefineJob &j : jobs) { j.words += d_words.addr(); if (j.pad) { j.dig += d_up.addr(); j.pad = 0; } }
+    std::vector<uint8_t> codes;                                        // the window as codes 0-4, whatever it came as
+    if (have_ref) {
+        codes.resize((size_t)(ref_end - ref_beg + 1));
+        for (size_t k = 0; k < codes.size(); ++k) {
+            const uint8_t b = ref_seq[k];
+            codes[k] = b <= 4 ? b : (b == 'A' || b == 'a') ? 0 : (b == 'C' || b == 'c') ? 1 : (b == 'G' || b == 'g') ? 2 : (b == 'T' || b == 't') ? 3 : 4;
+        }
+    }
+    StreamGuard st; if (st.create()) return nullptr;
+    auto hipfail = [&](const char *what) -> lcd_tagged_t * { (void)hipGetLastError(); set_err(-10, W + ": HIP call failed: " + what); return nullptr; };
+#define RCHK(x) do { if ((x) != hipSuccess) return hipfail(#x); } while (0)
+    const double w0 = now_ms();
+    RCHK(hipMemcpyAsync(d_jobs.p, jobs.data(), (size_t)n * sizeof(BamRefineJob), hipMemcpyHostToDevice, st));
+    if (n_up) { RCHK(hipMemcpyAsync(d_up.p, touched_digars + t0, (size_t)n_up * sizeof(DigarRec), hipMemcpyHostToDevice, st)); g_copy_bytes[1] += n_up * sizeof(DigarRec); }
+    if (have_ref) RCHK(hipMemcpyAsync(d_ref.p, codes.data(), codes.size(), hipMemcpyHostToDevice, st));
+    const long long rb = have_ref ? ref_beg : 1, re = have_ref ? ref_end : 0;    // (no window: every position reads as N)
+    lcd_launch_bam_refine_measure((const BamRefineJob *)d_jobs.p, (BamRefineOut *)d_outs.p, (const uint8_t *)d_ref.p, rb, re, n, st);
+    RCHK(hipGetLastError());
+    std::vector<BamRefineOut> outs(n);
+    RCHK(hipMemcpyAsync(outs.data(), d_outs.p, (size_t)n * sizeof(BamRefineOut), hipMemcpyDeviceToHost, st));
+    RCHK(hipStreamSynchronize(st));
+    const double w1 = now_ms();
+    uint64_t tot = 0;
+    lcd_refine_stats_t s; memset(&s, 0, sizeof(s));
+    for (int k = 0; k < n; ++k) {
+        BamRefineOut &o = outs[k]; const BamRefineJob &j = jobs[k];
+        // what the emit pass writes is what was measured: the deleted fields lie inside the record, ascending and apart, and the length adds up
+        uint64_t gone = 0, prev = 36; bool ok = o.state <= LCD_REFINE_CG && o.n_ops <= 65535 && (o.state == LCD_REFINE_CHANGED || !(o.flags & 39u));
+        for (int d = 0; d < 5; ++d) { ok = ok && o.del_beg[d] >= prev && o.del_end[d] >= o.del_beg[d] && o.del_end[d] <= j.len; prev = o.del_end[d]; gone += o.del_end[d] - o.del_beg[d]; }
+        const uint64_t app = ((o.flags & 1u) ? 7 : 0) + ((o.flags & 2u) ? 4ull + o.md_len : 0) + ((o.flags & 4u) ? 4ull + o.cs_len : 0) + ((o.flags & 8u) ? 7 : 0) + ((o.flags & 16u) ? 7 : 0);
+        const uint64_t nc_old = ((uint64_t)j.len + 4ull * o.n_ops + app - gone - (uint64_t)o.new_len);     // 4 * the record's own n_cigar
+        ok = ok && (uint64_t)o.new_len + gone >= 36 + app && nc_old % 4 == 0 && nc_old <= 4ull * 65535 && ((o.flags & 32u) || nc_old == 4ull * o.n_ops) &&
+             (!(o.flags & 32u) || (int)o.n_ops <= j.n_digar);
+        if (!ok) { set_err(-24, W + ": inconsistent measure pass"); return nullptr; }
+        o.dst = tot; tot += o.new_len;
+        ++s.n_records; s.n_kept += j.kept; s.n_pos_moved += o.pos_moved != 0;
+        switch (o.state) {
+        case LCD_REFINE_CHANGED: ++s.n_refined; s.n_nm_replaced += o.flags & 1u; s.n_md_replaced += (o.flags >> 1) & 1u; s.n_cs_replaced += (o.flags >> 2) & 1u; break;
+        case LCD_REFINE_IDENTICAL: ++s.n_identical; break;
+        case LCD_REFINE_NO_DIGARS: ++s.n_no_digars; break;
+        case LCD_REFINE_QLEN: ++s.n_qlen_mismatch; break;
+        case LCD_REFINE_POS: ++s.n_bad_pos; break;
+        case LCD_REFINE_OPS: ++s.n_too_many_ops; break;
+        case LCD_REFINE_CG: ++s.n_cg_cigar; break;
+        default: break;
+        }
+    }
+    s.n_unrefined = s.n_no_digars + s.n_qlen_mismatch + s.n_bad_pos + s.n_too_many_ops + s.n_cg_cigar;
+    s.n_touched = n_touched; s.bytes_digars_up = (int64_t)(n_up * sizeof(DigarRec)); s.bytes_ref_up = (int64_t)codes.size();
+    h->size = (size_t)tot;
+    if (h->out.ensure((size_t)tot + 64, 31)) return nullptr;
+    RCHK(hipMemcpyAsync(d_outs.p, outs.data(), (size_t)n * sizeof(BamRefineOut), hipMemcpyHostToDevice, st));
+    lcd_launch_bam_refine_emit((const BamRefineJob *)d_jobs.p, (const BamRefineOut *)d_outs.p, (const uint8_t *)d_ref.p, rb, re, (uint8_t *)h->out.p, n, st);
+    RCHK(hipGetLastError());
+    RCHK(hipStreamSynchronize(st));
+#undef RCHK
+    s.ms_measure = w1 - w0; s.ms_emit = now_ms() - w1;
+    if (stats) *stats = s;
+    return h.release();
 }
 uint64_t lcd_tagged_dev_ptr(const lcd_tagged_t *h) { return h ? h->out.addr() : 0; }
 size_t lcd_tagged_size(const lcd_tagged_t *h) { return h ? h->size : 0; }

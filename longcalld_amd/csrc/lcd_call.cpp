@@ -23,6 +23,10 @@ void lcd_call_free(int n, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_r
 int lcd_chunks_call(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body) {
     return lcd_chunks_call_fields(n, chunks, cfg, chrom, nullptr, records, n_records, vcf_body, nullptr);
 }
+int lcd_chunks_call_refine(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body) {
+    for (int c = 0; chunks && c < n; ++c) if (chunks[c].first.chunk) if (int rc = lcd_chunk_set_refine(const_cast<lcd_chunk_t *>(chunks[c].first.chunk), 1)) return rc;
+    return lcd_chunks_call(n, chunks, cfg, chrom, records, n_records, vcf_body);
+}
 int lcd_chunks_call_fields(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const lcd_vcf_fields_t *fields, lcd_var1_t **records, int *n_records,
                            char **vcf_body, lcd_vcf_fields_out_t *fields_out) {
     if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
@@ -97,7 +101,9 @@ int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cf
             r[c].chunk = x.chunk; r[c].vars = x.vars; r[c].state = x.state; r[c].ordered_read_ids = x.order; r[c].is_skipped = x.is_skipped;
             r[c].ref_seq = x.ref_seq; r[c].ref_beg = x.ref_beg; r[c].ref_end = x.ref_end; r[c].is_ont = x.is_ont;
         }
-        rc = lcd_chunks_noisy_rounds(n, r.data(), &cfg->opt, &cfg->pass);
+        std::vector<lcd_refine_log_t *> logs(n + 1, nullptr);      // the chunks a driver asked refined alignments for (lcd_chunk_set_refine): their rounds write the log
+        for (int c = 0; c < n; ++c) logs[c] = chunks[c].first.chunk ? chunks[c].first.chunk->refine_log : nullptr;
+        rc = lcd_chunks_noisy_rounds_log(n, r.data(), &cfg->opt, &cfg->pass, logs.data());
         if (rc) return fail(rc);
         for (int c = 0; c < n; ++c) { chunks[c].n_passes = r[c].n_passes; free(r[c].done); free(r[c].first_to_final); }
     }
@@ -212,6 +218,7 @@ struct lcd_bam_writer_s {
     // lcd_bam_writer_open_indexed: the builder of the output's .bai (NULL: none, or given up), where the index goes, the file offset of the next member
     lcd_bai_builder_t *bai = nullptr; std::string index_path; lcd_index_stats_t *ist = nullptr; uint64_t file_off = 0;
     int sort_output = 0;     // lcd_bam_writer_set_sort
+    lcd_refine_stats_t *rstats = nullptr;     // lcd_bam_writer_set_refine_stats: what the refined chunks' records became, summed over the appends
 };
 namespace {
 // download + fwrite of one compressed image, then free
@@ -305,7 +312,26 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
         const int n_out = lcd_merged_record_plan(n_rec, k->rec_file.data(), k->rec_pos0.data(), k->rec_endpos.data(), has_prev, pb, pe, w->sort_output, skip.data(), order.data());
         if (n_out < 0) return n_out;
         const double t0 = now_ms();
-        lcd_tagged_t *t = lcd_chunk_tag_records_sel(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, skip.data(), order.data());
+        lcd_tagged_t *t = nullptr;
+        if (k->refine_log) {     // refined alignments: the log of the chunk's rounds on a host copy of its digars, then the records from the final lists
+            int n_touched = 0; int *t_reads = nullptr; uint64_t *t_off = nullptr, *d_off = nullptr; lcd_digar_t *t_dg = nullptr, *dg = nullptr; int64_t n_rej = 0;
+            int rc = 0;
+            if (lcd_refine_log_n_entries(k->refine_log) > 0) {
+                rc = lcd_chunk_digars(k, &d_off, &dg);         // (returns the number of reads)
+                if (rc >= 0) rc = lcd_refine_log_apply(k->refine_log, k->n_reads, d_off, dg, k->qlen.data(), &n_touched, &t_reads, &t_off, &t_dg, &n_rej);
+            }
+            lcd_refine_stats_t rs;
+            if (!rc) t = lcd_chunk_refine_records(k, n_touched, t_reads, t_off, t_dg, x.ref_seq, x.ref_beg, x.ref_end, x.state ? x.state->haps : nullptr,
+                                                  x.state ? x.state->phase_sets : nullptr, skip.data(), order.data(), &rs);
+            free(t_reads); free(t_off); free(t_dg); free(d_off); free(dg);
+            if (!t) return rc ? rc : -30;
+            if (lcd_refine_stats_t *a = w->rstats) {
+                int64_t *dst = &a->n_records; const int64_t *src = &rs.n_records;
+                for (int q = 0; q < 17; ++q) dst[q] += src[q];           // the seventeen counters in front of the two times
+                a->ms_measure += rs.ms_measure; a->ms_emit += rs.ms_emit;
+                a->n_log_entries += lcd_refine_log_n_entries(k->refine_log); a->bytes_log_down += lcd_refine_log_row_bytes(k->refine_log); a->n_log_rejected += n_rej;
+            }
+        } else t = lcd_chunk_tag_records_sel(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, skip.data(), order.data());
         if (!t) return -30;
         out->ms_tag += now_ms() - t0;
         for (int i = 0; i < n_rec; ++i) if (!skip[i]) ++(k->rec_read[i] >= 0 ? out->n_records_out : out->n_filtered_out);
@@ -318,6 +344,12 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
         lcd_tagged_free(t);
         if (rc) return rc;
     }
+    return 0;
+}
+int lcd_bam_writer_set_refine_stats(lcd_bam_writer_t *w, lcd_refine_stats_t *stats) {
+    if (!w) return set_err(-4, "lcd_bam_writer_set_refine_stats: NULL writer");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    w->rstats = stats;
     return 0;
 }
 int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output) {
@@ -371,14 +403,17 @@ lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_o
     remove(w->index_path.c_str());     // (an index of an earlier file at this path would not describe the one being written)
     return w;
 }
-int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) {
+int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) { return lcd_write_phased_bam_refine(in_bam_path, n, chunks, out, nullptr); }
+int lcd_write_phased_bam_refine(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats) {
     const std::string W = "lcd_write_phased_bam";
+    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
     if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
     out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
     if (out->block_payload < 0 || out->block_payload > 0xff00) return set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00");
     if (int rc = writer_check_chunks(W, n, chunks)) return rc;     // (before the output file is touched)
     lcd_bam_writer_t *w = lcd_bam_writer_open(in_bam_path, out);
     if (!w) return -30;
+    w->rstats = refine_stats;
     if (int rc = lcd_bam_writer_append(w, n, chunks, nullptr, nullptr)) { lcd_bam_writer_abort(w); return rc; }
     return lcd_bam_writer_close(w);
 }
@@ -393,9 +428,28 @@ int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const c
     return lcd_call_bam_regions_fields(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, nullptr, chunks, records, n_records, vcf_body, bam_out, nullptr);
 }
 
+namespace {
+int call_bam_regions_core(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                          int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                          lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out, bool refine, lcd_refine_stats_t *refine_stats);
+}
 int lcd_call_bam_regions_fields(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
                                 int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
                                 lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out) {
+    return call_bam_regions_core(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, fields, chunks, records, n_records, vcf_body, bam_out, fields_out, false, nullptr);
+}
+int lcd_call_bam_regions_refine(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                                int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out,
+                                lcd_refine_stats_t *refine_stats) {
+    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
+    // (without -b the option has no effect, as in the reference: no log is written)
+    return call_bam_regions_core(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, nullptr, chunks, records, n_records, vcf_body, bam_out, nullptr, bam_out != nullptr,
+                                 refine_stats);
+}
+namespace {
+int call_bam_regions_core(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                          int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                          lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out, bool refine, lcd_refine_stats_t *refine_stats) {
     const std::string W = "lcd_call_bam_regions";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
@@ -439,17 +493,19 @@ int lcd_call_bam_regions_fields(const char *bam_path, const char *bai_path, cons
             handles[c] = lcd_chunk_create_from_bam_src(&dopt, bam_path, bai_path, chrom, reg_beg[c], reg_end[c], min_mapq, 1, &src, &metas[c]);
             if (!handles[c]) return fail(-30);
         }
+        if (refine && lcd_chunk_set_refine(handles[c], 1)) return fail(-11);
         lcd_first_chunk_t &x = chunks[c].first;
         x.chunk = handles[c]; x.ref_seq = refs[c]; x.ref_beg = b0 + 1; x.ref_end = b0 + got; x.reg_beg = reg_beg[c]; x.reg_end = reg_end[c]; x.is_ont = is_ont;
         x.ordered_read_ids = nullptr; x.is_rev = nullptr; x.meta = &metas[c];
     }
     int rc = chunks_call_core(n, chunks, cfg, chrom, nullptr, &fr, records, n_records, vcf_body);
     if (rc == 0) fr.give(fields_out);
-    if (rc == 0 && bam_out) rc = lcd_write_phased_bam(bam_path, n, chunks, bam_out);   // (a failure here leaves the records and the text valid)
+    if (rc == 0 && bam_out) rc = lcd_write_phased_bam_refine(bam_path, n, chunks, bam_out, refine_stats);   // (a failure here leaves the records and the text valid)
     const std::string m = g_err;
     drop_inputs();
     g_err = m;
     return rc;
 }
+} // namespace
 
 } // extern "C"

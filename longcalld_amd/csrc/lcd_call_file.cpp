@@ -299,6 +299,7 @@ struct Run {
     lcd_stitch_carry_t carry;
     lcd_vcf_writer_t *vcf = nullptr; lcd_bam_writer_t *bam = nullptr;
     std::vector<lcd_var1_t> kept;          // keep_records
+    bool refine = false;                   // refined alignments in the alignment output: every chunk's rounds write their log
     FieldsRun *fields = nullptr;           // the TE library and the names mode of the call (read-only here; its counters belong to the call stage)
     // the first error of any stage
     std::mutex err_mu; int err_code = 0; std::string err_msg; std::atomic<bool> failed{false};
@@ -331,6 +332,7 @@ struct Run {
                 if (got <= 0) { bad(got < 0 ? (int)got : -30, std::string("lcd_call_file: no reference sequence for ") + chrom + ":" + std::to_string(rb) + "-" + std::to_string(re) + " (" + (got < 0 ? lcd_io_last_error() : "empty window") + ")"); continue; }
                 lcd_chunk_src_t src; src.ref_seq = (const char *)w.refs[c]; src.ref_beg = b0 + 1; src.ref_end = b0 + got; src.is_ont = is_ont;
                 if (int r2 = lcd_chunk_resolve(w.handles[c], &src)) { bad(r2, g_err); continue; }
+                if (refine) if (int r3 = lcd_chunk_set_refine(w.handles[c], 1)) { bad(r3, g_err); continue; }
                 lcd_first_chunk_t &x = w.chunks[c].first;
                 x.chunk = w.handles[c]; x.ref_seq = w.refs[c]; x.ref_beg = b0 + 1; x.ref_end = b0 + got; x.reg_beg = rb; x.reg_end = re; x.is_ont = is_ont;
                 x.ordered_read_ids = nullptr; x.is_rev = nullptr; x.meta = &w.metas[c];
@@ -395,7 +397,9 @@ struct Run {
 namespace {
 // the whole-file run over the n input files of one sample; in == NULL: the one file of the job (lcd_call_file / lcd_call_file_indexed)
 int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
-                    lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out) {
+                    lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out, bool refine = false,
+                    lcd_refine_stats_t *refine_stats = nullptr) {
+    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
     lcd_index_stats_t ist_local;
@@ -417,6 +421,7 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
     FieldsRun fr; fr.collect_rnames = fields_out != nullptr && job->keep_records;
     if (int rc = fr.open(fields, W)) return rc;     // (an unreadable TE file: before an index is built or an output file is created)
     Run R; R.job = job; R.cfg = cfg; R.st = stats; R.fields = &fr;
+    R.refine = refine && job->bam_out;     // (without an alignment output the option has no effect, as in the reference)
     memset(&R.plan, 0, sizeof(R.plan)); memset(&R.carry, 0, sizeof(R.carry));
     const int n_in = in ? in->n : 1;
     for (int f = 0; f < n_in; ++f) {
@@ -505,6 +510,7 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
             R.bam = idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(bam0, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(bam0, job->bam_out);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
             lcd_bam_writer_set_sort(R.bam, in ? in->sort_output : 0);
+            if (R.refine) lcd_bam_writer_set_refine_stats(R.bam, refine_stats);
         }
     }
     const int n_windows = (R.plan.n + window - 1) / window;
@@ -587,4 +593,14 @@ extern "C" int lcd_call_files_fields(const lcd_inputs_t *in, const lcd_file_job_
                                      lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out) {
     if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); if (fields_out) memset(fields_out, 0, sizeof(*fields_out)); return set_err(-4, "lcd_call_files: NULL argument"); }
     return call_files_core("lcd_call_files", in, job, cfg, idx, fields, stats, idx_stats, n_reads_per_file, fields_out);
+}
+
+extern "C" int lcd_call_file_refine(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats,
+                                    lcd_refine_stats_t *refine_stats) {
+    return call_files_core(idx ? "lcd_call_file_indexed" : "lcd_call_file", nullptr, job, cfg, idx, nullptr, stats, idx_stats, nullptr, nullptr, true, refine_stats);
+}
+extern "C" int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
+                                     lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_refine_stats_t *refine_stats) {
+    if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats)); return set_err(-4, "lcd_call_files: NULL argument"); }
+    return call_files_core("lcd_call_files", in, job, cfg, idx, nullptr, stats, idx_stats, n_reads_per_file, nullptr, true, refine_stats);
 }

@@ -556,6 +556,13 @@ int lcd_chunk_digars(const lcd_chunk_t *c, uint64_t **digar_off, lcd_digar_t **d
 }
 void lcd_chunk_destroy(lcd_chunk_t *c) { delete c; }
 int lcd_chunk_n_reads(const lcd_chunk_t *c) { return c ? c->n_reads : 0; }
+int lcd_chunk_set_refine(lcd_chunk_t *c, int on) {
+    if (!c) return set_err(-4, "lcd_chunk_set_refine: NULL chunk");
+    lcd_refine_log_free(c->refine_log); c->refine_log = nullptr;
+    if (on && !(c->refine_log = lcd_refine_log_create())) return set_err(-11, "lcd_chunk_set_refine: out of memory");
+    return 0;
+}
+lcd_refine_log_t *lcd_chunk_refine_log(const lcd_chunk_t *c) { return c ? c->refine_log : nullptr; }
 // what collect_digar_from_eqx_cigar leaves on the host side of the reference: per read 0 / -1 (skipped as too noisy) / -2 ('M' operation), digar->beg / end, the number
 // of candidate variants; the reads' noisy windows in cr_index order (CSR; pointers into the chunk, valid until it is destroyed) and which of them enter chunk_noisy_regs
 int lcd_chunk_read_info(const lcd_chunk_t *c, int *status, int64_t *beg, int64_t *end, int *n_cand_vars, int *n_digars) {

@@ -786,10 +786,37 @@ struct RegionVarsOwned {           // lcd_batch_region_vars' outputs, freed with
     lcd_noisy_var_t *vars = nullptr; int n = 0, rows = 0; int *ids = nullptr, *ps = nullptr, *pe = nullptr, *pa = nullptr;
     void release() { for (int i = 0; i < n; ++i) free(vars[i].alt_seq); free(vars); free(ids); free(ps); free(pe); free(pa); vars = nullptr; ids = ps = pe = pa = nullptr; n = rows = 0; }
 };
+// one entry per (cluster, read) of a region that has just resolved, in update_digars_from_aln_str's order: the rows of lcd_batch_region_vars' row_read_ids
+int log_region(lcd_refine_log_t *log, lcd_batch_t *b, int region, const lcd_pass_plan_t &plan, int i, int pass, const RegionVarsOwned &x) {
+    const int rows = x.rows;
+    std::vector<int> len(rows + 1); std::vector<const uint8_t *> t(rows + 1), q(rows + 1);
+    const int n = lcd_batch_region_ref_read_rows(b, region, rows, len.data(), t.data(), q.data());
+    if (n < 0) return n;
+    if (n != rows) return set_err(-23, "lcd_chunks_noisy_rounds_log: the region's rows and its ref<->read rows differ in number");
+    const uint64_t k0 = plan.read_off[i], k1 = plan.read_off[i + 1];
+    for (int r = 0; r < rows; ++r) {
+        uint64_t k = k0;
+        while (k < k1 && plan.read_ids[k] != x.ids[r]) ++k;
+        if (k == k1) return set_err(-23, "lcd_chunks_noisy_rounds_log: a cluster read is not in the region's plan");
+        const lcd_refine_entry_t e = {x.ids[r], plan.cover[k], plan.read_beg[k], plan.read_end[k], len[r], pass, plan.beg[i], plan.end[i], t[r], q[r]};
+        if (int rc = lcd_refine_log_append(log, &e)) return rc;
+    }
+    return 0;
+}
+int rounds_core(const std::string &W, int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt, lcd_refine_log_t *const *logs);
 }
 extern "C" {
 int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt) {
-    const std::string W = "lcd_chunks_noisy_rounds";
+    return rounds_core("lcd_chunks_noisy_rounds", n_chunks, chunks, opt, pass_opt, nullptr);
+}
+int lcd_chunks_noisy_rounds_log(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt, lcd_refine_log_t *const *logs) {
+    bool any = false;
+    for (int c = 0; logs && c < n_chunks; ++c) any |= logs[c] != nullptr;
+    return rounds_core(any ? "lcd_chunks_noisy_rounds_log" : "lcd_chunks_noisy_rounds", n_chunks, chunks, opt, pass_opt, any ? logs : nullptr);
+}
+}
+namespace {
+int rounds_core(const std::string &W, int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_opt_t *opt, const lcd_pass_opt_t *pass_opt, lcd_refine_log_t *const *logs) {
     if (n_chunks <= 0) return n_chunks < 0 ? set_err(-4, W + ": n_chunks < 0") : 0;
     if (!chunks || !opt || !pass_opt) return set_err(-4, W + ": NULL argument");
     if (opt->collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode (collect_ref_read_aln_str) is not supported: the regions of a pass are order-dependent there");
@@ -805,6 +832,7 @@ int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_
         if (x.chunk->device != chunks[0].chunk->device) return set_err(-4, W + ": chunks on different devices");
     }
     lcd_opt_t bopt = *opt; bopt.collect_noisy_vars = 2;
+    if (logs) bopt.collect_ref_read_aln_str = 1;            // the sink's rows: the only strings that come down
     std::vector<RoundsChunk> rc(n_chunks);
     std::vector<lcd_batch_t *> batches;            // of the current pass
     std::vector<lcd_pass_plan_t> plans;
@@ -874,6 +902,10 @@ int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_
                 x.n = n > 0 ? n : 0;
                 got[a].push_back(x);
                 if (n < 0) { const std::string m = g_err; free_got(); g_err = m; return fail(n); }
+                if (logs && logs[c]) {
+                    const int lrc = log_region(logs[c], batches[a], ridx[a][i], plans[a], i, r.n_passes, got[a].back());
+                    if (lrc) { const std::string m = g_err; free_got(); g_err = m; return fail(lrc); }
+                }
                 r.done[i] = 1; new_done[a] = 1;
                 if (n > 0) new_var[a] = 1;
             }
@@ -926,5 +958,4 @@ int lcd_chunks_noisy_rounds(int n_chunks, lcd_rounds_chunk_t *chunks, const lcd_
     }
     return 0;
 }
-
-} // extern "C"
+} // namespace

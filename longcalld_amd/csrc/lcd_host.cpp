@@ -2495,6 +2495,31 @@ int lcd_batch_region_vars(lcd_batch_t *b, int region, int64_t noisy_reg_beg, con
     return n;
 }
 
+int lcd_batch_region_ref_read_rows(lcd_batch_t *b, int region, int n_rows, int *aln_len, const uint8_t **target, const uint8_t **query) {
+    const std::string W = "lcd_batch_region_ref_read_rows";
+    if (!b || !b->downloaded) return set_err(-3, W + " before lcd_batch_download");
+    if (!b->opt.collect_ref_read_aln_str || !b->opt.collect_noisy_vars) return set_err(-5, W + " needs opt.collect_ref_read_aln_str and opt.collect_noisy_vars");
+    if (region < 0 || region >= (int)b->regs.size()) return set_err(-4, "bad region index");
+    const RegionRec &R = b->regs[region];
+    const int vi = b->vreg_of[region];
+    if (R.n_cons <= 0 || vi < 0) return 0;
+    const VarRegionRec &V = b->vregs[vi];
+    const int rows = V.rows[0] + (V.n_cons == 2 ? V.rows[1] : 0);
+    if (n_rows < rows || !aln_len || !target || !query) return set_err(-4, W + ": fewer than the region's rows, or NULL arrays");
+    if (b->rr_len.size() != b->str_jobs.size() || b->reg_str0.size() != b->regs.size() + 1) return set_err(-23, W + ": the run left no ref<->read rows");
+    for (int r = 0; r < rows; ++r) aln_len[r] = -1;
+    for (size_t j = b->reg_str0[region]; j < b->reg_str0[region + 1]; ++j) {
+        if (b->str_region[j] != region) continue;
+        const int c = b->str_clu[j], k = b->str_k[j];
+        if (c < 0 || c >= V.n_cons || c > 1 || k < 0 || k >= V.rows[c]) continue;
+        const int r = c == 0 ? k : V.rows[0] + k;
+        if (b->rr_off[j] + 2ull * (uint64_t)b->rr_stride[j] > b->h_rr.size() || b->rr_len[j] < 0 || b->rr_len[j] > b->rr_stride[j]) return set_err(-23, W + ": rows outside the download");
+        aln_len[r] = b->rr_len[j]; target[r] = b->h_rr.data() + b->rr_off[j]; query[r] = target[r] + b->rr_stride[j];
+    }
+    for (int r = 0; r < rows; ++r) if (aln_len[r] < 0) return set_err(-23, W + ": a read of a cluster has no ref<->read row");
+    return rows;
+}
+
 int lcd_batch_region_sorted_ids(lcd_batch_t *b, int region, int *out) {
     if (region < 0 || region >= (int)b->regs.size()) return set_err(-4, "bad region index");
     const RegionRec &R = b->regs[region];

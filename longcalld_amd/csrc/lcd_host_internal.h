@@ -276,7 +276,8 @@ struct lcd_chunk_s {
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     std::unique_ptr<ChunkPending> pending;                 // lcd_chunk_open_from_bam: set until lcd_chunk_resolve (a handle with it has no digars yet)
     DevBuf d_plan; bool plan_ready = false; std::mutex plan_mu;   // lcd_chunk_plan_pass: PlanRead per read (beg / end / status / digar slot), uploaded on first use
-    ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); }
+    lcd_refine_log_t *refine_log = nullptr;                // lcd_chunk_set_refine: the sink of the chunk's rounds; with it the writer refines the chunk's records
+    ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); lcd_refine_log_free(refine_log); }
 };
 
 // ---- noisy-region intervals with cgranges' index order and merge rule (lcd_noisy_regs.cpp).  These names have C linkage and default visibility: written inside

@@ -31,6 +31,11 @@ int lcd_deflate_lds_bytes();
 // bam_tag_kernel.hip: HP / PS rewrite of records in the inflated stream: measure (one lane per record), emit (one wavefront per record)
 void lcd_launch_bam_tag_measure(const BamTagJob *jobs, BamTagOut *outs, int n_jobs, hipStream_t st);
 void lcd_launch_bam_tag_emit(const BamTagJob *jobs, const BamTagOut *outs, uint8_t *out, int n_jobs, hipStream_t st);
+// bam_refine_kernel.hip: records rewritten with the alignment of their final digars (CIGAR, POS, bin, NM / MD / cs, then HP / PS): measure and emit, one wavefront
+// per record each; ref: the chunk window's codes 0-4, ref[0] = position ref_beg, read where ref_beg <= pos < ref_end
+void lcd_launch_bam_refine_measure(const BamRefineJob *jobs, BamRefineOut *outs, const uint8_t *ref, long long ref_beg, long long ref_end, int n_jobs, hipStream_t st);
+void lcd_launch_bam_refine_emit(const BamRefineJob *jobs, const BamRefineOut *outs, const uint8_t *ref, long long ref_beg, long long ref_end, uint8_t *out, int n_jobs,
+                                hipStream_t st);
 // bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
 // counters; compact: scan of the workgroups' run heads + the dense chunk list)
 void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);

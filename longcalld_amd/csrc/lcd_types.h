@@ -262,6 +262,17 @@ struct BamTagJob { uint64_t src; uint32_t len; int kept, hap, pad; long long ps;
 // what the measure pass found: the record's new length, the first HP / PS field to delete as [beg, end) offsets from src (beg == end: none), flags bit 0 / 1:
 // HP:i / PS:i appended; dst: the record's place in the output (filled by the host's prefix sum)
 struct BamTagOut { uint32_t new_len, hp_beg, hp_end, ps_beg, ps_end, flags; uint64_t dst; };
+// ---------------- refined alignments in the phased output (bam_refine_kernel.hip) ----------------
+// one record to write, as BamTagJob, with the read's FINAL digar list: dig = device address of DigarRec[n_digar] (the chunk's own digars, or the uploaded list of a
+// read a noisy region rewrote); skipped: the chunk's is_skipped of the read; words: device address of uint32[n_digar], where the measure pass leaves the merged
+// CIGAR words for the emit pass
+struct BamRefineJob { uint64_t src, dig, words; uint32_t len; int kept, hap, n_digar, skipped, pad; long long ps; };
+// state of a record after the measure pass
+enum { LCD_REFINE_FILTERED = 0, LCD_REFINE_CHANGED = 1, LCD_REFINE_IDENTICAL = 2, LCD_REFINE_NO_DIGARS = 3, LCD_REFINE_QLEN = 4, LCD_REFINE_POS = 5, LCD_REFINE_OPS = 6,
+       LCD_REFINE_CG = 7 };
+// flags: bit 0..4 = NM:i / MD:Z / cs:Z / HP:i / PS:i appended (in that order), bit 5 = the CIGAR words come from `words`, bit 6 = pos and bin are patched;
+// del_*: up to five deleted fields as [beg, end) offsets from src, ascending, an absent one is [len, len); md_len / cs_len: the generated texts without their NUL
+struct BamRefineOut { uint32_t new_len, flags, state, n_ops, md_len, cs_len, new_bin; int nm, new_pos, pos_moved; uint32_t del_beg[5], del_end[5]; uint64_t dst; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;
