@@ -1,6 +1,6 @@
 """SURVEY 8(f) f3 -- BGZF blocks inflated on the device (inflate_kernel.hip, lcd_bgzf_inflate_dev): the checker is Python's zlib (the writer and the reader of the
-expected bytes), on data that exercises every part of RFC 1951 the decoder implements: stored / fixed / dynamic blocks, long codes (15 bits, behind the 11-bit primary
-table), matches at distance 1 and at the window's far end, blocks of 1 byte and of 65 280 bytes, several deflate blocks inside one BGZF block, and the container's
+expected bytes), on data that exercises every part of RFC 1951 the decoder implements: stored / fixed / dynamic blocks, long codes (15 bits, behind the 10-bit
+literal/length and 9-bit distance primary tables), matches at distance 1 and at the window's far end, blocks of 1 byte and of 65 280 bytes, several deflate blocks inside one BGZF block, and the container's
 own checks (ISIZE, CRC-32, truncation)."""
 import ctypes as C
 import struct
