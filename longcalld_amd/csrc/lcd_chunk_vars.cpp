@@ -339,7 +339,7 @@ int lcd_chunk_clean_vars_batch(int n, const lcd_chunk_t *const *chunks, const lc
             if (rc[i]) err[i] = lcd_last_error();
         }
     };
-    const int nt = std::max(1, std::min(n, host_team()));
+    const int nt = std::max(1, std::min(n, host_team(HostSwitches::from_env())));
     std::vector<std::thread> th;
     for (int t = 1; t < nt; ++t) th.emplace_back(work);
     work();

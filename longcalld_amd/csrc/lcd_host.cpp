@@ -47,58 +47,12 @@ bool is_homopolymer(const uint8_t *seq, int seq_len, int flank) { // src/align.c
     return hp_len >= 5;
 }
 
-std::atomic<int> g_wfa_hint{0}; // 0..2: learned from the overflow retries of earlier ANCHOR stages (read vs read windows of noisy reads)
-// first score bound of a job (WfaJob.s_cap on entry of run_wfa_stage; overflow -> x4 + 64): the length difference as one long gap plus a little
-// divergence.  Since the wavefront values live in a ring (wfa_kernel.hip) the bound no longer sizes a quadratic arena of retained wavefronts
-// (20 B x s^2), only the decision bytes (1 B per diagonal, blocked and checkpointed above 16 MB) -- but a tight bound keeps the small jobs in
-// the LDS class: a job of score <= ~100 holds its whole value ring in 16-32 KB of LDS.
-int wfa_default_scap(int plen, int tlen, bool anchor = false) {
-    int d = plen > tlen ? plen - tlen : tlen - plen;
-    int m = plen < tlen ? plen : tlen;
-    static const double div[3] = {0.005, 0.06, 0.20};
-    long long s = 24 + d + 40 + (long long)(m * div[anchor ? g_wfa_hint.load() : 0]) * 6; // (ref<->cons and segment jobs are clean: no hint.  Tried in round 4: twice / four times the slope -- 2 002 / 756 instead of 3 441 second-round jobs of 50 000, the stage within noise)
-    return (int)std::min<long long>(s, 2000000);
-}
-// LDS classes of the value ring.  A class is one launch whose jobs-per-CU is 160 KB / bucket: until round 4 the buckets were 16 / 32 / 64 KB, and the 64 KB class (two
-// jobs per CU) was the tail of both WFA stages -- 8 800 ref<->cons jobs of a 20-batch submission: 7.8 ms; in the HBM-ring class (256 threads, the ring in L2) the same
-// jobs take 2 ms.  LCD_WFA_BUCKETS_KB="a,b,c" overrides (ascending; the last one is the largest ring that stays in LDS unless LCD_WFA_LDS_MAX_KB says otherwise).
-static std::vector<int> wfa_buckets_init() {
-    std::vector<int> v;
-    if (const char *e = getenv("LCD_WFA_BUCKETS_KB")) { for (const char *p = e; *p;) { const int kb = atoi(p); if (kb > 0) v.push_back(kb << 10); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
-    if (v.empty()) v = {16 << 10, 32 << 10};
-    std::sort(v.begin(), v.end());
-    return v;
-}
-static const std::vector<int> kWfaLdsBuckets = wfa_buckets_init();
-// class (value ring in LDS or HBM), decision-byte block and snapshots of one job for the score bound s_want
-static uint64_t wfa_block_target() { return (uint64_t)(getenv("LCD_WFA_BLOCK_KB") ? atoi(getenv("LCD_WFA_BLOCK_KB")) : 16 << 10) << 10; } // (test switch: tiny blocks; read once per stage, not per job)
-void wfa_plan(WfaJob &j, const LcdScoring &sc, long long s_want, const uint64_t blk_target = wfa_block_target()) {
-    auto gap = [&](long long n) { return n <= 0 ? 0ll : std::min<long long>(sc.o1 + sc.e1 * n, sc.o2 + sc.e2 * n); };
-    const long long ub = gap(j.plen) + gap(j.tlen); // delete the pattern, insert the text: no optimal score is above it
-    s_want = std::max<long long>(8, std::min(s_want, ub));
-    WfaLayout L = wfa_layout(j.plen, j.tlen, (int)s_want, (int)s_want + 1, 0, 1, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2);
-    static const uint64_t lds_max = getenv("LCD_WFA_LDS_MAX_KB") ? (uint64_t)atoi(getenv("LCD_WFA_LDS_MAX_KB")) << 10 : (uint64_t)kWfaLdsBuckets.back();
-    if (L.ring_bytes <= lds_max && L.blk_bytes <= blk_target) { j.lds = 1; j.s_cap = (int)s_want; j.blk_rows = j.s_cap + 1; j.n_ckpt = 0; }
-    else {
-        j.lds = 0;
-        if (L.blk_bytes <= blk_target) { j.s_cap = (int)s_want; j.blk_rows = j.s_cap + 1; j.n_ckpt = 0; }
-        else {
-            const long long w = L.w_cap - 2;
-            j.blk_rows = (int)std::max<long long>(32, (long long)(blk_target / (uint64_t)w));
-            j.n_ckpt = (int)((s_want + j.blk_rows) / j.blk_rows) - 1;
-            j.s_cap = j.blk_rows * (j.n_ckpt + 1) - 1;
-        }
-        L = wfa_layout(j.plen, j.tlen, j.s_cap, j.blk_rows, j.n_ckpt, 0, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2);
-    }
-    j.ws_bytes = lcd_align_up(L.total, 256);
-}
-int wfa_class(const WfaJob &j, const LcdScoring &sc) { // 0: HBM ring, 1..: LDS bucket
-    if (!j.lds) return 0;
-    const WfaLayout L = wfa_layout(j.plen, j.tlen, j.s_cap, j.blk_rows, 0, 1, sc.mismatch, sc.o1, sc.e1, sc.o2, sc.e2);
-    for (size_t b = 0; b < kWfaLdsBuckets.size(); ++b) if (L.ring_bytes <= (uint64_t)kWfaLdsBuckets[b]) return (int)b + 1;
-    return (int)kWfaLdsBuckets.size();
-}
-uint64_t ed_arena_bytes(int qlen, int tlen) { return ed_tb_cap(qlen, tlen) * 20 + (uint64_t)qlen * 8 + (uint64_t)tlen * 2 + 512; }
+// The learned levels of the planner (lcd_plan.cpp), 0..2 each.  They belong to the code that learns them -- the POA rounds of a submission and the anchor WFA
+// stage -- and reach the planner as a PlanHints value loaded by whoever calls it.
+std::atomic<int> g_wfa_hint{0};                // learned from the overflow retries of earlier ANCHOR stages (read vs read windows of noisy reads)
+std::atomic<int> g_cell_hint[2] = {{0}, {0}};  // per mode (K1, K2), see chain_caps
+std::atomic<int> g_node_hint{0};               // graph capacity estimate, see chain_caps
+PlanHints learned_hints() { PlanHints h; h.cell[0] = g_cell_hint[0].load(); h.cell[1] = g_cell_hint[1].load(); h.node = g_node_hint.load(); h.wfa = g_wfa_hint.load(); return h; }
 
 // ---- generic stage runners (absolute device addresses in job structs) ----
 // (defer_copy: the statuses stay on the device -- a copy into pageable host memory holds the calling thread until the kernel has ended; the caller fetches them later)
@@ -122,16 +76,10 @@ int run_edlib_stage(hipStream_t st, std::vector<EdJob> &jobs, DevBuf &d_jobs, De
     return 0;
 }
 
-uint64_t wfa_out_bytes(const WfaJob &j) {
-    uint64_t maxl = (uint64_t)j.plen + j.tlen + 1, o = 0;
-    if (j.want & 1) o += lcd_align_up(maxl * 4, 16);
-    if (j.want & 2) o += lcd_align_up(maxl * 2, 16);
-    return o;
-}
 // WFA stage with the overflow retry ladder (score bound x4 + 64).  jobs[i].s_cap holds the wanted score bound on entry (wfa_default_scap);
 // every round plans the pending jobs (class, block, snapshots), launches the LDS buckets and the HBM-ring class and waits for the statuses.
 int run_wfa_stage(hipStream_t st, std::vector<WfaJob> &jobs, DevBuf &d_jobs, DevBuf &d_arena, DevBuf &d_out, DevBuf &d_outs,
-                  std::vector<WfaOut> &outs, LcdScoring sc, int *retries, bool learn = false, hipStream_t *side = nullptr, hipEvent_t *sev = nullptr, int n_side = 0) {
+                  std::vector<WfaOut> &outs, LcdScoring sc, const HostSwitches &sw, int *retries, bool learn = false, hipStream_t *side = nullptr, hipEvent_t *sev = nullptr, int n_side = 0) {
     // side / sev / n_side: the classes' launches are dealt to st and these streams (one kernel per class: six for a HiFi-shape stage, each as long as its longest job)
     const int n = (int)jobs.size();
     outs.assign(n, WfaOut());
@@ -154,14 +102,13 @@ int run_wfa_stage(hipStream_t st, std::vector<WfaJob> &jobs, DevBuf &d_jobs, Dev
         const double tw0 = now_ms();
         // (plans and classes of the jobs are independent: a few host threads -- 50 000 ref<->cons jobs of a 20-batch submission were 3.5 ms of one thread with the GPU idle)
         std::vector<int> cls(n, 0);
-        const uint64_t blk_target = wfa_block_target();
-        par_chunks(m, host_team(), 4096, [&](const size_t lo, const size_t hi, int) { for (size_t q = lo; q < hi; ++q) { const int i = which[q]; wfa_plan(jobs[i], sc, want[i], blk_target); cls[i] = wfa_class(jobs[i], sc); } });
+        par_chunks(m, host_team(sw), 4096, [&](const size_t lo, const size_t hi, int) { for (size_t q = lo; q < hi; ++q) { const int i = which[q]; wfa_plan(jobs[i], sc, want[i], sw); cls[i] = wfa_class(jobs[i], sc, sw); } });
         const double tw1 = now_ms();
         // equal classes contiguous (one launch each); inside a class the larger arenas first (they last longest): a stable counting sort on class | size class (the
         // arena size's exponent and four mantissa bits, descending) -- the order inside a launch is about its tail, nothing else depends on it
         {
             auto key_of = [&](const int i) { const uint64_t w = std::max<uint64_t>(jobs[i].ws_bytes, 16); const int e = 63 - __builtin_clzll(w); return (unsigned)cls[i] * 1024u + (1023u - (unsigned)(e * 16 + (int)((w >> (e - 4)) & 15))); };
-            std::vector<uint32_t> cnt((kWfaLdsBuckets.size() + 1) * 1024 + 1, 0);
+            std::vector<uint32_t> cnt((sw.wfa_buckets_kb.size() + 1) * 1024 + 1, 0);
             std::vector<unsigned> kq(m);
             for (size_t q = 0; q < m; ++q) { kq[q] = key_of(which[q]); cnt[kq[q] + 1]++; }
             for (size_t k = 1; k < cnt.size(); ++k) cnt[k] += cnt[k - 1];
@@ -171,7 +118,7 @@ int run_wfa_stage(hipStream_t st, std::vector<WfaJob> &jobs, DevBuf &d_jobs, Dev
         }
         uint64_t tot = 0;
         for (int i : which) { jobs[i].ws_off = tot; tot += jobs[i].ws_bytes; }
-        if (getenv("LCD_MEM_DEBUG")) {
+        if (sw.mem_debug) {
             size_t nl = 0, nck = 0; uint64_t big = 0; for (int i : which) { nl += jobs[i].lds; nck += jobs[i].n_ckpt > 0; big = std::max(big, jobs[i].ws_bytes); }
             fprintf(stderr, "[mem] WFA stage round %d: %zu jobs (%zu in LDS, %zu checkpointed), arena %.3f GB, largest job %.1f MB (hint %d)\n", round, m, nl, nck, tot / 1e9, big / 1e6, g_wfa_hint.load());
         }
@@ -179,17 +126,17 @@ int run_wfa_stage(hipStream_t st, std::vector<WfaJob> &jobs, DevBuf &d_jobs, Dev
         sub.resize(m); tmp.resize(m);
         for (size_t q = 0; q < m; ++q) { jobs[which[q]].ws_off += d_arena.addr(); sub[q] = jobs[which[q]]; }
         HIPCHK(hipMemcpyAsync(d_jobs.p, sub.data(), m * sizeof(WfaJob), hipMemcpyHostToDevice, st));
-        if (getenv("LCD_TIME_HOST")) fprintf(stderr, "[host]   WFA stage round %d: %zu jobs planned (%.1f ms), ordered and laid out in %.1f ms\n", round, m, tw1 - tw0, now_ms() - tw0);
+        if (sw.time_host) fprintf(stderr, "[host]   WFA stage round %d: %zu jobs planned (%.1f ms), ordered and laid out in %.1f ms\n", round, m, tw1 - tw0, now_ms() - tw0);
         const int ns = (side && sev && n_side > 0) ? n_side + 1 : 1;
         if (ns > 1) HIPCHK(hipEventRecord(sev[0], st)); // the job table is there
         std::vector<char> used(ns, 0);
         int turn = 0;
         // (the HBM-ring class's jobs with workspaces of a megabyte and more -- fronts of thousands of diagonals: SV-size gaps -- are a launch of their own, on the
         //  instantiation that keeps several diagonals per thread in flight; the class is sorted by workspace size, largest first, so they are its head)
-        static const uint64_t wide_from = getenv("LCD_WFA_WIDE_KB") ? (uint64_t)atoll(getenv("LCD_WFA_WIDE_KB")) << 10 : (uint64_t)1 << 20;
+        const uint64_t wide_from = (uint64_t)sw.wfa_wide_kb << 10; // LCD_WFA_WIDE_KB
         // (only when there are enough of them to be a workload of their own -- 64, LCD_WFA_WIDE_MIN: a handful of such jobs in a clean-read submission as one more launch
         //  took a stream's turn from the LDS classes, which then queued behind the longest jobs: 156 k against 172 k regions/s at the default flags, two lanes of 32 batches)
-        static const size_t wide_min = getenv("LCD_WFA_WIDE_MIN") ? (size_t)atoll(getenv("LCD_WFA_WIDE_MIN")) : 64;
+        const size_t wide_min = (size_t)sw.wfa_wide_min;
         size_t n_wide = 0;
         if (wide_from > 0) for (size_t q = 0; q < m; ++q) n_wide += cls[which[q]] == 0 && jobs[which[q]].ws_bytes >= wide_from;
         const bool wide_on = wide_from > 0 && n_wide >= wide_min;
@@ -200,7 +147,7 @@ int run_wfa_stage(hipStream_t st, std::vector<WfaJob> &jobs, DevBuf &d_jobs, Dev
             const int t = turn++ % ns;
             hipStream_t s2 = t == 0 ? st : side[t - 1];
             if (t != 0 && !used[t]) { HIPCHK(hipStreamWaitEvent(s2, sev[0], 0)); used[t] = 1; }
-            lcd_launch_wfa((const WfaJob *)d_jobs.p + a, nullptr, nullptr, nullptr, (WfaOut *)d_outs.p + a, sc, (int)(b - a), c ? kWfaLdsBuckets[c - 1] : 0, s2, wide ? 1 : 0);
+            lcd_launch_wfa((const WfaJob *)d_jobs.p + a, nullptr, nullptr, nullptr, (WfaOut *)d_outs.p + a, sc, (int)(b - a), c ? sw.wfa_buckets_kb[c - 1] << 10 : 0, s2, wide ? 1 : 0);
             HIPCHK(hipGetLastError());
             a = b;
         }
@@ -220,7 +167,7 @@ int run_wfa_stage(hipStream_t st, std::vector<WfaJob> &jobs, DevBuf &d_jobs, Dev
         which.swap(again);
     }
     if (!which.empty()) return set_err(-21, "WFA score bound exhausted after retries");
-    if (learn && getenv("LCD_MEM_DEBUG")) { // anchor stage: how the optimal scores compare with the first score bound
+    if (learn && sw.mem_debug) { // anchor stage: how the optimal scores compare with the first score bound
         double r_sum = 0; int cnt = 0, over = 0; double worst = 0;
         for (int i = 0; i < n; ++i) { const int mm = std::min(jobs[i].plen, jobs[i].tlen); if (mm < 50) continue; const double r = (double)outs[i].score / mm; r_sum += r; ++cnt; worst = std::max(worst, r); over += outs[i].score > first_want[i]; }
         fprintf(stderr, "[mem] anchor WFA: %d jobs >= 50 bp, score / min(len) mean %.3f max %.3f; %d above their first bound\n", cnt, cnt ? r_sum / cnt : 0.0, worst, over);
@@ -388,7 +335,7 @@ static int add_region_impl(lcd_batch_t *b, int64_t reg_len, int n_reads, const i
                 if (ext == 1) { ej.t_off = toff; ej.q_off = qoff; } else { ej.t_off = toff + tlen - min_len; ej.q_off = qoff + qlen - min_len; }
                 A.ed_job = (int)b->ed_jobs.size(); b->ed_jobs.push_back(ej);
                 WfaJob wj; wj.p_off = toff; wj.plen = tlen; wj.t_off = qoff; wj.tlen = qlen; wj.gap_aln = gap_aln; wj.want = 1;
-                wj.s_cap = wfa_default_scap(tlen, qlen, true); wj.ws_off = 0; wj.ws_bytes = 0; wj.out_off = 0;
+                wj.s_cap = wfa_default_scap(tlen, qlen, g_wfa_hint.load()); wj.ws_off = 0; wj.ws_bytes = 0; wj.out_off = 0;
                 A.wfa_job = (int)b->wfa_jobs.size(); b->wfa_jobs.push_back(wj);
                 b->anchors.push_back(A);
             }
@@ -540,261 +487,9 @@ int lcd_batch_upload(lcd_batch_t *b) {
 
 static int stage_gather(lcd_batch_t *b, hipStream_t st);
 static int stage_gather_many(lcd_batch_t **bs, int nb, hipStream_t st);
-static std::atomic<int> g_cell_hint[2] = {{0}, {0}}; // per mode (K1, K2): 0..2, see chain_caps
-static std::atomic<int> g_node_hint{0};                // 0..2: graph capacity estimate, see chain_caps
-static void chain_class(PoaChain &pc, bool noisy);
-// where a K2 chain goes when its certified band outgrew the window: full rows.  (Tried: the band in multi-wavefront windowed rows of 512 / 1 024 columns first;
-// their rows meet at a workgroup barrier twice per row and measured SLOWER than the systolic full rows they would replace -- configs[1]: 46.9 k instead of
-// 52.5 k regions/s with three such chains per batch; ONT shape with every K2 chain there: 6.6 k instead of 13.1 k)
-static int cert_next_level(const PoaChain &) { return 0; }
-// the test switches chain_caps looks at, read ONCE per caller (a submission sizes 46 000 chains: seven getenv() scans of the environment per chain were most of the
-// 3 ms x 8 threads this took)
-struct ChainEnv {
-    int cert_mode, solo_len, cert_sys, solo_mw, solo_cyc, cell_shrink, ring16; long long solo_rl;
-    long long n_chains = 1ll << 40, solo_cyc_min; // (chains in the submission at hand: Submission sets it)
-    ChainEnv() {
-        ring16 = getenv("LCD_RING16") ? atoi(getenv("LCD_RING16")) : 1; // (0: 32-bit rings; 2: test switch -- 16-bit pools whatever the bounds below say, so that the kernel's own range guard is what sends a read to the generic rows)
-        solo_cyc_min = getenv("LCD_SOLO_CYC_MIN") ? atoll(getenv("LCD_SOLO_CYC_MIN")) : 16000;
-        cert_mode = getenv("LCD_CERT") ? atoi(getenv("LCD_CERT")) : 1;
-        solo_len = getenv("LCD_CERT_SOLO_LEN") ? atoi(getenv("LCD_CERT_SOLO_LEN")) : 0;
-        cert_sys = getenv("LCD_CERT_SYS") ? atoi(getenv("LCD_CERT_SYS")) : 0;
-        solo_rl = getenv("LCD_SOLO_RL") ? atoll(getenv("LCD_SOLO_RL")) : 100000;
-        solo_mw = getenv("LCD_SOLO_MW") ? atoi(getenv("LCD_SOLO_MW")) : 0;
-        solo_cyc = getenv("LCD_SOLO_CYC") ? atoi(getenv("LCD_SOLO_CYC")) : 1;
-        cell_shrink = getenv("LCD_CELL_SHRINK") ? std::max(1, atoi(getenv("LCD_CELL_SHRINK"))) : 0;
-    }
-};
-static void chain_caps(const lcd_opt_t &opt, const ChainRec &C, const std::vector<PoaRead> &preads, int scale, PoaChain &pc, const ChainEnv &env) {
-    const int n = (int)C.members.size();
-    long long sum = 0; int maxl = 0;
-    for (int k = 0; k < n; ++k) { const PoaRead &r = preads[C.read0 + k]; sum += r.len; maxl = std::max(maxl, r.len); }
-    pc.n_reads = n; pc.read0 = C.read0; pc.mode = C.mode;
-    // K2 chains of clean reads run in the single-wavefront class with rows restricted to the CERTIFIED band (poa_kernel.hip align_certified: same
-    // alignments as the full rows, ~20x fewer cells on HiFi-shape regions); noisy reads' bounds are too loose for a 256-column window (LCD_CERT=2 forces
-    // them through it, 0 switches the path off).  A chain whose band outgrows the window comes back with LCD_ERR_CERT and is re-run with full rows.
-    const int cert_mode = env.cert_mode; // (LCD_CERT, read per submission: the tests switch it)
-    int lvl = C.cert_level;
-    // (Long chains are the critical path of a submission, and in a 64-thread workgroup a third to a half of such a chain is the per-read work around the rows --
-    // graph update, re-sort, plan: parallel over the nodes.  LCD_CERT_SOLO_LEN=n gives chains of reads >= n bases a 256-thread workgroup whose wavefront 0 runs
-    // the same rows (poa_kernel.hip align_windowed<.., SOLO>).  Measured slower at every threshold -- 20 batches: 36 - 42 k instead of 45 k regions/s, 2 x 32
-    // batches: 52 k instead of 66 k -- so it is off by default.)
-    const int solo_len = env.solo_len; // (LCD_CERT_SOLO_LEN, read per submission: a test switches it)
-    // Noisy reads (level 2): the band in the systolic rows of the class the reads' length asks for (poa_kernel.hip align_certified_sys); LCD_CERT_SYS=0: full rows
-    const int cert_sys = env.cert_sys; // (LCD_CERT_SYS, read per submission: the tests switch it)
-    if (lvl < 0) lvl = !(C.mode == 1 && maxl < 65535) ? 0 : (cert_mode == 2 || (cert_mode == 1 && !opt.is_ont)) ? 1 : (cert_mode == 1 && cert_sys && maxl >= 256) ? 2 : 0;
-    pc.cert = C.mode == 1 ? lvl : 0; pc.ring_k = 0;
-    // LONG chains -- the critical path of a submission, and of a single batch: 34 reads x 4 kb run 0.28 s on one wavefront, more than half of it the per-read phases around
-    // the rows (row plan, graph update, re-sort, backtrack: latency chains through L2 with 64 loads in flight) -- get a 256-thread workgroup: wavefront 0 runs the same
-    // lean rows, all four the phases around them (4x the loads in flight).  LCD_SOLO_RL: reads x longest read from which on (0 = off); LCD_CERT_SOLO_LEN: certified-band
-    // chains by read length (test switch)
-    {
-        const long long solo_rl = env.solo_rl; // (LCD_SOLO_RL, read per submission: tests switch it)
-        pc.solo = (C.solo >= 0 ? C.solo > 0 : (solo_rl > 0 && (long long)n * maxl >= solo_rl)) || (solo_len > 0 && pc.cert == 1 && maxl >= solo_len) ? 1 : 0;
-        // LCD_SOLO_MW=1: long certified-band chains run their rows on all four wavefronts of the workgroup (poa_kernel.hip align_lean_mw) instead of wavefront 0 alone.
-        // Same alignments (digest 0004c9ba86f18807 at the driver's flags), but measured SLOWER: 3 530 instead of 2 950 ticks per row of the longest chain, 80.6 k instead
-        // of 88.4 k regions/s -- every wavefront pays the row's fixed cost (plan word, interval, predecessor loop, metadata: ~400 instructions in this version, which
-        // reads every predecessor from the LDS ring) plus two LDS round trips and two barriers, and the cells it saves are ~75 instructions.  Off by default.
-        if (pc.solo && pc.cert == 1 && env.solo_mw > 0) pc.solo = 2;
-        // Round 4: the rows of the long certified-band chains run as a PIPELINE over the four wavefronts (poa_kernel.hip align_cyc: mailboxes, no barrier, the row before in
-        // registers) -- LCD_SOLO_CYC=0 keeps them on wavefront 0
-        // (the four-wavefront pipeline pays on a CROWDED chip, where a lone wavefront of the long chain gets a quarter of its SIMD: 16 / 20 batches 173 / 200 ms with it,
-        //  197 / 206 without.  A chain that has its CU to itself is faster on one wavefront -- a lone batch 117 ms instead of 128, four batches 152 instead of 154:
-        //  the pipeline from LCD_SOLO_CYC_MIN chains per submission on)
-        if (pc.solo == 1 && pc.cert == 1 && env.solo_cyc != 0 && env.n_chains >= env.solo_cyc_min) pc.solo = 3;
-    }
-    // graph capacity: the worst case is one node per base of every read (sum), the usual case a little more than the longest read.  Sized
-    // from an estimate (a few per cent of new nodes per read on top of the backbone; g_node_hint learns noisier data); a chain that runs
-    // out (LCD_ERR_NODES / LCD_ERR_EDGES) is re-run with 4x more per retry, up to the worst case.  The worst case for everybody was
-    // 10 GB of arena per 1 250 regions, nearly all of it never touched.
-    const long long node_worst = std::min<long long>(sum + 2, 2000000000ll), edge_worst = std::min<long long>(sum + n + 2, 2000000000ll);
-    {
-        static const double nf[3] = {1.25, 2.0, 4.0}, sf[3] = {0.03, 0.10, 0.30};
-        static const int nh_env = getenv("LCD_NODE_HINT") ? atoi(getenv("LCD_NODE_HINT")) : -1; // (test switch: the learned level, fixed)
-        const int nh = nh_env >= 0 && nh_env <= 2 ? nh_env : g_node_hint.load();
-        long long est = (long long)(nf[nh] * maxl + sf[nh] * (double)sum) + 64;
-        for (int sc2 = 1; sc2 < scale; sc2 *= 2) est *= 4;
-        pc.node_cap = (int)std::min(node_worst, est);
-        pc.edge_cap = (int)std::min(edge_worst, est + est / 4 + n);
-    }
-    pc.rid_words = (n + 63) / 64; pc.max_len = maxl;
-    int mw = (int)(n * opt.min_af); if (mw < 2) mw = 2;
-    pc.min_w = (uint32_t)mw;
-    // rows actually visited ~ graph size ~ a small multiple of the backbone; band ~ 2w+1 plus drift.  Overflow is detected
-    // in-kernel (LCD_ERR_CELLS) and the chain is re-run with `scale` x more, up to the worst case.
-    const long long rows_worst = pc.node_cap;
-    // g_cell_hint[mode]: learned from the overflow retries of earlier submissions (noisy reads: every read adds ~error-rate new nodes,
-    // and the row-max columns that steer the adaptive band drift further) -- a chain that overflows is re-run from scratch, so data that
-    // keeps overflowing is given the larger estimate up front
-    static const int ch_env = getenv("LCD_CELL_HINT") ? atoi(getenv("LCD_CELL_HINT")) : -1; // (test switch)
-    const int hint = ch_env >= 0 && ch_env <= 2 ? ch_env : g_cell_hint[C.mode ? 1 : 0].load();
-    static const double rows_f[3] = {1.3, 2.2, 3.2}; static const int band_x[3] = {64, 128, 192};
-    const long long rows_est = std::min<long long>(rows_worst, (long long)(rows_f[hint] * maxl) + 64);
-    long long band;
-    if (C.mode == 0) band = std::min<long long>(maxl + 1, 2ll * (10 + maxl / 100) + 1 + band_x[hint]);
-    else if (pc.cert == 2) band = std::min<long long>(maxl + 1, std::max<long long>(1040, (long long)(0.6 * maxl))); // (noisy reads: intervals of a third to a half of the read)
-    else if (pc.cert) { // windowed rows of <= 260 columns at 1 B of code per cell -- and room for a few reads through the generic rows (12 B per cell of intervals wider
-        // than the window, poa_kernel.hip align_certified): LCD_CERT_BAND columns per row
-        static const long long cert_band = getenv("LCD_CERT_BAND") ? atoll(getenv("LCD_CERT_BAND")) : 1040;
-        band = std::min<long long>(maxl + 1, cert_band);
-    }
-    else band = maxl + 1;
-    long long cells = rows_est * band;
-    if (env.cell_shrink > 0) cells = std::max<long long>(cells / env.cell_shrink, 1); // test switch: estimates far too small, so that the chains have to grow their regions (tests/test_gpu_region.py)
-    // (tried: the single-wavefront class compiled for 64 VGPRs (__launch_bounds__(64, 8): 32 instead of 16 wavefronts per CU, 4 - 8 KB pools): 34 - 37 k instead of
-    // 51 k regions/s -- the row loops spill (40 - 170 B of scratch per lane inside align_windowed) and the graph phases' scratch grows from 924 to 1 336 B)
-    // (tried: 3x the estimate up front for the long K1 chains of noisy reads, which overflow most -- 5 instead of 60 re-runs per 4 SV-shape batches, but
-    // the POA stage got 20 % LONGER: an overflowing chain gives up early and its re-run shares the chip with ~50 others instead of 9 000)
-    // K2 chains of noisy reads: at one code byte per worst-case cell EVERY such chain ran out of spilled value rows (a spilled row is 12 bytes
-    // per window column; clean graphs spill a few per cent of their rows, but in the graphs of 5 %-error reads most rows have a successor more
-    // than K rows away, and nearly every row has >= 2 usable predecessors, i.e. an ordinal word per cell) and was re-run with a 4x graph.
-    // Once the hint says the K2 chains overflow, their region is code | 4 ordinal planes | 8 planes of spilled rows (13 x cell_cap, not 4 x)
-    pc.spill_x = C.mode == 1 && hint >= 1 ? 8 : 2; // (a spilled row is 12 B per WINDOW column, 12-24x a code row: half of the rows spilled = 6-12x the code plane)
-    if (C.mode == 1 && hint >= 1) pc.edge_cap = (int)std::min<long long>(edge_worst, 2ll * pc.edge_cap); // (and their graphs have more bubbles per node)
-    // K1 chains of noisy reads: a dozen or two per ONT-shape submission ran out of EDGES (nothing grows those in place) and were re-run from their first read in a second
-    // round that lasts as long as its slowest chain -- 0.29 s of a 1.9 s stage for 0.05 % of the chains; 28 bytes per edge
-    if (C.mode == 0 && opt.is_ont) pc.edge_cap = (int)std::min<long long>(edge_worst, 2ll * pc.edge_cap);
-    const long long worst = rows_worst * (long long)(maxl + 1);
-    for (int s = 1; s < scale && cells < worst; s *= 2) cells *= 8;
-    cells = std::min(cells, worst);
-    pc.cell_cap = (uint64_t)std::max<long long>(cells, maxl + 64);
-    // 16-bit ring values: wanted (LCD_RING16) and representable -- the same bounds the kernel checks per read (poa_kernel.hip align_lean, "int16 range"), here on the
-    // chain's longest read with the scoring at hand: best case every base a match plus the heaviest bonus path (every traversed edge adds ilog2(weight) <= ilog2(reads),
-    // a path has ~1.1 nodes per base), worst case a gap over all rows plus a gap over all columns.  A chain that fails this is laid out for a 32-bit ring from the
-    // start (its pool and bucket are those of the 32-bit ring) instead of meeting the kernel's guard on every read and taking the generic rows
-    {
-        int lg = 0; while ((2 << lg) <= std::max(n, 1)) ++lg; // ilog2(n): the largest edge weight is the number of reads
-        const long long rows = (long long)(1.1 * maxl) + 64;
-        const long long o_max = std::max(opt.gap_open1, opt.gap_open2), e_min = std::min(opt.gap_ext1, opt.gap_ext2);
-        const long long best = (long long)maxl * opt.match + rows * lg + 64;
-        const long long worstv = 2 * (o_max + e_min * rows) + (opt.gap_open1 + opt.gap_open2) + 2ll * (opt.gap_ext1 + opt.gap_ext2) + 64;
-        pc.ring16 = env.ring16 == 2 ? 2 : env.ring16 && best <= 32000 && worstv <= 32000 ? 1 : 0; // (chain_class keeps it for certified-band chains of the single-wavefront class)
-    }
-    chain_class(pc, opt.is_ont != 0);
-    // SMALL graphs of noisy reads: nearly every row has a successor further away than the ring and is spilled -- 12 bytes per WINDOW column (768 B for the narrowest
-    // window) whatever the chain's width -- while their DP region, at the worst case of nodes x (length + 1) cells, is a few tens of KB: 45 of the 58 chains an
-    // SV-shape submission sent to a second round were chains of 44 - 110 bases that had run out of spilled rows (LCD_RETRY_DEBUG=1), and a second round lasts as long
-    // as its slowest chain.  Room for every row spilled, for graphs of up to 1 024 nodes (<= 1.5 MB per chain).
-    if (opt.is_ont && pc.node_cap <= 1024) {
-        const uint64_t win = (pc.threads == 64 || pc.solo) ? (uint64_t)pc.wmax : 4ull * pc.threads;
-        const uint64_t floor_cells = ((uint64_t)pc.node_cap + 2) * (3 * win * 4) / (uint64_t)(pc.spill_x > 2 ? pc.spill_x : 2) + 64;
-        if (pc.cell_cap < floor_cells) pc.cell_cap = floor_cells;
-    }
-}
-
-// Workgroup size class + LDS budget of a chain (poa_kernel.hip): threads follow the DP row width; the dynamic LDS pool holds
-// K ring slots of `wmax` columns + the query cache during the DP and the 16-bit graph copy of the re-sort (about 22 B per node)
-// afterwards.  Chains are launched in groups of equal (threads, LDS bucket) so that short chains do not pay a long chain's LDS.
-// LCD_SOLO_KB, rounded up to an LDS bucket (a value between two buckets -- 56 -- made the long chains' kernel end 3 s late: not understood, so not offered)
-static int solo_kb_env() {
-    const int v = getenv("LCD_SOLO_KB") ? atoi(getenv("LCD_SOLO_KB")) : 64;
-    for (int b : {8, 12, 16, 24, 32, 48, 64, 96, 148}) if (v <= b) return b;
-    return 148;
-}
-static void chain_class(PoaChain &pc, bool noisy) {
-    // DP row width: K2 rows span the whole read (+2 guard columns of the window); K1 rows are the adaptive band plus drift
-    const long long width = pc.cert == 1 ? 256 : pc.mode == 1 ? (long long)pc.max_len + 2 : 2ll * (10 + pc.max_len / 100) + 1 + 48;
-    int threads, K, wmax; // wmax: window / ring-slot width in columns, a power of two <= 4 * threads (poa_kernel.hip align_windowed)
-    if (width > 256) pc.solo = 0; // (the wide classes have their own rows)
-    // one lane per four columns of the window: 64 / 128 / 256 / 512 / 1024 threads, so that no wavefront of a workgroup idles
-    // (a 2 048-column chain in a 1 024-thread workgroup would hold a whole CU's registers with half of its wavefronts parked)
-    if (width <= 256) { // single wavefront; banded chains prefer the narrowest window their band fits (1, 2 or 4 cells per lane, align_windowed)
-        threads = 64; K = 2;
-        static const int margin = getenv("LCD_BAND_MARGIN") ? atoi(getenv("LCD_BAND_MARGIN")) : 12;
-        const long long bw = 2ll * (10 + pc.max_len / 100) + 1 + margin; // adaptive band + a little drift; a band that outgrows it is re-run wider
-        static const int cert_ring = getenv("LCD_CERT_RING") ? atoi(getenv("LCD_CERT_RING")) : 512; // (certified-band chains: ring slots wide enough for the reads that take the generic rows)
-        wmax = pc.cert == 1 ? std::max(256, cert_ring) : pc.mode == 1 ? 256 : bw <= 60 ? 64 : bw <= 124 ? 128 : 256;
-        if (pc.solo) threads = 256; // (same rows, same ring layout: only the per-read phases see the other three wavefronts)
-    }
-    else if (width <= 512) { threads = 128; K = 2; wmax = 512; }
-    else if (width <= 1024) { threads = 256; K = 2; wmax = 1024; }
-    else if (width <= 2048) { threads = 512; K = 2; wmax = 2048; }
-    else { threads = 1024; K = 2; wmax = 4096; } // wider rows take the generic (HBM) rows of the kernel
-    const long long est_nodes = (long long)(pc.max_len * 1.15) + 64;
-    const long long seq_bytes = lcd_align_up((long long)pc.max_len + 28, 16) + lcd_align_up(est_nodes + 16, 16); // query cache + first-predecessor distances
-    // ring slots of the single-wavefront class: 2, except long K1 chains of noisy reads -- their graphs interleave the alternatives of every column, a row's
-    // predecessors sit 3 - 6 rows back as often as not, and a predecessor that has left the ring costs the row two dependent trips to HBM (its metadata, then
-    // its spilled values); those chains are few and they are the latency of an SV-shape submission, so they get LCD_RING_K (8) slots and the LDS that takes
-    if ((threads == 64 || pc.solo) && pc.mode == 0 && noisy) {
-        static const int rk_env = getenv("LCD_RING_K") ? atoi(getenv("LCD_RING_K")) : 8, rk_len = getenv("LCD_RING_K_LEN") ? atoi(getenv("LCD_RING_K_LEN")) : 1500;
-        if (pc.max_len >= rk_len && rk_env >= 2 && (rk_env & (rk_env - 1)) == 0 && rk_env <= 32) K = rk_env;
-    }
-    // certified-band K2 chains of the single-wavefront class keep 16-bit ring values (H, E1, E2 of reads below 15 000 bases fit int16): their 512-column ring was 12 of
-    // their 16 KB, and LDS x time is what a submission runs out of first ("Where the chain kernels' time goes now").  LCD_RING16=0 (read per submission): 32-bit, as before
-    pc.ring16 = pc.ring16 /* wanted and representable: chain_caps, LCD_RING16 */ && threads == 64 && !pc.solo && pc.cert == 1 && (pc.ring16 == 2 || pc.max_len < 15000) ? 1 : 0; pc.pad3_ = 0;
-    const long long dp_bytes = (long long)K * 3 * wmax * (pc.ring16 ? 2 : 4) + seq_bytes; // the ring holds `wmax` columns per slot (4 * threads, or the narrower preferred window of a single-wavefront banded chain)
-    // the re-sort's LDS copy of the graph: 8 B per node + 4 B per edge (topo_sort_block); edges ~ nodes + a few per bubble
-    long long need = std::max(dp_bytes, est_nodes * 8 + (est_nodes + est_nodes / 8) * 4 + 64);
-    { // the single-wavefront class is kept to a small pool: 16 such chains per CU (8 KB each, the wavefront limit at 128 VGPRs) instead of 2-9
-      // is worth more than a fast re-sort -- bigger graphs do their Kahn walk on the same packed words in HBM (16 KB: +17 % regions/s over
-      // uncapped pools; 8 KB with the ring laid out for the preferred window: another +7 %).  Noisy reads (graphs twice the size, a re-sort after
-      // nearly every read) preferred 16 KB while the Kahn walk was a serial pass over every node; since it jumps chains (v12) 8 KB is best for them
-      // too (+6 % over 16 KB).  LCD_LDS_CAP_KB overrides.
-        static const int cap_env = getenv("LCD_LDS_CAP_KB") ? atoi(getenv("LCD_LDS_CAP_KB")) : -1;
-        const int cap_kb = cap_env >= 0 ? cap_env : 8;
-        // (tried: certified-band K2 chains -- few, some long: 35 reads x 3.7 kb is the critical path of a submission, a quarter of it re-sorts -- with the pool
-        //  the re-sort wants (32 / 64 KB instead of the cap): 42 k / 30 k instead of 43 k regions/s at 20 batches; the same for the long ones only (>= 1 000 /
-        //  1 500 bases): 30 k / 28 k; again after the streams learned to count a group's longest chain, so that the extra launch group is not queued behind
-        //  another: 41 k / 44 k / 48 k for chains >= 1 500 / 2 500 / 3 000 bases against 60.8 k -- it is the chains themselves that get slower with the
-        //  re-sort's LDS path, not their place in the queue)
-        const int cap_here = cap_kb;
-        if (cap_here > 0 && threads == 64) need = std::max(dp_bytes, std::min<long long>(need, (long long)cap_here << 10));
-        // (the long chains: what the re-sort would like beyond their bucket does not move them into the 148 KB bucket -- one workgroup per CU -- any more; LCD_SOLO_CAP=0: as before)
-        static const bool solo_cap = !(getenv("LCD_SOLO_CAP") && atoi(getenv("LCD_SOLO_CAP")) == 0);
-        static const int solo_kb0 = solo_kb_env();
-        if (solo_cap && pc.solo) need = std::max(dp_bytes, std::min<long long>(need, (long long)solo_kb0 << 10));
-    }
-    // LDS per workgroup decides how many single-wavefront chains share a CU (160 KB, 16 wavefronts at 128 VGPRs), and those chains are
-    // most of the work: fine-grained buckets; every (threads, bucket) group is one launch, a few streams run the groups (launch_poa_grouped)
-    static const int buckets[] = {8 << 10, 12 << 10, 16 << 10, 24 << 10, 32 << 10, 48 << 10, 64 << 10, 96 << 10, 148 << 10};
-    int lds = buckets[8];
-    for (int b : buckets) if (need <= b) { lds = b; break; }
-    // the long chains of a submission are ONE launch group (one LDS size): kernels of a stream run one after the other, and every group of a few long chains lasts as
-    // long as its longest chain -- four such groups on the four streams held everything else back for 0.2 s
-    if (pc.solo) { static const int solo_kb = solo_kb_env(); lds = std::max(std::min(lds, 148 << 10), solo_kb << 10); if (lds > (solo_kb << 10)) lds = 148 << 10; }
-    // The longest single-wavefront chains are the critical path of a submission (34 reads x 4 kb: 0.28 s against 0.20 s of work for the whole chip), and next to 15
-    // other chains of its CU such a wavefront issues one instruction per ~7 cycles.  Chains above LCD_ISO_RL read-bases ask for LCD_ISO_KB of LDS: three of them fill
-    // a CU's LDS, so each has a SIMD (nearly) to itself -- and a pool its re-sort runs in.
-    if (threads == 64) {
-        static const long long iso_rl = getenv("LCD_ISO_RL") ? atoll(getenv("LCD_ISO_RL")) : 90000;
-        static const int iso_kb = getenv("LCD_ISO_KB") ? atoi(getenv("LCD_ISO_KB")) : 0; // (measured: the isolated chain is 8 % faster, the submission 10 % slower -- the extra launch group costs more than it gives; off)
-        if (iso_kb > 0 && (long long)pc.n_reads * pc.max_len >= iso_rl) lds = std::max(lds, iso_kb << 10);
-    }
-    // (noisy K1 chains below that length: as many slots as the bucket they have anyway leaves room for -- LCD_RING_K_FREE=0 keeps them at 2.  Tried for the K1
-    //  chains of clean reads too: no change at 2 x 32 batches, 47 k instead of 60 k regions/s at one submission of 20)
-    if ((threads == 64 || pc.solo) && pc.mode == 0 && noisy && K == 2) {
-        static const bool rk_free = !(getenv("LCD_RING_K_FREE") && atoi(getenv("LCD_RING_K_FREE")) == 0);
-        // (until round 4 only in the buckets the default pool cap produces: with LCD_LDS_CAP_KB=16 the rule gives eight slots of 64 columns whose next wider window --
-        //  eight slots of 128 -- lies over the first-predecessor distances, and the rows that ran after it followed the overwritten distances for ever.  Root cause fixed
-        //  in poa_kernel.hip (WinOut.clobber; tests/test_gpu_kernels.py::test_wider_window_after_a_ring_that_outgrew_the_pool_layout); the restriction is gone: same
-        //  digest and rate on the ONT shape with and without it.  LCD_RING_K_MAXLDS_KB restores it)
-        static const int rk_maxlds = getenv("LCD_RING_K_MAXLDS_KB") ? atoi(getenv("LCD_RING_K_MAXLDS_KB")) : 148;
-        while (rk_free && lds <= (rk_maxlds << 10) && K < 8 && (long long)(2 * K) * 3 * wmax * 4 + seq_bytes <= lds) K *= 2;
-    }
-    pc.threads = threads; pc.wmax = wmax; pc.lds_words = lds / 4; pc.ring_k = (threads == 64 || pc.solo) ? K : 0;
-}
-static int chain_threads(const PoaChain &pc) { return pc.threads; }
-static long long chain_group_key(const PoaChain &pc) { return (long long)pc.threads * (1 << 20) + pc.lds_words; }
-// Chains of one launch group that share a CU: 160 KiB of LDS over the chain's pool plus what a workgroup takes besides it, and 16 wavefronts at 128 VGPRs.
-// The overhead exists with TWO sets of constants, and they are kept apart on purpose: the scheduling estimates (launch groups, LCD_PROFILE_CHAINS) say 1 KiB
-// for the single-wavefront class and 6 KiB for the wider ones, the arena slots' count says 912 B and 6 096 B.  They decide launch groups and slot counts, so
-// making them equal would change behaviour; nobody has measured which pair is right.
-struct LdsOverhead { int wave64, wider; };
-static constexpr LdsOverhead kSchedOverhead{1 * 1024, 6 * 1024}, kSlotOverhead{912, 6096};
-static int chains_per_cu(const int lds, const int thr, const LdsOverhead &besides) { return std::max(1, std::min((160 * 1024) / (lds + (thr == 64 ? besides.wave64 : besides.wider)), 1024 / thr)); }
-// The retry policy of the POA rounds, shared by a submission and lcd_poa_batch.  chain_goes_back: does a chain with this status run again in the next round?  A
-// chain that ran out of DP cells, nodes or edges does, with larger capacities; a chain whose certified band outgrew its window does too, demoted
-// (cert_next_level) and with the round remembered.  Anything else that is not LCD_OK is the caller's error.
-static bool chain_goes_back(const int status, const PoaChain &pc, ChainRec &CR, const int round) {
-    if (status == LCD_ERR_CELLS || status == LCD_ERR_NODES || status == LCD_ERR_EDGES) return true;
-    if (status != LCD_ERR_CERT || pc.cert <= 0) return false;
-    CR.cert_fail_round = round; CR.cert_level = cert_next_level(pc); // one class up (512, 1 024 columns), then full rows
-    return true;
-}
-// ... and the capacity scale it restarts with (`scale` doubles per round with retries): a chain sent back by the certified band starts its capacity ladder in the round after
-static int retry_scale(const ChainRec &CR, const int scale) { return CR.cert_fail_round < 0 ? scale : std::max(1, scale >> (CR.cert_fail_round + 1)); }
 // uploads `sub` (already ordered so that equal classes are contiguous) and launches one kernel per class
 // (different classes go to side streams so a long wide chain does not hold back the narrow ones)
-static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_t sub_n, DevBuf &d_chains, const PoaRead *d_reads, DevBuf &d_outs, LcdScoring sc,
+static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_t sub_n, DevBuf &d_chains, const PoaRead *d_reads, DevBuf &d_outs, LcdScoring sc, const HostSwitches &sw,
                               hipStream_t *side = nullptr, hipEvent_t *sev = nullptr, DevBuf *d_gate = nullptr, PoaSpare *spare = nullptr, int busy_idx = -1, double busy_load = 0, bool noisy = false) {
     struct View { const PoaChain *p; size_t n; size_t size() const { return n; } const PoaChain &operator[](size_t i) const { return p[i]; } const PoaChain *begin() const { return p; } const PoaChain *end() const { return p + n; } } sub{sub_p, sub_n};
     HIPCHK(hipMemcpyAsync(d_chains.p, sub_p, sub_n * sizeof(PoaChain), hipMemcpyHostToDevice, st));
@@ -802,14 +497,13 @@ static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_
     // them, so once narrower workgroups are spread over the chip they wait for a CU to drain completely -- and they are the longest
     // chains.  gate[0] / gate[1] count the 1 024- / 512-thread workgroups that have started; the 512-thread launch is held
     // (lcd_gate_kernel) until target0 of the former are resident, the narrow launches until target1 of the latter are as well.
-    static const int n_streams = std::max(1, std::min(LCD_NSIDE + 1, getenv("LCD_STREAMS") ? atoi(getenv("LCD_STREAMS")) : 4));
+    const int n_streams = sw.streams; // LCD_STREAMS
     int n1024 = 0, n512 = 0; bool any_narrow = false;
     for (const PoaChain &pc : sub) { if (pc.threads >= 1024) ++n1024; else if (pc.threads >= 512) ++n512; else any_narrow = true; }
-    static const double gate_frac = getenv("LCD_GATE_FRAC") ? atof(getenv("LCD_GATE_FRAC")) : 0.80;
-    const int cap = (int)(gate_frac * g_n_cus); // leave a share of the CUs to the narrow classes from the start
+    const int cap = (int)(sw.gate_frac * g_n_cus); // leave a share of the CUs to the narrow classes from the start
     // the narrow launches are also held until all but `keep` of the 512-thread workgroups have started: chains of that class beyond one round
     // of residency (2 per CU) otherwise become the tail of the submission, two per CU on half-empty CUs (+3.5 % at 32 batches per submission)
-    const int keep512 = getenv("LCD_GATE512_KEEP") ? atoi(getenv("LCD_GATE512_KEEP")) : 2 * g_n_cus; // one round of residency
+    const int keep512 = sw.gate512_keep != kSwitchUnset ? sw.gate512_keep : 2 * g_n_cus; // one round of residency
     const int target0 = std::min(n1024, cap), target1 = std::min(n512, std::max(n512 - keep512, std::max(0, 2 * (cap - target0))));
     int *gate = nullptr;
     if (side && d_gate && n_streams > 1 && (n1024 + n512) > 0 && (any_narrow || (n1024 && n512))) {
@@ -837,8 +531,7 @@ static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_
         // (noisy reads: a K1 chain's read-base costs 11 - 12 us -- general rows, a re-sort after every read -- against 6 - 7 us in the K2 classes (LCD_PROFILE_CHAINS, SV
         //  shape); unweighted, the two groups whose single longest K1 chain runs 4 s looked like the lightest streams and the last small groups queued behind them:
         //  342 + 170 ms at the end of a 6.2 s submission while another stream had been idle for 2.5 s -- tools/timeline.py)
-        static const double k1w = getenv("LCD_NOISY_K1_WEIGHT") ? atof(getenv("LCD_NOISY_K1_WEIGHT")) : 3.0;
-        static const double k1w_from = getenv("LCD_NOISY_K1_FROM") ? atof(getenv("LCD_NOISY_K1_FROM")) : 150000.0; // read-bases (reads x longest read)
+        const double k1w = sw.noisy_k1_weight, k1w_from = sw.noisy_k1_from; // LCD_NOISY_K1_WEIGHT; LCD_NOISY_K1_FROM: read-bases (reads x longest read)
         while (j < sub.size() && chain_group_key(sub[j]) == key) { const double t = (double)sub[j].n_reads * (sub[j].max_len + 64); cost += t; tail = std::max(tail, t * (noisy && sub[j].mode == 0 && t >= k1w_from ? k1w : 1.0)); ++j; } // (the weight on a group's LONGEST chain only, and only on chains of SV-shape size: weighting the ONT shape's K1 groups -- many short chains -- as well moved that shape from 18.5 to 16.9 - 17.5 k regions/s)
         cost /= chains_per_cu(sub[i].lds_words * 4, sub[i].threads, kSchedOverhead);
         grps.push_back({i, j, cost, tail});
@@ -862,7 +555,7 @@ static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_
         // a stream runs its kernels one after the other, and a kernel lasts at least as long as its longest chain whatever else shares the chip: what adds up on a
         // stream is tail + share of the chip's work, not the work alone (two groups of a few long chains each on one stream were the whole tail of an
         // SV-shape submission: 7.8 s before the last group could start, with 0.9 s of work for 256 CUs)
-        if (getenv("LCD_GROUP_DEBUG")) fprintf(stderr, "[groups] thr %4d lds %3dK: %6zu chains, tail %.3g, cost / CUs %.3g -> stream %d (load %.3g before)\n", chain_threads(sub[grps[k].i]), sub[grps[k].i].lds_words * 4 >> 10,
+        if (sw.group_debug) fprintf(stderr, "[groups] thr %4d lds %3dK: %6zu chains, tail %.3g, cost / CUs %.3g -> stream %d (load %.3g before)\n", chain_threads(sub[grps[k].i]), sub[grps[k].i].lds_words * 4 >> 10,
                                                grps[k].j - grps[k].i, grps[k].tail, grps[k].cost / std::max(1, g_n_cus), best, load[best]);
         load[best] += grps[k].tail + grps[k].cost / std::max(1, g_n_cus);
         // stream 0 is the caller's; the others are side streams that first wait for the chain table to be uploaded
@@ -876,12 +569,12 @@ static int launch_poa_grouped(hipStream_t st, const PoaChain *sub_p, const size_
         HIPCHK(hipGetLastError());
     }
     for (int t = 1; t < ns; ++t) if (used[t]) { HIPCHK(hipEventRecord(sev[t], side[t - 1])); HIPCHK(hipStreamWaitEvent(st, sev[t], 0)); }
-    if (gate && getenv("LCD_GATE_DEBUG")) { int h[8]; hipStreamSynchronize(st); hipMemcpy(h, gate, 32, hipMemcpyDeviceToHost); fprintf(stderr, "[gate] started: %d x 1024-thread, %d x 512-thread workgroups; longest gate wait %d polls (targets %d, %d)\n", h[0], h[1], h[4], target0, target1); }
+    if (gate && sw.gate_debug) { int h[8]; hipStreamSynchronize(st); hipMemcpy(h, gate, 32, hipMemcpyDeviceToHost); fprintf(stderr, "[gate] started: %d x 1024-thread, %d x 512-thread workgroups; longest gate wait %d polls (targets %d, %d)\n", h[0], h[1], h[4], target0, target1); }
     return 0;
 }
-static int launch_poa_grouped(hipStream_t st, const std::vector<PoaChain> &sub, DevBuf &d_chains, const PoaRead *d_reads, DevBuf &d_outs, LcdScoring sc,
+static int launch_poa_grouped(hipStream_t st, const std::vector<PoaChain> &sub, DevBuf &d_chains, const PoaRead *d_reads, DevBuf &d_outs, LcdScoring sc, const HostSwitches &sw,
                               hipStream_t *side = nullptr, hipEvent_t *sev = nullptr, DevBuf *d_gate = nullptr, PoaSpare *spare = nullptr, int busy_idx = -1, double busy_load = 0, bool noisy = false) {
-    return launch_poa_grouped(st, sub.data(), sub.size(), d_chains, d_reads, d_outs, sc, side, sev, d_gate, spare, busy_idx, busy_load, noisy);
+    return launch_poa_grouped(st, sub.data(), sub.size(), d_chains, d_reads, d_outs, sc, sw, side, sev, d_gate, spare, busy_idx, busy_load, noisy);
 }
 
 // ================= one submission: the hot path of n batches run JOINTLY =================
@@ -944,36 +637,6 @@ struct InflightGuard { int dev; int n; InflightGuard(int d) : dev(d) { n = g_inf
 
 namespace { // everything of a submission but its driver is local to this file
 
-// The switches of a submission.  PER CALL: read once at the start of every submission (the tests switch them between runs inside one process); nothing
-// else on the submission path reads the environment, apart from ChainEnv (the chains' sizing) and the stage runners' own test switches.
-struct SubmitEnv {
-    bool early, solo_rl, prep_thread, anchor_seq, strings_seq, wfa_seq, time_host, mem_debug, cert_debug, retry_debug, placement, profile_chains, dbg_intervals, spare_set;
-    double spare_gb;                        // LCD_SPARE_GB where spare_set (the default depends on the kind of reads)
-    int arena_slot_cus;                     // LCD_ARENA_SLOT_CUS, 0: not set
-    const char *dump_chain, *chain_times;   // LCD_DUMP_CHAIN, LCD_CHAIN_TIMES: file names, NULL: not set
-    SubmitEnv() {
-        auto on = [](const char *name) { return getenv(name) != nullptr; };
-        early = !(getenv("LCD_EARLY") && atoi(getenv("LCD_EARLY")) == 0);
-        solo_rl = on("LCD_SOLO_RL"); prep_thread = !on("LCD_NO_PREP_THREAD"); anchor_seq = on("LCD_ANCHOR_SEQ"); strings_seq = on("LCD_STRINGS_SEQ"); wfa_seq = on("LCD_WFA_SEQ");
-        time_host = on("LCD_TIME_HOST"); mem_debug = on("LCD_MEM_DEBUG"); cert_debug = on("LCD_CERT_DEBUG"); retry_debug = on("LCD_RETRY_DEBUG");
-        placement = on("LCD_PLACEMENT"); profile_chains = on("LCD_PROFILE_CHAINS"); dbg_intervals = getenv("LCD_DBG") && (atoi(getenv("LCD_DBG")) & 32);
-        spare_set = on("LCD_SPARE_GB"); spare_gb = spare_set ? atof(getenv("LCD_SPARE_GB")) : 0.0;
-        arena_slot_cus = on("LCD_ARENA_SLOT_CUS") ? std::max(1, atoi(getenv("LCD_ARENA_SLOT_CUS"))) : 0; // test switch: far fewer slots than resident workgroups (claims must wait)
-        dump_chain = getenv("LCD_DUMP_CHAIN"); chain_times = getenv("LCD_CHAIN_TIMES");
-    }
-};
-// ONCE PER PROCESS: read by the first submission, the same for every later one
-struct ProcessEnv {
-    long long solo_min; int solo_n, n_streams; bool arena_slots, anchor_wfa_two;
-    ProcessEnv() {
-        solo_min = getenv("LCD_SOLO_MIN") ? atoll(getenv("LCD_SOLO_MIN")) : 20000;
-        solo_n = getenv("LCD_SOLO_N") ? atoi(getenv("LCD_SOLO_N")) : -1;
-        n_streams = std::max(1, std::min(LCD_NSIDE + 1, getenv("LCD_STREAMS") ? atoi(getenv("LCD_STREAMS")) : 4));
-        arena_slots = !(getenv("LCD_ARENA_SLOTS") && atoi(getenv("LCD_ARENA_SLOTS")) == 0);
-        anchor_wfa_two = !(getenv("LCD_ANCHOR_WFA_SEQ") && atoi(getenv("LCD_ANCHOR_WFA_SEQ")) != 0);
-    }
-};
-static const ProcessEnv &process_env() { static const ProcessEnv e; return e; }
 
 // the arena layout of a round (pure host work: slot pools and private arenas per launch group); round 0's is made on the preparation thread
 struct ArenaItem { uint64_t start, bytes, phys; };
@@ -1001,13 +664,12 @@ struct Submission {
     // ---- set by the constructor, constant afterwards: read by every stage on every thread ----
     lcd_batch_t **const bs; const int nb;
     lcd_batch_t *const L;                 // the leader: lends its stream, events, job tables and arenas
-    const hipStream_t st; const LcdScoring sc; const SubmitEnv env; const double t_begin;
+    const hipStream_t st; const HostSwitches env; const LcdScoring sc; const double t_begin; // env: the switches, read once at the start of the submission (lcd_switches.h)
     InflightGuard inflight;               // (alive for the whole submission)
     // The long K2 chains ahead of the anchor stage (launch_early) take a stream -- one of the runtime's four hardware queues -- for the length of the submission.  That pays
     // when this submission has the device to itself; with other submissions in flight (host lanes) the queues are what is scarce and the lanes overlap each other's
     // stages anyway: measured with two lanes of 32 batches 82.8 k instead of 100 k regions/s.  LCD_EARLY=0: never.
     const bool early_k2;
-    ChainEnv cenv;
     // chain g of the submission is chain g - chain_base[k] of batch k = chain_batch[g]; the device read table is the concatenation of the batches' tables
     std::vector<size_t> chain_base, pread_base; std::vector<int> chain_batch; size_t nC_all = 0;
     // (streams share the runtime's four hardware queues in creation order: the leader's stream and its first three side streams have one each -- a later side
@@ -1042,12 +704,11 @@ struct Submission {
     Joiner prep_thread, strings_thread;
 
     Submission(lcd_batch_t **bs_, int nb_)
-        : bs(bs_), nb(nb_), L(bs_[0]), st(L->stream), sc(scoring_of(L->opt)), t_begin(now_ms()), inflight(L->device >= 0 && L->device < LCD_MAX_DEV ? L->device : 0),
+        : bs(bs_), nb(nb_), L(bs_[0]), st(L->stream), env(HostSwitches::from_env()), sc(scoring_of(L->opt, env)), t_begin(now_ms()), inflight(L->device >= 0 && L->device < LCD_MAX_DEV ? L->device : 0),
           early_k2(inflight.n == 1 && env.early), chain_base(nb_ + 1, 0), pread_base(nb_ + 1, 0), es(L->side[2]), n_cu(g_n_cus), preads(nb_), out_rel(nb_), out_tots(nb_, 0),
           rc_all(L->h_rc_all), str_all(L->h_str_all), str_outs(L->h_str_outs), rc_base(nb_ + 1, 0), str_base(nb_ + 1, 0), str_tots(nb_, 0) {
         for (int k = 0; k < nb; ++k) { chain_base[k + 1] = chain_base[k] + bs[k]->chains.size(); pread_base[k + 1] = pread_base[k] + bs[k]->preads.size(); }
         nC_all = chain_base[nb];
-        cenv.n_chains = (long long)nC_all;
         chain_batch.resize(nC_all);
         for (int k = 0; k < nb; ++k) for (size_t g = chain_base[k]; g < chain_base[k + 1]; ++g) chain_batch[g] = k;
         which.reserve(nC_all);
@@ -1081,7 +742,7 @@ struct Submission {
             S.n_chains = (int)bs[k]->chains.size(); S.n_anchor_jobs = (int)bs[k]->anchors.size();
         }
         HIPCHK(hipEventRecord(L->ev[0], st));
-        if (process_env().arena_slots) { const int rc3 = cu_rank_table(st, &cu_rank_addr, &n_cu, env.mem_debug); if (rc3) return rc3; }
+        if (env.arena_slots) { const int rc3 = cu_rank_table(st, &cu_rank_addr, &n_cu, env.mem_debug); if (rc3) return rc3; }
         if (env.arena_slot_cus) n_cu = env.arena_slot_cus;
         return 0;
     }
@@ -1090,12 +751,12 @@ struct Submission {
     // after the join): capacities (3 ms of a 20-batch submission), the early launch of the long K2 chains (2 ms) and classes / order / arenas (1 ms) run on a helper
     // thread while the calling thread builds the anchor job tables and runs the anchor kernels -- the anchor kernels start ~5 ms earlier.  LCD_NO_PREP_THREAD=1: in line, as before
     //
-    // ---- prep_chains: long-chain cut, capacities, output blocks, early launch.  Reads: the batches' chains / preads, cenv, early_k2.  Writes: the hand-over state
+    // ---- prep_chains: long-chain cut, capacities, output blocks, early launch.  Reads: the batches' chains / preads, env, the learned levels, early_k2.  Writes: the hand-over state
     // but which / plan0 (ChainRec.solo, preads, pchains, couts, out_rel, out_tots, d_poa_out, early, early_load, reads_up); the read table, ev[8] and the long
     // chains' launches on es.  Preparation thread (LCD_NO_PREP_THREAD: calling thread), with one team ----
     int prep_chains() {
         choose_long_chains();
-        over_batches(host_team(), [&](const int k) { size_chains(k); });
+        over_batches(host_team(env), [&](const int k) { size_chains(k); });
         for (int k = 0; k < nb; ++k) {
             lcd_batch_t *b = bs[k];
             const int nC = (int)b->chains.size();
@@ -1110,9 +771,9 @@ struct Submission {
     // longest chain IS its latency, so there the cut is low; twenty batches keep the wide workgroups for their top hundred.  LCD_SOLO_RL fixes the cut instead.
     // Reads: the batches' chains / preads, early_k2.  Writes: ChainRec.solo.  Preparation thread
     void choose_long_chains() {
-        if (env.solo_rl) { for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) C.solo = -1; return; }
-        const long long solo_min = process_env().solo_min;
-        const size_t solo_n = (size_t)(process_env().solo_n >= 0 ? process_env().solo_n : std::max(1, g_n_cus / 2));
+        if (env.solo_rl_set) { for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) C.solo = -1; return; }
+        const long long solo_min = env.solo_min;
+        const size_t solo_n = (size_t)(env.solo_n >= 0 ? env.solo_n : std::max(1, g_n_cus / 2));
         std::vector<long long> rls;
         for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) {
             int maxl = 0; for (size_t q = 0; q < C.members.size(); ++q) maxl = std::max(maxl, bs[k]->preads[C.read0 + q].len);
@@ -1126,7 +787,7 @@ struct Submission {
         //  which wait for their anchors, then stay in the single-wavefront class instead of forming a fourth launch group that would queue behind another)
         for (int k = 0; k < nb; ++k) for (ChainRec &C : bs[k]->chains) C.solo = rls[q++] >= cut && (C.mode == 1 || !early_k2) ? 1 : 0; // (noisy reads have no certified-band K2 chains, but their long K1 chains are no faster in the wide workgroup: SV shape 1 608 with them there, 1 680 without)
     }
-    // capacities, class and output offsets of a batch's chains (independent of the other batches).  Reads: batch k, cenv.  Writes: preads[k], out_rel[k], out_tots[k],
+    // capacities, class and output offsets of a batch's chains (independent of the other batches).  Reads: batch k, env, the learned levels.  Writes: preads[k], out_rel[k], out_tots[k],
     // batch k's couts / pchains / cert fields.  Team of prep_chains
     void size_chains(const int k) {
         lcd_batch_t *b = bs[k];
@@ -1136,9 +797,10 @@ struct Submission {
         b->pchains.assign(nC, PoaChain());
         out_rel[k].resize(nC);
         uint64_t out_tot = 0;
+        const PlanHints hints = learned_hints();
         for (int c = 0; c < nC; ++c) {
             b->chains[c].cert_level = -1; b->chains[c].cert_fail_round = -1; // (nothing about the certified band is remembered from an earlier run of the same batch)
-            chain_caps(b->opt, b->chains[c], preads[k], 1, b->pchains[c], cenv);
+            chain_caps(b->opt, b->chains[c], preads[k], 1, (long long)nC_all, env, hints, b->pchains[c]);
             out_rel[k][c] = out_tot; out_tot += lcd_align_up(poa_out_bytes(b->pchains[c].node_cap, b->pchains[c].n_reads), 256);
         }
         out_tots[k] = out_tot;
@@ -1171,7 +833,7 @@ struct Submission {
         if (!reads_up || L->d_early_arena.ensure(tot_e, 3) || L->d_chains_early.ensure(early.size() * sizeof(PoaChain)) ||
             L->d_poa_outs_early.ensure(early.size() * sizeof(PoaChainOut))) { (void)hipGetLastError(); early.clear(); return 0; } // (no memory for it: they start with the others)
         for (size_t i = 0; i < early.size(); ++i) { PoaChain &pc = chain(early[i]); pc.ws_off += L->d_early_arena.addr(); sub_e[i] = pc; sub_e[i].read0 += (int)pread_base[chain_batch[early[i]]]; }
-        { const int rc2 = launch_poa_grouped(es, sub_e, L->d_chains_early, (const PoaRead *)L->d_preads.p, L->d_poa_outs_early, sc); if (rc2) return rc2; }
+        { const int rc2 = launch_poa_grouped(es, sub_e, L->d_chains_early, (const PoaRead *)L->d_preads.p, L->d_poa_outs_early, sc, env); if (rc2) return rc2; }
         if (env.time_host) fprintf(stderr, "[host]   %zu long K2 chains launched %.1f ms after the start (%.2f GB of arenas)\n", early.size(), now_ms() - t_begin, tot_e / 1e9);
         return 0;
     }
@@ -1192,7 +854,7 @@ struct Submission {
         // No more launch groups than streams: a stream runs its kernels one after the other, so a fifth group starts only when some other group's LAST chain has
         // ended -- with the bulk of the work (40 000 short chains in the smallest LDS bucket) queued behind a group of a few hundred long chains the chip idled for a
         // third of the stage.  The single-wavefront group with the fewest chains moves up into the next larger LDS bucket in use (a bigger pool is always valid).
-        for (const int n_streams = process_env().n_streams;;) {
+        for (const int n_streams = env.streams;;) {
             // (only SMALL groups move -- less than 8 % of the submission's CU-time: a bigger pool means fewer chains per CU, and the bulk of the work must keep the
             //  occupancy of its own bucket; noisy-read submissions have five wide classes besides, there is no getting down to four groups)
             std::map<long long, std::pair<size_t, double>> cnt;
@@ -1229,7 +891,7 @@ struct Submission {
     // workgroups, not with the number of chains in flight.
     // Reads: which (ordered), P.need[i] for which[i], n_cu, cu_rank_addr.  Writes: P, the chains' ws_off (relative to P) and slot fields.  The thread of its caller
     void segment_arenas(ArenaPlan &P) {
-        const bool use_slots = process_env().arena_slots;
+        const bool use_slots = env.arena_slots;
         P.tot = 0; P.flag_ints = 0; P.n_pooled = P.n_pools = 0; P.private_bytes = P.pool_bytes = 0; P.items.clear(); P.item_of.assign(which.size(), 0);
         for (size_t i = 0; i < which.size();) {
             const long long key = chain_group_key(chain(which[i]));
@@ -1275,8 +937,8 @@ struct Submission {
     // ---- the preparation thread: prep_chains, then prepare_round0 when the submission is large enough to pay for it.  start_prep returns prep_chains' own code
     // when it ran in line (LCD_NO_PREP_THREAD).  A helper thread selects the device first and hands its error text over at the join.  Calling thread ----
     int start_prep() {
-        order_async = nC_all >= 2048 && env.prep_thread;
-        if (!env.prep_thread) return prep_chains();
+        order_async = nC_all >= 2048 && !env.no_prep_thread;
+        if (env.no_prep_thread) return prep_chains();
         const int dev_here = cur_device();
         prep_thread.t = std::thread([this, dev_here]() {
             if (hipSetDevice(dev_here) != hipSuccess) { prep_rc = -1; prep_err = "hipSetDevice failed on the preparation thread"; return; }
@@ -1302,7 +964,7 @@ struct Submission {
             ej_base[k] = ej.size(); wj_base[k] = wj.size();
             if (b->anchors.empty()) continue;
             for (EdJob j : b->ed_jobs) { j.q_off += in_base; j.t_off += in_base; ej.push_back(j); }
-            for (WfaJob j : b->wfa_jobs) { j.p_off += in_base; j.t_off += in_base; j.s_cap = wfa_default_scap(j.plen, j.tlen, true); wj.push_back(j); } // (the hint may have risen since the region was added)
+            for (WfaJob j : b->wfa_jobs) { j.p_off += in_base; j.t_off += in_base; j.s_cap = wfa_default_scap(j.plen, j.tlen, g_wfa_hint.load()); wj.push_back(j); } // (the hint may have risen since the region was added)
         }
         ej_base[nb] = ej.size(); wj_base[nb] = wj.size();
         if (ej.empty() && wj.empty()) return 0;
@@ -1322,8 +984,8 @@ struct Submission {
         if (th && !side_by_side) { hipStreamSynchronize(st); fprintf(stderr, "[host]   anchors: edlib stage done after %.1f ms\n", now_ms() - t_begin); }
         // (K3's class launches -- each as long as its longest job -- on the leader's stream and the second side stream: the first has K4, the third the long chains;
         //  LCD_ANCHOR_WFA_SEQ=1: one after the other on the leader's stream, as before)
-        const bool k3_two = process_env().anchor_wfa_two;
-        rc = run_wfa_stage(st, wj, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, wo, sc, nullptr, true, k3_two && side_by_side && L->side[1] ? L->side + 1 : nullptr, L->sev, k3_two && side_by_side && L->side[1] ? 1 : 0);
+        const bool k3_two = !env.anchor_wfa_seq;
+        rc = run_wfa_stage(st, wj, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, wo, sc, env, nullptr, true, k3_two && side_by_side && L->side[1] ? L->side + 1 : nullptr, L->sev, k3_two && side_by_side && L->side[1] ? 1 : 0);
         if (rc) return rc;
         if (side_by_side) { HIPCHK(hipMemcpyAsync(eo.data(), L->d_ed_outs.p, eo.size() * sizeof(EdOut), hipMemcpyDeviceToHost, ks)); HIPCHK(hipStreamSynchronize(ks)); }
         HIPCHK(hipStreamSynchronize(st));
@@ -1429,12 +1091,13 @@ struct Submission {
         L->h_sub_pin.resize(which.size() * sizeof(PoaChain));
         R.sub = (PoaChain *)L->h_sub_pin.data(); R.sub_n = which.size();
         if (!planned) {
+            const PlanHints hints = learned_hints(); // (as the round before left them)
             for (size_t i = 0; i < which.size(); ++i) {
                 const int k = chain_batch[which[i]]; const size_t c = which[i] - chain_base[k];
                 PoaChain &pc = chain(which[i]);
                 if (R.round) {
                     const int old_cap = pc.node_cap;
-                    chain_caps(bs[k]->opt, rec(which[i]), preads[k], retry_scale(rec(which[i]), scale), pc, cenv);
+                    chain_caps(bs[k]->opt, rec(which[i]), preads[k], retry_scale(rec(which[i]), scale), (long long)nC_all, env, hints, pc);
                     if (pc.node_cap > old_cap) { // the chain's output block (cons + MSA rows of node_cap columns) grows with it: a fresh block
                         lcd_batch_t *b = bs[k];
                         if (b->retry_out_used == b->retry_out.size()) b->retry_out.emplace_back(new DevBuf());
@@ -1476,7 +1139,7 @@ struct Submission {
                 it.phys = ch[k]->addr() + off; off += it.bytes; left -= it.bytes;
             }
         }
-        par_chunks(which.size(), host_team(), 4096, [&](const size_t lo, const size_t hi, int) { for (size_t i = lo; i < hi; ++i) {
+        par_chunks(which.size(), host_team(env), 4096, [&](const size_t lo, const size_t hi, int) { for (size_t i = lo; i < hi; ++i) {
             PoaChain &pc = chain(which[i]);
             pc.ws_off = P.items[P.item_of[i]].phys + (pc.ws_off - P.items[P.item_of[i]].start);
             if (pc.slot_flags) pc.slot_flags = L->d_slot_flags.addr() + (pc.slot_flags - 1) * 4;
@@ -1512,7 +1175,7 @@ struct Submission {
         const int round = R.round; const size_t sub_n = R.sub_n;
         if (env.time_host) fprintf(stderr, "[host] POA stage: %.1f ms of host work before the launches of round %d\n", now_ms() - tp0, round);
         HIPCHK(hipEventRecord(L->ev[6], st));
-        { int rc2 = launch_poa_grouped(st, R.sub, sub_n, L->d_chains, (const PoaRead *)L->d_preads.p, L->d_poa_outs, sc, L->side, L->sev, &L->d_gate, R.d_spare, round == 0 && !early.empty() ? 3 : -1, early_load, L->opt.is_ont != 0); if (rc2) return rc2; }
+        { int rc2 = launch_poa_grouped(st, R.sub, sub_n, L->d_chains, (const PoaRead *)L->d_preads.p, L->d_poa_outs, sc, env, L->side, L->sev, &L->d_gate, R.d_spare, round == 0 && !early.empty() ? 3 : -1, early_load, L->opt.is_ont != 0); if (rc2) return rc2; }
         HIPCHK(hipEventRecord(L->ev[7], st));
         L->h_tmp_pin.resize((sub_n + (round == 0 ? early.size() : 0)) * sizeof(PoaChainOut)); // (with room for the early chains' records: appending them to a vector re-allocated 9 MB with the GPU idle)
         R.tmp = (PoaChainOut *)L->h_tmp_pin.data();
@@ -1544,7 +1207,7 @@ struct Submission {
         //  with the GPU idle; the chains that did not end with LCD_OK are few and are looked at one by one below)
         std::vector<size_t> flagged;
         {
-            constexpr int NTH = 32; const int nth_r = host_team();
+            constexpr int NTH = 32; const int nth_r = host_team(env);
             std::vector<size_t> fl[NTH];
             par_chunks(which.size(), nth_r, 2048, [&](const size_t lo, const size_t hi, const int t) {
                 for (size_t i = lo; i < hi; ++i) {
@@ -1639,7 +1302,7 @@ struct Submission {
     // the joint ref<->cons job table.  Reads: the batches' couts / pchains.  Writes: the batches' rc tables and region statistics (teams), rc_base, rc_all; ev[3] on st.
     // Calling thread, with one team
     int refcons_jobs() {
-        over_batches(2 * host_team(), [&](const int k) { build_jobs(k, 1); });
+        over_batches(2 * host_team(env), [&](const int k) { build_jobs(k, 1); });
         for (int k = 0; k < nb; ++k) rc_base[k + 1] = rc_base[k] + bs[k]->rc_jobs.size();
         if (rc_all.capacity() < rc_base[nb]) rc_all.reserve(rc_base[nb] + rc_base[nb] / 4 + 64); // (headroom: the next submission's tables are a few per cent larger or smaller)
         rc_all.resize(rc_base[nb]);
@@ -1652,7 +1315,7 @@ struct Submission {
     // host threads, the joint table sized once and filled by the same threads, the batches' output blocks given their device memory in between.
     // Reads: the batches' couts / pchains / regs.  Writes: the batches' str tables, d_final, final_bytes, str_tots, str_base, str_all.  The thread of strings_stage, with two teams
     int build_string_tables() {
-        over_batches(2 * host_team(), [&](const int k) { build_jobs(k, 2); });
+        over_batches(2 * host_team(env), [&](const int k) { build_jobs(k, 2); });
         for (int k = 0; k < nb; ++k) {
             lcd_batch_t *b = bs[k]; const uint64_t str_tot = str_tots[k];
             if (!b->str_jobs.empty() && b->d_final.ensure(str_tot)) return -11;
@@ -1661,7 +1324,7 @@ struct Submission {
         }
         if (str_all.capacity() < str_base[nb]) str_all.reserve(str_base[nb] + str_base[nb] / 4 + 64);
         str_all.resize(str_base[nb]);
-        over_batches(2 * host_team(), [&](const int k) {
+        over_batches(2 * host_team(env), [&](const int k) {
             lcd_batch_t *b = bs[k];
             const uint64_t fin = b->d_final.addr();
             for (auto &j : b->str_jobs) j.out_off += fin;
@@ -1706,7 +1369,7 @@ struct Submission {
     int wfa_stage() {
         int wret = 0;
         std::vector<WfaOut> rc_outs;
-        int rc = run_wfa_stage(st, rc_all, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, rc_outs, sc, &wret, false, env.wfa_seq ? nullptr : L->side, L->sev, 3); // (the POA streams are idle by now)
+        int rc = run_wfa_stage(st, rc_all, L->d_wfa_jobs, L->d_poa_arena, L->d_wfa_out, L->d_wfa_outs, rc_outs, sc, env, &wret, false, env.wfa_seq ? nullptr : L->side, L->sev, 3); // (the POA streams are idle by now)
         if (rc) return rc;
         for (int k = 0; k < nb; ++k) {
             lcd_batch_t *b = bs[k];
@@ -1778,7 +1441,7 @@ struct Submission {
         }
         if (!sj2.empty()) {
             std::vector<WfaOut> so2;
-            int rc2 = run_wfa_stage(st, sj2, L->d_wfa_jobs, L->d_poa_arena, L->d_seg_out, L->d_wfa_outs, so2, sc, nullptr);
+            int rc2 = run_wfa_stage(st, sj2, L->d_wfa_jobs, L->d_poa_arena, L->d_seg_out, L->d_wfa_outs, so2, sc, env, nullptr);
             if (rc2) return rc2;
             sres.resize(sj2.size());
             for (size_t q = 0; q < sj2.size(); ++q) { sres[q].rows_off = sj2[q].out_off; sres[q].aln_len = so2[q].aln_len; sres[q].row_stride = sj2[q].plen + sj2[q].tlen + 1; }
@@ -2032,7 +1695,7 @@ static void report_profile_chains(const Submission &S) {
             tt += o.t_total; td += o.t_dp; tb += o.t_bt; tg += o.t_graph; to += o.t_out; ts += o.t_sub; tbp += o.t_bp; tad += o.t_add; tso += o.t_sort; tse += o.t_setup; tpl += o.t_plan; if (o.t_total >= mx) { mx = o.t_total; mxc = g; } }
         if (!cnt) continue;
         fprintf(stderr, "[lcd] class %4d: row plan %.3e  graph update %.3e  re-sort %.3e  row setup %.3e  bound arrays %.3e\n", cls, (double)tbp, (double)tad, (double)tso, (double)tse, (double)tpl);
-        if (S.env.dbg_intervals) { // reads of certified-band chains by their widest interval (the t_setup slot carries five 12-bit counters per chain)
+        if ((S.env.dbg & 32)) { // reads of certified-band chains by their widest interval (the t_setup slot carries five 12-bit counters per chain)
             unsigned long long h[5] = {0, 0, 0, 0, 0};
             for (size_t g = 0; g < nC_all; ++g) { if (chain_threads(S.chain(g)) != cls || !S.chain(g).cert) continue; const unsigned long long v = S.out(g).t_setup; for (int q = 0; q < 5; ++q) h[q] += (v >> (12 * q)) & 4095; }
             fprintf(stderr, "[lcd] class %4d: certified-band reads by widest interval <= 60 / 124 / 188 / 256 / wider: %llu / %llu / %llu / %llu / %llu\n", cls, h[0], h[1], h[2], h[3], h[4]);
@@ -2044,7 +1707,7 @@ static void report_profile_chains(const Submission &S) {
                 pm.n_reads, pm.max_len, o.n_node, (double)o.t_total, (double)o.t_dp, (double)o.t_bt, (double)o.t_graph, (double)o.t_sub, (double)o.t_out, o.cells);
         fprintf(stderr, "[lcd]     of its dp: plan-window refreshes %.3e  mailbox polls %.3e (one wavefront)\n", (double)o.t_plan, (double)o.t_poll);
         fprintf(stderr, "[lcd]     row plan %.3e  graph update %.3e  re-sort %.3e  row setup %.3e\n", (double)o.t_bp, (double)o.t_add, (double)o.t_sort, (double)o.t_setup);
-        if (S.env.dbg_intervals) fprintf(stderr, "[lcd]     reads by widest interval <=60 / <=124 / <=188 / <=380 / wider: %llu %llu %llu %llu %llu\n", (unsigned long long)(o.t_setup & 4095), (unsigned long long)((o.t_setup >> 12) & 4095), (unsigned long long)((o.t_setup >> 24) & 4095), (unsigned long long)((o.t_setup >> 36) & 4095), (unsigned long long)((o.t_setup >> 48) & 4095));
+        if ((S.env.dbg & 32)) fprintf(stderr, "[lcd]     reads by widest interval <=60 / <=124 / <=188 / <=380 / wider: %llu %llu %llu %llu %llu\n", (unsigned long long)(o.t_setup & 4095), (unsigned long long)((o.t_setup >> 12) & 4095), (unsigned long long)((o.t_setup >> 24) & 4095), (unsigned long long)((o.t_setup >> 36) & 4095), (unsigned long long)((o.t_setup >> 48) & 4095));
     }
 }
 
@@ -2391,7 +2054,7 @@ int lcd_batch_region_results_arena(lcd_batch_t *b, lcd_region_result_t **results
     // pass 1: bytes per region (a dry run of the same code with a counting allocator that returns a scratch block)
     std::vector<uint64_t> need(nr, 0);
     auto run = [&](const bool dry, uint8_t *base, lcd_region_result_t *tab) {
-        const int nth_max = host_arena_threads(); // (read per call; a caller that materialises several batches at once on its own threads wants fewer per batch)
+        const int nth_max = host_arena_threads(HostSwitches::from_env()); // (read per call; a caller that materialises several batches at once on its own threads wants fewer per batch)
         const int nth = dry ? 1 : (int)std::max<size_t>(1, std::min<size_t>((size_t)nth_max, nr / 64 + 1)); // (the sizing pass is a few additions per row)
         std::atomic<size_t> next{0};
         auto work = [&]() {
@@ -2632,7 +2295,7 @@ static int edlib_batch_mode(int mode, int n, const uint8_t *pool, uint64_t pool_
 uint64_t lcd_wfa_arena_bytes(int plen, int tlen, int score_bound, int b, int q, int e, int q2, int e2) {
     WfaJob j; memset(&j, 0, sizeof(j)); j.plen = plen; j.tlen = tlen;
     LcdScoring sc; sc.dbg = 0; sc.wd_s = 0; sc.match = 0; sc.mismatch = b; sc.o1 = q; sc.e1 = e; sc.o2 = q2; sc.e2 = e2;
-    wfa_plan(j, sc, score_bound);
+    wfa_plan(j, sc, score_bound, HostSwitches::from_env());
     return j.ws_bytes;
 }
 
@@ -2640,6 +2303,7 @@ int lcd_wfa_batch(int n, const uint8_t *pool, uint64_t pool_len, const uint64_t 
                   const int *gap_aln, int b, int q, int e, int q2, int e2, int want, int *score, uint32_t *cigars, int cigar_stride, int *n_cigar,
                   uint8_t *rows, int row_stride, int *aln_len) {
     if (ensure_init()) return -1;
+    const HostSwitches sw = HostSwitches::from_env();
     StreamGuard st; if (st.create()) return -10;
     DevBuf d_pool, d_jobs, d_arena, d_out, d_outs;
     if (d_pool.ensure(pool_len + 64)) return -11;
@@ -2652,7 +2316,7 @@ int lcd_wfa_batch(int n, const uint8_t *pool, uint64_t pool_len, const uint64_t 
     }
     LcdScoring sc; sc.dbg = 0; sc.wd_s = 0; sc.match = 0; sc.mismatch = b; sc.o1 = q; sc.e1 = e; sc.o2 = q2; sc.e2 = e2;
     std::vector<WfaOut> outs;
-    int rc = run_wfa_stage(st, jobs, d_jobs, d_arena, d_out, d_outs, outs, sc, nullptr);
+    int rc = run_wfa_stage(st, jobs, d_jobs, d_arena, d_out, d_outs, outs, sc, sw, nullptr);
     if (rc) return rc;
     for (int i = 0; i < n; ++i) {
         const uint64_t maxl = (uint64_t)plen[i] + tlen[i] + 1;
@@ -2734,12 +2398,13 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
         PoaRead &r = preads[i]; r.seq_off = d_pool.addr() + seq_off[i]; r.len = len[i]; r.skip = skip ? skip[i] : 0;
         r.ref_beg = anchors[4 * i]; r.ref_end = anchors[4 * i + 1]; r.read_beg = anchors[4 * i + 2]; r.read_end = anchors[4 * i + 3];
     }
-    const ChainEnv cenv;
+    const HostSwitches sw = HostSwitches::from_env(); const long long n_chains_unknown = 1ll << 40; // (no submission around these chains: the long ones take the four-wavefront pipeline, as in a crowded one)
+    const PlanHints hints = learned_hints();
     std::vector<ChainRec> crec(n_chains); std::vector<PoaChain> pch(n_chains); std::vector<uint64_t> out_rel(n_chains);
     uint64_t out_tot = 0;
     for (int c = 0; c < n_chains; ++c) {
         crec[c].mode = mode[c]; crec[c].read0 = chain_read0[c]; crec[c].members.resize(chain_n_reads[c]);
-        chain_caps(*opt, crec[c], preads, 1, pch[c], cenv);
+        chain_caps(*opt, crec[c], preads, 1, n_chains_unknown, sw, hints, pch[c]);
         out_rel[c] = out_tot; out_tot += lcd_align_up(poa_out_bytes(pch[c].node_cap, pch[c].n_reads), 256);
     }
     if (d_out.ensure(out_tot) || d_reads.ensure(preads.size() * sizeof(PoaRead) + 16) || d_chains.ensure(n_chains * sizeof(PoaChain)) || d_outs.ensure(n_chains * sizeof(PoaChainOut))) return -11;
@@ -2749,7 +2414,7 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
     for (int c = 0; c < n_chains; ++c) which[c] = c;
     int scale = 1;
     std::vector<std::unique_ptr<DevBuf>> retry_out;
-    const LcdScoring sc = scoring_of(*opt);
+    const LcdScoring sc = scoring_of(*opt, sw);
     for (int round = 0; round < 12 && !which.empty(); ++round) {
         uint64_t tot = 0; std::vector<PoaChain> sub(which.size());
         for (size_t i = 0; i < which.size(); ++i) {
@@ -2757,7 +2422,7 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
             if (!round) pc.out_off = d_out.addr() + out_rel[which[i]];
             else {
                 const int old_cap = pc.node_cap; const uint64_t keep = pc.out_off;
-                chain_caps(*opt, crec[which[i]], preads, retry_scale(crec[which[i]], scale), pc, cenv);
+                chain_caps(*opt, crec[which[i]], preads, retry_scale(crec[which[i]], scale), n_chains_unknown, sw, learned_hints(), pc);
                 pc.out_off = keep;
                 if (pc.node_cap > old_cap) { // larger graph capacity -> larger output block
                     retry_out.emplace_back(new DevBuf());
@@ -2770,7 +2435,7 @@ int lcd_poa_batch(const lcd_opt_t *opt, int n_chains, const int *mode, const int
         }
         if (d_arena.ensure(tot)) return -11;
         for (size_t i = 0; i < which.size(); ++i) { pch[which[i]].ws_off += d_arena.addr(); sub[i] = pch[which[i]]; }
-        { int rc2 = launch_poa_grouped(st, sub, d_chains, (const PoaRead *)d_reads.p, d_outs, sc); if (rc2) return rc2; }
+        { int rc2 = launch_poa_grouped(st, sub, d_chains, (const PoaRead *)d_reads.p, d_outs, sc, sw); if (rc2) return rc2; }
         std::vector<PoaChainOut> tmp(sub.size());
         HIPCHK(hipMemcpyAsync(tmp.data(), d_outs.p, sub.size() * sizeof(PoaChainOut), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
@@ -2830,6 +2495,31 @@ int lcd_batch_add_planned(lcd_batch_t *b, const lcd_chunk_t *c, const lcd_pass_p
         ++added;
     }
     return added;
+}
+
+// ---- the planner's probes (declared in lcd_host_internal.h only; tests/test_chain_plan.py): what chain_caps / wfa_plan decide for one chain / job, with the
+// switches read from the environment at this call.  No device is touched ----
+int lcd_plan_chain_probe(const lcd_opt_t *opt, int mode, int n_reads, const int *read_len, int scale, int cert_level, int solo, long long n_chains, const int *hints, int64_t *out) {
+    std::vector<PoaRead> preads(n_reads);
+    for (int i = 0; i < n_reads; ++i) { memset(&preads[i], 0, sizeof(PoaRead)); preads[i].len = read_len[i]; }
+    ChainRec C; C.region = 0; C.clu = 0; C.mode = mode; C.members.resize(n_reads); C.read0 = 0; C.cert_level = cert_level; C.solo = solo;
+    PlanHints h = learned_hints();
+    if (hints) { h.cell[0] = hints[0]; h.cell[1] = hints[1]; h.node = hints[2]; }
+    PoaChain pc; memset(&pc, 0, sizeof(pc));
+    chain_caps(*opt, C, preads, scale, n_chains, HostSwitches::from_env(), h, pc);
+    out[0] = pc.threads; out[1] = pc.wmax; out[2] = (int64_t)pc.lds_words * 4; out[3] = pc.ring_k; out[4] = pc.ring16; out[5] = pc.solo; out[6] = pc.cert;
+    out[7] = pc.node_cap; out[8] = pc.edge_cap; out[9] = (int64_t)pc.cell_cap; out[10] = pc.spill_x; out[11] = pc.min_w;
+    return 0;
+}
+// (s_want <= 0: wfa_default_scap, of an anchor-stage job where anchor != 0; wfa_hint < 0: the learned level; scoring: mismatch, o1, e1, o2, e2)
+int lcd_plan_wfa_probe(int plen, int tlen, long long s_want, int anchor, int wfa_hint, const int *scoring, int64_t *out) {
+    const HostSwitches sw = HostSwitches::from_env();
+    WfaJob j; memset(&j, 0, sizeof(j)); j.plen = plen; j.tlen = tlen;
+    LcdScoring sc; memset(&sc, 0, sizeof(sc)); sc.mismatch = scoring[0]; sc.o1 = scoring[1]; sc.e1 = scoring[2]; sc.o2 = scoring[3]; sc.e2 = scoring[4];
+    if (s_want <= 0) s_want = wfa_default_scap(plen, tlen, !anchor ? 0 : wfa_hint >= 0 ? wfa_hint : learned_hints().wfa);
+    wfa_plan(j, sc, s_want, sw);
+    out[0] = j.lds; out[1] = j.s_cap; out[2] = j.blk_rows; out[3] = j.n_ckpt; out[4] = (int64_t)j.ws_bytes; out[5] = wfa_class(j, sc, sw);
+    return 0;
 }
 
 } // extern "C"

@@ -19,6 +19,7 @@
 #include "lcd_kernels.h"
 #include "lcd_types.h"
 #include "lcd_io_internal.h"
+#include "lcd_plan.h" // the planner of lcd_plan.cpp (ChainRec, PlanHints, chain_caps, wfa_plan, ...) and, through it, lcd_switches.h (HostSwitches)
 
 namespace lcd_internal __attribute__((visibility("hidden"))) {
 
@@ -82,7 +83,7 @@ struct StagePut {
 };
 
 inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// host threads per team of the submission's short parallel loops (capacities, job tables, records, plans).  LCD_HOST_TEAM, read per call: a caller whose own
+// host threads per team of the submission's short parallel loops (capacities, job tables, records, plans).  LCD_HOST_TEAM (HostSwitches.host_team): a caller whose own
 // threads are busy beside the submission -- bench.py's PCIe-inclusive pipeline on a box whose cgroup allows 16 CPUs -- asks for fewer; a team that overruns the
 // quota freezes every thread of the process, the submitter included, until the next period
 // CPUs this process may use: its affinity mask, cut by the cgroup's CPU quota (v2 cpu.max, v1 cpu.cfs_quota_us / cpu.cfs_period_us) -- a container with 128 visible
@@ -113,15 +114,13 @@ inline int host_local_world() {
     return w < 1 ? 1 : w;
 }
 // With N ranks on one host every rank runs these teams at the same moments (the ranks step together): the default is the host's CPUs divided by the ranks, at most 8.
-inline int host_team() {
-    const char *e = getenv("LCD_HOST_TEAM");
-    const int v = e ? atoi(e) : std::min(8, std::max(1, host_cpus() / host_local_world()));
+inline int host_team(const HostSwitches &sw) {
+    const int v = sw.host_team != kSwitchUnset ? sw.host_team : std::min(8, std::max(1, host_cpus() / host_local_world()));
     return v < 1 ? 1 : v > 32 ? 32 : v;
 }
 // (threads that lay results out on the host, lcd_batch_results_arena: LCD_ARENA_THREADS, default 16 -- or the rank's share of the host's CPUs)
-inline int host_arena_threads() {
-    const char *e = getenv("LCD_ARENA_THREADS");
-    return e ? std::max(1, atoi(e)) : std::min(16, std::max(1, host_cpus() / host_local_world()));
+inline int host_arena_threads(const HostSwitches &sw) {
+    return sw.arena_threads != kSwitchUnset ? std::max(1, sw.arena_threads) : std::min(16, std::max(1, host_cpus() / host_local_world()));
 }
 // a loop over [0, n) cut into chunks taken by up to `max_threads` host threads (the calling thread is one of them); f(lo, hi, thread index)
 template <class F> static void par_chunks(const size_t n, const int max_threads, const size_t chunk, F f) {
@@ -134,22 +133,13 @@ template <class F> static void par_chunks(const size_t n, const int max_threads,
     work(0);
     for (auto &t : ths) t.join();
 }
-inline LcdScoring scoring_of(const lcd_opt_t &o) { LcdScoring s; s.match = o.match; s.mismatch = o.mismatch; s.o1 = o.gap_open1; s.e1 = o.gap_ext1; s.o2 = o.gap_open2; s.e2 = o.gap_ext2; s.dbg = getenv("LCD_DBG") ? atoi(getenv("LCD_DBG")) : 0; s.wd_s = getenv("LCD_WATCHDOG_S") ? atoi(getenv("LCD_WATCHDOG_S")) : 0; return s; }
+inline LcdScoring scoring_of(const lcd_opt_t &o, const HostSwitches &sw) { LcdScoring s; s.match = o.match; s.mismatch = o.mismatch; s.o1 = o.gap_open1; s.e1 = o.gap_ext1; s.o2 = o.gap_open2; s.e2 = o.gap_ext2; s.dbg = sw.dbg; s.wd_s = sw.watchdog_s; return s; }
 struct NIv { uint64_t x; long long en; int label; }; // x: the interval index's sort key (contig 0: the start)
 
 // ---- the records of a region batch (lcd_host.cpp) ----
 struct RegRead { // one read of a region, in sorted order after add
     int id, len, cover, hap; int64_t ps; uint64_t off; double err;
     int rb = -1, re = -2; // read_reg_beg / read_reg_end of collect_noisy_read_info (chunk-view entry only)
-};
-struct ChainRec {
-    int region, clu;              // clu: hap-1 for K1, 0 for K2 (clusters come out of the kernel)
-    int mode;
-    std::vector<int> members;     // indices into the region's sorted read list
-    int read0;                    // first PoaRead
-    int cert_fail_round = -1;     // K2: the last round in which the certified band did not fit its class's window (the chain then moves one class up)
-    int solo = -1;                // -1: by the fixed threshold (LCD_SOLO_RL); 0 / 1: decided for the submission at hand (lcd_host.cpp choose_long_chains: the longest chains of what is in flight)
-    int cert_level = -1;          // -1: not chosen yet; 1: certified band in the single-wavefront rows; 2: in the systolic rows of the class the reads' length asks for (noisy reads); 0: full rows
 };
 struct AnchorRec {
     int pread;                    // index into preads
@@ -193,11 +183,17 @@ struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint6
 } // namespace lcd_internal
 
 extern "C" void lcd_account_device_bytes(int device, long long delta); // the ledger's entry for buffers allocated outside DevBuf (lcd_io.cpp's inflated streams); exported, not in the public header
+// the planner's probes (lcd_host.cpp; exported, not in the public header): the decisions of lcd_plan.cpp for one chain / one WFA job, without a device.
+// out[12]: threads, wmax, lds_bytes, ring_k, ring16, solo, cert, node_cap, edge_cap, cell_cap, spill_x, min_w.  cert_level / solo: -1 automatic; hints: cell K1, cell K2, node (NULL: the learned ones)
+extern "C" int lcd_plan_chain_probe(const lcd_opt_t *opt, int mode, int n_reads, const int *read_len, int scale, int cert_level, int solo, long long n_chains, const int *hints, int64_t *out);
+// out[6]: lds, s_cap, blk_rows, n_ckpt, ws_bytes, class
+extern "C" int lcd_plan_wfa_probe(int plen, int tlen, long long s_want, int anchor, int wfa_hint, const int *scoring, int64_t *out);
 
 // lcd_batch_s and lcd_chunk_s are the global types behind the public handles: their members name the types above
 using lcd_internal::RegRead; using lcd_internal::ChainRec; using lcd_internal::AnchorRec; using lcd_internal::RegionRec; using lcd_internal::VarRegionRec;
 using lcd_internal::DevBuf; using lcd_internal::PinnedBuf;
 #define LCD_NSIDE 12
+static_assert(lcd_internal::kMaxStreams == LCD_NSIDE + 1, "LCD_STREAMS is clamped to the caller's stream plus the side streams of a batch");
 struct lcd_batch_s {
     lcd_opt_t opt;
     int device = 0;                      // every entry point on this batch selects it (HIP's current device is per host thread)

@@ -570,7 +570,7 @@ lcd_inflated_t *lcd_bgzf_inflate_dev(const uint8_t *file, size_t n, int verify_c
     IOHIP(hipMemcpyAsync(h->d_in, file, n, hipMemcpyHostToDevice, st));
     IOHIP(hipMemcpyAsync(h->d_jobs, jobs.data(), jobs.size() * sizeof(InflateJobH), hipMemcpyHostToDevice, st));
     IOHIP(hipEventRecord(ev[1], st));
-    const bool timers = getenv("LCD_INFLATE_PROFILE") != nullptr;
+    const bool timers = lcd_internal::HostSwitches::from_env().inflate_profile;
     lcd_launch_inflate(h->d_jobs, h->d_outs, (int)blks.size(), verify_crc, timers ? 1 : 0, st);
     IOHIP(hipGetLastError());
     IOHIP(hipEventRecord(ev[2], st));

@@ -55,7 +55,7 @@ std::atomic<long long> g_alloc_events{0}; // hipMalloc calls of the grow-only bu
 long long dev_budget(int d) {
     std::call_once(g_budget_once[d], [d] {
         size_t fr = 0, tot = 0;
-        g_dev_budget[d] = (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) ? (long long)((double)tot * (getenv("LCD_MEM_FRACTION") ? atof(getenv("LCD_MEM_FRACTION")) : 0.92)) : (1ll << 62);
+        g_dev_budget[d] = (hipMemGetInfo(&fr, &tot) == hipSuccess && tot > 0) ? (long long)((double)tot * HostSwitches::from_env().mem_fraction) : (1ll << 62);
         (void)hipGetLastError();
     });
     return g_dev_budget[d].load();
@@ -74,7 +74,7 @@ int DevBuf::ensure(size_t n, int headroom_shift) {
         g_dev_bytes[dev] -= (long long)want;
         p = nullptr; cap = 0; return set_err(-11, "hipMalloc failed for " + std::to_string(want) + " bytes");
     }
-    if (getenv("LCD_ALLOC_DEBUG")) fprintf(stderr, "[alloc] %zu bytes asked, %zu allocated (device %d now %.2f GB)\n", n, want, dev, g_dev_bytes[dev].load() / 1e9);
+    if (HostSwitches::from_env().alloc_debug) fprintf(stderr, "[alloc] %zu bytes asked, %zu allocated (device %d now %.2f GB)\n", n, want, dev, g_dev_bytes[dev].load() / 1e9);
     cap = want; ++g_alloc_events; return 0;
 }
 
@@ -104,8 +104,9 @@ int lcd_set_thread_device(int device) {
 const char *lcd_last_error(void) { return g_err.c_str(); }
 const char *lcd_version(void) { return "longcalld_amd hot path 0.1 (gfx950)"; }
 int lcd_host_threads(int *team, int *arena_threads, int *cpus, int *local_world) {
-    if (team) *team = host_team();
-    if (arena_threads) *arena_threads = host_arena_threads();
+    const HostSwitches sw = HostSwitches::from_env();
+    if (team) *team = host_team(sw);
+    if (arena_threads) *arena_threads = host_arena_threads(sw);
     if (cpus) *cpus = host_cpus();
     if (local_world) *local_world = host_local_world();
     return 0;

@@ -1,4 +1,6 @@
 """Parity of the HIP kernels (through the C ABI) against the CPU oracle on the same seeded inputs.  Bit-exact: integer/byte work."""
+import os
+
 import numpy as np
 import pytest
 
@@ -157,6 +159,51 @@ def test_wfa_matches_oracle(lcd, oracle):
             assert got[i]["score"] == exp["score"], (ga, i)
             assert (got[i]["cigar"] == exp["cigar"]).all() and len(got[i]["cigar"]) == len(exp["cigar"]), (ga, i)
             assert (got[i]["pattern_alg"] == exp["pattern_alg"]).all() and (got[i]["text_alg"] == exp["text_alg"]).all(), (ga, i)
+
+
+def _wide_wfa_pairs():
+    """16 pairs of a 1 000 - 1 200 base text and that text with ONE insertion of 1 500 - 2 900 bases (patterns of 2.5 - 4.1 kb; every other pair swapped: a deletion),
+    and four short pairs.  The batched rows of lcd_wfa_kernel<256, false, true> (wfa_kernel.hip: WIDE && khi - klo + 1 >= 2 * U * NT, U = 4, NT = 256) take every
+    score s whose row min(s, plen) + min(s, tlen) + 1 has at least 2 048 diagonals: with the shorter sequence <= 1 200 bases that is s >= 847 .. 1 047, and the optimal
+    score of an indel of D bases is 24 + D >= 1 524 -- all 16 long pairs cross it, from about a third of their scores on.  The short pairs (rows of <= 601
+    diagonals) never do: they run the plain loop of the same instantiation."""
+    rng = np.random.default_rng(1606)
+    pairs = []
+    for i in range(16):
+        t = rng.integers(0, 4, int(rng.integers(1000, 1201))).astype(np.uint8)
+        at = int(rng.integers(100, len(t) - 100))
+        p = np.concatenate([t[:at], rng.integers(0, 4, int(rng.integers(1500, 2901))).astype(np.uint8), t[at:]])
+        pairs.append((p, t) if i % 2 == 0 else (t, p))
+    for L in (40, 120, 300, 300):
+        t = rng.integers(0, 4, L).astype(np.uint8)
+        pairs.append((mutate(rng, t, 0.03, 0), t))
+    return pairs
+
+
+def test_wfa_wide_instantiation_matches_oracle(lcd, oracle):
+    """K3's instantiation with four diagonals per thread in flight, which a stage launches only for 64 jobs of a megabyte and more: LCD_WFA_LDS_MAX_KB=0 (every job in
+    the HBM-ring class), LCD_WFA_WIDE_KB=1 and LCD_WFA_WIDE_MIN=1 send all 20 jobs of ONE lcd_wfa_batch call through it (the switches are read at every call); the same
+    call with the switches unset runs the LDS classes and the plain HBM-ring instantiation.  Scores, CIGARs and rows: equal between the two and equal to the oracle's"""
+    pairs = _wide_wfa_pairs()
+    switches = {"LCD_WFA_LDS_MAX_KB": "0", "LCD_WFA_WIDE_KB": "1", "LCD_WFA_WIDE_MIN": "1"}
+    before = {k: os.environ.get(k) for k in switches}
+    try:
+        os.environ.update(switches)
+        wide = lcd.wfa_batch(pairs)
+        for k in switches:
+            os.environ.pop(k)
+        plain = lcd.wfa_batch(pairs)
+    finally:
+        for k, v in before.items():
+            if v is None: os.environ.pop(k, None)
+            else: os.environ[k] = v
+    for i, (p, t) in enumerate(pairs):
+        exp = oracle.wfa_end2end_aln(p, t)
+        for what, got in (("wide", wide), ("plain", plain)):
+            assert got[i]["score"] == exp["score"], (what, i)
+            assert (got[i]["cigar"] == exp["cigar"]).all() and len(got[i]["cigar"]) == len(exp["cigar"]), (what, i)
+            assert (got[i]["pattern_alg"] == exp["pattern_alg"]).all() and (got[i]["text_alg"] == exp["text_alg"]).all(), (what, i)
+        if i < 16: assert exp["score"] >= 1524 and min(len(p), len(t)) + min(exp["score"], max(len(p), len(t))) + 1 >= 2048, i   # (the pair's last rows are batched ones)
 
 
 def test_wfa_large_gap_retry(lcd, oracle):
