@@ -134,6 +134,14 @@ int lcdo_poa_debug_last_scores(int *banded, int *unbanded);
  * their row's interval (must be 0), [6] widest interval, [7] rows wider than the 256-column window, [11] cells under the product's guessing policy (a retried
  * read counted twice), [12] retries, [13] reads with a row wider than the window under the policy, [14] same for the true bound, [15] / [16] regions without / all */
 void lcdo_poa_cert_stats(long long *out);
+/* tie census of the POA backtrack (K1 and K2; oracle/poa.c), off by default: how often a backtrack step had more than one alternative satisfying the equality
+ * the backtrack tests.  It changes no result.  One increment per step: out[0] h_steps (steps in the H state), [1] cross_kind (at least two of: some predecessor
+ * satisfies the match equality / some (predecessor, piece) an E1 or E2 equality / some k the insertion-run equality), [2] multi_match (>= 2 predecessors
+ * satisfy the match equality), [3] multi_e (>= 2 (predecessor, piece) pairs the E equality), [4] multi_ins (>= 2 (k, piece) pairs the insertion-run
+ * equality), [5] e_steps (steps in an E state), [6] open_and_ext (H - oe == E holds and some predecessor satisfies the extend equality), [7] multi_ext (>= 2
+ * predecessors satisfy the extend equality).  lcdo_poa_tie_counts reads the counters and resets them. */
+void lcdo_poa_tie_census(int on);
+void lcdo_poa_tie_counts(long long out[8]);
 
 /* ---------------- align.c glue ---------------- */
 typedef struct {

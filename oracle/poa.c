@@ -60,6 +60,15 @@ struct lcdo_poa_s {
 
 static int g_dbg_banded, g_dbg_unbanded;
 
+/* ---- tie census (test infrastructure): how often the backtrack below had MORE than one alternative that satisfied the equality it tests, by kind.  Off by
+ * default; lcdo_poa_tie_census switches it, lcdo_poa_tie_counts reads and resets the counters.  It only evaluates the alternatives the backtrack does not
+ * take: no result depends on it.  One increment per backtrack step: [0] h_steps, [1] cross_kind, [2] multi_match, [3] multi_e, [4] multi_ins, [5] e_steps,
+ * [6] open_and_ext, [7] multi_ext (lcd_oracle.h). ---- */
+static int g_tie_on;
+static long long g_tie[8];
+void lcdo_poa_tie_census(int on) { g_tie_on = on != 0; }
+void lcdo_poa_tie_counts(long long out[8]) { for (int i = 0; i < 8; ++i) { out[i] = g_tie[i]; g_tie[i] = 0; } }
+
 static inline int ilog2_32(uint32_t v) { int r = 0; while (v >>= 1) ++r; return r; }
 
 static lcdo_poa_t *poa_init(int n_seq) {
@@ -351,6 +360,25 @@ static int align_to_subgraph(lcdo_poa_t *g, const lcdo_opt_t *opt, int wb, doubl
             if (st == 0) {
                 int hv = CELL(i, j, 0), hit = 0;
                 int s = sc_mat(opt, g->node[v].base, seq[j - 1]);
+                if (g_tie_on) { /* census: every alternative of this step, taken or not */
+                    int n_m = 0, n_e = 0, n_i = 0;
+                    for (int e = g->node[v].in_head; e >= 0; e = g->edge[e].next_in) {
+                        int pr = g->node2idx[g->edge[e].from] - bi, bonus = ilog2_32(g->edge[e].w);
+                        if (pr < 0 || pr >= nrow || !imap[pr]) continue;
+                        if (INBAND(pr, j - 1) && CELL(pr, j - 1, 0) + s + bonus == hv) ++n_m;
+                        if (INBAND(pr, j)) for (int c = 1; c <= 2; ++c) if (CELL(pr, j, c) + bonus == hv) ++n_e;
+                    }
+                    for (int k = j - 1; k >= rbeg[i]; --k) {
+                        int len = j - k, hk = CELL(i, k, 0);
+                        if (hk - o1 - len * e1 == hv) ++n_i;
+                        if (hk - o2 - len * e2 == hv) ++n_i;
+                    }
+                    ++g_tie[0];
+                    if ((n_m > 0) + (n_e > 0) + (n_i > 0) >= 2) ++g_tie[1];
+                    if (n_m >= 2) ++g_tie[2];
+                    if (n_e >= 2) ++g_tie[3];
+                    if (n_i >= 2) ++g_tie[4];
+                }
                 for (int e = g->node[v].in_head; e >= 0 && !hit; e = g->edge[e].next_in) {
                     int pr = g->node2idx[g->edge[e].from] - bi;
                     if (pr < 0 || pr >= nrow || !imap[pr] || !INBAND(pr, j - 1)) continue;
@@ -377,6 +405,17 @@ static int align_to_subgraph(lcdo_poa_t *g, const lcdo_opt_t *opt, int wb, doubl
             } else {
                 const int oe = st == 1 ? oe1 : oe2, ee = st == 1 ? e1 : e2;
                 int ev = CELL(i, j, st);
+                if (g_tie_on) { /* census: "open" and every "extend" of this step */
+                    int n_x = 0;
+                    for (int e = g->node[v].in_head; e >= 0; e = g->edge[e].next_in) {
+                        int pr = g->node2idx[g->edge[e].from] - bi;
+                        if (pr < 0 || pr >= nrow || !imap[pr] || !INBAND(pr, j)) continue;
+                        if (CELL(pr, j, st) + ilog2_32(g->edge[e].w) - ee == ev) ++n_x;
+                    }
+                    ++g_tie[5];
+                    if (CELL(i, j, 0) - oe == ev && n_x > 0) ++g_tie[6];
+                    if (n_x >= 2) ++g_tie[7];
+                }
                 if (CELL(i, j, 0) - oe == ev) { st = 0; continue; }
                 int hit = 0;
                 for (int e = g->node[v].in_head; e >= 0 && !hit; e = g->edge[e].next_in) {

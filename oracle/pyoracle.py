@@ -317,6 +317,34 @@ def poa_cert_stats():
                 policy_cells=o[11], policy_retries=o[12], policy_wide_reads=o[13], true_wide_reads=o[14])
 
 
+TIE_KINDS = ("h_steps", "cross_kind", "multi_match", "multi_e", "multi_ins", "e_steps", "open_and_ext", "multi_ext")
+
+
+class poa_tie_census:
+    """context manager: the tie census of oracle/poa.c's backtrack (lcd_oracle.h) over the K1 / K2 calls made inside it.  `counts` is a dict over TIE_KINDS,
+    filled when the block ends; the census is off again afterwards and changes no result.
+
+        with pyoracle.poa_tie_census() as census:
+            res = pyoracle.poa_aln_msa_cons(reads)
+        census.counts["multi_match"]"""
+
+    def __enter__(self):
+        L = lib()
+        L.lcdo_poa_tie_counts.argtypes = [C.POINTER(C.c_longlong)]; L.lcdo_poa_tie_counts.restype = None
+        L.lcdo_poa_tie_census.argtypes = [C.c_int]; L.lcdo_poa_tie_census.restype = None
+        L.lcdo_poa_tie_counts((C.c_longlong * 8)())   # (reset)
+        L.lcdo_poa_tie_census(1)
+        self.counts = None
+        return self
+
+    def __exit__(self, *exc):
+        out = (C.c_longlong * 8)()
+        lib().lcdo_poa_tie_census(0)
+        lib().lcdo_poa_tie_counts(out)
+        self.counts = dict(zip(TIE_KINDS, (int(x) for x in out)))
+        return False
+
+
 def poa_aln_msa_cons(reads, max_n_cons=2, opt=None):
     """K2, src/align.c:872"""
     opt = opt or default_opt()

@@ -81,6 +81,25 @@ def main():
     out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "edlib_golden.json")
     json.dump(dict(source="reference edlib (edlib/src/edlib.cpp) via oracle/_ref, NW + TASK_PATH, k=-1; hw_cases: HW + TASK_PATH", cases=cases, hw_cases=hw_cases), open(out, "w"))
     print(len(cases), "NW cases,", len(hw_cases), "HW cases ->", out, os.path.getsize(out), "bytes")
+    # tie-dense pairs (tests/tie_cases.py tie_pairs("edlib")): homopolymer and dinucleotide runs at edlib's word (64), tile and Hirschberg edges, where nearly every
+    # traceback step has more than one predecessor of equal cost -- NW and HW on the same pairs, under the keys tie_cases / tie_hw_cases.  They live in a file of
+    # their own, one case per line: edlib_golden.json is a single line of 260 KB, and a key added to it rewrites that whole line in every diff
+    from tie_cases import tie_pairs
+    tie_cases, tie_hw_cases = [], []
+    for t, q in tie_pairs("edlib"):
+        d, ops = pyoracle.ref_edlib_nw(q, t)
+        tie_cases.append(dict(target="".join(map(str, t)), query="".join(map(str, q)), dist=int(d), xgaps=int(pyoracle.ops_to_xgaps(ops)),
+                              n_eq=int((ops == 0).sum()), n_xid=int((ops != 0).sum()), path_sha1=hashlib.sha1(ops.tobytes()).hexdigest()))
+        d, s0, e0, ops = pyoracle.ref_edlib_hw(q, t)
+        tie_hw_cases.append(dict(target="".join(map(str, t)), query="".join(map(str, q)), dist=int(d), start=int(s0), end=int(e0), xgaps=int(pyoracle.ops_to_xgaps(ops)),
+                                 n_eq=int((ops == 0).sum()), n_xid=int((ops != 0).sum()), path_sha1=hashlib.sha1(ops.tobytes()).hexdigest()))
+    out = os.path.join(os.path.dirname(os.path.abspath(__file__)), "edlib_tie_golden.json")
+    with open(out, "w") as f:
+        f.write('{"source": "reference edlib (edlib/src/edlib.cpp) via oracle/_ref on tests/tie_cases.py tie_pairs(\\"edlib\\"): tie_cases NW + TASK_PATH, tie_hw_cases HW + TASK_PATH",\n')
+        for key, cs in (("tie_cases", tie_cases), ("tie_hw_cases", tie_hw_cases)):
+            f.write(f' "{key}": [\n' + ",\n".join("  " + json.dumps(c) for c in cs) + "\n ]" + (",\n" if key == "tie_cases" else "\n"))
+        f.write("}\n")
+    print(len(tie_cases), "+", len(tie_hw_cases), "tie cases ->", out, os.path.getsize(out), "bytes")
 
 
 if __name__ == "__main__":
