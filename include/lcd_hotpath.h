@@ -874,7 +874,7 @@ void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, 
  * without a newline, or NULL) appended to its text, compressed into its own block(s); then region c's records in region order, the skip counts of region c being
  * its kept / filtered records that overlap region c - 1's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691); every region's stream through
  * lcd_bgzf_deflate_dev_ptr; the EOF member last.  Only compressed bytes cross PCIe; the file is written with fwrite.  htslib's sam_hdr_add_pg chooses ID / PP
- * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written by these entry points (lcd_bam_writer_open_indexed writes one); --refine-aln and CRAM / SAM output are not supported (several input files: lcd_call_files).
+ * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written by these entry points (lcd_bam_writer_open_indexed writes one); --refine-aln and CRAM output are not supported (several input files: lcd_call_files; SAM text: lcd_bam_writer_open_sam).
  * lcd_call_bam_regions_out: lcd_call_bam_regions with the alignment output written after lcd_chunks_call succeeded (bam_out NULL: none).  A failure of the output
  * (unwritable path) returns < 0 with lcd_last_error and leaves *records / *vcf_body / the chunks' out members valid: free them with lcd_call_free as usual. */
 typedef struct lcd_tagged_s lcd_tagged_t;
@@ -1272,6 +1272,62 @@ int lcd_call_file_refine(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const 
                          lcd_refine_stats_t *refine_stats);
 int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
                           lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_refine_stats_t *refine_stats);
+
+/* ---- the alignment output as SAM text (the reference's -S FILE, src/call_var_main.c:961; here --sam FILE): records formatted in HBM (bam_sam_kernel.hip) ----
+ * lcd_tagged_to_sam turns a tagged / refined stream where it lies into SAM lines (SAM specification 1.4), one wavefront per record: a measure pass, the host's
+ * 64-bit prefix sum over the lines' lengths, an emit pass.  lcd_records_to_sam is the same for host bytes of back-to-back block_size-prefixed records (a stream
+ * that ends inside a record, or a block_size below 32: -24).  NULL + lcd_last_error on failure; NULL arguments are refused (-4) before any HIP call.
+ * A line is the eleven mandatory fields, one \tXX:T:value per auxiliary field, \n.  htslib's sam_format1 is not in the checkout; where it would decide, the rule
+ * is marked PROJECT RULE.
+ *   QNAME  the bytes of the name field in front of its first NUL; an empty name prints *.
+ *   FLAG, MAPQ, POS = pos + 1, PNEXT = next_pos + 1, TLEN (signed): decimal.
+ *   RNAME  * for refID < 0; PROJECT RULE: * for refID >= n_ref (and for a contig whose name is empty); else the contig's name.
+ *   RNEXT  * for next_refID < 0 or >= n_ref; = when it equals the record's (valid) refID; else the name.
+ *   CIGAR  * for n_cigar == 0; else <len><op> per word, MIDNSHP=XB for op 0-9 and ? above.  PROJECT RULE, a CIGAR that lives in a CG field (lcd_chunk_refine_records'
+ *          test: n_cigar == 2, the first word <l_seq>S, the second N, and a first CG field of type B -- here with subtype I, the only one whose elements are
+ *          words): the column is the CG array's words (* for an empty array) and that CG field is not printed among the auxiliary fields, as a BAM reader built on
+ *          htslib shows the record.
+ *   SEQ    * for l_seq == 0; else "=ACMGRSVTWYHKDBN"[nibble].   QUAL  * for l_seq == 0 or a first quality byte of 0xff; else byte + 33 (modulo 256).
+ *   PROJECT RULE: a record whose name, CIGAR, bases and qualities do not fit its block_size (or whose l_seq is negative) prints the fields that can be read -- the
+ *   name if it fits, else * -- with * for CIGAR / SEQ / QUAL and no auxiliary fields; it is counted in n_bad_layout.  Nothing outside the record is read.
+ *   Auxiliary fields in record order, walked as lcd_chunk_read_nm walks them: a field that runs past the record or has an unknown type ends the walk, nothing behind
+ *   it is printed, the record is counted in n_walk_stopped.  A: A:<char>; c C s S i I: i:<decimal>; f: f:<%g>; Z / H: the bytes in front of the NUL;
+ *   B: B:<sub> then ,<value> per element (count 0: B:<sub> alone; subtype f: %g).
+ *   A float prints exactly as glibc's printf("%g", (double)x): csrc/sam_fmt.h, exact on the value, no double arithmetic.
+ * lcd_sam_names_create uploads the contigs' names once (n_ref == 0: none).  lcd_sam_stats_t: bytes_records in, bytes_text out; ms_measure includes the length
+ * download, ms_download_write is the writer's.
+ * lcd_bam_writer_open_sam gives the same writer object as lcd_bam_writer_open: append runs the same skip / order plan, the same tag / refine rewrite and then
+ * lcd_tagged_to_sam instead of the deflate; only text comes down.  block_payload is ignored, ms_deflate stays 0, bytes_file counts text, close writes no EOF member,
+ * path "-" is stdout.  lcd_bam_writer_set_sort / _set_refine_stats / _set_sam_stats (the sum over the appends; NULL: none) work on it.  The header is the input
+ * header's text with trailing NULs dropped, pg_line appended as the BAM writer appends it, a newline at its end; PROJECT RULE: if no line starts with "@SQ\t" and
+ * the binary table has contigs, @SQ\tSN:<name>\tLN:<len> lines in table order go straight behind a leading @HD line, or to the front when there is none.
+ * lcd_write_phased_sam is open + one append + close.
+ * lcd_call_files_aln: lcd_call_files_fields / _refine with the alignment output's format chosen (in NULL: the job's one file; fields may be NULL).  format SAM with
+ * idx->write_out_bai: -4; refine together with fields: -2; a SAM output on stdout while the VCF goes to stdout: -4, before any file is created.  The records, the
+ * VCF, HP and PS of a run do not depend on the format.  A several-file run uses file 0's header, as the BAM output does. */
+typedef struct lcd_sam_names_s lcd_sam_names_t;
+typedef struct lcd_sam_text_s lcd_sam_text_t;
+typedef struct lcd_sam_stats_t {
+    int64_t n_records, bytes_records, bytes_text, n_float_values, n_cg_cigar, n_walk_stopped, n_bad_layout;
+    double ms_measure, ms_emit, ms_download_write;
+} lcd_sam_stats_t;
+lcd_sam_names_t *lcd_sam_names_create(int n_ref, const char *const *names);
+void lcd_sam_names_free(lcd_sam_names_t *names);
+lcd_sam_text_t *lcd_tagged_to_sam(const lcd_tagged_t *t, const lcd_sam_names_t *names, lcd_sam_stats_t *stats);
+lcd_sam_text_t *lcd_records_to_sam(const uint8_t *records, size_t n_bytes, const lcd_sam_names_t *names, lcd_sam_stats_t *stats);
+size_t lcd_sam_text_size(const lcd_sam_text_t *h);
+uint64_t lcd_sam_text_dev_ptr(const lcd_sam_text_t *h);
+int lcd_sam_text_to_host(const lcd_sam_text_t *h, size_t off, size_t n, uint8_t *out);
+void lcd_sam_text_free(lcd_sam_text_t *h);
+lcd_bam_writer_t *lcd_bam_writer_open_sam(const char *in_bam_path, lcd_bam_out_t *out);
+int lcd_bam_writer_set_sam_stats(lcd_bam_writer_t *w, lcd_sam_stats_t *sam_stats);
+int lcd_write_phased_sam(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats,
+                         lcd_sam_stats_t *sam_stats);
+enum { LCD_ALN_BAM = 0, LCD_ALN_SAM = 1 };
+typedef struct lcd_aln_opt_t { int format, refine; } lcd_aln_opt_t;
+int lcd_call_files_aln(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
+                       const lcd_aln_opt_t *aln, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out,
+                       lcd_refine_stats_t *refine_stats, lcd_sam_stats_t *sam_stats);
 
 #ifdef __cplusplus
 }

@@ -262,6 +262,17 @@ class LcdRefineStats(C.Structure):
                     (n, C.c_int64) for n in ("n_log_entries", "bytes_log_down", "n_log_rejected")]
 
 
+class LcdSamStats(C.Structure):
+    """lcd_sam_stats_t: what lcd_tagged_to_sam / lcd_records_to_sam formatted"""
+    _fields_ = [(n, C.c_int64) for n in ("n_records", "bytes_records", "bytes_text", "n_float_values", "n_cg_cigar", "n_walk_stopped", "n_bad_layout")] + [
+        (n, C.c_double) for n in ("ms_measure", "ms_emit", "ms_download_write")]
+
+
+class LcdAlnOpt(C.Structure):
+    """lcd_aln_opt_t: the alignment output's format (LCD_ALN_BAM / LCD_ALN_SAM) and whether its records are refined"""
+    _fields_ = [("format", C.c_int), ("refine", C.c_int)]
+
+
 class LcdRefineEntry(C.Structure):
     """lcd_refine_entry_t: one (cluster, read) of a resolved noisy region -- what lcd_update_digars_from_msa1 takes"""
     _fields_ = [(n, C.c_int) for n in ("read_id", "cover", "read_beg", "read_end", "aln_len", "pass_")] + [("reg_beg", C.c_int64), ("reg_end", C.c_int64),
@@ -271,6 +282,7 @@ class LcdRefineEntry(C.Structure):
 LCD_RNAMES_NONE, LCD_RNAMES_SV, LCD_RNAMES_ALL = 0, 1, 2
 LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG, LCD_ERR_INPUT_HEADERS = -50, -51, -52, -53, -54
 LCD_MAX_INPUTS = 64
+LCD_ALN_BAM, LCD_ALN_SAM = 0, 1
 LCD_CTG_AUTOSOME_XY, LCD_CTG_AUTOSOME, LCD_CTG_ALL = 0, 1, 2
 
 _lib = None
@@ -303,6 +315,8 @@ EXPORTS = [
     "lcd_refine_log_entry", "lcd_refine_log_apply", "lcd_chunks_noisy_rounds_log", "lcd_batch_region_ref_read_rows",
     "lcd_chunk_set_refine", "lcd_chunk_refine_log", "lcd_chunks_call_refine", "lcd_write_phased_bam_refine", "lcd_bam_writer_set_refine_stats", "lcd_call_bam_regions_refine",
     "lcd_call_file_refine", "lcd_call_files_refine",
+    "lcd_sam_names_create", "lcd_sam_names_free", "lcd_tagged_to_sam", "lcd_records_to_sam", "lcd_sam_text_size", "lcd_sam_text_dev_ptr", "lcd_sam_text_to_host", "lcd_sam_text_free",
+    "lcd_bam_writer_open_sam", "lcd_bam_writer_set_sam_stats", "lcd_write_phased_sam", "lcd_call_files_aln",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -549,6 +563,28 @@ def load_library():
     lib.lcd_call_bam_regions_refine.argtypes = lib.lcd_call_bam_regions_out.argtypes + [rsp]
     lib.lcd_call_file_refine.argtypes = lib.lcd_call_file_indexed.argtypes + [rsp]
     lib.lcd_call_files_refine.argtypes = lib.lcd_call_files.argtypes + [rsp]
+    ssp = C.POINTER(LcdSamStats)
+    lib.lcd_sam_names_create.restype = C.c_void_p
+    lib.lcd_sam_names_create.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
+    lib.lcd_sam_names_free.argtypes = [C.c_void_p]
+    lib.lcd_sam_names_free.restype = None
+    lib.lcd_tagged_to_sam.restype = C.c_void_p
+    lib.lcd_tagged_to_sam.argtypes = [C.c_void_p, C.c_void_p, ssp]
+    lib.lcd_records_to_sam.restype = C.c_void_p
+    lib.lcd_records_to_sam.argtypes = [u8p, C.c_size_t, C.c_void_p, ssp]
+    lib.lcd_sam_text_size.restype = C.c_size_t
+    lib.lcd_sam_text_size.argtypes = [C.c_void_p]
+    lib.lcd_sam_text_dev_ptr.restype = C.c_uint64
+    lib.lcd_sam_text_dev_ptr.argtypes = [C.c_void_p]
+    lib.lcd_sam_text_to_host.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, u8p]
+    lib.lcd_sam_text_free.argtypes = [C.c_void_p]
+    lib.lcd_sam_text_free.restype = None
+    lib.lcd_bam_writer_open_sam.restype = C.c_void_p
+    lib.lcd_bam_writer_open_sam.argtypes = [C.c_char_p, C.POINTER(LcdBamOut)]
+    lib.lcd_bam_writer_set_sam_stats.argtypes = [C.c_void_p, ssp]
+    lib.lcd_write_phased_sam.argtypes = lib.lcd_write_phased_bam.argtypes + [rsp, ssp]
+    lib.lcd_call_files_aln.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdVcfFields), C.POINTER(LcdAlnOpt),
+                                       C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats), i64p, C.POINTER(LcdVcfFieldsOut), rsp, ssp]
     _lib = lib
     return lib
 

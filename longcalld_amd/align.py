@@ -1721,6 +1721,116 @@ def bgzf_deflate(data, block_payload=0, add_eof=1):
         lib.lcd_deflated_free(h)
 
 
+# ---------------- records as SAM text (bam_sam_kernel.hip) ----------------
+class _SamNames:
+    """lcd_sam_names_t for a `with` block: the contigs' names in HBM"""
+
+    def __init__(self, names):
+        self.lib = load_library()
+        arr, n = _str_array(names)
+        self.h = self.lib.lcd_sam_names_create(n, arr)
+        if not self.h:
+            raise LcdError("lcd_sam_names_create failed: " + self.lib.lcd_last_error().decode())
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.lib.lcd_sam_names_free(self.h); self.h = None
+
+
+def _sam_text(lib, h, what, st):
+    """a lcd_sam_text_t handle -> (text bytes, stats dict); frees the handle"""
+    from ._lib import LcdSamStats
+    if not h:
+        raise LcdError(what + " failed: " + lib.lcd_last_error().decode())
+    try:
+        n = lib.lcd_sam_text_size(h)
+        buf = np.zeros(max(n, 1), np.uint8)
+        check(lib.lcd_sam_text_to_host(h, 0, n, _p8(buf)), lib)
+        return buf[:n].tobytes(), {k: getattr(st, k) for k, _t in LcdSamStats._fields_}
+    finally:
+        lib.lcd_sam_text_free(h)
+
+
+def records_to_sam(records, names):
+    """lcd_records_to_sam: host bytes of back-to-back block_size-prefixed BAM records + the contigs' names -> (the SAM lines formatted on the device, stats dict)"""
+    from ._lib import LcdSamStats
+    lib = load_library()
+    rec = np.frombuffer(bytes(records), np.uint8)
+    st = LcdSamStats()
+    with _SamNames(names) as nm:
+        h = lib.lcd_records_to_sam(_p8(rec) if len(rec) else None, len(rec), nm.h, C.byref(st))
+        return _sam_text(lib, h, "lcd_records_to_sam", st)
+
+
+def tagged_to_sam(chunk, haps, phase_sets, names, skip=None, order=None):
+    """lcd_chunk_tag_records_sel + lcd_tagged_to_sam: a chunk's records with HP / PS rewritten, as SAM lines, without the records leaving HBM
+    -> (text, number of records, stats dict)"""
+    from ._lib import LcdSamStats
+    lib = chunk.lib
+    hp = np.concatenate([np.ascontiguousarray(haps, np.int32), np.zeros(1, np.int32)]); ps = np.concatenate([np.ascontiguousarray(phase_sets, np.int64), np.zeros(1, np.int64)])
+    if len(hp) <= chunk.n or len(ps) <= chunk.n:
+        raise ValueError("tagged_to_sam: haps / phase_sets shorter than the chunk's reads")
+    sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
+    od = np.ascontiguousarray(order, np.int32) if order is not None else None
+    t = lib.lcd_chunk_tag_records_sel(chunk.h, hp.ctypes.data_as(i32p), ps.ctypes.data_as(C.POINTER(C.c_int64)), _p8(sk) if sk is not None else None,
+                                      od.ctypes.data_as(i32p) if od is not None else None)
+    if not t:
+        raise LcdError("lcd_chunk_tag_records_sel failed: " + lib.lcd_last_error().decode())
+    try:
+        st = LcdSamStats()
+        with _SamNames(names) as nm:
+            text, stats = _sam_text(lib, lib.lcd_tagged_to_sam(t, nm.h, C.byref(st)), "lcd_tagged_to_sam", st)
+        return text, int(lib.lcd_tagged_n_records(t)), stats
+    finally:
+        lib.lcd_tagged_free(t)
+
+
+def write_phased_sam(in_bam_path, chunks, path, pg_line=None, sort_output=False, aln_format="sam", block_payload=0):
+    """lcd_write_phased_sam (aln_format="bam": the BAM writer on the same chunks): chunks = [dict(chunk=DeviceChunk, haps, phase_sets, reg_beg, reg_end[, ref, ref_beg,
+    ref_end])] in region order, each with its final haplotypes -- the fields of lcd_call_chunk_t the writer reads.  sort_output: through lcd_bam_writer_open(_sam) /
+    _set_sort / _append / _close.  -> dict(bam_out = lcd_bam_out_t's counters, refine = lcd_refine_stats_t, sam = lcd_sam_stats_t)"""
+    from ._lib import LcdBamOut, LcdCallChunk, LcdHapState, LcdRefineStats, LcdSamStats
+    if aln_format not in ("sam", "bam"):
+        raise ValueError("write_phased_sam: aln_format must be 'sam' or 'bam'")
+    lib = load_library()
+    n = len(chunks)
+    arr = (LcdCallChunk * max(1, n))()
+    keep = []
+    for k, c in enumerate(chunks):
+        ch = c["chunk"]
+        hp = np.concatenate([np.ascontiguousarray(c["haps"], np.int32), np.zeros(1, np.int32)]); ps = np.concatenate([np.ascontiguousarray(c["phase_sets"], np.int64), np.zeros(1, np.int64)])
+        if len(hp) <= ch.n or len(ps) <= ch.n:
+            raise ValueError("write_phased_sam: haps / phase_sets shorter than the chunk's reads")
+        s = LcdHapState(); s.n_reads = ch.n; s.haps = hp.ctypes.data_as(i32p); s.phase_sets = ps.ctypes.data_as(C.POINTER(C.c_int64))
+        keep += [hp, ps, s]
+        f = arr[k].first
+        f.chunk, f.reg_beg, f.reg_end, f.n_reads, f.state = ch.h, int(c["reg_beg"]), int(c["reg_end"]), ch.n, C.pointer(s)
+        if c.get("ref") is not None:
+            rb = np.frombuffer(bytes(c["ref"]) if isinstance(c["ref"], (bytes, bytearray)) else np.ascontiguousarray(c["ref"], np.uint8).tobytes(), np.uint8).copy()
+            keep.append(rb)
+            f.ref_seq, f.ref_beg, f.ref_end = _p8(rb), int(c["ref_beg"]), int(c["ref_end"])
+    bo = LcdBamOut(); bo.path = _enc(path); bo.pg_line = _enc(pg_line) if pg_line is not None else None; bo.block_payload = int(block_payload)
+    rst, sst = LcdRefineStats(), LcdSamStats()
+    if aln_format == "sam" and not sort_output:
+        check(lib.lcd_write_phased_sam(_enc(in_bam_path), n, arr, C.byref(bo), C.byref(rst), C.byref(sst)), lib)
+    else:
+        w = (lib.lcd_bam_writer_open_sam if aln_format == "sam" else lib.lcd_bam_writer_open)(_enc(in_bam_path), C.byref(bo))
+        if not w:
+            raise LcdError("opening the alignment output failed: " + lib.lcd_last_error().decode())
+        lib.lcd_bam_writer_set_sort(w, int(bool(sort_output))); lib.lcd_bam_writer_set_refine_stats(w, C.byref(rst))
+        if aln_format == "sam":
+            lib.lcd_bam_writer_set_sam_stats(w, C.byref(sst))
+        rc = lib.lcd_bam_writer_append(w, n, arr, None, None)
+        if rc < 0:
+            lib.lcd_bam_writer_abort(w)
+            check(rc, lib)
+        check(lib.lcd_bam_writer_close(w), lib)
+    return dict(bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag", "ms_deflate", "ms_download_write")},
+                refine={k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}, sam={k: getattr(sst, k) for k, _t in LcdSamStats._fields_})
+
+
 def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
     bam_out = dict(path[, pg_line, block_payload]): lcd_call_bam_regions_out, the phased alignment file is written too; the result gets "bam_out" = the counters and
@@ -1881,7 +1991,7 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam"):
     """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
     phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
     flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -1890,8 +2000,12 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     te_fasta= (the -T file) / rnames=None|"sv"|"all" (--out-sv-rnames / --out-var-rnames): lcd_call_file_fields / lcd_call_files_fields; the result gains "te_names" and
     "n_mei_lines" (with a library) and the kept records "te_name" / "alt_read_names" (see _fields_result).
     refine=True (the command line's --refine-bam; no effect without bam_out, not with te_fasta / rnames): lcd_call_file_refine / lcd_call_files_refine; the result
-    gains "refine" = lcd_refine_stats_t's fields"""
-    from ._lib import LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats, LcdRefineStats
+    gains "refine" = lcd_refine_stats_t's fields.
+    aln_format="sam" (the command line's --sam; the default "bam" takes the entry points above untouched): lcd_call_files_aln -- bam_out's path gets SAM text ("-":
+    stdout), block_payload is ignored, no output index; the result gains "sam" = lcd_sam_stats_t's fields"""
+    from ._lib import LCD_ALN_SAM, LcdAlnOpt, LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats, LcdRefineStats, LcdSamStats
+    if aln_format not in ("bam", "sam"):
+        raise ValueError("call_file: aln_format must be 'bam' or 'sam'")
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
     job = LcdFileJob(); lib.lcd_file_job_default(C.byref(job))
@@ -1931,7 +2045,13 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     if refine and vf is not None:
         raise ValueError("call_file: refine= goes with neither te_fasta= nor rnames=")
     rst = LcdRefineStats() if refine else None
-    if rst is not None and _inputs is not None:
+    sst = None
+    if aln_format == "sam":
+        sst, ao = LcdSamStats(), LcdAlnOpt(LCD_ALN_SAM, int(bool(refine)))
+        rc = lib.lcd_call_files_aln(C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), iop, C.byref(vf) if vf is not None else None, C.byref(ao),
+                                    C.byref(st), istp, per_file if _inputs is not None else None, C.byref(fo) if vf is not None else None,
+                                    C.byref(rst) if rst is not None else None, C.byref(sst))
+    elif rst is not None and _inputs is not None:
         rc = lib.lcd_call_files_refine(C.byref(inp), C.byref(job), C.byref(cfg), iop, C.byref(st), istp, per_file, C.byref(rst))
     elif rst is not None:
         rc = lib.lcd_call_file_refine(C.byref(job), C.byref(cfg), iop, C.byref(st), istp, C.byref(rst))
@@ -1963,6 +2083,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res = _fields_result(lib, res, vf, fo)
         if rst is not None:
             res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
+        if sst is not None:
+            res["sam"] = {k: getattr(sst, k) for k, _t in LcdSamStats._fields_}
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))

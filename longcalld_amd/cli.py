@@ -7,7 +7,8 @@ REFUSED = {
     "-s": "somatic / mosaic calling is not supported", "--mosaic": "somatic / mosaic calling is not supported", "--somatic": "somatic / mosaic calling is not supported",
     "--refine-aln": "--refine-aln is not supported: ask for refined alignments in the output BAM with --refine-bam", "-L": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE", "--input-is-list": "-L/--input-is-list is not supported: give the list of input files with --bam-list FILE",
     "-X": "-X/--extra-bam is not supported: give further input files with --add-bam FILE", "--extra-bam": "-X/--extra-bam is not supported: give further input files with --add-bam FILE",
-    "-S": "SAM output (-S) is not supported: use -b", "--out-sam": "SAM output (-S) is not supported: use -b", "--out-cram": "CRAM output (-C FILE) is not supported: use -b",
+    "-S": "-S/--out-sam is not supported: ask for SAM text with --sam FILE", "--out-sam": "-S/--out-sam is not supported: ask for SAM text with --sam FILE",
+    "--out-cram": "CRAM output (-C FILE) is not supported: use -b or --sam",
     "-T": "-T/--trans-elem is not supported: give the TE sequence file with --te-lib FILE", "--trans-elem": "-T/--trans-elem is not supported: give the TE sequence file with --te-lib FILE",
     "--out-var-rnames": "--out-var-rnames is not supported: ask for the supporting read names of every record with --var-rnames",
     "--out-sv-rnames": "--out-sv-rnames is not supported: ask for the supporting read names of SV records with --sv-rnames",
@@ -18,7 +19,7 @@ VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E":
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
-          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib"}
+          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli faidx ref.fa               build ref.fa.fai
@@ -31,12 +32,13 @@ Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z 
           --te-lib FILE   TE sequences (FASTA, plain or gzip; the reference's -T): SVs that look like their insertion get MEI and REPNAME=
           --var-rnames | --sv-rnames   the supporting read names of every record | of SV records as the FORMAT field ALTREADS (the reference's --out-var-rnames /
           --out-sv-rnames; --var-rnames wins)
-          --refine-bam   with -b: every kept read is written with the alignment the caller arrived at (CIGAR, POS, NM / MD / cs; the reference's --refine-aln);
-          without -b it has no effect; a rewrite can move POS, so the output may stop being sorted (then no <out.bam>.bai is written, and the reason is printed)
+          --sam FILE   the alignment output as SAM text instead of -b (FILE "-": stdout, then -o must name a file); the records are formatted on the device
+          --refine-bam   with -b or --sam: every kept read is written with the alignment the caller arrived at (CIGAR, POS, NM / MD / cs; the reference's --refine-aln);
+          without -b / --sam it has no effect; a rewrite can move POS, so the output may stop being sorted (then no <out.bam>.bai is written, and the reason is printed)
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
-Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched)
+Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched; --sam gets no index)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
-Not supported (refused with exit status 2): -s, --refine-aln (use --refine-bam), -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S, -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
+Not supported (refused with exit status 2): -s, --refine-aln (use --refine-bam), -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S (use --sam), -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
           --out-som-var-rnames
 """
 
@@ -154,6 +156,10 @@ def main(argv=None):
             num["alt_ratio"] = float(o["alt_ratio"])
     except ValueError as e:
         return refuse(f"not a number: {e}")
+    if "out_sam" in o and "out_bam" in o:
+        return refuse("--sam cannot be combined with -b/--out-bam: one alignment output per run")
+    if o.get("out_sam") == "-" and o.get("out_vcf", "-") == "-":
+        return refuse("--sam - needs -o FILE: the SAM text and the VCF cannot both go to stdout")
     from . import align
     is_ont = 1 if "--ont" in o["flags"] else 0
     clean, opt, pass_, call = {}, {}, {}, {}
@@ -174,7 +180,8 @@ def main(argv=None):
     cfg = align.call_cfg(is_ont, clean=clean, opt=opt, pass_=pass_, call=call)
     mode = 2 if "--all-ctg" in o["flags"] else 1 if "--autosome" in o["flags"] else 0
     cmdline = "longcalld_amd call " + " ".join(argv[1:])
-    bam_out = dict(path=o["out_bam"], pg_line="@PG\tID:longcalld_amd\tPN:longcalld_amd\tCL:" + cmdline) if "out_bam" in o else None
+    sam = "out_sam" in o
+    bam_out = dict(path=o["out_sam" if sam else "out_bam"], pg_line="@PG\tID:longcalld_amd\tPN:longcalld_amd\tCL:" + cmdline) if sam or "out_bam" in o else None
     refine = "--refine-bam" in o["flags"]
     if refine and any(v is not None for v in vcf_fields(o).values()):
         return refuse("--refine-bam cannot be combined with --te-lib / --var-rnames / --sv-rnames in one run")
@@ -190,7 +197,8 @@ def main(argv=None):
                              window_chunks=num.get("window_chunks", 0), overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0),
                              min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
-                             index=True if "--make-index" in o["flags"] else None, **(dict(refine=True) if refine else vcf_fields(o)))
+                             index=(dict(build_missing_bai=1, build_missing_fai=1) if sam else True) if "--make-index" in o["flags"] else None,
+                             **(dict(aln_format="sam") if sam else {}), **(dict(refine=True) if refine else vcf_fields(o)))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
@@ -201,7 +209,8 @@ def main(argv=None):
     per_file = f" ({' + '.join(str(x) for x in st['n_reads_per_file'])} from the {len(bams)} input files)" if len(bams) > 1 else ""
     sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads{per_file}, {st['n_vcf_lines']} VCF lines, "
                      + (f"{st['n_mei_lines']} MEI records, " if "n_mei_lines" in st else "")
-                     + (f"{st['refine']['n_refined']} refined / {st['refine']['n_unrefined']} unrefined records, " if refine and bam_out is not None else "") + f"{st['ms_wall'] / 1000:.2f} s\n")
+                     + (f"{st['refine']['n_refined']} refined / {st['refine']['n_unrefined']} unrefined records, " if refine and bam_out is not None else "")
+                     + (f"{st['bam_out']['bytes_file']} bytes of SAM text, " if sam else "") + f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 
 

@@ -1,5 +1,6 @@
 // lcd_bam_out.cpp -- the device side of the phased alignment output (longcallD call -b): BGZF members compressed in HBM (deflate_kernel.hip) and the HP:i / PS:i
 // rewrite of a chunk's records where the inflate left them (bam_tag_kernel.hip).  The writer that joins them into a file is lcd_write_phased_bam (lcd_call.cpp).
+// The same records as SAM text lines (bam_sam_kernel.hip): lcd_tagged_to_sam / lcd_records_to_sam, behind lcd_bam_writer_open_sam.
 #include "lcd_host_internal.h"
 
 using namespace lcd_internal;
@@ -8,7 +9,10 @@ struct lcd_deflated_s {
     DevBuf image; size_t size = 0, n_blocks = 0; double ms_kernel = 0; int device = 0; bool eof = false;
     std::vector<DeflateOut> outs; std::vector<uint32_t> payloads;
 };
-struct lcd_tagged_s { DevBuf out; size_t size = 0; int n_records = 0, device = 0; };
+// offs: where record k starts in `out` (n_records + 1 entries, what the emit pass was given); d_offs: the same in HBM, uploaded by the first lcd_tagged_to_sam
+struct lcd_tagged_s { DevBuf out; size_t size = 0; int n_records = 0, device = 0; std::vector<unsigned long long> offs; mutable DevBuf d_offs; mutable bool offs_up = false; };
+struct lcd_sam_names_s { DevBuf pool, offs; size_t pool_bytes = 0; int n_ref = 0, device = 0; };
+struct lcd_sam_text_s { DevBuf text; size_t size = 0; int device = 0; };
 
 namespace {
 const uint8_t EOF_MEMBER[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -177,8 +181,9 @@ lcd_tagged_t *tag_records_core(const std::string &W, const lcd_chunk_t *c, const
     for (int i = 0; i < n; ++i) {
         const BamTagOut &o = outs[i];
         if (o.hp_end < o.hp_beg || o.ps_end < o.ps_beg || o.hp_end > jobs[i].len || o.ps_end > jobs[i].len || o.new_len < 36 || o.new_len > jobs[i].len + 14) { set_err(-24, W + ": inconsistent measure pass"); return nullptr; }
-        outs[i].dst = tot; tot += o.new_len;
+        outs[i].dst = tot; h->offs.push_back(tot); tot += o.new_len;
     }
+    h->offs.push_back(tot);
     h->size = (size_t)tot;
     if (h->out.ensure((size_t)tot + 64, 31)) return nullptr;
     TCHK(hipMemcpyAsync(d_outs.p, outs.data(), (size_t)n * sizeof(BamTagOut), hipMemcpyHostToDevice, st));
@@ -306,7 +311,7 @@ lcd_tagged_t *lcd_chunk_refine_records(const lcd_chunk_t *c, int n_touched, cons
         ok = ok && (uint64_t)o.new_len + gone >= 36 + app && nc_old % 4 == 0 && nc_old <= 4ull * 65535 && ((o.flags & 32u) || nc_old == 4ull * o.n_ops) &&
              (!(o.flags & 32u) || (int)o.n_ops <= j.n_digar);
         if (!ok) { set_err(-24, W + ": inconsistent measure pass"); return nullptr; }
-        o.dst = tot; tot += o.new_len;
+        o.dst = tot; h->offs.push_back(tot); tot += o.new_len;
         ++s.n_records; s.n_kept += j.kept; s.n_pos_moved += o.pos_moved != 0;
         switch (o.state) {
         case LCD_REFINE_CHANGED: ++s.n_refined; s.n_nm_replaced += o.flags & 1u; s.n_md_replaced += (o.flags >> 1) & 1u; s.n_cs_replaced += (o.flags >> 2) & 1u; break;
@@ -321,6 +326,7 @@ lcd_tagged_t *lcd_chunk_refine_records(const lcd_chunk_t *c, int n_touched, cons
     }
     s.n_unrefined = s.n_no_digars + s.n_qlen_mismatch + s.n_bad_pos + s.n_too_many_ops + s.n_cg_cigar;
     s.n_touched = n_touched; s.bytes_digars_up = (int64_t)(n_up * sizeof(DigarRec)); s.bytes_ref_up = (int64_t)codes.size();
+    h->offs.push_back(tot);
     h->size = (size_t)tot;
     if (h->out.ensure((size_t)tot + 64, 31)) return nullptr;
     RCHK(hipMemcpyAsync(d_outs.p, outs.data(), (size_t)n * sizeof(BamRefineOut), hipMemcpyHostToDevice, st));
@@ -343,5 +349,121 @@ int lcd_tagged_to_host(const lcd_tagged_t *h, size_t off, size_t n, uint8_t *out
     return 0;
 }
 void lcd_tagged_free(lcd_tagged_t *h) { delete h; }
+
+// ---- records as SAM text (bam_sam_kernel.hip) ----
+lcd_sam_names_t *lcd_sam_names_create(int n_ref, const char *const *names) {
+    const std::string W = "lcd_sam_names_create";
+    if (n_ref < 0 || (n_ref > 0 && !names)) { set_err(-4, W + ": n_ref < 0 or NULL names"); return nullptr; }
+    for (int r = 0; r < n_ref; ++r) if (!names[r]) { set_err(-4, W + ": NULL name"); return nullptr; }
+    if (ensure_init()) return nullptr;
+    std::vector<unsigned> offs((size_t)n_ref + 1, 0u); std::string pool;
+    for (int r = 0; r < n_ref; ++r) {
+        pool += names[r];
+        if (pool.size() > (size_t)1 << 31) { set_err(-4, W + ": the names exceed 2 GB"); return nullptr; }
+        offs[(size_t)r + 1] = (unsigned)pool.size();
+    }
+    std::unique_ptr<lcd_sam_names_s> h(new lcd_sam_names_s());
+    h->n_ref = n_ref; h->device = cur_device(); h->pool_bytes = pool.size();
+    if (h->pool.ensure(pool.size() + 64, 31) || h->offs.ensure(offs.size() * 4, 31)) return nullptr;
+    if ((pool.size() && hipMemcpy(h->pool.p, pool.data(), pool.size(), hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMemcpy(h->offs.p, offs.data(), offs.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError(); set_err(-10, W + ": upload failed"); return nullptr;
+    }
+    return h.release();
+}
+void lcd_sam_names_free(lcd_sam_names_t *h) { delete h; }
+
+namespace {
+// the records [offs[k], offs[k + 1]) of d_base (readable for 8 bytes behind the last one) as text; the calling thread's device is the buffers' device
+lcd_sam_text_t *sam_core(const std::string &W, const uint8_t *d_base, const unsigned long long *d_offs, const std::vector<unsigned long long> &offs,
+                         const lcd_sam_names_t *names, lcd_sam_stats_t *stats) {
+    std::unique_ptr<lcd_sam_text_s> h(new lcd_sam_text_s());
+    h->device = cur_device();
+    const size_t n = offs.empty() ? 0 : offs.size() - 1;
+    if (n > (size_t)INT32_MAX) { set_err(-4, W + ": too many records"); return nullptr; }
+    if (n == 0) return h.release();
+    StreamGuard st; if (st.create()) return nullptr;
+    DevBuf d_outs, d_toff;
+    if (d_outs.ensure(n * sizeof(BamSamOut), 31) || d_toff.ensure((n + 1) * 8, 31)) return nullptr;
+    auto hipfail = [&](const char *what) -> lcd_sam_text_t * { (void)hipGetLastError(); set_err(-10, W + ": HIP call failed: " + what); return nullptr; };
+#define SCHK(x) do { if ((x) != hipSuccess) return hipfail(#x); } while (0)
+    BamSamIn in; in.base = d_base; in.rec_off = d_offs; in.names = (const uint8_t *)names->pool.p; in.name_off = (const unsigned *)names->offs.p;
+    in.n_ref = names->n_ref; in.n_rec = (int)n;
+    const double w0 = now_ms();
+    lcd_launch_bam_sam_measure(in, (BamSamOut *)d_outs.p, st);
+    SCHK(hipGetLastError());
+    std::vector<BamSamOut> outs(n);
+    SCHK(hipMemcpyAsync(outs.data(), d_outs.p, n * sizeof(BamSamOut), hipMemcpyDeviceToHost, st));
+    SCHK(hipStreamSynchronize(st));
+    const double w1 = now_ms();
+    lcd_sam_stats_t s; memset(&s, 0, sizeof(s));
+    std::vector<unsigned long long> toff(n + 1, 0);
+    for (size_t k = 0; k < n; ++k) {
+        const BamSamOut &o = outs[k];
+        // a line is at least its eleven one-byte columns, ten tabs and the newline; an array element of one byte prints as at most five, and two names come from the pool
+        if (o.len < 22 || o.len > 64 + 5 * (offs[k + 1] - offs[k]) + 2 * names->pool_bytes) { set_err(-24, W + ": inconsistent measure pass"); return nullptr; }
+        toff[k + 1] = toff[k] + o.len;
+        s.n_float_values += o.n_float; s.n_cg_cigar += o.flags & 1u; s.n_walk_stopped += (o.flags >> 1) & 1u; s.n_bad_layout += (o.flags >> 2) & 1u;
+    }
+    s.n_records = (int64_t)n; s.bytes_records = (int64_t)(offs[n] - offs[0]); s.bytes_text = (int64_t)toff[n];
+    h->size = (size_t)toff[n];
+    if (h->text.ensure(h->size + 64, 31)) return nullptr;
+    SCHK(hipMemcpyAsync(d_toff.p, toff.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+    lcd_launch_bam_sam_emit(in, (const unsigned long long *)d_toff.p, (uint8_t *)h->text.p, st);
+    SCHK(hipGetLastError());
+    SCHK(hipStreamSynchronize(st));
+#undef SCHK
+    s.ms_measure = w1 - w0; s.ms_emit = now_ms() - w1;
+    if (stats) *stats = s;
+    return h.release();
+}
+} // namespace
+
+lcd_sam_text_t *lcd_tagged_to_sam(const lcd_tagged_t *t, const lcd_sam_names_t *names, lcd_sam_stats_t *stats) {
+    const std::string W = "lcd_tagged_to_sam";
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!t || !names) { set_err(-4, W + ": NULL argument"); return nullptr; }
+    if (t->device != names->device) { set_err(-4, W + ": the records and the names are on different devices"); return nullptr; }
+    if (t->n_records > 0 && t->offs.size() != (size_t)t->n_records + 1) { set_err(-24, W + ": the stream has no record offsets"); return nullptr; }
+    if (use_device(t->device)) return nullptr;
+    if (t->n_records > 0 && !t->offs_up) {
+        if (t->d_offs.ensure(t->offs.size() * 8, 31)) return nullptr;
+        if (hipMemcpy(t->d_offs.p, t->offs.data(), t->offs.size() * 8, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); set_err(-10, W + ": upload failed"); return nullptr; }
+        t->offs_up = true;
+    }
+    static const std::vector<unsigned long long> none;
+    return sam_core(W, (const uint8_t *)t->out.p, (const unsigned long long *)t->d_offs.p, t->n_records > 0 ? t->offs : none, names, stats);
+}
+lcd_sam_text_t *lcd_records_to_sam(const uint8_t *records, size_t n_bytes, const lcd_sam_names_t *names, lcd_sam_stats_t *stats) {
+    const std::string W = "lcd_records_to_sam";
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!names || (n_bytes && !records)) { set_err(-4, W + ": NULL argument"); return nullptr; }
+    std::vector<unsigned long long> offs(1, 0ull);
+    for (size_t o = 0; o < n_bytes;) {
+        uint32_t bs = 0;
+        if (n_bytes - o >= 4) memcpy(&bs, records + o, 4);
+        if (n_bytes - o < 4 || bs < 32 || bs > (uint32_t)INT32_MAX || n_bytes - o - 4 < bs) { set_err(-24, W + ": the stream ends inside a record, or a record is shorter than its fixed fields"); return nullptr; }
+        o += 4 + (size_t)bs; offs.push_back(o);
+    }
+    if (use_device(names->device)) return nullptr;
+    DevBuf d_in, d_offs;
+    if (n_bytes) {
+        if (d_in.ensure(n_bytes + 64, 31) || d_offs.ensure(offs.size() * 8, 31)) return nullptr;
+        if (hipMemcpy(d_in.p, records, n_bytes, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_offs.p, offs.data(), offs.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError(); set_err(-10, W + ": upload failed"); return nullptr;
+        }
+    }
+    return sam_core(W, (const uint8_t *)d_in.p, (const unsigned long long *)d_offs.p, offs, names, stats);   // (synchronised before d_in leaves scope)
+}
+size_t lcd_sam_text_size(const lcd_sam_text_t *h) { return h ? h->size : 0; }
+uint64_t lcd_sam_text_dev_ptr(const lcd_sam_text_t *h) { return h ? h->text.addr() : 0; }
+int lcd_sam_text_to_host(const lcd_sam_text_t *h, size_t off, size_t n, uint8_t *out) {
+    if (!h || off > h->size || n > h->size - off || (n && !out)) return set_err(-41, "lcd_sam_text_to_host: range past the end of the text");
+    if (n == 0) return 0;
+    if (use_device(h->device)) return -1;
+    HIPCHK(hipMemcpy(out, (const uint8_t *)h->text.p + off, n, hipMemcpyDeviceToHost));
+    return 0;
+}
+void lcd_sam_text_free(lcd_sam_text_t *h) { delete h; }
 
 } // extern "C"

@@ -219,6 +219,9 @@ struct lcd_bam_writer_s {
     lcd_bai_builder_t *bai = nullptr; std::string index_path; lcd_index_stats_t *ist = nullptr; uint64_t file_off = 0;
     int sort_output = 0;     // lcd_bam_writer_set_sort
     lcd_refine_stats_t *rstats = nullptr;     // lcd_bam_writer_set_refine_stats: what the refined chunks' records became, summed over the appends
+    // lcd_bam_writer_open_sam: the records go out as SAM text (lcd_tagged_to_sam) instead of BGZF members; f may be stdout
+    bool sam = false, own_f = true; lcd_sam_names_t *names = nullptr; lcd_sam_stats_t *sstats = nullptr;
+    ~lcd_bam_writer_s() { lcd_sam_names_free(names); }
 };
 namespace {
 // download + fwrite of one compressed image, then free
@@ -259,6 +262,40 @@ int writer_index_stream(lcd_bam_writer_s *w, const lcd_tagged_t *t, const lcd_de
     if (rc == LCD_ERR_BAI_ORDER || rc == LCD_ERR_BAI_CSI || rc == LCD_ERR_BAI_CONTIG) { writer_skip_index(w, rc); return 0; }
     if (!rc && next != lcd_tagged_size(t)) return set_err(-24, "lcd_write_phased_bam: the tagged stream ends inside a record");
     return rc;
+}
+// the SAM writer's append: the tagged stream as text, download + fwrite
+int writer_put_sam(lcd_bam_writer_s *w, const lcd_tagged_t *t, const std::string &W) {
+    lcd_bam_out_t *out = w->out;
+    lcd_sam_stats_t ss;
+    lcd_sam_text_t *x = lcd_tagged_to_sam(t, w->names, &ss);
+    if (!x) return -30;
+    const double t0 = now_ms();
+    const size_t sz = lcd_sam_text_size(x);
+    w->buf.resize(sz + 1);
+    int rc = lcd_sam_text_to_host(x, 0, sz, w->buf.data());
+    if (!rc && sz && fwrite(w->buf.data(), 1, sz, w->f) != sz) rc = set_err(-30, W + ": short write on " + w->path);
+    lcd_sam_text_free(x);
+    out->bytes_file += (int64_t)sz; w->file_off += sz;
+    ss.ms_download_write = now_ms() - t0; out->ms_download_write += ss.ms_download_write;
+    if (lcd_sam_stats_t *a = w->sstats) {
+        int64_t *dst = &a->n_records; const int64_t *src = &ss.n_records;
+        for (int q = 0; q < 7; ++q) dst[q] += src[q];                    // the seven counters in front of the three times
+        a->ms_measure += ss.ms_measure; a->ms_emit += ss.ms_emit; a->ms_download_write += ss.ms_download_write;
+    }
+    return rc;
+}
+// the SAM header of lcd_bam_writer_open_sam, in place: `text` comes in as the input header's text
+void sam_header_text(std::string &text, const char *pg_line, int n_ref, char **names, const int64_t *lens) {
+    while (!text.empty() && text.back() == 0) text.pop_back();
+    if (pg_line && pg_line[0]) { if (!text.empty() && text.back() != '\n') text += '\n'; text += pg_line; text += '\n'; }
+    if (!text.empty() && text.back() != '\n') text += '\n';
+    const bool have_sq = text.compare(0, 4, "@SQ\t") == 0 || text.find("\n@SQ\t") != std::string::npos;      // a line that starts with it
+    if (!have_sq && n_ref > 0) {
+        std::string sq;
+        for (int r = 0; r < n_ref; ++r) sq += std::string("@SQ\tSN:") + names[r] + "\tLN:" + std::to_string((long long)lens[r]) + "\n";
+        const size_t at = text.compare(0, 3, "@HD") == 0 && (text.size() == 3 || text[3] == '\t' || text[3] == '\n') ? text.find('\n') + 1 : 0;
+        text.insert(at, sq);
+    }
 }
 int writer_check_chunks(const std::string &W, int n, const lcd_call_chunk_t *chunks) {
     for (int c = 0; c < n; ++c) {
@@ -336,6 +373,12 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
         out->ms_tag += now_ms() - t0;
         for (int i = 0; i < n_rec; ++i) if (!skip[i]) ++(k->rec_read[i] >= 0 ? out->n_records_out : out->n_filtered_out);
         out->bytes_inflated += (int64_t)lcd_tagged_size(t);
+        if (w->sam) {
+            const int rc = lcd_tagged_size(t) ? writer_put_sam(w, t, W) : 0;
+            lcd_tagged_free(t);
+            if (rc) return rc;
+            continue;
+        }
         lcd_deflated_t *d = lcd_tagged_size(t) ? lcd_bgzf_deflate_dev_ptr(lcd_tagged_dev_ptr(t), lcd_tagged_size(t), out->block_payload, 0) : nullptr;
         int rc = 0;
         if (lcd_tagged_size(t) && d && w->bai) rc = writer_index_stream(w, t, d);
@@ -360,7 +403,7 @@ int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output) {
 void lcd_bam_writer_abort(lcd_bam_writer_t *w) {
     if (!w) return;
     const std::string m = g_err;
-    if (w->f) fclose(w->f);
+    if (w->f && w->own_f) fclose(w->f); else if (w->f) fflush(w->f);
     if (w->bai) { lcd_bai_builder_destroy(w->bai); remove(w->index_path.c_str()); }
     delete w;
     g_err = m;
@@ -368,9 +411,9 @@ void lcd_bam_writer_abort(lcd_bam_writer_t *w) {
 int lcd_bam_writer_close(lcd_bam_writer_t *w) {
     const std::string W = "lcd_write_phased_bam";
     if (!w) return set_err(-4, W + ": NULL argument");
-    if (int rc = writer_put(w, lcd_bgzf_deflate_dev(nullptr, 0, w->out->block_payload, 1), W)) { lcd_bam_writer_abort(w); return rc; }   // the EOF member
+    if (!w->sam) if (int rc = writer_put(w, lcd_bgzf_deflate_dev(nullptr, 0, w->out->block_payload, 1), W)) { lcd_bam_writer_abort(w); return rc; }   // the EOF member
     const std::string path = w->path;
-    int rc = fclose(w->f);
+    int rc = w->own_f ? fclose(w->f) : fflush(w->f);
     w->f = nullptr;
     if (rc != 0) { lcd_bam_writer_abort(w); return set_err(-30, W + ": closing " + path + " failed"); }
     if (w->bai) {   // the index after the EOF member
@@ -402,6 +445,50 @@ lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_o
     w->bai = bai; w->ist = idx_stats; w->index_path = index_path ? std::string(index_path) : std::string(out->path) + ".bai";
     remove(w->index_path.c_str());     // (an index of an earlier file at this path would not describe the one being written)
     return w;
+}
+lcd_bam_writer_t *lcd_bam_writer_open_sam(const char *in_bam_path, lcd_bam_out_t *out) {
+    const std::string W = "lcd_write_phased_sam";
+    if (!in_bam_path || !out || !out->path) { set_err(-4, W + ": NULL argument"); return nullptr; }
+    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
+    std::vector<uint8_t> hdr;
+    if (lcd_io_bam_header(in_bam_path, hdr)) { set_err(-30, W + ": " + lcd_io_last_error()); return nullptr; }
+    int n_ref = 0; char **names = nullptr; int64_t *lens = nullptr;
+    if (lcd_bam_contigs(in_bam_path, &n_ref, &names, &lens)) return nullptr;
+    int l_text = 0; memcpy(&l_text, hdr.data() + 4, 4);
+    std::string text((const char *)hdr.data() + 8, (size_t)l_text);
+    sam_header_text(text, out->pg_line, n_ref, names, lens);
+    std::unique_ptr<lcd_bam_writer_s> w(new lcd_bam_writer_s());
+    w->sam = true; w->out = out; w->path = out->path;
+    w->names = lcd_sam_names_create(n_ref, names);
+    lcd_bam_contigs_free(n_ref, names, lens);
+    if (!w->names) return nullptr;
+    if (!strcmp(out->path, "-")) { w->f = stdout; w->own_f = false; }
+    else w->f = fopen(out->path, "wb");
+    if (!w->f) { set_err(-30, W + ": cannot open " + out->path + " for writing"); return nullptr; }
+    if (!text.empty() && fwrite(text.data(), 1, text.size(), w->f) != text.size()) {
+        if (w->own_f) fclose(w->f);
+        set_err(-30, W + ": short write on " + w->path); return nullptr;
+    }
+    out->bytes_file += (int64_t)text.size(); w->file_off += text.size();
+    return w.release();
+}
+int lcd_bam_writer_set_sam_stats(lcd_bam_writer_t *w, lcd_sam_stats_t *stats) {
+    if (!w) return set_err(-4, "lcd_bam_writer_set_sam_stats: NULL writer");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    w->sstats = stats;
+    return 0;
+}
+int lcd_write_phased_sam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats, lcd_sam_stats_t *sam_stats) {
+    const std::string W = "lcd_write_phased_sam";
+    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
+    if (sam_stats) memset(sam_stats, 0, sizeof(*sam_stats));
+    if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
+    if (int rc = writer_check_chunks(W, n, chunks)) return rc;     // (before the output file is touched)
+    lcd_bam_writer_t *w = lcd_bam_writer_open_sam(in_bam_path, out);
+    if (!w) return -30;
+    w->rstats = refine_stats; w->sstats = sam_stats;
+    if (int rc = lcd_bam_writer_append(w, n, chunks, nullptr, nullptr)) { lcd_bam_writer_abort(w); return rc; }
+    return lcd_bam_writer_close(w);
 }
 int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) { return lcd_write_phased_bam_refine(in_bam_path, n, chunks, out, nullptr); }
 int lcd_write_phased_bam_refine(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats) {

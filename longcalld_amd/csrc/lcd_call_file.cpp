@@ -398,8 +398,9 @@ namespace {
 // the whole-file run over the n input files of one sample; in == NULL: the one file of the job (lcd_call_file / lcd_call_file_indexed)
 int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
                     lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out, bool refine = false,
-                    lcd_refine_stats_t *refine_stats = nullptr) {
+                    lcd_refine_stats_t *refine_stats = nullptr, int aln_format = LCD_ALN_BAM, lcd_sam_stats_t *sam_stats = nullptr) {
     if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
+    if (sam_stats) memset(sam_stats, 0, sizeof(*sam_stats));
     if (stats) memset(stats, 0, sizeof(*stats));
     if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
     lcd_index_stats_t ist_local;
@@ -415,6 +416,9 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
         if (job->bai_path && in->bai_paths && in->bai_paths[0] && strcmp(job->bai_path, in->bai_paths[0]) != 0) return set_err(-4, W + ": job->bai_path must be NULL or the first input's index");
     }
     if (job->bam_out && !job->bam_out->path) return set_err(-4, W + ": bam_out without a path");
+    const bool sam = aln_format == LCD_ALN_SAM && job->bam_out;
+    if (sam && idx && idx->write_out_bai) return set_err(-4, W + ": a SAM output has no index (write_out_bai)");
+    if (sam && !strcmp(job->bam_out->path, "-") && (!job->vcf_path || !strcmp(job->vcf_path, "-"))) return set_err(-4, W + ": the SAM output and the VCF cannot both go to stdout");
     if (job->window_chunks < 0 || job->loader_threads < 0 || job->chunk_len < 0 || job->overlap < -1 || job->overlap > 1) return set_err(-4, W + ": negative window_chunks / loader_threads / chunk_len, or overlap outside -1 ... 1");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
     const double t_wall = now_ms();
@@ -507,10 +511,12 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
         free(hdr); free(sm);
         if (!R.vcf) { lcd_file_stats_free(stats); return -30; }
         if (job->bam_out) {
-            R.bam = idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(bam0, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(bam0, job->bam_out);
+            R.bam = sam ? lcd_bam_writer_open_sam(bam0, job->bam_out)
+                        : idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(bam0, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(bam0, job->bam_out);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
             lcd_bam_writer_set_sort(R.bam, in ? in->sort_output : 0);
             if (R.refine) lcd_bam_writer_set_refine_stats(R.bam, refine_stats);
+            if (sam) lcd_bam_writer_set_sam_stats(R.bam, sam_stats);
         }
     }
     const int n_windows = (R.plan.n + window - 1) / window;
@@ -603,4 +609,20 @@ extern "C" int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_
                                      lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_refine_stats_t *refine_stats) {
     if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats)); return set_err(-4, "lcd_call_files: NULL argument"); }
     return call_files_core("lcd_call_files", in, job, cfg, idx, nullptr, stats, idx_stats, n_reads_per_file, nullptr, true, refine_stats);
+}
+
+extern "C" int lcd_call_files_aln(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
+                                  const lcd_aln_opt_t *aln, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out,
+                                  lcd_refine_stats_t *refine_stats, lcd_sam_stats_t *sam_stats) {
+    const std::string W = "lcd_call_files_aln";
+    auto refuse = [&](int code, const std::string &m) {
+        if (stats) memset(stats, 0, sizeof(*stats)); if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
+        if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats)); if (sam_stats) memset(sam_stats, 0, sizeof(*sam_stats));
+        return set_err(code, W + ": " + m);
+    };
+    if (!aln) return refuse(-4, "NULL argument");
+    if (aln->format != LCD_ALN_BAM && aln->format != LCD_ALN_SAM) return refuse(-4, "format must be LCD_ALN_BAM or LCD_ALN_SAM");
+    if (aln->refine && fields) return refuse(-2, "refined alignments together with the VCF fields are not supported");
+    const char *name = in ? "lcd_call_files" : idx ? "lcd_call_file_indexed" : "lcd_call_file";
+    return call_files_core(name, in, job, cfg, idx, fields, stats, idx_stats, n_reads_per_file, fields_out, aln->refine != 0, refine_stats, aln->format, sam_stats);
 }

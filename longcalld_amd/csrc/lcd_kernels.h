@@ -36,6 +36,10 @@ void lcd_launch_bam_tag_emit(const BamTagJob *jobs, const BamTagOut *outs, uint8
 void lcd_launch_bam_refine_measure(const BamRefineJob *jobs, BamRefineOut *outs, const uint8_t *ref, long long ref_beg, long long ref_end, int n_jobs, hipStream_t st);
 void lcd_launch_bam_refine_emit(const BamRefineJob *jobs, const BamRefineOut *outs, const uint8_t *ref, long long ref_beg, long long ref_end, uint8_t *out, int n_jobs,
                                 hipStream_t st);
+// bam_sam_kernel.hip: records in HBM as SAM text lines: measure (the length, flags and float count of every line) and emit (the lines at text_off[]), one
+// wavefront per record each
+void lcd_launch_bam_sam_measure(const BamSamIn &in, BamSamOut *outs, hipStream_t st);
+void lcd_launch_bam_sam_emit(const BamSamIn &in, const unsigned long long *text_off, uint8_t *text, hipStream_t st);
 // bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
 // counters; compact: scan of the workgroups' run heads + the dense chunk list)
 void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);

@@ -273,6 +273,13 @@ enum { LCD_REFINE_FILTERED = 0, LCD_REFINE_CHANGED = 1, LCD_REFINE_IDENTICAL = 2
 // flags: bit 0..4 = NM:i / MD:Z / cs:Z / HP:i / PS:i appended (in that order), bit 5 = the CIGAR words come from `words`, bit 6 = pos and bin are patched;
 // del_*: up to five deleted fields as [beg, end) offsets from src, ascending, an absent one is [len, len); md_len / cs_len: the generated texts without their NUL
 struct BamRefineOut { uint32_t new_len, flags, state, n_ops, md_len, cs_len, new_bin; int nm, new_pos, pos_moved; uint32_t del_beg[5], del_end[5]; uint64_t dst; };
+// ---------------- records as SAM text (bam_sam_kernel.hip) ----------------
+// the records lie back to back at `base`: record i is [rec_off[i], rec_off[i + 1]) with its block_size word first (at least 36 bytes); names: the contigs' names
+// back to back, name r = [name_off[r], name_off[r + 1]); text_off[i]: where line i starts in the text (the host's prefix sum over BamSamOut::len)
+struct BamSamIn { const uint8_t *base; const unsigned long long *rec_off; const uint8_t *names; const unsigned *name_off; int n_ref, n_rec; };
+// what the measure pass found: the line's length with its '\n'; flags bit 0: the CIGAR came from a CG field, bit 1: the field walk stopped in front of the
+// record's end, bit 2: name / CIGAR / bases / qualities do not fit the record; n_float: f values printed (scalar fields and B:f elements)
+struct BamSamOut { unsigned long long len; uint32_t flags, n_float; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;
