@@ -847,7 +847,8 @@ void lcd_first_round_free(lcd_first_chunk_t *c);
  * meta) gives the reads' span; the reference window is fetched around min(reg_beg, read begins) / max(reg_end, read ends) with get_bam_chunk_reg_ref_seq0's
  * 50 000-base padding (src/bam_utils.c:1558-1571) -- the reference, too, loads first and fetches then; when the pass left a read without a digar source (an 'M'
  * CIGAR: status -2) or the data is ONT (the SA-tag rule), the chunk is made again through lcd_chunk_create_from_bam_src with that window.  Then lcd_chunks_call;
- * the chunk handles are destroyed before the call returns (chunks[c].first.chunk / ref_seq / meta are NULL afterwards).  chunks: n caller-allocated entries. */
+ * the chunk handles are destroyed before the call returns (chunks[c].first.chunk / ref_seq / meta are NULL afterwards).  chunks: n caller-allocated entries.  It is
+ * declared with the other drivers and their options at the end of this header. */
 typedef struct lcd_cfg_t { lcd_clean_opt_t clean; lcd_opt_t opt; lcd_pass_opt_t pass; lcd_call_opt_t call; } lcd_cfg_t;
 void lcd_cfg_default(lcd_cfg_t *cfg, int is_ont);   /* lcd_clean_opt_default(is_ont), lcd_opt_default + is_ont, lcd_pass_opt_default, lcd_call_opt_default */
 typedef struct lcd_call_chunk_t {
@@ -855,8 +856,6 @@ typedef struct lcd_call_chunk_t {
     int n_passes, flip_hap; int64_t flip_pre_PS, flip_cur_PS; int n_records;   /* out */
 } lcd_call_chunk_t;
 int lcd_chunks_call(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body);
-int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
-                         const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body);
 void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, int n_records, char *vcf_body);
 
 /* ---- the phased alignment output (longcallD call -b): write_read_to_bam / write_processed_read_to_bam / write_unprocessed_read_to_bam, src/bam_utils.c:1944-2048 ----
@@ -870,12 +869,12 @@ void lcd_call_free(int n_chunks, lcd_call_chunk_t *chunks, lcd_var1_t *records, 
  * field is deleted.  Later fields of the same name stay.  The record is its bytes without the deleted fields, the appended HP, the appended PS; only block_size
  * changes.  A filtered record loses its first HP and first PS field.  The first n_skip_kept kept and n_skip_filtered filtered records are not written (the region
  * before has written them).  NULL + lcd_last_error for a chunk that was not made from a BAM.
- * lcd_write_phased_bam (after lcd_chunks_call, before lcd_call_free / the chunks' destruction): the input file's header block with pg_line (one finished @PG line
+ * lcd_write_phased (after lcd_chunks_call, before lcd_call_free / the chunks' destruction): the input file's header block with pg_line (one finished @PG line
  * without a newline, or NULL) appended to its text, compressed into its own block(s); then region c's records in region order, the skip counts of region c being
  * its kept / filtered records that overlap region c - 1's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691); every region's stream through
  * lcd_bgzf_deflate_dev_ptr; the EOF member last.  Only compressed bytes cross PCIe; the file is written with fwrite.  htslib's sam_hdr_add_pg chooses ID / PP
- * itself and is not in the checkout: the @PG text is the caller's.  No .bai is written by these entry points (lcd_bam_writer_open_indexed writes one); --refine-aln and CRAM output are not supported (several input files: lcd_call_files; SAM text: lcd_bam_writer_open_sam).
- * lcd_call_bam_regions_out: lcd_call_bam_regions with the alignment output written after lcd_chunks_call succeeded (bam_out NULL: none).  A failure of the output
+ * itself and is not in the checkout: the @PG text is the caller's.  CRAM output is not supported.
+ * lcd_call_bam_regions with bam_out: the alignment output is written after lcd_chunks_call succeeded (bam_out NULL: none).  A failure of the output
  * (unwritable path) returns < 0 with lcd_last_error and leaves *records / *vcf_body / the chunks' out members valid: free them with lcd_call_free as usual. */
 typedef struct lcd_tagged_s lcd_tagged_t;
 lcd_tagged_t *lcd_chunk_tag_records(const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, int n_skip_kept, int n_skip_filtered);
@@ -888,10 +887,6 @@ typedef struct lcd_bam_out_t {
     const char *path; const char *pg_line; int block_payload;        /* in; pg_line may be NULL, block_payload 0 = 0xff00 */
     int64_t n_records_out, n_filtered_out, bytes_inflated, bytes_file; double ms_tag, ms_deflate, ms_download_write;   /* out */
 } lcd_bam_out_t;
-int lcd_write_phased_bam(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out);
-int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
-                             const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
-                             lcd_bam_out_t *bam_out);
 
 /* ---- a whole BAM in one call (longcallD call ref.fa in.bam -o out.vcf -b out.bam): call_var_worker_pipeline, src/call_var_main.c:762-815, germline path ----
  * lcd_bam_contigs: the reference table of the BAM header, in header order.  *names: n malloc()'d strings in a malloc()'d array, *lens malloc()'d; release with
@@ -948,9 +943,9 @@ int lcd_chunk_resolve(lcd_chunk_t *chunk, const lcd_chunk_src_t *src);
  * accumulate.  append: the records of n called chunks in order (lcd_chunk_tag_records + lcd_bgzf_deflate_dev_ptr per chunk); a chunk leaves out the records that
  * overlap the region of the chunk before it when both are on the same contig (tids[c] == tids[c - 1]; tids NULL: all the same) -- across a window border that chunk
  * is described by prev (NULL: none; prev->valid, tid, reg_beg, reg_end are read).  close: the one EOF member and fclose; lcd_bam_writer_abort closes the file as
- * it is, without the EOF member.  Both free the writer.  lcd_write_phased_bam is open + one append + close.  *out must outlive the writer. */
+ * it is, without the EOF member.  Both free the writer.  lcd_write_phased is open + one append + close.  *out must outlive the writer.  lcd_bam_writer_open and
+ * lcd_write_phased are declared with their options (lcd_writer_opt_t) at the end of this header. */
 typedef struct lcd_bam_writer_s lcd_bam_writer_t;
-lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out);
 int lcd_bam_writer_append(lcd_bam_writer_t *w, int n_chunks, const lcd_call_chunk_t *chunks, const int *tids, const lcd_stitch_carry_t *prev);
 int lcd_bam_writer_close(lcd_bam_writer_t *w);
 void lcd_bam_writer_abort(lcd_bam_writer_t *w);
@@ -961,7 +956,7 @@ lcd_vcf_writer_t *lcd_vcf_writer_open(const char *path, int bgzf, const char *he
 int lcd_vcf_writer_append(lcd_vcf_writer_t *w, const char *text);
 int lcd_vcf_writer_close(lcd_vcf_writer_t *w);
 void lcd_vcf_writer_abort(lcd_vcf_writer_t *w);
-/* lcd_call_file: the whole-file run.  The plan (lcd_plan_chunks on the BAM header) is processed in windows of window_chunks consecutive entries (a window may span
+/* lcd_call_files: the whole-file run (declared with its options at the end of this header).  The plan (lcd_plan_chunks on the BAM header) is processed in windows of window_chunks consecutive entries (a window may span
  * contigs).  Per window -- load: every chunk is opened (lcd_chunk_open_from_bam, up to loader_threads host threads), its reference window fetched around the reads'
  * span with get_bam_chunk_reg_ref_seq0's padding, and resolved with that window (one file read and one inflate per chunk); a chunk without reads stays as an empty
  * entry: it yields nothing, but it is still the neighbour of the chunks beside it.  call: the body of lcd_chunks_call with a contig per chunk, the first chunk's up
@@ -969,7 +964,7 @@ void lcd_vcf_writer_abort(lcd_vcf_writer_t *w);
  * text to the VCF writer, the window to the BAM writer; then the window is freed: nothing of it stays but the carry.  overlap 1: the three stages run on three host
  * threads joined by queues of depth one (at most three windows alive); 0: in turn on the calling thread.  Records, text, flips and the output BAM's record stream do
  * not depend on window_chunks, overlap or loader_threads.  The first error stops the pipeline, every thread is joined, both outputs are closed as they are (no EOF
- * member) and the failing stage's code and lcd_last_error are returned.  Somatic / refine settings: -2.  A missing .bai / .fai: -30 with the path in the message (lcd_call_file_indexed builds them on request).
+ * member) and the failing stage's code and lcd_last_error are returned.  Somatic / refine settings: -2.  A missing .bai / .fai: -30 with the path in the message (lcd_run_opt_t.idx builds them on request).
  * Defaults: chunk_len 0 = 500 000; window_chunks 0 = 32 (HiFi) / 16 (ONT); overlap -1 = 0 (pipelining did not win reliably where it was measured, profiles/NOTES_call_file.md);
  * loader_threads 0 = 4, or the CPUs the process may use when fewer (an explicit value is cut to 16); bai_path NULL =
  * <bam>.bai; sample_name NULL = lcd_bam_sample_name, else the BAM path; vcf_path NULL or "-" = stdout.  The VCF header names every contig of the BAM header.
@@ -996,7 +991,6 @@ typedef struct lcd_file_stats_t {
     lcd_var1_t *records; int n_kept_records;
 } lcd_file_stats_t;
 void lcd_file_job_default(lcd_file_job_t *job);     /* zeroes; overlap = -1 */
-int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats);
 void lcd_file_stats_free(lcd_file_stats_t *stats);
 
 /* ---- indexes: .bai built on the device, .fai on the host (htslib's sam_index_build / fai_build are not in the checkout; src/call_var_main.c:675-686 builds a
@@ -1059,13 +1053,13 @@ typedef struct lcd_bai_stats_t {
 } lcd_bai_stats_t;
 int lcd_bai_build(const char *bam_path, const char *out_path, const lcd_bai_opt_t *opt /* may be NULL */, lcd_bai_stats_t *stats /* may be NULL */);
 int lcd_fai_build(const char *fasta_path, const char *out_path /* NULL: <fasta>.fai */);
-/* The outputs with their indexes.  lcd_bam_writer_open_indexed: the writer owns a builder; after each append's tag rewrite and deflate the tagged stream in HBM goes
+/* The outputs with their indexes.  lcd_writer_opt_t.write_index: the writer owns a builder; after each append's tag rewrite and deflate the tagged stream in HBM goes
  * to add_stream with the member table the deflater reports and the writer's running file offset; close writes the index to index_path (NULL: <out.bam>.bai) after
  * the EOF member.  If the output violates rule 3 -- lcd_plan_chunks sorts and merges a contig's regions, so the plan cannot cause it; an input whose records are out
  * of order inside a region can, and so can a caller of lcd_bam_writer_append who hands chunks over out of order -- or names a position outside the header's contigs
  * (LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_BAI_CONTIG), the BAM is still completed, no index file is left behind and idx_stats says so: that is not an error of
  * the run.  Any other failure of the index (a malformed record in the writer's own stream, a device error) fails the append.  *idx_stats must outlive the writer.
- * lcd_call_file_indexed: lcd_call_file is this call with idx == NULL.  build_missing_bai / build_missing_fai: a missing input index is built at the path the job
+ * lcd_index_opt_t (lcd_run_opt_t.idx of lcd_call_files; NULL: none of it).  build_missing_bai / build_missing_fai: a missing input index is built at the path the job
  * would have read (bai_path or <bam>.bai, <fasta>.fai) and the run goes on; an unwritable location is -30 with the path in the message; an index that exists is
  * never rebuilt or touched.  write_out_bai needs job->bam_out; out_bai_path NULL = <out.bam>.bai. */
 typedef struct lcd_index_opt_t { int build_missing_bai, build_missing_fai, write_out_bai; const char *out_bai_path; int slab_members; } lcd_index_opt_t;
@@ -1074,8 +1068,6 @@ typedef struct lcd_index_stats_t {
     char out_bai_skip_reason[256];
     int64_t out_bai_bytes, out_n_indexed, out_n_no_coor; double ms_build_bai, ms_build_fai, ms_out_bai;
 } lcd_index_stats_t;
-lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_out_t *out, const char *index_path, lcd_index_stats_t *idx_stats);
-int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats);
 
 /* ---- one sample from several alignment files (longcallD call ref.fa in.bam -X more.bam ... / -L list): src/call_var_main.c:361-400, 640-741 ----
  * The ordinary shape of a PacBio / ONT sample is one BAM per SMRT cell or flow cell.  A chunk is made from a region image (whole BGZF blocks plus ranges of the
@@ -1101,18 +1093,18 @@ int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const
  *   5 sort_output  additive: within each chunk the records to be written are ordered by (pos0, file index, position in the file), stable, before the tag rewrite -- a
  *                  host sort of the job table.  A chunk only writes records that do not overlap its predecessor, so the file is non-decreasing in (refid, pos) and the
  *                  output's .bai can be written.  Without it interleaved inputs make the index builder give up with LCD_ERR_BAI_ORDER: the BAM is completed, no index
- *                  is left, out_bai_skipped says so (lcd_bam_writer_open_indexed's rule, unchanged).
+ *                  is left, out_bai_skipped says so (the indexing writer's rule, unchanged).
  * lcd_chunk_open_from_bams: lcd_chunk_open_from_bam over n_bams files (1 ... LCD_MAX_INPUTS; bai_paths NULL, or an entry NULL: <bam>.bai); n_bams = 1 is
  * lcd_chunk_open_from_bam.  meta->tid / n_targets / target_len are file 0's.  lcd_chunk_n_files; lcd_chunk_read_files: per kept read its file index (returns n_reads).
  * lcd_merged_record_plan (pure host code): rules 4 and 5 on a record table in file-major order -- skip[i] = 1 for a record left out; order[0 .. m) = the records to
  * write in output order, order[m .. n_rec) = -1; returns m.  rec_file NULL: one file.  has_prev 0: nothing is left out.  -4 for n_rec < 0 or a NULL table.
  * lcd_chunk_tag_records_sel: lcd_chunk_tag_records for the records with skip[i] == 0 (skip NULL: all), in the order `order` names them (as the plan gives it; NULL:
  * table order); an order that does not name every such record exactly once is -4.
- * lcd_bam_writer_set_sort: the writer's appends use the plan with sort_output (default 0).  With one sorted input and 0 an append writes the bytes it always wrote.
- * lcd_call_files: lcd_call_file_indexed over in->n files (idx / idx_stats may be NULL).  job->bam_path / bai_path must be NULL or equal entry 0 (-4).  Every file's
+ * lcd_writer_opt_t.sort_output: the writer's appends use the plan with sort_output (default 0).  With one sorted input and 0 an append writes the bytes it always wrote.
+ * lcd_call_files over in->n files: in->sort_output is the writer's.  job->bam_path / bai_path must be NULL or equal entry 0 (-4).  Every file's
  * .bai is looked for (in->bai_paths NULL, or an entry NULL: <bam>.bai) and, with build_missing_bai, built at its own path; existing ones are never touched; a
  * missing one without the option is -30 with that path.  n_reads_per_file (in->n entries, or NULL): the kept reads each file contributed, summed over the chunks.
- * With in->n == 1 the run is lcd_call_file_indexed.  NULL in, n < 1, n > LCD_MAX_INPUTS or a NULL path: -4. */
+ * in == NULL is the job's one file (job->bam_path / bai_path), and in->n == 1 is that run byte for byte.  n < 1, n > LCD_MAX_INPUTS or a NULL path: -4. */
 #define LCD_ERR_INPUT_HEADERS (-54)
 #define LCD_MAX_INPUTS 64
 typedef struct lcd_inputs_t { int n; const char *const *bam_paths; const char *const *bai_paths; int sort_output; } lcd_inputs_t;
@@ -1123,9 +1115,6 @@ int lcd_chunk_read_files(const lcd_chunk_t *chunk, int *file_of_read);
 int lcd_merged_record_plan(int n_rec, const int *rec_file, const int64_t *rec_pos0, const int64_t *rec_endpos, int has_prev, int64_t prev_beg, int64_t prev_end,
                            int sort_output, uint8_t *skip, int *order);
 lcd_tagged_t *lcd_chunk_tag_records_sel(const lcd_chunk_t *chunk, const int *haps, const int64_t *phase_sets, const uint8_t *skip, const int *order);
-int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output);
-int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
-                   lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file /* n entries or NULL */);
 
 /* ---- VCF content: MEI annotation from a TE library (longcallD call -T FILE) and supporting read names (--out-var-rnames / --out-sv-rnames) ----
  * lcd_te_lib_from_fasta == make_te_kmer_idx (src/kmer.c:120-148) with its file reading: every record of a plain or gzip-compressed FASTA file (gzopen / gzread) as
@@ -1147,7 +1136,7 @@ int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_
  * without meta->name_off / name_pool: -4), whatever the number of chunks, contigs, windows or input files (several files: the reads, and so the names, are
  * file-major).  `fields` NULL or all zero: the text and every output file are byte-identical to the entry point without it.
  * lcd_vcf_fields_out_t (may be NULL; release with lcd_vcf_fields_out_free): the library's names, the MEI lines written, and -- with a names mode -- per returned /
- * kept record (*records of lcd_chunks_call_fields / lcd_call_bam_regions_fields, stats->records with keep_records) its ALTREADS value, NULL for a record the mode
+ * kept record (*records of lcd_chunks_call_fields / lcd_call_bam_regions, stats->records with keep_records) its ALTREADS value, NULL for a record the mode
  * leaves out.  --out-som-var-rnames belongs to somatic mode and is not supported. */
 #define LCD_RNAMES_NONE 0
 #define LCD_RNAMES_SV 1
@@ -1160,17 +1149,9 @@ int lcd_format_vcf_fields(const lcd_call_opt_t *opt, const char *chrom, const lc
                           const uint64_t *name_off, const char *name_pool, char **text_out, int *n_mei);
 int lcd_alt_read_names(const lcd_var1_t *var, int n_reads, const uint64_t *name_off, const char *name_pool, char **out);
 void lcd_vcf_fields_out_free(lcd_vcf_fields_out_t *out);
-/* the drivers with the options: lcd_chunks_call, lcd_call_bam_regions_out (bam_out may be NULL: lcd_call_bam_regions), lcd_call_file_indexed (idx may be NULL:
- * lcd_call_file) and lcd_call_files are these calls with fields == NULL and fields_out == NULL */
+/* lcd_chunks_call is lcd_chunks_call_fields with fields == NULL and fields_out == NULL; the file drivers take both through lcd_run_opt_t / lcd_run_out_t */
 int lcd_chunks_call_fields(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const lcd_vcf_fields_t *fields, lcd_var1_t **records,
                            int *n_records, char **vcf_body, lcd_vcf_fields_out_t *fields_out);
-int lcd_call_bam_regions_fields(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
-                                const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records,
-                                int *n_records, char **vcf_body, lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out);
-int lcd_call_file_fields(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields, lcd_file_stats_t *stats,
-                         lcd_index_stats_t *idx_stats, lcd_vcf_fields_out_t *fields_out);
-int lcd_call_files_fields(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
-                          lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out);
 
 /* ---- refined alignments in the phased output (longcallD call --refine-aln -b): refine_bam1 + update_bam1_tags (src/bam_utils.c:1718-1942) in HBM ----
  * lcd_chunk_refine_records == lcd_chunk_tag_records_sel (same records, same skip / order selection, same handle) where every KEPT record is first rewritten with the
@@ -1250,28 +1231,18 @@ lcd_tagged_t *lcd_chunk_refine_records(const lcd_chunk_t *chunk, int n_touched, 
 
 /* The drivers with refined alignments (longcallD call --refine-aln -b; here --refine-bam).  A chunk handle carries its own sink: lcd_chunk_set_refine(chunk, 1)
  * gives it an empty refine log (0 takes it away; lcd_chunk_refine_log: the log, owned by the handle).  chunks_call's rounds then write that log
- * (lcd_chunks_noisy_rounds_log), and the alignment writer -- lcd_bam_writer_append / lcd_write_phased_bam -- rewrites such a chunk's records with
+ * (lcd_chunks_noisy_rounds_log), and the alignment writer -- lcd_bam_writer_append / lcd_write_phased -- rewrites such a chunk's records with
  * lcd_chunk_refine_records instead of lcd_chunk_tag_records_sel: lcd_chunk_digars once and only if the log has entries, lcd_refine_log_apply, the touched reads'
  * final lists up, the window = the chunk's first.ref_seq / ref_beg / ref_end.  The VCF, HP and PS of a run are those of the run without it.  A several-file chunk
  * is one chunk with a selection and goes the same way.  A right-cover rewrite can move POS: the output may stop being sorted; the writer then completes without
  * <out.bam>.bai and says why (out_bai_skipped / out_bai_skip_reason), as for any unsorted stream; nothing is sorted here.
- * lcd_chunks_call_refine: lcd_chunk_set_refine on every chunk, then lcd_chunks_call.  lcd_write_phased_bam_refine / lcd_bam_writer_set_refine_stats: the writer
- * with the sum of the refined chunks' lcd_refine_stats_t (counters, times, and the logs: n_log_entries, bytes_log_down = the rows that came down,
- * n_log_rejected = entries double_check_digar rejected); stats NULL: no sum.  lcd_call_bam_regions_refine == lcd_call_bam_regions_out, lcd_call_file_refine ==
- * lcd_call_file_indexed (idx may be NULL), lcd_call_files_refine == lcd_call_files, each with every chunk refined when an alignment output is asked for; without
- * bam_out the option has no effect, as in the reference.  Existing entry points, structs, return codes and messages are unchanged. */
+ * lcd_chunks_call_refine: lcd_chunk_set_refine on every chunk, then lcd_chunks_call.  lcd_writer_opt_t.refine_stats: the writer's sum of the refined chunks'
+ * lcd_refine_stats_t (counters, times, and the logs: n_log_entries, bytes_log_down = the rows that came down, n_log_rejected = entries double_check_digar
+ * rejected); NULL: no sum.  lcd_aln_opt_t.refine of the file drivers: every chunk is refined when an alignment output is asked for; without bam_out the option
+ * has no effect, as in the reference. */
 int lcd_chunk_set_refine(lcd_chunk_t *chunk, int on);
 lcd_refine_log_t *lcd_chunk_refine_log(const lcd_chunk_t *chunk);
 int lcd_chunks_call_refine(int n_chunks, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, lcd_var1_t **records, int *n_records, char **vcf_body);
-int lcd_write_phased_bam_refine(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats);
-int lcd_bam_writer_set_refine_stats(lcd_bam_writer_t *w, lcd_refine_stats_t *refine_stats);
-int lcd_call_bam_regions_refine(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
-                                const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
-                                lcd_bam_out_t *bam_out, lcd_refine_stats_t *refine_stats);
-int lcd_call_file_refine(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats,
-                         lcd_refine_stats_t *refine_stats);
-int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
-                          lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_refine_stats_t *refine_stats);
 
 /* ---- the alignment output as SAM text (the reference's -S FILE, src/call_var_main.c:961; here --sam FILE): records formatted in HBM (bam_sam_kernel.hip) ----
  * lcd_tagged_to_sam turns a tagged / refined stream where it lies into SAM lines (SAM specification 1.4), one wavefront per record: a measure pass, the host's
@@ -1296,15 +1267,14 @@ int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_t *job, con
  *   A float prints exactly as glibc's printf("%g", (double)x): csrc/sam_fmt.h, exact on the value, no double arithmetic.
  * lcd_sam_names_create uploads the contigs' names once (n_ref == 0: none).  lcd_sam_stats_t: bytes_records in, bytes_text out; ms_measure includes the length
  * download, ms_download_write is the writer's.
- * lcd_bam_writer_open_sam gives the same writer object as lcd_bam_writer_open: append runs the same skip / order plan, the same tag / refine rewrite and then
+ * lcd_writer_opt_t.format LCD_ALN_SAM gives the same writer object as LCD_ALN_BAM: append runs the same skip / order plan, the same tag / refine rewrite and then
  * lcd_tagged_to_sam instead of the deflate; only text comes down.  block_payload is ignored, ms_deflate stays 0, bytes_file counts text, close writes no EOF member,
- * path "-" is stdout.  lcd_bam_writer_set_sort / _set_refine_stats / _set_sam_stats (the sum over the appends; NULL: none) work on it.  The header is the input
+ * path "-" is stdout.  sort_output, refine_stats and sam_stats (the sum over the appends; NULL: none) work on it.  The header is the input
  * header's text with trailing NULs dropped, pg_line appended as the BAM writer appends it, a newline at its end; PROJECT RULE: if no line starts with "@SQ\t" and
  * the binary table has contigs, @SQ\tSN:<name>\tLN:<len> lines in table order go straight behind a leading @HD line, or to the front when there is none.
- * lcd_write_phased_sam is open + one append + close.
- * lcd_call_files_aln: lcd_call_files_fields / _refine with the alignment output's format chosen (in NULL: the job's one file; fields may be NULL).  format SAM with
- * idx->write_out_bai: -4; refine together with fields: -2; a SAM output on stdout while the VCF goes to stdout: -4, before any file is created.  The records, the
- * VCF, HP and PS of a run do not depend on the format.  A several-file run uses file 0's header, as the BAM output does. */
+ * lcd_aln_opt_t of lcd_call_files: the alignment output's format and whether its records are refined.  format SAM with idx->write_out_bai: -4; refine together
+ * with fields: -2; a SAM output on stdout while the VCF goes to stdout: -4, before any file is created.  The records, the VCF, HP and PS of a run do not depend on
+ * the format.  A several-file run uses file 0's header, as the BAM output does. */
 typedef struct lcd_sam_names_s lcd_sam_names_t;
 typedef struct lcd_sam_text_s lcd_sam_text_t;
 typedef struct lcd_sam_stats_t {
@@ -1319,15 +1289,40 @@ size_t lcd_sam_text_size(const lcd_sam_text_t *h);
 uint64_t lcd_sam_text_dev_ptr(const lcd_sam_text_t *h);
 int lcd_sam_text_to_host(const lcd_sam_text_t *h, size_t off, size_t n, uint8_t *out);
 void lcd_sam_text_free(lcd_sam_text_t *h);
-lcd_bam_writer_t *lcd_bam_writer_open_sam(const char *in_bam_path, lcd_bam_out_t *out);
-int lcd_bam_writer_set_sam_stats(lcd_bam_writer_t *w, lcd_sam_stats_t *sam_stats);
-int lcd_write_phased_sam(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats,
-                         lcd_sam_stats_t *sam_stats);
 enum { LCD_ALN_BAM = 0, LCD_ALN_SAM = 1 };
 typedef struct lcd_aln_opt_t { int format, refine; } lcd_aln_opt_t;
-int lcd_call_files_aln(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
-                       const lcd_aln_opt_t *aln, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out,
-                       lcd_refine_stats_t *refine_stats, lcd_sam_stats_t *sam_stats);
+
+/* ---- the four drivers and their options ----
+ * Every optional feature of the sections above is a member of one of three structs; a NULL struct or a NULL / zero member means the feature is off, and a run
+ * without options writes the bytes it always wrote.
+ * lcd_run_opt_t (in): idx = the indexes (lcd_index_opt_t), fields = the VCF content (lcd_vcf_fields_t), aln = the alignment output's format and refinement
+ * (lcd_aln_opt_t).  aln->format outside LCD_ALN_BAM / LCD_ALN_SAM: -4; aln->refine together with fields: -2.
+ * lcd_run_out_t (out): what the run reports beside *stats; NULL: not reported.  Every non-NULL member is zeroed on entry, on refusal paths too
+ * (n_reads_per_file: in->n entries, 1 without `in`, zeroed once the inputs are accepted).  refine_stats / sam_stats are the writer's sums and stay zero when
+ * the run does not refine / does not write SAM.
+ * lcd_writer_opt_t: format (LCD_ALN_BAM / LCD_ALN_SAM, else -4), sort_output, write_index with index_path (NULL: <out>.bai) and idx_stats (not zeroed by the
+ * writer: a run may have counted the input indexes it built there), refine_stats and sam_stats (zeroed at open, summed over the appends).  SAM with write_index: -4.
+ * Everything named here must outlive the writer.
+ * lcd_call_files(in, job, cfg, opt, stats, out): the whole-file run.  in == NULL: the one file job->bam_path / bai_path; neither `in` nor job->bam_path: -4.
+ * Refusals come before an index is built or an output file is created.
+ * lcd_call_bam_regions(..., bam_out, opt, out): the regions of one contig; bam_out NULL: no alignment output.  opt->fields, opt->aln->refine (with bam_out) and
+ * out->fields_out / refine_stats as above.  This driver writes BAM only and builds no index: aln->format LCD_ALN_SAM is -2 and a non-NULL opt->idx is -4;
+ * out->n_reads_per_file is not written.
+ * lcd_bam_writer_open(in_bam_path, out, wopt): the appendable writer (lcd_bam_writer_append / _close / _abort above).  The index path is removed at open and by abort.
+ * lcd_write_phased(in_bam_path, n_chunks, chunks, out, wopt): open + one append + close; the chunks are checked before the output is touched. */
+typedef struct lcd_run_opt_t { const lcd_index_opt_t *idx; const lcd_vcf_fields_t *fields; const lcd_aln_opt_t *aln; } lcd_run_opt_t;
+typedef struct lcd_run_out_t {
+    lcd_index_stats_t *idx_stats; int64_t *n_reads_per_file; lcd_vcf_fields_out_t *fields_out; lcd_refine_stats_t *refine_stats; lcd_sam_stats_t *sam_stats;
+} lcd_run_out_t;
+typedef struct lcd_writer_opt_t {
+    int format, sort_output, write_index; const char *index_path; lcd_index_stats_t *idx_stats; lcd_refine_stats_t *refine_stats; lcd_sam_stats_t *sam_stats;
+} lcd_writer_opt_t;
+int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out);
+int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
+                         const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                         lcd_bam_out_t *bam_out, const lcd_run_opt_t *opt, const lcd_run_out_t *out);
+lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out, const lcd_writer_opt_t *wopt);
+int lcd_write_phased(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, const lcd_writer_opt_t *wopt);
 
 #ifdef __cplusplus
 }

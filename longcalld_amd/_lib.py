@@ -171,7 +171,7 @@ class LcdCallChunk(C.Structure):
 
 
 class LcdBamOut(C.Structure):
-    """lcd_bam_out_t: the phased alignment output of lcd_call_bam_regions_out / lcd_write_phased_bam"""
+    """lcd_bam_out_t: the phased alignment output of lcd_call_bam_regions / lcd_write_phased"""
     _fields_ = [("path", C.c_char_p), ("pg_line", C.c_char_p), ("block_payload", C.c_int)] + [(n, C.c_int64) for n in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file")] + [
         (n, C.c_double) for n in ("ms_tag", "ms_deflate", "ms_download_write")]
 
@@ -196,7 +196,7 @@ class LcdChunkPlan(C.Structure):
 
 
 class LcdFileJob(C.Structure):
-    """lcd_file_job_t: one whole-file run of lcd_call_file"""
+    """lcd_file_job_t: one whole-file run of lcd_call_files"""
     _fields_ = [("bam_path", C.c_char_p), ("bai_path", C.c_char_p), ("fasta_path", C.c_char_p), ("contig_mode", C.c_int), ("n_exclude", C.c_int),
                 ("exclude", C.POINTER(C.c_char_p)), ("n_regions", C.c_int), ("regions", C.POINTER(C.c_char_p)), ("region_bed_path", C.c_char_p), ("chunk_len", C.c_int64),
                 ("window_chunks", C.c_int), ("overlap", C.c_int), ("loader_threads", C.c_int), ("min_mapq", C.c_int), ("vcf_path", C.c_char_p), ("vcf_bgzf", C.c_int),
@@ -205,7 +205,7 @@ class LcdFileJob(C.Structure):
 
 
 class LcdFileStats(C.Structure):
-    """lcd_file_stats_t: the counters of lcd_call_file (and, with keep_records, the per-chunk results and the records)"""
+    """lcd_file_stats_t: the counters of lcd_call_files (and, with keep_records, the per-chunk results and the records)"""
     _i32p, _i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
     _fields_ = [(n, C.c_int) for n in ("n_planned", "n_loaded", "n_empty", "n_windows", "plan_fallback")] + [
         (n, C.c_int64) for n in ("n_reads", "n_records", "n_vcf_lines", "n_region_loads")] + [(n, C.c_double) for n in ("ms_load", "ms_call", "ms_write", "ms_wall")] + [
@@ -230,7 +230,7 @@ class LcdBaiStats(C.Structure):
 
 
 class LcdIndexOpt(C.Structure):
-    """lcd_index_opt_t: what lcd_call_file_indexed builds and writes"""
+    """lcd_index_opt_t: what lcd_call_files builds and writes (lcd_run_opt_t.idx)"""
     _fields_ = [("build_missing_bai", C.c_int), ("build_missing_fai", C.c_int), ("write_out_bai", C.c_int), ("out_bai_path", C.c_char_p), ("slab_members", C.c_int)]
 
 
@@ -273,6 +273,23 @@ class LcdAlnOpt(C.Structure):
     _fields_ = [("format", C.c_int), ("refine", C.c_int)]
 
 
+class LcdRunOpt(C.Structure):
+    """lcd_run_opt_t: the optional features of lcd_call_files / lcd_call_bam_regions; a NULL member is off"""
+    _fields_ = [("idx", C.POINTER(LcdIndexOpt)), ("fields", C.POINTER(LcdVcfFields)), ("aln", C.POINTER(LcdAlnOpt))]
+
+
+class LcdRunOut(C.Structure):
+    """lcd_run_out_t: what a driver reports beside its statistics; a NULL member is not reported"""
+    _fields_ = [("idx_stats", C.POINTER(LcdIndexStats)), ("n_reads_per_file", C.POINTER(C.c_int64)), ("fields_out", C.POINTER(LcdVcfFieldsOut)),
+                ("refine_stats", C.POINTER(LcdRefineStats)), ("sam_stats", C.POINTER(LcdSamStats))]
+
+
+class LcdWriterOpt(C.Structure):
+    """lcd_writer_opt_t: the options of lcd_bam_writer_open / lcd_write_phased"""
+    _fields_ = [("format", C.c_int), ("sort_output", C.c_int), ("write_index", C.c_int), ("index_path", C.c_char_p), ("idx_stats", C.POINTER(LcdIndexStats)),
+                ("refine_stats", C.POINTER(LcdRefineStats)), ("sam_stats", C.POINTER(LcdSamStats))]
+
+
 class LcdRefineEntry(C.Structure):
     """lcd_refine_entry_t: one (cluster, read) of a resolved noisy region -- what lcd_update_digars_from_msa1 takes"""
     _fields_ = [(n, C.c_int) for n in ("read_id", "cover", "read_beg", "read_end", "aln_len", "pass_")] + [("reg_beg", C.c_int64), ("reg_end", C.c_int64),
@@ -302,21 +319,18 @@ EXPORTS = [
     "lcd_chunk_read_nm", "lcd_sort_chunk_reads", "lcd_chunks_first_round", "lcd_first_round_free",
     "lcd_cfg_default", "lcd_chunks_call", "lcd_call_bam_regions", "lcd_call_free",
     "lcd_bgzf_deflate_dev", "lcd_bgzf_deflate_dev_ptr", "lcd_deflated_size", "lcd_deflated_n_blocks", "lcd_deflated_kernel_ms", "lcd_deflated_block_info", "lcd_deflated_to_host", "lcd_deflated_free",
-    "lcd_chunk_tag_records", "lcd_tagged_dev_ptr", "lcd_tagged_size", "lcd_tagged_n_records", "lcd_tagged_to_host", "lcd_tagged_free", "lcd_write_phased_bam", "lcd_call_bam_regions_out",
+    "lcd_chunk_tag_records", "lcd_tagged_dev_ptr", "lcd_tagged_size", "lcd_tagged_n_records", "lcd_tagged_to_host", "lcd_tagged_free", "lcd_write_phased",
     "lcd_bam_contigs", "lcd_bam_contigs_free", "lcd_bam_sample_name", "lcd_plan_chunks", "lcd_chunk_plan_free", "lcd_stitch_chunks_carry", "lcd_stitch_carry_free",
     "lcd_chunk_open_from_bam", "lcd_chunk_resolve", "lcd_bam_writer_open", "lcd_bam_writer_append", "lcd_bam_writer_close", "lcd_bam_writer_abort",
-    "lcd_vcf_writer_open", "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_call_file", "lcd_file_stats_free",
+    "lcd_vcf_writer_open", "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_file_stats_free",
     "lcd_bai_from_records", "lcd_bai_builder_create", "lcd_bai_builder_add_stream", "lcd_bai_builder_finish", "lcd_bai_builder_bytes", "lcd_bai_builder_destroy", "lcd_bai_build",
-    "lcd_fai_build", "lcd_bam_writer_open_indexed", "lcd_call_file_indexed",
-    "lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_bam_writer_set_sort", "lcd_call_files",
+    "lcd_fai_build",
+    "lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_call_files",
     "lcd_te_lib_from_fasta", "lcd_te_lib_from_fasta_free", "lcd_format_vcf_fields", "lcd_alt_read_names", "lcd_vcf_fields_out_free", "lcd_chunks_call_fields",
-    "lcd_call_bam_regions_fields", "lcd_call_file_fields", "lcd_call_files_fields",
     "lcd_chunk_refine_records", "lcd_refine_log_create", "lcd_refine_log_free", "lcd_refine_log_n_entries", "lcd_refine_log_row_bytes", "lcd_refine_log_append",
     "lcd_refine_log_entry", "lcd_refine_log_apply", "lcd_chunks_noisy_rounds_log", "lcd_batch_region_ref_read_rows",
-    "lcd_chunk_set_refine", "lcd_chunk_refine_log", "lcd_chunks_call_refine", "lcd_write_phased_bam_refine", "lcd_bam_writer_set_refine_stats", "lcd_call_bam_regions_refine",
-    "lcd_call_file_refine", "lcd_call_files_refine",
+    "lcd_chunk_set_refine", "lcd_chunk_refine_log", "lcd_chunks_call_refine",
     "lcd_sam_names_create", "lcd_sam_names_free", "lcd_tagged_to_sam", "lcd_records_to_sam", "lcd_sam_text_size", "lcd_sam_text_dev_ptr", "lcd_sam_text_to_host", "lcd_sam_text_free",
-    "lcd_bam_writer_open_sam", "lcd_bam_writer_set_sam_stats", "lcd_write_phased_sam", "lcd_call_files_aln",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
 ]
 
@@ -426,9 +440,8 @@ def load_library():
     lib.lcd_cfg_default.restype = None
     lib.lcd_chunks_call.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdCfg), C.c_char_p, C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p)]
     lib.lcd_call_bam_regions.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, i64p, i64p, C.c_int, C.POINTER(LcdCfg), C.POINTER(LcdCallChunk),
-                                         C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p)]
-    lib.lcd_call_bam_regions_out.argtypes = lib.lcd_call_bam_regions.argtypes + [C.POINTER(LcdBamOut)]
-    lib.lcd_write_phased_bam.argtypes = [C.c_char_p, C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdBamOut)]
+                                         C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p), C.POINTER(LcdBamOut), C.POINTER(LcdRunOpt), C.POINTER(LcdRunOut)]
+    lib.lcd_write_phased.argtypes = [C.c_char_p, C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdBamOut), C.POINTER(LcdWriterOpt)]
     for f in ("lcd_bgzf_deflate_dev", "lcd_bgzf_deflate_dev_ptr", "lcd_chunk_tag_records"):
         getattr(lib, f).restype = C.c_void_p
     lib.lcd_bgzf_deflate_dev.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int]
@@ -464,7 +477,7 @@ def load_library():
     lib.lcd_chunk_open_from_bam.argtypes = [C.POINTER(LcdDigarOpt), C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.POINTER(LcdBamReads)]
     lib.lcd_chunk_resolve.argtypes = [C.c_void_p, C.POINTER(LcdChunkSrc)]
     lib.lcd_bam_writer_open.restype = C.c_void_p
-    lib.lcd_bam_writer_open.argtypes = [C.c_char_p, C.POINTER(LcdBamOut)]
+    lib.lcd_bam_writer_open.argtypes = [C.c_char_p, C.POINTER(LcdBamOut), C.POINTER(LcdWriterOpt)]
     lib.lcd_bam_writer_append.argtypes = [C.c_void_p, C.c_int, C.POINTER(LcdCallChunk), i32p, C.POINTER(LcdStitchCarry)]
     lib.lcd_bam_writer_close.argtypes = [C.c_void_p]
     lib.lcd_bam_writer_abort.argtypes = [C.c_void_p]
@@ -477,11 +490,8 @@ def load_library():
     lib.lcd_vcf_writer_abort.restype = None
     lib.lcd_file_job_default.argtypes = [C.POINTER(LcdFileJob)]
     lib.lcd_file_job_default.restype = None
-    lib.lcd_call_file.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdFileStats)]
+    lib.lcd_call_files.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdRunOpt), C.POINTER(LcdFileStats), C.POINTER(LcdRunOut)]
     lib.lcd_file_stats_free.argtypes = [C.POINTER(LcdFileStats)]
-    lib.lcd_call_file_indexed.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats)]
-    lib.lcd_bam_writer_open_indexed.restype = C.c_void_p
-    lib.lcd_bam_writer_open_indexed.argtypes = [C.c_char_p, C.POINTER(LcdBamOut), C.c_char_p, C.POINTER(LcdIndexStats)]
     lib.lcd_bai_from_records.argtypes = [C.c_int, C.c_int64, i32p, i64p, i64p, i32p, u64p_, u64p_, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
     lib.lcd_bai_builder_create.restype = C.c_void_p
     lib.lcd_bai_builder_create.argtypes = [C.c_int, i64p]
@@ -500,7 +510,6 @@ def load_library():
     lib.lcd_merged_record_plan.argtypes = [C.c_int, i32p, i64p, i64p, C.c_int, C.c_int64, C.c_int64, C.c_int, u8p, i32p]
     lib.lcd_chunk_tag_records_sel.restype = C.c_void_p
     lib.lcd_chunk_tag_records_sel.argtypes = [C.c_void_p, i32p, i64p, u8p, i32p]
-    lib.lcd_bam_writer_set_sort.argtypes = [C.c_void_p, C.c_int]
     lib.lcd_refine_log_create.restype = C.c_void_p
     lib.lcd_refine_log_free.argtypes = [C.c_void_p]
     lib.lcd_refine_log_free.restype = None
@@ -515,7 +524,6 @@ def load_library():
     lib.lcd_chunk_refine_records.restype = C.c_void_p
     lib.lcd_chunk_refine_records.argtypes = [C.c_void_p, C.c_int, i32p, u64p_, C.POINTER(LcdDigar), C.c_char_p, C.c_int64, C.c_int64, i32p, i64p, u8p, i32p,
                                              C.POINTER(LcdRefineStats)]
-    lib.lcd_call_files.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats), i64p]
     lib.lcd_call_free.restype = None
     fo = C.POINTER(LcdVcfFieldsOut)
     lib.lcd_te_lib_from_fasta.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(i32p), i32p]
@@ -528,12 +536,6 @@ def load_library():
     lib.lcd_vcf_fields_out_free.restype = None
     lib.lcd_chunks_call_fields.argtypes = [C.c_int, C.POINTER(LcdCallChunk), C.POINTER(LcdCfg), C.c_char_p, C.POINTER(LcdVcfFields), C.POINTER(C.POINTER(LcdVar1)), i32p,
                                            C.POINTER(C.c_void_p), fo]
-    lib.lcd_call_bam_regions_fields.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, i64p, i64p, C.c_int, C.POINTER(LcdCfg), C.POINTER(LcdVcfFields),
-                                                C.POINTER(LcdCallChunk), C.POINTER(C.POINTER(LcdVar1)), i32p, C.POINTER(C.c_void_p), C.POINTER(LcdBamOut), fo]
-    lib.lcd_call_file_fields.argtypes = [C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdVcfFields), C.POINTER(LcdFileStats),
-                                         C.POINTER(LcdIndexStats), fo]
-    lib.lcd_call_files_fields.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdVcfFields), C.POINTER(LcdFileStats),
-                                          C.POINTER(LcdIndexStats), i64p, fo]
     lib.lcd_batch_region_sorted_ids.argtypes = [C.c_void_p, C.c_int, i32p]
     lib.lcd_batch_get_stats.argtypes = [C.c_void_p, C.POINTER(LcdBatchStats)]
     lib.lcd_batch_digest.argtypes = [C.c_void_p]
@@ -553,16 +555,10 @@ def load_library():
     lib.lcd_edlib_edit_distance.argtypes = [u8p, C.c_int, u8p, C.c_int]
     lib.lcd_collect_noisy_reg_aln_strs.argtypes = [C.POINTER(LcdOpt), C.POINTER(LcdReadView), C.c_int64, C.c_int64, C.c_int, C.c_int, i32p,
                                                    u8p, C.c_int, i32p, C.POINTER(i32p), C.POINTER(C.POINTER(LcdAlnStr))]
-    rsp = C.POINTER(LcdRefineStats)
     lib.lcd_chunk_set_refine.argtypes = [C.c_void_p, C.c_int]
     lib.lcd_chunk_refine_log.restype = C.c_void_p
     lib.lcd_chunk_refine_log.argtypes = [C.c_void_p]
     lib.lcd_chunks_call_refine.argtypes = lib.lcd_chunks_call.argtypes
-    lib.lcd_write_phased_bam_refine.argtypes = lib.lcd_write_phased_bam.argtypes + [rsp]
-    lib.lcd_bam_writer_set_refine_stats.argtypes = [C.c_void_p, rsp]
-    lib.lcd_call_bam_regions_refine.argtypes = lib.lcd_call_bam_regions_out.argtypes + [rsp]
-    lib.lcd_call_file_refine.argtypes = lib.lcd_call_file_indexed.argtypes + [rsp]
-    lib.lcd_call_files_refine.argtypes = lib.lcd_call_files.argtypes + [rsp]
     ssp = C.POINTER(LcdSamStats)
     lib.lcd_sam_names_create.restype = C.c_void_p
     lib.lcd_sam_names_create.argtypes = [C.c_int, C.POINTER(C.c_char_p)]
@@ -579,12 +575,6 @@ def load_library():
     lib.lcd_sam_text_to_host.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, u8p]
     lib.lcd_sam_text_free.argtypes = [C.c_void_p]
     lib.lcd_sam_text_free.restype = None
-    lib.lcd_bam_writer_open_sam.restype = C.c_void_p
-    lib.lcd_bam_writer_open_sam.argtypes = [C.c_char_p, C.POINTER(LcdBamOut)]
-    lib.lcd_bam_writer_set_sam_stats.argtypes = [C.c_void_p, ssp]
-    lib.lcd_write_phased_sam.argtypes = lib.lcd_write_phased_bam.argtypes + [rsp, ssp]
-    lib.lcd_call_files_aln.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdIndexOpt), C.POINTER(LcdVcfFields), C.POINTER(LcdAlnOpt),
-                                       C.POINTER(LcdFileStats), C.POINTER(LcdIndexStats), i64p, C.POINTER(LcdVcfFieldsOut), rsp, ssp]
     _lib = lib
     return lib
 

@@ -1788,10 +1788,10 @@ def tagged_to_sam(chunk, haps, phase_sets, names, skip=None, order=None):
 
 
 def write_phased_sam(in_bam_path, chunks, path, pg_line=None, sort_output=False, aln_format="sam", block_payload=0):
-    """lcd_write_phased_sam (aln_format="bam": the BAM writer on the same chunks): chunks = [dict(chunk=DeviceChunk, haps, phase_sets, reg_beg, reg_end[, ref, ref_beg,
-    ref_end])] in region order, each with its final haplotypes -- the fields of lcd_call_chunk_t the writer reads.  sort_output: through lcd_bam_writer_open(_sam) /
-    _set_sort / _append / _close.  -> dict(bam_out = lcd_bam_out_t's counters, refine = lcd_refine_stats_t, sam = lcd_sam_stats_t)"""
-    from ._lib import LcdBamOut, LcdCallChunk, LcdHapState, LcdRefineStats, LcdSamStats
+    """lcd_write_phased as SAM text (aln_format="bam": the BAM writer on the same chunks): chunks = [dict(chunk=DeviceChunk, haps, phase_sets, reg_beg, reg_end[, ref,
+    ref_beg, ref_end])] in region order, each with its final haplotypes -- the fields of lcd_call_chunk_t the writer reads.  sort_output: lcd_writer_opt_t's.
+    -> dict(bam_out = lcd_bam_out_t's counters, refine = lcd_refine_stats_t, sam = lcd_sam_stats_t)"""
+    from ._lib import LCD_ALN_BAM, LCD_ALN_SAM, LcdBamOut, LcdCallChunk, LcdHapState, LcdRefineStats, LcdSamStats, LcdWriterOpt
     if aln_format not in ("sam", "bam"):
         raise ValueError("write_phased_sam: aln_format must be 'sam' or 'bam'")
     lib = load_library()
@@ -1813,83 +1813,54 @@ def write_phased_sam(in_bam_path, chunks, path, pg_line=None, sort_output=False,
             f.ref_seq, f.ref_beg, f.ref_end = _p8(rb), int(c["ref_beg"]), int(c["ref_end"])
     bo = LcdBamOut(); bo.path = _enc(path); bo.pg_line = _enc(pg_line) if pg_line is not None else None; bo.block_payload = int(block_payload)
     rst, sst = LcdRefineStats(), LcdSamStats()
-    if aln_format == "sam" and not sort_output:
-        check(lib.lcd_write_phased_sam(_enc(in_bam_path), n, arr, C.byref(bo), C.byref(rst), C.byref(sst)), lib)
-    else:
-        w = (lib.lcd_bam_writer_open_sam if aln_format == "sam" else lib.lcd_bam_writer_open)(_enc(in_bam_path), C.byref(bo))
-        if not w:
-            raise LcdError("opening the alignment output failed: " + lib.lcd_last_error().decode())
-        lib.lcd_bam_writer_set_sort(w, int(bool(sort_output))); lib.lcd_bam_writer_set_refine_stats(w, C.byref(rst))
-        if aln_format == "sam":
-            lib.lcd_bam_writer_set_sam_stats(w, C.byref(sst))
-        rc = lib.lcd_bam_writer_append(w, n, arr, None, None)
-        if rc < 0:
-            lib.lcd_bam_writer_abort(w)
-            check(rc, lib)
-        check(lib.lcd_bam_writer_close(w), lib)
+    wo = LcdWriterOpt(format=LCD_ALN_SAM if aln_format == "sam" else LCD_ALN_BAM, sort_output=int(bool(sort_output)), refine_stats=C.pointer(rst), sam_stats=C.pointer(sst))
+    check(lib.lcd_write_phased(_enc(in_bam_path), n, arr, C.byref(bo), C.byref(wo)), lib)
     return dict(bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag", "ms_deflate", "ms_download_write")},
                 refine={k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}, sam={k: getattr(sst, k) for k, _t in LcdSamStats._fields_})
 
 
 def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
-    bam_out = dict(path[, pg_line, block_payload]): lcd_call_bam_regions_out, the phased alignment file is written too; the result gets "bam_out" = the counters and
-    stage times of lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
-    te_fasta= / rnames=: lcd_call_bam_regions_fields (as chunks_call).  refine=True (with bam_out; not with te_fasta / rnames): lcd_call_bam_regions_refine -- the
-    records are written with the alignments the call arrived at; the result gains "refine" = lcd_refine_stats_t's fields"""
-    from ._lib import LcdBamOut, LcdCallChunk, LcdRefineStats, LcdVar1
+    bam_out = dict(path[, pg_line, block_payload]): the phased alignment file is written too; the result gets "bam_out" = the counters and stage times of
+    lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
+    te_fasta= / rnames=: lcd_run_opt_t.fields (as chunks_call).  refine=True (with bam_out; not with te_fasta / rnames): lcd_aln_opt_t.refine -- the records are
+    written with the alignments the call arrived at; the result gains "refine" = lcd_refine_stats_t's fields"""
+    from ._lib import LCD_ALN_BAM, LcdAlnOpt, LcdBamOut, LcdCallChunk, LcdRefineStats, LcdRunOpt, LcdRunOut, LcdVar1
     vf, fo = _vcf_fields(te_fasta, rnames)
     if refine and vf is not None:
         raise ValueError("call_bam_regions: refine= goes with neither te_fasta= nor rnames=")
     rst = LcdRefineStats() if refine and bam_out is not None else None
-    if bam_out is not None or vf is not None:
-        lib = load_library()
-        cfg = cfg if cfg is not None else call_cfg()
-        n = len(reg_beg)
-        arr = (LcdCallChunk * max(1, n))()
-        rb = (C.c_int64 * max(1, n))(*[int(x) for x in reg_beg]); re_ = (C.c_int64 * max(1, n))(*[int(x) for x in reg_end])
-        recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
-        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
-        bo = None
-        if bam_out is not None:
-            bo = LcdBamOut(); bo.path = enc(bam_out["path"]); bo.pg_line = enc(bam_out["pg_line"]) if bam_out.get("pg_line") is not None else None
-            bo.block_payload = int(bam_out.get("block_payload", 0))
-        bop = C.byref(bo) if bo is not None else None
-        if vf is not None:
-            rc = lib.lcd_call_bam_regions_fields(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), C.byref(vf), arr, C.byref(recs),
-                                                 C.byref(n_recs), C.byref(text), bop, C.byref(fo))
-        elif rst is not None:
-            rc = lib.lcd_call_bam_regions_refine(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs),
-                                                 C.byref(n_recs), C.byref(text), bop, C.byref(rst))
-        else:
-            rc = lib.lcd_call_bam_regions_out(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
-                                              C.byref(text), bop)
-        err = lib.lcd_last_error().decode() if rc < 0 else ""
-        if rc < 0 and not text and not recs:
-            raise LcdError(f"liblcd_hotpath error {rc}: {err}")
-        res = _call_result(lib, n, arr, recs, n_recs, text)
-        if vf is not None:
-            res = _fields_result(lib, res, vf, fo)
-        if bo is None:
-            return res
-        res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
-                                                                                                   "ms_deflate", "ms_download_write")})
-        if rst is not None:
-            res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
-        return res
     lib = load_library()
     cfg = cfg if cfg is not None else call_cfg()
     n = len(reg_beg)
     arr = (LcdCallChunk * max(1, n))()
     rb = (C.c_int64 * max(1, n))(*[int(x) for x in reg_beg]); re_ = (C.c_int64 * max(1, n))(*[int(x) for x in reg_end])
     recs, n_recs, text = C.POINTER(LcdVar1)(), C.c_int(0), C.c_void_p()
-    enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
-    check(lib.lcd_call_bam_regions(enc(bam_path), enc(bai_path), enc(fasta_path), enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
-                                   C.byref(text)), lib)
-    return _call_result(lib, n, arr, recs, n_recs, text)
+    bo = None
+    if bam_out is not None:
+        bo = LcdBamOut(); bo.path = _enc(bam_out["path"]); bo.pg_line = _enc(bam_out["pg_line"]) if bam_out.get("pg_line") is not None else None
+        bo.block_payload = int(bam_out.get("block_payload", 0))
+    ao = LcdAlnOpt(LCD_ALN_BAM, int(rst is not None))
+    ro = LcdRunOpt(fields=C.pointer(vf) if vf is not None else None, aln=C.pointer(ao))
+    out = LcdRunOut(fields_out=C.pointer(fo) if vf is not None else None, refine_stats=C.pointer(rst) if rst is not None else None)
+    rc = lib.lcd_call_bam_regions(_enc(bam_path), _enc(bai_path), _enc(fasta_path), _enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
+                                  C.byref(text), C.byref(bo) if bo is not None else None, C.byref(ro), C.byref(out))
+    err = lib.lcd_last_error().decode() if rc < 0 else ""
+    if rc < 0 and (bo is None or (not text and not recs)):
+        raise LcdError(f"liblcd_hotpath error {rc}: {err}")
+    res = _call_result(lib, n, arr, recs, n_recs, text)
+    if vf is not None:
+        res = _fields_result(lib, res, vf, fo)
+    if bo is None:
+        return res
+    res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
+                                                                                               "ms_deflate", "ms_download_write")})
+    if rst is not None:
+        res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
+    return res
 
 
-# ---------------- a whole BAM in one call (lcd_call_file and what it is composed of) ----------------
+# ---------------- a whole BAM in one call (lcd_call_files and what it is composed of) ----------------
 def _enc(x):
     return x if isinstance(x, bytes) else str(x).encode()
 
@@ -1992,18 +1963,18 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
               keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam"):
-    """lcd_call_file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[, pg_line, block_payload]), the
-    phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads, n_passes, flip_hap,
-    flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
-    index (default None: lcd_call_file as it is): True, or a dict with build_missing_bai / build_missing_fai / write_out_bai / out_bai_path / slab_members ->
-    lcd_call_file_indexed; the result then has "index" = lcd_index_stats_t's fields (out_bai_skipped != 0: the output's index was not written, out_bai_skip_reason says why).
-    te_fasta= (the -T file) / rnames=None|"sv"|"all" (--out-sv-rnames / --out-var-rnames): lcd_call_file_fields / lcd_call_files_fields; the result gains "te_names" and
-    "n_mei_lines" (with a library) and the kept records "te_name" / "alt_read_names" (see _fields_result).
-    refine=True (the command line's --refine-bam; no effect without bam_out, not with te_fasta / rnames): lcd_call_file_refine / lcd_call_files_refine; the result
-    gains "refine" = lcd_refine_stats_t's fields.
-    aln_format="sam" (the command line's --sam; the default "bam" takes the entry points above untouched): lcd_call_files_aln -- bam_out's path gets SAM text ("-":
-    stdout), block_payload is ignored, no output index; the result gains "sam" = lcd_sam_stats_t's fields"""
-    from ._lib import LCD_ALN_SAM, LcdAlnOpt, LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats, LcdRefineStats, LcdSamStats
+    """lcd_call_files with the job's one file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[,
+    pg_line, block_payload]), the phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads,
+    n_passes, flip_hap, flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
+    index (default None: no lcd_index_opt_t): True, or a dict with build_missing_bai / build_missing_fai / write_out_bai / out_bai_path / slab_members; the result then
+    has "index" = lcd_index_stats_t's fields (out_bai_skipped != 0: the output's index was not written, out_bai_skip_reason says why).
+    te_fasta= (the -T file) / rnames=None|"sv"|"all" (--out-sv-rnames / --out-var-rnames): lcd_vcf_fields_t; the result gains "te_names" and "n_mei_lines" (with a
+    library) and the kept records "te_name" / "alt_read_names" (see _fields_result).
+    refine=True (the command line's --refine-bam; no effect without bam_out, not with te_fasta / rnames): lcd_aln_opt_t.refine; the result gains "refine" =
+    lcd_refine_stats_t's fields.
+    aln_format="sam" (the command line's --sam): bam_out's path gets SAM text ("-": stdout), block_payload is ignored, no output index; the result gains "sam" =
+    lcd_sam_stats_t's fields"""
+    from ._lib import LCD_ALN_BAM, LCD_ALN_SAM, LcdAlnOpt, LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats, LcdRefineStats, LcdRunOpt, LcdRunOut, LcdSamStats
     if aln_format not in ("bam", "sam"):
         raise ValueError("call_file: aln_format must be 'bam' or 'sam'")
     lib = load_library()
@@ -2041,30 +2012,15 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
         io = LcdIndexOpt(int(d.get("build_missing_bai", 0)), int(d.get("build_missing_fai", 0)), int(d.get("write_out_bai", 0)), opt_s(d.get("out_bai_path")), int(d.get("slab_members", 0)))
         ist = LcdIndexStats()
     vf, fo = _vcf_fields(te_fasta, rnames)
-    iop, istp = (C.byref(io) if io is not None else None), (C.byref(ist) if ist is not None else None)
     if refine and vf is not None:
         raise ValueError("call_file: refine= goes with neither te_fasta= nor rnames=")
     rst = LcdRefineStats() if refine else None
-    sst = None
-    if aln_format == "sam":
-        sst, ao = LcdSamStats(), LcdAlnOpt(LCD_ALN_SAM, int(bool(refine)))
-        rc = lib.lcd_call_files_aln(C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), iop, C.byref(vf) if vf is not None else None, C.byref(ao),
-                                    C.byref(st), istp, per_file if _inputs is not None else None, C.byref(fo) if vf is not None else None,
-                                    C.byref(rst) if rst is not None else None, C.byref(sst))
-    elif rst is not None and _inputs is not None:
-        rc = lib.lcd_call_files_refine(C.byref(inp), C.byref(job), C.byref(cfg), iop, C.byref(st), istp, per_file, C.byref(rst))
-    elif rst is not None:
-        rc = lib.lcd_call_file_refine(C.byref(job), C.byref(cfg), iop, C.byref(st), istp, C.byref(rst))
-    elif vf is not None and _inputs is not None:
-        rc = lib.lcd_call_files_fields(C.byref(inp), C.byref(job), C.byref(cfg), iop, C.byref(vf), C.byref(st), istp, per_file, C.byref(fo))
-    elif vf is not None:
-        rc = lib.lcd_call_file_fields(C.byref(job), C.byref(cfg), iop, C.byref(vf), C.byref(st), istp, C.byref(fo))
-    elif _inputs is not None:
-        rc = lib.lcd_call_files(C.byref(inp), C.byref(job), C.byref(cfg), C.byref(io) if io is not None else None, C.byref(st), C.byref(ist) if ist is not None else None, per_file)
-    elif index:
-        rc = lib.lcd_call_file_indexed(C.byref(job), C.byref(cfg), C.byref(io), C.byref(st), C.byref(ist))
-    else:
-        rc = lib.lcd_call_file(C.byref(job), C.byref(cfg), C.byref(st))
+    sst = LcdSamStats() if aln_format == "sam" else None
+    ao = LcdAlnOpt(LCD_ALN_SAM if aln_format == "sam" else LCD_ALN_BAM, int(bool(refine)))
+    ptr = lambda x: C.pointer(x) if x is not None else None
+    ro = LcdRunOpt(idx=ptr(io), fields=ptr(vf), aln=C.pointer(ao))
+    out = LcdRunOut(idx_stats=ptr(ist), n_reads_per_file=C.cast(per_file, C.POINTER(C.c_int64)) if _inputs is not None else None, fields_out=ptr(fo), refine_stats=ptr(rst), sam_stats=ptr(sst))
+    rc = lib.lcd_call_files(C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
     try:
         check(rc, lib)
         res = {k: getattr(st, k) for k, _t in LcdFileStats._fields_[:14]}

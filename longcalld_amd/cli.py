@@ -1,5 +1,5 @@
 """python -m longcalld_amd.cli call ref.fa in.bam [region ...] -- the reference's command line (src/call_var_main.c:812-1000) for what the library supports: a thin
-argument parser over lcd_call_file / lcd_call_files.  What is not supported is refused with one line and exit status 2."""
+argument parser over lcd_call_files.  What is not supported is refused with one line and exit status 2."""
 import sys
 
 VERSION_FALLBACK = "longcalld_amd"

@@ -1,6 +1,6 @@
 // lcd_bam_out.cpp -- the device side of the phased alignment output (longcallD call -b): BGZF members compressed in HBM (deflate_kernel.hip) and the HP:i / PS:i
-// rewrite of a chunk's records where the inflate left them (bam_tag_kernel.hip).  The writer that joins them into a file is lcd_write_phased_bam (lcd_call.cpp).
-// The same records as SAM text lines (bam_sam_kernel.hip): lcd_tagged_to_sam / lcd_records_to_sam, behind lcd_bam_writer_open_sam.
+// rewrite of a chunk's records where the inflate left them (bam_tag_kernel.hip).  The writer that joins them into a file is lcd_write_phased (lcd_call.cpp).
+// The same records as SAM text lines (bam_sam_kernel.hip): lcd_tagged_to_sam / lcd_records_to_sam, behind the writer's LCD_ALN_SAM format.
 #include "lcd_host_internal.h"
 
 using namespace lcd_internal;

@@ -1,6 +1,6 @@
 // lcd_call.cpp -- the germline path joined end to end: lcd_chunks_call (first round, noisy-region rounds, cross-chunk stitch, genotype records, VCF body lines
 // for a pipeline step's chunks of one contig), lcd_call_bam_regions (the same from an indexed BAM and a FASTA) and the phased alignment file beside it
-// (the appendable writer lcd_bam_writer_*, lcd_write_phased_bam, lcd_call_bam_regions_out).  chunks_call_core is the body of lcd_chunks_call that lcd_call_file
+// (the appendable writer lcd_bam_writer_*, lcd_write_phased).  chunks_call_core is the body of lcd_chunks_call that lcd_call_files
 // (lcd_call_file.cpp) runs per window of chunks.  Every stage is an export of its own
 // (lcd_first_round.cpp, lcd_chunk_vars.cpp, lcd_emit.cpp, lcd_chunk.cpp, lcd_io.cpp); this file only composes them as collect_var_main / stitch_var_main /
 // make_var_main do (src/collect_var.c:2897-3000).
@@ -73,7 +73,7 @@ lcd_internal::FieldsRun::~FieldsRun() {
     lcd_te_lib_destroy(lib);
 }
 
-// the body of lcd_chunks_call.  links == NULL: n chunks of the one contig `chrom`.  With links (lcd_call_file's window): a contig name and tid per chunk, the first
+// the body of lcd_chunks_call.  links == NULL: n chunks of the one contig `chrom`.  With links (lcd_call_files' window): a contig name and tid per chunk, the first
 // chunk's up list against the carried region, the last chunk's down list against the next planned region, the stitch carried in and out
 int lcd_internal::chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, FieldsRun *fields, lcd_var1_t **records,
                                    int *n_records, char **vcf_body) {
@@ -215,15 +215,25 @@ extern "C" {
 // records that overlap that region's [reg_beg, reg_end] (is_ovlp_with_prev_region, src/bam_utils.c:1684-1691) -- in a sorted file they are the first ones.
 struct lcd_bam_writer_s {
     FILE *f = nullptr; lcd_bam_out_t *out = nullptr; std::string path; std::vector<uint8_t> buf;
-    // lcd_bam_writer_open_indexed: the builder of the output's .bai (NULL: none, or given up), where the index goes, the file offset of the next member
-    lcd_bai_builder_t *bai = nullptr; std::string index_path; lcd_index_stats_t *ist = nullptr; uint64_t file_off = 0;
-    int sort_output = 0;     // lcd_bam_writer_set_sort
-    lcd_refine_stats_t *rstats = nullptr;     // lcd_bam_writer_set_refine_stats: what the refined chunks' records became, summed over the appends
-    // lcd_bam_writer_open_sam: the records go out as SAM text (lcd_tagged_to_sam) instead of BGZF members; f may be stdout
-    bool sam = false, own_f = true; lcd_sam_names_t *names = nullptr; lcd_sam_stats_t *sstats = nullptr;
-    ~lcd_bam_writer_s() { lcd_sam_names_free(names); }
+    lcd_writer_opt_t o;      // the options of the open (all zero for none): the format, sort_output, where the sums over the appends go
+    // write_index: the builder of the output's .bai (NULL: none, or given up), where the index goes; the file offset of the next member
+    lcd_bai_builder_t *bai = nullptr; std::string index_path; uint64_t file_off = 0;
+    // LCD_ALN_SAM: the records go out as SAM text (lcd_tagged_to_sam) instead of BGZF members; f may be stdout
+    bool sam = false, own_f = true; lcd_sam_names_t *names = nullptr;
+    ~lcd_bam_writer_s() { lcd_sam_names_free(names); lcd_bai_builder_destroy(bai); }
 };
 namespace {
+// a += one append's statistics (the log counters of lcd_refine_stats_t are the writer's own and are added where the log is read)
+void add_refine_stats(lcd_refine_stats_t &a, const lcd_refine_stats_t &b) {
+    a.n_records += b.n_records; a.n_kept += b.n_kept; a.n_refined += b.n_refined; a.n_identical += b.n_identical; a.n_unrefined += b.n_unrefined; a.n_pos_moved += b.n_pos_moved;
+    a.n_no_digars += b.n_no_digars; a.n_qlen_mismatch += b.n_qlen_mismatch; a.n_bad_pos += b.n_bad_pos; a.n_too_many_ops += b.n_too_many_ops; a.n_cg_cigar += b.n_cg_cigar;
+    a.n_nm_replaced += b.n_nm_replaced; a.n_md_replaced += b.n_md_replaced; a.n_cs_replaced += b.n_cs_replaced; a.n_touched += b.n_touched;
+    a.bytes_digars_up += b.bytes_digars_up; a.bytes_ref_up += b.bytes_ref_up; a.ms_measure += b.ms_measure; a.ms_emit += b.ms_emit;
+}
+void add_sam_stats(lcd_sam_stats_t &a, const lcd_sam_stats_t &b) {
+    a.n_records += b.n_records; a.bytes_records += b.bytes_records; a.bytes_text += b.bytes_text; a.n_float_values += b.n_float_values; a.n_cg_cigar += b.n_cg_cigar;
+    a.n_walk_stopped += b.n_walk_stopped; a.n_bad_layout += b.n_bad_layout; a.ms_measure += b.ms_measure; a.ms_emit += b.ms_emit; a.ms_download_write += b.ms_download_write;
+}
 // download + fwrite of one compressed image, then free
 int writer_put(lcd_bam_writer_s *w, lcd_deflated_t *d, const std::string &W) {
     if (!d) return -1;
@@ -241,7 +251,7 @@ int writer_put(lcd_bam_writer_s *w, lcd_deflated_t *d, const std::string &W) {
 // the output's index gives up (rule 3: an input with records out of order inside a region, or chunks appended out of order; a position outside the header's
 // contigs): the BAM goes on, no index file stays, the statistics say why
 void writer_skip_index(lcd_bam_writer_s *w, int code) {
-    if (w->ist) { w->ist->out_bai_skipped = code; snprintf(w->ist->out_bai_skip_reason, sizeof(w->ist->out_bai_skip_reason), "%s", g_err.c_str()); }
+    if (lcd_index_stats_t *ist = w->o.idx_stats) { ist->out_bai_skipped = code; snprintf(ist->out_bai_skip_reason, sizeof(ist->out_bai_skip_reason), "%s", g_err.c_str()); }
     lcd_bai_builder_destroy(w->bai); w->bai = nullptr;
     remove(w->index_path.c_str());
 }
@@ -258,9 +268,9 @@ int writer_index_stream(lcd_bam_writer_s *w, const lcd_tagged_t *t, const lcd_de
     }
     size_t next = 0;
     const int rc = lcd_bai_builder_add_stream(w->bai, lcd_tagged_dev_ptr(t), lcd_tagged_size(t), 0, nb, tab.data(), w->file_off + lcd_deflated_size(d), &next);
-    if (w->ist) w->ist->ms_out_bai += now_ms() - t0;
+    if (w->o.idx_stats) w->o.idx_stats->ms_out_bai += now_ms() - t0;
     if (rc == LCD_ERR_BAI_ORDER || rc == LCD_ERR_BAI_CSI || rc == LCD_ERR_BAI_CONTIG) { writer_skip_index(w, rc); return 0; }
-    if (!rc && next != lcd_tagged_size(t)) return set_err(-24, "lcd_write_phased_bam: the tagged stream ends inside a record");
+    if (!rc && next != lcd_tagged_size(t)) return set_err(-24, "lcd_bam_writer_append: the tagged stream ends inside a record");
     return rc;
 }
 // the SAM writer's append: the tagged stream as text, download + fwrite
@@ -277,17 +287,23 @@ int writer_put_sam(lcd_bam_writer_s *w, const lcd_tagged_t *t, const std::string
     lcd_sam_text_free(x);
     out->bytes_file += (int64_t)sz; w->file_off += sz;
     ss.ms_download_write = now_ms() - t0; out->ms_download_write += ss.ms_download_write;
-    if (lcd_sam_stats_t *a = w->sstats) {
-        int64_t *dst = &a->n_records; const int64_t *src = &ss.n_records;
-        for (int q = 0; q < 7; ++q) dst[q] += src[q];                    // the seven counters in front of the three times
-        a->ms_measure += ss.ms_measure; a->ms_emit += ss.ms_emit; a->ms_download_write += ss.ms_download_write;
-    }
+    if (w->o.sam_stats) add_sam_stats(*w->o.sam_stats, ss);
     return rc;
 }
-// the SAM header of lcd_bam_writer_open_sam, in place: `text` comes in as the input header's text
-void sam_header_text(std::string &text, const char *pg_line, int n_ref, char **names, const int64_t *lens) {
-    while (!text.empty() && text.back() == 0) text.pop_back();
-    if (pg_line && pg_line[0]) { if (!text.empty() && text.back() != '\n') text += '\n'; text += pg_line; text += '\n'; }
+// pg_line as a line of its own behind the header text of `hdr` (the BAM header block), in front of the text's NUL padding; returns where the text then ends
+size_t header_add_pg(std::vector<uint8_t> &hdr, const char *pg_line) {
+    int l_text = 0; memcpy(&l_text, hdr.data() + 4, 4);
+    size_t te = 8 + (size_t)l_text;
+    while (te > 8 && hdr[te - 1] == 0) --te;
+    if (!pg_line || !pg_line[0]) return te;
+    std::string add = (te > 8 && hdr[te - 1] != '\n') ? "\n" : "";
+    add += pg_line; add += '\n';
+    hdr.insert(hdr.begin() + (long)te, add.begin(), add.end());
+    l_text += (int)add.size(); memcpy(hdr.data() + 4, &l_text, 4);
+    return te + add.size();
+}
+// the SAM header, in place: `text` comes in as the header text without its padding, the @PG line added
+void sam_header_text(std::string &text, int n_ref, char **names, const int64_t *lens) {
     if (!text.empty() && text.back() != '\n') text += '\n';
     const bool have_sq = text.compare(0, 4, "@SQ\t") == 0 || text.find("\n@SQ\t") != std::string::npos;      // a line that starts with it
     if (!have_sq && n_ref > 0) {
@@ -296,6 +312,17 @@ void sam_header_text(std::string &text, const char *pg_line, int n_ref, char **n
         const size_t at = text.compare(0, 3, "@HD") == 0 && (text.size() == 3 || text[3] == '\t' || text[3] == '\n') ? text.find('\n') + 1 : 0;
         text.insert(at, sq);
     }
+}
+// what an open refuses before it reads or creates anything; then the one reset of *out's counters and of the statistics the options name
+int writer_begin(const std::string &W, const char *in_bam_path, lcd_bam_out_t *out, const lcd_writer_opt_t &o) {
+    if (o.refine_stats) memset(o.refine_stats, 0, sizeof(*o.refine_stats));
+    if (o.sam_stats) memset(o.sam_stats, 0, sizeof(*o.sam_stats));
+    if (!in_bam_path || !out || !out->path) return set_err(-4, W + ": NULL argument");
+    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
+    if (o.format != LCD_ALN_BAM && o.format != LCD_ALN_SAM) return set_err(-4, W + ": format must be LCD_ALN_BAM or LCD_ALN_SAM");
+    if (o.format == LCD_ALN_SAM && o.write_index) return set_err(-4, W + ": a SAM output has no index (write_index)");
+    if (o.format == LCD_ALN_BAM && (out->block_payload < 0 || out->block_payload > 0xff00)) return set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00");
+    return 0;
 }
 int writer_check_chunks(const std::string &W, int n, const lcd_call_chunk_t *chunks) {
     for (int c = 0; c < n; ++c) {
@@ -308,32 +335,47 @@ int writer_check_chunks(const std::string &W, int n, const lcd_call_chunk_t *chu
 }
 } // namespace
 
-lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out) {
-    const std::string W = "lcd_write_phased_bam";
-    if (!in_bam_path || !out || !out->path) { set_err(-4, W + ": NULL argument"); return nullptr; }
-    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
-    if (out->block_payload < 0 || out->block_payload > 0xff00) { set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00"); return nullptr; }
+lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out, const lcd_writer_opt_t *wopt) {
+    const std::string W = "lcd_bam_writer_open";
+    std::unique_ptr<lcd_bam_writer_s> w(new lcd_bam_writer_s());
+    if (wopt) w->o = *wopt; else memset(&w->o, 0, sizeof(w->o));
+    if (writer_begin(W, in_bam_path, out, w->o)) return nullptr;
+    w->sam = w->o.format == LCD_ALN_SAM; w->out = out; w->path = out->path;
     std::vector<uint8_t> hdr;
     if (lcd_io_bam_header(in_bam_path, hdr)) { set_err(-30, W + ": " + lcd_io_last_error()); return nullptr; }
-    if (out->pg_line && out->pg_line[0]) {
-        int l_text = 0; memcpy(&l_text, hdr.data() + 4, 4);
-        size_t te = 8 + (size_t)l_text;
-        while (te > 8 && hdr[te - 1] == 0) --te;                          // (a NUL-padded text: the line goes in front of the padding)
-        std::string add = (te > 8 && hdr[te - 1] != '\n') ? "\n" : "";
-        add += out->pg_line; add += '\n';
-        hdr.insert(hdr.begin() + (long)te, add.begin(), add.end());
-        l_text += (int)add.size(); memcpy(hdr.data() + 4, &l_text, 4);
+    const size_t text_end = header_add_pg(hdr, out->pg_line);
+    std::string text;
+    if (w->sam || w->o.write_index) {     // the contigs: their names for the SAM lines, their lengths for the index builder
+        int n_ref = 0; char **names = nullptr; int64_t *lens = nullptr;
+        if (lcd_bam_contigs(in_bam_path, &n_ref, &names, &lens)) return nullptr;
+        if (w->sam) {
+            text.assign((const char *)hdr.data() + 8, text_end - 8);
+            sam_header_text(text, n_ref, names, lens);
+            w->names = lcd_sam_names_create(n_ref, names);
+        } else w->bai = lcd_bai_builder_create(n_ref, lens);
+        lcd_bam_contigs_free(n_ref, names, lens);
+        if (w->sam ? !w->names : !w->bai) return nullptr;
     }
-    std::unique_ptr<lcd_bam_writer_s> w(new lcd_bam_writer_s());
-    w->out = out; w->path = out->path;
-    w->f = fopen(out->path, "wb");
+    if (w->sam && !strcmp(out->path, "-")) { w->f = stdout; w->own_f = false; }
+    else w->f = fopen(out->path, "wb");
     if (!w->f) { set_err(-30, W + ": cannot open " + out->path + " for writing"); return nullptr; }
-    if (writer_put(w.get(), lcd_bgzf_deflate_dev(hdr.data(), hdr.size(), out->block_payload, 0), W)) { const std::string m = g_err; fclose(w->f); g_err = m; return nullptr; }
-    out->bytes_inflated += (int64_t)hdr.size();
+    int rc = 0;
+    if (w->sam) {
+        if (!text.empty() && fwrite(text.data(), 1, text.size(), w->f) != text.size()) rc = set_err(-30, W + ": short write on " + w->path);
+        out->bytes_file += (int64_t)text.size(); w->file_off += text.size();
+    } else {
+        rc = writer_put(w.get(), lcd_bgzf_deflate_dev(hdr.data(), hdr.size(), out->block_payload, 0), W);
+        out->bytes_inflated += (int64_t)hdr.size();
+    }
+    if (rc) { const std::string m = g_err; if (w->own_f) fclose(w->f); g_err = m; return nullptr; }
+    if (w->bai) {
+        w->index_path = w->o.index_path ? std::string(w->o.index_path) : std::string(out->path) + ".bai";
+        remove(w->index_path.c_str());     // (an index of an earlier file at this path would not describe the one being written)
+    }
     return w.release();
 }
 int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *chunks, const int *tids, const lcd_stitch_carry_t *prev) {
-    const std::string W = "lcd_write_phased_bam";
+    const std::string W = "lcd_bam_writer_append";
     if (!w || !w->f || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
     if (int rc = writer_check_chunks(W, n, chunks)) return rc;
     lcd_bam_out_t *out = w->out;
@@ -346,7 +388,7 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
         // (file-major) order, or sorted by position
         const int n_rec = (int)k->rec_beg.size();
         std::vector<uint8_t> skip((size_t)n_rec + 1); std::vector<int> order((size_t)n_rec + 1);
-        const int n_out = lcd_merged_record_plan(n_rec, k->rec_file.data(), k->rec_pos0.data(), k->rec_endpos.data(), has_prev, pb, pe, w->sort_output, skip.data(), order.data());
+        const int n_out = lcd_merged_record_plan(n_rec, k->rec_file.data(), k->rec_pos0.data(), k->rec_endpos.data(), has_prev, pb, pe, w->o.sort_output != 0, skip.data(), order.data());
         if (n_out < 0) return n_out;
         const double t0 = now_ms();
         lcd_tagged_t *t = nullptr;
@@ -362,10 +404,8 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
                                                   x.state ? x.state->phase_sets : nullptr, skip.data(), order.data(), &rs);
             free(t_reads); free(t_off); free(t_dg); free(d_off); free(dg);
             if (!t) return rc ? rc : -30;
-            if (lcd_refine_stats_t *a = w->rstats) {
-                int64_t *dst = &a->n_records; const int64_t *src = &rs.n_records;
-                for (int q = 0; q < 17; ++q) dst[q] += src[q];           // the seventeen counters in front of the two times
-                a->ms_measure += rs.ms_measure; a->ms_emit += rs.ms_emit;
+            if (lcd_refine_stats_t *a = w->o.refine_stats) {
+                add_refine_stats(*a, rs);
                 a->n_log_entries += lcd_refine_log_n_entries(k->refine_log); a->bytes_log_down += lcd_refine_log_row_bytes(k->refine_log); a->n_log_rejected += n_rej;
             }
         } else t = lcd_chunk_tag_records_sel(k, x.state ? x.state->haps : nullptr, x.state ? x.state->phase_sets : nullptr, skip.data(), order.data());
@@ -389,27 +429,16 @@ int lcd_bam_writer_append(lcd_bam_writer_t *w, int n, const lcd_call_chunk_t *ch
     }
     return 0;
 }
-int lcd_bam_writer_set_refine_stats(lcd_bam_writer_t *w, lcd_refine_stats_t *stats) {
-    if (!w) return set_err(-4, "lcd_bam_writer_set_refine_stats: NULL writer");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    w->rstats = stats;
-    return 0;
-}
-int lcd_bam_writer_set_sort(lcd_bam_writer_t *w, int sort_output) {
-    if (!w) return set_err(-4, "lcd_bam_writer_set_sort: NULL writer");
-    w->sort_output = sort_output != 0;
-    return 0;
-}
 void lcd_bam_writer_abort(lcd_bam_writer_t *w) {
     if (!w) return;
     const std::string m = g_err;
     if (w->f && w->own_f) fclose(w->f); else if (w->f) fflush(w->f);
-    if (w->bai) { lcd_bai_builder_destroy(w->bai); remove(w->index_path.c_str()); }
+    if (w->bai) remove(w->index_path.c_str());
     delete w;
     g_err = m;
 }
 int lcd_bam_writer_close(lcd_bam_writer_t *w) {
-    const std::string W = "lcd_write_phased_bam";
+    const std::string W = "lcd_bam_writer_close";
     if (!w) return set_err(-4, W + ": NULL argument");
     if (!w->sam) if (int rc = writer_put(w, lcd_bgzf_deflate_dev(nullptr, 0, w->out->block_payload, 1), W)) { lcd_bam_writer_abort(w); return rc; }   // the EOF member
     const std::string path = w->path;
@@ -419,129 +448,46 @@ int lcd_bam_writer_close(lcd_bam_writer_t *w) {
     if (w->bai) {   // the index after the EOF member
         const double t0 = now_ms();
         rc = lcd_bai_builder_finish(w->bai, w->index_path.c_str());
-        if (!rc && w->ist) {
+        lcd_index_stats_t *ist = w->o.idx_stats;
+        if (!rc && ist) {
             const uint8_t *bytes = nullptr; size_t n = 0;
             (void)lcd_bai_builder_bytes(w->bai, &bytes, &n);
-            w->ist->wrote_out_bai = 1; w->ist->out_bai_bytes = (int64_t)n;
-            if (n >= 8) { uint64_t nc = 0; memcpy(&nc, bytes + n - 8, 8); w->ist->out_n_no_coor = (int64_t)nc; }
-            w->ist->out_n_indexed = w->out->n_records_out + w->out->n_filtered_out - w->ist->out_n_no_coor;
-            w->ist->ms_out_bai += now_ms() - t0;
+            ist->wrote_out_bai = 1; ist->out_bai_bytes = (int64_t)n;
+            if (n >= 8) { uint64_t nc = 0; memcpy(&nc, bytes + n - 8, 8); ist->out_n_no_coor = (int64_t)nc; }
+            ist->out_n_indexed = w->out->n_records_out + w->out->n_filtered_out - ist->out_n_no_coor;
+            ist->ms_out_bai += now_ms() - t0;
         }
-        lcd_bai_builder_destroy(w->bai); w->bai = nullptr;
     }
     delete w;
     return rc;
 }
-lcd_bam_writer_t *lcd_bam_writer_open_indexed(const char *in_bam_path, lcd_bam_out_t *out, const char *index_path, lcd_index_stats_t *idx_stats) {
-    const std::string W = "lcd_bam_writer_open_indexed";
-    if (!in_bam_path || !out || !out->path) { set_err(-4, W + ": NULL argument"); return nullptr; }
-    int n_ref = 0; char **names = nullptr; int64_t *lens = nullptr;
-    if (lcd_bam_contigs(in_bam_path, &n_ref, &names, &lens)) return nullptr;
-    lcd_bai_builder_t *bai = lcd_bai_builder_create(n_ref, lens);
-    lcd_bam_contigs_free(n_ref, names, lens);
-    if (!bai) return nullptr;
-    lcd_bam_writer_t *w = lcd_bam_writer_open(in_bam_path, out);
-    if (!w) { lcd_bai_builder_destroy(bai); return nullptr; }
-    w->bai = bai; w->ist = idx_stats; w->index_path = index_path ? std::string(index_path) : std::string(out->path) + ".bai";
-    remove(w->index_path.c_str());     // (an index of an earlier file at this path would not describe the one being written)
-    return w;
-}
-lcd_bam_writer_t *lcd_bam_writer_open_sam(const char *in_bam_path, lcd_bam_out_t *out) {
-    const std::string W = "lcd_write_phased_sam";
-    if (!in_bam_path || !out || !out->path) { set_err(-4, W + ": NULL argument"); return nullptr; }
-    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
-    std::vector<uint8_t> hdr;
-    if (lcd_io_bam_header(in_bam_path, hdr)) { set_err(-30, W + ": " + lcd_io_last_error()); return nullptr; }
-    int n_ref = 0; char **names = nullptr; int64_t *lens = nullptr;
-    if (lcd_bam_contigs(in_bam_path, &n_ref, &names, &lens)) return nullptr;
-    int l_text = 0; memcpy(&l_text, hdr.data() + 4, 4);
-    std::string text((const char *)hdr.data() + 8, (size_t)l_text);
-    sam_header_text(text, out->pg_line, n_ref, names, lens);
-    std::unique_ptr<lcd_bam_writer_s> w(new lcd_bam_writer_s());
-    w->sam = true; w->out = out; w->path = out->path;
-    w->names = lcd_sam_names_create(n_ref, names);
-    lcd_bam_contigs_free(n_ref, names, lens);
-    if (!w->names) return nullptr;
-    if (!strcmp(out->path, "-")) { w->f = stdout; w->own_f = false; }
-    else w->f = fopen(out->path, "wb");
-    if (!w->f) { set_err(-30, W + ": cannot open " + out->path + " for writing"); return nullptr; }
-    if (!text.empty() && fwrite(text.data(), 1, text.size(), w->f) != text.size()) {
-        if (w->own_f) fclose(w->f);
-        set_err(-30, W + ": short write on " + w->path); return nullptr;
-    }
-    out->bytes_file += (int64_t)text.size(); w->file_off += text.size();
-    return w.release();
-}
-int lcd_bam_writer_set_sam_stats(lcd_bam_writer_t *w, lcd_sam_stats_t *stats) {
-    if (!w) return set_err(-4, "lcd_bam_writer_set_sam_stats: NULL writer");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    w->sstats = stats;
-    return 0;
-}
-int lcd_write_phased_sam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats, lcd_sam_stats_t *sam_stats) {
-    const std::string W = "lcd_write_phased_sam";
-    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
-    if (sam_stats) memset(sam_stats, 0, sizeof(*sam_stats));
-    if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
+int lcd_write_phased(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, const lcd_writer_opt_t *wopt) {
+    const std::string W = "lcd_write_phased";
+    lcd_writer_opt_t o;
+    if (wopt) o = *wopt; else memset(&o, 0, sizeof(o));
+    if (int rc = writer_begin(W, in_bam_path, out, o)) return rc;
+    if (n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
     if (int rc = writer_check_chunks(W, n, chunks)) return rc;     // (before the output file is touched)
-    lcd_bam_writer_t *w = lcd_bam_writer_open_sam(in_bam_path, out);
+    lcd_bam_writer_t *w = lcd_bam_writer_open(in_bam_path, out, &o);
     if (!w) return -30;
-    w->rstats = refine_stats; w->sstats = sam_stats;
-    if (int rc = lcd_bam_writer_append(w, n, chunks, nullptr, nullptr)) { lcd_bam_writer_abort(w); return rc; }
-    return lcd_bam_writer_close(w);
-}
-int lcd_write_phased_bam(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out) { return lcd_write_phased_bam_refine(in_bam_path, n, chunks, out, nullptr); }
-int lcd_write_phased_bam_refine(const char *in_bam_path, int n, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, lcd_refine_stats_t *refine_stats) {
-    const std::string W = "lcd_write_phased_bam";
-    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
-    if (!in_bam_path || !out || !out->path || n < 0 || (n > 0 && !chunks)) return set_err(-4, W + ": NULL argument");
-    out->n_records_out = out->n_filtered_out = out->bytes_inflated = out->bytes_file = 0; out->ms_tag = out->ms_deflate = out->ms_download_write = 0;
-    if (out->block_payload < 0 || out->block_payload > 0xff00) return set_err(-4, W + ": block_payload must be 0 or 1 ... 0xff00");
-    if (int rc = writer_check_chunks(W, n, chunks)) return rc;     // (before the output file is touched)
-    lcd_bam_writer_t *w = lcd_bam_writer_open(in_bam_path, out);
-    if (!w) return -30;
-    w->rstats = refine_stats;
     if (int rc = lcd_bam_writer_append(w, n, chunks, nullptr, nullptr)) { lcd_bam_writer_abort(w); return rc; }
     return lcd_bam_writer_close(w);
 }
 
 int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
-                         int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body) {
-    return lcd_call_bam_regions_out(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, chunks, records, n_records, vcf_body, nullptr);
-}
-
-int lcd_call_bam_regions_out(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
-                             int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out) {
-    return lcd_call_bam_regions_fields(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, nullptr, chunks, records, n_records, vcf_body, bam_out, nullptr);
-}
-
-namespace {
-int call_bam_regions_core(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
-                          int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
-                          lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out, bool refine, lcd_refine_stats_t *refine_stats);
-}
-int lcd_call_bam_regions_fields(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
-                                int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
-                                lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out) {
-    return call_bam_regions_core(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, fields, chunks, records, n_records, vcf_body, bam_out, fields_out, false, nullptr);
-}
-int lcd_call_bam_regions_refine(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
-                                int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out,
-                                lcd_refine_stats_t *refine_stats) {
-    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
-    // (without -b the option has no effect, as in the reference: no log is written)
-    return call_bam_regions_core(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, nullptr, chunks, records, n_records, vcf_body, bam_out, nullptr, bam_out != nullptr,
-                                 refine_stats);
-}
-namespace {
-int call_bam_regions_core(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
-                          int min_mapq, const lcd_cfg_t *cfg, const lcd_vcf_fields_t *fields, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
-                          lcd_bam_out_t *bam_out, lcd_vcf_fields_out_t *fields_out, bool refine, lcd_refine_stats_t *refine_stats) {
+                         int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out,
+                         const lcd_run_opt_t *opt, const lcd_run_out_t *out) {
     const std::string W = "lcd_call_bam_regions";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (vcf_body) *vcf_body = nullptr;
-    if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
+    zero_run_out(out);
+    if (int rc = check_aln_opt(W, opt)) return rc;
+    if (opt && opt->aln && opt->aln->format == LCD_ALN_SAM) return set_err(-2, W + ": SAM text is not supported by this driver (lcd_write_phased on the called chunks writes it)");
+    if (opt && opt->idx) return set_err(-4, W + ": index options are not supported by this driver");
+    const lcd_vcf_fields_t *fields = opt ? opt->fields : nullptr;
+    lcd_vcf_fields_out_t *fields_out = out ? out->fields_out : nullptr;
+    const bool refine = opt && opt->aln && opt->aln->refine && bam_out;     // (without -b the option has no effect, as in the reference: no log is written)
     if (!bam_path || !bai_path || !fasta_path || !chrom || !cfg || !records || !n_records || !vcf_body) return set_err(-4, W + ": NULL argument");
     if (bam_out && !bam_out->path) return set_err(-4, W + ": bam_out without a path");
     if (n < 0 || (n > 0 && (!reg_beg || !reg_end || !chunks))) return set_err(-4, W + ": bad region list");
@@ -587,12 +533,14 @@ int call_bam_regions_core(const char *bam_path, const char *bai_path, const char
     }
     int rc = chunks_call_core(n, chunks, cfg, chrom, nullptr, &fr, records, n_records, vcf_body);
     if (rc == 0) fr.give(fields_out);
-    if (rc == 0 && bam_out) rc = lcd_write_phased_bam_refine(bam_path, n, chunks, bam_out, refine_stats);   // (a failure here leaves the records and the text valid)
+    if (rc == 0 && bam_out) {   // (a failure here leaves the records and the text valid)
+        lcd_writer_opt_t wo; memset(&wo, 0, sizeof(wo)); wo.refine_stats = out ? out->refine_stats : nullptr;
+        rc = lcd_write_phased(bam_path, n, chunks, bam_out, &wo);
+    }
     const std::string m = g_err;
     drop_inputs();
     g_err = m;
     return rc;
 }
-} // namespace
 
 } // extern "C"

@@ -329,7 +329,7 @@ struct Run {
                 const int64_t flank = 50000, len = w.metas[c].target_len;
                 const int64_t b0 = std::max<int64_t>(flank, lo1 - 1) - flank, e0 = std::min<int64_t>(len - flank - 1, hi1 - 1) + flank;
                 const int64_t got = lcd_fasta_fetch(job->fasta_path, chrom, b0 + 1, e0 + 1, &w.refs[c]);
-                if (got <= 0) { bad(got < 0 ? (int)got : -30, std::string("lcd_call_file: no reference sequence for ") + chrom + ":" + std::to_string(rb) + "-" + std::to_string(re) + " (" + (got < 0 ? lcd_io_last_error() : "empty window") + ")"); continue; }
+                if (got <= 0) { bad(got < 0 ? (int)got : -30, std::string("lcd_call_files: no reference sequence for ") + chrom + ":" + std::to_string(rb) + "-" + std::to_string(re) + " (" + (got < 0 ? lcd_io_last_error() : "empty window") + ")"); continue; }
                 lcd_chunk_src_t src; src.ref_seq = (const char *)w.refs[c]; src.ref_beg = b0 + 1; src.ref_end = b0 + got; src.is_ont = is_ont;
                 if (int r2 = lcd_chunk_resolve(w.handles[c], &src)) { bad(r2, g_err); continue; }
                 if (refine) if (int r3 = lcd_chunk_set_refine(w.handles[c], 1)) { bad(r3, g_err); continue; }
@@ -394,18 +394,18 @@ struct Run {
 };
 } // namespace
 
-namespace {
-// the whole-file run over the n input files of one sample; in == NULL: the one file of the job (lcd_call_file / lcd_call_file_indexed)
-int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
-                    lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out, bool refine = false,
-                    lcd_refine_stats_t *refine_stats = nullptr, int aln_format = LCD_ALN_BAM, lcd_sam_stats_t *sam_stats = nullptr) {
-    if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats));
-    if (sam_stats) memset(sam_stats, 0, sizeof(*sam_stats));
+// the whole-file run over the input files of one sample; in == NULL: the one file of the job
+extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out) {
+    const std::string W = "lcd_call_files";
+    const lcd_index_opt_t *idx = opt ? opt->idx : nullptr;
+    const lcd_vcf_fields_t *fields = opt ? opt->fields : nullptr;
+    lcd_vcf_fields_out_t *fields_out = out ? out->fields_out : nullptr;
+    int64_t *n_reads_per_file = out ? out->n_reads_per_file : nullptr;
+    zero_run_out(out);
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
-    lcd_index_stats_t ist_local;
-    lcd_index_stats_t *ist = idx_stats ? idx_stats : &ist_local;
-    memset(ist, 0, sizeof(*ist));
+    lcd_index_stats_t ist_local; memset(&ist_local, 0, sizeof(ist_local));
+    lcd_index_stats_t *ist = out && out->idx_stats ? out->idx_stats : &ist_local;
+    if (int rc = check_aln_opt(W, opt)) return rc;
     if (idx && idx->write_out_bai && (!job || !job->bam_out)) return set_err(-4, W + ": write_out_bai needs bam_out");
     if (idx && idx->slab_members < 0) return set_err(-4, W + ": negative slab_members");
     if (!job || !cfg || !stats || (!in && !job->bam_path) || !job->fasta_path) return set_err(-4, W + ": NULL argument");
@@ -416,7 +416,7 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
         if (job->bai_path && in->bai_paths && in->bai_paths[0] && strcmp(job->bai_path, in->bai_paths[0]) != 0) return set_err(-4, W + ": job->bai_path must be NULL or the first input's index");
     }
     if (job->bam_out && !job->bam_out->path) return set_err(-4, W + ": bam_out without a path");
-    const bool sam = aln_format == LCD_ALN_SAM && job->bam_out;
+    const bool sam = opt && opt->aln && opt->aln->format == LCD_ALN_SAM && job->bam_out;
     if (sam && idx && idx->write_out_bai) return set_err(-4, W + ": a SAM output has no index (write_out_bai)");
     if (sam && !strcmp(job->bam_out->path, "-") && (!job->vcf_path || !strcmp(job->vcf_path, "-"))) return set_err(-4, W + ": the SAM output and the VCF cannot both go to stdout");
     if (job->window_chunks < 0 || job->loader_threads < 0 || job->chunk_len < 0 || job->overlap < -1 || job->overlap > 1) return set_err(-4, W + ": negative window_chunks / loader_threads / chunk_len, or overlap outside -1 ... 1");
@@ -425,7 +425,7 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
     FieldsRun fr; fr.collect_rnames = fields_out != nullptr && job->keep_records;
     if (int rc = fr.open(fields, W)) return rc;     // (an unreadable TE file: before an index is built or an output file is created)
     Run R; R.job = job; R.cfg = cfg; R.st = stats; R.fields = &fr;
-    R.refine = refine && job->bam_out;     // (without an alignment output the option has no effect, as in the reference)
+    R.refine = opt && opt->aln && opt->aln->refine && job->bam_out;     // (without an alignment output the option has no effect, as in the reference)
     memset(&R.plan, 0, sizeof(R.plan)); memset(&R.carry, 0, sizeof(R.carry));
     const int n_in = in ? in->n : 1;
     for (int f = 0; f < n_in; ++f) {
@@ -444,7 +444,7 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
         const std::string p = is_bai ? R.bais[which] : std::string(job->fasta_path) + ".fai";
         FILE *f = fopen(p.c_str(), "rb");
         if (f) { fclose(f); continue; }
-        if (!idx) return set_err(-30, W + ": cannot open the index " + p + " (the library does not build indexes here: lcd_call_file_indexed / --make-index does)");
+        if (!idx) return set_err(-30, W + ": cannot open the index " + p + " (the library does not build indexes here: lcd_run_opt_t.idx / --make-index does)");
         if (!(is_bai ? idx->build_missing_bai : idx->build_missing_fai))
             return set_err(-30, W + ": cannot open the index " + p + " (lcd_index_opt_t." + (is_bai ? "build_missing_bai" : "build_missing_fai") + " would build it)");
         const double t0 = now_ms();
@@ -511,12 +511,13 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
         free(hdr); free(sm);
         if (!R.vcf) { lcd_file_stats_free(stats); return -30; }
         if (job->bam_out) {
-            R.bam = sam ? lcd_bam_writer_open_sam(bam0, job->bam_out)
-                        : idx && idx->write_out_bai ? lcd_bam_writer_open_indexed(bam0, job->bam_out, idx->out_bai_path, ist) : lcd_bam_writer_open(bam0, job->bam_out);
+            lcd_writer_opt_t wo; memset(&wo, 0, sizeof(wo));
+            wo.format = sam ? LCD_ALN_SAM : LCD_ALN_BAM; wo.sort_output = in ? in->sort_output : 0;
+            if (idx && idx->write_out_bai) { wo.write_index = 1; wo.index_path = idx->out_bai_path; wo.idx_stats = ist; }
+            if (R.refine) wo.refine_stats = out ? out->refine_stats : nullptr;
+            if (sam) wo.sam_stats = out ? out->sam_stats : nullptr;
+            R.bam = lcd_bam_writer_open(bam0, job->bam_out, &wo);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
-            lcd_bam_writer_set_sort(R.bam, in ? in->sort_output : 0);
-            if (R.refine) lcd_bam_writer_set_refine_stats(R.bam, refine_stats);
-            if (sam) lcd_bam_writer_set_sam_stats(R.bam, sam_stats);
         }
     }
     const int n_windows = (R.plan.n + window - 1) / window;
@@ -576,53 +577,4 @@ int call_files_core(const std::string &W, const lcd_inputs_t *in, const lcd_file
     if (n_reads_per_file) for (int f = 0; f < n_in; ++f) n_reads_per_file[f] = R.reads_per_file[f];
     stats->ms_wall = now_ms() - t_wall;
     return rc ? set_err(rc, R.err_msg) : 0;
-}
-} // namespace
-
-extern "C" int lcd_call_file(const lcd_file_job_t *job, const lcd_cfg_t *cfg, lcd_file_stats_t *stats) { return lcd_call_file_indexed(job, cfg, nullptr, stats, nullptr); }
-
-extern "C" int lcd_call_file_indexed(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats) {
-    return lcd_call_file_fields(job, cfg, idx, nullptr, stats, idx_stats, nullptr);
-}
-
-extern "C" int lcd_call_file_fields(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields, lcd_file_stats_t *stats,
-                                    lcd_index_stats_t *idx_stats, lcd_vcf_fields_out_t *fields_out) {
-    return call_files_core(idx ? "lcd_call_file_indexed" : "lcd_call_file", nullptr, job, cfg, idx, fields, stats, idx_stats, nullptr, fields_out);
-}
-
-extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
-                              lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file) {
-    return lcd_call_files_fields(in, job, cfg, idx, nullptr, stats, idx_stats, n_reads_per_file, nullptr);
-}
-
-extern "C" int lcd_call_files_fields(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
-                                     lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out) {
-    if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); if (fields_out) memset(fields_out, 0, sizeof(*fields_out)); return set_err(-4, "lcd_call_files: NULL argument"); }
-    return call_files_core("lcd_call_files", in, job, cfg, idx, fields, stats, idx_stats, n_reads_per_file, fields_out);
-}
-
-extern "C" int lcd_call_file_refine(const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats,
-                                    lcd_refine_stats_t *refine_stats) {
-    return call_files_core(idx ? "lcd_call_file_indexed" : "lcd_call_file", nullptr, job, cfg, idx, nullptr, stats, idx_stats, nullptr, nullptr, true, refine_stats);
-}
-extern "C" int lcd_call_files_refine(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, lcd_file_stats_t *stats,
-                                     lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_refine_stats_t *refine_stats) {
-    if (!in) { if (stats) memset(stats, 0, sizeof(*stats)); if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats)); return set_err(-4, "lcd_call_files: NULL argument"); }
-    return call_files_core("lcd_call_files", in, job, cfg, idx, nullptr, stats, idx_stats, n_reads_per_file, nullptr, true, refine_stats);
-}
-
-extern "C" int lcd_call_files_aln(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_index_opt_t *idx, const lcd_vcf_fields_t *fields,
-                                  const lcd_aln_opt_t *aln, lcd_file_stats_t *stats, lcd_index_stats_t *idx_stats, int64_t *n_reads_per_file, lcd_vcf_fields_out_t *fields_out,
-                                  lcd_refine_stats_t *refine_stats, lcd_sam_stats_t *sam_stats) {
-    const std::string W = "lcd_call_files_aln";
-    auto refuse = [&](int code, const std::string &m) {
-        if (stats) memset(stats, 0, sizeof(*stats)); if (fields_out) memset(fields_out, 0, sizeof(*fields_out));
-        if (refine_stats) memset(refine_stats, 0, sizeof(*refine_stats)); if (sam_stats) memset(sam_stats, 0, sizeof(*sam_stats));
-        return set_err(code, W + ": " + m);
-    };
-    if (!aln) return refuse(-4, "NULL argument");
-    if (aln->format != LCD_ALN_BAM && aln->format != LCD_ALN_SAM) return refuse(-4, "format must be LCD_ALN_BAM or LCD_ALN_SAM");
-    if (aln->refine && fields) return refuse(-2, "refined alignments together with the VCF fields are not supported");
-    const char *name = in ? "lcd_call_files" : idx ? "lcd_call_file_indexed" : "lcd_call_file";
-    return call_files_core(name, in, job, cfg, idx, fields, stats, idx_stats, n_reads_per_file, fields_out, aln->refine != 0, refine_stats, aln->format, sam_stats);
 }

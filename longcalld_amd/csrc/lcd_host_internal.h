@@ -162,7 +162,7 @@ struct RegionRec {
 // pre_process_noisy_regs' host part in front of the read support (lcd_noisy_regs.cpp): cr_index, low-complexity extension, cr_merge twice
 void pre_regs_merge(std::vector<NIv> &v, const int64_t *low_comp, int n_low);
 
-// lcd_call_file's links of a window of chunks to what lies outside it (lcd_call.cpp: chunks_call_core)
+// lcd_call_files' links of a window of chunks to what lies outside it (lcd_call.cpp: chunks_call_core)
 struct CallLinks { const char *const *chroms; const int *tids; const lcd_stitch_carry_t *carry_in; lcd_stitch_carry_t *carry_out; int next_tid; int64_t next_beg, next_end; };
 // the VCF options of one driver call (lcd_vcf_fields_t), resolved once: the TE library and its names, the names mode; and what the call gives back
 // (lcd_vcf_fields_out_t).  The library is read-only after open(); n_mei / rnames are written by the one thread that runs chunks_call_core
@@ -177,6 +177,21 @@ struct FieldsRun {
 };
 int chunks_call_core(int n, lcd_call_chunk_t *chunks, const lcd_cfg_t *cfg, const char *chrom, const CallLinks *links, FieldsRun *fields, lcd_var1_t **records, int *n_records,
                      char **vcf_body);
+// a driver's entry: every output the caller named is zeroed, refusal paths included (n_reads_per_file has the driver's own length and is zeroed there)
+inline void zero_run_out(const lcd_run_out_t *out) {
+    if (!out) return;
+    if (out->idx_stats) memset(out->idx_stats, 0, sizeof(*out->idx_stats));
+    if (out->fields_out) memset(out->fields_out, 0, sizeof(*out->fields_out));
+    if (out->refine_stats) memset(out->refine_stats, 0, sizeof(*out->refine_stats));
+    if (out->sam_stats) memset(out->sam_stats, 0, sizeof(*out->sam_stats));
+}
+// what the two drivers refuse of lcd_run_opt_t.aln before anything else
+inline int check_aln_opt(const std::string &W, const lcd_run_opt_t *opt) {
+    if (!opt || !opt->aln) return 0;
+    if (opt->aln->format != LCD_ALN_BAM && opt->aln->format != LCD_ALN_SAM) return set_err(-4, W + ": format must be LCD_ALN_BAM or LCD_ALN_SAM");
+    if (opt->aln->refine && opt->fields) return set_err(-2, W + ": refined alignments together with the VCF fields are not supported");
+    return 0;
+}
 
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
@@ -263,7 +278,7 @@ struct lcd_chunk_s {
     std::vector<uint8_t> source, pal; uint64_t tag_bytes = 0;   // lcd_chunk_create_from_bam_src: LCD_SRC_* and is_ont_palindrome per read; cs / MD bytes brought to the host
     double stage_ms[4] = {0, 0, 0, 0};                          // ... and its wall-clock split: aux fields, reference comparison, tag download + host parse, digars
     bool from_bam = false; std::vector<uint64_t> aux_off, rec_end;   // lcd_chunk_create_from_bam*: per read its auxiliary fields [aux_off, rec_end) as offsets of the inflated stream (lcd_chunk_read_nm)
-    // lcd_chunk_create_from_bam*: EVERY record the region's iterator yields, in file order (lcd_chunk_tag_records, lcd_write_phased_bam): [rec_beg, rec_stop) of the
+    // lcd_chunk_create_from_bam*: EVERY record the region's iterator yields, in file order (lcd_chunk_tag_records, lcd_write_phased): [rec_beg, rec_stop) of the
     // inflated stream from its block_size word on, the chunk read id of a kept record or -1 for one the loader's flag / MAPQ filter dropped, pos0 and bam_endpos
     std::vector<uint64_t> rec_beg, rec_stop; std::vector<int> rec_read; std::vector<int64_t> rec_pos0, rec_endpos;
     // lcd_chunk_open_from_bams: the number of input files (1 otherwise), and per record / per kept read the file it came from; both tables are file-major

@@ -13,5 +13,5 @@ struct LcdRegionImage { std::vector<uint8_t> image; std::vector<std::pair<uint64
 int lcd_io_region_image(const char *bam_path, const char *bai_path, const char *chrom, int64_t reg_beg, int64_t reg_end, LcdRegionImage &out);
 // The inflated size comes from the members' ISIZE footers: nothing is inflated to learn it.  On failure lcd_io_last_error names the file.
 int lcd_io_region_images(int n, const char *const *bam_paths, const char *const *bai_paths, const char *chrom, int64_t reg_beg, int64_t reg_end, LcdRegionImage &out);
-// The BAM header block (magic, l_text, text, n_ref, reference table) as it lies in the file's inflated stream (lcd_write_phased_bam copies it to the output).
+// The BAM header block (magic, l_text, text, n_ref, reference table) as it lies in the file's inflated stream (lcd_bam_writer_open copies it to the output).
 int lcd_io_bam_header(const char *bam_path, std::vector<uint8_t> &hdr);

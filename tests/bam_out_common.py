@@ -1,4 +1,4 @@
-"""Pure-Python oracle of the phased alignment output (lcd_chunk_tag_records, lcd_write_phased_bam): the HP:i / PS:i rewrite of write_read_to_bam
+"""Pure-Python oracle of the phased alignment output (lcd_chunk_tag_records, lcd_write_phased): the HP:i / PS:i rewrite of write_read_to_bam
 (src/bam_utils.c:1944-2006) on one record, a region's record stream with its skip counts, and the pieces the GPU tests need to read a BGZF / BAM file back.
 Written from the rules of include/lcd_hotpath.h, on bam_src_common.aux_walk (bam_aux_get's walk).  Every decision leaves a named entry in `trace`, so that
 tests/test_bam_out_oracle.py can prove from the oracle's own trace that each condition of its case table was reached.

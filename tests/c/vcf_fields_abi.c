@@ -1,6 +1,7 @@
-/* TEST ONLY: lcd_vcf_fields_t / lcd_vcf_fields_out_t of include/lcd_hotpath.h.  Without arguments: sizes and field offsets in the format of call_file_abi.c
- * (tests/test_vcf_fields.py compares them with the ctypes mirrors).  With <in.bam> <ref.fa> <out prefix> [te.fa]: the whole-file run through lcd_call_file and
- * through lcd_call_file_fields with a NULL options struct, with a zeroed one and -- when te.fa is given -- with that library; every run writes
+/* TEST ONLY: lcd_vcf_fields_t / lcd_vcf_fields_out_t and the drivers' option structs (lcd_run_opt_t, lcd_run_out_t, lcd_writer_opt_t) of include/lcd_hotpath.h.
+ * Without arguments: sizes and field offsets in the format of call_file_abi.c (tests/test_vcf_fields.py compares them with the ctypes mirrors).  With <in.bam>
+ * <ref.fa> <out prefix> [te.fa]: the whole-file run through lcd_call_files without options, and with lcd_run_opt_t whose fields member is NULL, a zeroed
+ * lcd_vcf_fields_t and -- when te.fa is given -- that library; every run writes
  * <prefix>.<tag>.vcf and <prefix>.<tag>.bam and prints "<tag> rc <code> lines <VCF lines> mei <MEI lines> err <lcd_last_error>". */
 #include <stddef.h>
 #include <stdio.h>
@@ -20,7 +21,9 @@ static void run(const char *tag, const char *bam, const char *fa, const char *pr
     job.bam_path = bam; job.fasta_path = fa; job.chunk_len = 6000; job.vcf_path = vcf; job.bam_out = &bo;
     job.source_version = "test-1"; job.cmdline = "call ref.fa in.bam"; job.date_yyyymmdd = "20240102";
     lcd_file_stats_t st; lcd_vcf_fields_out_t fo; memset(&fo, 0, sizeof(fo));
-    const int rc = use_fields ? lcd_call_file_fields(&job, &cfg, NULL, fields, &st, NULL, &fo) : lcd_call_file(&job, &cfg, &st);
+    lcd_run_opt_t opt; memset(&opt, 0, sizeof(opt)); opt.fields = fields;
+    lcd_run_out_t ro; memset(&ro, 0, sizeof(ro)); ro.fields_out = &fo;
+    const int rc = use_fields ? lcd_call_files(NULL, &job, &cfg, &opt, &st, &ro) : lcd_call_files(NULL, &job, &cfg, NULL, &st, NULL);
     printf("%s rc %d lines %lld mei %lld err %s\n", tag, rc, (long long)st.n_vcf_lines, (long long)fo.n_mei_lines, rc < 0 ? lcd_last_error() : "");
     lcd_file_stats_free(&st); lcd_vcf_fields_out_free(&fo);
 }
@@ -32,6 +35,13 @@ int main(int argc, char **argv) {
         SZ(lcd_vcf_fields_out_t);
         OFF(lcd_vcf_fields_out_t, n_te_seqs); OFF(lcd_vcf_fields_out_t, te_names); OFF(lcd_vcf_fields_out_t, n_mei_lines); OFF(lcd_vcf_fields_out_t, n_rnames);
         OFF(lcd_vcf_fields_out_t, rnames);
+        SZ(lcd_run_opt_t);
+        OFF(lcd_run_opt_t, idx); OFF(lcd_run_opt_t, fields); OFF(lcd_run_opt_t, aln);
+        SZ(lcd_run_out_t);
+        OFF(lcd_run_out_t, idx_stats); OFF(lcd_run_out_t, n_reads_per_file); OFF(lcd_run_out_t, fields_out); OFF(lcd_run_out_t, refine_stats); OFF(lcd_run_out_t, sam_stats);
+        SZ(lcd_writer_opt_t);
+        OFF(lcd_writer_opt_t, format); OFF(lcd_writer_opt_t, sort_output); OFF(lcd_writer_opt_t, write_index); OFF(lcd_writer_opt_t, index_path);
+        OFF(lcd_writer_opt_t, idx_stats); OFF(lcd_writer_opt_t, refine_stats); OFF(lcd_writer_opt_t, sam_stats);
         printf("LCD_RNAMES_NONE %d\nLCD_RNAMES_SV %d\nLCD_RNAMES_ALL %d\n", LCD_RNAMES_NONE, LCD_RNAMES_SV, LCD_RNAMES_ALL);
         return 0;
     }

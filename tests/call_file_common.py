@@ -1,4 +1,4 @@
-"""Helpers of the whole-file tests (lcd_plan_chunks, lcd_call_file): a multi-contig BAM + .bai writer and a multi-contig FASTA + .fai writer built from the
+"""Helpers of the whole-file tests (lcd_plan_chunks, lcd_call_files): a multi-contig BAM + .bai writer and a multi-contig FASTA + .fai writer built from the
 writers of tests/test_io.py, and the chunk plan restated in Python from the rules of include/lcd_hotpath.h (collect_regions, src/call_var_main.c:404-634)."""
 import struct
 

@@ -1,4 +1,4 @@
-"""Pure-Python oracle of the SAM text output (lcd_records_to_sam, lcd_tagged_to_sam, lcd_write_phased_sam): one BAM record body -> its SAM line, the header text,
+"""Pure-Python oracle of the SAM text output (lcd_records_to_sam, lcd_tagged_to_sam, lcd_write_phased): one BAM record body -> its SAM line, the header text,
 glibc's %g of a float32, a parser from a line back to a record, and the case table the GPU test runs.  Written from the rules of include/lcd_hotpath.h
 (lcd_tagged_to_sam) on bam_src_common.aux_walk (the field walk and its stop rule).  sam_line leaves a named entry in `trace` for every decision, so that
 tests/test_sam_out_oracle.py can prove from the oracle's own output that each condition of the case table was reached."""
@@ -153,7 +153,7 @@ def header_parts(hdr):
 
 
 def sam_header(header_block, pg_line):
-    """the SAM header of lcd_bam_writer_open_sam: the text without trailing NULs, pg_line (bytes or None) appended as the BAM writer appends it, a newline at the end;
+    """the SAM header of lcd_bam_writer_open (LCD_ALN_SAM): the text without trailing NULs, pg_line (bytes or None) appended as the BAM writer appends it, a newline at the end;
     no line starting with @SQ<tab> and a table with contigs: @SQ lines in table order behind a leading @HD line, or at the front"""
     text, refs = header_parts(header_block)
     text = text.rstrip(b"\0")

@@ -17,7 +17,7 @@ from conftest import ROOT
 REF_BAM = "/root/reference/test_data/HG002_chr11_hifi_test.bam"
 FIXTURE = os.path.join(ROOT, "tests", "golden", "bai_hg002.npz")
 NEW = ["lcd_bai_from_records", "lcd_bai_builder_create", "lcd_bai_builder_add_stream", "lcd_bai_builder_finish", "lcd_bai_builder_bytes", "lcd_bai_builder_destroy",
-       "lcd_bai_build", "lcd_fai_build", "lcd_bam_writer_open_indexed", "lcd_call_file_indexed"]
+       "lcd_bai_build", "lcd_fai_build", "lcd_bam_writer_open", "lcd_call_files"]
 
 
 @pytest.fixture(scope="module")
@@ -197,8 +197,13 @@ def test_host_exports_refuse_bad_arguments(lcd):
     assert lib.lcd_fai_build(None, None) == -4
     assert lib.lcd_bai_build(None, None, None, None) == -4
     assert lib.lcd_bai_builder_add_stream(None, 0, 0, 0, 0, None, 0, None) == -4 and lib.lcd_bai_builder_finish(None, None) == -4
-    assert not lib.lcd_bam_writer_open_indexed(None, None, None, None)
-    assert lib.lcd_call_file_indexed(None, None, None, None, None) == -4
+    from longcalld_amd import _lib
+    ist = _lib.LcdIndexStats()
+    wo = _lib.LcdWriterOpt(write_index=1, idx_stats=C.pointer(ist))
+    assert not lib.lcd_bam_writer_open(None, None, C.byref(wo))
+    io = _lib.LcdIndexOpt()
+    ro, out = _lib.LcdRunOpt(idx=C.pointer(io)), _lib.LcdRunOut(idx_stats=C.pointer(ist))
+    assert lib.lcd_call_files(None, None, None, C.byref(ro), None, C.byref(out)) == -4
 
 
 def cli(*args):

@@ -7,7 +7,7 @@ from conftest import ROOT
 
 NEW = ["lcd_bgzf_deflate_dev", "lcd_bgzf_deflate_dev_ptr", "lcd_deflated_size", "lcd_deflated_n_blocks", "lcd_deflated_kernel_ms", "lcd_deflated_block_info",
        "lcd_deflated_to_host", "lcd_deflated_free", "lcd_chunk_tag_records", "lcd_tagged_dev_ptr", "lcd_tagged_size", "lcd_tagged_n_records", "lcd_tagged_to_host",
-       "lcd_tagged_free", "lcd_write_phased_bam", "lcd_call_bam_regions_out"]
+       "lcd_tagged_free", "lcd_write_phased", "lcd_call_bam_regions"]
 
 
 def test_new_symbols_declared_listed_and_exported():
@@ -35,4 +35,4 @@ def test_arguments_are_checked_before_any_device_work():
     assert lib.lcd_deflated_size(None) == 0 and lib.lcd_tagged_size(None) == 0 and lib.lcd_tagged_n_records(None) == 0
     assert not lib.lcd_chunk_tag_records(None, None, None, 0, 0) and b"not made from a BAM" in lib.lcd_last_error()
     bo = _lib.LcdBamOut(); bo.path = None
-    assert lib.lcd_write_phased_bam(b"x.bam", 0, None, ctypes.byref(bo)) < 0 and b"NULL" in lib.lcd_last_error()
+    assert lib.lcd_write_phased(b"x.bam", 0, None, ctypes.byref(bo), None) < 0 and b"NULL" in lib.lcd_last_error()

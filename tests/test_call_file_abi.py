@@ -13,7 +13,7 @@ from conftest import ROOT
 
 NEW = ["lcd_bam_contigs", "lcd_bam_contigs_free", "lcd_bam_sample_name", "lcd_plan_chunks", "lcd_chunk_plan_free", "lcd_stitch_chunks_carry", "lcd_stitch_carry_free",
        "lcd_chunk_open_from_bam", "lcd_chunk_resolve", "lcd_bam_writer_open", "lcd_bam_writer_append", "lcd_bam_writer_close", "lcd_bam_writer_abort", "lcd_vcf_writer_open",
-       "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_call_file", "lcd_file_stats_free"]
+       "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_call_files", "lcd_file_stats_free"]
 
 
 def test_new_symbols_declared_listed_and_exported():
@@ -68,7 +68,7 @@ def run_file(lcd, bam, fa, cfg=None, **kw):
         setattr(job, k, v)
     st = _lib.LcdFileStats()
     cfg = cfg if cfg is not None else lcd.call_cfg()
-    rc = lib.lcd_call_file(C.byref(job), C.byref(cfg), C.byref(st))
+    rc = lib.lcd_call_files(None, C.byref(job), C.byref(cfg), None, C.byref(st), None)
     msg = lib.lcd_last_error().decode()
     lib.lcd_file_stats_free(C.byref(st))
     return rc, msg
@@ -78,16 +78,16 @@ def test_argument_errors(lcd, files, tmp_path):
     from longcalld_amd import _lib
     bam, fa = files
     lib = lcd.load_library()
-    assert lib.lcd_call_file(None, None, None) == -4
+    assert lib.lcd_call_files(None, None, None, None, None, None) == -4
     assert run_file(lcd, None, fa)[0] == -4 and run_file(lcd, bam, None)[0] == -4
     for kw in (dict(window_chunks=-1), dict(loader_threads=-2), dict(chunk_len=-5), dict(overlap=2), dict(overlap=-2)):
         rc, msg = run_file(lcd, bam, fa, **kw)
-        assert rc == -4 and "lcd_call_file" in msg, kw
+        assert rc == -4 and "lcd_call_files" in msg, kw
     bo = _lib.LcdBamOut(); bo.path = None
     assert run_file(lcd, bam, fa, bam_out=C.pointer(bo))[0] == -4
     assert lib.lcd_chunk_resolve(None, None) == -4 and b"lcd_chunk_resolve" in lib.lcd_last_error()
     assert not lib.lcd_chunk_open_from_bam(None, None, None, None, 1, 2, 0, 0, None) and b"NULL" in lib.lcd_last_error()
-    assert not lib.lcd_bam_writer_open(None, None) and b"NULL" in lib.lcd_last_error()
+    assert not lib.lcd_bam_writer_open(None, None, None) and b"NULL" in lib.lcd_last_error()
     assert lib.lcd_bam_writer_append(None, 0, None, None, None) == -4 and lib.lcd_bam_writer_close(None) == -4
     assert lib.lcd_vcf_writer_append(None, b"x") == -4 and lib.lcd_vcf_writer_close(None) == -4
     assert lib.lcd_bam_contigs(None, None, None, None) == -4 and lib.lcd_bam_sample_name(None, None) == -4

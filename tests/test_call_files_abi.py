@@ -13,7 +13,7 @@ import call_file_common as fc
 from conftest import ROOT
 from test_call_file_abi import cli
 
-NEW = ["lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_bam_writer_set_sort", "lcd_call_files"]
+NEW = ["lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_bam_writer_open", "lcd_call_files"]
 
 
 def test_new_symbols_declared_listed_and_exported():
@@ -37,7 +37,7 @@ def test_struct_mirror_has_the_compilers_layout(tmp_path):
     assert [f[0] for f in _lib.LcdInputs._fields_] == [k.split(".")[1] for k in want if k.startswith("lcd_inputs_t.")]
     for f, _t in _lib.LcdInputs._fields_:
         assert getattr(_lib.LcdInputs, f).offset == int(want[f"lcd_inputs_t.{f}"]), f
-    # the structs the new entry point shares with lcd_call_file_indexed keep their layouts
+    # the structs the several-input run shares with the one-file run keep their layouts
     for name, cls in (("lcd_file_job_t", _lib.LcdFileJob), ("lcd_file_stats_t", _lib.LcdFileStats), ("lcd_index_opt_t", _lib.LcdIndexOpt), ("lcd_index_stats_t", _lib.LcdIndexStats)):
         assert C.sizeof(cls) == int(want[name]), name
     assert (_lib.LCD_MAX_INPUTS, _lib.LCD_ERR_INPUT_HEADERS) == (int(want["LCD_MAX_INPUTS"]), int(want["LCD_ERR_INPUT_HEADERS"])) == (64, -54)
@@ -68,7 +68,8 @@ def run_files(lcd, bams, fa, bais=None, sort_output=0, idx=None, n=None, **kw):
     st = _lib.LcdFileStats(); per = (C.c_int64 * max(1, len(bams)))()
     cfg = lcd.call_cfg()
     io = _lib.LcdIndexOpt(*idx) if idx else None
-    rc = lib.lcd_call_files(C.byref(inp), C.byref(job), C.byref(cfg), C.byref(io) if io else None, C.byref(st), None, per)
+    ro, out = _lib.LcdRunOpt(idx=C.pointer(io) if io else None), _lib.LcdRunOut(n_reads_per_file=C.cast(per, C.POINTER(C.c_int64)))
+    rc = lib.lcd_call_files(C.byref(inp), C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
     msg = lib.lcd_last_error().decode()
     lib.lcd_file_stats_free(C.byref(st))
     return rc, msg
@@ -78,10 +79,11 @@ def test_argument_errors_are_minus_4(lcd, files, tmp_path):
     from longcalld_amd import _lib
     a, b, fa = files
     lib = lcd.load_library()
-    assert lib.lcd_call_files(None, None, None, None, None, None, None) == -4
+    assert lib.lcd_call_files(None, None, None, None, None, None) == -4
     job = _lib.LcdFileJob(); lib.lcd_file_job_default(C.byref(job)); job.fasta_path = fa.encode()
     st = _lib.LcdFileStats(); cfg = lcd.call_cfg()
-    assert lib.lcd_call_files(None, C.byref(job), C.byref(cfg), None, C.byref(st), None, None) == -4 and b"lcd_call_files" in lib.lcd_last_error()
+    assert not job.bam_path                                                          # neither `in` nor job->bam_path
+    assert lib.lcd_call_files(None, C.byref(job), C.byref(cfg), None, C.byref(st), None) == -4 and b"lcd_call_files" in lib.lcd_last_error()
     assert run_files(lcd, [], fa)[0] == -4                                            # n 0
     assert run_files(lcd, [a] * 65, fa)[0] == -4                                      # n > LCD_MAX_INPUTS
     assert run_files(lcd, [a, None], fa)[0] == -4 and run_files(lcd, [a, b], None)[0] == -4
@@ -99,7 +101,9 @@ def test_argument_errors_are_minus_4(lcd, files, tmp_path):
         assert not lib.lcd_chunk_open_from_bams(C.byref(opt), n, arr, None, b"chr1", 1, 2, 0, 0, None)
     arr[1] = None
     assert not lib.lcd_chunk_open_from_bams(C.byref(opt), 2, arr, None, b"chr1", 1, 2, 0, 0, None) and b"NULL path" in lib.lcd_last_error()
-    assert lib.lcd_bam_writer_set_sort(None, 1) == -4 and lib.lcd_chunk_read_files(None, None) == -4 and lib.lcd_chunk_n_files(None) == 0
+    wo = _lib.LcdWriterOpt(sort_output=1)
+    assert not lib.lcd_bam_writer_open(None, None, C.byref(wo)) and b"lcd_bam_writer_open" in lib.lcd_last_error()
+    assert lib.lcd_chunk_read_files(None, None) == -4 and lib.lcd_chunk_n_files(None) == 0
     assert not lib.lcd_chunk_tag_records_sel(None, None, None, None, None) and b"lcd_chunk_tag_records_sel" in lib.lcd_last_error()
 
 
@@ -127,7 +131,7 @@ def test_the_header_rule_and_a_missing_index_come_before_any_output(lcd, files, 
     assert rc == -30 and elsewhere in msg and not os.path.exists(vcf)
     with pytest.raises(lcd.LcdError, match="-54"):
         lcd.call_files([a, str(tmp_path / "len.bam")], fa, vcf_path=vcf)
-    with pytest.raises(lcd.LcdError, match="-2"):                                      # the refusals of lcd_call_file stay
+    with pytest.raises(lcd.LcdError, match="-2"):                                      # the refusals of the one-file run stay
         lcd.call_files([a, a], fa, vcf_path=vcf, cfg=lcd.call_cfg(0, clean=dict(out_somatic=1)))
 
 

@@ -1,4 +1,4 @@
-"""lcd_call_file on the MI355X: a whole BAM (five contigs) and a FASTA to one VCF and one phased BAM, in windows of chunks, against lcd_call_bam_regions(_out) per
+"""lcd_call_files with one file on the MI355X: a whole BAM (five contigs) and a FASTA to one VCF and one phased BAM, in windows of chunks, against lcd_call_bam_regions per
 contig with that contig's planned regions -- the merged code, itself pinned to the oracles (tests/test_gpu_call_chunks.py).  Records, VCF body, every chunk's flips
 and n_passes, and the output BAM's record stream must not depend on window_chunks, overlap or loader_threads."""
 import ctypes as C
@@ -60,7 +60,7 @@ def joined(parts):
 
 @pytest.fixture(scope="module")
 def yard(lcd, data):
-    """per contig lcd_call_bam_regions_out with the contig's planned regions, concatenated over the contigs the default mode keeps"""
+    """per contig lcd_call_bam_regions (with bam_out) with the contig's planned regions, concatenated over the contigs the default mode keeps"""
     plan, fb = lcd.plan_chunks(data["contigs"], chunk_len=CHUNK_LEN)
     assert fb == 0 and [(t, e - b + 1) for t, b, e in plan] == [(0, 6000)] * 2 + [(1, 6000)] * 2 + [(2, 6000)] * 3 + [(3, 6000)] * 2        # 2 + 2 + 3 + 2, chrM left out
     parts = {}

@@ -1,4 +1,4 @@
-"""lcd_call_file_indexed on the seeded multi-contig file of tests/test_gpu_call_file.py: the output BAM's .bai (built by the writer from the tagged stream in HBM)
+"""lcd_call_files with lcd_index_opt_t on the seeded multi-contig file of tests/test_gpu_call_file.py: the output BAM's .bai (built by the writer from the tagged stream in HBM)
 against the oracle's index of the written file, for every schedule; region queries on the output through lcd_bam_load_region_indexed; an output that is not sorted
 gets no index and says so; missing input indexes are built on request, change no result byte and are not touched again."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""lcd_call_bam_regions_out on the MI355X: two adjacent regions with reads across the cut, called and written as a phased BAM in one call.  The VCF side must be
+"""lcd_call_bam_regions with bam_out on the MI355X: two adjacent regions with reads across the cut, called and written as a phased BAM in one call.  The VCF side must be
 what lcd_call_bam_regions gives; the file must inflate with zlib block by block to the input's header plus the @PG line and the oracle's record stream
 (tests/bam_out_common.py) for the call's final haplotypes and phase sets, every shared read written once, by the first region."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""lcd_call_bam_regions_refine on the MI355X: the two-chunk seeded BAM in its EQX, cs, MD and plain-'M' spellings, called and written with refined alignments in one
+"""lcd_call_bam_regions with refined alignments on the MI355X: the two-chunk seeded BAM in its EQX, cs, MD and plain-'M' spellings, called and written with refined alignments in one
 call.  The VCF text and every read's HP / PS are those of the run without refine; every output record equals the oracle's (tests/refine_call_common.py); reads the
 two chunks share are written once; nothing is left unrefined; and the classes of change -- a CIGAR changed inside a noisy region, 'M' -> '=' / 'X', POS moved -- are
 shown on the oracle's output before anything is compared."""

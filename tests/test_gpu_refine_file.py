@@ -1,5 +1,5 @@
-"""lcd_call_file_refine / lcd_call_files_refine on the MI355X: two small contigs of plain-'M' reads called and written with refined alignments in one call.  The
-record stream is that of lcd_call_bam_regions_refine per contig (pinned to the oracle by tests/test_gpu_refine_call.py) and does not depend on window_chunks,
+"""lcd_call_files with refined alignments on the MI355X: two small contigs of plain-'M' reads called and written with refined alignments in one call.  The
+record stream is that of lcd_call_bam_regions (refined) per contig (pinned to the oracle by tests/test_gpu_refine_call.py) and does not depend on window_chunks,
 overlap, the VCF's -O z or --make-index; the file inflates with zlib and splits into records; its .bai equals the index oracle's for that very file, or is absent
 with the stated reason; the VCF is that of the run without refine.  Two input files once."""
 import gzip

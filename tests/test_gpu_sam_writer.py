@@ -1,7 +1,7 @@
-"""lcd_write_phased_sam / lcd_bam_writer_open_sam on the MI355X: the synthetic BAM of tests/test_gpu_bam_tags.py through chunk creation, a fixed haplotype state
+"""lcd_write_phased / lcd_bam_writer_open as SAM text on the MI355X: the synthetic BAM of tests/test_gpu_bam_tags.py through chunk creation, a fixed haplotype state
 and the writer.  The file is the oracle's header plus the oracle's lines of bam_out_common.tagged_stream's records, and it is the oracle formatting of the records
-decoded from what lcd_write_phased_bam writes for the same chunks (the BAM path against the SAM path) -- with one chunk, with two (the overlap skip), with
-lcd_bam_writer_set_sort, with a refine log on the chunk (refine_common's records), and with a header that has @SQ lines and NUL padding."""
+decoded from what the BAM format writes for the same chunks (the BAM path against the SAM path) -- with one chunk, with two (the overlap skip), with
+sort_output, with a refine log on the chunk (refine_common's records), and with a header that has @SQ lines and NUL padding."""
 import struct
 
 import pytest
@@ -79,7 +79,7 @@ def test_the_file_is_the_oracle_s_header_and_lines(lcd, bam, regions):
     hdr_b, bodies_b = bo.bam_split(inflate(out_bam))
     assert bodies_b == bodies and so.sam_text(bodies_b, NAMES)[0] == got[len(head):] and so.sam_header(hdr_b, None) == head
     assert stb["bam_out"]["n_records_out"] == b["n_records_out"] and stb["bam_out"]["ms_deflate"] > 0 and stb["sam"]["n_records"] == 0
-    # lcd_bam_writer_set_sort on a sorted input: the same lines, through open / append / close
+    # sort_output on a sorted input: the same lines, through open / append / close
     out_s = str(bam["dir"] / f"s{len(regions)}.sam")
     sts = lcd.write_phased_sam(bam["path"], chunks, out_s, pg_line=PG, sort_output=True)
     assert open(out_s, "rb").read() == got and {k: v for k, v in sts["sam"].items() if not k.startswith("ms_")} == wst

@@ -179,7 +179,7 @@ def test_region_and_chunk_entry_points_give_the_same_text(lcd, data, full):
 
 
 def test_no_options_and_zeroed_options_are_byte_identical(lcd, data, plain, tmp_path):
-    """the delegating entry points: lcd_call_file, lcd_call_file_fields with NULL and with a zeroed struct (from plain C, tests/c/vcf_fields_abi.c), and the Python run"""
+    """lcd_call_files without options, with lcd_run_opt_t.fields NULL and with a zeroed struct (from plain C, tests/c/vcf_fields_abi.c), and the Python run"""
     exe, libdir = str(tmp_path / "vcf_fields_abi"), os.path.join(ROOT, "longcalld_amd")
     subprocess.check_call(["gcc", "-O0", "-Wall", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "c", "vcf_fields_abi.c"), "-L", libdir, "-llcd_hotpath",
                            "-Wl,-rpath," + libdir, "-o", exe])

@@ -13,7 +13,7 @@ from test_call_file_abi import cli
 
 NEW = ["lcd_chunk_refine_records", "lcd_refine_log_create", "lcd_refine_log_free", "lcd_refine_log_n_entries", "lcd_refine_log_row_bytes", "lcd_refine_log_append",
        "lcd_refine_log_entry", "lcd_refine_log_apply", "lcd_chunks_noisy_rounds_log", "lcd_batch_region_ref_read_rows", "lcd_chunk_set_refine", "lcd_chunk_refine_log",
-       "lcd_chunks_call_refine", "lcd_write_phased_bam_refine", "lcd_bam_writer_set_refine_stats", "lcd_call_bam_regions_refine", "lcd_call_file_refine", "lcd_call_files_refine"]
+       "lcd_chunks_call_refine", "lcd_write_phased", "lcd_bam_writer_open", "lcd_call_bam_regions", "lcd_call_files"]
 
 
 def test_symbol_declared_listed_and_exported():
@@ -48,12 +48,20 @@ def test_argument_errors_need_no_device(lcd):
     assert b"lcd_chunk_refine_records" in lib.lcd_last_error() and b"not made from a BAM" in lib.lcd_last_error() and st.n_records == 0
     assert not lib.lcd_chunk_refine_records(None, 0, None, None, None, None, 1, 0, None, None, None, None, None)
     # the drivers: NULL arguments are answered as by the entry points they extend, and the stats come back zeroed
+    ao = _lib.LcdAlnOpt(_lib.LCD_ALN_BAM, 1)
+    ro, out = _lib.LcdRunOpt(aln=C.pointer(ao)), _lib.LcdRunOut(refine_stats=C.pointer(st))
     st.n_records = 7
-    assert lib.lcd_call_file_refine(None, None, None, None, None, C.byref(st)) == -4 and st.n_records == 0
+    assert lib.lcd_call_files(None, None, None, C.byref(ro), None, C.byref(out)) == -4 and st.n_records == 0
+    inp = _lib.LcdInputs()
     st.n_records = 7
-    assert lib.lcd_call_files_refine(None, None, None, None, None, None, None, C.byref(st)) == -4 and st.n_records == 0
-    assert lib.lcd_call_bam_regions_refine(None, None, None, None, 0, None, None, 30, None, None, None, None, None, None, None) == -4
-    assert lib.lcd_write_phased_bam_refine(None, 0, None, None, None) == -4 and lib.lcd_bam_writer_set_refine_stats(None, None) == -4
+    assert lib.lcd_call_files(C.byref(inp), None, None, C.byref(ro), None, C.byref(out)) == -4 and st.n_records == 0
+    st.n_records = 7
+    assert lib.lcd_call_bam_regions(None, None, None, None, 0, None, None, 30, None, None, None, None, None, None, C.byref(ro), C.byref(out)) == -4 and st.n_records == 0
+    wo = _lib.LcdWriterOpt(refine_stats=C.pointer(st))
+    st.n_records = 7
+    assert lib.lcd_write_phased(None, 0, None, None, C.byref(wo)) == -4 and st.n_records == 0
+    st.n_records = 7
+    assert not lib.lcd_bam_writer_open(None, None, C.byref(wo)) and b"NULL" in lib.lcd_last_error() and st.n_records == 0
     assert lib.lcd_chunk_set_refine(None, 1) == -4 and not lib.lcd_chunk_refine_log(None)
     assert lib.lcd_chunks_call_refine(0, None, None, None, None, None, None) == -4
 

@@ -7,7 +7,7 @@ import re
 from conftest import ROOT
 
 NEW = ["lcd_sam_names_create", "lcd_sam_names_free", "lcd_tagged_to_sam", "lcd_records_to_sam", "lcd_sam_text_size", "lcd_sam_text_dev_ptr", "lcd_sam_text_to_host",
-       "lcd_sam_text_free", "lcd_bam_writer_open_sam", "lcd_bam_writer_set_sam_stats", "lcd_write_phased_sam", "lcd_call_files_aln"]
+       "lcd_sam_text_free", "lcd_bam_writer_open", "lcd_write_phased", "lcd_call_files"]
 
 
 def test_new_symbols_declared_listed_and_exported():
@@ -44,19 +44,24 @@ def test_arguments_are_checked_before_any_device_work():
     assert not lib.lcd_records_to_sam(rec, 40, None, C.byref(st)) and b"NULL" in err() and st.n_records == 0
     assert lib.lcd_sam_text_size(None) == 0 and lib.lcd_sam_text_dev_ptr(None) == 0 and lib.lcd_sam_text_to_host(None, 0, 0, None) == -41
     lib.lcd_sam_text_free(None); lib.lcd_sam_names_free(None)
-    assert not lib.lcd_bam_writer_open_sam(None, None) and b"NULL" in err()
+    sam = _lib.LcdWriterOpt(format=_lib.LCD_ALN_SAM)
+    assert not lib.lcd_bam_writer_open(None, None, C.byref(sam)) and b"NULL" in err()
     bo = _lib.LcdBamOut(); bo.path = None
-    assert not lib.lcd_bam_writer_open_sam(b"x.bam", C.byref(bo)) and b"NULL" in err()
-    assert lib.lcd_bam_writer_set_sam_stats(None, None) == -4
-    assert lib.lcd_write_phased_sam(None, 0, None, None, None, None) == -4
-    assert lib.lcd_write_phased_sam(b"x.bam", 0, None, C.byref(bo), None, None) == -4 and b"NULL" in err()
+    assert not lib.lcd_bam_writer_open(b"x.bam", C.byref(bo), C.byref(sam)) and b"NULL" in err()
+    sam_st = _lib.LcdWriterOpt(format=_lib.LCD_ALN_SAM, sam_stats=C.pointer(st))
+    st.n_records = 7
+    assert not lib.lcd_bam_writer_open(None, None, C.byref(sam_st)) and st.n_records == 0
+    assert lib.lcd_write_phased(None, 0, None, None, C.byref(sam)) == -4
+    assert lib.lcd_write_phased(b"x.bam", 0, None, C.byref(bo), C.byref(sam)) == -4 and b"NULL" in err()
     bo.path = b"o.sam"
-    assert lib.lcd_write_phased_sam(b"x.bam", -1, None, C.byref(bo), None, None) == -4
-    assert lib.lcd_write_phased_sam(b"x.bam", 1, None, C.byref(bo), None, C.byref(st)) == -4
+    assert lib.lcd_write_phased(b"x.bam", -1, None, C.byref(bo), C.byref(sam)) == -4
+    assert lib.lcd_write_phased(b"x.bam", 1, None, C.byref(bo), C.byref(sam_st)) == -4
+    assert not os.path.exists("o.sam")
 
 
 def test_the_file_driver_s_refusals(tmp_path):
-    """format outside the enum and a NULL option: -4; refine with fields: -2; SAM with write_out_bai: -4; SAM and VCF both on stdout: -4 -- all before a file is created"""
+    """format outside the enum: -4; refine with fields: -2; SAM with write_out_bai: -4; SAM and VCF both on stdout: -4 -- all before a file is created; a NULL
+    option is the feature off"""
     from longcalld_amd import _lib, align
     lib = _lib.load_library()
     cfg = align.call_cfg()
@@ -65,9 +70,13 @@ def test_the_file_driver_s_refusals(tmp_path):
     bo = _lib.LcdBamOut(); bo.path = out.encode()
     job.bam_path, job.fasta_path, job.vcf_path, job.bam_out = b"missing_in.bam", b"missing_ref.fa", str(tmp_path / "o.vcf").encode(), C.pointer(bo)
     st, sst, rst = _lib.LcdFileStats(), _lib.LcdSamStats(), _lib.LcdRefineStats()
-    call = lambda ao, idx=None, vf=None: lib.lcd_call_files_aln(None, C.byref(job), C.byref(cfg), C.byref(idx) if idx is not None else None, C.byref(vf) if vf is not None else None,
-                                                                C.byref(ao) if ao is not None else None, C.byref(st), None, None, None, C.byref(rst), C.byref(sst))
-    assert call(None) == -4 and b"NULL" in lib.lcd_last_error()
+    ptr = lambda x: C.pointer(x) if x is not None else None
+    ro_out = []
+
+    def call(ao, idx=None, vf=None):
+        ro_out[:] = [_lib.LcdRunOpt(idx=ptr(idx), fields=ptr(vf), aln=ptr(ao)), _lib.LcdRunOut(refine_stats=C.pointer(rst), sam_stats=C.pointer(sst))]
+        return lib.lcd_call_files(None, C.byref(job), C.byref(cfg), C.byref(ro_out[0]), C.byref(st), C.byref(ro_out[1]))
+    assert call(None) == -30 and b"missing_in.bam" in lib.lcd_last_error()      # no lcd_aln_opt_t: a BAM output without refinement, refused for its input only
     assert call(_lib.LcdAlnOpt(2, 0)) == -4 and call(_lib.LcdAlnOpt(-1, 0)) == -4
     vf = _lib.LcdVcfFields(); vf.rnames_mode = _lib.LCD_RNAMES_ALL
     assert call(_lib.LcdAlnOpt(_lib.LCD_ALN_SAM, 1), vf=vf) == -2 and call(_lib.LcdAlnOpt(_lib.LCD_ALN_BAM, 1), vf=vf) == -2

@@ -18,7 +18,7 @@ import vcf_fields_common as vf
 from conftest import ROOT
 
 NEW = ["lcd_te_lib_from_fasta", "lcd_te_lib_from_fasta_free", "lcd_format_vcf_fields", "lcd_alt_read_names", "lcd_vcf_fields_out_free", "lcd_chunks_call_fields",
-       "lcd_call_bam_regions_fields", "lcd_call_file_fields", "lcd_call_files_fields"]
+       "lcd_call_bam_regions", "lcd_call_files"]
 
 
 # ---------------- the TE file reader ----------------
@@ -434,7 +434,8 @@ def _abi_exe(tmp_path):
 def test_struct_mirrors_have_the_compilers_layout(tmp_path):
     from longcalld_amd import _lib
     want = dict(l.split() for l in subprocess.check_output([_abi_exe(tmp_path)], text=True).splitlines())
-    for name, cls in {"lcd_vcf_fields_t": _lib.LcdVcfFields, "lcd_vcf_fields_out_t": _lib.LcdVcfFieldsOut}.items():
+    for name, cls in {"lcd_vcf_fields_t": _lib.LcdVcfFields, "lcd_vcf_fields_out_t": _lib.LcdVcfFieldsOut, "lcd_run_opt_t": _lib.LcdRunOpt, "lcd_run_out_t": _lib.LcdRunOut,
+                      "lcd_writer_opt_t": _lib.LcdWriterOpt}.items():
         assert C.sizeof(cls) == int(want[name]), name
         fields = [k.split(".")[1] for k in want if k.startswith(name + ".")]
         assert fields == [f[0] for f in cls._fields_], name
@@ -473,5 +474,9 @@ def test_driver_argument_errors(lcd, tmp_path):
         assert rc == (-30 if f.te_fasta_path else -4) and not text and fo.n_te_seqs == 0
     assert "none.fa" in lib.lcd_last_error().decode()
     lib.lcd_vcf_fields_out_free(C.byref(fo)); lib.lcd_vcf_fields_out_free(None)
-    assert lib.lcd_call_files_fields(None, None, None, None, None, None, None, None, None) == -4
-    assert lib.lcd_call_file_fields(None, None, None, None, None, None, None) == -4
+    vf = _lib.LcdVcfFields(); fo2 = _lib.LcdVcfFieldsOut(); fo2.n_te_seqs = 7
+    ro, out = _lib.LcdRunOpt(fields=C.pointer(vf)), _lib.LcdRunOut(fields_out=C.pointer(fo2))
+    inp = _lib.LcdInputs()
+    assert lib.lcd_call_files(C.byref(inp), None, None, C.byref(ro), None, C.byref(out)) == -4 and fo2.n_te_seqs == 0
+    fo2.n_te_seqs = 7
+    assert lib.lcd_call_files(None, None, None, C.byref(ro), None, C.byref(out)) == -4 and fo2.n_te_seqs == 0

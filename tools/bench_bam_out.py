@@ -1,6 +1,6 @@
 """Measurement of the phased alignment output's GPU side: the deflate kernel (lcd_bgzf_deflate_dev) on the payload classes of tests/test_gpu_deflate.py and on a
 HiFi-shape BAM stream, against Python zlib level 6 (htslib's default) on 16 host threads over the same blocks; and the stage times of the whole writer
-(lcd_call_bam_regions_out's lcd_bam_out_t) on the tests' seeded two-region BAM.  Prints one JSON line; no threshold is set on any number.
+(lcd_call_bam_regions' lcd_bam_out_t) on the tests' seeded two-region BAM.  Prints one JSON line; no threshold is set on any number.
 usage: python tools/bench_bam_out.py [MB per payload class, default 32] [repeats, default 3]"""
 import hashlib
 import json
@@ -64,7 +64,7 @@ def _members(d):
 
 
 def writer_stages():
-    """lcd_bam_out_t of lcd_call_bam_regions_out on the tests' two-region seed (small: the stage split, not a throughput)"""
+    """lcd_bam_out_t of lcd_call_bam_regions on the tests' two-region seed (small: the stage split, not a throughput)"""
     import call_chunks_common as kc
     import clean_vars_common as cc
     from test_gpu_clean_vars import write_chunk_bam

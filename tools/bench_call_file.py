@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""bench_call_file.py [n_contigs] [contig_kb] [repeats] -- the whole-file run (lcd_call_file) on a seeded multi-contig HiFi-shape file: wall time and the busy time of
+"""bench_call_file.py [n_contigs] [contig_kb] [repeats] -- the whole-file run (lcd_call_files) on a seeded multi-contig HiFi-shape file: wall time and the busy time of
 the three stages for overlap 0 / 1, loader_threads 1 / 2 / 4 and a few window sizes, and the same file through lcd_call_bam_regions per contig (the two-pass
 wrapper: what a caller had before).  Prints one JSON line; the reading is in profiles/NOTES_call_file.md.  The file is synthetic (tests' generator: 12x depth,
 2 - 6 kb reads, chunk_len 6000), so the chunks are a hundredth of a real 500 kb chunk: the figures compare schedules, they are not throughput."""

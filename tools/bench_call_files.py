@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """bench_call_files.py [n_contigs] [contig_kb] [repeats] [--root DIR] -- one sample from several BAMs (lcd_call_files) on the seeded file of tools/bench_call_file.py:
-the one BAM holding all reads through lcd_call_file, the same file through lcd_call_files with n = 1, and the reads dealt out to 2 and to 4 files (read i of a contig
+the one BAM holding all reads through lcd_call_files without an input list, the same file through lcd_call_files with n = 1, and the reads dealt out to 2 and to 4 files (read i of a contig
 goes to file i % n).  Per run the best of `repeats` wall times with its ms_load / ms_call / ms_write, n_region_loads and peak_device_bytes.  Prints one JSON line;
 the reading is in profiles/NOTES_call_files.md.
 --root DIR measures the library and the Python mirror of another checkout of this project (one that has been built), e.g. the parent commit: a tree without
-lcd_call_files records the lcd_call_file run only.  The data is written by this tree's test helpers in either case, so both trees read the same bytes.
+lcd_call_files records the one-file run only.  The data is written by this tree's test helpers in either case, so both trees read the same bytes.
 The file is synthetic (12x depth, 2 - 6 kb reads, chunk_len 6000): the chunks are a hundredth of a real 500 kb chunk, which was NOT measured."""
 import json
 import os

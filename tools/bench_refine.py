@@ -62,7 +62,7 @@ def one(kind, copies, reps, tmp):
 
 
 def whole_file(n_contigs=6, contig_kb=24, repeats=3):
-    """tools/bench_call_file.py's seeded file (6 contigs of 24 kb, 12x, chunk_len 6000), as EQX and as plain-'M' records, through lcd_call_file with and without
+    """tools/bench_call_file.py's seeded file (6 contigs of 24 kb, 12x, chunk_len 6000), as EQX and as plain-'M' records, through lcd_call_files with and without
     refine: wall time, the writer's ms_tag (without refine it is lcd_chunk_tag_records_sel, the writer as it was), the logs' bytes down, the digars' bytes up"""
     import call_file_common as fc
     import clean_vars_common as cc

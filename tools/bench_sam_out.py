@@ -1,5 +1,5 @@
 """Measurement of the SAM text output's GPU side on ONE chunk of HiFi shape: a synthetic sorted BAM (reads of ~15 kb with an EQX CIGAR, RG / NM / np / rq fields and,
-for every fourth read, a kinetics array as long as the read) through chunk creation, a fixed haplotype state and the writer -- lcd_write_phased_sam's ms_measure,
+for every fourth read, a kinetics array as long as the read) through chunk creation, a fixed haplotype state and the writer -- lcd_write_phased's ms_measure,
 ms_emit, text GB/s and the download + write, with the BAM path's ms_tag + ms_deflate + download for the same chunk beside them.  Prints one JSON line; no
 threshold is set on any number.
 usage: python tools/bench_sam_out.py [reads, default 2000] [repeats, default 3]"""

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """bench_vcf_fields.py [--root DIR] [n_contigs] [contig_kb] [repeats] -- what the supporting read names (--out-var-rnames / --out-sv-rnames) cost the whole-file run:
-tools/bench_call_file.py's seeded file (12x depth, 2 - 6 kb reads, chunk_len 6000) through lcd_call_file with no options, rnames="sv" and rnames="all", each as plain
+tools/bench_call_file.py's seeded file (12x depth, 2 - 6 kb reads, chunk_len 6000) through lcd_call_files with no options, rnames="sv" and rnames="all", each as plain
 VCF and as -O z, with a TE library of three seeded sequences where the options are on.  Per run ms_write, ms_wall (the best of `repeats` by wall time) and the VCF's
 bytes.  --root DIR imports the package of another checkout (a build of the parent commit): only the no-options runs are made there.  Prints one JSON line; the
 reading is in profiles/NOTES_vcf_fields.md.  The chunks are a hundredth of a real 500 kb chunk: the figures compare runs of this file, they are not throughput."""
