@@ -1292,11 +1292,91 @@ void lcd_sam_text_free(lcd_sam_text_t *h);
 enum { LCD_ALN_BAM = 0, LCD_ALN_SAM = 1 };
 typedef struct lcd_aln_opt_t { int format, refine; } lcd_aln_opt_t;
 
+/* ---- VCF indexes: the .tbi / .csi of a BGZF-compressed VCF, built on the device (the tabix and CSI specifications; any reader that follows them gets correct
+ * answers).  The input is VCF TEXT in HBM -- what the VCF writer is about to compress, or a slab inflated from an existing .vcf.gz -- with the table of the BGZF
+ * members it lies in (lcd_bai_member_t) and end_coff, exactly as lcd_bai_builder_add_stream takes them.  vcf_index_kernel.hip finds the line starts (ballots over
+ * bytes, per-workgroup counts, exclusive scan, compaction), parses every line with one wavefront (lanes striding 64 bytes) and then does for a line what
+ * lcd_bai_entry_kernel does for a record.
+ *   1 lines        a line ends at '\n'.  A line whose first byte is '#' is a meta line: counted, not indexed.  Every other line is a data line; data lines are numbered
+ *                  from 0 over the whole file, and that number is in every message about a line.
+ *   2 columns      a data line has at least 8 tab-separated columns (column 8 may end at the line end), a non-empty CHROM and a POS of decimal digits only, else
+ *                  LCD_ERR_VCF_LINE.  PROJECT RULE: an empty line is a data line with too few columns.
+ *   3 interval     beg = POS - 1 (POS 0: 0), end = beg + length of REF (PROJECT RULE: an empty REF spans one base).  END: if INFO begins with "END=", that value; else the
+ *                  value behind the first ";END=" inside INFO (so CIEND= / SVEND= never match); a value that begins with '.' is ignored, and so is one that does not
+ *                  begin with a decimal digit (PROJECT RULE: decimal digits only, where htslib's strtoll would also take a sign or a 0x prefix); if END > beg then
+ *                  end = END, else it is ignored.  Only the first of the two keys decides: "END=.;...;END=5000" has no END.
+ *   4 contigs      tids are given in order of first appearance; the lines of a contig are consecutive: a name that reappears after another contig is
+ *                  LCD_ERR_VIDX_ORDER.  Inside a contig beg is non-decreasing, else LCD_ERR_VIDX_ORDER.  Of several refused lines the one with the smallest number is reported.
+ *   5 offsets      rule 5 of the .bai section; a line's vbeg is its first byte's offset, its vend the offset of the byte behind its '\n' (the next line's vbeg).  A last
+ *                  line without '\n' ends at the end of the file's last payload.
+ *   6 bins         min_shift 14; TBI: depth 5, reg2bin of SAM specification 5.3, end > 2^29 is LCD_ERR_VIDX_CSI with a message that asks for CSI.  CSI: depth = max(5,
+ *                  the smallest d with 2^(14 + 3d) >= the longest length of the header's contig lines); a contig line is a meta line that begins with "##contig=<" and has
+ *                  "length=" directly behind a '<' or a ','.  With no such line the depth comes from the largest end seen.  An end behind 2^(14 + 3 depth) of a depth taken
+ *                  from the header, or behind 2^38 (depth 8, the deepest this library writes), is LCD_ERR_VIDX_CSI.
+ *   7 chunks       rules 6-7 of the .bai section: runs of equal (tid, bin), the merge rule, ascending bins, the pseudo-bin -- 37450 for TBI,
+ *                  ((1 << (3 depth + 3)) - 1) / 7 + 1 for CSI -- last with (vbeg of the contig's first line, vend of its last) and (number of lines, 0).
+ *   8 TBI          "TBI\1", n_ref, format 2, col_seq 1, col_beg 2, col_end 0, meta '#', skip 0, l_nm, the NUL-terminated names in tid order, per contig the bins and the
+ *                  linear index of .bai rule 8, the trailing uint64 n_no_coor = 0.
+ *   9 CSI          "CSI\1", min_shift 14, depth, l_aux, aux = the TBI header from format through the names, n_ref, per contig the bins, each with loffset in front of
+ *                  n_chunk (the pseudo-bin's is 0), no linear index, the trailing n_no_coor = 0.  PROJECT RULE: a bin's loffset is the smallest vbeg of the contig's
+ *                  lines that overlap the bin's interval; as beg never decreases inside a contig that is the value of the first set 16 kb window inside the bin's span.
+ *                  Why a reader may use it: htslib's lookup for a region starts at the leaf bin of the region's first base and, while the bin it looks at is
+ *                  absent from the index, goes to the bin on its left among its siblings or else to its parent; it takes the loffset of the first bin it finds
+ *                  (0 if none) and skips every chunk that ends at or in front of it.  The bin B it finds is an ancestor of that leaf (or the leaf) or lies
+ *                  wholly in front of it, so B ends behind the region's first base or in front of it -- never does B begin behind it.  Let W be a line that
+ *                  overlaps the region: W ends behind the region's first base.  If W begins in front of B's end, W overlaps B's interval (it ends behind B's
+ *                  begin), so loffset(B) <= vbeg(W) by the rule.  If W begins at or behind B's end: B is present, so a line lies inside B; that line begins in
+ *                  front of W, file order is position order inside a contig, and it overlaps B: loffset(B) <= its vbeg <= vbeg(W).  The chunk that holds W ends
+ *                  behind vbeg(W) and is kept.
+ *  10 slabs        the bytes depend on nothing but the file: not on the slab size, not on where a slab or an append border falls.
+ * lcd_tbx_from_records: the finisher on its own, pure host code -- rules 4 and 6-9 on a table of (tid, beg, end, vbeg, vend) with the names in tid order (tids never
+ * decrease) and the header's longest contig length (0: none).  *bytes = the UNCOMPRESSED index, malloc()'d.  0, LCD_ERR_VIDX_ORDER, LCD_ERR_VIDX_CSI or -4.
+ * lcd_vcf_index_builder_*: the accumulating builder, as lcd_bai_builder_*.  add_stream: the stream may begin inside a line; first_line_offset is where its first line
+ * starts, *next_line_offset the offset of the first line that is not complete inside the stream (n_bytes when all were).  The stream must be readable 64 bytes behind
+ * n_bytes.  Only the names of contig-run heads come to the host.  finish serialises, compresses the bytes with lcd_bgzf_deflate_dev(add_eof = 1) -- a .tbi / .csi is
+ * itself BGZF -- and writes them to out_path (NULL: nothing is written); _bytes gives the uncompressed bytes.  After an error the builder only accepts destroy.
+ * lcd_vcf_index_build: the whole-file driver, as lcd_bai_build (opt->slab_members members per slab, 0 = 4096; the next slab starts at the member that holds the first
+ * unfinished line; a line larger than a slab doubles the slab for that step).  out_path NULL: <path>.tbi or <path>.csi by opt->format; opt NULL: TBI.  A last line
+ * without '\n' is accepted.  A file that is not BGZF is refused with -33 and a message that says whether it is plain gzip or plain text.  On an error nothing is left at
+ * out_path and no device buffer stays in the ledger.
+ * lcd_vcf_writer_open_idx: lcd_vcf_writer_open with an index (vi NULL: without).  It needs bgzf = 1 and a real path (-4 otherwise).  Every append uploads its text
+ * once, compresses it with lcd_bgzf_deflate_dev_ptr and hands the same buffer to the builder with the member table of lcd_deflated_block_info and the running file
+ * offset; close writes the index to vi->index_path (NULL: <path>.tbi / .csi) after the EOF member, abort leaves none.  LCD_ERR_VIDX_ORDER / LCD_ERR_VIDX_CSI: the VCF
+ * is still completed, no index is left behind, vi->stats->skipped / skip_reason say so; any other failure of the index fails the append.  *vi->stats (may be NULL)
+ * must outlive the writer; it is zeroed at open.  The .vcf.gz bytes are those of lcd_vcf_writer_open. */
+#define LCD_ERR_VIDX_ORDER (-55)
+#define LCD_ERR_VIDX_CSI (-56)
+#define LCD_ERR_VCF_LINE (-57)
+enum { LCD_VIDX_TBI = 0, LCD_VIDX_CSI = 1 };
+typedef struct lcd_vcf_index_stats_t {
+    int64_t n_lines, n_data_lines, n_meta_lines, n_contigs, n_chunks, n_slabs, n_members, bytes_in, bytes_inflated, bytes_index, bytes_file;
+    int depth, wrote, skipped, pad;        /* skipped: the LCD_ERR_* code that kept the writer's index from being written, or 0 */
+    char skip_reason[256];
+    double ms_read, ms_inflate, ms_lines, ms_entry, ms_finish, ms_wall;
+} lcd_vcf_index_stats_t;
+typedef struct lcd_vcf_index_opt_t { int format; const char *index_path; int slab_members, verify_crc; lcd_vcf_index_stats_t *stats; } lcd_vcf_index_opt_t;
+int lcd_tbx_from_records(int format, int n_ref, const char *const *names, int64_t max_contig_len, int64_t n_rec, const int *tid, const int64_t *beg, const int64_t *end,
+                         const uint64_t *vbeg, const uint64_t *vend, uint8_t **bytes, size_t *n);
+typedef struct lcd_vcf_index_builder_s lcd_vcf_index_builder_t;
+lcd_vcf_index_builder_t *lcd_vcf_index_builder_create(int format);
+int lcd_vcf_index_builder_add_stream(lcd_vcf_index_builder_t *b, uint64_t dev_ptr, size_t n_bytes, size_t first_line_offset, size_t n_members, const lcd_bai_member_t *members,
+                                     uint64_t end_coff, size_t *next_line_offset);
+int lcd_vcf_index_builder_finish(lcd_vcf_index_builder_t *b, const char *out_path);
+int lcd_vcf_index_builder_bytes(const lcd_vcf_index_builder_t *b, const uint8_t **bytes, size_t *n);   /* after finish; borrowed */
+void lcd_vcf_index_builder_destroy(lcd_vcf_index_builder_t *b);
+int lcd_vcf_index_build(const char *vcf_gz_path, const char *out_path, const lcd_vcf_index_opt_t *opt /* may be NULL */, lcd_vcf_index_stats_t *stats /* may be NULL */);
+lcd_vcf_writer_t *lcd_vcf_writer_open_idx(const char *path, int bgzf, const char *header_text, const lcd_vcf_index_opt_t *vi);
+
 /* ---- the four drivers and their options ----
  * Every optional feature of the sections above is a member of one of three structs; a NULL struct or a NULL / zero member means the feature is off, and a run
  * without options writes the bytes it always wrote.
  * lcd_run_opt_t (in): idx = the indexes (lcd_index_opt_t), fields = the VCF content (lcd_vcf_fields_t), aln = the alignment output's format and refinement
  * (lcd_aln_opt_t).  aln->format outside LCD_ALN_BAM / LCD_ALN_SAM: -4; aln->refine together with fields: -2.
+ * lcd_run_ext_t (lcd_call_files_ext): the options that came after lcd_run_opt_t / lcd_run_out_t were laid out -- those two structs keep their size, so a caller
+ * compiled against them goes on working; a NULL struct or member is off.  vcf_idx = the index of the compressed VCF (lcd_vcf_index_opt_t; its `stats` member is not
+ * read: vcf_idx_stats, zeroed on entry, is where the run reports).  It needs job->vcf_bgzf and a vcf_path that names a file (-4, before any output is created); a VCF
+ * that cannot be indexed (LCD_ERR_VIDX_ORDER, LCD_ERR_VIDX_CSI) is completed without an index and vcf_idx_stats->skipped / skip_reason say so.
+ * lcd_call_files_ext(in, job, cfg, opt, stats, out, ext): lcd_call_files with those options; lcd_call_files is ext == NULL.
  * lcd_run_out_t (out): what the run reports beside *stats; NULL: not reported.  Every non-NULL member is zeroed on entry, on refusal paths too
  * (n_reads_per_file: in->n entries, 1 without `in`, zeroed once the inputs are accepted).  refine_stats / sam_stats are the writer's sums and stay zero when
  * the run does not refine / does not write SAM.
@@ -1306,7 +1386,8 @@ typedef struct lcd_aln_opt_t { int format, refine; } lcd_aln_opt_t;
  * lcd_call_files(in, job, cfg, opt, stats, out): the whole-file run.  in == NULL: the one file job->bam_path / bai_path; neither `in` nor job->bam_path: -4.
  * Refusals come before an index is built or an output file is created.
  * lcd_call_bam_regions(..., bam_out, opt, out): the regions of one contig; bam_out NULL: no alignment output.  opt->fields, opt->aln->refine (with bam_out) and
- * out->fields_out / refine_stats as above.  This driver writes BAM only and builds no index: aln->format LCD_ALN_SAM is -2 and a non-NULL opt->idx is -4;
+ * out->fields_out / refine_stats as above.  This driver writes BAM only and builds no index: aln->format LCD_ALN_SAM is -2 and a non-NULL opt->idx is -4; it returns
+ * its VCF body as text and writes no file, so there is no VCF index here (it takes no lcd_run_ext_t);
  * out->n_reads_per_file is not written.
  * lcd_bam_writer_open(in_bam_path, out, wopt): the appendable writer (lcd_bam_writer_append / _close / _abort above).  The index path is removed at open and by abort.
  * lcd_write_phased(in_bam_path, n_chunks, chunks, out, wopt): open + one append + close; the chunks are checked before the output is touched. */
@@ -1314,10 +1395,13 @@ typedef struct lcd_run_opt_t { const lcd_index_opt_t *idx; const lcd_vcf_fields_
 typedef struct lcd_run_out_t {
     lcd_index_stats_t *idx_stats; int64_t *n_reads_per_file; lcd_vcf_fields_out_t *fields_out; lcd_refine_stats_t *refine_stats; lcd_sam_stats_t *sam_stats;
 } lcd_run_out_t;
+typedef struct lcd_run_ext_t { const lcd_vcf_index_opt_t *vcf_idx; lcd_vcf_index_stats_t *vcf_idx_stats; } lcd_run_ext_t;
 typedef struct lcd_writer_opt_t {
     int format, sort_output, write_index; const char *index_path; lcd_index_stats_t *idx_stats; lcd_refine_stats_t *refine_stats; lcd_sam_stats_t *sam_stats;
 } lcd_writer_opt_t;
 int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out);
+int lcd_call_files_ext(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
+                       const lcd_run_ext_t *ext);
 int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
                          const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
                          lcd_bam_out_t *bam_out, const lcd_run_opt_t *opt, const lcd_run_out_t *out);

@@ -273,6 +273,18 @@ class LcdAlnOpt(C.Structure):
     _fields_ = [("format", C.c_int), ("refine", C.c_int)]
 
 
+class LcdVcfIndexStats(C.Structure):
+    """lcd_vcf_index_stats_t: the counters and per-stage times of lcd_vcf_index_build / of the indexing VCF writer"""
+    _fields_ = [(n, C.c_int64) for n in ("n_lines", "n_data_lines", "n_meta_lines", "n_contigs", "n_chunks", "n_slabs", "n_members", "bytes_in", "bytes_inflated", "bytes_index",
+                                         "bytes_file")] + [(n, C.c_int) for n in ("depth", "wrote", "skipped", "pad")] + [("skip_reason", C.c_char * 256)] + [
+                    (n, C.c_double) for n in ("ms_read", "ms_inflate", "ms_lines", "ms_entry", "ms_finish", "ms_wall")]
+
+
+class LcdVcfIndexOpt(C.Structure):
+    """lcd_vcf_index_opt_t: the index of a BGZF-compressed VCF (lcd_vcf_index_build, lcd_vcf_writer_open_idx, lcd_run_ext_t.vcf_idx)"""
+    _fields_ = [("format", C.c_int), ("index_path", C.c_char_p), ("slab_members", C.c_int), ("verify_crc", C.c_int), ("stats", C.POINTER(LcdVcfIndexStats))]
+
+
 class LcdRunOpt(C.Structure):
     """lcd_run_opt_t: the optional features of lcd_call_files / lcd_call_bam_regions; a NULL member is off"""
     _fields_ = [("idx", C.POINTER(LcdIndexOpt)), ("fields", C.POINTER(LcdVcfFields)), ("aln", C.POINTER(LcdAlnOpt))]
@@ -282,6 +294,11 @@ class LcdRunOut(C.Structure):
     """lcd_run_out_t: what a driver reports beside its statistics; a NULL member is not reported"""
     _fields_ = [("idx_stats", C.POINTER(LcdIndexStats)), ("n_reads_per_file", C.POINTER(C.c_int64)), ("fields_out", C.POINTER(LcdVcfFieldsOut)),
                 ("refine_stats", C.POINTER(LcdRefineStats)), ("sam_stats", C.POINTER(LcdSamStats))]
+
+
+class LcdRunExt(C.Structure):
+    """lcd_run_ext_t: the options of lcd_call_files_ext that came after lcd_run_opt_t / lcd_run_out_t were laid out; a NULL member is off"""
+    _fields_ = [("vcf_idx", C.POINTER(LcdVcfIndexOpt)), ("vcf_idx_stats", C.POINTER(LcdVcfIndexStats))]
 
 
 class LcdWriterOpt(C.Structure):
@@ -298,6 +315,8 @@ class LcdRefineEntry(C.Structure):
 
 LCD_RNAMES_NONE, LCD_RNAMES_SV, LCD_RNAMES_ALL = 0, 1, 2
 LCD_ERR_BAI_ORDER, LCD_ERR_BAI_CSI, LCD_ERR_FAI_FORMAT, LCD_ERR_BAI_CONTIG, LCD_ERR_INPUT_HEADERS = -50, -51, -52, -53, -54
+LCD_ERR_VIDX_ORDER, LCD_ERR_VIDX_CSI, LCD_ERR_VCF_LINE = -55, -56, -57
+LCD_VIDX_TBI, LCD_VIDX_CSI = 0, 1
 LCD_MAX_INPUTS = 64
 LCD_ALN_BAM, LCD_ALN_SAM = 0, 1
 LCD_CTG_AUTOSOME_XY, LCD_CTG_AUTOSOME, LCD_CTG_ALL = 0, 1, 2
@@ -325,6 +344,8 @@ EXPORTS = [
     "lcd_vcf_writer_open", "lcd_vcf_writer_append", "lcd_vcf_writer_close", "lcd_vcf_writer_abort", "lcd_file_job_default", "lcd_file_stats_free",
     "lcd_bai_from_records", "lcd_bai_builder_create", "lcd_bai_builder_add_stream", "lcd_bai_builder_finish", "lcd_bai_builder_bytes", "lcd_bai_builder_destroy", "lcd_bai_build",
     "lcd_fai_build",
+    "lcd_tbx_from_records", "lcd_vcf_index_builder_create", "lcd_vcf_index_builder_add_stream", "lcd_vcf_index_builder_finish", "lcd_vcf_index_builder_bytes",
+    "lcd_vcf_index_builder_destroy", "lcd_vcf_index_build", "lcd_vcf_writer_open_idx", "lcd_call_files_ext",
     "lcd_chunk_open_from_bams", "lcd_chunk_n_files", "lcd_chunk_read_files", "lcd_merged_record_plan", "lcd_chunk_tag_records_sel", "lcd_call_files",
     "lcd_te_lib_from_fasta", "lcd_te_lib_from_fasta_free", "lcd_format_vcf_fields", "lcd_alt_read_names", "lcd_vcf_fields_out_free", "lcd_chunks_call_fields",
     "lcd_chunk_refine_records", "lcd_refine_log_create", "lcd_refine_log_free", "lcd_refine_log_n_entries", "lcd_refine_log_row_bytes", "lcd_refine_log_append",
@@ -501,6 +522,19 @@ def load_library():
     lib.lcd_bai_builder_destroy.argtypes = [C.c_void_p]
     lib.lcd_bai_builder_destroy.restype = None
     lib.lcd_bai_build.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(LcdBaiOpt), C.POINTER(LcdBaiStats)]
+    lib.lcd_tbx_from_records.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_int64, C.c_int64, i32p, i64p, i64p, u64p_, u64p_, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    lib.lcd_vcf_index_builder_create.restype = C.c_void_p
+    lib.lcd_vcf_index_builder_create.argtypes = [C.c_int]
+    lib.lcd_vcf_index_builder_add_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(LcdBaiMember), C.c_uint64, C.POINTER(C.c_size_t)]
+    lib.lcd_vcf_index_builder_finish.argtypes = [C.c_void_p, C.c_char_p]
+    lib.lcd_vcf_index_builder_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    lib.lcd_vcf_index_builder_destroy.argtypes = [C.c_void_p]
+    lib.lcd_vcf_index_builder_destroy.restype = None
+    lib.lcd_vcf_index_build.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(LcdVcfIndexOpt), C.POINTER(LcdVcfIndexStats)]
+    lib.lcd_call_files_ext.argtypes = [C.POINTER(LcdInputs), C.POINTER(LcdFileJob), C.POINTER(LcdCfg), C.POINTER(LcdRunOpt), C.POINTER(LcdFileStats), C.POINTER(LcdRunOut),
+                                       C.POINTER(LcdRunExt)]
+    lib.lcd_vcf_writer_open_idx.restype = C.c_void_p
+    lib.lcd_vcf_writer_open_idx.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.POINTER(LcdVcfIndexOpt)]
     lib.lcd_fai_build.argtypes = [C.c_char_p, C.c_char_p]
     lib.lcd_file_stats_free.restype = None
     lib.lcd_chunk_open_from_bams.restype = C.c_void_p

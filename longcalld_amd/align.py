@@ -1919,18 +1919,41 @@ def stitch_chunks_carry(phases, update_reads=1, carry_in=None, carry_out=None, n
                                        C.byref(carry_out) if carry_out is not None else None)
 
 
-def vcf_write(path, texts, bgzf=0, header_text=None):
-    """lcd_vcf_writer_open / _append per text / _close"""
+def _vcf_index_opt(fmt, index_path=None, slab_members=0, with_stats=True):
+    """"tbi" / "csi" -> (lcd_vcf_index_opt_t, lcd_vcf_index_stats_t)"""
+    from ._lib import LCD_VIDX_CSI, LCD_VIDX_TBI, LcdVcfIndexOpt, LcdVcfIndexStats
+    if fmt not in ("tbi", "csi"):
+        raise ValueError("the VCF index format must be 'tbi' or 'csi'")
+    st = LcdVcfIndexStats()
+    vo = LcdVcfIndexOpt(LCD_VIDX_CSI if fmt == "csi" else LCD_VIDX_TBI, _enc(index_path) if index_path is not None else None, int(slab_members), 0,
+                        C.pointer(st) if with_stats else None)
+    return vo, st
+
+
+def _vcf_index_stats(st):
+    from ._lib import LcdVcfIndexStats
+    return {k: (getattr(st, k).decode() if k == "skip_reason" else getattr(st, k)) for k, _t in LcdVcfIndexStats._fields_ if k != "pad"}
+
+
+def vcf_write(path, texts, bgzf=0, header_text=None, index=None, index_path=None, abort=False):
+    """lcd_vcf_writer_open / _append per text / _close.  index "tbi" / "csi": lcd_vcf_writer_open_idx -- the index is written beside the file (or to index_path) at
+    close; -> the dict of lcd_vcf_index_stats_t then, else None.  abort: lcd_vcf_writer_abort instead of close"""
     lib = load_library()
-    w = lib.lcd_vcf_writer_open(_enc(path) if path is not None else None, int(bgzf), _enc(header_text) if header_text is not None else None)
+    vo, vst = _vcf_index_opt(index, index_path) if index is not None else (None, None)
+    w = lib.lcd_vcf_writer_open_idx(_enc(path) if path is not None else None, int(bgzf), _enc(header_text) if header_text is not None else None,
+                                    C.byref(vo) if vo is not None else None)
     if not w:
         raise LcdError("lcd_vcf_writer_open failed: " + lib.lcd_last_error().decode())
     for t in texts:
         rc = lib.lcd_vcf_writer_append(w, _enc(t))
-        if rc < 0:
+        if rc:
             lib.lcd_vcf_writer_abort(w)
             check(rc, lib)
-    check(lib.lcd_vcf_writer_close(w), lib)
+    if abort:
+        lib.lcd_vcf_writer_abort(w)
+    else:
+        check(lib.lcd_vcf_writer_close(w), lib)
+    return _vcf_index_stats(vst) if vst is not None else None
 
 
 def chunk_open_from_bams(bam_paths, bai_paths, chrom, reg_beg, reg_end, min_mapq=30, is_ont=0, verify_crc=1):
@@ -1962,7 +1985,7 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam"):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None):
     """lcd_call_files with the job's one file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[,
     pg_line, block_payload]), the phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads,
     n_passes, flip_hap, flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -1973,7 +1996,9 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     refine=True (the command line's --refine-bam; no effect without bam_out, not with te_fasta / rnames): lcd_aln_opt_t.refine; the result gains "refine" =
     lcd_refine_stats_t's fields.
     aln_format="sam" (the command line's --sam): bam_out's path gets SAM text ("-": stdout), block_payload is ignored, no output index; the result gains "sam" =
-    lcd_sam_stats_t's fields"""
+    lcd_sam_stats_t's fields.
+    vcf_index=None | "tbi" | "csi" (the command line's --vcf-index; needs vcf_bgzf=1 and a vcf_path): <vcf_path>.tbi / .csi is written beside the VCF; the result
+    gains "vcf_index" = lcd_vcf_index_stats_t's fields (skipped != 0: the VCF could not be indexed, skip_reason says why)"""
     from ._lib import LCD_ALN_BAM, LCD_ALN_SAM, LcdAlnOpt, LcdBamOut, LcdFileJob, LcdFileStats, LcdIndexOpt, LcdIndexStats, LcdRefineStats, LcdRunOpt, LcdRunOut, LcdSamStats
     if aln_format not in ("bam", "sam"):
         raise ValueError("call_file: aln_format must be 'bam' or 'sam'")
@@ -2018,9 +2043,16 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     sst = LcdSamStats() if aln_format == "sam" else None
     ao = LcdAlnOpt(LCD_ALN_SAM if aln_format == "sam" else LCD_ALN_BAM, int(bool(refine)))
     ptr = lambda x: C.pointer(x) if x is not None else None
+    vio, vist = _vcf_index_opt(vcf_index, with_stats=False) if vcf_index is not None else (None, None)
     ro = LcdRunOpt(idx=ptr(io), fields=ptr(vf), aln=C.pointer(ao))
     out = LcdRunOut(idx_stats=ptr(ist), n_reads_per_file=C.cast(per_file, C.POINTER(C.c_int64)) if _inputs is not None else None, fields_out=ptr(fo), refine_stats=ptr(rst), sam_stats=ptr(sst))
-    rc = lib.lcd_call_files(C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
+    args = (C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
+    if vio is not None:
+        from ._lib import LcdRunExt
+        ext = LcdRunExt(vcf_idx=C.pointer(vio), vcf_idx_stats=C.pointer(vist))
+        rc = lib.lcd_call_files_ext(*args, C.byref(ext))
+    else:
+        rc = lib.lcd_call_files(*args)
     try:
         check(rc, lib)
         res = {k: getattr(st, k) for k, _t in LcdFileStats._fields_[:14]}
@@ -2041,6 +2073,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
         if sst is not None:
             res["sam"] = {k: getattr(sst, k) for k, _t in LcdSamStats._fields_}
+        if vist is not None:
+            res["vcf_index"] = _vcf_index_stats(vist)
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))
@@ -2077,6 +2111,36 @@ def bai_build(bam_path, out_path=None, slab_members=0, verify_crc=0):
     opt, st = LcdBaiOpt(int(slab_members), int(verify_crc)), LcdBaiStats()
     check(lib.lcd_bai_build(_enc(bam_path), _enc(out_path if out_path is not None else bam_path + ".bai"), C.byref(opt), C.byref(st)), lib)
     return {k: getattr(st, k) for k, _t in LcdBaiStats._fields_}
+
+
+def tbx_from_records(fmt, names, tid, beg, end, vbeg, vend, max_contig_len=0):
+    """lcd_tbx_from_records (pure host code): a table of data lines -> the UNCOMPRESSED bytes of its .tbi / .csi"""
+    from ._lib import LCD_VIDX_CSI, LCD_VIDX_TBI
+    lib = load_library()
+    a = [np.ascontiguousarray(tid, np.int32), np.ascontiguousarray(beg, np.int64), np.ascontiguousarray(end, np.int64), np.ascontiguousarray(vbeg, np.uint64),
+         np.ascontiguousarray(vend, np.uint64)]
+    n = len(a[0])
+    assert all(len(x) == n for x in a)
+    nm, n_ref = _str_array(names)
+    out, sz = C.c_void_p(), C.c_size_t()
+    tys = [C.c_int, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64]
+    check(lib.lcd_tbx_from_records(LCD_VIDX_CSI if fmt == "csi" else LCD_VIDX_TBI, n_ref, nm, int(max_contig_len), n, *[x.ctypes.data_as(C.POINTER(t)) for x, t in zip(a, tys)],
+                                   C.byref(out), C.byref(sz)), lib)
+    try:
+        return C.string_at(out.value, sz.value)
+    finally:
+        _libc_free(out)
+
+
+def vcf_index_build(path, out_path=None, fmt="tbi", slab_members=0):
+    """lcd_vcf_index_build: the .tbi / .csi of a BGZF-compressed VCF of any size, built on the device (out_path None: <path>.tbi / <path>.csi) -> dict of
+    lcd_vcf_index_stats_t"""
+    from ._lib import LcdVcfIndexStats
+    lib = load_library()
+    vo, _ = _vcf_index_opt(fmt, slab_members=slab_members, with_stats=False)
+    st = LcdVcfIndexStats()
+    check(lib.lcd_vcf_index_build(_enc(path), _enc(out_path) if out_path is not None else None, C.byref(vo), C.byref(st)), lib)
+    return _vcf_index_stats(st)
 
 
 def fai_build(fasta_path, out_path=None):

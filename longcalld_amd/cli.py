@@ -19,9 +19,10 @@ VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E":
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
-          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam"}
+          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam", "--vcf-index": "vcf_index"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
+       python -m longcalld_amd.cli index [--csi] in.vcf.gz [out]   build in.vcf.gz.tbi (--csi: .csi) on the device; BAM or VCF is decided by the file's content, not its name
        python -m longcalld_amd.cli faidx ref.fa               build ref.fa.fai
   ref.fa needs ref.fa.fai, every input BAM needs its .bai; a missing one is an error unless --make-index is given
 Inputs:   one sample from several BAMs (one per SMRT cell / flow cell, same reference table): --add-bam FILE (repeatable)   --bam-list FILE (one path per line)
@@ -36,7 +37,9 @@ Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z 
           --refine-bam   with -b or --sam: every kept read is written with the alignment the caller arrived at (CIGAR, POS, NM / MD / cs; the reference's --refine-aln);
           without -b / --sam it has no effect; a rewrite can move POS, so the output may stop being sorted (then no <out.bam>.bai is written, and the reason is printed)
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
-Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched; --sam gets no index)
+Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched; --sam gets no index);
+                         it does not index the VCF: that is --vcf-index
+          --vcf-index tbi|csi   with -O z and -o FILE: write FILE.tbi / FILE.csi beside the compressed VCF (built on the device from the text being compressed)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
 Not supported (refused with exit status 2): -s, --refine-aln (use --refine-bam), -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S (use --sam), -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
           --out-som-var-rnames
@@ -100,16 +103,31 @@ def input_bams(o, bam):
 
 
 def parse_index(argv):
-    """index in.bam [out.bai] | faidx ref.fa -> (command, paths) or an int exit status"""
+    """index [--csi] FILE [OUT] | faidx ref.fa -> (command, paths) or an int exit status; `index --csi` comes back as the command index-csi"""
     cmd, rest = argv[0], argv[1:]
     if any(a in ("-h", "--help") for a in rest):
         sys.stdout.write(USAGE); return 0
+    if cmd == "index" and "--csi" in rest:
+        cmd, rest = "index-csi", [a for a in rest if a != "--csi"]
     bad = [a for a in rest if a.startswith("-") and a != "-"]
     if bad:
         return refuse(f"unknown option {bad[0]}")
-    if (cmd == "index" and len(rest) not in (1, 2)) or (cmd == "faidx" and len(rest) != 1):
+    if (cmd.startswith("index") and len(rest) not in (1, 2)) or (cmd == "faidx" and len(rest) != 1):
         sys.stderr.write(USAGE); return 2
     return cmd, rest
+
+
+def file_kind(path):
+    """"bam" / "vcf" / None by the file's content, not its name: the start of the first gzip member (BGZF or not), inflated on the host (a few kilobytes), or of
+    the file itself when it is not compressed.  None: neither "BAM\\1" nor "##fileformat=VCF" (or unreadable): `index` treats it as before, as a BAM"""
+    import zlib
+    try:
+        with open(path, "rb") as f:
+            head = f.read(1 << 16)
+        text = zlib.decompressobj(31).decompress(head, 64) if head[:2] == b"\x1f\x8b" else head[:64]
+    except (OSError, zlib.error):
+        return None
+    return "bam" if text[:4] == b"BAM\x01" else "vcf" if text.startswith(b"##fileformat=VCF") else None
 
 
 def main_index(argv):
@@ -119,14 +137,23 @@ def main_index(argv):
     cmd, paths = p
     from . import align
     try:
-        if cmd == "index":
-            st = align.bai_build(paths[0], paths[1] if len(paths) > 1 else None)
-            sys.stderr.write(f"longcalld_amd index: {st['n_records']} records ({st['n_no_coor']} without coordinate), {st['n_slabs']} slabs, {st['ms_wall'] / 1000:.2f} s\n")
+        if cmd.startswith("index"):
+            kind = file_kind(paths[0])
+            if cmd == "index-csi" and kind == "bam":
+                return refuse("index --csi: only BAI is built for a BAM, not CSI")
+            if cmd == "index-csi" and kind is None:
+                return refuse("index --csi: the file is not a VCF")
+            if kind != "vcf":
+                st = align.bai_build(paths[0], paths[1] if len(paths) > 1 else None)
+                sys.stderr.write(f"longcalld_amd index: {st['n_records']} records ({st['n_no_coor']} without coordinate), {st['n_slabs']} slabs, {st['ms_wall'] / 1000:.2f} s\n")
+            else:       # VCF text; uncompressed or plain gzip, the builder refuses it with a message that says which of the two it is
+                st = align.vcf_index_build(paths[0], paths[1] if len(paths) > 1 else None, fmt="csi" if cmd == "index-csi" else "tbi")
+                sys.stderr.write(f"longcalld_amd index: {st['n_data_lines']} data lines on {st['n_contigs']} contigs, {st['n_slabs']} slabs, {st['ms_wall'] / 1000:.2f} s\n")
         else:
             n = align.fai_build(paths[0])
             sys.stderr.write(f"longcalld_amd faidx: {n} sequences\n")
     except align.LcdError as e:
-        sys.stderr.write(f"longcalld_amd {cmd}: {e}\n")
+        sys.stderr.write(f"longcalld_amd {cmd.split('-')[0]}: {e}\n")
         return 1
     return 0
 
@@ -158,6 +185,11 @@ def main(argv=None):
         return refuse(f"not a number: {e}")
     if "out_sam" in o and "out_bam" in o:
         return refuse("--sam cannot be combined with -b/--out-bam: one alignment output per run")
+    if "vcf_index" in o:
+        if o["vcf_index"] not in ("tbi", "csi"):
+            return refuse("--vcf-index can only be tbi or csi")
+        if o.get("out_type") != "z" or o.get("out_vcf", "-") == "-":
+            return refuse("--vcf-index needs -O z and -o FILE: only a compressed VCF that goes to a file can be indexed")
     if o.get("out_sam") == "-" and o.get("out_vcf", "-") == "-":
         return refuse("--sam - needs -o FILE: the SAM text and the VCF cannot both go to stdout")
     from . import align
@@ -198,12 +230,15 @@ def main(argv=None):
                              min_mapq=num.get("min_mapq", 30), vcf_path=o.get("out_vcf"), vcf_bgzf=1 if o.get("out_type") == "z" else 0,
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
                              index=(dict(build_missing_bai=1, build_missing_fai=1) if sam else True) if "--make-index" in o["flags"] else None,
-                             **(dict(aln_format="sam") if sam else {}), **(dict(refine=True) if refine else vcf_fields(o)))
+                             **(dict(aln_format="sam") if sam else {}), **(dict(refine=True) if refine else vcf_fields(o)),
+                             **(dict(vcf_index=o["vcf_index"]) if "vcf_index" in o else {}))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
     if st.get("index", {}).get("out_bai_skipped"):
         sys.stderr.write("longcalld_amd call: the output BAM was written without an index: " + st["index"]["out_bai_skip_reason"] + "\n")
+    if st.get("vcf_index", {}).get("skipped"):
+        sys.stderr.write("longcalld_amd call: the VCF was written without an index: " + st["vcf_index"]["skip_reason"] + "\n")
     if st["plan_fallback"]:
         sys.stderr.write("longcalld_amd call: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
     per_file = f" ({' + '.join(str(x) for x in st['n_reads_per_file'])} from the {len(bams)} input files)" if len(bams) > 1 else ""

@@ -228,11 +228,9 @@ void lcd_bai_builder_destroy(lcd_bai_builder_t *b) {
 } // extern "C"
 
 // ---- the whole-file driver ----
-namespace {
-struct Member { uint64_t coff; uint32_t bsize, ulen; };
-const uint64_t MAX_RECORD = (1ull << 31) + 4;       // block_size is a signed 32-bit field
+using Member = lcd_bai::BgzfMember;
 // the BGZF members inside buf (file offset base): whole members only, at most `want`; 0 or < 0.  *used: the bytes they take
-int parse_members(const uint8_t *f, size_t n, uint64_t base, size_t want, bool at_eof, std::vector<Member> &out, size_t *used, const std::string &W) {
+int lcd_bai::parse_members(const uint8_t *f, size_t n, uint64_t base, size_t want, bool at_eof, std::vector<Member> &out, size_t *used, const std::string &W) {
     size_t o = 0;
     out.clear();
     while (out.size() < want && o < n) {
@@ -258,6 +256,8 @@ int parse_members(const uint8_t *f, size_t n, uint64_t base, size_t want, bool a
     return 0;
 }
 
+namespace {
+const uint64_t MAX_RECORD = (1ull << 31) + 4;       // block_size is a signed 32-bit field
 int bai_build_impl(const char *bam_path, const char *out_path, const lcd_bai_opt_t *opt, lcd_bai_stats_t *stats) {
     const std::string W = "lcd_bai_build";
     lcd_bai_stats_t S; memset(&S, 0, sizeof(S));

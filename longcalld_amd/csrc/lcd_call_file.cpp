@@ -10,7 +10,13 @@
 
 using namespace lcd_internal;
 
-struct lcd_vcf_writer_s { FILE *f = nullptr; bool own = false, bgzf = false; std::string path; };
+struct lcd_vcf_writer_s {
+    FILE *f = nullptr; bool own = false, bgzf = false; std::string path;
+    // lcd_vcf_writer_open_idx: the builder of the output's .tbi / .csi (NULL: none, or given up), where the index goes, the file offset of the next member, the
+    // append's text in HBM (uploaded once: the deflater and the builder read the same buffer)
+    lcd_vcf_index_builder_t *vidx = nullptr; std::string index_path; uint64_t file_off = 0; lcd_vcf_index_stats_t *vstats = nullptr; DevBuf d_text; int device = 0;
+    ~lcd_vcf_writer_s() { lcd_vcf_index_builder_destroy(vidx); }
+};
 
 namespace {
 char *dup_str(const std::string &s) { char *p = (char *)malloc(s.size() + 1); memcpy(p, s.c_str(), s.size() + 1); return p; }
@@ -185,35 +191,87 @@ int lcd_plan_chunks(int n_contigs, const char *const *names, const int64_t *lens
     return out->n;
 }
 
+} // extern "C"
+
 // ---- the VCF writer ----
-lcd_vcf_writer_t *lcd_vcf_writer_open(const char *path, int bgzf, const char *header_text) {
+namespace {
+// LCD_ERR_VIDX_ORDER / LCD_ERR_VIDX_CSI: the VCF goes on without an index (the BAM writer's out_bai_skipped behaviour); anything else is the caller's error
+int vcf_index_give_up(lcd_vcf_writer_s *w, int rc) {
+    if (rc != LCD_ERR_VIDX_ORDER && rc != LCD_ERR_VIDX_CSI) return rc;
+    if (w->vstats) { w->vstats->skipped = rc; snprintf(w->vstats->skip_reason, sizeof(w->vstats->skip_reason), "%s", g_err.c_str()); }
+    lcd_vcf_index_builder_destroy(w->vidx); w->vidx = nullptr;
+    remove(w->index_path.c_str());
+    return 0;
+}
+} // namespace
+extern "C" {
+lcd_vcf_writer_t *lcd_vcf_writer_open_idx(const char *path, int bgzf, const char *header_text, const lcd_vcf_index_opt_t *vi) {
+    const std::string W = "lcd_vcf_writer_open";
+    if (vi) {
+        if (vi->stats) memset(vi->stats, 0, sizeof(*vi->stats));
+        if (!bgzf || !path || !strcmp(path, "-")) { set_err(-4, W + "_idx: an index needs a BGZF-compressed VCF (bgzf = 1) that goes to a file"); return nullptr; }
+        if (vi->format != LCD_VIDX_TBI && vi->format != LCD_VIDX_CSI) { set_err(-4, W + "_idx: format must be LCD_VIDX_TBI or LCD_VIDX_CSI"); return nullptr; }
+    }
     std::unique_ptr<lcd_vcf_writer_s> w(new lcd_vcf_writer_s());
     w->bgzf = bgzf != 0;
     if (!path || !strcmp(path, "-")) { w->f = stdout; w->path = "-"; }
     else { w->f = fopen(path, "wb"); w->own = true; w->path = path; }
-    if (!w->f) { set_err(-30, std::string("lcd_vcf_writer_open: cannot open ") + path + " for writing"); return nullptr; }
+    if (!w->f) { set_err(-30, W + ": cannot open " + path + " for writing"); return nullptr; }
+    if (vi) {
+        w->index_path = vi->index_path ? std::string(vi->index_path) : w->path + (vi->format == LCD_VIDX_CSI ? ".csi" : ".tbi");
+        w->vstats = vi->stats;
+        remove(w->index_path.c_str());
+        w->vidx = lcd_vcf_index_builder_create(vi->format);
+        if (!w->vidx) { lcd_vcf_writer_t *p = w.release(); lcd_vcf_writer_abort(p); return nullptr; }
+        w->device = cur_device();
+    }
     if (header_text && header_text[0] && lcd_vcf_writer_append(w.get(), header_text)) { lcd_vcf_writer_t *p = w.release(); lcd_vcf_writer_abort(p); return nullptr; }
     return w.release();
 }
+lcd_vcf_writer_t *lcd_vcf_writer_open(const char *path, int bgzf, const char *header_text) { return lcd_vcf_writer_open_idx(path, bgzf, header_text, nullptr); }
 int lcd_vcf_writer_append(lcd_vcf_writer_t *w, const char *text) {
     const std::string W = "lcd_vcf_writer_append";
     if (!w || !w->f) return set_err(-4, W + ": NULL writer");
     const size_t n = text ? strlen(text) : 0;
     if (!n) return 0;
     if (!w->bgzf) return fwrite(text, 1, n, w->f) == n ? 0 : set_err(-30, W + ": short write on " + w->path);
-    lcd_deflated_t *d = lcd_bgzf_deflate_dev((const uint8_t *)text, n, 0, 0);
+    lcd_deflated_t *d = nullptr;
+    if (w->vidx) {      // one upload: the deflater and the index builder read the same text in HBM
+        if (text[n - 1] != '\n') return set_err(-4, W + ": with an index every append ends with a line end");
+        if (use_device(w->device)) return -1;
+        if (w->d_text.ensure(n + 64, 31)) return -1;
+        if (hipMemcpy(w->d_text.p, text, n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return set_err(-10, W + ": upload failed"); }
+        d = lcd_bgzf_deflate_dev_ptr(w->d_text.addr(), n, 0, 0);
+    } else d = lcd_bgzf_deflate_dev((const uint8_t *)text, n, 0, 0);
     if (!d) return -30;
     const size_t sz = lcd_deflated_size(d);
+    if (w->vidx) {
+        const size_t nb = lcd_deflated_n_blocks(d);
+        std::vector<lcd_bai_member_t> tab(nb);
+        uint64_t u = 0, c = w->file_off;
+        for (size_t k = 0; k < nb; ++k) {
+            uint32_t payload = 0, bsize = 0; int kind = 0;
+            if (lcd_deflated_block_info(d, k, &payload, &bsize, &kind)) { lcd_deflated_free(d); return -24; }
+            tab[k].uoff = u; tab[k].coff = c; tab[k].ulen = payload; tab[k].pad = 0; u += payload; c += bsize;
+        }
+        size_t next = 0;
+        int rc = (u == n && c == w->file_off + sz) ? lcd_vcf_index_builder_add_stream(w->vidx, w->d_text.addr(), n, 0, nb, tab.data(), w->file_off + sz, &next)
+                                                   : set_err(-24, W + ": the deflater's member table does not add up to the append");
+        if (rc) rc = vcf_index_give_up(w, rc);
+        if (rc) { lcd_deflated_free(d); return rc; }
+    }
     std::vector<uint8_t> buf(sz + 1);
     int rc = lcd_deflated_to_host(d, 0, sz, buf.data());
     lcd_deflated_free(d);
     if (!rc && fwrite(buf.data(), 1, sz, w->f) != sz) rc = set_err(-30, W + ": short write on " + w->path);
+    if (!rc) w->file_off += sz;
     return rc;
 }
 void lcd_vcf_writer_abort(lcd_vcf_writer_t *w) {
     if (!w) return;
     const std::string m = g_err;
     if (w->f) { if (w->own) fclose(w->f); else fflush(w->f); }
+    if (!w->index_path.empty()) remove(w->index_path.c_str());
     delete w;
     g_err = m;
 }
@@ -226,9 +284,17 @@ int lcd_vcf_writer_close(lcd_vcf_writer_t *w) {
         if (fwrite(eof_member, 1, 28, w->f) != 28) rc = set_err(-30, W + ": short write on " + w->path);
     }
     if ((w->own ? fclose(w->f) : fflush(w->f)) != 0 && !rc) rc = set_err(-30, W + ": closing " + w->path + " failed");
+    if (w->vidx && !rc) {      // the index after the EOF member
+        rc = lcd_vcf_index_builder_finish(w->vidx, w->index_path.c_str());
+        if (!rc) { if (w->vstats) { lcd_vcf_index_builder_counts(w->vidx, w->vstats); w->vstats->wrote = 1; } }
+        else rc = vcf_index_give_up(w, rc);
+    }
+    if (rc && !w->index_path.empty()) remove(w->index_path.c_str());
     delete w;
     return rc;
 }
+} // extern "C"
+extern "C" {
 
 void lcd_file_job_default(lcd_file_job_t *job) { memset(job, 0, sizeof(*job)); job->overlap = -1; }
 void lcd_file_stats_free(lcd_file_stats_t *s) {
@@ -396,18 +462,26 @@ struct Run {
 
 // the whole-file run over the input files of one sample; in == NULL: the one file of the job
 extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out) {
+    return lcd_call_files_ext(in, job, cfg, opt, stats, out, nullptr);
+}
+extern "C" int lcd_call_files_ext(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
+                                  const lcd_run_ext_t *ext) {
     const std::string W = "lcd_call_files";
     const lcd_index_opt_t *idx = opt ? opt->idx : nullptr;
     const lcd_vcf_fields_t *fields = opt ? opt->fields : nullptr;
     lcd_vcf_fields_out_t *fields_out = out ? out->fields_out : nullptr;
     int64_t *n_reads_per_file = out ? out->n_reads_per_file : nullptr;
     zero_run_out(out);
+    if (ext && ext->vcf_idx_stats) memset(ext->vcf_idx_stats, 0, sizeof(*ext->vcf_idx_stats));
     if (stats) memset(stats, 0, sizeof(*stats));
     lcd_index_stats_t ist_local; memset(&ist_local, 0, sizeof(ist_local));
     lcd_index_stats_t *ist = out && out->idx_stats ? out->idx_stats : &ist_local;
     if (int rc = check_aln_opt(W, opt)) return rc;
     if (idx && idx->write_out_bai && (!job || !job->bam_out)) return set_err(-4, W + ": write_out_bai needs bam_out");
     if (idx && idx->slab_members < 0) return set_err(-4, W + ": negative slab_members");
+    const lcd_vcf_index_opt_t *vcf_idx = ext ? ext->vcf_idx : nullptr;
+    if (vcf_idx && (!job || !job->vcf_bgzf || !job->vcf_path || !strcmp(job->vcf_path, "-"))) return set_err(-4, W + ": vcf_idx needs a BGZF-compressed VCF (vcf_bgzf) that goes to a file");
+    if (vcf_idx && vcf_idx->format != LCD_VIDX_TBI && vcf_idx->format != LCD_VIDX_CSI) return set_err(-4, W + ": vcf_idx->format must be LCD_VIDX_TBI or LCD_VIDX_CSI");
     if (!job || !cfg || !stats || (!in && !job->bam_path) || !job->fasta_path) return set_err(-4, W + ": NULL argument");
     if (in) {
         if (in->n < 1 || in->n > LCD_MAX_INPUTS || !in->bam_paths) return set_err(-4, W + ": the number of inputs must be 1 ... LCD_MAX_INPUTS, with their paths");
@@ -507,7 +581,9 @@ extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job,
             lcd_vcf_header(job->source_version ? job->source_version : lcd_version(), job->cmdline ? job->cmdline : "", job->date_yyyymmdd ? job->date_yyyymmdd : date, (int)nm.size(),
                            nm.data(), R.lens.data(), job->sample_name ? job->sample_name : sm ? sm : joined.c_str(), &hdr);
         }
-        R.vcf = lcd_vcf_writer_open(job->vcf_path, job->vcf_bgzf, hdr);
+        lcd_vcf_index_opt_t vio; memset(&vio, 0, sizeof(vio));
+        if (vcf_idx) { vio = *vcf_idx; vio.stats = ext->vcf_idx_stats; }
+        R.vcf = lcd_vcf_writer_open_idx(job->vcf_path, job->vcf_bgzf, hdr, vcf_idx ? &vio : nullptr);
         free(hdr); free(sm);
         if (!R.vcf) { lcd_file_stats_free(stats); return -30; }
         if (job->bam_out) {

@@ -197,6 +197,8 @@ struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint6
 
 } // namespace lcd_internal
 
+// lcd_vcf_index.cpp: what a VCF index builder has counted so far (lines, contigs, chunks, the bytes and times of finish), for the VCF writer and the whole-file driver
+void lcd_vcf_index_builder_counts(const lcd_vcf_index_builder_t *b, lcd_vcf_index_stats_t *S) __attribute__((visibility("hidden")));
 extern "C" void lcd_account_device_bytes(int device, long long delta); // the ledger's entry for buffers allocated outside DevBuf (lcd_io.cpp's inflated streams); exported, not in the public header
 // the planner's probes (lcd_host.cpp; exported, not in the public header): the decisions of lcd_plan.cpp for one chain / one WFA job, without a device.
 // out[12]: threads, wmax, lds_bytes, ring_k, ring16, solo, cert, node_cap, edge_cap, cell_cap, spill_x, min_w.  cert_level / solo: -1 automatic; hints: cell K1, cell K2, node (NULL: the learned ones)

@@ -45,6 +45,19 @@ void lcd_launch_bam_sam_emit(const BamSamIn &in, const unsigned long long *text_
 void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);
 void lcd_launch_bai_entry(const BaiJob &j, hipStream_t st);
 void lcd_launch_bai_compact(const BaiJob &j, hipStream_t st);
+// vcf_index_kernel.hip: VCF text in HBM -> line table, parsed data lines, contig runs, index entries (the stages are listed at the top of that file); scan: the
+// exclusive prefix of nb workgroup counts (j.block_cnt -> j.block_off, the total at [nb])
+void lcd_launch_vidx_scan(const VIdxJob &j, int nb, hipStream_t st);
+void lcd_launch_vidx_nl_count(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_nl_compact(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_flag(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_rank(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_parse(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_head_count(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_head(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_names(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_entry(const VIdxJob &j, hipStream_t st);
+void lcd_launch_vidx_compact(const VIdxJob &j, hipStream_t st);
 void lcd_launch_errrate(const ErrJob *jobs, const double *tab, double *out, int n_jobs, hipStream_t st);
 void lcd_launch_compose(const CmpJob *jobs, CmpOut *outs, const CmpSeg *segs, int n_jobs, int emit, hipStream_t stream);
 void lcd_launch_vars_scan(const VarScanJob *jobs, VarScanOut *outs, int n_jobs, hipStream_t stream);

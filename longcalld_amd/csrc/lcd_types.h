@@ -253,6 +253,21 @@ struct BaiJob {
     uint64_t end_coff; long long rec0;
     int n, n_members, n_ref, c_have, c_refid, c_pos, c_nocoor, pad;
 };
+// ---------------- the VCF index builder (vcf_index_kernel.hip) ----------------
+// one data line: its interval, [a, next) = its bytes in the stream with the '\n', its CHROM's length, the contig run of the stream it belongs to (0: the run
+// carried in from the stream before), flags bit 0: its CHROM differs from the data line's before it, bits 4-7: the code that refused it (VIdxJob::err)
+struct VIdxLine { long long beg, end; uint64_t a, next; uint32_t name_len, flags; int run, pad; };
+struct VIdxHead { uint64_t a; uint32_t name_len; int line; };                     // the first data line of a contig run: where its CHROM lies
+struct VIdxRun { unsigned long long n_lines, first_vbeg, last_vend, max_end; };   // per contig run of ONE stream (first_vbeg starts all-ones)
+// one stream.  lstart: n_lines + 1 line starts (a line is [lstart[k], lstart[k + 1] - 1) without its '\n'); rank: per line its data-line index or -1 (meta);
+// dline: per data line its line; run_win / run_nwin: per contig run the device address and length of its contig's window array; err: the smallest
+// (data-line number << 4 | code), code 1 beg decreases, 2 malformed line, 3 end behind `cap`, 5 no window; c_*: the data line in front of the stream
+struct VIdxJob {
+    uint64_t stream, lstart, rank, dline, lines, heads, entries, members, runs, run_win, run_nwin, err, block_cnt, block_off, chunks, carry_name, max_clen, name_offs, names;
+    uint64_t end_coff, n_bytes, first;
+    long long line0, c_beg, cap;
+    int n_lines, n_data, n_members, n_heads, c_have, c_name_len, n_blocks, pad;
+};
 // ---------------- the phased alignment output (deflate_kernel.hip, bam_tag_kernel.hip) ----------------
 // one BGZF payload's raw deflate stream in its slot: clen bytes, CRC-32 of the payload, kind 0 stored / 1 fixed / 2 dynamic codes, LZ77 tokens
 struct DeflateOut { uint32_t clen, crc, kind, n_tok; };
