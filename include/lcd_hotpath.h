@@ -1408,6 +1408,72 @@ int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char 
 lcd_bam_writer_t *lcd_bam_writer_open(const char *in_bam_path, lcd_bam_out_t *out, const lcd_writer_opt_t *wopt);
 int lcd_write_phased(const char *in_bam_path, int n_chunks, const lcd_call_chunk_t *chunks, lcd_bam_out_t *out, const lcd_writer_opt_t *wopt);
 
+/* ---- the per-haplotype CpG methylation table of a chunk, from the MM / ML tags of its records (mods_kernel.hip) ----
+ * The reference parses -m / --methylation and reads no tag; these are PROJECT RULES, restated in Python in tests/mods_common.py.  Positions are 1-based, as the
+ * chunk's region [reg_beg, reg_end] and the window [ref_beg, ref_end] are.
+ *   tags     MM: the first MM:Z, else the first Mm:Z.  ML: the first ML:B:C, else the first Ml:B:C.  MN: the first MN of an integer type.  The fields are hopped as
+ *            lcd_chunk_tag_records hops them: a field that runs past the record ends the walk.
+ *   MM       groups `B S codes [flag] (,delta)* ;` -- B one of ACGTUN, S + or -, codes lower-case letters (one modification each) or one decimal ChEBI id (one
+ *            code), flag . or ? or none, a delta of 1 ... 10 digits.  Anything else is a syntax error; the empty text has no groups.  Delta d skips d occurrences of
+ *            B in the read AS SEQUENCED; for a record with flag 0x10 those are the stored complements counted from the end of SEQ.  Only the exact 4-bit codes
+ *            A C G T match.  ML holds one byte per (called occurrence, code), group after group, the codes of one occurrence side by side.
+ *   wanted   the first group with B == C, S == +, and a letter list that holds opt->code; every group in front of it only moves the ML cursor.
+ *   class    v = the wanted code's byte, s = the sum of the occurrence's bytes: mod if v >= threshold, else canon if 255 - min(s, 255) >= threshold, else
+ *            filtered.  An occurrence the group does not list is canon under flag . or none and is not looked at under ?.
+ *   record   a kept record (the loader's flag / MAPQ filter; n_records) falls into the first of: n_no_mm (no MM), n_hard_clip (an H op), n_mn_mismatch (MN differs
+ *            from l_seq), n_syntax (anywhere in the text), n_no_group (no wanted group), n_overrun (a called ordinal at or behind the number of occurrences),
+ *            n_ml_short (ML has fewer bytes than the groups up to and including the wanted one need; no ML: none) -- and then adds nothing.
+ *   call     every other record's occurrences go, each, into the first of: n_unaligned (not in an M / = / X op), n_outside (p outside the region), n_off_context
+ *            (no CpG site of the record's strand at p: '+' is C at p with G at p + 1 and takes records without 0x10, '-' is G at p with C at p - 1 and takes records
+ *            with it; window codes 0-4, N and positions outside the window match nothing), else n_counted and the site's counter [3 * haps[read] + class].
+ * A chunk counts a site of its region for ALL its kept records.  Planned regions are disjoint and a chunk holds every record that overlaps its region, so a run
+ * counts every (record, site) pair once without the writer's skip plan.
+ * rows: the sites with a counter above zero, by position.  combine_strands: a row's key is the position of the CpG's C (p of a '+' site, p - 1 of a '-' site),
+ * its strand '.', and the chunk adds up what IT counted under the key; a CpG cut by the region's end gives one row in each of the two chunks, both with the key
+ * reg_end, and whoever joins tables of several chunks adds rows of equal key.
+ * lcd_chunk_mod_pileup: one site-map launch, one scan, one pile-up launch (a wavefront per kept record) and one compaction; only rows and statistics come down.
+ * opt->ref_seq: the window as letters or codes 0-4, uploaded once per call.  -4: a chunk not made from a BAM or not resolved, a code outside m / h, a threshold
+ * outside 128 ... 255, no window, a hap outside 0 ... 2.  lcd_mods_rows_to_host: pos[n], strand[n] ('+' '-' '.'), counts[9 n] (hap-major: mod, canon, filtered).
+ * lcd_mods_format (host only, no device): the rows as text lines `chrom start end code strand n_all mod_all n_h1 mod_h1 n_h2 mod_h2 n_filtered` (tabs; start =
+ * pos - 1, end = pos, or pos + 1 for '.'; n_* = mod + canon; integers only), behind the '#' header line when with_header; *text is malloc()'d. */
+typedef struct lcd_mods_opt_t { int code /* 'm' or 'h' */, threshold, combine_strands, reserved; const char *ref_seq; int64_t ref_beg, ref_end; } lcd_mods_opt_t;
+typedef struct lcd_mods_stats_t {
+    int64_t n_records, n_no_mm, n_no_group, n_hard_clip, n_mn_mismatch, n_syntax, n_overrun, n_ml_short, n_unaligned, n_outside, n_off_context, n_counted;
+    int64_t n_sites, n_rows;
+    double ms_site_map, ms_pileup, ms_compact;
+} lcd_mods_stats_t;
+typedef struct lcd_mods_s lcd_mods_t;
+void lcd_mods_opt_default(lcd_mods_opt_t *opt);
+int lcd_mods_opt_check(const lcd_mods_opt_t *opt);                       /* 0, or -4 (host only) */
+lcd_mods_t *lcd_chunk_mod_pileup(const lcd_chunk_t *chunk, const int *haps, const lcd_mods_opt_t *opt, lcd_mods_stats_t *stats);
+int lcd_mods_n_rows(const lcd_mods_t *m);
+int lcd_mods_rows_to_host(const lcd_mods_t *m, int64_t *pos, char *strand, uint32_t *counts);
+void lcd_mods_free(lcd_mods_t *m);
+/* host only: rows by position and strand -> combined rows in place (keys as above); returns their number, -4 for a NULL array or a strand outside + - */
+int lcd_mods_combine_rows(int n_rows, int64_t *pos, char *strand, uint32_t *counts);
+int lcd_mods_format(int n_rows, const int64_t *pos, const char *strand, const uint32_t *counts, const char *chrom, int code, int with_header, char **text);
+/* The table of a whole run: lcd_call_files_ext2 == lcd_call_files_ext with one more struct, lcd_run_ext2_t, whose FIRST member is its own size (sizeof as the
+ * caller compiled it): members behind `size` bytes read as zero, so the struct can grow without another export; a size that does not reach `mods_path` is -4.
+ * lcd_call_files_ext is the call with ext2 == NULL.  mods_path != NULL: at the writer stage, window by window and chunk by chunk in plan order, every chunk's
+ * lcd_chunk_mod_pileup with its final haplotypes (the array the tag writer gets) and the window the chunk was resolved with; the rows go to mods_path as
+ * lcd_mods_format writes them (the header line once), with or without an alignment output.  With mods_combine_strands the last row of a chunk is held back until
+ * the next chunk's first row is known and added to it when their keys and contigs are equal.  mods_code 0: 'm'; mods_threshold 0: 204.  Refused with -4 before
+ * any file is created: a code outside m / h, a threshold outside 128 ... 255, an empty path or "-".  The file is created after the refusals and removed when the
+ * run fails -- at any stage, the close of the other outputs included; the table is finished last.  *mods_stats: the sums over the chunks (n_rows: the data lines
+ * written), filled only by a run that succeeds. */
+typedef struct lcd_run_ext2_t {
+    size_t size;
+    const char *mods_path; int mods_code, mods_threshold, mods_combine_strands, reserved; lcd_mods_stats_t *mods_stats;
+} lcd_run_ext2_t;
+int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
+                        const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2);
+/* lcd_call_bam_regions_ext2 == lcd_call_bam_regions with the same struct: the table of the one contig, every region's chunk piled up with its final haplotypes (the
+ * chunks[c].first.state->haps the call returns) in region order, by the same writer.  The file is created after the refusals and the call, and removed when the
+ * table or the alignment output behind it fails.  lcd_call_bam_regions is the call with ext2 == NULL. */
+int lcd_call_bam_regions_ext2(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n_regions, const int64_t *reg_beg,
+                              const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
+                              lcd_bam_out_t *bam_out, const lcd_run_opt_t *opt, const lcd_run_out_t *out, const lcd_run_ext2_t *ext2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,21 @@ class LcdVcfFieldsOut(C.Structure):
     _fields_ = [("n_te_seqs", C.c_int), ("te_names", C.POINTER(C.c_char_p)), ("n_mei_lines", C.c_int64), ("n_rnames", C.c_int), ("rnames", C.POINTER(C.c_char_p))]
 
 
+class LcdModsOpt(C.Structure):
+    """lcd_mods_opt_t: the options of lcd_chunk_mod_pileup"""
+    _fields_ = [("code", C.c_int), ("threshold", C.c_int), ("combine_strands", C.c_int), ("reserved", C.c_int), ("ref_seq", C.c_char_p), ("ref_beg", C.c_int64),
+                ("ref_end", C.c_int64)]
+
+
+MODS_STAT_COUNTERS = ("n_records", "n_no_mm", "n_no_group", "n_hard_clip", "n_mn_mismatch", "n_syntax", "n_overrun", "n_ml_short", "n_unaligned", "n_outside", "n_off_context",
+                      "n_counted", "n_sites", "n_rows")
+
+
+class LcdModsStats(C.Structure):
+    """lcd_mods_stats_t: where the records and their calls went, and the wall-clock split of the call"""
+    _fields_ = [(n, C.c_int64) for n in MODS_STAT_COUNTERS] + [(n, C.c_double) for n in ("ms_site_map", "ms_pileup", "ms_compact")]
+
+
 class LcdRefineStats(C.Structure):
     """lcd_refine_stats_t: what lcd_chunk_refine_records did to the records it wrote"""
     _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "n_refined", "n_identical", "n_unrefined", "n_pos_moved", "n_no_digars", "n_qlen_mismatch", "n_bad_pos",
@@ -294,6 +309,12 @@ class LcdRunOut(C.Structure):
     """lcd_run_out_t: what a driver reports beside its statistics; a NULL member is not reported"""
     _fields_ = [("idx_stats", C.POINTER(LcdIndexStats)), ("n_reads_per_file", C.POINTER(C.c_int64)), ("fields_out", C.POINTER(LcdVcfFieldsOut)),
                 ("refine_stats", C.POINTER(LcdRefineStats)), ("sam_stats", C.POINTER(LcdSamStats))]
+
+
+class LcdRunExt2(C.Structure):
+    """lcd_run_ext2_t: the options of lcd_call_files_ext2; `size` comes first and is sizeof of the struct as the caller knows it"""
+    _fields_ = [("size", C.c_size_t), ("mods_path", C.c_char_p), ("mods_code", C.c_int), ("mods_threshold", C.c_int), ("mods_combine_strands", C.c_int), ("reserved", C.c_int),
+                ("mods_stats", C.POINTER(LcdModsStats))]
 
 
 class LcdRunExt(C.Structure):
@@ -353,6 +374,7 @@ EXPORTS = [
     "lcd_chunk_set_refine", "lcd_chunk_refine_log", "lcd_chunks_call_refine",
     "lcd_sam_names_create", "lcd_sam_names_free", "lcd_tagged_to_sam", "lcd_records_to_sam", "lcd_sam_text_size", "lcd_sam_text_dev_ptr", "lcd_sam_text_to_host", "lcd_sam_text_free",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
+    "lcd_mods_opt_default", "lcd_mods_opt_check", "lcd_chunk_mod_pileup", "lcd_mods_n_rows", "lcd_mods_rows_to_host", "lcd_mods_free", "lcd_mods_combine_rows", "lcd_mods_format", "lcd_call_files_ext2", "lcd_call_bam_regions_ext2",
 ]
 
 
@@ -609,6 +631,20 @@ def load_library():
     lib.lcd_sam_text_to_host.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, u8p]
     lib.lcd_sam_text_free.argtypes = [C.c_void_p]
     lib.lcd_sam_text_free.restype = None
+    i64p_m = C.POINTER(C.c_int64)
+    lib.lcd_mods_opt_default.argtypes = [C.POINTER(LcdModsOpt)]
+    lib.lcd_mods_opt_default.restype = None
+    lib.lcd_mods_opt_check.argtypes = [C.POINTER(LcdModsOpt)]
+    lib.lcd_chunk_mod_pileup.restype = C.c_void_p
+    lib.lcd_chunk_mod_pileup.argtypes = [C.c_void_p, i32p, C.POINTER(LcdModsOpt), C.POINTER(LcdModsStats)]
+    lib.lcd_mods_n_rows.argtypes = [C.c_void_p]
+    lib.lcd_mods_rows_to_host.argtypes = [C.c_void_p, i64p_m, C.c_char_p, u32p]
+    lib.lcd_mods_free.argtypes = [C.c_void_p]
+    lib.lcd_call_files_ext2.argtypes = list(lib.lcd_call_files_ext.argtypes) + [C.POINTER(LcdRunExt2)]
+    lib.lcd_call_bam_regions_ext2.argtypes = list(lib.lcd_call_bam_regions.argtypes) + [C.POINTER(LcdRunExt2)]
+    lib.lcd_mods_free.restype = None
+    lib.lcd_mods_combine_rows.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p]
+    lib.lcd_mods_format.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     _lib = lib
     return lib
 

@@ -694,6 +694,36 @@ class DeviceChunk:
         finally:
             lib.lcd_tagged_free(h)
 
+    def mod_pileup(self, haps, ref, ref_beg, ref_end, code="m", threshold=204, combine_strands=False):
+        """lcd_chunk_mod_pileup: the per-haplotype CpG methylation table of the chunk's region from the MM / ML tags of its kept records.  haps: 0 / 1 / 2 per kept
+        read; ref: the window as letters or codes 0-4 (bytes / uint8 array), ref[0] = position ref_beg (1-based), ref_end inclusive.
+        -> (rows [(position, strand, nine counters hap-major: mod, canon, filtered)], stats dict)"""
+        from ._lib import LcdModsOpt, LcdModsStats
+        lib = self.lib
+        hp = np.ascontiguousarray(haps, np.int32)
+        if len(hp) < self.n:
+            raise ValueError("mod_pileup: haps shorter than the chunk's reads")
+        hp = np.concatenate([hp, np.zeros(1, np.int32)])
+        refb = bytes(ref) if isinstance(ref, (bytes, bytearray)) else np.ascontiguousarray(ref, np.uint8).tobytes()
+        if len(refb) < int(ref_end) - int(ref_beg) + 1:
+            raise ValueError("mod_pileup: ref is shorter than [ref_beg, ref_end]")
+        refbuf = C.create_string_buffer(refb, len(refb) + 1)                  # (codes contain NULs: not a C string)
+        o = LcdModsOpt(); lib.lcd_mods_opt_default(C.byref(o))
+        o.code, o.threshold, o.combine_strands = ord(code) if isinstance(code, str) and len(code) == 1 else -1, int(threshold), int(bool(combine_strands))
+        o.ref_seq = C.cast(refbuf, C.c_char_p); o.ref_beg, o.ref_end = int(ref_beg), int(ref_end)
+        st = LcdModsStats()
+        h = lib.lcd_chunk_mod_pileup(self.h, hp.ctypes.data_as(i32p), C.byref(o), C.byref(st))
+        if not h:
+            raise LcdError("lcd_chunk_mod_pileup failed: " + lib.lcd_last_error().decode())
+        try:
+            n = int(lib.lcd_mods_n_rows(h))
+            pos = np.zeros(max(n, 1), np.int64); strand = C.create_string_buffer(max(n, 1)); cnt = np.zeros(9 * max(n, 1), np.uint32)
+            check(lib.lcd_mods_rows_to_host(h, pos.ctypes.data_as(C.POINTER(C.c_int64)), strand, cnt.ctypes.data_as(C.POINTER(C.c_uint32))), lib)
+            rows = [(int(pos[k]), strand.raw[k:k + 1].decode(), tuple(int(x) for x in cnt[9 * k:9 * k + 9])) for k in range(n)]
+            return rows, {f: getattr(st, f) for f, _ in LcdModsStats._fields_}
+        finally:
+            lib.lcd_mods_free(h)
+
     def read_info(self):
         n = self.n
         st = np.zeros(n, np.int32); beg = np.zeros(n, np.int64); end = np.zeros(n, np.int64); nc = np.zeros(n, np.int32); nd = np.zeros(n, np.int32)
@@ -1699,6 +1729,40 @@ def chunks_call(chunks, items, cfg=None, chrom="chr11", te_fasta=None, rnames=No
 call_chunks = chunks_call
 
 
+def chunk_mod_pileup(chunk, haps, ref, ref_beg, ref_end, code="m", threshold=204, combine_strands=False):
+    """DeviceChunk.mod_pileup"""
+    return chunk.mod_pileup(haps, ref, ref_beg, ref_end, code, threshold, combine_strands)
+
+
+def mods_combine_rows(rows):
+    """lcd_mods_combine_rows (host only): rows by position and strand -> the combined rows, keyed by the position of the CpG's C, strand '.'"""
+    lib = load_library()
+    n = len(rows)
+    pos = np.array([r[0] for r in rows] + [0], np.int64); strand = C.create_string_buffer(b"".join(r[1].encode() for r in rows), n + 1)
+    cnt = np.array([x for r in rows for x in r[2]] + [0] * 9, np.uint32)
+    m = lib.lcd_mods_combine_rows(n, pos.ctypes.data_as(C.POINTER(C.c_int64)), strand, cnt.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if m < 0:       # (host-only code: it sets no error text)
+        raise LcdError(f"lcd_mods_combine_rows: error {m}: a strand outside + / -")
+    return [(int(pos[k]), strand.raw[k:k + 1].decode(), tuple(int(x) for x in cnt[9 * k:9 * k + 9])) for k in range(m)]
+
+
+def mods_format(rows, chrom, code="m", with_header=False):
+    """lcd_mods_format (host only): the table's text for rows [(position, strand, nine counters)]"""
+    lib = load_library()
+    n = len(rows)
+    pos = np.array([r[0] for r in rows] + [0], np.int64); strand = C.create_string_buffer(b"".join(r[1].encode() for r in rows), n + 1)
+    cnt = np.array([x for r in rows for x in r[2]] + [0] * 9, np.uint32)
+    text = C.c_void_p()
+    rc = lib.lcd_mods_format(n, pos.ctypes.data_as(C.POINTER(C.c_int64)), strand, cnt.ctypes.data_as(C.POINTER(C.c_uint32)), _enc(chrom), ord(code) if len(code) == 1 else -1,
+                             int(bool(with_header)), C.byref(text))
+    if rc < 0:
+        raise LcdError(f"lcd_mods_format: error {rc}: a code outside m / h or a strand outside + - .")
+    try:
+        return C.string_at(text).decode()
+    finally:
+        _libc.free(text)
+
+
 def bgzf_deflate(data, block_payload=0, add_eof=1):
     """lcd_bgzf_deflate_dev: bytes -> dict(image = the BGZF file image compressed on the device, blocks = [(payload bytes, member bytes, kind 0 stored / 1 fixed /
     2 dynamic)], kernel_ms)"""
@@ -1819,12 +1883,14 @@ def write_phased_sam(in_bam_path, chunks, path, pg_line=None, sort_output=False,
                 refine={k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}, sam={k: getattr(sst, k) for k, _t in LcdSamStats._fields_})
 
 
-def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False):
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False, mods=None):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
     bam_out = dict(path[, pg_line, block_payload]): the phased alignment file is written too; the result gets "bam_out" = the counters and stage times of
     lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
     te_fasta= / rnames=: lcd_run_opt_t.fields (as chunks_call).  refine=True (with bam_out; not with te_fasta / rnames): lcd_aln_opt_t.refine -- the records are
-    written with the alignments the call arrived at; the result gains "refine" = lcd_refine_stats_t's fields"""
+    written with the alignments the call arrived at; the result gains "refine" = lcd_refine_stats_t's fields.
+    mods = dict(path[, code, threshold, combine_strands]) (lcd_call_bam_regions_ext2): the contig's methylation table goes to path, every region's chunk piled up
+    with the haplotypes the result returns for it; the result gains "mods" = the sums of lcd_mods_stats_t"""
     from ._lib import LCD_ALN_BAM, LcdAlnOpt, LcdBamOut, LcdCallChunk, LcdRefineStats, LcdRunOpt, LcdRunOut, LcdVar1
     vf, fo = _vcf_fields(te_fasta, rnames)
     if refine and vf is not None:
@@ -1843,14 +1909,22 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     ao = LcdAlnOpt(LCD_ALN_BAM, int(rst is not None))
     ro = LcdRunOpt(fields=C.pointer(vf) if vf is not None else None, aln=C.pointer(ao))
     out = LcdRunOut(fields_out=C.pointer(fo) if vf is not None else None, refine_stats=C.pointer(rst) if rst is not None else None)
-    rc = lib.lcd_call_bam_regions(_enc(bam_path), _enc(bai_path), _enc(fasta_path), _enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
-                                  C.byref(text), C.byref(bo) if bo is not None else None, C.byref(ro), C.byref(out))
+    args = (_enc(bam_path), _enc(bai_path), _enc(fasta_path), _enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
+            C.byref(text), C.byref(bo) if bo is not None else None, C.byref(ro), C.byref(out))
+    mst = None
+    if mods is not None:
+        ext2, mst = _run_ext2(mods)
+        rc = lib.lcd_call_bam_regions_ext2(*args, C.byref(ext2))
+    else:
+        rc = lib.lcd_call_bam_regions(*args)
     err = lib.lcd_last_error().decode() if rc < 0 else ""
     if rc < 0 and (bo is None or (not text and not recs)):
         raise LcdError(f"liblcd_hotpath error {rc}: {err}")
     res = _call_result(lib, n, arr, recs, n_recs, text)
     if vf is not None:
         res = _fields_result(lib, res, vf, fo)
+    if mst is not None:
+        res["mods"] = {k: getattr(mst, k) for k, _t in mst._fields_}
     if bo is None:
         return res
     res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
@@ -1858,6 +1932,15 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     if rst is not None:
         res["refine"] = {k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}
     return res
+
+
+def _run_ext2(mods):
+    """mods = dict(path[, code, threshold, combine_strands]) -> (lcd_run_ext2_t, the lcd_mods_stats_t it points to)"""
+    from ._lib import LcdModsStats, LcdRunExt2
+    mst = LcdModsStats()
+    code = mods.get("code", "m")
+    return LcdRunExt2(size=C.sizeof(LcdRunExt2), mods_path=_enc(mods["path"]), mods_code=ord(code) if isinstance(code, str) and len(code) == 1 else -1,
+                      mods_threshold=int(mods.get("threshold", 204)), mods_combine_strands=int(bool(mods.get("combine_strands", False))), mods_stats=C.pointer(mst)), mst
 
 
 # ---------------- a whole BAM in one call (lcd_call_files and what it is composed of) ----------------
@@ -1985,7 +2068,7 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None, mods=None):
     """lcd_call_files with the job's one file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[,
     pg_line, block_payload]), the phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads,
     n_passes, flip_hap, flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -2047,9 +2130,16 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     ro = LcdRunOpt(idx=ptr(io), fields=ptr(vf), aln=C.pointer(ao))
     out = LcdRunOut(idx_stats=ptr(ist), n_reads_per_file=C.cast(per_file, C.POINTER(C.c_int64)) if _inputs is not None else None, fields_out=ptr(fo), refine_stats=ptr(rst), sam_stats=ptr(sst))
     args = (C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
+    ext, mst = None, None
     if vio is not None:
         from ._lib import LcdRunExt
         ext = LcdRunExt(vcf_idx=C.pointer(vio), vcf_idx_stats=C.pointer(vist))
+    if mods is not None:
+        # mods = dict(path[, code "m" | "h", threshold 128 ... 255, combine_strands]): the per-haplotype CpG methylation table (lcd_run_ext2_t); the result gains
+        # "mods" = the sums of lcd_mods_stats_t over the chunks (n_rows: the data lines written)
+        ext2, mst = _run_ext2(mods)
+        rc = lib.lcd_call_files_ext2(*args, C.byref(ext) if ext is not None else None, C.byref(ext2))
+    elif ext is not None:
         rc = lib.lcd_call_files_ext(*args, C.byref(ext))
     else:
         rc = lib.lcd_call_files(*args)
@@ -2075,6 +2165,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["sam"] = {k: getattr(sst, k) for k, _t in LcdSamStats._fields_}
         if vist is not None:
             res["vcf_index"] = _vcf_index_stats(vist)
+        if mst is not None:
+            res["mods"] = {k: getattr(mst, k) for k, _t in mst._fields_}
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))

@@ -13,13 +13,16 @@ REFUSED = {
     "--out-var-rnames": "--out-var-rnames is not supported: ask for the supporting read names of every record with --var-rnames",
     "--out-sv-rnames": "--out-sv-rnames is not supported: ask for the supporting read names of SV records with --sv-rnames",
     "--out-som-var-rnames": "--out-som-var-rnames is not supported: somatic / mosaic calling is not supported",
+    "-m": "-m/--methylation is not supported (the reference reads no MM/ML tag behind it): ask for the per-haplotype CpG methylation table with --mods FILE",
+    "--methylation": "-m/--methylation is not supported (the reference reads no MM/ML tag behind it): ask for the per-haplotype CpG methylation table with --mods FILE",
 }
-FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam", "--mod-combine-strands"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
-          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam", "--vcf-index": "vcf_index"}
+          "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam", "--vcf-index": "vcf_index",
+          "--mods": "mods", "--mod-code": "mod_code", "--mod-threshold": "mod_threshold"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli index [--csi] in.vcf.gz [out]   build in.vcf.gz.tbi (--csi: .csi) on the device; BAM or VCF is decided by the file's content, not its name
@@ -36,13 +39,18 @@ Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z 
           --sam FILE   the alignment output as SAM text instead of -b (FILE "-": stdout, then -o must name a file); the records are formatted on the device
           --refine-bam   with -b or --sam: every kept read is written with the alignment the caller arrived at (CIGAR, POS, NM / MD / cs; the reference's --refine-aln);
           without -b / --sam it has no effect; a rewrite can move POS, so the output may stop being sorted (then no <out.bam>.bai is written, and the reason is printed)
+          --mods FILE   the per-haplotype CpG methylation table from the reads' MM / ML tags (5mC by default), piled up on the device with the haplotypes of this
+                        run: one line per reference CpG site and strand with a call (chrom start end code strand n_all mod_all n_h1 mod_h1 n_h2 mod_h2 n_filtered);
+                        works with or without -b / --sam
+          --mod-code m|h [m]   --mod-threshold INT [204] (128 ... 255: a call counts when its probability byte, or that of no modification, reaches it)
+          --mod-combine-strands   one line per CpG: the '-' site is added to the '+' site, strand "."
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
 Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched; --sam gets no index);
                          it does not index the VCF: that is --vcf-index
           --vcf-index tbi|csi   with -O z and -o FILE: write FILE.tbi / FILE.csi beside the compressed VCF (built on the device from the text being compressed)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
 Not supported (refused with exit status 2): -s, --refine-aln (use --refine-bam), -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S (use --sam), -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
-          --out-som-var-rnames
+          --out-som-var-rnames, -m/--methylation (use --mods FILE)
 """
 
 
@@ -90,6 +98,24 @@ def vcf_fields(o):
     """--te-lib FILE / --var-rnames / --sv-rnames -> the keywords te_fasta= / rnames= of align.call_file (the reference's `output_var_rnames || (is_sv &&
     output_sv_rnames)`, src/vcf_utils.c:208: --var-rnames wins)"""
     return dict(te_fasta=o.get("te_lib"), rnames="all" if "--var-rnames" in o["flags"] else "sv" if "--sv-rnames" in o["flags"] else None)
+
+
+def mods_option(o):
+    """--mods FILE / --mod-code / --mod-threshold / --mod-combine-strands -> the keyword mods= of align.call_file (None without --mods), or the refusal's text"""
+    extra = [k for k, name in (("mod_code", "--mod-code"), ("mod_threshold", "--mod-threshold")) if k in o] + (["x"] if "--mod-combine-strands" in o["flags"] else [])
+    if "mods" not in o:
+        return "--mod-code / --mod-threshold / --mod-combine-strands need --mods FILE" if extra else None
+    if o["mods"] in ("", "-"):
+        return "--mods needs a file: the table does not go to stdout"
+    if o.get("mod_code", "m") not in ("m", "h"):
+        return "--mod-code can only be m or h"
+    try:
+        thr = int(o.get("mod_threshold", 204))
+    except ValueError:
+        return "--mod-threshold is not a number"
+    if not 128 <= thr <= 255:
+        return "--mod-threshold must be 128 ... 255"
+    return dict(path=o["mods"], code=o.get("mod_code", "m"), threshold=thr, combine_strands="--mod-combine-strands" in o["flags"])
 
 
 def input_bams(o, bam):
@@ -192,6 +218,9 @@ def main(argv=None):
             return refuse("--vcf-index needs -O z and -o FILE: only a compressed VCF that goes to a file can be indexed")
     if o.get("out_sam") == "-" and o.get("out_vcf", "-") == "-":
         return refuse("--sam - needs -o FILE: the SAM text and the VCF cannot both go to stdout")
+    mods = mods_option(o)
+    if isinstance(mods, str):
+        return refuse(mods)
     from . import align
     is_ont = 1 if "--ont" in o["flags"] else 0
     clean, opt, pass_, call = {}, {}, {}, {}
@@ -231,7 +260,7 @@ def main(argv=None):
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
                              index=(dict(build_missing_bai=1, build_missing_fai=1) if sam else True) if "--make-index" in o["flags"] else None,
                              **(dict(aln_format="sam") if sam else {}), **(dict(refine=True) if refine else vcf_fields(o)),
-                             **(dict(vcf_index=o["vcf_index"]) if "vcf_index" in o else {}))
+                             **(dict(vcf_index=o["vcf_index"]) if "vcf_index" in o else {}), **(dict(mods=mods) if mods is not None else {}))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
@@ -245,7 +274,8 @@ def main(argv=None):
     sys.stderr.write(f"longcalld_amd call: {st['n_planned']} chunks in {st['n_windows']} windows, {st['n_reads']} reads{per_file}, {st['n_vcf_lines']} VCF lines, "
                      + (f"{st['n_mei_lines']} MEI records, " if "n_mei_lines" in st else "")
                      + (f"{st['refine']['n_refined']} refined / {st['refine']['n_unrefined']} unrefined records, " if refine and bam_out is not None else "")
-                     + (f"{st['bam_out']['bytes_file']} bytes of SAM text, " if sam else "") + f"{st['ms_wall'] / 1000:.2f} s\n")
+                     + (f"{st['bam_out']['bytes_file']} bytes of SAM text, " if sam else "") + (f"{st['mods']['n_rows']} methylation rows, " if mods is not None else "")
+                     + f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 
 

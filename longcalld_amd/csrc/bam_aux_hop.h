@@ -1,4 +1,4 @@
-// bam_aux_hop.h -- what the kernels that hop a record's auxiliary fields share (bam_tag_kernel.hip, bam_refine_kernel.hip): the NUL search of a Z / H value,
+// bam_aux_hop.h -- what the kernels that hop a record's auxiliary fields share (bam_tag_kernel.hip, bam_refine_kernel.hip, bam_sam_kernel.hip, mods_kernel.hip): the NUL search of a Z / H value,
 // a field's value size with the walk's stop rule, and bam_aux2i by the project's documented rule (types c C s S i I give their value, any other type 0).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -477,11 +477,19 @@ int lcd_write_phased(const char *in_bam_path, int n, const lcd_call_chunk_t *chu
 int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
                          int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out,
                          const lcd_run_opt_t *opt, const lcd_run_out_t *out) {
+    return lcd_call_bam_regions_ext2(bam_path, bai_path, fasta_path, chrom, n, reg_beg, reg_end, min_mapq, cfg, chunks, records, n_records, vcf_body, bam_out, opt, out, nullptr);
+}
+// ... with lcd_run_ext2_t: the contig's methylation table, every region's chunk piled up with its final haplotypes, in region order
+int lcd_call_bam_regions_ext2(const char *bam_path, const char *bai_path, const char *fasta_path, const char *chrom, int n, const int64_t *reg_beg, const int64_t *reg_end,
+                              int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body, lcd_bam_out_t *bam_out,
+                              const lcd_run_opt_t *opt, const lcd_run_out_t *out, const lcd_run_ext2_t *ext2) {
     const std::string W = "lcd_call_bam_regions";
     if (records) *records = nullptr;
     if (n_records) *n_records = 0;
     if (vcf_body) *vcf_body = nullptr;
     zero_run_out(out);
+    lcd_run_ext2_t x2; lcd_mods_opt_t mods_opt;
+    if (int rc = ModsSink::parse(W, ext2, &x2, &mods_opt)) return rc;
     if (int rc = check_aln_opt(W, opt)) return rc;
     if (opt && opt->aln && opt->aln->format == LCD_ALN_SAM) return set_err(-2, W + ": SAM text is not supported by this driver (lcd_write_phased on the called chunks writes it)");
     if (opt && opt->idx) return set_err(-4, W + ": index options are not supported by this driver");
@@ -533,10 +541,16 @@ int lcd_call_bam_regions(const char *bam_path, const char *bai_path, const char 
     }
     int rc = chunks_call_core(n, chunks, cfg, chrom, nullptr, &fr, records, n_records, vcf_body);
     if (rc == 0) fr.give(fields_out);
+    ModsSink mods;               // (created after the refusals and the call; removed when anything behind it fails)
+    if (rc == 0 && x2.mods_path) {
+        rc = mods.open(W, x2, mods_opt);
+        for (int c = 0; c < n && !rc; ++c) rc = mods.chunk(handles[c], chunks[c].first, chrom);
+    }
     if (rc == 0 && bam_out) {   // (a failure here leaves the records and the text valid)
         lcd_writer_opt_t wo; memset(&wo, 0, sizeof(wo)); wo.refine_stats = out ? out->refine_stats : nullptr;
         rc = lcd_write_phased(bam_path, n, chunks, bam_out, &wo);
     }
+    if (mods.active()) { const std::string m0 = g_err; const int rc3 = mods.finish(rc == 0); if (!rc) rc = rc3; else g_err = m0; }
     const std::string m = g_err;
     drop_inputs();
     g_err = m;

@@ -367,6 +367,7 @@ struct Run {
     std::vector<lcd_var1_t> kept;          // keep_records
     bool refine = false;                   // refined alignments in the alignment output: every chunk's rounds write their log
     FieldsRun *fields = nullptr;           // the TE library and the names mode of the call (read-only here; its counters belong to the call stage)
+    ModsSink mods;                         // the methylation table (lcd_run_ext2_t.mods_path): written by the write stage, chunk by chunk in plan order
     // the first error of any stage
     std::mutex err_mu; int err_code = 0; std::string err_msg; std::atomic<bool> failed{false};
     std::atomic<long long> peak{0};
@@ -440,6 +441,7 @@ struct Run {
         const double t0 = now_ms();
         int rc = vcf ? lcd_vcf_writer_append(vcf, w.text) : 0;
         if (!rc && bam) rc = lcd_bam_writer_append(bam, w.n, w.chunks.data(), w.tids.data(), &w.prev);
+        if (mods.active()) for (int c = 0; c < w.n && !rc; ++c) rc = mods.chunk(w.handles[c], w.chunks[c].first, w.chroms[c]);
         sample_peak();
         if (rc) { fail(rc, g_err); return rc; }
         std::lock_guard<std::mutex> lk(err_mu);
@@ -466,7 +468,13 @@ extern "C" int lcd_call_files(const lcd_inputs_t *in, const lcd_file_job_t *job,
 }
 extern "C" int lcd_call_files_ext(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
                                   const lcd_run_ext_t *ext) {
+    return lcd_call_files_ext2(in, job, cfg, opt, stats, out, ext, nullptr);
+}
+extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
+                                   const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2) {
     const std::string W = "lcd_call_files";
+    lcd_run_ext2_t x2; lcd_mods_opt_t mods_opt;
+    if (int rc = ModsSink::parse(W, ext2, &x2, &mods_opt)) return rc;
     const lcd_index_opt_t *idx = opt ? opt->idx : nullptr;
     const lcd_vcf_fields_t *fields = opt ? opt->fields : nullptr;
     lcd_vcf_fields_out_t *fields_out = out ? out->fields_out : nullptr;
@@ -595,6 +603,11 @@ extern "C" int lcd_call_files_ext(const lcd_inputs_t *in, const lcd_file_job_t *
             R.bam = lcd_bam_writer_open(bam0, job->bam_out, &wo);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
         }
+        if (x2.mods_path && R.mods.open(W, x2, mods_opt)) {
+            if (R.bam) lcd_bam_writer_abort(R.bam);
+            lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats);
+            return -30;
+        }
     }
     const int n_windows = (R.plan.n + window - 1) / window;
     auto make = [&](int k) { return std::unique_ptr<Window>(new Window(k * window, std::min(window, R.plan.n - k * window))); };
@@ -645,6 +658,8 @@ extern "C" int lcd_call_files_ext(const lcd_inputs_t *in, const lcd_file_job_t *
         if (!rc) rc = rc2;
         if (rc) R.err_msg = g_err;
     }
+    // the table is finished after the other outputs: a run that fails anywhere, their close included, leaves no table and no statistics of it
+    if (R.mods.active()) { const int rc3 = R.mods.finish(!rc); if (!rc && rc3) { rc = rc3; R.err_msg = g_err; } }
     if (job->keep_records) {
         stats->records = dup_vec(R.kept); stats->n_kept_records = (int)R.kept.size();
     }

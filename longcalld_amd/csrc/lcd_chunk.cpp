@@ -180,7 +180,7 @@ lcd_chunk_t *chunk_open_files(const lcd_digar_opt_t *opt, int n_bams, const char
     LcdRegionImage im;
     if (lcd_io_region_images(n_bams, bam_paths, bai_paths, chrom, reg_beg, reg_end, im)) { set_err(-30, std::string("lcd_chunk_create_from_bam: ") + lcd_io_last_error()); return nullptr; }
     std::unique_ptr<lcd_chunk_s> c(new lcd_chunk_s());
-    c->device = cur_device(); c->n_reads = 0; c->opt = *opt; c->from_bam = true; c->n_files = n_bams;
+    c->device = cur_device(); c->n_reads = 0; c->opt = *opt; c->from_bam = true; c->n_files = n_bams; c->reg_beg = reg_beg; c->reg_end = reg_end;
     c->pending.reset(new ChunkPending());
     ChunkPending &P = *c->pending; P.reg_beg = reg_beg; P.reg_end = reg_end; P.tlen = im.tlen;
     if (meta) { meta->tid = im.tid; meta->n_targets = im.n_ref; meta->target_len = im.tlen; }

@@ -193,6 +193,27 @@ inline int check_aln_opt(const std::string &W, const lcd_run_opt_t *opt) {
     return 0;
 }
 
+// the device buffers of lcd_chunk_mod_pileup: a call of its own makes and frees them, a driver run keeps one set for all its chunks (grow-only, as every DevBuf)
+struct ModsScratch { DevBuf d_jobs, d_cls, d_ref, d_idx, d_small, d_tab, d_rows; };
+lcd_mods_t *mod_pileup_core(const lcd_chunk_t *c, const int *haps, const lcd_mods_opt_t *opt, lcd_mods_stats_t *stats, ModsScratch &S);
+// the methylation table of a driver run (lcd_run_ext2_t.mods_path; lcd_mods.cpp): the refusals, the file, every chunk's pile-up in plan order, the sums of the
+// statistics and -- with combine_strands -- the last row of the chunk before, held back until the next chunk's first row is known.  One thread at a time.
+struct ModsSink {
+    FILE *f = nullptr; std::string path; lcd_mods_opt_t opt; lcd_mods_stats_t sum; lcd_mods_stats_t *stats_out = nullptr;
+    bool head = false, held = false; std::string held_chrom; int64_t held_pos = 0; uint32_t held_cnt[9];
+    ModsScratch scratch;     // (freed with the sink)
+    // ext2 as the caller's struct of any size -> *x2 (what lies behind its `size` reads as zero) and the pile-up's options; -4 before anything is created
+    static int parse(const std::string &W, const lcd_run_ext2_t *ext2, lcd_run_ext2_t *x2, lcd_mods_opt_t *mo);
+    int open(const std::string &W, const lcd_run_ext2_t &x2, const lcd_mods_opt_t &mo);     // creates the file
+    int chunk(const lcd_chunk_t *handle, const lcd_first_chunk_t &x, const char *chrom);    // the chunk's pile-up with its final haplotypes, its rows written
+    int finish(bool ok);     // ok: the held row, the header of an empty table, close, *stats_out; else (or when that fails): close and remove.  0 or -30
+    bool active() const { return f != nullptr; }
+    ~ModsSink() { if (f) { fclose(f); remove(path.c_str()); } }
+    ModsSink() = default; ModsSink(const ModsSink &) = delete; ModsSink &operator=(const ModsSink &) = delete;
+private:
+    int put(int n, const int64_t *pos, const char *strand, const uint32_t *cnt, const char *chrom);
+    int flush_held();
+};
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
 } // namespace lcd_internal
@@ -285,6 +306,7 @@ struct lcd_chunk_s {
     std::vector<uint64_t> rec_beg, rec_stop; std::vector<int> rec_read; std::vector<int64_t> rec_pos0, rec_endpos;
     // lcd_chunk_open_from_bams: the number of input files (1 otherwise), and per record / per kept read the file it came from; both tables are file-major
     int n_files = 1; std::vector<int> rec_file, read_file;
+    int64_t reg_beg = 0, reg_end = -1;                          // lcd_chunk_open_from_bam*: the region the chunk was made for (lcd_chunk_mod_pileup counts the sites inside it)
     uint64_t *iv_off = nullptr; lcd_noisy_iv_t *ivs = nullptr; uint8_t *iv_in_chunk = nullptr;
     DevBuf d_qual; std::mutex qual_mu;                     // lcd_chunk_clean_vars: a host-array chunk's qualities, uploaded on first use
     std::unique_ptr<ChunkPending> pending;                 // lcd_chunk_open_from_bam: set until lcd_chunk_resolve (a handle with it has no digars yet)

@@ -40,6 +40,11 @@ void lcd_launch_bam_refine_emit(const BamRefineJob *jobs, const BamRefineOut *ou
 // wavefront per record each
 void lcd_launch_bam_sam_measure(const BamSamIn &in, BamSamOut *outs, hipStream_t st);
 void lcd_launch_bam_sam_emit(const BamSamIn &in, const unsigned long long *text_off, uint8_t *text, hipStream_t st);
+// mods_kernel.hip: the CpG sites of a region (flags; lcd_launch_cv_scan makes them indices), the pile-up of the records' MM / ML calls (one wavefront per record),
+// the non-empty sites as rows (rows: one entry per site; *n_rows: zeroed device int)
+void lcd_launch_mods_sites(const ModsIn &in, int *flag, long long n_pos, hipStream_t st);
+void lcd_launch_mods_pileup(const ModsIn &in, hipStream_t st);
+void lcd_launch_mods_compact(const ModsIn &in, long long n_pos, ModsRow *rows, int *n_rows, hipStream_t st);
 // bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
 // counters; compact: scan of the workgroups' run heads + the dense chunk list)
 void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);

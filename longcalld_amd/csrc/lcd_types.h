@@ -295,6 +295,14 @@ struct BamSamIn { const uint8_t *base; const unsigned long long *rec_off; const 
 // what the measure pass found: the line's length with its '\n'; flags bit 0: the CIGAR came from a CG field, bit 1: the field walk stopped in front of the
 // record's end, bit 2: name / CIGAR / bases / qualities do not fit the record; n_float: f values printed (scalar fields and B:f elements)
 struct BamSamOut { unsigned long long len; uint32_t flags, n_float; };
+// ---------------- the per-haplotype CpG methylation table (mods_kernel.hip) ----------------
+// one kept record ([src, src + len): its block_size word and body) with its read's haplotype 0 / 1 / 2; cls: device address of `cap` scratch bytes (cap = l_seq),
+// where the pile-up keeps one class byte per occurrence of the base
+struct ModsJob { uint64_t src, cls; uint32_t len, cap; int hap, pad; };
+// ref: the window's codes 0-4, ref[0] = position ref_beg (1-based, as the region); site_idx: per position of the region the index of its site in the counter table
+// (the exclusive scan of the site flags); tab: nine counters per site (hap-major: mod, canon, filtered); stats: twelve counters in the order of lcd_mods_stats_t
+struct ModsIn { const ModsJob *jobs; const uint8_t *ref; const int *site_idx; unsigned *tab; unsigned long long *stats; long long ref_beg, ref_end, reg_beg, reg_end; int n_jobs, code, threshold, pad; };
+struct ModsRow { long long pos; int strand /* 1 '+', 2 '-' */, pad; unsigned count[9]; unsigned pad2; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;
