@@ -142,6 +142,16 @@ void lcdo_poa_cert_stats(long long *out);
  * predecessors satisfy the extend equality).  lcdo_poa_tie_counts reads the counters and resets them. */
 void lcdo_poa_tie_census(int on);
 void lcdo_poa_tie_counts(long long out[8]);
+/* re-sort census (K1 and K2; oracle/poa.c), off by default: what every read that added a node or an edge asks of an incremental re-sort that restarts the Kahn
+ * walk at a cut of the old order (cut[i]: the FIFO was empty right after the node of index i was popped).  PROPERTIES OF THE INPUT GRAPH, not a replay of the
+ * kernel; it changes no result.  A place is an old index where the read changed the graph (the source of a new edge that is an old node; idx - 1 of the old node
+ * a new node was aligned to); q / c the nearest cut at or before / behind it, span = c - q + 1.  out[0] topo_reads, [1] edges_only, [2] new_1_64, [3] new_65_128,
+ * [4] new_over_128 (reads, by new nodes), [5] max_places, [6] max_pieces (maxima over reads; a piece: consecutive places with one q), [7] places, [8] ring_grew,
+ * [9] no_cut_256 (p - q >= 256), [10] span_le_12, [11] span_13_52, [12] span_53_64, [13] span_over_64 (every place in one of the four), [14] max_span, and per
+ * place with span <= 64, when some old row of [q, c] has it: [15] fan_out4, [16] fan_in4, [17] far_target (an out-edge to an old row >= q + 64), [18]
+ * far_target_ring (that row has an aligned mate), [19] ring3_in_span.  lcdo_poa_resort_counts reads the counters and resets them. */
+void lcdo_poa_resort_census(int on);
+void lcdo_poa_resort_counts(long long out[20]);
 
 /* ---------------- align.c glue ---------------- */
 typedef struct {

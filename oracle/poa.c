@@ -55,6 +55,7 @@ struct lcdo_poa_s {
     uint64_t *rid; int rid_words;
     int n_seq;
     int *idx2node, *node2idx, *remain; int m_idx;
+    uint8_t *cut; /* cut[i]: the FIFO of topo_sort was empty right after it popped the node of index i (the kernel's definition, poa_kernel.hip Ctx::cut) */
     int last_score;
 };
 
@@ -68,6 +69,25 @@ static int g_tie_on;
 static long long g_tie[8];
 void lcdo_poa_tie_census(int on) { g_tie_on = on != 0; }
 void lcdo_poa_tie_counts(long long out[8]) { for (int i = 0; i < 8; ++i) { out[i] = g_tie[i]; g_tie[i] = 0; } }
+
+/* ---- re-sort census (test infrastructure): what each read that changed the topology asks of an INCREMENTAL re-sort that restarts the Kahn walk at a cut of the
+ * old order (poa_kernel.hip topo_sort_incremental).  Off by default; lcdo_poa_resort_census switches it, lcdo_poa_resort_counts reads and resets the counters.
+ * Everything below is a PROPERTY OF THE INPUT GRAPH -- the old order, the old cuts, the graph after the read's nodes and edges went in -- not a replay of the
+ * kernel: it says which class of input a read is, not which path the kernel took.  Nothing here feeds back into the graph: no result depends on it.
+ *   place   where the read changed the graph, as an index of the OLD order, in path order: the source of every newly created edge whose source is an old node, and
+ *           idx - 1 of the old node a new node was aligned to (the latter counted under ring_grew as well) -- the entries of the kernel's `ml` list
+ *   q, c    per place p: q the largest cut at or before p, c the smallest cut behind p;  span = c - q + 1  (index 0 and the sink's index are always cuts)
+ *   piece   a maximal run of a read's consecutive places with the same q
+ * Counters (lcd_oracle.h has the same list): per read [0] topo_reads, [1] edges_only, [2] new_1_64, [3] new_65_128, [4] new_over_128, [5] max_places (maximum
+ * over reads), [6] max_pieces (maximum over reads); per place [7] places, [8] ring_grew, [9] no_cut_256 (p - q >= 256), the span of EVERY place in one of
+ * [10] span_le_12, [11] span_13_52, [12] span_53_64, [13] span_over_64, [14] max_span; per place whose span is at most 64 rows, counted when some old row of
+ * [q, c] has the property: [15] fan_out4 (four or more out-edges), [16] fan_in4 (four or more in-edges), [17] far_target (an out-edge to an old row at or
+ * beyond q + 64), [18] far_target_ring (the same, the far row having an aligned mate), [19] ring3_in_span (an aligned ring of three or more nodes). ---- */
+#define N_RS 20
+static int g_rs_on;
+static long long g_rs[N_RS];
+void lcdo_poa_resort_census(int on) { g_rs_on = on != 0; }
+void lcdo_poa_resort_counts(long long out[N_RS]) { for (int i = 0; i < N_RS; ++i) { out[i] = g_rs[i]; g_rs[i] = 0; } }
 
 static inline int ilog2_32(uint32_t v) { int r = 0; while (v >>= 1) ++r; return r; }
 
@@ -85,7 +105,7 @@ static lcdo_poa_t *poa_init(int n_seq) {
     return g;
 }
 static void poa_free(lcdo_poa_t *g) {
-    free(g->node); free(g->edge); free(g->rid); free(g->idx2node); free(g->node2idx); free(g->remain); free(g);
+    free(g->node); free(g->edge); free(g->rid); free(g->idx2node); free(g->node2idx); free(g->remain); free(g->cut); free(g);
 }
 static int add_node(lcdo_poa_t *g, uint8_t base) {
     if (g->n_node == g->m_node) { g->m_node *= 2; g->node = (node_t *)realloc(g->node, g->m_node * sizeof(node_t)); }
@@ -94,13 +114,14 @@ static int add_node(lcdo_poa_t *g, uint8_t base) {
     n->aligned_next = g->n_node;
     return g->n_node++;
 }
-static void add_edge(lcdo_poa_t *g, int from, int to, int check, int read_id) {
+/* returns 1 if the edge was created, 0 if an existing one gained weight */
+static int add_edge(lcdo_poa_t *g, int from, int to, int check, int read_id) {
     if (check) {
         for (int e = g->node[from].out_head; e >= 0; e = g->edge[e].next_out)
             if (g->edge[e].to == to) {
                 g->edge[e].w += 1;
                 g->rid[(size_t)e * g->rid_words + (read_id >> 6)] |= 1ull << (read_id & 63);
-                return;
+                return 0;
             }
     }
     if (g->n_edge == g->m_edge) {
@@ -119,6 +140,7 @@ static void add_edge(lcdo_poa_t *g, int from, int to, int check, int read_id) {
     f->out_tail = e; f->n_out++;
     if (t->in_tail < 0) t->in_head = e; else g->edge[t->in_tail].next_in = e;
     t->in_tail = e; t->n_in++;
+    return 1;
 }
 static int get_aligned_id(lcdo_poa_t *g, int node_id, uint8_t base) {
     for (int a = g->node[node_id].aligned_next; a != node_id; a = g->node[a].aligned_next)
@@ -138,6 +160,7 @@ static void topo_sort(lcdo_poa_t *g) {
         g->idx2node = (int *)realloc(g->idx2node, g->m_idx * sizeof(int));
         g->node2idx = (int *)realloc(g->node2idx, g->m_idx * sizeof(int));
         g->remain = (int *)realloc(g->remain, g->m_idx * sizeof(int));
+        g->cut = (uint8_t *)realloc(g->cut, g->m_idx);
     }
     int *deg = (int *)malloc(n * sizeof(int)), *q = (int *)malloc(n * sizeof(int));
     for (int i = 0; i < n; ++i) deg[i] = g->node[i].n_in;
@@ -145,6 +168,7 @@ static void topo_sort(lcdo_poa_t *g) {
     q[qt++] = 0;
     while (qh < qt) {
         int cur = q[qh++];
+        g->cut[index] = (uint8_t)(qh == qt);
         g->idx2node[index] = cur; g->node2idx[cur] = index++;
         if (cur == 1) break;
         for (int e = g->node[cur].out_head; e >= 0; e = g->edge[e].next_out) {
@@ -574,10 +598,51 @@ static void add_sequence(lcdo_poa_t *g, const uint8_t *seq, int len, int read_id
     add_edge(g, last, 1, 0, read_id);
 }
 
+/* the re-sort census of one read (see the top of the file): idx2node / node2idx / cut are still the OLD order of the n_old nodes, the graph holds the read */
+static void resort_census(lcdo_poa_t *g, int n_old, int n_new, int n_newe, const int *pl, const uint8_t *pl_ring, int n_pl) {
+    if (n_new == 0 && n_newe == 0) return;
+    ++g_rs[0];
+    if (n_new == 0) ++g_rs[1]; else if (n_new <= 64) ++g_rs[2]; else if (n_new <= 128) ++g_rs[3]; else ++g_rs[4];
+    if (n_pl > g_rs[5]) g_rs[5] = n_pl;
+    int pieces = 0, q_prev = -2;
+    for (int k = 0; k < n_pl; ++k) {
+        const int p = pl[k];
+        int q = p, c = p + 1;
+        while (q >= 0 && !g->cut[q]) --q;
+        while (c < n_old - 1 && !g->cut[c]) ++c;
+        const int span = c - q + 1;
+        if (q != q_prev) { ++pieces; q_prev = q; }
+        ++g_rs[7]; g_rs[8] += pl_ring[k];
+        if (q < 0 || p - q >= 256) ++g_rs[9];
+        ++g_rs[span <= 12 ? 10 : span <= 52 ? 11 : span <= 64 ? 12 : 13];
+        if (span > g_rs[14]) g_rs[14] = span;
+        if (span > 64 || q < 0) continue;
+        int out4 = 0, in4 = 0, far = 0, far_ring = 0, ring3 = 0;
+        for (int r = q; r <= c; ++r) {
+            const int v = g->idx2node[r];
+            if (g->node[v].n_out >= 4) out4 = 1;
+            if (g->node[v].n_in >= 4) in4 = 1;
+            for (int e = g->node[v].out_head; e >= 0; e = g->edge[e].next_out) {
+                const int to = g->edge[e].to;
+                if (to < n_old && g->node2idx[to] >= q + 64) { far = 1; if (g->node[to].aligned_next != to) far_ring = 1; }
+            }
+            int ring = 1;
+            for (int a = g->node[v].aligned_next; a != v; a = g->node[a].aligned_next) ++ring;
+            if (ring >= 3) ring3 = 1;
+        }
+        g_rs[15] += out4; g_rs[16] += in4; g_rs[17] += far; g_rs[18] += far_ring; g_rs[19] += ring3;
+    }
+    if (pieces > g_rs[6]) g_rs[6] = pieces;
+}
+
 static void add_alignment(lcdo_poa_t *g, int beg_node, int end_node, const uint8_t *seq, int len, const gcig_t *cig,
                           int n_cig, int read_id) {
     if (g->n_node == 2) { add_sequence(g, seq, len, read_id); topo_sort(g); return; }
     if (n_cig == 0) return;
+    const int n_old = g->n_node, e_old = g->n_edge;
+    int *pl = NULL, n_pl = 0; uint8_t *pl_ring = NULL; /* census only: the places, in path order */
+    if (g_rs_on) { pl = (int *)malloc((size_t)(2 * n_cig + 2) * sizeof(int)); pl_ring = (uint8_t *)malloc((size_t)(2 * n_cig + 2)); }
+#define EDGE(from, to, chk) do { int f_ = (from); if (add_edge(g, f_, (to), (chk), read_id) && pl && !last_new) { pl_ring[n_pl] = 0; pl[n_pl++] = g->node2idx[f_]; } } while (0)
     int last = beg_node, last_new = 0;
     for (int i = 0; i < n_cig; ++i) {
         uint8_t b = seq[cig[i].qpos];
@@ -585,19 +650,22 @@ static void add_alignment(lcdo_poa_t *g, int beg_node, int end_node, const uint8
             int node = cig[i].node;
             if (g->node[node].base != b) {
                 int a = get_aligned_id(g, node, b);
-                if (a != -1) { add_edge(g, last, a, 1 - last_new, read_id); last = a; last_new = 0; }
+                if (a != -1) { EDGE(last, a, 1 - last_new); last = a; last_new = 0; }
                 else {
                     int nid = add_node(g, b);
-                    add_edge(g, last, nid, 0, read_id); last = nid; last_new = 1;
+                    EDGE(last, nid, 0); last = nid; last_new = 1;
                     add_aligned(g, node, nid);
+                    if (pl) { pl_ring[n_pl] = 1; pl[n_pl++] = g->node2idx[node] - 1; }
                 }
-            } else { add_edge(g, last, node, 1 - last_new, read_id); last = node; last_new = 0; }
+            } else { EDGE(last, node, 1 - last_new); last = node; last_new = 0; }
         } else {
             int nid = add_node(g, b);
-            add_edge(g, last, nid, 0, read_id); last = nid; last_new = 1;
+            EDGE(last, nid, 0); last = nid; last_new = 1;
         }
     }
-    add_edge(g, last, end_node, 1 - last_new, read_id);
+    EDGE(last, end_node, 1 - last_new);
+#undef EDGE
+    if (pl) { resort_census(g, n_old, g->n_node - n_old, g->n_edge - e_old, pl, pl_ring, n_pl); free(pl); free(pl_ring); }
     topo_sort(g);
 }
 

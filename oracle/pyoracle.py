@@ -345,6 +345,32 @@ class poa_tie_census:
         return False
 
 
+RESORT_KINDS = ("topo_reads", "edges_only", "new_1_64", "new_65_128", "new_over_128", "max_places", "max_pieces", "places", "ring_grew", "no_cut_256", "span_le_12",
+                "span_13_52", "span_53_64", "span_over_64", "max_span", "fan_out4", "fan_in4", "far_target", "far_target_ring", "ring3_in_span")
+
+
+class poa_resort_census:
+    """context manager: the re-sort census of oracle/poa.c (lcd_oracle.h) over the K1 / K2 calls made inside it: what the reads that changed the topology ask of an
+    incremental re-sort -- properties of the input graph, not a replay of the kernel.  `counts` is a dict over RESORT_KINDS, filled when the block ends; the
+    census is off again afterwards and changes no result."""
+
+    def __enter__(self):
+        L = lib()
+        L.lcdo_poa_resort_counts.argtypes = [C.POINTER(C.c_longlong)]; L.lcdo_poa_resort_counts.restype = None
+        L.lcdo_poa_resort_census.argtypes = [C.c_int]; L.lcdo_poa_resort_census.restype = None
+        L.lcdo_poa_resort_counts((C.c_longlong * len(RESORT_KINDS))())   # (reset)
+        L.lcdo_poa_resort_census(1)
+        self.counts = None
+        return self
+
+    def __exit__(self, *exc):
+        out = (C.c_longlong * len(RESORT_KINDS))()
+        lib().lcdo_poa_resort_census(0)
+        lib().lcdo_poa_resort_counts(out)
+        self.counts = dict(zip(RESORT_KINDS, (int(x) for x in out)))
+        return False
+
+
 def poa_aln_msa_cons(reads, max_n_cons=2, opt=None):
     """K2, src/align.c:872"""
     opt = opt or default_opt()

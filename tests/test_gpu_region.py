@@ -514,6 +514,23 @@ def test_resort_layouts_give_the_same_order(lcd, oracle, monkeypatch, shape, n):
         same_result(oracle.collect_noisy_reg_aln_strs(r), got)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,n", [("hifi", 200), ("ont", 100), ("sv", 8)])
+def test_incremental_resort_gives_the_full_resorts_order(lcd, monkeypatch, shape, n):
+    """the incremental re-sort (poa_kernel.hip topo_sort_incremental: the Kahn walk repeated from a cut of the old order, only where the read changed the graph)
+    leaves the order, the cut flags and `remain` the full re-sort would: the same digest over every consensus, cluster and alignment string with every topology
+    change handed to the full re-sort (LCD_DBG=1024).  tests/test_gpu_poa_resort.py holds both against the oracle on chains built for the walk's rare paths"""
+    from longcalld_amd import jobs
+    regs = jobs.make_regions(777, n, {"hifi": jobs.HIFI, "ont": jobs.ONT, "sv": jobs.SV}[shape])
+    o = lcd.default_opt(); o.is_ont = 0 if shape == "hifi" else 1
+    monkeypatch.delenv("LCD_DBG", raising=False)
+    _, _, _, d0 = _run_batch(lcd, regs, o)
+    monkeypatch.setenv("LCD_DBG", "1024")
+    _, _, _, d1 = _run_batch(lcd, regs, o)
+    print(f"{shape} x {n}: digest {d0} / incremental re-sort off {d1}")
+    assert d0 == d1 and d0 != 0
+
+
 @pytest.mark.parametrize("shape", ["hifi", "ont", "sv"])
 def test_dp_regions_grow_in_place(lcd, oracle, monkeypatch, shape):
     """DP regions sized far too small (test switch LCD_CELL_SHRINK): a chain whose read does not fit takes a larger region from the launch set's spare pool and
