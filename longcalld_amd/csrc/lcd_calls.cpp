@@ -6,7 +6,7 @@ using namespace lcd_internal;
 
 extern "C" {
 
-// ---- sdust on the device (sdust_kernel.hip): segments on lanes, the host chains their reports with sdust's merge rule ----
+// ---- sdust on the device (sdust_kernel.hip): segments on lanes, each reports what the automaton saves at its steps, the host chains the lists with sdust's merge rule ----
 // lcd_sdust_batch: the references of MANY chunks in one launch.  A lane's automaton is serial and latency-bound (21 ms for one 500 kb chunk against 9 ms
 // for the reference's sdust() on one core), but the chip holds ~60 000 lanes: the chunk workers' references of one pipeline step go in together.
 int lcd_sdust_batch(int n_seqs, const uint8_t *const *seqs, const int64_t *lens, int T, int W, int64_t **intervals_out, int *n_out) {
@@ -14,7 +14,7 @@ int lcd_sdust_batch(int n_seqs, const uint8_t *const *seqs, const int64_t *lens,
     if (ensure_init()) return -1;
     if (n_seqs <= 0) return 0;
     if (W > 64 || W < 4) return set_err(-4, "lcd_sdust: W must be in [4, 64]");
-    // segment length: the automaton is serial inside a segment (plus ~3W bases of lead-in and run-out), so short segments = more lanes, less latency
+    // segment length: the automaton is serial inside a segment (plus ~3W bases of lead-in), so short segments = more lanes, less latency
     const int seg = W <= 32 ? 128 : 256, cap = seg + 8;
     auto code = [](uint8_t c) { return c < 4 ? (int)c : (c == 'A' || c == 'a') ? 0 : (c == 'C' || c == 'c') ? 1 : (c == 'G' || c == 'g') ? 2 : (c == 'T' || c == 't') ? 3 : 4; };
     std::vector<SdSeg> segs; std::vector<size_t> first(n_seqs + 1, 0);
@@ -25,12 +25,13 @@ int lcd_sdust_batch(int n_seqs, const uint8_t *const *seqs, const int64_t *lens,
         if (lens[q] > 2000000000ll) return set_err(-4, "lcd_sdust: sequences below 2 Gb");
         const int len = (int)lens[q], n_seg = (len + seg - 1) / seg;
         const uint8_t *seq = seqs[q];
-        // where each segment's automaton starts: 2W + 4 triplet words before (segment start - W); a word ends at i when i-2..i are all A/C/G/T
-        std::vector<int> ring(2 * W + 4, -1); size_t rn = 0; // ring of the last 2W+4 word-end positions
+        // where each segment's automaton starts: W + 4 triplet words before (segment start - 2W); a word ends at i when i-2..i are all A/C/G/T
+        // (why that is enough: the header of sdust_kernel.hip; tests/sdust_model.py lane_starts is the same count)
+        std::vector<int> ring(W + 4, -1); size_t rn = 0; // ring of the last W+4 word-end positions
         int l = 0, next = 0;
         std::vector<int> from(n_seg, 0);
         for (int i = 0; i < len && next < n_seg; ++i) {
-            while (next < n_seg && std::max(0, next * seg - W) == i) { from[next] = rn >= ring.size() ? std::max(0, ring[rn % ring.size()] - 2) : 0; ++next; }
+            while (next < n_seg && std::max(0, next * seg - 2 * W) == i) { from[next] = rn >= ring.size() ? std::max(0, ring[rn % ring.size()] - 2) : 0; ++next; }
             if (code(seq[i]) < 4) { if (++l >= 3) { ring[rn % ring.size()] = i; ++rn; } } else l = 0;
         }
         for (int k = 0; k < n_seg; ++k) { SdSeg sg; sg.seq_off = pool_bytes; sg.len = len; sg.a = k * seg; sg.from = from[k]; sg.pad = 0; segs.push_back(sg); }
@@ -57,7 +58,7 @@ int lcd_sdust_batch(int n_seqs, const uint8_t *const *seqs, const int64_t *lens,
     HIPCHK(hipMemcpyAsync(raw.data(), d_out[dv].p, n_seg * (size_t)cap * 8, hipMemcpyDeviceToHost, st[dv]));
     HIPCHK(hipStreamSynchronize(st[dv]));
     for (int q = 0; q < n_seqs; ++q) {
-        std::vector<int64_t> res; // save_masked_regions' merge (src/sdust.c:97-103) over the segments' reports in order
+        std::vector<int64_t> res; // save_masked_regions' merge (src/sdust.c:93-98) over the lanes' lists in lane order = the order of the automaton's saves
         for (size_t s = first[q]; s < first[q + 1]; ++s) {
             if (n[s] < 0 || n[s] > cap) return set_err(-24, "lcd_sdust: per-segment capacity exceeded (sequence " + std::to_string(q) + ", segment " + std::to_string(s - first[q]) + ": " + std::to_string(n[s]) + ")");
             for (int k = 0; k < n[s]; ++k) {
