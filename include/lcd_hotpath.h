@@ -1452,6 +1452,55 @@ void lcd_mods_free(lcd_mods_t *m);
 /* host only: rows by position and strand -> combined rows in place (keys as above); returns their number, -4 for a NULL array or a strand outside + - */
 int lcd_mods_combine_rows(int n_rows, int64_t *pos, char *strand, uint32_t *counts);
 int lcd_mods_format(int n_rows, const int64_t *pos, const char *strand, const uint32_t *counts, const char *chrom, int code, int with_header, char **text);
+/* ---- the per-haplotype depth track of a chunk, from the CIGARs of its kept records (depth_kernel.hip) ----
+ * The reference has no such output; these are PROJECT RULES, restated in Python in tests/depth_common.py.  Positions are 1-based, as reg_beg / reg_end are.
+ *   record     a kept record of the chunk: the set lcd_chunk_mod_pileup walks (the loader's flag / MAPQ filter).  Its haplotype is haps[read]: 0, 1 or 2.
+ *   operations the record's own CIGAR, or those of its CG:B,I field by the rule of the loader (a placeholder `<l_seq>S<n>N` and a first CG field of subtype I / i
+ *              with at least n_cigar and fewer than 2^29 entries; one wording for both: lcd_aux::cg_ops, csrc/bam_aux_hop.h).  n_cg counts the latter; a record
+ *              with 0 operations, or whose fields run past its end, counts in n_no_cigar and adds nothing.
+ *   cover      M, = and X cover their reference span; D covers it unless skip_dels; N never does; I, S, H, P and every other code consume no reference; an
+ *              operation of length 0 does nothing.  Reference offsets are 64-bit: spans that sum past 2^31 are clipped, never wrapped.
+ *   intervals  the record's covered positions inside [reg_beg, reg_end], joined where they touch: what lies between two covering operations and consumes no
+ *              reference (I, S, P, a zero-length op; and D without skip_dels, which covers) does not break an interval.  A typical HiFi read is ONE interval.
+ *              n_intervals counts them; a record with operations and no interval counts in n_no_overlap.
+ *   depth      depth[h][p] = the kept records of haplotype h with p in an interval; bases[h] = its sum over the region.
+ *   rows       the maximal runs of equal (depth[0], depth[1], depth[2]) in position order: they tile [reg_beg, reg_end], zero runs included; a chunk without
+ *              records gives one zero row.  n_rows counts them.
+ *   windows    (host rule, lcd_depth_windows) window k of width W is [kW + 1, (k + 1)W] on the contig; the rows are cut at the window bounds and every window
+ *              that meets the rows gives one row: beg / end = the window cut to the rows' span, and per haplotype the 64-bit sum of depth x positions.
+ *   source     the track describes the records AS STORED in the input: refined alignments (lcd_aln_opt_t.refine, --refine-bam) do not change it.
+ * lcd_chunk_depth: one launch with a wavefront per kept record that adds +1 / -1 per interval to a three-plane difference array (32-bit integer atomics), then
+ * three launches that turn it into rows without a depth array and without one workgroup waiting for another (tile partials; their scan; the rows).  Only rows and
+ * statistics come down; `window` is not read here.  -4: a chunk not made from a BAM or not resolved, NULL haps with reads, a hap outside 0 ... 2, a region that
+ * is empty or longer than 2^31 - 1024.  lcd_depth_rows_to_host: beg[n], end[n], depth[3 n] (h0 h1 h2 per row).  lcd_depth_tile: the positions per workgroup of
+ * the row launches (host only; for tests that straddle it).
+ * lcd_depth_windows (host only): rows that tile a span, in order -> the windows' rows; returns their number m and malloc()'d wbeg[m], wend[m], wsum[3 m]; -4 for
+ * window < 1, NULL arrays, or rows that are not in order and contiguous; -11 without memory.
+ * lcd_depth_format (host only): text lines `chrom start end all h1 h2 unassigned` (tabs; start = beg - 1, end = end: BED; all = h0 + h1 + h2, unassigned = h0;
+ * integers only), from depth -- or from wsum when it is not NULL -- behind `#chrom start end depth_all depth_h1 depth_h2 depth_unassigned` (with wsum: bases_*)
+ * when with_header; *text is malloc()'d. */
+typedef struct lcd_depth_opt_t { int skip_dels, window, reserved[2]; } lcd_depth_opt_t;
+typedef struct lcd_depth_stats_t {
+    int64_t n_records, n_no_cigar, n_cg, n_no_overlap, n_intervals, bases[3], n_rows;
+    double ms_mark, ms_rows;
+} lcd_depth_stats_t;
+typedef struct lcd_depth_s lcd_depth_t;
+void lcd_depth_opt_default(lcd_depth_opt_t *opt);
+int lcd_depth_opt_check(const lcd_depth_opt_t *opt);                     /* 0, or -4: window outside 0 ... 2^30 (host only) */
+lcd_depth_t *lcd_chunk_depth(const lcd_chunk_t *chunk, const int *haps, const lcd_depth_opt_t *opt, lcd_depth_stats_t *stats);
+int lcd_depth_n_rows(const lcd_depth_t *d);
+int lcd_depth_rows_to_host(const lcd_depth_t *d, int64_t *beg, int64_t *end, uint32_t *depth);
+void lcd_depth_free(lcd_depth_t *d);
+int lcd_depth_tile(void);
+int lcd_depth_windows(int n_rows, const int64_t *beg, const int64_t *end, const uint32_t *depth, int window, int64_t **wbeg, int64_t **wend, uint64_t **wsum);
+int lcd_depth_format(int n_rows, const int64_t *beg, const int64_t *end, const uint32_t *depth, const uint64_t *wsum, const char *chrom, int with_header, char **text);
+/* The track of a whole run: lcd_run_ext2_t.depth_path != NULL (below).  At the writer stage, chunk by chunk in plan order, every chunk's lcd_chunk_depth with its
+ * final haplotypes; with depth_window = W > 0 its rows go through lcd_depth_windows.  The writer always holds a chunk's last row back: per base it and the next
+ * chunk's first row become one row when the contig is equal, held.end + 1 == next.beg and the three depths are equal; window rows are added into one when the
+ * contig and the window index are equal and held.end + 1 == next.beg; otherwise the held row is written as it is.  A track without rows still gets its header
+ * line.  It works with or without an alignment output and beside mods_path.  Refused with -4 before any file is created: an empty path or "-", a window outside
+ * 0 ... 2^30, depth_path equal to mods_path.  The file is removed when the run fails.  *depth_stats: the sums over the chunks (n_rows: the data lines
+ * written), filled only by a run that succeeds. */
 /* The table of a whole run: lcd_call_files_ext2 == lcd_call_files_ext with one more struct, lcd_run_ext2_t, whose FIRST member is its own size (sizeof as the
  * caller compiled it): members behind `size` bytes read as zero, so the struct can grow without another export; a size that does not reach `mods_path` is -4.
  * lcd_call_files_ext is the call with ext2 == NULL.  mods_path != NULL: at the writer stage, window by window and chunk by chunk in plan order, every chunk's
@@ -1464,6 +1513,7 @@ int lcd_mods_format(int n_rows, const int64_t *pos, const char *strand, const ui
 typedef struct lcd_run_ext2_t {
     size_t size;
     const char *mods_path; int mods_code, mods_threshold, mods_combine_strands, reserved; lcd_mods_stats_t *mods_stats;
+    const char *depth_path; int depth_window, depth_skip_dels; lcd_depth_stats_t *depth_stats;      /* the depth track of the run (below); added at the end */
 } lcd_run_ext2_t;
 int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
                         const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2);

@@ -269,6 +269,19 @@ class LcdModsStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in MODS_STAT_COUNTERS] + [(n, C.c_double) for n in ("ms_site_map", "ms_pileup", "ms_compact")]
 
 
+class LcdDepthOpt(C.Structure):
+    """lcd_depth_opt_t: the options of lcd_chunk_depth (window: the drivers' window rule, not read by the chunk call)"""
+    _fields_ = [("skip_dels", C.c_int), ("window", C.c_int), ("reserved", C.c_int * 2)]
+
+
+DEPTH_STAT_COUNTERS = ("n_records", "n_no_cigar", "n_cg", "n_no_overlap", "n_intervals")
+
+
+class LcdDepthStats(C.Structure):
+    """lcd_depth_stats_t: the records and their intervals, the covered bases per haplotype, the rows, and the wall-clock split of the call"""
+    _fields_ = [(n, C.c_int64) for n in DEPTH_STAT_COUNTERS] + [("bases", C.c_int64 * 3), ("n_rows", C.c_int64), ("ms_mark", C.c_double), ("ms_rows", C.c_double)]
+
+
 class LcdRefineStats(C.Structure):
     """lcd_refine_stats_t: what lcd_chunk_refine_records did to the records it wrote"""
     _fields_ = [(n, C.c_int64) for n in ("n_records", "n_kept", "n_refined", "n_identical", "n_unrefined", "n_pos_moved", "n_no_digars", "n_qlen_mismatch", "n_bad_pos",
@@ -314,7 +327,8 @@ class LcdRunOut(C.Structure):
 class LcdRunExt2(C.Structure):
     """lcd_run_ext2_t: the options of lcd_call_files_ext2; `size` comes first and is sizeof of the struct as the caller knows it"""
     _fields_ = [("size", C.c_size_t), ("mods_path", C.c_char_p), ("mods_code", C.c_int), ("mods_threshold", C.c_int), ("mods_combine_strands", C.c_int), ("reserved", C.c_int),
-                ("mods_stats", C.POINTER(LcdModsStats))]
+                ("mods_stats", C.POINTER(LcdModsStats)),
+                ("depth_path", C.c_char_p), ("depth_window", C.c_int), ("depth_skip_dels", C.c_int), ("depth_stats", C.POINTER(LcdDepthStats))]
 
 
 class LcdRunExt(C.Structure):
@@ -375,6 +389,7 @@ EXPORTS = [
     "lcd_sam_names_create", "lcd_sam_names_free", "lcd_tagged_to_sam", "lcd_records_to_sam", "lcd_sam_text_size", "lcd_sam_text_dev_ptr", "lcd_sam_text_to_host", "lcd_sam_text_free",
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
     "lcd_mods_opt_default", "lcd_mods_opt_check", "lcd_chunk_mod_pileup", "lcd_mods_n_rows", "lcd_mods_rows_to_host", "lcd_mods_free", "lcd_mods_combine_rows", "lcd_mods_format", "lcd_call_files_ext2", "lcd_call_bam_regions_ext2",
+    "lcd_depth_opt_default", "lcd_depth_opt_check", "lcd_chunk_depth", "lcd_depth_n_rows", "lcd_depth_rows_to_host", "lcd_depth_free", "lcd_depth_tile", "lcd_depth_windows", "lcd_depth_format",
 ]
 
 
@@ -643,6 +658,18 @@ def load_library():
     lib.lcd_call_files_ext2.argtypes = list(lib.lcd_call_files_ext.argtypes) + [C.POINTER(LcdRunExt2)]
     lib.lcd_call_bam_regions_ext2.argtypes = list(lib.lcd_call_bam_regions.argtypes) + [C.POINTER(LcdRunExt2)]
     lib.lcd_mods_free.restype = None
+    lib.lcd_depth_opt_default.argtypes = [C.POINTER(LcdDepthOpt)]
+    lib.lcd_depth_opt_default.restype = None
+    lib.lcd_depth_opt_check.argtypes = [C.POINTER(LcdDepthOpt)]
+    lib.lcd_chunk_depth.argtypes = [C.c_void_p, i32p, C.POINTER(LcdDepthOpt), C.POINTER(LcdDepthStats)]
+    lib.lcd_chunk_depth.restype = C.c_void_p
+    lib.lcd_depth_n_rows.argtypes = [C.c_void_p]
+    lib.lcd_depth_rows_to_host.argtypes = [C.c_void_p, i64p_m, i64p_m, u32p]
+    lib.lcd_depth_free.argtypes = [C.c_void_p]
+    lib.lcd_depth_free.restype = None
+    lib.lcd_depth_tile.argtypes = []
+    lib.lcd_depth_windows.argtypes = [C.c_int, i64p_m, i64p_m, u32p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    lib.lcd_depth_format.argtypes = [C.c_int, i64p_m, i64p_m, u32p, C.POINTER(C.c_uint64), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
     lib.lcd_mods_combine_rows.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p]
     lib.lcd_mods_format.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     _lib = lib

@@ -724,6 +724,30 @@ class DeviceChunk:
         finally:
             lib.lcd_mods_free(h)
 
+    def depth(self, haps, skip_dels=False):
+        """lcd_chunk_depth: the per-haplotype depth track of the chunk's region from the CIGARs of its kept records.  haps: 0 / 1 / 2 per kept read.
+        -> (rows [(beg, end, (depth of haplotype 0, 1, 2))] that tile the region in position order, stats dict; "bases" is a list of three)"""
+        from ._lib import LcdDepthOpt, LcdDepthStats
+        lib = self.lib
+        hp = np.ascontiguousarray(haps, np.int32)
+        if len(hp) < self.n:
+            raise ValueError("depth: haps shorter than the chunk's reads")
+        hp = np.concatenate([hp, np.zeros(1, np.int32)])
+        o = LcdDepthOpt(); lib.lcd_depth_opt_default(C.byref(o))
+        o.skip_dels = int(bool(skip_dels))
+        st = LcdDepthStats()
+        h = lib.lcd_chunk_depth(self.h, hp.ctypes.data_as(i32p), C.byref(o), C.byref(st))
+        if not h:
+            raise LcdError("lcd_chunk_depth failed: " + lib.lcd_last_error().decode())
+        try:
+            n = int(lib.lcd_depth_n_rows(h))
+            beg = np.zeros(max(n, 1), np.int64); end = np.zeros(max(n, 1), np.int64); dep = np.zeros(3 * max(n, 1), np.uint32)
+            check(lib.lcd_depth_rows_to_host(h, beg.ctypes.data_as(C.POINTER(C.c_int64)), end.ctypes.data_as(C.POINTER(C.c_int64)), dep.ctypes.data_as(C.POINTER(C.c_uint32))), lib)
+            rows = [(int(beg[k]), int(end[k]), tuple(int(x) for x in dep[3 * k:3 * k + 3])) for k in range(n)]
+            return rows, _depth_stats(st)
+        finally:
+            lib.lcd_depth_free(h)
+
     def read_info(self):
         n = self.n
         st = np.zeros(n, np.int32); beg = np.zeros(n, np.int64); end = np.zeros(n, np.int64); nc = np.zeros(n, np.int32); nd = np.zeros(n, np.int32)
@@ -1734,6 +1758,61 @@ def chunk_mod_pileup(chunk, haps, ref, ref_beg, ref_end, code="m", threshold=204
     return chunk.mod_pileup(haps, ref, ref_beg, ref_end, code, threshold, combine_strands)
 
 
+def _depth_stats(st):
+    return {k: (list(getattr(st, k)) if k == "bases" else getattr(st, k)) for k, _t in st._fields_}
+
+
+def chunk_depth(chunk, haps, skip_dels=False):
+    """DeviceChunk.depth"""
+    return chunk.depth(haps, skip_dels)
+
+
+def depth_tile():
+    """lcd_depth_tile (host only): the positions per workgroup of the depth track's row launches"""
+    return int(load_library().lcd_depth_tile())
+
+
+def _depth_arrays(rows):
+    n = len(rows)
+    beg = np.array([r[0] for r in rows] + [0], np.int64); end = np.array([r[1] for r in rows] + [0], np.int64)
+    return n, beg, end, beg.ctypes.data_as(C.POINTER(C.c_int64)), end.ctypes.data_as(C.POINTER(C.c_int64))
+
+
+def depth_windows(rows, window):
+    """lcd_depth_windows (host only): rows [(beg, end, three depths)] that tile a span, in order -> the windows' rows [(beg, end, three sums of depth x positions)];
+    window k of width `window` is [k * window + 1, (k + 1) * window]"""
+    lib = load_library()
+    n, beg, end, bp, ep = _depth_arrays(rows)
+    dep = np.array([x for r in rows for x in r[2]] + [0] * 3, np.uint32)
+    wb, we, ws = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    m = lib.lcd_depth_windows(n, bp, ep, dep.ctypes.data_as(C.POINTER(C.c_uint32)), int(window), C.byref(wb), C.byref(we), C.byref(ws))
+    if m < 0:       # (host-only code: it sets no error text)
+        raise LcdError(f"lcd_depth_windows: error {m}: a window below 1, or rows that are not in order and contiguous")
+    try:
+        b = np.ctypeslib.as_array(C.cast(wb, C.POINTER(C.c_int64)), (m + 1,)); e = np.ctypeslib.as_array(C.cast(we, C.POINTER(C.c_int64)), (m + 1,))
+        v = np.ctypeslib.as_array(C.cast(ws, C.POINTER(C.c_uint64)), (3 * m + 3,))
+        return [(int(b[k]), int(e[k]), tuple(int(x) for x in v[3 * k:3 * k + 3])) for k in range(m)]
+    finally:
+        _libc.free(wb); _libc.free(we); _libc.free(ws)
+
+
+def depth_format(rows, chrom, windows=False, with_header=False):
+    """lcd_depth_format (host only): the track's text for rows [(beg, end, three values)]; windows=True: the values are the 64-bit sums of depth_windows"""
+    lib = load_library()
+    n, beg, end, bp, ep = _depth_arrays(rows)
+    vals = [x for r in rows for x in r[2]] + [0] * 3
+    dep = np.array(vals, np.uint64 if windows else np.uint32)
+    text = C.c_void_p()
+    rc = lib.lcd_depth_format(n, bp, ep, None if windows else dep.ctypes.data_as(C.POINTER(C.c_uint32)), dep.ctypes.data_as(C.POINTER(C.c_uint64)) if windows else None,
+                              _enc(chrom), int(bool(with_header)), C.byref(text))
+    if rc < 0:
+        raise LcdError(f"lcd_depth_format: error {rc}: a row with beg < 1 or end < beg")
+    try:
+        return C.string_at(text).decode()
+    finally:
+        _libc.free(text)
+
+
 def mods_combine_rows(rows):
     """lcd_mods_combine_rows (host only): rows by position and strand -> the combined rows, keyed by the position of the CpG's C, strand '.'"""
     lib = load_library()
@@ -1883,14 +1962,16 @@ def write_phased_sam(in_bam_path, chunks, path, pg_line=None, sort_output=False,
                 refine={k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}, sam={k: getattr(sst, k) for k, _t in LcdSamStats._fields_})
 
 
-def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False, mods=None):
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False, mods=None, depth=None):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
     bam_out = dict(path[, pg_line, block_payload]): the phased alignment file is written too; the result gets "bam_out" = the counters and stage times of
     lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
     te_fasta= / rnames=: lcd_run_opt_t.fields (as chunks_call).  refine=True (with bam_out; not with te_fasta / rnames): lcd_aln_opt_t.refine -- the records are
     written with the alignments the call arrived at; the result gains "refine" = lcd_refine_stats_t's fields.
     mods = dict(path[, code, threshold, combine_strands]) (lcd_call_bam_regions_ext2): the contig's methylation table goes to path, every region's chunk piled up
-    with the haplotypes the result returns for it; the result gains "mods" = the sums of lcd_mods_stats_t"""
+    with the haplotypes the result returns for it; the result gains "mods" = the sums of lcd_mods_stats_t
+    depth = dict(path[, window, skip_dels]): the contig's per-haplotype depth track goes to path (per base, or per window of `window` positions), from the records
+    as stored and the same haplotypes; the result gains "depth" = the sums of lcd_depth_stats_t"""
     from ._lib import LCD_ALN_BAM, LcdAlnOpt, LcdBamOut, LcdCallChunk, LcdRefineStats, LcdRunOpt, LcdRunOut, LcdVar1
     vf, fo = _vcf_fields(te_fasta, rnames)
     if refine and vf is not None:
@@ -1911,9 +1992,9 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     out = LcdRunOut(fields_out=C.pointer(fo) if vf is not None else None, refine_stats=C.pointer(rst) if rst is not None else None)
     args = (_enc(bam_path), _enc(bai_path), _enc(fasta_path), _enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
             C.byref(text), C.byref(bo) if bo is not None else None, C.byref(ro), C.byref(out))
-    mst = None
-    if mods is not None:
-        ext2, mst = _run_ext2(mods)
+    mst = dst = None
+    if mods is not None or depth is not None:
+        ext2, mst, dst = _run_ext2(mods, depth)
         rc = lib.lcd_call_bam_regions_ext2(*args, C.byref(ext2))
     else:
         rc = lib.lcd_call_bam_regions(*args)
@@ -1925,6 +2006,8 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
         res = _fields_result(lib, res, vf, fo)
     if mst is not None:
         res["mods"] = {k: getattr(mst, k) for k, _t in mst._fields_}
+    if dst is not None:
+        res["depth"] = _depth_stats(dst)
     if bo is None:
         return res
     res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
@@ -1934,13 +2017,21 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     return res
 
 
-def _run_ext2(mods):
-    """mods = dict(path[, code, threshold, combine_strands]) -> (lcd_run_ext2_t, the lcd_mods_stats_t it points to)"""
-    from ._lib import LcdModsStats, LcdRunExt2
-    mst = LcdModsStats()
-    code = mods.get("code", "m")
-    return LcdRunExt2(size=C.sizeof(LcdRunExt2), mods_path=_enc(mods["path"]), mods_code=ord(code) if isinstance(code, str) and len(code) == 1 else -1,
-                      mods_threshold=int(mods.get("threshold", 204)), mods_combine_strands=int(bool(mods.get("combine_strands", False))), mods_stats=C.pointer(mst)), mst
+def _run_ext2(mods, depth=None):
+    """mods = dict(path[, code, threshold, combine_strands]) | None, depth = dict(path[, window, skip_dels]) | None -> (lcd_run_ext2_t, the lcd_mods_stats_t and the
+    lcd_depth_stats_t it points to; None for the one that was not asked for)"""
+    from ._lib import LcdDepthStats, LcdModsStats, LcdRunExt2
+    x = LcdRunExt2(size=C.sizeof(LcdRunExt2))
+    mst = dst = None
+    if mods is not None:
+        mst = LcdModsStats()
+        code = mods.get("code", "m")
+        x.mods_path, x.mods_code = _enc(mods["path"]), ord(code) if isinstance(code, str) and len(code) == 1 else -1
+        x.mods_threshold, x.mods_combine_strands, x.mods_stats = int(mods.get("threshold", 204)), int(bool(mods.get("combine_strands", False))), C.pointer(mst)
+    if depth is not None:
+        dst = LcdDepthStats()
+        x.depth_path, x.depth_window, x.depth_skip_dels, x.depth_stats = _enc(depth["path"]), int(depth.get("window", 0)), int(bool(depth.get("skip_dels", False))), C.pointer(dst)
+    return x, mst, dst
 
 
 # ---------------- a whole BAM in one call (lcd_call_files and what it is composed of) ----------------
@@ -2068,7 +2159,7 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None, mods=None):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None, mods=None, depth=None):
     """lcd_call_files with the job's one file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[,
     pg_line, block_payload]), the phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads,
     n_passes, flip_hap, flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -2130,14 +2221,16 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     ro = LcdRunOpt(idx=ptr(io), fields=ptr(vf), aln=C.pointer(ao))
     out = LcdRunOut(idx_stats=ptr(ist), n_reads_per_file=C.cast(per_file, C.POINTER(C.c_int64)) if _inputs is not None else None, fields_out=ptr(fo), refine_stats=ptr(rst), sam_stats=ptr(sst))
     args = (C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
-    ext, mst = None, None
+    ext, mst, dst = None, None, None
     if vio is not None:
         from ._lib import LcdRunExt
         ext = LcdRunExt(vcf_idx=C.pointer(vio), vcf_idx_stats=C.pointer(vist))
-    if mods is not None:
+    if mods is not None or depth is not None:
         # mods = dict(path[, code "m" | "h", threshold 128 ... 255, combine_strands]): the per-haplotype CpG methylation table (lcd_run_ext2_t); the result gains
         # "mods" = the sums of lcd_mods_stats_t over the chunks (n_rows: the data lines written)
-        ext2, mst = _run_ext2(mods)
+        # depth = dict(path[, window 0 ... 2^30, skip_dels]) (the command line's --depth / --depth-window / --depth-skip-dels): the per-haplotype depth track, per
+        # base or per window; the result gains "depth" = the sums of lcd_depth_stats_t over the chunks (n_rows: the data lines written)
+        ext2, mst, dst = _run_ext2(mods, depth)
         rc = lib.lcd_call_files_ext2(*args, C.byref(ext) if ext is not None else None, C.byref(ext2))
     elif ext is not None:
         rc = lib.lcd_call_files_ext(*args, C.byref(ext))
@@ -2167,6 +2260,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["vcf_index"] = _vcf_index_stats(vist)
         if mst is not None:
             res["mods"] = {k: getattr(mst, k) for k, _t in mst._fields_}
+        if dst is not None:
+            res["depth"] = _depth_stats(dst)
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))

@@ -16,13 +16,13 @@ REFUSED = {
     "-m": "-m/--methylation is not supported (the reference reads no MM/ML tag behind it): ask for the per-haplotype CpG methylation table with --mods FILE",
     "--methylation": "-m/--methylation is not supported (the reference reads no MM/ML tag behind it): ask for the per-haplotype CpG methylation table with --mods FILE",
 }
-FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam", "--mod-combine-strands"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam", "--mod-combine-strands", "--depth-skip-dels"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
           "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam", "--vcf-index": "vcf_index",
-          "--mods": "mods", "--mod-code": "mod_code", "--mod-threshold": "mod_threshold"}
+          "--mods": "mods", "--mod-code": "mod_code", "--mod-threshold": "mod_threshold", "--depth": "depth", "--depth-window": "depth_window"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli index [--csi] in.vcf.gz [out]   build in.vcf.gz.tbi (--csi: .csi) on the device; BAM or VCF is decided by the file's content, not its name
@@ -44,6 +44,12 @@ Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z 
                         works with or without -b / --sam
           --mod-code m|h [m]   --mod-threshold INT [204] (128 ... 255: a call counts when its probability byte, or that of no modification, reaches it)
           --mod-combine-strands   one line per CpG: the '-' site is added to the '+' site, strand "."
+          --depth FILE   the per-haplotype depth track, counted on the device from the records as stored in the input (--refine-bam does not change it) with the
+                        haplotypes of this run: one BED line per run of equal depth (chrom start end depth_all depth_h1 depth_h2 depth_unassigned); M, = and X
+                        cover, D covers, N does not; works with or without -b / --sam and beside --mods
+          --depth-window INT [0]   one line per window of INT positions ([k INT + 1, (k + 1) INT] on the contig, cut to the called regions) with the sums of
+                        depth x positions (bases_all bases_h1 bases_h2 bases_unassigned); 0: per base; at most 2^30
+          --depth-skip-dels   a D does not cover
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
 Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched; --sam gets no index);
                          it does not index the VCF: that is --vcf-index
@@ -116,6 +122,23 @@ def mods_option(o):
     if not 128 <= thr <= 255:
         return "--mod-threshold must be 128 ... 255"
     return dict(path=o["mods"], code=o.get("mod_code", "m"), threshold=thr, combine_strands="--mod-combine-strands" in o["flags"])
+
+
+def depth_option(o):
+    """--depth FILE / --depth-window INT / --depth-skip-dels -> the keyword depth= of align.call_file (None without --depth), or the refusal's text"""
+    if "depth" not in o:
+        return "--depth-window / --depth-skip-dels need --depth FILE" if "depth_window" in o or "--depth-skip-dels" in o["flags"] else None
+    if o["depth"] in ("", "-"):
+        return "--depth needs a file: the track does not go to stdout"
+    try:
+        win = int(o.get("depth_window", 0))
+    except ValueError:
+        return "--depth-window is not a number"
+    if not 0 <= win <= 1 << 30:
+        return "--depth-window must be 0 ... 2^30"
+    if o["depth"] == o.get("mods"):
+        return "--depth and --mods name one file"
+    return dict(path=o["depth"], window=win, skip_dels="--depth-skip-dels" in o["flags"])
 
 
 def input_bams(o, bam):
@@ -221,6 +244,9 @@ def main(argv=None):
     mods = mods_option(o)
     if isinstance(mods, str):
         return refuse(mods)
+    depth = depth_option(o)
+    if isinstance(depth, str):
+        return refuse(depth)
     from . import align
     is_ont = 1 if "--ont" in o["flags"] else 0
     clean, opt, pass_, call = {}, {}, {}, {}
@@ -260,7 +286,8 @@ def main(argv=None):
                              no_vcf_header=1 if o["flags"] & {"-H", "--no-vcf-header"} else 0, sample_name=o.get("sample_name"), cmdline=cmdline, bam_out=bam_out, cfg=cfg,
                              index=(dict(build_missing_bai=1, build_missing_fai=1) if sam else True) if "--make-index" in o["flags"] else None,
                              **(dict(aln_format="sam") if sam else {}), **(dict(refine=True) if refine else vcf_fields(o)),
-                             **(dict(vcf_index=o["vcf_index"]) if "vcf_index" in o else {}), **(dict(mods=mods) if mods is not None else {}))
+                             **(dict(vcf_index=o["vcf_index"]) if "vcf_index" in o else {}), **(dict(mods=mods) if mods is not None else {}),
+                             **(dict(depth=depth) if depth is not None else {}))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
@@ -275,6 +302,7 @@ def main(argv=None):
                      + (f"{st['n_mei_lines']} MEI records, " if "n_mei_lines" in st else "")
                      + (f"{st['refine']['n_refined']} refined / {st['refine']['n_unrefined']} unrefined records, " if refine and bam_out is not None else "")
                      + (f"{st['bam_out']['bytes_file']} bytes of SAM text, " if sam else "") + (f"{st['mods']['n_rows']} methylation rows, " if mods is not None else "")
+                     + (f"{st['depth']['n_rows']} depth rows, " if depth is not None else "")
                      + f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 

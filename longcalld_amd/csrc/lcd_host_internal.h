@@ -214,6 +214,27 @@ private:
     int put(int n, const int64_t *pos, const char *strand, const uint32_t *cnt, const char *chrom);
     int flush_held();
 };
+// the device buffers of lcd_chunk_depth (the difference array, the tile partials, the rows): kept by the sink of a driver run, as ModsScratch is
+struct DepthScratch { DevBuf d_jobs, d_diff, d_parts, d_small, d_rows; };
+lcd_depth_t *depth_core(const lcd_chunk_t *c, const int *haps, const lcd_depth_opt_t *opt, lcd_depth_stats_t *stats, DepthScratch &S);
+// the depth track of a driver run (lcd_run_ext2_t.depth_path; lcd_depth.cpp): the refusals, the file, every chunk's rows in plan order (through the window rule
+// with depth_window), the sums of the statistics and the last row of the chunk before, ALWAYS held back until the next chunk's first row is known: the two join
+// by the seam rule of include/lcd_hotpath.h, or the held row is written as it is.  One thread at a time.
+struct DepthSink {
+    FILE *f = nullptr; std::string path; lcd_depth_opt_t opt; lcd_depth_stats_t sum; lcd_depth_stats_t *stats_out = nullptr;
+    bool head = false, held = false; std::string held_chrom; int64_t held_beg = 0, held_end = 0; uint64_t held_val[3];
+    DepthScratch scratch;    // (freed with the sink)
+    static int parse(const std::string &W, const lcd_run_ext2_t &x2);          // x2 as ModsSink::parse left it; -4 before anything is created
+    int open(const std::string &W, const lcd_run_ext2_t &x2);                  // creates the file
+    int chunk(const lcd_chunk_t *handle, const lcd_first_chunk_t &x, const char *chrom);
+    int finish(bool ok);     // ok: the held row, the header of an empty track, close, *stats_out; else (or when that fails): close and remove.  0 or -30
+    bool active() const { return f != nullptr; }
+    ~DepthSink() { if (f) { fclose(f); remove(path.c_str()); } }
+    DepthSink() = default; DepthSink(const DepthSink &) = delete; DepthSink &operator=(const DepthSink &) = delete;
+private:
+    int put(int n, const int64_t *beg, const int64_t *end, const uint64_t *val, const char *chrom);      // val: depths, or the windows' sums
+    int flush_held();
+};
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
 } // namespace lcd_internal

@@ -45,6 +45,12 @@ void lcd_launch_bam_sam_emit(const BamSamIn &in, const unsigned long long *text_
 void lcd_launch_mods_sites(const ModsIn &in, int *flag, long long n_pos, hipStream_t st);
 void lcd_launch_mods_pileup(const ModsIn &in, hipStream_t st);
 void lcd_launch_mods_compact(const ModsIn &in, long long n_pos, ModsRow *rows, int *n_rows, hipStream_t st);
+// depth_kernel.hip: the cover intervals of the kept records as a difference array (one wavefront per record), then the maximal runs of equal depth as rows in
+// position order: per tile the plane sums and run heads, the scan of those partials by one workgroup (*n_rows: the total), per tile again the rows
+void lcd_launch_depth_mark(const DepthIn &in, hipStream_t st);
+void lcd_launch_depth_tiles(const DepthIn &in, DepthPart *parts, hipStream_t st);
+void lcd_launch_depth_scan(DepthPart *parts, long long n_tiles, int *n_rows, hipStream_t st);
+void lcd_launch_depth_rows(const DepthIn &in, const DepthPart *parts, DepthRow *rows, int cap, hipStream_t st);     // cap: the entries of rows (*n_rows of the scan)
 // bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
 // counters; compact: scan of the workgroups' run heads + the dense chunk list)
 void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);

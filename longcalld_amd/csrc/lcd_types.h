@@ -303,6 +303,16 @@ struct ModsJob { uint64_t src, cls; uint32_t len, cap; int hap, pad; };
 // (the exclusive scan of the site flags); tab: nine counters per site (hap-major: mod, canon, filtered); stats: twelve counters in the order of lcd_mods_stats_t
 struct ModsIn { const ModsJob *jobs; const uint8_t *ref; const int *site_idx; unsigned *tab; unsigned long long *stats; long long ref_beg, ref_end, reg_beg, reg_end; int n_jobs, code, threshold, pad; };
 struct ModsRow { long long pos; int strand /* 1 '+', 2 '-' */, pad; unsigned count[9]; unsigned pad2; };
+// ---------------- the per-haplotype depth track (depth_kernel.hip) ----------------
+#define LCD_DEPTH_TILE 1024   // positions per workgroup of the row kernels (256 threads x 4 positions); lcd_depth_tile() gives it to the tests
+// one kept record ([src, src + len): its block_size word and body; cap: the l_seq the loader took from it) with its read's haplotype 0 / 1 / 2
+struct DepthJob { uint64_t src; uint32_t len, cap; int hap, pad; };
+// diff: three planes (haplotype 0, 1, 2) of `pitch` ints each, zeroed: diff[h * pitch + (p - reg_beg)] = records of h whose cover begins at p minus those whose
+// cover ended at p - 1; pitch is n_pos rounded up to whole tiles, so a tile is read without a bound.  stats: nine counters in the order of lcd_depth_stats_t
+struct DepthIn { const DepthJob *jobs; int *diff; unsigned long long *stats; long long reg_beg, reg_end, n_pos, pitch; int n_jobs, skip_dels; };
+// a tile's partial: the three plane sums and the number of run heads; after the scan: the sums of the tiles in front of it
+struct DepthPart { int s[3], heads; };
+struct DepthRow { long long beg; unsigned d[3], pad; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;
