@@ -2244,7 +2244,83 @@ __device__ __forceinline__ int lean_wlane(const int val, const int l, int old) {
 // uniform band arithmetic (and everything derived from it: window base, offsets, loop-carried state) into VGPRs
 __device__ __forceinline__ int smax(const int a, const int b) { int r; asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(__builtin_amdgcn_readfirstlane(a)), "s"(__builtin_amdgcn_readfirstlane(b)) : "scc"); return r; }
 __device__ __forceinline__ int smin(const int a, const int b) { int r; asm("s_min_i32 %0, %1, %2" : "=s"(r) : "s"(__builtin_amdgcn_readfirstlane(a)), "s"(__builtin_amdgcn_readfirstlane(b)) : "scc"); return r; }
+// A comment line in the device assembly that names a place in a plain-row loop: tools/row_issue_slots.py counts the instructions between them.  No instruction.
+#define LCD_ROW_MARK(name) asm volatile("; LCD_ROW_MARK " name)
 __device__ __forceinline__ int dpp_shl1(const int old, const int v) { return __builtin_amdgcn_update_dpp(old, v, 0x130, 0xf, 0xf, false); } // lane i <- lane i + 1 (lane 63 keeps `old`)
+// The scans of a plain one-cell-per-lane row in one statement: the biased gap terms a1 = hp + c1, a2 = hp + c2, their EXCLUSIVE prefix maxima over the lanes
+// (pf1, pf2; 0 = nothing to the left) and, for the adaptive band, the inclusive maximum of hp itself (hb).  a1 / a2 are positive wherever a cell holds a real value
+// (the bias of 2^29 in c1 / c2) and negative in a masked lane, so 0 is an identity of their maxima: the first scan step is written out of place with the bound
+// control on, and needs no copy in front of it (hb is unbiased and keeps its copy).  Every DPP read is at least two instructions behind the write of its
+// source -- the terms are made here, the exclusive shifts follow the last step of the third chain -- so no statement of this block is a pad.
+__device__ __forceinline__ void plain1_scan3(const int hp, const int c1, const int c2, int &a1, int &a2, int &pf1, int &pf2, int &hb) {
+    asm volatile(
+        "v_add_u32 %0, %5, %6\n\t"
+        "v_add_u32 %1, %5, %7\n\t"
+        "v_mov_b32 %4, %5\n\t"
+        "v_max_i32_dpp %2, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_max_i32_dpp %3, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_max_i32_dpp %4, %4, %4 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %4, %4, %4 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %4, %4, %4 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %4, %4, %4 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "v_max_i32_dpp %4, %4, %4 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "v_max_i32_dpp %4, %4, %4 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "v_mov_b32_dpp %2, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_mov_b32_dpp %3, %3 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(a1), "=&v"(a2), "=&v"(pf1), "=&v"(pf2), "=&v"(hb) : "v"(hp), "v"(c1), "v"(c2));
+}
+// ... and without the row maximum (certified intervals): two chains, so every step needs one pad for the second wait state of its DPP read
+__device__ __forceinline__ void plain1_scan2(const int hp, const int c1, const int c2, int &a1, int &a2, int &pf1, int &pf2) {
+    asm volatile(
+        "v_add_u32 %0, %4, %5\n\t"
+        "v_add_u32 %1, %4, %6\n\t"
+        "s_nop 0\n\t"
+        "v_max_i32_dpp %2, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_max_i32_dpp %3, %1, %1 row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "s_nop 0\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_shr:8 row_mask:0xf bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_max_i32_dpp %2, %2, %2 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "v_max_i32_dpp %3, %3, %3 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t"
+        "s_nop 0\n\t"
+        "v_mov_b32_dpp %2, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+        "v_mov_b32_dpp %3, %3 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+        : "=&v"(a1), "=&v"(a2), "=&v"(pf1), "=&v"(pf2) : "v"(hp), "v"(c1), "v"(c2));
+}
+// The H source of a cell's direction code, hp >= fm ? spk : (f1 == h ? (f2 == h ? 5 : 3) : 4): the three compares first, into their own mask registers, then
+// the three selects -- each select two instructions behind its compare.  Written compare / select / compare / select, as the compiler emits it, every select
+// waits two states for its mask (s_nop 1, three times per row).
+__device__ __forceinline__ int plain1_hsrc(const int f1, const int f2, const int h, const int hp, const int fm, const int spk) {
+    int hs; unsigned long long m1, m2;
+    asm("v_cmp_eq_u32 %1, %3, %5\n\t"
+        "v_cmp_eq_u32 %2, %4, %5\n\t"
+        "v_cmp_lt_i32 vcc, %6, %7\n\t"
+        "v_cndmask_b32_e64 %0, 3, 5, %1\n\t"
+        "v_cndmask_b32_e64 %0, 4, %0, %2\n\t"
+        "v_cndmask_b32_e32 %0, %8, %0, vcc"
+        : "=&v"(hs), "=&s"(m1), "=&s"(m2) : "v"(f2), "v"(f1), "v"(h), "v"(hp), "v"(fm), "v"(spk) : "vcc");
+    return hs;
+}
 template <int MODE, int C>
 __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsigned ring_, const unsigned sq1_, const unsigned pd_ /* 0xffffffff: none */, const LcdScoring sc_, const int w_,
                                                     const int bi_, const int ei_, const int rem_beg_, const uint8_t *seq_hbm_, const int qlen_, WinOut *wo_) {
@@ -2266,17 +2342,15 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
     if (qlen >= 65535) return -1; // (beg | end << 16 words)
     if (BANDED && (oe1 <= 0 || oe2 <= 0 || e1 < 0 || e2 < 0)) return -1; // (the row maximum is taken from Hpre: a horizontal gap must cost something)
     if (s_match < -32 || s_match > 31 || s_mism < -32 || s_mism > 31) return -1; // (the substitution score of a cell is a 6-bit field of a per-row scalar word, see `lut`)
-    // Substitution scores: the query cache holds 6 * min(base, 4), and a row's five scores (its node's base against A C G T N, + 32) are 6-bit fields of ONE scalar
-    // word picked per row: the cell's score is a single v_bfe_u32 (was two compares and two selects per cell, plus two moves of the row's match / mismatch into VGPRs)
-    unsigned lut4 = 0;
-    for (int q = 0; q < 5; ++q) lut4 |= 32u << (6 * q);
+    // Substitution scores: the query cache holds 6 * min(base, 4), and a row's five scores (its node's base against A C G T N) are SIGNED 6-bit fields of ONE scalar
+    // word picked per row: the cell's score is a single v_bfe_i32 (was two compares and two selects per cell, plus two moves of the row's match / mismatch into VGPRs;
+    // then an unsigned field biased by 32, which cost every plain row two scalar instructions for a second copy of its bonus with the bias taken off)
     unsigned lutb[4];
-    for (int v = 0; v < 4; ++v) { unsigned w_ = 32u << 24; for (int q = 0; q < 4; ++q) w_ |= (unsigned)(32 + (q == v ? s_match : s_mism)) << (6 * q); lutb[v] = usgpr(w_); }
-    lut4 = usgpr(lut4);
+    for (int v = 0; v < 4; ++v) { unsigned w_ = 0; for (int q = 0; q < 4; ++q) w_ |= ((unsigned)(q == v ? s_match : s_mism) & 63u) << (6 * q); lutb[v] = usgpr(w_); }
     // (the five words sit in lanes 0 - 4 of one register and a row takes its own by v_readlane: as a select chain on the scalar side the choice was three branches per row)
-    int lutv = (int)lut4;
+    int lutv = 0; // (lane 4: an N node scores 0 against every base, as every node does against an N of the read -- field 4 of the other words)
     for (int v = 0; v < 4; ++v) lutv = lean_wlane((int)lutb[v], v, lutv);
-    auto lut_of = [&](const int vb) -> unsigned { return (unsigned)LCD_RL(lutv, smin(vb, 4)); };
+    auto lut_of = [&](const int vb) -> int { return LCD_RL(lutv, vb); }; // (vb <= 4: load_plan clamps the base field of the plan word, once per 64 rows)
     const int QB = (qlen + 12 + 15) & ~15;
     const bool r16 = FIXED && usgpr(g.ring16) != 0; // (16-bit ring values: lds_stc16 / lds_ldc16)
     const unsigned RB = r16 ? 2u : 4u;
@@ -2349,7 +2423,7 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
     unsigned cused_w0 = 0; // code offset of the metadata window's first row: the rows' offsets are made from it and the rows' intervals when the window is flushed
     int wbase = bi + 1;
     unsigned long long np_mask = ~0ull; // rows of the plan window that are NOT plain by their plan word (several / far / no predecessors, spilled, unreachable, past the end)
-    // packed plan word: #preds (8 bits, 255 = more) | base << 8 | spill << 11 | unreachable << 12 | backbone << 13 | bonus0 << 14 | bonus1 << 19
+    // packed plan word: #preds (8 bits, 255 = more) | min(base, 4) << 8 | spill << 11 | unreachable << 12 | backbone << 13 | bonus0 << 14 | bonus1 << 19
     auto load_plan = [&](const int base) {
         const int ri = base + lane;
         w_pk = 1 << 12;
@@ -2362,15 +2436,17 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
             if (cnt > 1) { w_pi1 = glb_ld(g.pl_pidx + s0 + 1); b1 = glb_ld(g.pl_bonus + s0 + 1); }
             const int rem = glb_ld(g.pl_rem + ri);
             w_x = FIXED ? glb_ld(hull + ri) : rem;
-            w_pk = imin(cnt, 255) | (glb_ld_u8(g.pl_base + ri) << 8) | ((glb_ld_u8(g.imap + ri) & 2) << 10) | (rem == (1 << 30) ? 1 << 12 : 0)
+            w_pk = imin(cnt, 255) | (imin(glb_ld_u8(g.pl_base + ri), 4) << 8) | ((glb_ld_u8(g.imap + ri) & 2) << 10) | (rem == (1 << 30) ? 1 << 12 : 0)
                  | ((cnt == 1 && w_pi0 == ri - 1) ? 1 << 13 : 0) | (b0 << 14) | (b1 << 19);
         }
         LCD_PIN(w_pk); LCD_PIN(w_x); LCD_PIN(w_pi0); LCD_PIN(w_pi1); LCD_PIN(w_p0);
-        np_mask = __ballot((w_pk & 0x38ff) != 0x2001);
+        const bool np_ = (w_pk & 0x38ff) != 0x2001;
+        np_mask = __ballot(np_);
         // rows whose ring slot a general row may read: one of the next K rows is not plain by its plan word (the last K rows of a window: always)
         unsigned long long km = 0;
         for (int d = 1; d <= K; ++d) km |= (np_mask >> d) | (1ull << (64 - d));
         w_pk |= (int)((km >> lane) & 1ull) << 24; // (bit 24 of the plan word: keep this row's ring slot)
+        if (np_) w_pk |= (int)0x80000000u;        // (bit 31: not plain -- the one-cell rows' admission takes the word's sign as it is, once per 64 rows instead of an AND / XOR per row)
     };
     auto flush_meta = [&](const int base, const int n) { // rows base .. base + n - 1
         // (a row's cells follow the previous row's in HBM, padded to a multiple of four: its offset is a prefix sum over the window's intervals -- one scan per 64 rows
@@ -2396,6 +2472,7 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
     // per-lane constants: (cl + k) * e and -(o + (cl + k) * e)
     int bcle1 = cl * e1 + (1 << 29), bcle2 = cl * e2 + (1 << 29), nbcle1 = -bcle1 - (C == 1 ? o1 : 0), nbcle2 = -bcle2 - (C == 1 ? o2 : 0); // (the plain rows' biased gap prefixes)
     if constexpr (C <= 2) { LCD_PIN(bcle1); LCD_PIN(bcle2); LCD_PIN(nbcle1); LCD_PIN(nbcle2); } // (opaque: the compiler would re-derive them from cl * e and add the bias in an instruction of its own; the wider variants have no registers to spare for that)
+    const int row_code_max = imin(WIN, (qlen + CP) & ~(CP - 1)); // the most code bytes a plain row can take: its band lies inside the window and inside [0, qlen], padded to CP
     int idx = bi + 1;
     // (statistics builds, tools/ab_build.sh <name> -DLCD_X_ROWSTAT / -DLCD_X_PLANSTAT: plain / general row counts and the kinds of graph change per read through the
     //  LCD_CHAIN_TIMES dump's t_setup / t_bt columns; ticks of the plan-window refreshes through t_plan.  Never defined in the product build.)
@@ -2424,7 +2501,10 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
         // next row keep their floor (max3).  What differs from the clamped rows is the code of cells NO alignment reaches -- never read.
         // The ring slot (and its lane of slot metadata) is written only for rows a general row will look at: one of the next K rows is not plain by its plan word
         // (bit 24 of the plan word; a row that stops being plain at run time has one predecessor, the row before: flushed from the registers when the run ends).
-        if (pv_ok) {
+        // The code capacity is tested HERE, once per run, not per row: a run is at most the rest of the plan window (and of the graph), and a row of it at most
+        // row_code_max code bytes.  Without that much room no run is entered: the general rows take the rows one by one, with the same codes, and raise
+        // LCD_ERR_CELLS at the row that does not fit (cused <= code_cap: every row was tested before it was counted).  The eight-cell rows keep their per-row test.
+        if (pv_ok && (C >= 8 || code_cap - usgpr(cused) >= (unsigned)(row_code_max * imin(64 - wk, ei - idx)))) {
 #ifdef LCD_X_ROWSTAT
             const int idx0_ = idx;
 #endif
@@ -2439,27 +2519,37 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
                 // is the lane's own previous value, the cell above it one lane to the right (two in-place DPP moves, unconditionally: no branch on how the window
                 // moved, no register copies where two branches join), and the band [beg, end] drifts inside the 64 lanes (the general rows leave LCD_DIAG_SLACK
                 // columns to its left; a band that reaches a window edge ends the run).  Codes in HBM still start at the row's first column. ----
-                while (wk < 64) {
-                    const int pk = LCD_RL(w_pk, wk);
-                    if ((pk & 0x38ff) != 0x2001) break; // #preds == 1, not spilled, reachable, backbone
-                    const int xw = LCD_RL(w_x, wk);
-                    int beg, end;
+                // The loop is ROTATED and has ONE exit: a row is admitted before the loop and again at the bottom of every row, by one scalar word that is
+                // negative when the row is not a plain row of this run, so the back edge is a compare and a branch.  (As `while` with two `break`s the three exits met
+                // in a flag register -- three 64-bit moves and an XOR / AND / branch per row on top of the tests -- and with three branches at the bottom they still do.)
+                // The admission is branch-free: past the plan window it works on whatever v_readlane returns and is refused by its first term.  It computes the
+                // row's band INTO the carried registers (beside them, every row copied four registers back); what a refused row has left there is taken back
+                // after the run: the window by its own step, the band from the metadata window.  The code capacity is not among the tests: see above.
+                int pk = 0, xw = 0, adv = 0;
+                int beg = l_beg, end = l_end, wb = l_begc; // the row before; then the row at hand
+                const int wk0 = wk;
+                auto admit = [&]() -> int { // row wk from the row before: < 0 = not a plain row of this run
+                    pk = LCD_RL(w_pk, wk); // (bit 31: not plain by its plan word -- several / far / no predecessors, spilled, unreachable, past the end; see load_plan)
+                    xw = LCD_RL(w_x, wk);
+                    const int wb_ = wb;
                     if (BANDED) {
                         const int diag = qlen - xw;
-                        beg = smax(smax(smin(l_ml + 1, diag) - w, 0), l_beg);
-                        end = smin(smin(smax(l_mr + 1, diag) + w, qlen), l_end + 1);
+                        beg = smax(smax(smin(l_ml + 1, diag) - w, 0), beg);
+                        end = smin(smin(smax(l_mr + 1, diag) + w, qlen), end + 1);
                     } else { beg = xw & 65535; end = (int)((unsigned)xw >> 16); }
-                    const int adv = smin(beg - l_begc, 1); // (0 or 1: beg >= l_beg >= l_begc) the window follows the band's first column by one column per row (a band that jumps further leaves lanes idle on its left)
-                    const int wb = l_begc + adv;        // this row's window: lane = column - wb
+                    adv = smin(beg - wb_, 1); // (0 or 1: beg >= l_beg >= l_begc) the window follows the band's first column by one column per row (a band that jumps further leaves lanes idle on its left)
+                    wb = wb_ + adv;           // this row's window: lane = column - wb
+                    // (one test: each of the quantities is negative exactly when its condition fails -- past the plan window; not plain; empty band; an interval of
+                    //  MODE 2 that starts left of the window; band past the window's last lane.  The adaptive band never starts left of the row before)
+                    return (63 - wk) | pk | (end - beg) | (FIXED ? beg - wb_ : 0) | (WIN - 2 - (end - wb));
+                };
+                LCD_ROW_MARK("plain_c1 enter");
+                if (admit() >= 0) do {
+                    LCD_ROW_MARK("plain_c1 top");
                     const int lo = beg - wb, span = end - beg;
                     const int cw4 = (span + CP) & ~(CP - 1);
-                    // (one test: each of the four quantities is negative exactly when its condition fails -- empty band; an interval of MODE 2 that starts left of the
-                    //  window; band past the window's last lane; code capacity, which is below 2^32 - 16 so the difference fits a signed compare after the shift)
-                    if (((end - beg) | (FIXED ? beg - l_begc : 0) | (WIN - 2 - (end - wb)) | (l_cused + (unsigned)cw4 > code_cap ? -1 : 0)) < 0) break; // (the adaptive band never starts left of the row before)
                     const int vb = (pk >> 8) & 7, bz0 = (pk >> 14) & 31;
-                    const int s = (idx - bi) & KM;
-                    const unsigned lut = lut_of(vb);
-                    const int bzb = bz0 - 32; // (the score fields of `lut` are biased by 32)
+                    const int lut = lut_of(vb);
                     // Hand-over from the row before WITHOUT a branch (two branches that join cost a register copy per value) and without touching the execution mask:
                     // v_cndmask with a DPP source, the condition a scalar mask that is all ones or all zeros.  Window moved (adv): the cell above is one lane to the
                     // right -- E values shift left in place (lane 63 keeps its own old values: its column is never inside a band, end - wb <= WIN - 2, and is
@@ -2478,50 +2568,58 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
                     static_assert(LCD_GUARD == (int)0xc0000000, "the filler above is written as the inline constant -2.0f");
                     const unsigned q6 = (unsigned)q_c1;
                     q_n1 = lds_ld_u8((unsigned)lane + (sq1 + (unsigned)(wb + 1))); // the next row's byte if its window moves again (the usual case): a row of latency to arrive in
-                    const int sk = (int)__builtin_amdgcn_ubfe(lut, q6, 6u);
-                    const int nn = pvh[0] + sk + bzb;
+                    const int sk = __builtin_amdgcn_sbfe(lut, q6, 6u);
+                    const int nn = pvh[0] + sk + bz0;
                     const int uu = pva[0] + bz0, vv = pvb[0] + bz0;
                     const bool inb = (unsigned)(lane - lo) <= (unsigned)span;
                     const int m_ = imax(uu, vv);
                     int spk = nn >= m_ ? 0 : uu >= vv ? 1 : 2;
                     LCD_PIN(spk); // (made here: left to the code store at the end it keeps the old E values alive past their successors)
                     const int hp = inb ? imax(nn, m_) : LCD_GUARD; // masked once: the gap prefixes, the row maximum and H all take it from here
-                    const int a1 = hp + bcle1, a2 = hp + bcle2; // (relative to the window's first column: the row's own offset cancels in every comparison; + 2^29, see x1)
-                    int t1 = a1, t2 = a2;
+                    // a1 / a2 = hp + bcle: relative to the window's first column (the row's own offset cancels in every comparison), + 2^29.  pf1 / pf2: their exclusive
+                    // prefix maxima over the lanes.  The bias makes every real term positive and a masked one negative, so the 0 that the bound control puts where a
+                    // lane has nothing to its left stands for "nothing to the left" without a register set up for it (see plain1_scan3)
+                    int a1, a2, pf1, pf2;
                     int ml = 0, mr = 0;
                     if (BANDED) { // the row maximum and its leftmost / rightmost column, from Hpre (see scan_max3), in the same scan as the gap prefixes
-                        int hbs = hp;
-                        scan_max3(t1, t2, hbs);
+                        int hbs;
+                        plain1_scan3(hp, bcle1, bcle2, a1, a2, pf1, pf2, hbs);
                         const int wm = lane63(hbs);
                         const unsigned long long mk = __ballot(hp == wm); // (the row is not empty: its in-band cells are real values > the filler)
                         ml = wb + usgpr((int)__builtin_ctzll(mk)); mr = wb + usgpr(63 - (int)__builtin_clzll(mk));
-                    } else scan_max2(t1, t2);
-                    // exclusive prefix over the lanes.  The prefixes carry a bias of 2^29 (every real one is positive, a masked one negative), so the 0 that lane 0
-                    // gets from the shift's bound control stands for "nothing to the left" without a register set up for it
-                    const int pf1 = __builtin_amdgcn_update_dpp(0, t1, 0x138, 0xf, 0xf, true), pf2 = __builtin_amdgcn_update_dpp(0, t2, 0x138, 0xf, 0xf, true);
+                    } else plain1_scan2(hp, bcle1, bcle2, a1, a2, pf1, pf2);
                     const int f1 = pf1 + nbcle1, f2 = pf2 + nbcle2; // (the opening penalty is in the lane's constant)
                     const int fm = imax(f1, f2);
                     const int h = imax(hp, fm);
                     const int q1 = h - oe1, w1 = uu - e1, q2 = h - oe2, w2 = vv - e2;
                     const int eo1 = imax(imax(q1, w1), LCD_NEG), eo2 = imax(imax(q2, w2), LCD_NEG);
-                    const int fk = f1 == h ? (f2 == h ? 5 : 3) : 4;
-                    const int hs = hp >= fm ? spk : fk;
+                    const int hs = plain1_hsrc(f1, f2, h, hp, fm, spk);
                     unsigned fl = q2 >= w2 ? 1u : 0u; // O2, O1, Y2, Y1 pushed in this order = bits 6, 5, 4, 3 of the code
                     LCD_PUSH_GE(fl, q1, w1); LCD_PUSH_GT(fl, pf2, a2); LCD_PUSH_GT(fl, pf1, a1);
                     const unsigned code = (unsigned)hs | (fl << 3);
                     pvh[0] = inb ? h : LCD_GUARD; pva[0] = inb ? eo1 : LCD_GUARD; pvb[0] = inb ? eo2 : LCD_GUARD;
-                    const int be = beg | (end << 16);
+                    const int be = FIXED ? xw : beg | (end << 16); // (MODE 2: the table's word is the packed interval)
                     if (pk & (1 << 24)) {
+                        LCD_ROW_MARK("plain_c1 slot");
+                        const int s = (wbase + wk - bi) & KM;
                         ring_st3(ring + RB * (unsigned)(s * SLOTW), (wb + lane) & WM, pvh, pva, pvb);
                         m_be = lean_wlane(be, s, m_be); m_mm = lean_wlane(ml | (mr << 16), s, m_mm);
-                        pend = 0;
-                    } else pend = 1;
+                        LCD_ROW_MARK("plain_c1 slot end");
+                    }
                     if (inb) *(__attribute__((address_space(1))) uint8_t *)(g.code8 + (size_t)(l_cused + (unsigned)(lane - lo))) = (uint8_t)code;
                     r_be = lean_wlane(be, wk, r_be);
-                    l_begc = wb; l_beg = beg; l_end = end; l_ml = ml; l_mr = mr;
+                    l_ml = ml; l_mr = mr;
                     l_cused += (unsigned)cw4; run_cells += (unsigned)(span + 1);
-                    ++idx; ++wk;
+                    ++wk;
+                } while (admit() >= 0);
+                LCD_ROW_MARK("plain_c1 leave");
+                l_begc = wb - adv; // (the refused row's window step, taken back)
+                if (wk != wk0) { // ... and its band: the last row's is in the metadata window; whether that row went to its ring slot is in its plan word
+                    const int be_ = LCD_RL(r_be, wk - 1);
+                    l_beg = be_ & 65535; l_end = (int)((unsigned)be_ >> 16);
+                    pend = (LCD_RL(w_pk, wk - 1) >> 24 & 1) ^ 1;
                 }
+                idx = wbase + wk; // (the rows of a run are counted in the plan window alone)
             } else if constexpr (C >= 8) {
                 // ---- eight cells per lane (intervals of 257 - 508 columns: a handful of reads per submission, but the longest ones): the rows as they were before
                 // round 5 -- clamped, every row to its ring slot.  The leaner formulation below needs more registers at this width than the class has (30 scratch
@@ -2630,24 +2728,29 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
                 }
             } else {
                 if (!q_ok) { q_cur = q_of(pv_begc); q_nxt = q_of(pv_begc + C); q_ok = 1; }
-                while (wk < 64) {
-                    const int pk = LCD_RL(w_pk, wk);
-                    if ((pk & 0x38ff) != 0x2001) break; // #preds == 1, not spilled, reachable, backbone
-                    const int xw = LCD_RL(w_x, wk);
-                    int beg, end;
+                // (rotated, one exit, the band computed into the carried registers: as the one-cell rows above)
+                int pk = 0, xw = 0, sh = 0;
+                int beg = l_beg, end = l_end, begc = l_begc; // the row before; then the row at hand
+                const int wk0 = wk;
+                auto admit = [&]() -> int { // row wk from the row before: < 0 = not a plain row of this run
+                    pk = LCD_RL(w_pk, wk); // (bit 31: not plain by its plan word)
+                    xw = LCD_RL(w_x, wk);
+                    const int bc_ = begc;
                     if (BANDED) {
                         const int diag = qlen - xw;
-                        beg = smax(smax(smin(l_ml + 1, diag) - w, 0), l_beg);
-                        end = smin(smin(smax(l_mr + 1, diag) + w, qlen), l_end + 1);
+                        beg = smax(smax(smin(l_ml + 1, diag) - w, 0), beg);
+                        end = smin(smin(smax(l_mr + 1, diag) + w, qlen), end + 1);
                     } else { beg = xw & 65535; end = (int)((unsigned)xw >> 16); }
-                    const int begc = beg & CM;
-                    const int sh = begc - l_begc;
+                    begc = beg & CM;
+                    sh = begc - bc_;
+                    // (one test, as above: past the plan window; not plain; empty band; band past the window's last lane; a window that moves left, or by more than a lane)
+                    return (63 - wk) | pk | (end - beg) | (WIN - 2 - (end - begc)) | sh | (C - sh);
+                };
+                if (admit() >= 0) do {
+                    LCD_ROW_MARK("plain_cn top");
                     const int cw4 = ((end - begc) + CP) & ~(CP - 1);
-                    if (((end - beg) | (WIN - 2 - (end - begc)) | ((unsigned)sh > (unsigned)C ? -1 : 0) | (l_cused + (unsigned)cw4 > code_cap ? -1 : 0)) < 0) break; // (one test, as above)
                     const int vb = (pk >> 8) & 7, bz0 = (pk >> 14) & 31;
-                    const int s = (idx - bi) & KM;
-                    const unsigned lut = lut_of(vb);
-                    const int bzb = bz0 - 32; // (the score fields of `lut` are biased by 32)
+                    const int lut = lut_of(vb);
                     // previous row: same lanes (sh == 0) or one lane to the left (sh == C); hd[k]: H of the previous row at this cell's column - 1
                     int hd[C];
                     if (sh == 0) {
@@ -2667,8 +2770,8 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
 #pragma unroll
                     for (int k = 0; k < C; ++k) {
                         const unsigned q6 = (unsigned)(q_cur >> (8 * k)) & 255u;
-                        const int sk = (int)__builtin_amdgcn_ubfe(lut, q6, 6u);
-                        const int nn = hd[k] + sk + bzb;
+                        const int sk = __builtin_amdgcn_sbfe(lut, q6, 6u);
+                        const int nn = hd[k] + sk + bz0;
                         uu[k] = pva[k] + bz0; vv[k] = pvb[k] + bz0;
                         inb[k] = (unsigned)(cl + k - lo) <= (unsigned)span;
                         const int m_ = imax(uu[k], vv[k]);
@@ -2718,12 +2821,14 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
                         code |= (word)((unsigned)hs | (fl << 3)) << (8 * k);
                         pvh[k] = inb[k] ? h : LCD_GUARD; pva[k] = inb[k] ? eo1 : LCD_GUARD; pvb[k] = inb[k] ? eo2 : LCD_GUARD;
                     }
-                    const int be = beg | (end << 16);
+                    const int be = FIXED ? xw : beg | (end << 16); // (MODE 2: the table's word is the packed interval)
                     if (pk & (1 << 24)) {
+                        LCD_ROW_MARK("plain_cn slot");
+                        const int s = (wbase + wk - bi) & KM;
                         ring_st3(ring + RB * (unsigned)(s * SLOTW), (begc + cl) & WM, pvh, pva, pvb);
                         m_be = lean_wlane(be, s, m_be); m_mm = lean_wlane(ml | (mr << 16), s, m_mm);
-                        pend = 0;
-                    } else pend = 1;
+                        LCD_ROW_MARK("plain_cn slot end");
+                    }
                     if (cl < cw4) {
                         uint8_t *cp = g.code8 + (size_t)(l_cused + (unsigned)cl);
                         if constexpr (C == 8) *(__attribute__((address_space(1))) unsigned long long *)cp = code;
@@ -2731,10 +2836,17 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
                         else *(__attribute__((address_space(1))) unsigned short *)cp = (unsigned short)code;
                     }
                     r_be = lean_wlane(be, wk, r_be);
-                    l_begc = begc; l_beg = beg; l_end = end; l_ml = ml; l_mr = mr;
+                    l_ml = ml; l_mr = mr;
                     l_cused += (unsigned)cw4; run_cells += (unsigned)(span + 1);
-                    ++idx; ++wk;
+                    ++wk;
+                } while (admit() >= 0);
+                l_begc = begc - sh; // (the refused row's window step, taken back)
+                if (wk != wk0) { // ... and its band: the last row's is in the metadata window; whether that row went to its ring slot is in its plan word
+                    const int be_ = LCD_RL(r_be, wk - 1);
+                    l_beg = be_ & 65535; l_end = (int)((unsigned)be_ >> 16);
+                    pend = (LCD_RL(w_pk, wk - 1) >> 24 & 1) ^ 1;
                 }
+                idx = wbase + wk; // (the rows of a run are counted in the plan window alone)
             }
             if (pend) { // a general row comes next (or the window ends): it reads its predecessor from the ring
                 const int sl = (idx - 1 - bi) & KM;
@@ -2799,12 +2911,12 @@ __device__ __attribute__((noinline)) int align_lean(const Ctx *gp_, const unsign
         const int lo_g = C == 1 ? beg - begc : 0; // the band's first lane
         const int jb = begc + cl;
         const word qw = q_of(begc);
-        const unsigned lutg = lut_of(vb);
+        const int lutg = lut_of(vb);
         bool inb[C]; int sk[C];
 #pragma unroll
         for (int k = 0; k < C; ++k) {
             inb[k] = jb + k >= beg && jb + k <= end;
-            sk[k] = (int)__builtin_amdgcn_ubfe(lutg, (unsigned)(qw >> (8 * k)) & 255u, 6u) - 32;
+            sk[k] = __builtin_amdgcn_sbfe(lutg, (unsigned)(qw >> (8 * k)) & 255u, 6u);
         }
         // ---- phase A: best match / E1 / E2 input of the cells over the predecessors (first maximum keeps its ordinal) ----
         int nn[C], uu[C], vv[C];
