@@ -1510,11 +1510,69 @@ int lcd_depth_format(int n_rows, const int64_t *beg, const int64_t *end, const u
  * any file is created: a code outside m / h, a threshold outside 128 ... 255, an empty path or "-".  The file is created after the refusals and removed when the
  * run fails -- at any stage, the close of the other outputs included; the table is finished last.  *mods_stats: the sums over the chunks (n_rows: the data lines
  * written), filled only by a run that succeeds. */
+/* ---- the per-haplotype read sets of a chunk: FASTQ entries and the haplotag list, written on the device from the records where they lie (split_kernel.hip) ----
+ * The reference has no such output; these are PROJECT RULES, restated in Python in tests/split_common.py.
+ *   selection   the records of the chunk's table that `skip` / `order` name (the meaning they have for lcd_chunk_tag_records_sel; NULL: all, in table order), in
+ *               that order: n_records.  A run hands in the plan of the alignment writer (lcd_merged_record_plan: rule 4's per-record overlap with the region
+ *               before, rule 5's order under sort_output) whether or not an alignment output is written.  Of those, a record that carries 0x100 or 0x800 is
+ *               left out (n_not_primary): every primary record a run visits appears exactly once in the run, in the order of the output BAM.
+ *   layout      a primary record with l_seq < 0, or whose name, CIGAR words, packed bases and qualities (36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 +
+ *               l_seq bytes) do not fit 4 + block_size or the table's entry, is left out of both outputs (n_bad_layout); nothing outside a record is read.
+ *               What is left is selected: n_selected = n_hap[0] + n_hap[1] + n_hap[2].
+ *   haplotype   a kept record of read r has haps[r] (0: none, 1, 2) and phase_sets[r] (NULL: 0), the arrays the tag writer gets; a record the loader filtered
+ *               (low MAPQ, unmapped with a position) has 0 and 0 (n_filtered_primary counts the selected ones).  The record's stream is its haplotype.
+ *   FASTQ entry `@` QNAME [comment] `\n` SEQ `\n+\n` QUAL `\n`.  QNAME: the bytes in front of the first NUL of the name, `*` when there are none.  SEQ:
+ *               "=ACMGRSVTWYHKDBN"[nibble].  QUAL: min(byte, 93) + 33; a first quality byte of 0xff prints `!` at every position.  With flag 0x10 the entry is the
+ *               read as sequenced (n_reverse): SEQ reversed and complemented through "=TGKCYSBAWRDMHVN", QUAL reversed.  The bases are the record's as stored
+ *               (refined alignments change none).  comment (opt.comment): `\tHP:i:<h>` when h != 0, then `\tPS:i:<ps>` when ps > 0, the 64-bit value in decimal.
+ *               A selected record with l_seq == 0 has no entry (n_no_seq) and keeps its line in the list.
+ *   list line   (opt.list) QNAME `\t` H1 | H2 | none `\t` <ps> in decimal when ps > 0, else none `\t` chromosome `\n`; chromosome by the RNAME rule of the SAM
+ *               output: `*` for a refID < 0, a refID >= n_ref or an empty name.  The header line `#readname haplotype phaseset chromosome` (tabs) is the file
+ *               writer's, not the chunk call's.
+ * lcd_chunk_split_reads: one wavefront per record in two launches, as lcd_tagged_to_sam: the measure pass gives one row per record (stream, the entry's and the
+ * line's exact length, flag bits), lcd_split_offsets makes the four 64-bit exclusive prefix sums on the host, the emit pass writes into four device buffers
+ * (stream 0 none, 1, 2: FASTQ; 3: the list).  A reverse record is walked from its far end: every step's loads and stores are contiguous across the wavefront.
+ * Only the rows and the statistics come down; lcd_split_to_host copies a range of a stream, lcd_split_dev_ptr hands it to lcd_bgzf_deflate_dev_ptr.  NULL with
+ * -4 before any HIP call: a NULL chunk or options, a chunk not made from a BAM or not resolved, NULL haps with reads, a hap outside 0 ... 2, list without names.
+ * Host only (lcd_split_format.cpp): lcd_split_opt_check (0 / -4); lcd_split_paths: prefix + gz -> the malloc()'d paths PREFIX.none|h1|h2.fastq[.gz] in stream
+ * order, -4 for an empty prefix or "-", or when two of them and the n_other paths are equal (NULL, empty and "-" entries name no file and are skipped; a NULL
+ * prefix compares the others alone);
+ * lcd_split_offsets: n rows' stream (-1 ... 2), fq_len and list_len -> fq_off[i] inside the record's stream, list_off[i], totals[4] (streams 0 1 2, the list);
+ * a row with stream -1 adds nothing; -4 for a NULL array or a stream outside -1 ... 2.
+ * The read sets of a whole run: lcd_run_ext2_split_t.split_prefix / haplotag_path (below).  At the writer stage, chunk by chunk in plan order, with the plan the
+ * alignment writer uses for the chunk; split_gz: every append goes through the BGZF deflate in HBM and the EOF member is written at close.  A stream without
+ * records still leaves its file.  Refused with -4 before any file is created: split_gz / split_comment without split_prefix, an empty prefix, "-", or one of the
+ * four paths equal to another output of the run (VCF, alignment output, mods, depth, each other).  The files are removed when the run fails; *split_stats: the
+ * sums over the chunks, filled only by a run that succeeds. */
+typedef struct lcd_split_opt_t { int comment, list, reserved[2]; } lcd_split_opt_t;
+typedef struct lcd_split_stats_t {
+    int64_t n_records, n_selected, n_hap[3], n_not_primary, n_filtered_primary, n_reverse, n_no_seq, n_bad_layout, bytes_fastq[3], bytes_list;
+    double ms_measure, ms_emit, ms_deflate, ms_download_write;
+} lcd_split_stats_t;
+typedef struct lcd_split_s lcd_split_t;
+void lcd_split_opt_default(lcd_split_opt_t *opt);
+int lcd_split_opt_check(const lcd_split_opt_t *opt);
+int lcd_split_paths(const char *prefix, int gz, int n_other, const char *const *other, char *paths[3]);
+int lcd_split_offsets(int n, const int *stream, const uint64_t *fq_len, const uint64_t *list_len, uint64_t *fq_off, uint64_t *list_off, uint64_t totals[4]);
+lcd_split_t *lcd_chunk_split_reads(const lcd_chunk_t *chunk, const int *haps, const int64_t *phase_sets, const uint8_t *skip, const int *order,
+                                   const lcd_sam_names_t *names /* list only; may be NULL when opt->list == 0 */, const lcd_split_opt_t *opt, lcd_split_stats_t *stats);
+size_t lcd_split_size(const lcd_split_t *s, int stream /* 0 none, 1, 2, 3 = list */);
+uint64_t lcd_split_dev_ptr(const lcd_split_t *s, int stream);
+int lcd_split_to_host(const lcd_split_t *s, int stream, size_t off, size_t n, uint8_t *out);
+void lcd_split_free(lcd_split_t *s);
 typedef struct lcd_run_ext2_t {
     size_t size;
     const char *mods_path; int mods_code, mods_threshold, mods_combine_strands, reserved; lcd_mods_stats_t *mods_stats;
     const char *depth_path; int depth_window, depth_skip_dels; lcd_depth_stats_t *depth_stats;      /* the depth track of the run (below); added at the end */
 } lcd_run_ext2_t;
+/* lcd_run_ext2_t grown at its end by the read sets of the run (above): the same bytes under a name of their own, so that a caller compiled against the shorter
+ * struct and the tests that pin its layout stay as they are.  It is handed to the two drivers as their ext2 with x.size = sizeof(lcd_run_ext2_split_t); by the
+ * `size` rule a shorter struct reads as one without these members; a size beyond sizeof(lcd_run_ext2_split_t) is a layout this library does not know and reads
+ * as lcd_run_ext2_t alone. */
+typedef struct lcd_run_ext2_split_t {
+    lcd_run_ext2_t x;
+    const char *split_prefix; int split_gz, split_comment; const char *haplotag_path; lcd_split_stats_t *split_stats;
+} lcd_run_ext2_split_t;
 int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
                         const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2);
 /* lcd_call_bam_regions_ext2 == lcd_call_bam_regions with the same struct: the table of the one contig, every region's chunk piled up with its final haplotypes (the

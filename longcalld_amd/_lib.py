@@ -331,6 +331,27 @@ class LcdRunExt2(C.Structure):
                 ("depth_path", C.c_char_p), ("depth_window", C.c_int), ("depth_skip_dels", C.c_int), ("depth_stats", C.POINTER(LcdDepthStats))]
 
 
+SPLIT_STAT_COUNTERS_HEAD = ("n_records", "n_selected")
+SPLIT_STAT_COUNTERS_TAIL = ("n_not_primary", "n_filtered_primary", "n_reverse", "n_no_seq", "n_bad_layout")
+
+
+class LcdSplitOpt(C.Structure):
+    """lcd_split_opt_t: the options of lcd_chunk_split_reads (comment: HP / PS behind the name; list: the haplotag list's lines as stream 3)"""
+    _fields_ = [("comment", C.c_int), ("list", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class LcdSplitStats(C.Structure):
+    """lcd_split_stats_t: where the records of the plan went, the bytes per stream, and the wall-clock split of the call (the last two: the drivers' sink)"""
+    _fields_ = [(n, C.c_int64) for n in SPLIT_STAT_COUNTERS_HEAD] + [("n_hap", C.c_int64 * 3)] + [(n, C.c_int64) for n in SPLIT_STAT_COUNTERS_TAIL] + [
+        ("bytes_fastq", C.c_int64 * 3), ("bytes_list", C.c_int64)] + [(n, C.c_double) for n in ("ms_measure", "ms_emit", "ms_deflate", "ms_download_write")]
+
+
+class LcdRunExt2Split(C.Structure):
+    """lcd_run_ext2_split_t: lcd_run_ext2_t grown at its end by the read sets of the run; handed to the drivers as byref(s.x) with s.x.size = sizeof of this struct"""
+    _fields_ = [("x", LcdRunExt2), ("split_prefix", C.c_char_p), ("split_gz", C.c_int), ("split_comment", C.c_int), ("haplotag_path", C.c_char_p),
+                ("split_stats", C.POINTER(LcdSplitStats))]
+
+
 class LcdRunExt(C.Structure):
     """lcd_run_ext_t: the options of lcd_call_files_ext that came after lcd_run_opt_t / lcd_run_out_t were laid out; a NULL member is off"""
     _fields_ = [("vcf_idx", C.POINTER(LcdVcfIndexOpt)), ("vcf_idx_stats", C.POINTER(LcdVcfIndexStats))]
@@ -390,6 +411,7 @@ EXPORTS = [
     "lcd_bgzf_inflate_dev", "lcd_inflated_dev_ptr", "lcd_inflated_size", "lcd_inflated_n_blocks", "lcd_inflated_kernel_ms", "lcd_inflated_upload_ms", "lcd_inflated_to_host", "lcd_inflated_free",
     "lcd_mods_opt_default", "lcd_mods_opt_check", "lcd_chunk_mod_pileup", "lcd_mods_n_rows", "lcd_mods_rows_to_host", "lcd_mods_free", "lcd_mods_combine_rows", "lcd_mods_format", "lcd_call_files_ext2", "lcd_call_bam_regions_ext2",
     "lcd_depth_opt_default", "lcd_depth_opt_check", "lcd_chunk_depth", "lcd_depth_n_rows", "lcd_depth_rows_to_host", "lcd_depth_free", "lcd_depth_tile", "lcd_depth_windows", "lcd_depth_format",
+    "lcd_split_opt_default", "lcd_split_opt_check", "lcd_split_paths", "lcd_split_offsets", "lcd_chunk_split_reads", "lcd_split_size", "lcd_split_dev_ptr", "lcd_split_to_host", "lcd_split_free",
 ]
 
 
@@ -670,6 +692,20 @@ def load_library():
     lib.lcd_depth_tile.argtypes = []
     lib.lcd_depth_windows.argtypes = [C.c_int, i64p_m, i64p_m, u32p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
     lib.lcd_depth_format.argtypes = [C.c_int, i64p_m, i64p_m, u32p, C.POINTER(C.c_uint64), C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+    lib.lcd_split_opt_default.argtypes = [C.POINTER(LcdSplitOpt)]
+    lib.lcd_split_opt_default.restype = None
+    lib.lcd_split_opt_check.argtypes = [C.POINTER(LcdSplitOpt)]
+    lib.lcd_split_paths.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_void_p)]
+    lib.lcd_split_offsets.argtypes = [C.c_int, i32p, u64p, u64p, u64p, u64p, u64p]
+    lib.lcd_chunk_split_reads.restype = C.c_void_p
+    lib.lcd_chunk_split_reads.argtypes = [C.c_void_p, i32p, i64p_m, u8p, i32p, C.c_void_p, C.POINTER(LcdSplitOpt), C.POINTER(LcdSplitStats)]
+    lib.lcd_split_size.restype = C.c_size_t
+    lib.lcd_split_size.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_split_dev_ptr.restype = C.c_uint64
+    lib.lcd_split_dev_ptr.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_split_to_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, u8p]
+    lib.lcd_split_free.argtypes = [C.c_void_p]
+    lib.lcd_split_free.restype = None
     lib.lcd_mods_combine_rows.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p]
     lib.lcd_mods_format.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     _lib = lib

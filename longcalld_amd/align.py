@@ -1962,7 +1962,94 @@ def write_phased_sam(in_bam_path, chunks, path, pg_line=None, sort_output=False,
                 refine={k: getattr(rst, k) for k, _t in LcdRefineStats._fields_}, sam={k: getattr(sst, k) for k, _t in LcdSamStats._fields_})
 
 
-def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False, mods=None, depth=None):
+def _split_stats(st):
+    return {k: (list(getattr(st, k)) if k in ("n_hap", "bytes_fastq") else getattr(st, k)) for k, _t in st._fields_}
+
+
+def chunk_split_reads(chunk, haps, phase_sets, skip=None, order=None, names=None, comment=False, list=False):
+    """lcd_chunk_split_reads: the records of the chunk's table that skip / order name (merged_record_plan's outputs; None: all, in table order) as per-haplotype
+    FASTQ entries and -- with list=True and names = the contigs' names -- haplotag list lines, formatted on the device.  haps / phase_sets per kept read.
+    -> ([FASTQ bytes of stream 0 (none), 1, 2, the list's bytes (no header line)], stats dict; "n_hap" and "bytes_fastq" are lists of three)"""
+    from ._lib import LcdSplitOpt, LcdSplitStats
+    lib = chunk.lib
+    hp = np.concatenate([np.ascontiguousarray(haps, np.int32), np.zeros(1, np.int32)]); ps = np.concatenate([np.ascontiguousarray(phase_sets, np.int64), np.zeros(1, np.int64)])
+    if len(hp) <= chunk.n or len(ps) <= chunk.n:
+        raise ValueError("chunk_split_reads: haps / phase_sets shorter than the chunk's reads")
+    if list and names is None:
+        raise ValueError("chunk_split_reads: list=True needs names= (the contigs' names)")
+    sk = np.ascontiguousarray(skip, np.uint8) if skip is not None else None
+    od = np.ascontiguousarray(order, np.int32) if order is not None else None
+    o = LcdSplitOpt(); lib.lcd_split_opt_default(C.byref(o)); o.comment, o.list = int(bool(comment)), int(bool(list))
+    st = LcdSplitStats()
+
+    def run(nm):
+        h = lib.lcd_chunk_split_reads(chunk.h, hp.ctypes.data_as(i32p), ps.ctypes.data_as(C.POINTER(C.c_int64)), _p8(sk) if sk is not None else None,
+                                      od.ctypes.data_as(i32p) if od is not None else None, nm, C.byref(o), C.byref(st))
+        if not h:
+            raise LcdError("lcd_chunk_split_reads failed: " + lib.lcd_last_error().decode())
+        try:
+            out = []
+            for s in range(4):
+                buf = np.zeros(max(1, int(lib.lcd_split_size(h, s))), np.uint8)
+                n = int(lib.lcd_split_size(h, s))
+                check(lib.lcd_split_to_host(h, s, 0, n, _p8(buf)), lib)
+                out.append(buf[:n].tobytes())
+            return out, _split_stats(st)
+        finally:
+            lib.lcd_split_free(h)
+    if not list:
+        return run(None)
+    with _SamNames(names) as nm:
+        return run(nm.h)
+
+
+def split_paths(prefix, gz=False, other=()):
+    """lcd_split_paths (host only): the FASTQ files of a prefix in stream order (none, h1, h2); LcdError when the prefix is empty or "-", or when two of them and the
+    `other` output paths (None entries are skipped) are equal.  prefix None: only the others are compared -> []"""
+    lib = load_library()
+    oth = [(_enc(x) if x is not None else None) for x in other]
+    arr = (C.c_char_p * max(1, len(oth)))(*oth)
+    p = (C.c_void_p * 3)()
+    rc = lib.lcd_split_paths(_enc(prefix) if prefix is not None else None, int(bool(gz)), len(oth), arr, p)
+    if rc:
+        raise LcdError(f"lcd_split_paths: error {rc}: an empty prefix or \"-\", or two outputs that name one file")
+    try:
+        return [C.string_at(p[k]).decode() for k in range(3) if p[k]]
+    finally:
+        for k in range(3):
+            if p[k]:
+                _libc_free(C.c_void_p(p[k]))
+
+
+def split_offsets(stream, fq_len, list_len):
+    """lcd_split_offsets (host only): the rows of a measure pass -> (fq_off per record inside its stream, list_off per record, the four totals)"""
+    lib = load_library()
+    sa = np.ascontiguousarray(stream, np.int32); fl = np.ascontiguousarray(fq_len, np.uint64); ll = np.ascontiguousarray(list_len, np.uint64)
+    n = len(sa)
+    assert len(fl) == n and len(ll) == n
+    fo, lo, tot = np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint64), np.zeros(4, np.uint64)
+    u64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint64))
+    rc = lib.lcd_split_offsets(n, sa.ctypes.data_as(i32p) if n else None, u64(fl) if n else None, u64(ll) if n else None, u64(fo), u64(lo), u64(tot))
+    if rc:
+        raise LcdError(f"lcd_split_offsets: error {rc}: a stream outside -1 ... 2, or lengths that overflow")
+    return [int(x) for x in fo[:n]], [int(x) for x in lo[:n]], [int(x) for x in tot]
+
+
+def _run_ext2_split(mods, depth, split):
+    """_run_ext2 grown by split = dict([prefix, gz, comment, haplotag_list]) -> (the lcd_run_ext2_split_t, whose member x is handed to the drivers, and the three
+    statistics structs it points to)"""
+    from ._lib import LcdRunExt2Split, LcdSplitStats
+    x, mst, dst = _run_ext2(mods, depth)
+    xs = LcdRunExt2Split(); xs.x = x; xs.x.size = C.sizeof(LcdRunExt2Split)
+    sst = LcdSplitStats()
+    opt_s = lambda v: _enc(v) if v is not None else None
+    xs.split_prefix, xs.split_gz, xs.split_comment = opt_s(split.get("prefix")), int(bool(split.get("gz", False))), int(bool(split.get("comment", False)))
+    xs.haplotag_path, xs.split_stats = opt_s(split.get("haplotag_list")), C.pointer(sst)
+    return xs, mst, dst, sst
+
+
+def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, min_mapq=30, cfg=None, bam_out=None, te_fasta=None, rnames=None, refine=False, mods=None, depth=None,
+                     split=None):
     """lcd_call_bam_regions: regions of one contig of an indexed BAM + a FASTA with its .fai -> the dict of chunks_call.
     bam_out = dict(path[, pg_line, block_payload]): the phased alignment file is written too; the result gets "bam_out" = the counters and stage times of
     lcd_bam_out_t and "bam_out_rc" / "bam_out_error" (a failed output leaves the VCF side valid: it is returned, not raised).
@@ -1971,7 +2058,9 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     mods = dict(path[, code, threshold, combine_strands]) (lcd_call_bam_regions_ext2): the contig's methylation table goes to path, every region's chunk piled up
     with the haplotypes the result returns for it; the result gains "mods" = the sums of lcd_mods_stats_t
     depth = dict(path[, window, skip_dels]): the contig's per-haplotype depth track goes to path (per base, or per window of `window` positions), from the records
-    as stored and the same haplotypes; the result gains "depth" = the sums of lcd_depth_stats_t"""
+    as stored and the same haplotypes; the result gains "depth" = the sums of lcd_depth_stats_t
+    split = dict([prefix, gz, comment, haplotag_list]): the contig's per-haplotype read sets (prefix.none|h1|h2.fastq[.gz]) and / or the haplotag list, from the
+    records the alignment output holds and the same haplotypes; the result gains "split" = the sums of lcd_split_stats_t"""
     from ._lib import LCD_ALN_BAM, LcdAlnOpt, LcdBamOut, LcdCallChunk, LcdRefineStats, LcdRunOpt, LcdRunOut, LcdVar1
     vf, fo = _vcf_fields(te_fasta, rnames)
     if refine and vf is not None:
@@ -1992,8 +2081,11 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
     out = LcdRunOut(fields_out=C.pointer(fo) if vf is not None else None, refine_stats=C.pointer(rst) if rst is not None else None)
     args = (_enc(bam_path), _enc(bai_path), _enc(fasta_path), _enc(chrom), n, rb, re_, int(min_mapq), C.byref(cfg), arr, C.byref(recs), C.byref(n_recs),
             C.byref(text), C.byref(bo) if bo is not None else None, C.byref(ro), C.byref(out))
-    mst = dst = None
-    if mods is not None or depth is not None:
+    mst = dst = spst = None
+    if split is not None:
+        ext2, mst, dst, spst = _run_ext2_split(mods, depth, split)
+        rc = lib.lcd_call_bam_regions_ext2(*args, C.byref(ext2.x))
+    elif mods is not None or depth is not None:
         ext2, mst, dst = _run_ext2(mods, depth)
         rc = lib.lcd_call_bam_regions_ext2(*args, C.byref(ext2))
     else:
@@ -2008,6 +2100,8 @@ def call_bam_regions(bam_path, bai_path, fasta_path, chrom, reg_beg, reg_end, mi
         res["mods"] = {k: getattr(mst, k) for k, _t in mst._fields_}
     if dst is not None:
         res["depth"] = _depth_stats(dst)
+    if spst is not None:
+        res["split"] = _split_stats(spst)
     if bo is None:
         return res
     res.update(bam_out_rc=int(rc), bam_out_error=err, bam_out={k: getattr(bo, k) for k in ("n_records_out", "n_filtered_out", "bytes_inflated", "bytes_file", "ms_tag",
@@ -2159,7 +2253,8 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
-              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None, mods=None, depth=None):
+              keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None, mods=None, depth=None,
+              split=None):
     """lcd_call_files with the job's one file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[,
     pg_line, block_payload]), the phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads,
     n_passes, flip_hap, flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -2221,11 +2316,17 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     ro = LcdRunOpt(idx=ptr(io), fields=ptr(vf), aln=C.pointer(ao))
     out = LcdRunOut(idx_stats=ptr(ist), n_reads_per_file=C.cast(per_file, C.POINTER(C.c_int64)) if _inputs is not None else None, fields_out=ptr(fo), refine_stats=ptr(rst), sam_stats=ptr(sst))
     args = (C.byref(inp) if _inputs is not None else None, C.byref(job), C.byref(cfg), C.byref(ro), C.byref(st), C.byref(out))
-    ext, mst, dst = None, None, None
+    ext, mst, dst, spst = None, None, None, None
     if vio is not None:
         from ._lib import LcdRunExt
         ext = LcdRunExt(vcf_idx=C.pointer(vio), vcf_idx_stats=C.pointer(vist))
-    if mods is not None or depth is not None:
+    if split is not None:
+        # split = dict([prefix, gz, comment, haplotag_list]) (the command line's --split-reads / --split-gz / --split-comment / --haplotag-list): the reads of
+        # each haplotype as FASTQ files prefix.none|h1|h2.fastq[.gz] and / or the haplotag list (lcd_run_ext2_split_t), in the order of the output BAM; the result
+        # gains "split" = the sums of lcd_split_stats_t over the chunks
+        ext2, mst, dst, spst = _run_ext2_split(mods, depth, split)
+        rc = lib.lcd_call_files_ext2(*args, C.byref(ext) if ext is not None else None, C.byref(ext2.x))
+    elif mods is not None or depth is not None:
         # mods = dict(path[, code "m" | "h", threshold 128 ... 255, combine_strands]): the per-haplotype CpG methylation table (lcd_run_ext2_t); the result gains
         # "mods" = the sums of lcd_mods_stats_t over the chunks (n_rows: the data lines written)
         # depth = dict(path[, window 0 ... 2^30, skip_dels]) (the command line's --depth / --depth-window / --depth-skip-dels): the per-haplotype depth track, per
@@ -2262,6 +2363,8 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["mods"] = {k: getattr(mst, k) for k, _t in mst._fields_}
         if dst is not None:
             res["depth"] = _depth_stats(dst)
+        if spst is not None:
+            res["split"] = _split_stats(spst)
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))

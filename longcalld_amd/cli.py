@@ -16,13 +16,14 @@ REFUSED = {
     "-m": "-m/--methylation is not supported (the reference reads no MM/ML tag behind it): ask for the per-haplotype CpG methylation table with --mods FILE",
     "--methylation": "-m/--methylation is not supported (the reference reads no MM/ML tag behind it): ask for the per-haplotype CpG methylation table with --mods FILE",
 }
-FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam", "--mod-combine-strands", "--depth-skip-dels"}
+FLAGS = {"--make-index", "--hifi", "--ont", "--autosome-XY", "--autosome", "--all-ctg", "-H", "--no-vcf-header", "--amb-base", "--no-overlap", "--overlap", "--sort-merged", "--var-rnames", "--sv-rnames", "--refine-bam", "--mod-combine-strands", "--depth-skip-dels", "--split-gz", "--split-comment"}
 VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E": "exclude", "--exclude-ctg": "exclude", "-r": "ref_idx", "--ref-idx": "ref_idx",
           "-n": "sample_name", "--sample-name": "sample_name", "-o": "out_vcf", "--out-vcf": "out_vcf", "-O": "out_type", "--out-type": "out_type", "-l": "min_sv_len",
           "--min-sv-len": "min_sv_len", "-b": "out_bam", "--out-bam": "out_bam", "-c": "min_cov", "--min-cov": "min_cov", "-d": "alt_cov", "--alt-cov": "alt_cov",
           "-a": "alt_ratio", "--alt-ratio": "alt_ratio", "-M": "min_mapq", "--min-mapq": "min_mapq", "-B": "min_bq", "--min-bq": "min_bq", "-C": "max_cov", "--max-cov": "max_cov",
           "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam", "--vcf-index": "vcf_index",
-          "--mods": "mods", "--mod-code": "mod_code", "--mod-threshold": "mod_threshold", "--depth": "depth", "--depth-window": "depth_window"}
+          "--mods": "mods", "--mod-code": "mod_code", "--mod-threshold": "mod_threshold", "--depth": "depth", "--depth-window": "depth_window", "--split-reads": "split_reads",
+          "--haplotag-list": "haplotag_list"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli index [--csi] in.vcf.gz [out]   build in.vcf.gz.tbi (--csi: .csi) on the device; BAM or VCF is decided by the file's content, not its name
@@ -50,6 +51,12 @@ Output:   -n/--sample-name STR   -o/--out-vcf FILE [stdout]   -O/--out-type v|z 
           --depth-window INT [0]   one line per window of INT positions ([k INT + 1, (k + 1) INT] on the contig, cut to the called regions) with the sums of
                         depth x positions (bases_all bases_h1 bases_h2 bases_unassigned); 0: per base; at most 2^30
           --depth-skip-dels   a D does not cover
+          --split-reads PREFIX   the reads of each haplotype as FASTQ, written on the device from the records with the haplotypes of this run: PREFIX.h1.fastq,
+                        PREFIX.h2.fastq and PREFIX.none.fastq hold every primary record of the called regions once, in the order of the output BAM (a reverse-strand
+                        record as it was sequenced; secondary and supplementary records are left out); works with or without -b / --sam
+          --split-gz    with --split-reads: PREFIX.*.fastq.gz, BGZF-compressed on the device (valid gzip; `bgzip -r` can index it)
+          --split-comment   with --split-reads: HP:i: and PS:i: behind the read name, tab-separated, where the output BAM carries the tag
+          --haplotag-list FILE   one line per primary record: readname, H1 | H2 | none, the phase set or none, the contig (header #readname haplotype phaseset chromosome)
 Calling:  -c/--min-cov INT   -d/--alt-cov INT   -a/--alt-ratio FLOAT   -M/--min-mapq INT   -B/--min-bq INT   -C/--max-cov INT
 Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it would have been read, and write <out.bam>.bai with -b (existing indexes are never touched; --sam gets no index);
                          it does not index the VCF: that is --vcf-index
@@ -139,6 +146,27 @@ def depth_option(o):
     if o["depth"] == o.get("mods"):
         return "--depth and --mods name one file"
     return dict(path=o["depth"], window=win, skip_dels="--depth-skip-dels" in o["flags"])
+
+
+def split_option(o):
+    """--split-reads PREFIX / --split-gz / --split-comment / --haplotag-list FILE -> the keyword split= of align.call_file (None without --split-reads and
+    --haplotag-list), or the refusal's text.  Refused: the two flags without --split-reads, an empty prefix or path, "-", and one of the four files equal to
+    another output of the run (-o, -b / --sam, --mods, --depth, or each other)"""
+    gz, comment = "--split-gz" in o["flags"], "--split-comment" in o["flags"]
+    if "split_reads" not in o and (gz or comment):
+        return "--split-gz / --split-comment need --split-reads PREFIX"
+    if "split_reads" not in o and "haplotag_list" not in o:
+        return None
+    if o.get("split_reads") in ("", "-"):
+        return "--split-reads needs a prefix: the read sets do not go to stdout"
+    if o.get("haplotag_list") in ("", "-"):
+        return "--haplotag-list needs a file: the list does not go to stdout"
+    mine = [o["split_reads"] + s + (".fastq.gz" if gz else ".fastq") for s in (".none", ".h1", ".h2")] if "split_reads" in o else []
+    mine += [o["haplotag_list"]] if "haplotag_list" in o else []
+    others = [o[k] for k in ("out_vcf", "out_bam", "out_sam", "mods", "depth") if o.get(k) not in (None, "", "-")]
+    if len(set(mine + others)) != len(mine + others):
+        return "--split-reads / --haplotag-list: two outputs of the run name one file"
+    return dict(prefix=o.get("split_reads"), gz=gz, comment=comment, haplotag_list=o.get("haplotag_list"))
 
 
 def input_bams(o, bam):
@@ -247,6 +275,9 @@ def main(argv=None):
     depth = depth_option(o)
     if isinstance(depth, str):
         return refuse(depth)
+    split = split_option(o)
+    if isinstance(split, str):
+        return refuse(split)
     from . import align
     is_ont = 1 if "--ont" in o["flags"] else 0
     clean, opt, pass_, call = {}, {}, {}, {}
@@ -287,7 +318,7 @@ def main(argv=None):
                              index=(dict(build_missing_bai=1, build_missing_fai=1) if sam else True) if "--make-index" in o["flags"] else None,
                              **(dict(aln_format="sam") if sam else {}), **(dict(refine=True) if refine else vcf_fields(o)),
                              **(dict(vcf_index=o["vcf_index"]) if "vcf_index" in o else {}), **(dict(mods=mods) if mods is not None else {}),
-                             **(dict(depth=depth) if depth is not None else {}))
+                             **(dict(depth=depth) if depth is not None else {}), **(dict(split=split) if split is not None else {}))
     except align.LcdError as e:
         sys.stderr.write(f"longcalld_amd call: {e}\n")
         return 2 if "error -2:" in str(e) else 1
@@ -303,6 +334,7 @@ def main(argv=None):
                      + (f"{st['refine']['n_refined']} refined / {st['refine']['n_unrefined']} unrefined records, " if refine and bam_out is not None else "")
                      + (f"{st['bam_out']['bytes_file']} bytes of SAM text, " if sam else "") + (f"{st['mods']['n_rows']} methylation rows, " if mods is not None else "")
                      + (f"{st['depth']['n_rows']} depth rows, " if depth is not None else "")
+                     + (f"{st['split']['n_hap'][1]} + {st['split']['n_hap'][2]} + {st['split']['n_hap'][0]} split reads, " if split is not None else "")
                      + f"{st['ms_wall'] / 1000:.2f} s\n")
     return 0
 

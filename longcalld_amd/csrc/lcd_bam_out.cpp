@@ -11,7 +11,6 @@ struct lcd_deflated_s {
 };
 // offs: where record k starts in `out` (n_records + 1 entries, what the emit pass was given); d_offs: the same in HBM, uploaded by the first lcd_tagged_to_sam
 struct lcd_tagged_s { DevBuf out; size_t size = 0; int n_records = 0, device = 0; std::vector<unsigned long long> offs; mutable DevBuf d_offs; mutable bool offs_up = false; };
-struct lcd_sam_names_s { DevBuf pool, offs; size_t pool_bytes = 0; int n_ref = 0, device = 0; };
 struct lcd_sam_text_s { DevBuf text; size_t size = 0; int device = 0; };
 
 namespace {
@@ -136,20 +135,6 @@ int lcd_merged_record_plan(int n_rec, const int *rec_file, const int64_t *rec_po
 
 // ---- HP / PS rewrite of a chunk's records ----
 namespace {
-// the records with skip[i] == 0 (NULL: all) in the order `order` names them (NULL: table order)
-int pick_selected(const std::string &W, const lcd_chunk_t *c, const uint8_t *skip, const int *order, std::vector<int> &pick) {
-    const int n_rec = (int)c->rec_beg.size();
-    int m = 0;
-    for (int i = 0; i < n_rec; ++i) if (!skip || !skip[i]) ++m;
-    pick.assign(m, 0); std::vector<uint8_t> seen(n_rec + 1, 0);
-    for (int k = 0, i = 0; k < m; ++k) {
-        if (order) i = order[k]; else { while (skip && skip[i]) ++i; }
-        if (i < 0 || i >= n_rec || (skip && skip[i]) || seen[i]) return set_err(-4, W + ": `order` must name every record that is not skipped exactly once");
-        seen[i] = 1; pick[k] = i;
-        if (!order) ++i;
-    }
-    return 0;
-}
 // the records `pick` names (indices of the chunk's record table), rewritten in that order
 lcd_tagged_t *tag_records_core(const std::string &W, const lcd_chunk_t *c, const int *haps, const int64_t *phase_sets, const std::vector<int> &pick) {
     if (use_device(c->device)) return nullptr;

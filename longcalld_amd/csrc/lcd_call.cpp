@@ -491,6 +491,11 @@ int lcd_call_bam_regions_ext2(const char *bam_path, const char *bai_path, const 
     lcd_run_ext2_t x2; lcd_mods_opt_t mods_opt;
     if (int rc = ModsSink::parse(W, ext2, &x2, &mods_opt)) return rc;
     if (int rc = DepthSink::parse(W, x2)) return rc;
+    lcd_run_ext2_split_t xs;
+    {
+        const char *other[3] = {bam_out ? bam_out->path : nullptr, x2.mods_path, x2.depth_path};
+        if (int rc = SplitSink::parse(W, ext2, &xs, 3, other)) return rc;
+    }
     if (int rc = check_aln_opt(W, opt)) return rc;
     if (opt && opt->aln && opt->aln->format == LCD_ALN_SAM) return set_err(-2, W + ": SAM text is not supported by this driver (lcd_write_phased on the called chunks writes it)");
     if (opt && opt->idx) return set_err(-4, W + ": index options are not supported by this driver");
@@ -552,12 +557,21 @@ int lcd_call_bam_regions_ext2(const char *bam_path, const char *bai_path, const 
         rc = depth.open(W, x2);
         for (int c = 0; c < n && !rc; ++c) rc = depth.chunk(handles[c], chunks[c].first, chrom);
     }
+    SplitSink split;             // the read sets and the haplotag list, likewise; the plan is lcd_write_phased's: one contig, file order
+    if (rc == 0 && (xs.split_prefix || xs.haplotag_path)) {
+        int n_ref = 0; char **names = nullptr; int64_t *lens = nullptr;
+        rc = xs.haplotag_path ? lcd_bam_contigs(bam_path, &n_ref, &names, &lens) : 0;
+        if (!rc) rc = split.open(W, xs, n_ref, names, 0);
+        if (names) lcd_bam_contigs_free(n_ref, names, lens);
+        if (!rc) rc = split.window(n, chunks, nullptr, nullptr);
+    }
     if (rc == 0 && bam_out) {   // (a failure here leaves the records and the text valid)
         lcd_writer_opt_t wo; memset(&wo, 0, sizeof(wo)); wo.refine_stats = out ? out->refine_stats : nullptr;
         rc = lcd_write_phased(bam_path, n, chunks, bam_out, &wo);
     }
     if (mods.active()) { const std::string m0 = g_err; const int rc3 = mods.finish(rc == 0); if (!rc) rc = rc3; else g_err = m0; }
     if (depth.active()) { const std::string m0 = g_err; const int rc3 = depth.finish(rc == 0); if (!rc) rc = rc3; else g_err = m0; }
+    if (split.active()) { const std::string m0 = g_err; const int rc3 = split.finish(rc == 0); if (!rc) rc = rc3; else g_err = m0; }
     const std::string m = g_err;
     drop_inputs();
     g_err = m;

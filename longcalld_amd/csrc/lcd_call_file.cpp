@@ -369,6 +369,7 @@ struct Run {
     FieldsRun *fields = nullptr;           // the TE library and the names mode of the call (read-only here; its counters belong to the call stage)
     ModsSink mods;                         // the methylation table (lcd_run_ext2_t.mods_path): written by the write stage, chunk by chunk in plan order
     DepthSink depth;                       // the depth track (lcd_run_ext2_t.depth_path): likewise
+    SplitSink split;                       // the per-haplotype read sets and the haplotag list (lcd_run_ext2_split_t): likewise, with the alignment writer's plan
     // the first error of any stage
     std::mutex err_mu; int err_code = 0; std::string err_msg; std::atomic<bool> failed{false};
     std::atomic<long long> peak{0};
@@ -444,6 +445,7 @@ struct Run {
         if (!rc && bam) rc = lcd_bam_writer_append(bam, w.n, w.chunks.data(), w.tids.data(), &w.prev);
         if (mods.active()) for (int c = 0; c < w.n && !rc; ++c) rc = mods.chunk(w.handles[c], w.chunks[c].first, w.chroms[c]);
         if (depth.active()) for (int c = 0; c < w.n && !rc; ++c) rc = depth.chunk(w.handles[c], w.chunks[c].first, w.chroms[c]);
+        if (split.active() && !rc) rc = split.window(w.n, w.chunks.data(), w.tids.data(), &w.prev);
         sample_peak();
         if (rc) { fail(rc, g_err); return rc; }
         std::lock_guard<std::mutex> lk(err_mu);
@@ -478,6 +480,11 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
     lcd_run_ext2_t x2; lcd_mods_opt_t mods_opt;
     if (int rc = ModsSink::parse(W, ext2, &x2, &mods_opt)) return rc;
     if (int rc = DepthSink::parse(W, x2)) return rc;
+    lcd_run_ext2_split_t xs;
+    {
+        const char *other[4] = {job ? job->vcf_path : nullptr, job && job->bam_out ? job->bam_out->path : nullptr, x2.mods_path, x2.depth_path};
+        if (int rc = SplitSink::parse(W, ext2, &xs, 4, other)) return rc;
+    }
     const lcd_index_opt_t *idx = opt ? opt->idx : nullptr;
     const lcd_vcf_fields_t *fields = opt ? opt->fields : nullptr;
     lcd_vcf_fields_out_t *fields_out = out ? out->fields_out : nullptr;
@@ -606,9 +613,12 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
             R.bam = lcd_bam_writer_open(bam0, job->bam_out, &wo);
             if (!R.bam) { lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats); return -30; }
         }
-        if ((x2.mods_path && R.mods.open(W, x2, mods_opt)) || (x2.depth_path && R.depth.open(W, x2))) {
+        std::vector<const char *> ref_names; for (const std::string &s : R.names) ref_names.push_back(s.c_str());
+        if ((x2.mods_path && R.mods.open(W, x2, mods_opt)) || (x2.depth_path && R.depth.open(W, x2)) ||
+            ((xs.split_prefix || xs.haplotag_path) && R.split.open(W, xs, (int)ref_names.size(), ref_names.data(), in ? in->sort_output : 0))) {
             const std::string m0 = g_err;
             if (R.mods.active()) R.mods.finish(false);
+            if (R.depth.active()) R.depth.finish(false);
             if (R.bam) lcd_bam_writer_abort(R.bam);
             lcd_vcf_writer_abort(R.vcf); lcd_file_stats_free(stats);
             return set_err(-30, m0);
@@ -666,6 +676,7 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
     // the table is finished after the other outputs: a run that fails anywhere, their close included, leaves no table and no statistics of it
     if (R.mods.active()) { const int rc3 = R.mods.finish(!rc); if (!rc && rc3) { rc = rc3; R.err_msg = g_err; } }
     if (R.depth.active()) { const int rc3 = R.depth.finish(!rc); if (!rc && rc3) { rc = rc3; R.err_msg = g_err; } }
+    if (R.split.active()) { const int rc3 = R.split.finish(!rc); if (!rc && rc3) { rc = rc3; R.err_msg = g_err; } }
     if (job->keep_records) {
         stats->records = dup_vec(R.kept); stats->n_kept_records = (int)R.kept.size();
     }

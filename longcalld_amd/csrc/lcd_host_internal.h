@@ -235,6 +235,26 @@ private:
     int put(int n, const int64_t *beg, const int64_t *end, const uint64_t *val, const char *chrom);      // val: depths, or the windows' sums
     int flush_held();
 };
+// the per-haplotype read sets of a driver run (lcd_run_ext2_split_t; lcd_split.cpp): the refusals, the three FASTQ files and the haplotag list, every chunk's
+// lcd_chunk_split_reads in plan order with the plan the alignment writer makes for that chunk (rules 4 and 5), the sums of the statistics.  With gz every append
+// of a FASTQ file is compressed in HBM and close adds the EOF member.  One thread at a time.
+struct SplitSink {
+    FILE *f[4] = {nullptr, nullptr, nullptr, nullptr}; std::string path[4];      // streams 0 none, 1, 2; 3: the list
+    bool gz = false; int sort_output = 0; lcd_split_opt_t opt; lcd_split_stats_t sum; lcd_split_stats_t *stats_out = nullptr; lcd_sam_names_t *names = nullptr;
+    // ext2 as the caller's struct of any size -> *xs (what lies behind its `size` reads as zero); other: the run's further output paths (NULL entries: none).
+    // -4 before anything is created
+    static int parse(const std::string &W, const lcd_run_ext2_t *ext2, lcd_run_ext2_split_t *xs, int n_other, const char *const *other);
+    int open(const std::string &W, const lcd_run_ext2_split_t &xs, int n_ref, const char *const *ref_names, int sort_output);     // creates the files
+    // the chunks of a window, as lcd_bam_writer_append takes them (tids NULL: one contig; prev: the chunk in front of the window or NULL)
+    int window(int n, const lcd_call_chunk_t *chunks, const int *tids, const lcd_stitch_carry_t *prev);
+    int finish(bool ok);     // ok: the EOF members, close, *stats_out; else (or when that fails): close and remove.  0 or -30
+    bool active() const { return f[0] || f[3]; }
+    ~SplitSink() { drop(); }
+    SplitSink() = default; SplitSink(const SplitSink &) = delete; SplitSink &operator=(const SplitSink &) = delete;
+private:
+    int put(int s, const lcd_split_t *h);
+    void drop();             // closes and removes what is open
+};
 struct VarRegionRec { int region, n_cons, rows[2], cap, n_vars, alt_bytes; uint64_t rec_off, alt_off, prof_off, se_off; };
 
 } // namespace lcd_internal
@@ -335,6 +355,26 @@ struct lcd_chunk_s {
     lcd_refine_log_t *refine_log = nullptr;                // lcd_chunk_set_refine: the sink of the chunk's rounds; with it the writer refines the chunk's records
     ~lcd_chunk_s() { free(iv_off); free(ivs); free(iv_in_chunk); if (stream) lcd_inflated_free(stream); lcd_refine_log_free(refine_log); }
 };
+
+// the contigs' names in HBM (lcd_sam_names_create, lcd_bam_out.cpp): back to back in `pool`, name r = [offs[r], offs[r + 1]); read by the SAM text and the haplotag list
+struct lcd_sam_names_s { DevBuf pool, offs; size_t pool_bytes = 0; int n_ref = 0, device = 0; };
+
+namespace lcd_internal __attribute__((visibility("hidden"))) {
+// the records with skip[i] == 0 (NULL: all) in the order `order` names them (NULL: table order)
+inline int pick_selected(const std::string &W, const lcd_chunk_t *c, const uint8_t *skip, const int *order, std::vector<int> &pick) {
+    const int n_rec = (int)c->rec_beg.size();
+    int m = 0;
+    for (int i = 0; i < n_rec; ++i) if (!skip || !skip[i]) ++m;
+    pick.assign(m, 0); std::vector<uint8_t> seen(n_rec + 1, 0);
+    for (int k = 0, i = 0; k < m; ++k) {
+        if (order) i = order[k]; else { while (skip && skip[i]) ++i; }
+        if (i < 0 || i >= n_rec || (skip && skip[i]) || seen[i]) return set_err(-4, W + ": `order` must name every record that is not skipped exactly once");
+        seen[i] = 1; pick[k] = i;
+        if (!order) ++i;
+    }
+    return 0;
+}
+} // namespace lcd_internal
 
 // ---- noisy-region intervals with cgranges' index order and merge rule (lcd_noisy_regs.cpp).  These names have C linkage and default visibility: written inside
 // an extern "C" block they have been dynamic symbols of the library from the start, and the export surface stays as it is ----

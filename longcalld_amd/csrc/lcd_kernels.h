@@ -50,6 +50,10 @@ void lcd_launch_mods_compact(const ModsIn &in, long long n_pos, ModsRow *rows, i
 void lcd_launch_depth_mark(const DepthIn &in, hipStream_t st);
 void lcd_launch_depth_tiles(const DepthIn &in, DepthPart *parts, hipStream_t st);
 void lcd_launch_depth_scan(DepthPart *parts, long long n_tiles, int *n_rows, hipStream_t st);
+// split_kernel.hip: the records of a plan as FASTQ entries per haplotype and haplotag list lines, one wavefront per record: the rows of the measure pass, then
+// (with the host's offsets in the rows) the text; fq[stream] and list are the four output buffers
+void lcd_launch_split_measure(const SplitIn &in, SplitRow *rows, hipStream_t st);
+void lcd_launch_split_emit(const SplitIn &in, const SplitRow *rows, uint8_t *fq0, uint8_t *fq1, uint8_t *fq2, uint8_t *list, hipStream_t st);
 void lcd_launch_depth_rows(const DepthIn &in, const DepthPart *parts, DepthRow *rows, int cap, hipStream_t st);     // cap: the entries of rows (*n_rows of the scan)
 // bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
 // counters; compact: scan of the workgroups' run heads + the dense chunk list)

@@ -313,6 +313,20 @@ struct DepthIn { const DepthJob *jobs; int *diff; unsigned long long *stats; lon
 // a tile's partial: the three plane sums and the number of run heads; after the scan: the sums of the tiles in front of it
 struct DepthPart { int s[3], heads; };
 struct DepthRow { long long beg; unsigned d[3], pad; };
+// ---------------- the per-haplotype read sets (split_kernel.hip) ----------------
+// one record the plan names ([src, src + len): its block_size word and body, len >= 36) with its read's haplotype 0 / 1 / 2 and phase set (0 and 0 for a record
+// the loader filtered)
+struct SplitJob { uint64_t src; uint32_t len; int hap; long long ps; };
+// the measure pass's row of a record: its stream (-1: in neither output; else its haplotype), the exact byte lengths of its FASTQ entry (0: none) and its list
+// line (0 without the list); flags bit 0: 0x100 / 0x800, bit 1: broken layout, bit 2: reverse strand, bit 3: l_seq == 0 (bits 2 and 3 only with a stream).  The
+// host fills fq_off (inside the record's stream) and list_off for the emit pass
+#define LCD_SPLIT_NOT_PRIMARY 1u
+#define LCD_SPLIT_BAD_LAYOUT 2u
+#define LCD_SPLIT_REVERSE 4u
+#define LCD_SPLIT_NO_SEQ 8u
+struct SplitRow { unsigned long long fq_len, list_len, fq_off, list_off; int stream; uint32_t flags; };
+// names / name_off / n_ref: the contigs' names as lcd_sam_names_t holds them (read only with `list`)
+struct SplitIn { const SplitJob *jobs; const uint8_t *names; const unsigned *name_off; int n_ref, n_jobs, comment, list; };
 struct EdJob {
     uint64_t q_off, t_off;
     int qlen, tlen;
