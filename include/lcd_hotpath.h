@@ -1582,6 +1582,121 @@ int lcd_call_bam_regions_ext2(const char *bam_path, const char *bai_path, const 
                               const int64_t *reg_end, int min_mapq, const lcd_cfg_t *cfg, lcd_call_chunk_t *chunks, lcd_var1_t **records, int *n_records, char **vcf_body,
                               lcd_bam_out_t *bam_out, const lcd_run_opt_t *opt, const lcd_run_out_t *out, const lcd_run_ext2_t *ext2);
 
+/* ---- haplotag: the reads of a chunk against the phased sites of a VCF (lcd_phased_vcf.cpp, haplotag_kernel.hip, lcd_haplotag.cpp) ----
+ * The reference has no such command; these are PROJECT RULES, restated in Python in tests/haplotag_common.py.  They give the haps[read] / phase_sets[read]
+ * arrays every per-haplotype output takes (tag rewrite, SAM text, mods, depth, read sets) without a calling run.  Positions are 1-based.
+ *
+ * The reader (host only, no HIP call; gzopen / gzread: plain, gzip and BGZF input).  The `#CHROM` line names the samples; `sample` NULL is the first one.  -4: an
+ * unknown sample, a file without a sample column or without a `#CHROM` line, a data line with fewer columns than the header (the message names the line), a NULL
+ * argument, max_indel < 1.  -30: the file cannot be opened or read (a gzip member cut short included).  Every data line is judged by the first rule that holds,
+ * and that one is counted:
+ *    1 CHROM is none of `names`                                          n_unknown_contig
+ *    2 FILTER is neither PASS nor `.`                                     n_filtered
+ *    3 the sample's GT (FORMAT's first key must be GT, else rule 3c): a '/' in it n_unphased; `a|b`, both numeric, a == b: n_hom; (3c) anything else --
+ *      no GT, a `.`, haploid, more than two alleles, a number beyond the ALT list --  n_other_gt
+ *    4 exactly one of a, b must be 0, else                                 n_both_alt.  The ALT allele is the non-zero one; hap_of_alt is 1 when it is a,
+ *      2 when it is b
+ *    5 REF or the ALT allele is empty or holds a byte outside ACGTNacgtn (symbolic alleles, `*`, breakends)    n_symbolic
+ *    6 the pair is normalised in upper case: the longest common suffix is stripped while both are longer than 1, then common first bases while both are longer
+ *      than 1, POS advancing.  SNV: lengths 1 and 1, bases differ.  INS: REF 1 long, ALT longer, first bases equal; len = the inserted bases.  DEL: ALT 1 long,
+ *      REF longer, first bases equal; len = the deleted bases.  Anything else            n_complex
+ *    7 an indel with len > max_indel (default 50)                          n_long_indel
+ *    8 snvs_only and an indel                                              n_indel_off
+ * What is left is a site (n_sites = n_snv + n_ins + n_del).  Its phase set is the integer value of the sample's PS key when that is > 0; the sites of a contig
+ * without one share ONE set whose value is the POS of the first of them in table order.  Lines need not be sorted: a contig's table is its sites stable-sorted
+ * by normalised POS (input order among equals; duplicates stay).  Per contig, a structure of arrays: pos (the anchor), kind (0 SNV, 1 INS, 2 DEL), hap_of_alt,
+ * len (1 for an SNV), ref_code / alt_code (the nt16 codes of the SNV's bases, `=ACMGRSVTWYHKDBN`; 0 for indels), ins_off (into the contig's pool of the inserted
+ * bases' nt16 codes, one per byte; 0 for others), ps_idx (dense, numbered by first appearance in table order), ps_value[ps_idx], and max_footprint.
+ * A site's footprint: SNV [pos, pos], INS [pos, pos + 1], DEL [pos, pos + len]; max_footprint is the largest footprint length of the contig (0 without sites).
+ *
+ * lcd_chunk_haplotag works on a resolved chunk's KEPT records where the inflate left them in HBM: the operations (the record's own, or its CG field's by the
+ * loader's rule), the packed bases and the qualities; no digars.  A record the loader filtered is no read and gets nothing.  `contig` is the index into the
+ * reader's `names`.  The contig's table goes up once per device and is reused by every later call; only the four per-read arrays and the statistics come down
+ * (the pair arrays on request, for the tests).
+ *   span       [pos0 + 1, end]: end = pos0 + the lengths of the M / = / X / D / N operations.  A record's candidates are the table's sites with
+ *              span.beg - (max_footprint - 1) <= pos <= span.end, a contiguous range; its PAIRS are those of them whose footprint intersects the span.
+ *   verdict    of a pair, over the whole operation list, whatever the order the operations are visited in:
+ *              disturbed   a D or N operation (length > 0) whose reference interval intersects the footprint, or an I operation (length > 0) at a boundary
+ *                          r - 1 | r with pos < r <= the footprint's end -- unless that operation is the pair's own alt match;
+ *              alt match   DEL: a D operation that starts at pos + 1 and has length len.  INS: an I operation at the boundary pos | pos + 1 of length len whose
+ *                          read bases' nt16 codes equal the site's (all of them inside l_seq);
+ *              base        (SNV) the M / = / X operation that contains pos gives the read's nt16 code there: alt_code ALT, ref_code REF, another one OTHER; a
+ *                          quality byte below min_bq turns it into LOWQ (0xff, absent qualities, passes); a base index outside l_seq (l_seq == 0 included) OTHER.
+ *              By the first that holds: the footprint is not inside the span NONE; disturbed OTHER; alt match ALT; an SNV: its base verdict; else (an indel
+ *              site, covered and undisturbed) REF.  S, H, P, zero-length operations and unknown codes do nothing.  A record with l_seq == 0 (n_no_seq) can
+ *              match no insertion: the I operation disturbs.
+ *   votes      ALT votes for hap_of_alt, REF for the other haplotype; NONE, OTHER and LOWQ do not vote.  The record's phase set is the one with the most votes
+ *              n1 + n2; among equals the one whose first voting site comes first in table order.  hap = 1 when n1 - n2 >= min_diff, 2 when n2 - n1 >= min_diff,
+ *              else 0; phase_set = ps_value when hap != 0, else 0; n1 / n2 are the chosen set's, 0 / 0 when nothing voted.  n_multi_ps: records with votes in
+ *              more than one set.
+ *   layout     a record with l_seq < 0 or whose name, operation words, packed bases and qualities do not fit its block_size has hap 0, no candidates, and is
+ *              counted in n_bad_record.  No lane reads outside the record or the tables.
+ * The verdict depends on the record and the contig's table alone, so a record that two overlapping chunks hold gets the same answer in both: a run over many
+ * chunks needs no stitch and no flip.
+ * Four launches: measure (one wavefront per record: layout, span, candidate range by binary search), scan (one workgroup: the exclusive prefix of the candidate
+ * counts), mark (one wavefront per record, 64 operations per step with carried 64-bit scans of the reference and query offsets; every lane ORs its own
+ * operation's bits into the pair bytes, four to a 32-bit word), reduce (one wavefront per record: the verdict bytes and the votes per phase set by wave sums).
+ * Integers only.  NULL with -4 before any HIP call: a NULL chunk / table, a chunk not made from a BAM or not resolved, a contig outside the table's, min_diff < 1,
+ * min_bq outside 0 ... 254.
+ * Verdict bytes: 0 NONE, 1 REF, 2 ALT, 3 OTHER, 4 LOWQ; 255: a candidate that is no pair. */
+typedef struct lcd_hapvcf_opt_t { int max_indel, snvs_only, reserved[2]; } lcd_hapvcf_opt_t;
+typedef struct lcd_hapvcf_stats_t {
+    int64_t n_lines, n_sites, n_unknown_contig, n_filtered, n_unphased, n_hom, n_other_gt, n_both_alt, n_symbolic, n_complex, n_long_indel, n_indel_off,
+            n_snv, n_ins, n_del, n_phase_sets;
+} lcd_hapvcf_stats_t;
+typedef struct lcd_phased_vcf_s lcd_phased_vcf_t;
+void lcd_hapvcf_opt_default(lcd_hapvcf_opt_t *opt);
+lcd_phased_vcf_t *lcd_phased_vcf_read(const char *path, const char *sample /* NULL: the first */, int n_contigs, const char *const *names, const lcd_hapvcf_opt_t *opt /* NULL: defaults */,
+                                      lcd_hapvcf_stats_t *stats /* may be NULL */);
+int lcd_phased_vcf_n_contigs(const lcd_phased_vcf_t *v);
+int64_t lcd_phased_vcf_n_sites(const lcd_phased_vcf_t *v, int contig);        /* -4: contig outside the table's */
+int lcd_phased_vcf_n_phase_sets(const lcd_phased_vcf_t *v, int contig);
+int64_t lcd_phased_vcf_pool_size(const lcd_phased_vcf_t *v, int contig);
+int lcd_phased_vcf_max_footprint(const lcd_phased_vcf_t *v, int contig);
+/* any output may be NULL; pos / ins_off: n_sites 64-bit entries, kind / hap_of_alt / ref_code / alt_code: n_sites bytes, len / ps_idx: n_sites ints,
+ * ps_value: n_phase_sets, pool: pool_size bytes */
+int lcd_phased_vcf_sites_to_host(const lcd_phased_vcf_t *v, int contig, int64_t *pos, uint8_t *kind, uint8_t *hap_of_alt, int *len, uint8_t *ref_code, uint8_t *alt_code,
+                                 int64_t *ins_off, int *ps_idx, int64_t *ps_value, uint8_t *pool);
+void lcd_phased_vcf_free(lcd_phased_vcf_t *v);
+int lcd_phased_vcf_errno(void);                                          /* of this thread's last lcd_phased_vcf_read: 0, -4 or -30 */
+const char *lcd_phased_vcf_error(void);                                  /* its message (the reader is host-only code of its own and does not set lcd_last_error) */
+
+typedef struct lcd_haplotag_opt_t { int min_bq, min_diff, reserved[2]; } lcd_haplotag_opt_t;
+typedef struct lcd_haplotag_stats_t {
+    int64_t n_records, n_pairs, n_verdict[5] /* NONE REF ALT OTHER LOWQ */, n_tagged[3] /* hap 0 1 2 */, n_multi_ps, n_cg, n_bad_record, n_no_seq;
+    double ms_measure, ms_mark, ms_reduce;
+} lcd_haplotag_stats_t;
+typedef struct lcd_haplotag_s lcd_haplotag_t;
+void lcd_haplotag_opt_default(lcd_haplotag_opt_t *opt);                    /* min_bq 0, min_diff 1 */
+int lcd_haplotag_opt_check(const lcd_haplotag_opt_t *opt);                /* 0 / -4 (host only) */
+lcd_haplotag_t *lcd_chunk_haplotag(const lcd_chunk_t *chunk, const lcd_phased_vcf_t *vcf, int contig, const lcd_haplotag_opt_t *opt /* NULL: defaults */,
+                                   lcd_haplotag_stats_t *stats /* may be NULL */);
+int lcd_haplotag_n_reads(const lcd_haplotag_t *h);
+int lcd_haplotag_n_records(const lcd_haplotag_t *h);                       /* the kept records: one per read, in the reads' order */
+int lcd_haplotag_to_host(const lcd_haplotag_t *h, int *haps, int64_t *phase_sets, int *n1, int *n2);      /* per kept read; any may be NULL */
+/* for tests: per kept record the first candidate's index in the contig's table and the candidates' offsets (n_records + 1 entries, the last one the total), and one
+ * verdict byte per candidate (copied from the device by this call) */
+int64_t lcd_haplotag_n_candidates(const lcd_haplotag_t *h);
+int lcd_haplotag_pairs_to_host(const lcd_haplotag_t *h, int64_t *first_site, int64_t *cand_off, uint8_t *verdict);
+void lcd_haplotag_free(lcd_haplotag_t *h);
+/* lcd_haplotag_files: a whole BAM (or the BAMs of one sample) against a phased VCF.  It IS lcd_call_files_ext2 with another middle stage: the plan, the windows,
+ * the load stage, the write stage and the closing order are shared (one function in lcd_call_file.cpp takes the stage as a parameter).  The middle stage runs
+ * lcd_chunk_haplotag on every chunk of the window (contig i of the BAM header is contig i of the site tables, read once with the header's names) and hands the
+ * result on as the chunk's first.state (lcd_hap_state_init(n_reads, 0) with haps and phase_sets filled), so the alignment writer (BAM or SAM, HP / PS tags), the
+ * methylation table, the depth track and the read sets run unchanged.  Because a record's answer depends on the record and its contig's table alone, two
+ * overlapping chunks agree on a record they both hold: no stitch, no flip.  No VCF is written and nothing goes to stdout unless a SAM output to "-" asks for it.
+ * hopt's FIRST member is its own size (members behind `size` read as zero; a size that does not reach vcf_path is -4): vcf_path, sample (NULL: the first),
+ * max_indel (0: 50), snvs_only, min_bq, min_diff (0: 1), *vcf_stats (the reader's), *stats (the sums of lcd_haplotag_stats_t over the chunks; filled only by a
+ * run that succeeds).  Refused with -4 before anything is created: job->vcf_path, opt->fields, opt->aln->refine, no vcf_path, negative max_indel / min_diff, min_bq
+ * outside 0 ... 254, and a run without any output (no bam_out, mods_path, depth_path, split_prefix, haplotag_path).  Index handling (.bai / .fai, write_out_bai)
+ * and every other refusal are those of a calling run; the reader's errors come back with its codes (-4 / -30).  stats->ms_call is the middle stage's time. */
+typedef struct lcd_haplotag_run_t {
+    size_t size;
+    const char *vcf_path, *sample; int max_indel, snvs_only, min_bq, min_diff; lcd_hapvcf_stats_t *vcf_stats; lcd_haplotag_stats_t *stats;
+} lcd_haplotag_run_t;
+int lcd_haplotag_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_haplotag_run_t *hopt, const lcd_run_opt_t *opt,
+                       lcd_file_stats_t *stats, const lcd_run_out_t *out, const lcd_run_ext2_t *ext2);
+
 #ifdef __cplusplus
 }
 #endif

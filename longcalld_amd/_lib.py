@@ -269,6 +269,37 @@ class LcdModsStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in MODS_STAT_COUNTERS] + [(n, C.c_double) for n in ("ms_site_map", "ms_pileup", "ms_compact")]
 
 
+HAPVCF_STAT_KEYS = ("n_lines", "n_sites", "n_unknown_contig", "n_filtered", "n_unphased", "n_hom", "n_other_gt", "n_both_alt", "n_symbolic", "n_complex", "n_long_indel",
+                    "n_indel_off", "n_snv", "n_ins", "n_del", "n_phase_sets")
+
+
+class LcdHapvcfOpt(C.Structure):
+    """lcd_hapvcf_opt_t: the options of lcd_phased_vcf_read"""
+    _fields_ = [("max_indel", C.c_int), ("snvs_only", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class LcdHapvcfStats(C.Structure):
+    """lcd_hapvcf_stats_t: the data lines, the sites, and the lines every rule left out"""
+    _fields_ = [(n, C.c_int64) for n in HAPVCF_STAT_KEYS]
+
+
+class LcdHaplotagOpt(C.Structure):
+    """lcd_haplotag_opt_t: the options of lcd_chunk_haplotag"""
+    _fields_ = [("min_bq", C.c_int), ("min_diff", C.c_int), ("reserved", C.c_int * 2)]
+
+
+class LcdHaplotagStats(C.Structure):
+    """lcd_haplotag_stats_t: records, pairs, pairs per verdict (NONE REF ALT OTHER LOWQ), reads per haplotype, and the wall-clock split of the call"""
+    _fields_ = [("n_records", C.c_int64), ("n_pairs", C.c_int64), ("n_verdict", C.c_int64 * 5), ("n_tagged", C.c_int64 * 3), ("n_multi_ps", C.c_int64), ("n_cg", C.c_int64),
+                ("n_bad_record", C.c_int64), ("n_no_seq", C.c_int64), ("ms_measure", C.c_double), ("ms_mark", C.c_double), ("ms_reduce", C.c_double)]
+
+
+class LcdHaplotagRun(C.Structure):
+    """lcd_haplotag_run_t: lcd_haplotag_files' own options; the first member is the struct's size"""
+    _fields_ = [("size", C.c_size_t), ("vcf_path", C.c_char_p), ("sample", C.c_char_p), ("max_indel", C.c_int), ("snvs_only", C.c_int), ("min_bq", C.c_int), ("min_diff", C.c_int),
+                ("vcf_stats", C.POINTER(LcdHapvcfStats)), ("stats", C.POINTER(LcdHaplotagStats))]
+
+
 class LcdDepthOpt(C.Structure):
     """lcd_depth_opt_t: the options of lcd_chunk_depth (window: the drivers' window rule, not read by the chunk call)"""
     _fields_ = [("skip_dels", C.c_int), ("window", C.c_int), ("reserved", C.c_int * 2)]
@@ -412,6 +443,10 @@ EXPORTS = [
     "lcd_mods_opt_default", "lcd_mods_opt_check", "lcd_chunk_mod_pileup", "lcd_mods_n_rows", "lcd_mods_rows_to_host", "lcd_mods_free", "lcd_mods_combine_rows", "lcd_mods_format", "lcd_call_files_ext2", "lcd_call_bam_regions_ext2",
     "lcd_depth_opt_default", "lcd_depth_opt_check", "lcd_chunk_depth", "lcd_depth_n_rows", "lcd_depth_rows_to_host", "lcd_depth_free", "lcd_depth_tile", "lcd_depth_windows", "lcd_depth_format",
     "lcd_split_opt_default", "lcd_split_opt_check", "lcd_split_paths", "lcd_split_offsets", "lcd_chunk_split_reads", "lcd_split_size", "lcd_split_dev_ptr", "lcd_split_to_host", "lcd_split_free",
+    "lcd_hapvcf_opt_default", "lcd_phased_vcf_read", "lcd_phased_vcf_n_contigs", "lcd_phased_vcf_n_sites", "lcd_phased_vcf_n_phase_sets", "lcd_phased_vcf_pool_size",
+    "lcd_phased_vcf_max_footprint", "lcd_phased_vcf_sites_to_host", "lcd_phased_vcf_free", "lcd_phased_vcf_errno", "lcd_phased_vcf_error",
+    "lcd_haplotag_opt_default", "lcd_haplotag_opt_check", "lcd_chunk_haplotag", "lcd_haplotag_n_reads", "lcd_haplotag_n_records", "lcd_haplotag_to_host", "lcd_haplotag_n_candidates",
+    "lcd_haplotag_pairs_to_host", "lcd_haplotag_free", "lcd_haplotag_files",
 ]
 
 
@@ -706,6 +741,34 @@ def load_library():
     lib.lcd_split_to_host.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_size_t, u8p]
     lib.lcd_split_free.argtypes = [C.c_void_p]
     lib.lcd_split_free.restype = None
+    lib.lcd_hapvcf_opt_default.argtypes = [C.POINTER(LcdHapvcfOpt)]
+    lib.lcd_hapvcf_opt_default.restype = None
+    lib.lcd_phased_vcf_read.restype = C.c_void_p
+    lib.lcd_phased_vcf_read.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), C.POINTER(LcdHapvcfOpt), C.POINTER(LcdHapvcfStats)]
+    lib.lcd_phased_vcf_n_contigs.argtypes = [C.c_void_p]
+    for f in (lib.lcd_phased_vcf_n_sites, lib.lcd_phased_vcf_n_phase_sets, lib.lcd_phased_vcf_pool_size, lib.lcd_phased_vcf_max_footprint):
+        f.argtypes = [C.c_void_p, C.c_int]
+    lib.lcd_phased_vcf_n_sites.restype = C.c_int64
+    lib.lcd_phased_vcf_pool_size.restype = C.c_int64
+    lib.lcd_phased_vcf_sites_to_host.argtypes = [C.c_void_p, C.c_int, i64p_m, u8p, u8p, i32p, u8p, u8p, i64p_m, i32p, i64p_m, u8p]
+    lib.lcd_phased_vcf_free.argtypes = [C.c_void_p]
+    lib.lcd_phased_vcf_free.restype = None
+    lib.lcd_phased_vcf_errno.argtypes = []
+    lib.lcd_phased_vcf_error.argtypes = []
+    lib.lcd_phased_vcf_error.restype = C.c_char_p
+    lib.lcd_haplotag_opt_default.argtypes = [C.POINTER(LcdHaplotagOpt)]
+    lib.lcd_haplotag_opt_default.restype = None
+    lib.lcd_haplotag_opt_check.argtypes = [C.POINTER(LcdHaplotagOpt)]
+    lib.lcd_chunk_haplotag.restype = C.c_void_p
+    lib.lcd_chunk_haplotag.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LcdHaplotagOpt), C.POINTER(LcdHaplotagStats)]
+    lib.lcd_haplotag_n_reads.argtypes = [C.c_void_p]
+    lib.lcd_haplotag_n_records.argtypes = [C.c_void_p]
+    lib.lcd_haplotag_to_host.argtypes = [C.c_void_p, i32p, i64p_m, i32p, i32p]
+    lib.lcd_haplotag_n_candidates.argtypes = [C.c_void_p]
+    lib.lcd_haplotag_n_candidates.restype = C.c_int64
+    lib.lcd_haplotag_pairs_to_host.argtypes = [C.c_void_p, i64p_m, i64p_m, u8p]
+    lib.lcd_haplotag_free.argtypes = [C.c_void_p]
+    lib.lcd_haplotag_free.restype = None
     lib.lcd_mods_combine_rows.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p]
     lib.lcd_mods_format.argtypes = [C.c_int, i64p_m, C.c_char_p, u32p, C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     _lib = lib

@@ -1758,6 +1758,86 @@ def chunk_mod_pileup(chunk, haps, ref, ref_beg, ref_end, code="m", threshold=204
     return chunk.mod_pileup(haps, ref, ref_beg, ref_end, code, threshold, combine_strands)
 
 
+class PhasedVcf:
+    """lcd_phased_vcf_read (host only): the heterozygous phased sites of one sample of a VCF (plain, gzip or BGZF) as per-contig tables.  names: the contigs, in
+    the order lcd_chunk_haplotag's `contig` counts them.  .stats: lcd_hapvcf_stats_t as a dict; .sites(contig): the table as a dict of arrays"""
+
+    def __init__(self, path, names, sample=None, max_indel=50, snvs_only=False):
+        from ._lib import LcdHapvcfOpt, LcdHapvcfStats
+        lib = load_library()
+        self.lib, self.names = lib, [str(n) for n in names]
+        o = LcdHapvcfOpt(); lib.lcd_hapvcf_opt_default(C.byref(o))
+        o.max_indel, o.snvs_only = int(max_indel), int(bool(snvs_only))
+        arr = (C.c_char_p * max(len(self.names), 1))(*[n.encode() for n in self.names])
+        st = LcdHapvcfStats()
+        self.h = lib.lcd_phased_vcf_read(str(path).encode(), None if sample is None else str(sample).encode(), len(self.names), arr, C.byref(o), C.byref(st))
+        if not self.h:
+            raise LcdError(f"lcd_phased_vcf_read failed: error {lib.lcd_phased_vcf_errno()}: {lib.lcd_phased_vcf_error().decode()}")
+        self.stats = {k: int(getattr(st, k)) for k, _t in st._fields_}
+
+    def sites(self, contig):
+        lib, c = self.lib, int(contig)
+        n = int(lib.lcd_phased_vcf_n_sites(self.h, c))
+        if n < 0:
+            raise LcdError("PhasedVcf.sites: contig outside the tables'")
+        nps, npool = int(lib.lcd_phased_vcf_n_phase_sets(self.h, c)), int(lib.lcd_phased_vcf_pool_size(self.h, c))
+        a = dict(pos=np.zeros(n, np.int64), kind=np.zeros(n, np.uint8), hap_of_alt=np.zeros(n, np.uint8), len=np.zeros(n, np.int32), ref_code=np.zeros(n, np.uint8),
+                 alt_code=np.zeros(n, np.uint8), ins_off=np.zeros(n, np.int64), ps_idx=np.zeros(n, np.int32), ps_value=np.zeros(nps, np.int64), pool=np.zeros(npool, np.uint8))
+        u8p, i32p, i64p = C.POINTER(C.c_uint8), C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        ptr = lambda k, t: a[k].ctypes.data_as(t)
+        check(lib.lcd_phased_vcf_sites_to_host(self.h, c, ptr("pos", i64p), ptr("kind", u8p), ptr("hap_of_alt", u8p), ptr("len", i32p), ptr("ref_code", u8p), ptr("alt_code", u8p),
+                                               ptr("ins_off", i64p), ptr("ps_idx", i32p), ptr("ps_value", i64p), ptr("pool", u8p)), lib)
+        a["max_footprint"] = int(lib.lcd_phased_vcf_max_footprint(self.h, c))
+        return a
+
+    def close(self):
+        if self.h:
+            self.lib.lcd_phased_vcf_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def phased_vcf_read(path, names, sample=None, max_indel=50, snvs_only=False):
+    """PhasedVcf"""
+    return PhasedVcf(path, names, sample, max_indel, snvs_only)
+
+
+def _haplotag_stats(st):
+    return {k: (list(getattr(st, k)) if k in ("n_verdict", "n_tagged") else getattr(st, k)) for k, _t in st._fields_}
+
+
+def chunk_haplotag(chunk, vcf, contig, min_bq=0, min_diff=1, pairs=False):
+    """lcd_chunk_haplotag: the kept records of a resolved chunk made from a BAM against the phased sites of contig `contig` (an index into vcf.names) ->
+    dict(haps, phase_sets, n1, n2: one entry per kept read; stats); with pairs=True also first_site (per record), cand_off (records + 1) and verdict (one byte per
+    candidate site: 0 NONE, 1 REF, 2 ALT, 3 OTHER, 4 LOWQ, 255 no pair)"""
+    from ._lib import LcdHaplotagOpt, LcdHaplotagStats
+    lib = load_library()
+    o = LcdHaplotagOpt(); lib.lcd_haplotag_opt_default(C.byref(o))
+    o.min_bq, o.min_diff = int(min_bq), int(min_diff)
+    st = LcdHaplotagStats()
+    h = lib.lcd_chunk_haplotag(chunk.h, vcf.h, int(contig), C.byref(o), C.byref(st))
+    if not h:
+        raise LcdError("lcd_chunk_haplotag failed: " + lib.lcd_last_error().decode())
+    try:
+        n = int(lib.lcd_haplotag_n_reads(h))
+        haps, n1, n2, ps = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int64)
+        i32p, i64p = C.POINTER(C.c_int), C.POINTER(C.c_int64)
+        check(lib.lcd_haplotag_to_host(h, haps.ctypes.data_as(i32p), ps.ctypes.data_as(i64p), n1.ctypes.data_as(i32p), n2.ctypes.data_as(i32p)), lib)
+        out = dict(haps=haps.tolist(), phase_sets=ps.tolist(), n1=n1.tolist(), n2=n2.tolist(), stats=_haplotag_stats(st))
+        if pairs:
+            nr, tot = int(lib.lcd_haplotag_n_records(h)), int(lib.lcd_haplotag_n_candidates(h))
+            first, off, ver = np.zeros(nr, np.int64), np.zeros(nr + 1, np.int64), np.zeros(tot, np.uint8)
+            check(lib.lcd_haplotag_pairs_to_host(h, first.ctypes.data_as(i64p), off.ctypes.data_as(i64p), ver.ctypes.data_as(C.POINTER(C.c_uint8))), lib)
+            out.update(first_site=first.tolist(), cand_off=off.tolist(), verdict=ver)
+        return out
+    finally:
+        lib.lcd_haplotag_free(h)
+
+
 def _depth_stats(st):
     return {k: (list(getattr(st, k)) if k == "bases" else getattr(st, k)) for k, _t in st._fields_}
 
@@ -2254,7 +2334,7 @@ def call_files(bams, fasta_path, bais=None, sort_output=False, index=None, **kw)
 def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), regions=(), region_bed_path=None, chunk_len=0, window_chunks=0, overlap=-1, loader_threads=0,
               min_mapq=30, vcf_path=None, vcf_bgzf=0, no_vcf_header=0, sample_name=None, source_version=None, cmdline=None, date_yyyymmdd=None, bam_out=None, cfg=None,
               keep_records=False, index=None, _inputs=None, te_fasta=None, rnames=None, refine=False, aln_format="bam", vcf_index=None, mods=None, depth=None,
-              split=None):
+              split=None, _haplotag=None):
     """lcd_call_files with the job's one file: a whole indexed BAM + a FASTA with its .fai -> the VCF file (vcf_path None: stdout) and, with bam_out = dict(path[,
     pg_line, block_payload]), the phased BAM.  -> dict of lcd_file_stats_t's counters; with keep_records also "chunks" (per planned chunk tid, reg_beg, reg_end, n_reads,
     n_passes, flip_hap, flip_pre_PS, flip_cur_PS, n_records), "records" (as chunks_call gives them) and, with bam_out, "bam_out" = its counters.
@@ -2320,7 +2400,22 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
     if vio is not None:
         from ._lib import LcdRunExt
         ext = LcdRunExt(vcf_idx=C.pointer(vio), vcf_idx_stats=C.pointer(vist))
-    if split is not None:
+    hvs = hts = None
+    if _haplotag is not None:       # haplotag_file(s): the same run with lcd_chunk_haplotag as its middle stage (lcd_haplotag_files)
+        from ._lib import LcdHaplotagRun, LcdHaplotagStats, LcdHapvcfStats
+        if vio is not None:
+            raise ValueError("haplotag_file: a haplotag run writes no VCF (vcf_index=)")
+        hvs, hts = LcdHapvcfStats(), LcdHaplotagStats()
+        hr = LcdHaplotagRun(size=C.sizeof(LcdHaplotagRun), vcf_path=_enc(_haplotag["vcf"]), sample=opt_s(_haplotag.get("sample")), max_indel=int(_haplotag.get("max_indel", 50)),
+                            snvs_only=int(bool(_haplotag.get("snvs_only", False))), min_bq=int(_haplotag.get("min_bq", 0)), min_diff=int(_haplotag.get("min_diff", 1)),
+                            vcf_stats=C.pointer(hvs), stats=C.pointer(hts))
+        x2p = None
+        if split is not None:
+            ext2, mst, dst, spst = _run_ext2_split(mods, depth, split); x2p = C.byref(ext2.x)
+        elif mods is not None or depth is not None:
+            ext2, mst, dst = _run_ext2(mods, depth); x2p = C.byref(ext2)
+        rc = lib.lcd_haplotag_files(args[0], args[1], args[2], C.byref(hr), args[3], args[4], args[5], x2p)
+    elif split is not None:
         # split = dict([prefix, gz, comment, haplotag_list]) (the command line's --split-reads / --split-gz / --split-comment / --haplotag-list): the reads of
         # each haplotype as FASTQ files prefix.none|h1|h2.fastq[.gz] and / or the haplotag list (lcd_run_ext2_split_t), in the order of the output BAM; the result
         # gains "split" = the sums of lcd_split_stats_t over the chunks
@@ -2365,9 +2460,28 @@ def call_file(bam_path, fasta_path, bai_path=None, contig_mode=0, exclude=(), re
             res["depth"] = _depth_stats(dst)
         if spst is not None:
             res["split"] = _split_stats(spst)
+        if hts is not None:
+            res["haplotag"] = _haplotag_stats(hts)
+            res["phased_vcf"] = {k: int(getattr(hvs, k)) for k, _t in hvs._fields_}
         return res
     finally:
         lib.lcd_file_stats_free(C.byref(st))
+
+
+def haplotag_file(bam_path, fasta_path, phased_vcf, sample=None, max_indel=50, snvs_only=False, min_bq=0, min_diff=1, **kw):
+    """lcd_haplotag_files with the job's one file: every read of an indexed BAM against the heterozygous phased sites of phased_vcf (plain, gzip or BGZF; sample None:
+    the first), written through the outputs of call_file that hang on the reads' haplotypes -- bam_out (aln_format "bam" | "sam"), mods=, depth=, split= -- with
+    call_file's input, region, index and run keywords.  No variant is called and no VCF is written; at least one output is needed.  -> call_file's counters (ms_call:
+    the haplotag stage) with "haplotag" = the sums of lcd_haplotag_stats_t over the chunks and "phased_vcf" = lcd_hapvcf_stats_t"""
+    for k in ("vcf_bgzf", "no_vcf_header", "sample_name", "source_version", "cmdline", "date_yyyymmdd", "keep_records", "_haplotag"):
+        if k in kw:
+            raise ValueError(f"haplotag_file: {k}= belongs to a calling run")
+    return call_file(bam_path, fasta_path, _haplotag=dict(vcf=phased_vcf, sample=sample, max_indel=max_indel, snvs_only=snvs_only, min_bq=min_bq, min_diff=min_diff), **kw)
+
+
+def haplotag_files(bams, fasta_path, phased_vcf, bais=None, sort_output=False, **kw):
+    """haplotag_file over the alignment files of one sample (call_files' rules for the inputs and the merged output)"""
+    return haplotag_file(list(bams), fasta_path, phased_vcf, _inputs=dict(bais=bais, sort_output=sort_output), **kw)
 
 
 # ---------------- indexes: .bai on the device, .fai on the host ----------------

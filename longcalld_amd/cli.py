@@ -24,7 +24,14 @@ VALUED = {"--region-file": "region_file", "--regions-file": "region_file", "-E":
           "--window-chunks": "window_chunks", "--loader-threads": "loader_threads", "--chunk-len": "chunk_len", "--add-bam": "add_bam", "--bam-list": "bam_list", "--te-lib": "te_lib", "--sam": "out_sam", "--vcf-index": "vcf_index",
           "--mods": "mods", "--mod-code": "mod_code", "--mod-threshold": "mod_threshold", "--depth": "depth", "--depth-window": "depth_window", "--split-reads": "split_reads",
           "--haplotag-list": "haplotag_list"}
+# haplotag: what `call` takes and it does not (no VCF is written, nothing is called), and its own options
+HAPLOTAG_REFUSED = {k: "a haplotag run writes no VCF and calls no variants: %s is not one of its options" % k for k in (
+    "-o", "--out-vcf", "-O", "--out-type", "--vcf-index", "--refine-bam", "--te-lib", "--var-rnames", "--sv-rnames", "-c", "--min-cov", "-d", "--alt-cov", "-a", "--alt-ratio",
+    "-C", "--max-cov", "-l", "--min-sv-len", "-n", "--sample-name", "-H", "--no-vcf-header", "--amb-base")}
+HAPLOTAG_FLAGS = {"--tag-snvs-only"}
+HAPLOTAG_VALUED = {"--vcf-sample": "vcf_sample", "--tag-max-indel": "tag_max_indel", "--tag-min-diff": "tag_min_diff"}
 USAGE = """Usage: python -m longcalld_amd.cli call [options] ref.fa in.bam [region ...]
+       python -m longcalld_amd.cli haplotag [options] ref.fa in.bam phased.vcf[.gz] [region ...]   carry the phasing of a VCF onto the reads of any BAM (below)
        python -m longcalld_amd.cli index in.bam [out.bai]     build in.bam.bai (or out.bai) on the device
        python -m longcalld_amd.cli index [--csi] in.vcf.gz [out]   build in.vcf.gz.tbi (--csi: .csi) on the device; BAM or VCF is decided by the file's content, not its name
        python -m longcalld_amd.cli faidx ref.fa               build ref.fa.fai
@@ -62,18 +69,29 @@ Index:    --make-index   build a missing .bai of any input / ref.fa.fai where it
                          it does not index the VCF: that is --vcf-index
           --vcf-index tbi|csi   with -O z and -o FILE: write FILE.tbi / FILE.csi beside the compressed VCF (built on the device from the text being compressed)
 Run:      --window-chunks INT   --no-overlap (default) | --overlap   --loader-threads INT   --chunk-len INT
+Haplotag: every read of in.bam is compared on the device with the heterozygous phased sites (GT a|b, PS) of phased.vcf -- SNVs and indels up to --tag-max-indel --
+          and gets the haplotype most of its sites vote for; no variant is called and no VCF is written.  It takes the input, region, index and run options of
+          `call`, -M, -B (the base quality an SNV base needs to vote), and the outputs that hang on the reads' haplotypes: -b | --sam, --sort-merged, --add-bam,
+          --bam-list, --mods ..., --depth ..., --split-reads ..., --haplotag-list; at least one of them.  Its own options:
+          --vcf-sample STR [the first]   --tag-snvs-only   --tag-max-indel INT [50]   --tag-min-diff INT [1] (votes the winning haplotype must lead by)
+          Refused (exit status 2): -o, -O, --vcf-index, --refine-bam, --te-lib, --var-rnames, --sv-rnames, -n, -H, --amb-base and the calling thresholds -c -d -a -C -l
 Not supported (refused with exit status 2): -s, --refine-aln (use --refine-bam), -L (use --bam-list), -X (use --add-bam), -T (use --te-lib), -S (use --sam), -C FILE, --out-var-rnames (use --var-rnames), --out-sv-rnames (use --sv-rnames),
           --out-som-var-rnames, -m/--methylation (use --mods FILE)
 """
 
 
-def refuse(msg):
-    sys.stderr.write("longcalld_amd call: " + msg + "\n")
+def refuse(msg, cmd="call"):
+    sys.stderr.write("longcalld_amd " + cmd + ": " + msg + "\n")
     return 2
 
 
-def parse(argv):
-    """-> (dict of options, positional arguments) or an int exit status"""
+def parse(argv, haplotag=False):
+    """-> (dict of options, positional arguments) or an int exit status; haplotag: that command's options and refusals on top of `call`'s"""
+    if haplotag:
+        REFUSED, FLAGS, VALUED = dict(globals()["REFUSED"], **HAPLOTAG_REFUSED), globals()["FLAGS"] | HAPLOTAG_FLAGS, dict(globals()["VALUED"], **HAPLOTAG_VALUED)
+        refuse = lambda msg: globals()["refuse"](msg, "haplotag")
+    else:
+        REFUSED, FLAGS, VALUED, refuse = globals()["REFUSED"], globals()["FLAGS"], globals()["VALUED"], globals()["refuse"]
     o = dict(flags=set(), exclude=[], add_bam=[])
     pos, i = [], 0
     while i < len(argv):
@@ -235,14 +253,79 @@ def main_index(argv):
     return 0
 
 
+def main_haplotag(argv):
+    """haplotag [options] ref.fa in.bam phased.vcf[.gz] [region ...]: a thin parser over align.haplotag_file(s)"""
+    no = lambda msg: refuse(msg, "haplotag")
+    p = parse(argv, haplotag=True)
+    if isinstance(p, int):
+        return p
+    o, pos = p
+    if len(pos) < 3:
+        sys.stderr.write(USAGE); return 2
+    fasta, bam, vcf, regions = pos[0], pos[1], pos[2], pos[3:]
+    if "ref_idx" in o and o["ref_idx"] != fasta + ".fai":
+        return no("-r/--ref-idx: only <ref.fa>.fai next to the FASTA is supported")
+    try:
+        num = {k: int(o[k]) for k in ("min_mapq", "min_bq", "window_chunks", "loader_threads", "chunk_len", "tag_max_indel", "tag_min_diff") if k in o}
+    except ValueError as e:
+        return no(f"not a number: {e}")
+    if num.get("tag_max_indel", 50) < 1:
+        return no("--tag-max-indel must be at least 1")
+    if num.get("tag_min_diff", 1) < 1:
+        return no("--tag-min-diff must be at least 1")
+    if not 0 <= num.get("min_bq", 0) <= 254:
+        return no("-B/--min-bq must be 0 ... 254")
+    if "out_sam" in o and "out_bam" in o:
+        return no("--sam cannot be combined with -b/--out-bam: one alignment output per run")
+    for f in (mods_option, depth_option, split_option):
+        if isinstance(f(o), str):
+            return no(f(o))
+    mods, depth, split = mods_option(o), depth_option(o), split_option(o)
+    sam = "out_sam" in o
+    if not sam and "out_bam" not in o and mods is None and depth is None and split is None:
+        return no("no output: give -b, --sam, --mods, --depth, --split-reads or --haplotag-list")
+    from . import align
+    cmdline = "longcalld_amd haplotag " + " ".join(argv)
+    bam_out = dict(path=o["out_sam" if sam else "out_bam"], pg_line="@PG\tID:longcalld_amd\tPN:longcalld_amd\tCL:" + cmdline) if sam or "out_bam" in o else None
+    try:
+        bams = input_bams(o, bam)
+    except OSError as e:
+        return no(f"--bam-list: {e}")
+    if len(bams) > 64:
+        return no("more than 64 input files")
+    mode = 2 if "--all-ctg" in o["flags"] else 1 if "--autosome" in o["flags"] else 0
+    kw = dict(contig_mode=mode, exclude=o["exclude"], regions=regions, region_bed_path=o.get("region_file"), chunk_len=num.get("chunk_len", 0), window_chunks=num.get("window_chunks", 0),
+              overlap=0 if "--no-overlap" in o["flags"] else 1 if "--overlap" in o["flags"] else -1, loader_threads=num.get("loader_threads", 0), min_mapq=num.get("min_mapq", 30),
+              bam_out=bam_out, cfg=align.call_cfg(1 if "--ont" in o["flags"] else 0), index=(dict(build_missing_bai=1, build_missing_fai=1) if sam else True) if "--make-index" in o["flags"] else None,
+              sample=o.get("vcf_sample"), max_indel=num.get("tag_max_indel", 50), snvs_only="--tag-snvs-only" in o["flags"], min_bq=num.get("min_bq", 0), min_diff=num.get("tag_min_diff", 1),
+              **(dict(aln_format="sam") if sam else {}), **(dict(mods=mods) if mods is not None else {}), **(dict(depth=depth) if depth is not None else {}),
+              **(dict(split=split) if split is not None else {}))
+    try:
+        st = align.haplotag_file(bam, fasta, vcf, **kw) if len(bams) == 1 else align.haplotag_files(bams, fasta, vcf, sort_output="--sort-merged" in o["flags"], **kw)
+    except align.LcdError as e:
+        sys.stderr.write(f"longcalld_amd haplotag: {e}\n")
+        return 1
+    if st.get("index", {}).get("out_bai_skipped"):
+        sys.stderr.write("longcalld_amd haplotag: the output BAM was written without an index: " + st["index"]["out_bai_skip_reason"] + "\n")
+    if st["plan_fallback"]:
+        sys.stderr.write("longcalld_amd haplotag: no contig of the requested kind (or no valid region): the entire alignment file was processed\n")
+    t, v = st["haplotag"], st["phased_vcf"]
+    sys.stderr.write(f"longcalld_amd haplotag: {v['n_sites']} phased sites in {v['n_phase_sets']} sets ({v['n_lines'] - v['n_sites']} lines left out), {st['n_planned']} chunks, "
+                     f"{st['n_reads']} reads: {t['n_tagged'][1]} H1 + {t['n_tagged'][2]} H2 + {t['n_tagged'][0]} untagged (records counted once per chunk that holds them), "
+                     f"{st['ms_wall'] / 1000:.2f} s\n")
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv or argv[0] in ("-h", "--help"):
         sys.stdout.write(USAGE); return 0 if argv else 2
     if argv[0] in ("index", "faidx"):
         return main_index(argv)
+    if argv[0] == "haplotag":
+        return main_haplotag(argv[1:])
     if argv[0] != "call":
-        return refuse(f"unknown command {argv[0]} (the commands are: call, index, faidx)")
+        return refuse(f"unknown command {argv[0]} (the commands are: call, haplotag, index, faidx)")
     p = parse(argv[1:])
     if isinstance(p, int):
         return p

@@ -4,6 +4,8 @@
 // the appendable BAM writer).  Everything here composes exports that exist; no kernel is launched from this file.
 // lcd_call_files runs the same driver over the alignment files of one sample (-X / -L, src/call_var_main.c:361-400, 640-741): every chunk is opened from all files at once
 // (lcd_chunk_open_from_bams), file 0 gives the contigs, the headers and the sample name, every further file must carry its reference table (LCD_ERR_INPUT_HEADERS).
+// lcd_haplotag_files is the same run with another middle stage: files_run() takes the stage as a parameter (TagStage: lcd_chunk_haplotag against a phased VCF
+// instead of chunks_call_core) and writes no VCF; plan, windows, load, write and the closing order are shared.
 #include <condition_variable>
 #include <ctime>
 #include "lcd_host_internal.h"
@@ -355,8 +357,12 @@ struct Tokens {
     void halt() { std::lock_guard<std::mutex> lk(mu); stop = true; cv.notify_all(); }
 };
 
+// the middle stage of lcd_haplotag_files: the site tables of the phased VCF (contig i of the tables is contig i of the BAM header), the options, the sums
+struct TagStage { lcd_phased_vcf_t *vcf = nullptr; lcd_haplotag_opt_t opt; lcd_haplotag_stats_t sum; ~TagStage() { lcd_phased_vcf_free(vcf); } };
+
 struct Run {
     const lcd_file_job_t *job; const lcd_cfg_t *cfg; lcd_file_stats_t *st;
+    TagStage *tag = nullptr;               // NULL: a calling run
     std::vector<std::string> bams, bais; std::vector<const char *> bam_p, bai_p;     // the input files of the one sample, in input order
     std::vector<int64_t> reads_per_file;
     int is_ont = 0, device = 0, loader_threads = 1;
@@ -438,6 +444,36 @@ struct Run {
         st->n_records += w.n_records; st->ms_call += now_ms() - t0;
         return 0;
     }
+    // ---- tag (lcd_haplotag_files' middle stage): every chunk's reads against the phased sites of its contig; the answer is handed on as the chunk's K5 state.  A
+    // record that two overlapping chunks hold gets the same answer in both (it depends on the record and the table alone): no stitch, no flip, nothing carried
+    // but the region in front of the window, which the writers leave out ----
+    int tag_window(Window &w) {
+        const double t0 = now_ms();
+        w.prev.valid = carry.valid; w.prev.tid = carry.tid; w.prev.reg_beg = carry.reg_beg; w.prev.reg_end = carry.reg_end;
+        w.called = true;                                            // (the window frees the states made below)
+        for (int c = 0; c < w.n; ++c) {
+            lcd_first_chunk_t &x = w.chunks[c].first;
+            lcd_haplotag_stats_t hs;
+            lcd_haplotag_t *h = lcd_chunk_haplotag(w.handles[c], tag->vcf, w.tids[c], &tag->opt, &hs);
+            if (!h) { fail(-1, g_err); return -1; }
+            const int n = lcd_haplotag_n_reads(h);
+            x.state = (lcd_hap_state_t *)calloc(1, sizeof(lcd_hap_state_t));
+            int rc = x.state ? lcd_hap_state_init(n, 0, x.state) : set_err(-11, "lcd_haplotag_files: out of memory");
+            if (!rc) rc = lcd_haplotag_to_host(h, x.state->haps, x.state->phase_sets, nullptr, nullptr) == n ? 0 : -24;
+            lcd_haplotag_free(h);
+            if (rc) { fail(rc, g_err); return rc; }
+            x.n_reads = n;
+            int64_t *a = &tag->sum.n_records; const int64_t *b = &hs.n_records;
+            for (int k = 0; k < 14; ++k) a[k] += b[k];
+            tag->sum.ms_measure += hs.ms_measure; tag->sum.ms_mark += hs.ms_mark; tag->sum.ms_reduce += hs.ms_reduce;
+        }
+        carry.valid = 1; carry.tid = w.tids[w.n - 1]; carry.reg_beg = w.chunks[w.n - 1].first.reg_beg; carry.reg_end = w.chunks[w.n - 1].first.reg_end;
+        sample_peak();
+        std::lock_guard<std::mutex> lk(err_mu);
+        st->ms_call += now_ms() - t0;
+        return 0;
+    }
+    int middle(Window &w) { return tag ? tag_window(w) : call(w); }
     // ---- write: the text, the window's records of the alignment output; the caller frees the window ----
     int write(Window &w) {
         const double t0 = now_ms();
@@ -474,9 +510,27 @@ extern "C" int lcd_call_files_ext(const lcd_inputs_t *in, const lcd_file_job_t *
                                   const lcd_run_ext_t *ext) {
     return lcd_call_files_ext2(in, job, cfg, opt, stats, out, ext, nullptr);
 }
+static int files_run(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
+                     const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2, const lcd_haplotag_run_t *hopt);
 extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
                                    const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2) {
-    const std::string W = "lcd_call_files";
+    return files_run(in, job, cfg, opt, stats, out, ext, ext2, nullptr);
+}
+extern "C" int lcd_haplotag_files(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_haplotag_run_t *hopt, const lcd_run_opt_t *opt,
+                                  lcd_file_stats_t *stats, const lcd_run_out_t *out, const lcd_run_ext2_t *ext2) {
+    if (hopt) {
+        if (hopt->stats) memset(hopt->stats, 0, sizeof(*hopt->stats));
+        if (hopt->size >= offsetof(lcd_haplotag_run_t, vcf_stats) + sizeof(void *) && hopt->vcf_stats) memset(hopt->vcf_stats, 0, sizeof(*hopt->vcf_stats));
+    }
+    if (!hopt || hopt->size < offsetof(lcd_haplotag_run_t, vcf_path) + sizeof(char *)) return set_err(-4, "lcd_haplotag_files: NULL options, or a size that does not reach vcf_path");
+    return files_run(in, job, cfg, opt, stats, out, nullptr, ext2, hopt);
+}
+// hopt == NULL: a calling run (lcd_call_files_ext2); else lcd_haplotag_files: the middle stage is TagStage and no VCF is written
+static int files_run(const lcd_inputs_t *in, const lcd_file_job_t *job, const lcd_cfg_t *cfg, const lcd_run_opt_t *opt, lcd_file_stats_t *stats, const lcd_run_out_t *out,
+                     const lcd_run_ext_t *ext, const lcd_run_ext2_t *ext2, const lcd_haplotag_run_t *hopt) {
+    const std::string W = hopt ? "lcd_haplotag_files" : "lcd_call_files";
+    lcd_haplotag_run_t hx; memset(&hx, 0, sizeof(hx));
+    if (hopt) memcpy(&hx, hopt, std::min(hopt->size, sizeof(hx)));     // (what lies behind `size` reads as zero)
     lcd_run_ext2_t x2; lcd_mods_opt_t mods_opt;
     if (int rc = ModsSink::parse(W, ext2, &x2, &mods_opt)) return rc;
     if (int rc = DepthSink::parse(W, x2)) return rc;
@@ -495,6 +549,17 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
     lcd_index_stats_t ist_local; memset(&ist_local, 0, sizeof(ist_local));
     lcd_index_stats_t *ist = out && out->idx_stats ? out->idx_stats : &ist_local;
     if (int rc = check_aln_opt(W, opt)) return rc;
+    TagStage tag;
+    if (hopt) {
+        if (!hx.vcf_path) return set_err(-4, W + ": no phased VCF (vcf_path)");
+        if (job && job->vcf_path) return set_err(-4, W + ": a haplotag run writes no VCF (job->vcf_path)");
+        if (opt && opt->fields) return set_err(-4, W + ": a haplotag run has no VCF fields (opt->fields)");
+        if (opt && opt->aln && opt->aln->refine) return set_err(-4, W + ": a haplotag run does not refine alignments (opt->aln->refine)");
+        if (hx.max_indel < 0 || hx.min_diff < 0 || hx.min_bq < 0 || hx.min_bq > 254) return set_err(-4, W + ": max_indel / min_diff below 0 (0: the default), or min_bq outside 0 ... 254");
+        if (!(job && job->bam_out) && !x2.mods_path && !x2.depth_path && !xs.split_prefix && !xs.haplotag_path) return set_err(-4, W + ": no output requested");
+        lcd_haplotag_opt_default(&tag.opt); tag.opt.min_bq = hx.min_bq; if (hx.min_diff) tag.opt.min_diff = hx.min_diff;
+        memset(&tag.sum, 0, sizeof(tag.sum));
+    }
     if (idx && idx->write_out_bai && (!job || !job->bam_out)) return set_err(-4, W + ": write_out_bai needs bam_out");
     if (idx && idx->slab_members < 0) return set_err(-4, W + ": negative slab_members");
     const lcd_vcf_index_opt_t *vcf_idx = ext ? ext->vcf_idx : nullptr;
@@ -510,13 +575,13 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
     if (job->bam_out && !job->bam_out->path) return set_err(-4, W + ": bam_out without a path");
     const bool sam = opt && opt->aln && opt->aln->format == LCD_ALN_SAM && job->bam_out;
     if (sam && idx && idx->write_out_bai) return set_err(-4, W + ": a SAM output has no index (write_out_bai)");
-    if (sam && !strcmp(job->bam_out->path, "-") && (!job->vcf_path || !strcmp(job->vcf_path, "-"))) return set_err(-4, W + ": the SAM output and the VCF cannot both go to stdout");
+    if (!hopt && sam && !strcmp(job->bam_out->path, "-") && (!job->vcf_path || !strcmp(job->vcf_path, "-"))) return set_err(-4, W + ": the SAM output and the VCF cannot both go to stdout");
     if (job->window_chunks < 0 || job->loader_threads < 0 || job->chunk_len < 0 || job->overlap < -1 || job->overlap > 1) return set_err(-4, W + ": negative window_chunks / loader_threads / chunk_len, or overlap outside -1 ... 1");
     if (cfg->clean.out_somatic || cfg->opt.collect_ref_read_aln_str) return set_err(-2, W + ": somatic / refine mode is not supported");
     const double t_wall = now_ms();
     FieldsRun fr; fr.collect_rnames = fields_out != nullptr && job->keep_records;
     if (int rc = fr.open(fields, W)) return rc;     // (an unreadable TE file: before an index is built or an output file is created)
-    Run R; R.job = job; R.cfg = cfg; R.st = stats; R.fields = &fr;
+    Run R; R.job = job; R.cfg = cfg; R.st = stats; R.fields = &fr; R.tag = hopt ? &tag : nullptr;
     R.refine = opt && opt->aln && opt->aln->refine && job->bam_out;     // (without an alignment output the option has no effect, as in the reference)
     memset(&R.plan, 0, sizeof(R.plan)); memset(&R.carry, 0, sizeof(R.carry));
     const int n_in = in ? in->n : 1;
@@ -565,6 +630,12 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
                                                       ", the first file has " + ent(R.names, R.lens));
         }
     }
+    if (hopt) {     // the site tables: contig i of the BAM header is contig i of the tables
+        std::vector<const char *> nm; for (const std::string &s : R.names) nm.push_back(s.c_str());
+        lcd_hapvcf_opt_t vo; lcd_hapvcf_opt_default(&vo); if (hx.max_indel) vo.max_indel = hx.max_indel; vo.snvs_only = hx.snvs_only != 0;
+        tag.vcf = lcd_phased_vcf_read(hx.vcf_path, hx.sample, (int)nm.size(), nm.data(), &vo, hx.vcf_stats);
+        if (!tag.vcf) return set_err(lcd_phased_vcf_errno() ? lcd_phased_vcf_errno() : -30, W + ": " + lcd_phased_vcf_error());
+    }
     {
         std::vector<const char *> nm; for (const std::string &s : R.names) nm.push_back(s.c_str());
         const int rc = lcd_plan_chunks((int)nm.size(), nm.data(), R.lens.data(), job->contig_mode, job->n_exclude, job->exclude, job->n_regions, job->regions, job->region_bed_path,
@@ -589,7 +660,7 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
     // the outputs: the header names every contig of the BAM header, in header order (src/vcf_utils.c:46-49)
     {
         char *hdr = nullptr, *sm = nullptr;
-        if (!job->no_vcf_header) {
+        if (!hopt && !job->no_vcf_header) {
             if (!job->sample_name && lcd_bam_sample_name(bam0, &sm)) return -30;
             std::string joined;     // src/call_var_main.c:733-735: without an SM, the input paths
             for (int f = 0; f < n_in; ++f) joined += (f ? "," : "") + R.bams[f];
@@ -601,9 +672,9 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
         }
         lcd_vcf_index_opt_t vio; memset(&vio, 0, sizeof(vio));
         if (vcf_idx) { vio = *vcf_idx; vio.stats = ext->vcf_idx_stats; }
-        R.vcf = lcd_vcf_writer_open_idx(job->vcf_path, job->vcf_bgzf, hdr, vcf_idx ? &vio : nullptr);
+        if (!hopt) R.vcf = lcd_vcf_writer_open_idx(job->vcf_path, job->vcf_bgzf, hdr, vcf_idx ? &vio : nullptr);
         free(hdr); free(sm);
-        if (!R.vcf) { lcd_file_stats_free(stats); return -30; }
+        if (!hopt && !R.vcf) { lcd_file_stats_free(stats); return -30; }
         if (job->bam_out) {
             lcd_writer_opt_t wo; memset(&wo, 0, sizeof(wo));
             wo.format = sam ? LCD_ALN_SAM : LCD_ALN_BAM; wo.sort_output = in ? in->sort_output : 0;
@@ -629,7 +700,7 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
     if (!overlap) {
         for (int k = 0; k < n_windows && !R.failed; ++k) {
             std::unique_ptr<Window> w = make(k);
-            if (R.load(*w) || R.call(*w) || R.write(*w)) break;
+            if (R.load(*w) || R.middle(*w) || R.write(*w)) break;
         }
     } else {
         Slot loaded, called; Tokens alive(3);
@@ -655,7 +726,7 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
         for (;;) {      // the call stage runs on the calling thread
             std::unique_ptr<Window> w = loaded.pop();
             if (!w) break;
-            if (R.failed || R.call(*w)) { w.reset(); alive.give(); break; }
+            if (R.failed || R.middle(*w)) { w.reset(); alive.give(); break; }
             if (!called.push(std::move(w))) { alive.give(); break; }
         }
         if (R.failed) { alive.halt(); loaded.abort(); }     // (the loader may be waiting for a token or for the slot)
@@ -669,7 +740,7 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
         rc = R.err_code;
     } else {
         if (R.bam) rc = lcd_bam_writer_close(R.bam);
-        const int rc2 = lcd_vcf_writer_close(R.vcf);
+        const int rc2 = R.vcf ? lcd_vcf_writer_close(R.vcf) : 0;
         if (!rc) rc = rc2;
         if (rc) R.err_msg = g_err;
     }
@@ -681,6 +752,7 @@ extern "C" int lcd_call_files_ext2(const lcd_inputs_t *in, const lcd_file_job_t 
         stats->records = dup_vec(R.kept); stats->n_kept_records = (int)R.kept.size();
     }
     if (!rc) fr.give(fields_out);
+    if (!rc && hopt && hx.stats) *hx.stats = tag.sum;
     stats->peak_device_bytes = R.peak.load();
     if (n_reads_per_file) for (int f = 0; f < n_in; ++f) n_reads_per_file[f] = R.reads_per_file[f];
     stats->ms_wall = now_ms() - t_wall;

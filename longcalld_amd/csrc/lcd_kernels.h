@@ -55,6 +55,12 @@ void lcd_launch_depth_scan(DepthPart *parts, long long n_tiles, int *n_rows, hip
 void lcd_launch_split_measure(const SplitIn &in, SplitRow *rows, hipStream_t st);
 void lcd_launch_split_emit(const SplitIn &in, const SplitRow *rows, uint8_t *fq0, uint8_t *fq1, uint8_t *fq2, uint8_t *list, hipStream_t st);
 void lcd_launch_depth_rows(const DepthIn &in, const DepthPart *parts, DepthRow *rows, int cap, hipStream_t st);     // cap: the entries of rows (*n_rows of the scan)
+// haplotag_kernel.hip: measure (span, candidate range; one wavefront per record), scan (the exclusive prefix of the candidate counts; one wavefront), mark (every
+// operation's bits into the pair bytes), reduce (verdict bytes, votes per phase set, the read's haplotype); in.bits must be zeroed between scan and mark
+void lcd_launch_htag_measure(const HtagIn &in, hipStream_t st);
+void lcd_launch_htag_scan(const HtagIn &in, hipStream_t st);
+void lcd_launch_htag_mark(const HtagIn &in, hipStream_t st);
+void lcd_launch_htag_reduce(const HtagIn &in, hipStream_t st);
 // bai_kernel.hip: a batch of walked records -> index entries (prep: the stat kernel's jobs and the batch's contig range; entry: offsets, bins, order test, windows,
 // counters; compact: scan of the workgroups' run heads + the dense chunk list)
 void lcd_launch_bai_prep(const BaiJob &j, hipStream_t st);

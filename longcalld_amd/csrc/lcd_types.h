@@ -313,6 +313,26 @@ struct DepthIn { const DepthJob *jobs; int *diff; unsigned long long *stats; lon
 // a tile's partial: the three plane sums and the number of run heads; after the scan: the sums of the tiles in front of it
 struct DepthPart { int s[3], heads; };
 struct DepthRow { long long beg; unsigned d[3], pad; };
+// ---------------- haplotag: the kept records against a contig's phased sites (haplotag_kernel.hip) ----------------
+// one kept record ([src, src + len): its block_size word and body; cap: the l_seq the loader took from it) of read `read`
+struct HtagJob { uint64_t src; uint32_t len, cap; int read, pad; };
+// what the measure pass leaves per record: its span [beg, end] (empty: end < beg), the operation words it is read with (its own or its CG field's), its first
+// candidate site and their number, l_seq and where the packed bases begin; bad: broken layout (no candidates)
+struct HtagRec { long long beg, end, lo; unsigned long long ops; unsigned n_ops, n_cand; int lseq; unsigned seq_off; int bad, pad; };
+// a contig's table in HBM: meta = kind | hap_of_alt << 2 | ref_code << 4 | alt_code << 8
+struct HtagSites { const long long *pos, *ins_off, *ps_value; const int *len, *ps_idx; const unsigned *meta; const uint8_t *pool; long long n_sites, pool_size; int max_fp, n_ps; };
+// bits of a pair byte (mark pass, four bytes to a word) and the verdict bytes (reduce pass)
+#define LCD_HTAG_DIST 1u
+#define LCD_HTAG_ALTM 2u
+#define LCD_HTAG_B_ALT 4u
+#define LCD_HTAG_B_REF 8u
+#define LCD_HTAG_B_OTHER 16u
+#define LCD_HTAG_B_LOWQ 32u
+enum { LCD_HTAG_NONE = 0, LCD_HTAG_REF = 1, LCD_HTAG_ALT = 2, LCD_HTAG_OTHER = 3, LCD_HTAG_LOWQ = 4, LCD_HTAG_NO_PAIR = 255 };
+// cand_off: n_jobs + 1 entries (the scan's); bits: (total + 3) / 4 words, zeroed; verdict: one byte per candidate; haps / ps / n1 / n2: per read; stats:
+// fourteen counters in the order of lcd_haplotag_stats_t
+struct HtagIn { const HtagJob *jobs; HtagRec *recs; unsigned long long *cand_off; unsigned *bits; uint8_t *verdict; int *haps; long long *ps; int *n1, *n2;
+                unsigned long long *stats; HtagSites t; int n_jobs, min_bq, min_diff, pad; };
 // ---------------- the per-haplotype read sets (split_kernel.hip) ----------------
 // one record the plan names ([src, src + len): its block_size word and body, len >= 36) with its read's haplotype 0 / 1 / 2 and phase set (0 and 0 for a record
 // the loader filtered)
